@@ -14,12 +14,17 @@ blocks are fed every step (the codec state advances, the data repeats - throughp
 value = channel-samples that went through the step per second (Msamples/s; a sample counts once, whichever legs the step has),
 whole job over all ranks.
 
-Prints ONE JSON line (contract in the task statement) with `roofline` (the dominant kernel priced live from hipEvents on
-its launch stream, plus the whole encode / decode legs against the same algorithmic bytes) and, at N=1, `cpu_baseline`
-(the C oracle timed on the host cores on a bounded sample of the same workload).
-The K timed steps run without the library's per-kernel hipEvents (22 marker packets per encode call, 3 per decode: 0.09 ms
-per step; ULCX_BENCH_TIMING=1 keeps them in); the per-kernel times and the roofline's kernel_ms come from three more steps
-of the same workload run straight after the timed region with the events on.
+Prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the
+headline (metric, value, unit, higher_is_better, dtype, ms_per_step, config); when the step decodes, the blocks of the last
+timed step are checked to decode within the bits written.  --full adds what takes work of its own: `roofline` (the dominant
+kernel priced live from hipEvents on its launch stream, plus the whole encode / decode legs against the same algorithmic
+bytes), `whole_pipeline`, `kernels_ms`, at N=1 `cpu_baseline` (the C oracle timed on the host cores on a bounded sample of
+the same workload, unless --no-cpu) and, on the headline's shape of run, `secondary` (unless --no-secondary).
+The timed steps run without the library's per-kernel hipEvents (22 marker packets per encode call, 3 per decode: 0.09 ms
+per step; ULCX_BENCH_TIMING=1 keeps them in); under --full the per-kernel times and the roofline's kernel_ms come from three
+more steps of the same workload run straight after the timed region with the events on.
+--dump-outputs DIR writes what the last timed step handed its caller (dump_outputs below) as float32 .npy files; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -205,6 +210,49 @@ def run_secondary(torch, ulc_amd, dev, name, B, K, steps=3):
     return res
 
 
+DUMP_BUDGET = 64 << 20          # bytes, all files of --dump-outputs together
+DUMP_STREAMS = 32               # streams in the sample of the large outputs
+DUMP_SEED = 20250917
+
+
+def dump_outputs(torch, np, out_dir, legs, B, K, bs, slot, d_out, d_bits, d_dec, d_dbits):
+    """--dump-outputs: the arrays the last timed step handed its caller, as float32 .npy files (every value is exact in
+    float32: bytes, bit counts below 2^24, f32 or int16 samples).
+      encoded_bits [B][K], decoded_bits [B][K]   bits of every block of every stream (of a fixed seeded sample of the
+                                                 streams, as below, if they alone would take more than a quarter of the budget)
+      encoded_bytes [S][Kd][slot]                the encoded blocks of a fixed seeded sample of S streams, zero past each
+                                                 block's last byte (what lies there is not output)
+      decoded_pcm / decoded_pcm16 [S][Kd*bs][2]  the decoded samples of the same streams (PCM16 variant: the int16 values)
+    Kd = K, or the last Kd blocks when S streams of K blocks would not fit in DUMP_BUDGET."""
+    dev = d_bits.device
+    os.makedirs(out_dir, exist_ok=True)
+    per_block = (slot * 4 if "encode" in legs else 0) + (bs * CH * 4 if "decode" in legs else 0)
+    sizes_bytes = B * K * 4 * len(legs)
+    S = min(B, DUMP_STREAMS)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, S, replace=False))
+    idx_t = torch.as_tensor(idx, device=dev)
+    all_sizes = sizes_bytes <= DUMP_BUDGET // 4
+    room = DUMP_BUDGET - (sizes_bytes if all_sizes else S * K * 4 * len(legs))
+    Kd = max(1, min(K, room // (S * per_block)))
+    arrays = {}
+
+    def sizes(d):
+        b = d.view(B, K)
+        return b if all_sizes else b.index_select(0, idx_t)
+
+    if "encode" in legs:
+        arrays["encoded_bits"] = sizes(d_bits)
+        blk = d_out.view(B, K, slot).index_select(0, idx_t)[:, K - Kd:]
+        nbytes = (d_bits.view(B, K).index_select(0, idx_t)[:, K - Kd:] + 7) // 8
+        arrays["encoded_bytes"] = torch.where(torch.arange(slot, device=dev) < nbytes[..., None], blk, torch.zeros_like(blk))
+    if "decode" in legs:
+        arrays["decoded_bits"] = sizes(d_dbits)
+        pcm = d_dec.view(B, K, bs, CH).index_select(0, idx_t)[:, K - Kd:].reshape(S, Kd * bs, CH)
+        arrays["decoded_pcm16" if d_dec.dtype == torch.int16 else "decoded_pcm"] = pcm
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.to(torch.float32).cpu().numpy())
+
+
 def self_launch(n):
     """Start n ranks of this script (one per GPU) and wait for them.  The launcher process initialises no GPU runtime (a
     process that has must not be replaced or forked); rank r gets LOCAL_RANK = r and talks to the others over 127.0.0.1."""
@@ -256,8 +304,12 @@ def main():
     ap.add_argument("--blocks", type=int, default=0, help="consecutive blocks per stream per step (default: the config's: 32 for vbr50, 16 otherwise)")
     ap.add_argument("--total-streams", type=int, default=0, help="fixed-total (strong-scaling) configurations: the total split over the GPUs "
                     "(default: the config's: 32768 / 16384); a reduced total is a test run, never a result line for BASELINE's configuration")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of the other two configurations that the default "
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: per-kernel times, roofline, "
+                    "cpu_baseline, secondary (each outside the timed region)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy "
+                    "(float32, at most 64 MB in all; rank 0's)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short runs of the other two configurations that the "
                     "1-GPU headline run appends as `secondary` (outside the timed region)")
     ap.add_argument("--pmc-summary", default="", help="tools/pmc_summary.py output of a rocprofv3 --pmc run of THIS command: fills roofline.traffic "
                     "(default: the committed profiles/r06_pmc_summary.json when its _meta.src_rev equals the library's ulcx_build_rev() "
@@ -360,7 +412,7 @@ def main():
     if args.mode == "decode":
         do_encode()                                              # the blocks the decode leg reads: produced once, untimed
     # the library's per-kernel hipEvents are marker packets between kernels: off for the timed region (a caller that wants
-    # throughput does not record them), on again for the per-kernel breakdown below; ULCX_BENCH_TIMING=1 keeps them on
+    # throughput does not record them), on again for the per-kernel breakdown of --full; ULCX_BENCH_TIMING=1 keeps them on
     keep_ev = bool(os.environ.get("ULCX_BENCH_TIMING"))
     enc.set_timing(keep_ev); dec.set_timing(keep_ev)
     for _ in range(args.warmup):
@@ -371,33 +423,65 @@ def main():
         step()
     barrier()
     el_rank = time.perf_counter() - t0
-    enc.set_timing(True); dec.set_timing(True)
-    # per-kernel device times of a few more (untimed) steps, from the library's own hipEvents on the launch stream
+    if args.dump_outputs and rank == 0:                          # before anything below runs the codec again
+        dump_outputs(torch, np, args.dump_outputs, legs, B, K, bs, slot, d_out, d_bits, d_dec16 if args.pcm16 else d_dec, d_dbits)
     acc_enc, acc_dec, nacc = {}, {}, 3
-    for _ in range(nacc):
-        step(); torch.cuda.synchronize(dev)
-        if "encode" in legs:
-            for k_, v in enc.stage_ms().items(): acc_enc[k_] = acc_enc.get(k_, 0.0) + v / nacc
-        if "decode" in legs:
-            for k_, v in dec.stage_ms().items(): acc_dec[k_] = acc_dec.get(k_, 0.0) + v / nacc
+    if args.full:
+        enc.set_timing(True); dec.set_timing(True)
+        # per-kernel device times of a few more (untimed) steps, from the library's own hipEvents on the launch stream
+        for _ in range(nacc):
+            step(); torch.cuda.synchronize(dev)
+            if "encode" in legs:
+                for k_, v in enc.stage_ms().items(): acc_enc[k_] = acc_enc.get(k_, 0.0) + v / nacc
+            if "decode" in legs:
+                for k_, v in dec.stage_ms().items(): acc_dec[k_] = acc_dec.get(k_, 0.0) + v / nacc
     el = shard.max_over_ranks(el_rank, dist, None if share else dev)
     per_rank_ms = [el_rank / args.steps * 1e3]
     if dist is not None:
         got = [None] * world
         dist.all_gather_object(got, el_rank / args.steps * 1e3)
         per_rank_ms = got
-    if args.mode == "encode":
+    if args.mode == "encode" and args.full:
         do_decode(); torch.cuda.synchronize(dev)                 # the check below wants a decode of the last encode either way
-    bits_host = d_bits.cpu().numpy()
-    dbits_host = d_dbits.cpu().numpy()
-    ok = bool((dbits_host > 0).all() and (dbits_host <= bits_host).all())
-    assert ok, "decode of the encoded blocks failed: some block was rejected or consumed more bits than were written"
+    ok = None
+    if "decode" in legs or args.full:
+        bits_host = d_bits.cpu().numpy()
+        dbits_host = d_dbits.cpu().numpy()
+        ok = bool((dbits_host > 0).all() and (dbits_host <= bits_host).all())
+        assert ok, "decode of the encoded blocks failed: some block was rejected or consumed more bits than were written"
     units = B * K * bs * CH                                      # channel-samples through the step (each goes through every leg of it), this rank
     if strong:
         total_units = total_streams * K * bs * CH
         value = total_units * args.steps / el / 1e6
     else:
         value = shard.whole_job_throughput(units * args.steps, world, el) / 1e6
+
+    lib_rev = ulc_amd.build_rev()
+    line = None
+    if rank == 0:
+        what = {"both": "encode+decode", "encode": "encode", "decode": "decode"}[args.mode]
+        rc = "VBR -%g" % cfg["p0"] if cfg["mode"] == "vbr" else "CBR %g kbps" % cfg["p0"]
+        wl = (f"{args.config} ({cfg['ref']}): Batch={B} independent {rate / 1000:g} kHz stereo streams/GPU x {K} blocks, BlockSize={bs}, {rc}; "
+              f"step = {' then '.join(legs)}" + (f"; {total_streams} streams in total over {world} GPU(s)" if strong else "")
+              + (" -- PCM16 ingest/output variant (int16 samples in HBM, not the C API's f32)" if args.pcm16 else ""))
+        line = {
+            "metric": f"{what} Msamples/s at BlockSize={bs} stereo (channel-samples through {what}, {rc}, {K} blocks per stream per call)",
+            "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic" + (" (TEST RUN: ranks share one GPU, gloo control plane - not a result)" if share else "")
+                    + (f" (TEST RUN: {total_streams} streams in total instead of the configuration's {cfg['total']} - not a result)" if strong and total_streams != cfg["total"] else ""),
+            "config": {"workload": wl, "config": args.config, "mode": args.mode,
+                       "streams_per_gpu": B, "blocks_per_stream_per_step": K, "block_size": bs, "channels": CH, "rate_hz": rate,
+                       "parallelism": f"batch split over {world} GPU(s), no collective on the data path",
+                       "per_rank_ms_per_step": [round(float(x), 4) for x in per_rank_ms]},
+            "library_src_rev": lib_rev,
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline (algorithmic bytes: SURVEY.md §8d / BASELINE.md §4)
     mean_bytes = float(bits_host.mean()) / 8.0
@@ -423,7 +507,6 @@ def main():
     # counter summary of the SAME command (tools/pmc_summary.py over separate FETCH_SIZE / WRITE_SIZE passes): the one handed in
     # with --pmc-summary, else the committed profiles/r06_pmc_summary.json (or r05's) - and that one ONLY when it was taken on exactly the
     # sources this library is built from (`_meta.src_rev` == ulcx_build_rev()) and on this workload.  Anything else: null.
-    lib_rev = ulc_amd.build_rev()
     cands = [args.pmc_summary] if args.pmc_summary else [os.path.join(ROOT, "profiles", f) for f in ("r06_pmc_summary.json", "r05_pmc_summary.json")]
     for pmc_path in cands:
         if not (pmc_path and os.path.exists(pmc_path)):
@@ -467,22 +550,7 @@ def main():
                 secondary[nm] = {"error": repr(e)}
 
     if rank == 0:
-        what = {"both": "encode+decode", "encode": "encode", "decode": "decode"}[args.mode]
-        rc = "VBR -%g" % cfg["p0"] if cfg["mode"] == "vbr" else "CBR %g kbps" % cfg["p0"]
-        wl = (f"{args.config} ({cfg['ref']}): Batch={B} independent {rate / 1000:g} kHz stereo streams/GPU x {K} blocks, BlockSize={bs}, {rc}; "
-              f"step = {' then '.join(legs)}" + (f"; {total_streams} streams in total over {world} GPU(s)" if strong else "")
-              + (" -- PCM16 ingest/output variant (int16 samples in HBM, not the C API's f32)" if args.pcm16 else ""))
-        line = {
-            "metric": f"{what} Msamples/s at BlockSize={bs} stereo (channel-samples through {what}, {rc}, {K} blocks per stream per call)",
-            "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic" + (" (TEST RUN: ranks share one GPU, gloo control plane - not a result)" if share else "")
-                    + (f" (TEST RUN: {total_streams} streams in total instead of the configuration's {cfg['total']} - not a result)" if strong and total_streams != cfg["total"] else ""),
-            "config": {"workload": wl, "config": args.config, "mode": args.mode,
-                       "streams_per_gpu": B, "blocks_per_stream_per_step": K, "block_size": bs, "channels": CH, "rate_hz": rate,
-                       "parallelism": f"batch split over {world} GPU(s), no collective on the data path",
-                       "per_rank_ms_per_step": [round(float(x), 4) for x in per_rank_ms]},
-            "library_src_rev": lib_rev,
+        line.update({
             "roofline": {"bound": "hbm", "kernel": f"{kname} ({side})", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "algorithmic_bytes_per_block": alg_bytes_block, "blocks_per_launch": B * K / launches,
@@ -496,7 +564,7 @@ def main():
                                "decode_Msamples_s": B * K * bs * CH / (dec_total * 1e-3) / 1e6 if dec_total else None,
                                "mean_block_bytes": mean_bytes, "decode_ok": ok},
             "kernels_ms": {**{f"enc.{k_}": round(v, 4) for k_, v in acc_enc.items()}, **{f"dec.{k_}": round(v, 4) for k_, v in acc_dec.items()}},
-        }
+        })
         if secondary is not None:
             line["secondary"] = secondary
         if cpu is not None:

@@ -41,7 +41,7 @@ def test_launcher_and_world_size_must_agree():
 
 @pytest.mark.gpu
 def test_two_ranks_share_the_gpu_box():
-    r = _run(["--gpus", "2", "--streams", "64", "--blocks", "4", "--steps", "2", "--warmup", "1", "--no-cpu"],
+    r = _run(["--gpus", "2", "--streams", "64", "--blocks", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
              env={"ULCX_BENCH_SHARE_GPU": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -66,7 +66,7 @@ def _one_line(r):
 def test_eight_ranks_share_the_gpu_box_weak_scaling():
     """World size 8 (the node the 1 -> 8 curve will be measured on) on the 1-GPU box: rendezvous of 8 ranks, 8 entries of
     per_rank_ms_per_step, MAX over ranks, whole-job value = 8 ranks' streams.  Eight small encoders share the device."""
-    r = _run(["--gpus", "8", "--streams", "64", "--blocks", "4", "--steps", "2", "--warmup", "1", "--no-cpu"],
+    r = _run(["--gpus", "8", "--streams", "64", "--blocks", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
              env={"ULCX_BENCH_SHARE_GPU": "1"}, timeout=900)
     d = _one_line(r)
     assert d["n_gpus"] == 8 and d["scaling"] == "weak" and len(d["config"]["per_rank_ms_per_step"]) == 8
@@ -80,7 +80,7 @@ def test_eight_ranks_share_the_gpu_box_weak_scaling():
 def test_eight_ranks_strong_scaling_split_of_the_fixed_total_configurations(config, bs):
     """configs[3] / configs[4] are fixed totals split over the GPUs (shard.stream_range): 8 ranks, an uneven total (516 =
     4 x 65 + 4 x 64 streams), value = the TOTAL's samples over the slowest rank's time."""
-    r = _run(["--gpus", "8", "--config", config, "--total-streams", "516", "--blocks", "4", "--steps", "2", "--warmup", "1", "--no-cpu"],
+    r = _run(["--gpus", "8", "--config", config, "--total-streams", "516", "--blocks", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"],
              env={"ULCX_BENCH_SHARE_GPU": "1"}, timeout=900)
     d = _one_line(r)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and len(d["config"]["per_rank_ms_per_step"]) == 8
@@ -96,7 +96,7 @@ def test_two_gpus_over_rccl():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("fewer than two GPUs visible")
-    r = _run(["--gpus", "2", "--streams", "256", "--blocks", "4", "--steps", "3", "--warmup", "1", "--no-cpu"], timeout=900)
+    r = _run(["--gpus", "2", "--streams", "256", "--blocks", "4", "--steps", "3", "--warmup", "1", "--full", "--no-cpu"], timeout=900)
     d = _one_line(r)
     assert d["n_gpus"] == 2 and len(d["config"]["per_rank_ms_per_step"]) == 2 and "TEST RUN" not in d["data"]
     assert d["whole_pipeline"]["decode_ok"] is True

@@ -1,14 +1,14 @@
 """Pins the oracle's restatement of the three reference sources that compile on
 their own (WindowControl, Psyopt, NoiseFill) to the REAL reference objects in
 oracle/_ref/libulc_ref_partial.so — bit-exact, same inputs, same state threading.
-Skipped only when neither /root/reference nor a prebuilt oracle/_ref exists."""
+Skipped only when build() left no oracle/_ref (no reference tree to compile it from)."""
 import ctypes as C
 import numpy as np
 import pytest
 from ulc_testlib import oracle, ref_partial, synth_pcm, ptr, f32p, i32p
 
 REF = ref_partial()
-needs_ref = pytest.mark.skipif(REF is None, reason="oracle/_ref not built and /root/reference absent")
+needs_ref = pytest.mark.skipif(REF is None, reason="oracle/_ref not built: build() found no reference tree to compile it from")
 
 
 def _chan_major_ms(pcm, bs, k):

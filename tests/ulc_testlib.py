@@ -69,13 +69,11 @@ def oracle():
 
 
 def ref_partial():
-    """The real reference's WindowControl/Psyopt/NoiseFill objects (oracle/_ref), or None."""
+    """The real reference's WindowControl/Psyopt/NoiseFill objects (oracle/_ref, built by build() where the reference tree
+    is present), or None."""
     so = os.path.join(ORACLE_DIR, "_ref", "libulc_ref_partial.so")
     if not os.path.exists(so):
-        if os.path.isdir("/root/reference/libulc"):
-            subprocess.check_call(["make", "-C", ORACLE_DIR, "ref"], stdout=subprocess.DEVNULL)
-        else:
-            return None
+        return None
     lib = C.CDLL(so)
     lib.ULCi_GetNoiseQ.argtypes = [f32p, C.c_int, C.c_int, C.c_float]
     lib.ULCi_GetHFExtParams.argtypes = [f32p, C.c_int, C.c_int, C.c_float, i32p, i32p]

@@ -11,5 +11,5 @@ if [ "${AB_TESTS:-1}" != 0 ]; then
   for f in ab/*.so; do echo "== $(basename $f) tests: $(ULC_AMD_LIB=$PWD/$f timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q 2>&1 | tail -1)"; done
 fi
 for r in 1 2; do for f in ab/*.so; do
-  ULC_AMD_LIB=$PWD/$f timeout 300 python bench.py --steps 10 --warmup 2 --no-cpu $AB_ARGS 2>/dev/null | python -c "$show" "$(basename $f .so)"
+  ULC_AMD_LIB=$PWD/$f timeout 300 python bench.py --full --steps 10 --warmup 2 --no-cpu $AB_ARGS 2>/dev/null | python -c "$show" "$(basename $f .so)"
 done; done
