@@ -43,15 +43,11 @@ def test_imdct_overlap_add_matches_formula(N, Ov):
     assert np.abs(out - expect).max() <= TOL * np.abs(expect).max()
 
 
-def test_tdac_perfect_reconstruction_through_window_switch():
-    """MDCT -> IMDCT through the oracle's own lapping, sizes and overlaps changing like a
-    window-switched block sequence: reconstruction error at float rounding level."""
+def test_tdac_perfect_reconstruction_equal_size_blocks():
+    """MDCT -> IMDCT through the oracle's own lapping, runs of equal-size blocks at full, quarter and 32-sample overlap:
+    reconstruction error at float rounding level.  Window-switched sequences: tests/test_transform_referee.py."""
     lib = oracle()
     rng = np.random.default_rng(5)
-    seq = [(2048, 2048), (2048, 128), (256, 128), (256, 256), (512, 256), (1024, 512), (2048, 1024), (2048, 2048)]
-    # forward: each entry (N, Ov_right); left overlap = previous right overlap
-    x = rng.normal(0, 0.3, sum(n for n, _ in seq) + 4096).astype(np.float32)
-    # drive the reference-style FIFO by hand is the encoder's job; here use equal-size runs only
     for N in (256, 2048):
         for Ov in (N, N // 4, 32):
             nblk = 6

@@ -281,3 +281,44 @@ def synth_block_stream(seed, n_blocks, n_chan, block_size, slot, spec_only=False
         a = np.array(nyb, np.uint8)
         out[b, :len(a) // 2] = a[0::2] | (a[1::2] << 4)
     return out, nbits
+
+
+def spec_stream(headers, n_chan, block_size, seed, silent_blocks=()):
+    """Hand-assembled blocks with the given header sequence (WindowCtrl words: first nybble in bits 0-3, for a decimated
+    block the second in bits 4-7), dense known coefficients and only codes FormatSpecs.md allocates: each unit is a
+    quantizer nybble X (2^-(5+X)) and coefficients +-2..+-7, one unit in four cut short by the stop code Fh,Eh,Fh; the units
+    of `silent_blocks` are all Eh,Fh.  No noise codes, so the dequantised coefficients are known exactly.
+    -> (blocks uint8 [K][slot], coefficients float32 [K][n_chan*block_size], sub-block sizes per block)."""
+    from spec_decoder import _WINDOWS
+    rng = np.random.default_rng(seed)
+    K = len(headers)
+    coefs = np.zeros((K, n_chan * block_size), np.float32)
+    rows, subs_all = [], []
+    mag = np.array([2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 14], np.int64)
+    for b, wc in enumerate(headers):
+        wc = int(wc)
+        nyb = [np.array([wc & 15] + ([wc >> 4 & 15] if wc & 8 else []), np.int64)]
+        subs = [block_size // d for d in _WINDOWS[wc >> 4 & 15]] if wc & 8 else [block_size]
+        subs_all.append(subs)
+        off = 0
+        for ch in range(n_chan):
+            for S in subs:
+                if b in silent_blocks:
+                    nyb.append(np.array([0xE, 0xF], np.int64))
+                else:
+                    q = int(rng.integers(0, 4))
+                    m = S if rng.random() < 0.75 else int(rng.integers(1, S))
+                    v = rng.choice(mag, m)
+                    s = np.where(v >= 8, v - 16, v)
+                    coefs[b, off:off + m] = (s * np.abs(s)).astype(np.float32) * np.float32(2.0 ** -(5 + q))
+                    nyb.append(np.concatenate([[q], v, [0xF, 0xE, 0xF] if m < S else []]).astype(np.int64))
+                off += S
+        a = np.concatenate(nyb)
+        if a.size & 1:
+            a = np.append(a, 0)
+        rows.append((a[0::2] | (a[1::2] << 4)).astype(np.uint8))
+    slot = max(r.size for r in rows) + 8
+    out = np.zeros((K, slot), np.uint8)
+    for b, r in enumerate(rows):
+        out[b, :r.size] = r
+    return out, coefs, subs_all

@@ -152,17 +152,19 @@ class BatchEncoder:
                                            stream or None), "ulcx_encode_dev_pcm16")
         self.lastK = n_blocks
 
-    def debug_fetch(self, K=None):
+    def debug_fetch(self, K=None, parts=("coef", "noise", "keys", "keep", "nout")):
+        """The taps of the last call; `parts` names the ones to fetch (the others are not copied and come back as None)."""
         K = K or self.lastK
         n = self.C * self.BS
-        coef = np.zeros((self.B, K, n), np.float32)
-        noise = np.zeros((self.B, K, n), np.float32)
-        keys = np.zeros((self.B, K, n), np.float32)
-        keep = np.zeros((self.B, K, n), np.uint8)
-        nout = np.zeros((self.B, K), np.int32)
-        _check(lib().ulcx_encoder_debug_fetch(self.h, K, _p(coef, _f32p), _p(noise, _f32p), _p(keys, _f32p),
-                                              _p(keep, _u8p), _p(nout, _i32p)), "ulcx_encoder_debug_fetch")
-        return dict(coef=coef, noise=noise, keys=keys, keep=keep, nout=nout)
+        shapes = dict(coef=((self.B, K, n), np.float32), noise=((self.B, K, n), np.float32), keys=((self.B, K, n), np.float32),
+                      keep=((self.B, K, n), np.uint8), nout=((self.B, K), np.int32))
+        unknown = set(parts) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown taps: {sorted(unknown)}")
+        r = {k: (np.zeros(*shapes[k]) if k in parts else None) for k in shapes}
+        _check(lib().ulcx_encoder_debug_fetch(self.h, K, _p(r["coef"], _f32p), _p(r["noise"], _f32p), _p(r["keys"], _f32p),
+                                              _p(r["keep"], _u8p), _p(r["nout"], _i32p)), "ulcx_encoder_debug_fetch")
+        return r
 
     def last_fallbacks(self):
         return lib().ulcx_encoder_last_fallbacks(self.h)
