@@ -13,13 +13,14 @@
  *   the image lacks):
  *       orc_get_window_ctrl, orc_calc_psychoacoustics,
  *       orc_calc_noise_log_spectrum, orc_get_noise_q, orc_get_hfext_params
- *   PARITY UNPINNED: everything that includes "Fourier.h" in the reference
- *   (ulcEncoder.c, ulcEncoder_BlockTransform.c, ulcEncoder_Encode.c,
- *   ulcDecoder.c) cannot be built here without writing a stand-in for the
- *   absent libfourier header, and the reference ships no tests or golden
- *   vectors.  Those parts are restated from the source text and checked against
- *   FormatSpecs.md (normative bitstream + IMDCT definition) and by
- *   encode->decode round trips only.
+ *   PINNED as well, against all seven reference sources compiled in place over
+ *   the project's standin/Fourier.h (oracle/_ref/libulc_ref_full.so, driven by
+ *   oracle/_ref/ulc_ref_driver; tests/test_oracle_fullref.py): the rate-control
+ *   drivers, block transform bookkeeping, sort, bitstream writer, rate search
+ *   and the decoder.
+ *   PARITY UNPINNED: the transforms (orc_fourier.c).  libfourier is absent and
+ *   its operation order unknown; the stand-in forwards to this file, so both
+ *   sides of the full-build comparison use the project's fourier spec v2.
  */
 #ifndef ULC_ORACLE_H
 #define ULC_ORACLE_H

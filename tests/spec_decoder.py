@@ -31,10 +31,15 @@ def _nybbles(block_bytes):
     return out
 
 
-def decode_block_coefficients(block_bytes, n_chan, block_size):
+def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None):
     """-> (coef [n_chan][block_size] float32, noise_run [n_chan][block_size] int32, nybbles_consumed).
     noise_run is 0 for coded/zero coefficients and the 1-based index of the noise code (run or tail) that produced the
-    coefficient otherwise; noise entries of `coef` hold the magnitude."""
+    coefficient otherwise; noise entries of `coef` hold the magnitude.  `kinds`, when a dict, counts the codes read by kind:
+    zero_run (0h), long_zero_run (1h), noise_run (8h), tail (Fh,Fh), quantizer (Fh,0h..Dh after the opening one),
+    ext_quantizer (Fh,Eh,0h..Ch, opening one included), stop (Fh,Eh,Fh), coefficient."""
+    def tally(k):
+        if kinds is not None:
+            kinds[k] = kinds.get(k, 0) + 1
     ny = _nybbles(block_bytes)
     pos = 0
 
@@ -66,17 +71,22 @@ def decode_block_coefficients(block_bytes, n_chan, block_size):
             quant = None
             done = False
             while n < S and not done:
+                opening = pending_escape
                 v = 0xF if pending_escape else get()
                 pending_escape = False
                 if v == 0xF:
                     x = get()
                     if x <= 0xD:
                         quant = f32(2.0) ** f32(-(5 + x))
+                        if not opening:
+                            tally("quantizer")
                     elif x == 0xE:
                         y = get()
                         if y <= 0xC:
                             quant = f32(2.0) ** f32(-(5 + 14 + y))
+                            tally("ext_quantizer")
                         elif y == 0xF:
+                            tally("stop")
                             done = True                             # Stop: rest zeros (:109-111)
                         else:
                             raise SpecError("unallocated code")
@@ -84,6 +94,7 @@ def decode_block_coefficients(block_bytes, n_chan, block_size):
                         if quant is None:
                             raise SpecError("tail noise before any quantizer")
                         z, y, x2 = get(), get(), get()
+                        tally("tail")
                         amp = f32((z + 1) ** 2) * quant / f32(16)
                         decay = f32(1.0) - f32(2.0 ** -19) * f32(((y << 4) | x2) ** 2)
                         run_id += 1
@@ -93,18 +104,21 @@ def decode_block_coefficients(block_bytes, n_chan, block_size):
                             n += 1
                         done = True
                 elif v == 0x0:
+                    tally("zero_run")
                     run = 1 + get()
                     if n + run > S:
                         raise SpecError("zero run past the end")
                     n += run
                 elif v == 0x1:
                     y, x = get(), get()
+                    tally("long_zero_run")
                     run = ((y << 4) | x) + 33
                     if n + run > S:
                         raise SpecError("zero run past the end")
                     n += run
                 elif v == 0x8:
                     z, y, x = get(), get(), get()
+                    tally("noise_run")
                     run = ((z << 5) | (y << 1) | (x & 1)) + 16
                     level = f32(((x >> 1) + 1) ** 2) * quant / f32(4)
                     if n + run > S:
@@ -114,6 +128,7 @@ def decode_block_coefficients(block_bytes, n_chan, block_size):
                     noise[ch, base + n: base + n + run] = run_id
                     n += run
                 else:
+                    tally("coefficient")
                     s = v - 16 if v >= 8 else v                       # -7..-2, +2..+7
                     coef[ch, base + n] = f32(s * abs(s)) * quant
                     n += 1

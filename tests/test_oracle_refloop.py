@@ -9,8 +9,9 @@ pointers and aliasing.  Two checks:
   * everywhere (also on the GPU box, where the reference is absent): the pure restatement's digests and streams equal the
     committed ones the refloop build produced (tests/golden/refloop_digests.json, made by make_refloop_digests.py).
 This moves those five functions from "equal on synthetic inputs" (test_oracle_pinned.py) to "equal on every input the
-configurations feed them, in situ".  It pins nothing of ulcEncoder.c, ulcEncoder_BlockTransform.c, ulcEncoder_Encode.c and
-ulcDecoder.c themselves (each includes Fourier.h of the absent libfourier)."""
+configurations feed them, in situ".  ulcEncoder.c, ulcEncoder_BlockTransform.c, ulcEncoder_Encode.c and ulcDecoder.c (each
+includes Fourier.h of the absent libfourier) are pinned separately, by the full reference build over the project's
+standin/Fourier.h (tests/test_oracle_fullref.py)."""
 import json
 import os
 import numpy as np
