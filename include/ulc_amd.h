@@ -166,6 +166,32 @@ int  ulcx_encode_host(ulcx_encoder *enc, int mode, float param0, float param1,
                       const float *h_pcm, int nBlocks,
                       uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx);
 
+/* Per-stream rate settings, in the reference tool's own argument convention (tools/ulcEncodeTool.c:157-159):
+ *   RateKbps < 0           -> VBR, Quality = -RateKbps        (ULC_EncodeBlock_VBR)
+ *   else AvgComplexity > 0 -> ABR(RateKbps, AvgComplexity)    (ULC_EncodeBlock_ABR)
+ *   else                   -> CBR(RateKbps)                   (ULC_EncodeBlock_CBR)
+ * Valid entries (what ulcEncodeTool.c:43-50 accepts): both values finite, RateKbps != 0, AvgComplexity >= 0. */
+typedef struct ulcx_rate { float RateKbps; float AvgComplexity; } ulcx_rate;     /* 8 bytes */
+
+/* As ulcx_encode_dev / ulcx_encode_dev_pcm16, with stream s encoded under d_rate[s] instead of one setting for the whole
+ * batch.  d_rate is a DEVICE array [nStreams], read by the call's kernels (it is not a kernel argument): the call stays
+ * asynchronous, and a caller may rewrite the table between calls (hipMemcpyAsync on the same stream).  A stream's setting
+ * may change from one call to the next: window control, the lapping state and BlockComplexity do not depend on it, and
+ * block k of stream s is encoded exactly as ULC_EncodeBlock_{VBR,CBR,ABR} encodes it with that call's entry for s.
+ * The device cannot validate the table without a synchronisation: an invalid entry is the caller's error (that stream's
+ * output is unspecified; nothing outside the call's buffers is read or written).
+ * These calls always enqueue the rate search's full number of probe passes; a pass in which every block has converged
+ * (VBR entries never search) returns at once on the device. */
+int  ulcx_encode_dev_rates(ulcx_encoder *enc, const ulcx_rate *d_rate, const float *d_pcm, int nBlocks,
+                           uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_encode_dev_pcm16_rates(ulcx_encoder *enc, const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
+                                 uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream);
+/* Host-pointer convenience (synchronous).  h_rate [nStreams] is validated first, as ulcEncodeTool.c:43-50 validates its
+ * argument: a non-finite value, RateKbps == 0 or AvgComplexity < 0 returns ULCX_ERR_ARG before any device work, and the
+ * encoder's state is untouched. */
+int  ulcx_encode_host_rates(ulcx_encoder *enc, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
+                            uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx);
+
 /* Debug/parity taps (device->host copies of the intermediates of the LAST call;
  * what the reference keeps in State->TransformBuffer / TransformNoise / the final
  * importance keys).  Each array is [nStreams][nBlocks][nChan*BlockSize] f32; pass

@@ -1,13 +1,19 @@
 /*
  * ulcx_tool.c — batched front-end over libulc_amd.so.
  *
- *   ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav IN2.wav ...
+ *   ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav [-rate:RATE[,AvgComplexity]] IN2.wav ...
  *   ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N]             IN1.ulc IN2.ulc ...
  *
  * What tools/ulcEncodeTool.c / tools/ulcDecodeTool.c of the reference do for ONE file per
  * process, done for MANY files per call: every input is one stream of the batch, all streams
  * advance K blocks per library call.  RATE follows the reference's convention
  * (ulcEncodeTool.c:38-50): negative = VBR quality, positive = CBR kbps, "kbps,complexity" = ABR.
+ * Files may have settings of their own in one batch: "-rate:RATE[,AvgComplexity]" among the inputs sets the
+ * rate of the inputs that follow it (the positional RATE is the default; per-stream table of
+ * ulcx_encode_host_rates), e.g. `ulcx-tool encode out -50 a.wav -rate:48 b.wav -rate:96,0.41 c.wav`.
+ * "RATE,auto" (positional or -rate:) is the reference's two-run ABR workflow in one command: an
+ * analysis pass in VBR sums each file's BlockComplexity (ulcEncodeTool.c:164,178), then each file is
+ * encoded in ABR at its own average complexity, in CBR where that is 0; its line reports the value used.
  * Files written are byte-identical to the reference tools' (tests/test_gpu_dropin.py):
  * container layout tools/ulc_Helper.h:10-20, block count ulcEncodeTool.c:93-98 (+2 blocks of
  * coding/MDCT delay), sample conversion WavIO_Helper.c:49-63 (x 2^-15 in, lrintf(clamp(x 2^15)) out).
@@ -102,12 +108,23 @@ static void out_path(char *dst, size_t n, const char *dir, const char *in, const
 }
 #define DIE(...) do { fprintf(stderr, "ulcx-tool: " __VA_ARGS__); fprintf(stderr, "\n"); return 2; } while (0)
 
-/* one group of inputs = one batch on one device (the whole command line, or a -devices:N share of it on its own thread) */
-struct group { int decode, device, n; char **files; const char *outdir; float rate, avgc; int bs, isFloat; int rc; };
+/* one group of inputs = one batch on one device (the whole command line, or a -devices:N share of it on its own thread);
+ * encode: file i is encoded under {RateKbps, AvgComplexity} = setting[i]; autoc[i] = 1: "RATE,auto" (two passes) */
+struct group { int decode, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int bs, isFloat; int rc; };
+
+/* "RATE[,AvgComplexity]" or "RATE,auto", validated as ulcEncodeTool.c:43-50 does (and finite: the library refuses the rest) */
+static int parse_rate(const char *s, ulcx_rate *r, int *isAuto) {
+    r->RateKbps = 0.0f; r->AvgComplexity = 0.0f; *isAuto = 0;
+    const char *comma = strchr(s, ',');
+    if (comma && !strcmp(comma + 1, "auto")) { *isAuto = 1; if (sscanf(s, "%f", &r->RateKbps) != 1) return -1; }
+    else if (sscanf(s, "%f,%f", &r->RateKbps, &r->AvgComplexity) < 1) return -1;
+    if (!isfinite(r->RateKbps) || !isfinite(r->AvgComplexity) || r->RateKbps == 0.0f || r->AvgComplexity < 0.0f) return -1;
+    if (*isAuto && r->RateKbps < 0.0f) return -1;                  /* ABR needs a rate in kbps */
+    return 0;
+}
 
 static int encode_group(const struct group *g) {
     const char *outdir = g->outdir;
-    const float rate = g->rate, avgc = g->avgc;
     const int bs = g->bs, B = g->n, a = 0;
     char **argv = g->files;
     struct wav *w = (struct wav *)calloc((size_t)B, sizeof(*w));
@@ -120,8 +137,16 @@ static int encode_group(const struct group *g) {
         if (nb > maxBlk) maxBlk = nb;
     }
     const int C = w[0].chan, hz = w[0].rate;
+    /* one setting for every file: the batch-wide call (ulcEncodeTool.c:157-159); otherwise the per-stream table */
+    int uniform = 1, anyAuto = 0;
+    for (int s = 0; s < B; s++) {
+        anyAuto |= g->autoc[s];
+        if (g->autoc[s] || g->setting[s].RateKbps != g->setting[0].RateKbps || g->setting[s].AvgComplexity != g->setting[0].AvgComplexity) uniform = 0;
+    }
+    const float rate = g->setting[0].RateKbps, avgc = g->setting[0].AvgComplexity;
     int mode = rate < 0.0f ? ULCX_MODE_VBR : (avgc > 0.0f ? ULCX_MODE_ABR : ULCX_MODE_CBR);
     float p0 = rate < 0.0f ? -rate : rate;
+    ulcx_rate *table = (ulcx_rate *)calloc((size_t)B, sizeof(ulcx_rate));
     ulcx_encoder *enc = NULL;
     if (ulcx_encoder_create(&enc, g->device, B, C, bs, hz, KBLOCKS) != ULCX_OK) DIE("encoder: %s", ulcx_last_error());
     const int slot = ulcx_encoder_slot_bytes(enc);
@@ -136,6 +161,31 @@ static int encode_group(const struct group *g) {
     uint64_t *total = (uint64_t *)calloc((size_t)B, sizeof(uint64_t));
     uint32_t *maxb = (uint32_t *)calloc((size_t)B, sizeof(uint32_t));
     char path[1024];
+    if (anyAuto) {
+        /* "RATE,auto": pass 1 in VBR (BlockComplexity does not depend on the rate mode; the bytes are dropped) sums each
+         * file's complexity over its own blocks in block order in double precision (ulcEncodeTool.c:130,164,178); after a
+         * reset, pass 2 encodes that file in ABR at (float)(sum / nBlocks) - in CBR if that is 0, as the tool does with RATE,0 */
+        for (int s = 0; s < B; s++) { table[s].RateKbps = -1.0f; table[s].AvgComplexity = 0.0f; }
+        for (uint32_t k0 = 0; k0 < maxBlk; k0 += KBLOCKS) {
+            int K = (maxBlk - k0 < KBLOCKS) ? (int)(maxBlk - k0) : KBLOCKS;
+            for (int s = 0; s < B; s++)
+                wav_read(&w[s], k0 * (uint32_t)bs, (uint32_t)(K * bs), pcm + (size_t)s * K * frame, tmp);
+            if (ulcx_encode_host_rates(enc, table, pcm, K, out, bits, NULL, cplx) != ULCX_OK) DIE("encode (analysis pass): %s", ulcx_last_error());
+            for (int s = 0; s < B; s++) {
+                uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
+                for (int k = 0; k < K && k0 + (uint32_t)k < nb; k++) cplxSum[s] += cplx[s * K + k];
+            }
+        }
+        if (ulcx_encoder_reset(enc) != ULCX_OK) DIE("encoder reset: %s", ulcx_last_error());
+    }
+    for (int s = 0; s < B; s++) {
+        table[s] = g->setting[s];
+        if (g->autoc[s]) {
+            uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
+            table[s].AvgComplexity = (float)(cplxSum[s] / nb);
+        }
+        cplxSum[s] = 0.0;                                              /* (pass 2 sums it again for the report) */
+    }
     for (int s = 0; s < B; s++) {
         out_path(path, sizeof(path), outdir, argv[a + s], ".ulc");
         fo[s] = fopen(path, "wb");
@@ -146,7 +196,9 @@ static int encode_group(const struct group *g) {
         int K = (maxBlk - k0 < KBLOCKS) ? (int)(maxBlk - k0) : KBLOCKS;
         for (int s = 0; s < B; s++)
             wav_read(&w[s], k0 * (uint32_t)bs, (uint32_t)(K * bs), pcm + (size_t)s * K * frame, tmp);
-        if (ulcx_encode_host(enc, mode, p0, avgc, pcm, K, out, bits, NULL, cplx) != ULCX_OK) DIE("encode: %s", ulcx_last_error());
+        const int rc = uniform ? ulcx_encode_host(enc, mode, p0, avgc, pcm, K, out, bits, NULL, cplx)
+                               : ulcx_encode_host_rates(enc, table, pcm, K, out, bits, NULL, cplx);
+        if (rc != ULCX_OK) DIE("encode: %s", ulcx_last_error());
         for (int s = 0; s < B; s++) {
             uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
             for (int k = 0; k < K && k0 + (uint32_t)k < nb; k++) {
@@ -165,11 +217,13 @@ static int encode_group(const struct group *g) {
         h.RateKbps = (uint16_t)ulcx_ulc_rate_kbps(total[s], (uint32_t)hz, (uint32_t)bs, nb);
         uint8_t hb[24]; ulcx_ulc_header_pack(hb, &h);
         fseek(fo[s], 0, SEEK_SET); fwrite(hb, 1, 24, fo[s]); fclose(fo[s]); fclose(w[s].f);
-        printf("%s: %u blocks, %.2f KiB, %u kbps, avg complexity %.5f\n", base_name(argv[a + s]), nb, total[s] / 1024.0, h.RateKbps,
-               cplxSum[s] / nb);                                                      /* ulcEncodeTool.c:176,186 */
+        char used[64] = "";                                                            /* "RATE,auto": the complexity pass 2 used */
+        if (g->autoc[s]) snprintf(used, sizeof(used), "ABR complexity %.9g%s, ", (double)table[s].AvgComplexity, table[s].AvgComplexity > 0.0f ? "" : " (CBR)");
+        printf("%s: %u blocks, %.2f KiB, %u kbps, %savg complexity %.5f\n", base_name(argv[a + s]), nb, total[s] / 1024.0, h.RateKbps,
+               used, cplxSum[s] / nb);                                                /* ulcEncodeTool.c:176,186 */
     }
     ulcx_encoder_destroy(enc);
-    free(pcm); free(out); free(bits); free(cplx); free(cplxSum); free(tmp); free(fo); free(total); free(maxb); free(w);
+    free(pcm); free(out); free(bits); free(cplx); free(cplxSum); free(tmp); free(fo); free(total); free(maxb); free(w); free(table);
     return 0;
 }
 
@@ -288,12 +342,17 @@ static int run_groups(struct group *proto, int nFiles, char **files, int nDev) {
     }
     struct group *gs = (struct group *)calloc((size_t)nDev, sizeof(*gs));
     char **deal = (char **)calloc((size_t)nFiles, sizeof(char *));
+    ulcx_rate *dealR = (ulcx_rate *)calloc((size_t)nFiles, sizeof(ulcx_rate));     /* each file keeps its own setting */
+    int *dealA = (int *)calloc((size_t)nFiles, sizeof(int));
     pthread_t *th = (pthread_t *)calloc((size_t)nDev, sizeof(pthread_t));
-    if (!gs || !deal || !th) { free(gs); free(deal); free(th); DIE("out of memory"); }
+    if (!gs || !deal || !dealR || !dealA || !th) { free(gs); free(deal); free(dealR); free(dealA); free(th); DIE("out of memory"); }
     int at = 0, rc = 0, started = 0;
     for (int g = 0; g < nDev; g++) {
-        gs[g] = *proto; gs[g].device = g % have; gs[g].files = deal + at; gs[g].n = 0; gs[g].rc = 0;
-        for (int i = g; i < nFiles; i += nDev) deal[at + gs[g].n++] = files[i];
+        gs[g] = *proto; gs[g].device = g % have; gs[g].files = deal + at; gs[g].setting = dealR + at; gs[g].autoc = dealA + at; gs[g].n = 0; gs[g].rc = 0;
+        for (int i = g; i < nFiles; i += nDev) {
+            if (!proto->decode) { dealR[at + gs[g].n] = proto->setting[i]; dealA[at + gs[g].n] = proto->autoc[i]; }
+            deal[at + gs[g].n++] = files[i];
+        }
         at += gs[g].n;
     }
     for (int g = 0; g < nDev; g++) {
@@ -302,26 +361,40 @@ static int run_groups(struct group *proto, int nFiles, char **files, int nDev) {
     }
     /* (a failed start: the groups already running work on gs / deal - they are joined before anything is freed) */
     for (int g = 0; g < started; g++) { pthread_join(th[g], NULL); if (gs[g].rc > rc) rc = gs[g].rc; }
-    free(gs); free(deal); free(th);
+    free(gs); free(deal); free(dealR); free(dealA); free(th);
     return rc;
 }
 static int do_encode(int argc, char **argv) {
-    if (argc < 5) DIE("usage: ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN.wav ...");
+    if (argc < 5) DIE("usage: ulcx-tool encode OUTDIR RATE[,AvgComplexity|,auto] [-blocksize:N] [-devices:N] IN.wav [-rate:RATE[,...]] IN.wav ...");
     struct group g; memset(&g, 0, sizeof(g));
     g.outdir = argv[2];
-    sscanf(argv[3], "%f,%f", &g.rate, &g.avgc);
-    if (g.rate == 0.0f || g.avgc < 0.0f) DIE("invalid coding rate '%s'", argv[3]);
-    int a = 4, nDev = 1;
+    ulcx_rate cur; int curAuto = 0;
+    if (parse_rate(argv[3], &cur, &curAuto)) DIE("invalid coding rate '%s'", argv[3]);
+    int a = 4, nDev = 1, endOpts = 0;
     g.bs = 2048;
     for (; a < argc && argv[a][0] == '-'; a++) {
-        if (!strcmp(argv[a], "--")) { a++; break; }          /* end of options: input names may start with '-' behind it */
+        if (!strcmp(argv[a], "--")) { a++; endOpts = 1; break; }    /* end of options: input names may start with '-' behind it */
         if (!strncmp(argv[a], "-blocksize:", 11)) g.bs = atoi(argv[a] + 11);
         else if (!strncmp(argv[a], "-devices:", 9)) nDev = atoi(argv[a] + 9);
+        else if (!strncmp(argv[a], "-rate:", 6)) { if (parse_rate(argv[a] + 6, &cur, &curAuto)) DIE("invalid coding rate '%s'", argv[a]); }
         else DIE("unknown option '%s'", argv[a]);
     }
     if (g.bs < 256 || g.bs > 8192 || (g.bs & -g.bs) != g.bs) DIE("unsupported block size %d", g.bs);
     if (nDev < 1 || nDev > 64) DIE("-devices:%d out of range", nDev);
-    return run_groups(&g, argc - a, argv + a, nDev);
+    /* the inputs, each with the setting in force where it stands: "-rate:RATE[,AvgComplexity|,auto]" between them sets it for
+     * the inputs that follow (behind "--" every argument is an input) */
+    char **files = (char **)calloc((size_t)(argc - a + 1), sizeof(char *));
+    g.setting = (ulcx_rate *)calloc((size_t)(argc - a + 1), sizeof(ulcx_rate));
+    g.autoc = (int *)calloc((size_t)(argc - a + 1), sizeof(int));
+    if (!files || !g.setting || !g.autoc) DIE("out of memory");
+    int n = 0;
+    for (; a < argc; a++) {
+        if (!endOpts && !strncmp(argv[a], "-rate:", 6)) { if (parse_rate(argv[a] + 6, &cur, &curAuto)) DIE("invalid coding rate '%s'", argv[a]); continue; }
+        files[n] = argv[a]; g.setting[n] = cur; g.autoc[n] = curAuto; n++;
+    }
+    const int rc = run_groups(&g, n, files, nDev);
+    free(files); free(g.setting); free(g.autoc);
+    return rc;
 }
 static int do_decode(int argc, char **argv) {
     if (argc < 4) DIE("usage: ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N] IN.ulc ...");
@@ -346,8 +419,10 @@ int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "decode")) return do_decode(argc, argv);
     fprintf(stderr,
             "ulcx-tool - batched ulc-codec front-end over libulc_amd.so (MI355X)\n"
-            "  ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav IN2.wav ...\n"
+            "  ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav [-rate:RATE[,...]] IN2.wav ...\n"
             "      RATE < 0: VBR quality; RATE > 0: CBR kbps; RATE,AvgComplexity: ABR  (as ulcencodetool)\n"
+            "      RATE,auto: two-pass ABR at each file's own average complexity (0: CBR)\n"
+            "      -rate:RATE[,AvgComplexity|,auto]  setting of the inputs that follow it (RATE is the default)\n"
             "  ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N] IN1.ulc IN2.ulc ...\n"
             "  --          end of options (input names that start with '-')\n"
             "  -devices:N  inputs dealt round-robin over N groups, one host thread + one codec object each (device g %% visible)\n");

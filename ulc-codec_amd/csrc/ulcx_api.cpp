@@ -27,6 +27,7 @@ struct ulcx_encoder {
     int nsSlots;              // resident workgroups of k_nsums (its persistent grid)
     // staging for the host-pointer API
     float *d_pcm; uint8_t *d_out; int32_t *d_bits, *d_wc; float *d_cplx;
+    ulcx_rate *d_rate;        // [B] the per-stream table of ulcx_encode_host_rates
     // single-block path (ulcx_encode_block1): own stream, pinned staging, the captured launch sequence
     struct Block1Meta { int32_t bits, wc; float cplx; int32_t pad; UlcxWcState wcs; };
     hipStream_t b1Stream; hipGraph_t b1Graph; hipGraphExec_t b1Exec; bool b1Init, b1Graphed, b1NoGraph;
@@ -140,7 +141,7 @@ extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams,
     ulcx_encoder *e = new ulcx_encoder();
     e->device = device; e->B = nStreams; e->C = nChan; e->BS = BlockSize; e->rate = RateHz; e->maxK = maxBlocksPerCall;
     e->tables = nullptr; e->evOk = false; e->evRecorded = false; e->timing = true; e->lastK = 0; e->sideOk = false; e->side = nullptr; e->keysFinal = false;
-    e->d_pcm = nullptr; e->d_out = nullptr; e->d_bits = nullptr; e->d_wc = nullptr; e->d_cplx = nullptr;
+    e->d_pcm = nullptr; e->d_out = nullptr; e->d_bits = nullptr; e->d_wc = nullptr; e->d_cplx = nullptr; e->d_rate = nullptr;
     e->b1Init = e->b1Graphed = e->b1NoGraph = false; e->b1Stream = nullptr; e->b1Rekeys = 0; e->pinIn = nullptr; e->pinOut = nullptr; e->pinMeta = nullptr;
     UlcxEncCtx &c = e->ctx;
     memset(&c, 0, sizeof(c));
@@ -277,14 +278,17 @@ extern "C" void ulcx_encoder_destroy(ulcx_encoder *e) { if (e) { hipSetDevice(e-
 extern "C" int ulcx_encoder_reset(ulcx_encoder *e) { if (!e) return ULCX_ERR_ARG; CKR(hipSetDevice(e->device)); return enc_reset_state(e); }
 extern "C" int ulcx_encoder_slot_bytes(const ulcx_encoder *e) { return e ? e->ctx.slot : 0; }
 
-static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
+// d_rate != NULL: per-stream settings read on the device (ulcx_encode_dev_rates); mode / p0 / p1 are then unused
+static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
                           uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
     if (!e || (!d_pcm && !d_pcm16) || !d_out || !d_bits || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_encode_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (d_rate) { mode = ULCX_MODE_VBR; p0 = 100.0f; p1 = 0.0f; }
     if (mode != ULCX_MODE_VBR && mode != ULCX_MODE_CBR && mode != ULCX_MODE_ABR) { ulcx_set_error("bad mode"); return ULCX_ERR_ARG; }
     CKR(hipSetDevice(e->device));
     UlcxEncCtx c = e->ctx;
     c.K = nBlocks; c.keyFinal = 0; c.mode = mode; c.p0 = p0; c.p1 = p1;
     c.vbrTarget = (mode == ULCX_MODE_VBR) ? 0x1.E4EFB7p3f * logf(100.0f / p0) : 0.0f;     // ulcEncoder.c:144 (host libm, data independent)
+    c.rates = (const float2 *)d_rate;
     c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = d_out; c.bits = d_bits; c.wcOut = d_wc; c.cplxOut = d_cplx;
     UlcxEncAux aux;
     aux.side = e->sideOk ? e->side : nullptr; aux.side2 = e->sideOk ? e->side2 : nullptr; aux.side3 = e->sideOk ? e->side3 : nullptr;
@@ -301,12 +305,57 @@ static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const f
 extern "C" int ulcx_encode_dev(ulcx_encoder *e, int mode, float p0, float p1, const float *d_pcm, int nBlocks,
                                uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
     if (!d_pcm) { ulcx_set_error("ulcx_encode_dev: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, mode, p0, p1, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+    return encode_dev_any(e, mode, p0, p1, nullptr, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
 }
 extern "C" int ulcx_encode_dev_pcm16(ulcx_encoder *e, int mode, float p0, float p1, const int16_t *d_pcm16, int nBlocks,
                                      uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
     if (!d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, mode, p0, p1, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+    return encode_dev_any(e, mode, p0, p1, nullptr, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encode_dev_rates(ulcx_encoder *e, const ulcx_rate *d_rate, const float *d_pcm, int nBlocks,
+                                     uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!d_rate || !d_pcm) { ulcx_set_error("ulcx_encode_dev_rates: bad argument"); return ULCX_ERR_ARG; }
+    return encode_dev_any(e, 0, 0.0f, 0.0f, d_rate, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encode_dev_pcm16_rates(ulcx_encoder *e, const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
+                                           uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!d_rate || !d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16_rates: bad argument"); return ULCX_ERR_ARG; }
+    return encode_dev_any(e, 0, 0.0f, 0.0f, d_rate, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+
+extern "C" int ulcx_encode_host_rates(ulcx_encoder *e, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
+                                      uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
+    if (!e || !h_rate || !h_pcm || !h_out || !h_bits) { ulcx_set_error("ulcx_encode_host_rates: bad argument"); return ULCX_ERR_ARG; }
+    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
+    for (int s = 0; s < e->B; s++) {                   // ulcEncodeTool.c:43-50, before any device work
+        const float r = h_rate[s].RateKbps, a = h_rate[s].AvgComplexity;
+        if (!isfinite(r) || !isfinite(a) || r == 0.0f || a < 0.0f) {
+            ulcx_set_error("ulcx_encode_host_rates: invalid entry for stream %d (RateKbps %g, AvgComplexity %g)", s, (double)r, (double)a);
+            return ULCX_ERR_ARG;
+        }
+    }
+    CKR(hipSetDevice(e->device));
+    size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS;
+    if (!e->d_pcm) {
+        int rc;
+        if ((rc = dalloc(e->allocs, &e->d_pcm, NBmax * cb, false))) return rc;
+        if ((rc = dalloc(e->allocs, &e->d_out, NBmax * e->ctx.slot, false))) return rc;
+        if ((rc = dalloc(e->allocs, &e->d_bits, NBmax, false))) return rc;
+        if ((rc = dalloc(e->allocs, &e->d_wc, NBmax, false))) return rc;
+        if ((rc = dalloc(e->allocs, &e->d_cplx, NBmax, false))) return rc;
+    }
+    if (!e->d_rate) { int rc = dalloc(e->allocs, &e->d_rate, (size_t)e->B, false); if (rc) return rc; }
+    size_t NB = (size_t)e->B * nBlocks;
+    CKR(hipMemcpy(e->d_rate, h_rate, sizeof(ulcx_rate) * (size_t)e->B, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
+    int rc = ulcx_encode_dev_rates(e, e->d_rate, e->d_pcm, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_out, e->d_out, NB * e->ctx.slot, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
 }
 
 extern "C" int ulcx_encode_host(ulcx_encoder *e, int mode, float p0, float p1, const float *h_pcm, int nBlocks,

@@ -81,7 +81,10 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     hipEvent_t evFork = aux.evFork, evJoin = aux.evJoin, evFork2 = aux.evFork2, *evWC = aux.evWC;
     const int wcPipe = (side && side2 && side3) ? aux.wcPipe : 1;
     if (aux.nXf) *aux.nXf = 0;
-    if (c.mode != ULCX_MODE_VBR) CK(hipMemsetAsync(c.cbrLive, 0, sizeof(int), st));
+    // per-stream rates (c.rates): the host does not know the table, so such a call runs the rate search's launch sequence
+    // whatever it holds (VBR blocks skip every probe on the device)
+    const bool search = c.mode != ULCX_MODE_VBR || c.rates != nullptr;
+    if (search) CK(hipMemsetAsync(c.cbrLive, 0, sizeof(int), st));
     if (c.barkRing) CK(hipMemsetAsync(c.decCount, 0, sizeof(int), st));           // k_xf lists this call's decimated blocks
     int NB = c.B * c.K;
     int stage = 0;
@@ -267,7 +270,7 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     // VBR: one pass.  CBR/ABR: the reference's binary search (ulcEncoder.c:98-110) needs at most
     // ceil(log2(MaxCoef))+1 probes; every block runs its own search in lock step, then one final pass.
     int probes = 0;
-    if (c.mode != ULCX_MODE_VBR) {
+    if (search) {
         probes = 2; int m = N; while (m > 1) { probes++; m >>= 1; }
         // No read-back: the host always enqueues the full count and a pass whose blocks have all converged (c.cbrLive,
         // counted down on the device) returns at the top of every kernel - nothing inside the call waits for the device.
@@ -279,9 +282,49 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
                        CK(hipFuncSetAttribute((const void *)k_select_wave<__VA_ARGS__, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)selLds)); } while (0)
         SELA(128, 0); SELA(64, 0); SELA(64, 11);
 #undef SELA
+        if (c.rates) {
+#define SELA(...) do { CK(hipFuncSetAttribute((const void *)k_select_wave_rates<__VA_ARGS__, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)selLds)); \
+                       CK(hipFuncSetAttribute((const void *)k_select_wave_rates<__VA_ARGS__, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)selLds)); \
+                       CK(hipFuncSetAttribute((const void *)k_select_wave_rates<__VA_ARGS__, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)selLds)); } while (0)
+            SELA(128, 0); SELA(64, 0); SELA(64, 11);
+#undef SELA
+        }
     }
     const size_t selLdsPair = (size_t)ulcx_sel_lds_words(c.BS) * sizeof(float);      // one block per workgroup
+    // Per-stream rates: the selection kernels' counterparts that leave the blocks of the other kind (k_select_wave_rates).  The
+    // probes select the searching blocks (PASS 1, 2); the final pass selects them from their stored keys (PASS 2) and the VBR
+    // blocks as a one-pass call does (PASS 0).
+    auto launch_select_rates = [&](int fin) {
+        int R = N / 64;
+        const dim3 g((NB + 3) / 4), b(256);
+        auto one = [&](int pass) {
+#define SELR(...) do { if (pass == 1) hipLaunchKernelGGL((k_select_wave_rates<__VA_ARGS__, 1>), g, b, selLds, st, c, fin); \
+                       else if (pass == 2) hipLaunchKernelGGL((k_select_wave_rates<__VA_ARGS__, 2>), g, b, selLds, st, c, fin); \
+                       else hipLaunchKernelGGL((k_select_wave_rates<__VA_ARGS__, 0>), g, b, selLds, st, c, fin); } while (0)
+            switch (R) {
+                case 128:
+                    if (c.C == 2 && c.selPair) {
+                        const dim3 gp(NB), bp(128);
+                        if (pass == 1) hipLaunchKernelGGL((k_select_pair_rates<64, 12, 1>), gp, bp, selLdsPair, st, c, fin);
+                        else if (pass == 2) hipLaunchKernelGGL((k_select_pair_rates<64, 12, 2>), gp, bp, selLdsPair, st, c, fin);
+                        else hipLaunchKernelGGL((k_select_pair_rates<64, 12, 0>), gp, bp, selLdsPair, st, c, fin);
+                    } else SELR(128, 0);
+                    return true;
+                case 64: if (c.lgBS == 11) SELR(64, 11); else SELR(64, 0); return true;
+                case 32: SELR(32, 0); return true;
+                case 16: SELR(16, 0); return true;
+                case 8:  SELR(8, 0); return true;
+                case 4:  SELR(4, 0); return true;
+                default: return false;
+            }
+#undef SELR
+        };
+        if (!one(c.selPass)) return false;
+        if (fin) one(0);
+        return true;
+    };
     auto launch_select = [&](int fin) {
+        if (c.rates && c.selPass) return launch_select_rates(fin);
         int R = N / 64;
         const dim3 g((NB + 3) / 4), b(256);
 #define SELW(...) do { if (c.selPass == 1) hipLaunchKernelGGL((k_select_wave<__VA_ARGS__, 1>), g, b, selLds, st, c, fin); \

@@ -522,6 +522,20 @@ __global__ __launch_bounds__(128) void k_select_pair(UlcxEncCtx c, int finalPass
 extern template __global__ void k_select_pair<64, 12, 0>(UlcxEncCtx, int);
 extern template __global__ void k_select_pair<64, 12, 1>(UlcxEncCtx, int);
 extern template __global__ void k_select_pair<64, 12, 2>(UlcxEncCtx, int);
+// the same kernels for per-stream-rates calls, split by the block's setting (ulcx_enc_psy.hip)
+template <int R, int LGBS = 0, int PASS = 0>
+__global__ __launch_bounds__(256, SEL_MINW(R, LGBS, PASS)) void k_select_wave_rates(UlcxEncCtx c, int finalPass);
+template <int R, int LGBS = 0, int PASS = 0>
+__global__ __launch_bounds__(128) void k_select_pair_rates(UlcxEncCtx c, int finalPass);
+#define ULCX_SEL_RATES_EXT(R, L) extern template __global__ void k_select_wave_rates<R, L, 0>(UlcxEncCtx, int); \
+                                 extern template __global__ void k_select_wave_rates<R, L, 1>(UlcxEncCtx, int); \
+                                 extern template __global__ void k_select_wave_rates<R, L, 2>(UlcxEncCtx, int);
+ULCX_SEL_RATES_EXT(128, 0) ULCX_SEL_RATES_EXT(64, 0) ULCX_SEL_RATES_EXT(64, 11) ULCX_SEL_RATES_EXT(32, 0)
+ULCX_SEL_RATES_EXT(16, 0) ULCX_SEL_RATES_EXT(8, 0) ULCX_SEL_RATES_EXT(4, 0)
+#undef ULCX_SEL_RATES_EXT
+extern template __global__ void k_select_pair_rates<64, 12, 0>(UlcxEncCtx, int);
+extern template __global__ void k_select_pair_rates<64, 12, 1>(UlcxEncCtx, int);
+extern template __global__ void k_select_pair_rates<64, 12, 2>(UlcxEncCtx, int);
 __global__ void k_heapsel(UlcxEncCtx c, int ldsEntries);
 __global__ void k_heapsel_pipe(UlcxEncCtx c, int fullRanking);
 __global__ void k_keep_ranks(UlcxEncCtx c, int finalPass);

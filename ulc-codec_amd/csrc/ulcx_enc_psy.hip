@@ -763,6 +763,38 @@ __global__ __launch_bounds__(128) void k_select_pair(UlcxEncCtx c, int finalPass
     select_body<R, LGBS, PASS, true>(c, finalPass, blockIdx.x, 0, lane, half, xch, sel_lds);
 }
 
+// Per-stream-rates calls (c.rates): the same selection, split by the block's setting.  A VBR block (cbrDone = ULCX_DONE_VBR)
+// runs no search, so no probe stores its ordered keys: PASS 1 / 2 leave it, and in the final pass a PASS 0 launch forms its
+// keys and selects its nTargetCoef coefficients, as a one-pass call does.  (Letting the first probe store them would not do:
+// that launch returns at once when no search is open - an all-VBR table - or once the open ones have all left.)
+template <int PASS>
+__device__ __forceinline__ bool rates_leave(const UlcxEncCtx &c, int blk) {
+    const bool vbr = c.cbrDone[blk] == ULCX_DONE_VBR;
+    return PASS == 0 ? !vbr : vbr;
+}
+
+template <int R, int LGBS, int PASS>
+__global__ __launch_bounds__(256, SEL_MINW(R, LGBS, PASS)) void k_select_wave_rates(UlcxEncCtx c, int finalPass) {
+    if (probes_over(c, finalPass)) return;
+    extern __shared__ float sel_lds[];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int blk = blockIdx.x * 4 + wv;
+    if (blk >= c.B * c.K || rates_leave<PASS>(c, blk)) return;      // (one block per wave, no workgroup barrier in select_body)
+    select_body<R, LGBS, PASS, false>(c, finalPass, blk, wv, lane, 0, nullptr, sel_lds);
+}
+
+template <int R, int LGBS, int PASS>
+__global__ __launch_bounds__(128) void k_select_pair_rates(UlcxEncCtx c, int finalPass) {
+    extern __shared__ float sel_lds[];
+    __shared__ uint32_t xch[4];
+    __shared__ int over;
+    if (threadIdx.x == 0) over = (probes_over(c, finalPass) || rates_leave<PASS>(c, blockIdx.x)) ? 1 : 0;
+    __syncthreads();
+    if (over) return;
+    const int half = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    select_body<R, LGBS, PASS, true>(c, finalPass, blockIdx.x, 0, lane, half, xch, sel_lds);
+}
+
 // Exact emulation of the reference's min-heap heapsort for the (rare) blocks whose
 // threshold tie group straddles the cut: ranks are assigned N-1 downwards in pop
 // order, so the kept set is everything still in the heap after N-k pops.
@@ -948,3 +980,12 @@ template __global__ void k_select_wave<8, 0, 2>(UlcxEncCtx, int);
 template __global__ void k_select_pair<64, 12, 0>(UlcxEncCtx, int);
 template __global__ void k_select_pair<64, 12, 1>(UlcxEncCtx, int);
 template __global__ void k_select_pair<64, 12, 2>(UlcxEncCtx, int);
+#define ULCX_SEL_RATES_INST(R, L) template __global__ void k_select_wave_rates<R, L, 0>(UlcxEncCtx, int); \
+                                  template __global__ void k_select_wave_rates<R, L, 1>(UlcxEncCtx, int); \
+                                  template __global__ void k_select_wave_rates<R, L, 2>(UlcxEncCtx, int);
+ULCX_SEL_RATES_INST(128, 0) ULCX_SEL_RATES_INST(64, 0) ULCX_SEL_RATES_INST(64, 11) ULCX_SEL_RATES_INST(32, 0)
+ULCX_SEL_RATES_INST(16, 0) ULCX_SEL_RATES_INST(8, 0) ULCX_SEL_RATES_INST(4, 0)
+#undef ULCX_SEL_RATES_INST
+template __global__ void k_select_pair_rates<64, 12, 0>(UlcxEncCtx, int);
+template __global__ void k_select_pair_rates<64, 12, 1>(UlcxEncCtx, int);
+template __global__ void k_select_pair_rates<64, 12, 2>(UlcxEncCtx, int);

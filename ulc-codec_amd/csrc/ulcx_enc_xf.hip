@@ -552,7 +552,19 @@ __global__ __launch_bounds__(64) void k_cplx(UlcxEncCtx c, int k0, int k1) {
             }
         }
     };
-    if (c.mode == ULCX_MODE_VBR) sums(std::false_type{}); else sums(std::true_type{});
+    // Per-stream rates (c.rates, one 8-byte entry per stream): the setting of this lane's block, in the reference tool's
+    // convention (ulcEncodeTool.c:157-159).  Scalar calls take the batch's mode and parameters as they always did.
+    int mode = c.mode;
+    float p0 = c.p0, p1 = c.p1, vbrTarget = c.vbrTarget;
+    if (c.rates) {
+        const float2 r = c.rates[blk / c.K];
+        if (r.x < 0.0f) {
+            mode = ULCX_MODE_VBR; p0 = -r.x;
+            vbrTarget = 0x1.E4EFB7p3f * ulcx_logf(100.0f / p0);       // ulcEncoder.c:144 (correctly rounded division, glibc logf)
+        } else { mode = (r.y > 0.0f) ? ULCX_MODE_ABR : ULCX_MODE_CBR; p0 = r.x; p1 = r.y; }
+        // (the collapsible-coefficient count is only needed by blocks that search: a wave of VBR blocks takes the short loop)
+        if (__ballot(mode != ULCX_MODE_VBR)) sums(std::true_type{}); else sums(std::false_type{});
+    } else if (c.mode == ULCX_MODE_VBR) sums(std::false_type{}); else sums(std::true_type{});
     if (cx != 0.0f) {
         cx = ulcx_logf((cw * cw) / cx) / c.cplxScale;
         if (cx < 0.0f) cx = 0.0f;
@@ -560,17 +572,27 @@ __global__ __launch_bounds__(64) void k_cplx(UlcxEncCtx c, int k0, int k1) {
     }
     c.cplx[blk] = cx;
     int maxCoef = c.nnz[blk];
-    if (c.mode == ULCX_MODE_VBR) {
+    if (mode == ULCX_MODE_VBR) {
         int nT = maxCoef;
-        if (c.vbrTarget > 0.0f) {
-            float ft = (c.C * c.BS) * cx / c.vbrTarget;
+        if (vbrTarget > 0.0f) {
+            float ft = (c.C * c.BS) * cx / vbrTarget;
             if (ft < maxCoef) nT = (int)ft;
         }
         c.nout[blk] = nT;
+        if (c.rates) {
+            // a VBR block of a call that also runs rate searches: its search is over before it starts (the probe passes skip
+            // it, it adds nothing to cbrLive) and the final pass encodes it at nTargetCoef; the rest of the state as a searching
+            // block leaves it, so that no probe-pass kernel reads a value of an earlier call
+            c.cbrLo[blk] = 0; c.cbrHi[blk] = maxCoef;
+            c.cbrDone[blk] = ULCX_DONE_VBR;
+            c.cbrBudget[blk] = 0;
+            c.selWin[blk] = make_uint4(0u, 0u, (uint32_t)(c.C * c.BS), 0u);
+            for (int u = 0; u < c.C * 4; u++) c.tailSum[((size_t)blk * c.C * 4 + u) * 8 + 6] = 0.0f;
+        }
     } else {
         // CBR/ABR binary search state (ulcEncoder.c:96-101)
-        float kbps = c.p0;
-        if (c.mode == ULCX_MODE_ABR) kbps = c.p0 * cx / c.p1;
+        float kbps = p0;
+        if (mode == ULCX_MODE_ABR) kbps = p0 * cx / p1;
         int budget = (int)((c.BS * kbps) * 1000.0f / c.rateHz);
         int lo = 0, hi = maxCoef;
         int done = (0 < maxCoef) ? 0 : 1;

@@ -15,6 +15,7 @@
 #define ULCX_COEF_EPS (0x1.0p-31f)     // include/ulcEncoder.h:36
 #define ULCX_HEAP_LDS_BYTES (128 * 1024)
 #define ULCX_HEAP_GRID 256
+#define ULCX_DONE_VBR 2                  // cbrDone of a VBR block in a per-stream-rates call (any non-zero value means "no search left")
 // Ablation switches for timing experiments (they break the results): compiled in only with `make EXTRA=-DULCX_ABLATE`,
 // then set by ULCX_DBG_SKIP=bits at create time.  The shipped library has no such branches.
 #ifdef ULCX_ABLATE
@@ -59,6 +60,7 @@ struct UlcxEncCtx {
     int unitCap;                         // bytes per (chan,subblock) nybble staging row = 2*BS+32 per channel
     int mode; float p0, p1;              // rate control
     float vbrTarget;                     // 0x1.E4EFB7p3f*logf(100/Quality) (host libm), ulcEncoder.c:144
+    const float2 *rates;                 // [B] per-stream {RateKbps, AvgComplexity} (ulcx_encode_*_rates: replaces mode/p0/p1); NULL = the scalar setting
     // window-control constants (1 - rate), host expf: WindowControl.c:75,76,94,95,120
     float cHP, cBP, qHP, qBP, cBlk;
     float cplxScale;                     // BlockTransform.c:320
@@ -86,7 +88,7 @@ struct UlcxEncCtx {
     int    *nnz;                         // [NB]
     float  *cplx;                        // [NB]
     int    *nout;                        // [NB]   nOutCoef of the current pass
-    int    *cbrLo, *cbrHi, *cbrDone;     // [NB]
+    int    *cbrLo, *cbrHi, *cbrDone;     // [NB]  (cbrDone = ULCX_DONE_VBR: a VBR block of a per-stream-rates call - no search, nOut = nTargetCoef)
     uint32_t *keep;                      // [NB][C*BS/32]
     int    *fbList; int *fbCount;        // tie-straddle fallback list
     uint8_t *unitBuf;                    // [NB][C][unitCap]

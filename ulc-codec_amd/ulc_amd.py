@@ -22,6 +22,7 @@ EXPORTS = [
     "ulcx_decoder_create", "ulcx_decoder_destroy", "ulcx_decoder_reset", "ulcx_decode_dev", "ulcx_decode_dev_pcm16", "ulcx_decode_host",
     "ulcx_encoder_last_fallbacks", "ulcx_encoder_debug_force_exact", "ulcx_ulc_header_pack", "ulcx_ulc_header_parse", "ulcx_ulc_rate_kbps",
     "ulcx_pack_streams_dev", "ulcx_decode_packed_dev", "ulcx_decode_packed_host", "ulcx_decoder_upload_payload", "ulcx_decode_resident_host", "ulcx_encoder_stage_ms", "ulcx_encoder_stage_name", "ulcx_encoder_last_xf_launches", "ulcx_decoder_stage_ms", "ulcx_decoder_stage_name", "ulcx_block_extent_bytes", "ulcx_encoder_set_timing", "ulcx_decoder_set_timing", "ulcx_encode_block1", "ulcx_decode_block1", "ulcx_decode_block1_rng", "ulcx_build_rev", "ulcx_dec_split_plan", "ulcx_dec_tail_plan", "ulcx_decoder_last_cut",
+    "ulcx_encode_dev_rates", "ulcx_encode_dev_pcm16_rates", "ulcx_encode_host_rates",
 ]
 
 
@@ -51,6 +52,10 @@ def lib():
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.ulcx_encode_dev_pcm16.argtypes = l.ulcx_encode_dev.argtypes
         l.ulcx_encode_host.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, _f32p, C.c_int, _u8p, _i32p, _i32p, _f32p]
+        if hasattr(l, "ulcx_encode_dev_rates"):            # (an older build named by ULC_AMD_LIB for an A/B run may lack them)
+            l.ulcx_encode_dev_rates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_encode_dev_pcm16_rates.argtypes = l.ulcx_encode_dev_rates.argtypes
+            l.ulcx_encode_host_rates.argtypes = [C.c_void_p, _f32p, _f32p, C.c_int, _u8p, _i32p, _i32p, _f32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -139,6 +144,32 @@ class BatchEncoder:
                                       _p(wc, _i32p), _p(cplx, _f32p)), "ulcx_encode_host")
         self.lastK = K
         return out, bits, wc, cplx
+
+    def encode_rates(self, pcm, rates):
+        """As encode(), with a setting per stream: rates is float32 [B][2] = {RateKbps, AvgComplexity} per stream in the
+        reference tool's convention (RateKbps < 0: VBR at quality -RateKbps; else AvgComplexity > 0: ABR; else CBR).
+        Invalid entries (non-finite, RateKbps == 0, AvgComplexity < 0) raise before any device work."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        rates = np.ascontiguousarray(rates, dtype=np.float32)
+        assert pcm.shape[0] == self.B and pcm.shape[-1] == self.C and rates.shape == (self.B, 2)
+        K = pcm.shape[1] // self.BS
+        assert pcm.shape[1] == K * self.BS
+        out = np.zeros((self.B, K, self.slot), np.uint8)
+        bits = np.zeros((self.B, K), np.int32)
+        wc = np.zeros((self.B, K), np.int32)
+        cplx = np.zeros((self.B, K), np.float32)
+        _check(lib().ulcx_encode_host_rates(self.h, _p(rates, _f32p), _p(pcm, _f32p), K, _p(out, _u8p), _p(bits, _i32p),
+                                            _p(wc, _i32p), _p(cplx, _f32p)), "ulcx_encode_host_rates")
+        self.lastK = K
+        return out, bits, wc, cplx
+
+    def encode_dev_rates(self, d_rates, d_pcm, n_blocks, d_out, d_bits, d_wc=0, d_cplx=0, stream=0, pcm16=False):
+        """Device-pointer path with a per-stream table: d_rates points to float32 [B][2] on the device (read by the call's
+        kernels, so it may be rewritten between calls on the same stream); pcm16=True takes int16 samples."""
+        fn = lib().ulcx_encode_dev_pcm16_rates if pcm16 else lib().ulcx_encode_dev_rates
+        _check(fn(self.h, d_rates, d_pcm, n_blocks, d_out, d_bits, d_wc or None, d_cplx or None, stream or None),
+               "ulcx_encode_dev_pcm16_rates" if pcm16 else "ulcx_encode_dev_rates")
+        self.lastK = n_blocks
 
     def encode_dev(self, d_pcm, n_blocks, d_out, d_bits, d_wc=0, d_cplx=0, mode=MODE_VBR, p0=50.0, p1=0.0, stream=0):
         """Device-pointer path (ints / .data_ptr()); asynchronous on `stream`."""
