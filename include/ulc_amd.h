@@ -192,6 +192,19 @@ int  ulcx_encode_dev_pcm16_rates(ulcx_encoder *enc, const ulcx_rate *d_rate, con
 int  ulcx_encode_host_rates(ulcx_encoder *enc, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
                             uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx);
 
+/* Analysis only: window control, MDCT and block complexity of nBlocks consecutive blocks of every stream.
+ * No selection, no writer, no output slots.  d_wc / d_cplx as in ulcx_encode_dev ([nStreams][nBlocks]); at least one
+ * of them non-NULL.  The streams' persistent state advances exactly as an encode call of the same blocks advances it:
+ * analysis and encode calls may be mixed freely on one encoder, and ulcx_encoder_reset() after an analysis pass gives
+ * the second pass of the reference tool's ABR workflow a fresh encoder (ulcEncodeTool.c:157-188).  The values are those
+ * ulcx_encode_dev writes for the same input - State->WindowCtrl and State->BlockComplexity after the block - and do
+ * not depend on a rate mode.  Asynchronous on hipStream like ulcx_encode_dev; nBlocks in 1 .. maxBlocksPerCall.
+ * After an analysis call there are no intermediates of a "last call": ulcx_encoder_debug_fetch returns ULCX_ERR_ARG and
+ * ulcx_encoder_last_fallbacks 0 until the next encode call; ulcx_encoder_stage_ms reports 0 for the stages that did not run. */
+int  ulcx_analyse_dev      (ulcx_encoder *enc, const float   *d_pcm,   int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_analyse_dev_pcm16(ulcx_encoder *enc, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_analyse_host     (ulcx_encoder *enc, const float   *h_pcm,   int nBlocks, int32_t *h_wc, float *h_cplx);   /* synchronous */
+
 /* Debug/parity taps (device->host copies of the intermediates of the LAST call;
  * what the reference keeps in State->TransformBuffer / TransformNoise / the final
  * importance keys).  Each array is [nStreams][nBlocks][nChan*BlockSize] f32; pass

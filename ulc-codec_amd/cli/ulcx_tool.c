@@ -3,6 +3,7 @@
  *
  *   ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav [-rate:RATE[,AvgComplexity]] IN2.wav ...
  *   ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N]             IN1.ulc IN2.ulc ...
+ *   ulcx-tool analyse [-blocksize:N] [-devices:N]                            IN1.wav IN2.wav ...
  *
  * What tools/ulcEncodeTool.c / tools/ulcDecodeTool.c of the reference do for ONE file per
  * process, done for MANY files per call: every input is one stream of the batch, all streams
@@ -12,8 +13,11 @@
  * rate of the inputs that follow it (the positional RATE is the default; per-stream table of
  * ulcx_encode_host_rates), e.g. `ulcx-tool encode out -50 a.wav -rate:48 b.wav -rate:96,0.41 c.wav`.
  * "RATE,auto" (positional or -rate:) is the reference's two-run ABR workflow in one command: an
- * analysis pass in VBR sums each file's BlockComplexity (ulcEncodeTool.c:164,178), then each file is
- * encoded in ABR at its own average complexity, in CBR where that is 0; its line reports the value used.
+ * analysis pass (ulcx_analyse_host: no selection, no writer) sums each file's BlockComplexity
+ * (ulcEncodeTool.c:164,178), then each file is encoded in ABR at its own average complexity, in CBR where
+ * that is 0; its line reports the value used.  "analyse" runs that pass alone and prints per file the block
+ * count, the average complexity `RATE,<complexity>` is to be fed with and the number of window-switched
+ * blocks; it writes no file.
  * Files written are byte-identical to the reference tools' (tests/test_gpu_dropin.py):
  * container layout tools/ulc_Helper.h:10-20, block count ulcEncodeTool.c:93-98 (+2 blocks of
  * coding/MDCT delay), sample conversion WavIO_Helper.c:49-63 (x 2^-15 in, lrintf(clamp(x 2^15)) out).
@@ -110,7 +114,7 @@ static void out_path(char *dst, size_t n, const char *dir, const char *in, const
 
 /* one group of inputs = one batch on one device (the whole command line, or a -devices:N share of it on its own thread);
  * encode: file i is encoded under {RateKbps, AvgComplexity} = setting[i]; autoc[i] = 1: "RATE,auto" (two passes) */
-struct group { int decode, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int bs, isFloat; int rc; };
+struct group { int decode, analyse, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int bs, isFloat; int rc; };
 
 /* "RATE[,AvgComplexity]" or "RATE,auto", validated as ulcEncodeTool.c:43-50 does (and finite: the library refuses the rest) */
 static int parse_rate(const char *s, ulcx_rate *r, int *isAuto) {
@@ -121,6 +125,61 @@ static int parse_rate(const char *s, ulcx_rate *r, int *isAuto) {
     if (!isfinite(r->RateKbps) || !isfinite(r->AvgComplexity) || r->RateKbps == 0.0f || r->AvgComplexity < 0.0f) return -1;
     if (*isAuto && r->RateKbps < 0.0f) return -1;                  /* ABR needs a rate in kbps */
     return 0;
+}
+
+/* The analysis pass over a batch of open inputs: each file's BlockComplexity summed over its own ceil(frames/BS)+2 blocks,
+ * in block order, in double precision (ulcEncodeTool.c:93-98,130,164,178); nSwitched (may be NULL): its blocks whose
+ * WindowCtrl is not the full-size, full-overlap 0x10.  Leaves the encoder's state behind the last block. */
+static int analysis_pass(ulcx_encoder *enc, struct wav *w, int B, int bs, uint32_t maxBlk, float *pcm, void *tmp,
+                         float *cplx, int32_t *wc, double *cplxSum, uint32_t *nSwitched) {
+    const size_t frame = (size_t)bs * w[0].chan;
+    for (uint32_t k0 = 0; k0 < maxBlk; k0 += KBLOCKS) {
+        int K = (maxBlk - k0 < KBLOCKS) ? (int)(maxBlk - k0) : KBLOCKS;
+        for (int s = 0; s < B; s++)
+            wav_read(&w[s], k0 * (uint32_t)bs, (uint32_t)(K * bs), pcm + (size_t)s * K * frame, tmp);
+        if (ulcx_analyse_host(enc, pcm, K, nSwitched ? wc : NULL, cplx) != ULCX_OK) DIE("analysis pass: %s", ulcx_last_error());
+        for (int s = 0; s < B; s++) {
+            uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
+            for (int k = 0; k < K && k0 + (uint32_t)k < nb; k++) {
+                cplxSum[s] += cplx[s * K + k];
+                if (nSwitched && wc[s * K + k] != 0x10) nSwitched[s]++;
+            }
+        }
+    }
+    return 0;
+}
+
+static int analyse_group(const struct group *g) {
+    const int bs = g->bs, B = g->n;
+    struct wav *w = (struct wav *)calloc((size_t)B, sizeof(*w));
+    uint32_t maxBlk = 0;
+    for (int s = 0; s < B; s++) {
+        int e = wav_open(&w[s], g->files[s]);
+        if (e) DIE("cannot read '%s' (error %d: RIFF PCM16 / float32 only)", g->files[s], e);
+        if (w[s].rate != w[0].rate || w[s].chan != w[0].chan) DIE("'%s': all inputs of one call must share rate and channel count", g->files[s]);
+        uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;      /* ulcEncodeTool.c:93-98 */
+        if (nb > maxBlk) maxBlk = nb;
+    }
+    const int C = w[0].chan;
+    ulcx_encoder *enc = NULL;
+    if (ulcx_encoder_create(&enc, g->device, B, C, bs, w[0].rate, KBLOCKS) != ULCX_OK) DIE("encoder: %s", ulcx_last_error());
+    const size_t frame = (size_t)bs * C;
+    float *pcm = (float *)malloc(sizeof(float) * (size_t)B * KBLOCKS * frame);
+    float *cplx = (float *)malloc(sizeof(float) * (size_t)B * KBLOCKS);
+    int32_t *wc = (int32_t *)malloc(sizeof(int32_t) * (size_t)B * KBLOCKS);
+    double *cplxSum = (double *)calloc((size_t)B, sizeof(double));
+    uint32_t *nSw = (uint32_t *)calloc((size_t)B, sizeof(uint32_t));
+    void *tmp = malloc(frame * 4 * KBLOCKS);
+    const int rc = analysis_pass(enc, w, B, bs, maxBlk, pcm, tmp, cplx, wc, cplxSum, nSw);
+    for (int s = 0; s < B && !rc; s++) {
+        uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
+        /* (float): the value "RATE,auto" encodes with, and what `RATE,<complexity>` parses back */
+        printf("%s: %u blocks, avg complexity %.9g, %u window-switched\n", base_name(g->files[s]), nb, (double)(float)(cplxSum[s] / nb), nSw[s]);
+    }
+    for (int s = 0; s < B; s++) fclose(w[s].f);
+    ulcx_encoder_destroy(enc);
+    free(pcm); free(cplx); free(wc); free(cplxSum); free(nSw); free(tmp); free(w);
+    return rc;
 }
 
 static int encode_group(const struct group *g) {
@@ -162,20 +221,11 @@ static int encode_group(const struct group *g) {
     uint32_t *maxb = (uint32_t *)calloc((size_t)B, sizeof(uint32_t));
     char path[1024];
     if (anyAuto) {
-        /* "RATE,auto": pass 1 in VBR (BlockComplexity does not depend on the rate mode; the bytes are dropped) sums each
-         * file's complexity over its own blocks in block order in double precision (ulcEncodeTool.c:130,164,178); after a
+        /* "RATE,auto": pass 1 (analysis only: BlockComplexity does not depend on the rate mode) sums each file's
+         * complexity over its own blocks in block order in double precision (ulcEncodeTool.c:130,164,178); after a
          * reset, pass 2 encodes that file in ABR at (float)(sum / nBlocks) - in CBR if that is 0, as the tool does with RATE,0 */
-        for (int s = 0; s < B; s++) { table[s].RateKbps = -1.0f; table[s].AvgComplexity = 0.0f; }
-        for (uint32_t k0 = 0; k0 < maxBlk; k0 += KBLOCKS) {
-            int K = (maxBlk - k0 < KBLOCKS) ? (int)(maxBlk - k0) : KBLOCKS;
-            for (int s = 0; s < B; s++)
-                wav_read(&w[s], k0 * (uint32_t)bs, (uint32_t)(K * bs), pcm + (size_t)s * K * frame, tmp);
-            if (ulcx_encode_host_rates(enc, table, pcm, K, out, bits, NULL, cplx) != ULCX_OK) DIE("encode (analysis pass): %s", ulcx_last_error());
-            for (int s = 0; s < B; s++) {
-                uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
-                for (int k = 0; k < K && k0 + (uint32_t)k < nb; k++) cplxSum[s] += cplx[s * K + k];
-            }
-        }
+        const int rca = analysis_pass(enc, w, B, bs, maxBlk, pcm, tmp, cplx, NULL, cplxSum, NULL);
+        if (rca) return rca;
         if (ulcx_encoder_reset(enc) != ULCX_OK) DIE("encoder reset: %s", ulcx_last_error());
     }
     for (int s = 0; s < B; s++) {
@@ -306,7 +356,7 @@ static int decode_group(const struct group *g) {
 
 static void *group_main(void *p) {
     struct group *g = (struct group *)p;
-    g->rc = g->decode ? decode_group(g) : encode_group(g);
+    g->rc = g->decode ? decode_group(g) : g->analyse ? analyse_group(g) : encode_group(g);
     return NULL;
 }
 /* the command line's inputs as nDev groups (input i goes to group i % nDev), one host thread and one codec object each */
@@ -315,7 +365,7 @@ static int run_groups(struct group *proto, int nFiles, char **files, int nDev) {
     if (nDev > nFiles) nDev = nFiles;
     const int have = ulcx_device_count();
     if (have < 1) DIE("no HIP device: %s", ulcx_last_error());
-    if (nDev <= 1) { proto->device = 0; proto->n = nFiles; proto->files = files; return proto->decode ? decode_group(proto) : encode_group(proto); }
+    if (nDev <= 1) { proto->device = 0; proto->n = nFiles; proto->files = files; return proto->decode ? decode_group(proto) : proto->analyse ? analyse_group(proto) : encode_group(proto); }
     /* what a single group checks per batch - every input of one call shares rate / channels (encode) or block size /
      * channels / rate (decode) - is checked here ONCE over all files, before they are dealt out: a command line that a
      * one-group run rejects must not be partly accepted with -devices:N */
@@ -350,7 +400,7 @@ static int run_groups(struct group *proto, int nFiles, char **files, int nDev) {
     for (int g = 0; g < nDev; g++) {
         gs[g] = *proto; gs[g].device = g % have; gs[g].files = deal + at; gs[g].setting = dealR + at; gs[g].autoc = dealA + at; gs[g].n = 0; gs[g].rc = 0;
         for (int i = g; i < nFiles; i += nDev) {
-            if (!proto->decode) { dealR[at + gs[g].n] = proto->setting[i]; dealA[at + gs[g].n] = proto->autoc[i]; }
+            if (!proto->decode && !proto->analyse) { dealR[at + gs[g].n] = proto->setting[i]; dealA[at + gs[g].n] = proto->autoc[i]; }
             deal[at + gs[g].n++] = files[i];
         }
         at += gs[g].n;
@@ -396,6 +446,21 @@ static int do_encode(int argc, char **argv) {
     free(files); free(g.setting); free(g.autoc);
     return rc;
 }
+static int do_analyse(int argc, char **argv) {
+    if (argc < 3) DIE("usage: ulcx-tool analyse [-blocksize:N] [-devices:N] IN.wav ...");
+    struct group g; memset(&g, 0, sizeof(g));
+    g.analyse = 1; g.bs = 2048;
+    int a = 2, nDev = 1;
+    for (; a < argc && argv[a][0] == '-'; a++) {
+        if (!strcmp(argv[a], "--")) { a++; break; }
+        if (!strncmp(argv[a], "-blocksize:", 11)) g.bs = atoi(argv[a] + 11);
+        else if (!strncmp(argv[a], "-devices:", 9)) nDev = atoi(argv[a] + 9);
+        else DIE("unknown option '%s'", argv[a]);
+    }
+    if (g.bs < 256 || g.bs > 8192 || (g.bs & -g.bs) != g.bs) DIE("unsupported block size %d", g.bs);
+    if (nDev < 1 || nDev > 64) DIE("-devices:%d out of range", nDev);
+    return run_groups(&g, argc - a, argv + a, nDev);
+}
 static int do_decode(int argc, char **argv) {
     if (argc < 4) DIE("usage: ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N] IN.ulc ...");
     struct group g; memset(&g, 0, sizeof(g));
@@ -417,6 +482,7 @@ static int do_decode(int argc, char **argv) {
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "encode")) return do_encode(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "decode")) return do_decode(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "analyse")) return do_analyse(argc, argv);
     fprintf(stderr,
             "ulcx-tool - batched ulc-codec front-end over libulc_amd.so (MI355X)\n"
             "  ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav [-rate:RATE[,...]] IN2.wav ...\n"
@@ -424,6 +490,8 @@ int main(int argc, char **argv) {
             "      RATE,auto: two-pass ABR at each file's own average complexity (0: CBR)\n"
             "      -rate:RATE[,AvgComplexity|,auto]  setting of the inputs that follow it (RATE is the default)\n"
             "  ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N] IN1.ulc IN2.ulc ...\n"
+            "  ulcx-tool analyse [-blocksize:N] [-devices:N] IN1.wav IN2.wav ...\n"
+            "      per file: blocks, the average complexity to feed RATE,<complexity> with, window-switched blocks; writes no file\n"
             "  --          end of options (input names that start with '-')\n"
             "  -devices:N  inputs dealt round-robin over N groups, one host thread + one codec object each (device g %% visible)\n");
     return 1;

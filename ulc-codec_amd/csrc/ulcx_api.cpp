@@ -25,6 +25,8 @@ struct ulcx_encoder {
     bool keysFinal;
     int wcSteps, wcFuse;      // environment switches, read once at create
     int nsSlots;              // resident workgroups of k_nsums (its persistent grid)
+    bool lastAnalyse;         // the last call was an analysis call: no intermediates, no exact-path count to report
+    int analyseKxf;           // ULCX_ANALYSE_KXF=1: analysis calls run the encode call's transform (timing comparisons)
     // staging for the host-pointer API
     float *d_pcm; uint8_t *d_out; int32_t *d_bits, *d_wc; float *d_cplx;
     ulcx_rate *d_rate;        // [B] the per-stream table of ulcx_encode_host_rates
@@ -140,7 +142,7 @@ extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams,
     if (rc) return rc;
     ulcx_encoder *e = new ulcx_encoder();
     e->device = device; e->B = nStreams; e->C = nChan; e->BS = BlockSize; e->rate = RateHz; e->maxK = maxBlocksPerCall;
-    e->tables = nullptr; e->evOk = false; e->evRecorded = false; e->timing = true; e->lastK = 0; e->sideOk = false; e->side = nullptr; e->keysFinal = false;
+    e->tables = nullptr; e->evOk = false; e->evRecorded = false; e->timing = true; e->lastK = 0; e->lastAnalyse = false; e->analyseKxf = 0; e->sideOk = false; e->side = nullptr; e->keysFinal = false;
     e->d_pcm = nullptr; e->d_out = nullptr; e->d_bits = nullptr; e->d_wc = nullptr; e->d_cplx = nullptr; e->d_rate = nullptr;
     e->b1Init = e->b1Graphed = e->b1NoGraph = false; e->b1Stream = nullptr; e->b1Rekeys = 0; e->pinIn = nullptr; e->pinOut = nullptr; e->pinMeta = nullptr;
     UlcxEncCtx &c = e->ctx;
@@ -241,6 +243,7 @@ extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams,
         e->wcSteps = -1; if (const char *sv = getenv("ULCX_WC_STEPS")) e->wcSteps = atoi(sv);      // -1: default; 0: the transform's chunks
         e->wcFuse = 1;                                           // (stereo: k_wc_ef; every other channel count: k_wc_energy + k_wc_forward)
     }
+    if (const char *av = getenv("ULCX_ANALYSE_KXF")) e->analyseKxf = (av[0] == '1');
     e->nsSlots = c.useGapSums ? ulcx_enc_nsums_slots(BlockSize, nChan) : 0;
     if (e->nsSlots <= 0) e->nsSlots = 1024;
     DA(c.isFb, NB, true);
@@ -299,7 +302,65 @@ static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const u
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     e->lastK = nBlocks;
     e->keysFinal = false;
+    e->lastAnalyse = false;
     return rc;
+}
+
+// ---- analysis only (include/ulc_amd.h): window control, MDCT, block complexity, next-call state
+static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!e || (!d_pcm && !d_pcm16) || (!d_wc && !d_cplx) || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_analyse_dev: bad argument"); return ULCX_ERR_ARG; }
+    CKR(hipSetDevice(e->device));
+    UlcxEncCtx c = e->ctx;
+    c.K = nBlocks; c.keyFinal = 0; c.mode = ULCX_MODE_VBR; c.p0 = 100.0f; c.p1 = 0.0f; c.vbrTarget = 0.0f; c.rates = nullptr;
+    c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = nullptr; c.bits = nullptr; c.wcOut = d_wc; c.cplxOut = d_cplx;
+    UlcxEncAux aux;
+    aux.side = e->sideOk ? e->side : nullptr; aux.side2 = e->sideOk ? e->side2 : nullptr; aux.side3 = e->sideOk ? e->side3 : nullptr;
+    aux.evFork = e->evFork; aux.evJoin = e->evJoin; aux.evFork2 = e->evFork2; aux.evWC = e->evWC; aux.evXf = e->evXf;
+    aux.wcPipe = (nBlocks >= 2 * e->wcPipe) ? e->wcPipe : (nBlocks >= 6 && e->wcPipe > 1 ? 3 : 1); aux.nXf = &e->nXf;      // (the encode call's chunking)
+    aux.wcSteps = e->wcSteps; aux.wcFuse = e->wcFuse; aux.nsSlots = e->nsSlots;
+    const int rc = ulcx_analyse_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux, e->analyseKxf);
+    e->evRecorded = (rc == ULCX_OK) && e->timing;
+    e->lastK = nBlocks;
+    e->keysFinal = false;
+    e->lastAnalyse = true;
+    return rc;
+}
+extern "C" int ulcx_analyse_dev(ulcx_encoder *e, const float *d_pcm, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!d_pcm) { ulcx_set_error("ulcx_analyse_dev: bad argument"); return ULCX_ERR_ARG; }
+    return analyse_dev_any(e, d_pcm, nullptr, nBlocks, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_analyse_dev_pcm16(ulcx_encoder *e, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!d_pcm16) { ulcx_set_error("ulcx_analyse_dev_pcm16: bad argument"); return ULCX_ERR_ARG; }
+    return analyse_dev_any(e, nullptr, d_pcm16, nBlocks, d_wc, d_cplx, hipStream);
+}
+
+// device staging of the host-pointer entries: input, window codes, complexities; withOut: output slots and sizes too (an
+// encoder that only ever analyses never allocates those)
+static int host_staging(ulcx_encoder *e, size_t nBlk, bool withOut) {
+    const size_t cb = (size_t)e->C * e->BS;
+    int rc;
+    if (!e->d_pcm && (rc = dalloc(e->allocs, &e->d_pcm, nBlk * cb, false))) return rc;
+    if (!e->d_wc && (rc = dalloc(e->allocs, &e->d_wc, nBlk, false))) return rc;
+    if (!e->d_cplx && (rc = dalloc(e->allocs, &e->d_cplx, nBlk, false))) return rc;
+    if (withOut && !e->d_out && (rc = dalloc(e->allocs, &e->d_out, nBlk * e->ctx.slot, false))) return rc;
+    if (withOut && !e->d_bits && (rc = dalloc(e->allocs, &e->d_bits, nBlk, false))) return rc;
+    return ULCX_OK;
+}
+
+extern "C" int ulcx_analyse_host(ulcx_encoder *e, const float *h_pcm, int nBlocks, int32_t *h_wc, float *h_cplx) {
+    if (!e || !h_pcm || (!h_wc && !h_cplx)) { ulcx_set_error("ulcx_analyse_host: bad argument"); return ULCX_ERR_ARG; }
+    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
+    CKR(hipSetDevice(e->device));
+    int rc = host_staging(e, (size_t)e->B * e->maxK, false);
+    if (rc) return rc;
+    const size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
+    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
+    rc = ulcx_analyse_dev(e, e->d_pcm, nBlocks, h_wc ? e->d_wc : nullptr, h_cplx ? e->d_cplx : nullptr, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
 }
 
 extern "C" int ulcx_encode_dev(ulcx_encoder *e, int mode, float p0, float p1, const float *d_pcm, int nBlocks,
@@ -336,14 +397,7 @@ extern "C" int ulcx_encode_host_rates(ulcx_encoder *e, const ulcx_rate *h_rate, 
     }
     CKR(hipSetDevice(e->device));
     size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS;
-    if (!e->d_pcm) {
-        int rc;
-        if ((rc = dalloc(e->allocs, &e->d_pcm, NBmax * cb, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_out, NBmax * e->ctx.slot, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_bits, NBmax, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_wc, NBmax, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_cplx, NBmax, false))) return rc;
-    }
+    { int rc = host_staging(e, NBmax, true); if (rc) return rc; }
     if (!e->d_rate) { int rc = dalloc(e->allocs, &e->d_rate, (size_t)e->B, false); if (rc) return rc; }
     size_t NB = (size_t)e->B * nBlocks;
     CKR(hipMemcpy(e->d_rate, h_rate, sizeof(ulcx_rate) * (size_t)e->B, hipMemcpyHostToDevice));
@@ -363,14 +417,7 @@ extern "C" int ulcx_encode_host(ulcx_encoder *e, int mode, float p0, float p1, c
     if (!e || !h_pcm || !h_out || !h_bits) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS;
-    if (!e->d_pcm) {
-        int rc;
-        if ((rc = dalloc(e->allocs, &e->d_pcm, NBmax * cb, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_out, NBmax * e->ctx.slot, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_bits, NBmax, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_wc, NBmax, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_cplx, NBmax, false))) return rc;
-    }
+    { int rc = host_staging(e, NBmax, true); if (rc) return rc; }
     if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
     size_t NB = (size_t)e->B * nBlocks;
     CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
@@ -394,13 +441,7 @@ extern "C" int ulcx_encode_block1(ulcx_encoder *e, int mode, float p0, float p1,
     const size_t cb = (size_t)e->C * e->BS, slot = (size_t)e->ctx.slot;
     if (!e->b1Init) {
         int rc;
-        if (!e->d_pcm) {
-            if ((rc = dalloc(e->allocs, &e->d_pcm, cb, false))) return rc;
-            if ((rc = dalloc(e->allocs, &e->d_out, slot, false))) return rc;
-            if ((rc = dalloc(e->allocs, &e->d_bits, 1, false))) return rc;
-            if ((rc = dalloc(e->allocs, &e->d_wc, 1, false))) return rc;
-            if ((rc = dalloc(e->allocs, &e->d_cplx, 1, false))) return rc;
-        }
+        if ((rc = host_staging(e, 1, true))) return rc;                // (one stream, one block per call)
         // (b1Init only once everything exists: a failed allocation leaves the call to be retried from scratch, never a
         //  later call copying into a null staging buffer)
         if (!e->b1Stream) CKR(hipStreamCreateWithFlags(&e->b1Stream, hipStreamNonBlocking));
@@ -455,6 +496,7 @@ extern "C" int ulcx_encode_block1(ulcx_encoder *e, int mode, float p0, float p1,
 
 extern "C" int ulcx_encoder_debug_fetch(ulcx_encoder *e, int nBlocks, float *h_coef, float *h_noise, float *h_keys, uint8_t *h_keep, int32_t *h_nout) {
     if (!e || nBlocks < 1 || nBlocks > e->maxK) return ULCX_ERR_ARG;
+    if (e->lastAnalyse) { ulcx_set_error("ulcx_encoder_debug_fetch: the last call was an analysis call (no intermediates)"); return ULCX_ERR_ARG; }
     CKR(hipSetDevice(e->device));
     CKR(hipDeviceSynchronize());
     size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
@@ -492,6 +534,7 @@ extern "C" int ulcx_encoder_debug_force_exact(ulcx_encoder *e, int every) {
 }
 extern "C" int ulcx_encoder_last_fallbacks(ulcx_encoder *e) {
     if (!e) return ULCX_ERR_ARG;
+    if (e->lastAnalyse) return 0;                                      // (an analysis call selects nothing)
     CKR(hipSetDevice(e->device));
     CKR(hipDeviceSynchronize());
     int n = 0;
@@ -505,7 +548,7 @@ extern "C" int ulcx_encoder_stage_ms(ulcx_encoder *e, float *ms, int maxStages) 
     for (int i = 0; i < ULCX_ENC_STAGES && i < maxStages; i++) {
         float t = 0;
         if (hipEventElapsedTime(&t, e->ev[i], e->ev[i + 1]) != hipSuccess) break;
-        ms[n++] = t;
+        ms[n++] = (e->lastAnalyse && i > 6 && i < ULCX_ENC_STAGES - 1) ? 0.0f : t;        // (an analysis call: the back half did not run)
     }
     // Pipelined window control: the k_xf interval spans start-up + waits + the transform chunk launches.
     // Report the launches themselves as k_xf (what a kernel trace shows) and the rest as "wc_pipeline_exposed".

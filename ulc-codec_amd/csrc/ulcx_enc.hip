@@ -33,6 +33,13 @@ size_t ulcx_enc_xf_lds_bytes(int BS, int C) {
     return full <= ULCX_LDS_LIMIT ? full : z + (size_t)BS * 2 + 32;   // (C > 2 at BlockSize 8192: twiddles stay in global memory)
 }
 
+// the analysis call's transform: the two MDCT arrays + BS/4 twiddles (+ the counter's slot, unused)
+size_t ulcx_enc_xfa_lds_bytes(int BS, int C) {
+    if (BS > 8192) return (size_t)BS * 4;                       // k_xfa_big: as k_xf_big
+    int ps = ulcx_xf_pad_shift(BS, C);
+    return (size_t)2 * (BS + (BS >> ps)) * 4 + (size_t)BS * 2 + 32;
+}
+
 // launch the input-reading kernels for the call's sample type (float | PCM16)
 static void launch_wc_energy(const UlcxEncCtx &c, unsigned grid, hipStream_t st, int k0, int k1) {
     if (c.pcm16) hipLaunchKernelGGL(k_wc_energy<int16_t>, dim3(grid), dim3(WG), 0, st, c, k0, k1);
@@ -60,6 +67,21 @@ static void launch_xf(const UlcxEncCtx &c, unsigned grid, size_t lds, hipStream_
     }
 }
 
+static void launch_xfa(const UlcxEncCtx &c, unsigned grid, size_t lds, hipStream_t st, int k0, int k1) {
+    if (c.BS > 8192) {
+        if (c.pcm16) hipLaunchKernelGGL(k_xfa_big<int16_t>, dim3(grid), dim3(WG), lds, st, c, k0, k1);
+        else hipLaunchKernelGGL(k_xfa_big<float>, dim3(grid), dim3(WG), lds, st, c, k0, k1);
+        return;
+    }
+    if (c.pcm16) {
+        if (c.C == 2) hipLaunchKernelGGL((k_xfa<true, int16_t>), dim3(grid), dim3(WG), lds, st, c, k0, k1);
+        else hipLaunchKernelGGL((k_xfa<false, int16_t>), dim3(grid), dim3(WG), lds, st, c, k0, k1);
+    } else {
+        if (c.C == 2) hipLaunchKernelGGL((k_xfa<true, float>), dim3(grid), dim3(WG), lds, st, c, k0, k1);
+        else hipLaunchKernelGGL((k_xfa<false, float>), dim3(grid), dim3(WG), lds, st, c, k0, k1);
+    }
+}
+
 static void launch_state_update(const UlcxEncCtx &c, hipStream_t st) {
     if (c.pcm16) hipLaunchKernelGGL(k_state_update<int16_t>, dim3(c.B), dim3(WG), 0, st, c);
     else hipLaunchKernelGGL(k_state_update<float>, dim3(c.B), dim3(WG), 0, st, c);
@@ -75,22 +97,23 @@ const char *const ulcx_enc_stage_names[ULCX_ENC_STAGES_REPORTED] = {
     "k_select", "k_nbark", "(k_nline: gone)", "k_heapsel", "k_nsums", "k_tails", "k_encode_wave", "k_encode_units", "k_pack", "cbr_probe_passes", "k_state_update", "wc_pipeline_exposed",
 };
 
-int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux) {
-    UlcxEncCtx c = cIn;                                        // (keyFinal is set below for geometries without a wave selection kernel)
-    hipStream_t side = aux.side, side2 = aux.side2, side3 = aux.side3;
-    hipEvent_t evFork = aux.evFork, evJoin = aux.evJoin, evFork2 = aux.evFork2, *evWC = aux.evWC;
-    const int wcPipe = (side && side2 && side3) ? aux.wcPipe : 1;
-    if (aux.nXf) *aux.nXf = 0;
-    // per-stream rates (c.rates): the host does not know the table, so such a call runs the rate search's launch sequence
-    // whatever it holds (VBR blocks skip every probe on the device)
-    const bool search = c.mode != ULCX_MODE_VBR || c.rates != nullptr;
-    if (search) CK(hipMemsetAsync(c.cbrLive, 0, sizeof(int), st));
-    if (c.barkRing) CK(hipMemsetAsync(c.decCount, 0, sizeof(int), st));           // k_xf lists this call's decimated blocks
-    int NB = c.B * c.K;
-    int stage = 0;
 #define MARK() do { if (ev) CK(hipEventRecord(ev[stage++], st)); } while (0)
-    MARK();
-    // --- window control + transform
+
+// The front half of a call: the window-control pipeline beside the transform chunks and the chunks' ordered sums.
+// what: the encode call's kernels (k_xf, k_cplx), the analysis call's (k_xfa, k_cplxa), the analysis call on the encode
+// call's transform (k_xf, k_cplxa: the plain launch subset, for timing comparisons) or window control alone with k_cplxa
+// behind it to write the window codes out (an analysis call that asks for nothing else).
+enum { ULCX_FRONT_ENCODE = 0, ULCX_FRONT_ANALYSE = 1, ULCX_FRONT_ANALYSE_KXF = 2, ULCX_FRONT_WC_ONLY = 3 };
+static int launch_front(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev, int &stage, const UlcxEncAux &aux, const int wcPipe, const int what) {
+    hipStream_t side = aux.side, side2 = aux.side2, side3 = aux.side3;
+    hipEvent_t *evWC = aux.evWC;
+    const int NB = c.B * c.K;
+    const bool slim = (what == ULCX_FRONT_ANALYSE || what == ULCX_FRONT_WC_ONLY);     // the MDCT-only transform's LDS
+    auto launch_tr = [&](unsigned grid, size_t lds, hipStream_t s2, int k0, int k1) {
+        if (what == ULCX_FRONT_WC_ONLY) return;
+        if (what == ULCX_FRONT_ANALYSE) launch_xfa(c, grid, lds, s2, k0, k1);
+        else launch_xf(c, grid, lds, s2, k0, k1);
+    };
     hipEvent_t *evX = evWC + 7 + 3 * ULCX_WC_MAXCH;            // [ULCX_XF_MAXCH] transform chunk done, [ULCX_XF_MAXCH]: all early k_cplx launches done
     const bool cplxEarly = wcPipe > 1;                        // the ordered complexity sums per transform chunk, beside the next chunk
     {
@@ -99,8 +122,15 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
         // hundred waves: latency-bound, nearly no machine resources) run on the side stream beside the
         // transform of chunk j on the main stream.  wcPipe = 1 keeps everything on the main stream.
         const int nCh = wcPipe;
-        size_t lds = ulcx_enc_xf_lds_bytes(c.BS, c.C);
-        if (lds > 48 * 1024) {
+        size_t lds = slim ? ulcx_enc_xfa_lds_bytes(c.BS, c.C) : ulcx_enc_xf_lds_bytes(c.BS, c.C);
+        if (slim && lds > 48 * 1024) {
+            CK(hipFuncSetAttribute((const void *)k_xfa<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            CK(hipFuncSetAttribute((const void *)k_xfa<false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            CK(hipFuncSetAttribute((const void *)k_xfa<true, int16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            CK(hipFuncSetAttribute((const void *)k_xfa<false, int16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            CK(hipFuncSetAttribute((const void *)k_xfa_big<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            CK(hipFuncSetAttribute((const void *)k_xfa_big<int16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        } else if (lds > 48 * 1024) {
             CK(hipFuncSetAttribute((const void *)k_xf<true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             CK(hipFuncSetAttribute((const void *)k_xf<false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             CK(hipFuncSetAttribute((const void *)k_xf<true, int16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -123,7 +153,7 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
         };
         if (nCh <= 1) {
             int rc = launch_wc(st, 0, c.K, true); if (rc) return rc;
-            launch_xf(c, ((NB + 7) / 8) * 8, lds, st, 0, c.K);
+            launch_tr(((NB + 7) / 8) * 8, lds, st, 0, c.K);
             MARK();
         } else {
             for (int i = 0; i < 5; i++) MARK();                    // (window-control stages: hidden in the k_xf interval in this mode)
@@ -173,7 +203,7 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
                     CK(hipStreamWaitEvent(st, evD[w], 0));
                     if (ev) CK(hipEventRecord(aux.evXf[2 * jx], st));
                     if (!(ULCX_DBG(c) & 0x2000))               // (ablation build: window control alone)
-                    launch_xf(c, ((nbk + 7) / 8) * 8, lds, st, x0, x1);
+                    launch_tr(((nbk + 7) / 8) * 8, lds, st, x0, x1);
                     if (ev) CK(hipEventRecord(aux.evXf[2 * jx + 1], st));
                     if (cplxEarly) CK(hipEventRecord(evX[jx], st));
                     jx++;
@@ -187,12 +217,34 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
                 for (int j = 0; j < nCh; j++) {
                     CK(hipStreamWaitEvent(side, evX[j], 0));
                     const int kc2 = cut[j + 1] - cut[j];
-                    hipLaunchKernelGGL(k_cplx, dim3((c.B * kc2 + 63) / 64), dim3(64), 0, side, c, cut[j], cut[j + 1]);
+                    if (what == ULCX_FRONT_ENCODE) hipLaunchKernelGGL(k_cplx, dim3((c.B * kc2 + 63) / 64), dim3(64), 0, side, c, cut[j], cut[j + 1]);
+                    else hipLaunchKernelGGL(k_cplxa, dim3((c.B * kc2 + 63) / 64), dim3(64), 0, side, c, cut[j], cut[j + 1]);
                 }
                 CK(hipEventRecord(evX[ULCX_XF_MAXCH], side));
             }
         }
     }
+    return ULCX_OK;
+}
+
+int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux) {
+    UlcxEncCtx c = cIn;                                        // (keyFinal is set below for geometries without a wave selection kernel)
+    hipStream_t side = aux.side, side2 = aux.side2, side3 = aux.side3;
+    hipEvent_t evFork = aux.evFork, evJoin = aux.evJoin, evFork2 = aux.evFork2, *evWC = aux.evWC;
+    const int wcPipe = (side && side2 && side3) ? aux.wcPipe : 1;
+    if (aux.nXf) *aux.nXf = 0;
+    // per-stream rates (c.rates): the host does not know the table, so such a call runs the rate search's launch sequence
+    // whatever it holds (VBR blocks skip every probe on the device)
+    const bool search = c.mode != ULCX_MODE_VBR || c.rates != nullptr;
+    if (search) CK(hipMemsetAsync(c.cbrLive, 0, sizeof(int), st));
+    if (c.barkRing) CK(hipMemsetAsync(c.decCount, 0, sizeof(int), st));           // k_xf lists this call's decimated blocks
+    int NB = c.B * c.K;
+    int stage = 0;
+    MARK();
+    // --- window control + transform
+    { int rcf = launch_front(c, st, ev, stage, aux, wcPipe, ULCX_FRONT_ENCODE); if (rcf) return rcf; }
+    hipEvent_t *evX = evWC + 7 + 3 * ULCX_WC_MAXCH;
+    const bool cplxEarly = wcPipe > 1;
     if (ULCX_DBG(c) & 0x6000) { MARK(); return ULCX_OK; }     // (ablation build: stop behind window control / transform)
     int nUnits = NB * c.C * 4;
     // (the noise log-spectrum does not feed the keys: it is launched after the selection so that the
@@ -476,6 +528,32 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     MARK();   // cbr_probe_passes (empty interval for VBR)
     if (noiseAside) { CK(hipStreamWaitEvent(st, evState, 0));                                               MARK(); }
     else { launch_state_update(c, st);                              MARK(); }
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+
+// The analysis call (ulcx_analyse_dev): the front half of an encode call - window control in the same steps over the same side
+// streams, then per transform chunk the MDCT-only transform and the chunk's ordered sums beside the next chunk - and the
+// state for the next call.  No Bark sums, selection, noise sums, tails or writer, no counter of the encode call is touched.
+// Every side stream is joined back into st: side through the sums' event, side2 and side3 through the last decide step the
+// last transform chunk waits for.
+int ulcx_analyse_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux, int useKxf) {
+    hipEvent_t *evWC = aux.evWC;
+    const int wcPipe = (aux.side && aux.side2 && aux.side3) ? aux.wcPipe : 1;
+    if (aux.nXf) *aux.nXf = 0;
+    const int what = !c.cplxOut ? ULCX_FRONT_WC_ONLY : useKxf ? ULCX_FRONT_ANALYSE_KXF : ULCX_FRONT_ANALYSE;
+    if (what == ULCX_FRONT_ANALYSE_KXF && c.barkRing) CK(hipMemsetAsync(c.decCount, 0, sizeof(int), st));   // (k_xf lists the decimated blocks)
+    const int NB = c.B * c.K;
+    int stage = 0;
+    MARK();
+    { int rcf = launch_front(c, st, ev, stage, aux, wcPipe, what); if (rcf) return rcf; }
+    hipEvent_t *evX = evWC + 7 + 3 * ULCX_WC_MAXCH;
+    if (wcPipe > 1) CK(hipStreamWaitEvent(st, evX[ULCX_XF_MAXCH], 0));          // the chunks' sums (on the first side stream)
+    else hipLaunchKernelGGL(k_cplxa, dim3((NB + 63) / 64), dim3(64), 0, st, c, 0, c.K);
+    MARK();                                                    // k_cplx
+    if (ev) while (stage < ULCX_ENC_STAGES) MARK();            // (the back half: empty intervals)
+    launch_state_update(c, st);
+    MARK();
     CK(hipGetLastError());
     return ULCX_OK;
 }

@@ -1,6 +1,6 @@
 // ulcx_enc_dev.h - what the encoder's translation units share (round 5: ulcx_enc.hip split by phase): device helpers, the
 // LDS geometry macros the host-side launch code needs too, and the declarations of every kernel (the launch sequence in
-// ulcx_enc.hip starts kernels defined in ulcx_enc_wc.hip / ulcx_enc_xf.hip / ulcx_enc_psy.hip / ulcx_enc_wr.hip; template kernels are
+// ulcx_enc.hip starts kernels defined in ulcx_enc_wc.hip / ulcx_enc_xf.hip (+ ulcx_enc_xfa.hip) / ulcx_enc_psy.hip / ulcx_enc_wr.hip; template kernels are
 // instantiated explicitly where they are defined).  Not part of the public ABI.
 #pragma once
 #include <utility>
@@ -476,6 +476,21 @@ __global__ __launch_bounds__(WG) void k_xf_big(UlcxEncCtx c, int k0, int k1);
 extern template __global__ void k_xf_big<float>(UlcxEncCtx, int, int);
 extern template __global__ void k_xf_big<int16_t>(UlcxEncCtx, int, int);
 __global__ void k_cplx(UlcxEncCtx c, int k0, int k1);
+// the analysis call (ulcx_analyse_launch): MDCT-only transform, sums without rate logic
+#ifndef XFA_LB
+#define XFA_LB 4
+#endif
+template <bool ST, typename IN>
+__global__ __launch_bounds__(WG, XFA_LB) void k_xfa(UlcxEncCtx c, int k0, int k1);
+extern template __global__ void k_xfa<false, float>(UlcxEncCtx, int, int);
+extern template __global__ void k_xfa<false, int16_t>(UlcxEncCtx, int, int);
+extern template __global__ void k_xfa<true, float>(UlcxEncCtx, int, int);
+extern template __global__ void k_xfa<true, int16_t>(UlcxEncCtx, int, int);
+template <typename IN>
+__global__ __launch_bounds__(WG) void k_xfa_big(UlcxEncCtx c, int k0, int k1);
+extern template __global__ void k_xfa_big<float>(UlcxEncCtx, int, int);
+extern template __global__ void k_xfa_big<int16_t>(UlcxEncCtx, int, int);
+__global__ void k_cplxa(UlcxEncCtx c, int k0, int k1);
 __global__ void k_nbark(UlcxEncCtx c, int useList);
 __global__ void k_nline(UlcxEncCtx c);
 __global__ void k_pbark(UlcxEncCtx c, int useList);

@@ -1,6 +1,9 @@
 // ulcx_enc_xf.hip - transform and analysis (libulc/ulcEncoder_BlockTransform.c:95-356): TDAC fold, MDCT + MDST, line energies, block complexity; next-call state
 // (one of the encoder's translation units; shared device code and every kernel's declaration: ulcx_enc_dev.h; the launch
 // sequence: ulcx_enc.hip.)  Compiled with -ffp-contract=off like every file of the library.
+// The analysis call's kernels (k_xfa, k_xfa_big, k_cplxa: the AN = true instantiations of the bodies below) are compiled from
+// this file as a translation unit of their own, ulcx_enc_xfa.hip (ULCX_XF_ANALYSIS_UNIT): instantiated beside k_xf they
+// change the code the compiler makes of k_xf<true, ...> (same registers, another schedule of the transform passes).
 #include "ulcx_enc_dev.h"
 
 // ---------------------------------------------------------------------------
@@ -28,15 +31,17 @@ __device__ __forceinline__ float win_apply(float x, int i, int S, int aL, int ov
 // order as the general body of k_xf below (which documents it) - only the index arithmetic, the loop bounds and the window
 // selects fold away, and the four transforms run the compile-time passes (fft_wave_dif_ct).
 // (BSC: 2048, the headline geometry; 4096 since round 4 - the window-switching configuration's un-decimated blocks)
-template <typename IN, int BSC>
+// AN (the analysis call, k_xfa): the MDCT alone - the two zc arrays side by side, no MDST arrays, fold products, transforms or
+// post-twiddle, no line energies, no non-zero count; what is left is the very arithmetic of the encode instantiation.
+template <typename IN, int BSC, bool AN = false>
 __device__ __forceinline__ int xf_fast(const UlcxEncCtx &c, float *lds, int s, int k, int blk, int tid) {
     constexpr int BS = BSC, S = BSC, M = BSC / 2, PS = 4, Mp = FFT_PADDEDS(M, PS);
     constexpr int LGM = BSC == 4096 ? 11 : 10;
     static_assert(BSC == 2048 || BSC == 4096, "sizes with a compile-time transform");
     static_assert(WG == 256 && (M / 2) % (2 * WG) == 0, "whole fold / epilogue trips per thread");
     float2 *z = (float2 *)lds;
-    float2 *twl = (float2 *)(lds + 4 * FFT_PADDEDS(BS, PS));
-    float2 *zc0 = z, *zs0 = z + Mp, *zc1 = z + 2 * Mp, *zs1 = z + 3 * Mp;
+    float2 *twl = (float2 *)(lds + (AN ? 2 : 4) * FFT_PADDEDS(BS, PS));
+    float2 *zc0 = z, *zs0 = z + Mp, *zc1 = z + (AN ? 1 : 2) * Mp, *zs1 = z + 3 * Mp;
     const float2 *pre = c.T.pre[0];
     const float *rise = c.T.winRise + S, *fall = c.T.winFall + S;
     // frame = [(k-2) BS, k BS): its first half (positions < S) is block k-2, its second half block k-1 of the stream's
@@ -80,16 +85,52 @@ __device__ __forceinline__ int xf_fast(const UlcxEncCtx &c, float *lds, int s, i
                 const float w1 = hsel ? wl : wr, w2 = hsel ? wr : wl;
                 float2 *zc = q ? zc1 : zc0, *zs = q ? zs1 : zs0;
                 zc[FFT_PADS(n, PS)] = cmulc(make_float2(v1, v2), P);
-                zs[FFT_PADS(n, PS)] = cmulc(make_float2(w2, w1), P);
+                if constexpr (!AN) zs[FFT_PADS(n, PS)] = cmulc(make_float2(w2, w1), P);
             }
         }
     }
     __syncthreads();
-    fft_wave_dif_ct<M, PS>(z + __builtin_amdgcn_readfirstlane(tid >> 6) * Mp, twl, tid & 63);
+    if constexpr (AN) { if (tid < 128) fft_wave_dif_ct<M, PS>(z + __builtin_amdgcn_readfirstlane(tid >> 6) * Mp, twl, tid & 63); }     // (two arrays: two waves)
+    else fft_wave_dif_ct<M, PS>(z + __builtin_amdgcn_readfirstlane(tid >> 6) * Mp, twl, tid & 63);
     __syncthreads();
     float *coefO = c.coef + (size_t)blk * (2 * BS);
     constexpr float norm = 2.0f / S;
     int nnz = 0;
+    if constexpr (AN) {
+        // the MDCT half of the epilogue below: same indices, same products, the same 16-byte stores of the coefficients
+#pragma unroll
+        for (int e0 = 0; e0 < M / 2; e0 += 2 * WG) {
+            const int kA = e0 + 2 * tid, kB = e0 + 2 * tid + 1;
+            const int kk2[2] = { kA, kB };
+            float re[2][2][4];
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const int k1 = kk2[u], k2 = M - 1 - k1;
+                const int r1 = (int)(__brev((unsigned)k1) >> (32 - LGM)), r2 = (int)(__brev((unsigned)k2) >> (32 - LGM));
+                const float2 P1 = pre[k1], P2 = pre[k2];
+                const fft_v2f Pv1 = { P1.x, P1.y }, Pv2 = { P2.x, P2.y };
+#pragma unroll
+                for (int q = 0; q < 2; q++) {
+                    const float2 *zc = q ? zc1 : zc0;
+                    auto cm = [](float2 d, fft_v2f w) { const fft_v2f dv = { d.x, d.y }; const fft_v2f r = fft_cmulc_post_pk(dv, w); return make_float2(r.x, r.y); };
+                    const float2 yc1 = cm(zc[FFT_PADS(r1, PS)], Pv1), yc2 = cm(zc[FFT_PADS(r2, PS)], Pv2);
+                    const float mdct[4] = { yc1.x, yc2.y, yc2.x, yc1.y };
+#pragma unroll
+                    for (int p = 0; p < 2; p++) {
+                        const int slot = p ? (1 - u) : u;
+                        re[q][p][2 * slot] = mdct[2*p] * norm; re[q][p][2 * slot + 1] = mdct[2*p+1] * norm;
+                    }
+                }
+            }
+            const int j1 = kA, j2 = M - 1 - kB;
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                stnt((float4 *)(coefO + q * BS + 2 * j1), make_float4(re[q][0][0], re[q][0][1], re[q][0][2], re[q][0][3]));
+                stnt((float4 *)(coefO + q * BS + 2 * j2), make_float4(re[q][1][0], re[q][1][1], re[q][1][2], re[q][1][3]));
+            }
+        }
+        return 0;
+    }
     // A thread takes TWO neighbouring post-twiddle indices (kk = 2 tid, 2 tid + 1: M/2 = 2 WG of them), so that what it
     // writes is contiguous: coefficients 4 tid .. 4 tid + 3 and BS - 4 - 4 tid .. BS - 1 - 4 tid of each channel as 16-byte
     // stores, line energies as 8-byte stores (one index per thread gave 8- and 4-byte stores: twice the store instructions).
@@ -165,23 +206,25 @@ __device__ __forceinline__ bool xf_is_fast(const UlcxEncCtx &c, int s, int k) {
 
 // One block (s, k) of the call by one workgroup: any window, any channel count up to BlockSize 8192.
 // ST: stereo instantiation (C = 2 as a compile-time constant: one channel pair, no per-pair branches)
-template <bool ST, typename IN>
+// AN: the analysis call's instantiation (k_xfa) - as in xf_fast, the MDCT arrays and coefficients only
+template <bool ST, typename IN, bool AN = false>
 __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s, int k, const int tid) {
     const int BS = c.BS, C = ST ? 2 : c.C;
     const int blk = s * c.K + k;
     const int ps = ulcx_xf_pad_shift(BS, C);          // FFT array padding (ulcx_fft.h)
     float2 *z    = (float2 *)lds;                     // 4 arrays of up to BS/2 complex: {MDCT, MDST} x {ch, ch+1}
-    float2 *twl  = (float2 *)(lds + 4 * FFT_PADDEDS(BS, ps));    // BS/4 complex: this subblock's FFT twiddles (no global-memory latency inside the FFT passes)
-    int    &s_nnz = *(int *)(lds + 4 * FFT_PADDEDS(BS, ps) + BS / 2);  // (inside the dynamic region: no static LDS in front of it)
-    const bool ampLds = (C > 2);                             // line energies accumulate across channel pairs: only then in LDS
+    constexpr int NA = AN ? 2 : 4;                    // (analysis: the two MDCT arrays, side by side)
+    float2 *twl  = (float2 *)(lds + NA * FFT_PADDEDS(BS, ps));    // BS/4 complex: this subblock's FFT twiddles (no global-memory latency inside the FFT passes)
+    int    &s_nnz = *(int *)(lds + NA * FFT_PADDEDS(BS, ps) + BS / 2);  // (inside the dynamic region: no static LDS in front of it)
+    const bool ampLds = !AN && (C > 2);                      // line energies accumulate across channel pairs: only then in LDS
     const bool twInLds = !(ampLds && (size_t)16 * (BS + (BS >> ps)) + (size_t)BS * 4 + 32 > ULCX_LDS_LIMIT);   // (BlockSize 8192 with C > 2: no room, twiddles from global memory)
     float  *amp2 = twInLds ? lds + 4 * FFT_PADDEDS(BS, ps) + BS / 2 + 4 : lds + 4 * FFT_PADDEDS(BS, ps);   // BS/2 (takes the twiddles' place when they are not resident)
-    if (tid == 0) s_nnz = 0;
+    if (!AN && tid == 0) s_nnz = 0;
     if (ampLds) for (int i = tid; i < BS / 2; i += WG) amp2[i] = 0.0f;
 
     const int *wrow = c.wcArr + (size_t)s * (c.maxK + 2) + k;
     int wcPrev = wrow[0], wc = wrow[1], wcNext = wrow[2];
-    if (c.barkRing && tid == 0 && (ulcx_pattern(wc) & ~8u) != 0) c.decList[atomicAdd(c.decCount, 1)] = blk;     // (its Bark sums take the lane-per-subblock kernels)
+    if (!AN && c.barkRing && tid == 0 && (ulcx_pattern(wc) & ~8u) != 0) c.decList[atomicAdd(c.decCount, 1)] = blk;     // (its Bark sums take the lane-per-subblock kernels)
     int nextOv = first_overlap(wcNext, BS);
     int ovFirst;                                       // right overlap of the previous block's last subblock
     {
@@ -204,7 +247,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
     const bool fastBlk = ST && (BS == 2048 || BS == 4096) && (k >= 2 || std::is_same<IN, float>::value) && (ulcx_pattern(wc) >> 4) == 0
                          && ovFirst == BS && nextOv >= BS;
 #endif
-    if (fastBlk) nnz = (BS == 2048) ? xf_fast<IN, 2048>(c, lds, s, k, blk, tid) : xf_fast<IN, 4096>(c, lds, s, k, blk, tid);
+    if (fastBlk) nnz = (BS == 2048) ? xf_fast<IN, 2048, AN>(c, lds, s, k, blk, tid) : xf_fast<IN, 4096, AN>(c, lds, s, k, blk, tid);
     else
     for (int ch0 = 0; ch0 < C; ch0 += 2) {             // one M/S pair (or a trailing single channel) at a time
         const int nch = ST ? 2 : ((ch0 + 1 < C) ? 2 : 1);
@@ -225,7 +268,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
             const float *rise = c.T.winRise + ovL, *fall = c.T.winFall + ov;
             const float2 *pre = c.T.pre[d];
             const int Mp = FFT_PADDEDS(M, ps);                // arrays are stored padded (ulcx_fft.h)
-            float2 *zc0 = z, *zs0 = z + Mp, *zc1 = z + 2 * Mp, *zs1 = z + 3 * Mp;
+            float2 *zc0 = z, *zs0 = z + Mp, *zc1 = z + (AN ? 1 : 2) * Mp, *zs1 = z + 3 * Mp;
 
             // 1. TDAC fold + DCT-IV pre-twiddle straight from the input timeline.
             //    Fold index n uses frame positions {M-1-2n, M+2n, S+M-1-2n, S+M+2n} (n < M/2) or their
@@ -304,7 +347,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
                             float w1 = hsel ? wl : wr, w2 = hsel ? wr : wl;  // w[2n], w[S-1-2n]
                             float2 *zc = q ? zc1 : zc0, *zs = q ? zs1 : zs0;
                             zc[FFT_PADS(n, ps)] = cmulc(make_float2(v1, v2), P);       // u = v      : (u[2n], u[S-1-2n])
-                            zs[FFT_PADS(n, ps)] = cmulc(make_float2(w2, w1), P);       // u = rev(w) : (w[S-1-2n], w[2n])
+                            if constexpr (!AN) zs[FFT_PADS(n, ps)] = cmulc(make_float2(w2, w1), P);       // u = rev(w) : (w[S-1-2n], w[2n])
                         }
                     }
                 }
@@ -318,7 +361,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
             __syncthreads();
 
             // 2. 2*nch M-point FFTs in LDS, one wave per array, no barriers in between
-            if (!(ULCX_DBG(c) & 1)) for (int a = __builtin_amdgcn_readfirstlane(tid >> 6); a < 2 * nch; a += WG / 64) {
+            if (!(ULCX_DBG(c) & 1)) for (int a = __builtin_amdgcn_readfirstlane(tid >> 6); a < (AN ? 1 : 2) * nch; a += WG / 64) {
                 if (twInLds) fft_wave_dif(z + a * Mp, M, twl, tid & 63, ps);
                 else fft_wave_dif(z + a * Mp, M, c.T.tw[d], tid & 63, ps);
             }
@@ -345,6 +388,15 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
                     //  meets a square
                     auto cm = [](float2 d, fft_v2f w) { const fft_v2f dv = { d.x, d.y }; const fft_v2f r = fft_cmulc_post_pk(dv, w); return make_float2(r.x, r.y); };
                     float2 yc1 = cm(zc[FFT_PADS(r1, ps)], Pv1), yc2 = cm(zc[FFT_PADS(r2, ps)], Pv2);
+                    if constexpr (AN) {                    // the coefficients alone, as below
+                        const float mdctA[4] = { yc1.x, yc2.y, yc2.x, yc1.y };
+#pragma unroll
+                        for (int p = 0; p < 2; p++) {
+                            const int j = p ? k2 : k1;
+                            stnt((float2 *)(coefO + (size_t)ch * BS + off + 2 * j), make_float2(mdctA[2*p] * norm, mdctA[2*p+1] * norm));
+                        }
+                        continue;
+                    }
                     float2 ys1 = cm(zs[FFT_PADS(r1, ps)], Pv1), ys2 = cm(zs[FFT_PADS(r2, ps)], Pv2);
                     // pair j = k1: coefficients 2k1, 2k1+1 ; pair j = k2: coefficients 2k2, 2k2+1
                     float mdct[4] = { yc1.x, yc2.y, yc2.x, yc1.y };
@@ -366,6 +418,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
                         if (p) { am2 += a0; am2 += a1; } else { am1 += a0; am1 += a1; } // channel order preserved
                     }
                 }
+                if (AN) continue;
                 if (ampLds) { amp2[off / 2 + k1] = am1; amp2[off / 2 + k2] = am2; }
                 else { c.amp2[tile_idx(BS / 2, blk, off / 2 + k1)] = am1; c.amp2[tile_idx(BS / 2, blk, off / 2 + k2)] = am2; }
             }
@@ -373,6 +426,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
             off += S; ovL = ov;
         } while (pat);
     }
+    if (AN) return;
     // wave-reduce the non-zero count
     for (int o = 32; o > 0; o >>= 1) nnz += __shfl_down(nnz, o);
     if ((tid & 63) == 0) atomicAdd(&s_nnz, nnz);
@@ -385,6 +439,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
 // headline one, and small calls).  Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one, each XCD has its
 // own L2); consecutive blocks of a stream read overlapping input (a frame spans two blocks), so an XCD gets a contiguous
 // run of blocks: block = (b % 8) * ceil(NB/8) + b / 8.  Speed only, never correctness.
+#ifndef ULCX_XF_ANALYSIS_UNIT
 template <bool ST, typename IN>
 __global__ __launch_bounds__(WG, 4) void k_xf(UlcxEncCtx c, int k0, int k1) {
     extern __shared__ float lds[];
@@ -395,6 +450,20 @@ __global__ __launch_bounds__(WG, 4) void k_xf(UlcxEncCtx c, int k0, int k1) {
     if (vb >= NBk) return;
     xf_block<ST, IN>(c, lds, vb / kc, k0 + vb % kc, threadIdx.x);
 }
+#else
+// The analysis call's transform (ulcx_analyse_launch): the same blocks in the same deal, the MDCT coefficients only.  Two
+// arrays instead of four (ulcx_enc_xfa_lds_bytes: 22 KB at BlockSize 2048) and no energy registers: seven workgroups a CU.
+template <bool ST, typename IN>
+__global__ __launch_bounds__(WG, XFA_LB) void k_xfa(UlcxEncCtx c, int k0, int k1) {
+    extern __shared__ float lds[];
+    const int kc = k1 - k0;
+    const int NBk = c.B * kc;
+    const int per = (NBk + 7) / 8;
+    const int vb = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
+    if (vb >= NBk) return;
+    xf_block<ST, IN, true>(c, lds, vb / kc, k0 + vb % kc, threadIdx.x);
+}
+#endif
 
 // ---------------------------------------------------------------------------
 // The same transform for BlockSize > 8192 (ulcEncoder.c:32-34 accepts up to 32768): the four arrays of a channel pair do
@@ -403,8 +472,9 @@ __global__ __launch_bounds__(WG, 4) void k_xf(UlcxEncCtx c, int k0, int k1) {
 // transformed by the whole workgroup (fftn_dif: the same butterflies, a barrier per pass).  Every arithmetic step is the
 // one k_xf takes, in the same order; not tuned (such block sizes are not a throughput case).
 // ---------------------------------------------------------------------------
-template <typename IN>
-__global__ __launch_bounds__(WG) void k_xf_big(UlcxEncCtx c, int k0, int k1) {
+// (AN: the analysis call - the MDCT pass of every channel, no MDST pass, no count, no list)
+template <typename IN, bool AN>
+__device__ __forceinline__ void xf_big_block(const UlcxEncCtx &c, int k0, int k1) {
     extern __shared__ float lds[];
     const int BS = c.BS, C = c.C;
     const int kc = k1 - k0;
@@ -419,7 +489,7 @@ __global__ __launch_bounds__(WG) void k_xf_big(UlcxEncCtx c, int k0, int k1) {
     if (tid == 0) s_nnz = 0;
     const int *wrow = c.wcArr + (size_t)s * (c.maxK + 2) + k;
     const int wcPrev = wrow[0], wc = wrow[1], wcNext = wrow[2];
-    if (c.barkRing && threadIdx.x == 0 && (ulcx_pattern(wc) & ~8u) != 0) c.decList[atomicAdd(c.decCount, 1)] = blk;
+    if (!AN && c.barkRing && threadIdx.x == 0 && (ulcx_pattern(wc) & ~8u) != 0) c.decList[atomicAdd(c.decCount, 1)] = blk;
     const int nextOv = first_overlap(wcNext, BS);
     int ovFirst;                                       // right overlap of the previous block's last subblock
     {
@@ -451,7 +521,7 @@ __global__ __launch_bounds__(WG) void k_xf_big(UlcxEncCtx c, int k0, int k1) {
             const float2 *pre = c.T.pre[d];
             const int bits = 31 - __clz(M);
             const float norm = 2.0f / S;
-            for (int kind = 0; kind < 2; kind++) {                // 0: MDCT, 1: MDST
+            for (int kind = 0; kind < (AN ? 1 : 2); kind++) {     // 0: MDCT, 1: MDST
                 // 1. TDAC fold + DCT-IV pre-twiddle
                 for (int jj = tid; jj < M / 2; jj += WG) {
                     const int iA = 2 * jj, iB = S - 2 - 2 * jj, iC = S + 2 * jj, iD = 2 * S - 2 - 2 * jj;
@@ -509,12 +579,26 @@ __global__ __launch_bounds__(WG) void k_xf_big(UlcxEncCtx c, int k0, int k1) {
             off += S; ovL = ov;
         } while (pat);
     }
+    if (AN) return;
     for (int o = 32; o > 0; o >>= 1) nnz += __shfl_down(nnz, o);
     if ((tid & 63) == 0) atomicAdd(&s_nnz, nnz);
     __syncthreads();
     if (tid == 0) c.nnz[blk] = s_nnz;
 }
 
+#ifndef ULCX_XF_ANALYSIS_UNIT
+template <typename IN>
+__global__ __launch_bounds__(WG) void k_xf_big(UlcxEncCtx c, int k0, int k1) {
+    xf_big_block<IN, false>(c, k0, k1);
+}
+#else
+template <typename IN>
+__global__ __launch_bounds__(WG) void k_xfa_big(UlcxEncCtx c, int k0, int k1) {
+    xf_big_block<IN, true>(c, k0, k1);
+}
+#endif
+
+#ifndef ULCX_XF_ANALYSIS_UNIT
 // ---------------------------------------------------------------------------
 // Block complexity + nOutCoef (BlockTransform.c:279-325, ulcEncoder.c:93-158)
 // ---------------------------------------------------------------------------
@@ -631,6 +715,43 @@ __global__ __launch_bounds__(64) void k_cplx(UlcxEncCtx c, int k0, int k1) {
     if (c.cplxOut) c.cplxOut[blk] = cx;
 }
 
+#else
+// The analysis call's sums: k_cplx without the rate logic - the two ordered sums of the block's coefficients (the loop and the
+// closing arithmetic above, operation for operation) and the two outputs.  It writes nothing the next encode call's k_cplx
+// does not initialise itself.  A call that asks for the window codes alone has no transform in front of it and takes no sums.
+__global__ __launch_bounds__(64) void k_cplxa(UlcxEncCtx c, int k0, int k1) {
+    const int gidc = blockIdx.x * 64 + threadIdx.x, kcc = k1 - k0;     // blocks [k0, k1) of every stream
+    if (gidc >= c.B * kcc) return;
+    const int s = gidc / kcc, k = k0 + gidc % kcc;
+    const int blk = s * c.K + k;
+    if (c.wcOut) c.wcOut[blk] = c.wcArr[(size_t)s * (c.maxK + 2) + k + 1];
+    if (!c.cplxOut) return;
+    const int n = c.C * c.BS;
+    const float4 *p = (const float4 *)(c.coef + (size_t)blk * n);
+    float cx = 0.0f, cw = 0.0f;
+    for (int i = 0; i < n / 4; i += 4) {
+        float4 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) q[u] = p[i + u];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            float4 v = q[u];
+            cx += v.x * v.x; cw += fabsf(v.x);
+            cx += v.y * v.y; cw += fabsf(v.y);
+            cx += v.z * v.z; cw += fabsf(v.z);
+            cx += v.w * v.w; cw += fabsf(v.w);
+        }
+    }
+    if (cx != 0.0f) {
+        cx = ulcx_logf((cw * cw) / cx) / c.cplxScale;
+        if (cx < 0.0f) cx = 0.0f;
+        if (cx > 1.0f) cx = 1.0f;
+    }
+    c.cplxOut[blk] = cx;
+}
+#endif
+
+#ifndef ULCX_XF_ANALYSIS_UNIT
 // ---------------------------------------------------------------------------
 // Persistent state for the next call (ulcEncoder_BlockTransform.c:93, :114)
 // ---------------------------------------------------------------------------
@@ -666,3 +787,11 @@ template __global__ void k_xf_big<float>(UlcxEncCtx, int, int);
 template __global__ void k_xf_big<int16_t>(UlcxEncCtx, int, int);
 template __global__ void k_state_update<float>(UlcxEncCtx);
 template __global__ void k_state_update<int16_t>(UlcxEncCtx);
+#else
+template __global__ void k_xfa<false, float>(UlcxEncCtx, int, int);
+template __global__ void k_xfa<false, int16_t>(UlcxEncCtx, int, int);
+template __global__ void k_xfa<true, float>(UlcxEncCtx, int, int);
+template __global__ void k_xfa<true, int16_t>(UlcxEncCtx, int, int);
+template __global__ void k_xfa_big<float>(UlcxEncCtx, int, int);
+template __global__ void k_xfa_big<int16_t>(UlcxEncCtx, int, int);
+#endif

@@ -205,6 +205,9 @@ int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the 
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
 size_t ulcx_enc_xf_lds_bytes(int BS, int C);
+size_t ulcx_enc_xfa_lds_bytes(int BS, int C);            // the analysis call's MDCT-only transform
+// analysis call (include/ulc_amd.h: ulcx_analyse_dev); useKxf: the encode call's transform instead of the MDCT-only one (timing comparisons)
+int ulcx_analyse_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev /* ULCX_ENC_STAGES+1 or NULL */, const UlcxEncAux &aux, int useKxf);
 int ulcx_enc_nsums_slots(int BS, int C);                 // resident workgroups of k_nsums on the current device
 // FFT array padding of k_xf (ulcx_fft.h).  One complex per 8 makes every pass conflict-free but costs 2 KB of LDS at
 // BlockSize 2048 and with it the 4th workgroup per CU: measured 2.13 ms vs 1.88 ms with one per 16.

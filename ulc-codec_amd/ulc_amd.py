@@ -23,6 +23,7 @@ EXPORTS = [
     "ulcx_encoder_last_fallbacks", "ulcx_encoder_debug_force_exact", "ulcx_ulc_header_pack", "ulcx_ulc_header_parse", "ulcx_ulc_rate_kbps",
     "ulcx_pack_streams_dev", "ulcx_decode_packed_dev", "ulcx_decode_packed_host", "ulcx_decoder_upload_payload", "ulcx_decode_resident_host", "ulcx_encoder_stage_ms", "ulcx_encoder_stage_name", "ulcx_encoder_last_xf_launches", "ulcx_decoder_stage_ms", "ulcx_decoder_stage_name", "ulcx_block_extent_bytes", "ulcx_encoder_set_timing", "ulcx_decoder_set_timing", "ulcx_encode_block1", "ulcx_decode_block1", "ulcx_decode_block1_rng", "ulcx_build_rev", "ulcx_dec_split_plan", "ulcx_dec_tail_plan", "ulcx_decoder_last_cut",
     "ulcx_encode_dev_rates", "ulcx_encode_dev_pcm16_rates", "ulcx_encode_host_rates",
+    "ulcx_analyse_dev", "ulcx_analyse_dev_pcm16", "ulcx_analyse_host",
 ]
 
 
@@ -56,6 +57,10 @@ def lib():
             l.ulcx_encode_dev_rates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             l.ulcx_encode_dev_pcm16_rates.argtypes = l.ulcx_encode_dev_rates.argtypes
             l.ulcx_encode_host_rates.argtypes = [C.c_void_p, _f32p, _f32p, C.c_int, _u8p, _i32p, _i32p, _f32p]
+        if hasattr(l, "ulcx_analyse_dev"):
+            l.ulcx_analyse_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_analyse_dev_pcm16.argtypes = l.ulcx_analyse_dev.argtypes
+            l.ulcx_analyse_host.argtypes = [C.c_void_p, _f32p, C.c_int, _i32p, _f32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -181,6 +186,26 @@ class BatchEncoder:
         """PCM16 ingest: d_pcm16 is a device pointer to int16 [B][K][BS][C]; converted on load as tools/WavIO_Helper.c:49-55."""
         _check(lib().ulcx_encode_dev_pcm16(self.h, mode, p0, p1, d_pcm16, n_blocks, d_out, d_bits, d_wc or None, d_cplx or None,
                                            stream or None), "ulcx_encode_dev_pcm16")
+        self.lastK = n_blocks
+
+    def analyse(self, pcm):
+        """Analysis only (no selection, no writer): pcm[B][K*BS][C] -> (wc[B][K], cplx[B][K]), the WindowCtrl and
+        BlockComplexity encode() returns for the same input; the streams' state advances as encode() advances it."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        assert pcm.shape[0] == self.B and pcm.shape[-1] == self.C
+        K = pcm.shape[1] // self.BS
+        assert pcm.shape[1] == K * self.BS
+        wc = np.zeros((self.B, K), np.int32)
+        cplx = np.zeros((self.B, K), np.float32)
+        _check(lib().ulcx_analyse_host(self.h, _p(pcm, _f32p), K, _p(wc, _i32p), _p(cplx, _f32p)), "ulcx_analyse_host")
+        self.lastK = K
+        return wc, cplx
+
+    def analyse_dev(self, d_pcm, n_blocks, d_wc=0, d_cplx=0, stream=0, pcm16=False):
+        """Device-pointer analysis call, asynchronous on `stream`; at least one of d_wc / d_cplx; pcm16=True takes int16 samples."""
+        fn = lib().ulcx_analyse_dev_pcm16 if pcm16 else lib().ulcx_analyse_dev
+        _check(fn(self.h, d_pcm, n_blocks, d_wc or None, d_cplx or None, stream or None),
+               "ulcx_analyse_dev_pcm16" if pcm16 else "ulcx_analyse_dev")
         self.lastK = n_blocks
 
     def debug_fetch(self, K=None, parts=("coef", "noise", "keys", "keep", "nout")):
