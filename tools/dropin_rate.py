@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from ulc_testlib import synth_pcm, oracle, ptr, f32p, u8p, i32p
 
-lib = C.CDLL(os.path.join(ROOT, "ulc-codec_amd", "libulc_amd.so"))
+lib = C.CDLL(os.environ.get("ULC_AMD_LIB") or os.path.join(ROOT, "ulc-codec_amd", "libulc_amd.so"))     # (ULC_AMD_LIB: another build, as ulc_amd.py)
 
 
 class Enc(C.Structure):

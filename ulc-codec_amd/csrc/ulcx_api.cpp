@@ -3,6 +3,7 @@
 // ulcx_enc.hip / ulcx_dec.hip.  There is no CPU fallback: if HIP cannot give us a
 // device, every entry point returns ULCX_ERR_NO_DEVICE.
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -12,50 +13,79 @@
 
 #define CKR(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ulcx_set_error("%s: %s", #x, hipGetErrorString(e_)); return ULCX_ERR_HIP; } } while (0)
 
+// The single-block calls (ulcx_encode_block1 / ulcx_decode_block1): own stream, and the call's enqueue sequence captured once
+// into a graph that every later call replays.  noGraph: direct launches from here on.
+struct Block1Graph {
+    hipStream_t stream = nullptr; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    bool graphed = false, noGraph = false;
+};
+static void block1_drop(Block1Graph &g) { if (g.graphed) { hipGraphExecDestroy(g.exec); hipGraphDestroy(g.graph); g.graphed = false; } }
+// capture + instantiate on the first call (a failure of either: direct launches from then on), then replay or enqueue, and wait
+template <class F> static int block1_run(Block1Graph &g, F enqueue) {
+    if (!g.graphed && !g.noGraph) {
+        bool ok = hipStreamBeginCapture(g.stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
+        if (ok) {
+            const int rc = enqueue();
+            hipGraph_t gr = nullptr;
+            const hipError_t ee = hipStreamEndCapture(g.stream, &gr);
+            ok = (rc == ULCX_OK) && ee == hipSuccess && gr != nullptr;
+            if (ok) ok = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0) == hipSuccess;
+            if (ok) { g.graph = gr; g.graphed = true; }
+            else if (gr) hipGraphDestroy(gr);
+        }
+        if (!ok) { (void)hipGetLastError(); g.noGraph = true; }
+    }
+    if (g.graphed) CKR(hipGraphLaunch(g.exec, g.stream));
+    else { int rc = enqueue(); if (rc) return rc; }
+    CKR(hipStreamSynchronize(g.stream));
+    return ULCX_OK;
+}
+
 struct ulcx_encoder {
-    int device, B, C, BS, rate, maxK;
-    UlcxEncCtx ctx;
-    void *tables;
+    int device = 0, B = 0, C = 0, BS = 0, rate = 0, maxK = 0;
+    UlcxEncCtx ctx = {};
+    void *tables = nullptr;
     std::vector<void *> allocs;
-    hipEvent_t ev[ULCX_ENC_STAGES + 1];
-    bool evOk, evRecorded;
-    int lastK;
-    hipStream_t side; hipEvent_t evFork, evJoin, evFork2; bool sideOk; bool timing;
-    hipEvent_t evWC[7 + 3 * ULCX_WC_MAXCH + ULCX_XF_MAXCH + 1]; int wcPipe; hipStream_t side2, side3; hipEvent_t evXf[2 * ULCX_XF_MAXCH]; int nXf;      // window-control / transform pipeline (ULCX_WC_PIPE chunks, default 4)
-    bool keysFinal;
-    int wcSteps, wcFuse;      // environment switches, read once at create
-    int nsSlots;              // resident workgroups of k_nsums (its persistent grid)
-    bool lastAnalyse;         // the last call was an analysis call: no intermediates, no exact-path count to report
-    int analyseKxf;           // ULCX_ANALYSE_KXF=1: analysis calls run the encode call's transform (timing comparisons)
+    hipEvent_t ev[ULCX_ENC_STAGES + 1] = {};
+    bool evOk = false, evRecorded = false, timing = true;
+    int lastK = 0;
+    UlcxEncSync sync = {};    // side streams and their events (ULCX_ASYNC_FB=0: none)
+    int wcPipe = 1, nXf = 0;  // window-control / transform pipeline (ULCX_WC_PIPE chunks, default 4); transform launches of the last call
+    bool keysFinal = false;
+    int wcSteps = -1, wcFuse = 1;     // environment switches, read once at create
+    int nsSlots = 0;                  // resident workgroups of k_nsums (its persistent grid)
+    bool lastAnalyse = false;         // the last call was an analysis call: no intermediates, no exact-path count to report
+    int analyseKxf = 0;               // ULCX_ANALYSE_KXF=1: analysis calls run the encode call's transform (timing comparisons)
     // staging for the host-pointer API
-    float *d_pcm; uint8_t *d_out; int32_t *d_bits, *d_wc; float *d_cplx;
-    ulcx_rate *d_rate;        // [B] the per-stream table of ulcx_encode_host_rates
-    // single-block path (ulcx_encode_block1): own stream, pinned staging, the captured launch sequence
+    float *d_pcm = nullptr; uint8_t *d_out = nullptr; int32_t *d_bits = nullptr, *d_wc = nullptr; float *d_cplx = nullptr;
+    ulcx_rate *d_rate = nullptr;      // [B] the per-stream table of ulcx_encode_host_rates
+    // single-block path (ulcx_encode_block1): pinned staging, the captured launch sequence and the parameters it was captured with
     struct Block1Meta { int32_t bits, wc; float cplx; int32_t pad; UlcxWcState wcs; };
-    hipStream_t b1Stream; hipGraph_t b1Graph; hipGraphExec_t b1Exec; bool b1Init, b1Graphed, b1NoGraph;
-    int b1Mode; float b1P0, b1P1; int b1Rekeys;
-    float *pinIn; uint8_t *pinOut; Block1Meta *pinMeta;
+    Block1Graph b1; bool b1Init = false;
+    int b1Mode = 0; float b1P0 = 0.0f, b1P1 = 0.0f; int b1Rekeys = 0;
+    float *pinIn = nullptr; uint8_t *pinOut = nullptr; Block1Meta *pinMeta = nullptr;
 };
 struct ulcx_decoder {
-    int device, B, C, BS, maxK;
-    UlcxDecCtx ctx;
-    void *tables;
+    int device = 0, B = 0, C = 0, BS = 0, maxK = 0;
+    UlcxDecCtx ctx = {};
+    void *tables = nullptr;
     std::vector<void *> allocs;
-    hipEvent_t ev[ULCX_DEC_STAGES + 1];
-    bool evOk, evRecorded, timing;
-    uint8_t *d_in; size_t d_in_bytes; float *d_pcm; int32_t *d_bits;
-    uint8_t *d_pay; int32_t *d_payBytes; long long payStride;     // resident packed payloads (ulcx_decoder_upload_payload)
+    hipEvent_t ev[ULCX_DEC_STAGES + 1] = {};
+    bool evOk = false, evRecorded = false, timing = true;
+    uint8_t *d_in = nullptr; size_t d_in_bytes = 0; float *d_pcm = nullptr; int32_t *d_bits = nullptr;
+    uint8_t *d_pay = nullptr; int32_t *d_payBytes = nullptr; long long payStride = 0;     // resident packed payloads (ulcx_decoder_upload_payload)
     // k_dsyn over an even cut of the call's (stream, block) pairs: the second set of state arrays, the resident
     // workgroups of the kernel on this device, ULCX_DSYN_SPLIT=0 switches it off
-    float *lap2; int *lastSub2; uint32_t *seed2; int *dead2; int synSlots, scratchRows, lastGrid, lastFull; bool splitOK, tailCut;
+    float *lap2 = nullptr; int *lastSub2 = nullptr; uint32_t *seed2 = nullptr; int *dead2 = nullptr;
+    int synSlots = 0, scratchRows = 0, lastGrid = 0, lastFull = 0; bool splitOK = false, tailCut = true;
     // single-block path (ulcx_decode_block1)
-    hipStream_t b1Stream; hipGraph_t b1Graph; hipGraphExec_t b1Exec; bool b1Init, b1Graphed, b1NoGraph; int b1Slot;
-    uint8_t *pinIn; float *pinPcm; int32_t *pinMeta;
-    uint32_t b1Seed;                                              // the stream's RNG state between single-block calls
+    Block1Graph b1; bool b1Init = false; int b1Slot = 0;
+    uint8_t *pinIn = nullptr; float *pinPcm = nullptr; int32_t *pinMeta = nullptr;
+    uint32_t b1Seed = 0;                                          // the stream's RNG state between single-block calls
     // The device word (ctx.seed) is the authoritative state of the object's own noise chain; b1Seed is its host copy, which the
     // single-block path uploads in front of every block.  Any OTHER decode call on this object advances the device word only:
     // it marks the copy stale, and the next single-block call without a caller-owned state reads the device word back first.
-    bool b1SeedStale, inBlock1;
+    bool b1SeedStale = false, inBlock1 = false;
 };
 
 #ifndef ULCX_SRC_REV
@@ -103,17 +133,36 @@ static int select_device(int device) {
 // ---------------------------------------------------------------------------
 // encoder
 // ---------------------------------------------------------------------------
+// The side streams and every event of UlcxEncSync: all of them or none.  Only the transform's timing pairs can be timed.
+static const size_t kEncSyncUntimed = offsetof(UlcxEncSync, xfTiming) / sizeof(hipEvent_t);
+static void enc_sync_destroy(UlcxEncSync &s) {
+    hipEvent_t *ev = &s.wcStart;
+    for (size_t i = 0; i < kEncSyncUntimed + 2 * ULCX_XF_MAXCH; i++) if (ev[i]) hipEventDestroy(ev[i]);
+    for (hipStream_t st : { s.side, s.side2, s.side3 }) if (st) hipStreamDestroy(st);
+    s = UlcxEncSync{};
+}
+static bool enc_sync_create(UlcxEncSync &s) {
+    static_assert(offsetof(UlcxEncSync, wcStart) == 0 && offsetof(UlcxEncSync, side) == (kEncSyncUntimed + 2 * ULCX_XF_MAXCH) * sizeof(hipEvent_t), "UlcxEncSync: events, then streams");
+    hipEvent_t *ev = &s.wcStart;
+    bool ok = true;
+    for (hipStream_t *st : { &s.side, &s.side2, &s.side3 }) ok = ok && hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess;
+    for (size_t i = 0; i < kEncSyncUntimed; i++) ok = ok && hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
+    for (auto &v : s.xfTiming) ok = ok && hipEventCreate(&v) == hipSuccess;
+    if (!ok) { (void)hipGetLastError(); enc_sync_destroy(s); }
+    return ok;
+}
+
 static void cleanup(ulcx_encoder *e) {
     if (!e) return;
     for (void *p : e->allocs) hipFree(p);
     if (e->tables) hipFree(e->tables);
     if (e->evOk) for (auto &v : e->ev) hipEventDestroy(v);
-    if (e->b1Graphed) { hipGraphExecDestroy(e->b1Exec); hipGraphDestroy(e->b1Graph); }
-    if (e->b1Stream) hipStreamDestroy(e->b1Stream);
+    block1_drop(e->b1);
+    if (e->b1.stream) hipStreamDestroy(e->b1.stream);
     if (e->pinIn) hipHostFree(e->pinIn);
     if (e->pinOut) hipHostFree(e->pinOut);
     if (e->pinMeta) hipHostFree(e->pinMeta);
-    if (e->sideOk) { hipStreamDestroy(e->side); hipEventDestroy(e->evFork); hipEventDestroy(e->evJoin); hipEventDestroy(e->evFork2); for (auto &v : e->evWC) hipEventDestroy(v); for (auto &v : e->evXf) hipEventDestroy(v); hipStreamDestroy(e->side2); hipStreamDestroy(e->side3); }
+    enc_sync_destroy(e->sync);
     delete e;
 }
 
@@ -142,11 +191,7 @@ extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams,
     if (rc) return rc;
     ulcx_encoder *e = new ulcx_encoder();
     e->device = device; e->B = nStreams; e->C = nChan; e->BS = BlockSize; e->rate = RateHz; e->maxK = maxBlocksPerCall;
-    e->tables = nullptr; e->evOk = false; e->evRecorded = false; e->timing = true; e->lastK = 0; e->lastAnalyse = false; e->analyseKxf = 0; e->sideOk = false; e->side = nullptr; e->keysFinal = false;
-    e->d_pcm = nullptr; e->d_out = nullptr; e->d_bits = nullptr; e->d_wc = nullptr; e->d_cplx = nullptr; e->d_rate = nullptr;
-    e->b1Init = e->b1Graphed = e->b1NoGraph = false; e->b1Stream = nullptr; e->b1Rekeys = 0; e->pinIn = nullptr; e->pinOut = nullptr; e->pinMeta = nullptr;
     UlcxEncCtx &c = e->ctx;
-    memset(&c, 0, sizeof(c));
     c.B = nStreams; c.C = nChan; c.BS = BlockSize; c.lgBS = ilog2i(BlockSize); c.maxK = maxBlocksPerCall; c.K = 0;
     c.rateHz = RateHz;
     c.slot = 2 * nChan * BlockSize + 16;          // >= worst case 4 nybbles/coefficient + header
@@ -227,21 +272,11 @@ extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams,
     e->evOk = true;
     {
         const char *evs = getenv("ULCX_ASYNC_FB");
-        if (!(evs && evs[0] == '0')) {
-            if (hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) == hipSuccess &&
-                hipEventCreateWithFlags(&e->evFork, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&e->evJoin, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&e->evFork2, hipEventDisableTiming) == hipSuccess) {
-                bool ok = hipStreamCreateWithFlags(&e->side2, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&e->side3, hipStreamNonBlocking) == hipSuccess;
-                for (auto &v : e->evWC) ok = ok && hipEventCreateWithFlags(&v, hipEventDisableTiming) == hipSuccess;
-                for (auto &v : e->evXf) ok = ok && hipEventCreate(&v) == hipSuccess;
-                e->sideOk = ok;
-            }
-        }
-        e->wcPipe = e->sideOk ? 4 : 1;                         // transform chunks per call: 1 block, then thirds (4 vs 5 chunks: 9.50 vs 9.56 ms per bench step)
-        if (const char *pv = getenv("ULCX_WC_PIPE")) { int n = atoi(pv); if (n >= 1 && n <= ULCX_XF_MAXCH && n != 2 && (n == 1 || e->sideOk)) e->wcPipe = n; }
-        e->wcSteps = -1; if (const char *sv = getenv("ULCX_WC_STEPS")) e->wcSteps = atoi(sv);      // -1: default; 0: the transform's chunks
-        e->wcFuse = 1;                                           // (stereo: k_wc_ef; every other channel count: k_wc_energy + k_wc_forward)
+        const bool sideOk = !(evs && evs[0] == '0') && enc_sync_create(e->sync);
+        e->wcPipe = sideOk ? 4 : 1;                            // transform chunks per call: 1 block, then thirds (4 vs 5 chunks: 9.50 vs 9.56 ms per bench step)
+        if (const char *pv = getenv("ULCX_WC_PIPE")) { int n = atoi(pv); if (n >= 1 && n <= ULCX_XF_MAXCH && n != 2 && (n == 1 || sideOk)) e->wcPipe = n; }
+        if (const char *sv = getenv("ULCX_WC_STEPS")) e->wcSteps = atoi(sv);      // -1: default; 0: the transform's chunks
+        // (wcFuse = 1: stereo k_wc_ef; every other channel count: k_wc_energy + k_wc_forward)
     }
     if (const char *av = getenv("ULCX_ANALYSE_KXF")) e->analyseKxf = (av[0] == '1');
     e->nsSlots = c.useGapSums ? ulcx_enc_nsums_slots(BlockSize, nChan) : 0;
@@ -281,6 +316,13 @@ extern "C" void ulcx_encoder_destroy(ulcx_encoder *e) { if (e) { hipSetDevice(e-
 extern "C" int ulcx_encoder_reset(ulcx_encoder *e) { if (!e) return ULCX_ERR_ARG; CKR(hipSetDevice(e->device)); return enc_reset_state(e); }
 extern "C" int ulcx_encoder_slot_bytes(const ulcx_encoder *e) { return e ? e->ctx.slot : 0; }
 
+// What a call of nBlocks launches with.  Short calls pipeline window control and transform in fewer chunks or not at all
+// (wcPipe > 1 only ever with side streams: ulcx_encoder_create).
+static UlcxEncAux enc_aux(ulcx_encoder *e, int nBlocks) {
+    const int wcPipe = (nBlocks >= 2 * e->wcPipe) ? e->wcPipe : (nBlocks >= 6 && e->wcPipe > 1 ? 3 : 1);
+    return UlcxEncAux{ e->sync, wcPipe, e->wcSteps, e->wcFuse, e->nsSlots, e->nXf };
+}
+
 // d_rate != NULL: per-stream settings read on the device (ulcx_encode_dev_rates); mode / p0 / p1 are then unused
 static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
                           uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
@@ -293,11 +335,7 @@ static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const u
     c.vbrTarget = (mode == ULCX_MODE_VBR) ? 0x1.E4EFB7p3f * logf(100.0f / p0) : 0.0f;     // ulcEncoder.c:144 (host libm, data independent)
     c.rates = (const float2 *)d_rate;
     c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = d_out; c.bits = d_bits; c.wcOut = d_wc; c.cplxOut = d_cplx;
-    UlcxEncAux aux;
-    aux.side = e->sideOk ? e->side : nullptr; aux.side2 = e->sideOk ? e->side2 : nullptr; aux.side3 = e->sideOk ? e->side3 : nullptr;
-    aux.evFork = e->evFork; aux.evJoin = e->evJoin; aux.evFork2 = e->evFork2; aux.evWC = e->evWC; aux.evXf = e->evXf;
-    aux.wcPipe = (nBlocks >= 2 * e->wcPipe) ? e->wcPipe : (nBlocks >= 6 && e->wcPipe > 1 ? 3 : 1); aux.nXf = &e->nXf;
-    aux.wcSteps = e->wcSteps; aux.wcFuse = e->wcFuse; aux.nsSlots = e->nsSlots;
+    const UlcxEncAux aux = enc_aux(e, nBlocks);
     const int rc = ulcx_enc_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     e->lastK = nBlocks;
@@ -313,11 +351,7 @@ static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d
     UlcxEncCtx c = e->ctx;
     c.K = nBlocks; c.keyFinal = 0; c.mode = ULCX_MODE_VBR; c.p0 = 100.0f; c.p1 = 0.0f; c.vbrTarget = 0.0f; c.rates = nullptr;
     c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = nullptr; c.bits = nullptr; c.wcOut = d_wc; c.cplxOut = d_cplx;
-    UlcxEncAux aux;
-    aux.side = e->sideOk ? e->side : nullptr; aux.side2 = e->sideOk ? e->side2 : nullptr; aux.side3 = e->sideOk ? e->side3 : nullptr;
-    aux.evFork = e->evFork; aux.evJoin = e->evJoin; aux.evFork2 = e->evFork2; aux.evWC = e->evWC; aux.evXf = e->evXf;
-    aux.wcPipe = (nBlocks >= 2 * e->wcPipe) ? e->wcPipe : (nBlocks >= 6 && e->wcPipe > 1 ? 3 : 1); aux.nXf = &e->nXf;      // (the encode call's chunking)
-    aux.wcSteps = e->wcSteps; aux.wcFuse = e->wcFuse; aux.nsSlots = e->nsSlots;
+    const UlcxEncAux aux = enc_aux(e, nBlocks);      // (the encode call's chunking)
     const int rc = ulcx_analyse_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux, e->analyseKxf);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     e->lastK = nBlocks;
@@ -384,6 +418,21 @@ extern "C" int ulcx_encode_dev_pcm16_rates(ulcx_encoder *e, const ulcx_rate *d_r
     return encode_dev_any(e, 0, 0.0f, 0.0f, d_rate, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
 }
 
+// the host-pointer encode calls behind their argument checks and staging: input up, one call on the null stream, results down
+static int encode_host_run(ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *h_pcm, int nBlocks,
+                           uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
+    const size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
+    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
+    int rc = encode_dev_any(e, mode, p0, p1, d_rate, e->d_pcm, nullptr, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_out, e->d_out, NB * e->ctx.slot, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+
 extern "C" int ulcx_encode_host_rates(ulcx_encoder *e, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
                                       uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
     if (!e || !h_rate || !h_pcm || !h_out || !h_bits) { ulcx_set_error("ulcx_encode_host_rates: bad argument"); return ULCX_ERR_ARG; }
@@ -396,39 +445,19 @@ extern "C" int ulcx_encode_host_rates(ulcx_encoder *e, const ulcx_rate *h_rate, 
         }
     }
     CKR(hipSetDevice(e->device));
-    size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS;
-    { int rc = host_staging(e, NBmax, true); if (rc) return rc; }
+    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
     if (!e->d_rate) { int rc = dalloc(e->allocs, &e->d_rate, (size_t)e->B, false); if (rc) return rc; }
-    size_t NB = (size_t)e->B * nBlocks;
     CKR(hipMemcpy(e->d_rate, h_rate, sizeof(ulcx_rate) * (size_t)e->B, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
-    int rc = ulcx_encode_dev_rates(e, e->d_rate, e->d_pcm, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_out, e->d_out, NB * e->ctx.slot, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
+    return encode_host_run(e, 0, 0.0f, 0.0f, e->d_rate, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx);
 }
 
 extern "C" int ulcx_encode_host(ulcx_encoder *e, int mode, float p0, float p1, const float *h_pcm, int nBlocks,
                                 uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
     if (!e || !h_pcm || !h_out || !h_bits) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS;
-    { int rc = host_staging(e, NBmax, true); if (rc) return rc; }
+    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
     if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
-    size_t NB = (size_t)e->B * nBlocks;
-    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
-    int rc = ulcx_encode_dev(e, mode, p0, p1, e->d_pcm, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_out, e->d_out, NB * e->ctx.slot, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
+    return encode_host_run(e, mode, p0, p1, nullptr, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx);
 }
 
 // One block of one stream per call (the drop-in ABI): include/ulc_amd.h.  The launch sequence of ulcx_encode_dev - side
@@ -444,7 +473,7 @@ extern "C" int ulcx_encode_block1(ulcx_encoder *e, int mode, float p0, float p1,
         if ((rc = host_staging(e, 1, true))) return rc;                // (one stream, one block per call)
         // (b1Init only once everything exists: a failed allocation leaves the call to be retried from scratch, never a
         //  later call copying into a null staging buffer)
-        if (!e->b1Stream) CKR(hipStreamCreateWithFlags(&e->b1Stream, hipStreamNonBlocking));
+        if (!e->b1.stream) CKR(hipStreamCreateWithFlags(&e->b1.stream, hipStreamNonBlocking));
         if (!e->pinIn) CKR(hipHostMalloc((void **)&e->pinIn, sizeof(float) * cb, hipHostMallocDefault));
         if (!e->pinOut) CKR(hipHostMalloc((void **)&e->pinOut, slot, hipHostMallocDefault));
         if (!e->pinMeta) CKR(hipHostMalloc((void **)&e->pinMeta, sizeof(*e->pinMeta), hipHostMallocDefault));
@@ -452,39 +481,25 @@ extern "C" int ulcx_encode_block1(ulcx_encoder *e, int mode, float p0, float p1,
         e->timing = false;                                 // (per-kernel events cannot be captured, and nobody reads them here)
     }
     auto enqueue = [&]() -> int {
-        CKR(hipMemcpyAsync(e->d_pcm, e->pinIn, sizeof(float) * cb, hipMemcpyHostToDevice, e->b1Stream));
-        int rc = ulcx_encode_dev(e, mode, p0, p1, e->d_pcm, 1, e->d_out, e->d_bits, e->d_wc, e->d_cplx, e->b1Stream);
+        CKR(hipMemcpyAsync(e->d_pcm, e->pinIn, sizeof(float) * cb, hipMemcpyHostToDevice, e->b1.stream));
+        int rc = ulcx_encode_dev(e, mode, p0, p1, e->d_pcm, 1, e->d_out, e->d_bits, e->d_wc, e->d_cplx, e->b1.stream);
         if (rc) return rc;
-        CKR(hipMemcpyAsync(e->pinOut, e->d_out, slot, hipMemcpyDeviceToHost, e->b1Stream));
-        CKR(hipMemcpyAsync(&e->pinMeta->bits, e->d_bits, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1Stream));
-        CKR(hipMemcpyAsync(&e->pinMeta->wc, e->d_wc, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1Stream));
-        CKR(hipMemcpyAsync(&e->pinMeta->cplx, e->d_cplx, sizeof(float), hipMemcpyDeviceToHost, e->b1Stream));
-        CKR(hipMemcpyAsync(&e->pinMeta->wcs, e->ctx.wcs, sizeof(UlcxWcState), hipMemcpyDeviceToHost, e->b1Stream));
+        CKR(hipMemcpyAsync(e->pinOut, e->d_out, slot, hipMemcpyDeviceToHost, e->b1.stream));
+        CKR(hipMemcpyAsync(&e->pinMeta->bits, e->d_bits, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1.stream));
+        CKR(hipMemcpyAsync(&e->pinMeta->wc, e->d_wc, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1.stream));
+        CKR(hipMemcpyAsync(&e->pinMeta->cplx, e->d_cplx, sizeof(float), hipMemcpyDeviceToHost, e->b1.stream));
+        CKR(hipMemcpyAsync(&e->pinMeta->wcs, e->ctx.wcs, sizeof(UlcxWcState), hipMemcpyDeviceToHost, e->b1.stream));
         return ULCX_OK;
     };
     memcpy(e->pinIn, h_pcm, sizeof(float) * cb);
-    if (e->b1Graphed && (e->b1Mode != mode || e->b1P0 != p0 || e->b1P1 != p1)) {          // the parameters are part of the captured kernels' arguments
-        hipGraphExecDestroy(e->b1Exec); hipGraphDestroy(e->b1Graph); e->b1Graphed = false;
+    if (e->b1.graphed && (e->b1Mode != mode || e->b1P0 != p0 || e->b1P1 != p1)) {         // the parameters are part of the captured kernels' arguments
+        block1_drop(e->b1);
         // a caller whose parameters change from block to block (ULC_EncodeBlock_ABR: the reference's tool updates
         // AvgComplexity every block) would pay a capture + instantiate per call: after the second change, direct launches
-        if (++e->b1Rekeys >= 2) e->b1NoGraph = true;
+        if (++e->b1Rekeys >= 2) e->b1.noGraph = true;
     }
-    if (!e->b1Graphed && !e->b1NoGraph) {
-        bool ok = hipStreamBeginCapture(e->b1Stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (ok) {
-            const int rc = enqueue();
-            hipGraph_t g = nullptr;
-            const hipError_t ee = hipStreamEndCapture(e->b1Stream, &g);
-            ok = (rc == ULCX_OK) && ee == hipSuccess && g != nullptr;
-            if (ok) ok = hipGraphInstantiate(&e->b1Exec, g, nullptr, nullptr, 0) == hipSuccess;
-            if (ok) { e->b1Graph = g; e->b1Graphed = true; e->b1Mode = mode; e->b1P0 = p0; e->b1P1 = p1; }
-            else if (g) hipGraphDestroy(g);
-        }
-        if (!ok) { (void)hipGetLastError(); e->b1NoGraph = true; }                         // direct launches from here on
-    }
-    if (e->b1Graphed) CKR(hipGraphLaunch(e->b1Exec, e->b1Stream));
-    else { int rc = enqueue(); if (rc) return rc; }
-    CKR(hipStreamSynchronize(e->b1Stream));
+    if (!e->b1.graphed) { e->b1Mode = mode; e->b1P0 = p0; e->b1P1 = p1; }                  // (what a capture in this call holds)
+    { int rc = block1_run(e->b1, enqueue); if (rc) return rc; }
     const int32_t nb = e->pinMeta->bits;
     memcpy(h_out, e->pinOut, (nb > 0 && (size_t)(nb + 7) / 8 <= slot) ? (size_t)(nb + 7) / 8 : slot);
     if (bits) *bits = nb;
@@ -557,7 +572,7 @@ extern "C" int ulcx_encoder_stage_ms(ulcx_encoder *e, float *ms, int maxStages) 
         float exposed = 0.0f;
         if (e->nXf > 0) {
             float sum = 0.0f; bool ok = true;
-            for (int j = 0; j < e->nXf; j++) { float t = 0; if (hipEventElapsedTime(&t, e->evXf[2 * j], e->evXf[2 * j + 1]) != hipSuccess) { ok = false; break; } sum += t; }
+            for (int j = 0; j < e->nXf; j++) { float t = 0; if (hipEventElapsedTime(&t, e->sync.xfTiming[2 * j], e->sync.xfTiming[2 * j + 1]) != hipSuccess) { ok = false; break; } sum += t; }
             if (ok) { exposed = ms[IX_XF] - sum; ms[IX_XF] = sum; }
         }
         ms[n++] = exposed;
@@ -577,8 +592,8 @@ static void cleanup(ulcx_decoder *e) {
     if (e->d_payBytes) hipFree(e->d_payBytes);
     if (e->tables) hipFree(e->tables);
     if (e->evOk) for (auto &v : e->ev) hipEventDestroy(v);
-    if (e->b1Graphed) { hipGraphExecDestroy(e->b1Exec); hipGraphDestroy(e->b1Graph); }
-    if (e->b1Stream) hipStreamDestroy(e->b1Stream);
+    block1_drop(e->b1);
+    if (e->b1.stream) hipStreamDestroy(e->b1.stream);
     if (e->pinIn) hipHostFree(e->pinIn);
     if (e->pinPcm) hipHostFree(e->pinPcm);
     if (e->pinMeta) hipHostFree(e->pinMeta);
@@ -719,12 +734,7 @@ extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams,
     if (rc) return rc;
     ulcx_decoder *e = new ulcx_decoder();
     e->device = device; e->B = nStreams; e->C = nChan; e->BS = BlockSize; e->maxK = maxBlocksPerCall;
-    e->tables = nullptr; e->evOk = false; e->evRecorded = false; e->timing = true;
-    e->d_in = nullptr; e->d_in_bytes = 0; e->d_pcm = nullptr; e->d_bits = nullptr; e->d_pay = nullptr; e->d_payBytes = nullptr; e->payStride = 0;
-    e->lap2 = nullptr; e->lastSub2 = nullptr; e->seed2 = nullptr; e->dead2 = nullptr; e->synSlots = 0; e->scratchRows = 0; e->lastGrid = 0; e->lastFull = 0; e->splitOK = false; e->tailCut = true;
-    e->b1Init = e->b1Graphed = e->b1NoGraph = false; e->b1Stream = nullptr; e->pinIn = nullptr; e->pinPcm = nullptr; e->pinMeta = nullptr; e->b1Slot = 0;
     UlcxDecCtx &c = e->ctx;
-    memset(&c, 0, sizeof(c));
     c.B = nStreams; c.C = nChan; c.BS = BlockSize; c.lgBS = ilog2i(BlockSize); c.maxK = maxBlocksPerCall;
 #ifdef ULCX_ABLATE
     if (const char *ev = getenv("ULCX_DBG_SKIP")) c.dbgSkip = atoi(ev);
@@ -792,6 +802,20 @@ extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams,
 extern "C" void ulcx_decoder_destroy(ulcx_decoder *e) { if (e) { hipSetDevice(e->device); cleanup(e); } }
 extern "C" int ulcx_decoder_reset(ulcx_decoder *e) { if (!e) return ULCX_ERR_ARG; CKR(hipSetDevice(e->device)); return dec_reset_state(e); }
 
+// device staging of the host-pointer entries: output samples and sizes of nBlk blocks; inBytes > 0: the input slots too
+static int dec_host_staging(ulcx_decoder *e, size_t nBlk, size_t inBytes) {
+    int rc;
+    if (inBytes && (!e->d_in || e->d_in_bytes < inBytes)) {
+        if ((rc = dalloc(e->allocs, &e->d_in, inBytes, true))) return rc;
+        e->d_in_bytes = inBytes;
+    }
+    if (!e->d_pcm) {
+        if ((rc = dalloc(e->allocs, &e->d_pcm, nBlk * (size_t)e->C * e->BS, false))) return rc;
+        if ((rc = dalloc(e->allocs, &e->d_bits, nBlk, false))) return rc;
+    }
+    return ULCX_OK;
+}
+
 static int decode_dev_any(ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
     if (!e || !d_in || (!d_pcm && !d_pcm16) || !d_bits || slotBytes < 1 || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_decode_dev: bad argument"); return ULCX_ERR_ARG; }
     CKR(hipSetDevice(e->device));
@@ -814,17 +838,7 @@ extern "C" int ulcx_decode_host(ulcx_decoder *e, const uint8_t *h_in, int slotBy
     if (!e || !h_in || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK || slotBytes < 1) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
-    size_t inBytes = NBmax * (size_t)slotBytes + 16;
-    if (!e->d_in || e->d_in_bytes < inBytes) {
-        int rc;
-        if ((rc = dalloc(e->allocs, &e->d_in, inBytes, true))) return rc;
-        e->d_in_bytes = inBytes;
-    }
-    if (!e->d_pcm) {
-        int rc;
-        if ((rc = dalloc(e->allocs, &e->d_pcm, NBmax * cb, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_bits, NBmax, false))) return rc;
-    }
+    { int rc = dec_host_staging(e, NBmax, NBmax * (size_t)slotBytes + 16); if (rc) return rc; }
     CKR(hipMemcpy(e->d_in, h_in, NB * slotBytes, hipMemcpyHostToDevice));
     int rc = ulcx_decode_dev(e, e->d_in, slotBytes, nBlocks, e->d_pcm, e->d_bits, nullptr);
     if (rc) return rc;
@@ -847,9 +861,8 @@ extern "C" int ulcx_decode_block1_rng(ulcx_decoder *e, const uint8_t *h_in, int 
     if (nBytes > slot) nBytes = slot;
     if (!e->b1Init) {
         int rc;
-        if (!e->d_in || e->d_in_bytes < (size_t)slot + 16) { if ((rc = dalloc(e->allocs, &e->d_in, (size_t)slot + 16, true))) return rc; e->d_in_bytes = (size_t)slot + 16; }
-        if (!e->d_pcm) { if ((rc = dalloc(e->allocs, &e->d_pcm, cb, false))) return rc; if ((rc = dalloc(e->allocs, &e->d_bits, 1, false))) return rc; }
-        if (!e->b1Stream) CKR(hipStreamCreateWithFlags(&e->b1Stream, hipStreamNonBlocking));
+        if ((rc = dec_host_staging(e, 1, (size_t)slot + 16))) return rc;             // (one stream, one block per call)
+        if (!e->b1.stream) CKR(hipStreamCreateWithFlags(&e->b1.stream, hipStreamNonBlocking));
         if (!e->pinIn) CKR(hipHostMalloc((void **)&e->pinIn, (size_t)slot, hipHostMallocDefault));
         if (!e->pinPcm) CKR(hipHostMalloc((void **)&e->pinPcm, sizeof(float) * cb, hipHostMallocDefault));
         if (!e->pinMeta) CKR(hipHostMalloc((void **)&e->pinMeta, 4 * sizeof(int32_t), hipHostMallocDefault));
@@ -857,14 +870,14 @@ extern "C" int ulcx_decode_block1_rng(ulcx_decoder *e, const uint8_t *h_in, int 
         e->timing = false;
     }
     auto enqueue = [&]() -> int {
-        CKR(hipMemcpyAsync(e->d_in, e->pinIn, (size_t)slot, hipMemcpyHostToDevice, e->b1Stream));
-        CKR(hipMemcpyAsync(e->ctx.seed, &e->pinMeta[2], sizeof(uint32_t), hipMemcpyHostToDevice, e->b1Stream));
-        int rc = ulcx_decode_dev(e, e->d_in, slot, 1, e->d_pcm, e->d_bits, e->b1Stream);
+        CKR(hipMemcpyAsync(e->d_in, e->pinIn, (size_t)slot, hipMemcpyHostToDevice, e->b1.stream));
+        CKR(hipMemcpyAsync(e->ctx.seed, &e->pinMeta[2], sizeof(uint32_t), hipMemcpyHostToDevice, e->b1.stream));
+        int rc = ulcx_decode_dev(e, e->d_in, slot, 1, e->d_pcm, e->d_bits, e->b1.stream);
         if (rc) return rc;
-        CKR(hipMemcpyAsync(&e->pinMeta[3], e->ctx.seed, sizeof(uint32_t), hipMemcpyDeviceToHost, e->b1Stream));
-        CKR(hipMemcpyAsync(e->pinPcm, e->d_pcm, sizeof(float) * cb, hipMemcpyDeviceToHost, e->b1Stream));
-        CKR(hipMemcpyAsync(&e->pinMeta[0], e->d_bits, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1Stream));
-        CKR(hipMemcpyAsync(&e->pinMeta[1], e->ctx.lastSub, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1Stream));
+        CKR(hipMemcpyAsync(&e->pinMeta[3], e->ctx.seed, sizeof(uint32_t), hipMemcpyDeviceToHost, e->b1.stream));
+        CKR(hipMemcpyAsync(e->pinPcm, e->d_pcm, sizeof(float) * cb, hipMemcpyDeviceToHost, e->b1.stream));
+        CKR(hipMemcpyAsync(&e->pinMeta[0], e->d_bits, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1.stream));
+        CKR(hipMemcpyAsync(&e->pinMeta[1], e->ctx.lastSub, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1.stream));
         return ULCX_OK;
     };
     memcpy(e->pinIn, h_in, (size_t)nBytes);
@@ -876,22 +889,7 @@ extern "C" int ulcx_decode_block1_rng(ulcx_decoder *e, const uint8_t *h_in, int 
     e->b1SeedStale = false;
     e->pinMeta[2] = (int32_t)(rngState ? *rngState : e->b1Seed);
     struct InB1 { ulcx_decoder *d; InB1(ulcx_decoder *x) : d(x) { d->inBlock1 = true; } ~InB1() { d->inBlock1 = false; } } inB1(e);
-    if (!e->b1Graphed && !e->b1NoGraph) {
-        bool ok = hipStreamBeginCapture(e->b1Stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (ok) {
-            const int rc = enqueue();
-            hipGraph_t g = nullptr;
-            const hipError_t ee = hipStreamEndCapture(e->b1Stream, &g);
-            ok = (rc == ULCX_OK) && ee == hipSuccess && g != nullptr;
-            if (ok) ok = hipGraphInstantiate(&e->b1Exec, g, nullptr, nullptr, 0) == hipSuccess;
-            if (ok) { e->b1Graph = g; e->b1Graphed = true; }
-            else if (g) hipGraphDestroy(g);
-        }
-        if (!ok) { (void)hipGetLastError(); e->b1NoGraph = true; }
-    }
-    if (e->b1Graphed) CKR(hipGraphLaunch(e->b1Exec, e->b1Stream));
-    else { int rc = enqueue(); if (rc) return rc; }
-    CKR(hipStreamSynchronize(e->b1Stream));
+    { int rc = block1_run(e->b1, enqueue); if (rc) return rc; }
     memcpy(h_pcm, e->pinPcm, sizeof(float) * cb);
     if (bits) *bits = e->pinMeta[0];
     if (lastSubBlockSize) *lastSubBlockSize = e->pinMeta[1];
@@ -985,11 +983,7 @@ extern "C" int ulcx_decode_resident_host(ulcx_decoder *e, int nBlocks, float *h_
     if (!e->d_pay) { ulcx_set_error("ulcx_decode_resident_host: no payload uploaded"); return ULCX_ERR_ARG; }
     CKR(hipSetDevice(e->device));
     size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
-    if (!e->d_pcm) {
-        int rc0; size_t NBmax = (size_t)e->B * e->maxK;
-        if ((rc0 = dalloc(e->allocs, &e->d_pcm, NBmax * cb, false))) return rc0;
-        if ((rc0 = dalloc(e->allocs, &e->d_bits, NBmax, false))) return rc0;
-    }
+    { int rc0 = dec_host_staging(e, (size_t)e->B * e->maxK, 0); if (rc0) return rc0; }
     int rc = ulcx_decode_packed_dev(e, e->d_pay, e->payStride, e->d_payBytes, nBlocks, e->d_pcm, e->d_bits, nullptr);
     if (rc != ULCX_OK) return rc;
     CKR(hipDeviceSynchronize());

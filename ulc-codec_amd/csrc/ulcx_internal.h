@@ -170,7 +170,6 @@ __host__ __device__ static inline unsigned ulcx_pattern(int wc) {
 }
 
 // host side (ulcx_tables.cpp)
-struct UlcxHostTables;
 int  ulcx_tables_build(UlcxTables *devT, void **devBlob, int BS, int rateHz, bool forEncoder);
 void ulcx_set_error(const char *fmt, ...);
 
@@ -182,17 +181,21 @@ extern const char *const ulcx_enc_stage_names[ULCX_ENC_STAGES_REPORTED];
 #define ULCX_WC_MAXCH 32    // fine steps of the window-control pipeline per call
 #define ULCX_XF_MAXCH 8     // coarse transform chunks per call
 #define ULCX_LDS_LIMIT (160 * 1024)     // LDS per workgroup on gfx950
-// streams and events the encoder launch uses beside the caller's stream
-struct UlcxEncAux {
-    hipStream_t side, side2, side3;      // NULL: everything on the caller's stream
-    hipEvent_t evFork, evJoin, evFork2;  // exact-path fork/join
-    hipEvent_t *evWC;                    // [7 + 3*ULCX_WC_MAXCH] window-control pipeline; then noise-spectrum fork/join, k_cplx join, k_tailsums fork/join, k_state_update join
-    hipEvent_t *evXf;                    // [2*ULCX_XF_MAXCH] timing pairs around each transform launch (used when ev != NULL)
-    int wcPipe;                          // chunks of blocks pipelined between window control and transform; 1 = off
-    int wcSteps;                         // fine steps of the window-control kernels per call (ULCX_WC_STEPS)
-    int wcFuse;                          // stereo: envelope + forward recurrence in one kernel (k_wc_ef)
-    int nsSlots;                         // workgroups of k_nsums the device holds at once (its persistent grid)
-    int *nXf;                            // out: transform launches this call
+// Streams (all three, or none: everything on the caller's) and events of the encoder launch, one event per role; the untimed ones first: created and destroyed as an array.
+struct UlcxEncSync {
+    hipEvent_t wcStart, wcForward[ULCX_WC_MAXCH], wcBackward[ULCX_WC_MAXCH], wcDecided[ULCX_WC_MAXCH];   // window-control pipeline: caller's -> side, then per fine step side -> side2 -> side3 -> caller's
+    hipEvent_t xfChunkDone[ULCX_XF_MAXCH], cplxChunksDone;   // transform chunk j done: its k_cplx may start on side; every chunk's k_cplx done
+    hipEvent_t noiseFork, noiseDone, tailFork, tailDone;     // side2: noise log-spectrum behind the transform, joined in front of the writer; k_tails beside k_nsums
+    hipEvent_t cplxDone, stateDone;      // side3: k_cplx, joined in front of the selection; k_state_update, joined at the end of the call
+    hipEvent_t exactFork, exactFork2, exactJoin;             // exact path on side: behind the selection, behind the noise join, back
+    hipEvent_t xfTiming[2 * ULCX_XF_MAXCH];                  // timed: pairs around each transform launch of a pipelined call (recorded when ev != NULL)
+    hipStream_t side, side2, side3;
+};
+struct UlcxEncAux {                      // what a call's launch needs beside its UlcxEncCtx (filled by enc_aux, ulcx_api.cpp)
+    UlcxEncSync &sync;
+    int wcPipe;                          // chunks of blocks pipelined between window control and transform; 1 = off (> 1 only with side streams)
+    int wcSteps, wcFuse, nsSlots;        // fine window-control steps per call (ULCX_WC_STEPS); stereo: k_wc_ef; resident workgroups of k_nsums (its persistent grid)
+    int &nXf;                            // out: transform launches of a pipelined call (0: one launch, no xfTiming pairs)
 };
 int ulcx_enc_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev /* ULCX_ENC_STAGES+1 or NULL */, const UlcxEncAux &aux);
 struct UlcxDecAux {
@@ -204,10 +207,7 @@ size_t ulcx_dec_lds_bytes(int BS, int C, int fast, int twInLds);
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
-size_t ulcx_enc_xf_lds_bytes(int BS, int C);
-size_t ulcx_enc_xfa_lds_bytes(int BS, int C);            // the analysis call's MDCT-only transform
-// analysis call (include/ulc_amd.h: ulcx_analyse_dev); useKxf: the encode call's transform instead of the MDCT-only one (timing comparisons)
-int ulcx_analyse_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev /* ULCX_ENC_STAGES+1 or NULL */, const UlcxEncAux &aux, int useKxf);
+int ulcx_analyse_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux, int useKxf);   // ulcx_analyse_dev; useKxf: the encode call's transform instead of the MDCT-only one (timing comparisons)
 int ulcx_enc_nsums_slots(int BS, int C);                 // resident workgroups of k_nsums on the current device
 // FFT array padding of k_xf (ulcx_fft.h).  One complex per 8 makes every pass conflict-free but costs 2 KB of LDS at
 // BlockSize 2048 and with it the 4th workgroup per CU: measured 2.13 ms vs 1.88 ms with one per 16.
