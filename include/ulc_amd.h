@@ -220,6 +220,11 @@ int  ulcx_encoder_last_fallbacks(ulcx_encoder *enc);
  * whole stream each (ulcx_dec_tail_plan; 0 for an even cut, ulcx_dec_split_plan), and the workgroups of the synthesis kernel
  * the device holds at once (0: this geometry runs the general kernel, never cut). */
 int  ulcx_decoder_last_cut(ulcx_decoder *dec, int *workgroups, int *wholeStreams, int *residentWG);
+/* The cut of the last round for a range call (ulcx_decode_range_*): as ulcx_dec_tail_plan for calls of 24 blocks or more;
+ * shorter calls (6 blocks or more, more streams than residentWG) are cut into pieces of max(2, nBlocks / 4) blocks - in a range
+ * call a whole-stream workgroup runs the block in front of its range too, so a piece costs little more than it saves.
+ * A range call of more streams than the device holds takes this plan before the even cut. */
+int  ulcx_dec_range_tail_plan(int nStreams, int nBlocks, int residentWG, int *wholeStreams);
 /* Test hook: from the next call on every `every`-th block of a call (block index % every == 0) is handed to the exact
  * heapsort path whether or not its threshold tie group straddles the cut (0 = off, the default).  The results must not
  * change: the full ranking decides the same kept set.  Exercises that path at a scale natural ties never reach. */
@@ -307,6 +312,57 @@ int  ulcx_decode_packed_host(ulcx_decoder *dec, const uint8_t *h_payload, long l
  * from the device-resident copy.  (ulcx_decode_packed_host uploads all payloads on every call.) */
 int  ulcx_decoder_upload_payload(ulcx_decoder *dec, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes);
 int  ulcx_decode_resident_host(ulcx_decoder *dec, int nBlocks, float *h_pcm, int32_t *h_bits);
+
+/* Block index and seek: any block range of a packed stream without decoding what lies in front of it.
+ * The container stores no block lengths, so a block's start is known only once every block in front of it has been
+ * parsed.  The index is that walk done once, kept in a plain array the caller owns (it may be copied to the host, stored
+ * beside the file and uploaded again later): per stream maxBlocks + 1 entries of 8 bytes.
+ *   entry k, 0 <= k <= d_nBlocks[s]:  ByteOffs = byte of the stream's payload at which block k starts,
+ *                                     RngState = state of the stream's noise generator there (ulcDecoder.c:75-81; the chain
+ *                                     starts at 1234567, as every batched entry's does)
+ *   entry d_nBlocks[s] closes the table: position and state behind the last whole block, so that the extent of block k is
+ *   ByteOffs[k+1] - ByteOffs[k]; entries behind it are {-1, 0}.
+ *   d_nBlocks[s] = whole, valid blocks found, at most maxBlocks: the walk stops where ulcx_decode_packed_dev would report
+ *   0 bits (a corrupt block, the end of the payload).
+ * maxBlocks is not limited by maxBlocksPerCall (the call uses none of the decoder's per-block scratch: a whole file is
+ * indexed in one call).  The call reads the decoder's geometry and tables; it neither reads nor changes any stream's
+ * state or read position.  Nothing outside [d_payload, d_payload + nStreams*payloadStride) is read.  Asynchronous on
+ * hipStream; the _host form is synchronous. */
+typedef struct ulcx_index_entry { int32_t ByteOffs; uint32_t RngState; } ulcx_index_entry;
+int  ulcx_index_packed_dev(ulcx_decoder *dec, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                           int maxBlocks, ulcx_index_entry *d_index /* [nStreams][maxBlocks+1] */, int32_t *d_nBlocks /* [nStreams] */,
+                           void *hipStream);
+int  ulcx_index_packed_host(ulcx_decoder *dec, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                            int maxBlocks, ulcx_index_entry *h_index, int32_t *h_nBlocks);
+/* Decode blocks d_first[s] .. d_first[s] + nBlocks - 1 of every stream s.
+ *   d_index        [nStreams][indexStride] entries (indexStride = maxBlocks + 1 of the index call), d_indexBlocks [nStreams]
+ *                  its block counts
+ *   d_pcm          [nStreams][nBlocks][BlockSize][nChan], d_bits [nStreams][nBlocks]: bit for bit what a sequential decode from
+ *                  block 0 writes for those blocks, the noise included
+ * A block at or past d_indexBlocks[s] reports 0 bits and so does every later block of that stream in the call (as a
+ * stream's end does in ulcx_decode_packed_dev); a d_first[s] outside [0, d_indexBlocks[s]] gives a stream of 0 bits (the
+ * device forms cannot refuse it without a synchronisation; the host forms refuse a negative one with ULCX_ERR_ARG before
+ * any device work).  Nothing outside the call's buffers is read or written.
+ * After the call a stream's persistent state - lapping, LastSubBlockSize, generator, dead flag, packed read position - is
+ * exactly what a sequential decode up to and including block d_first[s] + nBlocks - 1 leaves: a following
+ * ulcx_decode_packed_dev on the same payload continues with the next block, and a later range call may go backwards.
+ * nBlocks is 1 .. maxBlocksPerCall - 1: the block in front of a range is parsed and synthesised without output (its
+ * lapping state is what the range's first block overlaps with) and takes one row of the call's per-block scratch. */
+int  ulcx_decode_range_dev(ulcx_decoder *dec, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                           const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                           const int32_t *d_first /* [nStreams] */, int nBlocks,
+                           float *d_pcm, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_range_dev_pcm16(ulcx_decoder *dec, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                 const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                 const int32_t *d_first, int nBlocks,
+                                 int16_t *d_pcm16 /* converted as ulcx_decode_dev_pcm16 converts */, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_range_host(ulcx_decoder *dec, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                            const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                            const int32_t *h_first, int nBlocks, float *h_pcm, int32_t *h_bits);   /* synchronous */
+/* The same on the payload uploaded with ulcx_decoder_upload_payload: the index is built once and kept in the decoder
+ * (h_nBlocks [nStreams], optional: the block counts), then any range is decoded from it.  A new upload drops the index. */
+int  ulcx_decoder_index_resident(ulcx_decoder *dec, int maxBlocks, int32_t *h_nBlocks);
+int  ulcx_decode_resident_range_host(ulcx_decoder *dec, const int32_t *h_first, int nBlocks, float *h_pcm, int32_t *h_bits);
 
 /* Timing helper for bench.py: device time (ms, hipEvent) of the kernels the last
  * ulcx_*_dev call enqueued, per pipeline stage; returns number of stages written.

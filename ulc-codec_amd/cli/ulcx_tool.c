@@ -2,7 +2,7 @@
  * ulcx_tool.c — batched front-end over libulc_amd.so.
  *
  *   ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav [-rate:RATE[,AvgComplexity]] IN2.wav ...
- *   ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N]             IN1.ulc IN2.ulc ...
+ *   ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-blocks:FIRST,COUNT] [-devices:N] IN1.ulc IN2.ulc ...
  *   ulcx-tool analyse [-blocksize:N] [-devices:N]                            IN1.wav IN2.wav ...
  *
  * What tools/ulcEncodeTool.c / tools/ulcDecodeTool.c of the reference do for ONE file per
@@ -24,6 +24,11 @@
  * All inputs of one call must share rate / channel count (encode) or rate / channels / block size
  * (decode); inputs may have different lengths (shorter ones are padded with silence and trimmed
  * to their own block count on output).
+ *
+ * -blocks:FIRST,COUNT (decode): each output holds blocks FIRST .. FIRST+COUNT-1 of its file only (trimmed where the file's
+ * header counts fewer), exactly the bytes a full decode writes for them: the payloads are indexed once on the device
+ * (ulcx_decoder_index_resident), then decoded by range calls (ulcx_decode_resident_range_host) - nothing in front of FIRST
+ * but one block is synthesised.
  *
  * -devices:N (independent streams shard by plain batch split, one host thread per device, no collective): the
  * inputs are dealt round-robin over N groups, every group gets its own encoder / decoder and its own host thread; group g
@@ -114,7 +119,8 @@ static void out_path(char *dst, size_t n, const char *dir, const char *in, const
 
 /* one group of inputs = one batch on one device (the whole command line, or a -devices:N share of it on its own thread);
  * encode: file i is encoded under {RateKbps, AvgComplexity} = setting[i]; autoc[i] = 1: "RATE,auto" (two passes) */
-struct group { int decode, analyse, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int bs, isFloat; int rc; };
+struct group { int decode, analyse, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int bs, isFloat; int rc;
+               int32_t rFirst, rCount; /* decode -blocks:FIRST,COUNT (rCount 0: whole files) */ };
 
 /* "RATE[,AvgComplexity]" or "RATE,auto", validated as ulcEncodeTool.c:43-50 does (and finite: the library refuses the rest) */
 static int parse_rate(const char *s, ulcx_rate *r, int *isAuto) {
@@ -311,6 +317,20 @@ static int decode_group(const struct group *g) {
         if (h[s].nBlocks > maxBlk) maxBlk = h[s].nBlocks;
     }
     const int bs = h[0].BlockSize, C = h[0].nChan;
+    /* -blocks:FIRST,COUNT: nOut[s] blocks of file s from block FIRST on; else the whole file */
+    const int range = g->rCount > 0;
+    uint32_t *nOut = (uint32_t *)calloc((size_t)B, sizeof(uint32_t));
+    int32_t *first = (int32_t *)calloc((size_t)B, sizeof(int32_t));
+    uint32_t total = maxBlk;
+    if (range) {
+        total = 0;
+        for (int s = 0; s < B; s++) {
+            if ((uint32_t)g->rFirst >= h[s].nBlocks) DIE("'%s': -blocks starts at block %d, the file has %u blocks", argv[a + s], (int)g->rFirst, h[s].nBlocks);
+            const uint32_t left = h[s].nBlocks - (uint32_t)g->rFirst;
+            nOut[s] = left < (uint32_t)g->rCount ? left : (uint32_t)g->rCount;
+            if (nOut[s] > total) total = nOut[s];
+        }
+    } else for (int s = 0; s < B; s++) nOut[s] = h[s].nBlocks;
     stride = (stride + 15) & ~15LL;
     uint8_t *payload = (uint8_t *)calloc((size_t)B, (size_t)stride);
     for (int s = 0; s < B; s++) { memcpy(payload + (size_t)s * stride, pay[s] + h[s].StreamOffs, (size_t)payBytes[s]); free(pay[s]); }
@@ -326,16 +346,22 @@ static int decode_group(const struct group *g) {
         out_path(path, sizeof(path), outdir, argv[a + s], ".wav");
         fo[s] = fopen(path, "wb");
         if (!fo[s]) DIE("cannot create '%s'", path);
-        wav_write_header(fo[s], (int)h[s].RateHz, C, isFloat, h[s].nBlocks * (uint32_t)bs);
+        wav_write_header(fo[s], (int)h[s].RateHz, C, isFloat, nOut[s] * (uint32_t)bs);
     }
     if (ulcx_decoder_upload_payload(dec, payload, stride, payBytes) != ULCX_OK) DIE("upload: %s", ulcx_last_error());   /* once, not per call */
     int rcAll = 0;
-    for (uint32_t k0 = 0; k0 < maxBlk; k0 += KBLOCKS) {
-        int K = (maxBlk - k0 < KBLOCKS) ? (int)(maxBlk - k0) : KBLOCKS;
-        if (ulcx_decode_resident_host(dec, K, pcm, bits) != ULCX_OK) DIE("decode: %s", ulcx_last_error());
+    /* (a range call runs the block in front of its range too: one block fewer per call) */
+    const uint32_t step = range ? KBLOCKS - 1 : KBLOCKS, blk0 = range ? (uint32_t)g->rFirst : 0;
+    if (range && ulcx_decoder_index_resident(dec, (int)(blk0 + total), NULL) != ULCX_OK) DIE("index: %s", ulcx_last_error());   /* once */
+    for (uint32_t k0 = 0; k0 < total; k0 += step) {
+        int K = (total - k0 < step) ? (int)(total - k0) : (int)step;
+        if (range) {
+            for (int s = 0; s < B; s++) first[s] = (int32_t)(blk0 + k0);
+            if (ulcx_decode_resident_range_host(dec, first, K, pcm, bits) != ULCX_OK) DIE("decode: %s", ulcx_last_error());
+        } else if (ulcx_decode_resident_host(dec, K, pcm, bits) != ULCX_OK) DIE("decode: %s", ulcx_last_error());
         for (int s = 0; s < B; s++)
-            for (int k = 0; k < K && k0 + (uint32_t)k < h[s].nBlocks; k++) {
-                if (!bits[s * K + k]) { fprintf(stderr, "ulcx-tool: %s: corrupted stream at block %u\n", argv[a + s], k0 + (uint32_t)k); rcAll = 1; }
+            for (int k = 0; k < K && k0 + (uint32_t)k < nOut[s]; k++) {
+                if (!bits[s * K + k]) { fprintf(stderr, "ulcx-tool: %s: corrupted stream at block %u\n", argv[a + s], blk0 + k0 + (uint32_t)k); rcAll = 1; }
                 const float *src = pcm + ((size_t)s * K + k) * frame;
                 if (isFloat) fwrite(src, 4, frame, fo[s]);
                 else {
@@ -350,7 +376,7 @@ static int decode_group(const struct group *g) {
     }
     for (int s = 0; s < B; s++) fclose(fo[s]);
     ulcx_decoder_destroy(dec);
-    free(payload); free(pcm); free(bits); free(tmp); free(fo); free(h); free(pay); free(payBytes);
+    free(payload); free(pcm); free(bits); free(tmp); free(fo); free(h); free(pay); free(payBytes); free(nOut); free(first);
     return rcAll;
 }
 
@@ -462,7 +488,7 @@ static int do_analyse(int argc, char **argv) {
     return run_groups(&g, argc - a, argv + a, nDev);
 }
 static int do_decode(int argc, char **argv) {
-    if (argc < 4) DIE("usage: ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N] IN.ulc ...");
+    if (argc < 4) DIE("usage: ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-blocks:FIRST,COUNT] [-devices:N] IN.ulc ...");
     struct group g; memset(&g, 0, sizeof(g));
     g.decode = 1; g.outdir = argv[2];
     int a = 3, nDev = 1;
@@ -473,7 +499,16 @@ static int do_decode(int argc, char **argv) {
             if (!strcmp(f, "FLOAT32") || !strcmp(f, "float32")) g.isFloat = 1;
             else if (strcmp(f, "PCM16") && strcmp(f, "pcm16")) DIE("unsupported output format '%s'", f);
         } else if (!strncmp(argv[a], "-devices:", 9)) nDev = atoi(argv[a] + 9);
-        else DIE("unknown option '%s'", argv[a]);
+        else if (!strncmp(argv[a], "-blocks:", 8)) {
+            /* FIRST >= 0, COUNT >= 1, both plain decimal numbers; FIRST + COUNT within the container's 32-bit block count */
+            char *e1 = NULL, *e2 = NULL;
+            const char *v = argv[a] + 8;
+            const long long f = strtoll(v, &e1, 10);
+            const long long n = (e1 != v && *e1 == ',') ? strtoll(e1 + 1, &e2, 10) : 0;
+            if (e1 == v || *e1 != ',' || e2 == e1 + 1 || *e2 || v[0] == '+' || e1[1] == '+' || f < 0 || n < 1 || f > 0x3fffffffLL || n > 0x3fffffffLL)
+                DIE("invalid block range '%s' (-blocks:FIRST,COUNT with FIRST >= 0, COUNT >= 1)", argv[a]);
+            g.rFirst = (int32_t)f; g.rCount = (int32_t)n;
+        } else DIE("unknown option '%s'", argv[a]);
     }
     if (nDev < 1 || nDev > 64) DIE("-devices:%d out of range", nDev);
     return run_groups(&g, argc - a, argv + a, nDev);
@@ -489,7 +524,8 @@ int main(int argc, char **argv) {
             "      RATE < 0: VBR quality; RATE > 0: CBR kbps; RATE,AvgComplexity: ABR  (as ulcencodetool)\n"
             "      RATE,auto: two-pass ABR at each file's own average complexity (0: CBR)\n"
             "      -rate:RATE[,AvgComplexity|,auto]  setting of the inputs that follow it (RATE is the default)\n"
-            "  ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-devices:N] IN1.ulc IN2.ulc ...\n"
+            "  ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-blocks:FIRST,COUNT] [-devices:N] IN1.ulc IN2.ulc ...\n"
+            "      -blocks:FIRST,COUNT  only blocks FIRST .. FIRST+COUNT-1 of every file (block index + range decode)\n"
             "  ulcx-tool analyse [-blocksize:N] [-devices:N] IN1.wav IN2.wav ...\n"
             "      per file: blocks, the average complexity to feed RATE,<complexity> with, window-switched blocks; writes no file\n"
             "  --          end of options (input names that start with '-')\n"

@@ -74,10 +74,13 @@ struct ulcx_decoder {
     bool evOk = false, evRecorded = false, timing = true;
     uint8_t *d_in = nullptr; size_t d_in_bytes = 0; float *d_pcm = nullptr; int32_t *d_bits = nullptr;
     uint8_t *d_pay = nullptr; int32_t *d_payBytes = nullptr; long long payStride = 0;     // resident packed payloads (ulcx_decoder_upload_payload)
+    // block index of the resident payloads (ulcx_decoder_index_resident) and the staged range starts of the host-pointer range entries
+    ulcx_index_entry *d_index = nullptr; int32_t *d_idxBlocks = nullptr, *d_first = nullptr; int idxStride = 0;
+    int32_t *bitsScr = nullptr;                                   // [B][maxK] block sizes of a range call's rows (the scan's; the caller's array has no row for the block in front)
     // k_dsyn over an even cut of the call's (stream, block) pairs: the second set of state arrays, the resident
     // workgroups of the kernel on this device, ULCX_DSYN_SPLIT=0 switches it off
     float *lap2 = nullptr; int *lastSub2 = nullptr; uint32_t *seed2 = nullptr; int *dead2 = nullptr;
-    int synSlots = 0, scratchRows = 0, lastGrid = 0, lastFull = 0; bool splitOK = false, tailCut = true;
+    int synSlots = 0, scratchRows = 0, lastGrid = 0, lastFull = 0; bool splitOK = false, tailCut = true, rangeEvenFirst = false;
     // single-block path (ulcx_decode_block1)
     Block1Graph b1; bool b1Init = false; int b1Slot = 0;
     uint8_t *pinIn = nullptr; float *pinPcm = nullptr; int32_t *pinMeta = nullptr;
@@ -590,6 +593,8 @@ static void cleanup(ulcx_decoder *e) {
     for (void *p : e->allocs) hipFree(p);
     if (e->d_pay) hipFree(e->d_pay);
     if (e->d_payBytes) hipFree(e->d_payBytes);
+    if (e->d_index) hipFree(e->d_index);
+    if (e->d_idxBlocks) hipFree(e->d_idxBlocks);
     if (e->tables) hipFree(e->tables);
     if (e->evOk) for (auto &v : e->ev) hipEventDestroy(v);
     block1_drop(e->b1);
@@ -694,6 +699,22 @@ extern "C" int ulcx_dec_tail_plan(int nStreams, int nBlocks, int residentWG, int
     if (full) *full = nStreams - rem;
     return (int)n;
 }
+// Range calls (ulcx_decode_range_*).  Every workgroup that enters a stream runs the block in front of its range without output,
+// a whole-stream workgroup too: a piece of the last round costs its blocks + 1 against nBlocks + 1 for a whole stream, so
+// short calls are worth cutting as well, into shorter pieces (a quarter of the call, at least 2 blocks; three pieces per
+// stream at least, i.e. calls of 6 blocks or more).  Calls of 24 blocks or more are cut as any other call is.  Only when
+// there is a whole round in front of the last one.
+extern "C" int ulcx_dec_range_tail_plan(int nStreams, int nBlocks, int residentWG, int *full) {
+    if (nBlocks >= 3 * ULCX_DSYN_TAIL_LEN) return ulcx_dec_tail_plan(nStreams, nBlocks, residentWG, full);
+    if (full) *full = 0;
+    if (nStreams < 1 || nBlocks < 1 || residentWG < 1 || nStreams <= residentWG) return 0;
+    const int len = nBlocks / 4 > 2 ? nBlocks / 4 : 2;
+    if (nBlocks < 3 * len) return 0;
+    const int rem = nStreams % residentWG;
+    if (rem == 0 || (long long)rem * 5 > (long long)residentWG * 4) return 0;
+    if (full) *full = nStreams - rem;
+    return (int)((long long)rem * nBlocks / len);
+}
 extern "C" int ulcx_decoder_last_cut(ulcx_decoder *e, int *workgroups, int *wholeStreams, int *residentWG) {
     if (!e) return ULCX_ERR_ARG;
     if (workgroups) *workgroups = e->lastGrid;
@@ -706,15 +727,24 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st) {
     UlcxDecAux a;
     a.synGrid = 0; a.synFull = 0;
     c.lapO = c.lap; c.lastSubO = c.lastSub; c.seedO = c.seed; c.deadO = c.dead;
+    const int Kc = c.range ? c.K - 1 : c.K;                       // blocks of the call per stream (a range call's K counts the row of the block in front)
     if (e->splitOK && e->synSlots > 0) {
-        a.synGrid = ulcx_dec_split_plan(e->B, c.K, e->synSlots);
+        // A range call of more streams than the device holds at once: whole rounds, and the last one cut
+        // (ulcx_dec_range_tail_plan) - an even cut of everything ends every workgroup inside a stream, and in a range call every
+        // entry into a stream costs the block in front of the range (ULCX_RANGE_CUT=even: the even cut first, as for other calls)
+        if (c.range && e->B > e->synSlots && e->tailCut && !e->rangeEvenFirst) {
+            int full = 0;
+            const int tail = ulcx_dec_range_tail_plan(e->B, Kc, e->synSlots, &full);
+            if (tail > 0 && tail <= e->scratchRows) { a.synGrid = full + tail; a.synFull = full; }
+        }
+        if (!a.synGrid) a.synGrid = ulcx_dec_split_plan(e->B, Kc, e->synSlots);
         if (!a.synGrid) {
             int full = 0;
-            const int tail = ulcx_dec_tail_plan(e->B, c.K, e->synSlots, &full);
+            const int tail = c.range ? ulcx_dec_range_tail_plan(e->B, Kc, e->synSlots, &full) : ulcx_dec_tail_plan(e->B, Kc, e->synSlots, &full);
             if (tail > 0 && tail <= e->scratchRows && e->tailCut) { a.synGrid = full + tail; a.synFull = full; }
         }
         if (a.synGrid) {
-            if (getenv("ULCX_DEBUG_PRINT")) fprintf(stderr, "[ulcx] synthesis: %lld (stream, block) pairs over %d workgroups (%d of them one stream each; %d resident)\n", (long long)e->B * c.K, a.synGrid, a.synFull, e->synSlots);
+            if (getenv("ULCX_DEBUG_PRINT")) fprintf(stderr, "[ulcx] synthesis: %lld (stream, block) pairs over %d workgroups (%d of them one stream each; %d resident)\n", (long long)e->B * Kc, a.synGrid, a.synFull, e->synSlots);
             c.lapO = e->lap2; c.lastSubO = e->lastSub2; c.seedO = e->seed2; c.deadO = e->dead2;
         }
     }
@@ -757,6 +787,7 @@ extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams,
         bool want = true;
         if (const char *ev = getenv("ULCX_DSYN_SPLIT")) want = ev[0] != '0';
         if (const char *ev = getenv("ULCX_DSYN_TAIL")) e->tailCut = ev[0] != '0';          // (A/B: the last round uncut)
+        if (const char *ev = getenv("ULCX_RANGE_CUT")) e->rangeEvenFirst = !strcmp(ev, "even");   // (A/B: range calls planned as other calls are)
         e->synSlots = want ? ulcx_dec_syn_slots(c) : 0;
         if (e->synSlots > 0) {
             DA(e->lap2, B * nChan * (BlockSize / 2), true);
@@ -772,6 +803,8 @@ extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams,
     DA(c.draws, NB, true);
     DA(c.packOff, B, true);
     DA(c.blkOff, NB, true);
+    DA(c.rInfo, B, true);
+    DA(e->bitsScr, NB, true);
     DA(c.unitDraws, NB * nChan * 4, true);
     DA(c.unitTail, NB * nChan * 4, true);
     DA(c.unitRec, NB * nChan * 4, true);
@@ -970,6 +1003,7 @@ extern "C" int ulcx_decoder_upload_payload(ulcx_decoder *e, const uint8_t *h_pay
     CKR(hipSetDevice(e->device));
     if (e->d_pay) { hipFree(e->d_pay); e->d_pay = nullptr; }
     if (e->d_payBytes) { hipFree(e->d_payBytes); e->d_payBytes = nullptr; }
+    if (e->d_index) { hipFree(e->d_index); e->d_index = nullptr; e->idxStride = 0; }      // (the index belongs to the payload it was built from)
     size_t bytes = (size_t)e->B * (size_t)payloadStride;
     CKR(hipMalloc((void **)&e->d_pay, bytes + 16)); CKR(hipMalloc((void **)&e->d_payBytes, sizeof(int32_t) * e->B));
     CKR(hipMemset(e->d_pay, 0, bytes + 16));
@@ -985,6 +1019,123 @@ extern "C" int ulcx_decode_resident_host(ulcx_decoder *e, int nBlocks, float *h_
     size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
     { int rc0 = dec_host_staging(e, (size_t)e->B * e->maxK, 0); if (rc0) return rc0; }
     int rc = ulcx_decode_packed_dev(e, e->d_pay, e->payStride, e->d_payBytes, nBlocks, e->d_pcm, e->d_bits, nullptr);
+    if (rc != ULCX_OK) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Block index and range decode (include/ulc_amd.h section 3)
+// ---------------------------------------------------------------------------
+extern "C" int ulcx_index_packed_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                     int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
+    if (!e || !d_payload || !d_payloadBytes || !d_index || !d_nBlocks || payloadStride < 1 || maxBlocks < 1) { ulcx_set_error("ulcx_index_packed_dev: bad argument"); return ULCX_ERR_ARG; }
+    CKR(hipSetDevice(e->device));
+    UlcxDecCtx c = e->ctx;
+    c.in = d_payload; c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
+    c.inBytes = (long long)e->B * payloadStride;
+    return ulcx_index_launch(c, maxBlocks, d_index, d_nBlocks, (hipStream_t)hipStream);
+}
+// device buffers of a host-pointer call, freed when it returns
+namespace { struct DevTmp { std::vector<void *> v; ~DevTmp() { for (void *p : v) hipFree(p); } template <typename T> hipError_t get(T **p, size_t bytes) { void *q = nullptr; hipError_t r = hipMalloc(&q, bytes ? bytes : 16); if (r == hipSuccess) v.push_back(q); *p = (T *)q; return r; } }; }
+extern "C" int ulcx_index_packed_host(ulcx_decoder *e, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                      int maxBlocks, ulcx_index_entry *h_index, int32_t *h_nBlocks) {
+    if (!e || !h_payload || !h_payloadBytes || !h_index || !h_nBlocks || payloadStride < 1 || maxBlocks < 1) { ulcx_set_error("ulcx_index_packed_host: bad argument"); return ULCX_ERR_ARG; }
+    CKR(hipSetDevice(e->device));
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr; ulcx_index_entry *di = nullptr;
+    const size_t bytes = (size_t)e->B * (size_t)payloadStride, nEnt = (size_t)e->B * ((size_t)maxBlocks + 1);
+    CKR(t.get(&dp, bytes)); CKR(t.get(&dn, sizeof(int32_t) * e->B)); CKR(t.get(&dcnt, sizeof(int32_t) * e->B)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    CKR(hipMemcpy(dp, h_payload, bytes, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dn, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    int rc = ulcx_index_packed_dev(e, dp, payloadStride, dn, maxBlocks, di, dcnt, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * nEnt, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * e->B, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+static int decode_range_any(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                            const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const int32_t *d_first, int nBlocks,
+                            float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    // (the block in front of a range takes one row of the per-block scratch: nBlocks <= maxBlocksPerCall - 1)
+    if (!e || !d_payload || !d_payloadBytes || !d_index || !d_indexBlocks || !d_first || (!d_pcm && !d_pcm16) || !d_bits ||
+        payloadStride < 1 || indexStride < 1 || nBlocks < 1 || nBlocks > e->maxK - 1) { ulcx_set_error("ulcx_decode_range: bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return ULCX_ERR_ARG; }
+    CKR(hipSetDevice(e->device));
+    UlcxDecCtx c = e->ctx;
+    c.K = nBlocks + 1; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = d_pcm16;
+    c.bits = e->bitsScr; c.bitsOut = d_bits;
+    c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
+    c.inBytes = (long long)e->B * payloadStride;
+    c.range = 1; c.rIndex = d_index; c.rIndexStride = indexStride; c.rIndexBlocks = d_indexBlocks; c.rFirst = d_first;
+    int rc = dec_launch(e, c, (hipStream_t)hipStream);
+    e->evRecorded = (rc == ULCX_OK) && e->timing;
+    return rc;
+}
+extern "C" int ulcx_decode_range_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                     const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const int32_t *d_first, int nBlocks,
+                                     float *d_pcm, int32_t *d_bits, void *hipStream) {
+    if (!d_pcm) { ulcx_set_error("ulcx_decode_range_dev: bad argument"); return ULCX_ERR_ARG; }
+    return decode_range_any(e, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_first, nBlocks, d_pcm, nullptr, d_bits, hipStream);
+}
+extern "C" int ulcx_decode_range_dev_pcm16(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                           const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const int32_t *d_first, int nBlocks,
+                                           int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    if (!d_pcm16) { ulcx_set_error("ulcx_decode_range_dev_pcm16: bad argument"); return ULCX_ERR_ARG; }
+    return decode_range_any(e, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_first, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
+}
+static int range_first_ok(const ulcx_decoder *e, const int32_t *h_first, const char *who) {
+    for (int s = 0; s < e->B; s++) if (h_first[s] < 0) { ulcx_set_error("%s: stream %d starts at block %d", who, s, (int)h_first[s]); return 0; }
+    return 1;
+}
+extern "C" int ulcx_decode_range_host(ulcx_decoder *e, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                      const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks, const int32_t *h_first, int nBlocks,
+                                      float *h_pcm, int32_t *h_bits) {
+    if (!e || !h_payload || !h_payloadBytes || !h_index || !h_indexBlocks || !h_first || !h_pcm || !h_bits ||
+        payloadStride < 1 || indexStride < 1 || nBlocks < 1 || nBlocks > e->maxK - 1) { ulcx_set_error("ulcx_decode_range_host: bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return ULCX_ERR_ARG; }
+    if (!range_first_ok(e, h_first, "ulcx_decode_range_host")) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    const size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks, bytes = (size_t)e->B * (size_t)payloadStride, nEnt = (size_t)e->B * (size_t)indexStride;
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr, *df = nullptr, *dbits = nullptr; ulcx_index_entry *di = nullptr; float *dpcm = nullptr;
+    CKR(t.get(&dp, bytes)); CKR(t.get(&dn, sizeof(int32_t) * e->B)); CKR(t.get(&dcnt, sizeof(int32_t) * e->B)); CKR(t.get(&df, sizeof(int32_t) * e->B));
+    CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt)); CKR(t.get(&dpcm, sizeof(float) * NB * cb)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
+    CKR(hipMemcpy(dp, h_payload, bytes, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dn, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(df, h_first, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
+    int rc = ulcx_decode_range_dev(e, dp, payloadStride, dn, di, indexStride, dcnt, df, nBlocks, dpcm, dbits, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_pcm, dpcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, dbits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+extern "C" int ulcx_decoder_index_resident(ulcx_decoder *e, int maxBlocks, int32_t *h_nBlocks) {
+    if (!e || maxBlocks < 1) { ulcx_set_error("ulcx_decoder_index_resident: bad argument"); return ULCX_ERR_ARG; }
+    if (!e->d_pay) { ulcx_set_error("ulcx_decoder_index_resident: no payload uploaded"); return ULCX_ERR_ARG; }
+    CKR(hipSetDevice(e->device));
+    if (e->d_index) { hipFree(e->d_index); e->d_index = nullptr; e->idxStride = 0; }
+    CKR(hipMalloc((void **)&e->d_index, sizeof(ulcx_index_entry) * (size_t)e->B * ((size_t)maxBlocks + 1)));
+    if (!e->d_idxBlocks) CKR(hipMalloc((void **)&e->d_idxBlocks, sizeof(int32_t) * e->B));
+    int rc = ulcx_index_packed_dev(e, e->d_pay, e->payStride, e->d_payBytes, maxBlocks, e->d_index, e->d_idxBlocks, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    e->idxStride = maxBlocks + 1;
+    if (h_nBlocks) CKR(hipMemcpy(h_nBlocks, e->d_idxBlocks, sizeof(int32_t) * e->B, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+extern "C" int ulcx_decode_resident_range_host(ulcx_decoder *e, const int32_t *h_first, int nBlocks, float *h_pcm, int32_t *h_bits) {
+    if (!e || !h_first || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK - 1) { ulcx_set_error("ulcx_decode_resident_range_host: bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return ULCX_ERR_ARG; }
+    if (!e->d_pay || !e->idxStride) { ulcx_set_error("ulcx_decode_resident_range_host: no payload uploaded, or not indexed (ulcx_decoder_index_resident)"); return ULCX_ERR_ARG; }
+    if (!range_first_ok(e, h_first, "ulcx_decode_resident_range_host")) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    const size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
+    { int rc0 = dec_host_staging(e, (size_t)e->B * e->maxK, 0); if (rc0) return rc0; }
+    if (!e->d_first) { int rc0 = dalloc(e->allocs, &e->d_first, (size_t)e->B, true); if (rc0) return rc0; }
+    CKR(hipMemcpy(e->d_first, h_first, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    int rc = ulcx_decode_range_dev(e, e->d_pay, e->payStride, e->d_payBytes, e->d_index, e->idxStride, e->d_idxBlocks, e->d_first, nBlocks, e->d_pcm, e->d_bits, nullptr);
     if (rc != ULCX_OK) return rc;
     CKR(hipDeviceSynchronize());
     CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));

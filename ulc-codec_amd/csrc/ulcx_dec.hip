@@ -428,6 +428,104 @@ __global__ __launch_bounds__(64) void k_dscan_packed(UlcxDecCtx c) {
     c.packOff[s] = off;
 }
 
+// Pass 1 of a range call (ulcx_decode_range_*) - one lane per (stream, row), as k_dscan: the block index gives every
+// block's start and its exact extent, so nothing is walked in series.  Row r of stream s is block rFirst[s] - 1 + r (row 0:
+// the block in front of the range).  A row without a block - in front of block 0, at or past the index's block count, of a
+// stream whose start lies outside its index - is marked as a corrupt block is (window code 0: the stream ends there).  The
+// table is not trusted: an entry that points outside its stream's payload marks its row the same way.
+__global__ __launch_bounds__(64) void k_dscan_range(UlcxDecCtx c) {
+    __shared__ uint2 ringP[DSCAN_RP * 64], ringN[DSCAN_RN * 64];
+    const int id0 = blockIdx.x * 64 + threadIdx.x, K = c.K;
+    const bool live0 = id0 < c.B * K;
+    const int id = live0 ? id0 : c.B * K - 1;                             // (a lane without a row shadows the last one, and writes nothing)
+    const int s = id / K, r = id - s * K;
+    int nI = c.rIndexBlocks[s];
+    nI = nI < 0 ? 0 : nI > c.rIndexStride - 1 ? c.rIndexStride - 1 : nI;
+    const int first = c.rFirst[s];
+    const bool okS = first >= 0 && first <= nI;
+    const int k = first - 1 + r;
+    const ulcx_index_entry *row = c.rIndex + (size_t)s * c.rIndexStride;
+    int off = 0, ext = 0;
+    if (okS && k >= 0 && k < nI) { off = row[k].ByteOffs; ext = row[k + 1].ByteOffs - off; }
+    long long avail = c.payBytes[s];
+    avail = avail > c.payStride ? c.payStride : avail;
+    const bool sane = off >= 0 && ext > 0 && (long long)off + ext <= avail;
+    if (!sane) { off = 0; ext = 0; }
+    const uint8_t *p = c.in + (size_t)s * c.payStride + off, *bufEnd = c.in + c.inBytes;
+    // every look of every lane of the wave inside the buffer (k_dscan): the window without bounds checks
+    const bool inside = (size_t)(p - c.in) >= ((uintptr_t)p & 15) && (size_t)(bufEnd - p) >= (size_t)ext + 80;
+    const int blk = s * K + r;
+    const bool live = live0 && sane;
+    if (__ballot(!inside) == 0ull) scan_block<NybWinFast, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
+    else scan_block<NybWin, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
+    if (live0 && !sane) { c.bits[blk] = 0; c.wcScan[blk] = 0; c.draws[blk] = 0; }
+    if (live0 && r == 0) {
+        // what the synthesis needs to enter the stream, and the packed read position behind the range (the closing entry
+        // when the range runs past the stream's end: where a sequential decode stops)
+        const int pre = (okS && first > 0) ? 1 : 0;
+        c.rInfo[s] = make_int2(pre, okS ? (int)row[first - pre].RngState : 0);
+        if (okS) { const int e = first + K - 1; c.packOff[s] = row[e < nI ? e : nI].ByteOffs; }
+    }
+}
+
+// The walk of scan_block without its notes (k_dindex): the same syntax decisions, no records, no tail chains.  Returns the
+// bits consumed (0 = corrupt) and the block's draw count.
+template <typename WIN>
+__device__ __forceinline__ int walk_block(const UlcxDecCtx &c, const uint8_t *p, int limit, int readBytes,
+                                          const uint8_t *bufBeg, const uint8_t *bufEnd, int &drawsOut) {
+    WIN win; win.init(p, readBytes, bufBeg, bufEnd);
+    int pos, wc;
+    {
+        uint32_t w0 = (limit >= 8) ? win.at(0) : 0;                 // ulcDecoder.c:211-216
+        wc = w0 & 0xF;
+        bool dec = (wc & 0x8) != 0;
+        wc |= dec ? (int)(w0 & 0xF0) : (1 << 4);
+        pos = dec ? 8 : 4;
+    }
+    const unsigned pat = ulcx_pattern(wc);
+    int nsub = 0; { unsigned q = pat; do nsub++; while (q >>= 4); }
+    if ((c.BS >> (pat & 7)) == c.BS) nsub = 1;                      // ulcDecoder.c:242-245
+    const int total = c.C * nsub;
+    int u = 0, uj = 0, draws = 0;
+    int N = c.BS >> (pat & 7);
+    bool first = true, fin = limit < 16, bad = fin;
+    auto next_unit = [&]() {
+        u++;
+        fin = bad | (u >= total);
+        if (!fin) {
+            uj = (uj + 1 == nsub) ? 0 : uj + 1;
+            N = c.BS >> ((pat >> (4 * uj)) & 7);
+            first = true;
+        }
+    };
+    while (!fin) {
+        const uint64_t w64 = win.at64(pos);
+        uint32_t w = (uint32_t)w64;
+        int m = first ? 0 : plain_prefix(w);
+        m = m < N ? m : N;
+        m = (pos + 4 * m <= limit) ? m : 0;
+        if (m > 0) {
+            pos += 4 * m; N -= m;
+            if (N == 0) next_unit();
+            w = (uint32_t)(w64 >> (4 * m));
+        }
+        if (!fin) {
+            const Code k = decode_code(w, first);
+            const bool over = (k.zrun & (k.n > N)) | (k.n8 & (k.np > N));     // ulcDecoder.c:127,139,154
+            const int used = over ? 0 : ((k.stop | k.tail) ? N : k.n + k.np);
+            draws += over ? 0 : (k.tail ? N : k.np);
+            pos += 4 * k.len;
+            N -= used;
+            bad |= over;
+            first = false;
+            if ((N == 0) | over) next_unit();
+            if (pos > limit) { bad = true; fin = true; }               // ran off the readable bytes: corrupt
+        }
+    }
+    drawsOut = draws;
+    return bad ? 0 : pos;
+}
+
 // ---------------------------------------------------------------------------
 // xorshift32 is linear over GF(2): the state after n draws is T^n * state.  jumpT holds T^(d*16^i) for every
 // hexadecimal digit d of n at every position i, each as four 256-entry byte tables (host-built, ulcx_api.cpp):
@@ -442,6 +540,31 @@ __device__ __forceinline__ uint32_t rng_jump(const uint32_t *__restrict__ jt, ui
         }
     }
     return s;
+}
+
+// Block index of packed payloads (ulcx_index_packed_*) - one lane per stream, the walk of k_dscan_packed and nothing else:
+// per block its start and the state the stream's one generator chain has there (one jump by the block's draws).  It stops
+// where k_dscan_packed reports 0 bits.  No stream state, none of the per-block scratch.
+__global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx_index_entry *index, int32_t *nBlocks) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= c.B) return;
+    const int avail = c.payBytes[s];
+    const uint8_t *base = c.in + (size_t)s * c.payStride;
+    ulcx_index_entry *row = index + (size_t)s * ((size_t)maxBlocks + 1);
+    int off = 0, n = 0;
+    uint32_t st = 1234567u;                                          // ulcDecoder.c:76
+    row[0].ByteOffs = 0; row[0].RngState = st;
+    while (n < maxBlocks && off < avail) {
+        int draws;
+        const int bits = walk_block<NybWin>(c, base + off, (avail - off) * 8, avail - off, c.in, c.in + c.inBytes, draws);
+        if (!bits) break;
+        off += (bits + 7) >> 3;                                      // the tool rounds every block up to a byte
+        st = rng_jump(c.jumpT, st, (uint32_t)draws);
+        n++;
+        row[n].ByteOffs = off; row[n].RngState = st;
+    }
+    for (int k = n + 1; k <= maxBlocks; k++) { row[k].ByteOffs = -1; row[k].RngState = 0u; }
+    nBlocks[s] = n;
 }
 
 // wave-wide inclusive prefix sum / prefix maximum of one 32-bit value per lane (row shifts + row broadcasts)
@@ -760,8 +883,12 @@ __host__ __device__ static inline DsynLds dsyn_lds(int BS, int C, int fast, int 
 // workgroup per stream: the index arithmetic and the choice of the lapping rows below fold away)
 // BSC: BlockSize as a compile-time constant (2048: the headline geometry - the loops of an un-decimated block unroll, the
 // table and lapping-state loads of a thread's trips can be issued together; 0: read from the context)
-template <typename OUT, int DEC_MAXT, bool TWL, bool SPLIT = false, int BSC = 0>
+// RANGE: a range call (ulcx_decode_range_*; always with SPLIT).  A stream is entered from nothing instead of from its
+// persistent state: zero lapping state, the generator state the block index holds, and - unless the range starts at
+// block 0 - the block in front of it (row k0 - 1 of the stream) run without output, as a cut enters a stream.
+template <typename OUT, int DEC_MAXT, bool TWL, bool SPLIT = false, int BSC = 0, bool RANGE = false>
 __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
+    static_assert(!RANGE || SPLIT, "k_dsyn: a range call enters streams as a cut does");
     constexpr bool LAPG = true;
     extern __shared__ float lds[];
     const int BS = BSC ? BSC : c.BS, H2 = BS / 2;
@@ -820,6 +947,12 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
     bool warm = SPLIT && (f0 % Kc) != 0;
     int nTrip = (int)(f1 - f0) + (warm ? 1 : 0);
     int s = c.s0 + (int)((f0 - (warm ? 1 : 0)) / Kc), k = c.k0 + (int)((f0 - (warm ? 1 : 0)) % Kc) - 1;
+    if constexpr (RANGE) {
+        if (f0 % Kc == 0) {                                          // at a stream's start: its block in front first, if it has one
+            const int pre = c.rInfo[s].x;
+            warm = pre != 0; nTrip += pre; k -= pre;
+        }
+    }
     int sCur = -1, lastSub = 0, dead = 0, chunkK = -1;
     uint32_t seed = 0;
     const int laneOuter = lane, tidOuter = tid;
@@ -830,7 +963,10 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
         int lane = laneOuter, tid = tidOuter;
         asm volatile("" : "+v"(lane), "+v"(tid));
         sw.lane = lane;                                              // (round 3: 168 registers with spills -> 156 without, 1.05 -> 1.00 ms)
-        if (++k == c.k1) { k = c.k0; s++; }
+        if (++k == c.k1) {
+            k = c.k0; s++;
+            if constexpr (RANGE) { if (c.rInfo[s].x) { k = c.k0 - 1; warm = true; nTrip++; } }
+        }
         const int blk = s * c.K + k;
         if (s != sCur) {
             // entering a stream, at its first block of the launch or behind it: the state in front of block k
@@ -839,16 +975,18 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
             if (!LAPG) { const float *gi = c.lap + (size_t)s * C * H2; for (int i = tid; i < 2 * H2; i += WG) ldsLap[i] = gi[i]; }
             __syncthreads();
             int bad = 0; uint32_t dsum = 0;
-            for (int j = c.k0 + tid; j < k; j += WG) {               // blocks of the launch in front of k (none at the stream's start)
+            const int kf = RANGE ? c.k0 - c.rInfo[s].x : c.k0;       // the stream's first row of the launch
+            for (int j = kf + tid; j < k; j += WG) {                 // blocks of the launch in front of k (none at the stream's start)
                 const int bj = s * c.K + j;
                 if (c.wcScan[bj] == 0) bad = 1;
                 dsum += (uint32_t)c.draws[bj];
             }
             bad = __syncthreads_or(bad);
-            dead = c.dead[s] | bad;                                  // (a corrupt block in front: the stream is dead, no other state matters)
-            lastSub = c.lastSub[s];
-            seed = c.seed[s];
-            if (k > c.k0) {
+            dead = RANGE ? bad : (c.dead[s] | bad);                  // (a corrupt block in front: the stream is dead, no other state matters)
+            lastSub = RANGE ? 0 : c.lastSub[s];
+            seed = RANGE ? (uint32_t)c.rInfo[s].y : c.seed[s];
+            if constexpr (RANGE) { if (k == c.k0 && kf == c.k0) for (int i = tid; i < 2 * H2; i += WG) scr[i] = 0.0f; }   // a range from block 0: nothing pending (ordered by the barrier in front of the chunk's tables)
+            if (k > kf) {
                 const uint32_t ws = wave_scan_add(dsum);             // (lane 63: the wave's sum)
                 if (lane == 63) bseed[wv] = ws;
                 __syncthreads();
@@ -897,9 +1035,11 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
         const int wc = hb[0];
         if (wc == 0) dead = 1;                                       // a corrupt block ends the stream (ulcDecodeTool.c:154-157)
         const bool lastOfStream = k == c.k1 - 1;
-        OUT *outp = out_base<OUT>(c) + (size_t)blk * C * BS;
+        const size_t oblk = RANGE ? (size_t)s * (c.K - 1) + (warm ? 0 : k - 1) : (size_t)blk;   // (a range call's output has no row for the block in front)
+        OUT *outp = out_base<OUT>(c) + oblk * C * BS;
+        if constexpr (RANGE) { if (!warm && tid == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; }
         // where this block finds and leaves the lapping state
-        const float *lapR = !SPLIT ? scr : (k == c.k0 ? c.lap + (size_t)s * C * H2 : scr);
+        const float *lapR = (!SPLIT || RANGE) ? scr : (k == c.k0 ? c.lap + (size_t)s * C * H2 : scr);
         float *lapW = !SPLIT ? scr : (lastOfStream ? c.lapO + (size_t)s * C * H2 : scr);
         if (dead) {
             if (!warm) {
@@ -1180,7 +1320,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
 // the lapping state and the staging of the time samples in global memory.  Correct for every geometry the
 // reference accepts (ulcDecoder.c:33-35: up to 255 channels, BlockSize up to 32768), not tuned.
 // ---------------------------------------------------------------------------
-template <typename OUT>
+template <typename OUT, bool RANGE = false>
 __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
     extern __shared__ float lds[];
     const int BS = c.BS, C = c.C, H2 = BS / 2;
@@ -1200,13 +1340,25 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
     int dead = c.dead[s];
     uint32_t seed = c.seed[s];
     float *scr = c.scratch + (size_t)s * 4 * BS;                     // staging: dst[2][BS] | dec[BS] | tmpq[BS/2]
-    for (int k = 0; k < c.K; k++) {
+    int kBeg = 0;
+    if constexpr (RANGE) {
+        // a range call (k_dsyn): the stream is entered from nothing - zero lapping state, the index's generator state -, and
+        // row 0, the block in front of the range, runs without output when there is one
+        const int2 ri = c.rInfo[s];
+        lastSub = 0; dead = 0; seed = (uint32_t)ri.y; kBeg = 1 - ri.x;
+        for (int i = tid; i < C * H2; i += WG) glap[i] = 0.0f;
+        __syncthreads();
+    }
+    for (int k = kBeg; k < c.K; k++) {
         const int blk = s * c.K + k;
         const int wc = c.wcScan[blk];
         if (wc == 0) dead = 1;                                       // a corrupt block ends the stream (ulcDecodeTool.c:154-157)
-        OUT *outp = out_base<OUT>(c) + (size_t)blk * C * BS;
+        const bool warm = RANGE && k == 0;
+        const size_t oblk = RANGE ? (size_t)s * (c.K - 1) + (warm ? 0 : k - 1) : (size_t)blk;
+        OUT *outp = out_base<OUT>(c) + oblk * C * BS;
+        if constexpr (RANGE) { if (!warm && tid == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; }
         if (dead) {
-            for (int i = tid; i < C * BS; i += WG) st1(outp + i, 0.0f);
+            if (!warm) for (int i = tid; i < C * BS; i += WG) st1(outp + i, 0.0f);
             if (tid == 0) c.bits[blk] = 0;
             continue;
         }
@@ -1307,7 +1459,8 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
                 const bool pairDone = (ch & 1) || (ch == C - 1);
                 if (pairDone) {
                     __syncthreads();
-                    if (ch & 1) {
+                    if (warm) {
+                    } else if (ch & 1) {
                         const float *dm = scr, *ds = scr + BS;
                         for (int n = tid; n < BS; n += WG) {
                             const float m = dm[n], sd = ds[n];                            // ulcDecoder.c:281-289
@@ -1375,27 +1528,45 @@ static void launch_syn(const UlcxDecCtx &cc, unsigned g, size_t lds, hipStream_t
     else if (cc.BS == 4096 && DSYN_C4096) { if (split) hipLaunchKernelGGL((k_dsyn<OUT, 32, false, true, 4096>), dim3(g), dim3(WG), lds, s2, cc); else hipLaunchKernelGGL((k_dsyn<OUT, 32, false, false, 4096>), dim3(g), dim3(WG), lds, s2, cc); }
     else { if (split) hipLaunchKernelGGL((k_dsyn<OUT, 32, false, true>), dim3(g), dim3(WG), lds, s2, cc); else hipLaunchKernelGGL((k_dsyn<OUT, 32, false, false>), dim3(g), dim3(WG), lds, s2, cc); }
 }
+// the instantiation a range call's synthesis runs (the cut form of the stereo kernel for every grid)
+template <typename OUT>
+static const void *syn_fn_range(const UlcxDecCtx &cc) {
+    if (!cc.fastOK) return (const void *)k_dgen<OUT, true>;
+    if (cc.BS == 2048 && DSYN_C2048) return (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, true, 2048, true>;
+    if (cc.BS <= 2048) return (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, true, 0, true>;
+    if (cc.BS == 4096 && DSYN_C4096) return (const void *)k_dsyn<OUT, 32, false, true, 4096, true>;
+    return (const void *)k_dsyn<OUT, 32, false, true, 0, true>;
+}
 int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux) {
     int stage = 0;
     if (ev) CK(hipEventRecord(ev[stage++], st));
     UlcxDecCtx c = cIn;
-    c.s0 = 0; c.s1 = c.B; c.k0 = 0; c.k1 = c.K;
+    c.s0 = 0; c.s1 = c.B; c.k0 = c.range ? 1 : 0; c.k1 = c.K;
     const size_t lds = ulcx_dec_lds_bytes(c.BS, c.C, c.fastOK, c.twInLds);
+    const void *fnRange = !c.range ? nullptr : c.pcm16 ? syn_fn_range<int16_t>(c) : syn_fn_range<float>(c);
     if (lds > 48 * 1024) {
         const bool split = c.fastOK && aux.synGrid > 0;
-        const void *fn = c.pcm16 ? syn_fn<int16_t>(c, split) : syn_fn<float>(c, split);
+        const void *fn = c.range ? fnRange : c.pcm16 ? syn_fn<int16_t>(c, split) : syn_fn<float>(c, split);
         CK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
+    if (c.range) hipLaunchKernelGGL(k_dscan_range, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
+    else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     if (ev) CK(hipEventRecord(ev[stage++], st));
     if (!(ULCX_DBG(c) & 8)) {
         const bool split = c.fastOK && aux.synGrid > 0;
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
-        c.synFull = split ? aux.synFull : 0;
-        if (c.pcm16) launch_syn<int16_t>(c, g, lds, st, split); else launch_syn<float>(c, g, lds, st, split);
+        c.synFull = split ? aux.synFull : (c.range && c.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
+        if (c.range) { void *args[] = { &c }; CK(hipLaunchKernel(fnRange, dim3(g), dim3(WG), args, lds, st)); }
+        else if (c.pcm16) launch_syn<int16_t>(c, g, lds, st, split); else launch_syn<float>(c, g, lds, st, split);
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+
+int ulcx_index_launch(const UlcxDecCtx &c, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_dindex, dim3((c.B + 63) / 64), dim3(64), 0, st, c, maxBlocks, d_index, d_nBlocks);
     CK(hipGetLastError());
     return ULCX_OK;
 }

@@ -156,6 +156,15 @@ struct UlcxDecCtx {
     const int32_t *payBytes;             // [B] valid bytes per stream
     int  *packOff;                       // [B] persistent read position of each stream
     int  *blkOff;                        // [NB] byte offset of each block inside its stream payload
+    // range calls (ulcx_decode_range_*): blocks rFirst[s] .. rFirst[s] + K - 2 of every stream, found through a block index.
+    // A stream has K = nBlocks + 1 rows of the per-block scratch: row 0 is the block in front of the range (run without
+    // output, for the lapping state), rows 1 .. K-1 the blocks of the call; the synthesis works on rows [k0 = 1, K).
+    int   range;
+    const ulcx_index_entry *rIndex;      // [B][rIndexStride]
+    int   rIndexStride;
+    const int32_t *rIndexBlocks, *rFirst;   // [B] entries of each stream's index that are blocks; first block of the range
+    int2 *rInfo;                         // [B] {1 = row 0 holds a block, generator state in front of the stream's first row} (k_dscan_range)
+    int32_t *bitsOut;                    // [B][K-1] the caller's sizes (c.bits: the rows' own, [B][K])
 };
 
 // ulcHelper.h:24-46
@@ -203,6 +212,8 @@ struct UlcxDecAux {
     int synFull;                         // of those, the leading ones that take one whole stream each (0: an even cut of everything)
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
+// block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
+int ulcx_index_launch(const UlcxDecCtx &c, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, hipStream_t st);
 size_t ulcx_dec_lds_bytes(int BS, int C, int fast, int twInLds);
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,

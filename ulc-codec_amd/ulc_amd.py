@@ -24,7 +24,12 @@ EXPORTS = [
     "ulcx_pack_streams_dev", "ulcx_decode_packed_dev", "ulcx_decode_packed_host", "ulcx_decoder_upload_payload", "ulcx_decode_resident_host", "ulcx_encoder_stage_ms", "ulcx_encoder_stage_name", "ulcx_encoder_last_xf_launches", "ulcx_decoder_stage_ms", "ulcx_decoder_stage_name", "ulcx_block_extent_bytes", "ulcx_encoder_set_timing", "ulcx_decoder_set_timing", "ulcx_encode_block1", "ulcx_decode_block1", "ulcx_decode_block1_rng", "ulcx_build_rev", "ulcx_dec_split_plan", "ulcx_dec_tail_plan", "ulcx_decoder_last_cut",
     "ulcx_encode_dev_rates", "ulcx_encode_dev_pcm16_rates", "ulcx_encode_host_rates",
     "ulcx_analyse_dev", "ulcx_analyse_dev_pcm16", "ulcx_analyse_host",
+    "ulcx_index_packed_dev", "ulcx_index_packed_host", "ulcx_decode_range_dev", "ulcx_decode_range_dev_pcm16", "ulcx_decode_range_host",
+    "ulcx_decoder_index_resident", "ulcx_decode_resident_range_host", "ulcx_dec_range_tail_plan",
 ]
+
+# one entry of a block index (include/ulc_amd.h, ulcx_index_entry): 8 bytes
+INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
 
 
 
@@ -61,6 +66,16 @@ def lib():
             l.ulcx_analyse_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             l.ulcx_analyse_dev_pcm16.argtypes = l.ulcx_analyse_dev.argtypes
             l.ulcx_analyse_host.argtypes = [C.c_void_p, _f32p, C.c_int, _i32p, _f32p]
+        if hasattr(l, "ulcx_index_packed_dev"):
+            l.ulcx_index_packed_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_index_packed_host.argtypes = [C.c_void_p, _u8p, C.c_longlong, _i32p, C.c_int, C.c_void_p, _i32p]
+            l.ulcx_decode_range_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_decode_range_dev_pcm16.argtypes = l.ulcx_decode_range_dev.argtypes
+            l.ulcx_decode_range_host.argtypes = [C.c_void_p, _u8p, C.c_longlong, _i32p, C.c_void_p, C.c_int, _i32p, _i32p, C.c_int, _f32p, _i32p]
+            l.ulcx_decoder_index_resident.argtypes = [C.c_void_p, C.c_int, _i32p]
+            l.ulcx_dec_range_tail_plan.argtypes = [C.c_int, C.c_int, C.c_int, _i32p]
+            l.ulcx_decode_resident_range_host.argtypes = [C.c_void_p, _i32p, C.c_int, _f32p, _i32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -300,6 +315,66 @@ class BatchDecoder:
         bits = np.zeros((self.B, n_blocks), np.int32)
         _check(lib().ulcx_decode_resident_host(self.h, n_blocks, _p(pcm, _f32p), _p(bits, _i32p)), "ulcx_decode_resident_host")
         return pcm, bits
+
+    def index_packed(self, payload, payload_bytes, max_blocks):
+        """Block index of packed payloads: (index [B][max_blocks+1] of INDEX_DTYPE, n_blocks [B]).  Entry k of a stream is
+        the byte at which its block k starts and the noise generator's state there; entry n_blocks[s] closes the table,
+        later ones are (-1, 0).  No stream state is read or changed."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        B, stride = payload.shape
+        assert B == self.B
+        index = np.zeros((B, max_blocks + 1), INDEX_DTYPE)
+        count = np.zeros(B, np.int32)
+        _check(lib().ulcx_index_packed_host(self.h, _p(payload, _u8p), stride, _p(nbytes, _i32p), max_blocks, index.ctypes.data, _p(count, _i32p)),
+               "ulcx_index_packed_host")
+        return index, count
+
+    def decode_range(self, payload, payload_bytes, index, index_blocks, first, n_blocks):
+        """Blocks first[s] .. first[s]+n_blocks-1 of every stream -> (pcm [B][n_blocks*BS][C], bits [B][n_blocks]), as a
+        sequential decode from block 0 gives them; n_blocks <= max_blocks - 1.  The streams' state afterwards is that of a
+        sequential decode up to the range's last block."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+        count = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        B, stride = payload.shape
+        assert B == self.B and index.shape[0] == B and count.shape == (B,) and first.shape == (B,)
+        pcm = np.zeros((B, n_blocks * self.BS, self.C), np.float32)
+        bits = np.zeros((B, n_blocks), np.int32)
+        _check(lib().ulcx_decode_range_host(self.h, _p(payload, _u8p), stride, _p(nbytes, _i32p), index.ctypes.data, index.shape[1],
+                                            _p(count, _i32p), _p(first, _i32p), n_blocks, _p(pcm, _f32p), _p(bits, _i32p)), "ulcx_decode_range_host")
+        return pcm, bits
+
+    def index_resident(self, max_blocks):
+        """Index the payloads uploaded with upload_payload() and keep the index in the decoder -> n_blocks [B]."""
+        count = np.zeros(self.B, np.int32)
+        _check(lib().ulcx_decoder_index_resident(self.h, max_blocks, _p(count, _i32p)), "ulcx_decoder_index_resident")
+        return count
+
+    def decode_resident_range(self, first, n_blocks):
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        assert first.shape == (self.B,)
+        pcm = np.zeros((self.B, n_blocks * self.BS, self.C), np.float32)
+        bits = np.zeros((self.B, n_blocks), np.int32)
+        _check(lib().ulcx_decode_resident_range_host(self.h, _p(first, _i32p), n_blocks, _p(pcm, _f32p), _p(bits, _i32p)),
+               "ulcx_decode_resident_range_host")
+        return pcm, bits
+
+    def index_packed_dev(self, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream=0):
+        _check(lib().ulcx_index_packed_dev(self.h, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream or None),
+               "ulcx_index_packed_dev")
+
+    def decode_range_dev(self, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, d_first, n_blocks, d_pcm, d_bits,
+                         stream=0, pcm16=False):
+        fn = lib().ulcx_decode_range_dev_pcm16 if pcm16 else lib().ulcx_decode_range_dev
+        _check(fn(self.h, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, d_first, n_blocks, d_pcm, d_bits,
+                  stream or None), "ulcx_decode_range_dev_pcm16" if pcm16 else "ulcx_decode_range_dev")
+
+    def decode_packed_dev(self, d_payload, stride, d_payload_bytes, n_blocks, d_pcm, d_bits, stream=0):
+        _check(lib().ulcx_decode_packed_dev(self.h, d_payload, stride, d_payload_bytes, n_blocks, d_pcm, d_bits, stream or None),
+               "ulcx_decode_packed_dev")
 
     def decode_dev(self, d_in, slot, n_blocks, d_pcm, d_bits, stream=0):
         _check(lib().ulcx_decode_dev(self.h, d_in, slot, n_blocks, d_pcm, d_bits, stream or None), "ulcx_decode_dev")
