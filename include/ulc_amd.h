@@ -192,6 +192,37 @@ int  ulcx_encode_dev_pcm16_rates(ulcx_encoder *enc, const ulcx_rate *d_rate, con
 int  ulcx_encode_host_rates(ulcx_encoder *enc, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
                             uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx);
 
+/* Ladder: nBlocks blocks of every stream under nRungs rate settings in ONE call - several encodings of the same audio for
+ * adaptive delivery.  Window control, transform, complexity, Bark levels, noise spectrum and the state update run once;
+ * selection and writer run once per rung.  The streams' state advances once, and rung r's blocks are byte for byte those of
+ * an encoder of its own fed the same PCM since creation and called with rung r's setting.
+ *   d_out  [nRungs][nStreams][nBlocks][slot_bytes]      d_bits [nRungs][nStreams][nBlocks]
+ *   d_wc / d_cplx  optional, [nStreams][nBlocks], written once (they do not depend on a rate mode)
+ * nRungs is 1 .. ULCX_MAX_RUNGS; a bad count, a bad mode in a scalar rung or a non-zero `reserved` returns ULCX_ERR_ARG before
+ * any device work and leaves the encoder's state untouched.  A scalar rung behaves as ulcx_encode_dev does (VBR: one pass, no
+ * probe launches), a table rung as ulcx_encode_dev_rates does (always the full number of probe passes).  Asynchronous on
+ * hipStream like its siblings.  With nRungs == 1 the call writes what the plain call writes.  Ladder, plain, _rates and
+ * analysis calls may be mixed freely on one encoder.  ulcx_pack_streams_dev takes rung r at d_out + r * nStreams * nBlocks * slot.
+ * Test hooks after a ladder call: ulcx_encoder_debug_fetch's kept set and nout are the last rung's (coefficients, noise and
+ * keys are the same for every rung); ulcx_encoder_last_fallbacks is the sum over the rungs; the stage times cover rung 0's
+ * first pass, everything behind it falls into "cbr_probe_passes". */
+#define ULCX_MAX_RUNGS 8
+/* One rung of a ladder call.  A HOST struct (the array is read during the call, not kept).
+ * rate == NULL: one setting for the whole batch, as ulcx_encode_dev takes it (mode / param0 / param1).
+ * rate != NULL: a per-stream table [nStreams] as ulcx_encode_dev_rates takes it (a DEVICE pointer in the _dev forms,
+ *               a host pointer in the _host form); mode / param0 / param1 are then unused. */
+typedef struct ulcx_rung { int32_t mode; float param0, param1; int32_t reserved; const ulcx_rate *rate; } ulcx_rung;  /* 24 bytes, rate at 16 */
+
+int  ulcx_encode_dev_ladder      (ulcx_encoder *enc, const ulcx_rung *rungs, int nRungs, const float   *d_pcm,   int nBlocks,
+                                  uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_encode_dev_pcm16_ladder(ulcx_encoder *enc, const ulcx_rung *rungs, int nRungs, const int16_t *d_pcm16, int nBlocks,
+                                  uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream);
+/* Host-pointer convenience (synchronous).  Every table is validated as ulcx_encode_host_rates validates its own, a scalar
+ * rung's parameters by the same rule (finite, param0 != 0, param1 >= 0), before any device work. */
+int  ulcx_encode_host_ladder     (ulcx_encoder *enc, const ulcx_rung *rungs, int nRungs, const float   *h_pcm,   int nBlocks,
+                                  uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx);
+int  ulcx_encoder_last_rungs(ulcx_encoder *enc);   /* rungs of the last encode call (1 for every other encode call, 0 after an analysis call) */
+
 /* Analysis only: window control, MDCT and block complexity of nBlocks consecutive blocks of every stream.
  * No selection, no writer, no output slots.  d_wc / d_cplx as in ulcx_encode_dev ([nStreams][nBlocks]); at least one
  * of them non-NULL.  The streams' persistent state advances exactly as an encode call of the same blocks advances it:

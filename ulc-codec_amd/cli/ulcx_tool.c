@@ -18,6 +18,10 @@
  * that is 0; its line reports the value used.  "analyse" runs that pass alone and prints per file the block
  * count, the average complexity `RATE,<complexity>` is to be fed with and the number of window-switched
  * blocks; it writes no file.
+ * A ladder "R0/R1/.../Rn" (up to 8 rungs, each in RATE's syntax, `auto` included; positional and in every -rate:, all with
+ * the same number of rungs) encodes every file under each rung in ONE library call per batch of blocks
+ * (ulcx_encode_host_ladder: window control, transform and complexity once) and writes OUTDIR/stem.r<i>.ulc, i from 0, each
+ * the file the reference's tool writes at Ri; `auto` rungs share one analysis pass.
  * Files written are byte-identical to the reference tools' (tests/test_gpu_dropin.py):
  * container layout tools/ulc_Helper.h:10-20, block count ulcEncodeTool.c:93-98 (+2 blocks of
  * coding/MDCT delay), sample conversion WavIO_Helper.c:49-63 (x 2^-15 in, lrintf(clamp(x 2^15)) out).
@@ -118,8 +122,9 @@ static void out_path(char *dst, size_t n, const char *dir, const char *in, const
 #define DIE(...) do { fprintf(stderr, "ulcx-tool: " __VA_ARGS__); fprintf(stderr, "\n"); return 2; } while (0)
 
 /* one group of inputs = one batch on one device (the whole command line, or a -devices:N share of it on its own thread);
- * encode: file i is encoded under {RateKbps, AvgComplexity} = setting[i]; autoc[i] = 1: "RATE,auto" (two passes) */
-struct group { int decode, analyse, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int bs, isFloat; int rc;
+ * encode: rung r of file i is encoded under {RateKbps, AvgComplexity} = setting[i * ULCX_MAX_RUNGS + r], r < nRungs;
+ * autoc[...] = 1: "RATE,auto" (two passes) */
+struct group { int decode, analyse, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int nRungs; int bs, isFloat; int rc;
                int32_t rFirst, rCount; /* decode -blocks:FIRST,COUNT (rCount 0: whole files) */ };
 
 /* "RATE[,AvgComplexity]" or "RATE,auto", validated as ulcEncodeTool.c:43-50 does (and finite: the library refuses the rest) */
@@ -131,6 +136,23 @@ static int parse_rate(const char *s, ulcx_rate *r, int *isAuto) {
     if (!isfinite(r->RateKbps) || !isfinite(r->AvgComplexity) || r->RateKbps == 0.0f || r->AvgComplexity < 0.0f) return -1;
     if (*isAuto && r->RateKbps < 0.0f) return -1;                  /* ABR needs a rate in kbps */
     return 0;
+}
+
+/* A ladder "R0/R1/.../Rn" of 1 .. ULCX_MAX_RUNGS settings, each in parse_rate's syntax; returns the number of rungs, -1 for a
+ * malformed one (an empty rung: "-50/", "/64", "-50//64"; too many; a rung parse_rate refuses) */
+static int parse_ladder(const char *s, ulcx_rate *r, int *isAuto) {
+    int n = 0;
+    for (;;) {
+        const char *slash = strchr(s, '/');
+        const size_t len = slash ? (size_t)(slash - s) : strlen(s);
+        char one[64];
+        if (len == 0 || len >= sizeof(one) || n == ULCX_MAX_RUNGS) return -1;
+        memcpy(one, s, len); one[len] = 0;
+        if (parse_rate(one, &r[n], &isAuto[n])) return -1;
+        n++;
+        if (!slash) return n;
+        s = slash + 1;
+    }
 }
 
 /* The analysis pass over a batch of open inputs: each file's BlockComplexity summed over its own ceil(frames/BS)+2 blocks,
@@ -190,7 +212,7 @@ static int analyse_group(const struct group *g) {
 
 static int encode_group(const struct group *g) {
     const char *outdir = g->outdir;
-    const int bs = g->bs, B = g->n, a = 0;
+    const int bs = g->bs, B = g->n, a = 0, R = g->nRungs;
     char **argv = g->files;
     struct wav *w = (struct wav *)calloc((size_t)B, sizeof(*w));
     uint32_t maxBlk = 0;
@@ -202,81 +224,108 @@ static int encode_group(const struct group *g) {
         if (nb > maxBlk) maxBlk = nb;
     }
     const int C = w[0].chan, hz = w[0].rate;
-    /* one setting for every file: the batch-wide call (ulcEncodeTool.c:157-159); otherwise the per-stream table */
-    int uniform = 1, anyAuto = 0;
-    for (int s = 0; s < B; s++) {
-        anyAuto |= g->autoc[s];
-        if (g->autoc[s] || g->setting[s].RateKbps != g->setting[0].RateKbps || g->setting[s].AvgComplexity != g->setting[0].AvgComplexity) uniform = 0;
+    /* per rung: one setting for every file - the batch-wide form (ulcEncodeTool.c:157-159) -, otherwise the per-stream table */
+    int uniform[ULCX_MAX_RUNGS], anyAuto = 0;
+    for (int r = 0; r < R; r++) {
+        uniform[r] = 1;
+        for (int s = 0; s < B; s++) {
+            const ulcx_rate *x = &g->setting[s * ULCX_MAX_RUNGS + r], *x0 = &g->setting[r];
+            anyAuto |= g->autoc[s * ULCX_MAX_RUNGS + r];
+            if (g->autoc[s * ULCX_MAX_RUNGS + r] || x->RateKbps != x0->RateKbps || x->AvgComplexity != x0->AvgComplexity) uniform[r] = 0;
+        }
     }
-    const float rate = g->setting[0].RateKbps, avgc = g->setting[0].AvgComplexity;
-    int mode = rate < 0.0f ? ULCX_MODE_VBR : (avgc > 0.0f ? ULCX_MODE_ABR : ULCX_MODE_CBR);
-    float p0 = rate < 0.0f ? -rate : rate;
-    ulcx_rate *table = (ulcx_rate *)calloc((size_t)B, sizeof(ulcx_rate));
+    ulcx_rate *table = (ulcx_rate *)calloc((size_t)R * B, sizeof(ulcx_rate));         /* [R][B] */
     ulcx_encoder *enc = NULL;
     if (ulcx_encoder_create(&enc, g->device, B, C, bs, hz, KBLOCKS) != ULCX_OK) DIE("encoder: %s", ulcx_last_error());
     const int slot = ulcx_encoder_slot_bytes(enc);
     size_t frame = (size_t)bs * C;
     float *pcm = (float *)malloc(sizeof(float) * (size_t)B * KBLOCKS * frame);
-    uint8_t *out = (uint8_t *)malloc((size_t)B * KBLOCKS * slot);
-    int32_t *bits = (int32_t *)malloc(sizeof(int32_t) * (size_t)B * KBLOCKS);
+    uint8_t *out = (uint8_t *)malloc((size_t)R * B * KBLOCKS * slot);                 /* [R][B][K][slot] */
+    int32_t *bits = (int32_t *)malloc(sizeof(int32_t) * (size_t)R * B * KBLOCKS);     /* [R][B][K] */
     float *cplx = (float *)malloc(sizeof(float) * (size_t)B * KBLOCKS);
     double *cplxSum = (double *)calloc((size_t)B, sizeof(double));   /* ulcEncodeTool.c:130,164: feeds the ABR workflow */
     void *tmp = malloc(frame * 4 * KBLOCKS);
-    FILE **fo = (FILE **)calloc((size_t)B, sizeof(FILE *));
-    uint64_t *total = (uint64_t *)calloc((size_t)B, sizeof(uint64_t));
-    uint32_t *maxb = (uint32_t *)calloc((size_t)B, sizeof(uint32_t));
+    FILE **fo = (FILE **)calloc((size_t)R * B, sizeof(FILE *));                       /* [R][B], as total and maxb */
+    uint64_t *total = (uint64_t *)calloc((size_t)R * B, sizeof(uint64_t));
+    uint32_t *maxb = (uint32_t *)calloc((size_t)R * B, sizeof(uint32_t));
     char path[1024];
     if (anyAuto) {
-        /* "RATE,auto": pass 1 (analysis only: BlockComplexity does not depend on the rate mode) sums each file's
-         * complexity over its own blocks in block order in double precision (ulcEncodeTool.c:130,164,178); after a
-         * reset, pass 2 encodes that file in ABR at (float)(sum / nBlocks) - in CBR if that is 0, as the tool does with RATE,0 */
+        /* "RATE,auto": pass 1 (analysis only: BlockComplexity does not depend on the rate mode, so every auto rung of a
+         * ladder shares it) sums each file's complexity over its own blocks in block order in double precision
+         * (ulcEncodeTool.c:130,164,178); after a reset, pass 2 encodes that file in ABR at (float)(sum / nBlocks) - in CBR if
+         * that is 0, as the tool does with RATE,0 */
         const int rca = analysis_pass(enc, w, B, bs, maxBlk, pcm, tmp, cplx, NULL, cplxSum, NULL);
         if (rca) return rca;
         if (ulcx_encoder_reset(enc) != ULCX_OK) DIE("encoder reset: %s", ulcx_last_error());
     }
     for (int s = 0; s < B; s++) {
-        table[s] = g->setting[s];
-        if (g->autoc[s]) {
-            uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
-            table[s].AvgComplexity = (float)(cplxSum[s] / nb);
+        for (int r = 0; r < R; r++) {
+            table[r * B + s] = g->setting[s * ULCX_MAX_RUNGS + r];
+            if (g->autoc[s * ULCX_MAX_RUNGS + r]) {
+                uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
+                table[r * B + s].AvgComplexity = (float)(cplxSum[s] / nb);
+            }
         }
         cplxSum[s] = 0.0;                                              /* (pass 2 sums it again for the report) */
     }
-    for (int s = 0; s < B; s++) {
-        out_path(path, sizeof(path), outdir, argv[a + s], ".ulc");
-        fo[s] = fopen(path, "wb");
-        if (!fo[s]) DIE("cannot create '%s'", path);
-        fseek(fo[s], 24, SEEK_SET);
+    for (int s = 0; s < B; s++)
+        for (int r = 0; r < R; r++) {
+            char ext[32] = ".ulc";                                     /* a ladder: stem.r<i>.ulc */
+            if (R > 1) snprintf(ext, sizeof(ext), ".r%d.ulc", r);
+            out_path(path, sizeof(path), outdir, argv[a + s], ext);
+            fo[r * B + s] = fopen(path, "wb");
+            if (!fo[r * B + s]) DIE("cannot create '%s'", path);
+            fseek(fo[r * B + s], 24, SEEK_SET);
+        }
+    /* a rung goes out as a scalar rung when all files share its setting, else as a table */
+    ulcx_rung rungs[ULCX_MAX_RUNGS];
+    memset(rungs, 0, sizeof(rungs));
+    for (int r = 0; r < R; r++) {
+        const float rate = table[r * B].RateKbps, avgc = table[r * B].AvgComplexity;
+        rungs[r].mode = rate < 0.0f ? ULCX_MODE_VBR : (avgc > 0.0f ? ULCX_MODE_ABR : ULCX_MODE_CBR);
+        rungs[r].param0 = rate < 0.0f ? -rate : rate; rungs[r].param1 = avgc;
+        rungs[r].rate = uniform[r] ? NULL : table + (size_t)r * B;
     }
     for (uint32_t k0 = 0; k0 < maxBlk; k0 += KBLOCKS) {
         int K = (maxBlk - k0 < KBLOCKS) ? (int)(maxBlk - k0) : KBLOCKS;
         for (int s = 0; s < B; s++)
             wav_read(&w[s], k0 * (uint32_t)bs, (uint32_t)(K * bs), pcm + (size_t)s * K * frame, tmp);
-        const int rc = uniform ? ulcx_encode_host(enc, mode, p0, avgc, pcm, K, out, bits, NULL, cplx)
-                               : ulcx_encode_host_rates(enc, table, pcm, K, out, bits, NULL, cplx);
+        const int rc = R > 1 ? ulcx_encode_host_ladder(enc, rungs, R, pcm, K, out, bits, NULL, cplx)
+                     : uniform[0] ? ulcx_encode_host(enc, rungs[0].mode, rungs[0].param0, rungs[0].param1, pcm, K, out, bits, NULL, cplx)
+                                  : ulcx_encode_host_rates(enc, table, pcm, K, out, bits, NULL, cplx);
         if (rc != ULCX_OK) DIE("encode: %s", ulcx_last_error());
         for (int s = 0; s < B; s++) {
             uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
             for (int k = 0; k < K && k0 + (uint32_t)k < nb; k++) {
-                uint32_t sz = (uint32_t)(bits[s * K + k] + 7) / 8u;
-                fwrite(out + ((size_t)s * K + k) * slot, 1, sz, fo[s]);               /* ulcEncodeTool.c:160-169 */
-                total[s] += sz; if (sz > maxb[s]) maxb[s] = sz;
+                for (int r = 0; r < R; r++) {
+                    const size_t at = ((size_t)r * B + s) * K + k;
+                    uint32_t sz = (uint32_t)(bits[at] + 7) / 8u;
+                    fwrite(out + at * slot, 1, sz, fo[r * B + s]);                    /* ulcEncodeTool.c:160-169 */
+                    total[r * B + s] += sz; if (sz > maxb[r * B + s]) maxb[r * B + s] = sz;
+                }
                 cplxSum[s] += cplx[s * K + k];
             }
         }
     }
     for (int s = 0; s < B; s++) {
         uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
-        ulcx_file_header h;
-        h.Magic = ULCX_ULC_MAGIC; h.BlockSize = (uint16_t)bs; h.MaxBlockSize = (uint16_t)maxb[s]; h.nBlocks = nb;
-        h.RateHz = (uint32_t)hz; h.nChan = (uint16_t)C; h.StreamOffs = 24;
-        h.RateKbps = (uint16_t)ulcx_ulc_rate_kbps(total[s], (uint32_t)hz, (uint32_t)bs, nb);
-        uint8_t hb[24]; ulcx_ulc_header_pack(hb, &h);
-        fseek(fo[s], 0, SEEK_SET); fwrite(hb, 1, 24, fo[s]); fclose(fo[s]); fclose(w[s].f);
-        char used[64] = "";                                                            /* "RATE,auto": the complexity pass 2 used */
-        if (g->autoc[s]) snprintf(used, sizeof(used), "ABR complexity %.9g%s, ", (double)table[s].AvgComplexity, table[s].AvgComplexity > 0.0f ? "" : " (CBR)");
-        printf("%s: %u blocks, %.2f KiB, %u kbps, %savg complexity %.5f\n", base_name(argv[a + s]), nb, total[s] / 1024.0, h.RateKbps,
-               used, cplxSum[s] / nb);                                                /* ulcEncodeTool.c:176,186 */
+        if (R > 1) printf("%s: %u blocks, avg complexity %.5f", base_name(argv[a + s]), nb, cplxSum[s] / nb);
+        for (int r = 0; r < R; r++) {
+            const int i = r * B + s;
+            ulcx_file_header h;
+            h.Magic = ULCX_ULC_MAGIC; h.BlockSize = (uint16_t)bs; h.MaxBlockSize = (uint16_t)maxb[i]; h.nBlocks = nb;
+            h.RateHz = (uint32_t)hz; h.nChan = (uint16_t)C; h.StreamOffs = 24;
+            h.RateKbps = (uint16_t)ulcx_ulc_rate_kbps(total[i], (uint32_t)hz, (uint32_t)bs, nb);
+            uint8_t hb[24]; ulcx_ulc_header_pack(hb, &h);
+            fseek(fo[i], 0, SEEK_SET); fwrite(hb, 1, 24, fo[i]); fclose(fo[i]);
+            char used[64] = "";                                                        /* "RATE,auto": the complexity pass 2 used */
+            if (g->autoc[s * ULCX_MAX_RUNGS + r]) snprintf(used, sizeof(used), "ABR complexity %.9g%s", (double)table[i].AvgComplexity, table[i].AvgComplexity > 0.0f ? "" : " (CBR)");
+            if (R > 1) printf("; r%d: %.2f KiB, %u kbps%s%s", r, total[i] / 1024.0, h.RateKbps, used[0] ? ", " : "", used);
+            else printf("%s: %u blocks, %.2f KiB, %u kbps, %s%savg complexity %.5f\n", base_name(argv[a + s]), nb, total[i] / 1024.0, h.RateKbps,
+                        used, used[0] ? ", " : "", cplxSum[s] / nb);                  /* ulcEncodeTool.c:176,186 */
+        }
+        if (R > 1) printf("\n");
+        fclose(w[s].f);
     }
     ulcx_encoder_destroy(enc);
     free(pcm); free(out); free(bits); free(cplx); free(cplxSum); free(tmp); free(fo); free(total); free(maxb); free(w); free(table);
@@ -418,15 +467,18 @@ static int run_groups(struct group *proto, int nFiles, char **files, int nDev) {
     }
     struct group *gs = (struct group *)calloc((size_t)nDev, sizeof(*gs));
     char **deal = (char **)calloc((size_t)nFiles, sizeof(char *));
-    ulcx_rate *dealR = (ulcx_rate *)calloc((size_t)nFiles, sizeof(ulcx_rate));     /* each file keeps its own setting */
-    int *dealA = (int *)calloc((size_t)nFiles, sizeof(int));
+    ulcx_rate *dealR = (ulcx_rate *)calloc((size_t)nFiles * ULCX_MAX_RUNGS, sizeof(ulcx_rate));     /* each file keeps its own settings */
+    int *dealA = (int *)calloc((size_t)nFiles * ULCX_MAX_RUNGS, sizeof(int));
     pthread_t *th = (pthread_t *)calloc((size_t)nDev, sizeof(pthread_t));
     if (!gs || !deal || !dealR || !dealA || !th) { free(gs); free(deal); free(dealR); free(dealA); free(th); DIE("out of memory"); }
     int at = 0, rc = 0, started = 0;
     for (int g = 0; g < nDev; g++) {
-        gs[g] = *proto; gs[g].device = g % have; gs[g].files = deal + at; gs[g].setting = dealR + at; gs[g].autoc = dealA + at; gs[g].n = 0; gs[g].rc = 0;
+        gs[g] = *proto; gs[g].device = g % have; gs[g].files = deal + at; gs[g].setting = dealR + (size_t)at * ULCX_MAX_RUNGS; gs[g].autoc = dealA + (size_t)at * ULCX_MAX_RUNGS; gs[g].n = 0; gs[g].rc = 0;
         for (int i = g; i < nFiles; i += nDev) {
-            if (!proto->decode && !proto->analyse) { dealR[at + gs[g].n] = proto->setting[i]; dealA[at + gs[g].n] = proto->autoc[i]; }
+            if (!proto->decode && !proto->analyse) {
+                memcpy(dealR + (size_t)(at + gs[g].n) * ULCX_MAX_RUNGS, proto->setting + (size_t)i * ULCX_MAX_RUNGS, sizeof(ulcx_rate) * ULCX_MAX_RUNGS);
+                memcpy(dealA + (size_t)(at + gs[g].n) * ULCX_MAX_RUNGS, proto->autoc + (size_t)i * ULCX_MAX_RUNGS, sizeof(int) * ULCX_MAX_RUNGS);
+            }
             deal[at + gs[g].n++] = files[i];
         }
         at += gs[g].n;
@@ -440,33 +492,46 @@ static int run_groups(struct group *proto, int nFiles, char **files, int nDev) {
     free(gs); free(deal); free(dealR); free(dealA); free(th);
     return rc;
 }
+/* "-rate:LADDER": the setting of the inputs that follow; every group of one command names as many rungs as RATE does */
+static int parse_rate_group(const char *arg, ulcx_rate *cur, int *curAuto, int nRungs) {
+    ulcx_rate r[ULCX_MAX_RUNGS]; int au[ULCX_MAX_RUNGS];
+    const int n = parse_ladder(arg + 6, r, au);
+    if (n < 0) DIE("invalid coding rate '%s'", arg);
+    if (n != nRungs) DIE("'%s' names %d rung%s, RATE names %d: every -rate: group of one command needs as many rungs as RATE", arg, n, n == 1 ? "" : "s", nRungs);
+    memcpy(cur, r, sizeof(r)); memcpy(curAuto, au, sizeof(au));
+    return 0;
+}
 static int do_encode(int argc, char **argv) {
-    if (argc < 5) DIE("usage: ulcx-tool encode OUTDIR RATE[,AvgComplexity|,auto] [-blocksize:N] [-devices:N] IN.wav [-rate:RATE[,...]] IN.wav ...");
+    if (argc < 5) DIE("usage: ulcx-tool encode OUTDIR RATE[,AvgComplexity|,auto][/RATE...] [-blocksize:N] [-devices:N] IN.wav [-rate:RATE[,...][/RATE...]] IN.wav ...");
     struct group g; memset(&g, 0, sizeof(g));
     g.outdir = argv[2];
-    ulcx_rate cur; int curAuto = 0;
-    if (parse_rate(argv[3], &cur, &curAuto)) DIE("invalid coding rate '%s'", argv[3]);
+    ulcx_rate cur[ULCX_MAX_RUNGS]; int curAuto[ULCX_MAX_RUNGS];
+    memset(cur, 0, sizeof(cur)); memset(curAuto, 0, sizeof(curAuto));
+    g.nRungs = parse_ladder(argv[3], cur, curAuto);
+    if (g.nRungs < 0) DIE("invalid coding rate '%s' (RATE[,AvgComplexity|,auto], or a ladder R0/R1/... of 1 to %d of them)", argv[3], ULCX_MAX_RUNGS);
     int a = 4, nDev = 1, endOpts = 0;
     g.bs = 2048;
     for (; a < argc && argv[a][0] == '-'; a++) {
         if (!strcmp(argv[a], "--")) { a++; endOpts = 1; break; }    /* end of options: input names may start with '-' behind it */
         if (!strncmp(argv[a], "-blocksize:", 11)) g.bs = atoi(argv[a] + 11);
         else if (!strncmp(argv[a], "-devices:", 9)) nDev = atoi(argv[a] + 9);
-        else if (!strncmp(argv[a], "-rate:", 6)) { if (parse_rate(argv[a] + 6, &cur, &curAuto)) DIE("invalid coding rate '%s'", argv[a]); }
+        else if (!strncmp(argv[a], "-rate:", 6)) { if (parse_rate_group(argv[a], cur, curAuto, g.nRungs)) return 2; }
         else DIE("unknown option '%s'", argv[a]);
     }
     if (g.bs < 256 || g.bs > 8192 || (g.bs & -g.bs) != g.bs) DIE("unsupported block size %d", g.bs);
     if (nDev < 1 || nDev > 64) DIE("-devices:%d out of range", nDev);
-    /* the inputs, each with the setting in force where it stands: "-rate:RATE[,AvgComplexity|,auto]" between them sets it for
-     * the inputs that follow (behind "--" every argument is an input) */
+    /* the inputs, each with the setting in force where it stands: "-rate:RATE[,AvgComplexity|,auto][/...]" between them sets it
+     * for the inputs that follow (behind "--" every argument is an input) */
     char **files = (char **)calloc((size_t)(argc - a + 1), sizeof(char *));
-    g.setting = (ulcx_rate *)calloc((size_t)(argc - a + 1), sizeof(ulcx_rate));
-    g.autoc = (int *)calloc((size_t)(argc - a + 1), sizeof(int));
+    g.setting = (ulcx_rate *)calloc((size_t)(argc - a + 1) * ULCX_MAX_RUNGS, sizeof(ulcx_rate));
+    g.autoc = (int *)calloc((size_t)(argc - a + 1) * ULCX_MAX_RUNGS, sizeof(int));
     if (!files || !g.setting || !g.autoc) DIE("out of memory");
     int n = 0;
     for (; a < argc; a++) {
-        if (!endOpts && !strncmp(argv[a], "-rate:", 6)) { if (parse_rate(argv[a] + 6, &cur, &curAuto)) DIE("invalid coding rate '%s'", argv[a]); continue; }
-        files[n] = argv[a]; g.setting[n] = cur; g.autoc[n] = curAuto; n++;
+        if (!endOpts && !strncmp(argv[a], "-rate:", 6)) { if (parse_rate_group(argv[a], cur, curAuto, g.nRungs)) return 2; continue; }
+        files[n] = argv[a];
+        memcpy(g.setting + (size_t)n * ULCX_MAX_RUNGS, cur, sizeof(cur)); memcpy(g.autoc + (size_t)n * ULCX_MAX_RUNGS, curAuto, sizeof(curAuto));
+        n++;
     }
     const int rc = run_groups(&g, n, files, nDev);
     free(files); free(g.setting); free(g.autoc);
@@ -524,6 +589,7 @@ int main(int argc, char **argv) {
             "      RATE < 0: VBR quality; RATE > 0: CBR kbps; RATE,AvgComplexity: ABR  (as ulcencodetool)\n"
             "      RATE,auto: two-pass ABR at each file's own average complexity (0: CBR)\n"
             "      -rate:RATE[,AvgComplexity|,auto]  setting of the inputs that follow it (RATE is the default)\n"
+            "      R0/R1/.../Rn (RATE and every -rate:, the same count): a ladder, one OUTDIR/stem.r<i>.ulc per rung from one call\n"
             "  ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-blocks:FIRST,COUNT] [-devices:N] IN1.ulc IN2.ulc ...\n"
             "      -blocks:FIRST,COUNT  only blocks FIRST .. FIRST+COUNT-1 of every file (block index + range decode)\n"
             "  ulcx-tool analyse [-blocksize:N] [-devices:N] IN1.wav IN2.wav ...\n"

@@ -59,6 +59,9 @@ struct ulcx_encoder {
     // staging for the host-pointer API
     float *d_pcm = nullptr; uint8_t *d_out = nullptr; int32_t *d_bits = nullptr, *d_wc = nullptr; float *d_cplx = nullptr;
     ulcx_rate *d_rate = nullptr;      // [B] the per-stream table of ulcx_encode_host_rates
+    int lastRungs = 0;                // rungs of the last encode call (0: none yet, or an analysis call)
+    // staging of ulcx_encode_host_ladder: [ladRungs][B][maxK] slots and sizes (grown to the largest ladder seen), tables [ULCX_MAX_RUNGS][B]
+    uint8_t *ladOut = nullptr; int32_t *ladBits = nullptr; ulcx_rate *ladRate = nullptr; int ladRungs = 0;
     // single-block path (ulcx_encode_block1): pinned staging, the captured launch sequence and the parameters it was captured with
     struct Block1Meta { int32_t bits, wc; float cplx; int32_t pad; UlcxWcState wcs; };
     Block1Graph b1; bool b1Init = false;
@@ -165,6 +168,8 @@ static void cleanup(ulcx_encoder *e) {
     if (e->pinIn) hipHostFree(e->pinIn);
     if (e->pinOut) hipHostFree(e->pinOut);
     if (e->pinMeta) hipHostFree(e->pinMeta);
+    if (e->ladOut) hipFree(e->ladOut);
+    if (e->ladBits) hipFree(e->ladBits);
     enc_sync_destroy(e->sync);
     delete e;
 }
@@ -344,8 +349,59 @@ static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const u
     e->lastK = nBlocks;
     e->keysFinal = false;
     e->lastAnalyse = false;
+    e->lastRungs = 1;
     return rc;
 }
+
+// ---- ladder (include/ulc_amd.h): one context per rung from the shared one; tables are device pointers here
+static int ladder_check(const ulcx_rung *rungs, int nRungs, const char *who) {
+    if (!rungs || nRungs < 1 || nRungs > ULCX_MAX_RUNGS) { ulcx_set_error("%s: nRungs %d not in 1 .. %d (or no rungs)", who, nRungs, ULCX_MAX_RUNGS); return ULCX_ERR_ARG; }
+    for (int r = 0; r < nRungs; r++) {
+        if (rungs[r].reserved != 0) { ulcx_set_error("%s: rung %d: reserved must be 0", who, r); return ULCX_ERR_ARG; }
+        const int m = rungs[r].mode;
+        if (!rungs[r].rate && m != ULCX_MODE_VBR && m != ULCX_MODE_CBR && m != ULCX_MODE_ABR) { ulcx_set_error("%s: rung %d: bad mode %d", who, r, m); return ULCX_ERR_ARG; }
+    }
+    return ULCX_OK;
+}
+static int encode_ladder_any(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
+                             uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!e || !rungs || (!d_pcm && !d_pcm16) || !d_out || !d_bits || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_encode_dev_ladder: bad argument"); return ULCX_ERR_ARG; }
+    { const int rc = ladder_check(rungs, nRungs, "ulcx_encode_dev_ladder"); if (rc) return rc; }
+    CKR(hipSetDevice(e->device));
+    UlcxEncCtx cs[ULCX_MAX_RUNGS];
+    const size_t NB = (size_t)e->B * nBlocks;
+    for (int r = 0; r < nRungs; r++) {
+        UlcxEncCtx &c = cs[r];
+        c = e->ctx;
+        const bool table = rungs[r].rate != nullptr;
+        c.K = nBlocks; c.keyFinal = 0;
+        c.mode = table ? ULCX_MODE_VBR : rungs[r].mode; c.p0 = table ? 100.0f : rungs[r].param0; c.p1 = table ? 0.0f : rungs[r].param1;
+        c.vbrTarget = (c.mode == ULCX_MODE_VBR) ? 0x1.E4EFB7p3f * logf(100.0f / c.p0) : 0.0f;     // ulcEncoder.c:144 (host libm, data independent)
+        c.rates = (const float2 *)rungs[r].rate;
+        c.pcm = d_pcm; c.pcm16 = d_pcm16;
+        c.out = d_out + r * NB * (size_t)c.slot; c.bits = d_bits + r * NB;
+        c.wcOut = r ? nullptr : d_wc; c.cplxOut = r ? nullptr : d_cplx;
+    }
+    const UlcxEncAux aux = enc_aux(e, nBlocks);
+    const int rc = ulcx_enc_launch_ladder(cs, nRungs, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux);
+    e->evRecorded = (rc == ULCX_OK) && e->timing;
+    e->lastK = nBlocks;
+    e->keysFinal = false;
+    e->lastAnalyse = false;
+    e->lastRungs = nRungs;
+    return rc;
+}
+extern "C" int ulcx_encode_dev_ladder(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const float *d_pcm, int nBlocks,
+                                      uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!d_pcm) { ulcx_set_error("ulcx_encode_dev_ladder: bad argument"); return ULCX_ERR_ARG; }
+    return encode_ladder_any(e, rungs, nRungs, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encode_dev_pcm16_ladder(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const int16_t *d_pcm16, int nBlocks,
+                                            uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16_ladder: bad argument"); return ULCX_ERR_ARG; }
+    return encode_ladder_any(e, rungs, nRungs, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encoder_last_rungs(ulcx_encoder *e) { return e ? e->lastRungs : ULCX_ERR_ARG; }
 
 // ---- analysis only (include/ulc_amd.h): window control, MDCT, block complexity, next-call state
 static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
@@ -360,6 +416,7 @@ static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d
     e->lastK = nBlocks;
     e->keysFinal = false;
     e->lastAnalyse = true;
+    e->lastRungs = 0;
     return rc;
 }
 extern "C" int ulcx_analyse_dev(ulcx_encoder *e, const float *d_pcm, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
@@ -463,6 +520,55 @@ extern "C" int ulcx_encode_host(ulcx_encoder *e, int mode, float p0, float p1, c
     return encode_host_run(e, mode, p0, p1, nullptr, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx);
 }
 
+// The ladder's host-pointer form: every rung validated first (tables as ulcx_encode_host_rates validates its own, a scalar
+// rung's parameters by the same rule), then input and tables up, one call on the null stream, [R][B][K] results down.
+extern "C" int ulcx_encode_host_ladder(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const float *h_pcm, int nBlocks,
+                                       uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
+    if (!e || !rungs || !h_pcm || !h_out || !h_bits) { ulcx_set_error("ulcx_encode_host_ladder: bad argument"); return ULCX_ERR_ARG; }
+    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
+    { const int rc = ladder_check(rungs, nRungs, "ulcx_encode_host_ladder"); if (rc) return rc; }
+    for (int r = 0; r < nRungs; r++) {
+        const int n = rungs[r].rate ? e->B : 1;
+        for (int s = 0; s < n; s++) {
+            const float v = rungs[r].rate ? rungs[r].rate[s].RateKbps : rungs[r].param0, a = rungs[r].rate ? rungs[r].rate[s].AvgComplexity : rungs[r].param1;
+            if (!isfinite(v) || !isfinite(a) || v == 0.0f || a < 0.0f) {
+                ulcx_set_error("ulcx_encode_host_ladder: rung %d: invalid setting%s %d (rate %g, complexity %g)", r, rungs[r].rate ? " for stream" : ", mode", rungs[r].rate ? s : rungs[r].mode, (double)v, (double)a);
+                return ULCX_ERR_ARG;
+            }
+        }
+    }
+    CKR(hipSetDevice(e->device));
+    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
+    const size_t nBlk = (size_t)e->B * e->maxK;
+    if (e->ladRungs < nRungs) {
+        if (e->ladOut) CKR(hipFree(e->ladOut));
+        if (e->ladBits) CKR(hipFree(e->ladBits));
+        e->ladOut = nullptr; e->ladBits = nullptr; e->ladRungs = 0;
+        CKR(hipMalloc((void **)&e->ladOut, (size_t)nRungs * nBlk * e->ctx.slot));
+        CKR(hipMalloc((void **)&e->ladBits, sizeof(int32_t) * (size_t)nRungs * nBlk));
+        e->ladRungs = nRungs;
+    }
+    if (!e->ladRate) { int rc = dalloc(e->allocs, &e->ladRate, (size_t)ULCX_MAX_RUNGS * e->B, false); if (rc) return rc; }
+    ulcx_rung dev[ULCX_MAX_RUNGS];
+    for (int r = 0; r < nRungs; r++) {
+        dev[r] = rungs[r];
+        if (rungs[r].rate) {
+            dev[r].rate = e->ladRate + (size_t)r * e->B;
+            CKR(hipMemcpy((void *)dev[r].rate, rungs[r].rate, sizeof(ulcx_rate) * (size_t)e->B, hipMemcpyHostToDevice));
+        }
+    }
+    const size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
+    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
+    int rc = encode_ladder_any(e, dev, nRungs, e->d_pcm, nullptr, nBlocks, e->ladOut, e->ladBits, e->d_wc, e->d_cplx, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_out, e->ladOut, (size_t)nRungs * NB * e->ctx.slot, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, e->ladBits, sizeof(int32_t) * (size_t)nRungs * NB, hipMemcpyDeviceToHost));
+    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+
 // One block of one stream per call (the drop-in ABI): include/ulc_amd.h.  The launch sequence of ulcx_encode_dev - side
 // streams and their event fork/joins included - is captured once into a graph together with the copies between the pinned
 // staging buffers and the device; a call is then memcpy, one graph launch, one synchronisation, memcpy.
@@ -555,9 +661,9 @@ extern "C" int ulcx_encoder_last_fallbacks(ulcx_encoder *e) {
     if (e->lastAnalyse) return 0;                                      // (an analysis call selects nothing)
     CKR(hipSetDevice(e->device));
     CKR(hipDeviceSynchronize());
-    int n = 0;
-    CKR(hipMemcpy(&n, e->ctx.fbCount, sizeof(int), hipMemcpyDeviceToHost));
-    return n;
+    int n[2] = { 0, 0 };                                               // this call's (last rung's) count; a ladder call: the rungs in front of it
+    CKR(hipMemcpy(n, e->ctx.fbCount, sizeof(n), hipMemcpyDeviceToHost));
+    return n[0] + (e->lastRungs > 1 ? n[1] : 0);
 }
 extern "C" const char *ulcx_encoder_stage_name(int i) { return (i >= 0 && i < ULCX_ENC_STAGES_REPORTED) ? ulcx_enc_stage_names[i] : ""; }
 extern "C" int ulcx_encoder_stage_ms(ulcx_encoder *e, float *ms, int maxStages) {

@@ -227,6 +227,11 @@ struct EncPlan {
     bool haveFull, haveMid;
     int nsSlots;
 };
+static int enc_probes(const UlcxEncCtx &c, int N) {         // (see EncPlan::probes below)
+    int n = 0;
+    if (c.mode != ULCX_MODE_VBR || c.rates != nullptr) { n = 2; for (int m = N; m > 1; m >>= 1) n++; }
+    return n;
+}
 static EncPlan enc_plan(const UlcxEncCtx &c, const UlcxEncAux &aux) {
     EncPlan p;
     p.NB = c.B * c.K; p.N = c.C * c.BS; p.nUnits = p.NB * c.C * 4;
@@ -237,8 +242,7 @@ static EncPlan enc_plan(const UlcxEncCtx &c, const UlcxEncAux &aux) {
     // whatever it holds (VBR blocks skip every probe on the device).
     // No read-back: the host always enqueues the full count and a pass whose blocks have all converged (c.cbrLive,
     // counted down on the device) returns at the top of every kernel - nothing inside the call waits for the device.
-    p.probes = 0;
-    if (c.mode != ULCX_MODE_VBR || c.rates != nullptr) { p.probes = 2; for (int m = p.N; m > 1; m >>= 1) p.probes++; }
+    p.probes = enc_probes(c, p.N);
     p.barkLds = (size_t)c.barkRing * 3 * 64 * 8 + (size_t)2 * BK_TILE_FLOATS * 4;
     const int R = p.N / 64;
     p.selWave = (R == 4 || R == 8 || R == 16 || R == 32 || R == 64 || R == 128);
@@ -388,27 +392,13 @@ static int exact_passes(const UlcxEncCtx &c, const EncPlan &p, UlcxEncSync &sy, 
     return ULCX_OK;
 }
 
-int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux) {
-    UlcxEncCtx c = cIn;                                        // (keyFinal, selPass are set below)
-    UlcxEncSync &sy = aux.sync;
-    const EncPlan p = enc_plan(c, aux);
+// The pass loop of one rate setting over the call's intermediates: the probes of a rate search (none for VBR) and the final
+// pass, the exact path beside the final pass or behind the loop.  first: the call's first setting - its first pass carries
+// the stage events and is where the noise log-spectrum joins (or, without side streams, runs).
+static int launch_passes(UlcxEncCtx &c, const EncPlan &p, UlcxEncSync &sy, hipStream_t st, StageMarks &mk, bool first) {
     const int NB = p.NB;
-    StageMarks mk = { ev, 0 }, none = { nullptr, 0 };
-    if (p.probes) CK(hipMemsetAsync(c.cbrLive, 0, sizeof(int), st));
-    if (c.barkRing) CK(hipMemsetAsync(c.decCount, 0, sizeof(int), st));           // k_xf lists this call's decimated blocks
-    MARK(mk, st);
-    // --- window control + transform
-    TRY(launch_front(c, st, mk, aux, ULCX_FRONT_ENCODE));
-    if (ULCX_DBG(c) & 0x6000) { MARK(mk, st); return ULCX_OK; }     // (ablation build: stop behind window control / transform)
-    // --- sums, masking levels; the noise log-spectrum beside them (it does not feed the keys)
-    TRY(launch_psy(c, p, sy, st, mk, aux.wcPipe > 1));
-    // --- selection + encode pass(es)
-    // geometries the one-wave-per-block selection does not cover go through the multi-pass kernel, which reads every
-    // key several times: form the final keys once for it (and for the exact path's heapsort)
-    if (!p.selWave) { ulcx_enc_finalize_keys(c, st); c.keyFinal = 1; }
-    TRY(allow_lds((const void *)k_heapsel, p.heapLds)); TRY(allow_lds((const void *)k_heapsel_pipe, p.heapLds));
-    if (p.haveFull && (size_t)wavecaps_lds(p.capF) * 4 > 48 * 1024) CK(hipFuncSetAttribute((const void *)k_encode_wave<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wavecaps_lds(p.capF) * 4 + 16));
-    // (c.fbCount, c.isFb and the first pass's c.slow are cleared by k_cplx)
+    StageMarks none = { nullptr, 0 };
+    // (c.fbCount, c.isFb and the first pass's c.slow are cleared by k_cplx; for a further rung of a ladder call by k_rung_arm)
     // The exact path forks at the FINAL pass (a block can first straddle there) and runs on a side stream beside the main
     // path's final encode: VBR has only that pass; CBR/ABR blocks replay their whole search from the ranking there.
     // Without side streams it runs behind the lock-step passes on the caller's stream.
@@ -426,8 +416,10 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
             exact_sort(c, p, sy.side, 0);                      // needs only the keys: starts right behind the select
         }
         if (pass == 0) {
-            if (p.aside) CK(hipStreamWaitEvent(st, sy.noiseDone, 0));   // (k_nbark / k_nline intervals: hidden)
-            else launch_noise(c, p, st);
+            if (first) {
+                if (p.aside) CK(hipStreamWaitEvent(st, sy.noiseDone, 0));   // (k_nbark / k_nline intervals: hidden)
+                else launch_noise(c, p, st);
+            }
             MARK(m, st); MARK(m, st);
         }
         if (async_fb) {
@@ -451,12 +443,55 @@ int ulcx_enc_launch(const UlcxEncCtx &cIn, hipStream_t st, hipEvent_t *ev, const
             TRY(exact_passes(c, p, sy, st, lo));
         }
     }
-    MARK(mk, st);   // cbr_probe_passes (empty interval for VBR)
+    return ULCX_OK;
+}
+
+// One call under nRungs rate settings (ulcx_encode_*_ladder; a plain call is one rung).  The contexts differ in the setting
+// (mode / p0 / p1 / vbrTarget / rates) and in where the blocks and sizes go (out / bits).  Rung 0 is the call as it always
+// was: front half, sums and levels, then its passes - armed by k_cplx.  Every further rung is armed by k_rung_arm and runs
+// the pass loop again over the same intermediates, behind the previous rung's last kernel on the caller's stream and behind
+// its exact path's join: the arming clears what that path still reads.  The noise log-spectrum joins once (rung 0), the
+// state for the next call behind the last rung.
+int ulcx_enc_launch_ladder(const UlcxEncCtx *rungs, int nRungs, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux) {
+    UlcxEncCtx c = rungs[0];                                   // (keyFinal, selPass are set below)
+    UlcxEncSync &sy = aux.sync;
+    const EncPlan p = enc_plan(c, aux);
+    StageMarks mk = { ev, 0 }, none = { nullptr, 0 };
+    if (p.probes) CK(hipMemsetAsync(c.cbrLive, 0, sizeof(int), st));
+    if (c.barkRing) CK(hipMemsetAsync(c.decCount, 0, sizeof(int), st));           // k_xf lists this call's decimated blocks
+    if (nRungs > 1) CK(hipMemsetAsync(c.fbCount + 1, 0, sizeof(int), st));        // exact-path blocks of the rungs in front of the last
+    MARK(mk, st);
+    // --- window control + transform
+    TRY(launch_front(c, st, mk, aux, ULCX_FRONT_ENCODE));
+    if (ULCX_DBG(c) & 0x6000) { MARK(mk, st); return ULCX_OK; }     // (ablation build: stop behind window control / transform)
+    // --- sums, masking levels; the noise log-spectrum beside them (it does not feed the keys)
+    TRY(launch_psy(c, p, sy, st, mk, aux.wcPipe > 1));
+    // --- selection + encode pass(es)
+    // geometries the one-wave-per-block selection does not cover go through the multi-pass kernel, which reads every
+    // key several times: form the final keys once for it (and for the exact path's heapsort) - once per call, not per rung
+    if (!p.selWave) { ulcx_enc_finalize_keys(c, st); c.keyFinal = 1; }
+    TRY(allow_lds((const void *)k_heapsel, p.heapLds)); TRY(allow_lds((const void *)k_heapsel_pipe, p.heapLds));
+    if (p.haveFull && (size_t)wavecaps_lds(p.capF) * 4 > 48 * 1024) CK(hipFuncSetAttribute((const void *)k_encode_wave<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wavecaps_lds(p.capF) * 4 + 16));
+    TRY(launch_passes(c, p, sy, st, mk, true));
+    for (int r = 1; r < nRungs; r++) {
+        UlcxEncCtx cr = rungs[r];
+        cr.keyFinal = c.keyFinal;
+        EncPlan pr = p;
+        pr.probes = enc_probes(cr, p.N);
+        if (pr.probes) CK(hipMemsetAsync(cr.cbrLive, 0, sizeof(int), st));
+        ulcx_enc_rung_arm(cr, st);
+        TRY(launch_passes(cr, pr, sy, st, none, false));
+    }
+    MARK(mk, st);   // cbr_probe_passes (empty interval for VBR; a ladder call: every pass behind rung 0's first)
     if (p.aside) CK(hipStreamWaitEvent(st, sy.stateDone, 0));
     else launch_state_update(c, st);
     MARK(mk, st);
     CK(hipGetLastError());
     return ULCX_OK;
+}
+
+int ulcx_enc_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux) {
+    return ulcx_enc_launch_ladder(&c, 1, st, ev, aux);
 }
 
 // The analysis call (ulcx_analyse_dev): the front half of an encode call - window control in the same steps over the same side

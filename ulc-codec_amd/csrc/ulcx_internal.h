@@ -207,6 +207,9 @@ struct UlcxEncAux {                      // what a call's launch needs beside it
     int &nXf;                            // out: transform launches of a pipelined call (0: one launch, no xfTiming pairs)
 };
 int ulcx_enc_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev /* ULCX_ENC_STAGES+1 or NULL */, const UlcxEncAux &aux);
+// ulcx_encode_*_ladder: one context per rung (rung 0's carries wcOut / cplxOut); k_rung_arm arms rungs >= 1 (ulcx_enc_ladder.hip)
+int ulcx_enc_launch_ladder(const UlcxEncCtx *rungs, int nRungs, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux);
+void ulcx_enc_rung_arm(const UlcxEncCtx &c, hipStream_t st);
 struct UlcxDecAux {
     int synGrid;                         // > 0: workgroups of the synthesis over a cut of the (stream, block) pairs; 0: one per stream
     int synFull;                         // of those, the leading ones that take one whole stream each (0: an even cut of everything)

@@ -26,7 +26,10 @@ EXPORTS = [
     "ulcx_analyse_dev", "ulcx_analyse_dev_pcm16", "ulcx_analyse_host",
     "ulcx_index_packed_dev", "ulcx_index_packed_host", "ulcx_decode_range_dev", "ulcx_decode_range_dev_pcm16", "ulcx_decode_range_host",
     "ulcx_decoder_index_resident", "ulcx_decode_resident_range_host", "ulcx_dec_range_tail_plan",
+    "ulcx_encode_dev_ladder", "ulcx_encode_dev_pcm16_ladder", "ulcx_encode_host_ladder", "ulcx_encoder_last_rungs",
 ]
+
+MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
 
 # one entry of a block index (include/ulc_amd.h, ulcx_index_entry): 8 bytes
 INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
@@ -37,6 +40,11 @@ class FileHeader(C.Structure):
     """tools/ulc_Helper.h:10-20 (24 bytes)."""
     _fields_ = [("Magic", C.c_uint32), ("BlockSize", C.c_uint16), ("MaxBlockSize", C.c_uint16), ("nBlocks", C.c_uint32),
                 ("RateHz", C.c_uint32), ("nChan", C.c_uint16), ("RateKbps", C.c_uint16), ("StreamOffs", C.c_uint32)]
+
+
+class Rung(C.Structure):
+    """ulcx_rung (include/ulc_amd.h): one rung of a ladder call, 24 bytes; rate NULL = the scalar setting."""
+    _fields_ = [("mode", C.c_int32), ("param0", C.c_float), ("param1", C.c_float), ("reserved", C.c_int32), ("rate", C.c_void_p)]
 
 
 _lib = None
@@ -76,6 +84,11 @@ def lib():
             l.ulcx_decoder_index_resident.argtypes = [C.c_void_p, C.c_int, _i32p]
             l.ulcx_dec_range_tail_plan.argtypes = [C.c_int, C.c_int, C.c_int, _i32p]
             l.ulcx_decode_resident_range_host.argtypes = [C.c_void_p, _i32p, C.c_int, _f32p, _i32p]
+        if hasattr(l, "ulcx_encode_dev_ladder"):
+            l.ulcx_encode_dev_ladder.argtypes = [C.c_void_p, C.POINTER(Rung), C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_encode_dev_pcm16_ladder.argtypes = l.ulcx_encode_dev_ladder.argtypes
+            l.ulcx_encode_host_ladder.argtypes = [C.c_void_p, C.POINTER(Rung), C.c_int, _f32p, C.c_int, _u8p, _i32p, _i32p, _f32p]
+            l.ulcx_encoder_last_rungs.argtypes = [C.c_void_p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -190,6 +203,57 @@ class BatchEncoder:
         _check(fn(self.h, d_rates, d_pcm, n_blocks, d_out, d_bits, d_wc or None, d_cplx or None, stream or None),
                "ulcx_encode_dev_pcm16_rates" if pcm16 else "ulcx_encode_dev_rates")
         self.lastK = n_blocks
+
+    @staticmethod
+    def _rungs(rungs, table_ptr):
+        """ctypes array of ulcx_rung from a list whose entries are (mode, p0[, p1]) or a per-stream table; table_ptr(t) gives
+        the table's address.  No limit on the count here: the library checks it."""
+        arr = (Rung * max(len(rungs), 1))()
+        for r, g in enumerate(rungs):
+            if isinstance(g, tuple):
+                arr[r].mode, arr[r].param0, arr[r].param1 = int(g[0]), float(g[1]), float(g[2]) if len(g) > 2 else 0.0
+            else:
+                arr[r].rate = table_ptr(g)
+        return arr
+
+    def encode_ladder(self, pcm, rungs):
+        """One call, several rate settings: each rung is a tuple (mode, p0[, p1]) for the whole batch or a float32 array
+        [B][2] = {RateKbps, AvgComplexity} per stream (as encode_rates takes it).  Returns out[R][B][K][slot], bits[R][B][K],
+        wc[B][K], cplx[B][K]; the streams' state advances once."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        assert pcm.shape[0] == self.B and pcm.shape[-1] == self.C
+        K = pcm.shape[1] // self.BS
+        assert pcm.shape[1] == K * self.BS
+        tables = []                                            # (kept alive over the call)
+
+        def host_table(t):
+            t = np.ascontiguousarray(t, dtype=np.float32)
+            assert t.shape == (self.B, 2)
+            tables.append(t)
+            return t.ctypes.data
+        arr = self._rungs(rungs, host_table)
+        R = len(rungs)
+        out = np.zeros((max(R, 1), self.B, K, self.slot), np.uint8)
+        bits = np.zeros((max(R, 1), self.B, K), np.int32)
+        wc = np.zeros((self.B, K), np.int32)
+        cplx = np.zeros((self.B, K), np.float32)
+        _check(lib().ulcx_encode_host_ladder(self.h, arr, R, _p(pcm, _f32p), K, _p(out, _u8p), _p(bits, _i32p),
+                                             _p(wc, _i32p), _p(cplx, _f32p)), "ulcx_encode_host_ladder")
+        self.lastK = K
+        return out, bits, wc, cplx
+
+    def encode_dev_ladder(self, rungs, d_pcm, n_blocks, d_out, d_bits, d_wc=0, d_cplx=0, stream=0, pcm16=False):
+        """Device-pointer ladder call, asynchronous on `stream`: rungs as in encode_ladder, a table rung being the device
+        address (int / .data_ptr()) of float32 [B][2]; d_out [R][B][K][slot], d_bits [R][B][K]; pcm16=True takes int16 samples."""
+        arr = self._rungs(rungs, int)
+        fn = lib().ulcx_encode_dev_pcm16_ladder if pcm16 else lib().ulcx_encode_dev_ladder
+        _check(fn(self.h, arr, len(rungs), d_pcm, n_blocks, d_out, d_bits, d_wc or None, d_cplx or None, stream or None),
+               "ulcx_encode_dev_pcm16_ladder" if pcm16 else "ulcx_encode_dev_ladder")
+        self.lastK = n_blocks
+
+    def last_rungs(self):
+        """Rungs of the last encode call (1 for a plain or per-stream-rates call, 0 after an analysis call)."""
+        return int(lib().ulcx_encoder_last_rungs(self.h))
 
     def encode_dev(self, d_pcm, n_blocks, d_out, d_bits, d_wc=0, d_cplx=0, mode=MODE_VBR, p0=50.0, p1=0.0, stream=0):
         """Device-pointer path (ints / .data_ptr()); asynchronous on `stream`."""
