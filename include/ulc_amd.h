@@ -124,6 +124,37 @@ enum {
 
 enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
 
+/* Caller buffers of the device-pointer entries (ulcx_*_dev*, ulcx_pack_streams_dev).  tests/test_gpu_buffer_contract.py holds
+ * the library to every line of this: each call there runs on poisoned buffers between guards (tests/guarded_buffers.py).
+ *
+ * ALIGNMENT.  The widest access a kernel makes to the buffer; every row of a buffer keeps it (rows are multiples of it).
+ *   16 bytes  binary32 samples: d_pcm of the encode, analyse, decode, decode_packed and decode_range calls
+ *             (16-byte loads of the transform's fold, 16-byte stores of the stereo synthesis)
+ *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
+ *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
+ *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, and d_index (an entry is two
+ *             4-byte words)
+ *    none     the byte streams: d_out, d_in, d_slots, d_payload (slotBytes and payloadStride may be any positive value)
+ *   A pointer that violates this makes the call return ULCX_ERR_ARG before any device work; the object's state is untouched
+ *   and the next valid call continues as if the refused one had not been made.  (hipMalloc and the allocators built on it
+ *   return 256-byte aligned memory: only pointers INTO an allocation can fail this.)
+ *
+ * EXTENT.  A call reads its inputs and writes its outputs, nothing else of the caller's: no byte in front of a buffer, none
+ * behind the sizes given below for nBlocks (not maxBlocksPerCall) blocks, and no byte of an input.  Of the outputs
+ *   d_bits, d_wc, d_cplx, d_pcm / d_pcm16, d_nBlocks, d_payloadBytes, d_maxBlock and the index are written in full: every
+ *             element for nBlocks blocks - for a stream that ended (a corrupt block, the end of its payload) 0 bits and zero
+ *             samples for every block from there on, whatever the buffer held; all maxBlocks + 1 index entries of a stream,
+ *             the {-1, 0} ones behind the closing entry included
+ *   d_out     bytes [0, d_bits / 8) of each slot are the block; the rest of the slot is NOT defined (today it keeps what the
+ *             buffer held; no caller may rely on that): read a slot through its d_bits
+ *   d_payload bytes [0, d_payloadBytes[s]) of stream s; the rest of payloadStride is not defined (not written)
+ *   A NULL d_wc / d_cplx / d_maxBlock changes nothing else the call writes.
+ *
+ * ORDER.  Every call is enqueued on hipStream and returns without waiting for the device.  The private side streams it uses
+ * have been joined back into hipStream by then, for reads of the inputs as for writes of the outputs: work enqueued on
+ * hipStream after the call returns - a copy of the outputs, an overwrite of d_pcm with the next blocks - is ordered behind
+ * all of it, with no event or synchronisation of the caller's.  Another stream needs an event recorded on hipStream. */
+
 const char *ulcx_last_error(void);
 int  ulcx_device_count(void);                 /* <= 0 when no usable device */
 const char *ulcx_build_rev(void);             /* 12 hex digits: sha1 of the sources the library was built from (Makefile) */

@@ -245,6 +245,20 @@ def test_decode_bit_exact(bs, ch, rate, q):
     dec.close()
 
 
+def _decode_dev_filled(dec, blocks, bs, ch):
+    """decode_dev into buffers that hold noise-like values and impossible sizes before the call (the host form's results start
+    as zeros, and "a dead stream must stay silent" says nothing about a buffer that was silent already)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    B, K, slot = blocks.shape
+    d_in = torch.from_numpy(np.ascontiguousarray(blocks)).to(dev)
+    p = torch.full((B, K * bs, ch), 0.3125, dtype=torch.float32, device=dev)
+    b = torch.full((B, K), -7, dtype=torch.int32, device=dev)
+    dec.decode_dev(d_in.data_ptr(), slot, K, p.data_ptr(), b.data_ptr())
+    torch.cuda.synchronize()
+    return p.cpu().numpy(), b.cpu().numpy()
+
+
 @pytest.mark.parametrize("bs,rate", [(2048, 44100), (4096, 48000), (1024, 44100)])
 def test_decode_few_long_streams_cut_evenly(bs, rate):
     """Round 3: a batch that does not fill the machine with one workgroup per stream - here 3 stereo streams of 40 blocks per
@@ -267,7 +281,7 @@ def test_decode_few_long_streams_cut_evenly(bs, rate):
             dec = amd.BatchDecoder(B, ch, bs, K)
             got, gbits = [], []
             for c in range(calls):
-                p, b = dec.decode(blocks[:, c * K:(c + 1) * K])
+                p, b = _decode_dev_filled(dec, blocks[:, c * K:(c + 1) * K], bs, ch)
                 got.append(p); gbits.append(b)
             outs[split] = (np.concatenate(got, axis=1), np.concatenate(gbits, axis=1))
             dec.close()
@@ -333,7 +347,8 @@ def test_decode_last_round_cut_into_pieces():
             dec = amd.BatchDecoder(B, ch, bs, K)
             dp = torch.zeros(B, calls * K * bs, ch, dtype=torch.float32, device=dev); db = torch.zeros(B, calls * K, dtype=torch.int32, device=dev)
             for c in range(calls):
-                p = torch.zeros(B, K * bs, ch, dtype=torch.float32, device=dev); b = torch.zeros(B, K, dtype=torch.int32, device=dev)
+                # (not silent before the call: "a dead stream must stay silent" below has to be the decoder's doing)
+                p = torch.full((B, K * bs, ch), 0.3125, dtype=torch.float32, device=dev); b = torch.full((B, K), -7, dtype=torch.int32, device=dev)
                 dec.decode_dev(out[:, c * K:(c + 1) * K].contiguous().data_ptr(), slot, K, p.data_ptr(), b.data_ptr())
                 torch.cuda.synchronize()
                 dp[:, c * K * bs:(c + 1) * K * bs] = p; db[:, c * K:(c + 1) * K] = b
@@ -484,11 +499,15 @@ def test_packed_stream_pack_and_decode():
     dev = torch.device("cuda", 0)
     slots = torch.from_numpy(np.stack([r["out"] for r in refs])).to(dev)
     bits = torch.from_numpy(np.stack([r["bits"] for r in refs])).to(dev)
-    pay = torch.zeros(B, stride, dtype=torch.uint8, device=dev); pb = torch.zeros(B, dtype=torch.int32, device=dev); mb = torch.zeros(B, dtype=torch.int32, device=dev)
+    # (0xA5 / -7 before the call: the bytes of a payload row behind payloadBytes[s] are not defined, include/ulc_amd.h "Caller buffers")
+    pay = torch.full((B, stride), 0xA5, dtype=torch.uint8, device=dev); pb = torch.full((B,), -7, dtype=torch.int32, device=dev); mb = torch.full((B,), -7, dtype=torch.int32, device=dev)
     rc = amd.lib().ulcx_pack_streams_dev(0, B, K, slot, slots.data_ptr(), bits.data_ptr(), pay.data_ptr(), stride, pb.data_ptr(), mb.data_ptr(), None)
     assert rc == 0
     torch.cuda.synchronize()
-    assert np.array_equal(pb.cpu().numpy(), nbytes) and np.array_equal(pay.cpu().numpy(), host)
+    assert np.array_equal(pb.cpu().numpy(), nbytes)
+    gpay = pay.cpu().numpy()
+    for s in range(B):
+        assert np.array_equal(gpay[s, :nbytes[s]], host[s, :nbytes[s]]), f"payload of stream {s} differs from the host concatenation"
     assert np.array_equal(mb.cpu().numpy(), np.array([((r["bits"] + 7) // 8).max() for r in refs]))
     # packed decode in two calls
     dec = amd.BatchDecoder(B, ch, bs, K // 2)

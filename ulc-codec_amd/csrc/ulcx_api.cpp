@@ -113,6 +113,19 @@ static int validate(int C, int BS) {                 // ulcEncoder.c:32-34 / ulc
 }
 static int ilog2i(int x) { int r = 0; while ((1 << r) < x) r++; return r; }
 
+// Alignment of the caller's device pointers (include/ulc_amd.h, "Caller buffers"): each value is the widest access a kernel
+// makes to that buffer - 16 bytes for binary32 samples (float4 loads of the transform's fold, float4 stores of the
+// synthesis), 8 for PCM16 samples (short4) and for rate tables (float2), 4 for the int32 / binary32 / index arrays; the
+// byte streams (slots, payloads) need none.  A NULL (optional) pointer passes.  Checked by every _dev entry before any device
+// work, so that a refused call leaves the object's state as it was.
+enum { ULCX_ALIGN_PCM = 16, ULCX_ALIGN_PCM16 = 8, ULCX_ALIGN_RATE = 8, ULCX_ALIGN_WORD = 4 };
+static bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+static int misaligned(const char *who, const char *what, const void *p, int a) {
+    if (aligned_to(p, (uintptr_t)a)) return 0;
+    ulcx_set_error("%s: %s (%p) is not aligned to %d bytes", who, what, p, a);
+    return 1;
+}
+
 template <typename T>
 static int dalloc(std::vector<void *> &v, T **p, size_t count, bool zero) {
     void *q = nullptr;
@@ -337,6 +350,9 @@ static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const u
     if (!e || (!d_pcm && !d_pcm16) || !d_out || !d_bits || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_encode_dev: bad argument"); return ULCX_ERR_ARG; }
     if (d_rate) { mode = ULCX_MODE_VBR; p0 = 100.0f; p1 = 0.0f; }
     if (mode != ULCX_MODE_VBR && mode != ULCX_MODE_CBR && mode != ULCX_MODE_ABR) { ulcx_set_error("bad mode"); return ULCX_ERR_ARG; }
+    if (misaligned("ulcx_encode_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_encode_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned("ulcx_encode_dev", "d_rate", d_rate, ULCX_ALIGN_RATE) || misaligned("ulcx_encode_dev", "d_bits", d_bits, ULCX_ALIGN_WORD) ||
+        misaligned("ulcx_encode_dev", "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned("ulcx_encode_dev", "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxEncCtx c = e->ctx;
     c.K = nBlocks; c.keyFinal = 0; c.mode = mode; c.p0 = p0; c.p1 = p1;
@@ -367,6 +383,10 @@ static int encode_ladder_any(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs
                              uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
     if (!e || !rungs || (!d_pcm && !d_pcm16) || !d_out || !d_bits || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_encode_dev_ladder: bad argument"); return ULCX_ERR_ARG; }
     { const int rc = ladder_check(rungs, nRungs, "ulcx_encode_dev_ladder"); if (rc) return rc; }
+    if (misaligned("ulcx_encode_dev_ladder", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_encode_dev_ladder", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned("ulcx_encode_dev_ladder", "d_bits", d_bits, ULCX_ALIGN_WORD) || misaligned("ulcx_encode_dev_ladder", "d_wc", d_wc, ULCX_ALIGN_WORD) ||
+        misaligned("ulcx_encode_dev_ladder", "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    for (int r = 0; r < nRungs; r++) if (misaligned("ulcx_encode_dev_ladder", "a rung's rate table", rungs[r].rate, ULCX_ALIGN_RATE)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxEncCtx cs[ULCX_MAX_RUNGS];
     const size_t NB = (size_t)e->B * nBlocks;
@@ -406,6 +426,8 @@ extern "C" int ulcx_encoder_last_rungs(ulcx_encoder *e) { return e ? e->lastRung
 // ---- analysis only (include/ulc_amd.h): window control, MDCT, block complexity, next-call state
 static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
     if (!e || (!d_pcm && !d_pcm16) || (!d_wc && !d_cplx) || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_analyse_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (misaligned("ulcx_analyse_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_analyse_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned("ulcx_analyse_dev", "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned("ulcx_analyse_dev", "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxEncCtx c = e->ctx;
     c.K = nBlocks; c.keyFinal = 0; c.mode = ULCX_MODE_VBR; c.p0 = 100.0f; c.p1 = 0.0f; c.vbrTarget = 0.0f; c.rates = nullptr;
@@ -957,6 +979,8 @@ static int dec_host_staging(ulcx_decoder *e, size_t nBlk, size_t inBytes) {
 
 static int decode_dev_any(ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
     if (!e || !d_in || (!d_pcm && !d_pcm16) || !d_bits || slotBytes < 1 || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_decode_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (misaligned("ulcx_decode_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_decode_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned("ulcx_decode_dev", "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.K = nBlocks; c.slot = slotBytes; c.in = d_in; c.pcm = d_pcm; c.pcm16 = d_pcm16; c.bits = d_bits;
@@ -1064,6 +1088,8 @@ extern "C" int ulcx_ulc_rate_kbps(uint64_t totalBytes, uint32_t RateHz, uint32_t
 extern "C" int ulcx_pack_streams_dev(int device, int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits,
                                      uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock, void *hipStream) {
     if (nStreams < 1 || nBlocks < 1 || slotBytes < 1 || !d_slots || !d_bits || !d_payload || !d_payloadBytes || payloadStride < 1) { ulcx_set_error("ulcx_pack_streams_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (misaligned("ulcx_pack_streams_dev", "d_bits", d_bits, ULCX_ALIGN_WORD) || misaligned("ulcx_pack_streams_dev", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) ||
+        misaligned("ulcx_pack_streams_dev", "d_maxBlock", d_maxBlock, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     int rc = select_device(device);
     if (rc) return rc;
     return ulcx_pack_launch(nStreams, nBlocks, slotBytes, d_slots, d_bits, d_payload, payloadStride, d_payloadBytes, d_maxBlock, (hipStream_t)hipStream);
@@ -1071,6 +1097,8 @@ extern "C" int ulcx_pack_streams_dev(int device, int nStreams, int nBlocks, int 
 extern "C" int ulcx_decode_packed_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                                       int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
     if (!e || !d_payload || !d_payloadBytes || !d_pcm || !d_bits || payloadStride < 1 || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_decode_packed_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (misaligned("ulcx_decode_packed_dev", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned("ulcx_decode_packed_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) ||
+        misaligned("ulcx_decode_packed_dev", "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.K = nBlocks; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = nullptr; c.bits = d_bits;
@@ -1138,6 +1166,8 @@ extern "C" int ulcx_decode_resident_host(ulcx_decoder *e, int nBlocks, float *h_
 extern "C" int ulcx_index_packed_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                                      int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
     if (!e || !d_payload || !d_payloadBytes || !d_index || !d_nBlocks || payloadStride < 1 || maxBlocks < 1) { ulcx_set_error("ulcx_index_packed_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (misaligned("ulcx_index_packed_dev", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned("ulcx_index_packed_dev", "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned("ulcx_index_packed_dev", "d_nBlocks", d_nBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.in = d_payload; c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
@@ -1168,6 +1198,10 @@ static int decode_range_any(ulcx_decoder *e, const uint8_t *d_payload, long long
     // (the block in front of a range takes one row of the per-block scratch: nBlocks <= maxBlocksPerCall - 1)
     if (!e || !d_payload || !d_payloadBytes || !d_index || !d_indexBlocks || !d_first || (!d_pcm && !d_pcm16) || !d_bits ||
         payloadStride < 1 || indexStride < 1 || nBlocks < 1 || nBlocks > e->maxK - 1) { ulcx_set_error("ulcx_decode_range: bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return ULCX_ERR_ARG; }
+    if (misaligned("ulcx_decode_range", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned("ulcx_decode_range", "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned("ulcx_decode_range", "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned("ulcx_decode_range", "d_first", d_first, ULCX_ALIGN_WORD) ||
+        misaligned("ulcx_decode_range", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_decode_range", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned("ulcx_decode_range", "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.K = nBlocks + 1; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = d_pcm16;
