@@ -34,6 +34,35 @@ __device__ __forceinline__ int quant_coef_u(float v, int lim) { int q = quant_u(
 
 __device__ __forceinline__ int quant_coef(float v, int lim) { int q = quant_coef_u(fabsf(v), lim); return v < 0.0f ? -q : q; }
 
+__device__ __forceinline__ int build_quantizer(float maxv) {                         // Encode.c:50-87
+    int q = (int)(0x1.657006p2f + -0x1.715476p0f * ulcx_logf(maxv));
+    if (q < 5) q = 5;
+    if (q > 31) q = 31;
+    return q;
+}
+
+// get_noise_q with the sums already evaluated (k_nsums)
+__device__ __forceinline__ int noise_q_from_sums(float sum, float sumw, float q) {
+    if (sum == 0.0f) return 0;
+    float amp = ulcx_expf(sum / sumw);
+    return quant_coef_u(amp * q, 8);
+}
+
+// get_hfext with the five sums already evaluated (k_nsums)
+__device__ __forceinline__ void hfext_from_sums(float sx, float sx2, float sxy, float sy, float sw, float q, int &noiseQ, int &noiseDecay) {
+    float det = sw * sx2 - sx * sx;
+    if (det == 0.0f) { noiseQ = noiseDecay = 0; return; }
+    float amp = (sx2 * sy - sx * sxy) / det;
+    float dec = (sw * sxy - sx * sy) / det;
+    amp = ulcx_expf(amp);
+    dec = (dec < 0.0f) ? ulcx_expf(dec) : 1.0f;
+    int nq = quant_coef_u(amp * q * 4.0f, 16);
+    int nd = quant_u((dec - 1.0f) * -0x1.0p19f);
+    if (!nd) return;
+    if (nd > 0xFF) nd = 0xFF;
+    noiseQ = nq; noiseDecay = nd;
+}
+
 // Input samples.  IN = float: the C API's layout; IN = int16_t: PCM16 ingest, converted on load
 // exactly as the reference's WAV reader does (tools/WavIO_Helper.c:49-55: (float)x * 2^-15, exact).  The two blocks kept
 // from previous calls (c.hist) are always float.
@@ -350,6 +379,35 @@ __device__ __forceinline__ uint32_t key_ord(float f) {          // ascending ord
     uint32_t u = __float_as_uint(f);
     if ((u << 1) == 0) u = 0;                                   // -0 and +0 compare equal in the reference
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// BlockTransform.c:337-345: key = 2*key0 + MaskingNp[n/2] + Log[0.5^2]*(Chan&1), formed where the
+// keys are consumed (selection kernels) instead of being written back to HBM.
+__device__ __forceinline__ float final_key(float v, float m, int ch) {
+    float t = 2 * v + m;
+    if (ch & 1) t = t + -0x1.62E430p0f;
+    return t;
+}
+
+// BlockTransform.c:250-253: key0 = FastLog(Re^2), or -inf for a coefficient that counts as zero
+__device__ __forceinline__ float key0_of(float re) {
+    float k = fastlog(re * re);                            // evaluated unconditionally: a select, not a branch per coefficient
+    asm volatile("" : "+v"(k));
+    return (fabsf(re) < 0.5f * ULCX_COEF_EPS) ? __uint_as_float(0xff800000u) : k;
+}
+
+// The same key as key_ord(final_key(key0_of(re), m, ch)) for the wave selection (round 3: 30 -> 21 vector instructions per
+// key).  2*v is exact, so fma(v, 2, m) rounds once where 2*v + m rounds once: identical.  The key is never -0.0 (a sum is -0
+// only if both terms are, and ln2 * (float)e is +0 for e = 0; the channel constant is not 0), so the map needs no zero
+// test: two instructions, arithmetic shift + one three-input bit operation.
+__device__ __forceinline__ uint32_t sel_key(float re, float m, int ch) {
+    float k = fastlog(re * re);                            // (evaluated unconditionally: a select, not a branch per coefficient)
+    asm("" : "+v"(k));
+    k = (fabsf(re) < 0.5f * ULCX_COEF_EPS) ? __uint_as_float(0xff800000u) : k;
+    float t = __builtin_fmaf(k, 2.0f, m);
+    if (ch & 1) t = t + -0x1.62E430p0f;
+    const uint32_t u = __float_as_uint(t);
+    return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
 }
 
 // ---------------------------------------------------------------------------

@@ -239,35 +239,6 @@ __global__ __launch_bounds__(WG) void k_bark_levels(UlcxEncCtx c) {
         (NOISE ? c.barkN : c.barkP)[(size_t)row * 4 * ULCX_NBARK + b] = below ? taken : (NOISE ? -100.0f : 0.0f);
 }
 
-// BlockTransform.c:337-345: key = 2*key0 + MaskingNp[n/2] + Log[0.5^2]*(Chan&1), formed where the
-// keys are consumed (selection kernels) instead of being written back to HBM.
-__device__ __forceinline__ float final_key(float v, float m, int ch) {
-    float t = 2 * v + m;
-    if (ch & 1) t = t + -0x1.62E430p0f;
-    return t;
-}
-
-// BlockTransform.c:250-253: key0 = FastLog(Re^2), or -inf for a coefficient that counts as zero
-__device__ __forceinline__ float key0_of(float re) {
-    float k = fastlog(re * re);                            // evaluated unconditionally: a select, not a branch per coefficient
-    asm volatile("" : "+v"(k));
-    return (fabsf(re) < 0.5f * ULCX_COEF_EPS) ? __uint_as_float(0xff800000u) : k;
-}
-
-// The same key as key_ord(final_key(key0_of(re), m, ch)) for the wave selection (round 3: 30 -> 21 vector instructions per
-// key).  2*v is exact, so fma(v, 2, m) rounds once where 2*v + m rounds once: identical.  The key is never -0.0 (a sum is -0
-// only if both terms are, and ln2 * (float)e is +0 for e = 0; the channel constant is not 0), so the map needs no zero
-// test: two instructions, arithmetic shift + one three-input bit operation.
-__device__ __forceinline__ uint32_t sel_key(float re, float m, int ch) {
-    float k = fastlog(re * re);                            // (evaluated unconditionally: a select, not a branch per coefficient)
-    asm("" : "+v"(k));
-    k = (fabsf(re) < 0.5f * ULCX_COEF_EPS) ? __uint_as_float(0xff800000u) : k;
-    float t = __builtin_fmaf(k, 2.0f, m);
-    if (ch & 1) t = t + -0x1.62E430p0f;
-    const uint32_t u = __float_as_uint(t);
-    return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
-}
-
 // Psyopt.c:140-150: masking level of line pair jp (0 <= jp < BS/2) of a block: interpolation between the Bark levels of
 // its subblock (bark4 = the block's [4][25] levels from k_pbark).  Evaluated where the keys are formed: no array of it in HBM.
 __device__ __forceinline__ float mask_level(const UlcxEncCtx &c, const float *bark4, int wc, int jp) {

@@ -316,13 +316,6 @@ __device__ __forceinline__ void put_quantizer(NybWriter &w, int qi, bool lead) {
     else { w.put(0xE); w.put((unsigned)(s - 0xE)); }
 }
 
-__device__ __forceinline__ int build_quantizer(float maxv) {                         // Encode.c:50-87
-    int q = (int)(0x1.657006p2f + -0x1.715476p0f * ulcx_logf(maxv));
-    if (q < 5) q = 5;
-    if (q > 31) q = 31;
-    return q;
-}
-
 __device__ __forceinline__ bool kept(const uint32_t *keep, int i) { return (keep[i >> 5] >> (i & 31)) & 1; }
 
 // first kept index in [i, end), or end
@@ -345,28 +338,6 @@ __device__ __forceinline__ int get_noise_q(const SumSrc &g, int band, int n, flo
     if (sum == 0.0f) return 0;
     float amp = ulcx_expf(sum / sumw);
     return quant_coef_u(amp * q, 8);
-}
-
-// get_noise_q with the sums already evaluated (k_nsums)
-__device__ __forceinline__ int noise_q_from_sums(float sum, float sumw, float q) {
-    if (sum == 0.0f) return 0;
-    float amp = ulcx_expf(sum / sumw);
-    return quant_coef_u(amp * q, 8);
-}
-
-// get_hfext with the five sums already evaluated (k_nsums)
-__device__ __forceinline__ void hfext_from_sums(float sx, float sx2, float sxy, float sy, float sw, float q, int &noiseQ, int &noiseDecay) {
-    float det = sw * sx2 - sx * sx;
-    if (det == 0.0f) { noiseQ = noiseDecay = 0; return; }
-    float amp = (sx2 * sy - sx * sxy) / det;
-    float dec = (sw * sxy - sx * sy) / det;
-    amp = ulcx_expf(amp);
-    dec = (dec < 0.0f) ? ulcx_expf(dec) : 1.0f;
-    int nq = quant_coef_u(amp * q * 4.0f, 16);
-    int nd = quant_u((dec - 1.0f) * -0x1.0p19f);
-    if (!nd) return;
-    if (nd > 0xFF) nd = 0xFF;
-    noiseQ = nq; noiseDecay = nd;
 }
 
 // NoiseFill.c:41-94
