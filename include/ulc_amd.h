@@ -130,11 +130,13 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  * ALIGNMENT.  The widest access a kernel makes to the buffer; every row of a buffer keeps it (rows are multiples of it).
  *   16 bytes  binary32 samples: d_pcm of the encode, analyse, decode, decode_packed and decode_range calls
  *             (16-byte loads of the transform's fold, 16-byte stores of the stereo synthesis)
+ *             saved stream records: d_state of the stream-slot entries (16-byte loads and stores)
  *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
- *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, and d_index (an entry is two
- *             4-byte words)
- *    none     the byte streams: d_out, d_in, d_slots, d_payload (slotBytes and payloadStride may be any positive value)
+ *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_index (an entry is two
+ *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n])
+ *    none     the byte streams: d_out, d_in, d_payload and ulcx_pack_streams_dev's d_slots (slotBytes and payloadStride may be
+ *             any positive value)
  *   A pointer that violates this makes the call return ULCX_ERR_ARG before any device work; the object's state is untouched
  *   and the next valid call continues as if the refused one had not been made.  (hipMalloc and the allocators built on it
  *   return 256-byte aligned memory: only pointers INTO an allocation can fail this.)
@@ -332,6 +334,72 @@ int  ulcx_decode_block1_rng(ulcx_decoder *dec, const uint8_t *h_in, int nBytes, 
  * (tools/WavIO_Helper.c:9-13,56-63: lrintf(clamp(x * 2^15, -32768, 32767))). */
 int  ulcx_decode_dev_pcm16(ulcx_decoder *dec, const uint8_t *d_in, int slotBytes, int nBlocks,
                            int16_t *d_pcm16, int32_t *d_bits, void *hipStream);
+
+/* Stream slots: per-stream reset, save / load and calls on a subset of an object's streams.
+ * An object of nStreams streams has nStreams slots.  The entries above advance every slot in every call and the whole-object
+ * reset rewinds all of them; the entries below work on the slots a list names, so that a slot whose stream has ended can
+ * start another while its neighbours keep going, streams of different length share a batch without padding, and a stream
+ * can be carried from one object (or device) to another mid-way.
+ *   d_slots  DEVICE int32 [n], 4-byte aligned: slots of the object, n in 1 .. nStreams (h_slots of the host forms: a host array)
+ *   d_state  DEVICE bytes [n][ulcx_*_stream_state_bytes], 16-byte aligned: one saved record per listed slot
+ * All _dev forms are asynchronous on hipStream like their siblings and keep the ALIGNMENT / EXTENT / ORDER contract above
+ * (a misaligned d_slots or d_state returns ULCX_ERR_ARG before any device work; save writes all n records in full).
+ *
+ * RESET.  A reset slot is in the state right after create: the next block fed to it is block 0 of a new stream.
+ * SUBSET CALLS.  Row i of every buffer of the call belongs to slot d_slots[i] ([n][nBlocks]... instead of [nStreams][nBlocks]...);
+ * only the listed slots' state is read and advanced.  Block k of the stream in slot s is byte for byte what
+ * ULC_EncodeBlock_* / ULC_DecodeBlock writes for that stream fed on its own, every other slot's state is untouched, and
+ * subset, plain, _rates, ladder, analysis, packed and range calls may be mixed freely on one object.  With d_slots = 0 ..
+ * nStreams-1 a subset call writes what the plain call writes.  d_rate NULL: the scalar mode / param0 / param1; d_rate != NULL:
+ * a device table [n] as ulcx_encode_dev_rates takes it, row i for slot d_slots[i].  A subset call gathers the listed slots'
+ * state into a compact copy (allocated on the first such call, nStreams slots large), runs the plain call's kernels on it
+ * and scatters the result back, all on hipStream.  Ladder, packed and range subset forms do not exist (yet).
+ * SAVED RECORDS.  A record is a 16-byte header - uint32 magic, nChan, BlockSize, RateHz (0 in a decoder's record) - followed
+ * by the stream's state: the encoder's two blocks of input history and window-control state; the decoder's lapping buffer,
+ * LastSubBlockSize, noise generator, dead flag and packed read position.  ulcx_*_stream_state_bytes is a multiple of 16.
+ * A record loads into any slot of any object of the same kind, nChan, BlockSize, RateHz and ulcx_build_rev(); nStreams,
+ * maxBlocksPerCall and the device may differ (the bytes are plain: copy them through the host or peer to peer).  The host
+ * load form refuses a record whose header does not match with ULCX_ERR_ARG; the device form leaves that slot as it was.
+ * BAD LISTS.  The host forms refuse an entry outside [0, nStreams) and a duplicate entry with ULCX_ERR_ARG before any device
+ * work, leaving the object untouched.  The device forms cannot refuse without a synchronisation: the row of an out-of-range
+ * entry is processed from a fresh state and that state is discarded, save writes a fresh-state record for it, reset and load
+ * skip it; with duplicate entries every row starts from the slot's state in front of the call and which row's state
+ * remains is unspecified.  In every case nothing outside the call's buffers and the object is read or written. */
+size_t ulcx_encoder_stream_state_bytes(const ulcx_encoder *enc);      /* 0 for NULL */
+size_t ulcx_decoder_stream_state_bytes(const ulcx_decoder *dec);
+int  ulcx_encoder_reset_streams_dev(ulcx_encoder *enc, const int32_t *d_slots, int n, void *hipStream);
+int  ulcx_encoder_save_streams_dev (ulcx_encoder *enc, const int32_t *d_slots, int n, uint8_t *d_state, void *hipStream);
+int  ulcx_encoder_load_streams_dev (ulcx_encoder *enc, const int32_t *d_slots, int n, const uint8_t *d_state, void *hipStream);
+int  ulcx_decoder_reset_streams_dev(ulcx_decoder *dec, const int32_t *d_slots, int n, void *hipStream);
+int  ulcx_decoder_save_streams_dev (ulcx_decoder *dec, const int32_t *d_slots, int n, uint8_t *d_state, void *hipStream);
+int  ulcx_decoder_load_streams_dev (ulcx_decoder *dec, const int32_t *d_slots, int n, const uint8_t *d_state, void *hipStream);
+int  ulcx_encode_dev_subset      (ulcx_encoder *enc, const int32_t *d_slots, int n, int mode, float param0, float param1,
+                                  const ulcx_rate *d_rate, const float *d_pcm /* [n][nBlocks][BlockSize][nChan] */, int nBlocks,
+                                  uint8_t *d_out /* [n][nBlocks][slot_bytes] */, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_encode_dev_pcm16_subset(ulcx_encoder *enc, const int32_t *d_slots, int n, int mode, float param0, float param1,
+                                  const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
+                                  uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_analyse_dev_subset     (ulcx_encoder *enc, const int32_t *d_slots, int n, const float *d_pcm, int nBlocks,
+                                  int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_decode_dev_subset      (ulcx_decoder *dec, const int32_t *d_slots, int n, const uint8_t *d_in /* [n][nBlocks][slotBytes] */,
+                                  int slotBytes, int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_dev_pcm16_subset(ulcx_decoder *dec, const int32_t *d_slots, int n, const uint8_t *d_in,
+                                  int slotBytes, int nBlocks, int16_t *d_pcm16, int32_t *d_bits, void *hipStream);
+/* Synchronous host forms (host pointers throughout; h_rate, when given, is validated as ulcx_encode_host_rates validates it).
+ * Every check - list, record headers, rates - comes before any device work: a refused call leaves the object untouched. */
+int  ulcx_encoder_reset_streams_host(ulcx_encoder *enc, const int32_t *h_slots, int n);
+int  ulcx_encoder_save_streams_host (ulcx_encoder *enc, const int32_t *h_slots, int n, uint8_t *h_state);
+int  ulcx_encoder_load_streams_host (ulcx_encoder *enc, const int32_t *h_slots, int n, const uint8_t *h_state);
+int  ulcx_decoder_reset_streams_host(ulcx_decoder *dec, const int32_t *h_slots, int n);
+int  ulcx_decoder_save_streams_host (ulcx_decoder *dec, const int32_t *h_slots, int n, uint8_t *h_state);
+int  ulcx_decoder_load_streams_host (ulcx_decoder *dec, const int32_t *h_slots, int n, const uint8_t *h_state);
+int  ulcx_encode_host_subset(ulcx_encoder *enc, const int32_t *h_slots, int n, int mode, float param0, float param1,
+                             const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
+                             uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx);
+int  ulcx_decode_host_subset(ulcx_decoder *dec, const int32_t *h_slots, int n, const uint8_t *h_in, int slotBytes, int nBlocks,
+                             float *h_pcm, int32_t *h_bits);
+#define ULCX_STATE_MAGIC_ENC 0x45535855u      /* 'U' 'X' 'S' 'E' */
+#define ULCX_STATE_MAGIC_DEC 0x44535855u      /* 'U' 'X' 'S' 'D' */
 
 /* ------------------------------------------------------------------------- */
 /* 3. `.ulc` container and packed streams               */

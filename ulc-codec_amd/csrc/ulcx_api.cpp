@@ -68,6 +68,8 @@ struct ulcx_encoder {
     Block1Graph b1; bool b1Init = false;
     int b1Mode = 0; float b1P0 = 0.0f, b1P1 = 0.0f; int b1Rekeys = 0;
     float *pinIn = nullptr; uint8_t *pinOut = nullptr; Block1Meta *pinMeta = nullptr;
+    // stream slots: the compact shadow state of the subset calls ([B], allocated on the first one) and the device copy of a host form's list
+    float *subHist = nullptr; UlcxWcState *subWcs = nullptr; int32_t *subSlots = nullptr;
 };
 struct ulcx_decoder {
     int device = 0, B = 0, C = 0, BS = 0, maxK = 0;
@@ -93,6 +95,10 @@ struct ulcx_decoder {
     // single-block path uploads in front of every block.  Any OTHER decode call on this object advances the device word only:
     // it marks the copy stale, and the next single-block call without a caller-owned state reads the device word back first.
     bool b1SeedStale = false, inBlock1 = false;
+    // stream slots: the compact shadow state of the subset calls ([B], allocated on the first one; set 1 is where a cut
+    // synthesis leaves its result, as lap2 .. dead2 are for the object's own arrays) and the device copy of a host form's list
+    float *subLap[2] = {}; int *subLastSub[2] = {}; uint32_t *subSeed[2] = {}; int *subDead[2] = {}; int *subPackOff = nullptr;
+    int32_t *subSlots = nullptr;
 };
 
 #ifndef ULCX_SRC_REV
@@ -345,10 +351,73 @@ static UlcxEncAux enc_aux(ulcx_encoder *e, int nBlocks) {
     return UlcxEncAux{ e->sync, wcPipe, e->wcSteps, e->wcFuse, e->nsSlots, e->nXf };
 }
 
-// d_rate != NULL: per-stream settings read on the device (ulcx_encode_dev_rates); mode / p0 / p1 are then unused
+// ---- stream slots (include/ulc_amd.h): what the copies of ulcx_slots.hip work on
+// a list of the device forms: checked as far as the host can see it
+static int slots_list_bad(const char *who, const int32_t *d_slots, int n, int B) {
+    if (!d_slots || n < 1 || n > B) { ulcx_set_error("%s: no slot list, or n = %d not in 1 .. nStreams = %d", who, n, B); return 1; }
+    return misaligned(who, "d_slots", d_slots, ULCX_ALIGN_WORD);
+}
+// a list of the host forms: every entry a slot of the object, none twice
+static int slots_host_bad(const char *who, const int32_t *h_slots, int n, int B) {
+    if (!h_slots || n < 1 || n > B) { ulcx_set_error("%s: no slot list, or n = %d not in 1 .. nStreams = %d", who, n, B); return 1; }
+    std::vector<char> seen((size_t)B, 0);
+    for (int i = 0; i < n; i++) {
+        const int s = h_slots[i];
+        if (s < 0 || s >= B) { ulcx_set_error("%s: entry %d is slot %d, outside 0 .. %d", who, i, s, B - 1); return 1; }
+        if (seen[(size_t)s]) { ulcx_set_error("%s: slot %d is listed twice", who, s); return 1; }
+        seen[(size_t)s] = 1;
+    }
+    return 0;
+}
+static int record_headers_bad(const char *who, const uint8_t *h_state, int n, size_t bytes, const uint4 &want) {
+    for (int i = 0; i < n; i++) {
+        uint32_t h[4];
+        memcpy(h, h_state + (size_t)i * bytes, sizeof(h));
+        if (h[0] != want.x || h[1] != want.y || h[2] != want.z || h[3] != want.w) {
+            ulcx_set_error("%s: record %d is {magic %08x, nChan %u, BlockSize %u, RateHz %u}, this object takes {%08x, %u, %u, %u}", who, i,
+                           h[0], h[1], h[2], h[3], want.x, want.y, want.z, want.w);
+            return 1;
+        }
+    }
+    return 0;
+}
+enum { ULCX_ALIGN_STATE = 16, ULCX_STATE_HEADER = 16, ULCX_WCS_WORDS = sizeof(UlcxWcState) / 4, ULCX_WCS_REC_BYTES = (sizeof(UlcxWcState) + 15) / 16 * 16 };
+static size_t enc_hist_bytes(const ulcx_encoder *e) { return sizeof(float) * 2 * (size_t)e->BS * e->C; }
+extern "C" size_t ulcx_encoder_stream_state_bytes(const ulcx_encoder *e) { return e ? ULCX_STATE_HEADER + enc_hist_bytes(e) + ULCX_WCS_REC_BYTES : 0; }
+static UlcxSlotGeom enc_slot_geom(const ulcx_encoder *e, bool record) {
+    UlcxSlotGeom g = {};
+    g.B = e->B; g.rowVec = (int)(enc_hist_bytes(e) / 16); g.isEnc = 1; g.nSmall = 1; g.smallWords = ULCX_WCS_WORDS;
+    g.padWords = record ? ULCX_WCS_REC_BYTES / 4 : ULCX_WCS_WORDS;
+    g.header = make_uint4(ULCX_STATE_MAGIC_ENC, (unsigned)e->C, (unsigned)e->BS, (unsigned)e->rate);
+    return g;
+}
+static UlcxSlotRows enc_slot_rows(const ulcx_encoder *e, float *hist, UlcxWcState *wcs) {
+    UlcxSlotRows r = {};
+    r.big = (uint8_t *)hist; r.bigStride = enc_hist_bytes(e); r.small[0] = (uint8_t *)wcs; r.smallStride = sizeof(UlcxWcState);
+    return r;
+}
+static UlcxSlotRows enc_record_rows(const ulcx_encoder *e, uint8_t *state) {
+    UlcxSlotRows r = {};
+    const size_t bytes = ulcx_encoder_stream_state_bytes(e);
+    r.hdr = state; r.hdrStride = bytes; r.big = state + ULCX_STATE_HEADER; r.bigStride = bytes;
+    r.small[0] = state + ULCX_STATE_HEADER + enc_hist_bytes(e); r.smallStride = bytes;
+    return r;
+}
+static int enc_shadow(ulcx_encoder *e) {
+    int rc;
+    if (!e->subHist && (rc = dalloc(e->allocs, &e->subHist, (size_t)e->B * 2 * e->BS * e->C, false))) return rc;
+    if (!e->subWcs && (rc = dalloc(e->allocs, &e->subWcs, (size_t)e->B, false))) return rc;
+    return ULCX_OK;
+}
+
+// d_rate != NULL: per-stream settings read on the device (ulcx_encode_dev_rates); mode / p0 / p1 are then unused.
+// d_slots != NULL: a subset call - the n listed slots' state gathered into the compact shadow arrays, the plain call's launch
+// sequence on those with c.B = n (every kernel takes its strides from c.B, c.K and c.maxK; the per-call scratch is sized for
+// nStreams >= n), the result scattered back; all on the caller's stream, which the launch joins its side streams into.
 static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
-                          uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+                          uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream, const int32_t *d_slots = nullptr, int n = 0) {
     if (!e || (!d_pcm && !d_pcm16) || !d_out || !d_bits || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_encode_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (d_slots && slots_list_bad("ulcx_encode_dev_subset", d_slots, n, e->B)) return ULCX_ERR_ARG;
     if (d_rate) { mode = ULCX_MODE_VBR; p0 = 100.0f; p1 = 0.0f; }
     if (mode != ULCX_MODE_VBR && mode != ULCX_MODE_CBR && mode != ULCX_MODE_ABR) { ulcx_set_error("bad mode"); return ULCX_ERR_ARG; }
     if (misaligned("ulcx_encode_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_encode_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
@@ -361,7 +430,14 @@ static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const u
     c.rates = (const float2 *)d_rate;
     c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = d_out; c.bits = d_bits; c.wcOut = d_wc; c.cplxOut = d_cplx;
     const UlcxEncAux aux = enc_aux(e, nBlocks);
-    const int rc = ulcx_enc_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux);
+    if (d_slots) {
+        int rc0 = enc_shadow(e);
+        if (!rc0) rc0 = ulcx_slots_gather(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
+        if (rc0) return rc0;
+        c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
+    }
+    int rc = ulcx_enc_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux);
+    if (d_slots && rc == ULCX_OK) rc = ulcx_slots_scatter(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     e->lastK = nBlocks;
     e->keysFinal = false;
@@ -425,8 +501,10 @@ extern "C" int ulcx_encode_dev_pcm16_ladder(ulcx_encoder *e, const ulcx_rung *ru
 extern "C" int ulcx_encoder_last_rungs(ulcx_encoder *e) { return e ? e->lastRungs : ULCX_ERR_ARG; }
 
 // ---- analysis only (include/ulc_amd.h): window control, MDCT, block complexity, next-call state
-static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
+static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream,
+                           const int32_t *d_slots = nullptr, int n = 0) {      // (d_slots: a subset call, as in encode_dev_any)
     if (!e || (!d_pcm && !d_pcm16) || (!d_wc && !d_cplx) || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_analyse_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (d_slots && slots_list_bad("ulcx_analyse_dev_subset", d_slots, n, e->B)) return ULCX_ERR_ARG;
     if (misaligned("ulcx_analyse_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_analyse_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
         misaligned("ulcx_analyse_dev", "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned("ulcx_analyse_dev", "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
@@ -434,7 +512,14 @@ static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d
     c.K = nBlocks; c.keyFinal = 0; c.mode = ULCX_MODE_VBR; c.p0 = 100.0f; c.p1 = 0.0f; c.vbrTarget = 0.0f; c.rates = nullptr;
     c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = nullptr; c.bits = nullptr; c.wcOut = d_wc; c.cplxOut = d_cplx;
     const UlcxEncAux aux = enc_aux(e, nBlocks);      // (the encode call's chunking)
-    const int rc = ulcx_analyse_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux, e->analyseKxf);
+    if (d_slots) {
+        int rc0 = enc_shadow(e);
+        if (!rc0) rc0 = ulcx_slots_gather(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
+        if (rc0) return rc0;
+        c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
+    }
+    int rc = ulcx_analyse_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux, e->analyseKxf);
+    if (d_slots && rc == ULCX_OK) rc = ulcx_slots_scatter(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     e->lastK = nBlocks;
     e->keysFinal = false;
@@ -804,7 +889,10 @@ extern "C" int ulcx_decoder_last_cut(ulcx_decoder *e, int *workgroups, int *whol
     if (residentWG) *residentWG = e->synSlots;
     return ULCX_OK;
 }
-static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st) {
+// subsetSet != NULL: a subset call - c.B is the number of listed slots (what the cut is planned from) and c.lap .. c.dead are
+// set 0 of the compact shadow state; a cut leaves its result in set 1 of THAT state, the object's own sets are not swapped,
+// and *subsetSet receives the set that holds the result.
+static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subsetSet = nullptr) {
     if (!e->inBlock1) e->b1SeedStale = true;                      // (a batched / packed call on a one-stream decoder: see b1Seed)
     UlcxDecAux a;
     a.synGrid = 0; a.synFull = 0;
@@ -814,25 +902,27 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st) {
         // A range call of more streams than the device holds at once: whole rounds, and the last one cut
         // (ulcx_dec_range_tail_plan) - an even cut of everything ends every workgroup inside a stream, and in a range call every
         // entry into a stream costs the block in front of the range (ULCX_RANGE_CUT=even: the even cut first, as for other calls)
-        if (c.range && e->B > e->synSlots && e->tailCut && !e->rangeEvenFirst) {
+        if (c.range && c.B > e->synSlots && e->tailCut && !e->rangeEvenFirst) {
             int full = 0;
-            const int tail = ulcx_dec_range_tail_plan(e->B, Kc, e->synSlots, &full);
+            const int tail = ulcx_dec_range_tail_plan(c.B, Kc, e->synSlots, &full);
             if (tail > 0 && tail <= e->scratchRows) { a.synGrid = full + tail; a.synFull = full; }
         }
-        if (!a.synGrid) a.synGrid = ulcx_dec_split_plan(e->B, Kc, e->synSlots);
+        if (!a.synGrid) a.synGrid = ulcx_dec_split_plan(c.B, Kc, e->synSlots);
         if (!a.synGrid) {
             int full = 0;
-            const int tail = c.range ? ulcx_dec_range_tail_plan(e->B, Kc, e->synSlots, &full) : ulcx_dec_tail_plan(e->B, Kc, e->synSlots, &full);
+            const int tail = c.range ? ulcx_dec_range_tail_plan(c.B, Kc, e->synSlots, &full) : ulcx_dec_tail_plan(c.B, Kc, e->synSlots, &full);
             if (tail > 0 && tail <= e->scratchRows && e->tailCut) { a.synGrid = full + tail; a.synFull = full; }
         }
         if (a.synGrid) {
-            if (getenv("ULCX_DEBUG_PRINT")) fprintf(stderr, "[ulcx] synthesis: %lld (stream, block) pairs over %d workgroups (%d of them one stream each; %d resident)\n", (long long)e->B * Kc, a.synGrid, a.synFull, e->synSlots);
-            c.lapO = e->lap2; c.lastSubO = e->lastSub2; c.seedO = e->seed2; c.deadO = e->dead2;
+            if (getenv("ULCX_DEBUG_PRINT")) fprintf(stderr, "[ulcx] synthesis: %lld (stream, block) pairs over %d workgroups (%d of them one stream each; %d resident)\n", (long long)c.B * Kc, a.synGrid, a.synFull, e->synSlots);
+            if (subsetSet) { c.lapO = e->subLap[1]; c.lastSubO = e->subLastSub[1]; c.seedO = e->subSeed[1]; c.deadO = e->subDead[1]; }
+            else { c.lapO = e->lap2; c.lastSubO = e->lastSub2; c.seedO = e->seed2; c.deadO = e->dead2; }
         }
     }
     e->lastGrid = a.synGrid; e->lastFull = a.synFull;
     const int rc = ulcx_dec_launch(c, st, e->timing ? e->ev : nullptr, a);
-    if (rc == ULCX_OK && a.synGrid) {
+    if (subsetSet) *subsetSet = a.synGrid ? 1 : 0;
+    else if (rc == ULCX_OK && a.synGrid) {
         std::swap(e->ctx.lap, e->lap2); std::swap(e->ctx.lastSub, e->lastSub2); std::swap(e->ctx.seed, e->seed2); std::swap(e->ctx.dead, e->dead2);
     }
     return rc;
@@ -931,15 +1021,64 @@ static int dec_host_staging(ulcx_decoder *e, size_t nBlk, size_t inBytes) {
     return ULCX_OK;
 }
 
-static int decode_dev_any(ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+// ---- stream slots: the decoder's side (the object's CURRENT set of state arrays: e->ctx.lap .. - a cut synthesis swaps the sets)
+static size_t dec_lap_bytes(const ulcx_decoder *e) { return sizeof(float) * (size_t)e->C * (e->BS / 2); }
+extern "C" size_t ulcx_decoder_stream_state_bytes(const ulcx_decoder *e) { return e ? ULCX_STATE_HEADER + dec_lap_bytes(e) + 16 : 0; }
+static UlcxSlotGeom dec_slot_geom(const ulcx_decoder *e) {
+    UlcxSlotGeom g = {};
+    g.B = e->B; g.rowVec = (int)(dec_lap_bytes(e) / 16); g.isEnc = 0; g.nSmall = 4; g.smallWords = 1; g.padWords = 1;
+    g.header = make_uint4(ULCX_STATE_MAGIC_DEC, (unsigned)e->C, (unsigned)e->BS, 0u);
+    return g;
+}
+static UlcxSlotRows dec_slot_rows(const ulcx_decoder *e, float *lap, int *lastSub, uint32_t *seed, int *dead, int *packOff) {
+    UlcxSlotRows r = {};
+    r.big = (uint8_t *)lap; r.bigStride = dec_lap_bytes(e);
+    r.small[0] = (uint8_t *)lastSub; r.small[1] = (uint8_t *)seed; r.small[2] = (uint8_t *)dead; r.small[3] = (uint8_t *)packOff; r.smallStride = 4;
+    return r;
+}
+static UlcxSlotRows dec_obj_rows(const ulcx_decoder *e) { return dec_slot_rows(e, e->ctx.lap, e->ctx.lastSub, e->ctx.seed, e->ctx.dead, e->ctx.packOff); }
+static UlcxSlotRows dec_shadow_rows(const ulcx_decoder *e, int set) { return dec_slot_rows(e, e->subLap[set], e->subLastSub[set], e->subSeed[set], e->subDead[set], e->subPackOff); }
+static UlcxSlotRows dec_record_rows(const ulcx_decoder *e, uint8_t *state) {
+    UlcxSlotRows r = {};
+    const size_t bytes = ulcx_decoder_stream_state_bytes(e);
+    r.hdr = state; r.hdrStride = bytes; r.big = state + ULCX_STATE_HEADER; r.bigStride = bytes;
+    for (int a = 0; a < 4; a++) r.small[a] = state + ULCX_STATE_HEADER + dec_lap_bytes(e) + 4 * a;
+    r.smallStride = bytes;
+    return r;
+}
+static int dec_shadow(ulcx_decoder *e) {
+    int rc;
+    for (int set = 0; set < (e->splitOK ? 2 : 1); set++) {
+        if (!e->subLap[set] && (rc = dalloc(e->allocs, &e->subLap[set], (size_t)e->B * e->C * (e->BS / 2), false))) return rc;
+        if (!e->subLastSub[set] && (rc = dalloc(e->allocs, &e->subLastSub[set], (size_t)e->B, false))) return rc;
+        if (!e->subSeed[set] && (rc = dalloc(e->allocs, &e->subSeed[set], (size_t)e->B, false))) return rc;
+        if (!e->subDead[set] && (rc = dalloc(e->allocs, &e->subDead[set], (size_t)e->B, false))) return rc;
+    }
+    if (!e->subPackOff && (rc = dalloc(e->allocs, &e->subPackOff, (size_t)e->B, false))) return rc;
+    return ULCX_OK;
+}
+
+// d_slots != NULL: a subset call, as the encoder's (encode_dev_any): gather, the plain launch on the compact state, scatter
+static int decode_dev_any(ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream,
+                          const int32_t *d_slots = nullptr, int n = 0) {
     if (!e || !d_in || (!d_pcm && !d_pcm16) || !d_bits || slotBytes < 1 || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_decode_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (d_slots && slots_list_bad("ulcx_decode_dev_subset", d_slots, n, e->B)) return ULCX_ERR_ARG;
     if (misaligned("ulcx_decode_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_decode_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
         misaligned("ulcx_decode_dev", "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.K = nBlocks; c.slot = slotBytes; c.in = d_in; c.pcm = d_pcm; c.pcm16 = d_pcm16; c.bits = d_bits;
     c.inBytes = (long long)e->B * nBlocks * slotBytes;
-    int rc = dec_launch(e, c, (hipStream_t)hipStream);
+    if (d_slots) {
+        int rc0 = dec_shadow(e);
+        if (!rc0) rc0 = ulcx_slots_gather(dec_obj_rows(e), dec_shadow_rows(e, 0), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
+        if (rc0) return rc0;
+        c.B = n; c.inBytes = (long long)n * nBlocks * slotBytes;
+        c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
+    }
+    int set = 0;
+    int rc = dec_launch(e, c, (hipStream_t)hipStream, d_slots ? &set : nullptr);
+    if (d_slots && rc == ULCX_OK) rc = ulcx_slots_scatter(dec_obj_rows(e), dec_shadow_rows(e, set), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     return rc;
 }
@@ -1231,6 +1370,188 @@ extern "C" int ulcx_decode_resident_range_host(ulcx_decoder *e, const int32_t *h
     CKR(hipMemcpy(e->d_first, h_first, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
     int rc = ulcx_decode_range_dev(e, e->d_pay, e->payStride, e->d_payBytes, e->d_index, e->idxStride, e->d_idxBlocks, e->d_first, nBlocks, e->d_pcm, e->d_bits, nullptr);
     if (rc != ULCX_OK) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Stream slots (include/ulc_amd.h): per-stream reset, save / load, subset calls.  The copies are ulcx_slots.hip's.
+// ---------------------------------------------------------------------------
+extern "C" int ulcx_encoder_reset_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, void *hipStream) {
+    if (!e) { ulcx_set_error("ulcx_encoder_reset_streams_dev: no encoder"); return ULCX_ERR_ARG; }
+    if (slots_list_bad("ulcx_encoder_reset_streams_dev", d_slots, n, e->B)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    return ulcx_slots_reset(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
+}
+extern "C" int ulcx_encoder_save_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, uint8_t *d_state, void *hipStream) {
+    if (!e || !d_state) { ulcx_set_error("ulcx_encoder_save_streams_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_list_bad("ulcx_encoder_save_streams_dev", d_slots, n, e->B) || misaligned("ulcx_encoder_save_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    return ulcx_slots_gather(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_record_rows(e, d_state), d_slots, n, enc_slot_geom(e, true), (hipStream_t)hipStream);
+}
+extern "C" int ulcx_encoder_load_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, const uint8_t *d_state, void *hipStream) {
+    if (!e || !d_state) { ulcx_set_error("ulcx_encoder_load_streams_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_list_bad("ulcx_encoder_load_streams_dev", d_slots, n, e->B) || misaligned("ulcx_encoder_load_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    return ulcx_slots_scatter(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_record_rows(e, (uint8_t *)d_state), d_slots, n, enc_slot_geom(e, true), (hipStream_t)hipStream);
+}
+// (reset and load change the generator word behind the single-block path's host copy, as a batched decode call does: b1Seed)
+extern "C" int ulcx_decoder_reset_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, void *hipStream) {
+    if (!e) { ulcx_set_error("ulcx_decoder_reset_streams_dev: no decoder"); return ULCX_ERR_ARG; }
+    if (slots_list_bad("ulcx_decoder_reset_streams_dev", d_slots, n, e->B)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    if (!e->inBlock1) e->b1SeedStale = true;
+    return ulcx_slots_reset(dec_obj_rows(e), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
+}
+extern "C" int ulcx_decoder_save_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, uint8_t *d_state, void *hipStream) {
+    if (!e || !d_state) { ulcx_set_error("ulcx_decoder_save_streams_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_list_bad("ulcx_decoder_save_streams_dev", d_slots, n, e->B) || misaligned("ulcx_decoder_save_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    return ulcx_slots_gather(dec_obj_rows(e), dec_record_rows(e, d_state), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
+}
+extern "C" int ulcx_decoder_load_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_state, void *hipStream) {
+    if (!e || !d_state) { ulcx_set_error("ulcx_decoder_load_streams_dev: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_list_bad("ulcx_decoder_load_streams_dev", d_slots, n, e->B) || misaligned("ulcx_decoder_load_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    if (!e->inBlock1) e->b1SeedStale = true;
+    return ulcx_slots_scatter(dec_obj_rows(e), dec_record_rows(e, (uint8_t *)d_state), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
+}
+
+extern "C" int ulcx_encode_dev_subset(ulcx_encoder *e, const int32_t *d_slots, int n, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, int nBlocks,
+                                      uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!e || !d_slots || !d_pcm) { ulcx_set_error("ulcx_encode_dev_subset: bad argument"); return ULCX_ERR_ARG; }
+    return encode_dev_any(e, mode, p0, p1, d_rate, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream, d_slots, n);
+}
+extern "C" int ulcx_encode_dev_pcm16_subset(ulcx_encoder *e, const int32_t *d_slots, int n, int mode, float p0, float p1, const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
+                                            uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!e || !d_slots || !d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16_subset: bad argument"); return ULCX_ERR_ARG; }
+    return encode_dev_any(e, mode, p0, p1, d_rate, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream, d_slots, n);
+}
+extern "C" int ulcx_analyse_dev_subset(ulcx_encoder *e, const int32_t *d_slots, int n, const float *d_pcm, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    if (!e || !d_slots || !d_pcm) { ulcx_set_error("ulcx_analyse_dev_subset: bad argument"); return ULCX_ERR_ARG; }
+    return analyse_dev_any(e, d_pcm, nullptr, nBlocks, d_wc, d_cplx, hipStream, d_slots, n);
+}
+extern "C" int ulcx_decode_dev_subset(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
+    if (!e || !d_slots || !d_pcm) { ulcx_set_error("ulcx_decode_dev_subset: bad argument"); return ULCX_ERR_ARG; }
+    return decode_dev_any(e, d_in, slotBytes, nBlocks, d_pcm, nullptr, d_bits, hipStream, d_slots, n);
+}
+extern "C" int ulcx_decode_dev_pcm16_subset(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_in, int slotBytes, int nBlocks, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    if (!e || !d_slots || !d_pcm16) { ulcx_set_error("ulcx_decode_dev_pcm16_subset: bad argument"); return ULCX_ERR_ARG; }
+    return decode_dev_any(e, d_in, slotBytes, nBlocks, nullptr, d_pcm16, d_bits, hipStream, d_slots, n);
+}
+
+// host forms: the checked list to the device, the _dev form on the null stream, one synchronisation
+template <class OBJ> static int slots_list_up(OBJ *e, const int32_t *h_slots, int n) {
+    if (!e->subSlots) { int rc = dalloc(e->allocs, &e->subSlots, (size_t)e->B, false); if (rc) return rc; }
+    CKR(hipMemcpy(e->subSlots, h_slots, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    return ULCX_OK;
+}
+extern "C" int ulcx_encoder_reset_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n) {
+    if (!e) { ulcx_set_error("ulcx_encoder_reset_streams_host: no encoder"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_encoder_reset_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    int rc = slots_list_up(e, h_slots, n);
+    if (!rc) rc = ulcx_encoder_reset_streams_dev(e, e->subSlots, n, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    return ULCX_OK;
+}
+extern "C" int ulcx_decoder_reset_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n) {
+    if (!e) { ulcx_set_error("ulcx_decoder_reset_streams_host: no decoder"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_decoder_reset_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    int rc = slots_list_up(e, h_slots, n);
+    if (!rc) rc = ulcx_decoder_reset_streams_dev(e, e->subSlots, n, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    return ULCX_OK;
+}
+// save / load of either kind: records through a device buffer of the call's own
+template <class OBJ, class DEVFN> static int slots_save_host(OBJ *e, const int32_t *h_slots, int n, uint8_t *h_state, size_t bytes, DEVFN devForm) {
+    CKR(hipSetDevice(e->device));
+    DevTmp t; uint8_t *ds = nullptr;
+    CKR(t.get(&ds, (size_t)n * bytes));
+    int rc = slots_list_up(e, h_slots, n);
+    if (!rc) rc = devForm(e, e->subSlots, n, ds, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_state, ds, (size_t)n * bytes, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+template <class OBJ, class DEVFN> static int slots_load_host(OBJ *e, const int32_t *h_slots, int n, const uint8_t *h_state, size_t bytes, DEVFN devForm) {
+    CKR(hipSetDevice(e->device));
+    DevTmp t; uint8_t *ds = nullptr;
+    CKR(t.get(&ds, (size_t)n * bytes));
+    CKR(hipMemcpy(ds, h_state, (size_t)n * bytes, hipMemcpyHostToDevice));
+    int rc = slots_list_up(e, h_slots, n);
+    if (!rc) rc = devForm(e, e->subSlots, n, ds, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    return ULCX_OK;
+}
+extern "C" int ulcx_encoder_save_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n, uint8_t *h_state) {
+    if (!e || !h_state) { ulcx_set_error("ulcx_encoder_save_streams_host: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_encoder_save_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    return slots_save_host(e, h_slots, n, h_state, ulcx_encoder_stream_state_bytes(e), ulcx_encoder_save_streams_dev);
+}
+extern "C" int ulcx_encoder_load_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n, const uint8_t *h_state) {
+    if (!e || !h_state) { ulcx_set_error("ulcx_encoder_load_streams_host: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_encoder_load_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (record_headers_bad("ulcx_encoder_load_streams_host", h_state, n, ulcx_encoder_stream_state_bytes(e), enc_slot_geom(e, true).header)) return ULCX_ERR_ARG;
+    return slots_load_host(e, h_slots, n, h_state, ulcx_encoder_stream_state_bytes(e), ulcx_encoder_load_streams_dev);
+}
+extern "C" int ulcx_decoder_save_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n, uint8_t *h_state) {
+    if (!e || !h_state) { ulcx_set_error("ulcx_decoder_save_streams_host: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_decoder_save_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    return slots_save_host(e, h_slots, n, h_state, ulcx_decoder_stream_state_bytes(e), ulcx_decoder_save_streams_dev);
+}
+extern "C" int ulcx_decoder_load_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n, const uint8_t *h_state) {
+    if (!e || !h_state) { ulcx_set_error("ulcx_decoder_load_streams_host: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_decoder_load_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (record_headers_bad("ulcx_decoder_load_streams_host", h_state, n, ulcx_decoder_stream_state_bytes(e), dec_slot_geom(e).header)) return ULCX_ERR_ARG;
+    return slots_load_host(e, h_slots, n, h_state, ulcx_decoder_stream_state_bytes(e), ulcx_decoder_load_streams_dev);
+}
+extern "C" int ulcx_encode_host_subset(ulcx_encoder *e, const int32_t *h_slots, int n, int mode, float p0, float p1, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
+                                       uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
+    if (!e || !h_pcm || !h_out || !h_bits) { ulcx_set_error("ulcx_encode_host_subset: bad argument"); return ULCX_ERR_ARG; }
+    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_encode_host_subset", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (!h_rate && mode != ULCX_MODE_VBR && mode != ULCX_MODE_CBR && mode != ULCX_MODE_ABR) { ulcx_set_error("bad mode"); return ULCX_ERR_ARG; }
+    for (int i = 0; h_rate && i < n; i++) {                // (as ulcx_encode_host_rates)
+        const float r = h_rate[i].RateKbps, a = h_rate[i].AvgComplexity;
+        if (!isfinite(r) || !isfinite(a) || r == 0.0f || a < 0.0f) {
+            ulcx_set_error("ulcx_encode_host_subset: invalid entry for row %d (RateKbps %g, AvgComplexity %g)", i, (double)r, (double)a);
+            return ULCX_ERR_ARG;
+        }
+    }
+    CKR(hipSetDevice(e->device));
+    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
+    if (h_rate && !e->d_rate) { int rc = dalloc(e->allocs, &e->d_rate, (size_t)e->B, false); if (rc) return rc; }
+    { int rc = slots_list_up(e, h_slots, n); if (rc) return rc; }
+    if (h_rate) CKR(hipMemcpy(e->d_rate, h_rate, sizeof(ulcx_rate) * (size_t)n, hipMemcpyHostToDevice));
+    const size_t NB = (size_t)n * nBlocks, cb = (size_t)e->C * e->BS;
+    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
+    int rc = encode_dev_any(e, mode, p0, p1, h_rate ? e->d_rate : nullptr, e->d_pcm, nullptr, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr, e->subSlots, n);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_out, e->d_out, NB * e->ctx.slot, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+extern "C" int ulcx_decode_host_subset(ulcx_decoder *e, const int32_t *h_slots, int n, const uint8_t *h_in, int slotBytes, int nBlocks, float *h_pcm, int32_t *h_bits) {
+    if (!e || !h_in || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK || slotBytes < 1) { ulcx_set_error("ulcx_decode_host_subset: bad argument"); return ULCX_ERR_ARG; }
+    if (slots_host_bad("ulcx_decode_host_subset", h_slots, n, e->B)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    const size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS, NB = (size_t)n * nBlocks;
+    { int rc = dec_host_staging(e, NBmax, NBmax * (size_t)slotBytes + 16); if (rc) return rc; }
+    { int rc = slots_list_up(e, h_slots, n); if (rc) return rc; }
+    CKR(hipMemcpy(e->d_in, h_in, NB * slotBytes, hipMemcpyHostToDevice));
+    int rc = decode_dev_any(e, e->d_in, slotBytes, nBlocks, e->d_pcm, nullptr, e->d_bits, nullptr, e->subSlots, n);
+    if (rc) return rc;
     CKR(hipDeviceSynchronize());
     CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
     CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));

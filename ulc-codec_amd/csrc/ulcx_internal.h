@@ -233,5 +233,23 @@ __host__ __device__ static inline int ulcx_xf_pad_shift(int BS, int C) { (void)B
 #define ULCX_SEL_CAND 128
 #endif
 __host__ __device__ static inline int ulcx_sel_lds_words(int BS) { int a = BS / 2 + 4 * ULCX_NBARK, b = ULCX_SEL_CAP * 64; return a > b ? a : b; }
+// Stream slots (ulcx_slots.hip): one side of a copy of single streams' state - an object's own arrays, the compact shadow
+// state of a subset call, or the caller's records.  Row r of the large array is at big + r * bigStride, word w of small array
+// a at small[a] + r * smallStride + 4 * w (encoder: one array, the UlcxWcState; decoder: lastSub, seed, dead, packOff).
+struct UlcxSlotRows {
+    uint8_t *hdr; size_t hdrStride;      // records only: the 16-byte header (NULL: none)
+    uint8_t *big; size_t bigStride;      // hist / lap: 16-byte aligned rows
+    uint8_t *small[4]; size_t smallStride;
+};
+struct UlcxSlotGeom {
+    int B;                               // slots of the object: list entries outside [0, B) are not the object's
+    int rowVec;                          // 16-byte vectors of a large row
+    int isEnc, nSmall, smallWords;       // small arrays and the words of each
+    int padWords;                        // gather: words written per small array (>= smallWords; zeros behind the state)
+    uint4 header;                        // gather into records: written; scatter from records: a row whose header differs is skipped
+};
+int ulcx_slots_gather(const UlcxSlotRows &obj, const UlcxSlotRows &rows, const int32_t *d_slots, int n, const UlcxSlotGeom &g, hipStream_t st);
+int ulcx_slots_scatter(const UlcxSlotRows &obj, const UlcxSlotRows &rows, const int32_t *d_slots, int n, const UlcxSlotGeom &g, hipStream_t st);
+int ulcx_slots_reset(const UlcxSlotRows &obj, const int32_t *d_slots, int n, const UlcxSlotGeom &g, hipStream_t st);
 void ulcx_enc_finalize_keys(const UlcxEncCtx &c, hipStream_t st);
 void ulcx_enc_materialise_noise(const UlcxEncCtx &c, hipStream_t st);     // parity tap: the {w, w*log} pairs of the last call into c.npair

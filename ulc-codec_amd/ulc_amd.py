@@ -27,6 +27,13 @@ EXPORTS = [
     "ulcx_index_packed_dev", "ulcx_index_packed_host", "ulcx_decode_range_dev", "ulcx_decode_range_dev_pcm16", "ulcx_decode_range_host",
     "ulcx_decoder_index_resident", "ulcx_decode_resident_range_host", "ulcx_dec_range_tail_plan",
     "ulcx_encode_dev_ladder", "ulcx_encode_dev_pcm16_ladder", "ulcx_encode_host_ladder", "ulcx_encoder_last_rungs",
+    "ulcx_encoder_stream_state_bytes", "ulcx_decoder_stream_state_bytes",
+    "ulcx_encoder_reset_streams_dev", "ulcx_encoder_save_streams_dev", "ulcx_encoder_load_streams_dev",
+    "ulcx_decoder_reset_streams_dev", "ulcx_decoder_save_streams_dev", "ulcx_decoder_load_streams_dev",
+    "ulcx_encoder_reset_streams_host", "ulcx_encoder_save_streams_host", "ulcx_encoder_load_streams_host",
+    "ulcx_decoder_reset_streams_host", "ulcx_decoder_save_streams_host", "ulcx_decoder_load_streams_host",
+    "ulcx_encode_dev_subset", "ulcx_encode_dev_pcm16_subset", "ulcx_analyse_dev_subset", "ulcx_encode_host_subset",
+    "ulcx_decode_dev_subset", "ulcx_decode_dev_pcm16_subset", "ulcx_decode_host_subset",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -89,6 +96,25 @@ def lib():
             l.ulcx_encode_dev_pcm16_ladder.argtypes = l.ulcx_encode_dev_ladder.argtypes
             l.ulcx_encode_host_ladder.argtypes = [C.c_void_p, C.POINTER(Rung), C.c_int, _f32p, C.c_int, _u8p, _i32p, _i32p, _f32p]
             l.ulcx_encoder_last_rungs.argtypes = [C.c_void_p]
+        if hasattr(l, "ulcx_encode_dev_subset"):           # stream slots
+            for kind in ("encoder", "decoder"):
+                getattr(l, f"ulcx_{kind}_stream_state_bytes").restype = C.c_size_t
+                getattr(l, f"ulcx_{kind}_stream_state_bytes").argtypes = [C.c_void_p]
+                getattr(l, f"ulcx_{kind}_reset_streams_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+                getattr(l, f"ulcx_{kind}_save_streams_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+                getattr(l, f"ulcx_{kind}_load_streams_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+                getattr(l, f"ulcx_{kind}_reset_streams_host").argtypes = [C.c_void_p, _i32p, C.c_int]
+                getattr(l, f"ulcx_{kind}_save_streams_host").argtypes = [C.c_void_p, _i32p, C.c_int, _u8p]
+                getattr(l, f"ulcx_{kind}_load_streams_host").argtypes = [C.c_void_p, _i32p, C.c_int, _u8p]
+            l.ulcx_encode_dev_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_encode_dev_pcm16_subset.argtypes = l.ulcx_encode_dev_subset.argtypes
+            l.ulcx_analyse_dev_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_encode_host_subset.argtypes = [C.c_void_p, _i32p, C.c_int, C.c_int, C.c_float, C.c_float, _f32p, _f32p, C.c_int,
+                                                  _u8p, _i32p, _i32p, _f32p]
+            l.ulcx_decode_dev_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_decode_dev_pcm16_subset.argtypes = l.ulcx_decode_dev_subset.argtypes
+            l.ulcx_decode_host_subset.argtypes = [C.c_void_p, _i32p, C.c_int, _u8p, C.c_int, C.c_int, _f32p, _i32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -139,8 +165,59 @@ def _p(a, t):
     return a.ctypes.data_as(t) if a is not None else None
 
 
-class BatchEncoder:
+class _StreamSlots:
+    """Stream slots (include/ulc_amd.h): per-stream reset, save / load of single streams' state.  `slots` is a list of
+    slots of the object (host forms: no duplicate, every entry in 0 .. B-1, checked before any device work); records are
+    uint8 [n][state_bytes].  The *_dev forms take raw device pointers (ints / .data_ptr()) and are asynchronous on `stream`."""
+    _kind = None
+
+    def _fn(self, what):
+        return getattr(lib(), f"ulcx_{self._kind}_{what}"), f"ulcx_{self._kind}_{what}"
+
+    @staticmethod
+    def _slots(slots):
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        return s, _p(s, _i32p)
+
+    @property
+    def state_bytes(self):
+        return int(self._fn("stream_state_bytes")[0](self.h))
+
+    def reset_streams(self, slots):
+        s, sp = self._slots(slots)
+        fn, name = self._fn("reset_streams_host")
+        _check(fn(self.h, sp, s.size), name)
+
+    def save_streams(self, slots):
+        s, sp = self._slots(slots)
+        state = np.zeros((s.size, self.state_bytes), np.uint8)
+        fn, name = self._fn("save_streams_host")
+        _check(fn(self.h, sp, s.size, _p(state, _u8p)), name)
+        return state
+
+    def load_streams(self, slots, state):
+        s, sp = self._slots(slots)
+        state = np.ascontiguousarray(state, dtype=np.uint8)
+        assert state.size == s.size * self.state_bytes
+        fn, name = self._fn("load_streams_host")
+        _check(fn(self.h, sp, s.size, _p(state, _u8p)), name)
+
+    def reset_streams_dev(self, d_slots, n, stream=0):
+        fn, name = self._fn("reset_streams_dev")
+        _check(fn(self.h, d_slots, n, stream or None), name)
+
+    def save_streams_dev(self, d_slots, n, d_state, stream=0):
+        fn, name = self._fn("save_streams_dev")
+        _check(fn(self.h, d_slots, n, d_state, stream or None), name)
+
+    def load_streams_dev(self, d_slots, n, d_state, stream=0):
+        fn, name = self._fn("load_streams_dev")
+        _check(fn(self.h, d_slots, n, d_state, stream or None), name)
+
+
+class BatchEncoder(_StreamSlots):
     """B independent streams; encode(pcm[B][K*BS][C]) -> (bytes[B][K][slot], bits[B][K], wc[B][K], cplx[B][K])."""
+    _kind = "encoder"
 
     def __init__(self, n_streams, n_chan, block_size, rate_hz, max_blocks, device=0):
         self.B, self.C, self.BS, self.rate, self.maxK = n_streams, n_chan, block_size, rate_hz, max_blocks
@@ -287,6 +364,41 @@ class BatchEncoder:
                "ulcx_analyse_dev_pcm16" if pcm16 else "ulcx_analyse_dev")
         self.lastK = n_blocks
 
+    def encode_subset(self, slots, pcm, mode=MODE_VBR, p0=50.0, p1=0.0, rates=None):
+        """As encode() for the listed slots only: pcm [n][K*BS][C], row i for slot slots[i]; only those slots' state
+        advances.  rates: float32 [n][2] per row as encode_rates takes it (mode / p0 / p1 are then unused)."""
+        s, sp = self._slots(slots)
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        n = s.size
+        assert pcm.shape[0] == n and pcm.shape[-1] == self.C
+        K = pcm.shape[1] // self.BS
+        assert pcm.shape[1] == K * self.BS
+        if rates is not None:
+            rates = np.ascontiguousarray(rates, dtype=np.float32)
+            assert rates.shape == (n, 2)
+        out = np.zeros((n, K, self.slot), np.uint8)
+        bits = np.zeros((n, K), np.int32)
+        wc = np.zeros((n, K), np.int32)
+        cplx = np.zeros((n, K), np.float32)
+        _check(lib().ulcx_encode_host_subset(self.h, sp, n, mode, p0, p1, _p(rates, _f32p), _p(pcm, _f32p), K, _p(out, _u8p),
+                                             _p(bits, _i32p), _p(wc, _i32p), _p(cplx, _f32p)), "ulcx_encode_host_subset")
+        self.lastK = K
+        return out, bits, wc, cplx
+
+    def encode_subset_dev(self, d_slots, n, d_pcm, n_blocks, d_out, d_bits, d_wc=0, d_cplx=0, mode=MODE_VBR, p0=50.0, p1=0.0, d_rates=0,
+                          stream=0, pcm16=False):
+        """Device-pointer subset call, asynchronous on `stream`: d_slots int32 [n] on the device, every buffer [n][n_blocks]...;
+        d_rates: device table [n] (0: the scalar setting); pcm16=True takes int16 samples."""
+        fn = lib().ulcx_encode_dev_pcm16_subset if pcm16 else lib().ulcx_encode_dev_subset
+        _check(fn(self.h, d_slots, n, mode, p0, p1, d_rates or None, d_pcm, n_blocks, d_out, d_bits, d_wc or None, d_cplx or None,
+                  stream or None), "ulcx_encode_dev_pcm16_subset" if pcm16 else "ulcx_encode_dev_subset")
+        self.lastK = n_blocks
+
+    def analyse_subset_dev(self, d_slots, n, d_pcm, n_blocks, d_wc=0, d_cplx=0, stream=0):
+        _check(lib().ulcx_analyse_dev_subset(self.h, d_slots, n, d_pcm, n_blocks, d_wc or None, d_cplx or None, stream or None),
+               "ulcx_analyse_dev_subset")
+        self.lastK = n_blocks
+
     def debug_fetch(self, K=None, parts=("coef", "noise", "keys", "keep", "nout")):
         """The taps of the last call; `parts` names the ones to fetch (the others are not copied and come back as None)."""
         K = K or self.lastK
@@ -319,7 +431,9 @@ class BatchEncoder:
         return {lib().ulcx_encoder_stage_name(i).decode(): float(ms[i]) for i in range(n)}
 
 
-class BatchDecoder:
+class BatchDecoder(_StreamSlots):
+    _kind = "decoder"
+
     def __init__(self, n_streams, n_chan, block_size, max_blocks, device=0):
         self.B, self.C, self.BS, self.maxK = n_streams, n_chan, block_size, max_blocks
         self.h = C.c_void_p()
@@ -446,6 +560,23 @@ class BatchDecoder:
     def decode_dev_pcm16(self, d_in, slot, n_blocks, d_pcm16, d_bits, stream=0):
         """PCM16 output: d_pcm16 is a device pointer to int16 [B][K][BS][C]; converted on store as tools/WavIO_Helper.c:56-63."""
         _check(lib().ulcx_decode_dev_pcm16(self.h, d_in, slot, n_blocks, d_pcm16, d_bits, stream or None), "ulcx_decode_dev_pcm16")
+
+    def decode_subset(self, slots, blocks):
+        """As decode() for the listed slots only: blocks uint8 [n][K][slot], row i for slot slots[i]."""
+        s, sp = self._slots(slots)
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+        n, K, slot = blocks.shape
+        assert n == s.size
+        pcm = np.zeros((n, K * self.BS, self.C), np.float32)
+        bits = np.zeros((n, K), np.int32)
+        _check(lib().ulcx_decode_host_subset(self.h, sp, n, _p(blocks, _u8p), slot, K, _p(pcm, _f32p), _p(bits, _i32p)),
+               "ulcx_decode_host_subset")
+        return pcm, bits
+
+    def decode_subset_dev(self, d_slots, n, d_in, slot, n_blocks, d_pcm, d_bits, stream=0, pcm16=False):
+        fn = lib().ulcx_decode_dev_pcm16_subset if pcm16 else lib().ulcx_decode_dev_subset
+        _check(fn(self.h, d_slots, n, d_in, slot, n_blocks, d_pcm, d_bits, stream or None),
+               "ulcx_decode_dev_pcm16_subset" if pcm16 else "ulcx_decode_dev_subset")
 
     def set_timing(self, on):
         _check(lib().ulcx_decoder_set_timing(self.h, int(bool(on))), "ulcx_decoder_set_timing")
