@@ -3,16 +3,29 @@
 // ulcx_enc.hip / ulcx_dec.hip.  There is no CPU fallback: if HIP cannot give us a
 // device, every entry point returns ULCX_ERR_NO_DEVICE.
 #include <math.h>
+#include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 #include "ulcx_internal.h"
 #include "ulcx_rng_tables.h"
 
 
 #define CKR(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ulcx_set_error("%s: %s", #x, hipGetErrorString(e_)); return ULCX_ERR_HIP; } } while (0)
+// A refused call: ULCX_ERR_ARG, and ulcx_last_error() reads "<the entry that was called>: <why>".  Every refusal in this file
+// goes through here or through one of the *_bad checkers below, which take the same `who`.
+static int refuse(const char *who, const char *fmt, ...) {
+    char why[384];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(why, sizeof(why), fmt, ap);
+    va_end(ap);
+    ulcx_set_error("%s: %s", who, why);
+    return ULCX_ERR_ARG;
+}
 
 // The single-block calls (ulcx_encode_block1 / ulcx_decode_block1): own stream, and the call's enqueue sequence captured once
 // into a graph that every later call replays.  noGraph: direct launches from here on.
@@ -146,11 +159,24 @@ static int dalloc(std::vector<void *> &v, T **p, size_t count, bool zero) {
     return ULCX_OK;
 }
 #define DA(ptr, count, zero) do { int rc_ = dalloc(e->allocs, &(ptr), (size_t)(count), zero); if (rc_) { cleanup(e); return rc_; } } while (0)
+// Ownership: every device pointer an object owns is in its `allocs`, which cleanup() frees in one loop.  A buffer that
+// grows or is replaced during the object's life goes through dregrow: the old one is freed and leaves the list first, and a
+// failed allocation leaves *p == nullptr.  Buffers that live for one call are a DevTmp's.
+template <typename T>
+static void dfree(std::vector<void *> &v, T **p) {
+    if (!*p) return;
+    v.erase(std::remove(v.begin(), v.end(), (void *)*p), v.end());
+    hipFree((void *)*p);
+    *p = nullptr;
+}
+template <typename T>
+static int dregrow(std::vector<void *> &v, T **p, size_t count, bool zero) { dfree(v, p); return dalloc(v, p, count, zero); }
+namespace { struct DevTmp { std::vector<void *> v; ~DevTmp() { for (void *p : v) hipFree(p); } template <typename T> hipError_t get(T **p, size_t bytes) { void *q = nullptr; hipError_t r = hipMalloc(&q, bytes ? bytes : 16); if (r == hipSuccess) v.push_back(q); *p = (T *)q; return r; } }; }
 
-static int select_device(int device) {
+static int select_device(const char *who, int device) {
     int n = ulcx_device_count();
     if (n <= 0) { if (!ulcx_last_error()[0]) ulcx_set_error("no HIP device visible"); return ULCX_ERR_NO_DEVICE; }
-    if (device < 0 || device >= n) { ulcx_set_error("device %d out of range (have %d)", device, n); return ULCX_ERR_ARG; }
+    if (device < 0 || device >= n) return refuse(who, "device %d out of range (have %d)", device, n);
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) { ulcx_set_error("hipSetDevice: %s", hipGetErrorString(e)); return ULCX_ERR_NO_DEVICE; }
     return ULCX_OK;
@@ -188,8 +214,6 @@ static void cleanup(ulcx_encoder *e) {
     if (e->pinIn) hipHostFree(e->pinIn);
     if (e->pinOut) hipHostFree(e->pinOut);
     if (e->pinMeta) hipHostFree(e->pinMeta);
-    if (e->ladOut) hipFree(e->ladOut);
-    if (e->ladBits) hipFree(e->ladBits);
     enc_sync_destroy(e->sync);
     delete e;
 }
@@ -208,14 +232,13 @@ static int enc_reset_state(ulcx_encoder *e) {
 }
 
 extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams, int nChan, int BlockSize, int RateHz, int maxBlocksPerCall) {
-    if (!out) return ULCX_ERR_ARG;
+    const char *who = "ulcx_encoder_create";
+    if (!out) return refuse(who, "no place for the object");
     *out = nullptr;
-    if (!validate(nChan, BlockSize) || nStreams < 1 || maxBlocksPerCall < 1 || RateHz < 1) {
-        ulcx_set_error("invalid encoder geometry (nStreams=%d nChan=%d BlockSize=%d RateHz=%d maxBlocks=%d)", nStreams, nChan, BlockSize, RateHz, maxBlocksPerCall);
-        return ULCX_ERR_ARG;
-    }
+    if (!validate(nChan, BlockSize) || nStreams < 1 || maxBlocksPerCall < 1 || RateHz < 1)
+        return refuse(who, "invalid encoder geometry (nStreams=%d nChan=%d BlockSize=%d RateHz=%d maxBlocks=%d)", nStreams, nChan, BlockSize, RateHz, maxBlocksPerCall);
     if (BlockSize > ULCX_MAX_BS_DEVICE) { ulcx_set_error("BlockSize %d > %d not built for the device yet", BlockSize, ULCX_MAX_BS_DEVICE); return ULCX_ERR_UNSUPPORTED; }
-    int rc = select_device(device);
+    int rc = select_device(who, device);
     if (rc) return rc;
     ulcx_encoder *e = new ulcx_encoder();
     e->device = device; e->B = nStreams; e->C = nChan; e->BS = BlockSize; e->rate = RateHz; e->maxK = maxBlocksPerCall;
@@ -341,7 +364,7 @@ extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams,
 }
 
 extern "C" void ulcx_encoder_destroy(ulcx_encoder *e) { if (e) { hipSetDevice(e->device); cleanup(e); } }
-extern "C" int ulcx_encoder_reset(ulcx_encoder *e) { if (!e) return ULCX_ERR_ARG; CKR(hipSetDevice(e->device)); return enc_reset_state(e); }
+extern "C" int ulcx_encoder_reset(ulcx_encoder *e) { if (!e) return refuse("ulcx_encoder_reset", "no encoder"); CKR(hipSetDevice(e->device)); return enc_reset_state(e); }
 extern "C" int ulcx_encoder_slot_bytes(const ulcx_encoder *e) { return e ? e->ctx.slot : 0; }
 
 // What a call of nBlocks launches with.  Short calls pipeline window control and transform in fewer chunks or not at all
@@ -381,10 +404,14 @@ static int record_headers_bad(const char *who, const uint8_t *h_state, int n, si
     }
     return 0;
 }
+// What the slot entries need of an object, one overload per object type (the decoder's: further down): its own rows, the rows
+// of saved records, the geometry of either, a record's size, and what a change of the state behind the object's back touches.
 enum { ULCX_ALIGN_STATE = 16, ULCX_STATE_HEADER = 16, ULCX_WCS_WORDS = sizeof(UlcxWcState) / 4, ULCX_WCS_REC_BYTES = (sizeof(UlcxWcState) + 15) / 16 * 16 };
 static size_t enc_hist_bytes(const ulcx_encoder *e) { return sizeof(float) * 2 * (size_t)e->BS * e->C; }
 extern "C" size_t ulcx_encoder_stream_state_bytes(const ulcx_encoder *e) { return e ? ULCX_STATE_HEADER + enc_hist_bytes(e) + ULCX_WCS_REC_BYTES : 0; }
-static UlcxSlotGeom enc_slot_geom(const ulcx_encoder *e, bool record) {
+static size_t slot_state_bytes(const ulcx_encoder *e) { return ulcx_encoder_stream_state_bytes(e); }
+static void slot_touch(ulcx_encoder *) {}
+static UlcxSlotGeom slot_geom(const ulcx_encoder *e, bool record) {
     UlcxSlotGeom g = {};
     g.B = e->B; g.rowVec = (int)(enc_hist_bytes(e) / 16); g.isEnc = 1; g.nSmall = 1; g.smallWords = ULCX_WCS_WORDS;
     g.padWords = record ? ULCX_WCS_REC_BYTES / 4 : ULCX_WCS_WORDS;
@@ -396,9 +423,10 @@ static UlcxSlotRows enc_slot_rows(const ulcx_encoder *e, float *hist, UlcxWcStat
     r.big = (uint8_t *)hist; r.bigStride = enc_hist_bytes(e); r.small[0] = (uint8_t *)wcs; r.smallStride = sizeof(UlcxWcState);
     return r;
 }
-static UlcxSlotRows enc_record_rows(const ulcx_encoder *e, uint8_t *state) {
+static UlcxSlotRows slot_obj_rows(const ulcx_encoder *e) { return enc_slot_rows(e, e->ctx.hist, e->ctx.wcs); }
+static UlcxSlotRows slot_record_rows(const ulcx_encoder *e, uint8_t *state) {
     UlcxSlotRows r = {};
-    const size_t bytes = ulcx_encoder_stream_state_bytes(e);
+    const size_t bytes = slot_state_bytes(e);
     r.hdr = state; r.hdrStride = bytes; r.big = state + ULCX_STATE_HEADER; r.bigStride = bytes;
     r.small[0] = state + ULCX_STATE_HEADER + enc_hist_bytes(e); r.smallStride = bytes;
     return r;
@@ -410,136 +438,174 @@ static int enc_shadow(ulcx_encoder *e) {
     return ULCX_OK;
 }
 
-// d_rate != NULL: per-stream settings read on the device (ulcx_encode_dev_rates); mode / p0 / p1 are then unused.
-// d_slots != NULL: a subset call - the n listed slots' state gathered into the compact shadow arrays, the plain call's launch
-// sequence on those with c.B = n (every kernel takes its strides from c.B, c.K and c.maxK; the per-call scratch is sized for
-// nStreams >= n), the result scattered back; all on the caller's stream, which the launch joins its side streams into.
-static int encode_dev_any(ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
-                          uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream, const int32_t *d_slots = nullptr, int n = 0) {
-    if (!e || (!d_pcm && !d_pcm16) || !d_out || !d_bits || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_encode_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (d_slots && slots_list_bad("ulcx_encode_dev_subset", d_slots, n, e->B)) return ULCX_ERR_ARG;
-    if (d_rate) { mode = ULCX_MODE_VBR; p0 = 100.0f; p1 = 0.0f; }
-    if (mode != ULCX_MODE_VBR && mode != ULCX_MODE_CBR && mode != ULCX_MODE_ABR) { ulcx_set_error("bad mode"); return ULCX_ERR_ARG; }
-    if (misaligned("ulcx_encode_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_encode_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
-        misaligned("ulcx_encode_dev", "d_rate", d_rate, ULCX_ALIGN_RATE) || misaligned("ulcx_encode_dev", "d_bits", d_bits, ULCX_ALIGN_WORD) ||
-        misaligned("ulcx_encode_dev", "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned("ulcx_encode_dev", "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
-    CKR(hipSetDevice(e->device));
+// ---- the encoder's call families.  A public entry is a wrapper that names itself (`who`) to the body of its family:
+//   encode_dev_any     plain, _pcm16, _rates and _subset calls        encode_ladder_any   the ladder
+//   analyse_dev_any    analysis calls, whole object or subset
+// A body makes every check before any device work - so a refused call leaves the object as it was - and names `who` in every
+// message.  The host-pointer forms make their own checks first (through the same checkers), then: staging (host_staging),
+// input up (enc_pcm_up), the body on the null stream, results down (enc_results_down).
+static bool mode_ok(int m) { return m == ULCX_MODE_VBR || m == ULCX_MODE_CBR || m == ULCX_MODE_ABR; }
+// the arguments every entry of the encoder has: pcm = the one sample pointer the entry takes, device or host
+static int enc_args_bad(const char *who, const ulcx_encoder *e, const void *pcm, bool haveOut, int nBlocks) {
+    if (!e || !pcm || !haveOut) { refuse(who, "bad argument"); return 1; }
+    if (nBlocks < 1 || nBlocks > e->maxK) { refuse(who, "nBlocks out of range"); return 1; }
+    return 0;
+}
+// the one validator of a {RateKbps, AvgComplexity} pair: what ulcEncodeTool.c:43-50 accepts
+static int rate_entry_bad(const char *who, const char *what, int index, float r, float a) {
+    if (isfinite(r) && isfinite(a) && r != 0.0f && !(a < 0.0f)) return 0;
+    refuse(who, "%s %d (RateKbps %g, AvgComplexity %g)", what, index, (double)r, (double)a);
+    return 1;
+}
+static int rate_table_bad(const char *who, const char *what, const ulcx_rate *h_rate, int n) {
+    for (int i = 0; i < n; i++) if (rate_entry_bad(who, what, i, h_rate[i].RateKbps, h_rate[i].AvgComplexity)) return 1;
+    return 0;
+}
+// The context of one call (one rung of a ladder call): the object's, with the call's setting and input.  d_rate != NULL: a
+// per-stream table read on the device; the scalar setting is then VBR / 100 / 0 whatever was passed.  The outputs are the caller's.
+static UlcxEncCtx enc_call_ctx(const ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, const int16_t *d_pcm16, int nBlocks) {
     UlcxEncCtx c = e->ctx;
+    if (d_rate) { mode = ULCX_MODE_VBR; p0 = 100.0f; p1 = 0.0f; }
     c.K = nBlocks; c.keyFinal = 0; c.mode = mode; c.p0 = p0; c.p1 = p1;
     c.vbrTarget = (mode == ULCX_MODE_VBR) ? 0x1.E4EFB7p3f * logf(100.0f / p0) : 0.0f;     // ulcEncoder.c:144 (host libm, data independent)
     c.rates = (const float2 *)d_rate;
-    c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = d_out; c.bits = d_bits; c.wcOut = d_wc; c.cplxOut = d_cplx;
-    const UlcxEncAux aux = enc_aux(e, nBlocks);
-    if (d_slots) {
-        int rc0 = enc_shadow(e);
-        if (!rc0) rc0 = ulcx_slots_gather(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
-        if (rc0) return rc0;
-        c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
-    }
-    int rc = ulcx_enc_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux);
-    if (d_slots && rc == ULCX_OK) rc = ulcx_slots_scatter(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
+    c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = nullptr; c.bits = nullptr; c.wcOut = nullptr; c.cplxOut = nullptr;
+    return c;
+}
+// what the object remembers of its last call
+static int enc_call_done(ulcx_encoder *e, int rc, int nBlocks, bool analyse, int rungs) {
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     e->lastK = nBlocks;
     e->keysFinal = false;
-    e->lastAnalyse = false;
-    e->lastRungs = 1;
+    e->lastAnalyse = analyse;
+    e->lastRungs = rungs;
+    return rc;
+}
+// d_slots != NULL: a subset call - the n listed slots' state gathered into the compact shadow arrays, the plain call's launch
+// sequence on those with c.B = n (every kernel takes its strides from c.B, c.K and c.maxK; the per-call scratch is sized for
+// nStreams >= n), the result scattered back; all on the caller's stream, which the launch joins its side streams into.
+template <class F> static int enc_launch_on(ulcx_encoder *e, UlcxEncCtx &c, const int32_t *d_slots, int n, hipStream_t st, F launch) {
+    if (!d_slots) return launch(c);
+    int rc = enc_shadow(e);
+    if (rc) return rc;
+    const UlcxSlotRows shadow = enc_slot_rows(e, e->subHist, e->subWcs);
+    if ((rc = ulcx_slots_gather(slot_obj_rows(e), shadow, d_slots, n, slot_geom(e, false), st))) return rc;
+    c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
+    rc = launch(c);
+    if (rc == ULCX_OK) rc = ulcx_slots_scatter(slot_obj_rows(e), shadow, d_slots, n, slot_geom(e, false), st);
     return rc;
 }
 
-// ---- ladder (include/ulc_amd.h): one context per rung from the shared one; tables are device pointers here
-static int ladder_check(const ulcx_rung *rungs, int nRungs, const char *who) {
-    if (!rungs || nRungs < 1 || nRungs > ULCX_MAX_RUNGS) { ulcx_set_error("%s: nRungs %d not in 1 .. %d (or no rungs)", who, nRungs, ULCX_MAX_RUNGS); return ULCX_ERR_ARG; }
-    for (int r = 0; r < nRungs; r++) {
-        if (rungs[r].reserved != 0) { ulcx_set_error("%s: rung %d: reserved must be 0", who, r); return ULCX_ERR_ARG; }
-        const int m = rungs[r].mode;
-        if (!rungs[r].rate && m != ULCX_MODE_VBR && m != ULCX_MODE_CBR && m != ULCX_MODE_ABR) { ulcx_set_error("%s: rung %d: bad mode %d", who, r, m); return ULCX_ERR_ARG; }
-    }
-    return ULCX_OK;
+// needRate: the entry takes a table (the _rates calls); a subset call may have one.  subset: the entry takes a slot list.
+static int encode_dev_any(const char *who, ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, bool needRate,
+                          const float *d_pcm, const int16_t *d_pcm16, int nBlocks, uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx,
+                          void *hipStream, bool subset = false, const int32_t *d_slots = nullptr, int n = 0) {
+    if (enc_args_bad(who, e, d_pcm ? (const void *)d_pcm : d_pcm16, d_out && d_bits && (d_rate || !needRate), nBlocks)) return ULCX_ERR_ARG;
+    if (subset && slots_list_bad(who, d_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (!d_rate && !mode_ok(mode)) return refuse(who, "bad mode");
+    if (misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned(who, "d_rate", d_rate, ULCX_ALIGN_RATE) || misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned(who, "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    UlcxEncCtx c = enc_call_ctx(e, mode, p0, p1, d_rate, d_pcm, d_pcm16, nBlocks);
+    c.out = d_out; c.bits = d_bits; c.wcOut = d_wc; c.cplxOut = d_cplx;
+    const UlcxEncAux aux = enc_aux(e, nBlocks);
+    const int rc = enc_launch_on(e, c, subset ? d_slots : nullptr, n, (hipStream_t)hipStream,
+                                 [&](UlcxEncCtx &cc) { return ulcx_enc_launch(cc, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux); });
+    return enc_call_done(e, rc, nBlocks, false, 1);
 }
-static int encode_ladder_any(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
+extern "C" int ulcx_encode_dev(ulcx_encoder *e, int mode, float p0, float p1, const float *d_pcm, int nBlocks,
+                               uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_dev_any("ulcx_encode_dev", e, mode, p0, p1, nullptr, false, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encode_dev_pcm16(ulcx_encoder *e, int mode, float p0, float p1, const int16_t *d_pcm16, int nBlocks,
+                                     uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_dev_any("ulcx_encode_dev_pcm16", e, mode, p0, p1, nullptr, false, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encode_dev_rates(ulcx_encoder *e, const ulcx_rate *d_rate, const float *d_pcm, int nBlocks,
+                                     uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_dev_any("ulcx_encode_dev_rates", e, 0, 0.0f, 0.0f, d_rate, true, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encode_dev_pcm16_rates(ulcx_encoder *e, const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
+                                           uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_dev_any("ulcx_encode_dev_pcm16_rates", e, 0, 0.0f, 0.0f, d_rate, true, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_encode_dev_subset(ulcx_encoder *e, const int32_t *d_slots, int n, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, int nBlocks,
+                                      uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_dev_any("ulcx_encode_dev_subset", e, mode, p0, p1, d_rate, false, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream, true, d_slots, n);
+}
+extern "C" int ulcx_encode_dev_pcm16_subset(ulcx_encoder *e, const int32_t *d_slots, int n, int mode, float p0, float p1, const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
+                                            uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_dev_any("ulcx_encode_dev_pcm16_subset", e, mode, p0, p1, d_rate, false, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream, true, d_slots, n);
+}
+
+// ---- ladder (include/ulc_amd.h): one context per rung from the shared one; tables are device pointers here
+static int ladder_bad(const char *who, const ulcx_rung *rungs, int nRungs) {
+    if (!rungs || nRungs < 1 || nRungs > ULCX_MAX_RUNGS) { refuse(who, "nRungs %d not in 1 .. %d (or no rungs)", nRungs, ULCX_MAX_RUNGS); return 1; }
+    for (int r = 0; r < nRungs; r++) {
+        if (rungs[r].reserved != 0) { refuse(who, "rung %d: reserved must be 0", r); return 1; }
+        if (!rungs[r].rate && !mode_ok(rungs[r].mode)) { refuse(who, "rung %d: bad mode %d", r, rungs[r].mode); return 1; }
+    }
+    return 0;
+}
+static int encode_ladder_any(const char *who, ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const float *d_pcm, const int16_t *d_pcm16, int nBlocks,
                              uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!e || !rungs || (!d_pcm && !d_pcm16) || !d_out || !d_bits || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_encode_dev_ladder: bad argument"); return ULCX_ERR_ARG; }
-    { const int rc = ladder_check(rungs, nRungs, "ulcx_encode_dev_ladder"); if (rc) return rc; }
-    if (misaligned("ulcx_encode_dev_ladder", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_encode_dev_ladder", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
-        misaligned("ulcx_encode_dev_ladder", "d_bits", d_bits, ULCX_ALIGN_WORD) || misaligned("ulcx_encode_dev_ladder", "d_wc", d_wc, ULCX_ALIGN_WORD) ||
-        misaligned("ulcx_encode_dev_ladder", "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
-    for (int r = 0; r < nRungs; r++) if (misaligned("ulcx_encode_dev_ladder", "a rung's rate table", rungs[r].rate, ULCX_ALIGN_RATE)) return ULCX_ERR_ARG;
+    if (ladder_bad(who, rungs, nRungs) || enc_args_bad(who, e, d_pcm ? (const void *)d_pcm : d_pcm16, d_out && d_bits, nBlocks)) return ULCX_ERR_ARG;
+    if (misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD) || misaligned(who, "d_wc", d_wc, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    for (int r = 0; r < nRungs; r++) if (misaligned(who, "a rung's rate table", rungs[r].rate, ULCX_ALIGN_RATE)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxEncCtx cs[ULCX_MAX_RUNGS];
     const size_t NB = (size_t)e->B * nBlocks;
     for (int r = 0; r < nRungs; r++) {
         UlcxEncCtx &c = cs[r];
-        c = e->ctx;
-        const bool table = rungs[r].rate != nullptr;
-        c.K = nBlocks; c.keyFinal = 0;
-        c.mode = table ? ULCX_MODE_VBR : rungs[r].mode; c.p0 = table ? 100.0f : rungs[r].param0; c.p1 = table ? 0.0f : rungs[r].param1;
-        c.vbrTarget = (c.mode == ULCX_MODE_VBR) ? 0x1.E4EFB7p3f * logf(100.0f / c.p0) : 0.0f;     // ulcEncoder.c:144 (host libm, data independent)
-        c.rates = (const float2 *)rungs[r].rate;
-        c.pcm = d_pcm; c.pcm16 = d_pcm16;
+        c = enc_call_ctx(e, rungs[r].mode, rungs[r].param0, rungs[r].param1, rungs[r].rate, d_pcm, d_pcm16, nBlocks);
         c.out = d_out + r * NB * (size_t)c.slot; c.bits = d_bits + r * NB;
-        c.wcOut = r ? nullptr : d_wc; c.cplxOut = r ? nullptr : d_cplx;
+        if (!r) { c.wcOut = d_wc; c.cplxOut = d_cplx; }
     }
-    const UlcxEncAux aux = enc_aux(e, nBlocks);
-    const int rc = ulcx_enc_launch_ladder(cs, nRungs, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux);
-    e->evRecorded = (rc == ULCX_OK) && e->timing;
-    e->lastK = nBlocks;
-    e->keysFinal = false;
-    e->lastAnalyse = false;
-    e->lastRungs = nRungs;
-    return rc;
+    const int rc = ulcx_enc_launch_ladder(cs, nRungs, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, enc_aux(e, nBlocks));
+    return enc_call_done(e, rc, nBlocks, false, nRungs);
 }
 extern "C" int ulcx_encode_dev_ladder(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const float *d_pcm, int nBlocks,
                                       uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_pcm) { ulcx_set_error("ulcx_encode_dev_ladder: bad argument"); return ULCX_ERR_ARG; }
-    return encode_ladder_any(e, rungs, nRungs, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+    return encode_ladder_any("ulcx_encode_dev_ladder", e, rungs, nRungs, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
 }
 extern "C" int ulcx_encode_dev_pcm16_ladder(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const int16_t *d_pcm16, int nBlocks,
                                             uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16_ladder: bad argument"); return ULCX_ERR_ARG; }
-    return encode_ladder_any(e, rungs, nRungs, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
+    return encode_ladder_any("ulcx_encode_dev_pcm16_ladder", e, rungs, nRungs, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
 }
-extern "C" int ulcx_encoder_last_rungs(ulcx_encoder *e) { return e ? e->lastRungs : ULCX_ERR_ARG; }
+extern "C" int ulcx_encoder_last_rungs(ulcx_encoder *e) { return e ? e->lastRungs : refuse("ulcx_encoder_last_rungs", "no encoder"); }
 
 // ---- analysis only (include/ulc_amd.h): window control, MDCT, block complexity, next-call state
-static int analyse_dev_any(ulcx_encoder *e, const float *d_pcm, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream,
-                           const int32_t *d_slots = nullptr, int n = 0) {      // (d_slots: a subset call, as in encode_dev_any)
-    if (!e || (!d_pcm && !d_pcm16) || (!d_wc && !d_cplx) || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_analyse_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (d_slots && slots_list_bad("ulcx_analyse_dev_subset", d_slots, n, e->B)) return ULCX_ERR_ARG;
-    if (misaligned("ulcx_analyse_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_analyse_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
-        misaligned("ulcx_analyse_dev", "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned("ulcx_analyse_dev", "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+static int analyse_dev_any(const char *who, ulcx_encoder *e, const float *d_pcm, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream,
+                           bool subset = false, const int32_t *d_slots = nullptr, int n = 0) {
+    if (enc_args_bad(who, e, d_pcm ? (const void *)d_pcm : d_pcm16, d_wc || d_cplx, nBlocks)) return ULCX_ERR_ARG;
+    if (subset && slots_list_bad(who, d_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned(who, "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned(who, "d_cplx", d_cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    UlcxEncCtx c = e->ctx;
-    c.K = nBlocks; c.keyFinal = 0; c.mode = ULCX_MODE_VBR; c.p0 = 100.0f; c.p1 = 0.0f; c.vbrTarget = 0.0f; c.rates = nullptr;
-    c.pcm = d_pcm; c.pcm16 = d_pcm16; c.out = nullptr; c.bits = nullptr; c.wcOut = d_wc; c.cplxOut = d_cplx;
+    UlcxEncCtx c = enc_call_ctx(e, ULCX_MODE_VBR, 100.0f, 0.0f, nullptr, d_pcm, d_pcm16, nBlocks);
+    c.wcOut = d_wc; c.cplxOut = d_cplx;
     const UlcxEncAux aux = enc_aux(e, nBlocks);      // (the encode call's chunking)
-    if (d_slots) {
-        int rc0 = enc_shadow(e);
-        if (!rc0) rc0 = ulcx_slots_gather(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
-        if (rc0) return rc0;
-        c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
-    }
-    int rc = ulcx_analyse_launch(c, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux, e->analyseKxf);
-    if (d_slots && rc == ULCX_OK) rc = ulcx_slots_scatter(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_slot_rows(e, e->subHist, e->subWcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
-    e->evRecorded = (rc == ULCX_OK) && e->timing;
-    e->lastK = nBlocks;
-    e->keysFinal = false;
-    e->lastAnalyse = true;
-    e->lastRungs = 0;
-    return rc;
+    const int rc = enc_launch_on(e, c, subset ? d_slots : nullptr, n, (hipStream_t)hipStream,
+                                 [&](UlcxEncCtx &cc) { return ulcx_analyse_launch(cc, (hipStream_t)hipStream, e->timing ? e->ev : nullptr, aux, e->analyseKxf); });
+    return enc_call_done(e, rc, nBlocks, true, 0);
 }
 extern "C" int ulcx_analyse_dev(ulcx_encoder *e, const float *d_pcm, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_pcm) { ulcx_set_error("ulcx_analyse_dev: bad argument"); return ULCX_ERR_ARG; }
-    return analyse_dev_any(e, d_pcm, nullptr, nBlocks, d_wc, d_cplx, hipStream);
+    return analyse_dev_any("ulcx_analyse_dev", e, d_pcm, nullptr, nBlocks, d_wc, d_cplx, hipStream);
 }
 extern "C" int ulcx_analyse_dev_pcm16(ulcx_encoder *e, const int16_t *d_pcm16, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_pcm16) { ulcx_set_error("ulcx_analyse_dev_pcm16: bad argument"); return ULCX_ERR_ARG; }
-    return analyse_dev_any(e, nullptr, d_pcm16, nBlocks, d_wc, d_cplx, hipStream);
+    return analyse_dev_any("ulcx_analyse_dev_pcm16", e, nullptr, d_pcm16, nBlocks, d_wc, d_cplx, hipStream);
+}
+extern "C" int ulcx_analyse_dev_subset(ulcx_encoder *e, const int32_t *d_slots, int n, const float *d_pcm, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return analyse_dev_any("ulcx_analyse_dev_subset", e, d_pcm, nullptr, nBlocks, d_wc, d_cplx, hipStream, true, d_slots, n);
 }
 
-// device staging of the host-pointer entries: input, window codes, complexities; withOut: output slots and sizes too (an
-// encoder that only ever analyses never allocates those)
-static int host_staging(ulcx_encoder *e, size_t nBlk, bool withOut) {
-    const size_t cb = (size_t)e->C * e->BS;
+// ---- host-pointer forms.  Device staging kept by the object, sized for maxBlocksPerCall blocks of every stream: input,
+// window codes, complexities; withOut: output slots and sizes too (an encoder that only ever analyses never allocates those)
+static int host_staging(ulcx_encoder *e, bool withOut) {
+    const size_t nBlk = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS;
     int rc;
     if (!e->d_pcm && (rc = dalloc(e->allocs, &e->d_pcm, nBlk * cb, false))) return rc;
     if (!e->d_wc && (rc = dalloc(e->allocs, &e->d_wc, nBlk, false))) return rc;
@@ -548,115 +614,99 @@ static int host_staging(ulcx_encoder *e, size_t nBlk, bool withOut) {
     if (withOut && !e->d_bits && (rc = dalloc(e->allocs, &e->d_bits, nBlk, false))) return rc;
     return ULCX_OK;
 }
-
+// the device copy of a host form's slot list
+template <class OBJ> static int slots_list_up(OBJ *e, const int32_t *h_slots, int n) {
+    if (!e->subSlots) { int rc = dalloc(e->allocs, &e->subSlots, (size_t)e->B, false); if (rc) return rc; }
+    CKR(hipMemcpy(e->subSlots, h_slots, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+    return ULCX_OK;
+}
+static int enc_pcm_up(ulcx_encoder *e, const float *h_pcm, size_t NB) {
+    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * (size_t)e->C * e->BS, hipMemcpyHostToDevice));
+    return ULCX_OK;
+}
+// Waits for the device, then copies a call's results down: nSlotsDown slots and sizes from d_out / d_bits (none: an analysis
+// call; a ladder call: every rung's), NB window codes and complexities from the object's staging where the caller wants them.
+static int enc_results_down(ulcx_encoder *e, const uint8_t *d_out, const int32_t *d_bits, size_t nSlotsDown, size_t NB,
+                            uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
+    CKR(hipDeviceSynchronize());
+    if (h_out) CKR(hipMemcpy(h_out, d_out, nSlotsDown * e->ctx.slot, hipMemcpyDeviceToHost));
+    if (h_bits) CKR(hipMemcpy(h_bits, d_bits, sizeof(int32_t) * nSlotsDown, hipMemcpyDeviceToHost));
+    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
 extern "C" int ulcx_analyse_host(ulcx_encoder *e, const float *h_pcm, int nBlocks, int32_t *h_wc, float *h_cplx) {
-    if (!e || !h_pcm || (!h_wc && !h_cplx)) { ulcx_set_error("ulcx_analyse_host: bad argument"); return ULCX_ERR_ARG; }
-    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
+    const char *who = "ulcx_analyse_host";
+    if (enc_args_bad(who, e, h_pcm, h_wc || h_cplx, nBlocks)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    int rc = host_staging(e, (size_t)e->B * e->maxK, false);
-    if (rc) return rc;
-    const size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
-    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
-    rc = ulcx_analyse_dev(e, e->d_pcm, nBlocks, h_wc ? e->d_wc : nullptr, h_cplx ? e->d_cplx : nullptr, nullptr);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
+    const size_t NB = (size_t)e->B * nBlocks;
+    int rc = host_staging(e, false);
+    if (!rc) rc = enc_pcm_up(e, h_pcm, NB);
+    if (!rc) rc = analyse_dev_any(who, e, e->d_pcm, nullptr, nBlocks, h_wc ? e->d_wc : nullptr, h_cplx ? e->d_cplx : nullptr, nullptr);
+    return rc ? rc : enc_results_down(e, nullptr, nullptr, 0, NB, nullptr, nullptr, h_wc, h_cplx);
 }
-
-extern "C" int ulcx_encode_dev(ulcx_encoder *e, int mode, float p0, float p1, const float *d_pcm, int nBlocks,
-                               uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_pcm) { ulcx_set_error("ulcx_encode_dev: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, mode, p0, p1, nullptr, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
-}
-extern "C" int ulcx_encode_dev_pcm16(ulcx_encoder *e, int mode, float p0, float p1, const int16_t *d_pcm16, int nBlocks,
-                                     uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, mode, p0, p1, nullptr, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
-}
-extern "C" int ulcx_encode_dev_rates(ulcx_encoder *e, const ulcx_rate *d_rate, const float *d_pcm, int nBlocks,
-                                     uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_rate || !d_pcm) { ulcx_set_error("ulcx_encode_dev_rates: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, 0, 0.0f, 0.0f, d_rate, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
-}
-extern "C" int ulcx_encode_dev_pcm16_rates(ulcx_encoder *e, const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
-                                           uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!d_rate || !d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16_rates: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, 0, 0.0f, 0.0f, d_rate, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream);
-}
-
-// the host-pointer encode calls behind their argument checks and staging: input up, one call on the null stream, results down
-static int encode_host_run(ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *h_pcm, int nBlocks,
-                           uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
-    const size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
-    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
-    int rc = encode_dev_any(e, mode, p0, p1, d_rate, e->d_pcm, nullptr, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_out, e->d_out, NB * e->ctx.slot, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
-}
-
-extern "C" int ulcx_encode_host_rates(ulcx_encoder *e, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
-                                      uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
-    if (!e || !h_rate || !h_pcm || !h_out || !h_bits) { ulcx_set_error("ulcx_encode_host_rates: bad argument"); return ULCX_ERR_ARG; }
-    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
-    for (int s = 0; s < e->B; s++) {                   // ulcEncodeTool.c:43-50, before any device work
-        const float r = h_rate[s].RateKbps, a = h_rate[s].AvgComplexity;
-        if (!isfinite(r) || !isfinite(a) || r == 0.0f || a < 0.0f) {
-            ulcx_set_error("ulcx_encode_host_rates: invalid entry for stream %d (RateKbps %g, AvgComplexity %g)", s, (double)r, (double)a);
-            return ULCX_ERR_ARG;
-        }
-    }
+// The plain, _rates and _subset host forms behind their argument checks.  h_rate: a table of one entry per row of the call;
+// h_slots: a subset call of n rows.
+static int encode_host_any(const char *who, ulcx_encoder *e, int mode, float p0, float p1, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
+                           uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx, const int32_t *h_slots = nullptr, int n = 0) {
     CKR(hipSetDevice(e->device));
-    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
-    if (!e->d_rate) { int rc = dalloc(e->allocs, &e->d_rate, (size_t)e->B, false); if (rc) return rc; }
-    CKR(hipMemcpy(e->d_rate, h_rate, sizeof(ulcx_rate) * (size_t)e->B, hipMemcpyHostToDevice));
-    return encode_host_run(e, 0, 0.0f, 0.0f, e->d_rate, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx);
+    const size_t rows = h_slots ? (size_t)n : (size_t)e->B, NB = rows * nBlocks;
+    int rc = host_staging(e, true);
+    if (!rc && h_rate && !e->d_rate) rc = dalloc(e->allocs, &e->d_rate, (size_t)e->B, false);
+    if (!rc && h_slots) rc = slots_list_up(e, h_slots, n);
+    if (rc) return rc;
+    if (h_rate) CKR(hipMemcpy(e->d_rate, h_rate, sizeof(ulcx_rate) * rows, hipMemcpyHostToDevice));
+    if ((rc = enc_pcm_up(e, h_pcm, NB))) return rc;
+    rc = encode_dev_any(who, e, mode, p0, p1, h_rate ? e->d_rate : nullptr, false, e->d_pcm, nullptr, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr,
+                        h_slots != nullptr, e->subSlots, n);
+    return rc ? rc : enc_results_down(e, e->d_out, e->d_bits, NB, NB, h_out, h_bits, h_wc, h_cplx);
 }
-
 extern "C" int ulcx_encode_host(ulcx_encoder *e, int mode, float p0, float p1, const float *h_pcm, int nBlocks,
                                 uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
-    if (!e || !h_pcm || !h_out || !h_bits) return ULCX_ERR_ARG;
-    CKR(hipSetDevice(e->device));
-    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
-    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
-    return encode_host_run(e, mode, p0, p1, nullptr, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx);
+    const char *who = "ulcx_encode_host";
+    if (enc_args_bad(who, e, h_pcm, h_out && h_bits, nBlocks)) return ULCX_ERR_ARG;
+    if (!mode_ok(mode)) return refuse(who, "bad mode");
+    return encode_host_any(who, e, mode, p0, p1, nullptr, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx);
+}
+extern "C" int ulcx_encode_host_rates(ulcx_encoder *e, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
+                                      uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
+    const char *who = "ulcx_encode_host_rates";
+    if (enc_args_bad(who, e, h_pcm, h_out && h_bits && h_rate, nBlocks)) return ULCX_ERR_ARG;
+    if (rate_table_bad(who, "invalid entry for stream", h_rate, e->B)) return ULCX_ERR_ARG;          // ulcEncodeTool.c:43-50, before any device work
+    return encode_host_any(who, e, 0, 0.0f, 0.0f, h_rate, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx);
+}
+extern "C" int ulcx_encode_host_subset(ulcx_encoder *e, const int32_t *h_slots, int n, int mode, float p0, float p1, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
+                                       uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
+    const char *who = "ulcx_encode_host_subset";
+    if (enc_args_bad(who, e, h_pcm, h_out && h_bits, nBlocks) || slots_host_bad(who, h_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (!h_rate && !mode_ok(mode)) return refuse(who, "bad mode");
+    if (h_rate && rate_table_bad(who, "invalid entry for row", h_rate, n)) return ULCX_ERR_ARG;
+    return encode_host_any(who, e, mode, p0, p1, h_rate, h_pcm, nBlocks, h_out, h_bits, h_wc, h_cplx, h_slots, n);
 }
 
 // The ladder's host-pointer form: every rung validated first (tables as ulcx_encode_host_rates validates its own, a scalar
 // rung's parameters by the same rule), then input and tables up, one call on the null stream, [R][B][K] results down.
+// Its slots and sizes have staging of their own, [ladRungs][B][maxK], grown to the largest ladder seen.
 extern "C" int ulcx_encode_host_ladder(ulcx_encoder *e, const ulcx_rung *rungs, int nRungs, const float *h_pcm, int nBlocks,
                                        uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
-    if (!e || !rungs || !h_pcm || !h_out || !h_bits) { ulcx_set_error("ulcx_encode_host_ladder: bad argument"); return ULCX_ERR_ARG; }
-    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
-    { const int rc = ladder_check(rungs, nRungs, "ulcx_encode_host_ladder"); if (rc) return rc; }
+    const char *who = "ulcx_encode_host_ladder";
+    if (ladder_bad(who, rungs, nRungs) || enc_args_bad(who, e, h_pcm, h_out && h_bits, nBlocks)) return ULCX_ERR_ARG;
     for (int r = 0; r < nRungs; r++) {
-        const int n = rungs[r].rate ? e->B : 1;
-        for (int s = 0; s < n; s++) {
-            const float v = rungs[r].rate ? rungs[r].rate[s].RateKbps : rungs[r].param0, a = rungs[r].rate ? rungs[r].rate[s].AvgComplexity : rungs[r].param1;
-            if (!isfinite(v) || !isfinite(a) || v == 0.0f || a < 0.0f) {
-                ulcx_set_error("ulcx_encode_host_ladder: rung %d: invalid setting%s %d (rate %g, complexity %g)", r, rungs[r].rate ? " for stream" : ", mode", rungs[r].rate ? s : rungs[r].mode, (double)v, (double)a);
-                return ULCX_ERR_ARG;
-            }
-        }
+        char what[64];
+        snprintf(what, sizeof(what), "rung %d: %s", r, rungs[r].rate ? "invalid setting for stream" : "invalid setting, mode");
+        if (rungs[r].rate ? rate_table_bad(who, what, rungs[r].rate, e->B) : rate_entry_bad(who, what, rungs[r].mode, rungs[r].param0, rungs[r].param1)) return ULCX_ERR_ARG;
     }
     CKR(hipSetDevice(e->device));
-    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
-    const size_t nBlk = (size_t)e->B * e->maxK;
-    if (e->ladRungs < nRungs) {
-        if (e->ladOut) CKR(hipFree(e->ladOut));
-        if (e->ladBits) CKR(hipFree(e->ladBits));
-        e->ladOut = nullptr; e->ladBits = nullptr; e->ladRungs = 0;
-        CKR(hipMalloc((void **)&e->ladOut, (size_t)nRungs * nBlk * e->ctx.slot));
-        CKR(hipMalloc((void **)&e->ladBits, sizeof(int32_t) * (size_t)nRungs * nBlk));
-        e->ladRungs = nRungs;
+    const size_t nBlk = (size_t)e->B * e->maxK, NB = (size_t)e->B * nBlocks;
+    int rc = host_staging(e, true);
+    if (!rc && e->ladRungs < nRungs) {
+        e->ladRungs = 0;
+        rc = dregrow(e->allocs, &e->ladOut, (size_t)nRungs * nBlk * e->ctx.slot, false);
+        if (!rc) rc = dregrow(e->allocs, &e->ladBits, (size_t)nRungs * nBlk, false);
+        if (!rc) e->ladRungs = nRungs;
     }
-    if (!e->ladRate) { int rc = dalloc(e->allocs, &e->ladRate, (size_t)ULCX_MAX_RUNGS * e->B, false); if (rc) return rc; }
+    if (!rc && !e->ladRate) rc = dalloc(e->allocs, &e->ladRate, (size_t)ULCX_MAX_RUNGS * e->B, false);
+    if (rc) return rc;
     ulcx_rung dev[ULCX_MAX_RUNGS];
     for (int r = 0; r < nRungs; r++) {
         dev[r] = rungs[r];
@@ -665,16 +715,9 @@ extern "C" int ulcx_encode_host_ladder(ulcx_encoder *e, const ulcx_rung *rungs, 
             CKR(hipMemcpy((void *)dev[r].rate, rungs[r].rate, sizeof(ulcx_rate) * (size_t)e->B, hipMemcpyHostToDevice));
         }
     }
-    const size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
-    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
-    int rc = encode_ladder_any(e, dev, nRungs, e->d_pcm, nullptr, nBlocks, e->ladOut, e->ladBits, e->d_wc, e->d_cplx, nullptr);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_out, e->ladOut, (size_t)nRungs * NB * e->ctx.slot, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->ladBits, sizeof(int32_t) * (size_t)nRungs * NB, hipMemcpyDeviceToHost));
-    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
+    if ((rc = enc_pcm_up(e, h_pcm, NB))) return rc;
+    rc = encode_ladder_any(who, e, dev, nRungs, e->d_pcm, nullptr, nBlocks, e->ladOut, e->ladBits, e->d_wc, e->d_cplx, nullptr);
+    return rc ? rc : enc_results_down(e, e->ladOut, e->ladBits, (size_t)nRungs * NB, NB, h_out, h_bits, h_wc, h_cplx);
 }
 
 // One block of one stream per call (the drop-in ABI): include/ulc_amd.h.  The launch sequence of ulcx_encode_dev - side
@@ -682,12 +725,14 @@ extern "C" int ulcx_encode_host_ladder(ulcx_encoder *e, const ulcx_rung *rungs, 
 // staging buffers and the device; a call is then memcpy, one graph launch, one synchronisation, memcpy.
 extern "C" int ulcx_encode_block1(ulcx_encoder *e, int mode, float p0, float p1, const float *h_pcm,
                                   uint8_t *h_out, int32_t *bits, float *cplx, int32_t stateOut[2], float transientFilter[3]) {
-    if (!e || !h_pcm || !h_out || e->B != 1 || e->maxK != 1) { ulcx_set_error("ulcx_encode_block1: needs an encoder of one stream, one block per call"); return ULCX_ERR_ARG; }
+    const char *who = "ulcx_encode_block1";
+    if (!e || !h_pcm || !h_out || e->B != 1 || e->maxK != 1) return refuse(who, "needs an encoder of one stream, one block per call");
+    if (!mode_ok(mode)) return refuse(who, "bad mode");
     CKR(hipSetDevice(e->device));
     const size_t cb = (size_t)e->C * e->BS, slot = (size_t)e->ctx.slot;
     if (!e->b1Init) {
         int rc;
-        if ((rc = host_staging(e, 1, true))) return rc;                // (one stream, one block per call)
+        if ((rc = host_staging(e, true))) return rc;                   // (one stream, one block per call)
         // (b1Init only once everything exists: a failed allocation leaves the call to be retried from scratch, never a
         //  later call copying into a null staging buffer)
         if (!e->b1.stream) CKR(hipStreamCreateWithFlags(&e->b1.stream, hipStreamNonBlocking));
@@ -699,7 +744,7 @@ extern "C" int ulcx_encode_block1(ulcx_encoder *e, int mode, float p0, float p1,
     }
     auto enqueue = [&]() -> int {
         CKR(hipMemcpyAsync(e->d_pcm, e->pinIn, sizeof(float) * cb, hipMemcpyHostToDevice, e->b1.stream));
-        int rc = ulcx_encode_dev(e, mode, p0, p1, e->d_pcm, 1, e->d_out, e->d_bits, e->d_wc, e->d_cplx, e->b1.stream);
+        int rc = encode_dev_any(who, e, mode, p0, p1, nullptr, false, e->d_pcm, nullptr, 1, e->d_out, e->d_bits, e->d_wc, e->d_cplx, e->b1.stream);
         if (rc) return rc;
         CKR(hipMemcpyAsync(e->pinOut, e->d_out, slot, hipMemcpyDeviceToHost, e->b1.stream));
         CKR(hipMemcpyAsync(&e->pinMeta->bits, e->d_bits, sizeof(int32_t), hipMemcpyDeviceToHost, e->b1.stream));
@@ -727,8 +772,9 @@ extern "C" int ulcx_encode_block1(ulcx_encoder *e, int mode, float p0, float p1,
 }
 
 extern "C" int ulcx_encoder_debug_fetch(ulcx_encoder *e, int nBlocks, float *h_coef, float *h_noise, float *h_keys, uint8_t *h_keep, int32_t *h_nout) {
-    if (!e || nBlocks < 1 || nBlocks > e->maxK) return ULCX_ERR_ARG;
-    if (e->lastAnalyse) { ulcx_set_error("ulcx_encoder_debug_fetch: the last call was an analysis call (no intermediates)"); return ULCX_ERR_ARG; }
+    const char *who = "ulcx_encoder_debug_fetch";
+    if (!e || nBlocks < 1 || nBlocks > e->maxK) return refuse(who, "no encoder, or nBlocks out of range");
+    if (e->lastAnalyse) return refuse(who, "the last call was an analysis call (no intermediates)");
     CKR(hipSetDevice(e->device));
     CKR(hipDeviceSynchronize());
     size_t NB = (size_t)e->B * nBlocks, cb = (size_t)e->C * e->BS;
@@ -760,12 +806,12 @@ extern "C" int ulcx_encoder_debug_fetch(ulcx_encoder *e, int nBlocks, float *h_c
 }
 
 extern "C" int ulcx_encoder_debug_force_exact(ulcx_encoder *e, int every) {
-    if (!e || every < 0) return ULCX_ERR_ARG;
+    if (!e || every < 0) return refuse("ulcx_encoder_debug_force_exact", "no encoder, or every < 0");
     e->ctx.forceFb = every;
     return ULCX_OK;
 }
 extern "C" int ulcx_encoder_last_fallbacks(ulcx_encoder *e) {
-    if (!e) return ULCX_ERR_ARG;
+    if (!e) return refuse("ulcx_encoder_last_fallbacks", "no encoder");
     if (e->lastAnalyse) return 0;                                      // (an analysis call selects nothing)
     CKR(hipSetDevice(e->device));
     CKR(hipDeviceSynchronize());
@@ -805,10 +851,6 @@ extern "C" int ulcx_encoder_last_xf_launches(ulcx_encoder *e) { return (e && e->
 static void cleanup(ulcx_decoder *e) {
     if (!e) return;
     for (void *p : e->allocs) hipFree(p);
-    if (e->d_pay) hipFree(e->d_pay);
-    if (e->d_payBytes) hipFree(e->d_payBytes);
-    if (e->d_index) hipFree(e->d_index);
-    if (e->d_idxBlocks) hipFree(e->d_idxBlocks);
     if (e->tables) hipFree(e->tables);
     if (e->evOk) for (auto &v : e->ev) hipEventDestroy(v);
     block1_drop(e->b1);
@@ -883,7 +925,7 @@ extern "C" int ulcx_dec_range_tail_plan(int nStreams, int nBlocks, int residentW
     return (int)((long long)rem * nBlocks / len);
 }
 extern "C" int ulcx_decoder_last_cut(ulcx_decoder *e, int *workgroups, int *wholeStreams, int *residentWG) {
-    if (!e) return ULCX_ERR_ARG;
+    if (!e) return refuse("ulcx_decoder_last_cut", "no decoder");
     if (workgroups) *workgroups = e->lastGrid;
     if (wholeStreams) *wholeStreams = e->lastFull;
     if (residentWG) *residentWG = e->synSlots;
@@ -929,10 +971,11 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subse
 }
 
 extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams, int nChan, int BlockSize, int maxBlocksPerCall) {
-    if (!out) return ULCX_ERR_ARG;
+    const char *who = "ulcx_decoder_create";
+    if (!out) return refuse(who, "no place for the object");
     *out = nullptr;
-    if (!validate(nChan, BlockSize) || nStreams < 1 || maxBlocksPerCall < 1) { ulcx_set_error("invalid decoder geometry"); return ULCX_ERR_ARG; }
-    int rc = select_device(device);
+    if (!validate(nChan, BlockSize) || nStreams < 1 || maxBlocksPerCall < 1) return refuse(who, "invalid decoder geometry");
+    int rc = select_device(who, device);
     if (rc) return rc;
     ulcx_decoder *e = new ulcx_decoder();
     e->device = device; e->B = nStreams; e->C = nChan; e->BS = BlockSize; e->maxK = maxBlocksPerCall;
@@ -1005,26 +1048,32 @@ extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams,
     return ULCX_OK;
 }
 extern "C" void ulcx_decoder_destroy(ulcx_decoder *e) { if (e) { hipSetDevice(e->device); cleanup(e); } }
-extern "C" int ulcx_decoder_reset(ulcx_decoder *e) { if (!e) return ULCX_ERR_ARG; CKR(hipSetDevice(e->device)); return dec_reset_state(e); }
+extern "C" int ulcx_decoder_reset(ulcx_decoder *e) { if (!e) return refuse("ulcx_decoder_reset", "no decoder"); CKR(hipSetDevice(e->device)); return dec_reset_state(e); }
 
-// device staging of the host-pointer entries: output samples and sizes of nBlk blocks; inBytes > 0: the input slots too
-static int dec_host_staging(ulcx_decoder *e, size_t nBlk, size_t inBytes) {
+// Device staging of the host-pointer entries, kept by the object: output samples and sizes of maxBlocksPerCall blocks of every
+// stream; inBytes > 0: the input slots too, regrown for a larger slotBytes (a captured single-block sequence holds the old
+// buffer's address: it is dropped with the buffer and captured again by the next single-block call)
+static int dec_host_staging(ulcx_decoder *e, size_t inBytes) {
+    const size_t nBlk = (size_t)e->B * e->maxK;
     int rc;
-    if (inBytes && (!e->d_in || e->d_in_bytes < inBytes)) {
-        if ((rc = dalloc(e->allocs, &e->d_in, inBytes, true))) return rc;
+    if (inBytes && e->d_in_bytes < inBytes) {
+        if (e->d_in) block1_drop(e->b1);
+        e->d_in_bytes = 0;
+        if ((rc = dregrow(e->allocs, &e->d_in, inBytes, true))) return rc;
         e->d_in_bytes = inBytes;
     }
-    if (!e->d_pcm) {
-        if ((rc = dalloc(e->allocs, &e->d_pcm, nBlk * (size_t)e->C * e->BS, false))) return rc;
-        if ((rc = dalloc(e->allocs, &e->d_bits, nBlk, false))) return rc;
-    }
+    if (!e->d_pcm && (rc = dalloc(e->allocs, &e->d_pcm, nBlk * (size_t)e->C * e->BS, false))) return rc;
+    if (!e->d_bits && (rc = dalloc(e->allocs, &e->d_bits, nBlk, false))) return rc;
     return ULCX_OK;
 }
 
 // ---- stream slots: the decoder's side (the object's CURRENT set of state arrays: e->ctx.lap .. - a cut synthesis swaps the sets)
 static size_t dec_lap_bytes(const ulcx_decoder *e) { return sizeof(float) * (size_t)e->C * (e->BS / 2); }
 extern "C" size_t ulcx_decoder_stream_state_bytes(const ulcx_decoder *e) { return e ? ULCX_STATE_HEADER + dec_lap_bytes(e) + 16 : 0; }
-static UlcxSlotGeom dec_slot_geom(const ulcx_decoder *e) {
+static size_t slot_state_bytes(const ulcx_decoder *e) { return ulcx_decoder_stream_state_bytes(e); }
+// (a reset or a load changes the generator word behind the single-block path's host copy, as a batched decode call does: b1Seed)
+static void slot_touch(ulcx_decoder *e) { if (!e->inBlock1) e->b1SeedStale = true; }
+static UlcxSlotGeom slot_geom(const ulcx_decoder *e, bool /*record: the same layout*/) {
     UlcxSlotGeom g = {};
     g.B = e->B; g.rowVec = (int)(dec_lap_bytes(e) / 16); g.isEnc = 0; g.nSmall = 4; g.smallWords = 1; g.padWords = 1;
     g.header = make_uint4(ULCX_STATE_MAGIC_DEC, (unsigned)e->C, (unsigned)e->BS, 0u);
@@ -1036,11 +1085,11 @@ static UlcxSlotRows dec_slot_rows(const ulcx_decoder *e, float *lap, int *lastSu
     r.small[0] = (uint8_t *)lastSub; r.small[1] = (uint8_t *)seed; r.small[2] = (uint8_t *)dead; r.small[3] = (uint8_t *)packOff; r.smallStride = 4;
     return r;
 }
-static UlcxSlotRows dec_obj_rows(const ulcx_decoder *e) { return dec_slot_rows(e, e->ctx.lap, e->ctx.lastSub, e->ctx.seed, e->ctx.dead, e->ctx.packOff); }
+static UlcxSlotRows slot_obj_rows(const ulcx_decoder *e) { return dec_slot_rows(e, e->ctx.lap, e->ctx.lastSub, e->ctx.seed, e->ctx.dead, e->ctx.packOff); }
 static UlcxSlotRows dec_shadow_rows(const ulcx_decoder *e, int set) { return dec_slot_rows(e, e->subLap[set], e->subLastSub[set], e->subSeed[set], e->subDead[set], e->subPackOff); }
-static UlcxSlotRows dec_record_rows(const ulcx_decoder *e, uint8_t *state) {
+static UlcxSlotRows slot_record_rows(const ulcx_decoder *e, uint8_t *state) {
     UlcxSlotRows r = {};
-    const size_t bytes = ulcx_decoder_stream_state_bytes(e);
+    const size_t bytes = slot_state_bytes(e);
     r.hdr = state; r.hdrStride = bytes; r.big = state + ULCX_STATE_HEADER; r.bigStride = bytes;
     for (int a = 0; a < 4; a++) r.small[a] = state + ULCX_STATE_HEADER + dec_lap_bytes(e) + 4 * a;
     r.smallStride = bytes;
@@ -1058,66 +1107,97 @@ static int dec_shadow(ulcx_decoder *e) {
     return ULCX_OK;
 }
 
-// d_slots != NULL: a subset call, as the encoder's (encode_dev_any): gather, the plain launch on the compact state, scatter
-static int decode_dev_any(ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream,
-                          const int32_t *d_slots = nullptr, int n = 0) {
-    if (!e || !d_in || (!d_pcm && !d_pcm16) || !d_bits || slotBytes < 1 || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_decode_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (d_slots && slots_list_bad("ulcx_decode_dev_subset", d_slots, n, e->B)) return ULCX_ERR_ARG;
-    if (misaligned("ulcx_decode_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_decode_dev", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
-        misaligned("ulcx_decode_dev", "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+// ---- the decoder's call families, as the encoder's: a public entry names itself to the body of its family, which makes every
+// check before any device work.
+//   decode_dev_any     slots in, whole object or subset       decode_packed_any   the next blocks of packed payloads
+//   decode_range_any   any block range of packed payloads     index_packed_any    the block index
+// The host-pointer forms check, stage (dec_host_staging for what the object keeps, a DevTmp for what lives for the call), run the
+// body on the null stream and fetch the results with dec_results_down.
+// the arguments every decode entry has: in = slots or payloads, pcm = the one sample pointer the entry takes; device or host
+// front = 1: a range call (the block in front of a range takes one row of the per-block scratch: nBlocks <= maxBlocksPerCall - 1)
+static int dec_args_bad(const char *who, const ulcx_decoder *e, const void *in, const void *pcm, const void *bits, int nBlocks, int front) {
+    if (e && in && pcm && bits && nBlocks >= 1 && nBlocks <= e->maxK - front) return 0;
+    refuse(who, front ? "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)" : "bad argument");
+    return 1;
+}
+// subset: the entry takes a slot list, as the encoder's (encode_dev_any): gather, the plain launch on the compact state, scatter
+static int decode_dev_any(const char *who, ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream,
+                          bool subset = false, const int32_t *d_slots = nullptr, int n = 0) {
+    if (dec_args_bad(who, e, d_in, d_pcm ? (const void *)d_pcm : d_pcm16, d_bits, nBlocks, 0)) return ULCX_ERR_ARG;
+    if (slotBytes < 1) return refuse(who, "bad argument");
+    if (subset && slots_list_bad(who, d_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.K = nBlocks; c.slot = slotBytes; c.in = d_in; c.pcm = d_pcm; c.pcm16 = d_pcm16; c.bits = d_bits;
     c.inBytes = (long long)e->B * nBlocks * slotBytes;
-    if (d_slots) {
+    if (subset) {
         int rc0 = dec_shadow(e);
-        if (!rc0) rc0 = ulcx_slots_gather(dec_obj_rows(e), dec_shadow_rows(e, 0), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
+        if (!rc0) rc0 = ulcx_slots_gather(slot_obj_rows(e), dec_shadow_rows(e, 0), d_slots, n, slot_geom(e, false), (hipStream_t)hipStream);
         if (rc0) return rc0;
         c.B = n; c.inBytes = (long long)n * nBlocks * slotBytes;
         c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
     }
     int set = 0;
-    int rc = dec_launch(e, c, (hipStream_t)hipStream, d_slots ? &set : nullptr);
-    if (d_slots && rc == ULCX_OK) rc = ulcx_slots_scatter(dec_obj_rows(e), dec_shadow_rows(e, set), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
+    int rc = dec_launch(e, c, (hipStream_t)hipStream, subset ? &set : nullptr);
+    if (subset && rc == ULCX_OK) rc = ulcx_slots_scatter(slot_obj_rows(e), dec_shadow_rows(e, set), d_slots, n, slot_geom(e, false), (hipStream_t)hipStream);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     return rc;
 }
 extern "C" int ulcx_decode_dev(ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
-    if (!d_pcm) { ulcx_set_error("ulcx_decode_dev: bad argument"); return ULCX_ERR_ARG; }
-    return decode_dev_any(e, d_in, slotBytes, nBlocks, d_pcm, nullptr, d_bits, hipStream);
+    return decode_dev_any("ulcx_decode_dev", e, d_in, slotBytes, nBlocks, d_pcm, nullptr, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_dev_pcm16(ulcx_decoder *e, const uint8_t *d_in, int slotBytes, int nBlocks, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    if (!d_pcm16) { ulcx_set_error("ulcx_decode_dev_pcm16: bad argument"); return ULCX_ERR_ARG; }
-    return decode_dev_any(e, d_in, slotBytes, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
+    return decode_dev_any("ulcx_decode_dev_pcm16", e, d_in, slotBytes, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
 }
-extern "C" int ulcx_decode_host(ulcx_decoder *e, const uint8_t *h_in, int slotBytes, int nBlocks, float *h_pcm, int32_t *h_bits) {
-    if (!e || !h_in || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK || slotBytes < 1) return ULCX_ERR_ARG;
-    CKR(hipSetDevice(e->device));
-    size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
-    { int rc = dec_host_staging(e, NBmax, NBmax * (size_t)slotBytes + 16); if (rc) return rc; }
-    CKR(hipMemcpy(e->d_in, h_in, NB * slotBytes, hipMemcpyHostToDevice));
-    int rc = ulcx_decode_dev(e, e->d_in, slotBytes, nBlocks, e->d_pcm, e->d_bits, nullptr);
-    if (rc) return rc;
+extern "C" int ulcx_decode_dev_subset(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
+    return decode_dev_any("ulcx_decode_dev_subset", e, d_in, slotBytes, nBlocks, d_pcm, nullptr, d_bits, hipStream, true, d_slots, n);
+}
+extern "C" int ulcx_decode_dev_pcm16_subset(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_in, int slotBytes, int nBlocks, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    return decode_dev_any("ulcx_decode_dev_pcm16_subset", e, d_in, slotBytes, nBlocks, nullptr, d_pcm16, d_bits, hipStream, true, d_slots, n);
+}
+// waits for the device, then copies the samples and sizes of NB blocks down
+static int dec_results_down(ulcx_decoder *e, const float *d_pcm, const int32_t *d_bits, size_t NB, float *h_pcm, int32_t *h_bits) {
     CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_pcm, d_pcm, sizeof(float) * NB * (size_t)e->C * e->BS, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
-extern "C" int ulcx_decode_block1(ulcx_decoder *e, const uint8_t *h_in, int nBytes, float *h_pcm, int32_t *bits, int32_t *lastSubBlockSize) {
-    return ulcx_decode_block1_rng(e, h_in, nBytes, h_pcm, bits, lastSubBlockSize, nullptr);
+static int decode_host_any(const char *who, ulcx_decoder *e, const uint8_t *h_in, int slotBytes, int nBlocks, float *h_pcm, int32_t *h_bits,
+                           bool subset = false, const int32_t *h_slots = nullptr, int n = 0) {
+    if (dec_args_bad(who, e, h_in, h_pcm, h_bits, nBlocks, 0)) return ULCX_ERR_ARG;
+    if (slotBytes < 1) return refuse(who, "bad argument");
+    if (subset && slots_host_bad(who, h_slots, n, e->B)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    const size_t NBmax = (size_t)e->B * e->maxK, NB = (subset ? (size_t)n : (size_t)e->B) * nBlocks;
+    int rc = dec_host_staging(e, NBmax * (size_t)slotBytes + 16);
+    if (!rc && subset) rc = slots_list_up(e, h_slots, n);
+    if (rc) return rc;
+    CKR(hipMemcpy(e->d_in, h_in, NB * slotBytes, hipMemcpyHostToDevice));
+    rc = decode_dev_any(who, e, e->d_in, slotBytes, nBlocks, e->d_pcm, nullptr, e->d_bits, nullptr, subset, e->subSlots, n);
+    return rc ? rc : dec_results_down(e, e->d_pcm, e->d_bits, NB, h_pcm, h_bits);
 }
+extern "C" int ulcx_decode_host(ulcx_decoder *e, const uint8_t *h_in, int slotBytes, int nBlocks, float *h_pcm, int32_t *h_bits) {
+    return decode_host_any("ulcx_decode_host", e, h_in, slotBytes, nBlocks, h_pcm, h_bits);
+}
+extern "C" int ulcx_decode_host_subset(ulcx_decoder *e, const int32_t *h_slots, int n, const uint8_t *h_in, int slotBytes, int nBlocks, float *h_pcm, int32_t *h_bits) {
+    return decode_host_any("ulcx_decode_host_subset", e, h_in, slotBytes, nBlocks, h_pcm, h_bits, true, h_slots, n);
+}
+
+// One block of one stream per call, as ulcx_encode_block1.
 // rngState: the noise generator's state (ulcDecoder.c:75-81) before the block in, after it out.  The reference keeps it in a
 // function-static word, i.e. ONE state per process that every decoder object draws from; a caller that wants that behaviour
 // (the drop-in of section 1 does) owns the word and hands it through here.  NULL: the state stays with this decoder object.
-extern "C" int ulcx_decode_block1_rng(ulcx_decoder *e, const uint8_t *h_in, int nBytes, float *h_pcm, int32_t *bits, int32_t *lastSubBlockSize, uint32_t *rngState) {
-    if (!e || !h_in || !h_pcm || nBytes < 1 || e->B != 1 || e->maxK != 1) { ulcx_set_error("ulcx_decode_block1: needs a decoder of one stream, one block per call"); return ULCX_ERR_ARG; }
+static int decode_block1_any(const char *who, ulcx_decoder *e, const uint8_t *h_in, int nBytes, float *h_pcm, int32_t *bits, int32_t *lastSubBlockSize, uint32_t *rngState) {
+    if (!e || !h_in || !h_pcm || nBytes < 1 || e->B != 1 || e->maxK != 1) return refuse(who, "needs a decoder of one stream, one block per call");
     CKR(hipSetDevice(e->device));
     const size_t cb = (size_t)e->C * e->BS;
     const int slot = 2 * e->C * e->BS + 16;                       // the largest block
     if (nBytes > slot) nBytes = slot;
     if (!e->b1Init) {
         int rc;
-        if ((rc = dec_host_staging(e, 1, (size_t)slot + 16))) return rc;             // (one stream, one block per call)
+        if ((rc = dec_host_staging(e, (size_t)slot + 16))) return rc;                // (one stream, one block per call)
         if (!e->b1.stream) CKR(hipStreamCreateWithFlags(&e->b1.stream, hipStreamNonBlocking));
         if (!e->pinIn) CKR(hipHostMalloc((void **)&e->pinIn, (size_t)slot, hipHostMallocDefault));
         if (!e->pinPcm) CKR(hipHostMalloc((void **)&e->pinPcm, sizeof(float) * cb, hipHostMallocDefault));
@@ -1128,7 +1208,7 @@ extern "C" int ulcx_decode_block1_rng(ulcx_decoder *e, const uint8_t *h_in, int 
     auto enqueue = [&]() -> int {
         CKR(hipMemcpyAsync(e->d_in, e->pinIn, (size_t)slot, hipMemcpyHostToDevice, e->b1.stream));
         CKR(hipMemcpyAsync(e->ctx.seed, &e->pinMeta[2], sizeof(uint32_t), hipMemcpyHostToDevice, e->b1.stream));
-        int rc = ulcx_decode_dev(e, e->d_in, slot, 1, e->d_pcm, e->d_bits, e->b1.stream);
+        int rc = decode_dev_any(who, e, e->d_in, slot, 1, e->d_pcm, nullptr, e->d_bits, e->b1.stream);
         if (rc) return rc;
         CKR(hipMemcpyAsync(&e->pinMeta[3], e->ctx.seed, sizeof(uint32_t), hipMemcpyDeviceToHost, e->b1.stream));
         CKR(hipMemcpyAsync(e->pinPcm, e->d_pcm, sizeof(float) * cb, hipMemcpyDeviceToHost, e->b1.stream));
@@ -1153,6 +1233,12 @@ extern "C" int ulcx_decode_block1_rng(ulcx_decoder *e, const uint8_t *h_in, int 
     if (rngState) *rngState = e->b1Seed;
     return ULCX_OK;
 }
+extern "C" int ulcx_decode_block1(ulcx_decoder *e, const uint8_t *h_in, int nBytes, float *h_pcm, int32_t *bits, int32_t *lastSubBlockSize) {
+    return decode_block1_any("ulcx_decode_block1", e, h_in, nBytes, h_pcm, bits, lastSubBlockSize, nullptr);
+}
+extern "C" int ulcx_decode_block1_rng(ulcx_decoder *e, const uint8_t *h_in, int nBytes, float *h_pcm, int32_t *bits, int32_t *lastSubBlockSize, uint32_t *rngState) {
+    return decode_block1_any("ulcx_decode_block1_rng", e, h_in, nBytes, h_pcm, bits, lastSubBlockSize, rngState);
+}
 
 // ---------------------------------------------------------------------------
 // .ulc container + packed streams (tools/ulc_Helper.h:10-20, ulcEncodeTool.c:92-100,160-195, ulcDecodeTool.c:73-80,123-166)
@@ -1167,11 +1253,11 @@ extern "C" void ulcx_ulc_header_pack(uint8_t dst[24], const ulcx_file_header *h)
     put16(dst + 0x12, h->RateKbps); put32(dst + 0x14, h->StreamOffs);
 }
 extern "C" int ulcx_ulc_header_parse(ulcx_file_header *h, const uint8_t *src, size_t len) {
-    if (!h || !src || len < 24) { ulcx_set_error("ulc header: need 24 bytes"); return ULCX_ERR_ARG; }
+    if (!h || !src || len < 24) return refuse("ulcx_ulc_header_parse", "need 24 bytes");
     h->Magic = get32(src); h->BlockSize = (uint16_t)get16(src + 4); h->MaxBlockSize = (uint16_t)get16(src + 6);
     h->nBlocks = get32(src + 8); h->RateHz = get32(src + 12); h->nChan = (uint16_t)get16(src + 16);
     h->RateKbps = (uint16_t)get16(src + 18); h->StreamOffs = get32(src + 20);
-    if (h->Magic != ULCX_ULC_MAGIC) { ulcx_set_error("not a ULC2 container"); return ULCX_ERR_ARG; }   /* ulcDecodeTool.c:77-80 */
+    if (h->Magic != ULCX_ULC_MAGIC) return refuse("ulcx_ulc_header_parse", "not a ULC2 container");   /* ulcDecodeTool.c:77-80 */
     return ULCX_OK;
 }
 extern "C" int ulcx_ulc_rate_kbps(uint64_t totalBytes, uint32_t RateHz, uint32_t BlockSize, uint32_t nBlocks) {
@@ -1183,15 +1269,16 @@ extern "C" int ulcx_pack_streams_dev(int device, int nStreams, int nBlocks, int 
     if (nStreams < 1 || nBlocks < 1 || slotBytes < 1 || !d_slots || !d_bits || !d_payload || !d_payloadBytes || payloadStride < 1) { ulcx_set_error("ulcx_pack_streams_dev: bad argument"); return ULCX_ERR_ARG; }
     if (misaligned("ulcx_pack_streams_dev", "d_bits", d_bits, ULCX_ALIGN_WORD) || misaligned("ulcx_pack_streams_dev", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) ||
         misaligned("ulcx_pack_streams_dev", "d_maxBlock", d_maxBlock, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
-    int rc = select_device(device);
+    int rc = select_device("ulcx_pack_streams_dev", device);
     if (rc) return rc;
     return ulcx_pack_launch(nStreams, nBlocks, slotBytes, d_slots, d_bits, d_payload, payloadStride, d_payloadBytes, d_maxBlock, (hipStream_t)hipStream);
 }
-extern "C" int ulcx_decode_packed_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
-                                      int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
-    if (!e || !d_payload || !d_payloadBytes || !d_pcm || !d_bits || payloadStride < 1 || nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("ulcx_decode_packed_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (misaligned("ulcx_decode_packed_dev", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned("ulcx_decode_packed_dev", "d_pcm", d_pcm, ULCX_ALIGN_PCM) ||
-        misaligned("ulcx_decode_packed_dev", "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+static int decode_packed_any(const char *who, ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                             int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
+    if (dec_args_bad(who, e, d_payload, d_pcm, d_bits, nBlocks, 0)) return ULCX_ERR_ARG;
+    if (!d_payloadBytes || payloadStride < 1) return refuse(who, "bad argument");
+    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) ||
+        misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.K = nBlocks; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = nullptr; c.bits = d_bits;
@@ -1201,100 +1288,106 @@ extern "C" int ulcx_decode_packed_dev(ulcx_decoder *e, const uint8_t *d_payload,
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     return rc;
 }
+extern "C" int ulcx_decode_packed_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                      int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
+    return decode_packed_any("ulcx_decode_packed_dev", e, d_payload, payloadStride, d_payloadBytes, nBlocks, d_pcm, d_bits, hipStream);
+}
+// the payloads and their sizes of a host-pointer call, into buffers of the call's own (zeroed: `pad` bytes behind the last payload)
+static int payload_up(ulcx_decoder *e, DevTmp &t, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes, size_t pad, uint8_t **dp, int32_t **dn) {
+    const size_t bytes = (size_t)e->B * (size_t)payloadStride;
+    CKR(t.get(dp, bytes + pad)); CKR(t.get(dn, sizeof(int32_t) * e->B));
+    if (pad) CKR(hipMemset(*dp, 0, bytes + pad));
+    CKR(hipMemcpy(*dp, h_payload, bytes, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(*dn, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    return ULCX_OK;
+}
 extern "C" int ulcx_decode_packed_host(ulcx_decoder *e, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
                                        int nBlocks, float *h_pcm, int32_t *h_bits) {
-    if (!e || !h_payload || !h_payloadBytes || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK || payloadStride < 1) return ULCX_ERR_ARG;
+    const char *who = "ulcx_decode_packed_host";
+    if (dec_args_bad(who, e, h_payload, h_pcm, h_bits, nBlocks, 0)) return ULCX_ERR_ARG;
+    if (!h_payloadBytes || payloadStride < 1) return refuse(who, "bad argument");
     CKR(hipSetDevice(e->device));
-    size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
-    uint8_t *dp = nullptr; int32_t *dn = nullptr; float *dpcm = nullptr; int32_t *dbits = nullptr;
-    size_t payBytes = (size_t)e->B * (size_t)payloadStride + 16;
-    CKR(hipMalloc((void **)&dp, payBytes)); CKR(hipMalloc((void **)&dn, sizeof(int32_t) * e->B));
-    CKR(hipMalloc((void **)&dpcm, sizeof(float) * NB * cb)); CKR(hipMalloc((void **)&dbits, sizeof(int32_t) * NB));
-    CKR(hipMemset(dp, 0, payBytes));
-    CKR(hipMemcpy(dp, h_payload, (size_t)e->B * (size_t)payloadStride, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(dn, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
-    int rc = ulcx_decode_packed_dev(e, dp, payloadStride, dn, nBlocks, dpcm, dbits, nullptr);
-    if (rc == ULCX_OK) {
-        CKR(hipDeviceSynchronize());
-        CKR(hipMemcpy(h_pcm, dpcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
-        CKR(hipMemcpy(h_bits, dbits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    }
-    hipFree(dp); hipFree(dn); hipFree(dpcm); hipFree(dbits);
-    return rc;
+    const size_t NB = (size_t)e->B * nBlocks;
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dbits = nullptr; float *dpcm = nullptr;
+    int rc = payload_up(e, t, h_payload, payloadStride, h_payloadBytes, 16, &dp, &dn);
+    if (rc) return rc;
+    CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
+    rc = decode_packed_any(who, e, dp, payloadStride, dn, nBlocks, dpcm, dbits, nullptr);
+    return rc ? rc : dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
 }
 
 // Whole files: the payloads go to the device once, every later call decodes the next nBlocks of every stream from there
 // (ulcx_decode_packed_host re-uploads everything per call: fine for one call, quadratic over a long file).
+// A failed upload leaves the object without a payload (and without the index of the one before: it belongs to its payload).
 extern "C" int ulcx_decoder_upload_payload(ulcx_decoder *e, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes) {
-    if (!e || !h_payload || !h_payloadBytes || payloadStride < 1) return ULCX_ERR_ARG;
+    if (!e || !h_payload || !h_payloadBytes || payloadStride < 1) return refuse("ulcx_decoder_upload_payload", "bad argument");
     CKR(hipSetDevice(e->device));
-    if (e->d_pay) { hipFree(e->d_pay); e->d_pay = nullptr; }
-    if (e->d_payBytes) { hipFree(e->d_payBytes); e->d_payBytes = nullptr; }
-    if (e->d_index) { hipFree(e->d_index); e->d_index = nullptr; e->idxStride = 0; }      // (the index belongs to the payload it was built from)
-    size_t bytes = (size_t)e->B * (size_t)payloadStride;
-    CKR(hipMalloc((void **)&e->d_pay, bytes + 16)); CKR(hipMalloc((void **)&e->d_payBytes, sizeof(int32_t) * e->B));
-    CKR(hipMemset(e->d_pay, 0, bytes + 16));
-    CKR(hipMemcpy(e->d_pay, h_payload, bytes, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(e->d_payBytes, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    dfree(e->allocs, &e->d_index); e->idxStride = 0;
+    const size_t bytes = (size_t)e->B * (size_t)payloadStride;
+    int rc = dregrow(e->allocs, &e->d_pay, bytes + 16, true);
+    if (!rc) rc = dregrow(e->allocs, &e->d_payBytes, (size_t)e->B, false);
+    if (!rc && (hipMemcpy(e->d_pay, h_payload, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(e->d_payBytes, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice) != hipSuccess)) {
+        ulcx_set_error("ulcx_decoder_upload_payload: hipMemcpy: %s", hipGetErrorString(hipGetLastError()));
+        rc = ULCX_ERR_HIP;
+    }
+    if (rc) { dfree(e->allocs, &e->d_pay); return rc; }
     e->payStride = payloadStride;
     return ulcx_decoder_reset(e);
 }
 extern "C" int ulcx_decode_resident_host(ulcx_decoder *e, int nBlocks, float *h_pcm, int32_t *h_bits) {
-    if (!e || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK) return ULCX_ERR_ARG;
-    if (!e->d_pay) { ulcx_set_error("ulcx_decode_resident_host: no payload uploaded"); return ULCX_ERR_ARG; }
+    const char *who = "ulcx_decode_resident_host";
+    if (!e || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK) return refuse(who, "bad argument");
+    if (!e->d_pay) return refuse(who, "no payload uploaded");
     CKR(hipSetDevice(e->device));
-    size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
-    { int rc0 = dec_host_staging(e, (size_t)e->B * e->maxK, 0); if (rc0) return rc0; }
-    int rc = ulcx_decode_packed_dev(e, e->d_pay, e->payStride, e->d_payBytes, nBlocks, e->d_pcm, e->d_bits, nullptr);
-    if (rc != ULCX_OK) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
+    int rc = dec_host_staging(e, 0);
+    if (!rc) rc = decode_packed_any(who, e, e->d_pay, e->payStride, e->d_payBytes, nBlocks, e->d_pcm, e->d_bits, nullptr);
+    return rc ? rc : dec_results_down(e, e->d_pcm, e->d_bits, (size_t)e->B * nBlocks, h_pcm, h_bits);
 }
 
 // ---------------------------------------------------------------------------
 // Block index and range decode (include/ulc_amd.h section 3)
 // ---------------------------------------------------------------------------
-extern "C" int ulcx_index_packed_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
-                                     int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
-    if (!e || !d_payload || !d_payloadBytes || !d_index || !d_nBlocks || payloadStride < 1 || maxBlocks < 1) { ulcx_set_error("ulcx_index_packed_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (misaligned("ulcx_index_packed_dev", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned("ulcx_index_packed_dev", "d_index", d_index, ULCX_ALIGN_WORD) ||
-        misaligned("ulcx_index_packed_dev", "d_nBlocks", d_nBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+static int index_packed_any(const char *who, ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                            int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
+    if (!e || !d_payload || !d_payloadBytes || !d_index || !d_nBlocks || payloadStride < 1 || maxBlocks < 1) return refuse(who, "bad argument");
+    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_nBlocks", d_nBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.in = d_payload; c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
     c.inBytes = (long long)e->B * payloadStride;
     return ulcx_index_launch(c, maxBlocks, d_index, d_nBlocks, (hipStream_t)hipStream);
 }
-// device buffers of a host-pointer call, freed when it returns
-namespace { struct DevTmp { std::vector<void *> v; ~DevTmp() { for (void *p : v) hipFree(p); } template <typename T> hipError_t get(T **p, size_t bytes) { void *q = nullptr; hipError_t r = hipMalloc(&q, bytes ? bytes : 16); if (r == hipSuccess) v.push_back(q); *p = (T *)q; return r; } }; }
+extern "C" int ulcx_index_packed_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                     int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
+    return index_packed_any("ulcx_index_packed_dev", e, d_payload, payloadStride, d_payloadBytes, maxBlocks, d_index, d_nBlocks, hipStream);
+}
 extern "C" int ulcx_index_packed_host(ulcx_decoder *e, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
                                       int maxBlocks, ulcx_index_entry *h_index, int32_t *h_nBlocks) {
-    if (!e || !h_payload || !h_payloadBytes || !h_index || !h_nBlocks || payloadStride < 1 || maxBlocks < 1) { ulcx_set_error("ulcx_index_packed_host: bad argument"); return ULCX_ERR_ARG; }
+    const char *who = "ulcx_index_packed_host";
+    if (!e || !h_payload || !h_payloadBytes || !h_index || !h_nBlocks || payloadStride < 1 || maxBlocks < 1) return refuse(who, "bad argument");
     CKR(hipSetDevice(e->device));
     DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr; ulcx_index_entry *di = nullptr;
-    const size_t bytes = (size_t)e->B * (size_t)payloadStride, nEnt = (size_t)e->B * ((size_t)maxBlocks + 1);
-    CKR(t.get(&dp, bytes)); CKR(t.get(&dn, sizeof(int32_t) * e->B)); CKR(t.get(&dcnt, sizeof(int32_t) * e->B)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
-    CKR(hipMemcpy(dp, h_payload, bytes, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(dn, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
-    int rc = ulcx_index_packed_dev(e, dp, payloadStride, dn, maxBlocks, di, dcnt, nullptr);
+    const size_t nEnt = (size_t)e->B * ((size_t)maxBlocks + 1);
+    int rc = payload_up(e, t, h_payload, payloadStride, h_payloadBytes, 0, &dp, &dn);
     if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * e->B)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    if ((rc = index_packed_any(who, e, dp, payloadStride, dn, maxBlocks, di, dcnt, nullptr))) return rc;
     CKR(hipDeviceSynchronize());
     CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * nEnt, hipMemcpyDeviceToHost));
     CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * e->B, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
-static int decode_range_any(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+static int decode_range_any(const char *who, ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                             const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const int32_t *d_first, int nBlocks,
                             float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    // (the block in front of a range takes one row of the per-block scratch: nBlocks <= maxBlocksPerCall - 1)
-    if (!e || !d_payload || !d_payloadBytes || !d_index || !d_indexBlocks || !d_first || (!d_pcm && !d_pcm16) || !d_bits ||
-        payloadStride < 1 || indexStride < 1 || nBlocks < 1 || nBlocks > e->maxK - 1) { ulcx_set_error("ulcx_decode_range: bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return ULCX_ERR_ARG; }
-    if (misaligned("ulcx_decode_range", "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned("ulcx_decode_range", "d_index", d_index, ULCX_ALIGN_WORD) ||
-        misaligned("ulcx_decode_range", "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned("ulcx_decode_range", "d_first", d_first, ULCX_ALIGN_WORD) ||
-        misaligned("ulcx_decode_range", "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned("ulcx_decode_range", "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
-        misaligned("ulcx_decode_range", "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    if (dec_args_bad(who, e, d_payload, d_pcm ? (const void *)d_pcm : d_pcm16, d_bits, nBlocks, 1)) return ULCX_ERR_ARG;
+    if (!d_payloadBytes || !d_index || !d_indexBlocks || !d_first || payloadStride < 1 || indexStride < 1) return refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)");
+    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_first", d_first, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
     c.K = nBlocks + 1; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = d_pcm16;
@@ -1309,50 +1402,47 @@ static int decode_range_any(ulcx_decoder *e, const uint8_t *d_payload, long long
 extern "C" int ulcx_decode_range_dev(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                                      const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const int32_t *d_first, int nBlocks,
                                      float *d_pcm, int32_t *d_bits, void *hipStream) {
-    if (!d_pcm) { ulcx_set_error("ulcx_decode_range_dev: bad argument"); return ULCX_ERR_ARG; }
-    return decode_range_any(e, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_first, nBlocks, d_pcm, nullptr, d_bits, hipStream);
+    return decode_range_any("ulcx_decode_range_dev", e, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_first, nBlocks, d_pcm, nullptr, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_range_dev_pcm16(ulcx_decoder *e, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                                            const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const int32_t *d_first, int nBlocks,
                                            int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    if (!d_pcm16) { ulcx_set_error("ulcx_decode_range_dev_pcm16: bad argument"); return ULCX_ERR_ARG; }
-    return decode_range_any(e, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_first, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
+    return decode_range_any("ulcx_decode_range_dev_pcm16", e, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_first, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
 }
-static int range_first_ok(const ulcx_decoder *e, const int32_t *h_first, const char *who) {
-    for (int s = 0; s < e->B; s++) if (h_first[s] < 0) { ulcx_set_error("%s: stream %d starts at block %d", who, s, (int)h_first[s]); return 0; }
-    return 1;
+// the range starts of a host form: none negative (what the device forms cannot refuse)
+static int range_first_bad(const char *who, const ulcx_decoder *e, const int32_t *h_first) {
+    for (int s = 0; s < e->B; s++) if (h_first[s] < 0) { refuse(who, "stream %d starts at block %d", s, (int)h_first[s]); return 1; }
+    return 0;
 }
 extern "C" int ulcx_decode_range_host(ulcx_decoder *e, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
                                       const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks, const int32_t *h_first, int nBlocks,
                                       float *h_pcm, int32_t *h_bits) {
-    if (!e || !h_payload || !h_payloadBytes || !h_index || !h_indexBlocks || !h_first || !h_pcm || !h_bits ||
-        payloadStride < 1 || indexStride < 1 || nBlocks < 1 || nBlocks > e->maxK - 1) { ulcx_set_error("ulcx_decode_range_host: bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return ULCX_ERR_ARG; }
-    if (!range_first_ok(e, h_first, "ulcx_decode_range_host")) return ULCX_ERR_ARG;
+    const char *who = "ulcx_decode_range_host";
+    if (dec_args_bad(who, e, h_payload, h_pcm, h_bits, nBlocks, 1)) return ULCX_ERR_ARG;
+    if (!h_payloadBytes || !h_index || !h_indexBlocks || !h_first || payloadStride < 1 || indexStride < 1) return refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)");
+    if (range_first_bad(who, e, h_first)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    const size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks, bytes = (size_t)e->B * (size_t)payloadStride, nEnt = (size_t)e->B * (size_t)indexStride;
+    const size_t NB = (size_t)e->B * nBlocks, nEnt = (size_t)e->B * (size_t)indexStride;
     DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr, *df = nullptr, *dbits = nullptr; ulcx_index_entry *di = nullptr; float *dpcm = nullptr;
-    CKR(t.get(&dp, bytes)); CKR(t.get(&dn, sizeof(int32_t) * e->B)); CKR(t.get(&dcnt, sizeof(int32_t) * e->B)); CKR(t.get(&df, sizeof(int32_t) * e->B));
-    CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt)); CKR(t.get(&dpcm, sizeof(float) * NB * cb)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
-    CKR(hipMemcpy(dp, h_payload, bytes, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(dn, h_payloadBytes, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    int rc = payload_up(e, t, h_payload, payloadStride, h_payloadBytes, 0, &dp, &dn);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * e->B)); CKR(t.get(&df, sizeof(int32_t) * e->B));
+    CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt)); CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
     CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
     CKR(hipMemcpy(df, h_first, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
     CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
-    int rc = ulcx_decode_range_dev(e, dp, payloadStride, dn, di, indexStride, dcnt, df, nBlocks, dpcm, dbits, nullptr);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_pcm, dpcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, dbits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
+    rc = decode_range_any(who, e, dp, payloadStride, dn, di, indexStride, dcnt, df, nBlocks, dpcm, nullptr, dbits, nullptr);
+    return rc ? rc : dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
 }
 extern "C" int ulcx_decoder_index_resident(ulcx_decoder *e, int maxBlocks, int32_t *h_nBlocks) {
-    if (!e || maxBlocks < 1) { ulcx_set_error("ulcx_decoder_index_resident: bad argument"); return ULCX_ERR_ARG; }
-    if (!e->d_pay) { ulcx_set_error("ulcx_decoder_index_resident: no payload uploaded"); return ULCX_ERR_ARG; }
+    const char *who = "ulcx_decoder_index_resident";
+    if (!e || maxBlocks < 1) return refuse(who, "bad argument");
+    if (!e->d_pay) return refuse(who, "no payload uploaded");
     CKR(hipSetDevice(e->device));
-    if (e->d_index) { hipFree(e->d_index); e->d_index = nullptr; e->idxStride = 0; }
-    CKR(hipMalloc((void **)&e->d_index, sizeof(ulcx_index_entry) * (size_t)e->B * ((size_t)maxBlocks + 1)));
-    if (!e->d_idxBlocks) CKR(hipMalloc((void **)&e->d_idxBlocks, sizeof(int32_t) * e->B));
-    int rc = ulcx_index_packed_dev(e, e->d_pay, e->payStride, e->d_payBytes, maxBlocks, e->d_index, e->d_idxBlocks, nullptr);
+    e->idxStride = 0;
+    int rc = dregrow(e->allocs, &e->d_index, (size_t)e->B * ((size_t)maxBlocks + 1), false);
+    if (!rc && !e->d_idxBlocks) rc = dalloc(e->allocs, &e->d_idxBlocks, (size_t)e->B, false);
+    if (!rc) rc = index_packed_any(who, e, e->d_pay, e->payStride, e->d_payBytes, maxBlocks, e->d_index, e->d_idxBlocks, nullptr);
     if (rc) return rc;
     CKR(hipDeviceSynchronize());
     e->idxStride = maxBlocks + 1;
@@ -1360,210 +1450,103 @@ extern "C" int ulcx_decoder_index_resident(ulcx_decoder *e, int maxBlocks, int32
     return ULCX_OK;
 }
 extern "C" int ulcx_decode_resident_range_host(ulcx_decoder *e, const int32_t *h_first, int nBlocks, float *h_pcm, int32_t *h_bits) {
-    if (!e || !h_first || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK - 1) { ulcx_set_error("ulcx_decode_resident_range_host: bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return ULCX_ERR_ARG; }
-    if (!e->d_pay || !e->idxStride) { ulcx_set_error("ulcx_decode_resident_range_host: no payload uploaded, or not indexed (ulcx_decoder_index_resident)"); return ULCX_ERR_ARG; }
-    if (!range_first_ok(e, h_first, "ulcx_decode_resident_range_host")) return ULCX_ERR_ARG;
+    const char *who = "ulcx_decode_resident_range_host";
+    if (dec_args_bad(who, e, h_first, h_pcm, h_bits, nBlocks, 1)) return ULCX_ERR_ARG;
+    if (!e->d_pay || !e->idxStride) return refuse(who, "no payload uploaded, or not indexed (ulcx_decoder_index_resident)");
+    if (range_first_bad(who, e, h_first)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    const size_t cb = (size_t)e->C * e->BS, NB = (size_t)e->B * nBlocks;
-    { int rc0 = dec_host_staging(e, (size_t)e->B * e->maxK, 0); if (rc0) return rc0; }
-    if (!e->d_first) { int rc0 = dalloc(e->allocs, &e->d_first, (size_t)e->B, true); if (rc0) return rc0; }
+    int rc = dec_host_staging(e, 0);
+    if (!rc && !e->d_first) rc = dalloc(e->allocs, &e->d_first, (size_t)e->B, true);
+    if (rc) return rc;
     CKR(hipMemcpy(e->d_first, h_first, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
-    int rc = ulcx_decode_range_dev(e, e->d_pay, e->payStride, e->d_payBytes, e->d_index, e->idxStride, e->d_idxBlocks, e->d_first, nBlocks, e->d_pcm, e->d_bits, nullptr);
-    if (rc != ULCX_OK) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
+    rc = decode_range_any(who, e, e->d_pay, e->payStride, e->d_payBytes, e->d_index, e->idxStride, e->d_idxBlocks, e->d_first, nBlocks, e->d_pcm, nullptr, e->d_bits, nullptr);
+    return rc ? rc : dec_results_down(e, e->d_pcm, e->d_bits, (size_t)e->B * nBlocks, h_pcm, h_bits);
 }
 
 // ---------------------------------------------------------------------------
-// Stream slots (include/ulc_amd.h): per-stream reset, save / load, subset calls.  The copies are ulcx_slots.hip's.
+// Stream slots (include/ulc_amd.h): per-stream reset, save / load.  The copies are ulcx_slots.hip's; what they work on comes
+// from the slot_* overloads of the object's type.  (The subset calls are with their families above.)
 // ---------------------------------------------------------------------------
-extern "C" int ulcx_encoder_reset_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, void *hipStream) {
-    if (!e) { ulcx_set_error("ulcx_encoder_reset_streams_dev: no encoder"); return ULCX_ERR_ARG; }
-    if (slots_list_bad("ulcx_encoder_reset_streams_dev", d_slots, n, e->B)) return ULCX_ERR_ARG;
+template <class OBJ> static int slots_reset_dev(const char *who, OBJ *e, const int32_t *d_slots, int n, void *hipStream) {
+    if (!e) return refuse(who, "no object");
+    if (slots_list_bad(who, d_slots, n, e->B)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    return ulcx_slots_reset(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), d_slots, n, enc_slot_geom(e, false), (hipStream_t)hipStream);
+    slot_touch(e);
+    return ulcx_slots_reset(slot_obj_rows(e), d_slots, n, slot_geom(e, false), (hipStream_t)hipStream);
 }
-extern "C" int ulcx_encoder_save_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, uint8_t *d_state, void *hipStream) {
-    if (!e || !d_state) { ulcx_set_error("ulcx_encoder_save_streams_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_list_bad("ulcx_encoder_save_streams_dev", d_slots, n, e->B) || misaligned("ulcx_encoder_save_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
+template <class OBJ> static int slots_save_dev(const char *who, OBJ *e, const int32_t *d_slots, int n, uint8_t *d_state, void *hipStream) {
+    if (!e || !d_state) return refuse(who, "bad argument");
+    if (slots_list_bad(who, d_slots, n, e->B) || misaligned(who, "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    return ulcx_slots_gather(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_record_rows(e, d_state), d_slots, n, enc_slot_geom(e, true), (hipStream_t)hipStream);
+    return ulcx_slots_gather(slot_obj_rows(e), slot_record_rows(e, d_state), d_slots, n, slot_geom(e, true), (hipStream_t)hipStream);
 }
-extern "C" int ulcx_encoder_load_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, const uint8_t *d_state, void *hipStream) {
-    if (!e || !d_state) { ulcx_set_error("ulcx_encoder_load_streams_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_list_bad("ulcx_encoder_load_streams_dev", d_slots, n, e->B) || misaligned("ulcx_encoder_load_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
+template <class OBJ> static int slots_load_dev(const char *who, OBJ *e, const int32_t *d_slots, int n, const uint8_t *d_state, void *hipStream) {
+    if (!e || !d_state) return refuse(who, "bad argument");
+    if (slots_list_bad(who, d_slots, n, e->B) || misaligned(who, "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    return ulcx_slots_scatter(enc_slot_rows(e, e->ctx.hist, e->ctx.wcs), enc_record_rows(e, (uint8_t *)d_state), d_slots, n, enc_slot_geom(e, true), (hipStream_t)hipStream);
+    slot_touch(e);
+    return ulcx_slots_scatter(slot_obj_rows(e), slot_record_rows(e, (uint8_t *)d_state), d_slots, n, slot_geom(e, true), (hipStream_t)hipStream);
 }
-// (reset and load change the generator word behind the single-block path's host copy, as a batched decode call does: b1Seed)
-extern "C" int ulcx_decoder_reset_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, void *hipStream) {
-    if (!e) { ulcx_set_error("ulcx_decoder_reset_streams_dev: no decoder"); return ULCX_ERR_ARG; }
-    if (slots_list_bad("ulcx_decoder_reset_streams_dev", d_slots, n, e->B)) return ULCX_ERR_ARG;
-    CKR(hipSetDevice(e->device));
-    if (!e->inBlock1) e->b1SeedStale = true;
-    return ulcx_slots_reset(dec_obj_rows(e), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
-}
-extern "C" int ulcx_decoder_save_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, uint8_t *d_state, void *hipStream) {
-    if (!e || !d_state) { ulcx_set_error("ulcx_decoder_save_streams_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_list_bad("ulcx_decoder_save_streams_dev", d_slots, n, e->B) || misaligned("ulcx_decoder_save_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
-    CKR(hipSetDevice(e->device));
-    return ulcx_slots_gather(dec_obj_rows(e), dec_record_rows(e, d_state), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
-}
-extern "C" int ulcx_decoder_load_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_state, void *hipStream) {
-    if (!e || !d_state) { ulcx_set_error("ulcx_decoder_load_streams_dev: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_list_bad("ulcx_decoder_load_streams_dev", d_slots, n, e->B) || misaligned("ulcx_decoder_load_streams_dev", "d_state", d_state, ULCX_ALIGN_STATE)) return ULCX_ERR_ARG;
-    CKR(hipSetDevice(e->device));
-    if (!e->inBlock1) e->b1SeedStale = true;
-    return ulcx_slots_scatter(dec_obj_rows(e), dec_record_rows(e, (uint8_t *)d_state), d_slots, n, dec_slot_geom(e), (hipStream_t)hipStream);
-}
-
-extern "C" int ulcx_encode_dev_subset(ulcx_encoder *e, const int32_t *d_slots, int n, int mode, float p0, float p1, const ulcx_rate *d_rate, const float *d_pcm, int nBlocks,
-                                      uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!e || !d_slots || !d_pcm) { ulcx_set_error("ulcx_encode_dev_subset: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, mode, p0, p1, d_rate, d_pcm, nullptr, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream, d_slots, n);
-}
-extern "C" int ulcx_encode_dev_pcm16_subset(ulcx_encoder *e, const int32_t *d_slots, int n, int mode, float p0, float p1, const ulcx_rate *d_rate, const int16_t *d_pcm16, int nBlocks,
-                                            uint8_t *d_out, int32_t *d_bits, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!e || !d_slots || !d_pcm16) { ulcx_set_error("ulcx_encode_dev_pcm16_subset: bad argument"); return ULCX_ERR_ARG; }
-    return encode_dev_any(e, mode, p0, p1, d_rate, nullptr, d_pcm16, nBlocks, d_out, d_bits, d_wc, d_cplx, hipStream, d_slots, n);
-}
-extern "C" int ulcx_analyse_dev_subset(ulcx_encoder *e, const int32_t *d_slots, int n, const float *d_pcm, int nBlocks, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    if (!e || !d_slots || !d_pcm) { ulcx_set_error("ulcx_analyse_dev_subset: bad argument"); return ULCX_ERR_ARG; }
-    return analyse_dev_any(e, d_pcm, nullptr, nBlocks, d_wc, d_cplx, hipStream, d_slots, n);
-}
-extern "C" int ulcx_decode_dev_subset(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_in, int slotBytes, int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream) {
-    if (!e || !d_slots || !d_pcm) { ulcx_set_error("ulcx_decode_dev_subset: bad argument"); return ULCX_ERR_ARG; }
-    return decode_dev_any(e, d_in, slotBytes, nBlocks, d_pcm, nullptr, d_bits, hipStream, d_slots, n);
-}
-extern "C" int ulcx_decode_dev_pcm16_subset(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_in, int slotBytes, int nBlocks, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    if (!e || !d_slots || !d_pcm16) { ulcx_set_error("ulcx_decode_dev_pcm16_subset: bad argument"); return ULCX_ERR_ARG; }
-    return decode_dev_any(e, d_in, slotBytes, nBlocks, nullptr, d_pcm16, d_bits, hipStream, d_slots, n);
-}
-
-// host forms: the checked list to the device, the _dev form on the null stream, one synchronisation
-template <class OBJ> static int slots_list_up(OBJ *e, const int32_t *h_slots, int n) {
-    if (!e->subSlots) { int rc = dalloc(e->allocs, &e->subSlots, (size_t)e->B, false); if (rc) return rc; }
-    CKR(hipMemcpy(e->subSlots, h_slots, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-    return ULCX_OK;
-}
-extern "C" int ulcx_encoder_reset_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n) {
-    if (!e) { ulcx_set_error("ulcx_encoder_reset_streams_host: no encoder"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_encoder_reset_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+// host forms: the checked list to the device, the _dev form on the null stream, one synchronisation; save / load: the records
+// through a device buffer of the call's own
+template <class OBJ> static int slots_reset_host(const char *who, OBJ *e, const int32_t *h_slots, int n) {
+    if (!e) return refuse(who, "no object");
+    if (slots_host_bad(who, h_slots, n, e->B)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     int rc = slots_list_up(e, h_slots, n);
-    if (!rc) rc = ulcx_encoder_reset_streams_dev(e, e->subSlots, n, nullptr);
+    if (!rc) rc = slots_reset_dev(who, e, e->subSlots, n, nullptr);
     if (rc) return rc;
     CKR(hipDeviceSynchronize());
     return ULCX_OK;
 }
-extern "C" int ulcx_decoder_reset_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n) {
-    if (!e) { ulcx_set_error("ulcx_decoder_reset_streams_host: no decoder"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_decoder_reset_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
+template <class OBJ> static int slots_save_host(const char *who, OBJ *e, const int32_t *h_slots, int n, uint8_t *h_state) {
+    if (!e || !h_state) return refuse(who, "bad argument");
+    if (slots_host_bad(who, h_slots, n, e->B)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    int rc = slots_list_up(e, h_slots, n);
-    if (!rc) rc = ulcx_decoder_reset_streams_dev(e, e->subSlots, n, nullptr);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    return ULCX_OK;
-}
-// save / load of either kind: records through a device buffer of the call's own
-template <class OBJ, class DEVFN> static int slots_save_host(OBJ *e, const int32_t *h_slots, int n, uint8_t *h_state, size_t bytes, DEVFN devForm) {
-    CKR(hipSetDevice(e->device));
+    const size_t bytes = (size_t)n * slot_state_bytes(e);
     DevTmp t; uint8_t *ds = nullptr;
-    CKR(t.get(&ds, (size_t)n * bytes));
+    CKR(t.get(&ds, bytes));
     int rc = slots_list_up(e, h_slots, n);
-    if (!rc) rc = devForm(e, e->subSlots, n, ds, nullptr);
+    if (!rc) rc = slots_save_dev(who, e, e->subSlots, n, ds, nullptr);
     if (rc) return rc;
     CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_state, ds, (size_t)n * bytes, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_state, ds, bytes, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
-template <class OBJ, class DEVFN> static int slots_load_host(OBJ *e, const int32_t *h_slots, int n, const uint8_t *h_state, size_t bytes, DEVFN devForm) {
+template <class OBJ> static int slots_load_host(const char *who, OBJ *e, const int32_t *h_slots, int n, const uint8_t *h_state) {
+    if (!e || !h_state) return refuse(who, "bad argument");
+    if (slots_host_bad(who, h_slots, n, e->B)) return ULCX_ERR_ARG;
+    if (record_headers_bad(who, h_state, n, slot_state_bytes(e), slot_geom(e, true).header)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
+    const size_t bytes = (size_t)n * slot_state_bytes(e);
     DevTmp t; uint8_t *ds = nullptr;
-    CKR(t.get(&ds, (size_t)n * bytes));
-    CKR(hipMemcpy(ds, h_state, (size_t)n * bytes, hipMemcpyHostToDevice));
+    CKR(t.get(&ds, bytes));
+    CKR(hipMemcpy(ds, h_state, bytes, hipMemcpyHostToDevice));
     int rc = slots_list_up(e, h_slots, n);
-    if (!rc) rc = devForm(e, e->subSlots, n, ds, nullptr);
+    if (!rc) rc = slots_load_dev(who, e, e->subSlots, n, ds, nullptr);
     if (rc) return rc;
     CKR(hipDeviceSynchronize());
     return ULCX_OK;
 }
-extern "C" int ulcx_encoder_save_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n, uint8_t *h_state) {
-    if (!e || !h_state) { ulcx_set_error("ulcx_encoder_save_streams_host: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_encoder_save_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
-    return slots_save_host(e, h_slots, n, h_state, ulcx_encoder_stream_state_bytes(e), ulcx_encoder_save_streams_dev);
-}
-extern "C" int ulcx_encoder_load_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n, const uint8_t *h_state) {
-    if (!e || !h_state) { ulcx_set_error("ulcx_encoder_load_streams_host: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_encoder_load_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
-    if (record_headers_bad("ulcx_encoder_load_streams_host", h_state, n, ulcx_encoder_stream_state_bytes(e), enc_slot_geom(e, true).header)) return ULCX_ERR_ARG;
-    return slots_load_host(e, h_slots, n, h_state, ulcx_encoder_stream_state_bytes(e), ulcx_encoder_load_streams_dev);
-}
-extern "C" int ulcx_decoder_save_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n, uint8_t *h_state) {
-    if (!e || !h_state) { ulcx_set_error("ulcx_decoder_save_streams_host: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_decoder_save_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
-    return slots_save_host(e, h_slots, n, h_state, ulcx_decoder_stream_state_bytes(e), ulcx_decoder_save_streams_dev);
-}
-extern "C" int ulcx_decoder_load_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n, const uint8_t *h_state) {
-    if (!e || !h_state) { ulcx_set_error("ulcx_decoder_load_streams_host: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_decoder_load_streams_host", h_slots, n, e->B)) return ULCX_ERR_ARG;
-    if (record_headers_bad("ulcx_decoder_load_streams_host", h_state, n, ulcx_decoder_stream_state_bytes(e), dec_slot_geom(e).header)) return ULCX_ERR_ARG;
-    return slots_load_host(e, h_slots, n, h_state, ulcx_decoder_stream_state_bytes(e), ulcx_decoder_load_streams_dev);
-}
-extern "C" int ulcx_encode_host_subset(ulcx_encoder *e, const int32_t *h_slots, int n, int mode, float p0, float p1, const ulcx_rate *h_rate, const float *h_pcm, int nBlocks,
-                                       uint8_t *h_out, int32_t *h_bits, int32_t *h_wc, float *h_cplx) {
-    if (!e || !h_pcm || !h_out || !h_bits) { ulcx_set_error("ulcx_encode_host_subset: bad argument"); return ULCX_ERR_ARG; }
-    if (nBlocks < 1 || nBlocks > e->maxK) { ulcx_set_error("nBlocks out of range"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_encode_host_subset", h_slots, n, e->B)) return ULCX_ERR_ARG;
-    if (!h_rate && mode != ULCX_MODE_VBR && mode != ULCX_MODE_CBR && mode != ULCX_MODE_ABR) { ulcx_set_error("bad mode"); return ULCX_ERR_ARG; }
-    for (int i = 0; h_rate && i < n; i++) {                // (as ulcx_encode_host_rates)
-        const float r = h_rate[i].RateKbps, a = h_rate[i].AvgComplexity;
-        if (!isfinite(r) || !isfinite(a) || r == 0.0f || a < 0.0f) {
-            ulcx_set_error("ulcx_encode_host_subset: invalid entry for row %d (RateKbps %g, AvgComplexity %g)", i, (double)r, (double)a);
-            return ULCX_ERR_ARG;
-        }
-    }
-    CKR(hipSetDevice(e->device));
-    { int rc = host_staging(e, (size_t)e->B * e->maxK, true); if (rc) return rc; }
-    if (h_rate && !e->d_rate) { int rc = dalloc(e->allocs, &e->d_rate, (size_t)e->B, false); if (rc) return rc; }
-    { int rc = slots_list_up(e, h_slots, n); if (rc) return rc; }
-    if (h_rate) CKR(hipMemcpy(e->d_rate, h_rate, sizeof(ulcx_rate) * (size_t)n, hipMemcpyHostToDevice));
-    const size_t NB = (size_t)n * nBlocks, cb = (size_t)e->C * e->BS;
-    CKR(hipMemcpy(e->d_pcm, h_pcm, sizeof(float) * NB * cb, hipMemcpyHostToDevice));
-    int rc = encode_dev_any(e, mode, p0, p1, h_rate ? e->d_rate : nullptr, e->d_pcm, nullptr, nBlocks, e->d_out, e->d_bits, e->d_wc, e->d_cplx, nullptr, e->subSlots, n);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_out, e->d_out, NB * e->ctx.slot, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_wc) CKR(hipMemcpy(h_wc, e->d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    if (h_cplx) CKR(hipMemcpy(h_cplx, e->d_cplx, sizeof(float) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
-}
-extern "C" int ulcx_decode_host_subset(ulcx_decoder *e, const int32_t *h_slots, int n, const uint8_t *h_in, int slotBytes, int nBlocks, float *h_pcm, int32_t *h_bits) {
-    if (!e || !h_in || !h_pcm || !h_bits || nBlocks < 1 || nBlocks > e->maxK || slotBytes < 1) { ulcx_set_error("ulcx_decode_host_subset: bad argument"); return ULCX_ERR_ARG; }
-    if (slots_host_bad("ulcx_decode_host_subset", h_slots, n, e->B)) return ULCX_ERR_ARG;
-    CKR(hipSetDevice(e->device));
-    const size_t NBmax = (size_t)e->B * e->maxK, cb = (size_t)e->C * e->BS, NB = (size_t)n * nBlocks;
-    { int rc = dec_host_staging(e, NBmax, NBmax * (size_t)slotBytes + 16); if (rc) return rc; }
-    { int rc = slots_list_up(e, h_slots, n); if (rc) return rc; }
-    CKR(hipMemcpy(e->d_in, h_in, NB * slotBytes, hipMemcpyHostToDevice));
-    int rc = decode_dev_any(e, e->d_in, slotBytes, nBlocks, e->d_pcm, nullptr, e->d_bits, nullptr, e->subSlots, n);
-    if (rc) return rc;
-    CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_pcm, e->d_pcm, sizeof(float) * NB * cb, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_bits, e->d_bits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
-    return ULCX_OK;
-}
+extern "C" int ulcx_encoder_reset_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, void *st) { return slots_reset_dev("ulcx_encoder_reset_streams_dev", e, d_slots, n, st); }
+extern "C" int ulcx_encoder_save_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, uint8_t *d_state, void *st) { return slots_save_dev("ulcx_encoder_save_streams_dev", e, d_slots, n, d_state, st); }
+extern "C" int ulcx_encoder_load_streams_dev(ulcx_encoder *e, const int32_t *d_slots, int n, const uint8_t *d_state, void *st) { return slots_load_dev("ulcx_encoder_load_streams_dev", e, d_slots, n, d_state, st); }
+extern "C" int ulcx_decoder_reset_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, void *st) { return slots_reset_dev("ulcx_decoder_reset_streams_dev", e, d_slots, n, st); }
+extern "C" int ulcx_decoder_save_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, uint8_t *d_state, void *st) { return slots_save_dev("ulcx_decoder_save_streams_dev", e, d_slots, n, d_state, st); }
+extern "C" int ulcx_decoder_load_streams_dev(ulcx_decoder *e, const int32_t *d_slots, int n, const uint8_t *d_state, void *st) { return slots_load_dev("ulcx_decoder_load_streams_dev", e, d_slots, n, d_state, st); }
+extern "C" int ulcx_encoder_reset_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n) { return slots_reset_host("ulcx_encoder_reset_streams_host", e, h_slots, n); }
+extern "C" int ulcx_encoder_save_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n, uint8_t *h_state) { return slots_save_host("ulcx_encoder_save_streams_host", e, h_slots, n, h_state); }
+extern "C" int ulcx_encoder_load_streams_host(ulcx_encoder *e, const int32_t *h_slots, int n, const uint8_t *h_state) { return slots_load_host("ulcx_encoder_load_streams_host", e, h_slots, n, h_state); }
+extern "C" int ulcx_decoder_reset_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n) { return slots_reset_host("ulcx_decoder_reset_streams_host", e, h_slots, n); }
+extern "C" int ulcx_decoder_save_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n, uint8_t *h_state) { return slots_save_host("ulcx_decoder_save_streams_host", e, h_slots, n, h_state); }
+extern "C" int ulcx_decoder_load_streams_host(ulcx_decoder *e, const int32_t *h_slots, int n, const uint8_t *h_state) { return slots_load_host("ulcx_decoder_load_streams_host", e, h_slots, n, h_state); }
 
 // diagnostic, only in a `make EXTRA=-DULCX_DSYN_STAMPS` build (tools/dsyn_stamps.py): first nBytes of the general-path staging
 // buffer, where that build leaves per-phase cycle counts
 #ifdef ULCX_DSYN_STAMPS
 extern "C" int ulcx_decoder_debug_scratch(ulcx_decoder *e, void *h_out, size_t strideBytes, size_t nBytes, int nStreams);
 extern "C" int ulcx_decoder_debug_scratch(ulcx_decoder *e, void *h_out, size_t strideBytes, size_t nBytes, int nStreams) {
-    if (!e || !h_out) return ULCX_ERR_ARG;
+    if (!e || !h_out) return refuse("ulcx_decoder_debug_scratch", "bad argument");
     CKR(hipSetDevice(e->device));
     CKR(hipDeviceSynchronize());
     for (int s = 0; s < nStreams && s < e->B; s++)
@@ -1573,8 +1556,8 @@ extern "C" int ulcx_decoder_debug_scratch(ulcx_decoder *e, void *h_out, size_t s
 #endif
 // per-stage hipEvents around every kernel (ulcx_*_stage_ms): on by default; a caller that does not read them can switch
 // them off - each record is a marker packet in the stream between two kernels
-extern "C" int ulcx_encoder_set_timing(ulcx_encoder *e, int on) { if (!e) return ULCX_ERR_ARG; e->timing = on != 0; if (!on) e->evRecorded = false; return ULCX_OK; }
-extern "C" int ulcx_decoder_set_timing(ulcx_decoder *e, int on) { if (!e) return ULCX_ERR_ARG; e->timing = on != 0; if (!on) e->evRecorded = false; return ULCX_OK; }
+extern "C" int ulcx_encoder_set_timing(ulcx_encoder *e, int on) { if (!e) return refuse("ulcx_encoder_set_timing", "no encoder"); e->timing = on != 0; if (!on) e->evRecorded = false; return ULCX_OK; }
+extern "C" int ulcx_decoder_set_timing(ulcx_decoder *e, int on) { if (!e) return refuse("ulcx_decoder_set_timing", "no decoder"); e->timing = on != 0; if (!on) e->evRecorded = false; return ULCX_OK; }
 static const char *kDecStage[ULCX_DEC_STAGES] = { "k_dscan", "k_dsyn" };
 extern "C" const char *ulcx_decoder_stage_name(int i) { return (i >= 0 && i < ULCX_DEC_STAGES) ? kDecStage[i] : ""; }
 extern "C" int ulcx_decoder_stage_ms(ulcx_decoder *e, float *ms, int maxStages) {
