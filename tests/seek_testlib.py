@@ -67,6 +67,45 @@ def oracle_seeds(blocks, ch, bs):
     return seeds
 
 
+def damaged(payload, nbytes, seed):
+    """A copy of a packed payload with ONE nybble overwritten by another value, at a seeded position inside the payload's
+    first half."""
+    rng = np.random.default_rng(seed)
+    q = int(rng.integers(0, nbytes))                        # nybble number: [0, nbytes) is the first half of 2 * nbytes
+    out = payload.copy()
+    sh = 4 * (q & 1)
+    old = (int(out[q >> 1]) >> sh) & 15
+    new = (old + int(rng.integers(1, 16))) & 15
+    out[q >> 1] = (int(out[q >> 1]) & ~(15 << sh)) | (new << sh)
+    return out
+
+
+def oracle_walk(payload, nbytes, ch, bs, max_blocks):
+    """The oracle's decoder over a packed payload, block by block: every block's row is sliced from the payload (zeros behind
+    its end, so a row never reads past the buffer) at the offset the oracle's own bit counts give, and the generator's state
+    goes from block to block as in oracle_seeds.  It stops at the first block for which the oracle reports 0 bits, at the
+    payload's end or after max_blocks.  -> (bits [n], byte offsets [n + 1], generator states [n + 1], inside): inside =
+    every block walked ends inside the payload, i.e. no expected value comes from the zeros behind it."""
+    lib = oracle()
+    lib.orc_decode_stream_seeded.argtypes = [C.c_int, C.c_int, u8p, C.c_int, C.c_int, f32p, i32p, C.POINTER(C.c_uint32)]
+    slot = 2 * ch * bs + 16
+    padded = np.zeros(int(nbytes) + slot, np.uint8)
+    padded[:nbytes] = payload[:nbytes]
+    pcm = np.zeros((bs, ch), np.float32)
+    b = np.zeros(1, np.int32)
+    bits, offs, seeds, off, sd, inside = [], [0], [SEED0], 0, C.c_uint32(SEED0), True
+    while len(bits) < max_blocks and off < nbytes:
+        row = np.ascontiguousarray(padded[off:off + slot])
+        b[0] = 0
+        lib.orc_decode_stream_seeded(ch, bs, ptr(row, u8p), slot, 1, ptr(pcm, f32p), ptr(b, i32p), C.byref(sd))
+        if b[0] == 0:
+            break
+        off += (int(b[0]) + 7) // 8
+        inside = inside and off <= nbytes
+        bits.append(int(b[0])); offs.append(off); seeds.append(sd.value)
+    return np.array(bits, np.int32), np.array(offs, np.int64), np.array(seeds, np.uint32), inside
+
+
 def oracle_pcm(blocks, ch, bs):
     """-> (pcm [K][bs][ch], bits [K]) of the oracle's sequential decode from block 0."""
     rc, pcm, bits = oracle_decode_stream(blocks, ch, bs)

@@ -13,7 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
 from seek_testlib import (RATE, SEED0, ORACLE_BLOCKS, geometries, oracle_stream, pack, oracle_seeds, oracle_pcm, expected_range,
-                          switched_starts)
+                          switched_starts, damaged, oracle_walk)
 
 pytestmark = pytest.mark.gpu
 TOOL = os.path.join(ROOT, "ulc-codec_amd", "ulcx-tool")
@@ -92,6 +92,61 @@ def test_index_of_truncated_and_empty_payloads():
         assert np.array_equal(index["RngState"][s, :n + 1], seeds[:n + 1]), s
         assert (index["ByteOffs"][s, n + 1:] == -1).all() and (index["RngState"][s, n + 1:] == 0).all(), s
     assert index["ByteOffs"][3, 0] == 0 and index["RngState"][3, 0] == SEED0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2b. damaged payloads: the index and the decoder agree with the oracle, and so with each other
+# ---------------------------------------------------------------------------------------------------------------------
+# Seeds of seek_testlib.damaged(), found on the CPU with the oracle alone (of 6000 seeds per stream about one in 300 changes a
+# block's size and still lets the oracle run all 40 blocks, one in 10 stops it; most overwrite a coefficient's value).  Per
+# stream: six that change a size without stopping the walk, six that stop it, four that change no size.
+DAMAGE_SEEDS = {
+    (2048, 2): [92, 1734, 2871, 3651, 4324, 4554, 14, 77, 80, 102, 123, 315, 0, 1, 2, 3],
+    (4096, 2): [467, 938, 955, 1806, 3272, 3750, 35, 43, 47, 52, 94, 343, 0, 1, 2, 3],
+}
+
+
+@pytest.mark.parametrize("geom", sorted(DAMAGE_SEEDS))
+def test_index_and_decode_of_damaged_payloads_match_the_oracle(geom):
+    """Sixteen copies of one payload, each with one nybble overwritten inside its first half.  The index (count, offsets,
+    generator states) and the bits a packed decode reports must be what the oracle's decoder gives when it walks the same
+    bytes block by block (seek_testlib.oracle_walk): one walk serves both calls, and a range call trusts the index."""
+    amd = _amd()
+    bs, ch = geom
+    K, seeds = ORACLE_BLOCKS, DAMAGE_SEEDS[geom]
+    oracle_coded = {g: int((np.asarray(st[0][3]) != 0x10).sum()) for g, st in geometries().items() if st[0][3] is not None}
+    assert geom == (2048, 2) or oracle_coded[geom] == max(oracle_coded.values()), f"{geom} is not the most window-switched stream: {oracle_coded}"
+    name, blocks, bits, _ = geometries()[geom][0]
+    host1, nb1 = pack([(blocks, bits)])
+    nbytes = int(nb1[0])
+    host = np.stack([damaged(host1[0], nbytes, sd) for sd in seeds])
+    nb = np.full(len(seeds), nbytes, np.int32)
+    clean = oracle_walk(host1[0], nbytes, ch, bs, K)
+    assert len(clean[0]) == K and clean[3]
+    walks = [oracle_walk(host[s], nbytes, ch, bs, K) for s in range(len(seeds))]
+    # the inputs stress the walk: enough damages end it early, enough change a block's size and let it go on to the last block;
+    # and no expected value comes from the zeros behind a payload
+    stopped = sum(len(w[0]) < K for w in walks)
+    resized = sum(len(w[0]) == K and not np.array_equal(w[0], clean[0]) for w in walks)
+    print(f"{name}: {stopped} of {len(seeds)} damages stop the oracle before block {K}, {resized} change a block's size and run all {K}")
+    assert stopped >= 4 and resized >= 4, (stopped, resized)
+    assert all(w[3] for w in walks), "a walked block ends behind its payload"
+    dec = amd.BatchDecoder(len(seeds), ch, bs, K)
+    index, count = dec.index_packed(host, nb, K)
+    dec.close()
+    dec = amd.BatchDecoder(len(seeds), ch, bs, K)
+    _, gbits = dec.decode_packed(host, nb, K)
+    dec.close()
+    for s, (wbits, woffs, wseeds, _) in enumerate(walks):
+        n = len(wbits)
+        what = f"{name}, damage {seeds[s]} ({n} blocks)"
+        assert count[s] == n, f"{what}: the index counts {count[s]}"
+        assert np.array_equal(index["ByteOffs"][s, :n + 1], woffs), what
+        assert np.array_equal(index["RngState"][s, :n + 1], wseeds), f"{what}: generator states differ from the oracle's"
+        assert (index["ByteOffs"][s, n + 1:] == -1).all() and (index["RngState"][s, n + 1:] == 0).all(), f"{what}: unused entries"
+        want = np.zeros(K, np.int32)
+        want[:n] = wbits
+        assert np.array_equal(gbits[s], want), f"{what}: the decode reports {gbits[s]}, the oracle {want}"
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -21,19 +21,12 @@
 #define WG 128
 #define FFT_PACKED
 #include "ulcx_fft.h"
-#ifndef DSYN_C2048
-#define DSYN_C2048 1
-#endif
-#ifndef DSYN_C4096
-#define DSYN_C4096 1   // BlockSize 4096 with the size as a compile-time constant too (the pipelined epilogue; round 5)
-#endif
 #define DSYN_TWL ULCX_DSYN_TWL
-#ifndef DSYN_EPI2
-#define DSYN_EPI2 1  // headline geometry: the epilogue's global operands fetched one trip ahead (0: the generic loop)
-#endif
-#ifndef DPS
-#define DPS 4        // FFT array padding (ulcx_fft.h): one complex after every 16 (3: after every 8 - conflict-free passes, 1 KB more LDS)
-#endif
+// Settled by measurement: each line names the note that holds the alternative's numbers.
+#define DSYN_C2048 1   // BlockSize 2048 as a compile-time constant of k_dsyn (0: read from the context; profiles/NOTES_r01-r04.md)
+#define DSYN_C4096 1   // BlockSize 4096 likewise, with the pipelined epilogue (profiles/NOTES_r05.md)
+#define DSYN_EPI2 1    // those two: the epilogue's global operands fetched one trip ahead (0: the generic loop; profiles/NOTES_r05.md)
+#define DPS 4          // FFT array padding (ulcx_fft.h): one complex after every 16 (3: after every 8 - conflict-free passes, 1 KB more LDS; profiles/NOTES_r01-r04.md)
 
 // ---------------------------------------------------------------------------
 // The scan's view of the stream: 16-byte aligned chunks kept in registers, the next one always in flight, so a
@@ -169,6 +162,39 @@ __device__ __forceinline__ void ring_flush(uint2 *ring, int lane, int &f, int n,
     DSCAN_WAVE_SYNC();
 }
 
+// A block's shape from its window code: the subblock pattern (a nybble per subblock, ulcx_pattern; code 0000 behaves as one
+// plain N/1 block, as in the reference), the subblocks per channel, and whether that is the one full-size subblock
+// (ulcDecoder.c:242-245).
+struct BlockShape { unsigned pat; int nsub; bool whole; };
+__device__ __forceinline__ BlockShape block_shape(int BS, int wc) {
+    BlockShape b;
+    b.pat = ulcx_pattern(wc);
+    b.whole = (BS >> (b.pat & 7)) == BS;
+    b.nsub = 1;
+    if (!b.whole) { b.nsub = 0; unsigned q = b.pat; do b.nsub++; while (q >>= 4); }
+    return b;
+}
+// LastSubBlockSize as a block with this window code leaves it (ulcDecoder.c:300): the size of its last subblock
+__device__ __forceinline__ int last_sub_size(int BS, int wc) {
+    const unsigned pat = ulcx_pattern(wc);
+    unsigned pp = pat; int ls = BS;
+    if ((BS >> (pat & 7)) != BS) do { ls = BS >> (pp & 7); } while (pp >>= 4);
+    return ls;
+}
+// Windowed overlap-add of one pair (spec v2, oracle/orc_fourier.c orc_imdct): A the pending sample, B the new one, (cw, sn) the
+// window's falling and rising value at the pair.  Out[p] = fma(c, A, -(s B)), Out[S-1-p] = fma(s, A, c B) - the products
+// rounded on their own, as the reference writes them; below the ramp (pass) both go through unchanged.
+struct LapPair { float lo, hi; };
+__device__ __forceinline__ LapPair lap_pair(float A, float B, float cw, float sn, bool pass) {
+    LapPair r;
+    if (pass) { r.lo = A; r.hi = B; }
+    else {
+        const float m1 = sn * B, m3 = cw * B;
+        r.lo = __builtin_fmaf(cw, A, -m1); r.hi = __builtin_fmaf(sn, A, m3);
+    }
+    return r;
+}
+
 // Syntax walk of one block starting at p (limit = bits that may be consumed, readBytes = bytes that may be
 // used).  The walk is the one thing that cannot be done in parallel; everything it learns on the way is left for the
 // synthesis in a form that can: per (channel, subblock) unit
@@ -177,13 +203,17 @@ __device__ __forceinline__ void ring_flush(uint2 *ring, int lane, int &f, int n,
 //   * NOISE records, 8 bytes (the layout synth_noise reads): {first coefficient | count << 16 | tail << 31,
 //     draws made in the unit before the run | level << 16 | quantizer index << 21};
 //   * the unit's draws-so-far, its decaying-noise tail's parameters and (after the walk) the tail's level chain;
-// and bits / WindowCtrl / draws of the block.  Returns bits consumed (0 = corrupt).  One flat loop, one code (or one
+// and bits / WindowCtrl / draws of the block.  One flat loop, one code (or one
 // run of plain coefficients) per trip.
 // RING: the records through the wave's LDS rings (every lane of the wave is here, `live` or not, and stays to the end);
 // else stored one by one (lanes come and go as they please: k_dscan_packed).
-template <typename WIN = NybWin, bool RING = false>
-__device__ __forceinline__ int scan_block(const UlcxDecCtx &c, int blk, const uint8_t *p, int limit, int readBytes,
-                                          const uint8_t *bufBeg, const uint8_t *bufEnd, bool live = true, uint2 *ringP = nullptr, uint2 *ringN = nullptr) {
+// NOTES = false (k_dindex): the same walk and NOTHING stored - no records, no per-unit or per-block notes, no tail chains;
+// blk is not looked at.  What the walk hands back either way: the bits consumed (0 = corrupt) and the block's draws.
+struct Walked { int bits, draws; };
+template <typename WIN = NybWin, bool RING = false, bool NOTES = true>
+__device__ __forceinline__ Walked scan_block(const UlcxDecCtx &c, int blk, const uint8_t *p, int limit, int readBytes,
+                                             const uint8_t *bufBeg, const uint8_t *bufEnd, bool live = true, uint2 *ringP = nullptr, uint2 *ringN = nullptr) {
+    static_assert(NOTES || !RING, "scan_block: the rings carry records");
     const int rlane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     int fP = 0, fN = 0, wP = 0, wN = 0;                             // RING: records written out so far, ring rows of the next records
     WIN win; win.init(p, readBytes, bufBeg, bufEnd);
@@ -196,10 +226,13 @@ __device__ __forceinline__ int scan_block(const UlcxDecCtx &c, int blk, const ui
         wc |= dec ? (int)(w0 & 0xF0) : (1 << 4);
         pos = dec ? 8 : 4;
     }
+    // (block_shape, written out: with the helper's branch on `whole` the three scans grow by 16-36 bytes)
     unsigned pat = ulcx_pattern(wc);                                // (code 0000 behaves as one plain N/1 block, as in the reference)
     int nsub = 0; { unsigned q = pat; do nsub++; while (q >>= 4); }
     if ((c.BS >> (pat & 7)) == c.BS) nsub = 1;                      // ulcDecoder.c:242-245
     int total = c.C * nsub;
+    // the block's rows of the per-block scratch: addresses only - every access sits under NOTES (k_dindex walks more blocks
+    // than the scratch has rows)
     int *udraw  = c.unitDraws + (size_t)blk * c.C * 4;
     int4 *urec = c.unitRec + (size_t)blk * c.C * 4;
     float4 *utail = c.unitTail + (size_t)blk * c.C * 4;
@@ -207,22 +240,26 @@ __device__ __forceinline__ int scan_block(const UlcxDecCtx &c, int blk, const ui
     uint2 *nrec = c.nrec + (size_t)blk * c.nrecStride;
     int nP = 0, nN = 0, uP0 = 0, uN0 = 0;                           // records written so far in the block / at the current unit's start
     auto put_prec = [&](uint2 rec) {
-        if (RING) { ring_put<DSCAN_RP>(ringP, rlane, wP, rec); wP = (wP + 1 == DSCAN_RP) ? 0 : wP + 1; }
-        else if (nP < c.precStride) prec[nP] = rec;
-        nP++;
+        if constexpr (NOTES) {
+            if (RING) { ring_put<DSCAN_RP>(ringP, rlane, wP, rec); wP = (wP + 1 == DSCAN_RP) ? 0 : wP + 1; }
+            else if (nP < c.precStride) prec[nP] = rec;
+            nP++;
+        }
     };
     auto put_nrec = [&](uint2 rec) {
-        if (RING) { ring_put<DSCAN_RN>(ringN, rlane, wN, rec); wN = (wN + 1 == DSCAN_RN) ? 0 : wN + 1; }
-        else if (nN < c.nrecStride) nrec[nN] = rec;
-        nN++;
+        if constexpr (NOTES) {
+            if (RING) { ring_put<DSCAN_RN>(ringN, rlane, wN, rec); wN = (wN + 1 == DSCAN_RN) ? 0 : wN + 1; }
+            else if (nN < c.nrecStride) nrec[nN] = rec;
+            nN++;
+        }
     };
     int u = 0, draws = 0, uslot = 0, uDraw0 = 0, uj = 0, uch4 = 0;
-    if (live) { udraw[0] = 0; utail[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    if constexpr (NOTES) { if (live) { udraw[0] = 0; utail[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); } }
     int S = c.BS >> (pat & 7), N = S;
     bool first = true;
     bool fin = (limit < 16) | !live, bad = fin;
     auto next_unit = [&]() {
-        urec[uslot] = make_int4(uP0, nP - uP0, uN0, nN - uN0);
+        if constexpr (NOTES) urec[uslot] = make_int4(uP0, nP - uP0, uN0, nN - uN0);
         u++;
         fin = bad | (u >= total);
         if (!fin) {
@@ -230,8 +267,9 @@ __device__ __forceinline__ int scan_block(const UlcxDecCtx &c, int blk, const ui
             if (uj == nsub) { uj = 0; uch4 += 4; }
             const int j = uj;
             uslot = uch4 + j;
-            udraw[uslot] = draws; uDraw0 = draws;
-            utail[uslot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if constexpr (NOTES) udraw[uslot] = draws;
+            uDraw0 = draws;
+            if constexpr (NOTES) utail[uslot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             uP0 = nP; uN0 = nN;
             S = c.BS >> ((pat >> (4 * j)) & 7); N = S;
             first = true;
@@ -269,7 +307,7 @@ __device__ __forceinline__ int scan_block(const UlcxDecCtx &c, int blk, const ui
             put_nrec(make_uint2((uint32_t)(S - N) | ((uint32_t)(np - (k.tail ? 1 : 0)) << 16) | (k.tail ? 0x80000000u : 0u),
                                 (uint32_t)(draws - uDraw0) | ((uint32_t)k.l << 16) | ((uint32_t)qidx << 21)));
         }
-        if (k.tail & !over) {
+        if constexpr (NOTES) if (k.tail & !over) {
             // ulcDecoder.c:163-186: start amplitude, decay, first coefficient, count; the chain itself runs after the walk
             const float lev0 = (float)(k.l * k.l) * expand_quantizer(qidx) * (1.0f / 16);
             const float rr = 1.0f + (float)(k.dn * k.dn) * -0x1.0p-19f;
@@ -292,9 +330,10 @@ __device__ __forceinline__ int scan_block(const UlcxDecCtx &c, int blk, const ui
     if (RING) {
         ring_flush<DSCAN_RP>(ringP, rlane, fP, nP, c.prec, blk, c.precStride);
         ring_flush<DSCAN_RN>(ringN, rlane, fN, nN, c.nrec, blk, c.nrecStride);
-        if (!live) return 0;
+        if (!live) return Walked{ 0, 0 };
     }
     bool ok = !bad;
+    if constexpr (NOTES) {
     c.bits[blk] = ok ? pos : 0;
     c.wcScan[blk] = ok ? wc : 0;
     c.draws[blk] = draws;
@@ -319,7 +358,8 @@ __device__ __forceinline__ int scan_block(const UlcxDecCtx &c, int blk, const ui
             }
         }
     }
-    return ok ? pos : 0;
+    }
+    return Walked{ ok ? pos : 0, draws };
 }
 
 // Pass 1 - one lane per block.
@@ -350,7 +390,7 @@ __global__ __launch_bounds__(64) void k_dscan_packed(UlcxDecCtx c) {
         int blk = s * c.K + k;
         c.blkOff[blk] = off;
         int bits = 0;
-        if (!dead && off < avail) bits = scan_block(c, blk, base + off, (avail - off) * 8, avail - off, c.in, c.in + c.inBytes);
+        if (!dead && off < avail) bits = scan_block(c, blk, base + off, (avail - off) * 8, avail - off, c.in, c.in + c.inBytes).bits;
         else { c.bits[blk] = 0; c.wcScan[blk] = 0; c.draws[blk] = 0; }
         if (!bits) dead = true;
         off += (bits + 7) >> 3;                                     // the tool rounds every block up to a byte
@@ -398,65 +438,7 @@ __global__ __launch_bounds__(64) void k_dscan_range(UlcxDecCtx c) {
     }
 }
 
-// The walk of scan_block without its notes (k_dindex): the same syntax decisions, no records, no tail chains.  Returns the
-// bits consumed (0 = corrupt) and the block's draw count.
-template <typename WIN>
-__device__ __forceinline__ int walk_block(const UlcxDecCtx &c, const uint8_t *p, int limit, int readBytes,
-                                          const uint8_t *bufBeg, const uint8_t *bufEnd, int &drawsOut) {
-    WIN win; win.init(p, readBytes, bufBeg, bufEnd);
-    int pos, wc;
-    {
-        uint32_t w0 = (limit >= 8) ? win.at(0) : 0;                 // ulcDecoder.c:211-216
-        wc = w0 & 0xF;
-        bool dec = (wc & 0x8) != 0;
-        wc |= dec ? (int)(w0 & 0xF0) : (1 << 4);
-        pos = dec ? 8 : 4;
-    }
-    const unsigned pat = ulcx_pattern(wc);
-    int nsub = 0; { unsigned q = pat; do nsub++; while (q >>= 4); }
-    if ((c.BS >> (pat & 7)) == c.BS) nsub = 1;                      // ulcDecoder.c:242-245
-    const int total = c.C * nsub;
-    int u = 0, uj = 0, draws = 0;
-    int N = c.BS >> (pat & 7);
-    bool first = true, fin = limit < 16, bad = fin;
-    auto next_unit = [&]() {
-        u++;
-        fin = bad | (u >= total);
-        if (!fin) {
-            uj = (uj + 1 == nsub) ? 0 : uj + 1;
-            N = c.BS >> ((pat >> (4 * uj)) & 7);
-            first = true;
-        }
-    };
-    while (!fin) {
-        const uint64_t w64 = win.at64(pos);
-        uint32_t w = (uint32_t)w64;
-        int m = first ? 0 : plain_prefix(w);
-        m = m < N ? m : N;
-        m = (pos + 4 * m <= limit) ? m : 0;
-        if (m > 0) {
-            pos += 4 * m; N -= m;
-            if (N == 0) next_unit();
-            w = (uint32_t)(w64 >> (4 * m));
-        }
-        if (!fin) {
-            const Code k = decode_code(w, first);
-            const bool over = (k.zrun & (k.n > N)) | (k.n8 & (k.np > N));     // ulcDecoder.c:127,139,154
-            const int used = over ? 0 : ((k.stop | k.tail) ? N : k.n + k.np);
-            draws += over ? 0 : (k.tail ? N : k.np);
-            pos += 4 * k.len;
-            N -= used;
-            bad |= over;
-            first = false;
-            if ((N == 0) | over) next_unit();
-            if (pos > limit) { bad = true; fin = true; }               // ran off the readable bytes: corrupt
-        }
-    }
-    drawsOut = draws;
-    return bad ? 0 : pos;
-}
-
-// Block index of packed payloads (ulcx_index_packed_*) - one lane per stream, the walk of k_dscan_packed and nothing else:
+// Block index of packed payloads (ulcx_index_packed_*) - one lane per stream, the walk of k_dscan_packed without its notes:
 // per block its start and the state the stream's one generator chain has there (one jump by the block's draws).  It stops
 // where k_dscan_packed reports 0 bits.  No stream state, none of the per-block scratch.
 __global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx_index_entry *index, int32_t *nBlocks) {
@@ -469,11 +451,10 @@ __global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx
     uint32_t st = 1234567u;                                          // ulcDecoder.c:76
     row[0].ByteOffs = 0; row[0].RngState = st;
     while (n < maxBlocks && off < avail) {
-        int draws;
-        const int bits = walk_block<NybWin>(c, base + off, (avail - off) * 8, avail - off, c.in, c.in + c.inBytes, draws);
-        if (!bits) break;
-        off += (bits + 7) >> 3;                                      // the tool rounds every block up to a byte
-        st = rng_jump(c.jumpT, st, (uint32_t)draws);
+        const Walked w = scan_block<NybWin, false, false>(c, 0, base + off, (avail - off) * 8, avail - off, c.in, c.in + c.inBytes);
+        if (!w.bits) break;
+        off += (w.bits + 7) >> 3;                                    // the tool rounds every block up to a byte
+        st = rng_jump(c.jumpT, st, (uint32_t)w.draws);
         n++;
         row[n].ByteOffs = off; row[n].RngState = st;
     }
@@ -747,20 +728,19 @@ template <typename OUT> __device__ __forceinline__ OUT *out_base(const UlcxDecCt
 template <> __device__ __forceinline__ float *out_base<float>(const UlcxDecCtx &c) { return c.pcm; }
 template <> __device__ __forceinline__ int16_t *out_base<int16_t>(const UlcxDecCtx &c) { return c.pcm16; }
 
-// LDS carve, in floats.  Stereo kernel (k_dsyn):  z [2 padded arrays of BS/2 complex] | lap [2][BS/2] | twl [BS/4 complex] |
+// LDS carve, in floats.  Stereo kernel (k_dsyn):  z [2 padded arrays of BS/2 complex] | twl [BS/4 complex] |
 //   per wave: noise runs, prefix counts, seed table | 128 block / unit seeds.  General kernel (k_dgen): z [1 array] | per-wave lists.
 #define DSYN_PWORDS(BS) (((BS) / 32 > 64 ? (BS) / 32 : 64) + 2)
 #define DSYN_CHUNK 32            // blocks of a stream whose RNG states and headers the stereo kernel stages at once (<= 64)
-struct DsynLds { int zFloats, lapFloats, twFloats, listFloats; };
-__host__ __device__ static inline DsynLds dsyn_lds(int BS, int C, int fast, int twInLds) {
+struct DsynLds { int zFloats, twFloats, listFloats; };
+// twInLds: the stereo kernel's FFT twiddles resident in LDS (BlockSize <= 2048; above it they are read from the tables in
+// global memory, L1/L2-hot: a fourth workgroup per CU).  The lapping state is in global memory for every geometry.
+__host__ __device__ static inline DsynLds dsyn_lds(int BS, int fast, int twInLds) {
     DsynLds l;
     l.zFloats = (fast ? 2 : 1) * 2 * FFT_PADDEDS(BS / 2, DPS);
-    // twInLds: 1 = lapping state and twiddles in LDS, 0 = both in global memory, 2 = twiddles in LDS, lapping state in global memory
-    l.lapFloats = (fast && BS <= 2048 && twInLds == 1) ? 2 * (BS / 2) : 0;      // (above 2048 the stereo kernel keeps the lapping state in global memory: a third workgroup per CU)
-    l.twFloats = (fast && BS <= 2048 && twInLds != 0) ? BS / 2 : 0;               // (likewise the FFT twiddles: read from the tables in global memory, L1/L2-hot, a fourth workgroup per CU)
+    l.twFloats = (fast && BS <= 2048 && twInLds) ? BS / 2 : 0;
     l.listFloats = 2 * (64 + DSYN_PWORDS(BS)) + 128;             // per wave: prefix counts, sign-parity stream; per workgroup: 128 block / channel RNG states
     if (fast) l.listFloats += 2 * (DSYN_CHUNK + 4) * 8;          // stereo kernel: the headers of a chunk of blocks + of a decimated block's four units, per channel
-    (void)C;
     return l;
 }
 
@@ -778,28 +758,25 @@ __host__ __device__ static inline DsynLds dsyn_lds(int BS, int C, int fast, int 
 template <typename OUT, int DEC_MAXT, bool TWL, bool SPLIT = false, int BSC = 0, bool RANGE = false>
 __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
     static_assert(!RANGE || SPLIT, "k_dsyn: a range call enters streams as a cut does");
-    constexpr bool LAPG = true;
     extern __shared__ float lds[];
     const int BS = BSC ? BSC : c.BS, H2 = BS / 2;
     constexpr int C = 2;
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const DsynLds L = dsyn_lds(BS, C, 1, TWL ? 2 : 0);
+    const DsynLds L = dsyn_lds(BS, 1, TWL);
     float2 *z    = (float2 *)lds;
-    // lapping state: in LDS for the stream's blocks of this launch, or (LAPG) in global memory: the arrays a stream's state
-    // is read from / written to at its first / last block of the launch, the workgroup's own scratch rows in between.
-    // Every element is read and rewritten by the same thread in un-decimated blocks and by the same wave in decimated
-    // ones; the barriers between the two kinds of block order the rest.
-    float  *ldsLap = lds + L.zFloats;
+    // lapping state, in global memory: the arrays a stream's state is read from / written to at its first / last block of
+    // the launch, the workgroup's own scratch rows in between.  Every element is read and rewritten by the same thread in
+    // un-decimated blocks and by the same wave in decimated ones; the barriers between the two kinds of block order the rest.
     // (one workgroup per stream - grid = streams -: the stream's own rows serve, nothing else touches them during the launch)
     // (a cut launch: the leading workgroups still take one whole stream each and use its rows; the others their own scratch rows)
     const bool ownStream = !SPLIT || (int)blockIdx.x < c.synFull;
-    float  *scr = !LAPG ? ldsLap : ownStream ? c.lapO + (size_t)(c.s0 + blockIdx.x) * C * H2 : c.lapScratch + (size_t)((int)blockIdx.x - c.synFull) * C * H2;
-    float2 *twl  = (float2 *)(lds + L.zFloats + L.lapFloats);        // FFT twiddles: the full-size table, or the three of a decimated block's sizes
+    float  *scr = ownStream ? c.lapO + (size_t)(c.s0 + blockIdx.x) * C * H2 : c.lapScratch + (size_t)((int)blockIdx.x - c.synFull) * C * H2;
+    float2 *twl  = (float2 *)(lds + L.zFloats);        // FFT twiddles: the full-size table, or the three of a decimated block's sizes
     SynWave sw;
-    sw.pre  = (int *)(lds + L.zFloats + L.lapFloats + L.twFloats) + wv * (64 + DSYN_PWORDS(BS));
+    sw.pre  = (int *)(lds + L.zFloats + L.twFloats) + wv * (64 + DSYN_PWORDS(BS));
     sw.seedTab = (uint32_t *)(sw.pre + 64);
-    uint32_t *bseed = (uint32_t *)(lds + L.zFloats + L.lapFloats + L.twFloats + 2 * (64 + DSYN_PWORDS(BS)));   // [0,64): RNG state at each block's start, [64,128): at its second channel
+    uint32_t *bseed = (uint32_t *)(lds + L.zFloats + L.twFloats + 2 * (64 + DSYN_PWORDS(BS)));   // [0,64): RNG state at each block's start, [64,128): at its second channel
     // [wave][block of the chunk][8]: {window code, the first unit's four record fields, its draws (un-decimated block), its tail decay, -}
     int *hdr = (int *)(bseed + 128) + wv * ((DSYN_CHUNK + 4) * 8);
     sw.lane = lane;
@@ -859,9 +836,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
         const int blk = s * c.K + k;
         if (s != sCur) {
             // entering a stream, at its first block of the launch or behind it: the state in front of block k
-            if (!LAPG && sCur >= 0) { __syncthreads(); float *go = c.lapO + (size_t)sCur * C * H2; for (int i = tid; i < 2 * H2; i += WG) go[i] = ldsLap[i]; __syncthreads(); }
             sCur = s;
-            if (!LAPG) { const float *gi = c.lap + (size_t)s * C * H2; for (int i = tid; i < 2 * H2; i += WG) ldsLap[i] = gi[i]; }
             __syncthreads();
             int bad = 0; uint32_t dsum = 0;
             const int kf = RANGE ? c.k0 - c.rInfo[s].x : c.k0;       // the stream's first row of the launch
@@ -881,10 +856,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
                 __syncthreads();
                 seed = rng_jump(c.jumpT, seed, bseed[0] + bseed[1]);
                 __syncthreads();
-                const unsigned pp0 = ulcx_pattern(c.wcScan[blk - 1]);        // LastSubBlockSize as block k-1 left it (ulcDecoder.c:300)
-                unsigned pp = pp0; int ls = BS;
-                if ((BS >> (pp0 & 7)) != BS) do { ls = BS >> (pp & 7); } while (pp >>= 4);
-                lastSub = ls;
+                lastSub = last_sub_size(BS, c.wcScan[blk - 1]);              // as block k-1 left it
             }
             chunkK = -1;
         }
@@ -936,7 +908,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
                 if (tid == 0) c.bits[blk] = 0;
             }
             if (lastOfStream && tid == 0) { c.lastSubO[s] = lastSub; c.seedO[s] = seed; c.deadO[s] = 1; }
-            if (LAPG && lastOfStream) for (int i = tid; i < 2 * H2; i += WG) lapW[i] = 0.0f;     // (never read again: the stream stays dead)
+            if (lastOfStream) for (int i = tid; i < 2 * H2; i += WG) lapW[i] = 0.0f;     // (never read again: the stream stays dead)
             continue;
         }
         const int *udraw = c.unitDraws + (size_t)blk * C * 4;
@@ -944,10 +916,10 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
         const float4 *utail = c.unitTail + (size_t)blk * C * 4;
         const uint2 *prec = c.prec + (size_t)blk * c.precStride, *nrec = c.nrec + (size_t)blk * c.nrecStride;
         const float *tmag = c.tailMag + (size_t)blk * C * 4 * c.tailStride;
-        const unsigned pat0 = ulcx_pattern(wc);
-        const bool whole = (BS >> (pat0 & 7)) == BS;                 // one subblock per channel (ulcDecoder.c:242-245)
-        int nsub = 1;
-        if (!whole) { nsub = 0; unsigned q = pat0; do nsub++; while (q >>= 4); }
+        const BlockShape shape = block_shape(BS, wc);
+        const unsigned pat0 = shape.pat;
+        const bool whole = shape.whole;
+        const int nsub = shape.nsub;
         if (TWL && whole != twFull) {
             // twiddle tables for this block's transform sizes: the full-size one, or those of N/2, N/4, N/8 back to back
             if (whole) for (int i = tid; i < BS / 4; i += WG) twl[i] = c.T.tw[0][i];
@@ -1137,19 +1109,13 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
 #pragma unroll
                     for (int q = 0; q < 2; q++) {
                         const int p = pv[q];
-                        float mLo, mHi, sLo, sHi;                                      // outputs at positions p and S-1-p
-                        if (p < a) { mLo = Am[q]; mHi = Bm[q]; sLo = As[q]; sHi = Bs[q]; }
-                        else {
-                            const float cw = fall[p - a], sn = rise[p - a];
-                            // spec v2 (orc_imdct): Out[p] = fma(c, A, -(s B)), Out[S-1-p] = fma(s, A, c B)
-                            const float m1 = sn * Bm[q], m3 = cw * Bm[q];
-                            mLo = __builtin_fmaf(cw, Am[q], -m1); mHi = __builtin_fmaf(sn, Am[q], m3);
-                            const float s1 = sn * Bs[q], s3 = cw * Bs[q];
-                            sLo = __builtin_fmaf(cw, As[q], -s1); sHi = __builtin_fmaf(sn, As[q], s3);
-                        }
+                        const bool pass = p < a;
+                        float cw = 0.0f, sn = 0.0f;
+                        if (!pass) { cw = fall[p - a]; sn = rise[p - a]; }
+                        const LapPair m = lap_pair(Am[q], Bm[q], cw, sn, pass), sd = lap_pair(As[q], Bs[q], cw, sn, pass);   // outputs at positions p and S-1-p
                         // inverse M/S (ulcDecoder.c:281-289) + interleave (:292-297)
-                        lo2[q] = make_float2(mLo + sLo, mLo - sLo);
-                        hi2[q] = make_float2(mHi + sHi, mHi - sHi);
+                        lo2[q] = make_float2(m.lo + sd.lo, m.lo - sd.lo);
+                        hi2[q] = make_float2(m.hi + sd.hi, m.hi - sd.hi);
                     }
                     // positions pv[1] = pv[0]-1 and S-1-pv[0], S-pv[0] are neighbours: two aligned 16-byte stores
                     st4(outp + 2 * pv[1], lo2[1].x, lo2[1].y, lo2[0].x, lo2[0].y);
@@ -1168,14 +1134,13 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
             // ---- decimated block: each wave finishes its channel in LDS, then both channels together:
             //      inverse M/S (ulcDecoder.c:281-289) + interleave (:292-297)
             // (the time-domain pass works on the lapping state in place: in the workgroup's own rows)
-            if (LAPG && lapR != scr && !warm) { for (int i = tid; i < 2 * H2; i += WG) scr[i] = lapR[i]; __syncthreads(); }
-            float *lapD = LAPG ? scr : ldsLap;
+            if (lapR != scr && !warm) { for (int i = tid; i < 2 * H2; i += WG) scr[i] = lapR[i]; __syncthreads(); }
             WAVE_SYNC();
-            const int newLast = dec_time_wave<DEC_MAXT>(c, zc, lapD + wv * H2, wc, pat0, nsub, lastSub, lane);
+            const int newLast = dec_time_wave<DEC_MAXT>(c, zc, scr + wv * H2, wc, pat0, nsub, lastSub, lane);
             __syncthreads();
             // output = times [-BS/2, BS/2) of both channels: the old pending lists (time -1-i at lap[i]), then the arrays
             const float *t0 = (const float *)z, *t1 = (const float *)(z + Mp0);
-            const float *L0 = lapD, *L1 = lapD + H2;
+            const float *L0 = scr, *L1 = scr + H2;
             if (!warm) {
             for (int n = 2 * tid; n < H2; n += 2 * WG) {
                 const float mx = L0[H2 - 1 - n], my = L0[H2 - 2 - n], sx = L1[H2 - 1 - n], sy = L1[H2 - 2 - n];
@@ -1201,7 +1166,6 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
 #ifdef ULCX_DSYN_STAMPS
     if (lane == 0) for (int i = 0; i < DSYN_NSTAMP; i++) ((unsigned long long *)(c.scratch + (size_t)s * 4 * BS))[wv * DSYN_NSTAMP + i] = stq.t[i];
 #endif
-    if (!LAPG && sCur >= 0) { __syncthreads(); float *go = c.lapO + (size_t)sCur * C * H2; for (int i = tid; i < 2 * H2; i += WG) go[i] = ldsLap[i]; }
 }
 
 // ---------------------------------------------------------------------------
@@ -1215,7 +1179,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
     const int BS = c.BS, C = c.C, H2 = BS / 2;
     const int s = c.s0 + blockIdx.x, tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const DsynLds L = dsyn_lds(BS, C, 0, 0);
+    const DsynLds L = dsyn_lds(BS, 0, 0);
     float2 *z = (float2 *)lds;
     SynWave sw;
     sw.pre  = (int *)(lds + L.zFloats) + wv * (64 + DSYN_PWORDS(BS));
@@ -1256,10 +1220,9 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
         const float4 *utail = c.unitTail + (size_t)blk * C * 4;
         const uint2 *prec = c.prec + (size_t)blk * c.precStride, *nrec = c.nrec + (size_t)blk * c.nrecStride;
         const float *tmag = c.tailMag + (size_t)blk * C * 4 * c.tailStride;
-        const unsigned pat0 = ulcx_pattern(wc);
-        const bool whole = (BS >> (pat0 & 7)) == BS;                 // one subblock per channel (ulcDecoder.c:242-245)
-        int nsub = 1;
-        if (!whole) { nsub = 0; unsigned q = pat0; do nsub++; while (q >>= 4); }
+        const BlockShape shape = block_shape(BS, wc);
+        const unsigned pat0 = shape.pat;
+        const int nsub = shape.nsub;
         auto unit_draws = [&](int ch, int j) { return ((j + 1 < nsub) ? udraw[ch * 4 + j + 1] : (ch + 1 < C) ? udraw[(ch + 1) * 4] : c.draws[blk]) - udraw[ch * 4 + j]; };
         {
             float *dec = scr + 2 * BS, *tmpq = scr + 3 * BS;
@@ -1314,14 +1277,11 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
 #pragma unroll
                         for (int q = 0; q < 2; q++) {
                             const int p = pv[q];
-                            const float A = Av[q], B = Bv[q];
-                            if (p < a) { out[p] = A; out[S - 1 - p] = B; }
-                            else {
-                                const float cw = fall[p - a], sn = rise[p - a];
-                                const float m1 = sn * B, m3 = cw * B;       // spec v2: fused (orc_imdct)
-                                out[p] = __builtin_fmaf(cw, A, -m1);
-                                out[S - 1 - p] = __builtin_fmaf(sn, A, m3);
-                            }
+                            const bool pass = p < a;
+                            float cw = 0.0f, sn = 0.0f;
+                            if (!pass) { cw = fall[p - a]; sn = rise[p - a]; }
+                            const LapPair r = lap_pair(Av[q], Bv[q], cw, sn, pass);
+                            out[p] = r.lo; out[S - 1 - p] = r.hi;
                         }
                         Lp[2 * k1] = y1.x;
                         Lp[2 * k1 + 1] = y2.y;
@@ -1370,36 +1330,45 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
     if (tid == 0) { c.lastSub[s] = lastSub; c.seed[s] = seed; c.dead[s] = dead; }
 }
 
-size_t ulcx_dec_lds_bytes(int BS, int C, int fast, int twInLds) {
-    DsynLds l = dsyn_lds(BS, C, fast, twInLds);
-    return sizeof(float) * ((size_t)l.zFloats + l.lapFloats + l.twFloats + l.listFloats);
+size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds) {
+    DsynLds l = dsyn_lds(BS, fast, twInLds);
+    return sizeof(float) * ((size_t)l.zFloats + l.twFloats + l.listFloats);
 }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ulcx_set_error("%s: %s", #x, hipGetErrorString(e_)); return ULCX_ERR_HIP; } } while (0)
 
-// resident workgroups of the stereo synthesis kernel this context runs (float output; the PCM16 instantiation has the same
-// resources): what an even cut of the batch is sized for
-// the instantiation launch_syn() starts for this context (the one whose occupancy and dynamic-LDS attribute count)
-template <typename OUT>
-static const void *syn_fn(const UlcxDecCtx &cc, bool split) {
-    const bool small = cc.BS <= 2048;
-    if (!cc.fastOK) return (const void *)k_dgen<OUT>;
-    if (cc.BS == 2048 && DSYN_C2048) return split ? (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, true, 2048> : (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, false, 2048>;
-    if (small) return split ? (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, true> : (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, false>;
-    if (cc.BS == 4096 && DSYN_C4096) return split ? (const void *)k_dsyn<OUT, 32, false, true, 4096> : (const void *)k_dsyn<OUT, 32, false, false, 4096>;
-    return split ? (const void *)k_dsyn<OUT, 32, false, true> : (const void *)k_dsyn<OUT, 32, false, false>;
+// The synthesis instantiation of a context, THE one place that maps a geometry to its kernel: what is launched, what has
+// its dynamic-LDS limit raised and what is asked for its occupancy are this pointer.
+template <typename OUT, bool SPLIT, bool RANGE>
+static const void *syn_pick(const UlcxDecCtx &cc) {
+    constexpr bool TW = DSYN_TWL != 0;
+    if (!cc.fastOK) return (const void *)k_dgen<OUT, RANGE>;
+    if (cc.BS == 2048 && DSYN_C2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 2048, RANGE>;
+    if (cc.BS <= 2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 0, RANGE>;
+    if (cc.BS == 4096 && DSYN_C4096) return (const void *)k_dsyn<OUT, 32, false, SPLIT, 4096, RANGE>;
+    return (const void *)k_dsyn<OUT, 32, false, SPLIT, 0, RANGE>;
 }
+// split: the grid is a cut of the (stream, block) pairs; range: a range call, which runs the cut form for every grid
+template <typename OUT>
+static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range) {
+    return range ? syn_pick<OUT, true, true>(cc) : split ? syn_pick<OUT, true, false>(cc) : syn_pick<OUT, false, false>(cc);
+}
+// A launch with more than 48 KiB of dynamic LDS: raise the kernel's limit to this launch's size (ulcx_enc.hip: allow_lds).
+static hipError_t allow_lds(const void *fn, size_t lds) {
+    return lds > 48 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
+
+// resident workgroups of the stereo synthesis kernel this context runs: what an even cut of the batch is sized for
 int ulcx_dec_syn_slots(const UlcxDecCtx &c) {
     if (!c.fastOK) return 0;
     // what a cut would launch: the float and the PCM16 instantiation are both asked, the smaller residency sizes the cut
-    const void *fns[2] = { syn_fn<float>(c, true), syn_fn<int16_t>(c, true) };
-    const size_t lds = ulcx_dec_lds_bytes(c.BS, c.C, c.fastOK, c.twInLds);
+    const void *fns[2] = { syn_fn<float>(c, true, false), syn_fn<int16_t>(c, true, false) };
+    const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds);
     int dev = 0, cus = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
     for (const void *fn : fns) {
         int p1 = 0;
-        if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p1, fn, WG, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        if (allow_lds(fn, lds) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&p1, fn, WG, lds) != hipSuccess) { (void)hipGetLastError(); return 0; }
         per = (fn == fns[0] || p1 < per) ? p1 : per;
     }
     return cus * per;
@@ -1408,46 +1377,24 @@ int ulcx_dec_syn_slots(const UlcxDecCtx &c) {
 // Two kernels on the caller's stream: the syntax walk, then the synthesis.  (Measured and dropped, profiles/NOTES_r01-r04.md:
 // the walk of a chunk of streams / of the second half of the blocks beside the synthesis of the previous one - the
 // synthesis slows down by more than the walk it hides.)
-template <typename OUT>
-static void launch_syn(const UlcxDecCtx &cc, unsigned g, size_t lds, hipStream_t s2, bool split) {
-    const bool small = cc.BS <= 2048;
-    if (!cc.fastOK) hipLaunchKernelGGL(k_dgen<OUT>, dim3(g), dim3(WG), lds, s2, cc);
-    else if (cc.BS == 2048 && DSYN_C2048) { if (split) hipLaunchKernelGGL((k_dsyn<OUT, 16, DSYN_TWL != 0, true, 2048>), dim3(g), dim3(WG), lds, s2, cc); else hipLaunchKernelGGL((k_dsyn<OUT, 16, DSYN_TWL != 0, false, 2048>), dim3(g), dim3(WG), lds, s2, cc); }
-    else if (small) { if (split) hipLaunchKernelGGL((k_dsyn<OUT, 16, DSYN_TWL != 0, true>), dim3(g), dim3(WG), lds, s2, cc); else hipLaunchKernelGGL((k_dsyn<OUT, 16, DSYN_TWL != 0, false>), dim3(g), dim3(WG), lds, s2, cc); }
-    else if (cc.BS == 4096 && DSYN_C4096) { if (split) hipLaunchKernelGGL((k_dsyn<OUT, 32, false, true, 4096>), dim3(g), dim3(WG), lds, s2, cc); else hipLaunchKernelGGL((k_dsyn<OUT, 32, false, false, 4096>), dim3(g), dim3(WG), lds, s2, cc); }
-    else { if (split) hipLaunchKernelGGL((k_dsyn<OUT, 32, false, true>), dim3(g), dim3(WG), lds, s2, cc); else hipLaunchKernelGGL((k_dsyn<OUT, 32, false, false>), dim3(g), dim3(WG), lds, s2, cc); }
-}
-// the instantiation a range call's synthesis runs (the cut form of the stereo kernel for every grid)
-template <typename OUT>
-static const void *syn_fn_range(const UlcxDecCtx &cc) {
-    if (!cc.fastOK) return (const void *)k_dgen<OUT, true>;
-    if (cc.BS == 2048 && DSYN_C2048) return (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, true, 2048, true>;
-    if (cc.BS <= 2048) return (const void *)k_dsyn<OUT, 16, DSYN_TWL != 0, true, 0, true>;
-    if (cc.BS == 4096 && DSYN_C4096) return (const void *)k_dsyn<OUT, 32, false, true, 4096, true>;
-    return (const void *)k_dsyn<OUT, 32, false, true, 0, true>;
-}
 int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux) {
     int stage = 0;
     if (ev) CK(hipEventRecord(ev[stage++], st));
     UlcxDecCtx c = cIn;
     c.s0 = 0; c.s1 = c.B; c.k0 = c.range ? 1 : 0; c.k1 = c.K;
-    const size_t lds = ulcx_dec_lds_bytes(c.BS, c.C, c.fastOK, c.twInLds);
-    const void *fnRange = !c.range ? nullptr : c.pcm16 ? syn_fn_range<int16_t>(c) : syn_fn_range<float>(c);
-    if (lds > 48 * 1024) {
-        const bool split = c.fastOK && aux.synGrid > 0;
-        const void *fn = c.range ? fnRange : c.pcm16 ? syn_fn<int16_t>(c, split) : syn_fn<float>(c, split);
-        CK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds);
+    const bool split = c.fastOK && aux.synGrid > 0;
+    const void *syn = c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0) : syn_fn<float>(c, split, c.range != 0);
+    CK(allow_lds(syn, lds));
     if (c.range) hipLaunchKernelGGL(k_dscan_range, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     if (ev) CK(hipEventRecord(ev[stage++], st));
     if (!(ULCX_DBG(c) & 8)) {
-        const bool split = c.fastOK && aux.synGrid > 0;
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
         c.synFull = split ? aux.synFull : (c.range && c.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
-        if (c.range) { void *args[] = { &c }; CK(hipLaunchKernel(fnRange, dim3(g), dim3(WG), args, lds, st)); }
-        else if (c.pcm16) launch_syn<int16_t>(c, g, lds, st, split); else launch_syn<float>(c, g, lds, st, split);
+        void *args[] = { &c };
+        CK(hipLaunchKernel(syn, dim3(g), dim3(WG), args, lds, st));
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));
     CK(hipGetLastError());

@@ -149,7 +149,7 @@ struct UlcxDecCtx {
     float *scratch;                      // [B][4*BS] general-path staging of time samples (decimated / non-stereo blocks)
     const uint32_t *jumpT;               // [8][16][4][256] byte tables of T^(d*16^i), T = one xorshift32 step
     const uint32_t *parT;                // [4][256][64] byte tables, lane fastest: a lane's word of a unit's sign-parity stream from the unit's start state
-    int    fastOK, twInLds;              // stereo fast path / FFT twiddles resident in LDS
+    int    fastOK, twInLds;              // stereo fast path / its FFT twiddles resident in LDS (0 or 1)
     // packed-stream mode (.ulc payloads): blocks are located by parsing, not by slot
     int   packed;
     long long payStride;                 // bytes between stream payloads
@@ -217,7 +217,7 @@ struct UlcxDecAux {
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
 int ulcx_index_launch(const UlcxDecCtx &c, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, hipStream_t st);
-size_t ulcx_dec_lds_bytes(int BS, int C, int fast, int twInLds);
+size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds);
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
