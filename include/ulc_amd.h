@@ -135,8 +135,8 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
  *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_index (an entry is two
  *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n])
- *    none     the byte streams: d_out, d_in, d_payload and ulcx_pack_streams_dev's d_slots (slotBytes and payloadStride may be
- *             any positive value)
+ *    none     the byte streams: d_out, d_in, d_payload and the d_slots of ulcx_pack_streams_dev and ulcx_index_slots_dev
+ *             (slotBytes and payloadStride may be any positive value)
  *   A pointer that violates this makes the call return ULCX_ERR_ARG before any device work; the object's state is untouched
  *   and the next valid call continues as if the refused one had not been made.  (hipMalloc and the allocators built on it
  *   return 256-byte aligned memory: only pointers INTO an allocation can fail this.)
@@ -493,6 +493,54 @@ int  ulcx_decode_range_host(ulcx_decoder *dec, const uint8_t *h_payload, long lo
  * (h_nBlocks [nStreams], optional: the block counts), then any range is decoded from it.  A new upload drops the index. */
 int  ulcx_decoder_index_resident(ulcx_decoder *dec, int maxBlocks, int32_t *h_nBlocks);
 int  ulcx_decode_resident_range_host(ulcx_decoder *dec, const int32_t *h_first, int nBlocks, float *h_pcm, int32_t *h_bits);
+
+/* Index while encoding: the same table, grown call by call from what an encode call wrote - every block in its own slot,
+ * its size in d_bits - so all of a call's blocks are parsed side by side and nothing is walked in series.  The result is,
+ * entry for entry, what ulcx_index_packed_dev builds from the same blocks after ulcx_pack_streams_dev.
+ * The decoder object supplies the geometry (nChan, BlockSize) and the tables only: nRows is an argument of its own, not the
+ * decoder's nStreams (a one-stream decoder indexes 4096 rows; the [n] rows of a subset call; a ladder call's
+ * [nRungs][nStreams] output as nRungs * nStreams rows in one call).  No stream state is read or changed, none of the
+ * per-block scratch is used (nBlocks is not limited by maxBlocksPerCall) and nothing is allocated.
+ *   ulcx_index_begin_dev  opens nRows rows: entry 0 = {0, 1234567}, entries 1 .. indexStride-1 = {-1, 0}, d_nBlocks[s] = 0.
+ *   ulcx_index_slots_dev  appends.  Row s, with n0 = d_nBlocks[s] on entry: m = the leading blocks k of the row for which
+ *       d_bits[k] > 0 and d_bits[k] / 8 <= slotBytes; the walk of slot k, limited to d_bits[k] bits, is valid and consumes
+ *       (bits + 7) / 8 == d_bits[k] / 8 bytes; n0 + k + 1 <= indexStride - 1; and the new ByteOffs fits in an int32.
+ *       Entries n0+1 .. n0+m receive the running byte offset and the generator state (continued from entry n0's), entries
+ *       n0+m+1 .. min(n0 + nBlocks, indexStride - 1) are written {-1, 0}, d_nBlocks[s] = n0 + m.  A row whose n0 is outside
+ *       [0, indexStride - 1] is left untouched, count included.  A stream that is shorter in a call (d_bits 0 from some
+ *       block on) stops growing there; a later call appends behind it.
+ *   d_slots [nRows][nBlocks][slotBytes], d_bits [nRows][nBlocks] (multiples of 8, as the encoder writes them),
+ *   d_index [nRows][indexStride], d_nBlocks [nRows].  ALIGNMENT / EXTENT / ORDER as for every _dev call.
+ * The _host form is synchronous (h_index and h_nBlocks are read and written); it refuses an h_nBlocks entry outside
+ * [0, indexStride - 1] with ULCX_ERR_ARG before any device work. */
+int  ulcx_index_begin_dev(ulcx_decoder *dec, int nRows, ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, void *hipStream);
+int  ulcx_index_slots_dev(ulcx_decoder *dec, int nRows, const uint8_t *d_slots, int slotBytes, const int32_t *d_bits, int nBlocks,
+                          ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, void *hipStream);
+int  ulcx_index_slots_host(ulcx_decoder *dec, int nRows, const uint8_t *h_slots, int slotBytes, const int32_t *h_bits, int nBlocks,
+                           ulcx_index_entry *h_index, int indexStride, int32_t *h_nBlocks);
+/* Host code, no GPU: is `row` (indexStride entries, nBlocks of them blocks) an index a range call may be given for a payload
+ * of payloadBytes?  Entry 0 = {0, 1234567}, ByteOffs strictly increasing over entries 0 .. nBlocks, the closing offset
+ * <= payloadBytes, 0 <= nBlocks < indexStride.  Returns 0 or ULCX_ERR_ARG. */
+int  ulcx_index_check(const ulcx_index_entry *row, int nBlocks, int indexStride, long long payloadBytes);
+/* A stored index for the payload uploaded with ulcx_decoder_upload_payload, in place of ulcx_decoder_index_resident (no walk):
+ * h_index [nStreams][indexStride], h_nBlocks [nStreams].  Every row must pass ulcx_index_check against its stream's uploaded
+ * payload size (ULCX_ERR_ARG otherwise: the decoder is as it was, an index it had included).  A new upload drops the index. */
+int  ulcx_decoder_set_resident_index(ulcx_decoder *dec, const ulcx_index_entry *h_index, int indexStride, const int32_t *h_nBlocks);
+
+/* `.ulx` sidecar: the block index of ONE `.ulc` file, written beside it (stem.ulx).  16-byte little-endian header, then
+ * nBlocks + 1 entries of 8 bytes (ByteOffs, RngState; offsets relative to the .ulc file's StreamOffs).  The `.ulc` container
+ * itself stays the reference's. */
+#define ULCX_ULX_MAGIC 0x31584C55u            /* 'U' | 'L'<<8 | 'X'<<16 | '1'<<24 */
+#define ULCX_ULX_HEADER_BYTES 16
+typedef struct ulcx_index_file_header {
+    uint32_t Magic;
+    uint16_t BlockSize;
+    uint16_t nChan;
+    uint32_t nBlocks;                          /* blocks indexed: nBlocks + 1 entries follow */
+    uint32_t PayloadBytes;                     /* size of the .ulc file's payload the index was made for */
+} ulcx_index_file_header;
+void ulcx_ulx_header_pack(uint8_t dst[16], const ulcx_index_file_header *h);
+int  ulcx_ulx_header_parse(ulcx_index_file_header *h, const uint8_t *src, size_t len);   /* 0 ok, ULCX_ERR_ARG: short / bad magic */
 
 /* Timing helper for bench.py: device time (ms, hipEvent) of the kernels the last
  * ulcx_*_dev call enqueued, per pipeline stage; returns number of stages written.

@@ -1,7 +1,7 @@
 /*
  * ulcx_tool.c — batched front-end over libulc_amd.so.
  *
- *   ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav [-rate:RATE[,AvgComplexity]] IN2.wav ...
+ *   ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] [-index] IN1.wav [-rate:RATE[,AvgComplexity]] IN2.wav ...
  *   ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-blocks:FIRST,COUNT] [-devices:N] IN1.ulc IN2.ulc ...
  *   ulcx-tool analyse [-blocksize:N] [-devices:N]                            IN1.wav IN2.wav ...
  *
@@ -33,6 +33,13 @@
  * header counts fewer), exactly the bytes a full decode writes for them: the payloads are indexed once on the device
  * (ulcx_decoder_index_resident), then decoded by range calls (ulcx_decode_resident_range_host) - nothing in front of FIRST
  * but one block is synthesised.
+ *
+ * -index (encode): a block index beside every file written - OUTDIR/stem.ulx, OUTDIR/stem.r<i>.ulx per rung of a ladder
+ * (include/ulc_amd.h section 3, `.ulx`).  It grows with the encoder's output: after every encode call the call's blocks, still
+ * in their slots, are indexed side by side (ulcx_index_slots_host, all rungs' rows in one call); the file is never walked.
+ * decode -blocks: loads IN.ulx from beside IN.ulc when every input has one whose header agrees with the `.ulc` header and
+ * which passes ulcx_index_check against the payload's size (ulcx_decoder_set_resident_index); otherwise it indexes the
+ * payloads as before and says so on stderr.  The bytes written are the same either way.
  *
  * -devices:N (independent streams shard by plain batch split, one host thread per device, no collective): the
  * inputs are dealt round-robin over N groups, every group gets its own encoder / decoder and its own host thread; group g
@@ -125,7 +132,8 @@ static void out_path(char *dst, size_t n, const char *dir, const char *in, const
  * encode: rung r of file i is encoded under {RateKbps, AvgComplexity} = setting[i * ULCX_MAX_RUNGS + r], r < nRungs;
  * autoc[...] = 1: "RATE,auto" (two passes) */
 struct group { int decode, analyse, device, n; char **files; const char *outdir; ulcx_rate *setting; int *autoc; int nRungs; int bs, isFloat; int rc;
-               int32_t rFirst, rCount; /* decode -blocks:FIRST,COUNT (rCount 0: whole files) */ };
+               int32_t rFirst, rCount; /* decode -blocks:FIRST,COUNT (rCount 0: whole files) */
+               int index; /* encode -index: write stem.ulx beside every stem.ulc */ };
 
 /* "RATE[,AvgComplexity]" or "RATE,auto", validated as ulcEncodeTool.c:43-50 does (and finite: the library refuses the rest) */
 static int parse_rate(const char *s, ulcx_rate *r, int *isAuto) {
@@ -249,6 +257,22 @@ static int encode_group(const struct group *g) {
     uint64_t *total = (uint64_t *)calloc((size_t)R * B, sizeof(uint64_t));
     uint32_t *maxb = (uint32_t *)calloc((size_t)R * B, sizeof(uint32_t));
     char path[1024];
+    /* -index: one row per (rung, file) in the order of the call's output, grown after every encode call.  The decoder object
+     * lends its geometry and tables only (one stream, one block per call). */
+    const int nRows = R * B, iStride = (int)maxBlk + 1;
+    ulcx_decoder *idec = NULL;
+    ulcx_index_entry *idx = NULL; int32_t *idxN = NULL, *ibits = NULL;
+    if (g->index) {
+        if (ulcx_decoder_create(&idec, g->device, 1, C, bs, 1) != ULCX_OK) DIE("index: %s", ulcx_last_error());
+        idx = (ulcx_index_entry *)malloc(sizeof(ulcx_index_entry) * (size_t)nRows * iStride);
+        idxN = (int32_t *)calloc((size_t)nRows, sizeof(int32_t));
+        ibits = (int32_t *)malloc(sizeof(int32_t) * (size_t)nRows * KBLOCKS);
+        if (!idx || !idxN || !ibits) DIE("out of memory");
+        for (size_t i = 0; i < (size_t)nRows * iStride; i++) {                       /* an open index, as ulcx_index_begin_dev leaves it */
+            const int head = i % (size_t)iStride == 0;
+            idx[i].ByteOffs = head ? 0 : -1; idx[i].RngState = head ? 1234567u : 0u;
+        }
+    }
     if (anyAuto) {
         /* "RATE,auto": pass 1 (analysis only: BlockComplexity does not depend on the rate mode, so every auto rung of a
          * ladder shares it) sums each file's complexity over its own blocks in block order in double precision
@@ -306,6 +330,15 @@ static int encode_group(const struct group *g) {
                 cplxSum[s] += cplx[s * K + k];
             }
         }
+        if (g->index) {
+            /* a file that has ended stops growing: size 0 from its last block on (the encoder goes on coding silence for it) */
+            for (int r = 0; r < R; r++)
+                for (int s = 0; s < B; s++) {
+                    const uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
+                    for (int k = 0; k < K; k++) { const size_t at = ((size_t)r * B + s) * K + k; ibits[at] = k0 + (uint32_t)k < nb ? bits[at] : 0; }
+                }
+            if (ulcx_index_slots_host(idec, nRows, out, slot, ibits, K, idx, iStride, idxN) != ULCX_OK) DIE("index: %s", ulcx_last_error());
+        }
     }
     for (int s = 0; s < B; s++) {
         uint32_t nb = (w[s].nFrames + (uint32_t)bs - 1) / (uint32_t)bs + 2;
@@ -318,6 +351,25 @@ static int encode_group(const struct group *g) {
             h.RateKbps = (uint16_t)ulcx_ulc_rate_kbps(total[i], (uint32_t)hz, (uint32_t)bs, nb);
             uint8_t hb[24]; ulcx_ulc_header_pack(hb, &h);
             fseek(fo[i], 0, SEEK_SET); fwrite(hb, 1, 24, fo[i]); fclose(fo[i]);
+            if (g->index) {
+                char ext[32] = ".ulx";
+                if (R > 1) snprintf(ext, sizeof(ext), ".r%d.ulx", r);
+                out_path(path, sizeof(path), outdir, argv[a + s], ext);
+                FILE *fx = fopen(path, "wb");
+                if (!fx) DIE("cannot create '%s'", path);
+                if ((uint32_t)idxN[i] != nb) fprintf(stderr, "ulcx-tool: %s: %d of %u blocks indexed\n", path, (int)idxN[i], nb);
+                ulcx_index_file_header xh;
+                xh.Magic = ULCX_ULX_MAGIC; xh.BlockSize = (uint16_t)bs; xh.nChan = (uint16_t)C; xh.nBlocks = (uint32_t)idxN[i]; xh.PayloadBytes = (uint32_t)total[i];
+                uint8_t xb[ULCX_ULX_HEADER_BYTES]; ulcx_ulx_header_pack(xb, &xh);
+                fwrite(xb, 1, sizeof(xb), fx);
+                for (int k = 0; k <= idxN[i]; k++) {                                   /* little-endian, whatever the host is */
+                    const ulcx_index_entry *en = &idx[(size_t)i * iStride + k];
+                    const uint32_t o = (uint32_t)en->ByteOffs, st = en->RngState;
+                    const uint8_t eb[8] = { (uint8_t)o, (uint8_t)(o >> 8), (uint8_t)(o >> 16), (uint8_t)(o >> 24), (uint8_t)st, (uint8_t)(st >> 8), (uint8_t)(st >> 16), (uint8_t)(st >> 24) };
+                    fwrite(eb, 1, 8, fx);
+                }
+                fclose(fx);
+            }
             char used[64] = "";                                                        /* "RATE,auto": the complexity pass 2 used */
             if (g->autoc[s * ULCX_MAX_RUNGS + r]) snprintf(used, sizeof(used), "ABR complexity %.9g%s", (double)table[i].AvgComplexity, table[i].AvgComplexity > 0.0f ? "" : " (CBR)");
             if (R > 1) printf("; r%d: %.2f KiB, %u kbps%s%s", r, total[i] / 1024.0, h.RateKbps, used[0] ? ", " : "", used);
@@ -328,8 +380,43 @@ static int encode_group(const struct group *g) {
         fclose(w[s].f);
     }
     ulcx_encoder_destroy(enc);
+    if (idec) ulcx_decoder_destroy(idec);
+    free(idx); free(idxN); free(ibits);
     free(pcm); free(out); free(bits); free(cplx); free(cplxSum); free(tmp); free(fo); free(total); free(maxb); free(w); free(table);
     return 0;
+}
+
+/* The `.ulx` beside a `.ulc` input: its entries (caller frees) when the header agrees with the container's and the index
+ * passes ulcx_index_check against the payload's size; NULL and a reason otherwise. */
+static ulcx_index_entry *load_sidecar(const char *ulcPath, const ulcx_file_header *h, int32_t payBytes, const char **why) {
+    char path[1024];
+    const size_t n = strlen(ulcPath);
+    *why = "no .ulx beside it";
+    if (n < 4 || n + 1 > sizeof(path) || strcmp(ulcPath + n - 4, ".ulc")) return NULL;
+    memcpy(path, ulcPath, n + 1); path[n - 1] = 'x';
+    FILE *f = fopen(path, "rb");
+    if (!f) return NULL;
+    uint8_t hb[ULCX_ULX_HEADER_BYTES];
+    ulcx_index_file_header xh;
+    ulcx_index_entry *ent = NULL;
+    *why = "its .ulx is short or not a block index";
+    if (fread(hb, 1, sizeof(hb), f) == sizeof(hb) && ulcx_ulx_header_parse(&xh, hb, sizeof(hb)) == ULCX_OK) {
+        *why = "its .ulx was made for another file (header mismatch)";
+        if (xh.BlockSize == h->BlockSize && xh.nChan == h->nChan && xh.nBlocks == h->nBlocks && xh.PayloadBytes == (uint32_t)payBytes) {
+            const size_t cnt = (size_t)xh.nBlocks + 1;
+            uint8_t *raw = (uint8_t *)malloc(cnt * 8);
+            ent = (ulcx_index_entry *)malloc(cnt * sizeof(*ent));
+            *why = "its .ulx is short or not a block index";
+            if (raw && ent && fread(raw, 8, cnt, f) == cnt) {
+                for (size_t k = 0; k < cnt; k++) { ent[k].ByteOffs = (int32_t)rd32(raw + 8 * k); ent[k].RngState = rd32(raw + 8 * k + 4); }
+                *why = "its .ulx does not pass ulcx_index_check";
+                if (ulcx_index_check(ent, (int)xh.nBlocks, (int)cnt, payBytes) != ULCX_OK) { free(ent); ent = NULL; }
+            } else { free(ent); ent = NULL; }
+            free(raw);
+        }
+    }
+    fclose(f);
+    return ent;
 }
 
 static int decode_group(const struct group *g) {
@@ -401,7 +488,37 @@ static int decode_group(const struct group *g) {
     int rcAll = 0;
     /* (a range call runs the block in front of its range too: one block fewer per call) */
     const uint32_t step = range ? KBLOCKS - 1 : KBLOCKS, blk0 = range ? (uint32_t)g->rFirst : 0;
-    if (range && ulcx_decoder_index_resident(dec, (int)(blk0 + total), NULL) != ULCX_OK) DIE("index: %s", ulcx_last_error());   /* once */
+    if (range) {
+        /* stored indexes when every input has a usable one, else the walk (once) */
+        ulcx_index_entry **side = (ulcx_index_entry **)calloc((size_t)B, sizeof(*side));
+        int have = 1;
+        for (int s = 0; s < B && have; s++) {
+            const char *why = "";
+            side[s] = load_sidecar(argv[a + s], &h[s], payBytes[s], &why);
+            if (!side[s]) { fprintf(stderr, "ulcx-tool: %s: %s: indexing the payloads\n", argv[a + s], why); have = 0; }
+        }
+        if (have) {
+            const int iStride = (int)maxBlk + 1;
+            ulcx_index_entry *rows = (ulcx_index_entry *)malloc(sizeof(*rows) * (size_t)B * iStride);
+            int32_t *cnt = (int32_t *)malloc(sizeof(int32_t) * (size_t)B);
+            if (!rows || !cnt) DIE("out of memory");
+            for (int s = 0; s < B; s++) {
+                cnt[s] = (int32_t)h[s].nBlocks;
+                for (int k = 0; k < iStride; k++) {
+                    ulcx_index_entry *e = &rows[(size_t)s * iStride + k];
+                    if ((uint32_t)k <= h[s].nBlocks) *e = side[s][k]; else { e->ByteOffs = -1; e->RngState = 0u; }
+                }
+            }
+            if (ulcx_decoder_set_resident_index(dec, rows, iStride, cnt) != ULCX_OK) {
+                fprintf(stderr, "ulcx-tool: stored block index refused (%s): indexing the payloads\n", ulcx_last_error());
+                have = 0;
+            }
+            free(rows); free(cnt);
+        }
+        for (int s = 0; s < B; s++) free(side[s]);
+        free(side);
+        if (!have && ulcx_decoder_index_resident(dec, (int)(blk0 + total), NULL) != ULCX_OK) DIE("index: %s", ulcx_last_error());
+    }
     for (uint32_t k0 = 0; k0 < total; k0 += step) {
         int K = (total - k0 < step) ? (int)(total - k0) : (int)step;
         if (range) {
@@ -502,7 +619,7 @@ static int parse_rate_group(const char *arg, ulcx_rate *cur, int *curAuto, int n
     return 0;
 }
 static int do_encode(int argc, char **argv) {
-    if (argc < 5) DIE("usage: ulcx-tool encode OUTDIR RATE[,AvgComplexity|,auto][/RATE...] [-blocksize:N] [-devices:N] IN.wav [-rate:RATE[,...][/RATE...]] IN.wav ...");
+    if (argc < 5) DIE("usage: ulcx-tool encode OUTDIR RATE[,AvgComplexity|,auto][/RATE...] [-blocksize:N] [-devices:N] [-index] IN.wav [-rate:RATE[,...][/RATE...]] IN.wav ...");
     struct group g; memset(&g, 0, sizeof(g));
     g.outdir = argv[2];
     ulcx_rate cur[ULCX_MAX_RUNGS]; int curAuto[ULCX_MAX_RUNGS];
@@ -515,6 +632,7 @@ static int do_encode(int argc, char **argv) {
         if (!strcmp(argv[a], "--")) { a++; endOpts = 1; break; }    /* end of options: input names may start with '-' behind it */
         if (!strncmp(argv[a], "-blocksize:", 11)) g.bs = atoi(argv[a] + 11);
         else if (!strncmp(argv[a], "-devices:", 9)) nDev = atoi(argv[a] + 9);
+        else if (!strcmp(argv[a], "-index")) g.index = 1;
         else if (!strncmp(argv[a], "-rate:", 6)) { if (parse_rate_group(argv[a], cur, curAuto, g.nRungs)) return 2; }
         else DIE("unknown option '%s'", argv[a]);
     }
@@ -585,13 +703,14 @@ int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "analyse")) return do_analyse(argc, argv);
     fprintf(stderr,
             "ulcx-tool - batched ulc-codec front-end over libulc_amd.so (MI355X)\n"
-            "  ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] IN1.wav [-rate:RATE[,...]] IN2.wav ...\n"
+            "  ulcx-tool encode OUTDIR RATE[,AvgComplexity] [-blocksize:N] [-devices:N] [-index] IN1.wav [-rate:RATE[,...]] IN2.wav ...\n"
             "      RATE < 0: VBR quality; RATE > 0: CBR kbps; RATE,AvgComplexity: ABR  (as ulcencodetool)\n"
             "      RATE,auto: two-pass ABR at each file's own average complexity (0: CBR)\n"
             "      -rate:RATE[,AvgComplexity|,auto]  setting of the inputs that follow it (RATE is the default)\n"
+            "      -index  write a block index OUTDIR/stem.ulx (stem.r<i>.ulx) beside every file, grown from the encoder's output\n"
             "      R0/R1/.../Rn (RATE and every -rate:, the same count): a ladder, one OUTDIR/stem.r<i>.ulc per rung from one call\n"
             "  ulcx-tool decode OUTDIR [-format:PCM16|FLOAT32] [-blocks:FIRST,COUNT] [-devices:N] IN1.ulc IN2.ulc ...\n"
-            "      -blocks:FIRST,COUNT  only blocks FIRST .. FIRST+COUNT-1 of every file (block index + range decode)\n"
+            "      -blocks:FIRST,COUNT  only blocks FIRST .. FIRST+COUNT-1 of every file (block index + range decode; IN.ulx is used when present)\n"
             "  ulcx-tool analyse [-blocksize:N] [-devices:N] IN1.wav IN2.wav ...\n"
             "      per file: blocks, the average complexity to feed RATE,<complexity> with, window-switched blocks; writes no file\n"
             "  --          end of options (input names that start with '-')\n"

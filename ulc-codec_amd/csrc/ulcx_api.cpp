@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <string>
 #include <vector>
 #include "ulcx_internal.h"
 #include "ulcx_rng_tables.h"
@@ -1260,6 +1261,18 @@ extern "C" int ulcx_ulc_header_parse(ulcx_file_header *h, const uint8_t *src, si
     if (h->Magic != ULCX_ULC_MAGIC) return refuse("ulcx_ulc_header_parse", "not a ULC2 container");   /* ulcDecodeTool.c:77-80 */
     return ULCX_OK;
 }
+// `.ulx` sidecar (include/ulc_amd.h): 16 bytes in front of a file's index entries
+extern "C" void ulcx_ulx_header_pack(uint8_t dst[16], const ulcx_index_file_header *h) {
+    put32(dst + 0x00, h->Magic); put16(dst + 0x04, h->BlockSize); put16(dst + 0x06, h->nChan);
+    put32(dst + 0x08, h->nBlocks); put32(dst + 0x0C, h->PayloadBytes);
+}
+extern "C" int ulcx_ulx_header_parse(ulcx_index_file_header *h, const uint8_t *src, size_t len) {
+    if (!h || !src || len < ULCX_ULX_HEADER_BYTES) return refuse("ulcx_ulx_header_parse", "need 16 bytes");
+    h->Magic = get32(src); h->BlockSize = (uint16_t)get16(src + 4); h->nChan = (uint16_t)get16(src + 6);
+    h->nBlocks = get32(src + 8); h->PayloadBytes = get32(src + 12);
+    if (h->Magic != ULCX_ULX_MAGIC) return refuse("ulcx_ulx_header_parse", "not a ULX1 block index");
+    return ULCX_OK;
+}
 extern "C" int ulcx_ulc_rate_kbps(uint64_t totalBytes, uint32_t RateHz, uint32_t BlockSize, uint32_t nBlocks) {
     double avg = (double)totalBytes * 8.0 * RateHz / 1000.0 / ((double)BlockSize * nBlocks);          /* ulcEncodeTool.c:173,190 */
     return (int)lrint(avg);
@@ -1461,6 +1474,90 @@ extern "C" int ulcx_decode_resident_range_host(ulcx_decoder *e, const int32_t *h
     CKR(hipMemcpy(e->d_first, h_first, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
     rc = decode_range_any(who, e, e->d_pay, e->payStride, e->d_payBytes, e->d_index, e->idxStride, e->d_idxBlocks, e->d_first, nBlocks, e->d_pcm, nullptr, e->d_bits, nullptr);
     return rc ? rc : dec_results_down(e, e->d_pcm, e->d_bits, (size_t)e->B * nBlocks, h_pcm, h_bits);
+}
+
+// ---- index while encoding (include/ulc_amd.h section 3): index_rows_any is the body of begin (slots == nullptr) and append.
+// The decoder comes last among the checks: every other refusal needs no object (and so no device) to be seen.
+static int index_rows_any(const char *who, ulcx_decoder *e, int nRows, bool append, const uint8_t *d_slots, int slotBytes, const int32_t *d_bits, int nBlocks,
+                          ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, void *hipStream) {
+    if (nRows < 1 || indexStride < 1 || !d_index || !d_nBlocks) return refuse(who, "bad argument (nRows %d, indexStride %d, or no index / counts)", nRows, indexStride);
+    if (append && (!d_slots || !d_bits || slotBytes < 1 || nBlocks < 1)) return refuse(who, "bad argument (slotBytes %d, nBlocks %d, or no slots / sizes)", slotBytes, nBlocks);
+    if (misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_nBlocks", d_nBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    // (one lane per block in a grid of 2^31 - 1 workgroups at the most: d_bits alone would be 512 GB)
+    if (append && (long long)nRows * nBlocks > (0x7FFFFFFFLL << 6)) return refuse(who, "%d rows of %d blocks are more than one call takes", nRows, nBlocks);
+    if ((long long)nRows * indexStride > (0x7FFFFFFFLL << 8)) return refuse(who, "%d rows of %d entries are more than one call takes", nRows, indexStride);
+    if (!e) return refuse(who, "no decoder");
+    CKR(hipSetDevice(e->device));
+    if (!append) return ulcx_index_begin_launch(nRows, d_index, indexStride, d_nBlocks, (hipStream_t)hipStream);
+    UlcxDecCtx c = e->ctx;
+    c.in = d_slots; c.slot = slotBytes; c.inBytes = (long long)nRows * nBlocks * slotBytes;
+    return ulcx_index_slots_launch(c, nRows, nBlocks, d_bits, d_index, indexStride, d_nBlocks, (hipStream_t)hipStream);
+}
+extern "C" int ulcx_index_begin_dev(ulcx_decoder *e, int nRows, ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, void *hipStream) {
+    return index_rows_any("ulcx_index_begin_dev", e, nRows, false, nullptr, 0, nullptr, 0, d_index, indexStride, d_nBlocks, hipStream);
+}
+extern "C" int ulcx_index_slots_dev(ulcx_decoder *e, int nRows, const uint8_t *d_slots, int slotBytes, const int32_t *d_bits, int nBlocks,
+                                    ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, void *hipStream) {
+    return index_rows_any("ulcx_index_slots_dev", e, nRows, true, d_slots, slotBytes, d_bits, nBlocks, d_index, indexStride, d_nBlocks, hipStream);
+}
+extern "C" int ulcx_index_slots_host(ulcx_decoder *e, int nRows, const uint8_t *h_slots, int slotBytes, const int32_t *h_bits, int nBlocks,
+                                     ulcx_index_entry *h_index, int indexStride, int32_t *h_nBlocks) {
+    const char *who = "ulcx_index_slots_host";
+    if (nRows < 1 || indexStride < 1 || !h_index || !h_nBlocks || !h_slots || !h_bits || slotBytes < 1 || nBlocks < 1) return refuse(who, "bad argument");
+    for (int s = 0; s < nRows; s++)
+        if (h_nBlocks[s] < 0 || h_nBlocks[s] > indexStride - 1) return refuse(who, "row %d counts %d blocks, outside 0 .. indexStride - 1 = %d", s, (int)h_nBlocks[s], indexStride - 1);
+    if (!e) return refuse(who, "no decoder");
+    CKR(hipSetDevice(e->device));
+    const size_t NB = (size_t)nRows * nBlocks, nEnt = (size_t)nRows * (size_t)indexStride;
+    DevTmp t; uint8_t *ds = nullptr; int32_t *db = nullptr, *dcnt = nullptr; ulcx_index_entry *di = nullptr;
+    CKR(t.get(&ds, NB * (size_t)slotBytes)); CKR(t.get(&db, sizeof(int32_t) * NB));
+    CKR(t.get(&dcnt, sizeof(int32_t) * nRows)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    CKR(hipMemcpy(ds, h_slots, NB * (size_t)slotBytes, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(db, h_bits, sizeof(int32_t) * NB, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dcnt, h_nBlocks, sizeof(int32_t) * nRows, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
+    const int rc = index_rows_any(who, e, nRows, true, ds, slotBytes, db, nBlocks, di, indexStride, dcnt, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * nEnt, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * nRows, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+extern "C" int ulcx_index_check(const ulcx_index_entry *row, int nBlocks, int indexStride, long long payloadBytes) {
+    const char *who = "ulcx_index_check";
+    if (!row) return refuse(who, "no index");
+    if (nBlocks < 0 || nBlocks >= indexStride) return refuse(who, "%d blocks in a row of %d entries", nBlocks, indexStride);
+    if (row[0].ByteOffs != 0 || row[0].RngState != 1234567u) return refuse(who, "entry 0 is {%d, %u}, not {0, 1234567}", (int)row[0].ByteOffs, (unsigned)row[0].RngState);
+    for (int k = 1; k <= nBlocks; k++)
+        if (row[k].ByteOffs <= row[k - 1].ByteOffs) return refuse(who, "entry %d starts at byte %d, entry %d at %d", k, (int)row[k].ByteOffs, k - 1, (int)row[k - 1].ByteOffs);
+    if ((long long)row[nBlocks].ByteOffs > payloadBytes) return refuse(who, "the index closes at byte %d of a payload of %lld", (int)row[nBlocks].ByteOffs, payloadBytes);
+    return ULCX_OK;
+}
+extern "C" int ulcx_decoder_set_resident_index(ulcx_decoder *e, const ulcx_index_entry *h_index, int indexStride, const int32_t *h_nBlocks) {
+    const char *who = "ulcx_decoder_set_resident_index";
+    if (!e || !h_index || !h_nBlocks || indexStride < 1) return refuse(who, "bad argument");
+    if (!e->d_pay) return refuse(who, "no payload uploaded");
+    CKR(hipSetDevice(e->device));
+    std::vector<int32_t> payBytes((size_t)e->B);
+    CKR(hipMemcpy(payBytes.data(), e->d_payBytes, sizeof(int32_t) * e->B, hipMemcpyDeviceToHost));
+    for (int s = 0; s < e->B; s++) {
+        const long long avail = std::min<long long>(payBytes[(size_t)s], e->payStride);
+        if (ulcx_index_check(h_index + (size_t)s * indexStride, h_nBlocks[s], indexStride, avail)) {
+            const std::string why = ulcx_last_error();
+            return refuse(who, "stream %d: %s", s, why.c_str());
+        }
+    }
+    // checked: from here on the index the decoder had is replaced
+    e->idxStride = 0;
+    const size_t nEnt = (size_t)e->B * (size_t)indexStride;
+    int rc = dregrow(e->allocs, &e->d_index, nEnt, false);
+    if (!rc && !e->d_idxBlocks) rc = dalloc(e->allocs, &e->d_idxBlocks, (size_t)e->B, false);
+    if (rc) return rc;
+    CKR(hipMemcpy(e->d_index, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(e->d_idxBlocks, h_nBlocks, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
+    e->idxStride = indexStride;
+    return ULCX_OK;
 }
 
 // ---------------------------------------------------------------------------

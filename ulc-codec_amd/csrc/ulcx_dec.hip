@@ -462,6 +462,81 @@ __global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx
     nBlocks[s] = n;
 }
 
+// Block index of slot-form buffers (ulcx_index_slots_*): the blocks an encode call wrote, each in its own slot with its size
+// beside it, so nothing has to be walked in series.  Two launches and no scratch:
+//   k_dindex_slots_walk  one lane per (row, block), as k_dscan: the walk of k_dindex, limited to the size the caller gives.  It
+//                        parks {the block's bytes, or 0 for a block that is not what its size says; its draws} in the index
+//                        entry the block will close (n0 + k + 1: behind the row's entries so far, which nothing touches).
+//   k_dindex_slots_scan  one wave per row, 64 blocks per trip: prefix sums of the parked bytes and draws turn each entry into
+//                        {byte offset, generator state} - one jump per lane from the trip's start state, which is carried
+//                        from trip to trip (a trip's draws stay below 2^30; a row's need not) - and the first block that is
+//                        not valid, does not fit the table or would move the offset past an int32 closes the row: it and
+//                        everything behind it in the call become {-1, 0}.
+// A row whose count is outside [0, indexStride - 1] is skipped by both.  No stream state, none of the per-block scratch.
+__global__ __launch_bounds__(256) void k_dindex_begin(long long nEnt, int indexStride, ulcx_index_entry *index, int32_t *nBlocks) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nEnt) return;
+    const bool head = (i % indexStride) == 0;
+    index[i].ByteOffs = head ? 0 : -1; index[i].RngState = head ? 1234567u : 0u;     // ulcDecoder.c:76
+    if (head) nBlocks[i / indexStride] = 0;
+}
+__global__ __launch_bounds__(64) void k_dindex_slots_walk(UlcxDecCtx c, long long nAll, int nBlocks, const int32_t *bits,
+                                                          ulcx_index_entry *index, int indexStride, const int32_t *rowBlocks) {
+    const long long id = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (id >= nAll) return;
+    const long long s = id / nBlocks;
+    const int k = (int)(id - s * nBlocks);
+    const int n0 = rowBlocks[s];
+    if (n0 < 0 || n0 > indexStride - 1 || k >= indexStride - 1 - n0) return;       // no row to append to / no entry left for this block
+    const int b = bits[id], nb = b >> 3;
+    int bytes = 0, draws = 0;
+    if (b > 0 && nb <= c.slot) {
+        const int rb = (nb + ((b & 7) ? 1 : 0)) < c.slot ? nb + ((b & 7) ? 1 : 0) : c.slot;
+        const Walked w = scan_block<NybWin, false, false>(c, 0, c.in + (size_t)id * c.slot, b, rb, c.in, c.in + c.inBytes);
+        if (w.bits > 0 && ((w.bits + 7) >> 3) == nb) { bytes = nb; draws = w.draws; }
+    }
+    ulcx_index_entry *e = index + (size_t)s * indexStride + n0 + 1 + k;
+    e->ByteOffs = bytes; e->RngState = (uint32_t)draws;
+}
+__global__ __launch_bounds__(64) void k_dindex_slots_scan(const uint32_t *jumpT, int nBlocks, ulcx_index_entry *index, int indexStride, int32_t *rowBlocks) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int n0 = rowBlocks[s];
+    if (n0 < 0 || n0 > indexStride - 1) return;
+    ulcx_index_entry *row = index + (size_t)s * indexStride;
+    const int room = indexStride - 1 - n0, cap = nBlocks < room ? nBlocks : room;   // blocks of the call that have an entry
+    long long off = row[n0].ByteOffs;
+    uint32_t st = row[n0].RngState;
+    int m = 0;
+    bool open = true;
+    for (int k0 = 0; k0 < cap; k0 += 64) {
+        const bool have = k0 + lane < cap;
+        ulcx_index_entry *e = row + n0 + 1 + k0 + (have ? lane : 0);
+        if (!open) { if (have) { e->ByteOffs = -1; e->RngState = 0u; } continue; }
+        int by = 0; uint32_t dr = 0;
+        if (have) { by = e->ByteOffs; dr = e->RngState; }
+        const bool ok = by > 0;
+        if (!ok) { by = 0; dr = 0; }
+        // (64 blocks of up to 2^28 bytes: the sum in two halves, each within 32 bits)
+        const uint32_t lo = wave_scan_add((uint32_t)by & 0xFFFFu), hi = wave_scan_add((uint32_t)by >> 16);
+        const uint32_t dIncl = wave_scan_add(dr);
+        const long long end = off + (((long long)hi << 16) + lo);
+        const unsigned long long stop = __ballot(have && (!ok || end > 0x7FFFFFFFLL));
+        const int here = cap - k0 < 64 ? cap - k0 : 64;
+        const int good = stop ? (int)__builtin_ctzll(stop) : here;
+        if (have) {
+            if (lane < good) { e->ByteOffs = (int)end; e->RngState = rng_jump(jumpT, st, dIncl); }
+            else { e->ByteOffs = -1; e->RngState = 0u; }
+        }
+        m += good;
+        if (stop) open = false;
+        else {
+            off += ((long long)(uint32_t)__builtin_amdgcn_readlane((int)hi, 63) << 16) + (uint32_t)__builtin_amdgcn_readlane((int)lo, 63);
+            st = rng_jump(jumpT, st, (uint32_t)__builtin_amdgcn_readlane((int)dIncl, 63));
+        }
+    }
+    if (lane == 0) rowBlocks[s] = n0 + m;
+}
+
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
 // float index inside a padded FFT array (two floats of padding after every 32): complex n sits at FFT_PADS(n, DPS)
@@ -1403,6 +1478,21 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
 
 int ulcx_index_launch(const UlcxDecCtx &c, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, hipStream_t st) {
     hipLaunchKernelGGL(k_dindex, dim3((c.B + 63) / 64), dim3(64), 0, st, c, maxBlocks, d_index, d_nBlocks);
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+int ulcx_index_begin_launch(int nRows, ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, hipStream_t st) {
+    const long long nEnt = (long long)nRows * indexStride;
+    hipLaunchKernelGGL(k_dindex_begin, dim3((unsigned)((nEnt + 255) / 256)), dim3(256), 0, st, nEnt, indexStride, d_index, d_nBlocks);
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+// c.in / c.slot / c.inBytes: the slots, as for a slot-form decode call of nRows streams
+int ulcx_index_slots_launch(const UlcxDecCtx &c, int nRows, int nBlocks, const int32_t *d_bits, ulcx_index_entry *d_index, int indexStride,
+                            int32_t *d_nBlocks, hipStream_t st) {
+    const long long nAll = (long long)nRows * nBlocks;
+    hipLaunchKernelGGL(k_dindex_slots_walk, dim3((unsigned)((nAll + 63) / 64)), dim3(64), 0, st, c, nAll, nBlocks, d_bits, d_index, indexStride, d_nBlocks);
+    hipLaunchKernelGGL(k_dindex_slots_scan, dim3(nRows), dim3(64), 0, st, c.jumpT, nBlocks, d_index, indexStride, d_nBlocks);
     CK(hipGetLastError());
     return ULCX_OK;
 }

@@ -217,6 +217,11 @@ struct UlcxDecAux {
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
 int ulcx_index_launch(const UlcxDecCtx &c, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, hipStream_t st);
+// block index of slot-form buffers: open nRows rows; append nBlocks blocks per row (c.in / c.slot / c.inBytes set as for a
+// slot-form call of nRows streams; geometry and tables are all else that is read of c)
+int ulcx_index_begin_launch(int nRows, ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, hipStream_t st);
+int ulcx_index_slots_launch(const UlcxDecCtx &c, int nRows, int nBlocks, const int32_t *d_bits, ulcx_index_entry *d_index, int indexStride,
+                            int32_t *d_nBlocks, hipStream_t st);
 size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds);
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,

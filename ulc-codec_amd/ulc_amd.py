@@ -34,6 +34,8 @@ EXPORTS = [
     "ulcx_decoder_reset_streams_host", "ulcx_decoder_save_streams_host", "ulcx_decoder_load_streams_host",
     "ulcx_encode_dev_subset", "ulcx_encode_dev_pcm16_subset", "ulcx_analyse_dev_subset", "ulcx_encode_host_subset",
     "ulcx_decode_dev_subset", "ulcx_decode_dev_pcm16_subset", "ulcx_decode_host_subset",
+    "ulcx_index_begin_dev", "ulcx_index_slots_dev", "ulcx_index_slots_host", "ulcx_index_check", "ulcx_decoder_set_resident_index",
+    "ulcx_ulx_header_pack", "ulcx_ulx_header_parse",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -49,9 +51,47 @@ class FileHeader(C.Structure):
                 ("RateHz", C.c_uint32), ("nChan", C.c_uint16), ("RateKbps", C.c_uint16), ("StreamOffs", C.c_uint32)]
 
 
+class IndexFileHeader(C.Structure):
+    """ulcx_index_file_header (include/ulc_amd.h): the 16-byte header of a `.ulx` sidecar."""
+    _fields_ = [("Magic", C.c_uint32), ("BlockSize", C.c_uint16), ("nChan", C.c_uint16), ("nBlocks", C.c_uint32), ("PayloadBytes", C.c_uint32)]
+
+
 class Rung(C.Structure):
     """ulcx_rung (include/ulc_amd.h): one rung of a ladder call, 24 bytes; rate NULL = the scalar setting."""
     _fields_ = [("mode", C.c_int32), ("param0", C.c_float), ("param1", C.c_float), ("reserved", C.c_int32), ("rate", C.c_void_p)]
+
+
+def new_index(n_rows, index_stride):
+    """An open index as ulcx_index_begin_dev leaves it: entry 0 = (0, 1234567), every other entry (-1, 0)."""
+    index = np.zeros((n_rows, index_stride), INDEX_DTYPE)
+    index["ByteOffs"][:, 1:] = -1
+    index["RngState"][:, 0] = 1234567
+    return index
+
+
+def index_check(row, n_blocks, payload_bytes):
+    """ulcx_index_check (host code, no GPU): True when `row` may be handed to a range call for a payload of payload_bytes."""
+    row = np.ascontiguousarray(row, dtype=INDEX_DTYPE)
+    return lib().ulcx_index_check(row.ctypes.data, int(n_blocks), row.shape[0], int(payload_bytes)) == 0
+
+
+def ulx_pack(row, n_blocks, block_size, n_chan, payload_bytes):
+    """Bytes of a `.ulx` sidecar: the 16-byte header and entries 0 .. n_blocks of `row`."""
+    h = IndexFileHeader(0x31584C55, block_size, n_chan, int(n_blocks), int(payload_bytes))
+    hb = (C.c_uint8 * 16)()
+    lib().ulcx_ulx_header_pack(hb, C.byref(h))
+    return bytes(hb) + np.ascontiguousarray(row[:int(n_blocks) + 1], dtype=INDEX_DTYPE).tobytes()
+
+
+def ulx_parse(data):
+    """-> (IndexFileHeader, entries [nBlocks + 1]) of a `.ulx` sidecar's bytes; raises UlcError on a short or foreign file."""
+    buf = (C.c_uint8 * len(data)).from_buffer_copy(data)
+    h = IndexFileHeader()
+    _check(lib().ulcx_ulx_header_parse(C.byref(h), buf, len(data)), "ulcx_ulx_header_parse")
+    body = data[16:16 + 8 * (h.nBlocks + 1)]
+    if len(body) != 8 * (h.nBlocks + 1):
+        raise UlcError(f"ulx: {h.nBlocks} blocks need {8 * (h.nBlocks + 1)} bytes of entries, the file has {len(data) - 16}")
+    return h, np.frombuffer(body, INDEX_DTYPE).copy()
 
 
 _lib = None
@@ -115,6 +155,14 @@ def lib():
             l.ulcx_decode_dev_subset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             l.ulcx_decode_dev_pcm16_subset.argtypes = l.ulcx_decode_dev_subset.argtypes
             l.ulcx_decode_host_subset.argtypes = [C.c_void_p, _i32p, C.c_int, _u8p, C.c_int, C.c_int, _f32p, _i32p]
+        if hasattr(l, "ulcx_index_slots_dev"):             # index while encoding
+            l.ulcx_index_begin_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            l.ulcx_index_slots_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            l.ulcx_index_slots_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_int, _i32p, C.c_int, C.c_void_p, C.c_int, _i32p]
+            l.ulcx_index_check.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong]
+            l.ulcx_decoder_set_resident_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _i32p]
+            l.ulcx_ulx_header_pack.argtypes = [_u8p, C.POINTER(IndexFileHeader)]
+            l.ulcx_ulx_header_parse.argtypes = [C.POINTER(IndexFileHeader), _u8p, C.c_size_t]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -539,6 +587,41 @@ class BatchDecoder(_StreamSlots):
         _check(lib().ulcx_decode_resident_range_host(self.h, _p(first, _i32p), n_blocks, _p(pcm, _f32p), _p(bits, _i32p)),
                "ulcx_decode_resident_range_host")
         return pcm, bits
+
+    def index_begin_dev(self, n_rows, d_index, index_stride, d_n_blocks, stream=0):
+        """Open an index of n_rows rows on the device (entry 0 = (0, 1234567), the rest (-1, 0), counts 0)."""
+        _check(lib().ulcx_index_begin_dev(self.h, n_rows, d_index, index_stride, d_n_blocks, stream or None), "ulcx_index_begin_dev")
+
+    def index_slots_dev(self, n_rows, d_slots, slot, d_bits, n_blocks, d_index, index_stride, d_n_blocks, stream=0):
+        """Append the n_blocks blocks of a slot-form buffer (what an encode call wrote: d_slots [n_rows][n_blocks][slot],
+        d_bits [n_rows][n_blocks]) to each row's index; n_rows is the call's own, not the decoder's stream count."""
+        _check(lib().ulcx_index_slots_dev(self.h, n_rows, d_slots, slot, d_bits, n_blocks, d_index, index_stride, d_n_blocks, stream or None),
+               "ulcx_index_slots_dev")
+
+    def index_slots(self, blocks, bits, index=None, n_blocks=None, index_stride=None):
+        """Host form: blocks uint8 [R][K][slot], bits [R][K] -> (index [R][index_stride], n_blocks [R]).  Without `index` a new
+        one of index_stride entries per row (default K + 1) is opened; with it, the call appends behind n_blocks[r]."""
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
+        bits = np.ascontiguousarray(bits, dtype=np.int32)
+        R, K, slot = blocks.shape
+        assert bits.shape == (R, K)
+        if index is None:
+            index = new_index(R, index_stride or K + 1)
+            count = np.zeros(R, np.int32)
+        else:
+            index = np.ascontiguousarray(index, dtype=INDEX_DTYPE).copy()
+            count = np.ascontiguousarray(n_blocks, dtype=np.int32).copy()
+            assert index.shape[0] == R and count.shape == (R,)
+        _check(lib().ulcx_index_slots_host(self.h, R, _p(blocks, _u8p), slot, _p(bits, _i32p), K, index.ctypes.data, index.shape[1], _p(count, _i32p)),
+               "ulcx_index_slots_host")
+        return index, count
+
+    def set_resident_index(self, index, n_blocks):
+        """Install a stored index for the payloads uploaded with upload_payload() (checked against their sizes first)."""
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+        count = np.ascontiguousarray(n_blocks, dtype=np.int32)
+        assert index.shape[0] == self.B and count.shape == (self.B,)
+        _check(lib().ulcx_decoder_set_resident_index(self.h, index.ctypes.data, index.shape[1], _p(count, _i32p)), "ulcx_decoder_set_resident_index")
 
     def index_packed_dev(self, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream=0):
         _check(lib().ulcx_index_packed_dev(self.h, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream or None),
