@@ -128,12 +128,12 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  * the library to every line of this: each call there runs on poisoned buffers between guards (tests/guarded_buffers.py).
  *
  * ALIGNMENT.  The widest access a kernel makes to the buffer; every row of a buffer keeps it (rows are multiples of it).
- *   16 bytes  binary32 samples: d_pcm of the encode, analyse, decode, decode_packed and decode_range calls
+ *   16 bytes  binary32 samples: d_pcm of the encode, analyse, decode, decode_packed, decode_range and decode_crops calls
  *             (16-byte loads of the transform's fold, 16-byte stores of the stereo synthesis)
  *             saved stream records: d_state of the stream-slot entries (16-byte loads and stores)
  *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
- *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_index (an entry is two
+ *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_file, d_count, d_index (an entry is two
  *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n])
  *    none     the byte streams: d_out, d_in, d_payload and the d_slots of ulcx_pack_streams_dev and ulcx_index_slots_dev
  *             (slotBytes and payloadStride may be any positive value)
@@ -493,6 +493,56 @@ int  ulcx_decode_range_host(ulcx_decoder *dec, const uint8_t *h_payload, long lo
  * (h_nBlocks [nStreams], optional: the block counts), then any range is decoded from it.  A new upload drops the index. */
 int  ulcx_decoder_index_resident(ulcx_decoder *dec, int maxBlocks, int32_t *h_nBlocks);
 int  ulcx_decode_resident_range_host(ulcx_decoder *dec, const int32_t *h_first, int nBlocks, float *h_pcm, int32_t *h_bits);
+
+/* Crops: row i of the call is blocks d_first[i] .. d_first[i] + nBlocks - 1 of file d_file[i] of a corpus of nFiles packed
+ * payloads with their block indices.  nFiles is an argument of its own, not the decoder's nStreams (a 64-stream decoder
+ * crops a corpus of 100 000 files); a file may be named by any number of rows, ranges may overlap or coincide.
+ *   d_payload      [nFiles][payloadStride] bytes, d_payloadBytes [nFiles]; nFiles * payloadStride may exceed 2^31 (a single
+ *                  file stays below 2^31 bytes: ByteOffs is an int32)
+ *   d_index        [nFiles][indexStride] entries, d_indexBlocks [nFiles] their block counts (ulcx_index_packed_rows_dev, or
+ *                  stored `.ulx` indices)
+ *   n              rows of the call, 1 .. nStreams (the per-block scratch is the object's); nBlocks is 1 .. maxBlocksPerCall - 1,
+ *                  as for a range call; nFiles >= 1
+ *   d_file, d_first [n]; d_count [n] or NULL: the leading blocks wanted of each row, clamped to [0, nBlocks] - crops of
+ *                  different length in one call
+ *   d_pcm          [n][nBlocks][BlockSize][nChan], d_bits [n][nBlocks], written in full: row i is, bit for bit and with the noise
+ *                  included, what a sequential decode of file d_file[i] from its block 0 writes for those blocks
+ * A block at or past the file's d_indexBlocks, or at or past d_count[i], reports 0 bits and zero samples, and so does everything
+ * behind it in the row.  The device forms cannot refuse a row without a synchronisation: a d_file[i] outside [0, nFiles), a
+ * d_first[i] outside [0, d_indexBlocks[file]] and an index entry that points outside its file's payload each give a row of 0
+ * bits and zero samples and leave the other rows as they are; nothing outside the call's buffers is read or written.  The host
+ * form refuses a file number out of range, a first outside [0, h_indexBlocks[file]] and a negative count with ULCX_ERR_ARG
+ * before any device work.
+ * STATE: a crop call reads no stream's persistent state and changes none - lapping, LastSubBlockSize, generator, dead flag,
+ * packed read position, resident payload, resident index.  It may be mixed freely with every other call on the object; a
+ * sequential decode that is under way continues as if the crop call had not been made.  The call runs on the subset calls'
+ * compact state copy (allocated on the first subset or crop call; nothing is allocated afterwards), and a refused call
+ * leaves that copy as it was too.  ulcx_decoder_last_cut reports the call's launch plan, planned from n rows.
+ * ALIGNMENT / EXTENT / ORDER as for every _dev call: d_file, d_first, d_count, d_payloadBytes, d_indexBlocks, d_index and d_bits
+ * 4 bytes, d_pcm 16, d_pcm16 8, the payload none; a misaligned pointer returns ULCX_ERR_ARG before any device work.  Both
+ * kernels go on hipStream and nothing waits for the device; the _host form is synchronous. */
+int  ulcx_decode_crops_dev(ulcx_decoder *dec, int nFiles,
+                           const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes /* [nFiles] */,
+                           const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks /* [nFiles] */,
+                           int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count /* optional */,
+                           int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_dev_pcm16(ulcx_decoder *dec, int nFiles,
+                                 const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                 const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                 int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count,
+                                 int nBlocks, int16_t *d_pcm16 /* converted as ulcx_decode_dev_pcm16 converts */, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_host(ulcx_decoder *dec, int nFiles,
+                            const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                            const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                            int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
+                            int nBlocks, float *h_pcm, int32_t *h_bits);   /* synchronous */
+/* ulcx_index_packed_dev with a row count of its own (the corpus's nFiles), as ulcx_index_slots_dev has one: entry for entry
+ * what ulcx_index_packed_dev writes for the same payloads, for any nRows >= 1.  d_index [nRows][maxBlocks+1], d_nBlocks [nRows].
+ * It reads the decoder's geometry and tables only. */
+int  ulcx_index_packed_rows_dev(ulcx_decoder *dec, int nRows, const uint8_t *d_payload, long long payloadStride,
+                                const int32_t *d_payloadBytes, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream);
+int  ulcx_index_packed_rows_host(ulcx_decoder *dec, int nRows, const uint8_t *h_payload, long long payloadStride,
+                                 const int32_t *h_payloadBytes, int maxBlocks, ulcx_index_entry *h_index, int32_t *h_nBlocks);
 
 /* Index while encoding: the same table, grown call by call from what an encode call wrote - every block in its own slot,
  * its size in d_bits - so all of a call's blocks are parsed side by side and nothing is walked in series.  The result is,

@@ -1,0 +1,146 @@
+"""A corpus of `.ulc` files resident in device memory, and random crops of it (ulcx_decode_crops_dev): what a loader holds.
+
+    corpus = CropCorpus(n_chan=2, block_size=2048)
+    for ulc, ulx in files:                         # bytes of the .ulc file and of its .ulx sidecar (or None: indexed in freeze)
+        corpus.add_file(ulc, ulx)
+    corpus.freeze("cuda:0")                        # payloads and indices to the device, once
+    dec = ulc_amd.BatchDecoder(batch, 2, 2048, crop_blocks + 1)
+    pcm, bits = corpus.crops(dec, files, first, crop_blocks)      # [n][crop_blocks * 2048][2] on the device
+
+Everything in front of freeze() is host logic (numpy, and the library's host-side parsers): it needs no GPU.  Plumbing only -
+the decode is the library's crop call, and there is no fallback."""
+import ctypes as C
+import numpy as np
+import ulc_amd
+from ulc_amd import INDEX_DTYPE, UlcError
+
+ULC_HEADER_BYTES = 24
+PAYLOAD_PAD = 64                                           # bytes behind the longest payload, as the tests' pack() leaves
+
+
+def parse_ulc(data):
+    """-> (FileHeader, payload bytes) of a `.ulc` file's bytes (ulcx_ulc_header_parse); raises UlcError on a foreign or short file."""
+    h = ulc_amd.FileHeader()
+    head = (C.c_uint8 * ULC_HEADER_BYTES).from_buffer_copy(bytes(data[:ULC_HEADER_BYTES]).ljust(ULC_HEADER_BYTES, b"\0"))
+    ulc_amd._check(ulc_amd.lib().ulcx_ulc_header_parse(C.byref(h), head, min(len(data), ULC_HEADER_BYTES)), "ulcx_ulc_header_parse")
+    if h.StreamOffs < ULC_HEADER_BYTES or h.StreamOffs > len(data):
+        raise UlcError(f"ulc: the payload starts at byte {h.StreamOffs} of a file of {len(data)}")
+    return h, bytes(data[h.StreamOffs:])
+
+
+class CropCorpus:
+    def __init__(self, n_chan, block_size):
+        self.C, self.BS = int(n_chan), int(block_size)
+        self._payloads, self._index, self._blocks = [], [], []      # per file: bytes; entries [n + 1] or None; blocks (header's when not indexed yet)
+        self.frozen = False
+
+    def __len__(self):
+        return len(self._payloads)
+
+    def add_file(self, ulc_bytes, ulx_bytes=None):
+        """-> the file's number.  Refuses (UlcError) another geometry than the corpus's, and a `.ulx` that is not this payload's:
+        another geometry, another PayloadBytes, or entries ulcx_index_check does not accept for it.  Without `.ulx` bytes the
+        file is marked for indexing in freeze()."""
+        if self.frozen:
+            raise UlcError("corpus: frozen")
+        h, payload = parse_ulc(ulc_bytes)
+        if (h.BlockSize, h.nChan) != (self.BS, self.C):
+            raise UlcError(f"corpus: a file of BlockSize {h.BlockSize} x {h.nChan} channels in a corpus of {self.BS} x {self.C}")
+        if len(payload) < 1 or len(payload) >= 2 ** 31 - PAYLOAD_PAD - 16:
+            raise UlcError(f"corpus: a payload of {len(payload)} bytes")
+        entries, blocks = None, max(1, int(h.nBlocks))
+        if ulx_bytes is not None:
+            xh, entries = ulc_amd.ulx_parse(ulx_bytes)
+            if (xh.BlockSize, xh.nChan) != (self.BS, self.C):
+                raise UlcError(f"corpus: an index of BlockSize {xh.BlockSize} x {xh.nChan} channels in a corpus of {self.BS} x {self.C}")
+            if xh.PayloadBytes != len(payload):
+                raise UlcError(f"corpus: the index was made for a payload of {xh.PayloadBytes} bytes, the file's has {len(payload)}")
+            if not ulc_amd.index_check(entries, xh.nBlocks, len(payload)):
+                raise UlcError("corpus: the index does not fit the payload (ulcx_index_check)")
+            blocks = int(xh.nBlocks)
+        self._payloads.append(payload); self._index.append(entries); self._blocks.append(blocks)
+        return len(self._payloads) - 1
+
+    def layout(self):
+        """The frozen layout on numpy arrays: one stride for the payloads (the longest + 64, rounded up to 16), one for the
+        indices (the most blocks + 1); file f's payload starts at byte f * stride.  -> dict: stride, index_stride, payload uint8
+        [F][stride], payload_bytes int32 [F], index INDEX_DTYPE [F][index_stride] (an open row, ulc_amd.new_index, for a file to
+        index), index_blocks int32 [F] (0 for those), to_index: the numbers of the files without a stored index."""
+        F = len(self._payloads)
+        if F < 1:
+            raise UlcError("corpus: no files")
+        stride = (max(len(p) for p in self._payloads) + PAYLOAD_PAD + 15) & ~15
+        index_stride = max(self._blocks) + 1
+        payload = np.zeros((F, stride), np.uint8)
+        nbytes = np.zeros(F, np.int32)
+        index = ulc_amd.new_index(F, index_stride)
+        blocks = np.zeros(F, np.int32)
+        for f, (p, e) in enumerate(zip(self._payloads, self._index)):
+            payload[f, :len(p)] = np.frombuffer(p, np.uint8)
+            nbytes[f] = len(p)
+            if e is not None:
+                index[f, :len(e)] = e
+                blocks[f] = len(e) - 1
+        to_index = np.array([f for f, e in enumerate(self._index) if e is None], np.int64)
+        return {"stride": stride, "index_stride": index_stride, "payload": payload, "payload_bytes": nbytes, "index": index,
+                "index_blocks": blocks, "to_index": to_index}
+
+    def freeze(self, device="cuda:0"):
+        """Payloads and indices to `device` as torch tensors (uint8 / int32), at the strides of layout(); the files without a
+        stored index are indexed there with ONE ulcx_index_packed_rows_dev call."""
+        import torch
+        dev = torch.device(device)
+        lay = self.layout()
+        self.n_files, self.stride, self.index_stride = len(self._payloads), lay["stride"], lay["index_stride"]
+        self.device = dev
+        self.d_payload = torch.from_numpy(lay["payload"]).to(dev)
+        self.d_payload_bytes = torch.from_numpy(lay["payload_bytes"]).to(dev)
+        self.d_index = torch.from_numpy(lay["index"].view(np.int32).reshape(self.n_files, self.index_stride, 2)).to(dev)
+        self.d_index_blocks = torch.from_numpy(lay["index_blocks"]).to(dev)
+        todo = lay["to_index"]
+        if todo.size:
+            rows = torch.from_numpy(todo).to(dev)
+            pay = self.d_payload.index_select(0, rows).contiguous()
+            nb = self.d_payload_bytes.index_select(0, rows).contiguous()
+            idx = torch.zeros((todo.size, self.index_stride, 2), dtype=torch.int32, device=dev)
+            cnt = torch.zeros(todo.size, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                dec = ulc_amd.BatchDecoder(1, self.C, self.BS, 1, device=dev.index or 0)     # geometry and tables are all the call reads of it
+                try:
+                    dec.index_packed_rows_dev(int(todo.size), pay.data_ptr(), self.stride, nb.data_ptr(), self.index_stride - 1, idx.data_ptr(),
+                                              cnt.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+                    torch.cuda.current_stream(dev).synchronize()
+                finally:
+                    dec.close()
+            self.d_index.index_copy_(0, rows, idx)
+            self.d_index_blocks.index_copy_(0, rows, cnt)
+        self.frozen = True
+        return self
+
+    def device_bytes(self):
+        """HBM bytes of the frozen corpus: payloads, their sizes, indices, block counts."""
+        return sum(t.numel() * t.element_size() for t in (self.d_payload, self.d_payload_bytes, self.d_index, self.d_index_blocks))
+
+    def crops(self, dec, files, first, n_blocks, count=None, pcm16=False):
+        """Row i: blocks first[i] .. first[i] + n_blocks - 1 of file files[i] (the leading count[i] of them when `count` is
+        given; zeros behind).  files / first / count: int32 tensors on the corpus's device, or anything torch.as_tensor takes.
+        -> (pcm [n][n_blocks * BlockSize][nChan] float32, or int16 with pcm16; bits int32 [n][n_blocks]) on the device, enqueued on
+        torch's current stream.  `dec`: a BatchDecoder of this geometry with n_streams >= n and max_blocks > n_blocks; no stream
+        state of it is read or changed."""
+        import torch
+        if not self.frozen:
+            raise UlcError("corpus: not frozen")
+        if (dec.C, dec.BS) != (self.C, self.BS):
+            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
+        as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=self.device).contiguous()
+        files, first = as_i32(files), as_i32(first)
+        want = None if count is None else as_i32(count)
+        n = files.numel()
+        assert first.numel() == n and (want is None or want.numel() == n)
+        pcm = torch.empty((n, n_blocks * self.BS, self.C), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
+        bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        dec.decode_crops_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
+                             self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), first.data_ptr(),
+                             want.data_ptr() if want is not None else 0, n_blocks, pcm.data_ptr(), bits.data_ptr(),
+                             stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
+        return pcm, bits

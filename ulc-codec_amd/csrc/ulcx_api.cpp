@@ -935,9 +935,12 @@ extern "C" int ulcx_decoder_last_cut(ulcx_decoder *e, int *workgroups, int *whol
 // subsetSet != NULL: a subset call - c.B is the number of listed slots (what the cut is planned from) and c.lap .. c.dead are
 // set 0 of the compact shadow state; a cut leaves its result in set 1 of THAT state, the object's own sets are not swapped,
 // and *subsetSet receives the set that holds the result.
-static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subsetSet = nullptr) {
-    if (!e->inBlock1) e->b1SeedStale = true;                      // (a batched / packed call on a one-stream decoder: see b1Seed)
+// crop != NULL: a crop call (with subsetSet: it runs on the shadow state as a subset call does) - the walk's corpus arguments;
+// no stream's generator word moves, so the single-block path's host copy stays good.
+static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subsetSet = nullptr, const UlcxDecAux *crop = nullptr) {
+    if (!e->inBlock1 && !crop) e->b1SeedStale = true;             // (a batched / packed call on a one-stream decoder: see b1Seed)
     UlcxDecAux a;
+    if (crop) a = *crop;
     a.synGrid = 0; a.synFull = 0;
     c.lapO = c.lap; c.lastSubO = c.lastSub; c.seedO = c.seed; c.deadO = c.dead;
     const int Kc = c.range ? c.K - 1 : c.K;                       // blocks of the call per stream (a range call's K counts the row of the block in front)
@@ -1474,6 +1477,137 @@ extern "C" int ulcx_decode_resident_range_host(ulcx_decoder *e, const int32_t *h
     CKR(hipMemcpy(e->d_first, h_first, sizeof(int32_t) * e->B, hipMemcpyHostToDevice));
     rc = decode_range_any(who, e, e->d_pay, e->payStride, e->d_payBytes, e->d_index, e->idxStride, e->d_idxBlocks, e->d_first, nBlocks, e->d_pcm, nullptr, e->d_bits, nullptr);
     return rc ? rc : dec_results_down(e, e->d_pcm, e->d_bits, (size_t)e->B * nBlocks, h_pcm, h_bits);
+}
+
+// ---- crops (include/ulc_amd.h section 3): rows of a call that each name a file of a corpus.  The range synthesis enters every
+// row from nothing, so the call needs no stream's state; what the synthesis leaves behind a row goes to the subset calls'
+// shadow state (dec_shadow) and is never scattered back.
+// the checks every crop entry makes, device or host pointers; the object comes last among them: every other refusal needs none
+static int crops_args_bad(const char *who, const ulcx_decoder *e, int nFiles, const void *payload, long long payloadStride, const void *payloadBytes,
+                          const void *index, int indexStride, const void *indexBlocks, int n, const void *file, const void *first,
+                          int nBlocks, const void *pcm, const void *bits) {
+    if (!payload || !payloadBytes || !index || !indexBlocks || !file || !first || !pcm || !bits) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
+    if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
+    if (nFiles < 1) { refuse(who, "bad argument (nFiles %d)", nFiles); return 1; }
+    if (nBlocks < 1) { refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return 1; }
+    if (payloadStride < 1 || indexStride < 1) { refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride); return 1; }
+    if (!e) { refuse(who, "no decoder"); return 1; }
+    if (n > e->B) { refuse(who, "bad argument (n %d: a call takes 1 .. nStreams = %d rows)", n, e->B); return 1; }
+    if (nBlocks > e->maxK - 1) { refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return 1; }
+    return 0;
+}
+static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                            const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                            int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
+                            float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    if (crops_args_bad(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, d_first, nBlocks,
+                       d_pcm ? (const void *)d_pcm : d_pcm16, d_bits)) return ULCX_ERR_ARG;
+    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_file", d_file, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_first", d_first, ULCX_ALIGN_WORD) || misaligned(who, "d_count", d_count, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
+        misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    int rc = dec_shadow(e);
+    if (rc) return rc;
+    UlcxDecCtx c = e->ctx;
+    c.B = n; c.K = nBlocks + 1; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = d_pcm16;
+    c.bits = e->bitsScr; c.bitsOut = d_bits;
+    c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
+    c.inBytes = (long long)nFiles * payloadStride;
+    c.range = 1; c.rIndex = d_index; c.rIndexStride = indexStride; c.rIndexBlocks = d_indexBlocks; c.rFirst = d_first;
+    c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
+    UlcxDecAux crop = {};
+    crop.nFiles = nFiles; crop.cropFile = d_file; crop.cropCount = d_count;
+    int set = 0;
+    rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &crop);
+    e->evRecorded = (rc == ULCX_OK) && e->timing;
+    return rc;
+}
+extern "C" int ulcx_decode_crops_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                     const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                     int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
+                                     float *d_pcm, int32_t *d_bits, void *hipStream) {
+    return decode_crops_any("ulcx_decode_crops_dev", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks,
+                            n, d_file, d_first, d_count, nBlocks, d_pcm, nullptr, d_bits, hipStream);
+}
+extern "C" int ulcx_decode_crops_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                           const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                           int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
+                                           int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    return decode_crops_any("ulcx_decode_crops_dev_pcm16", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks,
+                            n, d_file, d_first, d_count, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
+}
+// nRows payloads and their sizes of a host-pointer call, into buffers of the call's own (payload_up with a row count of its own)
+static int payload_rows_up(DevTmp &t, int nRows, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes, uint8_t **dp, int32_t **dn) {
+    const size_t bytes = (size_t)nRows * (size_t)payloadStride;
+    CKR(t.get(dp, bytes)); CKR(t.get(dn, sizeof(int32_t) * (size_t)nRows));
+    CKR(hipMemcpy(*dp, h_payload, bytes, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(*dn, h_payloadBytes, sizeof(int32_t) * (size_t)nRows, hipMemcpyHostToDevice));
+    return ULCX_OK;
+}
+extern "C" int ulcx_decode_crops_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                      const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                      int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                                      float *h_pcm, int32_t *h_bits) {
+    const char *who = "ulcx_decode_crops_host";
+    if (crops_args_bad(who, e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, n, h_file, h_first, nBlocks, h_pcm, h_bits)) return ULCX_ERR_ARG;
+    // what the device forms cannot refuse
+    for (int i = 0; i < n; i++) {
+        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
+        int nI = h_indexBlocks[h_file[i]];
+        nI = nI < 0 ? 0 : nI > indexStride - 1 ? indexStride - 1 : nI;                   // (as the walk reads a count)
+        if (h_first[i] < 0 || h_first[i] > nI) return refuse(who, "row %d starts at block %d of a file of %d", i, (int)h_first[i], nI);
+        if (h_count && h_count[i] < 0) return refuse(who, "row %d wants %d blocks", i, (int)h_count[i]);
+    }
+    CKR(hipSetDevice(e->device));
+    const size_t NB = (size_t)n * nBlocks, nEnt = (size_t)nFiles * (size_t)indexStride;
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr, *dfile = nullptr, *df = nullptr, *dwant = nullptr, *dbits = nullptr;
+    ulcx_index_entry *di = nullptr; float *dpcm = nullptr;
+    int rc = payload_rows_up(t, nFiles, h_payload, payloadStride, h_payloadBytes, &dp, &dn);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&dfile, sizeof(int32_t) * n)); CKR(t.get(&df, sizeof(int32_t) * n));
+    CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt)); CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
+    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dfile, h_file, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(df, h_first, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
+    if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
+    rc = decode_crops_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, n, dfile, df, dwant, nBlocks, dpcm, nullptr, dbits, nullptr);
+    return rc ? rc : dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+}
+// ulcx_index_packed_* with a row count of its own: k_dindex over nRows (geometry and tables are all that is read of the object)
+static int index_rows_packed_any(const char *who, ulcx_decoder *e, int nRows, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                 int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
+    if (!d_payload || !d_payloadBytes || !d_index || !d_nBlocks || nRows < 1 || payloadStride < 1 || maxBlocks < 1) return refuse(who, "bad argument");
+    if (!e) return refuse(who, "no decoder");
+    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_nBlocks", d_nBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    UlcxDecCtx c = e->ctx;
+    c.B = nRows; c.in = d_payload; c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
+    c.inBytes = (long long)nRows * payloadStride;
+    return ulcx_index_launch(c, maxBlocks, d_index, d_nBlocks, (hipStream_t)hipStream);
+}
+extern "C" int ulcx_index_packed_rows_dev(ulcx_decoder *e, int nRows, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                          int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
+    return index_rows_packed_any("ulcx_index_packed_rows_dev", e, nRows, d_payload, payloadStride, d_payloadBytes, maxBlocks, d_index, d_nBlocks, hipStream);
+}
+extern "C" int ulcx_index_packed_rows_host(ulcx_decoder *e, int nRows, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                           int maxBlocks, ulcx_index_entry *h_index, int32_t *h_nBlocks) {
+    const char *who = "ulcx_index_packed_rows_host";
+    if (!e || !h_payload || !h_payloadBytes || !h_index || !h_nBlocks || nRows < 1 || payloadStride < 1 || maxBlocks < 1) return refuse(who, "bad argument");
+    CKR(hipSetDevice(e->device));
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr; ulcx_index_entry *di = nullptr;
+    const size_t nEnt = (size_t)nRows * ((size_t)maxBlocks + 1);
+    int rc = payload_rows_up(t, nRows, h_payload, payloadStride, h_payloadBytes, &dp, &dn);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nRows)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    if ((rc = index_rows_packed_any(who, e, nRows, dp, payloadStride, dn, maxBlocks, di, dcnt, nullptr))) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * nEnt, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * (size_t)nRows, hipMemcpyDeviceToHost));
+    return ULCX_OK;
 }
 
 // ---- index while encoding (include/ulc_amd.h section 3): index_rows_any is the body of begin (slots == nullptr) and append.

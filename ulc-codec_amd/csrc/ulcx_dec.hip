@@ -438,6 +438,59 @@ __global__ __launch_bounds__(64) void k_dscan_range(UlcxDecCtx c) {
     }
 }
 
+// Pass 1 of a crop call (ulcx_decode_crops_*) - one lane per (row, block-row), as k_dscan_range, but a row of the call is not a
+// stream of the object: row i is blocks rFirst[i] .. of file `file[i]` of a corpus of nFiles payloads, and c.in / payStride /
+// payBytes / rIndex / rIndexBlocks are the corpus's ([nFiles]), looked at only once the file number is known to lie inside
+// [0, nFiles).  Any number of rows may name one file.  A lane without a block - a file or a start out of range, a block at or
+// past the file's block count or the row's `count`, a row one of whose index entries points outside its file's payload - marks
+// it as k_dscan_range does (window code 0: the row ends there).  No read position is written: a crop belongs to no stream.
+__global__ __launch_bounds__(64) void k_dscan_crop(UlcxDecCtx c, int nFiles, const int32_t *file, const int32_t *count) {
+    __shared__ uint2 ringP[DSCAN_RP * 64], ringN[DSCAN_RN * 64];
+    const int id0 = blockIdx.x * 64 + threadIdx.x, K = c.K;
+    const bool live0 = id0 < c.B * K;
+    const int id = live0 ? id0 : c.B * K - 1;                             // (a lane without a row shadows the last one, and writes nothing)
+    const int s = id / K, r = id - s * K;
+    const int f = file[s];
+    const bool okF = f >= 0 && f < nFiles;
+    const size_t fi = okF ? (size_t)f : 0;                                // (nFiles >= 1: file 0 exists, and nothing of it is used for a bad row)
+    int nI = c.rIndexBlocks[fi];
+    nI = nI < 0 ? 0 : nI > c.rIndexStride - 1 ? c.rIndexStride - 1 : nI;
+    const int first = c.rFirst[s];
+    int want = count ? count[s] : K - 1;                                  // leading blocks of the row that are wanted
+    want = want > K - 1 ? K - 1 : want;
+    bool okS = okF && first >= 0 && first <= nI && want > 0;
+    const int k = first - 1 + r;
+    const ulcx_index_entry *row = c.rIndex + fi * (size_t)c.rIndexStride;
+    long long avail = c.payBytes[fi];
+    avail = avail > c.payStride ? c.payStride : avail;
+    if (okS) {
+        // the table is not trusted, and a row is all or nothing: every entry that bounds a block of the row (the one in front
+        // included) inside the file's payload and behind its predecessor - each lane looks at its row's <= K + 1 entries
+        const int j0 = first > 0 ? first - 1 : 0, j1 = first + want < nI ? first + want : nI;
+        long long prev = row[j0].ByteOffs;
+        bool okT = prev >= 0;
+        for (int j = j0 + 1; j <= j1; j++) { const long long o = row[j].ByteOffs; okT &= o > prev && o <= avail; prev = o; }
+        okS = okT;
+    }
+    int off = 0, ext = 0;
+    if (okS && k >= 0 && k < nI && r <= want) { off = row[k].ByteOffs; ext = row[k + 1].ByteOffs - off; }
+    const bool sane = off >= 0 && ext > 0 && (long long)off + ext <= avail;
+    if (!sane) { off = 0; ext = 0; }
+    const uint8_t *p = c.in + fi * (size_t)c.payStride + off, *bufEnd = c.in + c.inBytes;
+    // every look of every lane of the wave inside the buffer (k_dscan): the window without bounds checks
+    const bool inside = (size_t)(p - c.in) >= ((uintptr_t)p & 15) && (size_t)(bufEnd - p) >= (size_t)ext + 80;
+    const int blk = s * K + r;
+    const bool live = live0 && sane;
+    if (__ballot(!inside) == 0ull) scan_block<NybWinFast, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
+    else scan_block<NybWin, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
+    if (live0 && !sane) { c.bits[blk] = 0; c.wcScan[blk] = 0; c.draws[blk] = 0; }
+    if (live0 && r == 0) {
+        // what the synthesis needs to enter the row: whether row 0 holds a block, and the generator state in front of it
+        const int pre = (okS && first > 0) ? 1 : 0;
+        c.rInfo[s] = make_int2(pre, okS ? (int)row[first - pre].RngState : 0);
+    }
+}
+
 // Block index of packed payloads (ulcx_index_packed_*) - one lane per stream, the walk of k_dscan_packed without its notes:
 // per block its start and the state the stream's one generator chain has there (one jump by the block's draws).  It stops
 // where k_dscan_packed reports 0 bits.  No stream state, none of the per-block scratch.
@@ -1461,7 +1514,8 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     const bool split = c.fastOK && aux.synGrid > 0;
     const void *syn = c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0) : syn_fn<float>(c, split, c.range != 0);
     CK(allow_lds(syn, lds));
-    if (c.range) hipLaunchKernelGGL(k_dscan_range, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
+    if (aux.nFiles > 0) hipLaunchKernelGGL(k_dscan_crop, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount);
+    else if (c.range) hipLaunchKernelGGL(k_dscan_range, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     if (ev) CK(hipEventRecord(ev[stage++], st));

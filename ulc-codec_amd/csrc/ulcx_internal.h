@@ -213,6 +213,11 @@ void ulcx_enc_rung_arm(const UlcxEncCtx &c, hipStream_t st);
 struct UlcxDecAux {
     int synGrid;                         // > 0: workgroups of the synthesis over a cut of the (stream, block) pairs; 0: one per stream
     int synFull;                         // of those, the leading ones that take one whole stream each (0: an even cut of everything)
+    // crop calls (ulcx_decode_crops_*): nFiles > 0 - the walk is k_dscan_crop, c.B rows that each name a file of the corpus.
+    // c.in / payStride / payBytes / rIndex / rIndexBlocks describe the nFiles files, c.rFirst and these two the c.B rows.
+    int nFiles = 0;
+    const int32_t *cropFile = nullptr;   // [c.B] file of each row
+    const int32_t *cropCount = nullptr;  // [c.B] leading blocks wanted of each row, or NULL: all of them
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)

@@ -36,6 +36,7 @@ EXPORTS = [
     "ulcx_decode_dev_subset", "ulcx_decode_dev_pcm16_subset", "ulcx_decode_host_subset",
     "ulcx_index_begin_dev", "ulcx_index_slots_dev", "ulcx_index_slots_host", "ulcx_index_check", "ulcx_decoder_set_resident_index",
     "ulcx_ulx_header_pack", "ulcx_ulx_header_parse",
+    "ulcx_decode_crops_dev", "ulcx_decode_crops_dev_pcm16", "ulcx_decode_crops_host", "ulcx_index_packed_rows_dev", "ulcx_index_packed_rows_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -163,6 +164,14 @@ def lib():
             l.ulcx_decoder_set_resident_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _i32p]
             l.ulcx_ulx_header_pack.argtypes = [_u8p, C.POINTER(IndexFileHeader)]
             l.ulcx_ulx_header_parse.argtypes = [C.POINTER(IndexFileHeader), _u8p, C.c_size_t]
+        if hasattr(l, "ulcx_decode_crops_dev"):            # crops of a resident corpus
+            l.ulcx_decode_crops_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_decode_crops_dev_pcm16.argtypes = l.ulcx_decode_crops_dev.argtypes
+            l.ulcx_decode_crops_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i32p, C.c_void_p, C.c_int, _i32p,
+                                                 C.c_int, _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p]
+            l.ulcx_index_packed_rows_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_index_packed_rows_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i32p, C.c_int, C.c_void_p, _i32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -632,6 +641,52 @@ class BatchDecoder(_StreamSlots):
         fn = lib().ulcx_decode_range_dev_pcm16 if pcm16 else lib().ulcx_decode_range_dev
         _check(fn(self.h, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, d_first, n_blocks, d_pcm, d_bits,
                   stream or None), "ulcx_decode_range_dev_pcm16" if pcm16 else "ulcx_decode_range_dev")
+
+    def decode_crops(self, payload, payload_bytes, index, index_blocks, files, first, n_blocks, count=None):
+        """Crops of a corpus: payload uint8 [F][stride], payload_bytes [F], index [F][index_stride], index_blocks [F]; row i of
+        the result is blocks first[i] .. first[i]+n_blocks-1 of file files[i] (its leading count[i] blocks when `count` is
+        given) -> (pcm [n][n_blocks*BS][C], bits [n][n_blocks]), as a sequential decode of that file from block 0 gives them.
+        n <= n_streams, n_blocks <= max_blocks - 1; F is the corpus's own.  No stream's state is read or changed."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        want = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+        F, stride = payload.shape
+        n = files.shape[0]
+        assert nbytes.shape == (F,) and index.shape[0] == F and blocks.shape == (F,) and first.shape == (n,)
+        assert want is None or want.shape == (n,)
+        pcm = np.zeros((n, n_blocks * self.BS, self.C), np.float32)
+        bits = np.zeros((n, n_blocks), np.int32)
+        _check(lib().ulcx_decode_crops_host(self.h, F, _p(payload, _u8p), stride, _p(nbytes, _i32p), index.ctypes.data, index.shape[1], _p(blocks, _i32p),
+                                            n, _p(files, _i32p), _p(first, _i32p), _p(want, _i32p), n_blocks, _p(pcm, _f32p), _p(bits, _i32p)),
+               "ulcx_decode_crops_host")
+        return pcm, bits
+
+    def decode_crops_dev(self, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_first, d_count,
+                         n_blocks, d_pcm, d_bits, stream=0, pcm16=False):
+        """Device form (d_count 0 / None: every row takes all n_blocks); d_pcm is int16 [n][n_blocks][BS][C] with pcm16."""
+        fn = lib().ulcx_decode_crops_dev_pcm16 if pcm16 else lib().ulcx_decode_crops_dev
+        _check(fn(self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_first, d_count or None,
+                  n_blocks, d_pcm, d_bits, stream or None), "ulcx_decode_crops_dev_pcm16" if pcm16 else "ulcx_decode_crops_dev")
+
+    def index_packed_rows(self, payload, payload_bytes, max_blocks):
+        """index_packed() for any number of rows (a corpus's files), whatever the decoder's stream count."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        R, stride = payload.shape
+        assert nbytes.shape == (R,)
+        index = np.zeros((R, max_blocks + 1), INDEX_DTYPE)
+        count = np.zeros(R, np.int32)
+        _check(lib().ulcx_index_packed_rows_host(self.h, R, _p(payload, _u8p), stride, _p(nbytes, _i32p), max_blocks, index.ctypes.data, _p(count, _i32p)),
+               "ulcx_index_packed_rows_host")
+        return index, count
+
+    def index_packed_rows_dev(self, n_rows, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream=0):
+        _check(lib().ulcx_index_packed_rows_dev(self.h, n_rows, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream or None),
+               "ulcx_index_packed_rows_dev")
 
     def decode_packed_dev(self, d_payload, stride, d_payload_bytes, n_blocks, d_pcm, d_bits, stream=0):
         _check(lib().ulcx_decode_packed_dev(self.h, d_payload, stride, d_payload_bytes, n_blocks, d_pcm, d_bits, stream or None),
