@@ -133,6 +133,7 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  *             saved stream records: d_state of the stream-slot entries (16-byte loads and stores)
  *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
+ *             offset tables: d_payloadOffs and d_indexOffs of the ragged-corpus calls (one int64 entry per load)
  *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_file, d_count, d_index (an entry is two
  *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n])
  *    none     the byte streams: d_out, d_in, d_payload and the d_slots of ulcx_pack_streams_dev and ulcx_index_slots_dev
@@ -543,6 +544,57 @@ int  ulcx_index_packed_rows_dev(ulcx_decoder *dec, int nRows, const uint8_t *d_p
                                 const int32_t *d_payloadBytes, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream);
 int  ulcx_index_packed_rows_host(ulcx_decoder *dec, int nRows, const uint8_t *h_payload, long long payloadStride,
                                  const int32_t *h_payloadBytes, int maxBlocks, ulcx_index_entry *h_index, int32_t *h_nBlocks);
+
+/* Ragged corpus: the crop calls for files kept at their own length.  The strided layout above costs every file what the
+ * longest one costs; here payloads and index rows lie back to back, found through two offset tables (CSR; caller-owned, plain
+ * arrays):
+ *   d_payload      payloadTotal bytes: the files' payloads back to back, no alignment; payloadTotal may be any size
+ *   d_payloadOffs  int64 [nFiles + 1], 8-byte aligned: file f is bytes [offs[f], offs[f+1]) - its size is the difference, and stays
+ *                  below 2^31
+ *   d_index        indexTotal entries: the files' rows back to back
+ *   d_indexOffs    int64 [nFiles + 1], 8-byte aligned, in entries: row f has capacity offs[f+1] - offs[f], and so at most
+ *                  capacity - 1 blocks
+ *   d_indexBlocks  [nFiles], as above
+ * Everything else - n, nBlocks, d_file, d_first, d_count, rows past a file's end, STATE, ALIGNMENT / EXTENT / ORDER, the launch plan
+ * ulcx_decoder_last_cut reports - is exactly as for ulcx_decode_crops_dev with the same file held in the strided layout, and so
+ * is the output, bit for bit and with the noise included.
+ * The tables are trusted as little as the strided walk trusts its own: a file number outside [0, nFiles), offs[f] < 0,
+ * offs[f+1] < offs[f], offs[f+1] > the total, a file of 2^31 bytes or more, an index row whose capacity is below
+ * d_indexBlocks[f] + 1 or that leaves [0, indexTotal], and an entry among those that bound the row's blocks that points outside
+ * the file or not behind its predecessor each give a row of 0 bits and zero samples and leave the other rows as they are; no byte
+ * outside [d_payload, d_payload + payloadTotal), the index and the call's buffers is read or written.  The host form refuses
+ * with ULCX_ERR_ARG, before any device work, what ulcx_decode_crops_host refuses and an offset table that is not monotone or
+ * leaves its buffer. */
+int  ulcx_decode_crops_ragged_dev(ulcx_decoder *dec, int nFiles,
+                                  const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs /* [nFiles+1] */,
+                                  const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs /* [nFiles+1] */,
+                                  const int32_t *d_indexBlocks /* [nFiles] */,
+                                  int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count /* optional */,
+                                  int nBlocks, float *d_pcm, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_ragged_dev_pcm16(ulcx_decoder *dec, int nFiles,
+                                        const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                        const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs,
+                                        const int32_t *d_indexBlocks,
+                                        int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count,
+                                        int nBlocks, int16_t *d_pcm16, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_ragged_host(ulcx_decoder *dec, int nFiles,
+                                   const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                   const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs,
+                                   const int32_t *h_indexBlocks,
+                                   int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
+                                   int nBlocks, float *h_pcm, int32_t *h_bits);   /* synchronous */
+/* The index of a ragged corpus in one call: row f receives, entry for entry, what ulcx_index_packed_rows_dev writes for file f's
+ * payload alone with maxBlocks = capacity - 1, the {-1, 0} entries behind the closing one up to the row's capacity included, and
+ * d_nBlocks[f] the count.  A row of capacity below 1, or a file whose offsets are as refused above, gets d_nBlocks[f] = 0 and no
+ * entry; nothing outside [d_indexOffs[f], d_indexOffs[f+1]) is written for file f.  It reads the decoder's geometry and tables
+ * only, and no stream state.  One lane walks one file, so files of very different length in one wave wait for the longest.
+ * The host form refuses an offset table that is not monotone or leaves its buffer; entries of h_index outside the rows stay. */
+int  ulcx_index_packed_ragged_dev(ulcx_decoder *dec, int nFiles, const uint8_t *d_payload, long long payloadTotal,
+                                  const int64_t *d_payloadOffs, ulcx_index_entry *d_index, long long indexTotal,
+                                  const int64_t *d_indexOffs, int32_t *d_nBlocks, void *hipStream);
+int  ulcx_index_packed_ragged_host(ulcx_decoder *dec, int nFiles, const uint8_t *h_payload, long long payloadTotal,
+                                   const int64_t *h_payloadOffs, ulcx_index_entry *h_index, long long indexTotal,
+                                   const int64_t *h_indexOffs, int32_t *h_nBlocks);
 
 /* Index while encoding: the same table, grown call by call from what an encode call wrote - every block in its own slot,
  * its size in d_bits - so all of a call's blocks are parsed side by side and nothing is walked in series.  The result is,

@@ -7,6 +7,9 @@
     dec = ulc_amd.BatchDecoder(batch, 2, 2048, crop_blocks + 1)
     pcm, bits = corpus.crops(dec, files, first, crop_blocks)      # [n][crop_blocks * 2048][2] on the device
 
+CropCorpus(..., layout="ragged") keeps every file at its own length (payloads and index rows back to back behind offset tables,
+ulcx_decode_crops_ragged_dev) instead of at the longest file's: the layout for a corpus of files of very different length.
+
 Everything in front of freeze() is host logic (numpy, and the library's host-side parsers): it needs no GPU.  Plumbing only -
 the decode is the library's crop call, and there is no fallback."""
 import ctypes as C
@@ -29,8 +32,10 @@ def parse_ulc(data):
 
 
 class CropCorpus:
-    def __init__(self, n_chan, block_size):
-        self.C, self.BS = int(n_chan), int(block_size)
+    def __init__(self, n_chan, block_size, layout="strided"):
+        if layout not in ("strided", "ragged"):
+            raise UlcError(f"corpus: layout {layout!r} (strided or ragged)")
+        self.C, self.BS, self.ragged = int(n_chan), int(block_size), layout == "ragged"
         self._payloads, self._index, self._blocks = [], [], []      # per file: bytes; entries [n + 1] or None; blocks (header's when not indexed yet)
         self.frozen = False
 
@@ -69,6 +74,8 @@ class CropCorpus:
         F = len(self._payloads)
         if F < 1:
             raise UlcError("corpus: no files")
+        if self.ragged:
+            return self._layout_ragged()
         stride = (max(len(p) for p in self._payloads) + PAYLOAD_PAD + 15) & ~15
         index_stride = max(self._blocks) + 1
         payload = np.zeros((F, stride), np.uint8)
@@ -85,11 +92,75 @@ class CropCorpus:
         return {"stride": stride, "index_stride": index_stride, "payload": payload, "payload_bytes": nbytes, "index": index,
                 "index_blocks": blocks, "to_index": to_index}
 
+    def _layout_ragged(self):
+        """layout() of a ragged corpus: the payloads back to back with PAYLOAD_PAD bytes behind the last one, row f of the index
+        with blocks_f + 1 entries.  -> dict: payload uint8 [total], payload_offs int64 [F + 1] (file f is bytes offs[f] ..
+        offs[f + 1]), index INDEX_DTYPE [entries], index_offs int64 [F + 1], index_blocks, to_index as above."""
+        F = len(self._payloads)
+        poffs = np.zeros(F + 1, np.int64)
+        poffs[1:] = np.cumsum([len(p) for p in self._payloads])
+        ioffs = np.zeros(F + 1, np.int64)
+        ioffs[1:] = np.cumsum([b + 1 for b in self._blocks])
+        payload = np.zeros(int(poffs[-1]) + PAYLOAD_PAD, np.uint8)
+        index = np.zeros(int(ioffs[-1]), INDEX_DTYPE)
+        blocks = np.zeros(F, np.int32)
+        for f, (p, e) in enumerate(zip(self._payloads, self._index)):
+            payload[poffs[f]:poffs[f + 1]] = np.frombuffer(p, np.uint8)
+            if e is not None:
+                index[ioffs[f]:ioffs[f + 1]] = e
+                blocks[f] = len(e) - 1
+            else:
+                index[ioffs[f]:ioffs[f + 1]] = ulc_amd.new_index(1, self._blocks[f] + 1)[0]
+        to_index = np.array([f for f, e in enumerate(self._index) if e is None], np.int64)
+        return {"payload": payload, "payload_offs": poffs, "index": index, "index_offs": ioffs, "index_blocks": blocks, "to_index": to_index}
+
+    def _freeze_ragged(self, dev):
+        """freeze() of a ragged corpus: the files without a stored index are indexed with ONE ulcx_index_packed_ragged_dev call - in
+        place when that is every file, else on a copy of those files' payloads, whose rows then go to their places."""
+        import torch
+        lay = self.layout()
+        F = self.n_files = len(self._payloads)
+        self.device = dev
+        self.d_payload = torch.from_numpy(lay["payload"]).to(dev)
+        self.d_payload_offs = torch.from_numpy(lay["payload_offs"]).to(dev)
+        self.d_index = torch.from_numpy(lay["index"].view(np.int32).reshape(-1, 2)).to(dev)
+        self.d_index_offs = torch.from_numpy(lay["index_offs"]).to(dev)
+        self.d_index_blocks = torch.from_numpy(lay["index_blocks"]).to(dev)
+        todo = lay["to_index"]
+        if todo.size:
+            poffs, ioffs = lay["payload_offs"], lay["index_offs"]
+            if todo.size == F:
+                pay, po, idx, io, cnt, dst = self.d_payload, self.d_payload_offs, self.d_index, self.d_index_offs, self.d_index_blocks, None
+            else:
+                sub = np.concatenate([lay["payload"][poffs[f]:poffs[f + 1]] for f in todo] + [np.zeros(PAYLOAD_PAD, np.uint8)])
+                caps = np.array([ioffs[f + 1] - ioffs[f] for f in todo], np.int64)
+                pay = torch.from_numpy(sub).to(dev)
+                po = torch.from_numpy(np.concatenate([[0], np.cumsum([poffs[f + 1] - poffs[f] for f in todo])]).astype(np.int64)).to(dev)
+                io = torch.from_numpy(np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)).to(dev)
+                idx = torch.zeros((int(caps.sum()), 2), dtype=torch.int32, device=dev)
+                cnt = torch.zeros(todo.size, dtype=torch.int32, device=dev)
+                dst = torch.from_numpy(np.concatenate([np.arange(ioffs[f], ioffs[f + 1]) for f in todo])).to(dev)
+            with torch.cuda.device(dev):
+                dec = ulc_amd.BatchDecoder(1, self.C, self.BS, 1, device=dev.index or 0)     # geometry and tables are all the call reads of it
+                try:
+                    dec.index_packed_ragged_dev(int(todo.size), pay.data_ptr(), pay.numel(), po.data_ptr(), idx.data_ptr(), idx.shape[0], io.data_ptr(),
+                                                cnt.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+                    torch.cuda.current_stream(dev).synchronize()
+                finally:
+                    dec.close()
+            if dst is not None:
+                self.d_index.index_copy_(0, dst, idx)
+                self.d_index_blocks.index_copy_(0, torch.from_numpy(todo).to(dev), cnt)
+        self.frozen = True
+        return self
+
     def freeze(self, device="cuda:0"):
         """Payloads and indices to `device` as torch tensors (uint8 / int32), at the strides of layout(); the files without a
-        stored index are indexed there with ONE ulcx_index_packed_rows_dev call."""
+        stored index are indexed there with ONE ulcx_index_packed_rows_dev call.  (A ragged corpus: _freeze_ragged.)"""
         import torch
         dev = torch.device(device)
+        if self.ragged:
+            return self._freeze_ragged(dev)
         lay = self.layout()
         self.n_files, self.stride, self.index_stride = len(self._payloads), lay["stride"], lay["index_stride"]
         self.device = dev
@@ -118,8 +189,10 @@ class CropCorpus:
         return self
 
     def device_bytes(self):
-        """HBM bytes of the frozen corpus: payloads, their sizes, indices, block counts."""
-        return sum(t.numel() * t.element_size() for t in (self.d_payload, self.d_payload_bytes, self.d_index, self.d_index_blocks))
+        """HBM bytes of the frozen corpus: payloads, their sizes (ragged: the two offset tables), indices, block counts."""
+        held = ((self.d_payload, self.d_payload_offs, self.d_index, self.d_index_offs, self.d_index_blocks) if self.ragged else
+                (self.d_payload, self.d_payload_bytes, self.d_index, self.d_index_blocks))
+        return sum(t.numel() * t.element_size() for t in held)
 
     def crops(self, dec, files, first, n_blocks, count=None, pcm16=False):
         """Row i: blocks first[i] .. first[i] + n_blocks - 1 of file files[i] (the leading count[i] of them when `count` is
@@ -139,6 +212,12 @@ class CropCorpus:
         assert first.numel() == n and (want is None or want.numel() == n)
         pcm = torch.empty((n, n_blocks * self.BS, self.C), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
         bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        if self.ragged:
+            dec.decode_crops_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
+                                        self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
+                                        n, files.data_ptr(), first.data_ptr(), want.data_ptr() if want is not None else 0, n_blocks,
+                                        pcm.data_ptr(), bits.data_ptr(), stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
+            return pcm, bits
         dec.decode_crops_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
                              self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), first.data_ptr(),
                              want.data_ptr() if want is not None else 0, n_blocks, pcm.data_ptr(), bits.data_ptr(),

@@ -136,10 +136,10 @@ static int ilog2i(int x) { int r = 0; while ((1 << r) < x) r++; return r; }
 
 // Alignment of the caller's device pointers (include/ulc_amd.h, "Caller buffers"): each value is the widest access a kernel
 // makes to that buffer - 16 bytes for binary32 samples (float4 loads of the transform's fold, float4 stores of the
-// synthesis), 8 for PCM16 samples (short4) and for rate tables (float2), 4 for the int32 / binary32 / index arrays; the
+// synthesis), 8 for PCM16 samples (short4), for rate tables (float2) and for int64 offset tables, 4 for the int32 / binary32 / index arrays; the
 // byte streams (slots, payloads) need none.  A NULL (optional) pointer passes.  Checked by every _dev entry before any device
 // work, so that a refused call leaves the object's state as it was.
-enum { ULCX_ALIGN_PCM = 16, ULCX_ALIGN_PCM16 = 8, ULCX_ALIGN_RATE = 8, ULCX_ALIGN_WORD = 4 };
+enum { ULCX_ALIGN_PCM = 16, ULCX_ALIGN_PCM16 = 8, ULCX_ALIGN_RATE = 8, ULCX_ALIGN_OFFS = 8, ULCX_ALIGN_WORD = 4 };
 static bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 static int misaligned(const char *who, const char *what, const void *p, int a) {
     if (aligned_to(p, (uintptr_t)a)) return 0;
@@ -1483,25 +1483,46 @@ extern "C" int ulcx_decode_resident_range_host(ulcx_decoder *e, const int32_t *h
 // row from nothing, so the call needs no stream's state; what the synthesis leaves behind a row goes to the subset calls'
 // shadow state (dec_shadow) and is never scattered back.
 // the checks every crop entry makes, device or host pointers; the object comes last among them: every other refusal needs none
-static int crops_args_bad(const char *who, const ulcx_decoder *e, int nFiles, const void *payload, long long payloadStride, const void *payloadBytes,
-                          const void *index, int indexStride, const void *indexBlocks, int n, const void *file, const void *first,
-                          int nBlocks, const void *pcm, const void *bits) {
-    if (!payload || !payloadBytes || !index || !indexBlocks || !file || !first || !pcm || !bits) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
+// (layoutBad: NULL, or what is wrong with the scalars of the corpus's layout - strides, or a ragged corpus's totals)
+static int crops_checks(const char *who, const ulcx_decoder *e, int nFiles, bool anyNull, int n, int nBlocks, const char *layoutBad) {
+    if (anyNull) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
     if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
     if (nFiles < 1) { refuse(who, "bad argument (nFiles %d)", nFiles); return 1; }
     if (nBlocks < 1) { refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return 1; }
-    if (payloadStride < 1 || indexStride < 1) { refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride); return 1; }
+    if (layoutBad) { refuse(who, "bad argument (%s)", layoutBad); return 1; }
     if (!e) { refuse(who, "no decoder"); return 1; }
     if (n > e->B) { refuse(who, "bad argument (n %d: a call takes 1 .. nStreams = %d rows)", n, e->B); return 1; }
     if (nBlocks > e->maxK - 1) { refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return 1; }
     return 0;
 }
+static int crops_args_bad(const char *who, const ulcx_decoder *e, int nFiles, const void *payload, long long payloadStride, const void *payloadBytes,
+                          const void *index, int indexStride, const void *indexBlocks, int n, const void *file, const void *first,
+                          int nBlocks, const void *pcm, const void *bits) {
+    char bad[96];
+    snprintf(bad, sizeof bad, "payloadStride %lld, indexStride %d", payloadStride, indexStride);
+    return crops_checks(who, e, nFiles, !payload || !payloadBytes || !index || !indexBlocks || !file || !first || !pcm || !bits, n, nBlocks,
+                        (payloadStride < 1 || indexStride < 1) ? bad : nullptr);
+}
+// a ragged corpus: the files' payloads and index rows back to back, found through two int64 offset tables of nFiles + 1 entries
+struct CropsRagged { long long payloadTotal; const int64_t *payloadOffs; long long indexTotal; const int64_t *indexOffs; };
+static int crops_ragged_args_bad(const char *who, const ulcx_decoder *e, int nFiles, const void *payload, const CropsRagged &g, const void *index,
+                                 const void *indexBlocks, int n, const void *file, const void *first, int nBlocks, const void *pcm, const void *bits) {
+    char bad[96];
+    snprintf(bad, sizeof bad, "payloadTotal %lld, indexTotal %lld", g.payloadTotal, g.indexTotal);
+    return crops_checks(who, e, nFiles, !payload || !g.payloadOffs || !index || !g.indexOffs || !indexBlocks || !file || !first || !pcm || !bits, n, nBlocks,
+                        (g.payloadTotal < 0 || g.indexTotal < 0) ? bad : nullptr);
+}
+// ragged != NULL: the ragged layout (payloadStride, d_payloadBytes and indexStride are not looked at)
 static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                             const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
                             int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
-                            float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    if (crops_args_bad(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, d_first, nBlocks,
-                       d_pcm ? (const void *)d_pcm : d_pcm16, d_bits)) return ULCX_ERR_ARG;
+                            float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, const CropsRagged *ragged = nullptr) {
+    const void *out = d_pcm ? (const void *)d_pcm : d_pcm16;
+    if (ragged ? crops_ragged_args_bad(who, e, nFiles, d_payload, *ragged, d_index, d_indexBlocks, n, d_file, d_first, nBlocks, out, d_bits)
+               : crops_args_bad(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, d_first, nBlocks, out, d_bits))
+        return ULCX_ERR_ARG;
+    if (ragged && (misaligned(who, "d_payloadOffs", ragged->payloadOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", ragged->indexOffs, ULCX_ALIGN_OFFS)))
+        return ULCX_ERR_ARG;
     if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_file", d_file, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_first", d_first, ULCX_ALIGN_WORD) || misaligned(who, "d_count", d_count, ULCX_ALIGN_WORD) ||
@@ -1514,11 +1535,12 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const 
     c.B = n; c.K = nBlocks + 1; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = d_pcm16;
     c.bits = e->bitsScr; c.bitsOut = d_bits;
     c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
-    c.inBytes = (long long)nFiles * payloadStride;
+    c.inBytes = ragged ? ragged->payloadTotal : (long long)nFiles * payloadStride;
     c.range = 1; c.rIndex = d_index; c.rIndexStride = indexStride; c.rIndexBlocks = d_indexBlocks; c.rFirst = d_first;
     c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
     UlcxDecAux crop = {};
     crop.nFiles = nFiles; crop.cropFile = d_file; crop.cropCount = d_count;
+    if (ragged) { crop.payOffs = ragged->payloadOffs; crop.idxOffs = ragged->indexOffs; crop.idxTotal = ragged->indexTotal; }
     int set = 0;
     rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &crop);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
@@ -1607,6 +1629,115 @@ extern "C" int ulcx_index_packed_rows_host(ulcx_decoder *e, int nRows, const uin
     CKR(hipDeviceSynchronize());
     CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * nEnt, hipMemcpyDeviceToHost));
     CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * (size_t)nRows, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+
+// ---- crops of a ragged corpus (include/ulc_amd.h section 3): the crop family's body with the files found through offset tables.
+extern "C" int ulcx_decode_crops_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                            const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                            int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
+                                            float *d_pcm, int32_t *d_bits, void *hipStream) {
+    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
+    return decode_crops_any("ulcx_decode_crops_ragged_dev", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, d_first, d_count, nBlocks,
+                            d_pcm, nullptr, d_bits, hipStream, &g);
+}
+extern "C" int ulcx_decode_crops_ragged_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                  const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                  int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
+                                                  int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
+    return decode_crops_any("ulcx_decode_crops_ragged_dev_pcm16", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, d_first, d_count, nBlocks,
+                            nullptr, d_pcm16, d_bits, hipStream, &g);
+}
+// what a host form can refuse of the two tables: offsets that are negative, fall or leave their buffer, a file of 2^31 bytes or more
+static int ragged_tables_bad(const char *who, int nFiles, const CropsRagged &g) {
+    for (int f = 0; f < nFiles; f++) {
+        const long long p0 = g.payloadOffs[f], p1 = g.payloadOffs[f + 1], i0 = g.indexOffs[f], i1 = g.indexOffs[f + 1];
+        if (p0 < 0 || p1 < p0 || p1 > g.payloadTotal || p1 - p0 >= 0x80000000LL) { refuse(who, "file %d is bytes %lld .. %lld of a payload buffer of %lld", f, p0, p1, g.payloadTotal); return 1; }
+        if (i0 < 0 || i1 < i0 || i1 > g.indexTotal) { refuse(who, "file %d has index entries %lld .. %lld of %lld", f, i0, i1, g.indexTotal); return 1; }
+    }
+    return 0;
+}
+// the buffer and the two tables of a ragged host-pointer call, into buffers of the call's own (as payload_rows_up)
+static int ragged_up(DevTmp &t, int nFiles, const uint8_t *h_payload, const CropsRagged &g, uint8_t **dp, CropsRagged *dg) {
+    const size_t tb = sizeof(int64_t) * ((size_t)nFiles + 1);
+    int64_t *po = nullptr, *io = nullptr;
+    CKR(t.get(dp, (size_t)g.payloadTotal)); CKR(t.get(&po, tb)); CKR(t.get(&io, tb));
+    if (g.payloadTotal) CKR(hipMemcpy(*dp, h_payload, (size_t)g.payloadTotal, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(po, g.payloadOffs, tb, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(io, g.indexOffs, tb, hipMemcpyHostToDevice));
+    *dg = CropsRagged{ g.payloadTotal, po, g.indexTotal, io };
+    return ULCX_OK;
+}
+extern "C" int ulcx_decode_crops_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                             const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                             int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                                             float *h_pcm, int32_t *h_bits) {
+    const char *who = "ulcx_decode_crops_ragged_host";
+    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
+    if (crops_ragged_args_bad(who, e, nFiles, h_payload, g, h_index, h_indexBlocks, n, h_file, h_first, nBlocks, h_pcm, h_bits)) return ULCX_ERR_ARG;
+    // what the device forms cannot refuse: the tables, then the rows as the strided host form
+    if (ragged_tables_bad(who, nFiles, g)) return ULCX_ERR_ARG;
+    for (int i = 0; i < n; i++) {
+        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
+        const long long cap = h_indexOffs[h_file[i] + 1] - h_indexOffs[h_file[i]];
+        long long nI = h_indexBlocks[h_file[i]];
+        nI = nI < 0 ? 0 : nI > cap - 1 ? cap - 1 : nI;
+        if (h_first[i] < 0 || h_first[i] > nI) return refuse(who, "row %d starts at block %d of a file of %lld", i, (int)h_first[i], nI);
+        if (h_count && h_count[i] < 0) return refuse(who, "row %d wants %d blocks", i, (int)h_count[i]);
+    }
+    CKR(hipSetDevice(e->device));
+    const size_t NB = (size_t)n * nBlocks;
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dcnt = nullptr, *dfile = nullptr, *df = nullptr, *dwant = nullptr, *dbits = nullptr;
+    ulcx_index_entry *di = nullptr; float *dpcm = nullptr; CropsRagged dg = {};
+    int rc = ragged_up(t, nFiles, h_payload, g, &dp, &dg);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&dfile, sizeof(int32_t) * n)); CKR(t.get(&df, sizeof(int32_t) * n));
+    CKR(t.get(&di, sizeof(ulcx_index_entry) * (size_t)indexTotal)); CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
+    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dfile, h_file, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(df, h_first, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    if (indexTotal) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyHostToDevice));
+    if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
+    rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, dfile, df, dwant, nBlocks, dpcm, nullptr, dbits, nullptr, &dg);
+    return rc ? rc : dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+}
+// ulcx_index_packed_rows_* for files back to back: k_dindex_ragged over nFiles (geometry and tables are all that is read of the object)
+static int index_ragged_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, const CropsRagged &g, ulcx_index_entry *d_index,
+                            int32_t *d_nBlocks, void *hipStream) {
+    if (!d_payload || !g.payloadOffs || !d_index || !g.indexOffs || !d_nBlocks || nFiles < 1 || g.payloadTotal < 0 || g.indexTotal < 0) return refuse(who, "bad argument");
+    if (!e) return refuse(who, "no decoder");
+    if (misaligned(who, "d_payloadOffs", g.payloadOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", g.indexOffs, ULCX_ALIGN_OFFS) ||
+        misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) || misaligned(who, "d_nBlocks", d_nBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    UlcxDecCtx c = e->ctx;
+    c.B = nFiles; c.in = d_payload; c.packed = 1; c.payStride = 0; c.payBytes = nullptr;
+    c.inBytes = g.payloadTotal;
+    return ulcx_index_ragged_launch(c, g.payloadOffs, g.indexOffs, g.indexTotal, d_index, d_nBlocks, (hipStream_t)hipStream);
+}
+extern "C" int ulcx_index_packed_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                            ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, int32_t *d_nBlocks, void *hipStream) {
+    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
+    return index_ragged_any("ulcx_index_packed_ragged_dev", e, nFiles, d_payload, g, d_index, d_nBlocks, hipStream);
+}
+// (h_index is read as well as written: the entries between and behind the rows go back as they came)
+extern "C" int ulcx_index_packed_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                             ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, int32_t *h_nBlocks) {
+    const char *who = "ulcx_index_packed_ragged_host";
+    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
+    if (!h_payload || !h_payloadOffs || !h_index || !h_indexOffs || !h_nBlocks || nFiles < 1 || payloadTotal < 0 || indexTotal < 0) return refuse(who, "bad argument");
+    if (!e) return refuse(who, "no decoder");
+    if (ragged_tables_bad(who, nFiles, g)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dcnt = nullptr; ulcx_index_entry *di = nullptr; CropsRagged dg = {};
+    int rc = ragged_up(t, nFiles, h_payload, g, &dp, &dg);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * (size_t)indexTotal));
+    if (indexTotal) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyHostToDevice));
+    if ((rc = index_ragged_any(who, e, nFiles, dp, dg, di, dcnt, nullptr))) return rc;
+    CKR(hipDeviceSynchronize());
+    if (indexTotal) CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * (size_t)nFiles, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
 

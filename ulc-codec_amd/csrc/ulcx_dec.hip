@@ -491,15 +491,70 @@ __global__ __launch_bounds__(64) void k_dscan_crop(UlcxDecCtx c, int nFiles, con
     }
 }
 
+// The same for a corpus whose files lie back to back (ulcx_decode_crops_ragged_*): c.in is the whole buffer of c.inBytes bytes,
+// file f is its bytes [payOffs[f], payOffs[f + 1]) and its index row the entries [idxOffs[f], idxOffs[f + 1]) of c.rIndex (idxTotal
+// entries in all); both tables have nFiles + 1 entries, and all of this arithmetic is 64-bit.  Neither table is trusted: offsets
+// that are negative, fall, leave their buffer, give a file of 2^31 bytes or more, or give a row without room for the file's
+// rIndexBlocks + 1 entries make the file one that does not exist - its rows report 0 bits, and none of its bytes is looked at.
+__global__ __launch_bounds__(64) void k_dscan_crop_ragged(UlcxDecCtx c, int nFiles, const int32_t *file, const int32_t *count,
+                                                          const int64_t *payOffs, const int64_t *idxOffs, long long idxTotal) {
+    __shared__ uint2 ringP[DSCAN_RP * 64], ringN[DSCAN_RN * 64];
+    const int id0 = blockIdx.x * 64 + threadIdx.x, K = c.K;
+    const bool live0 = id0 < c.B * K;
+    const int id = live0 ? id0 : c.B * K - 1;                             // (a lane without a row shadows the last one, and writes nothing)
+    const int s = id / K, r = id - s * K;
+    const int f = file[s];
+    bool okF = f >= 0 && f < nFiles;
+    const size_t fi = okF ? (size_t)f : 0;                                // (nFiles >= 1: entries 0 and 1 of both tables exist)
+    const long long p0 = payOffs[fi], p1 = payOffs[fi + 1], i0 = idxOffs[fi], i1 = idxOffs[fi + 1];
+    int nI = c.rIndexBlocks[fi];
+    nI = nI < 0 ? 0 : nI;
+    okF = okF && p0 >= 0 && p1 >= p0 && p1 <= c.inBytes && p1 - p0 < 0x80000000LL
+              && i0 >= 0 && i1 >= i0 && i1 <= idxTotal && i1 - i0 > (long long)nI;
+    nI = okF ? nI : 0;
+    const long long avail = okF ? p1 - p0 : 0;
+    const uint8_t *base = c.in + (okF ? p0 : 0);
+    const ulcx_index_entry *row = c.rIndex + (okF ? i0 : 0);
+    // from here on the row logic of k_dscan_crop, line for line (kept apart: hoisted into a function of both, k_dscan_crop's
+    // code object changes)
+    const int first = c.rFirst[s];
+    int want = count ? count[s] : K - 1;                                  // leading blocks of the row that are wanted
+    want = want > K - 1 ? K - 1 : want;
+    bool okS = okF && first >= 0 && first <= nI && want > 0;
+    const int k = first - 1 + r;
+    if (okS) {
+        // the table is not trusted, and a row is all or nothing: every entry that bounds a block of the row (the one in front
+        // included) inside the file's payload and behind its predecessor - each lane looks at its row's <= K + 1 entries
+        const int j0 = first > 0 ? first - 1 : 0, j1 = first + want < nI ? first + want : nI;
+        long long prev = row[j0].ByteOffs;
+        bool okT = prev >= 0;
+        for (int j = j0 + 1; j <= j1; j++) { const long long o = row[j].ByteOffs; okT &= o > prev && o <= avail; prev = o; }
+        okS = okT;
+    }
+    int off = 0, ext = 0;
+    if (okS && k >= 0 && k < nI && r <= want) { off = row[k].ByteOffs; ext = row[k + 1].ByteOffs - off; }
+    const bool sane = off >= 0 && ext > 0 && (long long)off + ext <= avail;
+    if (!sane) { off = 0; ext = 0; }
+    const uint8_t *p = base + off, *bufEnd = c.in + c.inBytes;
+    // every look of every lane of the wave inside the buffer (k_dscan): the window without bounds checks
+    const bool inside = (size_t)(p - c.in) >= ((uintptr_t)p & 15) && (size_t)(bufEnd - p) >= (size_t)ext + 80;
+    const int blk = s * K + r;
+    const bool live = live0 && sane;
+    if (__ballot(!inside) == 0ull) scan_block<NybWinFast, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
+    else scan_block<NybWin, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
+    if (live0 && !sane) { c.bits[blk] = 0; c.wcScan[blk] = 0; c.draws[blk] = 0; }
+    if (live0 && r == 0) {
+        // what the synthesis needs to enter the row: whether row 0 holds a block, and the generator state in front of it
+        const int pre = (okS && first > 0) ? 1 : 0;
+        c.rInfo[s] = make_int2(pre, okS ? (int)row[first - pre].RngState : 0);
+    }
+}
+
 // Block index of packed payloads (ulcx_index_packed_*) - one lane per stream, the walk of k_dscan_packed without its notes:
 // per block its start and the state the stream's one generator chain has there (one jump by the block's draws).  It stops
 // where k_dscan_packed reports 0 bits.  No stream state, none of the per-block scratch.
-__global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx_index_entry *index, int32_t *nBlocks) {
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= c.B) return;
-    const int avail = c.payBytes[s];
-    const uint8_t *base = c.in + (size_t)s * c.payStride;
-    ulcx_index_entry *row = index + (size_t)s * ((size_t)maxBlocks + 1);
+// index_walk: one payload (avail bytes at base) into one row of maxBlocks + 1 entries -> the blocks found.
+__device__ __forceinline__ int index_walk(const UlcxDecCtx &c, const uint8_t *base, int avail, int maxBlocks, ulcx_index_entry *row) {
     int off = 0, n = 0;
     uint32_t st = 1234567u;                                          // ulcDecoder.c:76
     row[0].ByteOffs = 0; row[0].RngState = st;
@@ -512,7 +567,27 @@ __global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx
         row[n].ByteOffs = off; row[n].RngState = st;
     }
     for (int k = n + 1; k <= maxBlocks; k++) { row[k].ByteOffs = -1; row[k].RngState = 0u; }
-    nBlocks[s] = n;
+    return n;
+}
+__global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx_index_entry *index, int32_t *nBlocks) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= c.B) return;
+    nBlocks[s] = index_walk(c, c.in + (size_t)s * c.payStride, c.payBytes[s], maxBlocks, index + (size_t)s * ((size_t)maxBlocks + 1));
+}
+// The same for files that lie back to back (ulcx_index_packed_ragged_*) - one lane per file: file f is bytes [payOffs[f],
+// payOffs[f + 1]) of c.in, its row the entries [idxOffs[f], idxOffs[f + 1]) of `index` (idxTotal in all), filled as k_dindex fills
+// a row of maxBlocks = capacity - 1.  Offsets as k_dscan_crop_ragged refuses them, or a row without an entry: a count of 0 and
+// nothing written.  (A row of 2^31 entries or more is used up to that: a file below 2^31 bytes has fewer blocks.)  Lanes of one
+// wave wait for the longest file among them; the index is built once.
+__global__ __launch_bounds__(64) void k_dindex_ragged(UlcxDecCtx c, const int64_t *payOffs, const int64_t *idxOffs, long long idxTotal,
+                                                      ulcx_index_entry *index, int32_t *nBlocks) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= c.B) return;
+    const long long p0 = payOffs[f], p1 = payOffs[f + 1], i0 = idxOffs[f], i1 = idxOffs[f + 1];
+    const bool ok = p0 >= 0 && p1 >= p0 && p1 <= c.inBytes && p1 - p0 < 0x80000000LL && i0 >= 0 && i1 > i0 && i1 <= idxTotal;
+    if (!ok) { nBlocks[f] = 0; return; }
+    const long long cap = i1 - i0 < 0x7FFFFFFFLL ? i1 - i0 : 0x7FFFFFFFLL;
+    nBlocks[f] = index_walk(c, c.in + p0, (int)(p1 - p0), (int)cap - 1, index + i0);
 }
 
 // Block index of slot-form buffers (ulcx_index_slots_*): the blocks an encode call wrote, each in its own slot with its size
@@ -1514,7 +1589,9 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     const bool split = c.fastOK && aux.synGrid > 0;
     const void *syn = c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0) : syn_fn<float>(c, split, c.range != 0);
     CK(allow_lds(syn, lds));
-    if (aux.nFiles > 0) hipLaunchKernelGGL(k_dscan_crop, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount);
+    if (aux.nFiles > 0 && aux.payOffs) hipLaunchKernelGGL(k_dscan_crop_ragged, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount,
+                                                          aux.payOffs, aux.idxOffs, aux.idxTotal);
+    else if (aux.nFiles > 0) hipLaunchKernelGGL(k_dscan_crop, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount);
     else if (c.range) hipLaunchKernelGGL(k_dscan_range, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
@@ -1532,6 +1609,12 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
 
 int ulcx_index_launch(const UlcxDecCtx &c, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, hipStream_t st) {
     hipLaunchKernelGGL(k_dindex, dim3((c.B + 63) / 64), dim3(64), 0, st, c, maxBlocks, d_index, d_nBlocks);
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+int ulcx_index_ragged_launch(const UlcxDecCtx &c, const int64_t *d_payOffs, const int64_t *d_idxOffs, long long idxTotal, ulcx_index_entry *d_index,
+                             int32_t *d_nBlocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_dindex_ragged, dim3((c.B + 63) / 64), dim3(64), 0, st, c, d_payOffs, d_idxOffs, idxTotal, d_index, d_nBlocks);
     CK(hipGetLastError());
     return ULCX_OK;
 }

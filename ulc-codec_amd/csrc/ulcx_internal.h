@@ -218,10 +218,18 @@ struct UlcxDecAux {
     int nFiles = 0;
     const int32_t *cropFile = nullptr;   // [c.B] file of each row
     const int32_t *cropCount = nullptr;  // [c.B] leading blocks wanted of each row, or NULL: all of them
+    // ragged corpus (ulcx_decode_crops_ragged_*): payOffs != NULL - the walk is k_dscan_crop_ragged; c.in / c.inBytes are the whole
+    // payload buffer, c.rIndex the whole index, and the files are found through the two offset tables (c.payStride, c.payBytes
+    // and c.rIndexStride are not looked at)
+    const int64_t *payOffs = nullptr, *idxOffs = nullptr;   // [nFiles + 1] bytes of c.in / entries of c.rIndex
+    long long idxTotal = 0;              // entries of c.rIndex
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
 int ulcx_index_launch(const UlcxDecCtx &c, int maxBlocks, ulcx_index_entry *d_index, int32_t *d_nBlocks, hipStream_t st);
+// the same for c.B files back to back in c.in (c.inBytes: all of it), found through offset tables of c.B + 1 entries
+int ulcx_index_ragged_launch(const UlcxDecCtx &c, const int64_t *d_payOffs, const int64_t *d_idxOffs, long long idxTotal, ulcx_index_entry *d_index,
+                             int32_t *d_nBlocks, hipStream_t st);
 // block index of slot-form buffers: open nRows rows; append nBlocks blocks per row (c.in / c.slot / c.inBytes set as for a
 // slot-form call of nRows streams; geometry and tables are all else that is read of c)
 int ulcx_index_begin_launch(int nRows, ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, hipStream_t st);

@@ -13,6 +13,7 @@ MODE_VBR, MODE_CBR, MODE_ABR = 0, 1, 2
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
+_i64p = C.POINTER(C.c_int64)
 
 EXPORTS = [
     "ULC_EncoderState_Init", "ULC_EncoderState_Destroy", "ULC_EncodeBlock_CBR", "ULC_EncodeBlock_ABR",
@@ -37,6 +38,8 @@ EXPORTS = [
     "ulcx_index_begin_dev", "ulcx_index_slots_dev", "ulcx_index_slots_host", "ulcx_index_check", "ulcx_decoder_set_resident_index",
     "ulcx_ulx_header_pack", "ulcx_ulx_header_parse",
     "ulcx_decode_crops_dev", "ulcx_decode_crops_dev_pcm16", "ulcx_decode_crops_host", "ulcx_index_packed_rows_dev", "ulcx_index_packed_rows_host",
+    "ulcx_decode_crops_ragged_dev", "ulcx_decode_crops_ragged_dev_pcm16", "ulcx_decode_crops_ragged_host",
+    "ulcx_index_packed_ragged_dev", "ulcx_index_packed_ragged_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -172,6 +175,15 @@ def lib():
                                                  C.c_int, _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p]
             l.ulcx_index_packed_rows_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
             l.ulcx_index_packed_rows_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i32p, C.c_int, C.c_void_p, _i32p]
+        if hasattr(l, "ulcx_decode_crops_ragged_dev"):     # crops of a ragged corpus
+            l.ulcx_decode_crops_ragged_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_decode_crops_ragged_dev_pcm16.argtypes = l.ulcx_decode_crops_ragged_dev.argtypes
+            l.ulcx_decode_crops_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p,
+                                                        C.c_int, _i32p, _i32p, _i32p, C.c_int, _f32p, _i32p]
+            l.ulcx_index_packed_ragged_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]
+            l.ulcx_index_packed_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -687,6 +699,55 @@ class BatchDecoder(_StreamSlots):
     def index_packed_rows_dev(self, n_rows, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream=0):
         _check(lib().ulcx_index_packed_rows_dev(self.h, n_rows, d_payload, stride, d_payload_bytes, max_blocks, d_index, d_n_blocks, stream or None),
                "ulcx_index_packed_rows_dev")
+
+    def decode_crops_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, first, n_blocks, count=None):
+        """decode_crops() of a ragged corpus: payload uint8 [total], the files back to back, file f its bytes payload_offs[f] ..
+        payload_offs[f+1] (int64 [F+1]); index [entries], row f its entries index_offs[f] .. index_offs[f+1] (int64 [F+1]);
+        index_blocks [F].  Rows, counts and the result as decode_crops()."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        poffs = np.ascontiguousarray(payload_offs, dtype=np.int64)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE).reshape(-1)
+        ioffs = np.ascontiguousarray(index_offs, dtype=np.int64)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        want = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+        F, n = blocks.shape[0], files.shape[0]
+        assert poffs.shape == (F + 1,) and ioffs.shape == (F + 1,) and first.shape == (n,) and (want is None or want.shape == (n,))
+        pcm = np.zeros((n, n_blocks * self.BS, self.C), np.float32)
+        bits = np.zeros((n, n_blocks), np.int32)
+        _check(lib().ulcx_decode_crops_ragged_host(self.h, F, _p(payload, _u8p), payload.size, _p(poffs, _i64p), index.ctypes.data, index.size,
+                                                   _p(ioffs, _i64p), _p(blocks, _i32p), n, _p(files, _i32p), _p(first, _i32p), _p(want, _i32p),
+                                                   n_blocks, _p(pcm, _f32p), _p(bits, _i32p)), "ulcx_decode_crops_ragged_host")
+        return pcm, bits
+
+    def decode_crops_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
+                                n, d_file, d_first, d_count, n_blocks, d_pcm, d_bits, stream=0, pcm16=False):
+        """Device form (d_count 0 / None: every row takes all n_blocks); d_pcm is int16 [n][n_blocks][BS][C] with pcm16."""
+        fn = lib().ulcx_decode_crops_ragged_dev_pcm16 if pcm16 else lib().ulcx_decode_crops_ragged_dev
+        _check(fn(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks, n, d_file, d_first,
+                  d_count or None, n_blocks, d_pcm, d_bits, stream or None),
+               "ulcx_decode_crops_ragged_dev_pcm16" if pcm16 else "ulcx_decode_crops_ragged_dev")
+
+    def index_packed_ragged(self, payload, payload_offs, index_offs, index=None):
+        """The index of files back to back: row f (entries index_offs[f] .. index_offs[f+1]) as index_packed_rows() fills a row of
+        that capacity - 1 blocks.  -> (index [index_offs[-1]], or `index` filled in place: entries outside the rows stay; count [F])."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        poffs = np.ascontiguousarray(payload_offs, dtype=np.int64)
+        ioffs = np.ascontiguousarray(index_offs, dtype=np.int64)
+        F = poffs.shape[0] - 1
+        assert F >= 1 and ioffs.shape == (F + 1,)
+        if index is None:
+            index = np.zeros(max(0, int(ioffs.max())), INDEX_DTYPE)
+        assert index.dtype == INDEX_DTYPE and index.ndim == 1 and index.flags["C_CONTIGUOUS"]
+        count = np.zeros(F, np.int32)
+        _check(lib().ulcx_index_packed_ragged_host(self.h, F, _p(payload, _u8p), payload.size, _p(poffs, _i64p), index.ctypes.data, index.size,
+                                                   _p(ioffs, _i64p), _p(count, _i32p)), "ulcx_index_packed_ragged_host")
+        return index, count
+
+    def index_packed_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_n_blocks, stream=0):
+        _check(lib().ulcx_index_packed_ragged_dev(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs,
+                                                  d_n_blocks, stream or None), "ulcx_index_packed_ragged_dev")
 
     def decode_packed_dev(self, d_payload, stride, d_payload_bytes, n_blocks, d_pcm, d_bits, stream=0):
         _check(lib().ulcx_decode_packed_dev(self.h, d_payload, stride, d_payload_bytes, n_blocks, d_pcm, d_bits, stream or None),
