@@ -134,6 +134,10 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
  *             offset tables: d_payloadOffs and d_indexOffs of the ragged-corpus calls (one int64 entry per load)
+ *             sample positions: d_start of the sample-crop calls (one int64 entry per load)
+ *    4 bytes  d_pcm of the sample-crop calls (ulcx_decode_crops_samples_*: a channel's plane starts at any sample; the kernels
+ *             store two samples at once only where the address is a multiple of 8), and their d_len
+ *    2 bytes  d_pcm16 of the sample-crop calls (likewise; two samples at once only at a multiple of 4)
  *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_file, d_count, d_index (an entry is two
  *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n])
  *    none     the byte streams: d_out, d_in, d_payload and the d_slots of ulcx_pack_streams_dev and ulcx_index_slots_dev
@@ -583,6 +587,64 @@ int  ulcx_decode_crops_ragged_host(ulcx_decoder *dec, int nFiles,
                                    const int32_t *h_indexBlocks,
                                    int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
                                    int nBlocks, float *h_pcm, int32_t *h_bits);   /* synchronous */
+/* Sample crops: the crop calls with rows given in samples and the output written channels-first - what a training loader draws
+ * (a crop of nSamples samples from sample t0 of a file) in the layout models take ([batch][channel][time]), straight from the
+ * synthesis: the trim, the per-row offset and the planar layout happen where the samples are stored, no pass over the output.
+ * The corpus arguments are those of ulcx_decode_crops_dev / ulcx_decode_crops_ragged_dev; n is 1 .. nStreams.
+ *   d_start  int64 [n]: the row's first sample, a position in the DECODED stream of file d_file[i]: sample j of the stream is
+ *            sample j % BlockSize of block j / BlockSize of the sequential decode.  The codec's delay is not compensated here
+ *            (INTEGRATION.md section 2).
+ *   d_len    [n] or NULL: samples wanted of the row, clamped to [0, nSamples]; NULL: nSamples for every row
+ *   nSamples >= 1, any value (no multiple of anything); the blocks a row can touch, nB = ulcx_crop_blocks(BlockSize, nSamples),
+ *            must be at most maxBlocksPerCall - 1
+ *   d_pcm    [n][nChan][nSamples], written in full: d_pcm[i][ch][t] is, bit for bit and with the noise included, sample
+ *            d_start[i] + t of channel ch of the sequential decode of the file, for t < d_len[i] and inside the file's whole
+ *            valid blocks; zero everywhere else - behind d_len[i], behind the file's last indexed block, from a corrupt block on
+ *   d_bits   [n][nB]: entry k is the size of block d_start[i] / BlockSize + k; 0 behind the blocks the row needs and behind the
+ *            file's end - what a crop call with first = start / BlockSize and count = the blocks the row touches reports
+ * Untrusted rows: whatever gives a crop row of zeros gives one here (a file number out of range, a bad index entry, bad ragged
+ * tables), and so do d_start[i] < 0 and d_start[i] / BlockSize > d_indexBlocks[file]; the other rows are left alone and nothing
+ * outside the call's buffers is read or written.  The host forms refuse, with ULCX_ERR_ARG before any device work, a negative
+ * start, a start beyond the file's indexBlocks * BlockSize, a negative length, and whatever ulcx_decode_crops_host /
+ * ulcx_decode_crops_ragged_host refuse.
+ * STATE / ORDER: exactly the crop calls' - no stream's persistent state is read or changed, the call mixes freely with streaming
+ * decodes on the object, it is asynchronous on hipStream (three kernels: the rows, the walk, the synthesis), and nothing is
+ * allocated after the first subset or crop call.
+ * ALIGNMENT: d_start 8 bytes; d_file, d_len, d_bits 4; d_pcm 4, d_pcm16 2 (a plane starts at any sample); the corpus as above. */
+int  ulcx_crop_blocks(int BlockSize, int nSamples);   /* 1 + (nSamples + BlockSize - 2) / BlockSize: the blocks a crop touches at the worst start; host arithmetic (0: a bad argument) */
+int  ulcx_decode_crops_samples_dev(ulcx_decoder *dec, int nFiles,
+                                   const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes /* [nFiles] */,
+                                   const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks /* [nFiles] */,
+                                   int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len /* optional */,
+                                   int nSamples, float *d_pcm, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_samples_dev_pcm16(ulcx_decoder *dec, int nFiles,
+                                         const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                         const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                         int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len,
+                                         int nSamples, int16_t *d_pcm16 /* converted as ulcx_decode_dev_pcm16 converts */, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_samples_host(ulcx_decoder *dec, int nFiles,
+                                    const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                    const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                    int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len,
+                                    int nSamples, float *h_pcm, int32_t *h_bits);   /* synchronous */
+int  ulcx_decode_crops_samples_ragged_dev(ulcx_decoder *dec, int nFiles,
+                                          const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs /* [nFiles+1] */,
+                                          const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs /* [nFiles+1] */,
+                                          const int32_t *d_indexBlocks /* [nFiles] */,
+                                          int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len /* optional */,
+                                          int nSamples, float *d_pcm, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_samples_ragged_dev_pcm16(ulcx_decoder *dec, int nFiles,
+                                                const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs,
+                                                const int32_t *d_indexBlocks,
+                                                int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len,
+                                                int nSamples, int16_t *d_pcm16, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_samples_ragged_host(ulcx_decoder *dec, int nFiles,
+                                           const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                           const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs,
+                                           const int32_t *h_indexBlocks,
+                                           int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len,
+                                           int nSamples, float *h_pcm, int32_t *h_bits);   /* synchronous */
 /* The index of a ragged corpus in one call: row f receives, entry for entry, what ulcx_index_packed_rows_dev writes for file f's
  * payload alone with maxBlocks = capacity - 1, the {-1, 0} entries behind the closing one up to the row's capacity included, and
  * d_nBlocks[f] the count.  A row of capacity below 1, or a file whose offsets are as refused above, gets d_nBlocks[f] = 0 and no

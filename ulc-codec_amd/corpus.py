@@ -6,6 +6,8 @@
     corpus.freeze("cuda:0")                        # payloads and indices to the device, once
     dec = ulc_amd.BatchDecoder(batch, 2, 2048, crop_blocks + 1)
     pcm, bits = corpus.crops(dec, files, first, crop_blocks)      # [n][crop_blocks * 2048][2] on the device
+    pcm, bits = corpus.sample_crops(dec, files, start, n_samples) # [n][2][n_samples]: n_samples from sample start[i], channels-first
+                                                                  # (dec: max_blocks > ulc_amd.crop_blocks(2048, n_samples))
 
 CropCorpus(..., layout="ragged") keeps every file at its own length (payloads and index rows back to back behind offset tables,
 ulcx_decode_crops_ragged_dev) instead of at the longest file's: the layout for a corpus of files of very different length.
@@ -29,6 +31,21 @@ def parse_ulc(data):
     if h.StreamOffs < ULC_HEADER_BYTES or h.StreamOffs > len(data):
         raise UlcError(f"ulc: the payload starts at byte {h.StreamOffs} of a file of {len(data)}")
     return h, bytes(data[h.StreamOffs:])
+
+
+def sample_rows(start, length, block_size):
+    """The block rows of sample crops, as the library's prologue kernel derives them (pure numpy; the tests hold the two together):
+    start int64 [n] sample positions in the decoded streams, length [n] samples wanted (already clamped to [0, n_samples]).
+    -> (first, count, skip) int64 [n]: the crop starts `skip` samples into block `first` and touches `count` blocks (0 for an
+    empty row).  A negative start is refused as the library refuses it: first -1, count 0, skip 0."""
+    start = np.asarray(start, np.int64)
+    length = np.asarray(length, np.int64)
+    bs = int(block_size)
+    ok = start >= 0
+    first = np.where(ok, start // bs, -1)
+    skip = np.where(ok, start % bs, 0)
+    count = np.where(ok & (length > 0), (skip + length - 1) // bs + 1, 0)
+    return first, count, skip
 
 
 class CropCorpus:
@@ -222,4 +239,36 @@ class CropCorpus:
                              self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), first.data_ptr(),
                              want.data_ptr() if want is not None else 0, n_blocks, pcm.data_ptr(), bits.data_ptr(),
                              stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
+        return pcm, bits
+
+    def sample_crops(self, dec, files, start, n_samples, length=None, pcm16=False):
+        """Row i: n_samples samples from sample start[i] of the decoded stream of file files[i] (its leading length[i] when
+        `length` is given; zeros behind, and behind the file's end), written channels-first by the synthesis itself
+        (ulcx_decode_crops_samples_dev): no gather, no transpose.  start: int64; files / length: int32; tensors on the corpus's
+        device, or anything torch.as_tensor takes.  Positions are of the decoded stream: the codec's delay is not compensated.
+        -> (pcm [n][nChan][n_samples] float32, or int16 with pcm16; bits int32 [n][crop_blocks]) on the device, enqueued on
+        torch's current stream.  `dec`: a BatchDecoder of this geometry with n_streams >= n and max_blocks > crop_blocks =
+        ulc_amd.crop_blocks(BlockSize, n_samples); no stream state of it is read or changed."""
+        import torch
+        if not self.frozen:
+            raise UlcError("corpus: not frozen")
+        if (dec.C, dec.BS) != (self.C, self.BS):
+            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
+        as_t = lambda v, t: torch.as_tensor(v, dtype=t, device=self.device).contiguous()
+        files, start = as_t(files, torch.int32), as_t(start, torch.int64)
+        want = None if length is None else as_t(length, torch.int32)
+        n = files.numel()
+        assert start.numel() == n and (want is None or want.numel() == n)
+        pcm = torch.empty((n, self.C, n_samples), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
+        bits = torch.empty((n, ulc_amd.crop_blocks(self.BS, n_samples)), dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.ragged:
+            dec.decode_crops_samples_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
+                                                self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
+                                                n, files.data_ptr(), start.data_ptr(), want.data_ptr() if want is not None else 0, n_samples,
+                                                pcm.data_ptr(), bits.data_ptr(), stream=stream, pcm16=pcm16)
+            return pcm, bits
+        dec.decode_crops_samples_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
+                                     self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), start.data_ptr(),
+                                     want.data_ptr() if want is not None else 0, n_samples, pcm.data_ptr(), bits.data_ptr(), stream=stream, pcm16=pcm16)
         return pcm, bits

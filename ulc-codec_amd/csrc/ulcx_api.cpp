@@ -113,6 +113,7 @@ struct ulcx_decoder {
     // synthesis leaves its result, as lap2 .. dead2 are for the object's own arrays) and the device copy of a host form's list
     float *subLap[2] = {}; int *subLastSub[2] = {}; uint32_t *subSeed[2] = {}; int *subDead[2] = {}; int *subPackOff = nullptr;
     int32_t *subSlots = nullptr;
+    int32_t *sampRows = nullptr;                                  // [4][B] a sample-crop call's rows as k_crop_sample_rows leaves them: first, count, skip, len (allocated with the shadow state)
 };
 
 #ifndef ULCX_SRC_REV
@@ -1108,6 +1109,7 @@ static int dec_shadow(ulcx_decoder *e) {
         if (!e->subDead[set] && (rc = dalloc(e->allocs, &e->subDead[set], (size_t)e->B, false))) return rc;
     }
     if (!e->subPackOff && (rc = dalloc(e->allocs, &e->subPackOff, (size_t)e->B, false))) return rc;
+    if (!e->sampRows && (rc = dalloc(e->allocs, &e->sampRows, 4 * (size_t)e->B, false))) return rc;
     return ULCX_OK;
 }
 
@@ -1512,22 +1514,30 @@ static int crops_ragged_args_bad(const char *who, const ulcx_decoder *e, int nFi
     return crops_checks(who, e, nFiles, !payload || !g.payloadOffs || !index || !g.indexOffs || !indexBlocks || !file || !first || !pcm || !bits, n, nBlocks,
                         (g.payloadTotal < 0 || g.indexTotal < 0) ? bad : nullptr);
 }
+// the rows of a sample-crop call (ulcx_decode_crops_samples_*): d_first / d_count are not given, nBlocks is ulcx_crop_blocks(nSamples)
+struct CropsSamples { const int64_t *start; const int32_t *len; int nSamples; };
 // ragged != NULL: the ragged layout (payloadStride, d_payloadBytes and indexStride are not looked at)
+// samp != NULL: a sample-crop call - the rows come from (start, len), the output is [n][nChan][nSamples] and needs its element's alignment only
 static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                             const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
                             int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
-                            float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, const CropsRagged *ragged = nullptr) {
+                            float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, const CropsRagged *ragged = nullptr,
+                            const CropsSamples *samp = nullptr) {
     const void *out = d_pcm ? (const void *)d_pcm : d_pcm16;
-    if (ragged ? crops_ragged_args_bad(who, e, nFiles, d_payload, *ragged, d_index, d_indexBlocks, n, d_file, d_first, nBlocks, out, d_bits)
-               : crops_args_bad(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, d_first, nBlocks, out, d_bits))
+    const void *rows = samp ? (const void *)samp->start : d_first;
+    if (ragged ? crops_ragged_args_bad(who, e, nFiles, d_payload, *ragged, d_index, d_indexBlocks, n, d_file, rows, nBlocks, out, d_bits)
+               : crops_args_bad(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, rows, nBlocks, out, d_bits))
         return ULCX_ERR_ARG;
     if (ragged && (misaligned(who, "d_payloadOffs", ragged->payloadOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", ragged->indexOffs, ULCX_ALIGN_OFFS)))
         return ULCX_ERR_ARG;
     if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_file", d_file, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_first", d_first, ULCX_ALIGN_WORD) || misaligned(who, "d_count", d_count, ULCX_ALIGN_WORD) ||
-        misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16) ||
         misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    // (a plane of a sample crop starts at any sample: the kernels use wider stores only where the address allows them)
+    if (samp ? (misaligned(who, "d_start", samp->start, ULCX_ALIGN_OFFS) || misaligned(who, "d_len", samp->len, ULCX_ALIGN_WORD) ||
+                misaligned(who, "d_pcm", d_pcm, (int)sizeof(float)) || misaligned(who, "d_pcm16", d_pcm16, (int)sizeof(int16_t)))
+             : (misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16))) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     int rc = dec_shadow(e);
     if (rc) return rc;
@@ -1541,6 +1551,11 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const 
     UlcxDecAux crop = {};
     crop.nFiles = nFiles; crop.cropFile = d_file; crop.cropCount = d_count;
     if (ragged) { crop.payOffs = ragged->payloadOffs; crop.idxOffs = ragged->indexOffs; crop.idxTotal = ragged->indexTotal; }
+    if (samp) {
+        crop.sampStart = samp->start; crop.sampLen = samp->len; crop.nSamples = samp->nSamples;
+        crop.sampFirst = e->sampRows; crop.sampCount = e->sampRows + e->B; crop.sampSkip = e->sampRows + 2 * (size_t)e->B; crop.sampLenC = e->sampRows + 3 * (size_t)e->B;
+        c.rFirst = crop.sampFirst; crop.cropCount = crop.sampCount;
+    }
     int set = 0;
     rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &crop);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
@@ -1701,6 +1716,144 @@ extern "C" int ulcx_decode_crops_ragged_host(ulcx_decoder *e, int nFiles, const 
     if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
     rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, dfile, df, dwant, nBlocks, dpcm, nullptr, dbits, nullptr, &dg);
     return rc ? rc : dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+}
+// ---- sample crops (include/ulc_amd.h section 3): the crop families' bodies with rows given in samples and the output channels-first.
+extern "C" int ulcx_crop_blocks(int BlockSize, int nSamples) {
+    if (BlockSize < 1 || nSamples < 1) return 0;
+    const long long nB = 1 + ((long long)nSamples + BlockSize - 2) / BlockSize;
+    return nB > 0x7FFFFFFFLL ? 0x7FFFFFFF : (int)nB;
+}
+// nSamples of a sample-crop entry -> the blocks per row the crop body is called with (checked there against maxBlocksPerCall - 1);
+// 0: refused here.  Without an object the count is 1: the body then refuses the call for the object's absence, or for what it
+// checks before that.
+static int samples_blocks(const char *who, const ulcx_decoder *e, int nSamples) {
+    if (nSamples < 1) { refuse(who, "bad argument (nSamples %d)", nSamples); return 0; }
+    if (!e) return 1;
+    const int nB = ulcx_crop_blocks(e->BS, nSamples);
+    if (nB > e->maxK - 1) { refuse(who, "bad argument (nSamples %d touches up to %d blocks; a row has maxBlocksPerCall - 1 = %d)", nSamples, nB, e->maxK - 1); return 0; }
+    return nB;
+}
+extern "C" int ulcx_decode_crops_samples_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                             const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                             int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
+                                             float *d_pcm, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_samples_dev";
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    const CropsSamples sm = { d_start, d_len, nSamples };
+    return decode_crops_any(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, nullptr, nullptr, nB,
+                            d_pcm, nullptr, d_bits, hipStream, nullptr, &sm);
+}
+extern "C" int ulcx_decode_crops_samples_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                                   const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                                   int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
+                                                   int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_samples_dev_pcm16";
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    const CropsSamples sm = { d_start, d_len, nSamples };
+    return decode_crops_any(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, nullptr, nullptr, nB,
+                            nullptr, d_pcm16, d_bits, hipStream, nullptr, &sm);
+}
+extern "C" int ulcx_decode_crops_samples_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                    const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                    int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
+                                                    float *d_pcm, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_samples_ragged_dev";
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
+    const CropsSamples sm = { d_start, d_len, nSamples };
+    return decode_crops_any(who, e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, nullptr, nullptr, nB, d_pcm, nullptr, d_bits, hipStream, &g, &sm);
+}
+extern "C" int ulcx_decode_crops_samples_ragged_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                          const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                          int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
+                                                          int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_samples_ragged_dev_pcm16";
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
+    const CropsSamples sm = { d_start, d_len, nSamples };
+    return decode_crops_any(who, e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, nullptr, nullptr, nB, nullptr, d_pcm16, d_bits, hipStream, &g, &sm);
+}
+// what the device forms cannot refuse of row i, which names a file of nI indexed blocks
+static int sample_row_bad(const char *who, int i, int BS, long long nI, long long start, const int32_t *h_len) {
+    if (start < 0 || start > nI * BS) { refuse(who, "row %d starts at sample %lld of a file of %lld blocks of %d", i, start, nI, BS); return 1; }
+    if (h_len && h_len[i] < 0) { refuse(who, "row %d wants %d samples", i, (int)h_len[i]); return 1; }
+    return 0;
+}
+// the rows of a host form up, its output buffers, and after the call the results down: [n][nChan][nSamples] samples, [n][nB] sizes
+struct SampleStage { int32_t *file = nullptr, *len = nullptr, *bits = nullptr; int64_t *start = nullptr; float *pcm = nullptr; };
+static int sample_rows_up(DevTmp &t, const ulcx_decoder *e, int n, int nB, int nSamples, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, SampleStage *g) {
+    CKR(t.get(&g->file, sizeof(int32_t) * n)); CKR(t.get(&g->start, sizeof(int64_t) * n));
+    CKR(t.get(&g->pcm, sizeof(float) * (size_t)n * e->C * (size_t)nSamples)); CKR(t.get(&g->bits, sizeof(int32_t) * (size_t)n * nB));
+    CKR(hipMemcpy(g->file, h_file, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(g->start, h_start, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    if (h_len) { CKR(t.get(&g->len, sizeof(int32_t) * n)); CKR(hipMemcpy(g->len, h_len, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
+    return ULCX_OK;
+}
+static int sample_results_down(const ulcx_decoder *e, const SampleStage &g, int n, int nB, int nSamples, float *h_pcm, int32_t *h_bits) {
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_pcm, g.pcm, sizeof(float) * (size_t)n * e->C * (size_t)nSamples, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_bits, g.bits, sizeof(int32_t) * (size_t)n * nB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+extern "C" int ulcx_decode_crops_samples_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                              const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                              int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples,
+                                              float *h_pcm, int32_t *h_bits) {
+    const char *who = "ulcx_decode_crops_samples_host";
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    if (crops_args_bad(who, e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, n, h_file, h_start, nB, h_pcm, h_bits)) return ULCX_ERR_ARG;
+    for (int i = 0; i < n; i++) {
+        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
+        int nI = h_indexBlocks[h_file[i]];
+        nI = nI < 0 ? 0 : nI > indexStride - 1 ? indexStride - 1 : nI;                   // (as the walk reads a count)
+        if (sample_row_bad(who, i, e->BS, nI, h_start[i], h_len)) return ULCX_ERR_ARG;
+    }
+    CKR(hipSetDevice(e->device));
+    const size_t nEnt = (size_t)nFiles * (size_t)indexStride;
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr; ulcx_index_entry *di = nullptr; SampleStage g;
+    int rc = payload_rows_up(t, nFiles, h_payload, payloadStride, h_payloadBytes, &dp, &dn);
+    if (!rc) rc = sample_rows_up(t, e, n, nB, nSamples, h_file, h_start, h_len, &g);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
+    const CropsSamples sm = { g.start, g.len, nSamples };
+    rc = decode_crops_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, n, g.file, nullptr, nullptr, nB, g.pcm, nullptr, g.bits, nullptr, nullptr, &sm);
+    return rc ? rc : sample_results_down(e, g, n, nB, nSamples, h_pcm, h_bits);
+}
+extern "C" int ulcx_decode_crops_samples_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                                     const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                                     int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples,
+                                                     float *h_pcm, int32_t *h_bits) {
+    const char *who = "ulcx_decode_crops_samples_ragged_host";
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
+    if (crops_ragged_args_bad(who, e, nFiles, h_payload, g, h_index, h_indexBlocks, n, h_file, h_start, nB, h_pcm, h_bits)) return ULCX_ERR_ARG;
+    if (ragged_tables_bad(who, nFiles, g)) return ULCX_ERR_ARG;
+    for (int i = 0; i < n; i++) {
+        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
+        const long long cap = h_indexOffs[h_file[i] + 1] - h_indexOffs[h_file[i]];
+        long long nI = h_indexBlocks[h_file[i]];
+        nI = nI < 0 ? 0 : nI > cap - 1 ? cap - 1 : nI;
+        if (sample_row_bad(who, i, e->BS, nI < 0 ? 0 : nI, h_start[i], h_len)) return ULCX_ERR_ARG;
+    }
+    CKR(hipSetDevice(e->device));
+    DevTmp t; uint8_t *dp = nullptr; int32_t *dcnt = nullptr; ulcx_index_entry *di = nullptr; CropsRagged dg = {}; SampleStage sg;
+    int rc = ragged_up(t, nFiles, h_payload, g, &dp, &dg);
+    if (!rc) rc = sample_rows_up(t, e, n, nB, nSamples, h_file, h_start, h_len, &sg);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * (size_t)indexTotal));
+    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
+    if (indexTotal) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyHostToDevice));
+    const CropsSamples sm = { sg.start, sg.len, nSamples };
+    rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, sg.file, nullptr, nullptr, nB, sg.pcm, nullptr, sg.bits, nullptr, &dg, &sm);
+    return rc ? rc : sample_results_down(e, sg, n, nB, nSamples, h_pcm, h_bits);
 }
 // ulcx_index_packed_rows_* for files back to back: k_dindex_ragged over nFiles (geometry and tables are all that is read of the object)
 static int index_ragged_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, const CropsRagged &g, ulcx_index_entry *d_index,

@@ -931,6 +931,71 @@ template <typename OUT> __device__ __forceinline__ OUT *out_base(const UlcxDecCt
 template <> __device__ __forceinline__ float *out_base<float>(const UlcxDecCtx &c) { return c.pcm; }
 template <> __device__ __forceinline__ int16_t *out_base<int16_t>(const UlcxDecCtx &c) { return c.pcm16; }
 
+// ---------------------------------------------------------------------------
+// Sample-crop store mode (ulcx_decode_crops_samples_*): a row of the call is nSamples samples from sample `skip` of its first
+// block on, and the output is channels-first, [row][channel][nSamples].  The synthesis is the range synthesis, block for block;
+// only where a sample goes changes: sample m of output block kOut of a row belongs at t = kOut * BlockSize + m - skip of each
+// channel's plane, it is stored when t lies in [0, nSamples), and as 0 when t >= len (the row's length).  Both kernels take the
+// mode as a further argument (k_dsyn<..., UlcxSampArg>): no other instantiation sees any of it.
+// One (row, block)'s clip is three bounds on m and is the same for every thread: scalars.
+struct UlcxSampArg { const int32_t *skip, *len; int nSamples; };      // [rows] each, written by k_crop_sample_rows
+struct UlcxSampNone {};
+__device__ __forceinline__ UlcxSampNone samp_arg() { return UlcxSampNone{}; }
+__device__ __forceinline__ const UlcxSampArg &samp_arg(const UlcxSampArg &a) { return a; }
+template <typename OUT>
+struct SampBlk {
+    OUT *org;                    // where sample m = 0 of channel 0 would go (in front of the plane when the row starts inside the block: an address only)
+    int nS;                      // elements per plane
+    int mLo, mHi, mLen;          // m in [mLo, mHi) is stored; m >= mLen as 0
+    __device__ __forceinline__ OUT *plane(int ch) const { return org + (long long)ch * nS; }
+    // a sample pair at an even m of this plane may go out as one store
+    static __device__ __forceinline__ bool pairs(const OUT *pl) { return ((uintptr_t)pl & (2 * sizeof(OUT) - 1)) == 0; }
+    // (m is never negative and a block is below 2^32 bytes: a uniform base and a 32-bit byte offset per thread)
+    static __device__ __forceinline__ OUT *at(OUT *pl, int m) { return (OUT *)((char *)pl + (unsigned)m * (unsigned)sizeof(OUT)); }
+    __device__ __forceinline__ void one(OUT *pl, int m, float v) const {
+        if (m >= mLo && m < mHi) st1(at(pl, m), m < mLen ? v : 0.0f);
+    }
+    // samples m (even) and m + 1; al = pairs(pl)
+    __device__ __forceinline__ void two(OUT *pl, bool al, int m, float v0, float v1) const {
+        if (al && m >= mLo && m + 1 < mHi) st2(at(pl, m), m < mLen ? v0 : 0.0f, m + 1 < mLen ? v1 : 0.0f);
+        else { one(pl, m, v0); one(pl, m + 1, v1); }
+    }
+    // a dead block: zeros wherever the block has samples of the row
+    __device__ __forceinline__ void zero(int C, int tid) const {
+        for (int ch = 0; ch < C; ch++) { OUT *pl = plane(ch); for (int m = mLo + tid; m < mHi; m += WG) st1(at(pl, m), 0.0f); }
+    }
+};
+template <typename OUT>
+__device__ __forceinline__ SampBlk<OUT> samp_blk(OUT *base, int C, int BS, int nS, int row, int kOut, int skip, int len) {
+    SampBlk<OUT> b;
+    const long long lo = (long long)skip - (long long)kOut * BS;      // m of the row's sample 0
+    b.nS = nS;
+    b.org = base + ((long long)row * C * nS - lo);
+    b.mLo = lo > 0 ? (int)lo : 0;
+    b.mHi = lo + nS < BS ? (int)(lo + nS) : BS;                        // (a block behind the row's samples: mHi <= mLo, nothing stored)
+    b.mLen = lo + len < BS ? (int)(lo + len) : BS;
+    return b;
+}
+// The rows of a sample-crop call, one lane per row: (start, len) -> the block range the crop walk works on and what the stores
+// clip by.  first = start / BlockSize, skip = start % BlockSize, count = the blocks samples [skip, skip + len) touch, len clamped
+// to [0, nSamples] (NULL: nSamples).  A start the walk must refuse - negative, or a block number no index can hold - becomes
+// first = -1: the row comes back as zeros, as a crop row with that first does.
+__global__ __launch_bounds__(64) void k_crop_sample_rows(int n, int BS, int nSamples, const int64_t *start, const int32_t *len,
+                                                         int32_t *first, int32_t *count, int32_t *skip, int32_t *lenC) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const long long st = start[i];
+    int l = len ? len[i] : nSamples;
+    l = l < 0 ? 0 : l > nSamples ? nSamples : l;
+    const long long b = st / BS;
+    const bool ok = st >= 0 && b < 0x40000000LL;
+    const int sk = ok ? (int)(st - b * BS) : 0;
+    first[i] = ok ? (int)b : -1;
+    count[i] = (ok && l > 0) ? (int)(((long long)sk + l - 1) / BS) + 1 : 0;
+    skip[i] = sk;
+    lenC[i] = ok ? l : 0;
+}
+
 // LDS carve, in floats.  Stereo kernel (k_dsyn):  z [2 padded arrays of BS/2 complex] | twl [BS/4 complex] |
 //   per wave: noise runs, prefix counts, seed table | 128 block / unit seeds.  General kernel (k_dgen): z [1 array] | per-wave lists.
 #define DSYN_PWORDS(BS) (((BS) / 32 > 64 ? (BS) / 32 : 64) + 2)
@@ -958,9 +1023,14 @@ __host__ __device__ static inline DsynLds dsyn_lds(int BS, int fast, int twInLds
 // RANGE: a range call (ulcx_decode_range_*; always with SPLIT).  A stream is entered from nothing instead of from its
 // persistent state: zero lapping state, the generator state the block index holds, and - unless the range starts at
 // block 0 - the block in front of it (row k0 - 1 of the stream) run without output, as a cut enters a stream.
-template <typename OUT, int DEC_MAXT, bool TWL, bool SPLIT = false, int BSC = 0, bool RANGE = false>
-__global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
+// SA = UlcxSampArg (one further argument; RANGE launches only): the sample-crop store mode - every store of output samples
+// goes through the (row, block)'s SampBlk instead of to the block's interleaved row.  SA empty: none of that exists.
+template <typename OUT, int DEC_MAXT, bool TWL, bool SPLIT = false, int BSC = 0, bool RANGE = false, typename... SA>
+__global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
     static_assert(!RANGE || SPLIT, "k_dsyn: a range call enters streams as a cut does");
+    constexpr bool SAMP = sizeof...(SA) != 0;
+    static_assert(!SAMP || RANGE, "k_dsyn: sample crops are range launches");
+    const auto &samp = samp_arg(sa...);
     extern __shared__ float lds[];
     const int BS = BSC ? BSC : c.BS, H2 = BS / 2;
     constexpr int C = 2;
@@ -1024,6 +1094,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
     }
     int sCur = -1, lastSub = 0, dead = 0, chunkK = -1;
     uint32_t seed = 0;
+    int rowSkip = 0, rowLen = 0;                                     // SAMP: the row's first sample within its first block, its length
     const int laneOuter = lane, tidOuter = tid;
     for (; nTrip > 0; nTrip--, warm = false) {
         // Inside this loop over the blocks the compiler hoists every load and index that depends on the thread only
@@ -1052,6 +1123,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
             dead = RANGE ? bad : (c.dead[s] | bad);                  // (a corrupt block in front: the stream is dead, no other state matters)
             lastSub = RANGE ? 0 : c.lastSub[s];
             seed = RANGE ? (uint32_t)c.rInfo[s].y : c.seed[s];
+            if constexpr (SAMP) { rowSkip = samp.skip[s]; rowLen = samp.len[s]; }
             if constexpr (RANGE) { if (k == c.k0 && kf == c.k0) for (int i = tid; i < 2 * H2; i += WG) scr[i] = 0.0f; }   // a range from block 0: nothing pending (ordered by the barrier in front of the chunk's tables)
             if (k > kf) {
                 const uint32_t ws = wave_scan_add(dsum);             // (lane 63: the wave's sum)
@@ -1101,13 +1173,19 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
         const bool lastOfStream = k == c.k1 - 1;
         const size_t oblk = RANGE ? (size_t)s * (c.K - 1) + (warm ? 0 : k - 1) : (size_t)blk;   // (a range call's output has no row for the block in front)
         OUT *outp = out_base<OUT>(c) + oblk * C * BS;
+        SampBlk<OUT> sb; OUT *sp0 = nullptr, *sp1 = nullptr; bool sal0 = false, sal1 = false;   // SAMP: where this block's samples go instead - the two planes, and whether their pairs are aligned
+        if constexpr (SAMP) {
+            sb = samp_blk<OUT>(out_base<OUT>(c), C, BS, samp.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
+            sp0 = sb.plane(0); sp1 = sb.plane(1); sal0 = sb.pairs(sp0); sal1 = sb.pairs(sp1);
+        }
         if constexpr (RANGE) { if (!warm && tid == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; }
         // where this block finds and leaves the lapping state
         const float *lapR = (!SPLIT || RANGE) ? scr : (k == c.k0 ? c.lap + (size_t)s * C * H2 : scr);
         float *lapW = !SPLIT ? scr : (lastOfStream ? c.lapO + (size_t)s * C * H2 : scr);
         if (dead) {
             if (!warm) {
-                for (int i = tid; i < C * BS; i += WG) st1(outp + i, 0.0f);
+                if constexpr (SAMP) sb.zero(C, tid);
+                else for (int i = tid; i < C * BS; i += WG) st1(outp + i, 0.0f);
                 if (tid == 0) c.bits[blk] = 0;
             }
             if (lastOfStream && tid == 0) { c.lastSubO[s] = lastSub; c.seedO[s] = seed; c.deadO[s] = 1; }
@@ -1276,8 +1354,13 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
                             lo2[q] = make_float2(mLo + sLo, mLo - sLo);
                             hi2[q] = make_float2(mHi + sHi, mHi - sHi);
                         }
+                        if constexpr (SAMP) {
+                            sb.two(sp0, sal0, pv[1], lo2[1].x, lo2[0].x); sb.two(sp1, sal1, pv[1], lo2[1].y, lo2[0].y);
+                            sb.two(sp0, sal0, S - 1 - pv[0], hi2[0].x, hi2[1].x); sb.two(sp1, sal1, S - 1 - pv[0], hi2[0].y, hi2[1].y);
+                        } else {
                         st4(outp + 2 * pv[1], lo2[1].x, lo2[1].y, lo2[0].x, lo2[0].y);
                         st4(outp + 2 * (S - 1 - pv[0]), hi2[0].x, hi2[0].y, hi2[1].x, hi2[1].y);
+                        }
                     }
                     *(float2 *)(L0 + 2 * k1) = make_float2(ya1.x, ya2.y);
                     *(float2 *)(L1 + 2 * k1) = make_float2(yb1.x, yb2.y);
@@ -1321,8 +1404,13 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
                         hi2[q] = make_float2(m.hi + sd.hi, m.hi - sd.hi);
                     }
                     // positions pv[1] = pv[0]-1 and S-1-pv[0], S-pv[0] are neighbours: two aligned 16-byte stores
+                    if constexpr (SAMP) {
+                        sb.two(sp0, sal0, pv[1], lo2[1].x, lo2[0].x); sb.two(sp1, sal1, pv[1], lo2[1].y, lo2[0].y);
+                        sb.two(sp0, sal0, S - 1 - pv[0], hi2[0].x, hi2[1].x); sb.two(sp1, sal1, S - 1 - pv[0], hi2[0].y, hi2[1].y);
+                    } else {
                     st4(outp + 2 * pv[1], lo2[1].x, lo2[1].y, lo2[0].x, lo2[0].y);
                     st4(outp + 2 * (S - 1 - pv[0]), hi2[0].x, hi2[0].y, hi2[1].x, hi2[1].y);
+                    }
                     }
                     L0[2 * k1] = ya1.x; L0[2 * k1 + 1] = ya2.y;
                     L1[2 * k1] = yb1.x; L1[2 * k1 + 1] = yb2.y;
@@ -1347,11 +1435,13 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
             if (!warm) {
             for (int n = 2 * tid; n < H2; n += 2 * WG) {
                 const float mx = L0[H2 - 1 - n], my = L0[H2 - 2 - n], sx = L1[H2 - 1 - n], sy = L1[H2 - 2 - n];
-                st4(outp + 2 * n, mx + sx, mx - sx, my + sy, my - sy);
+                if constexpr (SAMP) { sb.two(sp0, sal0, n, mx + sx, my + sy); sb.two(sp1, sal1, n, mx - sx, my - sy); }
+                else st4(outp + 2 * n, mx + sx, mx - sx, my + sy, my - sy);
             }
             for (int n = 2 * tid; n < H2; n += 2 * WG) {
                 const float2 m = *(const float2 *)(t0 + padf(n)), sd = *(const float2 *)(t1 + padf(n));
-                st4(outp + 2 * (H2 + n), m.x + sd.x, m.x - sd.x, m.y + sd.y, m.y - sd.y);
+                if constexpr (SAMP) { sb.two(sp0, sal0, H2 + n, m.x + sd.x, m.y + sd.y); sb.two(sp1, sal1, H2 + n, m.x - sd.x, m.y - sd.y); }
+                else st4(outp + 2 * (H2 + n), m.x + sd.x, m.x - sd.x, m.y + sd.y, m.y - sd.y);
             }
             }
             __syncthreads();
@@ -1376,8 +1466,11 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c) {
 // the lapping state and the staging of the time samples in global memory.  Correct for every geometry the
 // reference accepts (ulcDecoder.c:33-35: up to 255 channels, BlockSize up to 32768), not tuned.
 // ---------------------------------------------------------------------------
-template <typename OUT, bool RANGE = false>
-__global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
+template <typename OUT, bool RANGE = false, typename... SA>
+__global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
+    constexpr bool SAMP = sizeof...(SA) != 0;                        // the sample-crop store mode, as k_dsyn's
+    static_assert(!SAMP || RANGE, "k_dgen: sample crops are range launches");
+    const auto &samp = samp_arg(sa...);
     extern __shared__ float lds[];
     const int BS = c.BS, C = c.C, H2 = BS / 2;
     const int s = c.s0 + blockIdx.x, tid = threadIdx.x;
@@ -1396,7 +1489,8 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
     int dead = c.dead[s];
     uint32_t seed = c.seed[s];
     float *scr = c.scratch + (size_t)s * 4 * BS;                     // staging: dst[2][BS] | dec[BS] | tmpq[BS/2]
-    int kBeg = 0;
+    int kBeg = 0, rowSkip = 0, rowLen = 0;
+    if constexpr (SAMP) { rowSkip = samp.skip[s]; rowLen = samp.len[s]; }
     if constexpr (RANGE) {
         // a range call (k_dsyn): the stream is entered from nothing - zero lapping state, the index's generator state -, and
         // row 0, the block in front of the range, runs without output when there is one
@@ -1412,8 +1506,12 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
         const bool warm = RANGE && k == 0;
         const size_t oblk = RANGE ? (size_t)s * (c.K - 1) + (warm ? 0 : k - 1) : (size_t)blk;
         OUT *outp = out_base<OUT>(c) + oblk * C * BS;
+        SampBlk<OUT> sb;
+        if constexpr (SAMP) sb = samp_blk<OUT>(out_base<OUT>(c), C, BS, samp.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
         if constexpr (RANGE) { if (!warm && tid == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; }
         if (dead) {
+            if constexpr (SAMP) { if (!warm) sb.zero(C, tid); }
+            else
             if (!warm) for (int i = tid; i < C * BS; i += WG) st1(outp + i, 0.0f);
             if (tid == 0) c.bits[blk] = 0;
             continue;
@@ -1517,11 +1615,12 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c) {
                         for (int n = tid; n < BS; n += WG) {
                             const float m = dm[n], sd = ds[n];                            // ulcDecoder.c:281-289
                             const float l = m + sd, r = m - sd;
-                            if (C == 2) st2(outp + 2 * n, l, r);
+                            if constexpr (SAMP) { sb.one(sb.plane(ch - 1), n, l); sb.one(sb.plane(ch), n, r); }
+                            else if (C == 2) st2(outp + 2 * n, l, r);
                             else { st1(outp + (size_t)n * C + ch - 1, l); st1(outp + (size_t)n * C + ch, r); }
                         }
                     } else {
-                        for (int n = tid; n < BS; n += WG) st1(outp + (size_t)n * C + ch, dst[n]);
+                        for (int n = tid; n < BS; n += WG) { if constexpr (SAMP) sb.one(sb.plane(ch), n, dst[n]); else st1(outp + (size_t)n * C + ch, dst[n]); }
                     }
                     __syncthreads();
                 }
@@ -1542,19 +1641,22 @@ size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds) {
 
 // The synthesis instantiation of a context, THE one place that maps a geometry to its kernel: what is launched, what has
 // its dynamic-LDS limit raised and what is asked for its occupancy are this pointer.
-template <typename OUT, bool SPLIT, bool RANGE>
+// (SA: UlcxSampArg for the sample-crop store mode - the kernel then takes that further argument -, else empty)
+template <typename OUT, bool SPLIT, bool RANGE, typename... SA>
 static const void *syn_pick(const UlcxDecCtx &cc) {
     constexpr bool TW = DSYN_TWL != 0;
-    if (!cc.fastOK) return (const void *)k_dgen<OUT, RANGE>;
-    if (cc.BS == 2048 && DSYN_C2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 2048, RANGE>;
-    if (cc.BS <= 2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 0, RANGE>;
-    if (cc.BS == 4096 && DSYN_C4096) return (const void *)k_dsyn<OUT, 32, false, SPLIT, 4096, RANGE>;
-    return (const void *)k_dsyn<OUT, 32, false, SPLIT, 0, RANGE>;
+    if (!cc.fastOK) return (const void *)k_dgen<OUT, RANGE, SA...>;
+    if (cc.BS == 2048 && DSYN_C2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 2048, RANGE, SA...>;
+    if (cc.BS <= 2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 0, RANGE, SA...>;
+    if (cc.BS == 4096 && DSYN_C4096) return (const void *)k_dsyn<OUT, 32, false, SPLIT, 4096, RANGE, SA...>;
+    return (const void *)k_dsyn<OUT, 32, false, SPLIT, 0, RANGE, SA...>;
 }
-// split: the grid is a cut of the (stream, block) pairs; range: a range call, which runs the cut form for every grid
+// split: the grid is a cut of the (stream, block) pairs; range: a range call, which runs the cut form for every grid;
+// samp: a sample-crop call, a range call in the sample store mode
 template <typename OUT>
-static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range) {
-    return range ? syn_pick<OUT, true, true>(cc) : split ? syn_pick<OUT, true, false>(cc) : syn_pick<OUT, false, false>(cc);
+static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range, bool samp = false) {
+    return samp ? syn_pick<OUT, true, true, UlcxSampArg>(cc)
+         : range ? syn_pick<OUT, true, true>(cc) : split ? syn_pick<OUT, true, false>(cc) : syn_pick<OUT, false, false>(cc);
 }
 // A launch with more than 48 KiB of dynamic LDS: raise the kernel's limit to this launch's size (ulcx_enc.hip: allow_lds).
 static hipError_t allow_lds(const void *fn, size_t lds) {
@@ -1587,8 +1689,11 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     c.s0 = 0; c.s1 = c.B; c.k0 = c.range ? 1 : 0; c.k1 = c.K;
     const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds);
     const bool split = c.fastOK && aux.synGrid > 0;
-    const void *syn = c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0) : syn_fn<float>(c, split, c.range != 0);
+    const bool samp = aux.sampStart != nullptr;                       // a sample-crop call: rows from (start, len) first, then the crop walk on them
+    const void *syn = c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp) : syn_fn<float>(c, split, c.range != 0, samp);
     CK(allow_lds(syn, lds));
+    if (samp) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, c.BS, aux.nSamples, aux.sampStart, aux.sampLen,
+                                 aux.sampFirst, aux.sampCount, aux.sampSkip, aux.sampLenC);
     if (aux.nFiles > 0 && aux.payOffs) hipLaunchKernelGGL(k_dscan_crop_ragged, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount,
                                                           aux.payOffs, aux.idxOffs, aux.idxTotal);
     else if (aux.nFiles > 0) hipLaunchKernelGGL(k_dscan_crop, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount);
@@ -1599,7 +1704,8 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     if (!(ULCX_DBG(c) & 8)) {
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
         c.synFull = split ? aux.synFull : (c.range && c.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
-        void *args[] = { &c };
+        UlcxSampArg sa = { aux.sampSkip, aux.sampLenC, aux.nSamples };
+        void *args[] = { &c, &sa };                                  // (the second one: the sample-crop instantiations only)
         CK(hipLaunchKernel(syn, dim3(g), dim3(WG), args, lds, st));
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));

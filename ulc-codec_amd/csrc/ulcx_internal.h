@@ -223,6 +223,13 @@ struct UlcxDecAux {
     // and c.rIndexStride are not looked at)
     const int64_t *payOffs = nullptr, *idxOffs = nullptr;   // [nFiles + 1] bytes of c.in / entries of c.rIndex
     long long idxTotal = 0;              // entries of c.rIndex
+    // sample crops (ulcx_decode_crops_samples_*): sampStart != NULL - k_crop_sample_rows first turns the caller's (start, len) rows
+    // into the decoder-owned arrays below ([nStreams] each); c.rFirst is sampFirst and cropCount is sampCount, so the crop walk
+    // runs on them as on a caller's, and the synthesis is the sample-store instantiation, which takes sampSkip / sampLenC / nSamples
+    const int64_t *sampStart = nullptr;  // [c.B] first sample of each row in its file's decoded stream
+    const int32_t *sampLen = nullptr;    // [c.B] samples wanted of each row, or NULL: nSamples
+    int nSamples = 0;                    // samples per plane of the output
+    int32_t *sampFirst = nullptr, *sampCount = nullptr, *sampSkip = nullptr, *sampLenC = nullptr;
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)

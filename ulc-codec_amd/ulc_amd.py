@@ -40,6 +40,8 @@ EXPORTS = [
     "ulcx_decode_crops_dev", "ulcx_decode_crops_dev_pcm16", "ulcx_decode_crops_host", "ulcx_index_packed_rows_dev", "ulcx_index_packed_rows_host",
     "ulcx_decode_crops_ragged_dev", "ulcx_decode_crops_ragged_dev_pcm16", "ulcx_decode_crops_ragged_host",
     "ulcx_index_packed_ragged_dev", "ulcx_index_packed_ragged_host",
+    "ulcx_crop_blocks", "ulcx_decode_crops_samples_dev", "ulcx_decode_crops_samples_dev_pcm16", "ulcx_decode_crops_samples_host",
+    "ulcx_decode_crops_samples_ragged_dev", "ulcx_decode_crops_samples_ragged_dev_pcm16", "ulcx_decode_crops_samples_ragged_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -184,6 +186,18 @@ def lib():
             l.ulcx_index_packed_ragged_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                                        C.c_void_p, C.c_void_p]
             l.ulcx_index_packed_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p]
+        if hasattr(l, "ulcx_decode_crops_samples_dev"):    # sample crops, channels-first
+            l.ulcx_crop_blocks.argtypes = [C.c_int, C.c_int]
+            l.ulcx_decode_crops_samples_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_decode_crops_samples_dev_pcm16.argtypes = l.ulcx_decode_crops_samples_dev.argtypes
+            l.ulcx_decode_crops_samples_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i32p, C.c_void_p, C.c_int, _i32p,
+                                                         C.c_int, _i32p, _i64p, _i32p, C.c_int, _f32p, _i32p]
+            l.ulcx_decode_crops_samples_ragged_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_decode_crops_samples_ragged_dev_pcm16.argtypes = l.ulcx_decode_crops_samples_ragged_dev.argtypes
+            l.ulcx_decode_crops_samples_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p,
+                                                                C.c_int, _i32p, _i64p, _i32p, C.c_int, _f32p, _i32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -218,6 +232,12 @@ def lib():
 
 class UlcError(RuntimeError):
     pass
+
+
+def crop_blocks(block_size, n_samples):
+    """Blocks a crop of n_samples samples touches at the worst start (ulcx_crop_blocks): a sample-crop call's d_bits row, and
+    what max_blocks - 1 of its decoder must reach."""
+    return int(lib().ulcx_crop_blocks(int(block_size), int(n_samples)))
 
 
 def build_rev():
@@ -728,6 +748,62 @@ class BatchDecoder(_StreamSlots):
         _check(fn(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks, n, d_file, d_first,
                   d_count or None, n_blocks, d_pcm, d_bits, stream or None),
                "ulcx_decode_crops_ragged_dev_pcm16" if pcm16 else "ulcx_decode_crops_ragged_dev")
+
+    def decode_crops_samples(self, payload, payload_bytes, index, index_blocks, files, start, n_samples, length=None):
+        """Sample crops of a corpus held as for decode_crops(): row i is n_samples samples from sample start[i] (int64) of the
+        decoded stream of file files[i], its leading length[i] when `length` is given (zeros behind), channels-first
+        -> (pcm [n][C][n_samples], bits [n][crop_blocks(BS, n_samples)])."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int64)
+        want = None if length is None else np.ascontiguousarray(length, dtype=np.int32)
+        F, stride = payload.shape
+        n = files.shape[0]
+        assert nbytes.shape == (F,) and index.shape[0] == F and blocks.shape == (F,) and start.shape == (n,)
+        assert want is None or want.shape == (n,)
+        pcm = np.zeros((n, self.C, max(1, n_samples)), np.float32)
+        bits = np.zeros((n, max(1, crop_blocks(self.BS, n_samples))), np.int32)
+        _check(lib().ulcx_decode_crops_samples_host(self.h, F, _p(payload, _u8p), stride, _p(nbytes, _i32p), index.ctypes.data, index.shape[1],
+                                                    _p(blocks, _i32p), n, _p(files, _i32p), _p(start, _i64p), _p(want, _i32p), n_samples,
+                                                    _p(pcm, _f32p), _p(bits, _i32p)), "ulcx_decode_crops_samples_host")
+        return pcm, bits
+
+    def decode_crops_samples_dev(self, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_start, d_len,
+                                 n_samples, d_pcm, d_bits, stream=0, pcm16=False):
+        """Device form (d_len 0 / None: every row takes all n_samples); d_pcm is [n][C][n_samples], int16 with pcm16."""
+        fn = lib().ulcx_decode_crops_samples_dev_pcm16 if pcm16 else lib().ulcx_decode_crops_samples_dev
+        _check(fn(self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_start, d_len or None,
+                  n_samples, d_pcm, d_bits, stream or None), "ulcx_decode_crops_samples_dev_pcm16" if pcm16 else "ulcx_decode_crops_samples_dev")
+
+    def decode_crops_samples_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, start, n_samples, length=None):
+        """decode_crops_samples() of a ragged corpus, held as for decode_crops_ragged()."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        poffs = np.ascontiguousarray(payload_offs, dtype=np.int64)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE).reshape(-1)
+        ioffs = np.ascontiguousarray(index_offs, dtype=np.int64)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        start = np.ascontiguousarray(start, dtype=np.int64)
+        want = None if length is None else np.ascontiguousarray(length, dtype=np.int32)
+        F, n = blocks.shape[0], files.shape[0]
+        assert poffs.shape == (F + 1,) and ioffs.shape == (F + 1,) and start.shape == (n,) and (want is None or want.shape == (n,))
+        pcm = np.zeros((n, self.C, max(1, n_samples)), np.float32)
+        bits = np.zeros((n, max(1, crop_blocks(self.BS, n_samples))), np.int32)
+        _check(lib().ulcx_decode_crops_samples_ragged_host(self.h, F, _p(payload, _u8p), payload.size, _p(poffs, _i64p), index.ctypes.data, index.size,
+                                                           _p(ioffs, _i64p), _p(blocks, _i32p), n, _p(files, _i32p), _p(start, _i64p), _p(want, _i32p),
+                                                           n_samples, _p(pcm, _f32p), _p(bits, _i32p)), "ulcx_decode_crops_samples_ragged_host")
+        return pcm, bits
+
+    def decode_crops_samples_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
+                                        n, d_file, d_start, d_len, n_samples, d_pcm, d_bits, stream=0, pcm16=False):
+        """Device form (d_len 0 / None: every row takes all n_samples); d_pcm is [n][C][n_samples], int16 with pcm16."""
+        fn = lib().ulcx_decode_crops_samples_ragged_dev_pcm16 if pcm16 else lib().ulcx_decode_crops_samples_ragged_dev
+        _check(fn(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks, n, d_file, d_start,
+                  d_len or None, n_samples, d_pcm, d_bits, stream or None),
+               "ulcx_decode_crops_samples_ragged_dev_pcm16" if pcm16 else "ulcx_decode_crops_samples_ragged_dev")
 
     def index_packed_ragged(self, payload, payload_offs, index_offs, index=None):
         """The index of files back to back: row f (entries index_offs[f] .. index_offs[f+1]) as index_packed_rows() fills a row of
