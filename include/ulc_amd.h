@@ -133,11 +133,13 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  *             saved stream records: d_state of the stream-slot entries (16-byte loads and stores)
  *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
- *             offset tables: d_payloadOffs and d_indexOffs of the ragged-corpus calls (one int64 entry per load)
+ *             offset tables: d_payloadOffs and d_indexOffs of the ragged-corpus calls (one int64 entry per load), and d_need
+ *             of ulcx_corpus_ragged_dev
  *             sample positions: d_start of the sample-crop calls (one int64 entry per load)
  *    4 bytes  d_pcm of the sample-crop calls (ulcx_decode_crops_samples_*: a channel's plane starts at any sample; the kernels
- *             store two samples at once only where the address is a multiple of 8), and their d_len
- *    2 bytes  d_pcm16 of the sample-crop calls (likewise; two samples at once only at a multiple of 4)
+ *             store two samples at once only where the address is a multiple of 8), and their d_len;
+ *             d_pcm and d_len of the clip calls (ulcx_encode_clips_*: likewise, two samples per load only at a multiple of 8)
+ *    2 bytes  d_pcm16 of the sample-crop calls (likewise; two samples at once only at a multiple of 4) and of the clip calls
  *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_file, d_count, d_index (an entry is two
  *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n])
  *    none     the byte streams: d_out, d_in, d_payload and the d_slots of ulcx_pack_streams_dev and ulcx_index_slots_dev
@@ -154,13 +156,18 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  *             the {-1, 0} ones behind the closing entry included
  *   d_out     bytes [0, d_bits / 8) of each slot are the block; the rest of the slot is NOT defined (today it keeps what the
  *             buffer held; no caller may rely on that): read a slot through its d_bits
- *   d_payload bytes [0, d_payloadBytes[s]) of stream s; the rest of payloadStride is not defined (not written)
+ *   d_payload bytes [0, d_payloadBytes[s]) of stream s; the rest of payloadStride is not defined (not written).  The clip calls:
+ *             the same per row, and all indexStride entries of every row of d_index.  ulcx_corpus_ragged_dev: bytes
+ *             [0, d_payloadOffs[nFiles]) of d_outPayload and entries [0, d_indexOffs[nFiles]) of d_outIndex; both offset tables,
+ *             d_outIndexBlocks and d_need in full; nothing behind payloadCap bytes / indexCap entries
  *   A NULL d_wc / d_cplx / d_maxBlock changes nothing else the call writes.
  *
  * ORDER.  Every call is enqueued on hipStream and returns without waiting for the device.  The private side streams it uses
  * have been joined back into hipStream by then, for reads of the inputs as for writes of the outputs: work enqueued on
  * hipStream after the call returns - a copy of the outputs, an overwrite of d_pcm with the next blocks - is ordered behind
- * all of it, with no event or synchronisation of the caller's.  Another stream needs an event recorded on hipStream. */
+ * all of it, with no event or synchronisation of the caller's.  Another stream needs an event recorded on hipStream.
+ * A clip call's corpus (d_payload, d_payloadBytes, d_index, d_indexBlocks) may be handed to a crop call enqueued on hipStream
+ * the moment the clip call returns; so may the tables of ulcx_corpus_ragged_dev. */
 
 const char *ulcx_last_error(void);
 int  ulcx_device_count(void);                 /* <= 0 when no usable device */
@@ -690,6 +697,73 @@ int  ulcx_index_check(const ulcx_index_entry *row, int nBlocks, int indexStride,
  * h_index [nStreams][indexStride], h_nBlocks [nStreams].  Every row must pass ulcx_index_check against its stream's uploaded
  * payload size (ULCX_ERR_ARG otherwise: the decoder is as it was, an index it had included).  A new upload drops the index. */
 int  ulcx_decoder_set_resident_index(ulcx_decoder *dec, const ulcx_index_entry *h_index, int indexStride, const int32_t *h_nBlocks);
+
+/* Clips: the encode mirror of the sample-crop calls.  Row i of the call is a whole clip in samples, channels-first, at its own
+ * length, encoded from a fresh state; the call's output is a resident corpus - payloads, byte counts, block index, block counts -
+ * that ulcx_decode_crops_* and ulcx_decode_crops_samples_* read the moment the call returns on the stream.
+ *   n        rows, 1 .. nStreams of the encoder;  nSamples >= 1: samples per plane of d_pcm, any value
+ *   d_pcm    [n][nChan][nSamples] binary32 (d_pcm16: int16, converted on load as ulcx_encode_dev_pcm16 converts); row i is the clip
+ *            d_pcm[i][ch][0 .. L_i), L_i = d_len[i] clamped to [0, nSamples], d_len NULL: nSamples
+ *   mode / param0 / param1, or d_rate [n] in the tool's convention: exactly as ulcx_encode_dev_subset takes them
+ *   dec      supplies geometry and tables for the index, as for ulcx_index_slots_dev (same device, nChan and BlockSize as enc;
+ *            its nStreams and maxBlocksPerCall do not matter)
+ * A row with L_i >= 1 gets nb_i = ulcx_clip_blocks(BlockSize, L_i) blocks: what ULC_EncodeBlock_* of a freshly created encoder
+ * writes under the row's setting for the clip, interleaved, then zeros - the blocks of the `.ulc` file the tool writes for that
+ * clip alone (tools/ulcEncodeTool.c:93-98,133-169).  d_payload[i * payloadStride ..] holds them back to back, d_payloadBytes[i]
+ * their length, d_maxBlock[i] (optional) the largest block.  Row i of d_index ([n][indexStride]) and d_indexBlocks[i] are, entry
+ * for entry, what ulcx_index_packed_rows_dev builds from that payload with maxBlocks = indexStride - 1, the {-1, 0} entries
+ * behind the closing one included.  A row with L_i == 0 is empty: 0 bytes, 0 blocks, the open index row.
+ * CAPACITY.  A row keeps its leading whole blocks that fit payloadStride and indexStride - 1 and stops growing there (the rule of
+ * ulcx_index_slots_dev for a stream that stops); d_indexBlocks[i] < ulcx_clip_blocks(BlockSize, L_i) tells a truncated row.
+ * payloadStride >= ulcx_encoder_slot_bytes * ulcx_clip_blocks(BlockSize, nSamples) always suffices.
+ * STATE.  The call reads and changes no slot of enc and no stream state of dec: it runs the plain call's launch sequence on the
+ * subset calls' shadow state, reset to the state right after create, and scatters nothing back.  It mixes freely with streaming,
+ * subset, ladder and analysis calls on the object; a refused call leaves everything as it was.  The staging of the call (one chunk
+ * of interleaved input, slots and sizes) is the object's, allocated on the first clips call; nothing is allocated afterwards.
+ * ORDER.  Everything is enqueued on hipStream and nothing waits for the device: ceil(ulcx_clip_blocks(BlockSize, nSamples) /
+ * maxBlocksPerCall) chunks of (stage, the launch sequence, append, index).  Rows that have ended go on encoding silence that is
+ * masked; the encoder is causal in its input, so the chunking changes no byte.
+ * The _dev forms refuse with ULCX_ERR_ARG before any device work: a NULL required pointer, a misaligned one (d_pcm 4 bytes,
+ * d_pcm16 2, d_rate 8, everything else 4, the payload none), nSamples < 1, indexStride < 2, payloadStride < 1, a bad scalar mode
+ * without a table, n outside 1 .. nStreams, a decoder of another geometry or device.  The host form is synchronous; it knows the
+ * lengths, refuses a negative h_len entry and a bad rate entry too, and stops at the longest row's last chunk. */
+int  ulcx_clip_blocks(int BlockSize, int nSamples);   /* (nSamples + BlockSize - 1) / BlockSize + 2 for nSamples >= 1; 0 for nSamples <= 0 or a bad BlockSize; host arithmetic */
+int  ulcx_encode_clips_dev(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mode, float param0, float param1, const ulcx_rate *d_rate /* [n] or NULL */,
+                           const float *d_pcm /* [n][nChan][nSamples] */, const int32_t *d_len /* [n] or NULL */, int nSamples,
+                           uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes /* [n] */, int32_t *d_maxBlock /* [n], optional */,
+                           ulcx_index_entry *d_index /* [n][indexStride] */, int indexStride, int32_t *d_indexBlocks /* [n] */, void *hipStream);
+int  ulcx_encode_clips_dev_pcm16(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mode, float param0, float param1, const ulcx_rate *d_rate,
+                                 const int16_t *d_pcm16, const int32_t *d_len, int nSamples,
+                                 uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock,
+                                 ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream);
+int  ulcx_encode_clips_host(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mode, float param0, float param1, const ulcx_rate *h_rate,
+                            const float *h_pcm, const int32_t *h_len, int nSamples,
+                            uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes, int32_t *h_maxBlock,
+                            ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks);   /* synchronous */
+
+/* Strided corpus -> ragged corpus on the device: the layout ulcx_decode_crops_ragged_* and ulcx_decode_crops_samples_ragged_* read,
+ * from the strided one (a clip call's output, or any corpus held for ulcx_decode_crops_dev).  No object: `device` is the HIP ordinal.
+ * File f contributes clamp(d_payloadBytes[f], 0, payloadStride) bytes and clamp(d_indexBlocks[f], 0, indexStride - 1) + 1 entries
+ * (its row up to and including the closing entry); d_payloadOffs / d_indexOffs [nFiles + 1] are the exclusive int64 prefix sums,
+ * d_outIndexBlocks [nFiles] the clamped counts.  The files are laid out in order while both running totals stay within payloadCap
+ * bytes and indexCap entries: the capacities of d_outPayload and d_outIndex.  The ragged crop calls read nothing outside
+ * [d_payload, d_payload + payloadTotal) and so ask for no slack behind the last payload: payloadCap needs none either (a
+ * caller who wants the 64 bytes corpus.py leaves passes a cap that much below its buffer).  The first file that does not fit,
+ * and every file behind it, gets an empty range in both tables and 0 blocks - the crop calls give rows of zeros for it.
+ * d_need [2] always receives the bytes and the entries the WHOLE corpus needs, so that a caller can allocate and call again.
+ * payloadTotal / indexTotal for the crop calls: the capacities, or d_payloadOffs[nFiles] / d_indexOffs[nFiles].
+ * Asynchronous on hipStream (two kernels); ULCX_ERR_ARG before any device work for nFiles < 1, a stride below 1, a negative
+ * capacity, a NULL or misaligned pointer (offset tables and d_need 8 bytes, counts and index 4, payloads none). */
+int  ulcx_corpus_ragged_dev(int device, int nFiles,
+                            const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes, const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                            uint8_t *d_outPayload, long long payloadCap, int64_t *d_payloadOffs /* [nFiles+1] */,
+                            ulcx_index_entry *d_outIndex, long long indexCap, int64_t *d_indexOffs /* [nFiles+1] */, int32_t *d_outIndexBlocks /* [nFiles] */,
+                            int64_t *d_need /* [2]: bytes and entries the whole corpus needs */, void *hipStream);
+int  ulcx_corpus_ragged_host(int device, int nFiles,
+                             const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes, const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                             uint8_t *h_outPayload, long long payloadCap, int64_t *h_payloadOffs,
+                             ulcx_index_entry *h_outIndex, long long indexCap, int64_t *h_indexOffs, int32_t *h_outIndexBlocks,
+                             int64_t *h_need);   /* synchronous */
 
 /* `.ulx` sidecar: the block index of ONE `.ulc` file, written beside it (stem.ulx).  16-byte little-endian header, then
  * nBlocks + 1 entries of 8 bytes (ByteOffs, RngState; offsets relative to the .ulc file's StreamOffs).  The `.ulc` container

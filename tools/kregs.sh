@@ -3,7 +3,7 @@
 # usage: tools/kregs.sh [build dir] [pattern]
 DIR=${1:-ulc-codec_amd/build}; PAT=${2:-.}
 T=$(mktemp -d); trap 'rm -rf $T' EXIT
-for o in $DIR/ulcx_enc_wc.o $DIR/ulcx_enc_xf.o $DIR/ulcx_enc_xfa.o $DIR/ulcx_enc_psy.o $DIR/ulcx_enc_wr.o $DIR/ulcx_enc_ladder.o $DIR/ulcx_dec.o; do
+for o in $DIR/ulcx_enc_wc.o $DIR/ulcx_enc_xf.o $DIR/ulcx_enc_xfa.o $DIR/ulcx_enc_psy.o $DIR/ulcx_enc_wr.o $DIR/ulcx_enc_ladder.o $DIR/ulcx_dec.o $DIR/ulcx_slots.o $DIR/ulcx_clips.o; do
   [ -f $o ] || continue
   objcopy -O binary --only-section=.hip_fatbin $o $T/fat.bin
   /opt/rocm/lib/llvm/bin/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/fat.bin --output=$T/dev.co --unbundle 2>/dev/null || continue

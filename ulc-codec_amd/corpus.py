@@ -57,7 +57,68 @@ class CropCorpus:
         self.frozen = False
 
     def __len__(self):
-        return len(self._payloads)
+        return self.n_files if self.frozen else len(self._payloads)
+
+    @classmethod
+    def from_clips(cls, enc, dec, wave, lengths=None, rate=(ulc_amd.MODE_VBR, 50.0), layout="strided", payload_stride=None):
+        """A frozen corpus straight from waveforms on the device (ulcx_encode_clips_dev): wave is a torch tensor [n][C][T], float32
+        or int16, row i the clip wave[i, :, :lengths[i]] (lengths: int32 [n] on the device or anything torch.as_tensor takes; None:
+        every row T samples), each encoded from a fresh state.  rate: (mode, p0[, p1]) for every row, or a float32 [n][2] table
+        {RateKbps, AvgComplexity} in the tool's convention.  enc: a BatchEncoder with n_streams >= n (none of its slots is read or
+        changed); dec: a BatchDecoder of the same geometry.  Everything is enqueued on torch's current stream and the corpus adopts
+        the tensors the call wrote: no host trip and no freeze().  payload_stride: bytes per file of the strided layout (default:
+        what always suffices, slot bytes x blocks of T samples; a row that does not fit keeps its leading blocks).
+        layout="ragged" runs ulcx_corpus_ragged_dev behind it; sizing the ragged buffers takes ONE 16-byte read of the totals."""
+        import torch
+        n, ch, T = wave.shape
+        if (ch, enc.BS) != (dec.C, dec.BS) or ch != enc.C:
+            raise UlcError(f"corpus: clips of {ch} channels, an encoder of {enc.BS} x {enc.C}, a decoder of {dec.BS} x {dec.C}")
+        c = cls(ch, enc.BS, layout)
+        dev = wave.device
+        pcm16 = wave.dtype == torch.int16
+        wave = wave.contiguous() if pcm16 else wave.to(torch.float32).contiguous()
+        want = None if lengths is None else torch.as_tensor(lengths, dtype=torch.int32, device=dev).contiguous()
+        table = None
+        mode, p0, p1 = ulc_amd.MODE_VBR, 50.0, 0.0
+        if isinstance(rate, tuple):
+            mode, p0, p1 = int(rate[0]), float(rate[1]), float(rate[2]) if len(rate) > 2 else 0.0
+        else:
+            table = torch.as_tensor(rate, dtype=torch.float32, device=dev).contiguous()
+            assert tuple(table.shape) == (n, 2)
+        nb = ulc_amd.clip_blocks(enc.BS, T)
+        stride = int(payload_stride or enc.slot * nb)
+        index_stride = nb + 1
+        payload = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+        nbytes = torch.empty(n, dtype=torch.int32, device=dev)
+        index = torch.empty((n, index_stride, 2), dtype=torch.int32, device=dev)
+        blocks = torch.empty(n, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            enc.encode_clips_dev(dec, n, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, payload.data_ptr(), stride, nbytes.data_ptr(),
+                                 index.data_ptr(), index_stride, blocks.data_ptr(), mode=mode, p0=p0, p1=p1,
+                                 d_rates=table.data_ptr() if table is not None else 0, stream=stream, pcm16=pcm16)
+            c.n_files, c.device = n, dev
+            if not c.ragged:
+                c.stride, c.index_stride = stride, index_stride
+                c.d_payload, c.d_payload_bytes, c.d_index, c.d_index_blocks = payload, nbytes, index, blocks
+            else:
+                poffs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+                ioffs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+                oblocks = torch.empty(n, dtype=torch.int32, device=dev)
+                need = torch.empty(2, dtype=torch.int64, device=dev)
+                none = torch.empty(16, dtype=torch.uint8, device=dev)
+                args = (n, payload.data_ptr(), stride, nbytes.data_ptr(), index.data_ptr(), index_stride, blocks.data_ptr())
+                ulc_amd.corpus_ragged_dev(*args, none.data_ptr(), 0, poffs.data_ptr(), none.data_ptr(), 0, ioffs.data_ptr(), oblocks.data_ptr(),
+                                          need.data_ptr(), stream=stream, device=dev.index or 0)
+                nbytes_all, nent_all = (int(v) for v in need.cpu())
+                opay = torch.empty(nbytes_all + PAYLOAD_PAD, dtype=torch.uint8, device=dev)
+                oidx = torch.empty((max(1, nent_all), 2), dtype=torch.int32, device=dev)
+                ulc_amd.corpus_ragged_dev(*args, opay.data_ptr(), nbytes_all, poffs.data_ptr(), oidx.data_ptr(), nent_all, ioffs.data_ptr(), oblocks.data_ptr(),
+                                          need.data_ptr(), stream=stream, device=dev.index or 0)
+                c.d_payload, c.d_payload_offs, c.d_index, c.d_index_offs, c.d_index_blocks = opay, poffs, oidx, ioffs, oblocks
+                # (the strided tensors go back to torch's allocator, which hands them out again on this stream only: behind the copy)
+        c.frozen = True
+        return c
 
     def add_file(self, ulc_bytes, ulx_bytes=None):
         """-> the file's number.  Refuses (UlcError) another geometry than the corpus's, and a `.ulx` that is not this payload's:

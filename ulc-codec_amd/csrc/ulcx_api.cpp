@@ -84,6 +84,8 @@ struct ulcx_encoder {
     float *pinIn = nullptr; uint8_t *pinOut = nullptr; Block1Meta *pinMeta = nullptr;
     // stream slots: the compact shadow state of the subset calls ([B], allocated on the first one) and the device copy of a host form's list
     float *subHist = nullptr; UlcxWcState *subWcs = nullptr; int32_t *subSlots = nullptr;
+    // clips (ulcx_encode_clips_*): one chunk of the call - [B][maxK] interleaved blocks, slots and sizes (allocated on the first clips call)
+    float *clipPcm = nullptr; uint8_t *clipOut = nullptr; int32_t *clipBits = nullptr;
 };
 struct ulcx_decoder {
     int device = 0, B = 0, C = 0, BS = 0, maxK = 0;
@@ -720,6 +722,188 @@ extern "C" int ulcx_encode_host_ladder(ulcx_encoder *e, const ulcx_rung *rungs, 
     if ((rc = enc_pcm_up(e, h_pcm, NB))) return rc;
     rc = encode_ladder_any(who, e, dev, nRungs, e->d_pcm, nullptr, nBlocks, e->ladOut, e->ladBits, e->d_wc, e->d_cplx, nullptr);
     return rc ? rc : enc_results_down(e, e->ladOut, e->ladBits, (size_t)nRungs * NB, NB, h_out, h_bits, h_wc, h_cplx);
+}
+
+// ---- clips (include/ulc_amd.h section 3): rows are whole clips in samples, channels-first; the output is a resident corpus.
+// Per chunk of maxBlocksPerCall blocks: k_clip_stage into the object's staging, the plain call's launch sequence with c.B = n on
+// the shadow state (reset in front of the first chunk, never scattered back) into the object's slots and sizes, k_clip_append,
+// then the two kernels of ulcx_index_slots_dev on the masked sizes.  Everything on the caller's stream.
+extern "C" int ulcx_clip_blocks(int BlockSize, int nSamples) {
+    if (!validate(1, BlockSize) || nSamples < 1) return 0;
+    return (int)(((long long)nSamples + BlockSize - 1) / BlockSize) + 2;          // cli/ulcx_tool.c:196 = ulcEncodeTool.c:93-98
+}
+// the checks every clips entry makes, device or host pointers: the arguments, then (behind the device forms' alignment checks)
+// the objects - every other refusal needs none
+static int clips_args_bad(const char *who, int n, int mode, const void *rate, const void *pcm, int nSamples,
+                          const void *payload, long long payloadStride, const void *payloadBytes, const void *index, int indexStride, const void *indexBlocks) {
+    if (!pcm || !payload || !payloadBytes || !index || !indexBlocks) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
+    if (nSamples < 1) { refuse(who, "bad argument (nSamples %d)", nSamples); return 1; }
+    if (indexStride < 2 || payloadStride < 1) { refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride); return 1; }
+    if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
+    if (!rate && !mode_ok(mode)) { refuse(who, "bad mode"); return 1; }
+    return 0;
+}
+static int clips_objects_bad(const char *who, const ulcx_encoder *e, const ulcx_decoder *dec, int n) {
+    if (!e) { refuse(who, "no encoder"); return 1; }
+    if (!dec) { refuse(who, "no decoder"); return 1; }
+    if (n > e->B) { refuse(who, "bad argument (n %d: a call takes 1 .. nStreams = %d rows)", n, e->B); return 1; }
+    if (dec->C != e->C || dec->BS != e->BS || dec->device != e->device) {
+        refuse(who, "the decoder (%d x %d on device %d) is not of the encoder's geometry and device (%d x %d on %d)", dec->BS, dec->C, dec->device, e->BS, e->C, e->device);
+        return 1;
+    }
+    return 0;
+}
+static int clips_staging(ulcx_encoder *e) {
+    const size_t nBlk = (size_t)e->B * e->maxK;
+    int rc = enc_shadow(e);
+    if (!rc && !e->clipPcm) rc = dalloc(e->allocs, &e->clipPcm, nBlk * (size_t)e->C * e->BS, false);
+    if (!rc && !e->clipOut) rc = dalloc(e->allocs, &e->clipOut, nBlk * e->ctx.slot, false);
+    if (!rc && !e->clipBits) rc = dalloc(e->allocs, &e->clipBits, nBlk, false);
+    return rc;
+}
+// chunkSamples: the longest row as far as the caller knows it (the _dev forms: nSamples) - the chunks stop behind its last block
+static int encode_clips_any(const char *who, ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
+                            const float *d_pcm, const int16_t *d_pcm16, const int32_t *d_len, int nSamples, int chunkSamples,
+                            uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock,
+                            ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream) {
+    if (clips_args_bad(who, n, mode, d_rate, d_pcm ? (const void *)d_pcm : d_pcm16, nSamples, d_payload, payloadStride, d_payloadBytes,
+                       d_index, indexStride, d_indexBlocks)) return ULCX_ERR_ARG;
+    // (a plane starts at any sample: the staging kernel uses wider loads only where the address allows them)
+    if (misaligned(who, "d_pcm", d_pcm, (int)sizeof(float)) || misaligned(who, "d_pcm16", d_pcm16, (int)sizeof(int16_t)) ||
+        misaligned(who, "d_rate", d_rate, ULCX_ALIGN_RATE) || misaligned(who, "d_len", d_len, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_maxBlock", d_maxBlock, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) || misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    if (clips_objects_bad(who, e, dec, n)) return ULCX_ERR_ARG;
+    if ((long long)n * indexStride > (0x7FFFFFFFLL << 8)) return refuse(who, "%d rows of %d entries are more than one call takes", n, indexStride);
+    CKR(hipSetDevice(e->device));
+    int rc = clips_staging(e);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)hipStream;
+    if ((rc = ulcx_clips_begin_launch(e->subHist, e->subWcs, n, e->C, e->BS, d_payloadBytes, d_maxBlock, st))) return rc;
+    if ((rc = ulcx_index_begin_launch(n, d_index, indexStride, d_indexBlocks, st))) return rc;
+    const int total = ulcx_clip_blocks(e->BS, chunkSamples);
+    int K = 0;
+    for (int k0 = 0; k0 < total && rc == ULCX_OK; k0 += K) {
+        K = total - k0 < e->maxK ? total - k0 : e->maxK;
+        if ((rc = ulcx_clips_stage_launch(d_pcm, d_pcm16, d_len, nSamples, n, e->C, e->BS, k0, K, e->clipPcm, st))) break;
+        UlcxEncCtx c = enc_call_ctx(e, mode, p0, p1, d_rate, e->clipPcm, nullptr, K);
+        c.out = e->clipOut; c.bits = e->clipBits;
+        c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
+        if ((rc = ulcx_enc_launch(c, st, e->timing ? e->ev : nullptr, enc_aux(e, K)))) break;
+        if ((rc = ulcx_clips_append_launch(n, K, k0, e->BS, nSamples, d_len, c.slot, e->clipOut, e->clipBits, d_payload, payloadStride, d_payloadBytes, d_maxBlock,
+                                           indexStride, d_indexBlocks, st))) break;
+        UlcxDecCtx dc = dec->ctx;
+        dc.in = e->clipOut; dc.slot = c.slot; dc.inBytes = (long long)n * K * c.slot;
+        rc = ulcx_index_slots_launch(dc, n, K, e->clipBits, d_index, indexStride, d_indexBlocks, st);
+    }
+    return K ? enc_call_done(e, rc, K, false, 1) : rc;
+}
+extern "C" int ulcx_encode_clips_dev(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
+                                     const float *d_pcm, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
+                                     int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream) {
+    return encode_clips_any("ulcx_encode_clips_dev", e, dec, n, mode, p0, p1, d_rate, d_pcm, nullptr, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream);
+}
+extern "C" int ulcx_encode_clips_dev_pcm16(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
+                                           const int16_t *d_pcm16, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
+                                           int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream) {
+    return encode_clips_any("ulcx_encode_clips_dev_pcm16", e, dec, n, mode, p0, p1, d_rate, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream);
+}
+// The host form: every check first, then everything up into buffers of the call's own, the body on the null stream with the
+// longest row's length, one synchronisation, and down: counts, index, and of every payload the bytes that are defined.
+extern "C" int ulcx_encode_clips_host(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
+                                      const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
+                                      int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks) {
+    const char *who = "ulcx_encode_clips_host";
+    if (clips_args_bad(who, n, mode, h_rate, h_pcm, nSamples, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks) ||
+        clips_objects_bad(who, e, dec, n)) return ULCX_ERR_ARG;
+    int longest = h_len ? 0 : nSamples;
+    for (int i = 0; h_len && i < n; i++) {
+        if (h_len[i] < 0) return refuse(who, "row %d has %d samples", i, (int)h_len[i]);
+        const int l = h_len[i] > nSamples ? nSamples : h_len[i];
+        if (l > longest) longest = l;
+    }
+    if (h_rate && rate_table_bad(who, "invalid entry for row", h_rate, n)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    const size_t nPcm = (size_t)n * e->C * (size_t)nSamples, nEnt = (size_t)n * (size_t)indexStride;
+    DevTmp t; float *dpcm = nullptr; int32_t *dlen = nullptr, *dbytes = nullptr, *dmax = nullptr, *dcnt = nullptr; ulcx_rate *drate = nullptr;
+    uint8_t *dpay = nullptr; ulcx_index_entry *di = nullptr;
+    CKR(t.get(&dpcm, sizeof(float) * nPcm)); CKR(t.get(&dpay, (size_t)n * (size_t)payloadStride));
+    CKR(t.get(&dbytes, sizeof(int32_t) * n)); CKR(t.get(&dmax, sizeof(int32_t) * n)); CKR(t.get(&dcnt, sizeof(int32_t) * n));
+    CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    CKR(hipMemcpy(dpcm, h_pcm, sizeof(float) * nPcm, hipMemcpyHostToDevice));
+    if (h_len) { CKR(t.get(&dlen, sizeof(int32_t) * n)); CKR(hipMemcpy(dlen, h_len, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
+    if (h_rate) { CKR(t.get(&drate, sizeof(ulcx_rate) * n)); CKR(hipMemcpy(drate, h_rate, sizeof(ulcx_rate) * n, hipMemcpyHostToDevice)); }
+    const int rc = encode_clips_any(who, e, dec, n, mode, p0, p1, drate, dpcm, nullptr, dlen, nSamples, longest, dpay, payloadStride, dbytes, dmax, di, indexStride, dcnt, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_payloadBytes, dbytes, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    if (h_maxBlock) CKR(hipMemcpy(h_maxBlock, dmax, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_indexBlocks, dcnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * nEnt, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++)
+        if (h_payloadBytes[i] > 0) CKR(hipMemcpy(h_payload + (size_t)i * (size_t)payloadStride, dpay + (size_t)i * (size_t)payloadStride, (size_t)h_payloadBytes[i], hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+
+// ---- strided corpus -> ragged corpus (include/ulc_amd.h section 3): no object; two kernels of ulcx_clips.hip
+static int corpus_ragged_bad(const char *who, int nFiles, const void *payload, long long payloadStride, const void *payloadBytes, const void *index, int indexStride,
+                             const void *indexBlocks, const void *outPayload, long long payloadCap, const void *payloadOffs, const void *outIndex, long long indexCap,
+                             const void *indexOffs, const void *outIndexBlocks, const void *need) {
+    if (!payload || !payloadBytes || !index || !indexBlocks || !outPayload || !payloadOffs || !outIndex || !indexOffs || !outIndexBlocks || !need) {
+        refuse(who, "bad argument (a NULL pointer)"); return 1;
+    }
+    if (nFiles < 1) { refuse(who, "bad argument (nFiles %d)", nFiles); return 1; }
+    if (payloadStride < 1 || indexStride < 1) { refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride); return 1; }
+    if (payloadCap < 0 || indexCap < 0) { refuse(who, "bad argument (payloadCap %lld, indexCap %lld)", payloadCap, indexCap); return 1; }
+    return 0;
+}
+extern "C" int ulcx_corpus_ragged_dev(int device, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                      const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                      uint8_t *d_outPayload, long long payloadCap, int64_t *d_payloadOffs, ulcx_index_entry *d_outIndex, long long indexCap,
+                                      int64_t *d_indexOffs, int32_t *d_outIndexBlocks, int64_t *d_need, void *hipStream) {
+    const char *who = "ulcx_corpus_ragged_dev";
+    if (corpus_ragged_bad(who, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_outPayload, payloadCap, d_payloadOffs,
+                          d_outIndex, indexCap, d_indexOffs, d_outIndexBlocks, d_need)) return ULCX_ERR_ARG;
+    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_payloadOffs", d_payloadOffs, ULCX_ALIGN_OFFS) ||
+        misaligned(who, "d_outIndex", d_outIndex, ULCX_ALIGN_WORD) || misaligned(who, "d_indexOffs", d_indexOffs, ULCX_ALIGN_OFFS) ||
+        misaligned(who, "d_outIndexBlocks", d_outIndexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_need", d_need, ULCX_ALIGN_OFFS)) return ULCX_ERR_ARG;
+    const int rc = select_device(who, device);
+    if (rc) return rc;
+    return ulcx_corpus_ragged_launch(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, d_outPayload, payloadCap, d_payloadOffs,
+                                     d_outIndex, indexCap, d_indexOffs, d_outIndexBlocks, d_need, (hipStream_t)hipStream);
+}
+extern "C" int ulcx_corpus_ragged_host(int device, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                       const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                       uint8_t *h_outPayload, long long payloadCap, int64_t *h_payloadOffs, ulcx_index_entry *h_outIndex, long long indexCap,
+                                       int64_t *h_indexOffs, int32_t *h_outIndexBlocks, int64_t *h_need) {
+    const char *who = "ulcx_corpus_ragged_host";
+    if (corpus_ragged_bad(who, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, h_outPayload, payloadCap, h_payloadOffs,
+                          h_outIndex, indexCap, h_indexOffs, h_outIndexBlocks, h_need)) return ULCX_ERR_ARG;
+    int rc = select_device(who, device);
+    if (rc) return rc;
+    const size_t F = (size_t)nFiles, nEnt = F * (size_t)indexStride;
+    DevTmp t; uint8_t *dp = nullptr, *dop = nullptr; int32_t *dn = nullptr, *dcnt = nullptr, *docnt = nullptr; ulcx_index_entry *di = nullptr, *doi = nullptr;
+    int64_t *dpo = nullptr, *dio = nullptr, *dneed = nullptr;
+    CKR(t.get(&dp, F * (size_t)payloadStride)); CKR(t.get(&dn, sizeof(int32_t) * F)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    CKR(t.get(&dcnt, sizeof(int32_t) * F)); CKR(t.get(&dop, (size_t)payloadCap)); CKR(t.get(&doi, sizeof(ulcx_index_entry) * (size_t)indexCap));
+    CKR(t.get(&dpo, sizeof(int64_t) * (F + 1))); CKR(t.get(&dio, sizeof(int64_t) * (F + 1))); CKR(t.get(&docnt, sizeof(int32_t) * F)); CKR(t.get(&dneed, sizeof(int64_t) * 2));
+    CKR(hipMemcpy(dp, h_payload, F * (size_t)payloadStride, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dn, h_payloadBytes, sizeof(int32_t) * F, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * F, hipMemcpyHostToDevice));
+    rc = ulcx_corpus_ragged_dev(device, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, dop, payloadCap, dpo, doi, indexCap, dio, docnt, dneed, nullptr);
+    if (rc) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_payloadOffs, dpo, sizeof(int64_t) * (F + 1), hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_indexOffs, dio, sizeof(int64_t) * (F + 1), hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_outIndexBlocks, docnt, sizeof(int32_t) * F, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_need, dneed, sizeof(int64_t) * 2, hipMemcpyDeviceToHost));
+    if (h_payloadOffs[F] > 0) CKR(hipMemcpy(h_outPayload, dop, (size_t)h_payloadOffs[F], hipMemcpyDeviceToHost));
+    if (h_indexOffs[F] > 0) CKR(hipMemcpy(h_outIndex, doi, sizeof(ulcx_index_entry) * (size_t)h_indexOffs[F], hipMemcpyDeviceToHost));
+    return ULCX_OK;
 }
 
 // One block of one stream per call (the drop-in ABI): include/ulc_amd.h.  The launch sequence of ulcx_encode_dev - side

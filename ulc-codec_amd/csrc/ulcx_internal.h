@@ -246,6 +246,19 @@ size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds);
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
+// clips (ulcx_clips.hip): the kernels around the launch sequence of ulcx_encode_clips_* - the shadow state of n rows to the state
+// right after create and the caller's byte counts to 0; planar samples of blocks [k0, k0 + K) of every row into the interleaved
+// staging chunk (exactly one of d_pcm / d_pcm16); the chunk's sizes masked and its kept slots appended to the payloads
+int ulcx_clips_begin_launch(float *hist, UlcxWcState *wcs, int n, int C, int BS, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
+int ulcx_clips_stage_launch(const float *d_pcm, const int16_t *d_pcm16, const int32_t *d_len, int nSamples, int n, int C, int BS, int k0, int K,
+                            float *stage, hipStream_t st);
+int ulcx_clips_append_launch(int n, int K, int k0, int BS, int nSamples, const int32_t *d_len, int slot, const uint8_t *slots, int32_t *bits,
+                             uint8_t *d_payload, long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, int indexStride, const int32_t *d_indexBlocks,
+                             hipStream_t st);
+// strided corpus -> ragged corpus (ulcx_clips.hip): the offsets, then a file per workgroup
+int ulcx_corpus_ragged_launch(int nFiles, const uint8_t *d_payload, long long stride, const int32_t *d_payloadBytes, const ulcx_index_entry *d_index,
+                              int indexStride, const int32_t *d_indexBlocks, uint8_t *d_outPayload, long long payloadCap, int64_t *d_payloadOffs,
+                              ulcx_index_entry *d_outIndex, long long indexCap, int64_t *d_indexOffs, int32_t *d_outIndexBlocks, int64_t *d_need, hipStream_t st);
 int ulcx_analyse_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux, int useKxf);   // ulcx_analyse_dev; useKxf: the encode call's transform instead of the MDCT-only one (timing comparisons)
 int ulcx_enc_nsums_slots(int BS, int C);                 // resident workgroups of k_nsums on the current device
 // FFT array padding of k_xf (ulcx_fft.h).  One complex per 8 makes every pass conflict-free but costs 2 KB of LDS at

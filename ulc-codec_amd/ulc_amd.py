@@ -42,6 +42,8 @@ EXPORTS = [
     "ulcx_index_packed_ragged_dev", "ulcx_index_packed_ragged_host",
     "ulcx_crop_blocks", "ulcx_decode_crops_samples_dev", "ulcx_decode_crops_samples_dev_pcm16", "ulcx_decode_crops_samples_host",
     "ulcx_decode_crops_samples_ragged_dev", "ulcx_decode_crops_samples_ragged_dev_pcm16", "ulcx_decode_crops_samples_ragged_host",
+    "ulcx_clip_blocks", "ulcx_encode_clips_dev", "ulcx_encode_clips_dev_pcm16", "ulcx_encode_clips_host",
+    "ulcx_corpus_ragged_dev", "ulcx_corpus_ragged_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -198,6 +200,17 @@ def lib():
             l.ulcx_decode_crops_samples_ragged_dev_pcm16.argtypes = l.ulcx_decode_crops_samples_ragged_dev.argtypes
             l.ulcx_decode_crops_samples_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p,
                                                                 C.c_int, _i32p, _i64p, _i32p, C.c_int, _f32p, _i32p]
+        if hasattr(l, "ulcx_encode_clips_dev"):            # clips -> a resident corpus; strided -> ragged
+            l.ulcx_clip_blocks.argtypes = [C.c_int, C.c_int]
+            l.ulcx_encode_clips_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            l.ulcx_encode_clips_dev_pcm16.argtypes = l.ulcx_encode_clips_dev.argtypes
+            l.ulcx_encode_clips_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, _f32p, _f32p, _i32p, C.c_int,
+                                                 _u8p, C.c_longlong, _i32p, _i32p, C.c_void_p, C.c_int, _i32p]
+            l.ulcx_corpus_ragged_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_corpus_ragged_host.argtypes = [C.c_int, C.c_int, _u8p, C.c_longlong, _i32p, C.c_void_p, C.c_int, _i32p,
+                                                  _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p, _i64p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -238,6 +251,44 @@ def crop_blocks(block_size, n_samples):
     """Blocks a crop of n_samples samples touches at the worst start (ulcx_crop_blocks): a sample-crop call's d_bits row, and
     what max_blocks - 1 of its decoder must reach."""
     return int(lib().ulcx_crop_blocks(int(block_size), int(n_samples)))
+
+
+def clip_blocks(block_size, n_samples):
+    """Blocks of a clip of n_samples samples (ulcx_clip_blocks): what the reference tool writes for a file of that length,
+    (n_samples + block_size - 1) // block_size + 2; 0 for an empty clip or a bad block size."""
+    return int(lib().ulcx_clip_blocks(int(block_size), int(n_samples)))
+
+
+def corpus_ragged_dev(n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, d_out_payload, payload_cap, d_payload_offs,
+                      d_out_index, index_cap, d_index_offs, d_out_index_blocks, d_need, stream=0, device=0):
+    """ulcx_corpus_ragged_dev: a strided corpus on the device into the ragged layout (raw device pointers; asynchronous on
+    `stream`).  d_payload_offs / d_index_offs int64 [n_files + 1], d_out_index_blocks int32 [n_files], d_need int64 [2]: the bytes
+    and entries the whole corpus needs.  Files behind the first one that does not fit the capacities come out empty."""
+    _check(lib().ulcx_corpus_ragged_dev(int(device), int(n_files), d_payload, int(stride), d_payload_bytes, d_index, int(index_stride), d_index_blocks,
+                                        d_out_payload, int(payload_cap), d_payload_offs, d_out_index, int(index_cap), d_index_offs, d_out_index_blocks,
+                                        d_need, stream or None), "ulcx_corpus_ragged_dev")
+
+
+def corpus_ragged(payload, payload_bytes, index, index_blocks, payload_cap=None, index_cap=None, device=0):
+    """Host form (ulcx_corpus_ragged_host): payload uint8 [F][stride], payload_bytes [F], index [F][index_stride], index_blocks [F]
+    -> dict(payload uint8 [payload_cap], payload_offs int64 [F + 1], index [index_cap], index_offs int64 [F + 1], index_blocks [F],
+    need int64 [2]).  Without capacities: what the whole corpus needs (host arithmetic)."""
+    payload = np.ascontiguousarray(payload, dtype=np.uint8)
+    nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+    index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+    blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+    F, stride = payload.shape
+    assert nbytes.shape == (F,) and index.shape[0] == F and blocks.shape == (F,)
+    if payload_cap is None:
+        payload_cap = int(np.clip(nbytes.astype(np.int64), 0, stride).sum())
+    if index_cap is None:
+        index_cap = int((np.clip(blocks.astype(np.int64), 0, index.shape[1] - 1) + 1).sum())
+    r = dict(payload=np.zeros(max(1, payload_cap), np.uint8), payload_offs=np.zeros(F + 1, np.int64), index=np.zeros(max(1, index_cap), INDEX_DTYPE),
+             index_offs=np.zeros(F + 1, np.int64), index_blocks=np.zeros(F, np.int32), need=np.zeros(2, np.int64))
+    _check(lib().ulcx_corpus_ragged_host(int(device), F, _p(payload, _u8p), stride, _p(nbytes, _i32p), index.ctypes.data, index.shape[1], _p(blocks, _i32p),
+                                         _p(r["payload"], _u8p), int(payload_cap), _p(r["payload_offs"], _i64p), r["index"].ctypes.data, int(index_cap),
+                                         _p(r["index_offs"], _i64p), _p(r["index_blocks"], _i32p), _p(r["need"], _i64p)), "ulcx_corpus_ragged_host")
+    return r
 
 
 def build_rev():
@@ -482,6 +533,40 @@ class BatchEncoder(_StreamSlots):
         _check(fn(self.h, d_slots, n, mode, p0, p1, d_rates or None, d_pcm, n_blocks, d_out, d_bits, d_wc or None, d_cplx or None,
                   stream or None), "ulcx_encode_dev_pcm16_subset" if pcm16 else "ulcx_encode_dev_subset")
         self.lastK = n_blocks
+
+    def encode_clips_dev(self, dec, n, d_pcm, d_len, n_samples, d_payload, payload_stride, d_payload_bytes, d_index, index_stride, d_index_blocks,
+                         d_max_block=0, mode=MODE_VBR, p0=50.0, p1=0.0, d_rates=0, stream=0, pcm16=False):
+        """Clips into a resident corpus (ulcx_encode_clips_dev), asynchronous on `stream`: d_pcm [n][C][n_samples] (int16 with
+        pcm16), d_len int32 [n] or 0 (every row n_samples long), each row encoded from a fresh state under the scalar setting or
+        d_rates [n]; d_payload [n][payload_stride], d_payload_bytes [n], d_index [n][index_stride], d_index_blocks [n].  `dec`: a
+        BatchDecoder of this geometry (tables for the index).  No slot of the encoder is read or changed."""
+        fn = lib().ulcx_encode_clips_dev_pcm16 if pcm16 else lib().ulcx_encode_clips_dev
+        _check(fn(self.h, dec.h, n, mode, p0, p1, d_rates or None, d_pcm, d_len or None, n_samples, d_payload, payload_stride, d_payload_bytes,
+                  d_max_block or None, d_index, index_stride, d_index_blocks, stream or None),
+               "ulcx_encode_clips_dev_pcm16" if pcm16 else "ulcx_encode_clips_dev")
+
+    def encode_clips(self, dec, wave, lengths=None, mode=MODE_VBR, p0=50.0, p1=0.0, rates=None, payload_stride=None, index_stride=None):
+        """Host form (ulcx_encode_clips_host): wave float32 [n][C][T], lengths [n] or None, rates float32 [n][2] or None
+        -> (payload uint8 [n][payload_stride], payload_bytes [n], max_block [n], index [n][index_stride], index_blocks [n]).
+        The default strides hold every row in full."""
+        wave = np.ascontiguousarray(wave, dtype=np.float32)
+        n, ch, T = wave.shape
+        assert ch == self.C
+        want = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        assert want is None or want.shape == (n,)
+        if rates is not None:
+            rates = np.ascontiguousarray(rates, dtype=np.float32)
+            assert rates.shape == (n, 2)
+        nb = clip_blocks(self.BS, T)
+        payload_stride = payload_stride or self.slot * nb
+        index_stride = index_stride or nb + 1
+        payload = np.zeros((n, payload_stride), np.uint8)
+        nbytes, maxb, count = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        index = np.zeros((n, index_stride), INDEX_DTYPE)
+        _check(lib().ulcx_encode_clips_host(self.h, dec.h, n, mode, p0, p1, _p(rates, _f32p), _p(wave, _f32p), _p(want, _i32p), T, _p(payload, _u8p),
+                                            payload_stride, _p(nbytes, _i32p), _p(maxb, _i32p), index.ctypes.data, index_stride, _p(count, _i32p)),
+               "ulcx_encode_clips_host")
+        return payload, nbytes, maxb, index, count
 
     def analyse_subset_dev(self, d_slots, n, d_pcm, n_blocks, d_wc=0, d_cplx=0, stream=0):
         _check(lib().ulcx_analyse_dev_subset(self.h, d_slots, n, d_pcm, n_blocks, d_wc or None, d_cplx or None, stream or None),
