@@ -1,7 +1,9 @@
 """Clips and the strided -> ragged corpus call (include/ulc_amd.h section 3: ulcx_clip_blocks, ulcx_encode_clips_*,
 ulcx_corpus_ragged_*) at the C-ABI boundary, without a GPU: exported symbols and their prototypes, the block arithmetic against
 the tool's formula, every refusal that needs no device, and the numpy restatement of the ragged tables (clips_testlib.ragged_plan,
-which the GPU tests hold the kernels to) against a hand-written table of cases."""
+which the GPU tests hold the kernels to) against a hand-written table of cases, and the properties of clips_testlib's case tables
+that tests/test_gpu_clips_paths.py leans on (block counts against chunk boundaries, window-switched blocks behind the first
+chunk, rows whose rate search moves, capacities that cut where they say, every alignment pair of the byte copy)."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +14,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clips_testlib as ct
+
 LIB = os.path.join(ROOT, "ulc-codec_amd", "libulc_amd.so")
 NAMES = ("ulcx_clip_blocks", "ulcx_encode_clips_dev", "ulcx_encode_clips_dev_pcm16", "ulcx_encode_clips_host", "ulcx_corpus_ragged_dev", "ulcx_corpus_ragged_host")
 ERR_ARG = -1
@@ -180,3 +184,102 @@ def test_ragged_plan_restates_the_rule(case):
     got = ragged_plan(nbytes, stride, blocks, istride, pcap, icap)
     for g, w in zip(got, want):
         assert g.tolist() == w, (case, [x.tolist() for x in got])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# What tests/test_gpu_clips_paths.py leans on, from clips_testlib and the oracle alone: a GPU test there cannot pass because
+# its inputs miss the path it is named for.
+# ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("geom", ct.PATH_GEOMS, ids=lambda g: f"{g[0]}x{g[1]}")
+def test_path_rows_end_at_every_position_of_a_chunk(geom):
+    bs, ch, streams, maxk = geom
+    case, rows = ct.path_case(bs), ct.path_rows(bs, ch)
+    assert case.T == 20 * bs + 3 and ct.clip_blocks(bs, case.T) == 23
+    assert [ct.clip_blocks(bs, n) for n in case.lengths] == ct.PATH_BLOCKS == [0, 3, 8, 9, 16, 17, 23]
+    refs = ct.refs(bs, ch, case=case, rows=rows)
+    assert [r.nb for r in refs] == [ct.PATH_BLOCKS[i] for i in rows] and len(rows) <= streams
+    assert set(rows) >= {1, 3, 6}                           # inside the first chunk, one block into the second, the short last chunk
+    chunks = [min(maxk, 23 - k0) for k0 in range(0, 23, maxk)]
+    assert chunks == {8: [8, 8, 7], 6: [6, 6, 6, 5], 2: [2] * 11 + [1]}[maxk]
+    wave = ct.wave(bs, ch, case.T)
+    for i in rows:                                          # samples behind a row's length are not zero
+        assert case.lengths[i] == case.T or np.abs(wave[i][:, case.lengths[i]:]).max() > 0.01, i
+    if (bs, ch) == (16384, 1):
+        return
+    # decimated blocks go through k_pack, un-decimated ones through the direct packing: both behind the first chunk
+    wc = np.concatenate([r.wc[maxk:] for r in refs])
+    assert (wc != 0x10).any() and (wc == 0x10).any(), [hex(w) for w in wc]
+
+
+@pytest.mark.parametrize("geom", ct.PATH_GEOMS[:2], ids=lambda g: f"{g[0]}x{g[1]}")
+def test_path_table_rows_search_their_rate(geom):
+    bs, ch = geom[:2]
+    case = ct.path_case(bs)
+    vbr, tab = ct.refs(bs, ch, case=case), ct.refs(bs, ch, table=True, case=case)
+    searched = [i for i in range(7) if ct.TABLE[i][0] > 0 and tab[i].nb and not np.array_equal(tab[i].sizes, vbr[i].sizes)]
+    assert searched, "no CBR or ABR row differs from VBR 50"
+    assert any(not np.array_equal(tab[i].sizes[geom[3]:], vbr[i].sizes[geom[3]:]) for i in searched), "... behind the first chunk"
+
+
+def test_path_capacities_cut_inside_the_second_chunk():
+    bs, ch, _, maxk = ct.PATH_GEOMS[0]
+    refs = ct.refs(bs, ch, case=ct.path_case(bs))
+    pstride, istride = ct.path_cut_strides(refs)
+    nb = 23
+    whole = (refs[0].slot * nb, nb + 1)                     # the strides that hold every row in full
+    assert refs[6].kept(pstride, whole[1]) == 10 and maxk + 1 <= 10 < 2 * maxk < refs[6].nb
+    assert pstride == int(refs[6].sizes[:11].sum()) - 1
+    assert len([r for r in refs if r.kept(pstride, whole[1]) == r.nb]) >= 2            # rows that fit, to be unchanged
+    assert istride - 1 == 9 and [r.kept(whole[0], istride) for r in refs] == [0, 3, 8, 9, 9, 9, 9]
+
+
+def test_grid_rows():
+    bs, ch, streams, maxk = ct.GRID_GEOM
+    case = ct.grid_case(bs)
+    assert (bs, ch, maxk) == (256, 1, 2) and streams == 16384 + 5 and (streams - 1) // 16384 == 1
+    assert case.T == 2 * bs + 1 and case.lengths == (0, 1, bs - 1, bs, bs + 1, 2 * bs, case.T)
+    refs = ct.refs(bs, ch, case=case)
+    assert [r.nb for r in refs] == [0, 3, 3, 3, 4, 4, 5]
+    assert len({r.payload.tobytes() for r in refs}) == 7     # a row that got another row's clip is seen
+
+
+def test_ragged_tile_corpora_cut_where_they_say():
+    for F in ct.TILE_FILES:
+        c = ct.corpus_tiles(F)
+        assert c.pay.shape == (F, ct.TILE_STRIDE) and ct.TILE_STRIDE % 2 == 1 and c.index.shape == (F, 4)
+        assert c.nbytes.min() >= 0 and c.nbytes.max() <= ct.TILE_STRIDE and (F < 200 or (c.nbytes.min() == 0 and c.nbytes.max() == ct.TILE_STRIDE))
+        for what, pcap, icap, cut in ct.tile_caps(F):
+            assert ct.cut_file(c, pcap, icap) == cut, (F, what)
+    cuts = {what: cut for what, _, _, cut in ct.tile_caps(513)}
+    assert sorted(cuts.values()) == [0, 256, 300, 400, 512, 513, 513]
+    assert cuts["cut at exactly 256 files"] == 256 and 257 <= cuts["cut inside the second tile"] <= 511 and cuts["cut inside the third tile"] == 512
+    assert cuts["the first file does not fit"] == 0
+    # the index capacity is the one that cuts: the payload capacity alone would keep more files
+    what, pcap, icap, cut = ct.tile_caps(513)[-1]
+    assert cut == 300 < ct.cut_file(ct.corpus_tiles(513), pcap, ct.NO_CAP) == 450 and ct.cut_file(ct.corpus_tiles(513), ct.NO_CAP, icap) == 300
+    assert [cut for _, _, _, cut in ct.tile_caps(1000)][-1] == 700 > 512
+
+
+def test_ragged_untrusted_corpus_holds_the_values():
+    c = ct.corpus_untrusted()
+    S = ct.TILE_STRIDE
+    assert c.pay.shape[0] == 300
+    assert {-1, -2 ** 31, S + 1, 2 ** 31 - 1} <= set(c.nbytes.tolist()) and {-1, ct.RAGGED_ISTRIDE, 2 ** 31 - 1} <= set(c.blocks.tolist())
+    poffs, ioffs, blocks, need = ct.plan_of(c)
+    b, e = np.diff(poffs), np.diff(ioffs)
+    assert b[3] == 0 and b[100] == 0 and b[200] == S and b[259] == S and e[5] == 1 and e[150] == 4 and e[270] == 4
+    assert 0 <= b.min() and b.max() <= S and 1 <= e.min() and e.max() <= ct.RAGGED_ISTRIDE and need.tolist() == [b.sum(), e.sum()]
+
+
+def test_ragged_byte_copy_corpus_covers_every_alignment_pair():
+    c = ct.corpus_bytecopy()
+    assert c.pay.shape == (64, ct.COPY_STRIDE) and {(f * ct.COPY_STRIDE) & 3 for f in range(64)} == {0, 1, 2, 3}
+    assert set(c.nbytes.tolist()) == set(ct.COPY_SIZES) | {4 * 256 * 2 + 3, 4 * 256 + 1}
+    poffs = ct.plan_of(c)[0]
+    pairs = {(int(poffs[f]) & 3, (f * ct.COPY_STRIDE) & 3) for f in range(64) if c.nbytes[f] >= 4}     # relative to 4-aligned bases
+    assert len(pairs) == 16
+    for size in range(4):
+        assert len({int(poffs[f]) & 3 for f in range(64) if c.nbytes[f] == size}) >= 2, size
+    F = ct.corpus_many().pay.shape[0]
+    assert F == 16384 + 3 and ct.corpus_many().nbytes.max() == 9 and ct.corpus_many().blocks.max() == 2

@@ -4,7 +4,8 @@ byte for byte against the oracle (clips_testlib: oracle_encode_debug of the inte
 count; the index from the oracle decoder's walk of that payload) - never against this library's own plain encode call.
 Shapes: (BlockSize, nChan) = (256, 2), (512, 1), (256, 3); maxBlocksPerCall = 2, so a call is four chunks and rows end in the
 middle of one; nSamples = 5 * BS + 3; seven rows of 0, 1, BS - 1, BS, BS + 1, 3 * BS + 7 and nSamples samples.  All outputs sit
-on poisoned buffers between guards (tests/guarded_buffers.py)."""
+on poisoned buffers between guards (tests/guarded_buffers.py).  tests/test_gpu_clips_paths.py runs the same call (Call, _check_rows)
+at the shapes where the launch sequence pipelines its chunks, and at scale."""
 import os
 import sys
 import numpy as np
@@ -35,31 +36,37 @@ def _to_pcm16(x):
 
 
 class Call:
-    """One ulcx_encode_clips_dev(_pcm16) call of the seven rows on a guarded arena -> the outputs as numpy."""
+    """One ulcx_encode_clips_dev(_pcm16) call on a guarded arena -> the outputs as numpy.  n rows on an object of `streams`
+    streams; case: nSamples and the lengths of the seven (clip, length) pairs (clips_testlib.Case; default: this file's);
+    rows: the pair of every row (default: row i is pair i % 7).  The call's chunks are the encoder's maxBlocksPerCall."""
 
-    def __init__(self, enc, dec, bs, ch, pstride=None, istride=None, table=False, pcm16=False, null_len=False, n=N):
-        T, nb = ct.n_samples(bs), ct.clip_blocks(bs, ct.n_samples(bs))
-        self.n, self.T = n, T
+    def __init__(self, enc, dec, bs, ch, pstride=None, istride=None, table=False, pcm16=False, null_len=False, n=N, streams=B, case=None, rows=None):
+        case = case or ct.short_case(bs)
+        rows = [i % 7 for i in range(n)] if rows is None else list(rows)
+        assert len(rows) == n <= streams
+        T, nb = case.T, ct.clip_blocks(bs, case.T)
+        G = min(streams, 8)                                 # rows of a guard (the guards of a large object: as those of eight streams)
+        self.n, self.T, self.rows, self.case = n, T, rows, case
         self.pstride = pstride or enc.slot * nb
         self.istride = istride or nb + 1
         esz = 2 if pcm16 else 4
-        word = lambda name, k, role: dict(name=name, nbytes=4 * k, align=4, role=role, guard=4 * B, row=4)
-        specs = [dict(name="d_pcm", nbytes=n * ch * T * esz, align=esz, role="in", guard=B * ch * T * esz, row=T * esz, rows_per_stream=ch)]
+        word = lambda name, k, role: dict(name=name, nbytes=4 * k, align=4, role=role, guard=4 * G, row=4)
+        specs = [dict(name="d_pcm", nbytes=n * ch * T * esz, align=esz, role="in", guard=G * ch * T * esz, row=T * esz, rows_per_stream=ch)]
         if not null_len:
             specs.append(word("d_len", n, "in"))
         if table:
-            specs.append(dict(name="d_rate", nbytes=8 * n, align=8, role="in", guard=8 * B, row=8))
-        specs += [dict(name="d_payload", nbytes=n * self.pstride, align=1, role="out", guard=B * self.pstride, row=self.pstride),
+            specs.append(dict(name="d_rate", nbytes=8 * n, align=8, role="in", guard=8 * G, row=8))
+        specs += [dict(name="d_payload", nbytes=n * self.pstride, align=1, role="out", guard=G * self.pstride, row=self.pstride),
                   word("d_payloadBytes", n, "out"), word("d_maxBlock", n, "out"),
-                  dict(name="d_index", nbytes=8 * n * self.istride, align=4, role="out", guard=8 * B * self.istride, row=8, rows_per_stream=self.istride),
+                  dict(name="d_index", nbytes=8 * n * self.istride, align=4, role="out", guard=8 * G * self.istride, row=8, rows_per_stream=self.istride),
                   word("d_indexBlocks", n, "out")]
         a = self.a = gb.build(_dev(), specs)
-        w = ct.wave(bs, ch)[:n]
+        w = ct.wave(bs, ch, T)[rows]
         a.load("d_pcm", _to_pcm16(w) if pcm16 else w)
         if not null_len:
-            a.load("d_len", np.array(ct.lengths(bs)[:n], np.int32))
+            a.load("d_len", np.array(case.lengths, np.int32)[rows])
         if table:
-            a.load("d_rate", np.array(ct.TABLE[:n], np.float32))
+            a.load("d_rate", np.array(ct.TABLE, np.float32)[rows])
         self.args = dict(pcm16=pcm16, d_rates=a.ptr("d_rate") if table else 0, mode=0, p0=50.0)
         self.enc, self.dec = enc, dec
 
