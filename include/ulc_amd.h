@@ -485,6 +485,14 @@ int  ulcx_index_packed_host(ulcx_decoder *dec, const uint8_t *h_payload, long lo
  * stream's end does in ulcx_decode_packed_dev); a d_first[s] outside [0, d_indexBlocks[s]] gives a stream of 0 bits (the
  * device forms cannot refuse it without a synchronisation; the host forms refuse a negative one with ULCX_ERR_ARG before
  * any device work).  Nothing outside the call's buffers is read or written.
+ * A PAYLOAD THAT IS NOT THE ONE THE INDEX WAS BUILT FROM (bytes changed behind a stored index): every block is read at its index
+ * offset and inside its index extent only.  A block that is corrupt, or that runs past its extent, ends the stream there for this
+ * call - 0 bits and zero samples from it on, the blocks in front of it as they are; a corrupt block in front of the range gives
+ * a stream of 0 bits.  A damaged block that still parses inside its extent is decoded as it reads, and behind it the noise follows
+ * the draws actually made, counted from the stored RngState of the block in front of the range.  A stream none of whose blocks -
+ * the block in front of the range included - is touched is unaffected.  The state left is the same continuation: a stream that
+ * ended this way is dead for the packed calls that follow (a later range call does not inherit that), any other continues with the
+ * block at the closing index entry of the range.  (tests/test_gpu_damaged_crops.py, against the reference decoder run block by block.)
  * After the call a stream's persistent state - lapping, LastSubBlockSize, generator, dead flag, packed read position - is
  * exactly what a sequential decode up to and including block d_first[s] + nBlocks - 1 leaves: a following
  * ulcx_decode_packed_dev on the same payload continues with the next block, and a later range call may go backwards.
@@ -525,6 +533,11 @@ int  ulcx_decode_resident_range_host(ulcx_decoder *dec, const int32_t *h_first, 
  * bits and zero samples and leave the other rows as they are; nothing outside the call's buffers is read or written.  The host
  * form refuses a file number out of range, a first outside [0, h_indexBlocks[file]] and a negative count with ULCX_ERR_ARG
  * before any device work.
+ * A file whose bytes changed behind its stored index is read as a range call reads it: each block inside its index extent; a block
+ * that is corrupt or runs past its extent ends the row there (0 bits and zero samples from it on; a row whose block in front is such
+ * a block is all zeros); behind a damaged block that still parses, the noise follows the draws actually made.  Rows none of whose
+ * blocks, the block in front included, is touched - of the same file or of others - are unaffected.  The ragged and the sample
+ * forms below do the same (a sample row is zero from the dead block's first sample to its exact end).
  * STATE: a crop call reads no stream's persistent state and changes none - lapping, LastSubBlockSize, generator, dead flag,
  * packed read position, resident payload, resident index.  It may be mixed freely with every other call on the object; a
  * sequential decode that is under way continues as if the crop call had not been made.  The call runs on the subset calls'

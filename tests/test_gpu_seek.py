@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
 from seek_testlib import (RATE, SEED0, ORACLE_BLOCKS, geometries, oracle_stream, pack, oracle_seeds, oracle_pcm, expected_range,
                           switched_starts, damaged, oracle_walk)
+from ulc_testlib import oracle_decode_stream
 
 pytestmark = pytest.mark.gpu
 TOOL = os.path.join(ROOT, "ulc-codec_amd", "ulcx-tool")
@@ -110,7 +111,8 @@ DAMAGE_SEEDS = {
 def test_index_and_decode_of_damaged_payloads_match_the_oracle(geom):
     """Sixteen copies of one payload, each with one nybble overwritten inside its first half.  The index (count, offsets,
     generator states) and the bits a packed decode reports must be what the oracle's decoder gives when it walks the same
-    bytes block by block (seek_testlib.oracle_walk): one walk serves both calls, and a range call trusts the index."""
+    bytes block by block (seek_testlib.oracle_walk): one walk serves both calls, and a range call trusts the index.  The
+    samples of the packed decode are the oracle's too, bit for bit, up to the block where the walk stops, and zero behind it."""
     amd = _amd()
     bs, ch = geom
     K, seeds = ORACLE_BLOCKS, DAMAGE_SEEDS[geom]
@@ -135,7 +137,7 @@ def test_index_and_decode_of_damaged_payloads_match_the_oracle(geom):
     index, count = dec.index_packed(host, nb, K)
     dec.close()
     dec = amd.BatchDecoder(len(seeds), ch, bs, K)
-    _, gbits = dec.decode_packed(host, nb, K)
+    gpcm, gbits = dec.decode_packed(host, nb, K)
     dec.close()
     for s, (wbits, woffs, wseeds, _) in enumerate(walks):
         n = len(wbits)
@@ -147,6 +149,14 @@ def test_index_and_decode_of_damaged_payloads_match_the_oracle(geom):
         want = np.zeros(K, np.int32)
         want[:n] = wbits
         assert np.array_equal(gbits[s], want), f"{what}: the decode reports {gbits[s]}, the oracle {want}"
+        # the samples: the damaged payload cut into slot rows at the walk's offsets, decoded by the oracle in one run
+        rows = np.zeros((max(n, 1), 2 * ch * bs + 16), np.uint8)
+        for k in range(n):
+            rows[k, :woffs[k + 1] - woffs[k]] = host[s, woffs[k]:woffs[k + 1]]
+        rc, rpcm, rbits = oracle_decode_stream(rows[:n], ch, bs) if n else (0, np.zeros((0, ch), np.float32), wbits)
+        assert rc == 0 and np.array_equal(rbits, wbits), what
+        assert _same_bits(gpcm[s][:n * bs], rpcm), f"{what}: the decoded samples differ from the oracle's"
+        assert not gpcm[s][n * bs:].any(), f"{what}: samples behind block {n}, where the walk stops"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
