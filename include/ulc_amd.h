@@ -130,6 +130,7 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  * ALIGNMENT.  The widest access a kernel makes to the buffer; every row of a buffer keeps it (rows are multiples of it).
  *   16 bytes  binary32 samples: d_pcm of the encode, analyse, decode, decode_packed, decode_range and decode_crops calls
  *             (16-byte loads of the transform's fold, 16-byte stores of the stereo synthesis)
+ *             binary32 coefficients: d_coef of the spectra calls (ulcx_decode_crops_spectra_*: 16-byte stores)
  *             saved stream records: d_state of the stream-slot entries (16-byte loads and stores)
  *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
@@ -665,6 +666,65 @@ int  ulcx_decode_crops_samples_ragged_host(ulcx_decoder *dec, int nFiles,
                                            const int32_t *h_indexBlocks,
                                            int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len,
                                            int nSamples, float *h_pcm, int32_t *h_bits);   /* synchronous */
+/* Spectra: the crop calls stopped in front of the inverse transform - the dequantised MDCT coefficients of every block of a row,
+ * the noise fill included, for models that take time-frequency input.  No FFT, no window, no lapping state and no synthesis of the
+ * block in front of the range: behind the crop walk one workgroup per (row, block, channel pair) expands the walk's records.
+ * The corpus, n, nBlocks, d_file, d_first and d_count are exactly the crop calls' (n is 1 .. nStreams, nBlocks is
+ * 1 .. maxBlocksPerCall - 1, the walk's per-block scratch is the object's).  There is no PCM16 form: coefficients are not samples.
+ *   d_coef  float32 [n][nChan][nBlocks][BlockSize], channels-first as the sample crops are: one channel's blocks form a
+ *           [frames][bins] plane.  Written in full.  d_coef[i][ch][k] is, bit for bit and with the noise included, what the
+ *           reference decoder holds in TransformBuffer for channel ch of block d_first[i] + k of a sequential decode of file
+ *           d_file[i] from its block 0 (ulcDecoder.c:228-231): the block's sub-blocks in coded order, each S coefficients long.
+ *           The values are the normalised coefficients of the CODED channels (mid / side for a pair); nothing is re-ordered onto
+ *           a uniform grid, and the codec's delay is not compensated.
+ *   d_wc    int32 [n][nBlocks]: the block's window code as the decoder forms it - the first nybble, | second << 4 when bit 3 is
+ *           set, else | 0x10 - and 0 for a block that is not live.  ulcx_window_subblocks(BlockSize, wc, sizes) tells how the
+ *           block's BlockSize coefficients split into shorter spectra.
+ *   d_bits  int32 [n][nBlocks]: entry for entry what ulcx_decode_crops_dev writes for the same rows.  A block is live in this call
+ *           exactly when it is live in the crop call, under every rule stated above for crops: a block past the file's end or past
+ *           d_count, everything behind a corrupt block, a row whose block in front is corrupt, untrusted file numbers, firsts,
+ *           index entries and ragged tables.  A block that is not live has 0 bits, wc 0 and coefficients of +0.0f.  Behind a
+ *           damaged block that still parses, the noise follows the draws actually made, as in the crop call.
+ *   flags   0, or ULCX_SPECTRA_LR: the channel pairs the decoder un-mixes in the time domain - (0,1), (2,3), ...; a trailing
+ *           single channel is untouched (ulcDecoder.c:281-289) - come out as m + s and m - s, one float32 addition or subtraction
+ *           per coefficient.  A block's window code is common to its channels and the transform is linear, so this is the
+ *           linear-domain equivalent of the decoder's un-mixing: the spectrum of the left / right signal up to the rounding of
+ *           the transform.  It is NOT a value the reference ever holds.  Any other bit: ULCX_ERR_ARG.
+ * STATE / ORDER: the call reads and changes no stream's persistent state and mixes freely with every other call on the object
+ * (it does not even touch the compact state copy the crop calls run on); it allocates nothing after the first subset or crop
+ * call; the device forms are asynchronous on hipStream (two kernels: the walk, the expansion).  ulcx_decoder_last_cut reports
+ * the plain plan (0 workgroups of a cut): the kernel's grid is n * nBlocks * ceil(nChan / 2) whatever n is.
+ * The host forms refuse what ulcx_decode_crops_host / ulcx_decode_crops_ragged_host refuse, before any device work.
+ * ALIGNMENT: d_coef 16 bytes; d_wc, d_bits, d_file, d_first, d_count and the corpus's int32 arrays 4; the ragged tables 8; a
+ * misaligned pointer returns ULCX_ERR_ARG before any device work. */
+#define ULCX_SPECTRA_LR 1   /* flags: left/right instead of the coded mid/side (see above) */
+int  ulcx_window_subblocks(int BlockSize, int wc, int sizes[4]);
+    /* host arithmetic: the number of sub-blocks (1..4) of a block with window code wc and their sizes in coded order (unused
+       entries 0; sizes may be NULL); 0 for a code no block can carry - among them 0, a block that is not live - or a bad
+       BlockSize.  A decimated header whose second nybble is 0 or 1 (no row of FormatSpecs.md's table; the reference decodes it
+       as one full-size block) gives 1 sub-block of BlockSize. */
+int  ulcx_decode_crops_spectra_dev(ulcx_decoder *dec, int nFiles,
+                                   const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes /* [nFiles] */,
+                                   const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks /* [nFiles] */,
+                                   int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count /* optional */,
+                                   int nBlocks, int flags, float *d_coef, int32_t *d_wc, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_spectra_host(ulcx_decoder *dec, int nFiles,
+                                    const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                    const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                    int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
+                                    int nBlocks, int flags, float *h_coef, int32_t *h_wc, int32_t *h_bits);   /* synchronous */
+int  ulcx_decode_crops_spectra_ragged_dev(ulcx_decoder *dec, int nFiles,
+                                          const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs /* [nFiles+1] */,
+                                          const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs /* [nFiles+1] */,
+                                          const int32_t *d_indexBlocks /* [nFiles] */,
+                                          int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count /* optional */,
+                                          int nBlocks, int flags, float *d_coef, int32_t *d_wc, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_spectra_ragged_host(ulcx_decoder *dec, int nFiles,
+                                           const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                           const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs,
+                                           const int32_t *h_indexBlocks,
+                                           int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
+                                           int nBlocks, int flags, float *h_coef, int32_t *h_wc, int32_t *h_bits);   /* synchronous */
 /* The index of a ragged corpus in one call: row f receives, entry for entry, what ulcx_index_packed_rows_dev writes for file f's
  * payload alone with maxBlocks = capacity - 1, the {-1, 0} entries behind the closing one up to the row's capacity included, and
  * d_nBlocks[f] the count.  A row of capacity below 1, or a file whose offsets are as refused above, gets d_nBlocks[f] = 0 and no

@@ -333,3 +333,37 @@ class CropCorpus:
                                      self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), start.data_ptr(),
                                      want.data_ptr() if want is not None else 0, n_samples, pcm.data_ptr(), bits.data_ptr(), stream=stream, pcm16=pcm16)
         return pcm, bits
+
+    def spectra(self, dec, files, first, n_blocks, count=None, lr=False):
+        """Row i: the dequantised MDCT coefficients, noise fill included, of blocks first[i] .. first[i] + n_blocks - 1 of file
+        files[i] (the leading count[i] of them when `count` is given; zeros behind) - crops() stopped in front of the inverse
+        transform (ulcx_decode_crops_spectra_dev).  The channels are the coded ones (mid / side for a pair) unless `lr`; a block's
+        sub-blocks lie in coded order: ulc_amd.window_subblocks(BlockSize, wc) splits it.  No delay compensation.
+        -> (coef [n][nChan][n_blocks][BlockSize] float32, wc int32 [n][n_blocks], bits int32 [n][n_blocks]) on the device, enqueued
+        on torch's current stream.  `dec`: as for crops(); no stream state of it is read or changed."""
+        import torch
+        if not self.frozen:
+            raise UlcError("corpus: not frozen")
+        if (dec.C, dec.BS) != (self.C, self.BS):
+            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
+        as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=self.device).contiguous()
+        files, first = as_i32(files), as_i32(first)
+        want = None if count is None else as_i32(count)
+        n = files.numel()
+        assert first.numel() == n and (want is None or want.numel() == n)
+        coef = torch.empty((n, self.C, n_blocks, self.BS), dtype=torch.float32, device=self.device)
+        wc = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        flags = ulc_amd.SPECTRA_LR if lr else 0
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.ragged:
+            dec.decode_crops_spectra_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
+                                                self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
+                                                n, files.data_ptr(), first.data_ptr(), want.data_ptr() if want is not None else 0, n_blocks, flags,
+                                                coef.data_ptr(), wc.data_ptr(), bits.data_ptr(), stream=stream)
+            return coef, wc, bits
+        dec.decode_crops_spectra_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
+                                     self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), first.data_ptr(),
+                                     want.data_ptr() if want is not None else 0, n_blocks, flags, coef.data_ptr(), wc.data_ptr(), bits.data_ptr(),
+                                     stream=stream)
+        return coef, wc, bits

@@ -1129,7 +1129,7 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subse
     a.synGrid = 0; a.synFull = 0;
     c.lapO = c.lap; c.lastSubO = c.lastSub; c.seedO = c.seed; c.deadO = c.dead;
     const int Kc = c.range ? c.K - 1 : c.K;                       // blocks of the call per stream (a range call's K counts the row of the block in front)
-    if (e->splitOK && e->synSlots > 0) {
+    if (e->splitOK && e->synSlots > 0 && !a.specCoef) {             // (a spectra call has no synthesis to cut: the plain plan)
         // A range call of more streams than the device holds at once: whole rounds, and the last one cut
         // (ulcx_dec_range_tail_plan) - an even cut of everything ends every workgroup inside a stream, and in a range call every
         // entry into a stream costs the block in front of the range (ULCX_RANGE_CUT=even: the even cut first, as for other calls)
@@ -1700,14 +1700,22 @@ static int crops_ragged_args_bad(const char *who, const ulcx_decoder *e, int nFi
 }
 // the rows of a sample-crop call (ulcx_decode_crops_samples_*): d_first / d_count are not given, nBlocks is ulcx_crop_blocks(nSamples)
 struct CropsSamples { const int64_t *start; const int32_t *len; int nSamples; };
+// the outputs of a spectra call (ulcx_decode_crops_spectra_*) beside d_bits: coefficients instead of samples, and the window codes
+struct CropsSpectra { float *coef; int32_t *wc; int flags; };
+static int spectra_flags_bad(const char *who, int flags) {
+    if (flags & ~ULCX_SPECTRA_LR) { refuse(who, "bad argument (flags 0x%x: 0 or ULCX_SPECTRA_LR)", (unsigned)flags); return 1; }
+    return 0;
+}
 // ragged != NULL: the ragged layout (payloadStride, d_payloadBytes and indexStride are not looked at)
 // samp != NULL: a sample-crop call - the rows come from (start, len), the output is [n][nChan][nSamples] and needs its element's alignment only
+// spec != NULL: a spectra call - d_pcm and d_pcm16 are NULL, the outputs are spec's [n][nChan][nBlocks][BlockSize] and [n][nBlocks]
 static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                             const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
                             int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
                             float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, const CropsRagged *ragged = nullptr,
-                            const CropsSamples *samp = nullptr) {
-    const void *out = d_pcm ? (const void *)d_pcm : d_pcm16;
+                            const CropsSamples *samp = nullptr, const CropsSpectra *spec = nullptr) {
+    if (spec && spectra_flags_bad(who, spec->flags)) return ULCX_ERR_ARG;
+    const void *out = spec ? (spec->wc ? (const void *)spec->coef : nullptr) : d_pcm ? (const void *)d_pcm : d_pcm16;
     const void *rows = samp ? (const void *)samp->start : d_first;
     if (ragged ? crops_ragged_args_bad(who, e, nFiles, d_payload, *ragged, d_index, d_indexBlocks, n, d_file, rows, nBlocks, out, d_bits)
                : crops_args_bad(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, rows, nBlocks, out, d_bits))
@@ -1718,6 +1726,8 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const 
         misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_file", d_file, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_first", d_first, ULCX_ALIGN_WORD) || misaligned(who, "d_count", d_count, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    if (spec && (misaligned(who, "d_coef", spec->coef, ULCX_ALIGN_PCM) || misaligned(who, "d_wc", spec->wc, ULCX_ALIGN_WORD))) return ULCX_ERR_ARG;
+    if (spec && (long long)n * nBlocks * ((e->C + 1) / 2) > 0x7FFFFFFFLL) return refuse(who, "bad argument (n x nBlocks x channel pairs exceeds a grid)");
     // (a plane of a sample crop starts at any sample: the kernels use wider stores only where the address allows them)
     if (samp ? (misaligned(who, "d_start", samp->start, ULCX_ALIGN_OFFS) || misaligned(who, "d_len", samp->len, ULCX_ALIGN_WORD) ||
                 misaligned(who, "d_pcm", d_pcm, (int)sizeof(float)) || misaligned(who, "d_pcm16", d_pcm16, (int)sizeof(int16_t)))
@@ -1740,6 +1750,7 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const 
         crop.sampFirst = e->sampRows; crop.sampCount = e->sampRows + e->B; crop.sampSkip = e->sampRows + 2 * (size_t)e->B; crop.sampLenC = e->sampRows + 3 * (size_t)e->B;
         c.rFirst = crop.sampFirst; crop.cropCount = crop.sampCount;
     }
+    if (spec) { crop.specCoef = spec->coef; crop.specWc = spec->wc; crop.specLR = (spec->flags & ULCX_SPECTRA_LR) ? 1 : 0; }
     int set = 0;
     rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &crop);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
@@ -1767,12 +1778,19 @@ static int payload_rows_up(DevTmp &t, int nRows, const uint8_t *h_payload, long 
     CKR(hipMemcpy(*dn, h_payloadBytes, sizeof(int32_t) * (size_t)nRows, hipMemcpyHostToDevice));
     return ULCX_OK;
 }
-extern "C" int ulcx_decode_crops_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
-                                      const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
-                                      int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
-                                      float *h_pcm, int32_t *h_bits) {
-    const char *who = "ulcx_decode_crops_host";
-    if (crops_args_bad(who, e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, n, h_file, h_first, nBlocks, h_pcm, h_bits)) return ULCX_ERR_ARG;
+// what a host form leaves of a spectra call beside the crop results: the window codes (hspec: the HOST outputs, flags as given)
+static int spectra_wc_down(const int32_t *d_wc, size_t NB, int32_t *h_wc) {
+    CKR(hipMemcpy(h_wc, d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+// the strided host forms: ulcx_decode_crops_host (h_pcm) and ulcx_decode_crops_spectra_host (hspec: h_pcm is its coefficients)
+static int crops_host_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                          const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                          int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                          float *h_pcm, int32_t *h_bits, const CropsSpectra *hspec = nullptr) {
+    if (hspec && spectra_flags_bad(who, hspec->flags)) return ULCX_ERR_ARG;
+    if (crops_args_bad(who, e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, n, h_file, h_first, nBlocks,
+                       (hspec && !hspec->wc) ? nullptr : h_pcm, h_bits)) return ULCX_ERR_ARG;
     // what the device forms cannot refuse
     for (int i = 0; i < n; i++) {
         if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
@@ -1794,8 +1812,19 @@ extern "C" int ulcx_decode_crops_host(ulcx_decoder *e, int nFiles, const uint8_t
     CKR(hipMemcpy(df, h_first, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
     if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
-    rc = decode_crops_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, n, dfile, df, dwant, nBlocks, dpcm, nullptr, dbits, nullptr);
-    return rc ? rc : dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+    CropsSpectra ds = {};
+    if (hspec) { ds.coef = dpcm; ds.flags = hspec->flags; CKR(t.get(&ds.wc, sizeof(int32_t) * NB)); }
+    rc = decode_crops_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, n, dfile, df, dwant, nBlocks, hspec ? nullptr : dpcm, nullptr, dbits, nullptr,
+                          nullptr, nullptr, hspec ? &ds : nullptr);
+    if (!rc) rc = dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+    return (rc || !hspec) ? rc : spectra_wc_down(ds.wc, NB, hspec->wc);
+}
+extern "C" int ulcx_decode_crops_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                      const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                      int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                                      float *h_pcm, int32_t *h_bits) {
+    return crops_host_any("ulcx_decode_crops_host", e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks,
+                          n, h_file, h_first, h_count, nBlocks, h_pcm, h_bits);
 }
 // ulcx_index_packed_* with a row count of its own: k_dindex over nRows (geometry and tables are all that is read of the object)
 static int index_rows_packed_any(const char *who, ulcx_decoder *e, int nRows, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
@@ -1868,13 +1897,14 @@ static int ragged_up(DevTmp &t, int nFiles, const uint8_t *h_payload, const Crop
     *dg = CropsRagged{ g.payloadTotal, po, g.indexTotal, io };
     return ULCX_OK;
 }
-extern "C" int ulcx_decode_crops_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
-                                             const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
-                                             int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
-                                             float *h_pcm, int32_t *h_bits) {
-    const char *who = "ulcx_decode_crops_ragged_host";
+// the ragged host forms: ulcx_decode_crops_ragged_host and ulcx_decode_crops_spectra_ragged_host (hspec, as crops_host_any)
+static int crops_ragged_host_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                 const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                 int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                                 float *h_pcm, int32_t *h_bits, const CropsSpectra *hspec = nullptr) {
+    if (hspec && spectra_flags_bad(who, hspec->flags)) return ULCX_ERR_ARG;
     const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
-    if (crops_ragged_args_bad(who, e, nFiles, h_payload, g, h_index, h_indexBlocks, n, h_file, h_first, nBlocks, h_pcm, h_bits)) return ULCX_ERR_ARG;
+    if (crops_ragged_args_bad(who, e, nFiles, h_payload, g, h_index, h_indexBlocks, n, h_file, h_first, nBlocks, (hspec && !hspec->wc) ? nullptr : h_pcm, h_bits)) return ULCX_ERR_ARG;
     // what the device forms cannot refuse: the tables, then the rows as the strided host form
     if (ragged_tables_bad(who, nFiles, g)) return ULCX_ERR_ARG;
     for (int i = 0; i < n; i++) {
@@ -1898,8 +1928,67 @@ extern "C" int ulcx_decode_crops_ragged_host(ulcx_decoder *e, int nFiles, const 
     CKR(hipMemcpy(df, h_first, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     if (indexTotal) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyHostToDevice));
     if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
-    rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, dfile, df, dwant, nBlocks, dpcm, nullptr, dbits, nullptr, &dg);
-    return rc ? rc : dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+    CropsSpectra ds = {};
+    if (hspec) { ds.coef = dpcm; ds.flags = hspec->flags; CKR(t.get(&ds.wc, sizeof(int32_t) * NB)); }
+    rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, dfile, df, dwant, nBlocks, hspec ? nullptr : dpcm, nullptr, dbits, nullptr, &dg,
+                          nullptr, hspec ? &ds : nullptr);
+    if (!rc) rc = dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+    return (rc || !hspec) ? rc : spectra_wc_down(ds.wc, NB, hspec->wc);
+}
+extern "C" int ulcx_decode_crops_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                             const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                             int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                                             float *h_pcm, int32_t *h_bits) {
+    return crops_ragged_host_any("ulcx_decode_crops_ragged_host", e, nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks,
+                                 n, h_file, h_first, h_count, nBlocks, h_pcm, h_bits);
+}
+// ---- spectra (include/ulc_amd.h section 3): the crop families' bodies, ending in the dequantised coefficients instead of samples.
+extern "C" int ulcx_window_subblocks(int BlockSize, int wc, int sizes[4]) {
+    // a code a block can carry (ulcDecoder.c:211-216): the first nybble, and the second one only behind a first with bit 3 set
+    if (!validate(1, BlockSize) || wc < 0 || wc > 0xFF || (!(wc & 8) && (wc >> 4) != 1)) return 0;
+    unsigned pat = ulcx_pattern(wc);
+    int nsub = 0;
+    do {
+        const int S = BlockSize >> (pat & 7);
+        if (sizes) sizes[nsub] = S;
+        nsub++;
+        if (S == BlockSize) break;                                // ulcDecoder.c:242-245
+    } while (pat >>= 4);
+    if (sizes) for (int j = nsub; j < 4; j++) sizes[j] = 0;
+    return nsub;
+}
+extern "C" int ulcx_decode_crops_spectra_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                             const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                             int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks, int flags,
+                                             float *d_coef, int32_t *d_wc, int32_t *d_bits, void *hipStream) {
+    const CropsSpectra sp = { d_coef, d_wc, flags };
+    return decode_crops_any("ulcx_decode_crops_spectra_dev", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks,
+                            n, d_file, d_first, d_count, nBlocks, nullptr, nullptr, d_bits, hipStream, nullptr, nullptr, &sp);
+}
+extern "C" int ulcx_decode_crops_spectra_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                    const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                    int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks, int flags,
+                                                    float *d_coef, int32_t *d_wc, int32_t *d_bits, void *hipStream) {
+    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
+    const CropsSpectra sp = { d_coef, d_wc, flags };
+    return decode_crops_any("ulcx_decode_crops_spectra_ragged_dev", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, d_first, d_count, nBlocks,
+                            nullptr, nullptr, d_bits, hipStream, &g, nullptr, &sp);
+}
+extern "C" int ulcx_decode_crops_spectra_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                              const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                              int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks, int flags,
+                                              float *h_coef, int32_t *h_wc, int32_t *h_bits) {
+    const CropsSpectra sp = { h_coef, h_wc, flags };
+    return crops_host_any("ulcx_decode_crops_spectra_host", e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks,
+                          n, h_file, h_first, h_count, nBlocks, h_coef, h_bits, &sp);
+}
+extern "C" int ulcx_decode_crops_spectra_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                                     const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                                     int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks, int flags,
+                                                     float *h_coef, int32_t *h_wc, int32_t *h_bits) {
+    const CropsSpectra sp = { h_coef, h_wc, flags };
+    return crops_ragged_host_any("ulcx_decode_crops_spectra_ragged_host", e, nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs,
+                                 h_indexBlocks, n, h_file, h_first, h_count, nBlocks, h_coef, h_bits, &sp);
 }
 // ---- sample crops (include/ulc_amd.h section 3): the crop families' bodies with rows given in samples and the output channels-first.
 extern "C" int ulcx_crop_blocks(int BlockSize, int nSamples) {

@@ -14,6 +14,8 @@
 //             (the reference's reversed-time FIFO without the shifting: dec_time_wave), inverse M/S,
 //             interleave (libulc/ulcDecoder.c:198-302; IMDCT per FormatSpecs.md:150-157).
 //   k_dgen    every other geometry (mono, multichannel, BlockSize > 4096): same pieces, one array.
+//   k_dspec   spectra calls (ulcx_decode_crops_spectra_*): in place of the synthesis - the dequantised coefficients themselves,
+//             one workgroup per (row, block, channel pair), stored channels-first; the one call whose coefficients do reach HBM.
 // Compiled with -ffp-contract=off (see ulcx_enc.hip).
 #include "ulcx_internal.h"
 #include "ulcx_dec_dev.h"
@@ -1632,6 +1634,139 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
     if (tid == 0) { c.lastSub[s] = lastSub; c.seed[s] = seed; c.dead[s] = dead; }
 }
 
+// ---------------------------------------------------------------------------
+// Spectra (ulcx_decode_crops_spectra_*): the call stops where the synthesis would start its transforms - the dequantised
+// coefficients of every (row, block, channel), noise included, go out as they stand in the unit arrays, channels-first:
+// coef [row][channel][block][BS], a block's subblocks in coded order (ulcDecoder.c:228-231: what TransformBuffer holds).
+// Behind the crop walk nothing of a block depends on another block but the generator state (a jump over the draws of the rows in
+// front) and liveness (no walked row up to this one is corrupt), so the grid is one workgroup per (row, output block, channel
+// pair), pair fastest, and no workgroup loops over blocks.  Row 0 of the walk, the block in front, is only ever looked at for
+// those two; its records are not expanded.
+//   two = 1: one wave per channel of the pair, each into its own array (BS + BS/16 floats, the FFT arrays' padding: synth_unit
+//            writes through padf).  LR: a barrier, then each wave forms its own channel's m + s / m - s from both arrays.
+//   two = 0: two arrays do not fit a CU's LDS (spec_lds): wave 0 dequantises the pair's channels one after the other into one
+//            array and all 128 threads store it.  LR: the first channel goes out with plain stores, and behind a device-scope
+//            fence and a barrier the second channel's store re-reads it (each thread the 16 bytes it stored itself) and writes both.
+// Live blocks: every element stored exactly once (two = 0 with LR: the first plane twice, by the same thread).  Dead blocks: +0.0f.
+// ---------------------------------------------------------------------------
+struct UlcxSpecArg { float *coef; int32_t *wc; int nPairs; };
+struct SpecLds { int arrFloats, nArr, listInts; };
+__host__ __device__ static inline SpecLds spec_lds(int BS) {
+    SpecLds l;
+    l.arrFloats = BS + BS / 16;                                  // = 2 * FFT_PADDEDS(BS / 2, DPS) at DPS 4: padf's layout
+    l.listInts = 64 + DSYN_PWORDS(BS);                           // per dequantising wave: prefix counts, sign-parity stream
+    l.nArr = (sizeof(float) * 2 * ((size_t)l.arrFloats + l.listInts) <= (size_t)ULCX_LDS_LIMIT) ? 2 : 1;
+    return l;
+}
+// the padded array's floats [i, i + 4), i a multiple of 4 (never across a padding gap)
+__device__ __forceinline__ f32x4 spec_ld4(const float *A, int i) {
+    const float2 a = *(const float2 *)(A + padf(i)), b = *(const float2 *)(A + padf(i) + 2);
+    f32x4 v = { a.x, a.y, b.x, b.y };
+    return v;
+}
+template <bool LR>
+__global__ __launch_bounds__(WG) void k_dspec(UlcxDecCtx c, UlcxSpecArg sp) {
+    static_assert(DPS == 4, "k_dspec: a unit's offset (a multiple of 32) and four consecutive floats stay clear of the padding gaps");
+    extern __shared__ float lds[];
+    const int BS = c.BS, C = c.C, N = c.K - 1;
+    const int tid = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const SpecLds L = spec_lds(BS);
+    const bool two = L.nArr == 2;
+    const unsigned pr = blockIdx.x % (unsigned)sp.nPairs, rb = blockIdx.x / (unsigned)sp.nPairs;
+    const int kOut = (int)(rb % (unsigned)N), s = (int)(rb / (unsigned)N), k = kOut + 1;
+    const int blk = s * c.K + k;
+    const int ch0 = 2 * (int)pr;
+    const bool pair = ch0 + 1 < C;
+    // entering the block: liveness and the draws of the walked rows in front (k_dsyn's RANGE entry; at most maxBlocksPerCall terms)
+    const int2 ri = c.rInfo[s];
+    int bad = 0; uint32_t dsum = 0;
+    for (int j = 1 - ri.x + lane; j <= k; j += 64) {
+        const int bj = s * c.K + j;
+        if (c.wcScan[bj] == 0) bad = 1;
+        if (j < k) dsum += (uint32_t)c.draws[bj];
+    }
+    const bool dead = __ballot(bad) != 0ull;                     // (each wave for itself, both the same: uniform over the workgroup)
+    const size_t oblk = (size_t)s * N + kOut;
+    const int wc = dead ? 0 : c.wcScan[blk];
+    if (pr == 0 && tid == 0) { c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; sp.wc[oblk] = wc; }
+    float *pl0 = sp.coef + (((size_t)s * C + ch0) * N + kOut) * BS, *pl1 = pl0 + (size_t)N * BS;     // the pair's planes
+    if (dead) {
+        for (int i = 4 * tid; i < BS; i += 4 * WG) { st4(pl0 + i, 0.0f, 0.0f, 0.0f, 0.0f); if (pair) st4(pl1 + i, 0.0f, 0.0f, 0.0f, 0.0f); }
+        return;
+    }
+    const uint32_t seed = rng_jump(c.jumpT, (uint32_t)ri.y, (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add(dsum), 63));
+    const int *udraw = c.unitDraws + (size_t)blk * C * 4;
+    const int4 *urec = c.unitRec + (size_t)blk * C * 4;
+    const float4 *utail = c.unitTail + (size_t)blk * C * 4;
+    const uint2 *prec = c.prec + (size_t)blk * c.precStride, *nrec = c.nrec + (size_t)blk * c.nrecStride;
+    const float *tmag = c.tailMag + (size_t)blk * C * 4 * c.tailStride;
+    const BlockShape shape = block_shape(BS, wc);
+    const int nsub = shape.nsub;
+    auto unit_draws = [&](int ch, int j) { return ((j + 1 < nsub) ? udraw[ch * 4 + j + 1] : (ch + 1 < C) ? udraw[(ch + 1) * 4] : c.draws[blk]) - udraw[ch * 4 + j]; };
+    SynWave sw;
+    sw.pre = (int *)(lds + (size_t)L.nArr * L.arrFloats) + (two ? wv : 0) * L.listInts;
+    sw.seedTab = (uint32_t *)(sw.pre + 64);
+    sw.lane = lane;
+#ifdef ULCX_DSYN_STAMPS
+    sw.stp = nullptr;
+#endif
+    // channel ch of the block into A: its units one behind the other, each cleared behind its own record loads
+    auto dequant = [&](int ch, float *A) {
+        int off = 0;
+        for (int j = 0; j < nsub; j++) {
+            const int S = BS >> ((shape.pat >> (4 * j)) & 7), us = ch * 4 + j;
+            sw.A = A + padf(off);
+            const uint32_t unitSeed = rng_jump(c.jumpT, seed, (uint32_t)udraw[us]);
+            synth_unit(c, sw, S, prec, nrec, urec[us], unitSeed, unit_draws(ch, j), utail[us].y, tmag + (size_t)us * c.tailStride, (S + S / 16) >> 1);
+            off += S;
+        }
+    };
+    if (two) {
+        float *A = lds + (size_t)wv * L.arrFloats;
+        const bool mine = wv == 0 || pair;
+        if (mine) dequant(ch0 + wv, A);
+        float *pl = wv ? pl1 : pl0;
+        if (LR && pair) {
+            __syncthreads();
+            const float *Am = lds, *As = lds + L.arrFloats;
+            for (int i = 4 * lane; i < BS; i += 256) {
+                const f32x4 m = spec_ld4(Am, i), sd = spec_ld4(As, i);                   // ulcDecoder.c:281-289, on the coefficients
+                if (wv == 0) st4(pl + i, m.x + sd.x, m.y + sd.y, m.z + sd.z, m.w + sd.w);
+                else         st4(pl + i, m.x - sd.x, m.y - sd.y, m.z - sd.z, m.w - sd.w);
+            }
+        } else if (mine) {
+            for (int i = 4 * lane; i < BS; i += 256) { const f32x4 v = spec_ld4(A, i); st4(pl + i, v.x, v.y, v.z, v.w); }
+        }
+    } else {
+        float *A = lds;
+        if (wv == 0) dequant(ch0, A);
+        __syncthreads();
+        for (int i = 4 * tid; i < BS; i += 4 * WG) {
+            const f32x4 v = spec_ld4(A, i);
+            if (LR && pair) *(f32x4 *)(pl0 + i) = v;                                      // (read again below: not non-temporal)
+            else st4(pl0 + i, v.x, v.y, v.z, v.w);
+        }
+        if (!pair) return;
+        if (LR) __threadfence();
+        __syncthreads();                                                                  // the array is free again; LR: plane 0 is visible
+        if (wv == 0) dequant(ch0 + 1, A);
+        __syncthreads();
+        for (int i = 4 * tid; i < BS; i += 4 * WG) {
+            const f32x4 sd = spec_ld4(A, i);
+            if (LR) {
+                const f32x4 m = *(const f32x4 *)(pl0 + i);
+                st4(pl0 + i, m.x + sd.x, m.y + sd.y, m.z + sd.z, m.w + sd.w);
+                st4(pl1 + i, m.x - sd.x, m.y - sd.y, m.z - sd.z, m.w - sd.w);
+            } else st4(pl1 + i, sd.x, sd.y, sd.z, sd.w);
+        }
+    }
+}
+size_t ulcx_spec_lds_bytes(int BS) {
+    const SpecLds l = spec_lds(BS);
+    return sizeof(float) * (size_t)l.nArr * ((size_t)l.arrFloats + l.listInts);
+}
+
 size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds) {
     DsynLds l = dsyn_lds(BS, fast, twInLds);
     return sizeof(float) * ((size_t)l.zFloats + l.twFloats + l.listFloats);
@@ -1690,8 +1825,9 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds);
     const bool split = c.fastOK && aux.synGrid > 0;
     const bool samp = aux.sampStart != nullptr;                       // a sample-crop call: rows from (start, len) first, then the crop walk on them
-    const void *syn = c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp) : syn_fn<float>(c, split, c.range != 0, samp);
-    CK(allow_lds(syn, lds));
+    const bool spec = aux.specCoef != nullptr;                        // a spectra call: the crop walk, then k_dspec in place of the synthesis
+    const void *syn = spec ? nullptr : c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp) : syn_fn<float>(c, split, c.range != 0, samp);
+    if (syn) CK(allow_lds(syn, lds));
     if (samp) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, c.BS, aux.nSamples, aux.sampStart, aux.sampLen,
                                  aux.sampFirst, aux.sampCount, aux.sampSkip, aux.sampLenC);
     if (aux.nFiles > 0 && aux.payOffs) hipLaunchKernelGGL(k_dscan_crop_ragged, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount,
@@ -1701,7 +1837,17 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     if (ev) CK(hipEventRecord(ev[stage++], st));
-    if (!(ULCX_DBG(c) & 8)) {
+    if (spec) {
+        const void *fn = aux.specLR ? (const void *)k_dspec<true> : (const void *)k_dspec<false>;
+        const size_t slds = ulcx_spec_lds_bytes(c.BS);
+        const int nPairs = (c.C + 1) / 2;
+        const long long g = (long long)c.B * (c.K - 1) * nPairs;
+        if (g > 0x7FFFFFFFLL) { ulcx_set_error("spectra call: %lld workgroups", g); return ULCX_ERR_ARG; }
+        CK(allow_lds(fn, slds));
+        UlcxSpecArg sp = { aux.specCoef, aux.specWc, nPairs };
+        void *args[] = { &c, &sp };
+        CK(hipLaunchKernel(fn, dim3((unsigned)g), dim3(WG), args, slds, st));
+    } else if (!(ULCX_DBG(c) & 8)) {
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
         c.synFull = split ? aux.synFull : (c.range && c.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
         UlcxSampArg sa = { aux.sampSkip, aux.sampLenC, aux.nSamples };

@@ -230,6 +230,11 @@ struct UlcxDecAux {
     const int32_t *sampLen = nullptr;    // [c.B] samples wanted of each row, or NULL: nSamples
     int nSamples = 0;                    // samples per plane of the output
     int32_t *sampFirst = nullptr, *sampCount = nullptr, *sampSkip = nullptr, *sampLenC = nullptr;
+    // spectra (ulcx_decode_crops_spectra_*): specCoef != NULL - behind the crop walk k_dspec runs in place of the synthesis, one
+    // workgroup per (row, block, channel pair); synGrid / synFull are not looked at, c.pcm / c.pcm16 are both NULL
+    float *specCoef = nullptr;           // [c.B][C][c.K - 1][BS] dequantised coefficients, channels-first
+    int32_t *specWc = nullptr;           // [c.B][c.K - 1] window codes (0: the block is not live)
+    int specLR = 0;                      // channel pairs as m + s, m - s
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
@@ -243,6 +248,7 @@ int ulcx_index_begin_launch(int nRows, ulcx_index_entry *d_index, int indexStrid
 int ulcx_index_slots_launch(const UlcxDecCtx &c, int nRows, int nBlocks, const int32_t *d_bits, ulcx_index_entry *d_index, int indexStride,
                             int32_t *d_nBlocks, hipStream_t st);
 size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds);
+size_t ulcx_spec_lds_bytes(int BS);               // k_dspec's dynamic LDS: two unit arrays where a CU holds them, else one
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);

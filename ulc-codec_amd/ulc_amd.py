@@ -44,9 +44,12 @@ EXPORTS = [
     "ulcx_decode_crops_samples_ragged_dev", "ulcx_decode_crops_samples_ragged_dev_pcm16", "ulcx_decode_crops_samples_ragged_host",
     "ulcx_clip_blocks", "ulcx_encode_clips_dev", "ulcx_encode_clips_dev_pcm16", "ulcx_encode_clips_host",
     "ulcx_corpus_ragged_dev", "ulcx_corpus_ragged_host",
+    "ulcx_window_subblocks", "ulcx_decode_crops_spectra_dev", "ulcx_decode_crops_spectra_host",
+    "ulcx_decode_crops_spectra_ragged_dev", "ulcx_decode_crops_spectra_ragged_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
+SPECTRA_LR = 1                                             # ULCX_SPECTRA_LR: flags of the spectra calls
 
 # one entry of a block index (include/ulc_amd.h, ulcx_index_entry): 8 bytes
 INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
@@ -211,6 +214,18 @@ def lib():
                                                  C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             l.ulcx_corpus_ragged_host.argtypes = [C.c_int, C.c_int, _u8p, C.c_longlong, _i32p, C.c_void_p, C.c_int, _i32p,
                                                   _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p, _i64p]
+        if hasattr(l, "ulcx_decode_crops_spectra_dev"):    # spectra: dequantised coefficients of crop rows
+            l.ulcx_window_subblocks.argtypes = [C.c_int, C.c_int, _i32p]
+            l.ulcx_decode_crops_spectra_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]
+            l.ulcx_decode_crops_spectra_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i32p, C.c_void_p, C.c_int, _i32p,
+                                                         C.c_int, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p]
+            l.ulcx_decode_crops_spectra_ragged_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p]
+            l.ulcx_decode_crops_spectra_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p,
+                                                                C.c_int, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -251,6 +266,15 @@ def crop_blocks(block_size, n_samples):
     """Blocks a crop of n_samples samples touches at the worst start (ulcx_crop_blocks): a sample-crop call's d_bits row, and
     what max_blocks - 1 of its decoder must reach."""
     return int(lib().ulcx_crop_blocks(int(block_size), int(n_samples)))
+
+
+def window_subblocks(block_size, wc):
+    """Sizes, in coded order, of the sub-blocks of a block with window code `wc` (ulcx_window_subblocks; host arithmetic): how the
+    block_size coefficients of a spectra call's block split into shorter spectra.  () for a code no block can carry - 0, a block
+    that is not live, among them - or a bad block size."""
+    sizes = (C.c_int32 * 4)()
+    n = lib().ulcx_window_subblocks(int(block_size), int(wc), sizes)
+    return tuple(int(sizes[j]) for j in range(n))
 
 
 def clip_blocks(block_size, n_samples):
@@ -833,6 +857,64 @@ class BatchDecoder(_StreamSlots):
         _check(fn(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks, n, d_file, d_first,
                   d_count or None, n_blocks, d_pcm, d_bits, stream or None),
                "ulcx_decode_crops_ragged_dev_pcm16" if pcm16 else "ulcx_decode_crops_ragged_dev")
+
+    def decode_crops_spectra(self, payload, payload_bytes, index, index_blocks, files, first, n_blocks, count=None, flags=0):
+        """decode_crops() stopped in front of the inverse transform (ulcx_decode_crops_spectra_host): the dequantised MDCT
+        coefficients of the same rows, noise included -> (coef [n][C][n_blocks][BS], wc [n][n_blocks], bits [n][n_blocks]).
+        flags: 0, or SPECTRA_LR (channel pairs as m + s, m - s)."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        want = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+        F, stride = payload.shape
+        n = files.shape[0]
+        assert nbytes.shape == (F,) and index.shape[0] == F and blocks.shape == (F,) and first.shape == (n,)
+        assert want is None or want.shape == (n,)
+        coef = np.zeros((n, self.C, n_blocks, self.BS), np.float32)
+        wc = np.zeros((n, n_blocks), np.int32)
+        bits = np.zeros((n, n_blocks), np.int32)
+        _check(lib().ulcx_decode_crops_spectra_host(self.h, F, _p(payload, _u8p), stride, _p(nbytes, _i32p), index.ctypes.data, index.shape[1],
+                                                    _p(blocks, _i32p), n, _p(files, _i32p), _p(first, _i32p), _p(want, _i32p), n_blocks, int(flags),
+                                                    _p(coef, _f32p), _p(wc, _i32p), _p(bits, _i32p)), "ulcx_decode_crops_spectra_host")
+        return coef, wc, bits
+
+    def decode_crops_spectra_dev(self, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_first, d_count,
+                                 n_blocks, flags, d_coef, d_wc, d_bits, stream=0):
+        """Device form (d_count 0 / None: every row takes all n_blocks); d_coef float32 [n][C][n_blocks][BS], d_wc / d_bits [n][n_blocks]."""
+        _check(lib().ulcx_decode_crops_spectra_dev(self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file,
+                                                   d_first, d_count or None, n_blocks, int(flags), d_coef, d_wc, d_bits, stream or None),
+               "ulcx_decode_crops_spectra_dev")
+
+    def decode_crops_spectra_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, first, n_blocks, count=None, flags=0):
+        """decode_crops_spectra() of a ragged corpus, held as for decode_crops_ragged()."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        poffs = np.ascontiguousarray(payload_offs, dtype=np.int64)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE).reshape(-1)
+        ioffs = np.ascontiguousarray(index_offs, dtype=np.int64)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        want = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+        F, n = blocks.shape[0], files.shape[0]
+        assert poffs.shape == (F + 1,) and ioffs.shape == (F + 1,) and first.shape == (n,) and (want is None or want.shape == (n,))
+        coef = np.zeros((n, self.C, n_blocks, self.BS), np.float32)
+        wc = np.zeros((n, n_blocks), np.int32)
+        bits = np.zeros((n, n_blocks), np.int32)
+        _check(lib().ulcx_decode_crops_spectra_ragged_host(self.h, F, _p(payload, _u8p), payload.size, _p(poffs, _i64p), index.ctypes.data, index.size,
+                                                           _p(ioffs, _i64p), _p(blocks, _i32p), n, _p(files, _i32p), _p(first, _i32p), _p(want, _i32p),
+                                                           n_blocks, int(flags), _p(coef, _f32p), _p(wc, _i32p), _p(bits, _i32p)),
+               "ulcx_decode_crops_spectra_ragged_host")
+        return coef, wc, bits
+
+    def decode_crops_spectra_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
+                                        n, d_file, d_first, d_count, n_blocks, flags, d_coef, d_wc, d_bits, stream=0):
+        """Device form of a ragged corpus (d_count 0 / None: every row takes all n_blocks)."""
+        _check(lib().ulcx_decode_crops_spectra_ragged_dev(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs,
+                                                          d_index_blocks, n, d_file, d_first, d_count or None, n_blocks, int(flags), d_coef, d_wc, d_bits,
+                                                          stream or None), "ulcx_decode_crops_spectra_ragged_dev")
 
     def decode_crops_samples(self, payload, payload_bytes, index, index_blocks, files, start, n_samples, length=None):
         """Sample crops of a corpus held as for decode_crops(): row i is n_samples samples from sample start[i] (int64) of the
