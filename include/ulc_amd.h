@@ -130,7 +130,8 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  * ALIGNMENT.  The widest access a kernel makes to the buffer; every row of a buffer keeps it (rows are multiples of it).
  *   16 bytes  binary32 samples: d_pcm of the encode, analyse, decode, decode_packed, decode_range and decode_crops calls
  *             (16-byte loads of the transform's fold, 16-byte stores of the stereo synthesis)
- *             binary32 coefficients: d_coef of the spectra calls (ulcx_decode_crops_spectra_*: 16-byte stores)
+ *             binary32 coefficients: d_coef of the spectra calls (ulcx_decode_crops_spectra_*, ulcx_analyse_clips_*,
+ *             ulcx_encode_clips_spectra_*: 16-byte stores)
  *             saved stream records: d_state of the stream-slot entries (16-byte loads and stores)
  *    8 bytes  PCM16 samples: d_pcm16 of the same calls (four samples per load / store);
  *             rate tables: d_rate, and ulcx_rung::rate of the _dev ladder forms (one 8-byte entry per load)
@@ -813,6 +814,67 @@ int  ulcx_encode_clips_host(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mod
                             const float *h_pcm, const int32_t *h_len, int nSamples,
                             uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes, int32_t *h_maxBlock,
                             ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks);   /* synchronous */
+
+/* Clip spectra: the encoder's own MDCT coefficients of clips - the encode mirror of ulcx_decode_crops_spectra_*, and with it the
+ * clean half of a (coded spectrum, clean spectrum) pair on one grid: the same layout, under the window code the encoder chose for
+ * that very block.  Two families on the clips calls' rows (d_pcm / d_pcm16 [n][nChan][nSamples], d_len, nSamples: exactly as above,
+ * every row from a fresh state):
+ *   ulcx_analyse_clips_*         no rate, no decoder, no corpus: per chunk the analysis launch sequence of ulcx_analyse_dev (window
+ *                                control, the MDCT-only transform, the ordered sums)
+ *   ulcx_encode_clips_spectra_*  ulcx_encode_clips_* with the tap: the arguments of the clips call, then nBlocks .. d_cplx.  The
+ *                                corpus it writes is byte for byte and entry for entry the plain clips call's; window control and
+ *                                the transform run once for both outputs.
+ *   nBlocks  >= 1: the depth of the caller's planes, any value; ulcx_clip_blocks(BlockSize, nSamples) holds every row in full.
+ *            Block k of row i is LIVE when k < min(nBlocks, ulcx_clip_blocks(BlockSize, L_i)), L_i the clamped length.  Liveness
+ *            depends on the length alone, not on payloadStride / indexStride: a row truncated by capacity still has all its
+ *            spectra, and d_indexBlocks[i] tells how many of them have a coded partner.
+ *   d_coef   float32 [n][nChan][nBlocks][BlockSize], channels-first as the decode side's; required; written in full.  A live block
+ *            holds, bit for bit, what the reference encoder holds in TransformBuffer for channel ch after ULC_EncodeBlock_* of
+ *            block k of that clip (interleaved, then zeros) from a freshly created encoder: the normalised coefficients of the
+ *            mid / side channels, the block's sub-blocks in coded order.  A block that is not live is +0.0f, the planes behind the
+ *            call's last chunk included.
+ *   d_wc     optional, int32 [n][nBlocks]: State->WindowCtrl of the block, 0 where the block is not live.  This is the value
+ *            ulcx_decode_crops_spectra_* reports for that block of the encoded file - an un-decimated block: 0x10 | the overlap
+ *            scale; a decimated one: the low nybble with bit 3 set, the pattern in the high nybble - so
+ *            ulcx_window_subblocks(BlockSize, wc, sizes) splits both sides' blocks alike.
+ *   d_cplx   optional, float32 [n][nBlocks]: State->BlockComplexity after the block, +0.0f where the block is not live.
+ *   flags    0, or ULCX_SPECTRA_LR with the decode side's meaning: pairs (0,1), (2,3), ... come out as m + s and m - s, one
+ *            float32 addition or subtraction per coefficient, a trailing single channel untouched.  NOT a value the reference
+ *            holds.  Any other bit: ULCX_ERR_ARG.
+ * PAIRING.  ulcx_encode_clips_spectra_dev, then ulcx_decode_crops_spectra_dev on the corpus it wrote with d_file[i] = i and
+ * d_first[i] = 0 (a decoder of maxBlocksPerCall > nBlocks): block k of row i of the two d_coef arrays is the clean and the coded
+ * spectrum of the same block, and the two d_wc arrays agree, for every k < d_indexBlocks[i].
+ * STATE / ORDER: the clips call's rules.  No slot of enc is read or changed; everything is enqueued on hipStream and nothing
+ * waits for the device; the chunks are the clips call's, each followed by one more kernel (one workgroup per row, block and
+ * channel pair), and plane blocks behind the last chunk are zeroed by a last launch of it.  The staging of a chunk's window
+ * codes and complexities is the object's, allocated on the first such call; nothing is allocated afterwards.  After an analysis
+ * form the object is as ulcx_analyse_dev leaves it (ulcx_encoder_debug_fetch refuses, ulcx_encoder_last_rungs is 0), after an
+ * encode form as the clips call leaves it.
+ * The _dev forms refuse with ULCX_ERR_ARG before any device work what the clips call refuses (the analysis forms: without the
+ * rate, corpus and decoder checks), and: d_coef NULL or not aligned to 16 bytes, d_wc / d_cplx not aligned to 4, nBlocks < 1, a
+ * bad flag.  The host forms are synchronous, refuse what ulcx_encode_clips_host refuses, and stop at the longest row's last chunk. */
+int  ulcx_analyse_clips_dev(ulcx_encoder *enc, int n, const float *d_pcm /* [n][nChan][nSamples] */, const int32_t *d_len /* [n] or NULL */, int nSamples,
+                            int nBlocks, int flags, float *d_coef /* [n][nChan][nBlocks][BlockSize] */, int32_t *d_wc /* [n][nBlocks], optional */,
+                            float *d_cplx /* [n][nBlocks], optional */, void *hipStream);
+int  ulcx_analyse_clips_dev_pcm16(ulcx_encoder *enc, int n, const int16_t *d_pcm16, const int32_t *d_len, int nSamples,
+                                  int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_analyse_clips_host(ulcx_encoder *enc, int n, const float *h_pcm, const int32_t *h_len, int nSamples,
+                             int nBlocks, int flags, float *h_coef, int32_t *h_wc, float *h_cplx);   /* synchronous */
+int  ulcx_encode_clips_spectra_dev(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mode, float param0, float param1, const ulcx_rate *d_rate,
+                                   const float *d_pcm, const int32_t *d_len, int nSamples,
+                                   uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock,
+                                   ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks,
+                                   int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_encode_clips_spectra_dev_pcm16(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mode, float param0, float param1, const ulcx_rate *d_rate,
+                                         const int16_t *d_pcm16, const int32_t *d_len, int nSamples,
+                                         uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock,
+                                         ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks,
+                                         int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream);
+int  ulcx_encode_clips_spectra_host(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mode, float param0, float param1, const ulcx_rate *h_rate,
+                                    const float *h_pcm, const int32_t *h_len, int nSamples,
+                                    uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes, int32_t *h_maxBlock,
+                                    ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks,
+                                    int nBlocks, int flags, float *h_coef, int32_t *h_wc, float *h_cplx);   /* synchronous */
 
 /* Strided corpus -> ragged corpus on the device: the layout ulcx_decode_crops_ragged_* and ulcx_decode_crops_samples_ragged_* read,
  * from the strided one (a clip call's output, or any corpus held for ulcx_decode_crops_dev).  No object: `device` is the HIP ordinal.

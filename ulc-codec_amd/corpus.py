@@ -48,6 +48,37 @@ def sample_rows(start, length, block_size):
     return first, count, skip
 
 
+def clip_spectra(enc, wave, lengths=None, n_blocks=None, lr=False):
+    """The encoder's own MDCT coefficients of clips, without encoding them (ulcx_analyse_clips_dev): wave is a torch tensor
+    [n][C][T], float32 or int16, row i the clip wave[i, :, :lengths[i]] (lengths as from_clips takes them), each analysed from a
+    fresh state.  -> (coef float32 [n][C][n_blocks][BS], wc int32 [n][n_blocks], cplx float32 [n][n_blocks]) on wave's device,
+    enqueued on torch's current stream: the normalised coefficients of the mid / side channels (lr: left / right, m + s and m - s)
+    under the encoder's window code of that block - the layout of CropCorpus.spectra() - and zeros behind a row's last block.
+    n_blocks: the planes' depth (default: what holds T samples).  enc: a BatchEncoder with n_streams >= n; no slot of it changes."""
+    import torch
+    n, ch, T = wave.shape
+    if ch != enc.C:
+        raise UlcError(f"clip spectra: clips of {ch} channels, an encoder of {enc.BS} x {enc.C}")
+    dev = wave.device
+    pcm16 = wave.dtype == torch.int16
+    wave = wave.contiguous() if pcm16 else wave.to(torch.float32).contiguous()
+    want = None if lengths is None else torch.as_tensor(lengths, dtype=torch.int32, device=dev).contiguous()
+    depth = ulc_amd.clip_blocks(enc.BS, T) if n_blocks is None else int(n_blocks)
+    coef, wc, cplx = _spectra_planes(n, ch, depth, enc.BS, dev)
+    with torch.cuda.device(dev):
+        enc.analyse_clips_dev(n, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, depth, coef.data_ptr(), wc.data_ptr(), cplx.data_ptr(),
+                              flags=ulc_amd.SPECTRA_LR if lr else 0, stream=torch.cuda.current_stream(dev).cuda_stream, pcm16=pcm16)
+    return coef, wc, cplx
+
+
+def _spectra_planes(n, ch, depth, block_size, dev):
+    import torch
+    if depth < 1:
+        raise UlcError(f"clip spectra: n_blocks {depth}")
+    return (torch.empty((n, ch, depth, block_size), dtype=torch.float32, device=dev), torch.empty((n, depth), dtype=torch.int32, device=dev),
+            torch.empty((n, depth), dtype=torch.float32, device=dev))
+
+
 class CropCorpus:
     def __init__(self, n_chan, block_size, layout="strided"):
         if layout not in ("strided", "ragged"):
@@ -60,7 +91,15 @@ class CropCorpus:
         return self.n_files if self.frozen else len(self._payloads)
 
     @classmethod
-    def from_clips(cls, enc, dec, wave, lengths=None, rate=(ulc_amd.MODE_VBR, 50.0), layout="strided", payload_stride=None):
+    def from_clips_spectra(cls, enc, dec, wave, lengths=None, rate=(ulc_amd.MODE_VBR, 50.0), layout="strided", payload_stride=None,
+                           n_blocks=None, lr=False):
+        """from_clips() with the tap (ulcx_encode_clips_spectra_dev) -> (corpus, coef, wc, cplx): the same corpus, and the clean
+        spectra of the same blocks as clip_spectra() returns them, out of the same pass.  corpus.spectra(dec, arange(n), zeros(n),
+        n_blocks) then gives the coded spectra on the same grid: block k of row i pairs up for every k below the file's block count."""
+        return cls.from_clips(enc, dec, wave, lengths, rate, layout, payload_stride, _tap=(n_blocks, lr))
+
+    @classmethod
+    def from_clips(cls, enc, dec, wave, lengths=None, rate=(ulc_amd.MODE_VBR, 50.0), layout="strided", payload_stride=None, _tap=None):
         """A frozen corpus straight from waveforms on the device (ulcx_encode_clips_dev): wave is a torch tensor [n][C][T], float32
         or int16, row i the clip wave[i, :, :lengths[i]] (lengths: int32 [n] on the device or anything torch.as_tensor takes; None:
         every row T samples), each encoded from a fresh state.  rate: (mode, p0[, p1]) for every row, or a float32 [n][2] table
@@ -93,10 +132,19 @@ class CropCorpus:
         index = torch.empty((n, index_stride, 2), dtype=torch.int32, device=dev)
         blocks = torch.empty(n, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
+        planes = None
+        if _tap is not None:
+            depth = nb if _tap[0] is None else int(_tap[0])
+            planes = _spectra_planes(n, ch, depth, enc.BS, dev)
         with torch.cuda.device(dev):
-            enc.encode_clips_dev(dec, n, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, payload.data_ptr(), stride, nbytes.data_ptr(),
-                                 index.data_ptr(), index_stride, blocks.data_ptr(), mode=mode, p0=p0, p1=p1,
-                                 d_rates=table.data_ptr() if table is not None else 0, stream=stream, pcm16=pcm16)
+            args = (dec, n, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, payload.data_ptr(), stride, nbytes.data_ptr(),
+                    index.data_ptr(), index_stride, blocks.data_ptr())
+            kw = dict(mode=mode, p0=p0, p1=p1, d_rates=table.data_ptr() if table is not None else 0, stream=stream, pcm16=pcm16)
+            if planes is None:
+                enc.encode_clips_dev(*args, **kw)
+            else:
+                enc.encode_clips_spectra_dev(*args, depth, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
+                                             flags=ulc_amd.SPECTRA_LR if _tap[1] else 0, **kw)
             c.n_files, c.device = n, dev
             if not c.ragged:
                 c.stride, c.index_stride = stride, index_stride
@@ -118,7 +166,7 @@ class CropCorpus:
                 c.d_payload, c.d_payload_offs, c.d_index, c.d_index_offs, c.d_index_blocks = opay, poffs, oidx, ioffs, oblocks
                 # (the strided tensors go back to torch's allocator, which hands them out again on this stream only: behind the copy)
         c.frozen = True
-        return c
+        return c if planes is None else (c, *planes)
 
     def add_file(self, ulc_bytes, ulx_bytes=None):
         """-> the file's number.  Refuses (UlcError) another geometry than the corpus's, and a `.ulx` that is not this payload's:

@@ -86,6 +86,8 @@ struct ulcx_encoder {
     float *subHist = nullptr; UlcxWcState *subWcs = nullptr; int32_t *subSlots = nullptr;
     // clips (ulcx_encode_clips_*): one chunk of the call - [B][maxK] interleaved blocks, slots and sizes (allocated on the first clips call)
     float *clipPcm = nullptr; uint8_t *clipOut = nullptr; int32_t *clipBits = nullptr;
+    // clip spectra (ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*): the chunk's [B][maxK] window codes and complexities (allocated on the first such call)
+    int32_t *clipWc = nullptr; float *clipCplx = nullptr;
 };
 struct ulcx_decoder {
     int device = 0, B = 0, C = 0, BS = 0, maxK = 0;
@@ -734,6 +736,12 @@ extern "C" int ulcx_clip_blocks(int BlockSize, int nSamples) {
 }
 // the checks every clips entry makes, device or host pointers: the arguments, then (behind the device forms' alignment checks)
 // the objects - every other refusal needs none
+static int clips_rows_bad(const char *who, int n, const void *pcm, int nSamples) {
+    if (!pcm) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
+    if (nSamples < 1) { refuse(who, "bad argument (nSamples %d)", nSamples); return 1; }
+    if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
+    return 0;
+}
 static int clips_args_bad(const char *who, int n, int mode, const void *rate, const void *pcm, int nSamples,
                           const void *payload, long long payloadStride, const void *payloadBytes, const void *index, int indexStride, const void *indexBlocks) {
     if (!pcm || !payload || !payloadBytes || !index || !indexBlocks) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
@@ -743,60 +751,98 @@ static int clips_args_bad(const char *who, int n, int mode, const void *rate, co
     if (!rate && !mode_ok(mode)) { refuse(who, "bad mode"); return 1; }
     return 0;
 }
-static int clips_objects_bad(const char *who, const ulcx_encoder *e, const ulcx_decoder *dec, int n) {
+// dec == NULL passes with needDec false: the analysis forms have no decoder
+static int clips_objects_bad(const char *who, const ulcx_encoder *e, const ulcx_decoder *dec, int n, bool needDec = true) {
     if (!e) { refuse(who, "no encoder"); return 1; }
-    if (!dec) { refuse(who, "no decoder"); return 1; }
+    if (needDec && !dec) { refuse(who, "no decoder"); return 1; }
     if (n > e->B) { refuse(who, "bad argument (n %d: a call takes 1 .. nStreams = %d rows)", n, e->B); return 1; }
-    if (dec->C != e->C || dec->BS != e->BS || dec->device != e->device) {
+    if (needDec && (dec->C != e->C || dec->BS != e->BS || dec->device != e->device)) {
         refuse(who, "the decoder (%d x %d on device %d) is not of the encoder's geometry and device (%d x %d on %d)", dec->BS, dec->C, dec->device, e->BS, e->C, e->device);
         return 1;
     }
     return 0;
 }
-static int clips_staging(ulcx_encoder *e) {
+// The tap of ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*: the caller's planes, device or host pointers.  on == false: the
+// plain clips call.
+struct ClipSpec { bool on = false; int nBlocks = 0, flags = 0; float *coef = nullptr; int32_t *wc = nullptr; float *cplx = nullptr; };
+static int clip_spec_bad(const char *who, const ClipSpec &sp) {
+    if (!sp.on) return 0;
+    if (!sp.coef) { refuse(who, "bad argument (no coefficient planes)"); return 1; }
+    if (sp.nBlocks < 1) { refuse(who, "bad argument (nBlocks %d)", sp.nBlocks); return 1; }
+    if (sp.flags & ~ULCX_SPECTRA_LR) { refuse(who, "bad flags 0x%x", (unsigned)sp.flags); return 1; }
+    return 0;
+}
+// withOut: slots and sizes too (the analysis forms write none); withSpec: the chunk's window codes and complexities
+static int clips_staging(ulcx_encoder *e, bool withOut, bool withSpec) {
     const size_t nBlk = (size_t)e->B * e->maxK;
     int rc = enc_shadow(e);
     if (!rc && !e->clipPcm) rc = dalloc(e->allocs, &e->clipPcm, nBlk * (size_t)e->C * e->BS, false);
-    if (!rc && !e->clipOut) rc = dalloc(e->allocs, &e->clipOut, nBlk * e->ctx.slot, false);
-    if (!rc && !e->clipBits) rc = dalloc(e->allocs, &e->clipBits, nBlk, false);
+    if (!rc && withOut && !e->clipOut) rc = dalloc(e->allocs, &e->clipOut, nBlk * e->ctx.slot, false);
+    if (!rc && withOut && !e->clipBits) rc = dalloc(e->allocs, &e->clipBits, nBlk, false);
+    if (!rc && withSpec && !e->clipWc) rc = dalloc(e->allocs, &e->clipWc, nBlk, false);
+    if (!rc && withSpec && !e->clipCplx) rc = dalloc(e->allocs, &e->clipCplx, nBlk, false);
     return rc;
 }
-// chunkSamples: the longest row as far as the caller knows it (the _dev forms: nSamples) - the chunks stop behind its last block
+// The body of the three clips families.  chunkSamples: the longest row as far as the caller knows it (the _dev forms: nSamples) -
+// the chunks stop behind its last block.  analyse: ulcx_analyse_clips_* - no rate, decoder or corpus, the analysis launch sequence
+// per chunk.  sp.on: k_clip_spec behind every chunk's launch sequence, which then writes the chunk's window codes and
+// complexities into the object's staging; plane blocks behind the last chunk are one more launch of it with an empty chunk.
 static int encode_clips_any(const char *who, ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
                             const float *d_pcm, const int16_t *d_pcm16, const int32_t *d_len, int nSamples, int chunkSamples,
                             uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock,
-                            ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream) {
-    if (clips_args_bad(who, n, mode, d_rate, d_pcm ? (const void *)d_pcm : d_pcm16, nSamples, d_payload, payloadStride, d_payloadBytes,
-                       d_index, indexStride, d_indexBlocks)) return ULCX_ERR_ARG;
+                            ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream,
+                            bool analyse = false, const ClipSpec &sp = ClipSpec()) {
+    const void *pcm = d_pcm ? (const void *)d_pcm : d_pcm16;
+    if (analyse ? clips_rows_bad(who, n, pcm, nSamples)
+                : clips_args_bad(who, n, mode, d_rate, pcm, nSamples, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks)) return ULCX_ERR_ARG;
+    if (clip_spec_bad(who, sp)) return ULCX_ERR_ARG;
     // (a plane starts at any sample: the staging kernel uses wider loads only where the address allows them)
     if (misaligned(who, "d_pcm", d_pcm, (int)sizeof(float)) || misaligned(who, "d_pcm16", d_pcm16, (int)sizeof(int16_t)) ||
         misaligned(who, "d_rate", d_rate, ULCX_ALIGN_RATE) || misaligned(who, "d_len", d_len, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_maxBlock", d_maxBlock, ULCX_ALIGN_WORD) ||
-        misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) || misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
-    if (clips_objects_bad(who, e, dec, n)) return ULCX_ERR_ARG;
-    if ((long long)n * indexStride > (0x7FFFFFFFLL << 8)) return refuse(who, "%d rows of %d entries are more than one call takes", n, indexStride);
+        misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) || misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_coef", sp.coef, ULCX_ALIGN_PCM) || misaligned(who, "d_wc", sp.wc, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_cplx", sp.cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    if (clips_objects_bad(who, e, dec, n, !analyse)) return ULCX_ERR_ARG;
+    if (!analyse && (long long)n * indexStride > (0x7FFFFFFFLL << 8)) return refuse(who, "%d rows of %d entries are more than one call takes", n, indexStride);
     CKR(hipSetDevice(e->device));
-    int rc = clips_staging(e);
+    int rc = clips_staging(e, !analyse, sp.on);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)hipStream;
-    if ((rc = ulcx_clips_begin_launch(e->subHist, e->subWcs, n, e->C, e->BS, d_payloadBytes, d_maxBlock, st))) return rc;
-    if ((rc = ulcx_index_begin_launch(n, d_index, indexStride, d_indexBlocks, st))) return rc;
+    // (an analysis form has no byte counts: the begin kernel's zeros go to the window-code staging, which every chunk rewrites)
+    if ((rc = ulcx_clips_begin_launch(e->subHist, e->subWcs, n, e->C, e->BS, analyse ? e->clipWc : d_payloadBytes, d_maxBlock, st))) return rc;
+    if (!analyse && (rc = ulcx_index_begin_launch(n, d_index, indexStride, d_indexBlocks, st))) return rc;
     const int total = ulcx_clip_blocks(e->BS, chunkSamples);
+    const int lr = sp.flags & ULCX_SPECTRA_LR;
     int K = 0;
     for (int k0 = 0; k0 < total && rc == ULCX_OK; k0 += K) {
         K = total - k0 < e->maxK ? total - k0 : e->maxK;
         if ((rc = ulcx_clips_stage_launch(d_pcm, d_pcm16, d_len, nSamples, n, e->C, e->BS, k0, K, e->clipPcm, st))) break;
-        UlcxEncCtx c = enc_call_ctx(e, mode, p0, p1, d_rate, e->clipPcm, nullptr, K);
-        c.out = e->clipOut; c.bits = e->clipBits;
+        UlcxEncCtx c = analyse ? enc_call_ctx(e, ULCX_MODE_VBR, 100.0f, 0.0f, nullptr, e->clipPcm, nullptr, K)
+                               : enc_call_ctx(e, mode, p0, p1, d_rate, e->clipPcm, nullptr, K);
+        if (!analyse) { c.out = e->clipOut; c.bits = e->clipBits; }
+        if (sp.on) { c.wcOut = e->clipWc; c.cplxOut = e->clipCplx; }
         c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
-        if ((rc = ulcx_enc_launch(c, st, e->timing ? e->ev : nullptr, enc_aux(e, K)))) break;
+        if (analyse) rc = ulcx_analyse_launch(c, st, e->timing ? e->ev : nullptr, enc_aux(e, K), e->analyseKxf);
+        else rc = ulcx_enc_launch(c, st, e->timing ? e->ev : nullptr, enc_aux(e, K));
+        if (rc) break;
+        if (sp.on && (rc = ulcx_clips_spec_launch(n, K, k0, sp.nBlocks - k0 < K ? sp.nBlocks - k0 : K, e->C, e->BS, nSamples, d_len, c.coef, e->clipWc, e->clipCplx,
+                                                  sp.nBlocks, lr, sp.coef, sp.wc, sp.cplx, st))) break;
+        if (analyse) continue;
         if ((rc = ulcx_clips_append_launch(n, K, k0, e->BS, nSamples, d_len, c.slot, e->clipOut, e->clipBits, d_payload, payloadStride, d_payloadBytes, d_maxBlock,
                                            indexStride, d_indexBlocks, st))) break;
         UlcxDecCtx dc = dec->ctx;
         dc.in = e->clipOut; dc.slot = c.slot; dc.inBytes = (long long)n * K * c.slot;
         rc = ulcx_index_slots_launch(dc, n, K, e->clipBits, d_index, indexStride, d_indexBlocks, st);
     }
-    return K ? enc_call_done(e, rc, K, false, 1) : rc;
+    if (sp.on && rc == ULCX_OK && total < sp.nBlocks)
+        rc = ulcx_clips_spec_launch(n, 0, total, sp.nBlocks - total, e->C, e->BS, nSamples, d_len, e->ctx.coef, e->clipWc, e->clipCplx,
+                                    sp.nBlocks, lr, sp.coef, sp.wc, sp.cplx, st);
+    return K ? enc_call_done(e, rc, K, analyse, analyse ? 0 : 1) : rc;
+}
+static ClipSpec clip_spec(int nBlocks, int flags, float *coef, int32_t *wc, float *cplx) {
+    ClipSpec sp; sp.on = true; sp.nBlocks = nBlocks; sp.flags = flags; sp.coef = coef; sp.wc = wc; sp.cplx = cplx;
+    return sp;
 }
 extern "C" int ulcx_encode_clips_dev(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
                                      const float *d_pcm, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
@@ -810,14 +856,39 @@ extern "C" int ulcx_encode_clips_dev_pcm16(ulcx_encoder *e, ulcx_decoder *dec, i
     return encode_clips_any("ulcx_encode_clips_dev_pcm16", e, dec, n, mode, p0, p1, d_rate, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
                             d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream);
 }
-// The host form: every check first, then everything up into buffers of the call's own, the body on the null stream with the
-// longest row's length, one synchronisation, and down: counts, index, and of every payload the bytes that are defined.
-extern "C" int ulcx_encode_clips_host(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
-                                      const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
-                                      int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks) {
-    const char *who = "ulcx_encode_clips_host";
-    if (clips_args_bad(who, n, mode, h_rate, h_pcm, nSamples, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks) ||
-        clips_objects_bad(who, e, dec, n)) return ULCX_ERR_ARG;
+extern "C" int ulcx_encode_clips_spectra_dev(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
+                                             const float *d_pcm, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
+                                             int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks,
+                                             int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_clips_any("ulcx_encode_clips_spectra_dev", e, dec, n, mode, p0, p1, d_rate, d_pcm, nullptr, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream, false, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+}
+extern "C" int ulcx_encode_clips_spectra_dev_pcm16(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
+                                                   const int16_t *d_pcm16, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride,
+                                                   int32_t *d_payloadBytes, int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks,
+                                                   int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_clips_any("ulcx_encode_clips_spectra_dev_pcm16", e, dec, n, mode, p0, p1, d_rate, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream, false, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+}
+extern "C" int ulcx_analyse_clips_dev(ulcx_encoder *e, int n, const float *d_pcm, const int32_t *d_len, int nSamples,
+                                      int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_clips_any("ulcx_analyse_clips_dev", e, nullptr, n, 0, 0.0f, 0.0f, nullptr, d_pcm, nullptr, d_len, nSamples, nSamples, nullptr, 0,
+                            nullptr, nullptr, nullptr, 0, nullptr, hipStream, true, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+}
+extern "C" int ulcx_analyse_clips_dev_pcm16(ulcx_encoder *e, int n, const int16_t *d_pcm16, const int32_t *d_len, int nSamples,
+                                            int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
+    return encode_clips_any("ulcx_analyse_clips_dev_pcm16", e, nullptr, n, 0, 0.0f, 0.0f, nullptr, nullptr, d_pcm16, d_len, nSamples, nSamples, nullptr, 0,
+                            nullptr, nullptr, nullptr, 0, nullptr, hipStream, true, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+}
+// The host forms: every check first, then everything up into buffers of the call's own, the body on the null stream with the
+// longest row's length, one synchronisation, and down: counts, index, and of every payload the bytes that are defined; the
+// planes of a spectra form in full.  analyse: no rate, decoder or corpus.
+static int encode_clips_host_any(const char *who, ulcx_encoder *e, ulcx_decoder *dec, bool analyse, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
+                                 const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
+                                 int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks, const ClipSpec &sp) {
+    if ((analyse ? clips_rows_bad(who, n, h_pcm, nSamples)
+                 : clips_args_bad(who, n, mode, h_rate, h_pcm, nSamples, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks)) ||
+        clip_spec_bad(who, sp) || clips_objects_bad(who, e, dec, n, !analyse)) return ULCX_ERR_ARG;
     int longest = h_len ? 0 : nSamples;
     for (int i = 0; h_len && i < n; i++) {
         if (h_len[i] < 0) return refuse(who, "row %d has %d samples", i, (int)h_len[i]);
@@ -827,17 +898,34 @@ extern "C" int ulcx_encode_clips_host(ulcx_encoder *e, ulcx_decoder *dec, int n,
     if (h_rate && rate_table_bad(who, "invalid entry for row", h_rate, n)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     const size_t nPcm = (size_t)n * e->C * (size_t)nSamples, nEnt = (size_t)n * (size_t)indexStride;
+    const size_t nPlane = (size_t)n * (size_t)sp.nBlocks, nCoef = nPlane * (size_t)e->C * e->BS;
     DevTmp t; float *dpcm = nullptr; int32_t *dlen = nullptr, *dbytes = nullptr, *dmax = nullptr, *dcnt = nullptr; ulcx_rate *drate = nullptr;
     uint8_t *dpay = nullptr; ulcx_index_entry *di = nullptr;
-    CKR(t.get(&dpcm, sizeof(float) * nPcm)); CKR(t.get(&dpay, (size_t)n * (size_t)payloadStride));
-    CKR(t.get(&dbytes, sizeof(int32_t) * n)); CKR(t.get(&dmax, sizeof(int32_t) * n)); CKR(t.get(&dcnt, sizeof(int32_t) * n));
-    CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    ClipSpec dsp = sp;
+    CKR(t.get(&dpcm, sizeof(float) * nPcm));
+    if (!analyse) {
+        CKR(t.get(&dpay, (size_t)n * (size_t)payloadStride));
+        CKR(t.get(&dbytes, sizeof(int32_t) * n)); CKR(t.get(&dmax, sizeof(int32_t) * n)); CKR(t.get(&dcnt, sizeof(int32_t) * n));
+        CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    }
+    if (sp.on) {
+        CKR(t.get(&dsp.coef, sizeof(float) * nCoef));
+        if (sp.wc) CKR(t.get(&dsp.wc, sizeof(int32_t) * nPlane));
+        if (sp.cplx) CKR(t.get(&dsp.cplx, sizeof(float) * nPlane));
+    }
     CKR(hipMemcpy(dpcm, h_pcm, sizeof(float) * nPcm, hipMemcpyHostToDevice));
     if (h_len) { CKR(t.get(&dlen, sizeof(int32_t) * n)); CKR(hipMemcpy(dlen, h_len, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
     if (h_rate) { CKR(t.get(&drate, sizeof(ulcx_rate) * n)); CKR(hipMemcpy(drate, h_rate, sizeof(ulcx_rate) * n, hipMemcpyHostToDevice)); }
-    const int rc = encode_clips_any(who, e, dec, n, mode, p0, p1, drate, dpcm, nullptr, dlen, nSamples, longest, dpay, payloadStride, dbytes, dmax, di, indexStride, dcnt, nullptr);
+    const int rc = encode_clips_any(who, e, dec, n, mode, p0, p1, drate, dpcm, nullptr, dlen, nSamples, longest, dpay, payloadStride, dbytes, dmax, di, indexStride, dcnt, nullptr,
+                                    analyse, dsp);
     if (rc) return rc;
     CKR(hipDeviceSynchronize());
+    if (sp.on) {
+        CKR(hipMemcpy(sp.coef, dsp.coef, sizeof(float) * nCoef, hipMemcpyDeviceToHost));
+        if (sp.wc) CKR(hipMemcpy(sp.wc, dsp.wc, sizeof(int32_t) * nPlane, hipMemcpyDeviceToHost));
+        if (sp.cplx) CKR(hipMemcpy(sp.cplx, dsp.cplx, sizeof(float) * nPlane, hipMemcpyDeviceToHost));
+    }
+    if (analyse) return ULCX_OK;
     CKR(hipMemcpy(h_payloadBytes, dbytes, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     if (h_maxBlock) CKR(hipMemcpy(h_maxBlock, dmax, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     CKR(hipMemcpy(h_indexBlocks, dcnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
@@ -845,6 +933,24 @@ extern "C" int ulcx_encode_clips_host(ulcx_encoder *e, ulcx_decoder *dec, int n,
     for (int i = 0; i < n; i++)
         if (h_payloadBytes[i] > 0) CKR(hipMemcpy(h_payload + (size_t)i * (size_t)payloadStride, dpay + (size_t)i * (size_t)payloadStride, (size_t)h_payloadBytes[i], hipMemcpyDeviceToHost));
     return ULCX_OK;
+}
+extern "C" int ulcx_encode_clips_host(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
+                                      const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
+                                      int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks) {
+    return encode_clips_host_any("ulcx_encode_clips_host", e, dec, false, n, mode, p0, p1, h_rate, h_pcm, h_len, nSamples, h_payload, payloadStride, h_payloadBytes,
+                                 h_maxBlock, h_index, indexStride, h_indexBlocks, ClipSpec());
+}
+extern "C" int ulcx_encode_clips_spectra_host(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
+                                              const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
+                                              int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks,
+                                              int nBlocks, int flags, float *h_coef, int32_t *h_wc, float *h_cplx) {
+    return encode_clips_host_any("ulcx_encode_clips_spectra_host", e, dec, false, n, mode, p0, p1, h_rate, h_pcm, h_len, nSamples, h_payload, payloadStride, h_payloadBytes,
+                                 h_maxBlock, h_index, indexStride, h_indexBlocks, clip_spec(nBlocks, flags, h_coef, h_wc, h_cplx));
+}
+extern "C" int ulcx_analyse_clips_host(ulcx_encoder *e, int n, const float *h_pcm, const int32_t *h_len, int nSamples,
+                                       int nBlocks, int flags, float *h_coef, int32_t *h_wc, float *h_cplx) {
+    return encode_clips_host_any("ulcx_analyse_clips_host", e, nullptr, true, n, 0, 0.0f, 0.0f, nullptr, h_pcm, h_len, nSamples, nullptr, 0, nullptr,
+                                 nullptr, nullptr, 0, nullptr, clip_spec(nBlocks, flags, h_coef, h_wc, h_cplx));
 }
 
 // ---- strided corpus -> ragged corpus (include/ulc_amd.h section 3): no object; two kernels of ulcx_clips.hip

@@ -9,6 +9,8 @@
 //                    behind the capacity rule: blocks that do not fit) keep their size, every other size becomes 0; the kept
 //                    slots' bytes go behind the row's running payload
 // The index of the chunk is then ulcx_index_slots_dev's two kernels on the masked sizes (ulcx_dec.hip).
+// ulcx_analyse_clips_* / ulcx_encode_clips_spectra_* add k_clip_spec behind the launch sequence: the chunk's MDCT coefficients,
+// window codes and complexities into the caller's channels-first planes.
 //
 // ulcx_corpus_ragged_*: k_corpus_offsets (one workgroup: the two exclusive int64 prefix sums, the first file that does not
 // fit, the totals) and k_corpus_copy (a file per workgroup).
@@ -138,6 +140,44 @@ __global__ __launch_bounds__(CLIP_WG) void k_clip_append(int K, int k0, int BS, 
     if (tid == 0) { payBytes[i] = (int32_t)off; if (maxBlock) maxBlock[i] = mx; }
 }
 
+// The tap of ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*.  One workgroup per (row, block of the launch, channel pair):
+// the pair's two BS runs of the chunk's coef [n][K][C][BS] (what the transform left for blocks [k0, k0 + K) of every row) go to
+// plane position k0 + k of out [n][C][nBlocks][BS], m + s / m - s under LR (a trailing single channel as it is).  Both sides are
+// touched once: 16-byte loads and stores with the non-temporal hint, a lane's accesses 16 bytes from its neighbour's.  A block
+// that is not the clip's (block number at or behind nb_i, from d_len on the device) or that no chunk holds (k >= K: the planes
+// behind the call's last chunk) is zeros.  The pair-0 workgroup also moves the block's wc / cplx from [n][K] to [n][nBlocks].
+// The launch covers plane blocks below nBlocks only (kOut), so nothing is written outside the planes.
+typedef float clip_f4 __attribute__((ext_vector_type(4)));
+template <bool LR>
+__global__ __launch_bounds__(CLIP_WG) void k_clip_spec(int K, int k0, int kOut, int C, int BS, int nSamples, const int32_t *len, const float *coef,
+                                                       const int32_t *wcIn, const float *cplxIn, int nBlocks, float *out, int32_t *wcOut, float *cplxOut) {
+    const int pairs = (C + 1) >> 1, tid = threadIdx.x;
+    const unsigned b = blockIdx.x;
+    const int pair = (int)(b % (unsigned)pairs), k = (int)((b / (unsigned)pairs) % (unsigned)kOut), i = (int)(b / ((unsigned)pairs * (unsigned)kOut));
+    const int g = k0 + k, ch = 2 * pair, vecs = BS >> 2;
+    const bool two = ch + 1 < C;
+    const bool live = k < K && g < clip_blocks(BS, clip_len(len, i, nSamples));
+    const clip_f4 *src = (const clip_f4 *)(coef + (((size_t)i * K + k) * C + ch) * (size_t)BS);       // (read for a live block only)
+    clip_f4 *dst0 = (clip_f4 *)(out + (((size_t)i * C + ch) * nBlocks + g) * (size_t)BS), *dst1 = dst0 + (size_t)nBlocks * vecs;
+    const clip_f4 zero = { 0.0f, 0.0f, 0.0f, 0.0f };
+    for (int v = tid; v < vecs; v += CLIP_WG) {
+        clip_f4 x = zero, y = zero;
+        if (live) {
+            x = __builtin_nontemporal_load(src + v);
+            if (two) {
+                y = __builtin_nontemporal_load(src + vecs + v);
+                if (LR) { const clip_f4 m = x, s = y; x = m + s; y = m - s; }
+            }
+        }
+        __builtin_nontemporal_store(x, dst0 + v);
+        if (two) __builtin_nontemporal_store(y, dst1 + v);
+    }
+    if (pair == 0 && tid == 0) {
+        if (wcOut) wcOut[(size_t)i * nBlocks + g] = live ? wcIn[(size_t)i * K + k] : 0;
+        if (cplxOut) cplxOut[(size_t)i * nBlocks + g] = live ? cplxIn[(size_t)i * K + k] : 0.0f;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Strided corpus -> ragged corpus
 // ---------------------------------------------------------------------------
@@ -248,6 +288,17 @@ int ulcx_clips_append_launch(int n, int K, int k0, int BS, int nSamples, const i
                              hipStream_t st) {
     hipLaunchKernelGGL(k_clip_append, dim3(n), dim3(CLIP_WG), 0, st, K, k0, BS, nSamples, d_len, slot, slots, bits, d_payload, stride, d_payloadBytes, d_maxBlock,
                        indexStride, d_indexBlocks);
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+int ulcx_clips_spec_launch(int n, int K, int k0, int kOut, int C, int BS, int nSamples, const int32_t *d_len, const float *coef, const int32_t *wc,
+                           const float *cplx, int nBlocks, int lr, float *d_coef, int32_t *d_wc, float *d_cplx, hipStream_t st) {
+    if (kOut < 1) return ULCX_OK;
+    if (k0 < 0 || (long long)k0 + kOut > nBlocks) { ulcx_set_error("ulcx_clips_spec_launch: blocks %d + %d of planes %d deep", k0, kOut, nBlocks); return ULCX_ERR_ARG; }
+    const long long wgs = (long long)n * kOut * ((C + 1) / 2);
+    if (wgs > 0x7FFFFFFFLL) { ulcx_set_error("clip spectra: %d rows of %d blocks are more than one launch takes", n, kOut); return ULCX_ERR_ARG; }
+    if (lr) hipLaunchKernelGGL(k_clip_spec<true>, dim3((unsigned)wgs), dim3(CLIP_WG), 0, st, K, k0, kOut, C, BS, nSamples, d_len, coef, wc, cplx, nBlocks, d_coef, d_wc, d_cplx);
+    else hipLaunchKernelGGL(k_clip_spec<false>, dim3((unsigned)wgs), dim3(CLIP_WG), 0, st, K, k0, kOut, C, BS, nSamples, d_len, coef, wc, cplx, nBlocks, d_coef, d_wc, d_cplx);
     CK(hipGetLastError());
     return ULCX_OK;
 }

@@ -261,6 +261,10 @@ int ulcx_clips_stage_launch(const float *d_pcm, const int16_t *d_pcm16, const in
 int ulcx_clips_append_launch(int n, int K, int k0, int BS, int nSamples, const int32_t *d_len, int slot, const uint8_t *slots, int32_t *bits,
                              uint8_t *d_payload, long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, int indexStride, const int32_t *d_indexBlocks,
                              hipStream_t st);
+// the tap of ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*: blocks [k0, k0 + kOut) of every row's planes (k0 + kOut <= nBlocks)
+// from the chunk's coef [n][K][C][BS], wc [n][K] and cplx [n][K]; a block at or behind K, or behind the row's own count, is zeros
+int ulcx_clips_spec_launch(int n, int K, int k0, int kOut, int C, int BS, int nSamples, const int32_t *d_len, const float *coef, const int32_t *wc,
+                           const float *cplx, int nBlocks, int lr, float *d_coef, int32_t *d_wc, float *d_cplx, hipStream_t st);
 // strided corpus -> ragged corpus (ulcx_clips.hip): the offsets, then a file per workgroup
 int ulcx_corpus_ragged_launch(int nFiles, const uint8_t *d_payload, long long stride, const int32_t *d_payloadBytes, const ulcx_index_entry *d_index,
                               int indexStride, const int32_t *d_indexBlocks, uint8_t *d_outPayload, long long payloadCap, int64_t *d_payloadOffs,

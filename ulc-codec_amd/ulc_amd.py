@@ -46,6 +46,8 @@ EXPORTS = [
     "ulcx_corpus_ragged_dev", "ulcx_corpus_ragged_host",
     "ulcx_window_subblocks", "ulcx_decode_crops_spectra_dev", "ulcx_decode_crops_spectra_host",
     "ulcx_decode_crops_spectra_ragged_dev", "ulcx_decode_crops_spectra_ragged_host",
+    "ulcx_analyse_clips_dev", "ulcx_analyse_clips_dev_pcm16", "ulcx_analyse_clips_host",
+    "ulcx_encode_clips_spectra_dev", "ulcx_encode_clips_spectra_dev_pcm16", "ulcx_encode_clips_spectra_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -226,6 +228,15 @@ def lib():
                                                                C.c_void_p, C.c_void_p]
             l.ulcx_decode_crops_spectra_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p,
                                                                 C.c_int, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p]
+        if hasattr(l, "ulcx_analyse_clips_dev"):           # clip spectra: the encoder's MDCT coefficients of clips
+            tap_dev = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]            # nBlocks, flags, d_coef, d_wc, d_cplx
+            tap_host = [C.c_int, C.c_int, _f32p, _i32p, _f32p]
+            l.ulcx_analyse_clips_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + tap_dev + [C.c_void_p]
+            l.ulcx_analyse_clips_dev_pcm16.argtypes = l.ulcx_analyse_clips_dev.argtypes
+            l.ulcx_analyse_clips_host.argtypes = [C.c_void_p, C.c_int, _f32p, _i32p, C.c_int] + tap_host
+            l.ulcx_encode_clips_spectra_dev.argtypes = l.ulcx_encode_clips_dev.argtypes[:-1] + tap_dev + [C.c_void_p]
+            l.ulcx_encode_clips_spectra_dev_pcm16.argtypes = l.ulcx_encode_clips_spectra_dev.argtypes
+            l.ulcx_encode_clips_spectra_host.argtypes = l.ulcx_encode_clips_host.argtypes + tap_host
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -591,6 +602,69 @@ class BatchEncoder(_StreamSlots):
                                             payload_stride, _p(nbytes, _i32p), _p(maxb, _i32p), index.ctypes.data, index_stride, _p(count, _i32p)),
                "ulcx_encode_clips_host")
         return payload, nbytes, maxb, index, count
+
+    def encode_clips_spectra_dev(self, dec, n, d_pcm, d_len, n_samples, d_payload, payload_stride, d_payload_bytes, d_index, index_stride, d_index_blocks,
+                                 n_blocks, d_coef, d_wc=0, d_cplx=0, flags=0, d_max_block=0, mode=MODE_VBR, p0=50.0, p1=0.0, d_rates=0, stream=0,
+                                 pcm16=False):
+        """encode_clips_dev() with the tap (ulcx_encode_clips_spectra_dev): the same corpus, and the encoder's own MDCT coefficients
+        of the same blocks in d_coef float32 [n][C][n_blocks][BS], their window codes in d_wc int32 [n][n_blocks] and block
+        complexities in d_cplx float32 [n][n_blocks] (0: not wanted).  flags: 0, or SPECTRA_LR."""
+        fn = lib().ulcx_encode_clips_spectra_dev_pcm16 if pcm16 else lib().ulcx_encode_clips_spectra_dev
+        _check(fn(self.h, dec.h, n, mode, p0, p1, d_rates or None, d_pcm, d_len or None, n_samples, d_payload, payload_stride, d_payload_bytes,
+                  d_max_block or None, d_index, index_stride, d_index_blocks, n_blocks, flags, d_coef or None, d_wc or None, d_cplx or None,
+                  stream or None), "ulcx_encode_clips_spectra_dev_pcm16" if pcm16 else "ulcx_encode_clips_spectra_dev")
+
+    def encode_clips_spectra(self, dec, wave, lengths=None, n_blocks=None, flags=0, mode=MODE_VBR, p0=50.0, p1=0.0, rates=None,
+                             payload_stride=None, index_stride=None):
+        """Host form (ulcx_encode_clips_spectra_host): encode_clips()'s arguments and results, followed by
+        (coef float32 [n][C][n_blocks][BS], wc int32 [n][n_blocks], cplx float32 [n][n_blocks]); n_blocks None: every row in full."""
+        wave = np.ascontiguousarray(wave, dtype=np.float32)
+        n, ch, T = wave.shape
+        assert ch == self.C
+        want = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        assert want is None or want.shape == (n,)
+        if rates is not None:
+            rates = np.ascontiguousarray(rates, dtype=np.float32)
+            assert rates.shape == (n, 2)
+        nb = clip_blocks(self.BS, T)
+        depth = nb if n_blocks is None else int(n_blocks)
+        payload_stride = payload_stride or self.slot * nb
+        index_stride = index_stride or nb + 1
+        payload = np.zeros((n, payload_stride), np.uint8)
+        nbytes, maxb, count = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        index = np.zeros((n, index_stride), INDEX_DTYPE)
+        coef = np.zeros((n, self.C, max(depth, 0), self.BS), np.float32)
+        wc = np.zeros((n, max(depth, 0)), np.int32)
+        cplx = np.zeros((n, max(depth, 0)), np.float32)
+        _check(lib().ulcx_encode_clips_spectra_host(self.h, dec.h, n, mode, p0, p1, _p(rates, _f32p), _p(wave, _f32p), _p(want, _i32p), T, _p(payload, _u8p),
+                                                    payload_stride, _p(nbytes, _i32p), _p(maxb, _i32p), index.ctypes.data, index_stride, _p(count, _i32p),
+                                                    depth, flags, _p(coef, _f32p), _p(wc, _i32p), _p(cplx, _f32p)),
+               "ulcx_encode_clips_spectra_host")
+        return payload, nbytes, maxb, index, count, coef, wc, cplx
+
+    def analyse_clips_dev(self, n, d_pcm, d_len, n_samples, n_blocks, d_coef, d_wc=0, d_cplx=0, flags=0, stream=0, pcm16=False):
+        """The encoder's MDCT coefficients of clips without encoding them (ulcx_analyse_clips_dev), asynchronous on `stream`:
+        d_pcm [n][C][n_samples] (int16 with pcm16), d_len int32 [n] or 0 -> d_coef float32 [n][C][n_blocks][BS], d_wc int32
+        [n][n_blocks], d_cplx float32 [n][n_blocks] (0: not wanted).  No slot of the encoder is read or changed."""
+        fn = lib().ulcx_analyse_clips_dev_pcm16 if pcm16 else lib().ulcx_analyse_clips_dev
+        _check(fn(self.h, n, d_pcm, d_len or None, n_samples, n_blocks, flags, d_coef or None, d_wc or None, d_cplx or None, stream or None),
+               "ulcx_analyse_clips_dev_pcm16" if pcm16 else "ulcx_analyse_clips_dev")
+
+    def analyse_clips(self, wave, lengths=None, n_blocks=None, flags=0):
+        """Host form (ulcx_analyse_clips_host): wave float32 [n][C][T], lengths [n] or None
+        -> (coef float32 [n][C][n_blocks][BS], wc int32 [n][n_blocks], cplx float32 [n][n_blocks]); n_blocks None: every row in full."""
+        wave = np.ascontiguousarray(wave, dtype=np.float32)
+        n, ch, T = wave.shape
+        assert ch == self.C
+        want = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        assert want is None or want.shape == (n,)
+        depth = clip_blocks(self.BS, T) if n_blocks is None else int(n_blocks)
+        coef = np.zeros((n, self.C, max(depth, 0), self.BS), np.float32)
+        wc = np.zeros((n, max(depth, 0)), np.int32)
+        cplx = np.zeros((n, max(depth, 0)), np.float32)
+        _check(lib().ulcx_analyse_clips_host(self.h, n, _p(wave, _f32p), _p(want, _i32p), T, depth, flags, _p(coef, _f32p), _p(wc, _i32p), _p(cplx, _f32p)),
+               "ulcx_analyse_clips_host")
+        return coef, wc, cplx
 
     def analyse_subset_dev(self, d_slots, n, d_pcm, n_blocks, d_wc=0, d_cplx=0, stream=0):
         _check(lib().ulcx_analyse_dev_subset(self.h, d_slots, n, d_pcm, n_blocks, d_wc or None, d_cplx or None, stream or None),
