@@ -793,7 +793,8 @@ int  ulcx_decoder_set_resident_index(ulcx_decoder *dec, const ulcx_index_entry *
  * STATE.  The call reads and changes no slot of enc and no stream state of dec: it runs the plain call's launch sequence on the
  * subset calls' shadow state, reset to the state right after create, and scatters nothing back.  It mixes freely with streaming,
  * subset, ladder and analysis calls on the object; a refused call leaves everything as it was.  The staging of the call (one chunk
- * of interleaved input, slots and sizes) is the object's, allocated on the first clips call; nothing is allocated afterwards.
+ * of interleaved input, slots and sizes) is the object's, allocated on the first clips call; nothing is allocated afterwards (but by a clips
+ * ladder call of more rungs, below).
  * ORDER.  Everything is enqueued on hipStream and nothing waits for the device: ceil(ulcx_clip_blocks(BlockSize, nSamples) /
  * maxBlocksPerCall) chunks of (stage, the launch sequence, append, index).  Rows that have ended go on encoding silence that is
  * masked; the encoder is causal in its input, so the chunking changes no byte.
@@ -814,6 +815,56 @@ int  ulcx_encode_clips_host(ulcx_encoder *enc, ulcx_decoder *dec, int n, int mod
                             const float *h_pcm, const int32_t *h_len, int nSamples,
                             uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes, int32_t *h_maxBlock,
                             ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks);   /* synchronous */
+
+/* Clips ladder: the clips call under nRungs rate settings in ONE call - the same clip at several rates, two-pass ABR included.
+ * Rows (d_pcm / d_pcm16, d_len, nSamples, ulcx_clip_blocks) and dec are exactly the clips call's; rungs are ulcx_rung as
+ * ulcx_encode_dev_ladder takes them with nStreams read as n (a table rung: a DEVICE table [n]; a host table in the host form).
+ * Staging, window control, transform, complexity, Bark levels and noise spectrum run once per chunk, selection and writer once
+ * per rung (the ladder's launch sequence on the shadow state), then one append and one index launch over all files.
+ * OUTPUT.  One corpus of nRungs * n files: file r * n + i is clip i under rung r - its payload at d_payload + (r * n + i) *
+ * payloadStride, its index row d_index[r * n + i], its counts at [r * n + i] of d_payloadBytes / d_maxBlock / d_indexBlocks.  The
+ * crop calls take it as it is (nFiles = nRungs * n, d_file = r * n + i).  Every file is byte for byte and entry for entry what
+ * ulcx_encode_clips_dev writes for that clip under rung r's setting; with one rung without AUTO the call writes what the plain
+ * clips call writes.
+ * CAPACITY.  The clips call's rule per FILE: rung r of row i keeps its leading whole blocks that fit payloadStride and
+ * indexStride - 1, whatever the other rungs of that row keep (a high-rate rung may stop blocks before a low-rate one).
+ * ULCX_RUNG_AUTO in ulcx_rung::reserved - the tool's `RATE,auto` (cli/ulcx_tool.c; tools/ulcEncodeTool.c:130,164,178).  In front of
+ * the encode ONE analysis pass over all chunks runs (the launch sequence of ulcx_analyse_clips_* on the freshly reset shadow
+ * state), shared by every AUTO rung; it gives row i  avg_i = (float)(S_i / nb_i),  nb_i = ulcx_clip_blocks(BlockSize, L_i),  S_i
+ * the binary64 sum of the row's BlockComplexity values added in block order 0 .. nb_i - 1 - all of the clip's blocks, whatever
+ * the capacities keep.  An AUTO rung then encodes row i at {RateKbps, avg_i}: RateKbps is param0 of a scalar rung (mode CBR or
+ * ABR, param0 finite and > 0; param1 is ignored) or the row's entry of a table rung (the table's own AvgComplexity is ignored;
+ * a row with RateKbps < 0 stays the VBR row it is).  avg_i == 0 means CBR, as the table convention has it.  The caller's tables
+ * are not written: the resolved tables [ULCX_MAX_RUNGS][nStreams] live in the object.  An AUTO scalar rung therefore behaves
+ * as a table rung (always the full number of probe passes).  A call without an AUTO rung runs no analysis pass.
+ *   d_avg   optional, float32 [n]: avg_i (0 for an empty row).  WITHOUT an AUTO rung it is NOT written.
+ * STATE / ORDER.  The clips call's rules: no slot of enc and no stream state of dec is read or changed, everything is enqueued on
+ * hipStream, nothing waits for the device; the shadow state is reset in front of the analysis pass and again in front of the
+ * encode pass; the call mixes freely with every other call on the object.  STAGING: the object's slots and sizes of a chunk hold
+ * nRungs rungs - nRungs * nStreams * maxBlocksPerCall * slot_bytes bytes of slots - and grow to the largest clips ladder seen
+ * (the rule of ulcx_encode_host_ladder's staging; growing allocates the larger staging, then frees the smaller one, which waits for
+ * the device; if the allocation fails the call returns ULCX_ERR_NOMEM and the object keeps the staging it had): size
+ * maxBlocksPerCall by it.  After the call ulcx_encoder_last_rungs is nRungs.
+ * The _dev forms refuse with ULCX_ERR_ARG before any device work, the object as it was: everything the clips call refuses;
+ * everything ulcx_encode_dev_ladder refuses except `reserved`; `reserved` outside {0, ULCX_RUNG_AUTO}; AUTO on a scalar rung of
+ * mode VBR or with a param0 that is no rate; a rung table not aligned to 8 bytes, d_avg not aligned to 4; nRungs * n * indexStride
+ * beyond what ulcx_index_slots_dev takes.  The host form is synchronous (h_payload .. h_indexBlocks hold nRungs * n files); it
+ * also refuses a bad table entry and bad scalar parameters as ulcx_encode_host_ladder does, and AUTO on a table row with
+ * RateKbps < 0.  ulcx_encode_*_ladder go on refusing any non-zero `reserved`. */
+#define ULCX_RUNG_AUTO 1   /* in ulcx_rung::reserved, accepted by the clips ladder calls only */
+int  ulcx_encode_clips_ladder_dev(ulcx_encoder *enc, ulcx_decoder *dec, int n, const ulcx_rung *rungs, int nRungs,
+                                  const float *d_pcm /* [n][nChan][nSamples] */, const int32_t *d_len /* [n] or NULL */, int nSamples,
+                                  uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes /* [nRungs][n] */, int32_t *d_maxBlock /* [nRungs][n], optional */,
+                                  ulcx_index_entry *d_index /* [nRungs][n][indexStride] */, int indexStride, int32_t *d_indexBlocks /* [nRungs][n] */,
+                                  float *d_avg /* [n], optional */, void *hipStream);
+int  ulcx_encode_clips_ladder_dev_pcm16(ulcx_encoder *enc, ulcx_decoder *dec, int n, const ulcx_rung *rungs, int nRungs,
+                                        const int16_t *d_pcm16, const int32_t *d_len, int nSamples,
+                                        uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock,
+                                        ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, float *d_avg, void *hipStream);
+int  ulcx_encode_clips_ladder_host(ulcx_encoder *enc, ulcx_decoder *dec, int n, const ulcx_rung *rungs, int nRungs,
+                                   const float *h_pcm, const int32_t *h_len, int nSamples,
+                                   uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes, int32_t *h_maxBlock,
+                                   ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks, float *h_avg);   /* synchronous */
 
 /* Clip spectra: the encoder's own MDCT coefficients of clips - the encode mirror of ulcx_decode_crops_spectra_*, and with it the
  * clean half of a (coded spectrum, clean spectrum) pair on one grid: the same layout, under the window code the encoder chose for

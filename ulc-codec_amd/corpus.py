@@ -145,28 +145,105 @@ class CropCorpus:
             else:
                 enc.encode_clips_spectra_dev(*args, depth, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
                                              flags=ulc_amd.SPECTRA_LR if _tap[1] else 0, **kw)
-            c.n_files, c.device = n, dev
-            if not c.ragged:
-                c.stride, c.index_stride = stride, index_stride
-                c.d_payload, c.d_payload_bytes, c.d_index, c.d_index_blocks = payload, nbytes, index, blocks
-            else:
-                poffs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-                ioffs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-                oblocks = torch.empty(n, dtype=torch.int32, device=dev)
-                need = torch.empty(2, dtype=torch.int64, device=dev)
-                none = torch.empty(16, dtype=torch.uint8, device=dev)
-                args = (n, payload.data_ptr(), stride, nbytes.data_ptr(), index.data_ptr(), index_stride, blocks.data_ptr())
-                ulc_amd.corpus_ragged_dev(*args, none.data_ptr(), 0, poffs.data_ptr(), none.data_ptr(), 0, ioffs.data_ptr(), oblocks.data_ptr(),
-                                          need.data_ptr(), stream=stream, device=dev.index or 0)
-                nbytes_all, nent_all = (int(v) for v in need.cpu())
-                opay = torch.empty(nbytes_all + PAYLOAD_PAD, dtype=torch.uint8, device=dev)
-                oidx = torch.empty((max(1, nent_all), 2), dtype=torch.int32, device=dev)
-                ulc_amd.corpus_ragged_dev(*args, opay.data_ptr(), nbytes_all, poffs.data_ptr(), oidx.data_ptr(), nent_all, ioffs.data_ptr(), oblocks.data_ptr(),
-                                          need.data_ptr(), stream=stream, device=dev.index or 0)
-                c.d_payload, c.d_payload_offs, c.d_index, c.d_index_offs, c.d_index_blocks = opay, poffs, oidx, ioffs, oblocks
-                # (the strided tensors go back to torch's allocator, which hands them out again on this stream only: behind the copy)
+            c._adopt(dev, stream, n, payload, stride, nbytes, index, index_stride, blocks)
         c.frozen = True
         return c if planes is None else (c, *planes)
+
+    def _adopt(self, dev, stream, n, payload, stride, nbytes, index, index_stride, blocks):
+        """The tensors a clips call wrote (n files, strided) become the corpus's; a ragged corpus lays them out with
+        ulcx_corpus_ragged_dev on `stream` first.  Called inside torch.cuda.device(dev)."""
+        import torch
+        self.n_files, self.device = n, dev
+        if not self.ragged:
+            self.stride, self.index_stride = stride, index_stride
+            self.d_payload, self.d_payload_bytes, self.d_index, self.d_index_blocks = payload, nbytes, index, blocks
+            return
+        poffs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        ioffs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        oblocks = torch.empty(n, dtype=torch.int32, device=dev)
+        need = torch.empty(2, dtype=torch.int64, device=dev)
+        none = torch.empty(16, dtype=torch.uint8, device=dev)
+        args = (n, payload.data_ptr(), stride, nbytes.data_ptr(), index.data_ptr(), index_stride, blocks.data_ptr())
+        ulc_amd.corpus_ragged_dev(*args, none.data_ptr(), 0, poffs.data_ptr(), none.data_ptr(), 0, ioffs.data_ptr(), oblocks.data_ptr(),
+                                  need.data_ptr(), stream=stream, device=dev.index or 0)
+        nbytes_all, nent_all = (int(v) for v in need.cpu())
+        opay = torch.empty(nbytes_all + PAYLOAD_PAD, dtype=torch.uint8, device=dev)
+        oidx = torch.empty((max(1, nent_all), 2), dtype=torch.int32, device=dev)
+        ulc_amd.corpus_ragged_dev(*args, opay.data_ptr(), nbytes_all, poffs.data_ptr(), oidx.data_ptr(), nent_all, ioffs.data_ptr(), oblocks.data_ptr(),
+                                  need.data_ptr(), stream=stream, device=dev.index or 0)
+        self.d_payload, self.d_payload_offs, self.d_index, self.d_index_offs, self.d_index_blocks = opay, poffs, oidx, ioffs, oblocks
+        # (the strided tensors go back to torch's allocator, which hands them out again on this stream only: behind the copy)
+
+    @classmethod
+    def from_clips_ladder(cls, enc, dec, wave, lengths=None, rates=((ulc_amd.MODE_VBR, 50.0),), layout="strided", payload_stride=None):
+        """from_clips() under several rates in one call (ulcx_encode_clips_ladder_dev) -> ONE frozen corpus of R * n files: file
+        corpus.file_of(rung, clip) = rung * n + clip is that clip under rates[rung].  A rate is (mode, p0[, p1]) for every clip,
+        ("auto", kbps) - the clip in ABR at kbps and at its OWN average block complexity, the tool's two-run `RATE,auto`, with the
+        analysis pass on the device - or a float32 [n][2] table {RateKbps, AvgComplexity} per clip; ("auto_table", table) puts each
+        clip's own average in the table's second column.  corpus.avg is then a float32 [n] tensor of the clips' averages (None
+        without an "auto" rate); corpus.n_rungs and corpus.n_clips are R and n.  At most ulc_amd.MAX_RUNGS rates; enc, dec, wave,
+        lengths, layout and payload_stride (bytes per FILE) as from_clips takes them."""
+        import numbers
+        import torch
+        n, ch, T = wave.shape
+        if (ch, enc.BS) != (dec.C, dec.BS) or ch != enc.C:
+            raise UlcError(f"corpus: clips of {ch} channels, an encoder of {enc.BS} x {enc.C}, a decoder of {dec.BS} x {dec.C}")
+        rates = list(rates)
+        R = len(rates)
+        c = cls(ch, enc.BS, layout)
+        dev = wave.device
+        pcm16 = wave.dtype == torch.int16
+        wave = wave.contiguous() if pcm16 else wave.to(torch.float32).contiguous()
+        want = None if lengths is None else torch.as_tensor(lengths, dtype=torch.int32, device=dev).contiguous()
+        tables = []                                             # (alive until the call is enqueued; torch frees them in stream order)
+
+        def table_ptr(r, t):
+            t = torch.as_tensor(t, dtype=torch.float32, device=dev).contiguous()
+            if tuple(t.shape) != (n, 2):
+                raise UlcError(f"corpus: rate {r}: a table of shape {tuple(t.shape)} for {n} clips ([n][2] = RateKbps, AvgComplexity per clip)")
+            tables.append(t)
+            return t.data_ptr()
+        number = lambda x: isinstance(x, numbers.Real) and not isinstance(x, bool)
+        rungs = []
+        for r, g in enumerate(rates):
+            # a scalar rate is a tuple of 2 or 3 numbers, or ("auto", number); anything else must be a table [n][2] - a table
+            # written as a tuple of rows included
+            if isinstance(g, tuple) and len(g) == 2 and g[0] == "auto_table":
+                rungs.append(("auto_table", table_ptr(r, g[1])))
+            elif isinstance(g, tuple) and len(g) == 2 and g[0] == "auto" and number(g[1]):
+                rungs.append(("auto", float(g[1])))
+            elif isinstance(g, tuple) and len(g) in (2, 3) and all(number(x) for x in g):
+                rungs.append(g)
+            elif isinstance(g, tuple) and len(g) and isinstance(g[0], str):
+                raise UlcError(f"corpus: rate {r}: {g!r} ((mode, p0[, p1]), ('auto', kbps), ('auto_table', table) or a table)")
+            else:
+                rungs.append(table_ptr(r, g))
+        auto = any(isinstance(g, tuple) and g[0] in ("auto", "auto_table") for g in rungs)
+        nb = ulc_amd.clip_blocks(enc.BS, T)
+        stride = int(payload_stride or enc.slot * nb)
+        index_stride = nb + 1
+        F = max(R, 1) * n
+        payload = torch.empty((F, stride), dtype=torch.uint8, device=dev)
+        nbytes = torch.empty(F, dtype=torch.int32, device=dev)
+        index = torch.empty((F, index_stride, 2), dtype=torch.int32, device=dev)
+        blocks = torch.empty(F, dtype=torch.int32, device=dev)
+        avg = torch.empty(n, dtype=torch.float32, device=dev) if auto else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            enc.encode_clips_ladder_dev(dec, n, rungs, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, payload.data_ptr(), stride, nbytes.data_ptr(),
+                                        index.data_ptr(), index_stride, blocks.data_ptr(), d_avg=avg.data_ptr() if auto else 0, stream=stream, pcm16=pcm16)
+            c._adopt(dev, stream, F, payload, stride, nbytes, index, index_stride, blocks)
+        c.n_rungs, c.n_clips, c.avg = R, n, avg
+        c.frozen = True
+        return c
+
+    def file_of(self, rung, clip):
+        """The file number of `clip` under rate `rung` in a corpus from_clips_ladder() made."""
+        if not hasattr(self, "n_rungs"):
+            raise UlcError("corpus: file_of() is for a corpus that from_clips_ladder() made")
+        if not (0 <= rung < self.n_rungs and 0 <= clip < self.n_clips):
+            raise UlcError(f"corpus: rung {rung}, clip {clip} of {self.n_rungs} x {self.n_clips}")
+        return rung * self.n_clips + clip
 
     def add_file(self, ulc_bytes, ulx_bytes=None):
         """-> the file's number.  Refuses (UlcError) another geometry than the corpus's, and a `.ulx` that is not this payload's:

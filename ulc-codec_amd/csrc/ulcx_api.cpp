@@ -85,7 +85,10 @@ struct ulcx_encoder {
     // stream slots: the compact shadow state of the subset calls ([B], allocated on the first one) and the device copy of a host form's list
     float *subHist = nullptr; UlcxWcState *subWcs = nullptr; int32_t *subSlots = nullptr;
     // clips (ulcx_encode_clips_*): one chunk of the call - [B][maxK] interleaved blocks, slots and sizes (allocated on the first clips call)
-    float *clipPcm = nullptr; uint8_t *clipOut = nullptr; int32_t *clipBits = nullptr;
+    // (slots and sizes: [clipRungs][B][maxK], grown to the largest clips ladder seen; the plain clips calls are one rung)
+    float *clipPcm = nullptr; uint8_t *clipOut = nullptr; int32_t *clipBits = nullptr; int clipRungs = 0;
+    // ULCX_RUNG_AUTO rungs of a clips ladder call: the rows' complexity sums [B] and the resolved tables [ULCX_MAX_RUNGS][B] (allocated on the first such call)
+    double *clipSum = nullptr; ulcx_rate *clipRate = nullptr;
     // clip spectra (ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*): the chunk's [B][maxK] window codes and complexities (allocated on the first such call)
     int32_t *clipWc = nullptr; float *clipCplx = nullptr;
 };
@@ -730,6 +733,9 @@ extern "C" int ulcx_encode_host_ladder(ulcx_encoder *e, const ulcx_rung *rungs, 
 // Per chunk of maxBlocksPerCall blocks: k_clip_stage into the object's staging, the plain call's launch sequence with c.B = n on
 // the shadow state (reset in front of the first chunk, never scattered back) into the object's slots and sizes, k_clip_append,
 // then the two kernels of ulcx_index_slots_dev on the masked sizes.  Everything on the caller's stream.
+// ulcx_encode_clips_ladder_*: the same chunks with the ladder's launch sequence (nRungs contexts, rung r into its own part of
+// the slots and sizes), the append and the index over nRungs * n files; ULCX_RUNG_AUTO rungs: an analysis pass over the same
+// chunks in front, k_clip_cplx_sum behind each of them, k_clip_auto behind the last.
 extern "C" int ulcx_clip_blocks(int BlockSize, int nSamples) {
     if (!validate(1, BlockSize) || nSamples < 1) return 0;
     return (int)(((long long)nSamples + BlockSize - 1) / BlockSize) + 2;          // cli/ulcx_tool.c:196 = ulcEncodeTool.c:93-98
@@ -742,14 +748,42 @@ static int clips_rows_bad(const char *who, int n, const void *pcm, int nSamples)
     if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
     return 0;
 }
-static int clips_args_bad(const char *who, int n, int mode, const void *rate, const void *pcm, int nSamples,
+static int clips_args_bad(const char *who, int n, const void *pcm, int nSamples,
                           const void *payload, long long payloadStride, const void *payloadBytes, const void *index, int indexStride, const void *indexBlocks) {
     if (!pcm || !payload || !payloadBytes || !index || !indexBlocks) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
     if (nSamples < 1) { refuse(who, "bad argument (nSamples %d)", nSamples); return 1; }
     if (indexStride < 2 || payloadStride < 1) { refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride); return 1; }
     if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
-    if (!rate && !mode_ok(mode)) { refuse(who, "bad mode"); return 1; }
     return 0;
+}
+// The setting(s) of a clips call.  The plain and _spectra entries hand the body one rung made of their own arguments
+// (ladder == false: "bad mode" as ever); the ladder entries hand it the caller's rungs, checked as ulcx_encode_dev_ladder
+// checks its own except that `reserved` may be ULCX_RUNG_AUTO - on a table rung, or on a scalar rung of mode CBR or ABR
+// whose param0 is a rate (finite, > 0: it becomes RateKbps of a table entry, where a negative value would read as VBR).
+static ulcx_rung clip_rung(int mode, float p0, float p1, const ulcx_rate *rate) { const ulcx_rung g = { mode, p0, p1, 0, rate }; return g; }
+static bool rung_auto(const ulcx_rung &g) { return (g.reserved & ULCX_RUNG_AUTO) != 0; }
+static int clips_setting_bad(const char *who, const ulcx_rung *rungs, int nRungs, bool ladder) {
+    if (!ladder) {
+        if (!rungs[0].rate && !mode_ok(rungs[0].mode)) { refuse(who, "bad mode"); return 1; }
+        return 0;
+    }
+    if (!rungs || nRungs < 1 || nRungs > ULCX_MAX_RUNGS) { refuse(who, "nRungs %d not in 1 .. %d (or no rungs)", nRungs, ULCX_MAX_RUNGS); return 1; }
+    for (int r = 0; r < nRungs; r++) {
+        const ulcx_rung &g = rungs[r];
+        if (g.reserved & ~ULCX_RUNG_AUTO) { refuse(who, "rung %d: reserved %d is neither 0 nor ULCX_RUNG_AUTO", r, (int)g.reserved); return 1; }
+        if (!g.rate && !mode_ok(g.mode)) { refuse(who, "rung %d: bad mode %d", r, (int)g.mode); return 1; }
+        if (!rung_auto(g) || g.rate) continue;
+        if (g.mode == ULCX_MODE_VBR) { refuse(who, "rung %d: ULCX_RUNG_AUTO on a VBR rung (it needs a rate: mode CBR or ABR)", r); return 1; }
+        if (!(isfinite(g.param0) && g.param0 > 0.0f)) { refuse(who, "rung %d: ULCX_RUNG_AUTO with RateKbps %g", r, (double)g.param0); return 1; }
+    }
+    return 0;
+}
+// the call's files (rows x rungs) and their index entries: what ulcx_index_slots_dev takes in one call (index_rows_any), and
+// a file count that is an int.  It needs no object, so it stands in front of the object checks.
+static int clips_files_bad(const char *who, long long nFiles, int indexStride) {
+    if (nFiles <= 0x7FFFFFFFLL && nFiles * indexStride <= (0x7FFFFFFFLL << 8)) return 0;
+    refuse(who, "%lld rows of %d entries are more than one call takes", nFiles, indexStride);
+    return 1;
 }
 // dec == NULL passes with needDec false: the analysis forms have no decoder
 static int clips_objects_bad(const char *who, const ulcx_encoder *e, const ulcx_decoder *dec, int n, bool needDec = true) {
@@ -772,73 +806,116 @@ static int clip_spec_bad(const char *who, const ClipSpec &sp) {
     if (sp.flags & ~ULCX_SPECTRA_LR) { refuse(who, "bad flags 0x%x", (unsigned)sp.flags); return 1; }
     return 0;
 }
-// withOut: slots and sizes too (the analysis forms write none); withSpec: the chunk's window codes and complexities
-static int clips_staging(ulcx_encoder *e, bool withOut, bool withSpec) {
+// nOutRungs: slots and sizes for that many rungs (0: the analysis forms write none), grown to the largest count seen as
+// ulcx_encode_host_ladder's staging is; withSpec: the chunk's window codes and complexities; withAuto: the sums and tables of
+// ULCX_RUNG_AUTO rungs
+static int clips_staging(ulcx_encoder *e, int nOutRungs, bool withSpec, bool withAuto) {
     const size_t nBlk = (size_t)e->B * e->maxK;
     int rc = enc_shadow(e);
     if (!rc && !e->clipPcm) rc = dalloc(e->allocs, &e->clipPcm, nBlk * (size_t)e->C * e->BS, false);
-    if (!rc && withOut && !e->clipOut) rc = dalloc(e->allocs, &e->clipOut, nBlk * e->ctx.slot, false);
-    if (!rc && withOut && !e->clipBits) rc = dalloc(e->allocs, &e->clipBits, nBlk, false);
+    if (!rc && e->clipRungs < nOutRungs) {
+        // the larger pair first, the smaller one freed behind it: a failed allocation leaves the staging the object had
+        uint8_t *out = nullptr; int32_t *bits = nullptr;
+        rc = dalloc(e->allocs, &out, (size_t)nOutRungs * nBlk * e->ctx.slot, false);
+        if (!rc) rc = dalloc(e->allocs, &bits, (size_t)nOutRungs * nBlk, false);
+        if (rc) { dfree(e->allocs, &out); dfree(e->allocs, &bits); return rc; }
+        dfree(e->allocs, &e->clipOut); dfree(e->allocs, &e->clipBits);
+        e->clipOut = out; e->clipBits = bits; e->clipRungs = nOutRungs;
+    }
     if (!rc && withSpec && !e->clipWc) rc = dalloc(e->allocs, &e->clipWc, nBlk, false);
     if (!rc && withSpec && !e->clipCplx) rc = dalloc(e->allocs, &e->clipCplx, nBlk, false);
+    if (!rc && withAuto && !e->clipSum) rc = dalloc(e->allocs, &e->clipSum, (size_t)e->B, false);
+    if (!rc && withAuto && !e->clipRate) rc = dalloc(e->allocs, &e->clipRate, (size_t)ULCX_MAX_RUNGS * e->B, false);
     return rc;
 }
-// The body of the three clips families.  chunkSamples: the longest row as far as the caller knows it (the _dev forms: nSamples) -
-// the chunks stop behind its last block.  analyse: ulcx_analyse_clips_* - no rate, decoder or corpus, the analysis launch sequence
-// per chunk.  sp.on: k_clip_spec behind every chunk's launch sequence, which then writes the chunk's window codes and
-// complexities into the object's staging; plane blocks behind the last chunk are one more launch of it with an empty chunk.
-static int encode_clips_any(const char *who, ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
+// The body of the clips families.  rungs: the call's settings, file r * n + i being row i under rung r (ladder == false: the one
+// rung a plain, _spectra or analysis entry made of its arguments).  chunkSamples: the longest row as far as the caller knows it
+// (the _dev forms: nSamples) - the chunks stop behind its last block.  analyse: ulcx_analyse_clips_* - no rate, decoder or
+// corpus, the analysis launch sequence per chunk.  sp.on: k_clip_spec behind every chunk's launch sequence, which then writes
+// the chunk's window codes and complexities into the object's staging; plane blocks behind the last chunk are one more launch of
+// it with an empty chunk.  A ULCX_RUNG_AUTO rung: the chunks run twice from the reset shadow state - an analysis pass whose
+// complexities go into the rows' ordered sums, k_clip_auto, then the encode pass with the resolved tables in the AUTO rungs' place.
+static int encode_clips_any(const char *who, ulcx_encoder *e, ulcx_decoder *dec, int n, const ulcx_rung *rungs, int nRungs, bool ladder,
                             const float *d_pcm, const int16_t *d_pcm16, const int32_t *d_len, int nSamples, int chunkSamples,
                             uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes, int32_t *d_maxBlock,
-                            ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream,
+                            ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, float *d_avg, void *hipStream,
                             bool analyse = false, const ClipSpec &sp = ClipSpec()) {
     const void *pcm = d_pcm ? (const void *)d_pcm : d_pcm16;
     if (analyse ? clips_rows_bad(who, n, pcm, nSamples)
-                : clips_args_bad(who, n, mode, d_rate, pcm, nSamples, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks)) return ULCX_ERR_ARG;
+                : (clips_args_bad(who, n, pcm, nSamples, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks) ||
+                   clips_setting_bad(who, rungs, nRungs, ladder))) return ULCX_ERR_ARG;
     if (clip_spec_bad(who, sp)) return ULCX_ERR_ARG;
     // (a plane starts at any sample: the staging kernel uses wider loads only where the address allows them)
-    if (misaligned(who, "d_pcm", d_pcm, (int)sizeof(float)) || misaligned(who, "d_pcm16", d_pcm16, (int)sizeof(int16_t)) ||
-        misaligned(who, "d_rate", d_rate, ULCX_ALIGN_RATE) || misaligned(who, "d_len", d_len, ULCX_ALIGN_WORD) ||
+    if (misaligned(who, "d_pcm", d_pcm, (int)sizeof(float)) || misaligned(who, "d_pcm16", d_pcm16, (int)sizeof(int16_t))) return ULCX_ERR_ARG;
+    for (int r = 0; r < nRungs; r++) if (misaligned(who, ladder ? "a rung's rate table" : "d_rate", rungs[r].rate, ULCX_ALIGN_RATE)) return ULCX_ERR_ARG;
+    if (misaligned(who, "d_len", d_len, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_maxBlock", d_maxBlock, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) || misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_avg", d_avg, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_coef", sp.coef, ULCX_ALIGN_PCM) || misaligned(who, "d_wc", sp.wc, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_cplx", sp.cplx, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    const long long nFiles = (long long)nRungs * n;
+    if (!analyse && clips_files_bad(who, nFiles, indexStride)) return ULCX_ERR_ARG;
     if (clips_objects_bad(who, e, dec, n, !analyse)) return ULCX_ERR_ARG;
-    if (!analyse && (long long)n * indexStride > (0x7FFFFFFFLL << 8)) return refuse(who, "%d rows of %d entries are more than one call takes", n, indexStride);
+    bool anyAuto = false;
+    for (int r = 0; r < nRungs; r++) anyAuto = anyAuto || rung_auto(rungs[r]);
     CKR(hipSetDevice(e->device));
-    int rc = clips_staging(e, !analyse, sp.on);
+    int rc = clips_staging(e, analyse ? 0 : nRungs, sp.on || anyAuto, anyAuto);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)hipStream;
-    // (an analysis form has no byte counts: the begin kernel's zeros go to the window-code staging, which every chunk rewrites)
-    if ((rc = ulcx_clips_begin_launch(e->subHist, e->subWcs, n, e->C, e->BS, analyse ? e->clipWc : d_payloadBytes, d_maxBlock, st))) return rc;
-    if (!analyse && (rc = ulcx_index_begin_launch(n, d_index, indexStride, d_indexBlocks, st))) return rc;
     const int total = ulcx_clip_blocks(e->BS, chunkSamples);
     const int lr = sp.flags & ULCX_SPECTRA_LR;
+    ulcx_rung eff[ULCX_MAX_RUNGS];                                 // the rungs the encode pass runs: AUTO ones as their resolved tables
+    for (int r = 0; r < nRungs; r++) eff[r] = rungs[r];
     int K = 0;
-    for (int k0 = 0; k0 < total && rc == ULCX_OK; k0 += K) {
-        K = total - k0 < e->maxK ? total - k0 : e->maxK;
-        if ((rc = ulcx_clips_stage_launch(d_pcm, d_pcm16, d_len, nSamples, n, e->C, e->BS, k0, K, e->clipPcm, st))) break;
-        UlcxEncCtx c = analyse ? enc_call_ctx(e, ULCX_MODE_VBR, 100.0f, 0.0f, nullptr, e->clipPcm, nullptr, K)
-                               : enc_call_ctx(e, mode, p0, p1, d_rate, e->clipPcm, nullptr, K);
-        if (!analyse) { c.out = e->clipOut; c.bits = e->clipBits; }
-        if (sp.on) { c.wcOut = e->clipWc; c.cplxOut = e->clipCplx; }
-        c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
-        if (analyse) rc = ulcx_analyse_launch(c, st, e->timing ? e->ev : nullptr, enc_aux(e, K), e->analyseKxf);
-        else rc = ulcx_enc_launch(c, st, e->timing ? e->ev : nullptr, enc_aux(e, K));
-        if (rc) break;
-        if (sp.on && (rc = ulcx_clips_spec_launch(n, K, k0, sp.nBlocks - k0 < K ? sp.nBlocks - k0 : K, e->C, e->BS, nSamples, d_len, c.coef, e->clipWc, e->clipCplx,
-                                                  sp.nBlocks, lr, sp.coef, sp.wc, sp.cplx, st))) break;
-        if (analyse) continue;
-        if ((rc = ulcx_clips_append_launch(n, K, k0, e->BS, nSamples, d_len, c.slot, e->clipOut, e->clipBits, d_payload, payloadStride, d_payloadBytes, d_maxBlock,
-                                           indexStride, d_indexBlocks, st))) break;
-        UlcxDecCtx dc = dec->ctx;
-        dc.in = e->clipOut; dc.slot = c.slot; dc.inBytes = (long long)n * K * c.slot;
-        rc = ulcx_index_slots_launch(dc, n, K, e->clipBits, d_index, indexStride, d_indexBlocks, st);
+    // One pass over the call's chunks from the reset shadow state.  an: the analysis launch sequence; pre: the pass in front of
+    // an encode with AUTO rungs (the sums instead of the tap).
+    auto pass = [&](bool an, bool pre) -> int {
+        const bool tap = sp.on && !pre;
+        // (an analysis pass has no byte counts: the begin kernel's zeros go to the window-code staging, which every chunk rewrites)
+        int rp = ulcx_clips_begin_launch(e->subHist, e->subWcs, n, e->C, e->BS, an ? n : (int)nFiles, an ? e->clipWc : d_payloadBytes, pre ? nullptr : d_maxBlock,
+                                         pre ? e->clipSum : nullptr, st);
+        if (rp) return rp;
+        if (!an && (rp = ulcx_index_begin_launch((int)nFiles, d_index, indexStride, d_indexBlocks, st))) return rp;
+        for (int k0 = 0; k0 < total; k0 += K) {
+            K = total - k0 < e->maxK ? total - k0 : e->maxK;
+            if ((rp = ulcx_clips_stage_launch(d_pcm, d_pcm16, d_len, nSamples, n, e->C, e->BS, k0, K, e->clipPcm, st))) return rp;
+            UlcxEncCtx cs[ULCX_MAX_RUNGS];
+            const int nc = an ? 1 : nRungs;
+            for (int r = 0; r < nc; r++) {
+                UlcxEncCtx &c = cs[r];
+                c = an ? enc_call_ctx(e, ULCX_MODE_VBR, 100.0f, 0.0f, nullptr, e->clipPcm, nullptr, K)
+                       : enc_call_ctx(e, eff[r].mode, eff[r].param0, eff[r].param1, eff[r].rate, e->clipPcm, nullptr, K);
+                if (!an) { c.out = e->clipOut + (size_t)r * n * K * c.slot; c.bits = e->clipBits + (size_t)r * n * K; }
+                if (!r && (tap || pre)) { c.wcOut = e->clipWc; c.cplxOut = e->clipCplx; }
+                c.B = n; c.hist = e->subHist; c.wcs = e->subWcs;
+            }
+            if (an) rp = ulcx_analyse_launch(cs[0], st, e->timing ? e->ev : nullptr, enc_aux(e, K), e->analyseKxf);
+            else rp = ulcx_enc_launch_ladder(cs, nRungs, st, e->timing ? e->ev : nullptr, enc_aux(e, K));
+            if (rp) return rp;
+            if (tap && (rp = ulcx_clips_spec_launch(n, K, k0, sp.nBlocks - k0 < K ? sp.nBlocks - k0 : K, e->C, e->BS, nSamples, d_len, cs[0].coef, e->clipWc, e->clipCplx,
+                                                    sp.nBlocks, lr, sp.coef, sp.wc, sp.cplx, st))) return rp;
+            if (pre && (rp = ulcx_clips_cplx_sum_launch(n, K, k0, e->BS, nSamples, d_len, e->clipCplx, e->clipSum, st))) return rp;
+            if (an) continue;
+            const int slot = cs[0].slot;
+            if ((rp = ulcx_clips_append_launch(n, nRungs, K, k0, e->BS, nSamples, d_len, slot, e->clipOut, e->clipBits, d_payload, payloadStride, d_payloadBytes, d_maxBlock,
+                                               indexStride, d_indexBlocks, st))) return rp;
+            UlcxDecCtx dc = dec->ctx;
+            dc.in = e->clipOut; dc.slot = slot; dc.inBytes = nFiles * K * slot;
+            if ((rp = ulcx_index_slots_launch(dc, (int)nFiles, K, e->clipBits, d_index, indexStride, d_indexBlocks, st))) return rp;
+        }
+        return ULCX_OK;
+    };
+    if (anyAuto) {
+        rc = pass(true, true);
+        if (rc == ULCX_OK) rc = ulcx_clips_auto_launch(n, e->BS, nSamples, d_len, e->clipSum, rungs, nRungs, e->clipRate, d_avg, st);
+        for (int r = 0; r < nRungs; r++) if (rung_auto(rungs[r])) { eff[r].rate = e->clipRate + (size_t)r * n; eff[r].reserved = 0; }
     }
+    if (rc == ULCX_OK) rc = pass(analyse, false);
     if (sp.on && rc == ULCX_OK && total < sp.nBlocks)
         rc = ulcx_clips_spec_launch(n, 0, total, sp.nBlocks - total, e->C, e->BS, nSamples, d_len, e->ctx.coef, e->clipWc, e->clipCplx,
                                     sp.nBlocks, lr, sp.coef, sp.wc, sp.cplx, st);
-    return K ? enc_call_done(e, rc, K, analyse, analyse ? 0 : 1) : rc;
+    return K ? enc_call_done(e, rc, K, analyse, analyse ? 0 : nRungs) : rc;
 }
 static ClipSpec clip_spec(int nBlocks, int flags, float *coef, int32_t *wc, float *cplx) {
     ClipSpec sp; sp.on = true; sp.nBlocks = nBlocks; sp.flags = flags; sp.coef = coef; sp.wc = wc; sp.cplx = cplx;
@@ -847,65 +924,100 @@ static ClipSpec clip_spec(int nBlocks, int flags, float *coef, int32_t *wc, floa
 extern "C" int ulcx_encode_clips_dev(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
                                      const float *d_pcm, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
                                      int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream) {
-    return encode_clips_any("ulcx_encode_clips_dev", e, dec, n, mode, p0, p1, d_rate, d_pcm, nullptr, d_len, nSamples, nSamples, d_payload, payloadStride,
-                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream);
+    const ulcx_rung g = clip_rung(mode, p0, p1, d_rate);
+    return encode_clips_any("ulcx_encode_clips_dev", e, dec, n, &g, 1, false, d_pcm, nullptr, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, nullptr, hipStream);
 }
 extern "C" int ulcx_encode_clips_dev_pcm16(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
                                            const int16_t *d_pcm16, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
                                            int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, void *hipStream) {
-    return encode_clips_any("ulcx_encode_clips_dev_pcm16", e, dec, n, mode, p0, p1, d_rate, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
-                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream);
+    const ulcx_rung g = clip_rung(mode, p0, p1, d_rate);
+    return encode_clips_any("ulcx_encode_clips_dev_pcm16", e, dec, n, &g, 1, false, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, nullptr, hipStream);
+}
+extern "C" int ulcx_encode_clips_ladder_dev(ulcx_encoder *e, ulcx_decoder *dec, int n, const ulcx_rung *rungs, int nRungs,
+                                            const float *d_pcm, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
+                                            int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks, float *d_avg, void *hipStream) {
+    return encode_clips_any("ulcx_encode_clips_ladder_dev", e, dec, n, rungs, nRungs, true, d_pcm, nullptr, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, d_avg, hipStream);
+}
+extern "C" int ulcx_encode_clips_ladder_dev_pcm16(ulcx_encoder *e, ulcx_decoder *dec, int n, const ulcx_rung *rungs, int nRungs,
+                                                  const int16_t *d_pcm16, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride,
+                                                  int32_t *d_payloadBytes, int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks,
+                                                  float *d_avg, void *hipStream) {
+    return encode_clips_any("ulcx_encode_clips_ladder_dev_pcm16", e, dec, n, rungs, nRungs, true, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, d_avg, hipStream);
 }
 extern "C" int ulcx_encode_clips_spectra_dev(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
                                              const float *d_pcm, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride, int32_t *d_payloadBytes,
                                              int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks,
                                              int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    return encode_clips_any("ulcx_encode_clips_spectra_dev", e, dec, n, mode, p0, p1, d_rate, d_pcm, nullptr, d_len, nSamples, nSamples, d_payload, payloadStride,
-                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream, false, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+    const ulcx_rung g = clip_rung(mode, p0, p1, d_rate);
+    return encode_clips_any("ulcx_encode_clips_spectra_dev", e, dec, n, &g, 1, false, d_pcm, nullptr, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, nullptr, hipStream, false, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
 }
 extern "C" int ulcx_encode_clips_spectra_dev_pcm16(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *d_rate,
                                                    const int16_t *d_pcm16, const int32_t *d_len, int nSamples, uint8_t *d_payload, long long payloadStride,
                                                    int32_t *d_payloadBytes, int32_t *d_maxBlock, ulcx_index_entry *d_index, int indexStride, int32_t *d_indexBlocks,
                                                    int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    return encode_clips_any("ulcx_encode_clips_spectra_dev_pcm16", e, dec, n, mode, p0, p1, d_rate, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
-                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, hipStream, false, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+    const ulcx_rung g = clip_rung(mode, p0, p1, d_rate);
+    return encode_clips_any("ulcx_encode_clips_spectra_dev_pcm16", e, dec, n, &g, 1, false, nullptr, d_pcm16, d_len, nSamples, nSamples, d_payload, payloadStride,
+                            d_payloadBytes, d_maxBlock, d_index, indexStride, d_indexBlocks, nullptr, hipStream, false, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
 }
+static const ulcx_rung kNoRung = { ULCX_MODE_VBR, 100.0f, 0.0f, 0, nullptr };      // the analysis forms: no setting
 extern "C" int ulcx_analyse_clips_dev(ulcx_encoder *e, int n, const float *d_pcm, const int32_t *d_len, int nSamples,
                                       int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    return encode_clips_any("ulcx_analyse_clips_dev", e, nullptr, n, 0, 0.0f, 0.0f, nullptr, d_pcm, nullptr, d_len, nSamples, nSamples, nullptr, 0,
-                            nullptr, nullptr, nullptr, 0, nullptr, hipStream, true, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+    return encode_clips_any("ulcx_analyse_clips_dev", e, nullptr, n, &kNoRung, 1, false, d_pcm, nullptr, d_len, nSamples, nSamples, nullptr, 0,
+                            nullptr, nullptr, nullptr, 0, nullptr, nullptr, hipStream, true, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
 }
 extern "C" int ulcx_analyse_clips_dev_pcm16(ulcx_encoder *e, int n, const int16_t *d_pcm16, const int32_t *d_len, int nSamples,
                                             int nBlocks, int flags, float *d_coef, int32_t *d_wc, float *d_cplx, void *hipStream) {
-    return encode_clips_any("ulcx_analyse_clips_dev_pcm16", e, nullptr, n, 0, 0.0f, 0.0f, nullptr, nullptr, d_pcm16, d_len, nSamples, nSamples, nullptr, 0,
-                            nullptr, nullptr, nullptr, 0, nullptr, hipStream, true, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
+    return encode_clips_any("ulcx_analyse_clips_dev_pcm16", e, nullptr, n, &kNoRung, 1, false, nullptr, d_pcm16, d_len, nSamples, nSamples, nullptr, 0,
+                            nullptr, nullptr, nullptr, 0, nullptr, nullptr, hipStream, true, clip_spec(nBlocks, flags, d_coef, d_wc, d_cplx));
 }
 // The host forms: every check first, then everything up into buffers of the call's own, the body on the null stream with the
-// longest row's length, one synchronisation, and down: counts, index, and of every payload the bytes that are defined; the
-// planes of a spectra form in full.  analyse: no rate, decoder or corpus.
-static int encode_clips_host_any(const char *who, ulcx_encoder *e, ulcx_decoder *dec, bool analyse, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
+// longest row's length, one synchronisation, and down: counts, index, and of every payload the bytes that are defined (the
+// nRungs * n files of a ladder form; its averages where an AUTO rung wrote them); the planes of a spectra form in full.
+// analyse: no rate, decoder or corpus.  A rung's table is validated by the one validator (rate_entry_bad); the ladder form also
+// validates a scalar rung's parameters as ulcx_encode_host_ladder does, and refuses AUTO on a table row that is VBR.
+static int encode_clips_host_any(const char *who, ulcx_encoder *e, ulcx_decoder *dec, bool analyse, int n, const ulcx_rung *rungs, int nRungs, bool ladder,
                                  const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
-                                 int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks, const ClipSpec &sp) {
+                                 int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks, float *h_avg, const ClipSpec &sp) {
     if ((analyse ? clips_rows_bad(who, n, h_pcm, nSamples)
-                 : clips_args_bad(who, n, mode, h_rate, h_pcm, nSamples, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks)) ||
-        clip_spec_bad(who, sp) || clips_objects_bad(who, e, dec, n, !analyse)) return ULCX_ERR_ARG;
+                 : (clips_args_bad(who, n, h_pcm, nSamples, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks) ||
+                    clips_setting_bad(who, rungs, nRungs, ladder))) ||
+        clip_spec_bad(who, sp) || (!analyse && clips_files_bad(who, (long long)nRungs * n, indexStride)) ||
+        clips_objects_bad(who, e, dec, n, !analyse)) return ULCX_ERR_ARG;
     int longest = h_len ? 0 : nSamples;
     for (int i = 0; h_len && i < n; i++) {
         if (h_len[i] < 0) return refuse(who, "row %d has %d samples", i, (int)h_len[i]);
         const int l = h_len[i] > nSamples ? nSamples : h_len[i];
         if (l > longest) longest = l;
     }
-    if (h_rate && rate_table_bad(who, "invalid entry for row", h_rate, n)) return ULCX_ERR_ARG;
+    bool anyAuto = false;
+    for (int r = 0; r < nRungs && !analyse; r++) {
+        const ulcx_rung &g = rungs[r];
+        char what[64];
+        if (!ladder) snprintf(what, sizeof(what), "invalid entry for row");
+        else snprintf(what, sizeof(what), "rung %d: %s", r, g.rate ? "invalid entry for row" : "invalid setting, mode");
+        if (g.rate ? rate_table_bad(who, what, g.rate, n) : (ladder && rate_entry_bad(who, what, g.mode, g.param0, rung_auto(g) ? 0.0f : g.param1))) return ULCX_ERR_ARG;
+        if (!rung_auto(g)) continue;
+        anyAuto = true;
+        for (int i = 0; g.rate && i < n; i++)
+            if (g.rate[i].RateKbps < 0.0f) return refuse(who, "rung %d: ULCX_RUNG_AUTO on row %d, a VBR row (RateKbps %g)", r, i, (double)g.rate[i].RateKbps);
+    }
+    const long long nFiles = (long long)nRungs * n;
     CKR(hipSetDevice(e->device));
-    const size_t nPcm = (size_t)n * e->C * (size_t)nSamples, nEnt = (size_t)n * (size_t)indexStride;
+    const size_t nF = (size_t)nFiles, nPcm = (size_t)n * e->C * (size_t)nSamples, nEnt = nF * (size_t)indexStride;
     const size_t nPlane = (size_t)n * (size_t)sp.nBlocks, nCoef = nPlane * (size_t)e->C * e->BS;
-    DevTmp t; float *dpcm = nullptr; int32_t *dlen = nullptr, *dbytes = nullptr, *dmax = nullptr, *dcnt = nullptr; ulcx_rate *drate = nullptr;
+    DevTmp t; float *dpcm = nullptr, *davg = nullptr; int32_t *dlen = nullptr, *dbytes = nullptr, *dmax = nullptr, *dcnt = nullptr;
     uint8_t *dpay = nullptr; ulcx_index_entry *di = nullptr;
     ClipSpec dsp = sp;
+    ulcx_rung dev[ULCX_MAX_RUNGS];
     CKR(t.get(&dpcm, sizeof(float) * nPcm));
     if (!analyse) {
-        CKR(t.get(&dpay, (size_t)n * (size_t)payloadStride));
-        CKR(t.get(&dbytes, sizeof(int32_t) * n)); CKR(t.get(&dmax, sizeof(int32_t) * n)); CKR(t.get(&dcnt, sizeof(int32_t) * n));
+        CKR(t.get(&dpay, nF * (size_t)payloadStride));
+        CKR(t.get(&dbytes, sizeof(int32_t) * nF)); CKR(t.get(&dmax, sizeof(int32_t) * nF)); CKR(t.get(&dcnt, sizeof(int32_t) * nF));
         CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
     }
     if (sp.on) {
@@ -915,9 +1027,16 @@ static int encode_clips_host_any(const char *who, ulcx_encoder *e, ulcx_decoder 
     }
     CKR(hipMemcpy(dpcm, h_pcm, sizeof(float) * nPcm, hipMemcpyHostToDevice));
     if (h_len) { CKR(t.get(&dlen, sizeof(int32_t) * n)); CKR(hipMemcpy(dlen, h_len, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
-    if (h_rate) { CKR(t.get(&drate, sizeof(ulcx_rate) * n)); CKR(hipMemcpy(drate, h_rate, sizeof(ulcx_rate) * n, hipMemcpyHostToDevice)); }
-    const int rc = encode_clips_any(who, e, dec, n, mode, p0, p1, drate, dpcm, nullptr, dlen, nSamples, longest, dpay, payloadStride, dbytes, dmax, di, indexStride, dcnt, nullptr,
-                                    analyse, dsp);
+    for (int r = 0; r < nRungs; r++) {
+        dev[r] = rungs[r];
+        if (!rungs[r].rate) continue;
+        ulcx_rate *drate = nullptr;
+        CKR(t.get(&drate, sizeof(ulcx_rate) * n)); CKR(hipMemcpy(drate, rungs[r].rate, sizeof(ulcx_rate) * n, hipMemcpyHostToDevice));
+        dev[r].rate = drate;
+    }
+    if (anyAuto && h_avg) CKR(t.get(&davg, sizeof(float) * n));
+    const int rc = encode_clips_any(who, e, dec, n, dev, nRungs, ladder, dpcm, nullptr, dlen, nSamples, longest, dpay, payloadStride, dbytes, dmax, di, indexStride, dcnt, davg,
+                                    nullptr, analyse, dsp);
     if (rc) return rc;
     CKR(hipDeviceSynchronize());
     if (sp.on) {
@@ -926,31 +1045,40 @@ static int encode_clips_host_any(const char *who, ulcx_encoder *e, ulcx_decoder 
         if (sp.cplx) CKR(hipMemcpy(sp.cplx, dsp.cplx, sizeof(float) * nPlane, hipMemcpyDeviceToHost));
     }
     if (analyse) return ULCX_OK;
-    CKR(hipMemcpy(h_payloadBytes, dbytes, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    if (h_maxBlock) CKR(hipMemcpy(h_maxBlock, dmax, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    CKR(hipMemcpy(h_indexBlocks, dcnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_payloadBytes, dbytes, sizeof(int32_t) * nF, hipMemcpyDeviceToHost));
+    if (h_maxBlock) CKR(hipMemcpy(h_maxBlock, dmax, sizeof(int32_t) * nF, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_indexBlocks, dcnt, sizeof(int32_t) * nF, hipMemcpyDeviceToHost));
     CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * nEnt, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; i++)
-        if (h_payloadBytes[i] > 0) CKR(hipMemcpy(h_payload + (size_t)i * (size_t)payloadStride, dpay + (size_t)i * (size_t)payloadStride, (size_t)h_payloadBytes[i], hipMemcpyDeviceToHost));
+    if (davg) CKR(hipMemcpy(h_avg, davg, sizeof(float) * n, hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < nF; f++)
+        if (h_payloadBytes[f] > 0) CKR(hipMemcpy(h_payload + f * (size_t)payloadStride, dpay + f * (size_t)payloadStride, (size_t)h_payloadBytes[f], hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
 extern "C" int ulcx_encode_clips_host(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
                                       const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
                                       int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks) {
-    return encode_clips_host_any("ulcx_encode_clips_host", e, dec, false, n, mode, p0, p1, h_rate, h_pcm, h_len, nSamples, h_payload, payloadStride, h_payloadBytes,
-                                 h_maxBlock, h_index, indexStride, h_indexBlocks, ClipSpec());
+    const ulcx_rung g = clip_rung(mode, p0, p1, h_rate);
+    return encode_clips_host_any("ulcx_encode_clips_host", e, dec, false, n, &g, 1, false, h_pcm, h_len, nSamples, h_payload, payloadStride, h_payloadBytes,
+                                 h_maxBlock, h_index, indexStride, h_indexBlocks, nullptr, ClipSpec());
+}
+extern "C" int ulcx_encode_clips_ladder_host(ulcx_encoder *e, ulcx_decoder *dec, int n, const ulcx_rung *rungs, int nRungs,
+                                             const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
+                                             int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks, float *h_avg) {
+    return encode_clips_host_any("ulcx_encode_clips_ladder_host", e, dec, false, n, rungs, nRungs, true, h_pcm, h_len, nSamples, h_payload, payloadStride, h_payloadBytes,
+                                 h_maxBlock, h_index, indexStride, h_indexBlocks, h_avg, ClipSpec());
 }
 extern "C" int ulcx_encode_clips_spectra_host(ulcx_encoder *e, ulcx_decoder *dec, int n, int mode, float p0, float p1, const ulcx_rate *h_rate,
                                               const float *h_pcm, const int32_t *h_len, int nSamples, uint8_t *h_payload, long long payloadStride, int32_t *h_payloadBytes,
                                               int32_t *h_maxBlock, ulcx_index_entry *h_index, int indexStride, int32_t *h_indexBlocks,
                                               int nBlocks, int flags, float *h_coef, int32_t *h_wc, float *h_cplx) {
-    return encode_clips_host_any("ulcx_encode_clips_spectra_host", e, dec, false, n, mode, p0, p1, h_rate, h_pcm, h_len, nSamples, h_payload, payloadStride, h_payloadBytes,
-                                 h_maxBlock, h_index, indexStride, h_indexBlocks, clip_spec(nBlocks, flags, h_coef, h_wc, h_cplx));
+    const ulcx_rung g = clip_rung(mode, p0, p1, h_rate);
+    return encode_clips_host_any("ulcx_encode_clips_spectra_host", e, dec, false, n, &g, 1, false, h_pcm, h_len, nSamples, h_payload, payloadStride, h_payloadBytes,
+                                 h_maxBlock, h_index, indexStride, h_indexBlocks, nullptr, clip_spec(nBlocks, flags, h_coef, h_wc, h_cplx));
 }
 extern "C" int ulcx_analyse_clips_host(ulcx_encoder *e, int n, const float *h_pcm, const int32_t *h_len, int nSamples,
                                        int nBlocks, int flags, float *h_coef, int32_t *h_wc, float *h_cplx) {
-    return encode_clips_host_any("ulcx_analyse_clips_host", e, nullptr, true, n, 0, 0.0f, 0.0f, nullptr, h_pcm, h_len, nSamples, nullptr, 0, nullptr,
-                                 nullptr, nullptr, 0, nullptr, clip_spec(nBlocks, flags, h_coef, h_wc, h_cplx));
+    return encode_clips_host_any("ulcx_analyse_clips_host", e, nullptr, true, n, &kNoRung, 1, false, h_pcm, h_len, nSamples, nullptr, 0, nullptr,
+                                 nullptr, nullptr, 0, nullptr, nullptr, clip_spec(nBlocks, flags, h_coef, h_wc, h_cplx));
 }
 
 // ---- strided corpus -> ragged corpus (include/ulc_amd.h section 3): no object; two kernels of ulcx_clips.hip

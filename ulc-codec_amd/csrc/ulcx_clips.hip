@@ -3,14 +3,19 @@
 // ulcx_encode_clips_*: rows are whole clips in samples, channels-first, each at its own length.  The encoder's kernels are
 // not touched: they still read [rows][K][BlockSize][nChan] interleaved blocks, here from a staging buffer of the object, and
 // write per-block slots, here into slots of the object.  Three kernels of this file stand around them:
-//   k_clip_begin     the shadow state of the call's rows to the state right after create; byte counts and largest blocks to 0
+//   k_clip_begin     the shadow state of the call's rows to the state right after create; byte counts and largest blocks of
+//                    the call's files (rows x rungs) to 0
 //   k_clip_stage     planar samples of rows x blocks [k0, k0 + K) -> the interleaved chunk, zeros outside [0, L_i)
-//   k_clip_append    one workgroup per row: the chunk's blocks that belong to the row (behind nb_i: silence nobody asked for;
-//                    behind the capacity rule: blocks that do not fit) keep their size, every other size becomes 0; the kept
-//                    slots' bytes go behind the row's running payload
+//   k_clip_append    one workgroup per file (row i under rung r is file r * n + i; the plain call: one rung): the chunk's blocks
+//                    that belong to the row (behind nb_i: silence nobody asked for; behind the capacity rule: blocks that do
+//                    not fit) keep their size, every other size becomes 0; the kept slots' bytes go behind the file's running
+//                    payload
 // The index of the chunk is then ulcx_index_slots_dev's two kernels on the masked sizes (ulcx_dec.hip).
 // ulcx_analyse_clips_* / ulcx_encode_clips_spectra_* add k_clip_spec behind the launch sequence: the chunk's MDCT coefficients,
 // window codes and complexities into the caller's channels-first planes.
+// ulcx_encode_clips_ladder_* with a ULCX_RUNG_AUTO rung run an analysis pass in front: k_clip_cplx_sum behind each of its chunks
+// (a row's complexities into one binary64 sum, in block order), k_clip_auto behind the last one (the rows' averages and the
+// AUTO rungs' tables {RateKbps, avg_i}).
 //
 // ulcx_corpus_ragged_*: k_corpus_offsets (one workgroup: the two exclusive int64 prefix sums, the first file that does not
 // fit, the totals) and k_corpus_copy (a file per workgroup).
@@ -41,7 +46,8 @@ __device__ static inline int clip_len(const int32_t *len, int i, int nSamples) {
 // ulcx_clip_blocks on the device (BS a valid block size)
 __device__ static inline int clip_blocks(int BS, int L) { return L >= 1 ? (int)(((long long)L + BS - 1) / BS) + 2 : 0; }
 
-__global__ __launch_bounds__(CLIP_WG) void k_clip_begin(float *hist, UlcxWcState *wcs, int n, int histVec, int32_t *payBytes, int32_t *maxBlock) {
+// n rows of state; nOut >= n counters (the call's files: rows x rungs); sum: the rows' complexity sums of an analysis pass, or NULL
+__global__ __launch_bounds__(CLIP_WG) void k_clip_begin(float *hist, UlcxWcState *wcs, int n, int histVec, int nOut, int32_t *payBytes, int32_t *maxBlock, double *sum) {
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         float4 *h = (float4 *)hist + (size_t)i * histVec;
         for (int v = threadIdx.x; v < histVec; v += CLIP_WG) h[v] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -49,8 +55,9 @@ __global__ __launch_bounds__(CLIP_WG) void k_clip_begin(float *hist, UlcxWcState
         // (enc_reset_state, ulcx_api.cpp: all zero, WindowCtrl of the virtual block -1 and of block 0 = 0x10)
         for (int t = threadIdx.x; t < (int)(sizeof(UlcxWcState) / 4); t += CLIP_WG)
             w[t] = (t == (int)(offsetof(UlcxWcState, wcPrev) / 4) || t == (int)(offsetof(UlcxWcState, wcCur) / 4)) ? 0x10u : 0u;
-        if (threadIdx.x == 0) { payBytes[i] = 0; if (maxBlock) maxBlock[i] = 0; }
+        if (threadIdx.x == 0 && sum) sum[i] = 0.0;
     }
+    for (int j = blockIdx.x * CLIP_WG + threadIdx.x; j < nOut; j += gridDim.x * CLIP_WG) { payBytes[j] = 0; if (maxBlock) maxBlock[j] = 0; }
 }
 
 // Stereo: a lane takes two time steps of both planes and stores one 16-byte interleaved vector {l0, r0, l1, r1}.
@@ -105,14 +112,15 @@ __device__ static inline void wg_copy_bytes(uint8_t *dst, const uint8_t *src, in
     if (tid < n - done) dst[done + tid] = src[done + tid];
 }
 
-// One workgroup per row.  bits [n][K] and slots [n][K][slot] are the object's (what the launch sequence just wrote for blocks
-// [k0, k0 + K) of every row); payBytes / maxBlock / idxBlocks are the caller's running values.  A row is still growing when all
-// its blocks so far were kept, idxBlocks[i] == k0; it keeps the chunk's leading blocks that are the clip's (block number below
-// nb_i), have an index entry left (block number + 1 <= indexStride - 1) and fit the payload's stride.
-__global__ __launch_bounds__(CLIP_WG) void k_clip_append(int K, int k0, int BS, int nSamples, const int32_t *len, int slot, const uint8_t *slots, int32_t *bits,
+// One workgroup per file: file i = r * n + row, the row's clip under rung r (the plain call: n files).  bits [files][K] and slots
+// [files][K][slot] are the object's (what the launch sequence just wrote for blocks [k0, k0 + K) of every row under every rung);
+// payBytes / maxBlock / idxBlocks are the caller's running values, per file.  A file is still growing when all its blocks so far
+// were kept, idxBlocks[i] == k0; it keeps the chunk's leading blocks that are the clip's (block number below nb_row), have an
+// index entry left (block number + 1 <= indexStride - 1) and fit the payload's stride - whatever the row's other files keep.
+__global__ __launch_bounds__(CLIP_WG) void k_clip_append(int n, int K, int k0, int BS, int nSamples, const int32_t *len, int slot, const uint8_t *slots, int32_t *bits,
                                                          uint8_t *payload, long long stride, int32_t *payBytes, int32_t *maxBlock, int indexStride, const int32_t *idxBlocks) {
     const int i = blockIdx.x, tid = threadIdx.x;
-    const int nb = clip_blocks(BS, clip_len(len, i, nSamples));
+    const int nb = clip_blocks(BS, clip_len(len, i % n, nSamples));
     int32_t *rb = bits + (size_t)i * K;
     const long long lim = stride < 0x7FFFFFFFLL ? stride : 0x7FFFFFFFLL;      // (ByteOffs and d_payloadBytes are int32)
     const int off0 = payBytes[i];
@@ -138,6 +146,35 @@ __global__ __launch_bounds__(CLIP_WG) void k_clip_append(int K, int k0, int BS, 
         at += by;
     }
     if (tid == 0) { payBytes[i] = (int32_t)off; if (maxBlock) maxBlock[i] = mx; }
+}
+
+// The analysis pass of a clips ladder call with ULCX_RUNG_AUTO rungs.  A lane per row: the chunk's complexities cplx [n][K] of the
+// row's own blocks (block number below nb_i, whatever a capacity keeps) go to sum[i], one after the other in block order - ONE
+// chain of binary64 additions per row over the whole call (cli/ulcx_tool.c:276-291 = ulcEncodeTool.c:130,164,178).
+__global__ __launch_bounds__(CLIP_WG) void k_clip_cplx_sum(int n, int K, int k0, int BS, int nSamples, const int32_t *len, const float *cplx, double *sum) {
+    const int i = blockIdx.x * CLIP_WG + threadIdx.x;
+    if (i >= n) return;
+    const int nb = clip_blocks(BS, clip_len(len, i, nSamples));
+    double s = sum[i];
+    for (int k = 0; k < K && k0 + k < nb; k++) s += (double)cplx[(size_t)i * K + k];
+    sum[i] = s;
+}
+// Behind the pass's last chunk, a lane per row: avg_i = (float)(S_i / nb_i), 0 for an empty row, to avg[i] (optional) and into
+// the table of every AUTO rung: {the rung's RateKbps - its scalar one or its table's entry for the row -, avg_i}; a table row with
+// RateKbps < 0 stays the VBR row it is.  tables [ULCX_MAX_RUNGS][n]; a rung without AUTO has no table here.
+struct ClipAutoRungs { const float2 *src[ULCX_MAX_RUNGS]; float kbps[ULCX_MAX_RUNGS]; int nRungs; uint32_t autoMask; };
+__global__ __launch_bounds__(CLIP_WG) void k_clip_auto(int n, int BS, int nSamples, const int32_t *len, const double *sum, ClipAutoRungs rg, float2 *tables, float *avg) {
+    const int i = blockIdx.x * CLIP_WG + threadIdx.x;
+    if (i >= n) return;
+    const int nb = clip_blocks(BS, clip_len(len, i, nSamples));
+    const float a = nb ? (float)(sum[i] / (double)nb) : 0.0f;
+    if (avg) avg[i] = a;
+    for (int r = 0; r < rg.nRungs; r++) {
+        if (!((rg.autoMask >> r) & 1u)) continue;
+        float2 v = make_float2(rg.kbps[r], a);
+        if (rg.src[r]) { const float2 t = rg.src[r][i]; v = t.x < 0.0f ? t : make_float2(t.x, a); }
+        tables[(size_t)r * n + i] = v;
+    }
 }
 
 // The tap of ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*.  One workgroup per (row, block of the launch, channel pair):
@@ -266,8 +303,8 @@ __global__ __launch_bounds__(CLIP_WG) void k_corpus_copy(int nFiles, const uint8
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ulcx_set_error("%s: %s", #x, hipGetErrorString(e_)); return ULCX_ERR_HIP; } } while (0)
 static unsigned clip_grid(int n) { return (unsigned)(n < CLIP_GRID ? n : CLIP_GRID); }
 
-int ulcx_clips_begin_launch(float *hist, UlcxWcState *wcs, int n, int C, int BS, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st) {
-    hipLaunchKernelGGL(k_clip_begin, dim3(clip_grid(n)), dim3(CLIP_WG), 0, st, hist, wcs, n, 2 * BS * C / 4, d_payloadBytes, d_maxBlock);
+int ulcx_clips_begin_launch(float *hist, UlcxWcState *wcs, int n, int C, int BS, int nOut, int32_t *d_payloadBytes, int32_t *d_maxBlock, double *sum, hipStream_t st) {
+    hipLaunchKernelGGL(k_clip_begin, dim3(clip_grid(n)), dim3(CLIP_WG), 0, st, hist, wcs, n, 2 * BS * C / 4, nOut, d_payloadBytes, d_maxBlock, sum);
     CK(hipGetLastError());
     return ULCX_OK;
 }
@@ -283,11 +320,28 @@ int ulcx_clips_stage_launch(const float *d_pcm, const int16_t *d_pcm16, const in
     CK(hipGetLastError());
     return ULCX_OK;
 }
-int ulcx_clips_append_launch(int n, int K, int k0, int BS, int nSamples, const int32_t *d_len, int slot, const uint8_t *slots, int32_t *bits,
+int ulcx_clips_append_launch(int n, int nRungs, int K, int k0, int BS, int nSamples, const int32_t *d_len, int slot, const uint8_t *slots, int32_t *bits,
                              uint8_t *d_payload, long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, int indexStride, const int32_t *d_indexBlocks,
                              hipStream_t st) {
-    hipLaunchKernelGGL(k_clip_append, dim3(n), dim3(CLIP_WG), 0, st, K, k0, BS, nSamples, d_len, slot, slots, bits, d_payload, stride, d_payloadBytes, d_maxBlock,
-                       indexStride, d_indexBlocks);
+    hipLaunchKernelGGL(k_clip_append, dim3((unsigned)n * (unsigned)nRungs), dim3(CLIP_WG), 0, st, n, K, k0, BS, nSamples, d_len, slot, slots, bits, d_payload, stride,
+                       d_payloadBytes, d_maxBlock, indexStride, d_indexBlocks);
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+int ulcx_clips_cplx_sum_launch(int n, int K, int k0, int BS, int nSamples, const int32_t *d_len, const float *cplx, double *sum, hipStream_t st) {
+    hipLaunchKernelGGL(k_clip_cplx_sum, dim3((unsigned)((n + CLIP_WG - 1) / CLIP_WG)), dim3(CLIP_WG), 0, st, n, K, k0, BS, nSamples, d_len, cplx, sum);
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+int ulcx_clips_auto_launch(int n, int BS, int nSamples, const int32_t *d_len, const double *sum, const ulcx_rung *rungs, int nRungs, ulcx_rate *tables, float *d_avg,
+                           hipStream_t st) {
+    ClipAutoRungs rg = {};
+    rg.nRungs = nRungs;
+    for (int r = 0; r < nRungs; r++) {
+        rg.src[r] = (const float2 *)rungs[r].rate; rg.kbps[r] = rungs[r].param0;
+        if (rungs[r].reserved & ULCX_RUNG_AUTO) rg.autoMask |= 1u << r;
+    }
+    hipLaunchKernelGGL(k_clip_auto, dim3((unsigned)((n + CLIP_WG - 1) / CLIP_WG)), dim3(CLIP_WG), 0, st, n, BS, nSamples, d_len, sum, rg, (float2 *)tables, d_avg);
     CK(hipGetLastError());
     return ULCX_OK;
 }

@@ -255,12 +255,19 @@ int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_
 // clips (ulcx_clips.hip): the kernels around the launch sequence of ulcx_encode_clips_* - the shadow state of n rows to the state
 // right after create and the caller's byte counts to 0; planar samples of blocks [k0, k0 + K) of every row into the interleaved
 // staging chunk (exactly one of d_pcm / d_pcm16); the chunk's sizes masked and its kept slots appended to the payloads
-int ulcx_clips_begin_launch(float *hist, UlcxWcState *wcs, int n, int C, int BS, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
+// nOut: the byte counters to zero (the call's files, rows x rungs); sum: the rows' complexity sums of an analysis pass to zero, or NULL
+int ulcx_clips_begin_launch(float *hist, UlcxWcState *wcs, int n, int C, int BS, int nOut, int32_t *d_payloadBytes, int32_t *d_maxBlock, double *sum, hipStream_t st);
 int ulcx_clips_stage_launch(const float *d_pcm, const int16_t *d_pcm16, const int32_t *d_len, int nSamples, int n, int C, int BS, int k0, int K,
                             float *stage, hipStream_t st);
-int ulcx_clips_append_launch(int n, int K, int k0, int BS, int nSamples, const int32_t *d_len, int slot, const uint8_t *slots, int32_t *bits,
+// file r * n + i: row i under rung r; slots / bits / the caller's arrays are [nRungs * n]...
+int ulcx_clips_append_launch(int n, int nRungs, int K, int k0, int BS, int nSamples, const int32_t *d_len, int slot, const uint8_t *slots, int32_t *bits,
                              uint8_t *d_payload, long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, int indexStride, const int32_t *d_indexBlocks,
                              hipStream_t st);
+// the analysis pass of a clips ladder call with ULCX_RUNG_AUTO rungs: a chunk's complexities into the rows' ordered binary64 sums;
+// behind the last chunk the averages (d_avg optional) and the AUTO rungs' tables, tables [ULCX_MAX_RUNGS][n]
+int ulcx_clips_cplx_sum_launch(int n, int K, int k0, int BS, int nSamples, const int32_t *d_len, const float *cplx, double *sum, hipStream_t st);
+int ulcx_clips_auto_launch(int n, int BS, int nSamples, const int32_t *d_len, const double *sum, const ulcx_rung *rungs, int nRungs, ulcx_rate *tables, float *d_avg,
+                           hipStream_t st);
 // the tap of ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*: blocks [k0, k0 + kOut) of every row's planes (k0 + kOut <= nBlocks)
 // from the chunk's coef [n][K][C][BS], wc [n][K] and cplx [n][K]; a block at or behind K, or behind the row's own count, is zeros
 int ulcx_clips_spec_launch(int n, int K, int k0, int kOut, int C, int BS, int nSamples, const int32_t *d_len, const float *coef, const int32_t *wc,

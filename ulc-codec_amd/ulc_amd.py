@@ -48,9 +48,11 @@ EXPORTS = [
     "ulcx_decode_crops_spectra_ragged_dev", "ulcx_decode_crops_spectra_ragged_host",
     "ulcx_analyse_clips_dev", "ulcx_analyse_clips_dev_pcm16", "ulcx_analyse_clips_host",
     "ulcx_encode_clips_spectra_dev", "ulcx_encode_clips_spectra_dev_pcm16", "ulcx_encode_clips_spectra_host",
+    "ulcx_encode_clips_ladder_dev", "ulcx_encode_clips_ladder_dev_pcm16", "ulcx_encode_clips_ladder_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
+RUNG_AUTO = 1                                              # ULCX_RUNG_AUTO: Rung.reserved of the clips ladder calls
 SPECTRA_LR = 1                                             # ULCX_SPECTRA_LR: flags of the spectra calls
 
 # one entry of a block index (include/ulc_amd.h, ulcx_index_entry): 8 bytes
@@ -237,6 +239,12 @@ def lib():
             l.ulcx_encode_clips_spectra_dev.argtypes = l.ulcx_encode_clips_dev.argtypes[:-1] + tap_dev + [C.c_void_p]
             l.ulcx_encode_clips_spectra_dev_pcm16.argtypes = l.ulcx_encode_clips_spectra_dev.argtypes
             l.ulcx_encode_clips_spectra_host.argtypes = l.ulcx_encode_clips_host.argtypes + tap_host
+        if hasattr(l, "ulcx_encode_clips_ladder_dev"):     # clips under a rate ladder
+            l.ulcx_encode_clips_ladder_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Rung), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_encode_clips_ladder_dev_pcm16.argtypes = l.ulcx_encode_clips_ladder_dev.argtypes
+            l.ulcx_encode_clips_ladder_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Rung), C.c_int, _f32p, _i32p, C.c_int,
+                                                        _u8p, C.c_longlong, _i32p, _i32p, C.c_void_p, C.c_int, _i32p, _f32p]
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -459,10 +467,19 @@ class BatchEncoder(_StreamSlots):
     @staticmethod
     def _rungs(rungs, table_ptr):
         """ctypes array of ulcx_rung from a list whose entries are (mode, p0[, p1]) or a per-stream table; table_ptr(t) gives
-        the table's address.  No limit on the count here: the library checks it."""
+        the table's address.  The clips ladder calls also take ("auto", kbps) and ("auto_table", table): ULCX_RUNG_AUTO on a
+        scalar ABR rung or on a table rung.  No limit on the count here: the library checks it."""
         arr = (Rung * max(len(rungs), 1))()
         for r, g in enumerate(rungs):
-            if isinstance(g, tuple):
+            if isinstance(g, tuple) and isinstance(g[0], str):
+                if g[0] not in ("auto", "auto_table"):
+                    raise UlcError(f"rung {r}: {g[0]!r} (a mode number, 'auto' or 'auto_table')")
+                arr[r].reserved = RUNG_AUTO
+                if g[0] == "auto":
+                    arr[r].mode, arr[r].param0 = MODE_ABR, float(g[1])
+                else:
+                    arr[r].rate = table_ptr(g[1])
+            elif isinstance(g, tuple):
                 arr[r].mode, arr[r].param0, arr[r].param1 = int(g[0]), float(g[1]), float(g[2]) if len(g) > 2 else 0.0
             else:
                 arr[r].rate = table_ptr(g)
@@ -602,6 +619,49 @@ class BatchEncoder(_StreamSlots):
                                             payload_stride, _p(nbytes, _i32p), _p(maxb, _i32p), index.ctypes.data, index_stride, _p(count, _i32p)),
                "ulcx_encode_clips_host")
         return payload, nbytes, maxb, index, count
+
+    def encode_clips_ladder_dev(self, dec, n, rungs, d_pcm, d_len, n_samples, d_payload, payload_stride, d_payload_bytes, d_index, index_stride, d_index_blocks,
+                                d_max_block=0, d_avg=0, stream=0, pcm16=False):
+        """encode_clips_dev() under several rate settings in one call (ulcx_encode_clips_ladder_dev): rungs as encode_dev_ladder
+        takes them - (mode, p0[, p1]) or the device address of a float32 [n][2] table - and ("auto", kbps) / ("auto_table", table address):
+        two-pass ABR at the clip's own average complexity.  The outputs hold R * n files, file r * n + i = clip i under rung r;
+        d_avg float32 [n] (optional) receives the averages when a rung is "auto"."""
+        arr = self._rungs(rungs, int)
+        fn = lib().ulcx_encode_clips_ladder_dev_pcm16 if pcm16 else lib().ulcx_encode_clips_ladder_dev
+        _check(fn(self.h, dec.h, n, arr, len(rungs), d_pcm, d_len or None, n_samples, d_payload, payload_stride, d_payload_bytes, d_max_block or None,
+                  d_index, index_stride, d_index_blocks, d_avg or None, stream or None),
+               "ulcx_encode_clips_ladder_dev_pcm16" if pcm16 else "ulcx_encode_clips_ladder_dev")
+
+    def encode_clips_ladder(self, dec, wave, lengths=None, rungs=((MODE_VBR, 50.0),), payload_stride=None, index_stride=None):
+        """Host form (ulcx_encode_clips_ladder_host): wave float32 [n][C][T], lengths [n] or None; a rung is (mode, p0[, p1]), a
+        float32 [n][2] table, ("auto", kbps) or ("auto_table", table)
+        -> (payload uint8 [R][n][payload_stride], payload_bytes [R][n], max_block [R][n], index [R][n][index_stride], index_blocks [R][n],
+            avg float32 [n]: the clips' average complexities, zeros without an "auto" rung).  The default strides hold every file in full."""
+        wave = np.ascontiguousarray(wave, dtype=np.float32)
+        n, ch, T = wave.shape
+        assert ch == self.C
+        want = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+        assert want is None or want.shape == (n,)
+        tables = []                                            # (kept alive over the call)
+
+        def host_table(t):
+            t = np.ascontiguousarray(t, dtype=np.float32)
+            assert t.shape == (n, 2)
+            tables.append(t)
+            return t.ctypes.data
+        arr = self._rungs(rungs, host_table)
+        R = len(rungs)
+        nb = clip_blocks(self.BS, T)
+        payload_stride = payload_stride or self.slot * nb
+        index_stride = index_stride or nb + 1
+        payload = np.zeros((max(R, 1), n, payload_stride), np.uint8)
+        nbytes, maxb, count = (np.zeros((max(R, 1), n), np.int32) for _ in range(3))
+        index = np.zeros((max(R, 1), n, index_stride), INDEX_DTYPE)
+        avg = np.zeros(n, np.float32)
+        _check(lib().ulcx_encode_clips_ladder_host(self.h, dec.h, n, arr, R, _p(wave, _f32p), _p(want, _i32p), T, _p(payload, _u8p), payload_stride,
+                                                   _p(nbytes, _i32p), _p(maxb, _i32p), index.ctypes.data, index_stride, _p(count, _i32p), _p(avg, _f32p)),
+               "ulcx_encode_clips_ladder_host")
+        return payload, nbytes, maxb, index, count, avg
 
     def encode_clips_spectra_dev(self, dec, n, d_pcm, d_len, n_samples, d_payload, payload_stride, d_payload_bytes, d_index, index_stride, d_index_blocks,
                                  n_blocks, d_coef, d_wc=0, d_cplx=0, flags=0, d_max_block=0, mode=MODE_VBR, p0=50.0, p1=0.0, d_rates=0, stream=0,
