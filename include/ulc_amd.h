@@ -251,7 +251,7 @@ int  ulcx_encode_host_rates(ulcx_encoder *enc, const ulcx_rate *h_rate, const fl
  * hipStream like its siblings.  With nRungs == 1 the call writes what the plain call writes.  Ladder, plain, _rates and
  * analysis calls may be mixed freely on one encoder.  ulcx_pack_streams_dev takes rung r at d_out + r * nStreams * nBlocks * slot.
  * Test hooks after a ladder call: ulcx_encoder_debug_fetch's kept set and nout are the last rung's (coefficients, noise and
- * keys are the same for every rung); ulcx_encoder_last_fallbacks is the sum over the rungs; the stage times cover rung 0's
+ * keys are the same for every rung); ulcx_encoder_last_fallbacks is the sum over the rungs, ulcx_encoder_debug_writer_flags the last rung's; the stage times cover rung 0's
  * first pass, everything behind it falls into "cbr_probe_passes". */
 #define ULCX_MAX_RUNGS 8
 /* One rung of a ladder call.  A HOST struct (the array is read during the call, not kept).
@@ -294,6 +294,18 @@ int  ulcx_encoder_debug_fetch(ulcx_encoder *enc, int nBlocks, float *h_coef, flo
 /* Number of blocks of the last call (final pass) whose threshold tie group straddled the
  * cut and went through the exact heapsort emulation (BlockTransform.c:20-77).  Test hook. */
 int  ulcx_encoder_last_fallbacks(ulcx_encoder *enc);
+/* Test hooks, read-only: which capacity tier of the wave writer every block of the last encode call ended in, as the call's
+ * final pass (of its last rung) left it.  h_flags [nStreams][nBlocks] (a subset call: its first n rows), per block
+ *   bit 0: a unit overflowed the small capacities, the block left the first launch of k_encode_wave;
+ *   bit 1: the block was left to the serial kernel k_encode_units (a retry launch could not hold it, or there is none);
+ *   bit 2: the wave writer packed the block into its slot itself (stereo, un-decimated; k_pack passes).
+ * Synchronises the device and copies; no kernel, no work in a call that does not ask.  Refuses (ULCX_ERR_ARG) before the first
+ * encode call, after an analysis call and with an nBlocks other than the last call's.
+ * _plan: the capacities {kept coefficients, zones, nybbles} of the small, the medium and the full tier this object launches
+ * with, then haveMid (rate-search probes and the exact path retry on the medium tier, not on the full one) and haveFull (0: one
+ * launch, no retry - what the small capacities cannot hold goes straight to the serial kernel). */
+int  ulcx_encoder_debug_writer_flags(ulcx_encoder *enc, int nBlocks, int32_t *h_flags);
+int  ulcx_encoder_debug_writer_plan(ulcx_encoder *enc, int32_t plan[11]);
 /* Test hook: how the last decode call's synthesis was launched - workgroups (0: one per stream), how many of them took one
  * whole stream each (ulcx_dec_tail_plan; 0 for an even cut, ulcx_dec_split_plan), and the workgroups of the synthesis kernel
  * the device holds at once (0: this geometry runs the general kernel, never cut). */

@@ -31,12 +31,16 @@ def _nybbles(block_bytes):
     return out
 
 
-def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None):
+def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None, units=None):
     """-> (coef [n_chan][block_size] float32, noise_run [n_chan][block_size] int32, nybbles_consumed).
     noise_run is 0 for coded/zero coefficients and the 1-based index of the noise code (run or tail) that produced the
     coefficient otherwise; noise entries of `coef` hold the magnitude.  `kinds`, when a dict, counts the codes read by kind:
     zero_run (0h), long_zero_run (1h), noise_run (8h), tail (Fh,Fh), quantizer (Fh,0h..Dh after the opening one),
-    ext_quantizer (Fh,Eh,0h..Ch, opening one included), stop (Fh,Eh,Fh), coefficient."""
+    ext_quantizer (Fh,Eh,0h..Ch, opening one included), stop (Fh,Eh,Fh), coefficient.
+    `units`, when a list, gets one dict per (channel, sub-block) unit in coded order: ch, j, size, the nybble positions
+    [start, end) of the unit inside the block, nyb = end - start, quantizer_changes (quantizer codes behind the unit's opening
+    one, extended ones included) and max_gap_run_nybbles (the most nybbles of run codes - 0h, 1h, 8h - between two coefficients
+    or in front of the first; runs behind the last coefficient belong to the unit's end, not to a gap)."""
     def tally(k):
         if kinds is not None:
             kinds[k] = kinds.get(k, 0) + 1
@@ -64,14 +68,16 @@ def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None):
     f32 = np.float32
     for ch in range(n_chan):
         base = 0
-        for S in sizes:
+        for j, S in enumerate(sizes):
             n = 0
+            u_start, u_changes, gap, gap_max = pos, 0, 0, 0
             # "Each channel begins with a nybble specifying the initial quantizer, akin to a silent Fh" (:107)
             pending_escape = True
             quant = None
             done = False
             while n < S and not done:
                 opening = pending_escape
+                at = pos
                 v = 0xF if pending_escape else get()
                 pending_escape = False
                 if v == 0xF:
@@ -80,11 +86,13 @@ def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None):
                         quant = f32(2.0) ** f32(-(5 + x))
                         if not opening:
                             tally("quantizer")
+                            u_changes += 1
                     elif x == 0xE:
                         y = get()
                         if y <= 0xC:
                             quant = f32(2.0) ** f32(-(5 + 14 + y))
                             tally("ext_quantizer")
+                            u_changes += 0 if opening else 1
                         elif y == 0xF:
                             tally("stop")
                             done = True                             # Stop: rest zeros (:109-111)
@@ -109,6 +117,7 @@ def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None):
                     if n + run > S:
                         raise SpecError("zero run past the end")
                     n += run
+                    gap += pos - at
                 elif v == 0x1:
                     y, x = get(), get()
                     tally("long_zero_run")
@@ -116,6 +125,7 @@ def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None):
                     if n + run > S:
                         raise SpecError("zero run past the end")
                     n += run
+                    gap += pos - at
                 elif v == 0x8:
                     z, y, x = get(), get(), get()
                     tally("noise_run")
@@ -127,10 +137,15 @@ def decode_block_coefficients(block_bytes, n_chan, block_size, kinds=None):
                     coef[ch, base + n: base + n + run] = level
                     noise[ch, base + n: base + n + run] = run_id
                     n += run
+                    gap += pos - at
                 else:
                     tally("coefficient")
                     s = v - 16 if v >= 8 else v                       # -7..-2, +2..+7
                     coef[ch, base + n] = f32(s * abs(s)) * quant
                     n += 1
+                    gap_max, gap = max(gap_max, gap), 0
+            if units is not None:
+                units.append(dict(ch=ch, j=j, size=S, start=u_start, end=pos, nyb=pos - u_start, quantizer_changes=u_changes,
+                                  max_gap_run_nybbles=gap_max))
             base += S
     return coef, noise, pos

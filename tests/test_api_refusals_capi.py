@@ -75,7 +75,7 @@ def test_the_header_was_understood():
     for n in ("ulcx_encode_dev", "ulcx_encode_host_ladder", "ulcx_analyse_dev_pcm16", "ulcx_encode_block1", "ulcx_decode_block1_rng",
               "ulcx_decode_range_dev_pcm16", "ulcx_decode_resident_range_host", "ulcx_decoder_upload_payload", "ulcx_decoder_last_cut",
               "ulcx_encoder_set_timing", "ulcx_decoder_set_timing", "ulcx_encoder_debug_force_exact", "ulcx_encoder_reset",
-              "ulcx_decoder_load_streams_host", "ulcx_index_packed_dev"):
+              "ulcx_decoder_load_streams_host", "ulcx_index_packed_dev", "ulcx_encoder_debug_writer_flags", "ulcx_encoder_debug_writer_plan"):
         assert n in COVERED, n
     assert len(COVERED) >= 57, len(COVERED)
     assert not [n for n in ENTRIES if "create" in n or "destroy" in n or "stage_name" in n or "state_bytes" in n]

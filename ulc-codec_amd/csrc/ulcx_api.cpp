@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "ulcx_internal.h"
+#include "ulcx_enc_dev.h"                 // (WaveCaps, WAVE_S*, wavecaps_lds: ulcx_encoder_debug_writer_plan)
 #include "ulcx_rng_tables.h"
 
 
@@ -1238,6 +1239,37 @@ extern "C" int ulcx_encoder_last_fallbacks(ulcx_encoder *e) {
     int n[2] = { 0, 0 };                                               // this call's (last rung's) count; a ladder call: the rungs in front of it
     CKR(hipMemcpy(n, e->ctx.fbCount, sizeof(n), hipMemcpyDeviceToHost));
     return n[0] + (e->lastRungs > 1 ? n[1] : 0);
+}
+// Test hooks: the wave writer's give-up bits of the last call's final pass (c.slow[0 .. B*K)), and the capacities it launches with.
+// The capacities are enc_plan's (ulcx_enc.hip), restated over the same constants and the same LDS formula (ulcx_enc_dev.h): that
+// translation unit holds kernels and is not rebuilt for a test hook.  tests/test_gpu_writer_tiers.py pins the values per geometry.
+static void ulcx_enc_writer_plan(const UlcxEncCtx &c, int caps[3][3], int *haveMid, int *haveFull) {
+    const WaveCaps capS = { WAVE_SK, WAVE_SZ, WAVE_SN }, capM = { 1024, 512, 4096 };
+    WaveCaps capF = { (c.BS + 63) & ~63, ((c.BS / 2) + 63) & ~63, 4 * c.BS + 64 };
+    while ((size_t)wavecaps_lds(capF) * 4 > 150 * 1024) { capF.k = (capF.k / 2 + 63) & ~63; capF.z = (capF.z / 2 + 63) & ~63; capF.nyb = capF.nyb / 2 + 32; }
+    const WaveCaps t[3] = { capS, capM, capF };
+    for (int i = 0; i < 3; i++) { caps[i][0] = t[i].k; caps[i][1] = t[i].z; caps[i][2] = t[i].nyb; }
+    *haveFull = capF.k > capS.k;
+    *haveMid = capM.k < capF.k;
+}
+extern "C" int ulcx_encoder_debug_writer_flags(ulcx_encoder *e, int nBlocks, int32_t *h_flags) {
+    const char *who = "ulcx_encoder_debug_writer_flags";
+    if (!e || !h_flags) return refuse(who, "no encoder, or no array");
+    if (e->lastAnalyse) return refuse(who, "the last call was an analysis call (no writer ran)");
+    if (e->lastRungs < 1 || nBlocks != e->lastK) return refuse(who, "nBlocks is not the last encode call's (or there was none)");
+    CKR(hipSetDevice(e->device));
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(h_flags, e->ctx.slow, sizeof(int32_t) * (size_t)e->B * nBlocks, hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+extern "C" int ulcx_encoder_debug_writer_plan(ulcx_encoder *e, int32_t plan[11]) {
+    const char *who = "ulcx_encoder_debug_writer_plan";
+    if (!e || !plan) return refuse(who, "no encoder, or no array");
+    int caps[3][3], haveMid = 0, haveFull = 0;
+    ulcx_enc_writer_plan(e->ctx, caps, &haveMid, &haveFull);
+    for (int t = 0; t < 3; t++) for (int i = 0; i < 3; i++) plan[3 * t + i] = caps[t][i];
+    plan[9] = haveMid; plan[10] = haveFull;
+    return ULCX_OK;
 }
 extern "C" const char *ulcx_encoder_stage_name(int i) { return (i >= 0 && i < ULCX_ENC_STAGES_REPORTED) ? ulcx_enc_stage_names[i] : ""; }
 extern "C" int ulcx_encoder_stage_ms(ulcx_encoder *e, float *ms, int maxStages) {

@@ -21,7 +21,7 @@ EXPORTS = [
     "ulcx_last_error", "ulcx_device_count", "ulcx_encoder_create", "ulcx_encoder_destroy", "ulcx_encoder_reset",
     "ulcx_encoder_slot_bytes", "ulcx_encode_dev", "ulcx_encode_dev_pcm16", "ulcx_encode_host", "ulcx_encoder_debug_fetch",
     "ulcx_decoder_create", "ulcx_decoder_destroy", "ulcx_decoder_reset", "ulcx_decode_dev", "ulcx_decode_dev_pcm16", "ulcx_decode_host",
-    "ulcx_encoder_last_fallbacks", "ulcx_encoder_debug_force_exact", "ulcx_ulc_header_pack", "ulcx_ulc_header_parse", "ulcx_ulc_rate_kbps",
+    "ulcx_encoder_last_fallbacks", "ulcx_encoder_debug_force_exact", "ulcx_encoder_debug_writer_flags", "ulcx_encoder_debug_writer_plan", "ulcx_ulc_header_pack", "ulcx_ulc_header_parse", "ulcx_ulc_rate_kbps",
     "ulcx_pack_streams_dev", "ulcx_decode_packed_dev", "ulcx_decode_packed_host", "ulcx_decoder_upload_payload", "ulcx_decode_resident_host", "ulcx_encoder_stage_ms", "ulcx_encoder_stage_name", "ulcx_encoder_last_xf_launches", "ulcx_decoder_stage_ms", "ulcx_decoder_stage_name", "ulcx_block_extent_bytes", "ulcx_encoder_set_timing", "ulcx_decoder_set_timing", "ulcx_encode_block1", "ulcx_decode_block1", "ulcx_decode_block1_rng", "ulcx_build_rev", "ulcx_dec_split_plan", "ulcx_dec_tail_plan", "ulcx_decoder_last_cut",
     "ulcx_encode_dev_rates", "ulcx_encode_dev_pcm16_rates", "ulcx_encode_host_rates",
     "ulcx_analyse_dev", "ulcx_analyse_dev_pcm16", "ulcx_analyse_host",
@@ -253,6 +253,8 @@ def lib():
         l.ulcx_decode_dev_pcm16.argtypes = l.ulcx_decode_dev.argtypes
         l.ulcx_decode_host.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_int, _f32p, _i32p]
         l.ulcx_encoder_last_fallbacks.argtypes = [C.c_void_p]
+        l.ulcx_encoder_debug_writer_flags.argtypes = [C.c_void_p, C.c_int, _i32p]
+        l.ulcx_encoder_debug_writer_plan.argtypes = [C.c_void_p, _i32p]
         l.ulcx_decoder_last_cut.argtypes = [C.c_void_p, _i32p, _i32p, _i32p]
         l.ulcx_dec_tail_plan.argtypes = [C.c_int, C.c_int, C.c_int, _i32p]
         l.ulcx_encoder_debug_force_exact.argtypes = [C.c_void_p, C.c_int]
@@ -747,6 +749,22 @@ class BatchEncoder(_StreamSlots):
 
     def last_fallbacks(self):
         return lib().ulcx_encoder_last_fallbacks(self.h)
+
+    def writer_flags(self, K=None):
+        """int32 [B][K]: the wave writer's tier of every block of the last encode call (bit 0: left the small-capacity launch,
+        bit 1: left to the serial kernel, bit 2: packed by the wave writer itself).  Test hook."""
+        K = K or self.lastK
+        flags = np.zeros((self.B, K), np.int32)
+        _check(lib().ulcx_encoder_debug_writer_flags(self.h, K, _p(flags, _i32p)), "ulcx_encoder_debug_writer_flags")
+        return flags
+
+    def writer_plan(self):
+        """The wave writer's capacity tiers of this object: dict small / medium / full -> (kept, zones, nybbles), have_mid,
+        have_full.  Test hook."""
+        p = np.zeros(11, np.int32)
+        _check(lib().ulcx_encoder_debug_writer_plan(self.h, _p(p, _i32p)), "ulcx_encoder_debug_writer_plan")
+        return dict(small=tuple(int(v) for v in p[0:3]), medium=tuple(int(v) for v in p[3:6]), full=tuple(int(v) for v in p[6:9]),
+                    have_mid=bool(p[9]), have_full=bool(p[10]))
 
     def force_exact(self, every):
         _check(lib().ulcx_encoder_debug_force_exact(self.h, int(every)), "ulcx_encoder_debug_force_exact")
