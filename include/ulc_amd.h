@@ -738,6 +738,49 @@ int  ulcx_decode_crops_spectra_ragged_host(ulcx_decoder *dec, int nFiles,
                                            const int32_t *h_indexBlocks,
                                            int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
                                            int nBlocks, int flags, float *h_coef, int32_t *h_wc, int32_t *h_bits);   /* synchronous */
+/* Synthesis from spectra: the way back - PCM from caller-held MDCT planes, through the decoder's own inverse transform (pre-twiddle,
+ * FFT, post-twiddle with the windowed overlap, the centring of decimated sub-blocks, lapping state), the very kernels the crop
+ * calls run, with the syntax walk replaced by loads from the planes.  For models that work on the planes of the spectra calls or
+ * of the clip-spectra calls (section 2) and have to be heard and scored in the time domain.
+ *   d_coef  float32 [n][nChan][nBlocks][BlockSize], d_wc int32 [n][nBlocks]: layout, sub-block order and window-code convention are
+ *           exactly what ulcx_decode_crops_spectra_*, ulcx_analyse_clips_* and ulcx_encode_clips_spectra_* write - their outputs go
+ *           in unchanged.  THE WINDOW CODES MUST ACCOMPANY THE PLANES: they say how a plane splits into sub-blocks and which
+ *           window overlaps them.  n is 1 .. nStreams.
+ *   flags   ULCX_SYNTH_WARM: plane 0 of every row is the block in FRONT of the output: it is transformed for the lapping state
+ *           and the LastSubBlockSize it leaves, and has no output.  nOut = nBlocks - (WARM ? 1 : 0) is 1 .. maxBlocksPerCall - 1
+ *           (the call uses the object's per-block scratch rows, as the crop calls do).
+ *           ULCX_SPECTRA_LR: the planes already hold left/right, and the time-domain un-mix (ulcDecoder.c:281-289) is skipped.
+ *           Without it the pairs (0,1), (2,3), ... are un-mixed as the decoder does it; a trailing single channel is left alone.
+ *           Any other bit: ULCX_ERR_ARG.
+ *   d_pcm   [n][nChan][nOut * BlockSize], channels-first as the sample crops are, written in full.  Output block k of row i is,
+ *           bit for bit, what a freshly initialised reference decoder (LastSubBlockSize 0, TransformInvLap zero) writes that holds
+ *           the row's planes in TransformBuffer and d_wc[i][k] in WindowCtrl, block after block, from ulcDecoder.c:217 on.  The
+ *           PCM16 form rounds as every PCM16 form does (lrintf of the clamped sample * 2^15).
+ *           The PCM of a block depends on the planes and codes of that block and the one in front only.  Hence
+ *           ulcx_decode_crops_spectra_dev(first - 1, nBlocks + 1), then this call with ULCX_SYNTH_WARM, is bit for bit
+ *           ulcx_decode_crops_samples_dev of nBlocks whole blocks from block `first`; without WARM the same holds for rows with
+ *           first = 0.  Without WARM on planes from mid-stream only output block 0 differs (it laps against silence).
+ *           d_pcm must not overlap d_coef (not checked).
+ *   d_live  int32 [n][nOut]: 1 where the block was synthesised, 0 where it was not.  A row ends at its first plane whose code
+ *           fails ulcx_window_subblocks(BlockSize, wc, NULL) > 0 - 0, the spectra calls' "not live", and any int32 no block can
+ *           carry: that block and everything behind it come out as +0.0 samples and live 0, as a corrupt block ends a decode; a
+ *           bad plane in front (WARM) ends the whole row.  Other rows are untouched.  d_wc is not trusted: it is validated on the
+ *           device before it steers anything.  Coefficient VALUES are not inspected: NaN and Inf travel through the arithmetic
+ *           and cannot leave the two blocks and the row they belong to.
+ * STATE / ORDER: the call reads and changes no stream's persistent state (it runs on the compact state copy of the subset and crop
+ * calls) and mixes freely with every other call on the object; it allocates nothing after the first subset or crop call; the
+ * device forms are asynchronous on hipStream (two kernels: the rows' prologue, the synthesis).  The launch plan is the range
+ * call's for the same n and nOut: few long rows are cut evenly, a workgroup that enters a row mid-way runs the plane in front
+ * without output; ulcx_decoder_last_cut reports it.
+ * ALIGNMENT: d_coef and d_pcm 16 bytes; d_pcm16, d_wc and d_live 4; a misaligned or NULL pointer returns ULCX_ERR_ARG before any
+ * device work. */
+#define ULCX_SYNTH_WARM 2   /* flags: plane 0 of every row is the block in front of the output (see above) */
+int  ulcx_synth_spectra_dev(ulcx_decoder *dec, int n, int nBlocks, int flags, const float *d_coef, const int32_t *d_wc,
+                            float *d_pcm, int32_t *d_live, void *hipStream);
+int  ulcx_synth_spectra_dev_pcm16(ulcx_decoder *dec, int n, int nBlocks, int flags, const float *d_coef, const int32_t *d_wc,
+                                  int16_t *d_pcm16, int32_t *d_live, void *hipStream);
+int  ulcx_synth_spectra_host(ulcx_decoder *dec, int n, int nBlocks, int flags, const float *h_coef, const int32_t *h_wc,
+                             float *h_pcm, int32_t *h_live);   /* synchronous */
 /* The index of a ragged corpus in one call: row f receives, entry for entry, what ulcx_index_packed_rows_dev writes for file f's
  * payload alone with maxBlocks = capacity - 1, the {-1, 0} entries behind the closing one up to the row's capacity included, and
  * d_nBlocks[f] the count.  A row of capacity below 1, or a file whose offsets are as refused above, gets d_nBlocks[f] = 0 and no

@@ -8,6 +8,8 @@
     pcm, bits = corpus.crops(dec, files, first, crop_blocks)      # [n][crop_blocks * 2048][2] on the device
     pcm, bits = corpus.sample_crops(dec, files, start, n_samples) # [n][2][n_samples]: n_samples from sample start[i], channels-first
                                                                   # (dec: max_blocks > ulc_amd.crop_blocks(2048, n_samples))
+    coef, wc, bits = corpus.spectra(dec, files, first, n_blocks)  # [n][2][n_blocks][2048]: the dequantised MDCT coefficients
+    pcm, live = synth_spectra(dec, coef, wc, warm=True)           # and back: [n][2][(n_blocks - 1) * 2048], plane 0 the block in front
 
 CropCorpus(..., layout="ragged") keeps every file at its own length (payloads and index rows back to back behind offset tables,
 ulcx_decode_crops_ragged_dev) instead of at the longest file's: the layout for a corpus of files of very different length.
@@ -69,6 +71,40 @@ def clip_spectra(enc, wave, lengths=None, n_blocks=None, lr=False):
         enc.analyse_clips_dev(n, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, depth, coef.data_ptr(), wc.data_ptr(), cplx.data_ptr(),
                               flags=ulc_amd.SPECTRA_LR if lr else 0, stream=torch.cuda.current_stream(dev).cuda_stream, pcm16=pcm16)
     return coef, wc, cplx
+
+
+def synth_spectra(dec, coef, wc, *, lr=False, warm=False, pcm16=False):
+    """PCM from MDCT planes held in torch tensors, through the decoder's own inverse transform (ulcx_synth_spectra_dev): coef float32
+    [n][C][n_blocks][BS] and wc int32 [n][n_blocks] on one device, as CropCorpus.spectra(), clip_spectra() and from_clips_spectra()
+    leave them - the window codes must come with the planes.  -> (pcm [n][C][n_out * BS] float32, or int16 with pcm16; live int32
+    [n][n_out]) on that device, enqueued on torch's current stream.  warm: plane 0 of every row is the block in front of the output
+    (n_out = n_blocks - 1, else n_blocks); lr: the planes hold left / right, nothing is un-mixed.  Contiguous input is not copied.
+    dec: a BatchDecoder with n_streams >= n and max_blocks > n_out; no stream of it changes."""
+    import torch
+    if coef.dim() != 4 or wc.dim() != 2:
+        raise UlcError(f"synth spectra: planes of {coef.dim()} dimensions and codes of {wc.dim()} ([n][C][n_blocks][BS] and [n][n_blocks])")
+    n, ch, depth, bs = coef.shape
+    if ch != dec.C or bs != dec.BS:
+        raise UlcError(f"synth spectra: planes of {bs} x {ch}, a decoder of {dec.BS} x {dec.C}")
+    if tuple(wc.shape) != (n, depth):
+        raise UlcError(f"synth spectra: codes {tuple(wc.shape)} beside planes of {n} rows x {depth} blocks")
+    if coef.dtype != torch.float32 or wc.dtype != torch.int32:
+        raise UlcError(f"synth spectra: planes {coef.dtype} (float32), codes {wc.dtype} (int32)")
+    if wc.device != coef.device or not coef.is_cuda:
+        raise UlcError(f"synth spectra: planes on {coef.device}, codes on {wc.device} (one GPU)")
+    n_out = depth - (1 if warm else 0)
+    if n < 1 or n_out < 1:
+        raise UlcError(f"synth spectra: {n} rows of {n_out} output blocks")
+    dev = coef.device
+    coef = coef.contiguous()
+    wc = wc.contiguous()
+    pcm = torch.empty((n, ch, n_out * bs), dtype=torch.int16 if pcm16 else torch.float32, device=dev)
+    live = torch.empty((n, n_out), dtype=torch.int32, device=dev)
+    flags = (ulc_amd.SPECTRA_LR if lr else 0) | (ulc_amd.SYNTH_WARM if warm else 0)
+    with torch.cuda.device(dev):
+        dec.synth_spectra_dev(n, depth, flags, coef.data_ptr(), wc.data_ptr(), pcm.data_ptr(), live.data_ptr(),
+                              stream=torch.cuda.current_stream(dev).cuda_stream, pcm16=pcm16)
+    return pcm, live
 
 
 def _spectra_planes(n, ch, depth, block_size, dev):

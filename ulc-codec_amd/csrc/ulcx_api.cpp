@@ -2394,6 +2394,72 @@ extern "C" int ulcx_decode_crops_samples_ragged_host(ulcx_decoder *e, int nFiles
     rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, sg.file, nullptr, nullptr, nB, sg.pcm, nullptr, sg.bits, nullptr, &dg, &sm);
     return rc ? rc : sample_results_down(e, sg, n, nB, nSamples, h_pcm, h_bits);
 }
+// ---- synthesis from spectra (include/ulc_amd.h section 3): the decoder's inverse transform on caller-held planes.  The range
+// synthesis of a crop call without any walk in front: the call runs on the shadow state as the crop calls do (dec_shadow; nothing
+// is scattered back), on the object's per-block rows, under the range call's launch plan for n rows of nOut blocks.
+// The checks of every synth entry, device or host pointers; *nOut: the blocks per row that come out
+static int synth_args_bad(const char *who, const ulcx_decoder *e, int n, int nBlocks, int flags, const void *coef, const void *wc, const void *pcm, const void *live, int *nOut) {
+    if (flags & ~(ULCX_SPECTRA_LR | ULCX_SYNTH_WARM)) { refuse(who, "bad argument (flags 0x%x: ULCX_SPECTRA_LR, ULCX_SYNTH_WARM)", (unsigned)flags); return 1; }
+    if (!coef || !wc || !pcm || !live) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
+    if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
+    if (!e) { refuse(who, "no decoder"); return 1; }
+    if (n > e->B) { refuse(who, "bad argument (n %d: a call takes 1 .. nStreams = %d rows)", n, e->B); return 1; }
+    const int warm = (flags & ULCX_SYNTH_WARM) ? 1 : 0;
+    if (nBlocks < 1 + warm || nBlocks - warm > e->maxK - 1) {
+        refuse(who, "bad argument (nBlocks %d: %d .. %d%s)", nBlocks, 1 + warm, e->maxK - 1 + warm, warm ? " with the plane in front" : "");
+        return 1;
+    }
+    if ((long long)(nBlocks - warm) * e->BS > 0x7FFFFFFFLL) { refuse(who, "bad argument (a row of %d blocks exceeds 2^31 samples)", nBlocks - warm); return 1; }
+    *nOut = nBlocks - warm;
+    return 0;
+}
+static int synth_spectra_any(const char *who, ulcx_decoder *e, int n, int nBlocks, int flags, const float *d_coef, const int32_t *d_wc,
+                             float *d_pcm, int16_t *d_pcm16, int32_t *d_live, void *hipStream) {
+    int nOut = 0;
+    if (synth_args_bad(who, e, n, nBlocks, flags, d_coef, d_wc, d_pcm ? (const void *)d_pcm : d_pcm16, d_live, &nOut)) return ULCX_ERR_ARG;
+    if (misaligned(who, "d_coef", d_coef, ULCX_ALIGN_PCM) || misaligned(who, "d_wc", d_wc, ULCX_ALIGN_WORD) || misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) ||
+        misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_WORD) || misaligned(who, "d_live", d_live, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    // (d_pcm16 at 4 bytes: the sample store mode pairs its stores only where a plane's address allows it)
+    CKR(hipSetDevice(e->device));
+    int rc = dec_shadow(e);
+    if (rc) return rc;
+    UlcxDecCtx c = e->ctx;
+    c.B = n; c.K = nOut + 1; c.slot = 0; c.in = nullptr; c.inBytes = 0; c.pcm = d_pcm; c.pcm16 = d_pcm16;
+    c.bits = e->bitsScr; c.bitsOut = d_live;
+    c.packed = 1; c.payStride = 0; c.payBytes = nullptr;
+    c.range = 1; c.rIndex = nullptr; c.rIndexStride = 0; c.rIndexBlocks = nullptr; c.rFirst = nullptr;
+    c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
+    UlcxDecAux syn = {};
+    syn.synCoef = d_coef; syn.synWc = d_wc; syn.synPlanes = nBlocks; syn.synLR = (flags & ULCX_SPECTRA_LR) ? 1 : 0;
+    syn.nSamples = nOut * e->BS;
+    syn.sampSkip = e->sampRows + 2 * (size_t)e->B; syn.sampLenC = e->sampRows + 3 * (size_t)e->B;
+    int set = 0;
+    rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &syn);
+    e->evRecorded = (rc == ULCX_OK) && e->timing;
+    return rc;
+}
+extern "C" int ulcx_synth_spectra_dev(ulcx_decoder *e, int n, int nBlocks, int flags, const float *d_coef, const int32_t *d_wc, float *d_pcm, int32_t *d_live,
+                                      void *hipStream) {
+    return synth_spectra_any("ulcx_synth_spectra_dev", e, n, nBlocks, flags, d_coef, d_wc, d_pcm, nullptr, d_live, hipStream);
+}
+extern "C" int ulcx_synth_spectra_dev_pcm16(ulcx_decoder *e, int n, int nBlocks, int flags, const float *d_coef, const int32_t *d_wc, int16_t *d_pcm16, int32_t *d_live,
+                                            void *hipStream) {
+    return synth_spectra_any("ulcx_synth_spectra_dev_pcm16", e, n, nBlocks, flags, d_coef, d_wc, nullptr, d_pcm16, d_live, hipStream);
+}
+extern "C" int ulcx_synth_spectra_host(ulcx_decoder *e, int n, int nBlocks, int flags, const float *h_coef, const int32_t *h_wc, float *h_pcm, int32_t *h_live) {
+    const char *who = "ulcx_synth_spectra_host";
+    int nOut = 0;
+    if (synth_args_bad(who, e, n, nBlocks, flags, h_coef, h_wc, h_pcm, h_live, &nOut)) return ULCX_ERR_ARG;
+    CKR(hipSetDevice(e->device));
+    const size_t nCoef = (size_t)n * e->C * (size_t)nBlocks * e->BS, nWc = (size_t)n * nBlocks, NB = (size_t)n * nOut;
+    DevTmp t; float *dcoef = nullptr, *dpcm = nullptr; int32_t *dwc = nullptr, *dlive = nullptr;
+    CKR(t.get(&dcoef, sizeof(float) * nCoef)); CKR(t.get(&dwc, sizeof(int32_t) * nWc));
+    CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dlive, sizeof(int32_t) * NB));
+    CKR(hipMemcpy(dcoef, h_coef, sizeof(float) * nCoef, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dwc, h_wc, sizeof(int32_t) * nWc, hipMemcpyHostToDevice));
+    const int rc = synth_spectra_any(who, e, n, nBlocks, flags, dcoef, dwc, dpcm, nullptr, dlive, nullptr);
+    return rc ? rc : dec_results_down(e, dpcm, dlive, NB, h_pcm, h_live);
+}
 // ulcx_index_packed_rows_* for files back to back: k_dindex_ragged over nFiles (geometry and tables are all that is read of the object)
 static int index_ragged_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, const CropsRagged &g, ulcx_index_entry *d_index,
                             int32_t *d_nBlocks, void *hipStream) {

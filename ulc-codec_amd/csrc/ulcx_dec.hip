@@ -998,6 +998,56 @@ __global__ __launch_bounds__(64) void k_crop_sample_rows(int n, int BS, int nSam
     lenC[i] = ok ? l : 0;
 }
 
+// ---------------------------------------------------------------------------
+// Plane source mode (ulcx_synth_spectra_*): the synthesis of caller-held coefficients.  A second further argument beside the
+// sample store mode's (k_dsyn<..., UlcxSampArg, UlcxPlaneArg<LR>>; RANGE launches only): where the other instantiations
+// dequantise a unit from the walk's records (synth_unit), these load its S floats from the row's plane - coef
+// [row][channel][nPl][BS], a block's subblocks in coded order, what the spectra calls write - into the same padded array, and
+// everything behind that is the one shared text.  No walk has run: k_synth_rows wrote the rows the synthesis reads (window
+// codes, liveness), and nothing of the walk's records, draws or generator states is looked at.
+// LR: the planes hold left/right already - the time-domain un-mix (ulcDecoder.c:281-289) is skipped, each channel stored as it stands.
+// Row k of a stream's K per-block rows is plane k - (K - nPl): nPl = K when plane 0 is the block in front (ULCX_SYNTH_WARM), else K - 1.
+template <bool LR> struct UlcxPlaneArg { const float *coef; int nPl; };
+struct UlcxPlaneNone {};
+template <typename... SA> struct SynSrc { static constexpr bool plane = false, lr = false; };
+template <bool LR_> struct SynSrc<UlcxSampArg, UlcxPlaneArg<LR_>> { static constexpr bool plane = true, lr = LR_; };
+template <bool LR> __device__ __forceinline__ const UlcxSampArg &samp_arg(const UlcxSampArg &a, const UlcxPlaneArg<LR> &) { return a; }
+__device__ __forceinline__ UlcxPlaneNone plane_arg() { return UlcxPlaneNone{}; }
+__device__ __forceinline__ UlcxPlaneNone plane_arg(const UlcxSampArg &) { return UlcxPlaneNone{}; }
+template <bool LR> __device__ __forceinline__ const UlcxPlaneArg<LR> &plane_arg(const UlcxSampArg &, const UlcxPlaneArg<LR> &p) { return p; }
+__device__ __forceinline__ const float *plane_of(const UlcxPlaneNone &, int, int, int, int, int, int) { return nullptr; }
+template <bool LR> __device__ __forceinline__ const float *plane_of(const UlcxPlaneArg<LR> &p, int row, int C, int ch, int K, int k, int BS) {
+    return p.coef + (((size_t)row * C + ch) * p.nPl + (k - (K - p.nPl))) * (size_t)BS;
+}
+// S coefficients at src (16-byte aligned, read once) into the padded array A; thread t0 of `step`.  DPS 4: four floats at a
+// multiple of four never straddle a padding gap (spec_ld4).  The padding itself is never read by the transform.
+__device__ __forceinline__ void plane_unit(float *A, const float *__restrict__ src, int S, int t0, int step) {
+    static_assert(DPS == 4, "plane_unit: four consecutive floats stay clear of the padding gaps");
+    for (int i = 4 * t0; i < S; i += 4 * step) {
+        const f32x4 v = __builtin_nontemporal_load((const f32x4 *)(src + i));
+        float *d = A + padf(i);
+        *(float2 *)d = make_float2(v.x, v.y); *(float2 *)(d + 2) = make_float2(v.z, v.w);
+    }
+}
+// The rows of a synth call, one lane per (row, per-block row) - what a walk would have left for the RANGE synthesis, from the
+// caller's window codes alone.  wc [n][nPl] is not trusted: a code is taken when ulcx_window_subblocks accepts it (the codes a
+// block can carry, ulcDecoder.c:211-216: 0 .. 0xFF, the second nybble only behind a first with bit 3 set), every other int32
+// becomes 0, the mark of a corrupt block - the row ends there.  Nothing is drawn (draws 0), a live row's size is 1 (bitsOut
+// then carries the caller's `live`), the row is entered as a range is: {1 = row 0 holds the block in front, generator state 0}.
+// Without WARM row 0 is empty and the planes sit in rows 1 .. K-1, as in a range call from block 0.
+__global__ __launch_bounds__(64) void k_synth_rows(int n, int K, int nPl, const int32_t *wc, int *wcScan, int *draws, int *bits, int2 *rInfo,
+                                                   int32_t *skip, int32_t *len, int lenAll) {
+    const long long id = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (id >= (long long)n * K) return;
+    const int s = (int)(id / K), r = (int)(id - (long long)s * K);
+    const int p = r - (K - nPl);
+    int w = p >= 0 ? wc[(size_t)s * nPl + p] : 0;
+    const bool ok = w > 0 && w <= 0xFF && ((w & 8) || (w >> 4) == 1);
+    w = ok ? w : 0;
+    wcScan[id] = w; draws[id] = 0; bits[id] = ok ? 1 : 0;
+    if (r == 0) { rInfo[s] = make_int2(nPl == K ? 1 : 0, 0); skip[s] = 0; len[s] = lenAll; }
+}
+
 // LDS carve, in floats.  Stereo kernel (k_dsyn):  z [2 padded arrays of BS/2 complex] | twl [BS/4 complex] |
 //   per wave: noise runs, prefix counts, seed table | 128 block / unit seeds.  General kernel (k_dgen): z [1 array] | per-wave lists.
 #define DSYN_PWORDS(BS) (((BS) / 32 > 64 ? (BS) / 32 : 64) + 2)
@@ -1033,6 +1083,8 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
     constexpr bool SAMP = sizeof...(SA) != 0;
     static_assert(!SAMP || RANGE, "k_dsyn: sample crops are range launches");
     const auto &samp = samp_arg(sa...);
+    constexpr bool PLANE = SynSrc<SA...>::plane, LR = SynSrc<SA...>::lr;      // the plane source mode (UlcxPlaneArg): no records, no generator
+    const auto &pla = plane_arg(sa...);
     extern __shared__ float lds[];
     const int BS = BSC ? BSC : c.BS, H2 = BS / 2;
     constexpr int C = 2;
@@ -1119,20 +1171,22 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
             for (int j = kf + tid; j < k; j += WG) {                 // blocks of the launch in front of k (none at the stream's start)
                 const int bj = s * c.K + j;
                 if (c.wcScan[bj] == 0) bad = 1;
-                dsum += (uint32_t)c.draws[bj];
+                if constexpr (!PLANE) dsum += (uint32_t)c.draws[bj];
             }
             bad = __syncthreads_or(bad);
             dead = RANGE ? bad : (c.dead[s] | bad);                  // (a corrupt block in front: the stream is dead, no other state matters)
             lastSub = RANGE ? 0 : c.lastSub[s];
-            seed = RANGE ? (uint32_t)c.rInfo[s].y : c.seed[s];
+            if constexpr (!PLANE) seed = RANGE ? (uint32_t)c.rInfo[s].y : c.seed[s];
             if constexpr (SAMP) { rowSkip = samp.skip[s]; rowLen = samp.len[s]; }
             if constexpr (RANGE) { if (k == c.k0 && kf == c.k0) for (int i = tid; i < 2 * H2; i += WG) scr[i] = 0.0f; }   // a range from block 0: nothing pending (ordered by the barrier in front of the chunk's tables)
             if (k > kf) {
+                if constexpr (!PLANE) {
                 const uint32_t ws = wave_scan_add(dsum);             // (lane 63: the wave's sum)
                 if (lane == 63) bseed[wv] = ws;
                 __syncthreads();
                 seed = rng_jump(c.jumpT, seed, bseed[0] + bseed[1]);
                 __syncthreads();
+                }
                 lastSub = last_sub_size(BS, c.wcScan[blk - 1]);              // as block k-1 left it
             }
             chunkK = -1;
@@ -1147,6 +1201,10 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
             const int kk = k + lane, bk = s * c.K + (kk < c.k1 && lane < DSYN_CHUNK ? kk : k);
             const bool on = kk < c.k1 && lane < DSYN_CHUNK;
             const int wcl = c.wcScan[bk];
+            if constexpr (PLANE) {                                   // the chunk's tables keep the window codes only
+                if (lane < DSYN_CHUNK) hdr[lane * 8] = wcl;
+                __syncthreads();
+            } else {
             const int drb = c.draws[bk];
             const int ud4 = c.unitDraws[(size_t)bk * C * 4 + 4];
             const int4 url = c.unitRec[(size_t)bk * C * 4 + wv * 4];
@@ -1166,6 +1224,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
             const uint32_t chunkDraws = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             __syncthreads();
             seed = rng_jump(c.jumpT, seed, chunkDraws);            // state after the chunk: the next chunk's start / the stream's state behind the launch
+            }
             chunkK = k;
         }
         const int kb = k - chunkK;                                   // this block's slot in the chunk's tables
@@ -1218,7 +1277,9 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
         // states (a table jump of up to four dependent look-ups each) are fetched for ALL units at once, unit j in lane j, and
         // handed out by lane reads; a unit used to start with its own loads and its own jump, one after the other.
         int *uh = hdr + DSYN_CHUNK * 8;                              // [4 units][8] of this wave, behind its chunk table
-        if (!whole) {
+        const float *plane = nullptr;                                // PLANE: this wave's channel of the block, where the records' place is
+        if constexpr (PLANE) plane = plane_of(pla, s, C, wv, c.K, k, BS);
+        if (!PLANE && !whole) {
             if (lane < nsub) {
                 const int dj = udraw[wv * 4 + lane];
                 const int dn = (lane + 1 < nsub) ? udraw[wv * 4 + lane + 1] : (wv + 1 < C) ? udraw[(wv + 1) * 4] : c.draws[blk];
@@ -1237,6 +1298,11 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
                 const int d = pat & 7, S = BS >> d, M = S >> 1, Mp = FFT_PADDEDS(M, DPS);
                 float2 *zj = zc + FFT_PADS(off >> 1, DPS);
                 sw.A = (float *)zj;
+                if constexpr (PLANE) {
+                    // the unit's coefficients from the caller's plane, where synth_unit sits: in flight beside the other wave's transform
+                    plane_unit((float *)zj, plane + off, S, lane, 64);
+                    WAVE_SYNC();
+                } else {
                 const int *uj = uh + j * 8;
                 const uint32_t unitSeed = whole ? bseed[wv * 64 + kb] : (uint32_t)uj[0];
                 STAMP(1);
@@ -1245,6 +1311,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
                 const float urr = __int_as_float(whole ? hb[6] : uj[6]);
                 if (!(ULCX_DBG(c) & 1)) synth_unit(c, sw, S, prec, nrec, ur, unitSeed, ud, urr, tmag + (size_t)(wv * 4 + j) * c.tailStride, Mp);
                 else for (int i = lane; i < Mp; i += 64) zj[i] = make_float2(0.0f, 0.0f);
+                }
                 STAMP(2);
 
                 // DCT-IV pre-twiddle in place: n and M-1-n together read and write the same two complex slots
@@ -1353,8 +1420,11 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
                                 const float s1 = sn * Bs[q], s3 = cw * Bs[q];
                                 sLo = __builtin_fmaf(cw, As[q], -s1); sHi = __builtin_fmaf(sn, As[q], s3);
                             }
+                            if constexpr (LR) { lo2[q] = make_float2(mLo, sLo); hi2[q] = make_float2(mHi, sHi); }
+                            else {
                             lo2[q] = make_float2(mLo + sLo, mLo - sLo);
                             hi2[q] = make_float2(mHi + sHi, mHi - sHi);
+                            }
                         }
                         if constexpr (SAMP) {
                             sb.two(sp0, sal0, pv[1], lo2[1].x, lo2[0].x); sb.two(sp1, sal1, pv[1], lo2[1].y, lo2[0].y);
@@ -1402,8 +1472,11 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
                         if (!pass) { cw = fall[p - a]; sn = rise[p - a]; }
                         const LapPair m = lap_pair(Am[q], Bm[q], cw, sn, pass), sd = lap_pair(As[q], Bs[q], cw, sn, pass);   // outputs at positions p and S-1-p
                         // inverse M/S (ulcDecoder.c:281-289) + interleave (:292-297)
+                        if constexpr (LR) { lo2[q] = make_float2(m.lo, sd.lo); hi2[q] = make_float2(m.hi, sd.hi); }
+                        else {
                         lo2[q] = make_float2(m.lo + sd.lo, m.lo - sd.lo);
                         hi2[q] = make_float2(m.hi + sd.hi, m.hi - sd.hi);
+                        }
                     }
                     // positions pv[1] = pv[0]-1 and S-1-pv[0], S-pv[0] are neighbours: two aligned 16-byte stores
                     if constexpr (SAMP) {
@@ -1437,12 +1510,14 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
             if (!warm) {
             for (int n = 2 * tid; n < H2; n += 2 * WG) {
                 const float mx = L0[H2 - 1 - n], my = L0[H2 - 2 - n], sx = L1[H2 - 1 - n], sy = L1[H2 - 2 - n];
-                if constexpr (SAMP) { sb.two(sp0, sal0, n, mx + sx, my + sy); sb.two(sp1, sal1, n, mx - sx, my - sy); }
+                if constexpr (LR) { sb.two(sp0, sal0, n, mx, my); sb.two(sp1, sal1, n, sx, sy); }
+                else if constexpr (SAMP) { sb.two(sp0, sal0, n, mx + sx, my + sy); sb.two(sp1, sal1, n, mx - sx, my - sy); }
                 else st4(outp + 2 * n, mx + sx, mx - sx, my + sy, my - sy);
             }
             for (int n = 2 * tid; n < H2; n += 2 * WG) {
                 const float2 m = *(const float2 *)(t0 + padf(n)), sd = *(const float2 *)(t1 + padf(n));
-                if constexpr (SAMP) { sb.two(sp0, sal0, H2 + n, m.x + sd.x, m.y + sd.y); sb.two(sp1, sal1, H2 + n, m.x - sd.x, m.y - sd.y); }
+                if constexpr (LR) { sb.two(sp0, sal0, H2 + n, m.x, m.y); sb.two(sp1, sal1, H2 + n, sd.x, sd.y); }
+                else if constexpr (SAMP) { sb.two(sp0, sal0, H2 + n, m.x + sd.x, m.y + sd.y); sb.two(sp1, sal1, H2 + n, m.x - sd.x, m.y - sd.y); }
                 else st4(outp + 2 * (H2 + n), m.x + sd.x, m.x - sd.x, m.y + sd.y, m.y - sd.y);
             }
             }
@@ -1473,6 +1548,8 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
     constexpr bool SAMP = sizeof...(SA) != 0;                        // the sample-crop store mode, as k_dsyn's
     static_assert(!SAMP || RANGE, "k_dgen: sample crops are range launches");
     const auto &samp = samp_arg(sa...);
+    constexpr bool PLANE = SynSrc<SA...>::plane, LR = SynSrc<SA...>::lr;      // the plane source mode, as k_dsyn's
+    const auto &pla = plane_arg(sa...);
     extern __shared__ float lds[];
     const int BS = c.BS, C = c.C, H2 = BS / 2;
     const int s = c.s0 + blockIdx.x, tid = threadIdx.x;
@@ -1542,12 +1619,15 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
                     if (pat & 8) ov >>= (wc & 7);
                     if (ov > last) ov = last;
                     last = S;
+                    if constexpr (PLANE) plane_unit((float *)z, plane_of(pla, s, C, ch, c.K, k, BS) + dpos, S, tid, WG);   // the unit from the caller's plane
+                    else {
                     for (int i = tid; i < Mp; i += WG) z[i] = make_float2(0.0f, 0.0f);
                     __syncthreads();
                     if (wv == 0) {
                         sw.A = (float *)z;
                         const uint32_t unitSeed = rng_jump(c.jumpT, seed, (uint32_t)udraw[ch * 4 + j]);
                         synth_unit(c, sw, S, prec, nrec, urec[ch * 4 + j], unitSeed, unit_draws(ch, j), utail[ch * 4 + j].y, tmag + (size_t)(ch * 4 + j) * c.tailStride);
+                    }
                     }
                     __syncthreads();
                     const float2 *pre = c.T.pre[d];
@@ -1608,11 +1688,11 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
                 } while (pat >>= 4);
                 newLast = last;
                 // inverse M/S + interleave once both members of a pair (or a trailing single) are staged
-                const bool pairDone = (ch & 1) || (ch == C - 1);
+                const bool pairDone = LR || (ch & 1) || (ch == C - 1);   // (LR: every channel goes out as it stands)
                 if (pairDone) {
                     __syncthreads();
                     if (warm) {
-                    } else if (ch & 1) {
+                    } else if (!LR && (ch & 1)) {
                         const float *dm = scr, *ds = scr + BS;
                         for (int n = tid; n < BS; n += WG) {
                             const float m = dm[n], sd = ds[n];                            // ulcDecoder.c:281-289
@@ -1629,7 +1709,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
             }
             lastSub = newLast;
         }
-        seed = rng_jump(c.jumpT, seed, (uint32_t)c.draws[blk]);      // the one RNG chain of the stream (ulcDecoder.c:75-81)
+        if constexpr (!PLANE) seed = rng_jump(c.jumpT, seed, (uint32_t)c.draws[blk]);      // the one RNG chain of the stream (ulcDecoder.c:75-81)
     }
     if (tid == 0) { c.lastSub[s] = lastSub; c.seed[s] = seed; c.dead[s] = dead; }
 }
@@ -1787,10 +1867,13 @@ static const void *syn_pick(const UlcxDecCtx &cc) {
     return (const void *)k_dsyn<OUT, 32, false, SPLIT, 0, RANGE, SA...>;
 }
 // split: the grid is a cut of the (stream, block) pairs; range: a range call, which runs the cut form for every grid;
-// samp: a sample-crop call, a range call in the sample store mode
+// samp: a sample-crop call, a range call in the sample store mode; plane: a synth call, that mode with the plane source
+// (1: the planes hold the coded mid/side, 2: left/right)
 template <typename OUT>
-static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range, bool samp = false) {
-    return samp ? syn_pick<OUT, true, true, UlcxSampArg>(cc)
+static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range, bool samp = false, int plane = 0) {
+    return plane == 2 ? syn_pick<OUT, true, true, UlcxSampArg, UlcxPlaneArg<true>>(cc)
+         : plane ? syn_pick<OUT, true, true, UlcxSampArg, UlcxPlaneArg<false>>(cc)
+         : samp ? syn_pick<OUT, true, true, UlcxSampArg>(cc)
          : range ? syn_pick<OUT, true, true>(cc) : split ? syn_pick<OUT, true, false>(cc) : syn_pick<OUT, false, false>(cc);
 }
 // A launch with more than 48 KiB of dynamic LDS: raise the kernel's limit to this launch's size (ulcx_enc.hip: allow_lds).
@@ -1826,8 +1909,12 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     const bool split = c.fastOK && aux.synGrid > 0;
     const bool samp = aux.sampStart != nullptr;                       // a sample-crop call: rows from (start, len) first, then the crop walk on them
     const bool spec = aux.specCoef != nullptr;                        // a spectra call: the crop walk, then k_dspec in place of the synthesis
-    const void *syn = spec ? nullptr : c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp) : syn_fn<float>(c, split, c.range != 0, samp);
+    const int plane = aux.synCoef ? (aux.synLR ? 2 : 1) : 0;          // a synth call: k_synth_rows in place of every walk, then the plane source synthesis
+    const void *syn = spec ? nullptr : c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp, plane) : syn_fn<float>(c, split, c.range != 0, samp, plane);
     if (syn) CK(allow_lds(syn, lds));
+    if (plane) hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)(((long long)c.B * c.K + 63) / 64)), dim3(64), 0, st, c.B, c.K, aux.synPlanes, aux.synWc,
+                                  c.wcScan, c.draws, c.bits, c.rInfo, aux.sampSkip, aux.sampLenC, aux.nSamples);
+    else {
     if (samp) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, c.BS, aux.nSamples, aux.sampStart, aux.sampLen,
                                  aux.sampFirst, aux.sampCount, aux.sampSkip, aux.sampLenC);
     if (aux.nFiles > 0 && aux.payOffs) hipLaunchKernelGGL(k_dscan_crop_ragged, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount,
@@ -1836,6 +1923,7 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     else if (c.range) hipLaunchKernelGGL(k_dscan_range, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
+    }
     if (ev) CK(hipEventRecord(ev[stage++], st));
     if (spec) {
         const void *fn = aux.specLR ? (const void *)k_dspec<true> : (const void *)k_dspec<false>;
@@ -1851,7 +1939,8 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
         c.synFull = split ? aux.synFull : (c.range && c.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
         UlcxSampArg sa = { aux.sampSkip, aux.sampLenC, aux.nSamples };
-        void *args[] = { &c, &sa };                                  // (the second one: the sample-crop instantiations only)
+        UlcxPlaneArg<false> pa = { aux.synCoef, aux.synPlanes };     // (one layout for both LR settings)
+        void *args[] = { &c, &sa, &pa };                             // (the second one: the sample-store instantiations only; the third: the plane source's)
         CK(hipLaunchKernel(syn, dim3(g), dim3(WG), args, lds, st));
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));

@@ -235,6 +235,13 @@ struct UlcxDecAux {
     float *specCoef = nullptr;           // [c.B][C][c.K - 1][BS] dequantised coefficients, channels-first
     int32_t *specWc = nullptr;           // [c.B][c.K - 1] window codes (0: the block is not live)
     int specLR = 0;                      // channel pairs as m + s, m - s
+    // synthesis from spectra (ulcx_synth_spectra_*): synCoef != NULL - no walk at all; k_synth_rows turns the caller's window codes
+    // into the per-block rows a range synthesis reads (and sampSkip / sampLenC; nSamples = the output blocks x BlockSize), and the
+    // synthesis is the sample-store instantiation with the plane source.  nFiles is 0, c.in is not looked at.
+    const float *synCoef = nullptr;      // [c.B][C][synPlanes][BS] the caller's planes
+    const int32_t *synWc = nullptr;      // [c.B][synPlanes] their window codes (untrusted)
+    int synPlanes = 0;                   // planes per row: c.K with the plane in front (ULCX_SYNTH_WARM), else c.K - 1
+    int synLR = 0;                       // the planes hold left/right: no un-mix
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)

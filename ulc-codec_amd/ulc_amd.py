@@ -49,11 +49,13 @@ EXPORTS = [
     "ulcx_analyse_clips_dev", "ulcx_analyse_clips_dev_pcm16", "ulcx_analyse_clips_host",
     "ulcx_encode_clips_spectra_dev", "ulcx_encode_clips_spectra_dev_pcm16", "ulcx_encode_clips_spectra_host",
     "ulcx_encode_clips_ladder_dev", "ulcx_encode_clips_ladder_dev_pcm16", "ulcx_encode_clips_ladder_host",
+    "ulcx_synth_spectra_dev", "ulcx_synth_spectra_dev_pcm16", "ulcx_synth_spectra_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
 RUNG_AUTO = 1                                              # ULCX_RUNG_AUTO: Rung.reserved of the clips ladder calls
 SPECTRA_LR = 1                                             # ULCX_SPECTRA_LR: flags of the spectra calls
+SYNTH_WARM = 2                                             # ULCX_SYNTH_WARM: flags of the synth calls - plane 0 is the block in front
 
 # one entry of a block index (include/ulc_amd.h, ulcx_index_entry): 8 bytes
 INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
@@ -230,6 +232,10 @@ def lib():
                                                                C.c_void_p, C.c_void_p]
             l.ulcx_decode_crops_spectra_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p,
                                                                 C.c_int, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p]
+        if hasattr(l, "ulcx_synth_spectra_dev"):           # synthesis from spectra: PCM from caller-held planes
+            l.ulcx_synth_spectra_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.ulcx_synth_spectra_dev_pcm16.argtypes = l.ulcx_synth_spectra_dev.argtypes
+            l.ulcx_synth_spectra_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, _i32p, _f32p, _i32p]
         if hasattr(l, "ulcx_analyse_clips_dev"):           # clip spectra: the encoder's MDCT coefficients of clips
             tap_dev = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]            # nBlocks, flags, d_coef, d_wc, d_cplx
             tap_host = [C.c_int, C.c_int, _f32p, _i32p, _f32p]
@@ -1039,6 +1045,29 @@ class BatchDecoder(_StreamSlots):
         _check(lib().ulcx_decode_crops_spectra_dev(self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file,
                                                    d_first, d_count or None, n_blocks, int(flags), d_coef, d_wc, d_bits, stream or None),
                "ulcx_decode_crops_spectra_dev")
+
+    def synth_spectra(self, coef, wc, flags=0):
+        """PCM from caller-held MDCT planes through the decoder's inverse transform (ulcx_synth_spectra_host): coef float32
+        [n][C][n_blocks][BS] and wc int32 [n][n_blocks] as the spectra and clip-spectra calls write them -> (pcm [n][C][n_out * BS],
+        live [n][n_out]), n_out = n_blocks - 1 with SYNTH_WARM (plane 0 is the block in front: no output), else n_blocks.
+        flags: SPECTRA_LR (the planes hold left/right: no un-mix), SYNTH_WARM."""
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        wc = np.ascontiguousarray(wc, dtype=np.int32)
+        assert coef.ndim == 4 and coef.shape[1] == self.C and coef.shape[3] == self.BS and wc.shape == (coef.shape[0], coef.shape[2])
+        n, n_blocks = wc.shape
+        n_out = max(1, n_blocks - (1 if int(flags) & SYNTH_WARM else 0))
+        pcm = np.zeros((n, self.C, n_out * self.BS), np.float32)
+        live = np.zeros((n, n_out), np.int32)
+        _check(lib().ulcx_synth_spectra_host(self.h, n, n_blocks, int(flags), _p(coef, _f32p), _p(wc, _i32p), _p(pcm, _f32p), _p(live, _i32p)),
+               "ulcx_synth_spectra_host")
+        return pcm, live
+
+    def synth_spectra_dev(self, n, n_blocks, flags, d_coef, d_wc, d_pcm, d_live, stream=0, pcm16=False):
+        """Device form, asynchronous on `stream`: d_coef float32 [n][C][n_blocks][BS], d_wc int32 [n][n_blocks] -> d_pcm
+        [n][C][n_out * BS] (int16 with pcm16), d_live int32 [n][n_out]."""
+        fn = lib().ulcx_synth_spectra_dev_pcm16 if pcm16 else lib().ulcx_synth_spectra_dev
+        _check(fn(self.h, n, n_blocks, int(flags), d_coef, d_wc, d_pcm, d_live, stream or None),
+               "ulcx_synth_spectra_dev_pcm16" if pcm16 else "ulcx_synth_spectra_dev")
 
     def decode_crops_spectra_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, first, n_blocks, count=None, flags=0):
         """decode_crops_spectra() of a ragged corpus, held as for decode_crops_ragged()."""
