@@ -143,7 +143,8 @@ enum { ULCX_MODE_VBR = 0, ULCX_MODE_CBR = 1, ULCX_MODE_ABR = 2 };
  *             d_pcm and d_len of the clip calls (ulcx_encode_clips_*: likewise, two samples per load only at a multiple of 8)
  *    2 bytes  d_pcm16 of the sample-crop calls (likewise; two samples at once only at a multiple of 4) and of the clip calls
  *    4 bytes  d_bits, d_wc, d_cplx, d_payloadBytes, d_maxBlock, d_nBlocks, d_indexBlocks, d_first, d_file, d_count, d_index (an entry is two
- *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n])
+ *             4-byte words), and the slot lists of the stream-slot entries (their d_slots: int32 [n]);
+ *             d_segOffs, d_seg (a segment is three 4-byte words) and d_segStart of the splice calls, and their d_out* tables
  *    none     the byte streams: d_out, d_in, d_payload and the d_slots of ulcx_pack_streams_dev and ulcx_index_slots_dev
  *             (slotBytes and payloadStride may be any positive value)
  *   A pointer that violates this makes the call return ULCX_ERR_ARG before any device work; the object's state is untouched
@@ -1005,6 +1006,74 @@ int  ulcx_corpus_ragged_host(int device, int nFiles,
                              uint8_t *h_outPayload, long long payloadCap, int64_t *h_payloadOffs,
                              ulcx_index_entry *h_outIndex, long long indexCap, int64_t *h_indexOffs, int32_t *h_outIndexBlocks,
                              int64_t *h_need);   /* synchronous */
+
+/* Corpus splice: new files made of block ranges of resident files - rung switches of a ladder corpus, trims, joins.  The source
+ * is a strided corpus as ulcx_decode_crops_dev takes it (or a ragged one, as ulcx_decode_crops_ragged_dev does); the output is a
+ * strided corpus exactly as a clip call leaves one: every crop call reads it the moment the call returns on hipStream, and
+ * ulcx_corpus_ragged_dev converts it.  `dec` supplies geometry and tables only, as for ulcx_index_slots_dev: nFiles, nOut and
+ * nSeg are the call's own (limited neither by nStreams nor by maxBlocksPerCall), no stream state is read or changed, none of the
+ * object's per-block scratch is used, nothing is allocated, and the call mixes freely with every other call on the object.
+ *
+ * Positions are whole blocks.  Blocks are byte-aligned and self-contained, so a splice is a byte copy plus a new block index:
+ * the generator state in front of a block depends on the draws of the blocks now in front of it, and is rebuilt from a parse of
+ * every block taken (the source index's RngState is never read).
+ *
+ * Output file o is the segments d_segOffs[o] .. d_segOffs[o + 1] - 1 of d_seg, in order (CSR).  It takes the blocks they name one
+ * by one and stops growing at the first block that cannot be taken - which may lie in the middle of a segment; everything behind
+ * it is absent (the rule of a stream that stops in ulcx_index_slots_dev).  Block k of source file f can be taken when
+ *   - File is in [0, nFiles), First >= 0, and k < clamp(d_indexBlocks[f], 0, indexStride - 1) (ragged: the file's offsets and row
+ *     capacity are ones the ragged crop calls accept);
+ *   - 0 <= ByteOffs[k] < ByteOffs[k + 1] <= the file's byte count;
+ *   - the parse of those bytes, limited to that extent, is valid and consumes exactly the extent: a block damaged behind a stored
+ *     index ends the output file in front of it;
+ *   - it fits: the running block count stays within outIndexStride - 1, the running byte count within outPayloadStride and an int32.
+ * A segment whose Count is 0 or negative names no block and contributes nothing.  A file with no segment, or whose first block
+ * cannot be taken, is empty: 0 bytes, 0 blocks, the open index row.  An output file whose d_segOffs pair falls or leaves
+ * [0, nSeg] is empty, and those of its segments that exist get d_segStart = -1.
+ *
+ * Written: d_outPayload[o * outPayloadStride ..] the taken blocks back to back (bytes behind d_outPayloadBytes[o] are not
+ * written); row o of d_outIndex and d_outIndexBlocks[o], entry for entry what ulcx_index_packed_rows_dev builds from that payload
+ * with maxBlocks = outIndexStride - 1, the {-1, 0} entries behind the closing one included; d_outMaxBlock[o] (optional) the
+ * largest taken block in bytes; d_segStart[j] the output block at which segment j begins in the plan - the sum of max(Count, 0)
+ * over the earlier segments of its output file, saturating at INT32_MAX - whatever is taken: segment j is present in full exactly
+ * when d_segStart[j] + Count <= d_outIndexBlocks[o].  It is an output for labels that follow their blocks, and the table the
+ * kernels search: required.
+ *
+ * The _dev forms enqueue everything on hipStream and wait for nothing; ULCX_ERR_ARG before any device work for a NULL required
+ * pointer, a misaligned one (offset tables 8 bytes, every other table 4, payloads none), nFiles / nOut / nSeg below 1, a stride
+ * below 1 (ragged: a negative total), outIndexStride < 2, more output than one call's grids take, or an output payload or index
+ * range that overlaps the source's payload or index.  The host forms are synchronous and know the tables: they also refuse an
+ * h_segOffs that does not rise from >= 0 to <= nSeg, a File out of range, a negative First or Count, First + Count beyond
+ * h_indexBlocks[File], and (ragged) what ulcx_decode_crops_ragged_host refuses of the offset tables. */
+typedef struct ulcx_segment { int32_t File, First, Count; } ulcx_segment;   /* blocks First .. First + Count - 1 of source file File; 12 bytes */
+int  ulcx_corpus_splice_dev(ulcx_decoder *dec, int nFiles,
+                            const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                            const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                            int nOut, const int32_t *d_segOffs /* [nOut+1] */, const ulcx_segment *d_seg, int nSeg,
+                            uint8_t *d_outPayload, long long outPayloadStride, int32_t *d_outPayloadBytes /* [nOut] */, int32_t *d_outMaxBlock /* [nOut], optional */,
+                            ulcx_index_entry *d_outIndex, int outIndexStride, int32_t *d_outIndexBlocks /* [nOut] */,
+                            int32_t *d_segStart /* [nSeg] */, void *hipStream);
+int  ulcx_corpus_splice_ragged_dev(ulcx_decoder *dec, int nFiles,
+                                   const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                   const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                   int nOut, const int32_t *d_segOffs, const ulcx_segment *d_seg, int nSeg,
+                                   uint8_t *d_outPayload, long long outPayloadStride, int32_t *d_outPayloadBytes, int32_t *d_outMaxBlock,
+                                   ulcx_index_entry *d_outIndex, int outIndexStride, int32_t *d_outIndexBlocks,
+                                   int32_t *d_segStart, void *hipStream);
+int  ulcx_corpus_splice_host(ulcx_decoder *dec, int nFiles,
+                             const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                             const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                             int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg,
+                             uint8_t *h_outPayload, long long outPayloadStride, int32_t *h_outPayloadBytes, int32_t *h_outMaxBlock,
+                             ulcx_index_entry *h_outIndex, int outIndexStride, int32_t *h_outIndexBlocks,
+                             int32_t *h_segStart);   /* synchronous; of h_outPayload only bytes [0, h_outPayloadBytes[o]) of each file are written */
+int  ulcx_corpus_splice_ragged_host(ulcx_decoder *dec, int nFiles,
+                                    const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                    const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                    int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg,
+                                    uint8_t *h_outPayload, long long outPayloadStride, int32_t *h_outPayloadBytes, int32_t *h_outMaxBlock,
+                                    ulcx_index_entry *h_outIndex, int outIndexStride, int32_t *h_outIndexBlocks,
+                                    int32_t *h_segStart);   /* synchronous */
 
 /* `.ulx` sidecar: the block index of ONE `.ulc` file, written beside it (stem.ulx).  16-byte little-endian header, then
  * nBlocks + 1 entries of 8 bytes (ByteOffs, RngState; offsets relative to the .ulc file's StreamOffs).  The `.ulc` container

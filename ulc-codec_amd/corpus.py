@@ -463,6 +463,92 @@ class CropCorpus:
                              stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
         return pcm, bits
 
+    def splice(self, dec, segments):
+        """A new corpus whose files are block ranges of this one's (ulcx_corpus_splice_dev): rung switches, trims, joins.
+        `segments` is one list of (file, first, count) per output file - output file o is those ranges back to back, in order - or
+        the tuple (file, first, count, offs): three int32 [nSeg] tensors and the int32 [nOut + 1] offsets of each output file's
+        segments among them.  Positions are whole blocks; an output file stops in front of the first block that cannot be taken.
+        -> (corpus, seg_start): a frozen CropCorpus on the device in this corpus's layout (strided; ragged: ulcx_corpus_ragged_dev
+        behind the call), sized from this corpus's index (ONE 16-byte read of the largest planned file), and the int32 [nSeg]
+        output block at which each segment begins in its file.  Enqueued on torch's current stream.  `dec`: a BatchDecoder of this
+        geometry; geometry and tables are all the call reads of it."""
+        import torch
+        if not self.frozen:
+            raise UlcError("corpus: not frozen")
+        if (dec.C, dec.BS) != (self.C, self.BS):
+            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
+        dev = self.device
+        as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=dev).contiguous()
+        if isinstance(segments, tuple):
+            file, first, count, offs = (as_i32(v).reshape(-1) for v in segments)
+        else:
+            flat = np.array([tuple(g) for f in segments for g in f], np.int32).reshape(-1, 3)
+            file, first, count = (as_i32(flat[:, j].copy()) for j in range(3))
+            offs = as_i32(np.concatenate([[0], np.cumsum([len(f) for f in segments])]))
+        n_out, n_seg = offs.numel() - 1, file.numel()
+        if n_out < 1 or n_seg < 1 or first.numel() != n_seg or count.numel() != n_seg:
+            raise UlcError(f"corpus: a splice of {n_out} files from {n_seg} segments")
+        seg = torch.stack((file, first, count), dim=1).contiguous()
+        # the plan's size from the index: per segment the blocks and bytes its range holds, summed per output file
+        F = self.n_files
+        f = file.long().clamp(0, F - 1)
+        if self.ragged:
+            i0 = self.d_index_offs[:-1]
+            n_i = torch.minimum(self.d_index_blocks.long().clamp(min=0), (self.d_index_offs[1:] - i0 - 1).clamp(min=0))[f]
+            at = lambda k: self.d_index[:, 0][(i0[f] + k).clamp(0, max(self.d_index.shape[0] - 1, 0))]
+        else:
+            n_i = self.d_index_blocks.long().clamp(0, self.index_stride - 1)[f]
+            at = lambda k: self.d_index[:, :, 0][f, k]
+        a = torch.minimum(first.long().clamp(min=0), n_i)
+        b = torch.minimum(a + count.long().clamp(min=0), n_i)
+        size = torch.stack((b - a, (at(b) - at(a)).long().clamp(min=0)), dim=1)
+        owner = (torch.searchsorted(offs.long(), torch.arange(n_seg, device=dev), right=True) - 1).clamp(0, n_out - 1)
+        most = torch.zeros((n_out, 2), dtype=torch.int64, device=dev).index_add_(0, owner, size).amax(dim=0)
+        n_blocks, n_bytes = (int(v) for v in most.cpu())
+        stride = (n_bytes + PAYLOAD_PAD + 15) & ~15
+        index_stride = n_blocks + 1 if n_blocks > 0 else 2
+        payload = torch.empty((n_out, stride), dtype=torch.uint8, device=dev)
+        nbytes = torch.empty(n_out, dtype=torch.int32, device=dev)
+        index = torch.empty((n_out, index_stride, 2), dtype=torch.int32, device=dev)
+        blocks = torch.empty(n_out, dtype=torch.int32, device=dev)
+        seg_start = torch.empty(n_seg, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        out = (n_out, offs.data_ptr(), seg.data_ptr(), n_seg, payload.data_ptr(), stride, nbytes.data_ptr(), 0, index.data_ptr(), index_stride,
+               blocks.data_ptr(), seg_start.data_ptr())
+        c = CropCorpus(self.C, self.BS, "ragged" if self.ragged else "strided")
+        with torch.cuda.device(dev):
+            if self.ragged:
+                dec.corpus_splice_ragged_dev(F, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(), self.d_index.data_ptr(),
+                                             self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(), *out, stream=stream)
+            else:
+                dec.corpus_splice_dev(F, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(), self.index_stride,
+                                      self.d_index_blocks.data_ptr(), *out, stream=stream)
+            c._adopt(dev, stream, n_out, payload, stride, nbytes, index, index_stride, blocks)
+        c.frozen = True
+        return c, seg_start
+
+    def trim(self, dec, first, count):
+        """Every file cut to its blocks first[f] .. first[f] + count[f] - 1 (int32 [n_files], or anything torch.as_tensor takes;
+        a scalar for all files) -> the new corpus, file for file (splice() with one segment per file)."""
+        import torch
+        n = self.n_files
+        as_row = lambda v: torch.as_tensor(v, dtype=torch.int32, device=self.device).reshape(-1).expand(n).contiguous()
+        every = torch.arange(n + 1, dtype=torch.int32, device=self.device)
+        return self.splice(dec, (every[:n], as_row(first), as_row(count), every))[0]
+
+    def switch(self, dec, plan):
+        """Rung switching on a corpus from_clips_ladder() made: plan[clip] is a list of (rung, n_blocks) - output file `clip` takes
+        n_blocks blocks of the clip under that rung, then goes on where it stands under the next one.  Every rung of a clip has the
+        same window code in every block, so the aliasing cancels at each joint.  -> the new corpus of len(plan) files."""
+        segments = []
+        for clip, runs in enumerate(plan):
+            at, row = 0, []
+            for rung, n_blocks in runs:
+                row.append((self.file_of(int(rung), clip), at, int(n_blocks)))
+                at += int(n_blocks)
+            segments.append(row)
+        return self.splice(dec, segments)[0]
+
     def sample_crops(self, dec, files, start, n_samples, length=None, pcm16=False):
         """Row i: n_samples samples from sample start[i] of the decoded stream of file files[i] (its leading length[i] when
         `length` is given; zeros behind, and behind the file's end), written channels-first by the synthesis itself

@@ -2547,6 +2547,142 @@ extern "C" int ulcx_index_slots_host(ulcx_decoder *e, int nRows, const uint8_t *
     CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * nRows, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
+// ---- corpus splice (include/ulc_amd.h section 2): splice_any is the body of the two _dev forms (ragged != NULL: payloadStride,
+// d_payloadBytes and indexStride are not looked at), splice_host_any of the two host forms.  The decoder comes last among the
+// checks, as in index_rows_any.
+struct SpliceOut { uint8_t *payload; long long payloadStride; int32_t *payloadBytes, *maxBlock; ulcx_index_entry *index; int indexStride; int32_t *indexBlocks, *segStart; };
+static bool ranges_meet(const void *a, unsigned long long na, const void *b, unsigned long long nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+static int splice_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                      const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const CropsRagged *ragged,
+                      int nOut, const int32_t *d_segOffs, const ulcx_segment *d_seg, int nSeg, const SpliceOut &o, void *hipStream) {
+    if (!d_payload || !d_index || !d_indexBlocks || !d_segOffs || !d_seg || !o.payload || !o.payloadBytes || !o.index || !o.indexBlocks || !o.segStart ||
+        (ragged ? (!ragged->payloadOffs || !ragged->indexOffs) : !d_payloadBytes)) return refuse(who, "bad argument (a NULL pointer)");
+    if (nFiles < 1 || nOut < 1 || nSeg < 1) return refuse(who, "bad argument (nFiles %d, nOut %d, nSeg %d)", nFiles, nOut, nSeg);
+    if (ragged ? (ragged->payloadTotal < 0 || ragged->indexTotal < 0) : (payloadStride < 1 || indexStride < 1))
+        return ragged ? refuse(who, "bad argument (payloadTotal %lld, indexTotal %lld)", ragged->payloadTotal, ragged->indexTotal)
+                      : refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride);
+    if (o.payloadStride < 1 || o.indexStride < 2) return refuse(who, "bad argument (outPayloadStride %lld, outIndexStride %d: at least 1 and 2)", o.payloadStride, o.indexStride);
+    if (ragged && (misaligned(who, "d_payloadOffs", ragged->payloadOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", ragged->indexOffs, ULCX_ALIGN_OFFS)))
+        return ULCX_ERR_ARG;
+    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_segOffs", d_segOffs, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_seg", d_seg, ULCX_ALIGN_WORD) || misaligned(who, "d_outPayloadBytes", o.payloadBytes, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_outMaxBlock", o.maxBlock, ULCX_ALIGN_WORD) || misaligned(who, "d_outIndex", o.index, ULCX_ALIGN_WORD) ||
+        misaligned(who, "d_outIndexBlocks", o.indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_segStart", o.segStart, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
+    // (one lane per output block and per 16-byte line, each in a grid of 2^31 - 1 workgroups at the most; a payload range within 2^62)
+    if ((long long)nOut * o.indexStride > (0x7FFFFFFFLL << 6) || o.payloadStride > (1LL << 40) || (long long)nOut * ((o.payloadStride + 30) / 16) > (0x7FFFFFFFLL << 8))
+        return refuse(who, "%d output files of %d entries and %lld bytes are more than one call takes", nOut, o.indexStride, o.payloadStride);
+    if (!ragged && payloadStride > (1LL << 40)) return refuse(who, "bad argument (payloadStride %lld)", payloadStride);
+    const unsigned long long srcPay = ragged ? (unsigned long long)ragged->payloadTotal : (unsigned long long)nFiles * (unsigned long long)payloadStride;
+    const unsigned long long srcIdx = sizeof(ulcx_index_entry) * (ragged ? (unsigned long long)ragged->indexTotal : (unsigned long long)nFiles * (unsigned long long)indexStride);
+    const unsigned long long outPay = (unsigned long long)nOut * (unsigned long long)o.payloadStride, outIdx = sizeof(ulcx_index_entry) * (unsigned long long)nOut * (unsigned long long)o.indexStride;
+    if (ranges_meet(o.payload, outPay, d_payload, srcPay) || ranges_meet(o.payload, outPay, d_index, srcIdx) ||
+        ranges_meet(o.index, outIdx, d_payload, srcPay) || ranges_meet(o.index, outIdx, d_index, srcIdx))
+        return refuse(who, "the output payload or index overlaps the source's");
+    if (!e) return refuse(who, "no decoder");
+    CKR(hipSetDevice(e->device));
+    UlcxDecCtx c = e->ctx;
+    c.in = d_payload; c.inBytes = (long long)srcPay; c.packed = 1;
+    UlcxSpliceArgs a = {};
+    a.nFiles = nFiles; a.payStride = payloadStride; a.payBytes = d_payloadBytes; a.index = d_index; a.indexStride = indexStride; a.indexBlocks = d_indexBlocks;
+    if (ragged) { a.payOffs = ragged->payloadOffs; a.idxOffs = ragged->indexOffs; a.idxTotal = ragged->indexTotal; }
+    a.nOut = nOut; a.nSeg = nSeg; a.segOffs = d_segOffs; a.seg = d_seg; a.segStart = o.segStart;
+    a.outPay = o.payload; a.outPayStride = o.payloadStride; a.outPayBytes = o.payloadBytes; a.outMaxBlock = o.maxBlock;
+    a.outIndex = o.index; a.outIndexStride = o.indexStride; a.outIndexBlocks = o.indexBlocks;
+    return ulcx_splice_launch(c, a, (hipStream_t)hipStream);
+}
+extern "C" int ulcx_corpus_splice_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                      const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                      int nOut, const int32_t *d_segOffs, const ulcx_segment *d_seg, int nSeg,
+                                      uint8_t *d_outPayload, long long outPayloadStride, int32_t *d_outPayloadBytes, int32_t *d_outMaxBlock,
+                                      ulcx_index_entry *d_outIndex, int outIndexStride, int32_t *d_outIndexBlocks, int32_t *d_segStart, void *hipStream) {
+    const SpliceOut o = { d_outPayload, outPayloadStride, d_outPayloadBytes, d_outMaxBlock, d_outIndex, outIndexStride, d_outIndexBlocks, d_segStart };
+    return splice_any("ulcx_corpus_splice_dev", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, nullptr,
+                      nOut, d_segOffs, d_seg, nSeg, o, hipStream);
+}
+extern "C" int ulcx_corpus_splice_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                             const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                             int nOut, const int32_t *d_segOffs, const ulcx_segment *d_seg, int nSeg,
+                                             uint8_t *d_outPayload, long long outPayloadStride, int32_t *d_outPayloadBytes, int32_t *d_outMaxBlock,
+                                             ulcx_index_entry *d_outIndex, int outIndexStride, int32_t *d_outIndexBlocks, int32_t *d_segStart, void *hipStream) {
+    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
+    const SpliceOut o = { d_outPayload, outPayloadStride, d_outPayloadBytes, d_outMaxBlock, d_outIndex, outIndexStride, d_outIndexBlocks, d_segStart };
+    return splice_any("ulcx_corpus_splice_ragged_dev", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, &g, nOut, d_segOffs, d_seg, nSeg, o, hipStream);
+}
+// the host forms: the scalar checks of the _dev form first (on the host pointers), then what only a host form can refuse; the
+// outputs go through device buffers of the call's own, and of the payload only the bytes the call wrote come back
+static int splice_host_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                           const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks, const CropsRagged *ragged,
+                           int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg, const SpliceOut &o) {
+    if (!h_payload || !h_index || !h_indexBlocks || !h_segOffs || !h_seg || !o.payload || !o.payloadBytes || !o.index || !o.indexBlocks || !o.segStart ||
+        (ragged ? (!ragged->payloadOffs || !ragged->indexOffs) : !h_payloadBytes)) return refuse(who, "bad argument (a NULL pointer)");
+    if (nFiles < 1 || nOut < 1 || nSeg < 1) return refuse(who, "bad argument (nFiles %d, nOut %d, nSeg %d)", nFiles, nOut, nSeg);
+    if (ragged ? (ragged->payloadTotal < 0 || ragged->indexTotal < 0) : (payloadStride < 1 || indexStride < 1))
+        return ragged ? refuse(who, "bad argument (payloadTotal %lld, indexTotal %lld)", ragged->payloadTotal, ragged->indexTotal)
+                      : refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride);
+    if (o.payloadStride < 1 || o.indexStride < 2) return refuse(who, "bad argument (outPayloadStride %lld, outIndexStride %d: at least 1 and 2)", o.payloadStride, o.indexStride);
+    if (ragged && ragged_tables_bad(who, nFiles, *ragged)) return ULCX_ERR_ARG;
+    if (h_segOffs[0] < 0 || h_segOffs[nOut] > nSeg) return refuse(who, "h_segOffs runs from %d to %d, outside 0 .. nSeg = %d", (int)h_segOffs[0], (int)h_segOffs[nOut], nSeg);
+    for (int i = 0; i < nOut; i++)
+        if (h_segOffs[i + 1] < h_segOffs[i]) return refuse(who, "h_segOffs falls from %d to %d at output file %d", (int)h_segOffs[i], (int)h_segOffs[i + 1], i);
+    for (int j = 0; j < nSeg; j++) {
+        const ulcx_segment &g = h_seg[j];
+        if (g.File < 0 || g.File >= nFiles) return refuse(who, "segment %d names file %d of %d", j, (int)g.File, nFiles);
+        if (g.First < 0 || g.Count < 0) return refuse(who, "segment %d is %d blocks from block %d", j, (int)g.Count, (int)g.First);
+        if ((long long)g.First + g.Count > (long long)h_indexBlocks[g.File])
+            return refuse(who, "segment %d ends at block %lld of a file of %d", j, (long long)g.First + g.Count, (int)h_indexBlocks[g.File]);
+    }
+    if (!e) return refuse(who, "no decoder");
+    CKR(hipSetDevice(e->device));
+    const size_t nEnt = ragged ? (size_t)ragged->indexTotal : (size_t)nFiles * (size_t)indexStride, outEnt = (size_t)nOut * (size_t)o.indexStride;
+    DevTmp t; uint8_t *dp = nullptr, *dop = nullptr; int32_t *dn = nullptr, *dcnt = nullptr, *dso = nullptr, *dob = nullptr, *dom = nullptr, *docnt = nullptr, *dss = nullptr;
+    ulcx_index_entry *di = nullptr, *doi = nullptr; ulcx_segment *dseg = nullptr; CropsRagged dg = {};
+    int rc = ragged ? ragged_up(t, nFiles, h_payload, *ragged, &dp, &dg) : payload_rows_up(t, nFiles, h_payload, payloadStride, h_payloadBytes, &dp, &dn);
+    if (rc) return rc;
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
+    CKR(t.get(&dso, sizeof(int32_t) * ((size_t)nOut + 1))); CKR(t.get(&dseg, sizeof(ulcx_segment) * (size_t)nSeg)); CKR(t.get(&dss, sizeof(int32_t) * (size_t)nSeg));
+    CKR(t.get(&dop, (size_t)nOut * (size_t)o.payloadStride)); CKR(t.get(&dob, sizeof(int32_t) * (size_t)nOut)); CKR(t.get(&dom, sizeof(int32_t) * (size_t)nOut));
+    CKR(t.get(&docnt, sizeof(int32_t) * (size_t)nOut)); CKR(t.get(&doi, sizeof(ulcx_index_entry) * outEnt));
+    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
+    if (nEnt) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dso, h_segOffs, sizeof(int32_t) * ((size_t)nOut + 1), hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dseg, h_seg, sizeof(ulcx_segment) * (size_t)nSeg, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(dss, o.segStart, sizeof(int32_t) * (size_t)nSeg, hipMemcpyHostToDevice));     // (segments of no output file go back as they came)
+    const SpliceOut d = { dop, o.payloadStride, dob, dom, doi, o.indexStride, docnt, dss };
+    if ((rc = splice_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, ragged ? &dg : nullptr, nOut, dso, dseg, nSeg, d, nullptr))) return rc;
+    CKR(hipDeviceSynchronize());
+    CKR(hipMemcpy(o.payloadBytes, dob, sizeof(int32_t) * (size_t)nOut, hipMemcpyDeviceToHost));
+    if (o.maxBlock) CKR(hipMemcpy(o.maxBlock, dom, sizeof(int32_t) * (size_t)nOut, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(o.indexBlocks, docnt, sizeof(int32_t) * (size_t)nOut, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(o.index, doi, sizeof(ulcx_index_entry) * outEnt, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(o.segStart, dss, sizeof(int32_t) * (size_t)nSeg, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nOut; i++)
+        if (o.payloadBytes[i] > 0)
+            CKR(hipMemcpy(o.payload + (size_t)i * (size_t)o.payloadStride, dop + (size_t)i * (size_t)o.payloadStride, (size_t)o.payloadBytes[i], hipMemcpyDeviceToHost));
+    return ULCX_OK;
+}
+extern "C" int ulcx_corpus_splice_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                       const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                       int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg,
+                                       uint8_t *h_outPayload, long long outPayloadStride, int32_t *h_outPayloadBytes, int32_t *h_outMaxBlock,
+                                       ulcx_index_entry *h_outIndex, int outIndexStride, int32_t *h_outIndexBlocks, int32_t *h_segStart) {
+    const SpliceOut o = { h_outPayload, outPayloadStride, h_outPayloadBytes, h_outMaxBlock, h_outIndex, outIndexStride, h_outIndexBlocks, h_segStart };
+    return splice_host_any("ulcx_corpus_splice_host", e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, nullptr,
+                           nOut, h_segOffs, h_seg, nSeg, o);
+}
+extern "C" int ulcx_corpus_splice_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                              const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                              int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg,
+                                              uint8_t *h_outPayload, long long outPayloadStride, int32_t *h_outPayloadBytes, int32_t *h_outMaxBlock,
+                                              ulcx_index_entry *h_outIndex, int outIndexStride, int32_t *h_outIndexBlocks, int32_t *h_segStart) {
+    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
+    const SpliceOut o = { h_outPayload, outPayloadStride, h_outPayloadBytes, h_outMaxBlock, h_outIndex, outIndexStride, h_outIndexBlocks, h_segStart };
+    return splice_host_any("ulcx_corpus_splice_ragged_host", e, nFiles, h_payload, 0, nullptr, h_index, 0, h_indexBlocks, &g,
+                           nOut, h_segOffs, h_seg, nSeg, o);
+}
 extern "C" int ulcx_index_check(const ulcx_index_entry *row, int nBlocks, int indexStride, long long payloadBytes) {
     const char *who = "ulcx_index_check";
     if (!row) return refuse(who, "no index");

@@ -667,6 +667,206 @@ __global__ __launch_bounds__(64) void k_dindex_slots_scan(const uint32_t *jumpT,
     if (lane == 0) rowBlocks[s] = n0 + m;
 }
 
+// Corpus splice (ulcx_corpus_splice_*): new files from block ranges of resident files.  Output file o is the blocks its
+// segments segOffs[o] .. segOffs[o + 1] - 1 name, in order, up to the first one that cannot be taken.  Nothing is walked in
+// series, and the output index and segStart are the only working memory; behind k_dindex_begin on the output rows:
+//   k_splice_plan  one wave per output file, 64 segments per trip: segStart[j] = the blocks the file's earlier segments plan
+//                  (the exclusive sum of max(Count, 0), saturating) - the table the two kernels below search.
+//   k_splice_walk  one lane per (output file, output block): the block's segment by binary search, then its source file and
+//                  block; the two bounding entries of the source index, and k_dindex_slots_walk's parse of that extent.  It
+//                  parks {bytes, draws} in the output entry the block will close; a block that cannot be taken leaves the
+//                  {-1, 0} k_dindex_begin wrote there.
+//   k_splice_scan  one wave per output file: k_dindex_slots_scan's prefix sums and jumps from an open row, with the byte
+//                  capacity as a further stop; the file's bytes, blocks and largest block.
+//   k_splice_copy  one lane per aligned 16-byte line of the output payloads: the output block a line begins in by binary search
+//                  in the finished row, its source as the walk found it, and on through the blocks the line holds.
+// SpliceSrc: the source corpus, strided (payOffs == NULL) or ragged; splice_file is k_dscan_crop's / k_dscan_crop_ragged's view of
+// file f (the caller has f inside [0, nFiles)).
+struct SpliceSrc {
+    const uint8_t *pay; long long payTotal;                         // the whole payload buffer: nothing outside it is read
+    long long payStride; const int32_t *payBytes;
+    const ulcx_index_entry *index; int indexStride; const int32_t *indexBlocks;
+    const int64_t *payOffs, *idxOffs; long long idxTotal;
+    int nFiles;
+};
+struct SpliceFile { const uint8_t *base; const ulcx_index_entry *row; long long avail; int nI; };
+template <bool RAGGED>
+__device__ __forceinline__ SpliceFile splice_file(const SpliceSrc &s, int f) {
+    SpliceFile r;
+    int nI = s.indexBlocks[f];
+    nI = nI < 0 ? 0 : nI;
+    if constexpr (RAGGED) {
+        const long long p0 = s.payOffs[f], p1 = s.payOffs[f + 1], i0 = s.idxOffs[f], i1 = s.idxOffs[f + 1];
+        const bool okF = p0 >= 0 && p1 >= p0 && p1 <= s.payTotal && p1 - p0 < 0x80000000LL
+                      && i0 >= 0 && i1 >= i0 && i1 <= s.idxTotal && i1 - i0 > (long long)nI;
+        r.nI = okF ? nI : 0; r.avail = okF ? p1 - p0 : 0;
+        r.base = s.pay + (okF ? p0 : 0); r.row = s.index + (okF ? i0 : 0);
+    } else {
+        r.nI = nI > s.indexStride - 1 ? s.indexStride - 1 : nI;
+        long long avail = s.payBytes[f];
+        r.avail = avail < 0 ? 0 : avail > s.payStride ? s.payStride : avail;
+        r.base = s.pay + (size_t)f * (size_t)s.payStride; r.row = s.index + (size_t)f * (size_t)s.indexStride;
+    }
+    return r;
+}
+// the segments of output file o: {first, end}, or {0, -1} for a pair that falls or leaves [0, nSeg]
+__device__ __forceinline__ int2 splice_segs(const int32_t *segOffs, int o, int nSeg) {
+    const int s0 = segOffs[o], s1 = segOffs[o + 1];
+    return (s0 >= 0 && s0 <= s1 && s1 <= nSeg) ? make_int2(s0, s1) : make_int2(0, -1);
+}
+// Output block j of a file with segments [sg.x, sg.y): the source block it names -> {byte offset in its file, bytes} and the
+// file in sf; bytes 0 when there is none - j at or behind the plan's end, or a file, a block or index entries that cannot be taken.
+// The search: the last segment that starts at or in front of j (zero-count segments in front of it start where it does).
+struct SpliceBlk { int off, ext; };
+template <bool RAGGED>
+__device__ __forceinline__ SpliceBlk splice_block(const SpliceSrc &s, const int32_t *segStart, const ulcx_segment *seg, int2 sg, int j, SpliceFile &sf) {
+    SpliceBlk b = { 0, 0 };
+    int lo = sg.x, hi = sg.y;                                       // the last segment that starts at or in front of j
+    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (segStart[mid] <= j) lo = mid + 1; else hi = mid; }
+    if (lo <= sg.x) return b;
+    const ulcx_segment g = seg[lo - 1];
+    const int r = j - segStart[lo - 1];
+    if (r < 0 || r >= g.Count || g.File < 0 || g.File >= s.nFiles || g.First < 0) return b;
+    const long long k = (long long)g.First + r;
+    sf = splice_file<RAGGED>(s, g.File);
+    if (k >= sf.nI) return b;
+    const long long o0 = sf.row[k].ByteOffs, o1 = sf.row[k + 1].ByteOffs;
+    if (o0 < 0 || o1 <= o0 || o1 > sf.avail) return b;
+    b.off = (int)o0; b.ext = (int)(o1 - o0);
+    return b;
+}
+__global__ __launch_bounds__(64) void k_splice_plan(int nSeg, const int32_t *segOffs, const ulcx_segment *seg, int32_t *segStart) {
+    const int o = blockIdx.x, lane = threadIdx.x;
+    const int2 sg = splice_segs(segOffs, o, nSeg);
+    if (sg.y < 0) {
+        // the segments of a bad pair that exist
+        const long long a = segOffs[o], b = segOffs[o + 1];
+        const int s0 = (int)(a < 0 ? 0 : a > nSeg ? nSeg : a), s1 = (int)(b < 0 ? 0 : b > nSeg ? nSeg : b);
+        for (int j = s0 + lane; j < s1; j += 64) segStart[j] = -1;
+        return;
+    }
+    long long carry = 0;
+    for (int j0 = sg.x; j0 < sg.y; j0 += 64) {
+        const bool have = j0 + lane < sg.y;
+        int cnt = have ? seg[j0 + lane].Count : 0;
+        cnt = cnt < 0 ? 0 : cnt;
+        // (64 counts of up to 2^31 - 1: the sum in two halves, each within 32 bits)
+        const uint32_t lo = wave_scan_add((uint32_t)cnt & 0xFFFFu), hi = wave_scan_add((uint32_t)cnt >> 16);
+        const long long incl = carry + (((long long)hi << 16) + lo), excl = incl - cnt;
+        if (have) segStart[j0 + lane] = excl > 0x7FFFFFFFLL ? 0x7FFFFFFF : (int)excl;
+        carry += ((long long)(uint32_t)__builtin_amdgcn_readlane((int)hi, 63) << 16) + (uint32_t)__builtin_amdgcn_readlane((int)lo, 63);
+    }
+}
+template <bool RAGGED>
+__global__ __launch_bounds__(64) void k_splice_walk(UlcxDecCtx c, SpliceSrc s, long long nAll, int nSeg, const int32_t *segOffs, const ulcx_segment *seg,
+                                                    const int32_t *segStart, ulcx_index_entry *outIndex, int outIndexStride) {
+    const long long id = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (id >= nAll) return;
+    const int per = outIndexStride - 1;
+    const long long o = id / per;
+    const int j = (int)(id - o * per);
+    const int2 sg = splice_segs(segOffs, (int)o, nSeg);
+    SpliceFile sf;
+    const SpliceBlk b = splice_block<RAGGED>(s, segStart, seg, sg, j, sf);
+    if (!b.ext) return;
+    const Walked w = scan_block<NybWin, false, false>(c, 0, sf.base + b.off, b.ext * 8, b.ext, c.in, c.in + c.inBytes);
+    if (w.bits <= 0 || ((w.bits + 7) >> 3) != b.ext) return;
+    ulcx_index_entry *e = outIndex + (size_t)o * outIndexStride + 1 + j;
+    e->ByteOffs = b.ext; e->RngState = (uint32_t)w.draws;
+}
+__global__ __launch_bounds__(64) void k_splice_scan(const uint32_t *jumpT, ulcx_index_entry *outIndex, int outIndexStride, long long outPayStride,
+                                                    int32_t *outPayBytes, int32_t *outMaxBlock, int32_t *outBlocks) {
+    const int o = blockIdx.x, lane = threadIdx.x;
+    ulcx_index_entry *row = outIndex + (size_t)o * outIndexStride;
+    const int cap = outIndexStride - 1;
+    const long long room = outPayStride < 0x7FFFFFFFLL ? outPayStride : 0x7FFFFFFFLL;
+    long long off = 0;
+    uint32_t st = 1234567u;                                          // ulcDecoder.c:76
+    int m = 0;
+    uint32_t mx = 0;
+    bool open = true;
+    for (int k0 = 0; k0 < cap; k0 += 64) {
+        const bool have = k0 + lane < cap;
+        ulcx_index_entry *e = row + 1 + k0 + (have ? lane : 0);
+        if (!open) { if (have) { e->ByteOffs = -1; e->RngState = 0u; } continue; }
+        int by = 0; uint32_t dr = 0;
+        if (have) { by = e->ByteOffs; dr = e->RngState; }
+        const bool ok = by > 0;
+        if (!ok) { by = 0; dr = 0; }
+        const uint32_t lo = wave_scan_add((uint32_t)by & 0xFFFFu), hi = wave_scan_add((uint32_t)by >> 16);
+        const uint32_t dIncl = wave_scan_add(dr);
+        const long long end = off + (((long long)hi << 16) + lo);
+        const unsigned long long stop = __ballot(have && (!ok || end > room));
+        const int here = cap - k0 < 64 ? cap - k0 : 64;
+        const int good = stop ? (int)__builtin_ctzll(stop) : here;
+        if (have) {
+            if (lane < good) { e->ByteOffs = (int)end; e->RngState = rng_jump(jumpT, st, dIncl); }
+            else { e->ByteOffs = -1; e->RngState = 0u; }
+        }
+        mx = umax32(mx, (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_max(lane < good ? (uint32_t)by : 0u), 63));
+        m += good;
+        if (stop) {
+            open = false;
+            if (good > 0) off += ((long long)(uint32_t)__builtin_amdgcn_readlane((int)hi, good - 1) << 16) + (uint32_t)__builtin_amdgcn_readlane((int)lo, good - 1);
+        } else {
+            off += ((long long)(uint32_t)__builtin_amdgcn_readlane((int)hi, 63) << 16) + (uint32_t)__builtin_amdgcn_readlane((int)lo, 63);
+            st = rng_jump(jumpT, st, (uint32_t)__builtin_amdgcn_readlane((int)dIncl, 63));
+        }
+    }
+    if (lane == 0) { outBlocks[o] = m; outPayBytes[o] = (int)off; if (outMaxBlock) outMaxBlock[o] = (int)mx; }
+}
+// 16 bytes from any address: the aligned words that hold them (4, or 5 for a source off its words), put together by shifts
+__device__ __forceinline__ uint4 splice_load16(const uint8_t *src) {
+    const unsigned sh = (unsigned)((uintptr_t)src & 3u) * 8u;
+    const uint32_t *sw = (const uint32_t *)(src - (sh >> 3));
+    uint32_t w0 = sw[0], w1 = sw[1], w2 = sw[2], w3 = sw[3];
+    if (sh) {
+        const uint32_t w4 = sw[4];
+        w0 = (w0 >> sh) | (w1 << (32u - sh)); w1 = (w1 >> sh) | (w2 << (32u - sh));
+        w2 = (w2 >> sh) | (w3 << (32u - sh)); w3 = (w3 >> sh) | (w4 << (32u - sh));
+    }
+    return make_uint4(w0, w1, w2, w3);
+}
+#define SPLICE_COPY_WG 256
+template <bool RAGGED>
+__global__ __launch_bounds__(SPLICE_COPY_WG) void k_splice_copy(SpliceSrc s, long long nAll, long long lines, int nSeg, const int32_t *segOffs, const ulcx_segment *seg,
+                                                                const int32_t *segStart, const ulcx_index_entry *outIndex, int outIndexStride,
+                                                                const int32_t *outBlocks, uint8_t *outPay, long long outPayStride) {
+    const long long id = (long long)blockIdx.x * SPLICE_COPY_WG + threadIdx.x;
+    if (id >= nAll) return;
+    const long long o = id / lines, line = id - o * lines;
+    const int nB = outBlocks[o];
+    if (nB <= 0) return;
+    const ulcx_index_entry *row = outIndex + (size_t)o * outIndexStride;
+    const int total = row[nB].ByteOffs;
+    uint8_t *dst = outPay + (size_t)o * (size_t)outPayStride;
+    // the line: bytes [a, z) of the file, z - a == 16 everywhere but at the file's two ends
+    const long long l0 = line * 16 - (long long)((uintptr_t)dst & 15u);
+    const int a = l0 < 0 ? 0 : (int)(l0 < total ? l0 : total), z = l0 + 16 < total ? (int)(l0 + 16) : total;
+    if (a >= z) return;
+    int lo = 0, hi = nB;                                             // the block byte a lies in: the last one that starts at or in front of it
+    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (row[mid].ByteOffs <= a) lo = mid + 1; else hi = mid; }
+    int blk = lo - 1;
+    const int2 sg = splice_segs(segOffs, (int)o, nSeg);
+    uint32_t v[4] = { 0u, 0u, 0u, 0u };
+    bool whole = false;
+    for (int at = a; at < z; blk++) {
+        const int b0 = row[blk].ByteOffs, b1 = row[blk + 1].ByteOffs, end = b1 < z ? b1 : z;
+        SpliceFile sf;
+        const SpliceBlk b = splice_block<RAGGED>(s, segStart, seg, sg, blk, sf);
+        if (b.ext != b1 - b0) return;                               // (not what the walk saw: tables that changed under the call)
+        const uint8_t *src = sf.base + b.off + (at - b0);
+        if (end - at == 16) { const uint4 x = splice_load16(src); v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; whole = true; }
+        else for (int i = at; i < end; i++) {
+            const unsigned q = (unsigned)(i - a), x = (unsigned)src[i - at] << ((q & 3u) * 8u);
+            v[0] |= (q >> 2) == 0u ? x : 0u; v[1] |= (q >> 2) == 1u ? x : 0u; v[2] |= (q >> 2) == 2u ? x : 0u; v[3] |= (q >> 2) == 3u ? x : 0u;
+        }
+        at = end;
+    }
+    if (whole || z - a == 16) *(uint4 *)(dst + a) = make_uint4(v[0], v[1], v[2], v[3]);
+    else for (int i = 0; i < z - a; i++) dst[a + i] = (uint8_t)((i < 4 ? v[0] : i < 8 ? v[1] : i < 12 ? v[2] : v[3]) >> ((i & 3) * 8));
+}
+
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
 // float index inside a padded FFT array (two floats of padding after every 32): complex n sits at FFT_PADS(n, DPS)
@@ -1971,6 +2171,27 @@ int ulcx_index_slots_launch(const UlcxDecCtx &c, int nRows, int nBlocks, const i
     const long long nAll = (long long)nRows * nBlocks;
     hipLaunchKernelGGL(k_dindex_slots_walk, dim3((unsigned)((nAll + 63) / 64)), dim3(64), 0, st, c, nAll, nBlocks, d_bits, d_index, indexStride, d_nBlocks);
     hipLaunchKernelGGL(k_dindex_slots_scan, dim3(nRows), dim3(64), 0, st, c.jumpT, nBlocks, d_index, indexStride, d_nBlocks);
+    CK(hipGetLastError());
+    return ULCX_OK;
+}
+
+// c.in / c.inBytes: the source's whole payload buffer; geometry and tables are all else that is read of c
+int ulcx_splice_launch(const UlcxDecCtx &c, const UlcxSpliceArgs &a, hipStream_t st) {
+    SpliceSrc s = { c.in, c.inBytes, a.payStride, a.payBytes, a.index, a.indexStride, a.indexBlocks, a.payOffs, a.idxOffs, a.idxTotal, a.nFiles };
+    const bool ragged = a.payOffs != nullptr;
+    const long long nEnt = (long long)a.nOut * a.outIndexStride, nBlk = (long long)a.nOut * (a.outIndexStride - 1);
+    // aligned 16-byte lines a file of outPayStride bytes can touch, wherever it starts
+    const long long lines = (a.outPayStride + 15 + 15) / 16, nLines = (long long)a.nOut * lines;
+    hipLaunchKernelGGL(k_dindex_begin, dim3((unsigned)((nEnt + 255) / 256)), dim3(256), 0, st, nEnt, a.outIndexStride, a.outIndex, a.outIndexBlocks);
+    hipLaunchKernelGGL(k_splice_plan, dim3(a.nOut), dim3(64), 0, st, a.nSeg, a.segOffs, a.seg, a.segStart);
+    if (ragged) hipLaunchKernelGGL(k_splice_walk<true>, dim3((unsigned)((nBlk + 63) / 64)), dim3(64), 0, st, c, s, nBlk, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride);
+    else hipLaunchKernelGGL(k_splice_walk<false>, dim3((unsigned)((nBlk + 63) / 64)), dim3(64), 0, st, c, s, nBlk, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride);
+    hipLaunchKernelGGL(k_splice_scan, dim3(a.nOut), dim3(64), 0, st, c.jumpT, a.outIndex, a.outIndexStride, a.outPayStride, a.outPayBytes, a.outMaxBlock, a.outIndexBlocks);
+    const dim3 cg((unsigned)((nLines + SPLICE_COPY_WG - 1) / SPLICE_COPY_WG));
+    if (ragged) hipLaunchKernelGGL(k_splice_copy<true>, cg, dim3(SPLICE_COPY_WG), 0, st, s, nLines, lines, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride,
+                                   a.outIndexBlocks, a.outPay, a.outPayStride);
+    else hipLaunchKernelGGL(k_splice_copy<false>, cg, dim3(SPLICE_COPY_WG), 0, st, s, nLines, lines, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride,
+                            a.outIndexBlocks, a.outPay, a.outPayStride);
     CK(hipGetLastError());
     return ULCX_OK;
 }

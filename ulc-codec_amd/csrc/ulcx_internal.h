@@ -254,6 +254,18 @@ int ulcx_index_ragged_launch(const UlcxDecCtx &c, const int64_t *d_payOffs, cons
 int ulcx_index_begin_launch(int nRows, ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, hipStream_t st);
 int ulcx_index_slots_launch(const UlcxDecCtx &c, int nRows, int nBlocks, const int32_t *d_bits, ulcx_index_entry *d_index, int indexStride,
                             int32_t *d_nBlocks, hipStream_t st);
+// corpus splice (ulcx_corpus_splice_*): the source corpus beside c.in / c.inBytes (payOffs != NULL: ragged, as UlcxDecAux), the
+// segment list and the outputs; five launches, no scratch
+struct UlcxSpliceArgs {
+    int nFiles;
+    long long payStride; const int32_t *payBytes;
+    const ulcx_index_entry *index; int indexStride; const int32_t *indexBlocks;
+    const int64_t *payOffs, *idxOffs; long long idxTotal;
+    int nOut, nSeg; const int32_t *segOffs; const ulcx_segment *seg; int32_t *segStart;
+    uint8_t *outPay; long long outPayStride; int32_t *outPayBytes, *outMaxBlock;
+    ulcx_index_entry *outIndex; int outIndexStride; int32_t *outIndexBlocks;
+};
+int ulcx_splice_launch(const UlcxDecCtx &c, const UlcxSpliceArgs &a, hipStream_t st);
 size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds);
 size_t ulcx_spec_lds_bytes(int BS);               // k_dspec's dynamic LDS: two unit arrays where a CU holds them, else one
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device

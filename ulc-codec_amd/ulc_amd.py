@@ -50,6 +50,7 @@ EXPORTS = [
     "ulcx_encode_clips_spectra_dev", "ulcx_encode_clips_spectra_dev_pcm16", "ulcx_encode_clips_spectra_host",
     "ulcx_encode_clips_ladder_dev", "ulcx_encode_clips_ladder_dev_pcm16", "ulcx_encode_clips_ladder_host",
     "ulcx_synth_spectra_dev", "ulcx_synth_spectra_dev_pcm16", "ulcx_synth_spectra_host",
+    "ulcx_corpus_splice_dev", "ulcx_corpus_splice_ragged_dev", "ulcx_corpus_splice_host", "ulcx_corpus_splice_ragged_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -59,6 +60,8 @@ SYNTH_WARM = 2                                             # ULCX_SYNTH_WARM: fl
 
 # one entry of a block index (include/ulc_amd.h, ulcx_index_entry): 8 bytes
 INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
+# one segment of a splice (ulcx_segment): blocks First .. First + Count - 1 of source file File; 12 bytes
+SEGMENT_DTYPE = np.dtype([("File", np.int32), ("First", np.int32), ("Count", np.int32)])
 
 
 
@@ -251,6 +254,14 @@ def lib():
             l.ulcx_encode_clips_ladder_dev_pcm16.argtypes = l.ulcx_encode_clips_ladder_dev.argtypes
             l.ulcx_encode_clips_ladder_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Rung), C.c_int, _f32p, _i32p, C.c_int,
                                                         _u8p, C.c_longlong, _i32p, _i32p, C.c_void_p, C.c_int, _i32p, _f32p]
+        if hasattr(l, "ulcx_corpus_splice_dev"):           # splice: new files from block ranges of resident files
+            out_dev = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            out_host = [C.c_int, _i32p, C.c_void_p, C.c_int, _u8p, C.c_longlong, _i32p, _i32p, C.c_void_p, C.c_int, _i32p, _i32p]
+            l.ulcx_corpus_splice_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + out_dev + [C.c_void_p]
+            l.ulcx_corpus_splice_ragged_dev.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+                                                        + out_dev + [C.c_void_p])
+            l.ulcx_corpus_splice_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i32p, C.c_void_p, C.c_int, _i32p] + out_host
+            l.ulcx_corpus_splice_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p] + out_host
         l.ulcx_encoder_debug_fetch.argtypes = [C.c_void_p, C.c_int, _f32p, _f32p, _f32p, _u8p, _i32p]
         l.ulcx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         l.ulcx_decoder_destroy.argtypes = [C.c_void_p]
@@ -970,6 +981,73 @@ class BatchDecoder(_StreamSlots):
         fn = lib().ulcx_decode_crops_dev_pcm16 if pcm16 else lib().ulcx_decode_crops_dev
         _check(fn(self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_first, d_count or None,
                   n_blocks, d_pcm, d_bits, stream or None), "ulcx_decode_crops_dev_pcm16" if pcm16 else "ulcx_decode_crops_dev")
+
+    @staticmethod
+    def _segments(segments):
+        """One list of (file, first, count) per output file -> (seg_offs int32 [nOut + 1], seg SEGMENT_DTYPE [nSeg])."""
+        offs = np.zeros(len(segments) + 1, np.int32)
+        offs[1:] = np.cumsum([len(f) for f in segments])
+        seg = np.zeros(max(int(offs[-1]), 1), SEGMENT_DTYPE)
+        flat = [tuple(int(x) for x in g) for f in segments for g in f]
+        if flat:
+            seg[:len(flat)] = np.array(flat, SEGMENT_DTYPE)
+        return offs, seg
+
+    def _splice_host(self, ragged, F, src, segments, out_payload_stride, out_index_stride, out):
+        offs, seg = segments if isinstance(segments, tuple) else self._segments(segments)
+        offs = np.ascontiguousarray(offs, dtype=np.int32)
+        seg = np.ascontiguousarray(seg, dtype=SEGMENT_DTYPE)
+        n_out, n_seg = offs.shape[0] - 1, seg.shape[0]
+        r = out or {"payload": np.zeros((n_out, out_payload_stride), np.uint8), "payload_bytes": np.zeros(n_out, np.int32),
+                    "max_block": np.zeros(n_out, np.int32), "index": np.zeros((n_out, out_index_stride), INDEX_DTYPE),
+                    "index_blocks": np.zeros(n_out, np.int32), "seg_start": np.zeros(n_seg, np.int32)}
+        fn = lib().ulcx_corpus_splice_ragged_host if ragged else lib().ulcx_corpus_splice_host
+        _check(fn(self.h, F, *src, n_out, _p(offs, _i32p), seg.ctypes.data, n_seg, _p(r["payload"], _u8p), r["payload"].shape[1], _p(r["payload_bytes"], _i32p),
+                  _p(r["max_block"], _i32p), r["index"].ctypes.data, r["index"].shape[1], _p(r["index_blocks"], _i32p), _p(r["seg_start"], _i32p)),
+               "ulcx_corpus_splice_ragged_host" if ragged else "ulcx_corpus_splice_host")
+        return r
+
+    def corpus_splice(self, payload, payload_bytes, index, index_blocks, segments, out_payload_stride, out_index_stride, out=None):
+        """New files from block ranges of a corpus's files (ulcx_corpus_splice_host).  The source as decode_crops() takes it;
+        `segments` is one list of (file, first, count) per output file, or the pair (seg_offs int32 [nOut + 1], seg SEGMENT_DTYPE
+        [nSeg]).  -> dict: payload uint8 [nOut][out_payload_stride] (bytes behind payload_bytes[o] as `out` held them, or zeros),
+        payload_bytes, max_block, index [nOut][out_index_stride], index_blocks, seg_start [nSeg]."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        F, stride = payload.shape
+        assert nbytes.shape == (F,) and index.shape[0] == F and blocks.shape == (F,)
+        src = (_p(payload, _u8p), stride, _p(nbytes, _i32p), index.ctypes.data, index.shape[1], _p(blocks, _i32p))
+        return self._splice_host(False, F, src, segments, out_payload_stride, out_index_stride, out)
+
+    def corpus_splice_ragged(self, payload, payload_offs, index, index_offs, index_blocks, segments, out_payload_stride, out_index_stride, out=None):
+        """corpus_splice() of a ragged source (ulcx_corpus_splice_ragged_host), as decode_crops_ragged() takes it; the output is strided."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        poffs = np.ascontiguousarray(payload_offs, dtype=np.int64)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE).reshape(-1)
+        ioffs = np.ascontiguousarray(index_offs, dtype=np.int64)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        F = blocks.shape[0]
+        assert poffs.shape == (F + 1,) and ioffs.shape == (F + 1,)
+        src = (_p(payload, _u8p), payload.size, _p(poffs, _i64p), index.ctypes.data, index.size, _p(ioffs, _i64p), _p(blocks, _i32p))
+        return self._splice_host(True, F, src, segments, out_payload_stride, out_index_stride, out)
+
+    def corpus_splice_dev(self, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n_out, d_seg_offs, d_seg, n_seg,
+                          d_out_payload, out_payload_stride, d_out_payload_bytes, d_out_max_block, d_out_index, out_index_stride, d_out_index_blocks,
+                          d_seg_start, stream=0):
+        """Device form (raw device pointers; d_out_max_block 0 / None: not wanted); asynchronous on `stream`."""
+        _check(lib().ulcx_corpus_splice_dev(self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n_out, d_seg_offs, d_seg,
+                                            n_seg, d_out_payload, out_payload_stride, d_out_payload_bytes, d_out_max_block or None, d_out_index,
+                                            out_index_stride, d_out_index_blocks, d_seg_start, stream or None), "ulcx_corpus_splice_dev")
+
+    def corpus_splice_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks, n_out,
+                                 d_seg_offs, d_seg, n_seg, d_out_payload, out_payload_stride, d_out_payload_bytes, d_out_max_block, d_out_index,
+                                 out_index_stride, d_out_index_blocks, d_seg_start, stream=0):
+        _check(lib().ulcx_corpus_splice_ragged_dev(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
+                                                   n_out, d_seg_offs, d_seg, n_seg, d_out_payload, out_payload_stride, d_out_payload_bytes,
+                                                   d_out_max_block or None, d_out_index, out_index_stride, d_out_index_blocks, d_seg_start, stream or None),
+               "ulcx_corpus_splice_ragged_dev")
 
     def index_packed_rows(self, payload, payload_bytes, max_blocks):
         """index_packed() for any number of rows (a corpus's files), whatever the decoder's stream count."""
