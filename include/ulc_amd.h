@@ -307,6 +307,21 @@ int  ulcx_encoder_last_fallbacks(ulcx_encoder *enc);
  * launch, no retry - what the small capacities cannot hold goes straight to the serial kernel). */
 int  ulcx_encoder_debug_writer_flags(ulcx_encoder *enc, int nBlocks, int32_t *h_flags);
 int  ulcx_encoder_debug_writer_plan(ulcx_encoder *enc, int32_t plan[11]);
+/* Test hooks, read-only: the sample-rate axis.  RateHz decides at create time which Bark kernels an encoder runs: the band edges
+ * of every subblock size follow from (BlockSize, RateHz), and the most bands the full-size tables have open at one line sizes
+ * the snapshot ring of k_bark_uniform - 4 or 8, or 0 where more than 8 are open: then the lane-per-subblock kernels
+ * (k_nbark / k_pbark) take every block.
+ * ulcx_debug_band_plan: host arithmetic only, no device and no object; the code ulcx_encoder_create runs.  edges
+ *   [2: noise | masking][4: subblock size BlockSize >> d][2: first line | end line][25 bands] int16; *most: the most bands open at
+ *   one line (first line <= line <= end line) over both full-size tables; *ring: 0, 4 or 8.  most and ring may be NULL.
+ * ulcx_debug_band_events: the same edges as the lists k_bark_uniform walks, [2][4][52] words line | kind << 16 | band << 24
+ *   (kind 0: lower edge, 1: upper edge, 2: end of the subblock, 3: padding behind it).
+ * ulcx_encoder_debug_plan: what this object decided - {ring, most bands open, k_nsums in use (useGapSums), the exact path's heap in
+ *   LDS (0: in the object's scratch), resident workgroups of k_nsums, chunks of the window-control pipeline, selection with a wave
+ *   per channel (k_select_pair)}.  No device work. */
+int  ulcx_debug_band_plan(int BlockSize, int RateHz, int16_t *edges, int32_t *most, int32_t *ring);
+int  ulcx_debug_band_events(int BlockSize, int RateHz, uint32_t *events);
+int  ulcx_encoder_debug_plan(ulcx_encoder *enc, int32_t plan[7]);
 /* Test hook: how the last decode call's synthesis was launched - workgroups (0: one per stream), how many of them took one
  * whole stream each (ulcx_dec_tail_plan; 0 for an even cut, ulcx_dec_split_plan), and the workgroups of the synthesis kernel
  * the device holds at once (0: this geometry runs the general kernel, never cut). */

@@ -70,6 +70,7 @@ struct ulcx_encoder {
     bool keysFinal = false;
     int wcSteps = -1, wcFuse = 1;     // environment switches, read once at create
     int nsSlots = 0;                  // resident workgroups of k_nsums (its persistent grid)
+    int barkMost = 0;                 // most Bark bands the full-size band tables have open at one line: what sized ctx.barkRing
     bool lastAnalyse = false;         // the last call was an analysis call: no intermediates, no exact-path count to report
     int analyseKxf = 0;               // ULCX_ANALYSE_KXF=1: analysis calls run the encode call's transform (timing comparisons)
     // staging for the host-pointer API
@@ -266,28 +267,9 @@ extern "C" int ulcx_encoder_create(ulcx_encoder **out, int device, int nStreams,
     c.cplxScale = 0x1.62E430p-1f * (31 - __builtin_clz((unsigned)BlockSize));   // BlockTransform.c:320
     rc = ulcx_tables_build(&c.T, &e->tables, BlockSize, RateHz, true);
     if (rc) { cleanup(e); return rc; }
-    {   // k_bark_uniform keeps one snapshot of the running sums per Bark band that is open (lower edge passed, upper edge
-        // not yet): the most the full-size band tables ever have open at once sizes its ring
-        int most = 0;
-        const int N = BlockSize / 2;
-        for (int t = 0; t < 2; t++) {
-            const short *beg = t ? c.T.pBeg[0] : c.T.nBeg[0], *end = t ? c.T.pEnd[0] : c.T.nEnd[0];
-            for (int b = 0; b < ULCX_NBARK; b++) {
-                if (beg[b] > end[b] || end[b] > N) most = 1 << 20;
-                if (b && (beg[b] < beg[b - 1] || end[b] < end[b - 1])) most = 1 << 20;
-            }
-            for (int pos = 0; pos <= N; pos++) {
-                int open = 0;
-                for (int b = 0; b < ULCX_NBARK; b++) open += (beg[b] <= pos && pos <= end[b]) ? 1 : 0;
-                if (open > most) most = open;
-            }
-        }
-        int ring = 4;
-        while (ring < most) ring *= 2;
-        c.barkRing = (ring <= 8 && N % 32 == 0) ? ring : 0;               // (0: k_nbark / k_pbark for every block - geometries whose band edges need a deeper ring)
-        // (round 3: also for a few blocks per call - the drop-in's one: the four-wave kernel walks a row's 1024 lines in a
-        //  quarter of the time the lane-per-subblock kernels take, which is what a single stream waits for)
-    }
+    c.barkRing = ulcx_tables_bark_ring(c.T, BlockSize, &e->barkMost);
+    // (round 3: the ring kernels also for a few blocks per call - the drop-in's one: the four-wave kernel walks a row's 1024 lines in
+    //  a quarter of the time the lane-per-subblock kernels take, which is what a single stream waits for)
     size_t B = nStreams, K = maxBlocksPerCall, NB = B * K, cb = (size_t)nChan * BlockSize;
     DA(c.hist, B * 2 * BlockSize * nChan, true);
     DA(c.wcs, B, true);
@@ -1269,6 +1251,18 @@ extern "C" int ulcx_encoder_debug_writer_plan(ulcx_encoder *e, int32_t plan[11])
     ulcx_enc_writer_plan(e->ctx, caps, &haveMid, &haveFull);
     for (int t = 0; t < 3; t++) for (int i = 0; i < 3; i++) plan[3 * t + i] = caps[t][i];
     plan[9] = haveMid; plan[10] = haveFull;
+    return ULCX_OK;
+}
+// Test hook: what create decided for this object.  selPair and the heap's place are enc_plan's (ulcx_enc.hip), restated for the
+// reason given at ulcx_enc_writer_plan.
+extern "C" int ulcx_encoder_debug_plan(ulcx_encoder *e, int32_t plan[7]) {
+    if (!e || !plan) return refuse("ulcx_encoder_debug_plan", "no encoder, or no array");
+    const UlcxEncCtx &c = e->ctx;
+    const size_t cb = (size_t)c.C * c.BS;
+    plan[0] = c.barkRing; plan[1] = e->barkMost; plan[2] = c.useGapSums;
+    plan[3] = (cb * 8 <= ULCX_HEAP_LDS_BYTES) ? 1 : 0;
+    plan[4] = e->nsSlots; plan[5] = e->wcPipe;
+    plan[6] = (cb / 64 == 128 && c.C == 2 && c.selPair) ? 1 : 0;
     return ULCX_OK;
 }
 extern "C" const char *ulcx_encoder_stage_name(int i) { return (i >= 0 && i < ULCX_ENC_STAGES_REPORTED) ? ulcx_enc_stage_names[i] : ""; }

@@ -180,6 +180,7 @@ __host__ __device__ static inline unsigned ulcx_pattern(int wc) {
 
 // host side (ulcx_tables.cpp)
 int  ulcx_tables_build(UlcxTables *devT, void **devBlob, int BS, int rateHz, bool forEncoder);
+int  ulcx_tables_bark_ring(const UlcxTables &T, int BS, int *mostOpen);   // the snapshot ring of k_bark_uniform for full-size band tables (0: none fits); the most bands open at one line
 void ulcx_set_error(const char *fmt, ...);
 
 // launchers (ulcx_enc.hip / ulcx_dec.hip)

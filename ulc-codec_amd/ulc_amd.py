@@ -15,13 +15,16 @@ _i32p = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
 _i64p = C.POINTER(C.c_int64)
 
+N_BARK, MAX_SUB, BARK_EVENTS = 25, 4, 52
+PLAN_FIELDS = ("bark_ring", "most_open", "use_gap_sums", "heap_in_lds", "ns_slots", "wc_pipe", "sel_pair")
+
 EXPORTS = [
     "ULC_EncoderState_Init", "ULC_EncoderState_Destroy", "ULC_EncodeBlock_CBR", "ULC_EncodeBlock_ABR",
     "ULC_EncodeBlock_VBR", "ULC_DecoderState_Init", "ULC_DecoderState_Destroy", "ULC_DecodeBlock",
     "ulcx_last_error", "ulcx_device_count", "ulcx_encoder_create", "ulcx_encoder_destroy", "ulcx_encoder_reset",
     "ulcx_encoder_slot_bytes", "ulcx_encode_dev", "ulcx_encode_dev_pcm16", "ulcx_encode_host", "ulcx_encoder_debug_fetch",
     "ulcx_decoder_create", "ulcx_decoder_destroy", "ulcx_decoder_reset", "ulcx_decode_dev", "ulcx_decode_dev_pcm16", "ulcx_decode_host",
-    "ulcx_encoder_last_fallbacks", "ulcx_encoder_debug_force_exact", "ulcx_encoder_debug_writer_flags", "ulcx_encoder_debug_writer_plan", "ulcx_ulc_header_pack", "ulcx_ulc_header_parse", "ulcx_ulc_rate_kbps",
+    "ulcx_encoder_last_fallbacks", "ulcx_encoder_debug_force_exact", "ulcx_encoder_debug_writer_flags", "ulcx_encoder_debug_writer_plan", "ulcx_debug_band_plan", "ulcx_debug_band_events", "ulcx_encoder_debug_plan", "ulcx_ulc_header_pack", "ulcx_ulc_header_parse", "ulcx_ulc_rate_kbps",
     "ulcx_pack_streams_dev", "ulcx_decode_packed_dev", "ulcx_decode_packed_host", "ulcx_decoder_upload_payload", "ulcx_decode_resident_host", "ulcx_encoder_stage_ms", "ulcx_encoder_stage_name", "ulcx_encoder_last_xf_launches", "ulcx_decoder_stage_ms", "ulcx_decoder_stage_name", "ulcx_block_extent_bytes", "ulcx_encoder_set_timing", "ulcx_decoder_set_timing", "ulcx_encode_block1", "ulcx_decode_block1", "ulcx_decode_block1_rng", "ulcx_build_rev", "ulcx_dec_split_plan", "ulcx_dec_tail_plan", "ulcx_decoder_last_cut",
     "ulcx_encode_dev_rates", "ulcx_encode_dev_pcm16_rates", "ulcx_encode_host_rates",
     "ulcx_analyse_dev", "ulcx_analyse_dev_pcm16", "ulcx_analyse_host",
@@ -272,6 +275,9 @@ def lib():
         l.ulcx_encoder_last_fallbacks.argtypes = [C.c_void_p]
         l.ulcx_encoder_debug_writer_flags.argtypes = [C.c_void_p, C.c_int, _i32p]
         l.ulcx_encoder_debug_writer_plan.argtypes = [C.c_void_p, _i32p]
+        l.ulcx_encoder_debug_plan.argtypes = [C.c_void_p, _i32p]
+        l.ulcx_debug_band_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int16), _i32p, _i32p]
+        l.ulcx_debug_band_events.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_uint32)]
         l.ulcx_decoder_last_cut.argtypes = [C.c_void_p, _i32p, _i32p, _i32p]
         l.ulcx_dec_tail_plan.argtypes = [C.c_int, C.c_int, C.c_int, _i32p]
         l.ulcx_encoder_debug_force_exact.argtypes = [C.c_void_p, C.c_int]
@@ -415,6 +421,25 @@ class _StreamSlots:
     def load_streams_dev(self, d_slots, n, d_state, stream=0):
         fn, name = self._fn("load_streams_dev")
         _check(fn(self.h, d_slots, n, d_state, stream or None), name)
+
+
+def band_plan(block_size, rate_hz):
+    """The Bark band tables an encoder of (block_size, rate_hz) is created with, host arithmetic only (no device, no object):
+    edges int16 [noise|psycho][MAX_SUB][beg|end][N_BARK], the most bands open at one line of the full-size tables, and the snapshot
+    ring ulcx_encoder_create derives from them (0: the lane-per-subblock kernels for every block).  Test hook."""
+    edges = np.zeros((2, MAX_SUB, 2, N_BARK), np.int16)
+    most, ring = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    _check(lib().ulcx_debug_band_plan(int(block_size), int(rate_hz), _p(edges, C.POINTER(C.c_int16)), _p(most, _i32p), _p(ring, _i32p)),
+           "ulcx_debug_band_plan")
+    return edges, int(most[0]), int(ring[0])
+
+
+def band_events(block_size, rate_hz):
+    """The band-edge lists k_bark_uniform walks: uint32 [noise|psycho][MAX_SUB][BARK_EVENTS] words line | kind << 16 | band << 24
+    (kind 0: lower edge, 1: upper edge, 2: end of the subblock, 3: padding).  Test hook."""
+    ev = np.zeros((2, MAX_SUB, BARK_EVENTS), np.uint32)
+    _check(lib().ulcx_debug_band_events(int(block_size), int(rate_hz), _p(ev, C.POINTER(C.c_uint32))), "ulcx_debug_band_events")
+    return ev
 
 
 class BatchEncoder(_StreamSlots):
@@ -782,6 +807,13 @@ class BatchEncoder(_StreamSlots):
         _check(lib().ulcx_encoder_debug_writer_plan(self.h, _p(p, _i32p)), "ulcx_encoder_debug_writer_plan")
         return dict(small=tuple(int(v) for v in p[0:3]), medium=tuple(int(v) for v in p[3:6]), full=tuple(int(v) for v in p[6:9]),
                     have_mid=bool(p[9]), have_full=bool(p[10]))
+
+    def plan(self):
+        """What create decided for this object: bark_ring (0, 4 or 8), most_open, use_gap_sums, heap_in_lds, ns_slots, wc_pipe,
+        sel_pair.  Test hook."""
+        p = np.zeros(len(PLAN_FIELDS), np.int32)
+        _check(lib().ulcx_encoder_debug_plan(self.h, _p(p, _i32p)), "ulcx_encoder_debug_plan")
+        return {k: int(v) for k, v in zip(PLAN_FIELDS, p)}
 
     def force_exact(self, every):
         _check(lib().ulcx_encoder_debug_force_exact(self.h, int(every)), "ulcx_encoder_debug_force_exact")
