@@ -553,3 +553,65 @@ def test_hfext_from_sums_on_device(noise_cases):
     bad = np.flatnonzero((gh != refhf).any(1))
     assert bad.size == 0, (f"hfext_from_sums: {bad.size} of {q.size} cases differ from orc_get_hfext_params, first case {bad[0]} ({cnt[bad[0]]} pairs, q = {q[bad[0]]!r}, "
                            f"sums {[f'{x!r} ({bits_of(x):#010x})' for x in sum5[bad[0]]]}): device {{NoiseQ, NoiseDecay}} = {gh[bad[0]].tolist()}, oracle {refhf[bad[0]].tolist()}")
+
+
+# ---- the view of a corpus --------------------------------------------------------------------------------------------
+# corpus_file / file_block (ulcx_dec_dev.h): what every indexed walk and the splice kernels read a corpus through.  The model is
+# the rule as include/ulc_amd.h states it, in Python integers; the tables hold every hostile case once.  Nothing is decoded and no
+# payload byte exists: the offsets are arithmetic only (one file is exactly 2^31 bytes long).
+VIEW_KS = (-1, 0, 1, 2, 3, 4, 5)
+
+
+def _view_model(byte_offs, index_blocks, pay_offs=None, idx_offs=None, pay_total=0, pay_stride=0, pay_bytes=None, index_stride=0):
+    rows = []
+    for f, nb in enumerate(int(x) for x in index_blocks):
+        if pay_offs is not None:
+            p0, p1, i0, i1 = int(pay_offs[f]), int(pay_offs[f + 1]), int(idx_offs[f]), int(idx_offs[f + 1])
+            ok = 0 <= p0 <= p1 <= pay_total and p1 - p0 < 2 ** 31 and 0 <= i0 <= i1 <= len(byte_offs) and i1 - i0 >= max(nb, 0) + 1
+            base, row, avail, nI = (p0, i0, p1 - p0, max(nb, 0)) if ok else (0, 0, 0, 0)
+        else:
+            base, row = f * pay_stride, f * index_stride
+            avail, nI = min(max(int(pay_bytes[f]), 0), pay_stride), min(max(nb, 0), index_stride - 1)
+        out = [base, row, avail, nI]
+        for k in VIEW_KS:
+            off = ext = 0
+            if 0 <= k < nI:
+                o0, o1 = int(byte_offs[row + k]), int(byte_offs[row + k + 1])
+                if o0 >= 0 and o0 < o1 <= avail:
+                    off, ext = o0, o1 - o0
+            out += [off, ext]
+        rows.append(out)
+    return np.array(rows, np.int64)
+
+
+_G = 2 ** 31
+VIEW_CORPORA = {
+    # rows of 6 entries, payloads 1000 bytes apart
+    "strided": dict(pay_stride=1000, index_stride=6,
+                    #            sound  count < 0  count > stride-1  bytes < 0  bytes > stride  falling entry  entry < 0  entries past the bytes / equal
+                    index_blocks=[4,    -3,        9,                2,         3,              3,             2,         4],
+                    pay_bytes=[900,     500,       60,               -5,        5000,           1000,          1000,      150],
+                    byte_offs=[0, 100, 250, 400, 900, -1,   0, 10, 20, -1, -1, -1,   0, 10, 20, 30, 40, 50,   0, 10, 20, -1, -1, -1,
+                               0, 500, 1000, 1200, -1, -1,   0, 300, 200, 400, -1, -1,   -4, 100, 200, -1, -1, -1,   0, 100, 100, 200, 120, -1]),
+    # hostile payload offsets: a pair that falls into a negative entry, a negative start, a falling pair, a file of exactly 2^31
+    # bytes, an end past the total; among the sound files one whose row is one entry short and one whose entries fall / leave it
+    "ragged, payload table": dict(pay_total=_G + 5000, pay_offs=[0, 900, -8, 1000, 3000, 2000, 2000 + _G, _G + 4000, _G + 9000],
+                                  idx_offs=[0, 5, 5, 10, 14, 14, 20, 26, 30], index_blocks=[4, 0, 2, 4, 0, 3, 4, 2],
+                                  byte_offs=[0, 100, 250, 400, 900,   0, 10, 20, 30, 40,   0, 500, 1000, 2000,   0, 10, 20, 30, 40, 50,
+                                             0, 500, 400, 2500, 1900, 2000,   0, 10, 20, 30]),
+    # hostile index offsets: a falling pair, a negative start, an end and a start past the total; a count < 0
+    "ragged, index table": dict(pay_total=800, pay_offs=[0, 100, 200, 300, 400, 500, 600, 700, 800],
+                                idx_offs=[0, 4, -2, 8, 6, 12, 16, 40, 20], index_blocks=[-1, 1, 1, 1, 5, 3, 2, 2],
+                                byte_offs=[0, 10, 20, 30,   0, 50, 100, -1,   0, 20, 40, 60,   80, 100, 0, 30, 60, 100,   0, 1, 2, 3, 4, 5]),
+}
+
+
+@pytest.mark.parametrize("name", list(VIEW_CORPORA))
+def test_corpus_view_on_device(name):
+    c = VIEW_CORPORA[name]
+    want = _view_model(**c)
+    got = U.dev_corpus_view(ks=VIEW_KS, **c)
+    assert (want[:, 5::2] > 0).any() and (want[:, 3] == 0).any(), "the tables hold neither a block that is found nor a file without blocks"
+    bad = np.flatnonzero((got != want).any(1))
+    assert bad.size == 0, (f"corpus_file / file_block, {name} corpus: {bad.size} of {len(want)} files differ, first file {bad[0]}: device "
+                           f"{{base, row, avail, nI, (off, ext) of blocks {VIEW_KS}}} = {got[bad[0]].tolist()}, model {want[bad[0]].tolist()}")

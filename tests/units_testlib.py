@@ -109,6 +109,7 @@ def units_lib():
         l.ulcx_units_wave.argtypes = [P, LL, P]
         l.ulcx_units_noise_q.argtypes = [P, P, P, LL, P]
         l.ulcx_units_hfext.argtypes = [P, P, LL, P]
+        l.ulcx_units_corpus.argtypes = [I, LL, LL, P, P, P, LL, I, P, P, P, I, P]
         assert l.ulcx_units_function_count() == UF_COUNT, "function numbers of ulcx_units.hip and of the tests differ"
         _units = l
     return _units
@@ -230,6 +231,23 @@ def dev_hfext(sum5, q):
     ts, tq, out = to_dev(sum5.reshape(-1)), to_dev(q), dev_empty(2 * n, np.int32)
     _run(units_lib().ulcx_units_hfext, ts.data_ptr(), tq.data_ptr(), n, out.data_ptr())
     return from_dev(out, np.int32).reshape(n, 2)
+
+
+def dev_corpus_view(byte_offs, index_blocks, ks, pay_offs=None, idx_offs=None, pay_total=0, pay_stride=0, pay_bytes=None, index_stride=0):
+    """corpus_file and file_block over every file of caller-given tables: [nFiles][4 + 2 * len(ks)] int64 =
+    {base offset, row offset in entries, avail, nI, then {off, ext} of block ks[j]}.  byte_offs: the ByteOffs of the whole index
+    (its RngState words are zeros).  pay_offs / idx_offs given: a ragged corpus of pay_total bytes; else a strided one."""
+    byte_offs, index_blocks, ks = (np.ascontiguousarray(a, np.int32) for a in (byte_offs, index_blocks, ks))
+    index = np.zeros((byte_offs.size, 2), np.int32)
+    index[:, 0] = byte_offs
+    n, opt = index_blocks.size, lambda a, dt: None if a is None else to_dev(np.ascontiguousarray(a, dt))
+    ti, tb, tk = to_dev(index.reshape(-1)), to_dev(index_blocks), to_dev(ks)
+    tpo, tio, tpb = opt(pay_offs, np.int64), opt(idx_offs, np.int64), opt(pay_bytes, np.int32)
+    out = dev_empty(n * (4 + 2 * ks.size), np.int64)
+    p = lambda t: None if t is None else t.data_ptr()
+    _run(units_lib().ulcx_units_corpus, n, pay_total, pay_stride, p(tpb), p(tpo), ti.data_ptr(), byte_offs.size, index_stride, p(tio), tb.data_ptr(),
+         tk.data_ptr(), ks.size, out.data_ptr())
+    return from_dev(out, np.int64).reshape(n, 4 + 2 * ks.size)
 
 
 # ---- grids -----------------------------------------------------------------------------------------------------------

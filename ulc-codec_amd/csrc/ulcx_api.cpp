@@ -1925,38 +1925,85 @@ extern "C" int ulcx_decode_resident_range_host(ulcx_decoder *e, const int32_t *h
     return rc ? rc : dec_results_down(e, e->d_pcm, e->d_bits, (size_t)e->B * nBlocks, h_pcm, h_bits);
 }
 
+// ---- the corpus of a call (UlcxCorpus, ulcx_internal.h): every entry of the crop, sample-crop, spectra and splice families builds
+// it once from its public arguments (ulcx_corpus_strided / ulcx_corpus_ragged), and from there on it is one argument.  What the
+// families check of it, in the pieces their orders of refusal need: its pointers, the scalars of its layout, its alignments.
+static bool corpus_null(const UlcxCorpus &g) { return !g.pay || !g.index || !g.indexBlocks || (g.ragged ? (!g.payOffs || !g.idxOffs) : !g.payBytes); }
+static int corpus_layout_bad(const char *who, const UlcxCorpus &g) {
+    if (g.ragged ? (g.payTotal >= 0 && g.idxTotal >= 0) : (g.payStride >= 1 && g.indexStride >= 1)) return 0;
+    if (g.ragged) refuse(who, "bad argument (payloadTotal %lld, indexTotal %lld)", g.payTotal, g.idxTotal);
+    else refuse(who, "bad argument (payloadStride %lld, indexStride %d)", g.payStride, g.indexStride);
+    return 1;
+}
+static int corpus_misaligned(const char *who, const UlcxCorpus &g) {
+    return misaligned(who, "d_payloadOffs", g.payOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", g.idxOffs, ULCX_ALIGN_OFFS) ||
+           misaligned(who, "d_payloadBytes", g.payBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", g.index, ULCX_ALIGN_WORD) ||
+           misaligned(who, "d_indexBlocks", g.indexBlocks, ULCX_ALIGN_WORD);
+}
+// What only a host form can refuse of a corpus, and its way to the device.
+// the two tables of a ragged corpus: offsets that are negative, fall or leave their buffer, a file of 2^31 bytes or more
+static int ragged_tables_bad(const char *who, const UlcxCorpus &g) {
+    for (int f = 0; f < g.nFiles; f++) {
+        const long long p0 = g.payOffs[f], p1 = g.payOffs[f + 1], i0 = g.idxOffs[f], i1 = g.idxOffs[f + 1];
+        if (p0 < 0 || p1 < p0 || p1 > g.payTotal || p1 - p0 >= 0x80000000LL) { refuse(who, "file %d is bytes %lld .. %lld of a payload buffer of %lld", f, p0, p1, g.payTotal); return 1; }
+        if (i0 < 0 || i1 < i0 || i1 > g.idxTotal) { refuse(who, "file %d has index entries %lld .. %lld of %lld", f, i0, i1, g.idxTotal); return 1; }
+    }
+    return 0;
+}
+// row i names file f: refused outside the corpus, else *nI = the file's blocks as the walk reads the count (ulcx_row_blocks)
+static int host_row_file(const char *who, const UlcxCorpus &g, int i, int f, long long *nI) {
+    if (f < 0 || f >= g.nFiles) { refuse(who, "row %d names file %d of %d", i, f, g.nFiles); return 1; }
+    *nI = ulcx_row_blocks(g.indexBlocks[f], g.ragged ? g.idxOffs[f + 1] - g.idxOffs[f] : g.indexStride);
+    return 0;
+}
+// nRows payloads and their sizes of a host-pointer call, into buffers of the call's own (payload_up with a row count of its own)
+static int payload_rows_up(DevTmp &t, int nRows, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes, uint8_t **dp, int32_t **dn) {
+    const size_t bytes = (size_t)nRows * (size_t)payloadStride;
+    CKR(t.get(dp, bytes)); CKR(t.get(dn, sizeof(int32_t) * (size_t)nRows));
+    CKR(hipMemcpy(*dp, h_payload, bytes, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(*dn, h_payloadBytes, sizeof(int32_t) * (size_t)nRows, hipMemcpyHostToDevice));
+    return ULCX_OK;
+}
+// the same for a ragged corpus: its buffer and its two tables (*d: h with these three on the device)
+static int ragged_up(DevTmp &t, const UlcxCorpus &h, UlcxCorpus *d) {
+    const size_t tb = sizeof(int64_t) * ((size_t)h.nFiles + 1);
+    uint8_t *dp = nullptr; int64_t *po = nullptr, *io = nullptr;
+    CKR(t.get(&dp, (size_t)h.payTotal)); CKR(t.get(&po, tb)); CKR(t.get(&io, tb));
+    if (h.payTotal) CKR(hipMemcpy(dp, h.pay, (size_t)h.payTotal, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(po, h.payOffs, tb, hipMemcpyHostToDevice));
+    CKR(hipMemcpy(io, h.idxOffs, tb, hipMemcpyHostToDevice));
+    *d = h; d->pay = dp; d->payOffs = po; d->idxOffs = io;
+    return ULCX_OK;
+}
+// a whole host corpus, either layout: the above, its index and its block counts -> *d, the same corpus on the device
+static int corpus_up(DevTmp &t, const UlcxCorpus &h, UlcxCorpus *d) {
+    uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr; ulcx_index_entry *di = nullptr;
+    *d = h;
+    const int rc = h.ragged ? ragged_up(t, h, d) : payload_rows_up(t, h.nFiles, h.pay, h.payStride, h.payBytes, &dp, &dn);
+    if (rc) return rc;
+    if (!h.ragged) { d->pay = dp; d->payBytes = dn; }
+    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)h.nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * (size_t)h.idxTotal));
+    CKR(hipMemcpy(dcnt, h.indexBlocks, sizeof(int32_t) * (size_t)h.nFiles, hipMemcpyHostToDevice));
+    if (h.idxTotal) CKR(hipMemcpy(di, h.index, sizeof(ulcx_index_entry) * (size_t)h.idxTotal, hipMemcpyHostToDevice));
+    d->indexBlocks = dcnt; d->index = di;
+    return ULCX_OK;
+}
+
 // ---- crops (include/ulc_amd.h section 3): rows of a call that each name a file of a corpus.  The range synthesis enters every
 // row from nothing, so the call needs no stream's state; what the synthesis leaves behind a row goes to the subset calls'
 // shadow state (dec_shadow) and is never scattered back.
 // the checks every crop entry makes, device or host pointers; the object comes last among them: every other refusal needs none
-// (layoutBad: NULL, or what is wrong with the scalars of the corpus's layout - strides, or a ragged corpus's totals)
-static int crops_checks(const char *who, const ulcx_decoder *e, int nFiles, bool anyNull, int n, int nBlocks, const char *layoutBad) {
-    if (anyNull) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
+// (rowNull: one of the call's pointers beside the corpus's is NULL)
+static int crops_checks(const char *who, const ulcx_decoder *e, const UlcxCorpus &g, bool rowNull, int n, int nBlocks) {
+    if (rowNull || corpus_null(g)) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
     if (n < 1) { refuse(who, "bad argument (n %d)", n); return 1; }
-    if (nFiles < 1) { refuse(who, "bad argument (nFiles %d)", nFiles); return 1; }
+    if (g.nFiles < 1) { refuse(who, "bad argument (nFiles %d)", g.nFiles); return 1; }
     if (nBlocks < 1) { refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return 1; }
-    if (layoutBad) { refuse(who, "bad argument (%s)", layoutBad); return 1; }
+    if (corpus_layout_bad(who, g)) return 1;
     if (!e) { refuse(who, "no decoder"); return 1; }
     if (n > e->B) { refuse(who, "bad argument (n %d: a call takes 1 .. nStreams = %d rows)", n, e->B); return 1; }
     if (nBlocks > e->maxK - 1) { refuse(who, "bad argument (nBlocks is 1 .. maxBlocksPerCall - 1)"); return 1; }
     return 0;
-}
-static int crops_args_bad(const char *who, const ulcx_decoder *e, int nFiles, const void *payload, long long payloadStride, const void *payloadBytes,
-                          const void *index, int indexStride, const void *indexBlocks, int n, const void *file, const void *first,
-                          int nBlocks, const void *pcm, const void *bits) {
-    char bad[96];
-    snprintf(bad, sizeof bad, "payloadStride %lld, indexStride %d", payloadStride, indexStride);
-    return crops_checks(who, e, nFiles, !payload || !payloadBytes || !index || !indexBlocks || !file || !first || !pcm || !bits, n, nBlocks,
-                        (payloadStride < 1 || indexStride < 1) ? bad : nullptr);
-}
-// a ragged corpus: the files' payloads and index rows back to back, found through two int64 offset tables of nFiles + 1 entries
-struct CropsRagged { long long payloadTotal; const int64_t *payloadOffs; long long indexTotal; const int64_t *indexOffs; };
-static int crops_ragged_args_bad(const char *who, const ulcx_decoder *e, int nFiles, const void *payload, const CropsRagged &g, const void *index,
-                                 const void *indexBlocks, int n, const void *file, const void *first, int nBlocks, const void *pcm, const void *bits) {
-    char bad[96];
-    snprintf(bad, sizeof bad, "payloadTotal %lld, indexTotal %lld", g.payloadTotal, g.indexTotal);
-    return crops_checks(who, e, nFiles, !payload || !g.payloadOffs || !index || !g.indexOffs || !indexBlocks || !file || !first || !pcm || !bits, n, nBlocks,
-                        (g.payloadTotal < 0 || g.indexTotal < 0) ? bad : nullptr);
 }
 // the rows of a sample-crop call (ulcx_decode_crops_samples_*): d_first / d_count are not given, nBlocks is ulcx_crop_blocks(nSamples)
 struct CropsSamples { const int64_t *start; const int32_t *len; int nSamples; };
@@ -1966,24 +2013,16 @@ static int spectra_flags_bad(const char *who, int flags) {
     if (flags & ~ULCX_SPECTRA_LR) { refuse(who, "bad argument (flags 0x%x: 0 or ULCX_SPECTRA_LR)", (unsigned)flags); return 1; }
     return 0;
 }
-// ragged != NULL: the ragged layout (payloadStride, d_payloadBytes and indexStride are not looked at)
 // samp != NULL: a sample-crop call - the rows come from (start, len), the output is [n][nChan][nSamples] and needs its element's alignment only
 // spec != NULL: a spectra call - d_pcm and d_pcm16 are NULL, the outputs are spec's [n][nChan][nBlocks][BlockSize] and [n][nBlocks]
-static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
-                            const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
-                            int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
-                            float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, const CropsRagged *ragged = nullptr,
-                            const CropsSamples *samp = nullptr, const CropsSpectra *spec = nullptr) {
+static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count,
+                            int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, const CropsSamples *samp = nullptr,
+                            const CropsSpectra *spec = nullptr) {
     if (spec && spectra_flags_bad(who, spec->flags)) return ULCX_ERR_ARG;
     const void *out = spec ? (spec->wc ? (const void *)spec->coef : nullptr) : d_pcm ? (const void *)d_pcm : d_pcm16;
     const void *rows = samp ? (const void *)samp->start : d_first;
-    if (ragged ? crops_ragged_args_bad(who, e, nFiles, d_payload, *ragged, d_index, d_indexBlocks, n, d_file, rows, nBlocks, out, d_bits)
-               : crops_args_bad(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, rows, nBlocks, out, d_bits))
-        return ULCX_ERR_ARG;
-    if (ragged && (misaligned(who, "d_payloadOffs", ragged->payloadOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", ragged->indexOffs, ULCX_ALIGN_OFFS)))
-        return ULCX_ERR_ARG;
-    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
-        misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_file", d_file, ULCX_ALIGN_WORD) ||
+    if (crops_checks(who, e, g, !d_file || !rows || !out || !d_bits, n, nBlocks)) return ULCX_ERR_ARG;
+    if (corpus_misaligned(who, g) || misaligned(who, "d_file", d_file, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_first", d_first, ULCX_ALIGN_WORD) || misaligned(who, "d_count", d_count, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     if (spec && (misaligned(who, "d_coef", spec->coef, ULCX_ALIGN_PCM) || misaligned(who, "d_wc", spec->wc, ULCX_ALIGN_WORD))) return ULCX_ERR_ARG;
@@ -1996,15 +2035,12 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, int nFiles, const 
     int rc = dec_shadow(e);
     if (rc) return rc;
     UlcxDecCtx c = e->ctx;
-    c.B = n; c.K = nBlocks + 1; c.slot = 0; c.in = d_payload; c.pcm = d_pcm; c.pcm16 = d_pcm16;
+    c.B = n; c.K = nBlocks + 1; c.slot = 0; c.in = g.pay; c.inBytes = g.payTotal; c.pcm = d_pcm; c.pcm16 = d_pcm16;
     c.bits = e->bitsScr; c.bitsOut = d_bits;
-    c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
-    c.inBytes = ragged ? ragged->payloadTotal : (long long)nFiles * payloadStride;
-    c.range = 1; c.rIndex = d_index; c.rIndexStride = indexStride; c.rIndexBlocks = d_indexBlocks; c.rFirst = d_first;
+    c.packed = 1; c.range = 1; c.rFirst = d_first;
     c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
     UlcxDecAux crop = {};
-    crop.nFiles = nFiles; crop.cropFile = d_file; crop.cropCount = d_count;
-    if (ragged) { crop.payOffs = ragged->payloadOffs; crop.idxOffs = ragged->indexOffs; crop.idxTotal = ragged->indexTotal; }
+    crop.corpus = g; crop.cropFile = d_file; crop.cropCount = d_count;
     if (samp) {
         crop.sampStart = samp->start; crop.sampLen = samp->len; crop.nSamples = samp->nSamples;
         crop.sampFirst = e->sampRows; crop.sampCount = e->sampRows + e->B; crop.sampSkip = e->sampRows + 2 * (size_t)e->B; crop.sampLenC = e->sampRows + 3 * (size_t)e->B;
@@ -2020,62 +2056,48 @@ extern "C" int ulcx_decode_crops_dev(ulcx_decoder *e, int nFiles, const uint8_t 
                                      const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
                                      int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
                                      float *d_pcm, int32_t *d_bits, void *hipStream) {
-    return decode_crops_any("ulcx_decode_crops_dev", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks,
+    return decode_crops_any("ulcx_decode_crops_dev", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
                             n, d_file, d_first, d_count, nBlocks, d_pcm, nullptr, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_crops_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                                            const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
                                            int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
                                            int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    return decode_crops_any("ulcx_decode_crops_dev_pcm16", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks,
+    return decode_crops_any("ulcx_decode_crops_dev_pcm16", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
                             n, d_file, d_first, d_count, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
-}
-// nRows payloads and their sizes of a host-pointer call, into buffers of the call's own (payload_up with a row count of its own)
-static int payload_rows_up(DevTmp &t, int nRows, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes, uint8_t **dp, int32_t **dn) {
-    const size_t bytes = (size_t)nRows * (size_t)payloadStride;
-    CKR(t.get(dp, bytes)); CKR(t.get(dn, sizeof(int32_t) * (size_t)nRows));
-    CKR(hipMemcpy(*dp, h_payload, bytes, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(*dn, h_payloadBytes, sizeof(int32_t) * (size_t)nRows, hipMemcpyHostToDevice));
-    return ULCX_OK;
 }
 // what a host form leaves of a spectra call beside the crop results: the window codes (hspec: the HOST outputs, flags as given)
 static int spectra_wc_down(const int32_t *d_wc, size_t NB, int32_t *h_wc) {
     CKR(hipMemcpy(h_wc, d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
-// the strided host forms: ulcx_decode_crops_host (h_pcm) and ulcx_decode_crops_spectra_host (hspec: h_pcm is its coefficients)
-static int crops_host_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
-                          const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
-                          int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
-                          float *h_pcm, int32_t *h_bits, const CropsSpectra *hspec = nullptr) {
+// the host forms, either layout: ulcx_decode_crops[_ragged]_host (h_pcm) and ulcx_decode_crops_spectra[_ragged]_host (hspec: h_pcm
+// is its coefficients)
+static int crops_host_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
+                          int nBlocks, float *h_pcm, int32_t *h_bits, const CropsSpectra *hspec = nullptr) {
     if (hspec && spectra_flags_bad(who, hspec->flags)) return ULCX_ERR_ARG;
-    if (crops_args_bad(who, e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, n, h_file, h_first, nBlocks,
-                       (hspec && !hspec->wc) ? nullptr : h_pcm, h_bits)) return ULCX_ERR_ARG;
-    // what the device forms cannot refuse
+    if (crops_checks(who, e, g, !h_file || !h_first || (hspec && !hspec->wc) || !h_pcm || !h_bits, n, nBlocks)) return ULCX_ERR_ARG;
+    // what the device forms cannot refuse: a ragged corpus's tables, then the rows
+    if (g.ragged && ragged_tables_bad(who, g)) return ULCX_ERR_ARG;
     for (int i = 0; i < n; i++) {
-        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
-        int nI = h_indexBlocks[h_file[i]];
-        nI = nI < 0 ? 0 : nI > indexStride - 1 ? indexStride - 1 : nI;                   // (as the walk reads a count)
-        if (h_first[i] < 0 || h_first[i] > nI) return refuse(who, "row %d starts at block %d of a file of %d", i, (int)h_first[i], nI);
+        long long nI;
+        if (host_row_file(who, g, i, h_file[i], &nI)) return ULCX_ERR_ARG;
+        if (h_first[i] < 0 || h_first[i] > nI) return refuse(who, "row %d starts at block %d of a file of %lld", i, (int)h_first[i], nI);
         if (h_count && h_count[i] < 0) return refuse(who, "row %d wants %d blocks", i, (int)h_count[i]);
     }
     CKR(hipSetDevice(e->device));
-    const size_t NB = (size_t)n * nBlocks, nEnt = (size_t)nFiles * (size_t)indexStride;
-    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr, *dfile = nullptr, *df = nullptr, *dwant = nullptr, *dbits = nullptr;
-    ulcx_index_entry *di = nullptr; float *dpcm = nullptr;
-    int rc = payload_rows_up(t, nFiles, h_payload, payloadStride, h_payloadBytes, &dp, &dn);
+    const size_t NB = (size_t)n * nBlocks;
+    DevTmp t; UlcxCorpus d; int32_t *dfile = nullptr, *df = nullptr, *dwant = nullptr, *dbits = nullptr; float *dpcm = nullptr;
+    int rc = corpus_up(t, g, &d);
     if (rc) return rc;
-    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&dfile, sizeof(int32_t) * n)); CKR(t.get(&df, sizeof(int32_t) * n));
-    CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt)); CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
-    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
+    CKR(t.get(&dfile, sizeof(int32_t) * n)); CKR(t.get(&df, sizeof(int32_t) * n));
+    CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
     CKR(hipMemcpy(dfile, h_file, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     CKR(hipMemcpy(df, h_first, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
     if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
     CropsSpectra ds = {};
     if (hspec) { ds.coef = dpcm; ds.flags = hspec->flags; CKR(t.get(&ds.wc, sizeof(int32_t) * NB)); }
-    rc = decode_crops_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, n, dfile, df, dwant, nBlocks, hspec ? nullptr : dpcm, nullptr, dbits, nullptr,
-                          nullptr, nullptr, hspec ? &ds : nullptr);
+    rc = decode_crops_any(who, e, d, n, dfile, df, dwant, nBlocks, hspec ? nullptr : dpcm, nullptr, dbits, nullptr, nullptr, hspec ? &ds : nullptr);
     if (!rc) rc = dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
     return (rc || !hspec) ? rc : spectra_wc_down(ds.wc, NB, hspec->wc);
 }
@@ -2083,7 +2105,7 @@ extern "C" int ulcx_decode_crops_host(ulcx_decoder *e, int nFiles, const uint8_t
                                       const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
                                       int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
                                       float *h_pcm, int32_t *h_bits) {
-    return crops_host_any("ulcx_decode_crops_host", e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks,
+    return crops_host_any("ulcx_decode_crops_host", e, ulcx_corpus_strided(nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks),
                           n, h_file, h_first, h_count, nBlocks, h_pcm, h_bits);
 }
 // ulcx_index_packed_* with a row count of its own: k_dindex over nRows (geometry and tables are all that is read of the object)
@@ -2120,87 +2142,27 @@ extern "C" int ulcx_index_packed_rows_host(ulcx_decoder *e, int nRows, const uin
     return ULCX_OK;
 }
 
-// ---- crops of a ragged corpus (include/ulc_amd.h section 3): the crop family's body with the files found through offset tables.
+// ---- crops of a ragged corpus (include/ulc_amd.h section 3): the crop family's bodies on a corpus whose files are found through offset tables.
 extern "C" int ulcx_decode_crops_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
                                             const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
                                             int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
                                             float *d_pcm, int32_t *d_bits, void *hipStream) {
-    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
-    return decode_crops_any("ulcx_decode_crops_ragged_dev", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, d_first, d_count, nBlocks,
-                            d_pcm, nullptr, d_bits, hipStream, &g);
+    return decode_crops_any("ulcx_decode_crops_ragged_dev", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                            n, d_file, d_first, d_count, nBlocks, d_pcm, nullptr, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_crops_ragged_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
                                                   const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
                                                   int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
                                                   int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
-    return decode_crops_any("ulcx_decode_crops_ragged_dev_pcm16", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, d_first, d_count, nBlocks,
-                            nullptr, d_pcm16, d_bits, hipStream, &g);
-}
-// what a host form can refuse of the two tables: offsets that are negative, fall or leave their buffer, a file of 2^31 bytes or more
-static int ragged_tables_bad(const char *who, int nFiles, const CropsRagged &g) {
-    for (int f = 0; f < nFiles; f++) {
-        const long long p0 = g.payloadOffs[f], p1 = g.payloadOffs[f + 1], i0 = g.indexOffs[f], i1 = g.indexOffs[f + 1];
-        if (p0 < 0 || p1 < p0 || p1 > g.payloadTotal || p1 - p0 >= 0x80000000LL) { refuse(who, "file %d is bytes %lld .. %lld of a payload buffer of %lld", f, p0, p1, g.payloadTotal); return 1; }
-        if (i0 < 0 || i1 < i0 || i1 > g.indexTotal) { refuse(who, "file %d has index entries %lld .. %lld of %lld", f, i0, i1, g.indexTotal); return 1; }
-    }
-    return 0;
-}
-// the buffer and the two tables of a ragged host-pointer call, into buffers of the call's own (as payload_rows_up)
-static int ragged_up(DevTmp &t, int nFiles, const uint8_t *h_payload, const CropsRagged &g, uint8_t **dp, CropsRagged *dg) {
-    const size_t tb = sizeof(int64_t) * ((size_t)nFiles + 1);
-    int64_t *po = nullptr, *io = nullptr;
-    CKR(t.get(dp, (size_t)g.payloadTotal)); CKR(t.get(&po, tb)); CKR(t.get(&io, tb));
-    if (g.payloadTotal) CKR(hipMemcpy(*dp, h_payload, (size_t)g.payloadTotal, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(po, g.payloadOffs, tb, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(io, g.indexOffs, tb, hipMemcpyHostToDevice));
-    *dg = CropsRagged{ g.payloadTotal, po, g.indexTotal, io };
-    return ULCX_OK;
-}
-// the ragged host forms: ulcx_decode_crops_ragged_host and ulcx_decode_crops_spectra_ragged_host (hspec, as crops_host_any)
-static int crops_ragged_host_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
-                                 const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
-                                 int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
-                                 float *h_pcm, int32_t *h_bits, const CropsSpectra *hspec = nullptr) {
-    if (hspec && spectra_flags_bad(who, hspec->flags)) return ULCX_ERR_ARG;
-    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
-    if (crops_ragged_args_bad(who, e, nFiles, h_payload, g, h_index, h_indexBlocks, n, h_file, h_first, nBlocks, (hspec && !hspec->wc) ? nullptr : h_pcm, h_bits)) return ULCX_ERR_ARG;
-    // what the device forms cannot refuse: the tables, then the rows as the strided host form
-    if (ragged_tables_bad(who, nFiles, g)) return ULCX_ERR_ARG;
-    for (int i = 0; i < n; i++) {
-        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
-        const long long cap = h_indexOffs[h_file[i] + 1] - h_indexOffs[h_file[i]];
-        long long nI = h_indexBlocks[h_file[i]];
-        nI = nI < 0 ? 0 : nI > cap - 1 ? cap - 1 : nI;
-        if (h_first[i] < 0 || h_first[i] > nI) return refuse(who, "row %d starts at block %d of a file of %lld", i, (int)h_first[i], nI);
-        if (h_count && h_count[i] < 0) return refuse(who, "row %d wants %d blocks", i, (int)h_count[i]);
-    }
-    CKR(hipSetDevice(e->device));
-    const size_t NB = (size_t)n * nBlocks;
-    DevTmp t; uint8_t *dp = nullptr; int32_t *dcnt = nullptr, *dfile = nullptr, *df = nullptr, *dwant = nullptr, *dbits = nullptr;
-    ulcx_index_entry *di = nullptr; float *dpcm = nullptr; CropsRagged dg = {};
-    int rc = ragged_up(t, nFiles, h_payload, g, &dp, &dg);
-    if (rc) return rc;
-    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&dfile, sizeof(int32_t) * n)); CKR(t.get(&df, sizeof(int32_t) * n));
-    CKR(t.get(&di, sizeof(ulcx_index_entry) * (size_t)indexTotal)); CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
-    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(dfile, h_file, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(df, h_first, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    if (indexTotal) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyHostToDevice));
-    if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
-    CropsSpectra ds = {};
-    if (hspec) { ds.coef = dpcm; ds.flags = hspec->flags; CKR(t.get(&ds.wc, sizeof(int32_t) * NB)); }
-    rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, dfile, df, dwant, nBlocks, hspec ? nullptr : dpcm, nullptr, dbits, nullptr, &dg,
-                          nullptr, hspec ? &ds : nullptr);
-    if (!rc) rc = dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
-    return (rc || !hspec) ? rc : spectra_wc_down(ds.wc, NB, hspec->wc);
+    return decode_crops_any("ulcx_decode_crops_ragged_dev_pcm16", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                            n, d_file, d_first, d_count, nBlocks, nullptr, d_pcm16, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_crops_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
                                              const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
                                              int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
                                              float *h_pcm, int32_t *h_bits) {
-    return crops_ragged_host_any("ulcx_decode_crops_ragged_host", e, nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks,
-                                 n, h_file, h_first, h_count, nBlocks, h_pcm, h_bits);
+    return crops_host_any("ulcx_decode_crops_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
+                          n, h_file, h_first, h_count, nBlocks, h_pcm, h_bits);
 }
 // ---- spectra (include/ulc_amd.h section 3): the crop families' bodies, ending in the dequantised coefficients instead of samples.
 extern "C" int ulcx_window_subblocks(int BlockSize, int wc, int sizes[4]) {
@@ -2222,24 +2184,23 @@ extern "C" int ulcx_decode_crops_spectra_dev(ulcx_decoder *e, int nFiles, const 
                                              int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks, int flags,
                                              float *d_coef, int32_t *d_wc, int32_t *d_bits, void *hipStream) {
     const CropsSpectra sp = { d_coef, d_wc, flags };
-    return decode_crops_any("ulcx_decode_crops_spectra_dev", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks,
-                            n, d_file, d_first, d_count, nBlocks, nullptr, nullptr, d_bits, hipStream, nullptr, nullptr, &sp);
+    return decode_crops_any("ulcx_decode_crops_spectra_dev", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                            n, d_file, d_first, d_count, nBlocks, nullptr, nullptr, d_bits, hipStream, nullptr, &sp);
 }
 extern "C" int ulcx_decode_crops_spectra_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
                                                     const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
                                                     int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks, int flags,
                                                     float *d_coef, int32_t *d_wc, int32_t *d_bits, void *hipStream) {
-    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
     const CropsSpectra sp = { d_coef, d_wc, flags };
-    return decode_crops_any("ulcx_decode_crops_spectra_ragged_dev", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, d_first, d_count, nBlocks,
-                            nullptr, nullptr, d_bits, hipStream, &g, nullptr, &sp);
+    return decode_crops_any("ulcx_decode_crops_spectra_ragged_dev", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                            n, d_file, d_first, d_count, nBlocks, nullptr, nullptr, d_bits, hipStream, nullptr, &sp);
 }
 extern "C" int ulcx_decode_crops_spectra_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
                                               const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
                                               int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks, int flags,
                                               float *h_coef, int32_t *h_wc, int32_t *h_bits) {
     const CropsSpectra sp = { h_coef, h_wc, flags };
-    return crops_host_any("ulcx_decode_crops_spectra_host", e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks,
+    return crops_host_any("ulcx_decode_crops_spectra_host", e, ulcx_corpus_strided(nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks),
                           n, h_file, h_first, h_count, nBlocks, h_coef, h_bits, &sp);
 }
 extern "C" int ulcx_decode_crops_spectra_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
@@ -2247,8 +2208,8 @@ extern "C" int ulcx_decode_crops_spectra_ragged_host(ulcx_decoder *e, int nFiles
                                                      int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks, int flags,
                                                      float *h_coef, int32_t *h_wc, int32_t *h_bits) {
     const CropsSpectra sp = { h_coef, h_wc, flags };
-    return crops_ragged_host_any("ulcx_decode_crops_spectra_ragged_host", e, nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs,
-                                 h_indexBlocks, n, h_file, h_first, h_count, nBlocks, h_coef, h_bits, &sp);
+    return crops_host_any("ulcx_decode_crops_spectra_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
+                          n, h_file, h_first, h_count, nBlocks, h_coef, h_bits, &sp);
 }
 // ---- sample crops (include/ulc_amd.h section 3): the crop families' bodies with rows given in samples and the output channels-first.
 extern "C" int ulcx_crop_blocks(int BlockSize, int nSamples) {
@@ -2266,49 +2227,40 @@ static int samples_blocks(const char *who, const ulcx_decoder *e, int nSamples) 
     if (nB > e->maxK - 1) { refuse(who, "bad argument (nSamples %d touches up to %d blocks; a row has maxBlocksPerCall - 1 = %d)", nSamples, nB, e->maxK - 1); return 0; }
     return nB;
 }
+static int crops_samples_dev_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len,
+                                 int nSamples, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    const CropsSamples sm = { d_start, d_len, nSamples };
+    return decode_crops_any(who, e, g, n, d_file, nullptr, nullptr, nB, d_pcm, d_pcm16, d_bits, hipStream, &sm);
+}
 extern "C" int ulcx_decode_crops_samples_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                                              const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
                                              int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
                                              float *d_pcm, int32_t *d_bits, void *hipStream) {
-    const char *who = "ulcx_decode_crops_samples_dev";
-    const int nB = samples_blocks(who, e, nSamples);
-    if (!nB) return ULCX_ERR_ARG;
-    const CropsSamples sm = { d_start, d_len, nSamples };
-    return decode_crops_any(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, nullptr, nullptr, nB,
-                            d_pcm, nullptr, d_bits, hipStream, nullptr, &sm);
+    return crops_samples_dev_any("ulcx_decode_crops_samples_dev", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, d_pcm, nullptr, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_crops_samples_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
                                                    const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
                                                    int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
                                                    int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    const char *who = "ulcx_decode_crops_samples_dev_pcm16";
-    const int nB = samples_blocks(who, e, nSamples);
-    if (!nB) return ULCX_ERR_ARG;
-    const CropsSamples sm = { d_start, d_len, nSamples };
-    return decode_crops_any(who, e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, n, d_file, nullptr, nullptr, nB,
-                            nullptr, d_pcm16, d_bits, hipStream, nullptr, &sm);
+    return crops_samples_dev_any("ulcx_decode_crops_samples_dev_pcm16", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, nullptr, d_pcm16, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_crops_samples_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
                                                     const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
                                                     int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
                                                     float *d_pcm, int32_t *d_bits, void *hipStream) {
-    const char *who = "ulcx_decode_crops_samples_ragged_dev";
-    const int nB = samples_blocks(who, e, nSamples);
-    if (!nB) return ULCX_ERR_ARG;
-    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
-    const CropsSamples sm = { d_start, d_len, nSamples };
-    return decode_crops_any(who, e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, nullptr, nullptr, nB, d_pcm, nullptr, d_bits, hipStream, &g, &sm);
+    return crops_samples_dev_any("ulcx_decode_crops_samples_ragged_dev", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, d_pcm, nullptr, d_bits, hipStream);
 }
 extern "C" int ulcx_decode_crops_samples_ragged_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
                                                           const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
                                                           int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples,
                                                           int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    const char *who = "ulcx_decode_crops_samples_ragged_dev_pcm16";
-    const int nB = samples_blocks(who, e, nSamples);
-    if (!nB) return ULCX_ERR_ARG;
-    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
-    const CropsSamples sm = { d_start, d_len, nSamples };
-    return decode_crops_any(who, e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, n, d_file, nullptr, nullptr, nB, nullptr, d_pcm16, d_bits, hipStream, &g, &sm);
+    return crops_samples_dev_any("ulcx_decode_crops_samples_ragged_dev_pcm16", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, nullptr, d_pcm16, d_bits, hipStream);
 }
 // what the device forms cannot refuse of row i, which names a file of nI indexed blocks
 static int sample_row_bad(const char *who, int i, int BS, long long nI, long long start, const int32_t *h_len) {
@@ -2332,61 +2284,40 @@ static int sample_results_down(const ulcx_decoder *e, const SampleStage &g, int 
     CKR(hipMemcpy(h_bits, g.bits, sizeof(int32_t) * (size_t)n * nB, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
+// the host forms, either layout
+static int crops_samples_host_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len,
+                                  int nSamples, float *h_pcm, int32_t *h_bits) {
+    const int nB = samples_blocks(who, e, nSamples);
+    if (!nB) return ULCX_ERR_ARG;
+    if (crops_checks(who, e, g, !h_file || !h_start || !h_pcm || !h_bits, n, nB)) return ULCX_ERR_ARG;
+    if (g.ragged && ragged_tables_bad(who, g)) return ULCX_ERR_ARG;
+    for (int i = 0; i < n; i++) {
+        long long nI;
+        if (host_row_file(who, g, i, h_file[i], &nI)) return ULCX_ERR_ARG;
+        if (sample_row_bad(who, i, e->BS, nI < 0 ? 0 : nI, h_start[i], h_len)) return ULCX_ERR_ARG;
+    }
+    CKR(hipSetDevice(e->device));
+    DevTmp t; UlcxCorpus d; SampleStage sg;
+    int rc = corpus_up(t, g, &d);
+    if (!rc) rc = sample_rows_up(t, e, n, nB, nSamples, h_file, h_start, h_len, &sg);
+    if (rc) return rc;
+    const CropsSamples sm = { sg.start, sg.len, nSamples };
+    rc = decode_crops_any(who, e, d, n, sg.file, nullptr, nullptr, nB, sg.pcm, nullptr, sg.bits, nullptr, &sm);
+    return rc ? rc : sample_results_down(e, sg, n, nB, nSamples, h_pcm, h_bits);
+}
 extern "C" int ulcx_decode_crops_samples_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
                                               const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
                                               int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples,
                                               float *h_pcm, int32_t *h_bits) {
-    const char *who = "ulcx_decode_crops_samples_host";
-    const int nB = samples_blocks(who, e, nSamples);
-    if (!nB) return ULCX_ERR_ARG;
-    if (crops_args_bad(who, e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, n, h_file, h_start, nB, h_pcm, h_bits)) return ULCX_ERR_ARG;
-    for (int i = 0; i < n; i++) {
-        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
-        int nI = h_indexBlocks[h_file[i]];
-        nI = nI < 0 ? 0 : nI > indexStride - 1 ? indexStride - 1 : nI;                   // (as the walk reads a count)
-        if (sample_row_bad(who, i, e->BS, nI, h_start[i], h_len)) return ULCX_ERR_ARG;
-    }
-    CKR(hipSetDevice(e->device));
-    const size_t nEnt = (size_t)nFiles * (size_t)indexStride;
-    DevTmp t; uint8_t *dp = nullptr; int32_t *dn = nullptr, *dcnt = nullptr; ulcx_index_entry *di = nullptr; SampleStage g;
-    int rc = payload_rows_up(t, nFiles, h_payload, payloadStride, h_payloadBytes, &dp, &dn);
-    if (!rc) rc = sample_rows_up(t, e, n, nB, nSamples, h_file, h_start, h_len, &g);
-    if (rc) return rc;
-    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
-    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
-    CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
-    const CropsSamples sm = { g.start, g.len, nSamples };
-    rc = decode_crops_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, n, g.file, nullptr, nullptr, nB, g.pcm, nullptr, g.bits, nullptr, nullptr, &sm);
-    return rc ? rc : sample_results_down(e, g, n, nB, nSamples, h_pcm, h_bits);
+    return crops_samples_host_any("ulcx_decode_crops_samples_host", e, ulcx_corpus_strided(nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks),
+                                  n, h_file, h_start, h_len, nSamples, h_pcm, h_bits);
 }
 extern "C" int ulcx_decode_crops_samples_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
                                                      const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
                                                      int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples,
                                                      float *h_pcm, int32_t *h_bits) {
-    const char *who = "ulcx_decode_crops_samples_ragged_host";
-    const int nB = samples_blocks(who, e, nSamples);
-    if (!nB) return ULCX_ERR_ARG;
-    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
-    if (crops_ragged_args_bad(who, e, nFiles, h_payload, g, h_index, h_indexBlocks, n, h_file, h_start, nB, h_pcm, h_bits)) return ULCX_ERR_ARG;
-    if (ragged_tables_bad(who, nFiles, g)) return ULCX_ERR_ARG;
-    for (int i = 0; i < n; i++) {
-        if (h_file[i] < 0 || h_file[i] >= nFiles) return refuse(who, "row %d names file %d of %d", i, (int)h_file[i], nFiles);
-        const long long cap = h_indexOffs[h_file[i] + 1] - h_indexOffs[h_file[i]];
-        long long nI = h_indexBlocks[h_file[i]];
-        nI = nI < 0 ? 0 : nI > cap - 1 ? cap - 1 : nI;
-        if (sample_row_bad(who, i, e->BS, nI < 0 ? 0 : nI, h_start[i], h_len)) return ULCX_ERR_ARG;
-    }
-    CKR(hipSetDevice(e->device));
-    DevTmp t; uint8_t *dp = nullptr; int32_t *dcnt = nullptr; ulcx_index_entry *di = nullptr; CropsRagged dg = {}; SampleStage sg;
-    int rc = ragged_up(t, nFiles, h_payload, g, &dp, &dg);
-    if (!rc) rc = sample_rows_up(t, e, n, nB, nSamples, h_file, h_start, h_len, &sg);
-    if (rc) return rc;
-    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * (size_t)indexTotal));
-    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
-    if (indexTotal) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyHostToDevice));
-    const CropsSamples sm = { sg.start, sg.len, nSamples };
-    rc = decode_crops_any(who, e, nFiles, dp, 0, nullptr, di, 0, dcnt, n, sg.file, nullptr, nullptr, nB, sg.pcm, nullptr, sg.bits, nullptr, &dg, &sm);
-    return rc ? rc : sample_results_down(e, sg, n, nB, nSamples, h_pcm, h_bits);
+    return crops_samples_host_any("ulcx_decode_crops_samples_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
+                                  n, h_file, h_start, h_len, nSamples, h_pcm, h_bits);
 }
 // ---- synthesis from spectra (include/ulc_amd.h section 3): the decoder's inverse transform on caller-held planes.  The range
 // synthesis of a crop call without any walk in front: the call runs on the shadow state as the crop calls do (dec_shadow; nothing
@@ -2454,39 +2385,39 @@ extern "C" int ulcx_synth_spectra_host(ulcx_decoder *e, int n, int nBlocks, int 
     const int rc = synth_spectra_any(who, e, n, nBlocks, flags, dcoef, dwc, dpcm, nullptr, dlive, nullptr);
     return rc ? rc : dec_results_down(e, dpcm, dlive, NB, h_pcm, h_live);
 }
-// ulcx_index_packed_rows_* for files back to back: k_dindex_ragged over nFiles (geometry and tables are all that is read of the object)
-static int index_ragged_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, const CropsRagged &g, ulcx_index_entry *d_index,
-                            int32_t *d_nBlocks, void *hipStream) {
-    if (!d_payload || !g.payloadOffs || !d_index || !g.indexOffs || !d_nBlocks || nFiles < 1 || g.payloadTotal < 0 || g.indexTotal < 0) return refuse(who, "bad argument");
+// ulcx_index_packed_rows_* for files back to back: k_dindex_ragged over the files of g, whose index is the output and which has no
+// block counts yet (geometry and tables are all that is read of the object)
+static int index_ragged_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, ulcx_index_entry *d_index, int32_t *d_nBlocks, void *hipStream) {
+    if (!g.pay || !g.payOffs || !d_index || !g.idxOffs || !d_nBlocks || g.nFiles < 1 || g.payTotal < 0 || g.idxTotal < 0) return refuse(who, "bad argument");
     if (!e) return refuse(who, "no decoder");
-    if (misaligned(who, "d_payloadOffs", g.payloadOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", g.indexOffs, ULCX_ALIGN_OFFS) ||
+    if (misaligned(who, "d_payloadOffs", g.payOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", g.idxOffs, ULCX_ALIGN_OFFS) ||
         misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) || misaligned(who, "d_nBlocks", d_nBlocks, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
-    c.B = nFiles; c.in = d_payload; c.packed = 1; c.payStride = 0; c.payBytes = nullptr;
-    c.inBytes = g.payloadTotal;
-    return ulcx_index_ragged_launch(c, g.payloadOffs, g.indexOffs, g.indexTotal, d_index, d_nBlocks, (hipStream_t)hipStream);
+    c.B = g.nFiles; c.in = g.pay; c.packed = 1; c.payStride = 0; c.payBytes = nullptr;
+    c.inBytes = g.payTotal;
+    return ulcx_index_ragged_launch(c, g.payOffs, g.idxOffs, g.idxTotal, d_index, d_nBlocks, (hipStream_t)hipStream);
 }
 extern "C" int ulcx_index_packed_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
                                             ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, int32_t *d_nBlocks, void *hipStream) {
-    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
-    return index_ragged_any("ulcx_index_packed_ragged_dev", e, nFiles, d_payload, g, d_index, d_nBlocks, hipStream);
+    return index_ragged_any("ulcx_index_packed_ragged_dev", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, nullptr),
+                            d_index, d_nBlocks, hipStream);
 }
 // (h_index is read as well as written: the entries between and behind the rows go back as they came)
 extern "C" int ulcx_index_packed_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
                                              ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, int32_t *h_nBlocks) {
     const char *who = "ulcx_index_packed_ragged_host";
-    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
+    const UlcxCorpus g = ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, nullptr);
     if (!h_payload || !h_payloadOffs || !h_index || !h_indexOffs || !h_nBlocks || nFiles < 1 || payloadTotal < 0 || indexTotal < 0) return refuse(who, "bad argument");
     if (!e) return refuse(who, "no decoder");
-    if (ragged_tables_bad(who, nFiles, g)) return ULCX_ERR_ARG;
+    if (ragged_tables_bad(who, g)) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
-    DevTmp t; uint8_t *dp = nullptr; int32_t *dcnt = nullptr; ulcx_index_entry *di = nullptr; CropsRagged dg = {};
-    int rc = ragged_up(t, nFiles, h_payload, g, &dp, &dg);
+    DevTmp t; int32_t *dcnt = nullptr; ulcx_index_entry *di = nullptr; UlcxCorpus d;
+    int rc = ragged_up(t, g, &d);
     if (rc) return rc;
     CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * (size_t)indexTotal));
     if (indexTotal) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyHostToDevice));
-    if ((rc = index_ragged_any(who, e, nFiles, dp, dg, di, dcnt, nullptr))) return rc;
+    if ((rc = index_ragged_any(who, e, d, di, dcnt, nullptr))) return rc;
     CKR(hipDeviceSynchronize());
     if (indexTotal) CKR(hipMemcpy(h_index, di, sizeof(ulcx_index_entry) * (size_t)indexTotal, hipMemcpyDeviceToHost));
     CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * (size_t)nFiles, hipMemcpyDeviceToHost));
@@ -2541,48 +2472,43 @@ extern "C" int ulcx_index_slots_host(ulcx_decoder *e, int nRows, const uint8_t *
     CKR(hipMemcpy(h_nBlocks, dcnt, sizeof(int32_t) * nRows, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
-// ---- corpus splice (include/ulc_amd.h section 2): splice_any is the body of the two _dev forms (ragged != NULL: payloadStride,
-// d_payloadBytes and indexStride are not looked at), splice_host_any of the two host forms.  The decoder comes last among the
-// checks, as in index_rows_any.
+// ---- corpus splice (include/ulc_amd.h section 2): splice_any is the body of the two _dev forms, splice_host_any of the two host
+// forms.  The decoder comes last among the checks, as in index_rows_any.
 struct SpliceOut { uint8_t *payload; long long payloadStride; int32_t *payloadBytes, *maxBlock; ulcx_index_entry *index; int indexStride; int32_t *indexBlocks, *segStart; };
 static bool ranges_meet(const void *a, unsigned long long na, const void *b, unsigned long long nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return na && nb && x < y + nb && y < x + na;
 }
-static int splice_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
-                      const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks, const CropsRagged *ragged,
-                      int nOut, const int32_t *d_segOffs, const ulcx_segment *d_seg, int nSeg, const SpliceOut &o, void *hipStream) {
-    if (!d_payload || !d_index || !d_indexBlocks || !d_segOffs || !d_seg || !o.payload || !o.payloadBytes || !o.index || !o.indexBlocks || !o.segStart ||
-        (ragged ? (!ragged->payloadOffs || !ragged->indexOffs) : !d_payloadBytes)) return refuse(who, "bad argument (a NULL pointer)");
-    if (nFiles < 1 || nOut < 1 || nSeg < 1) return refuse(who, "bad argument (nFiles %d, nOut %d, nSeg %d)", nFiles, nOut, nSeg);
-    if (ragged ? (ragged->payloadTotal < 0 || ragged->indexTotal < 0) : (payloadStride < 1 || indexStride < 1))
-        return ragged ? refuse(who, "bad argument (payloadTotal %lld, indexTotal %lld)", ragged->payloadTotal, ragged->indexTotal)
-                      : refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride);
-    if (o.payloadStride < 1 || o.indexStride < 2) return refuse(who, "bad argument (outPayloadStride %lld, outIndexStride %d: at least 1 and 2)", o.payloadStride, o.indexStride);
-    if (ragged && (misaligned(who, "d_payloadOffs", ragged->payloadOffs, ULCX_ALIGN_OFFS) || misaligned(who, "d_indexOffs", ragged->indexOffs, ULCX_ALIGN_OFFS)))
-        return ULCX_ERR_ARG;
-    if (misaligned(who, "d_payloadBytes", d_payloadBytes, ULCX_ALIGN_WORD) || misaligned(who, "d_index", d_index, ULCX_ALIGN_WORD) ||
-        misaligned(who, "d_indexBlocks", d_indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_segOffs", d_segOffs, ULCX_ALIGN_WORD) ||
+// the pointers and scalars both bodies check first, device or host pointers
+static int splice_args_bad(const char *who, const UlcxCorpus &g, int nOut, const int32_t *segOffs, const ulcx_segment *seg, int nSeg, const SpliceOut &o) {
+    if (corpus_null(g) || !segOffs || !seg || !o.payload || !o.payloadBytes || !o.index || !o.indexBlocks || !o.segStart) { refuse(who, "bad argument (a NULL pointer)"); return 1; }
+    if (g.nFiles < 1 || nOut < 1 || nSeg < 1) { refuse(who, "bad argument (nFiles %d, nOut %d, nSeg %d)", g.nFiles, nOut, nSeg); return 1; }
+    if (corpus_layout_bad(who, g)) return 1;
+    if (o.payloadStride < 1 || o.indexStride < 2) { refuse(who, "bad argument (outPayloadStride %lld, outIndexStride %d: at least 1 and 2)", o.payloadStride, o.indexStride); return 1; }
+    return 0;
+}
+static int splice_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int nOut, const int32_t *d_segOffs, const ulcx_segment *d_seg, int nSeg,
+                      const SpliceOut &o, void *hipStream) {
+    if (splice_args_bad(who, g, nOut, d_segOffs, d_seg, nSeg, o)) return ULCX_ERR_ARG;
+    if (corpus_misaligned(who, g) || misaligned(who, "d_segOffs", d_segOffs, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_seg", d_seg, ULCX_ALIGN_WORD) || misaligned(who, "d_outPayloadBytes", o.payloadBytes, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_outMaxBlock", o.maxBlock, ULCX_ALIGN_WORD) || misaligned(who, "d_outIndex", o.index, ULCX_ALIGN_WORD) ||
         misaligned(who, "d_outIndexBlocks", o.indexBlocks, ULCX_ALIGN_WORD) || misaligned(who, "d_segStart", o.segStart, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     // (one lane per output block and per 16-byte line, each in a grid of 2^31 - 1 workgroups at the most; a payload range within 2^62)
     if ((long long)nOut * o.indexStride > (0x7FFFFFFFLL << 6) || o.payloadStride > (1LL << 40) || (long long)nOut * ((o.payloadStride + 30) / 16) > (0x7FFFFFFFLL << 8))
         return refuse(who, "%d output files of %d entries and %lld bytes are more than one call takes", nOut, o.indexStride, o.payloadStride);
-    if (!ragged && payloadStride > (1LL << 40)) return refuse(who, "bad argument (payloadStride %lld)", payloadStride);
-    const unsigned long long srcPay = ragged ? (unsigned long long)ragged->payloadTotal : (unsigned long long)nFiles * (unsigned long long)payloadStride;
-    const unsigned long long srcIdx = sizeof(ulcx_index_entry) * (ragged ? (unsigned long long)ragged->indexTotal : (unsigned long long)nFiles * (unsigned long long)indexStride);
+    if (!g.ragged && g.payStride > (1LL << 40)) return refuse(who, "bad argument (payloadStride %lld)", g.payStride);
+    const unsigned long long srcPay = (unsigned long long)g.payTotal, srcIdx = sizeof(ulcx_index_entry) * (unsigned long long)g.idxTotal;
     const unsigned long long outPay = (unsigned long long)nOut * (unsigned long long)o.payloadStride, outIdx = sizeof(ulcx_index_entry) * (unsigned long long)nOut * (unsigned long long)o.indexStride;
-    if (ranges_meet(o.payload, outPay, d_payload, srcPay) || ranges_meet(o.payload, outPay, d_index, srcIdx) ||
-        ranges_meet(o.index, outIdx, d_payload, srcPay) || ranges_meet(o.index, outIdx, d_index, srcIdx))
+    if (ranges_meet(o.payload, outPay, g.pay, srcPay) || ranges_meet(o.payload, outPay, g.index, srcIdx) ||
+        ranges_meet(o.index, outIdx, g.pay, srcPay) || ranges_meet(o.index, outIdx, g.index, srcIdx))
         return refuse(who, "the output payload or index overlaps the source's");
     if (!e) return refuse(who, "no decoder");
     CKR(hipSetDevice(e->device));
     UlcxDecCtx c = e->ctx;
-    c.in = d_payload; c.inBytes = (long long)srcPay; c.packed = 1;
+    c.in = g.pay; c.inBytes = g.payTotal; c.packed = 1;
     UlcxSpliceArgs a = {};
-    a.nFiles = nFiles; a.payStride = payloadStride; a.payBytes = d_payloadBytes; a.index = d_index; a.indexStride = indexStride; a.indexBlocks = d_indexBlocks;
-    if (ragged) { a.payOffs = ragged->payloadOffs; a.idxOffs = ragged->indexOffs; a.idxTotal = ragged->indexTotal; }
+    a.src = g;
     a.nOut = nOut; a.nSeg = nSeg; a.segOffs = d_segOffs; a.seg = d_seg; a.segStart = o.segStart;
     a.outPay = o.payload; a.outPayStride = o.payloadStride; a.outPayBytes = o.payloadBytes; a.outMaxBlock = o.maxBlock;
     a.outIndex = o.index; a.outIndexStride = o.indexStride; a.outIndexBlocks = o.indexBlocks;
@@ -2594,7 +2520,7 @@ extern "C" int ulcx_corpus_splice_dev(ulcx_decoder *e, int nFiles, const uint8_t
                                       uint8_t *d_outPayload, long long outPayloadStride, int32_t *d_outPayloadBytes, int32_t *d_outMaxBlock,
                                       ulcx_index_entry *d_outIndex, int outIndexStride, int32_t *d_outIndexBlocks, int32_t *d_segStart, void *hipStream) {
     const SpliceOut o = { d_outPayload, outPayloadStride, d_outPayloadBytes, d_outMaxBlock, d_outIndex, outIndexStride, d_outIndexBlocks, d_segStart };
-    return splice_any("ulcx_corpus_splice_dev", e, nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks, nullptr,
+    return splice_any("ulcx_corpus_splice_dev", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
                       nOut, d_segOffs, d_seg, nSeg, o, hipStream);
 }
 extern "C" int ulcx_corpus_splice_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
@@ -2602,51 +2528,41 @@ extern "C" int ulcx_corpus_splice_ragged_dev(ulcx_decoder *e, int nFiles, const 
                                              int nOut, const int32_t *d_segOffs, const ulcx_segment *d_seg, int nSeg,
                                              uint8_t *d_outPayload, long long outPayloadStride, int32_t *d_outPayloadBytes, int32_t *d_outMaxBlock,
                                              ulcx_index_entry *d_outIndex, int outIndexStride, int32_t *d_outIndexBlocks, int32_t *d_segStart, void *hipStream) {
-    const CropsRagged g = { payloadTotal, d_payloadOffs, indexTotal, d_indexOffs };
     const SpliceOut o = { d_outPayload, outPayloadStride, d_outPayloadBytes, d_outMaxBlock, d_outIndex, outIndexStride, d_outIndexBlocks, d_segStart };
-    return splice_any("ulcx_corpus_splice_ragged_dev", e, nFiles, d_payload, 0, nullptr, d_index, 0, d_indexBlocks, &g, nOut, d_segOffs, d_seg, nSeg, o, hipStream);
+    return splice_any("ulcx_corpus_splice_ragged_dev", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                      nOut, d_segOffs, d_seg, nSeg, o, hipStream);
 }
 // the host forms: the scalar checks of the _dev form first (on the host pointers), then what only a host form can refuse; the
 // outputs go through device buffers of the call's own, and of the payload only the bytes the call wrote come back
-static int splice_host_any(const char *who, ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
-                           const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks, const CropsRagged *ragged,
-                           int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg, const SpliceOut &o) {
-    if (!h_payload || !h_index || !h_indexBlocks || !h_segOffs || !h_seg || !o.payload || !o.payloadBytes || !o.index || !o.indexBlocks || !o.segStart ||
-        (ragged ? (!ragged->payloadOffs || !ragged->indexOffs) : !h_payloadBytes)) return refuse(who, "bad argument (a NULL pointer)");
-    if (nFiles < 1 || nOut < 1 || nSeg < 1) return refuse(who, "bad argument (nFiles %d, nOut %d, nSeg %d)", nFiles, nOut, nSeg);
-    if (ragged ? (ragged->payloadTotal < 0 || ragged->indexTotal < 0) : (payloadStride < 1 || indexStride < 1))
-        return ragged ? refuse(who, "bad argument (payloadTotal %lld, indexTotal %lld)", ragged->payloadTotal, ragged->indexTotal)
-                      : refuse(who, "bad argument (payloadStride %lld, indexStride %d)", payloadStride, indexStride);
-    if (o.payloadStride < 1 || o.indexStride < 2) return refuse(who, "bad argument (outPayloadStride %lld, outIndexStride %d: at least 1 and 2)", o.payloadStride, o.indexStride);
-    if (ragged && ragged_tables_bad(who, nFiles, *ragged)) return ULCX_ERR_ARG;
+static int splice_host_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg,
+                           const SpliceOut &o) {
+    if (splice_args_bad(who, g, nOut, h_segOffs, h_seg, nSeg, o)) return ULCX_ERR_ARG;
+    if (g.ragged && ragged_tables_bad(who, g)) return ULCX_ERR_ARG;
     if (h_segOffs[0] < 0 || h_segOffs[nOut] > nSeg) return refuse(who, "h_segOffs runs from %d to %d, outside 0 .. nSeg = %d", (int)h_segOffs[0], (int)h_segOffs[nOut], nSeg);
     for (int i = 0; i < nOut; i++)
         if (h_segOffs[i + 1] < h_segOffs[i]) return refuse(who, "h_segOffs falls from %d to %d at output file %d", (int)h_segOffs[i], (int)h_segOffs[i + 1], i);
     for (int j = 0; j < nSeg; j++) {
-        const ulcx_segment &g = h_seg[j];
-        if (g.File < 0 || g.File >= nFiles) return refuse(who, "segment %d names file %d of %d", j, (int)g.File, nFiles);
-        if (g.First < 0 || g.Count < 0) return refuse(who, "segment %d is %d blocks from block %d", j, (int)g.Count, (int)g.First);
-        if ((long long)g.First + g.Count > (long long)h_indexBlocks[g.File])
-            return refuse(who, "segment %d ends at block %lld of a file of %d", j, (long long)g.First + g.Count, (int)h_indexBlocks[g.File]);
+        const ulcx_segment &s = h_seg[j];
+        if (s.File < 0 || s.File >= g.nFiles) return refuse(who, "segment %d names file %d of %d", j, (int)s.File, g.nFiles);
+        if (s.First < 0 || s.Count < 0) return refuse(who, "segment %d is %d blocks from block %d", j, (int)s.Count, (int)s.First);
+        if ((long long)s.First + s.Count > (long long)g.indexBlocks[s.File])
+            return refuse(who, "segment %d ends at block %lld of a file of %d", j, (long long)s.First + s.Count, (int)g.indexBlocks[s.File]);
     }
     if (!e) return refuse(who, "no decoder");
     CKR(hipSetDevice(e->device));
-    const size_t nEnt = ragged ? (size_t)ragged->indexTotal : (size_t)nFiles * (size_t)indexStride, outEnt = (size_t)nOut * (size_t)o.indexStride;
-    DevTmp t; uint8_t *dp = nullptr, *dop = nullptr; int32_t *dn = nullptr, *dcnt = nullptr, *dso = nullptr, *dob = nullptr, *dom = nullptr, *docnt = nullptr, *dss = nullptr;
-    ulcx_index_entry *di = nullptr, *doi = nullptr; ulcx_segment *dseg = nullptr; CropsRagged dg = {};
-    int rc = ragged ? ragged_up(t, nFiles, h_payload, *ragged, &dp, &dg) : payload_rows_up(t, nFiles, h_payload, payloadStride, h_payloadBytes, &dp, &dn);
+    const size_t outEnt = (size_t)nOut * (size_t)o.indexStride;
+    DevTmp t; UlcxCorpus d; uint8_t *dop = nullptr; int32_t *dso = nullptr, *dob = nullptr, *dom = nullptr, *docnt = nullptr, *dss = nullptr;
+    ulcx_index_entry *doi = nullptr; ulcx_segment *dseg = nullptr;
+    int rc = corpus_up(t, g, &d);
     if (rc) return rc;
-    CKR(t.get(&dcnt, sizeof(int32_t) * (size_t)nFiles)); CKR(t.get(&di, sizeof(ulcx_index_entry) * nEnt));
     CKR(t.get(&dso, sizeof(int32_t) * ((size_t)nOut + 1))); CKR(t.get(&dseg, sizeof(ulcx_segment) * (size_t)nSeg)); CKR(t.get(&dss, sizeof(int32_t) * (size_t)nSeg));
     CKR(t.get(&dop, (size_t)nOut * (size_t)o.payloadStride)); CKR(t.get(&dob, sizeof(int32_t) * (size_t)nOut)); CKR(t.get(&dom, sizeof(int32_t) * (size_t)nOut));
     CKR(t.get(&docnt, sizeof(int32_t) * (size_t)nOut)); CKR(t.get(&doi, sizeof(ulcx_index_entry) * outEnt));
-    CKR(hipMemcpy(dcnt, h_indexBlocks, sizeof(int32_t) * (size_t)nFiles, hipMemcpyHostToDevice));
-    if (nEnt) CKR(hipMemcpy(di, h_index, sizeof(ulcx_index_entry) * nEnt, hipMemcpyHostToDevice));
     CKR(hipMemcpy(dso, h_segOffs, sizeof(int32_t) * ((size_t)nOut + 1), hipMemcpyHostToDevice));
     CKR(hipMemcpy(dseg, h_seg, sizeof(ulcx_segment) * (size_t)nSeg, hipMemcpyHostToDevice));
     CKR(hipMemcpy(dss, o.segStart, sizeof(int32_t) * (size_t)nSeg, hipMemcpyHostToDevice));     // (segments of no output file go back as they came)
-    const SpliceOut d = { dop, o.payloadStride, dob, dom, doi, o.indexStride, docnt, dss };
-    if ((rc = splice_any(who, e, nFiles, dp, payloadStride, dn, di, indexStride, dcnt, ragged ? &dg : nullptr, nOut, dso, dseg, nSeg, d, nullptr))) return rc;
+    const SpliceOut od = { dop, o.payloadStride, dob, dom, doi, o.indexStride, docnt, dss };
+    if ((rc = splice_any(who, e, d, nOut, dso, dseg, nSeg, od, nullptr))) return rc;
     CKR(hipDeviceSynchronize());
     CKR(hipMemcpy(o.payloadBytes, dob, sizeof(int32_t) * (size_t)nOut, hipMemcpyDeviceToHost));
     if (o.maxBlock) CKR(hipMemcpy(o.maxBlock, dom, sizeof(int32_t) * (size_t)nOut, hipMemcpyDeviceToHost));
@@ -2664,7 +2580,7 @@ extern "C" int ulcx_corpus_splice_host(ulcx_decoder *e, int nFiles, const uint8_
                                        uint8_t *h_outPayload, long long outPayloadStride, int32_t *h_outPayloadBytes, int32_t *h_outMaxBlock,
                                        ulcx_index_entry *h_outIndex, int outIndexStride, int32_t *h_outIndexBlocks, int32_t *h_segStart) {
     const SpliceOut o = { h_outPayload, outPayloadStride, h_outPayloadBytes, h_outMaxBlock, h_outIndex, outIndexStride, h_outIndexBlocks, h_segStart };
-    return splice_host_any("ulcx_corpus_splice_host", e, nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks, nullptr,
+    return splice_host_any("ulcx_corpus_splice_host", e, ulcx_corpus_strided(nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks),
                            nOut, h_segOffs, h_seg, nSeg, o);
 }
 extern "C" int ulcx_corpus_splice_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
@@ -2672,9 +2588,8 @@ extern "C" int ulcx_corpus_splice_ragged_host(ulcx_decoder *e, int nFiles, const
                                               int nOut, const int32_t *h_segOffs, const ulcx_segment *h_seg, int nSeg,
                                               uint8_t *h_outPayload, long long outPayloadStride, int32_t *h_outPayloadBytes, int32_t *h_outMaxBlock,
                                               ulcx_index_entry *h_outIndex, int outIndexStride, int32_t *h_outIndexBlocks, int32_t *h_segStart) {
-    const CropsRagged g = { payloadTotal, h_payloadOffs, indexTotal, h_indexOffs };
     const SpliceOut o = { h_outPayload, outPayloadStride, h_outPayloadBytes, h_outMaxBlock, h_outIndex, outIndexStride, h_outIndexBlocks, h_segStart };
-    return splice_host_any("ulcx_corpus_splice_ragged_host", e, nFiles, h_payload, 0, nullptr, h_index, 0, h_indexBlocks, &g,
+    return splice_host_any("ulcx_corpus_splice_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
                            nOut, h_segOffs, h_seg, nSeg, o);
 }
 extern "C" int ulcx_index_check(const ulcx_index_entry *row, int nBlocks, int indexStride, long long payloadBytes) {

@@ -6,6 +6,9 @@
 //             nothing but walk and take notes: 8-byte records of the runs of coded coefficients and of
 //             the noise runs (about 1 KB per block instead of 16 KB of coefficients), RNG draw counts,
 //             and the decaying-noise level chain of each unit's tail.
+//   k_dscan_rows  the same walk for every call that finds its blocks through a block index (range calls, crops of a strided or
+//             ragged corpus, sample crops, spectra): one lane per (row, block), the row's file and the block's extent through the
+//             one view of a corpus (UlcxCorpus; corpus_file / file_block in ulcx_dec_dev.h), which the splice kernels share.
 //   k_dsyn    stereo streams: one workgroup (2 waves) per stream, blocks in order, one wave per channel:
 //             the records are scattered STRAIGHT INTO the FFT's LDS arrays, noise runs are synthesised
 //             32 coefficients per lane from a jumped-ahead xorshift state (top bits by parity masks), then
@@ -400,157 +403,62 @@ __global__ __launch_bounds__(64) void k_dscan_packed(UlcxDecCtx c) {
     c.packOff[s] = off;
 }
 
-// Pass 1 of a range call (ulcx_decode_range_*) - one lane per (stream, row), as k_dscan: the block index gives every
-// block's start and its exact extent, so nothing is walked in series.  Row r of stream s is block rFirst[s] - 1 + r (row 0:
-// the block in front of the range).  A row without a block - in front of block 0, at or past the index's block count, of a
-// stream whose start lies outside its index - is marked as a corrupt block is (window code 0: the stream ends there).  The
-// table is not trusted: an entry that points outside its stream's payload marks its row the same way.
-__global__ __launch_bounds__(64) void k_dscan_range(UlcxDecCtx c) {
+// Pass 1 of every call that finds its blocks through a block index - one lane per (row, block-row), as k_dscan: the index gives
+// every block's start and its exact extent, so nothing is walked in series.  Row r of row-of-the-call i is block rFirst[i] - 1 + r
+// of the row's file (row 0: the block in front, run without output for the lapping state), found through the one view of the
+// corpus (corpus_file / file_block).  The two kinds of call differ in four things, each picked by `crop` (one kernel with uniform
+// branches: compiled once for each kind, the range call's scan stage measured 2 % longer, profiles/corpus_view_ab.txt):
+//   a range call (ulcx_decode_range_*, file == NULL): the corpus is the decoder's own streams and row i is stream i; every block
+//     of the row is wanted; a row stays sane block by block (an entry that points outside its stream's payload marks that block
+//     alone); and the packed read position behind the range is written (the closing entry when the range runs past the
+//     stream's end: where a sequential decode stops).
+//   a crop call (ulcx_decode_crops_*): row i names file file[i] of a corpus, strided or ragged, that is looked at only once the
+//     number is known to lie inside [0, nFiles), and any number of rows may name one file; count[i] leading blocks are wanted, or
+//     all; a row is all or nothing (below); no read position is written - a crop belongs to no stream.
+// A lane without a block - a file or a start out of range, a block in front of block 0, at or past the file's block count or
+// the row's count, a refused file or entry - marks it as a corrupt block is (window code 0: the row ends there).
+__global__ __launch_bounds__(64) void k_dscan_rows(UlcxDecCtx c, UlcxCorpus cp, const int32_t *file, const int32_t *count) {
     __shared__ uint2 ringP[DSCAN_RP * 64], ringN[DSCAN_RN * 64];
     const int id0 = blockIdx.x * 64 + threadIdx.x, K = c.K;
-    const bool live0 = id0 < c.B * K;
+    const bool live0 = id0 < c.B * K, crop = file != nullptr;
     const int id = live0 ? id0 : c.B * K - 1;                             // (a lane without a row shadows the last one, and writes nothing)
     const int s = id / K, r = id - s * K;
-    int nI = c.rIndexBlocks[s];
-    nI = nI < 0 ? 0 : nI > c.rIndexStride - 1 ? c.rIndexStride - 1 : nI;
-    const int first = c.rFirst[s];
-    const bool okS = first >= 0 && first <= nI;
-    const int k = first - 1 + r;
-    const ulcx_index_entry *row = c.rIndex + (size_t)s * c.rIndexStride;
-    int off = 0, ext = 0;
-    if (okS && k >= 0 && k < nI) { off = row[k].ByteOffs; ext = row[k + 1].ByteOffs - off; }
-    long long avail = c.payBytes[s];
-    avail = avail > c.payStride ? c.payStride : avail;
-    const bool sane = off >= 0 && ext > 0 && (long long)off + ext <= avail;
-    if (!sane) { off = 0; ext = 0; }
-    const uint8_t *p = c.in + (size_t)s * c.payStride + off, *bufEnd = c.in + c.inBytes;
-    // every look of every lane of the wave inside the buffer (k_dscan): the window without bounds checks
-    const bool inside = (size_t)(p - c.in) >= ((uintptr_t)p & 15) && (size_t)(bufEnd - p) >= (size_t)ext + 80;
-    const int blk = s * K + r;
-    const bool live = live0 && sane;
-    if (__ballot(!inside) == 0ull) scan_block<NybWinFast, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
-    else scan_block<NybWin, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
-    if (live0 && !sane) { c.bits[blk] = 0; c.wcScan[blk] = 0; c.draws[blk] = 0; }
-    if (live0 && r == 0) {
-        // what the synthesis needs to enter the stream, and the packed read position behind the range (the closing entry
-        // when the range runs past the stream's end: where a sequential decode stops)
-        const int pre = (okS && first > 0) ? 1 : 0;
-        c.rInfo[s] = make_int2(pre, okS ? (int)row[first - pre].RngState : 0);
-        if (okS) { const int e = first + K - 1; c.packOff[s] = row[e < nI ? e : nI].ByteOffs; }
-    }
-}
-
-// Pass 1 of a crop call (ulcx_decode_crops_*) - one lane per (row, block-row), as k_dscan_range, but a row of the call is not a
-// stream of the object: row i is blocks rFirst[i] .. of file `file[i]` of a corpus of nFiles payloads, and c.in / payStride /
-// payBytes / rIndex / rIndexBlocks are the corpus's ([nFiles]), looked at only once the file number is known to lie inside
-// [0, nFiles).  Any number of rows may name one file.  A lane without a block - a file or a start out of range, a block at or
-// past the file's block count or the row's `count`, a row one of whose index entries points outside its file's payload - marks
-// it as k_dscan_range does (window code 0: the row ends there).  No read position is written: a crop belongs to no stream.
-__global__ __launch_bounds__(64) void k_dscan_crop(UlcxDecCtx c, int nFiles, const int32_t *file, const int32_t *count) {
-    __shared__ uint2 ringP[DSCAN_RP * 64], ringN[DSCAN_RN * 64];
-    const int id0 = blockIdx.x * 64 + threadIdx.x, K = c.K;
-    const bool live0 = id0 < c.B * K;
-    const int id = live0 ? id0 : c.B * K - 1;                             // (a lane without a row shadows the last one, and writes nothing)
-    const int s = id / K, r = id - s * K;
-    const int f = file[s];
-    const bool okF = f >= 0 && f < nFiles;
-    const size_t fi = okF ? (size_t)f : 0;                                // (nFiles >= 1: file 0 exists, and nothing of it is used for a bad row)
-    int nI = c.rIndexBlocks[fi];
-    nI = nI < 0 ? 0 : nI > c.rIndexStride - 1 ? c.rIndexStride - 1 : nI;
-    const int first = c.rFirst[s];
-    int want = count ? count[s] : K - 1;                                  // leading blocks of the row that are wanted
+    const int f = crop ? file[s] : s;
+    const bool okF = f >= 0 && f < cp.nFiles;
+    const CorpusFile cf = corpus_file(cp, okF ? (size_t)f : 0, cp.payOffs != nullptr);           // (nFiles >= 1: file 0 exists, and nothing of it is used for a bad row)
+    const int nI = cf.nI, first = c.rFirst[s];
+    int want = count ? count[s] : K - 1;                                  // leading blocks of the row that are wanted (K >= 2)
     want = want > K - 1 ? K - 1 : want;
-    bool okS = okF && first >= 0 && first <= nI && want > 0;
-    const int k = first - 1 + r;
-    const ulcx_index_entry *row = c.rIndex + fi * (size_t)c.rIndexStride;
-    long long avail = c.payBytes[fi];
-    avail = avail > c.payStride ? c.payStride : avail;
-    if (okS) {
-        // the table is not trusted, and a row is all or nothing: every entry that bounds a block of the row (the one in front
+    bool okS = okF && cf.ok && first >= 0 && first <= nI && want > 0;
+    if (okS && crop) {
+        // the table is not trusted, and a crop row is all or nothing: every entry that bounds a block of the row (the one in front
         // included) inside the file's payload and behind its predecessor - each lane looks at its row's <= K + 1 entries
         const int j0 = first > 0 ? first - 1 : 0, j1 = first + want < nI ? first + want : nI;
-        long long prev = row[j0].ByteOffs;
+        long long prev = cf.row[j0].ByteOffs;
         bool okT = prev >= 0;
-        for (int j = j0 + 1; j <= j1; j++) { const long long o = row[j].ByteOffs; okT &= o > prev && o <= avail; prev = o; }
+        for (int j = j0 + 1; j <= j1; j++) { const long long o = cf.row[j].ByteOffs; okT &= o > prev && o <= cf.avail; prev = o; }
         okS = okT;
     }
-    int off = 0, ext = 0;
-    if (okS && k >= 0 && k < nI && r <= want) { off = row[k].ByteOffs; ext = row[k + 1].ByteOffs - off; }
-    const bool sane = off >= 0 && ext > 0 && (long long)off + ext <= avail;
-    if (!sane) { off = 0; ext = 0; }
-    const uint8_t *p = c.in + fi * (size_t)c.payStride + off, *bufEnd = c.in + c.inBytes;
+    FileBlock b = { 0, 0 };
+    if (okS && r <= want) b = file_block(cf, first - 1 + r);
+    const bool sane = b.ext > 0;
+    const int ext = b.ext;
+    const uint8_t *p = cf.base + b.off, *bufEnd = cp.pay + cp.payTotal;
     // every look of every lane of the wave inside the buffer (k_dscan): the window without bounds checks
-    const bool inside = (size_t)(p - c.in) >= ((uintptr_t)p & 15) && (size_t)(bufEnd - p) >= (size_t)ext + 80;
+    const bool inside = (size_t)(p - cp.pay) >= ((uintptr_t)p & 15) && (size_t)(bufEnd - p) >= (size_t)ext + 80;
     const int blk = s * K + r;
     const bool live = live0 && sane;
-    if (__ballot(!inside) == 0ull) scan_block<NybWinFast, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
-    else scan_block<NybWin, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
+    if (__ballot(!inside) == 0ull) scan_block<NybWinFast, true>(c, blk, p, ext * 8, ext, cp.pay, bufEnd, live, ringP, ringN);
+    else scan_block<NybWin, true>(c, blk, p, ext * 8, ext, cp.pay, bufEnd, live, ringP, ringN);
     if (live0 && !sane) { c.bits[blk] = 0; c.wcScan[blk] = 0; c.draws[blk] = 0; }
     if (live0 && r == 0) {
         // what the synthesis needs to enter the row: whether row 0 holds a block, and the generator state in front of it
         const int pre = (okS && first > 0) ? 1 : 0;
-        c.rInfo[s] = make_int2(pre, okS ? (int)row[first - pre].RngState : 0);
+        c.rInfo[s] = make_int2(pre, okS ? (int)cf.row[first - pre].RngState : 0);
+        if (okS && !crop) { const int e = first + K - 1; c.packOff[s] = cf.row[e < nI ? e : nI].ByteOffs; }
     }
 }
 
-// The same for a corpus whose files lie back to back (ulcx_decode_crops_ragged_*): c.in is the whole buffer of c.inBytes bytes,
-// file f is its bytes [payOffs[f], payOffs[f + 1]) and its index row the entries [idxOffs[f], idxOffs[f + 1]) of c.rIndex (idxTotal
-// entries in all); both tables have nFiles + 1 entries, and all of this arithmetic is 64-bit.  Neither table is trusted: offsets
-// that are negative, fall, leave their buffer, give a file of 2^31 bytes or more, or give a row without room for the file's
-// rIndexBlocks + 1 entries make the file one that does not exist - its rows report 0 bits, and none of its bytes is looked at.
-__global__ __launch_bounds__(64) void k_dscan_crop_ragged(UlcxDecCtx c, int nFiles, const int32_t *file, const int32_t *count,
-                                                          const int64_t *payOffs, const int64_t *idxOffs, long long idxTotal) {
-    __shared__ uint2 ringP[DSCAN_RP * 64], ringN[DSCAN_RN * 64];
-    const int id0 = blockIdx.x * 64 + threadIdx.x, K = c.K;
-    const bool live0 = id0 < c.B * K;
-    const int id = live0 ? id0 : c.B * K - 1;                             // (a lane without a row shadows the last one, and writes nothing)
-    const int s = id / K, r = id - s * K;
-    const int f = file[s];
-    bool okF = f >= 0 && f < nFiles;
-    const size_t fi = okF ? (size_t)f : 0;                                // (nFiles >= 1: entries 0 and 1 of both tables exist)
-    const long long p0 = payOffs[fi], p1 = payOffs[fi + 1], i0 = idxOffs[fi], i1 = idxOffs[fi + 1];
-    int nI = c.rIndexBlocks[fi];
-    nI = nI < 0 ? 0 : nI;
-    okF = okF && p0 >= 0 && p1 >= p0 && p1 <= c.inBytes && p1 - p0 < 0x80000000LL
-              && i0 >= 0 && i1 >= i0 && i1 <= idxTotal && i1 - i0 > (long long)nI;
-    nI = okF ? nI : 0;
-    const long long avail = okF ? p1 - p0 : 0;
-    const uint8_t *base = c.in + (okF ? p0 : 0);
-    const ulcx_index_entry *row = c.rIndex + (okF ? i0 : 0);
-    // from here on the row logic of k_dscan_crop, line for line (kept apart: hoisted into a function of both, k_dscan_crop's
-    // code object changes)
-    const int first = c.rFirst[s];
-    int want = count ? count[s] : K - 1;                                  // leading blocks of the row that are wanted
-    want = want > K - 1 ? K - 1 : want;
-    bool okS = okF && first >= 0 && first <= nI && want > 0;
-    const int k = first - 1 + r;
-    if (okS) {
-        // the table is not trusted, and a row is all or nothing: every entry that bounds a block of the row (the one in front
-        // included) inside the file's payload and behind its predecessor - each lane looks at its row's <= K + 1 entries
-        const int j0 = first > 0 ? first - 1 : 0, j1 = first + want < nI ? first + want : nI;
-        long long prev = row[j0].ByteOffs;
-        bool okT = prev >= 0;
-        for (int j = j0 + 1; j <= j1; j++) { const long long o = row[j].ByteOffs; okT &= o > prev && o <= avail; prev = o; }
-        okS = okT;
-    }
-    int off = 0, ext = 0;
-    if (okS && k >= 0 && k < nI && r <= want) { off = row[k].ByteOffs; ext = row[k + 1].ByteOffs - off; }
-    const bool sane = off >= 0 && ext > 0 && (long long)off + ext <= avail;
-    if (!sane) { off = 0; ext = 0; }
-    const uint8_t *p = base + off, *bufEnd = c.in + c.inBytes;
-    // every look of every lane of the wave inside the buffer (k_dscan): the window without bounds checks
-    const bool inside = (size_t)(p - c.in) >= ((uintptr_t)p & 15) && (size_t)(bufEnd - p) >= (size_t)ext + 80;
-    const int blk = s * K + r;
-    const bool live = live0 && sane;
-    if (__ballot(!inside) == 0ull) scan_block<NybWinFast, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
-    else scan_block<NybWin, true>(c, blk, p, ext * 8, ext, c.in, bufEnd, live, ringP, ringN);
-    if (live0 && !sane) { c.bits[blk] = 0; c.wcScan[blk] = 0; c.draws[blk] = 0; }
-    if (live0 && r == 0) {
-        // what the synthesis needs to enter the row: whether row 0 holds a block, and the generator state in front of it
-        const int pre = (okS && first > 0) ? 1 : 0;
-        c.rInfo[s] = make_int2(pre, okS ? (int)row[first - pre].RngState : 0);
-    }
-}
 
 // Block index of packed payloads (ulcx_index_packed_*) - one lane per stream, the walk of k_dscan_packed without its notes:
 // per block its start and the state the stream's one generator chain has there (one jump by the block's draws).  It stops
@@ -578,7 +486,7 @@ __global__ __launch_bounds__(64) void k_dindex(UlcxDecCtx c, int maxBlocks, ulcx
 }
 // The same for files that lie back to back (ulcx_index_packed_ragged_*) - one lane per file: file f is bytes [payOffs[f],
 // payOffs[f + 1]) of c.in, its row the entries [idxOffs[f], idxOffs[f + 1]) of `index` (idxTotal in all), filled as k_dindex fills
-// a row of maxBlocks = capacity - 1.  Offsets as k_dscan_crop_ragged refuses them, or a row without an entry: a count of 0 and
+// a row of maxBlocks = capacity - 1.  Payload offsets as corpus_file refuses them, or a row without an entry: a count of 0 and
 // nothing written.  (A row of 2^31 entries or more is used up to that: a file below 2^31 bytes has fewer blocks.)  Lanes of one
 // wave wait for the longest file among them; the index is built once.
 __global__ __launch_bounds__(64) void k_dindex_ragged(UlcxDecCtx c, const int64_t *payOffs, const int64_t *idxOffs, long long idxTotal,
@@ -586,7 +494,7 @@ __global__ __launch_bounds__(64) void k_dindex_ragged(UlcxDecCtx c, const int64_
     const int f = blockIdx.x * 64 + threadIdx.x;
     if (f >= c.B) return;
     const long long p0 = payOffs[f], p1 = payOffs[f + 1], i0 = idxOffs[f], i1 = idxOffs[f + 1];
-    const bool ok = p0 >= 0 && p1 >= p0 && p1 <= c.inBytes && p1 - p0 < 0x80000000LL && i0 >= 0 && i1 > i0 && i1 <= idxTotal;
+    const bool ok = corpus_bytes_ok(p0, p1, c.inBytes) && i0 >= 0 && i1 > i0 && i1 <= idxTotal;
     if (!ok) { nBlocks[f] = 0; return; }
     const long long cap = i1 - i0 < 0x7FFFFFFFLL ? i1 - i0 : 0x7FFFFFFFLL;
     nBlocks[f] = index_walk(c, c.in + p0, (int)(p1 - p0), (int)cap - 1, index + i0);
@@ -680,35 +588,7 @@ __global__ __launch_bounds__(64) void k_dindex_slots_scan(const uint32_t *jumpT,
 //                  capacity as a further stop; the file's bytes, blocks and largest block.
 //   k_splice_copy  one lane per aligned 16-byte line of the output payloads: the output block a line begins in by binary search
 //                  in the finished row, its source as the walk found it, and on through the blocks the line holds.
-// SpliceSrc: the source corpus, strided (payOffs == NULL) or ragged; splice_file is k_dscan_crop's / k_dscan_crop_ragged's view of
-// file f (the caller has f inside [0, nFiles)).
-struct SpliceSrc {
-    const uint8_t *pay; long long payTotal;                         // the whole payload buffer: nothing outside it is read
-    long long payStride; const int32_t *payBytes;
-    const ulcx_index_entry *index; int indexStride; const int32_t *indexBlocks;
-    const int64_t *payOffs, *idxOffs; long long idxTotal;
-    int nFiles;
-};
-struct SpliceFile { const uint8_t *base; const ulcx_index_entry *row; long long avail; int nI; };
-template <bool RAGGED>
-__device__ __forceinline__ SpliceFile splice_file(const SpliceSrc &s, int f) {
-    SpliceFile r;
-    int nI = s.indexBlocks[f];
-    nI = nI < 0 ? 0 : nI;
-    if constexpr (RAGGED) {
-        const long long p0 = s.payOffs[f], p1 = s.payOffs[f + 1], i0 = s.idxOffs[f], i1 = s.idxOffs[f + 1];
-        const bool okF = p0 >= 0 && p1 >= p0 && p1 <= s.payTotal && p1 - p0 < 0x80000000LL
-                      && i0 >= 0 && i1 >= i0 && i1 <= s.idxTotal && i1 - i0 > (long long)nI;
-        r.nI = okF ? nI : 0; r.avail = okF ? p1 - p0 : 0;
-        r.base = s.pay + (okF ? p0 : 0); r.row = s.index + (okF ? i0 : 0);
-    } else {
-        r.nI = nI > s.indexStride - 1 ? s.indexStride - 1 : nI;
-        long long avail = s.payBytes[f];
-        r.avail = avail < 0 ? 0 : avail > s.payStride ? s.payStride : avail;
-        r.base = s.pay + (size_t)f * (size_t)s.payStride; r.row = s.index + (size_t)f * (size_t)s.indexStride;
-    }
-    return r;
-}
+// The source corpus and its files are read through corpus_file / file_block, as the indexed walk reads them.
 // the segments of output file o: {first, end}, or {0, -1} for a pair that falls or leaves [0, nSeg]
 __device__ __forceinline__ int2 splice_segs(const int32_t *segOffs, int o, int nSeg) {
     const int s0 = segOffs[o], s1 = segOffs[o + 1];
@@ -717,23 +597,17 @@ __device__ __forceinline__ int2 splice_segs(const int32_t *segOffs, int o, int n
 // Output block j of a file with segments [sg.x, sg.y): the source block it names -> {byte offset in its file, bytes} and the
 // file in sf; bytes 0 when there is none - j at or behind the plan's end, or a file, a block or index entries that cannot be taken.
 // The search: the last segment that starts at or in front of j (zero-count segments in front of it start where it does).
-struct SpliceBlk { int off, ext; };
 template <bool RAGGED>
-__device__ __forceinline__ SpliceBlk splice_block(const SpliceSrc &s, const int32_t *segStart, const ulcx_segment *seg, int2 sg, int j, SpliceFile &sf) {
-    SpliceBlk b = { 0, 0 };
+__device__ __forceinline__ FileBlock splice_block(const UlcxCorpus &s, const int32_t *segStart, const ulcx_segment *seg, int2 sg, int j, CorpusFile &sf) {
+    const FileBlock none = { 0, 0 };
     int lo = sg.x, hi = sg.y;                                       // the last segment that starts at or in front of j
     while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (segStart[mid] <= j) lo = mid + 1; else hi = mid; }
-    if (lo <= sg.x) return b;
+    if (lo <= sg.x) return none;
     const ulcx_segment g = seg[lo - 1];
     const int r = j - segStart[lo - 1];
-    if (r < 0 || r >= g.Count || g.File < 0 || g.File >= s.nFiles || g.First < 0) return b;
-    const long long k = (long long)g.First + r;
-    sf = splice_file<RAGGED>(s, g.File);
-    if (k >= sf.nI) return b;
-    const long long o0 = sf.row[k].ByteOffs, o1 = sf.row[k + 1].ByteOffs;
-    if (o0 < 0 || o1 <= o0 || o1 > sf.avail) return b;
-    b.off = (int)o0; b.ext = (int)(o1 - o0);
-    return b;
+    if (r < 0 || r >= g.Count || g.File < 0 || g.File >= s.nFiles || g.First < 0) return none;
+    sf = corpus_file(s, (size_t)g.File, RAGGED);
+    return file_block(sf, (long long)g.First + r);
 }
 __global__ __launch_bounds__(64) void k_splice_plan(int nSeg, const int32_t *segOffs, const ulcx_segment *seg, int32_t *segStart) {
     const int o = blockIdx.x, lane = threadIdx.x;
@@ -758,7 +632,7 @@ __global__ __launch_bounds__(64) void k_splice_plan(int nSeg, const int32_t *seg
     }
 }
 template <bool RAGGED>
-__global__ __launch_bounds__(64) void k_splice_walk(UlcxDecCtx c, SpliceSrc s, long long nAll, int nSeg, const int32_t *segOffs, const ulcx_segment *seg,
+__global__ __launch_bounds__(64) void k_splice_walk(UlcxDecCtx c, UlcxCorpus s, long long nAll, int nSeg, const int32_t *segOffs, const ulcx_segment *seg,
                                                     const int32_t *segStart, ulcx_index_entry *outIndex, int outIndexStride) {
     const long long id = (long long)blockIdx.x * 64 + threadIdx.x;
     if (id >= nAll) return;
@@ -766,8 +640,8 @@ __global__ __launch_bounds__(64) void k_splice_walk(UlcxDecCtx c, SpliceSrc s, l
     const long long o = id / per;
     const int j = (int)(id - o * per);
     const int2 sg = splice_segs(segOffs, (int)o, nSeg);
-    SpliceFile sf;
-    const SpliceBlk b = splice_block<RAGGED>(s, segStart, seg, sg, j, sf);
+    CorpusFile sf;
+    const FileBlock b = splice_block<RAGGED>(s, segStart, seg, sg, j, sf);
     if (!b.ext) return;
     const Walked w = scan_block<NybWin, false, false>(c, 0, sf.base + b.off, b.ext * 8, b.ext, c.in, c.in + c.inBytes);
     if (w.bits <= 0 || ((w.bits + 7) >> 3) != b.ext) return;
@@ -829,7 +703,7 @@ __device__ __forceinline__ uint4 splice_load16(const uint8_t *src) {
 }
 #define SPLICE_COPY_WG 256
 template <bool RAGGED>
-__global__ __launch_bounds__(SPLICE_COPY_WG) void k_splice_copy(SpliceSrc s, long long nAll, long long lines, int nSeg, const int32_t *segOffs, const ulcx_segment *seg,
+__global__ __launch_bounds__(SPLICE_COPY_WG) void k_splice_copy(UlcxCorpus s, long long nAll, long long lines, int nSeg, const int32_t *segOffs, const ulcx_segment *seg,
                                                                 const int32_t *segStart, const ulcx_index_entry *outIndex, int outIndexStride,
                                                                 const int32_t *outBlocks, uint8_t *outPay, long long outPayStride) {
     const long long id = (long long)blockIdx.x * SPLICE_COPY_WG + threadIdx.x;
@@ -852,8 +726,8 @@ __global__ __launch_bounds__(SPLICE_COPY_WG) void k_splice_copy(SpliceSrc s, lon
     bool whole = false;
     for (int at = a; at < z; blk++) {
         const int b0 = row[blk].ByteOffs, b1 = row[blk + 1].ByteOffs, end = b1 < z ? b1 : z;
-        SpliceFile sf;
-        const SpliceBlk b = splice_block<RAGGED>(s, segStart, seg, sg, blk, sf);
+        CorpusFile sf;
+        const FileBlock b = splice_block<RAGGED>(s, segStart, seg, sg, blk, sf);
         if (b.ext != b1 - b0) return;                               // (not what the walk saw: tables that changed under the call)
         const uint8_t *src = sf.base + b.off + (at - b0);
         if (end - at == 16) { const uint4 x = splice_load16(src); v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; whole = true; }
@@ -2117,10 +1991,10 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     else {
     if (samp) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, c.BS, aux.nSamples, aux.sampStart, aux.sampLen,
                                  aux.sampFirst, aux.sampCount, aux.sampSkip, aux.sampLenC);
-    if (aux.nFiles > 0 && aux.payOffs) hipLaunchKernelGGL(k_dscan_crop_ragged, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount,
-                                                          aux.payOffs, aux.idxOffs, aux.idxTotal);
-    else if (aux.nFiles > 0) hipLaunchKernelGGL(k_dscan_crop, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.nFiles, aux.cropFile, aux.cropCount);
-    else if (c.range) hipLaunchKernelGGL(k_dscan_range, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
+    // the indexed walk: over a crop call's corpus, or for a range call over the decoder's own streams as a strided corpus (file = stream)
+    if (aux.corpus.nFiles > 0) hipLaunchKernelGGL(k_dscan_rows, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.corpus, aux.cropFile, aux.cropCount);
+    else if (c.range) hipLaunchKernelGGL(k_dscan_rows, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c,
+                                         ulcx_corpus_strided(c.B, c.in, c.payStride, c.payBytes, c.rIndex, c.rIndexStride, c.rIndexBlocks), nullptr, nullptr);
     else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     }
@@ -2175,23 +2049,19 @@ int ulcx_index_slots_launch(const UlcxDecCtx &c, int nRows, int nBlocks, const i
     return ULCX_OK;
 }
 
-// c.in / c.inBytes: the source's whole payload buffer; geometry and tables are all else that is read of c
+// c.in / c.inBytes: the source's whole payload buffer, as a.src has it; geometry and tables are all else that is read of c
 int ulcx_splice_launch(const UlcxDecCtx &c, const UlcxSpliceArgs &a, hipStream_t st) {
-    SpliceSrc s = { c.in, c.inBytes, a.payStride, a.payBytes, a.index, a.indexStride, a.indexBlocks, a.payOffs, a.idxOffs, a.idxTotal, a.nFiles };
-    const bool ragged = a.payOffs != nullptr;
     const long long nEnt = (long long)a.nOut * a.outIndexStride, nBlk = (long long)a.nOut * (a.outIndexStride - 1);
     // aligned 16-byte lines a file of outPayStride bytes can touch, wherever it starts
     const long long lines = (a.outPayStride + 15 + 15) / 16, nLines = (long long)a.nOut * lines;
     hipLaunchKernelGGL(k_dindex_begin, dim3((unsigned)((nEnt + 255) / 256)), dim3(256), 0, st, nEnt, a.outIndexStride, a.outIndex, a.outIndexBlocks);
     hipLaunchKernelGGL(k_splice_plan, dim3(a.nOut), dim3(64), 0, st, a.nSeg, a.segOffs, a.seg, a.segStart);
-    if (ragged) hipLaunchKernelGGL(k_splice_walk<true>, dim3((unsigned)((nBlk + 63) / 64)), dim3(64), 0, st, c, s, nBlk, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride);
-    else hipLaunchKernelGGL(k_splice_walk<false>, dim3((unsigned)((nBlk + 63) / 64)), dim3(64), 0, st, c, s, nBlk, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride);
+    const bool ragged = a.src.payOffs != nullptr;
+    hipLaunchKernelGGL(ragged ? k_splice_walk<true> : k_splice_walk<false>, dim3((unsigned)((nBlk + 63) / 64)), dim3(64), 0, st, c, a.src, nBlk, a.nSeg, a.segOffs, a.seg,
+                       a.segStart, a.outIndex, a.outIndexStride);
     hipLaunchKernelGGL(k_splice_scan, dim3(a.nOut), dim3(64), 0, st, c.jumpT, a.outIndex, a.outIndexStride, a.outPayStride, a.outPayBytes, a.outMaxBlock, a.outIndexBlocks);
-    const dim3 cg((unsigned)((nLines + SPLICE_COPY_WG - 1) / SPLICE_COPY_WG));
-    if (ragged) hipLaunchKernelGGL(k_splice_copy<true>, cg, dim3(SPLICE_COPY_WG), 0, st, s, nLines, lines, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride,
-                                   a.outIndexBlocks, a.outPay, a.outPayStride);
-    else hipLaunchKernelGGL(k_splice_copy<false>, cg, dim3(SPLICE_COPY_WG), 0, st, s, nLines, lines, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride,
-                            a.outIndexBlocks, a.outPay, a.outPayStride);
+    hipLaunchKernelGGL(ragged ? k_splice_copy<true> : k_splice_copy<false>, dim3((unsigned)((nLines + SPLICE_COPY_WG - 1) / SPLICE_COPY_WG)), dim3(SPLICE_COPY_WG), 0, st,
+                       a.src, nLines, lines, a.nSeg, a.segOffs, a.seg, a.segStart, a.outIndex, a.outIndexStride, a.outIndexBlocks, a.outPay, a.outPayStride);
     CK(hipGetLastError());
     return ULCX_OK;
 }

@@ -3,6 +3,47 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ulcx_internal.h"
+
+// ---------------------------------------------------------------------------
+// The one view of a corpus (UlcxCorpus): file f of it, f inside [0, nFiles) by the caller's own test, and block k of that file.
+// Neither the offset tables nor the index are trusted.  A ragged file whose offsets are negative, fall, leave their buffer, give a
+// file of 2^31 bytes or more, or give a row without room for the file's indexBlocks + 1 entries is refused: ok false, nI = 0,
+// avail = 0, and none of its bytes or entries is looked at.  A strided row's count is clamped so that its closing entry stays in the row,
+// and its bytes to [0, payStride] (a negative payBytes fails every later comparison as it stands - avail is only ever the upper
+// bound of an offset that is >= 0 -, so the clamp to 0 changes no result).
+// ---------------------------------------------------------------------------
+// bytes [p0, p1) of a buffer of `total` bytes as a file's payload (also k_dindex_ragged's test, which has no block count yet)
+__device__ __forceinline__ bool corpus_bytes_ok(long long p0, long long p1, long long total) { return p0 >= 0 && p1 >= p0 && p1 <= total && p1 - p0 < 0x80000000LL; }
+struct CorpusFile { const uint8_t *base; const ulcx_index_entry *row; long long avail; int nI; bool ok; };   // ok: not refused (row[0] exists)
+// (ragged: s.payOffs != NULL, handed in so that a kernel compiled for one layout holds no code of the other)
+__device__ __forceinline__ CorpusFile corpus_file(const UlcxCorpus &s, size_t f, bool ragged) {
+    CorpusFile r;
+    const int nI = s.indexBlocks[f];
+    if (ragged) {
+        const long long p0 = s.payOffs[f], p1 = s.payOffs[f + 1], i0 = s.idxOffs[f], i1 = s.idxOffs[f + 1];
+        const bool okF = corpus_bytes_ok(p0, p1, s.payTotal) && i0 >= 0 && i1 >= i0 && i1 <= s.idxTotal && i1 - i0 > (long long)(nI < 0 ? 0 : nI);
+        r.ok = okF; r.nI = okF ? (nI < 0 ? 0 : nI) : 0; r.avail = okF ? p1 - p0 : 0;
+        r.base = s.pay + (okF ? p0 : 0); r.row = s.index + (okF ? i0 : 0);
+    } else {
+        r.ok = true; r.nI = (int)ulcx_row_blocks(nI, s.indexStride);
+        const long long avail = s.payBytes[f];
+        r.avail = avail < 0 ? 0 : avail > s.payStride ? s.payStride : avail;
+        r.base = s.pay + f * (size_t)s.payStride; r.row = s.index + f * (size_t)s.indexStride;
+    }
+    return r;
+}
+// block k of the file: {byte offset in the file, bytes}; bytes 0 when there is none - k outside [0, nI), or bounding entries
+// that are negative, do not rise or leave the file's bytes
+struct FileBlock { int off, ext; };
+__device__ __forceinline__ FileBlock file_block(const CorpusFile &f, long long k) {
+    FileBlock b = { 0, 0 };
+    if (k < 0 || k >= f.nI) return b;
+    const long long o0 = f.row[k].ByteOffs, o1 = f.row[k + 1].ByteOffs;
+    if (o0 < 0 || o1 <= o0 || o1 > f.avail) return b;
+    b.off = (int)o0; b.ext = (int)(o1 - o0);
+    return b;
+}
 
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float expand_quantizer(int q) {        // ulcDecoder.c:96-98

@@ -163,7 +163,7 @@ struct UlcxDecCtx {
     const ulcx_index_entry *rIndex;      // [B][rIndexStride]
     int   rIndexStride;
     const int32_t *rIndexBlocks, *rFirst;   // [B] entries of each stream's index that are blocks; first block of the range
-    int2 *rInfo;                         // [B] {1 = row 0 holds a block, generator state in front of the stream's first row} (k_dscan_range)
+    int2 *rInfo;                         // [B] {1 = row 0 holds a block, generator state in front of the stream's first row} (k_dscan_rows)
     int32_t *bitsOut;                    // [B][K-1] the caller's sizes (c.bits: the rows' own, [B][K])
 };
 
@@ -211,19 +211,42 @@ int ulcx_enc_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev /* ULCX_
 // ulcx_encode_*_ladder: one context per rung (rung 0's carries wcOut / cplxOut); k_rung_arm arms rungs >= 1 (ulcx_enc_ladder.hip)
 int ulcx_enc_launch_ladder(const UlcxEncCtx *rungs, int nRungs, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux);
 void ulcx_enc_rung_arm(const UlcxEncCtx &c, hipStream_t st);
+// A corpus of indexed files in HBM, strided or ragged (payOffs != NULL): the one description every call family that finds a file
+// and a block in a corpus hands its kernels, by value - crops, sample crops, spectra, splice, and a range call, whose corpus is
+// the decoder's own streams (file = stream).  corpus_file / file_block (ulcx_dec_dev.h) are the one reading of it; none of its
+// tables is trusted.  Pointers are device pointers in a launch, host pointers while a host form checks and uploads them.
+struct UlcxCorpus {
+    const uint8_t *pay; long long payTotal;                  // the whole payload buffer: nothing outside it is read
+    const ulcx_index_entry *index; long long idxTotal;      // the whole index, in entries
+    const int32_t *indexBlocks;          // [nFiles] entries of each file's row that are blocks
+    int nFiles;
+    int ragged;                          // host side only: the entry is a ragged form (its tables may still be NULL, and are then refused)
+    // strided: file f is payBytes[f] bytes at pay + f * payStride, its row the indexStride entries at index + f * indexStride
+    long long payStride; const int32_t *payBytes; int indexStride;
+    // ragged: file f is bytes [payOffs[f], payOffs[f + 1]) of pay, its row the entries [idxOffs[f], idxOffs[f + 1]) of index
+    const int64_t *payOffs, *idxOffs;    // [nFiles + 1]
+};
+static inline UlcxCorpus ulcx_corpus_strided(int nFiles, const uint8_t *pay, long long payStride, const int32_t *payBytes, const ulcx_index_entry *index,
+                                             int indexStride, const int32_t *indexBlocks) {
+    return UlcxCorpus{ pay, (long long)nFiles * payStride, index, (long long)nFiles * indexStride, indexBlocks, nFiles, 0, payStride, payBytes, indexStride, nullptr, nullptr };
+}
+static inline UlcxCorpus ulcx_corpus_ragged(int nFiles, const uint8_t *pay, long long payTotal, const int64_t *payOffs, const ulcx_index_entry *index,
+                                            long long idxTotal, const int64_t *idxOffs, const int32_t *indexBlocks) {
+    return UlcxCorpus{ pay, payTotal, index, idxTotal, indexBlocks, nFiles, 1, 0, nullptr, 0, payOffs, idxOffs };
+}
+// The blocks of an index row of `entries` entries that counts nI, as every walk reads a count: the closing entry stays inside the
+// row.  (The kernels' file view and the host forms' row checks both call this.)
+__host__ __device__ static inline long long ulcx_row_blocks(long long nI, long long entries) { return nI < 0 ? 0 : nI > entries - 1 ? entries - 1 : nI; }
+
 struct UlcxDecAux {
     int synGrid;                         // > 0: workgroups of the synthesis over a cut of the (stream, block) pairs; 0: one per stream
     int synFull;                         // of those, the leading ones that take one whole stream each (0: an even cut of everything)
-    // crop calls (ulcx_decode_crops_*): nFiles > 0 - the walk is k_dscan_crop, c.B rows that each name a file of the corpus.
-    // c.in / payStride / payBytes / rIndex / rIndexBlocks describe the nFiles files, c.rFirst and these two the c.B rows.
-    int nFiles = 0;
+    // crop calls (ulcx_decode_crops_*): corpus.nFiles > 0 - c.B rows that each name a file of the corpus, found by the indexed
+    // walk (k_dscan_rows) as a range call's streams are; c.rFirst and these two describe the rows.  c.payStride, c.payBytes and
+    // c.rIndex* are not looked at.
+    UlcxCorpus corpus = {};
     const int32_t *cropFile = nullptr;   // [c.B] file of each row
     const int32_t *cropCount = nullptr;  // [c.B] leading blocks wanted of each row, or NULL: all of them
-    // ragged corpus (ulcx_decode_crops_ragged_*): payOffs != NULL - the walk is k_dscan_crop_ragged; c.in / c.inBytes are the whole
-    // payload buffer, c.rIndex the whole index, and the files are found through the two offset tables (c.payStride, c.payBytes
-    // and c.rIndexStride are not looked at)
-    const int64_t *payOffs = nullptr, *idxOffs = nullptr;   // [nFiles + 1] bytes of c.in / entries of c.rIndex
-    long long idxTotal = 0;              // entries of c.rIndex
     // sample crops (ulcx_decode_crops_samples_*): sampStart != NULL - k_crop_sample_rows first turns the caller's (start, len) rows
     // into the decoder-owned arrays below ([nStreams] each); c.rFirst is sampFirst and cropCount is sampCount, so the crop walk
     // runs on them as on a caller's, and the synthesis is the sample-store instantiation, which takes sampSkip / sampLenC / nSamples
@@ -255,13 +278,9 @@ int ulcx_index_ragged_launch(const UlcxDecCtx &c, const int64_t *d_payOffs, cons
 int ulcx_index_begin_launch(int nRows, ulcx_index_entry *d_index, int indexStride, int32_t *d_nBlocks, hipStream_t st);
 int ulcx_index_slots_launch(const UlcxDecCtx &c, int nRows, int nBlocks, const int32_t *d_bits, ulcx_index_entry *d_index, int indexStride,
                             int32_t *d_nBlocks, hipStream_t st);
-// corpus splice (ulcx_corpus_splice_*): the source corpus beside c.in / c.inBytes (payOffs != NULL: ragged, as UlcxDecAux), the
-// segment list and the outputs; five launches, no scratch
+// corpus splice (ulcx_corpus_splice_*): the source corpus, the segment list and the outputs; five launches, no scratch
 struct UlcxSpliceArgs {
-    int nFiles;
-    long long payStride; const int32_t *payBytes;
-    const ulcx_index_entry *index; int indexStride; const int32_t *indexBlocks;
-    const int64_t *payOffs, *idxOffs; long long idxTotal;
+    UlcxCorpus src;
     int nOut, nSeg; const int32_t *segOffs; const ulcx_segment *seg; int32_t *segStart;
     uint8_t *outPay; long long outPayStride; int32_t *outPayBytes, *outMaxBlock;
     ulcx_index_entry *outIndex; int outIndexStride; int32_t *outIndexBlocks;

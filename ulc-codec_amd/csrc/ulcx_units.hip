@@ -127,6 +127,24 @@ __global__ __launch_bounds__(UT) void k_unit_hfext(const float *sums, const floa
     out[2 * i] = nq; out[2 * i + 1] = nd;
 }
 
+// The view of a corpus (corpus_file, file_block) for the files f < s.nFiles of caller-given tables: out[f][4 + 2 * nk] =
+// {base - s.pay, row - s.index in entries, avail, nI, then {off, ext} of block ks[j], j < nk}.  No payload byte is read (s.pay
+// is only ever an address to count from).  A view whose row leaves the index is not followed: the lookups store -1 (the test's
+// model never has it), so a wrong view fails the test instead of reading outside the caller's buffers.
+__global__ __launch_bounds__(UT) void k_unit_corpus(UlcxCorpus s, const int32_t *ks, int nk, long long *out) {
+    const int f = blockIdx.x * UT + threadIdx.x;
+    if (f >= s.nFiles) return;
+    const CorpusFile cf = corpus_file(s, (size_t)f, s.payOffs != nullptr);
+    long long *o = out + (size_t)f * (4 + 2 * nk);
+    const long long rowAt = cf.row - s.index;
+    o[0] = cf.base - s.pay; o[1] = rowAt; o[2] = cf.avail; o[3] = cf.nI;
+    const bool rowInside = cf.nI >= 0 && rowAt >= 0 && rowAt + cf.nI + (cf.ok ? 1 : 0) <= s.idxTotal;
+    for (int j = 0; j < nk; j++) {
+        const FileBlock b = rowInside ? file_block(cf, ks[j]) : FileBlock{ -1, -1 };
+        o[4 + 2 * j] = b.off; o[5 + 2 * j] = b.ext;
+    }
+}
+
 static int unit_done() {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -210,6 +228,17 @@ int ulcx_units_noise_q(const float *sum, const float *sumw, const float *q, long
     if (n < 0 || n > UNIT_NMAX || !sum || !sumw || !q || !out) return (int)hipErrorInvalidValue;
     if (n == 0) return 0;
     k_unit_noise_q<<<unit_grid(n), UT>>>(sum, sumw, q, n, out);
+    return unit_done();
+}
+// payOffs != NULL: a ragged corpus (payBytes, payStride and indexStride are not looked at), else a strided one (payTotal is not); every table on the
+// device, index of idxTotal entries (strided: nFiles * indexStride); out[nFiles][4 + 2 * nk]
+int ulcx_units_corpus(int nFiles, long long payTotal, long long payStride, const int32_t *payBytes, const int64_t *payOffs, const ulcx_index_entry *index,
+                      long long idxTotal, int indexStride, const int64_t *idxOffs, const int32_t *indexBlocks, const int32_t *ks, int nk, long long *out) {
+    if (nFiles < 1 || nFiles > (1 << 20) || nk < 0 || nk > 64 || !index || !indexBlocks || !ks || !out || idxTotal < 0) return (int)hipErrorInvalidValue;
+    if (payOffs ? !idxOffs : (!payBytes || indexStride < 1 || idxTotal != (long long)nFiles * indexStride)) return (int)hipErrorInvalidValue;
+    UlcxCorpus s = payOffs ? ulcx_corpus_ragged(nFiles, (const uint8_t *)index, payTotal, payOffs, index, idxTotal, idxOffs, indexBlocks)
+                           : ulcx_corpus_strided(nFiles, (const uint8_t *)index, payStride, payBytes, index, indexStride, indexBlocks);
+    k_unit_corpus<<<unit_grid(nFiles), UT>>>(s, ks, nk, out);
     return unit_done();
 }
 int ulcx_units_hfext(const float *sums, const float *q, long long n, int32_t *out) {
