@@ -754,6 +754,69 @@ int  ulcx_decode_crops_spectra_ragged_host(ulcx_decoder *dec, int nFiles,
                                            const int32_t *h_indexBlocks,
                                            int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
                                            int nBlocks, int flags, float *h_coef, int32_t *h_wc, int32_t *h_bits);   /* synchronous */
+/* Distortion: the spectra calls with the coded planes summed on chip against caller-held reference planes instead of written - how
+ * good a coded file is, per (row, channel, block, segment of the spectrum), without a coded plane in HBM.  The reference is
+ * typically the clean spectrum of the same clip on the same grid (ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*, section 2);
+ * with no reference the call is a band-energy extractor of the coded corpus.  The corpus, n, d_file, d_first, d_count, nBlocks,
+ * d_wc, d_bits and hipStream are exactly the spectra calls'; in place of d_coef:
+ *   d_ref      float32 [nRef][nChan][nRefBlocks][BlockSize], laid out as the spectra calls' d_coef, or NULL: no reference (nRef,
+ *              nRefBlocks, d_refRow and d_refFirst are then ignored).  Taken as it is: under ULCX_SPECTRA_LR pass planes made with it.
+ *   d_refRow   int32 [n], optional: the reference row of crop row i (NULL: i).  Several rows may name one reference row.
+ *   d_refFirst int32 [n], optional: the reference block paired with output block 0 of row i (NULL: 0).
+ *   nSeg       segments per block: a power of two, 1 .. 64, with BlockSize / nSeg >= 4.  Segment g covers coefficients
+ *              [g * W, (g + 1) * W), W = BlockSize / nSeg, in CODED order, as the planes are.  Sub-block boundaries of a decimated
+ *              block are multiples of BlockSize / 8: from nSeg >= 8 on every segment lies inside one sub-block.
+ *   flags      0 or ULCX_SPECTRA_LR, with the spectra calls' meaning.
+ *   d_dist     binary64 [n][nChan][nBlocks][nSeg][3] = {S, Y, E}, written in full.  With y[j] the value
+ *              ulcx_decode_crops_spectra_dev writes at d_coef[i][ch][k][j] under the same flags, and
+ *              r[j] = d_ref[d_refRow[i]][ch][d_refFirst[i] + k][j]:   S = sum r^2,  Y = sum y^2,  E = sum (r - y)^2  over the segment.
+ * ARITHMETIC, which is the contract: every term is formed in binary64 from the float32 values - (double)r * (double)r and
+ * (double)y * (double)y (exact), d = (double)r - (double)y (one subtraction), d * d (one multiplication); no contraction; float32
+ * denormals are values, not zeros.  The W terms of a segment are added by the pairwise tree over adjacent elements: level 0 is the
+ * terms, t[l+1][j] = t[l][2j] + t[l][2j+1].  So every result is one defined bit pattern, and the result at nSeg is the pairwise sum
+ * of the results at 2 * nSeg, down to the whole block.
+ * ABSENT REFERENCE: d_ref NULL, a d_refRow[i] outside [0, nRef), or a reference block d_refFirst[i] + k (formed in 64 bits) outside
+ * [0, nRefBlocks) make that block's reference all +0.0f, and nothing is read for it: S = 0 and E = Y.  Both tables are untrusted,
+ * as d_file is.
+ * LIVENESS: d_wc and d_bits are entry for entry the spectra call's, under every rule stated for it.  A block that is not live has
+ * +0.0 in all three sums of every segment, and its reference is not read.  NaN / Inf in the reference stay inside their segment.
+ * STATE / ORDER: the spectra calls' - no stream's persistent state is read or changed, nothing is allocated after the first subset
+ * or crop call, the device forms are asynchronous on hipStream (two kernels: the walk, the reduction; the grid is the spectra
+ * call's).  ULCX_ERR_ARG before any device work for: whatever the spectra call refuses; a bad nSeg; d_dist NULL or not 8-byte
+ * aligned; d_ref not 16-byte aligned; d_ref != NULL with nRef < 1 or nRefBlocks < 1; d_refRow / d_refFirst not 4-byte aligned; a
+ * flag other than ULCX_SPECTRA_LR; and ULCX_SPECTRA_LR at a BlockSize whose two unit arrays do not fit a compute unit's LDS
+ * (32768): left and right cannot be formed on chip there without a plane to park the first channel in.  The mid/side form works
+ * at every BlockSize.  The host forms are synchronous and refuse what the spectra host forms refuse. */
+int  ulcx_decode_crops_distortion_dev(ulcx_decoder *dec, int nFiles,
+                                      const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes /* [nFiles] */,
+                                      const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks /* [nFiles] */,
+                                      int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count /* optional */,
+                                      int nBlocks, const float *d_ref /* optional */, int nRef, int nRefBlocks,
+                                      const int32_t *d_refRow /* optional */, const int32_t *d_refFirst /* optional */, int nSeg, int flags,
+                                      double *d_dist, int32_t *d_wc, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_distortion_host(ulcx_decoder *dec, int nFiles,
+                                       const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                       const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                       int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
+                                       int nBlocks, const float *h_ref, int nRef, int nRefBlocks,
+                                       const int32_t *h_refRow, const int32_t *h_refFirst, int nSeg, int flags,
+                                       double *h_dist, int32_t *h_wc, int32_t *h_bits);   /* synchronous */
+int  ulcx_decode_crops_distortion_ragged_dev(ulcx_decoder *dec, int nFiles,
+                                             const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs /* [nFiles+1] */,
+                                             const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs /* [nFiles+1] */,
+                                             const int32_t *d_indexBlocks /* [nFiles] */,
+                                             int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count /* optional */,
+                                             int nBlocks, const float *d_ref /* optional */, int nRef, int nRefBlocks,
+                                             const int32_t *d_refRow /* optional */, const int32_t *d_refFirst /* optional */, int nSeg, int flags,
+                                             double *d_dist, int32_t *d_wc, int32_t *d_bits, void *hipStream);
+int  ulcx_decode_crops_distortion_ragged_host(ulcx_decoder *dec, int nFiles,
+                                              const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                              const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs,
+                                              const int32_t *h_indexBlocks,
+                                              int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
+                                              int nBlocks, const float *h_ref, int nRef, int nRefBlocks,
+                                              const int32_t *h_refRow, const int32_t *h_refFirst, int nSeg, int flags,
+                                              double *h_dist, int32_t *h_wc, int32_t *h_bits);   /* synchronous */
 /* Synthesis from spectra: the way back - PCM from caller-held MDCT planes, through the decoder's own inverse transform (pre-twiddle,
  * FFT, post-twiddle with the windowed overlap, the centring of decimated sub-blocks, lapping state), the very kernels the crop
  * calls run, with the syntax walk replaced by loads from the planes.  For models that work on the planes of the spectra calls or

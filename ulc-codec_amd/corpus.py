@@ -10,6 +10,8 @@
                                                                   # (dec: max_blocks > ulc_amd.crop_blocks(2048, n_samples))
     coef, wc, bits = corpus.spectra(dec, files, first, n_blocks)  # [n][2][n_blocks][2048]: the dequantised MDCT coefficients
     pcm, live = synth_spectra(dec, coef, wc, warm=True)           # and back: [n][2][(n_blocks - 1) * 2048], plane 0 the block in front
+    dist, wc, bits = corpus.distortion(dec, files, first, n_blocks, ref, n_seg=8)   # [n][2][n_blocks][8][3] float64 {S, Y, E}: the coded
+                                                                  # spectrum summed against reference planes; rung_plan() turns a ladder's into a plan
 
 CropCorpus(..., layout="ragged") keeps every file at its own length (payloads and index rows back to back behind offset tables,
 ulcx_decode_crops_ragged_dev) instead of at the longest file's: the layout for a corpus of files of very different length.
@@ -614,3 +616,86 @@ class CropCorpus:
                                      want.data_ptr() if want is not None else 0, n_blocks, flags, coef.data_ptr(), wc.data_ptr(), bits.data_ptr(),
                                      stream=stream)
         return coef, wc, bits
+
+    def distortion(self, dec, files, first, n_blocks, ref=None, ref_row=None, ref_first=None, count=None, n_seg=1, lr=False):
+        """Row i: spectra()'s coefficients summed on chip against reference planes instead of written
+        (ulcx_decode_crops_distortion_dev): per (row, channel, block, segment of BlockSize / n_seg coefficients) the binary64 sums
+        {S, Y, E} = {reference energy, coded energy, error energy}, added in one fixed order (include/ulc_amd.h).  ref: float32
+        [n_ref][nChan][n_ref_blocks][BlockSize] on the device, typically clip_spectra()'s planes (made with the same `lr`), or None:
+        no reference, S = 0 and E = Y.  ref_row[i]: the reference row of crop row i (None: i); ref_first[i]: the reference block
+        beside output block 0 (None: 0); a row or a block outside the reference counts as zeros.  n_seg: a power of two, 1 .. 64.
+        -> (dist float64 [n][nChan][n_blocks][n_seg][3], wc int32 [n][n_blocks], bits int32 [n][n_blocks]) on the device, enqueued on
+        torch's current stream; a contiguous `ref` is not copied.  `dec`: as for crops(); no stream state of it is read or changed."""
+        import torch
+        if not self.frozen:
+            raise UlcError("corpus: not frozen")
+        if (dec.C, dec.BS) != (self.C, self.BS):
+            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
+        as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=self.device).contiguous()
+        opt = lambda v: None if v is None else as_i32(v)
+        files, first = as_i32(files), as_i32(first)
+        want, row, rfirst = opt(count), opt(ref_row), opt(ref_first)
+        n = files.numel()
+        assert first.numel() == n and all(v is None or v.numel() == n for v in (want, row, rfirst))
+        n_ref = n_ref_blocks = 0
+        if ref is not None:
+            ref = torch.as_tensor(ref, dtype=torch.float32, device=self.device).contiguous()
+            if ref.dim() != 4 or ref.shape[1] != self.C or ref.shape[3] != self.BS:
+                raise UlcError(f"corpus: reference planes of shape {tuple(ref.shape)} for a corpus of {self.BS} x {self.C}")
+            n_ref, n_ref_blocks = ref.shape[0], ref.shape[2]
+        dist = torch.empty((n, self.C, n_blocks, n_seg, 3), dtype=torch.float64, device=self.device)
+        wc = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        ptr = lambda v: v.data_ptr() if v is not None else 0
+        tail = (n, files.data_ptr(), first.data_ptr(), ptr(want), n_blocks, ptr(ref), n_ref, n_ref_blocks, ptr(row), ptr(rfirst), int(n_seg),
+                ulc_amd.SPECTRA_LR if lr else 0, dist.data_ptr(), wc.data_ptr(), bits.data_ptr())
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.ragged:
+            dec.decode_crops_distortion_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
+                                                   self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
+                                                   *tail, stream=stream)
+        else:
+            dec.decode_crops_distortion_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
+                                            self.index_stride, self.d_index_blocks.data_ptr(), *tail, stream=stream)
+        return dist, wc, bits
+
+
+def rung_plan(dist_by_rung, blocks, target_db):
+    """The plan CropCorpus.switch() takes, from the distortion of every rung of a ladder: dist_by_rung[r][clip][ch][k][seg][3] is
+    CropCorpus.distortion() of file file_of(r, clip) from block 0 against the clip's clean planes (a tensor, or a sequence of
+    one tensor per rung; CPU or device).  A block's SNR is 10 log10(sum S / sum E) over its channels and segments - E = 0: +inf;
+    S = 0 with E > 0: -inf.  Block k of a clip takes the first rung, in the ladder's order, whose SNR reaches target_db, else the
+    last rung; equal neighbours merge.  blocks[clip]: the blocks of the clip (the row's leading ones are planned).
+    -> [[(rung, n_blocks), ...] per clip].  Pure tensor arithmetic in a fixed order - the same plan from the same bits on a CPU
+    and on a device tensor; one transfer of the chosen rungs to the host."""
+    import torch
+    d = dist_by_rung if torch.is_tensor(dist_by_rung) else torch.stack(list(dist_by_rung))
+    if d.dim() != 6 or d.shape[-1] != 3:
+        raise UlcError(f"rung_plan: distortion of shape {tuple(d.shape)}, not [rung][clip][channel][block][segment][3]")
+    if d.shape[4] & (d.shape[4] - 1):
+        raise UlcError(f"rung_plan: {d.shape[4]} segments (a power of two, as the distortion calls give)")
+    # a block's sums in ONE order on every device, so that a plan is a function of the distortion's bits: the segments up the
+    # calls' own pairwise tree, then the channels in order; the target as a ratio, compared without a logarithm
+    t = d.to(torch.float64)[..., (0, 2)]
+    while t.shape[4] > 1:
+        t = t[:, :, :, :, 0::2] + t[:, :, :, :, 1::2]
+    t = t[:, :, :, :, 0]                                                        # [rung][clip][ch][block][2]
+    tot = t[:, :, 0]
+    for ch in range(1, t.shape[2]):
+        tot = tot + t[:, :, ch]
+    S, E = tot[..., 0], tot[..., 1]                                             # [rung][clip][block]
+    ratio = 10.0 ** (float(target_db) / 10.0)                                   # SNR >= target_db  <=>  S >= ratio * E
+    ok = (E == 0) | (S >= ratio * E)                                            # E = 0: +inf reaches; S = 0 with E > 0: -inf does not
+    n_rungs = d.shape[0]
+    first = torch.where(ok.any(dim=0), ok.to(torch.int8).argmax(dim=0), torch.full(ok.shape[1:], n_rungs - 1, dtype=torch.int64, device=d.device))
+    first = first.cpu().numpy()
+    blocks = np.asarray(torch.as_tensor(blocks).cpu() if torch.is_tensor(blocks) else blocks, np.int64).reshape(-1)
+    if blocks.shape[0] != first.shape[0]:
+        raise UlcError(f"rung_plan: {blocks.shape[0]} block counts for {first.shape[0]} clips")
+    plan = []
+    for clip in range(first.shape[0]):
+        row = first[clip, :max(0, min(int(blocks[clip]), first.shape[1]))]
+        cut = np.flatnonzero(np.diff(row)) + 1
+        edges = np.concatenate([[0], cut, [len(row)]])
+        plan.append([(int(row[a]), int(b - a)) for a, b in zip(edges[:-1], edges[1:]) if b > a])
+    return plan

@@ -1389,7 +1389,7 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subse
     a.synGrid = 0; a.synFull = 0;
     c.lapO = c.lap; c.lastSubO = c.lastSub; c.seedO = c.seed; c.deadO = c.dead;
     const int Kc = c.range ? c.K - 1 : c.K;                       // blocks of the call per stream (a range call's K counts the row of the block in front)
-    if (e->splitOK && e->synSlots > 0 && !a.specCoef) {             // (a spectra call has no synthesis to cut: the plain plan)
+    if (e->splitOK && e->synSlots > 0 && !a.specCoef && !a.distOut) {      // (a spectra or distortion call has no synthesis to cut: the plain plan)
         // A range call of more streams than the device holds at once: whole rounds, and the last one cut
         // (ulcx_dec_range_tail_plan) - an even cut of everything ends every workgroup inside a stream, and in a range call every
         // entry into a stream costs the block in front of the range (ULCX_RANGE_CUT=even: the even cut first, as for other calls)
@@ -2013,13 +2013,28 @@ static int spectra_flags_bad(const char *who, int flags) {
     if (flags & ~ULCX_SPECTRA_LR) { refuse(who, "bad argument (flags 0x%x: 0 or ULCX_SPECTRA_LR)", (unsigned)flags); return 1; }
     return 0;
 }
+// the arguments of a distortion call (ulcx_decode_crops_distortion_*) in place of d_coef; the window codes travel in a CropsSpectra
+struct CropsDistortion { const float *ref; int nRef, nRefBlocks; const int32_t *refRow, *refFirst; int nSeg; double *dist; };
+// what a distortion call refuses beyond the spectra call, behind that call's own checks (the object is known by then)
+static int distortion_bad(const char *who, const ulcx_decoder *e, const CropsDistortion &d, int flags, bool host) {
+    const int W = d.nSeg > 0 ? e->BS / d.nSeg : 0;
+    if (d.nSeg < 1 || d.nSeg > 64 || (d.nSeg & (d.nSeg - 1)) || W < 4) { refuse(who, "bad argument (nSeg %d: a power of two, 1 .. 64, with BlockSize / nSeg >= 4)", d.nSeg); return 1; }
+    if (!host && (misaligned(who, "d_dist", d.dist, (int)sizeof(double)) || misaligned(who, "d_ref", d.ref, ULCX_ALIGN_PCM) ||
+                  misaligned(who, "d_refRow", d.refRow, ULCX_ALIGN_WORD) || misaligned(who, "d_refFirst", d.refFirst, ULCX_ALIGN_WORD))) return 1;
+    if (d.ref && (d.nRef < 1 || d.nRefBlocks < 1)) { refuse(who, "bad argument (nRef %d, nRefBlocks %d with a reference)", d.nRef, d.nRefBlocks); return 1; }
+    if ((flags & ULCX_SPECTRA_LR) && ulcx_spec_arrays(e->BS) == 1) {
+        refuse(who, "bad argument (flags: ULCX_SPECTRA_LR at BlockSize %d, where one unit array fills the LDS)", e->BS); return 1;
+    }
+    return 0;
+}
 // samp != NULL: a sample-crop call - the rows come from (start, len), the output is [n][nChan][nSamples] and needs its element's alignment only
 // spec != NULL: a spectra call - d_pcm and d_pcm16 are NULL, the outputs are spec's [n][nChan][nBlocks][BlockSize] and [n][nBlocks]
+// dist != NULL (with spec, whose coef is NULL): a distortion call - the sums of dist in place of the coefficients
 static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count,
                             int nBlocks, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, const CropsSamples *samp = nullptr,
-                            const CropsSpectra *spec = nullptr) {
+                            const CropsSpectra *spec = nullptr, const CropsDistortion *dist = nullptr) {
     if (spec && spectra_flags_bad(who, spec->flags)) return ULCX_ERR_ARG;
-    const void *out = spec ? (spec->wc ? (const void *)spec->coef : nullptr) : d_pcm ? (const void *)d_pcm : d_pcm16;
+    const void *out = spec ? (spec->wc ? (dist ? (const void *)dist->dist : (const void *)spec->coef) : nullptr) : d_pcm ? (const void *)d_pcm : d_pcm16;
     const void *rows = samp ? (const void *)samp->start : d_first;
     if (crops_checks(who, e, g, !d_file || !rows || !out || !d_bits, n, nBlocks)) return ULCX_ERR_ARG;
     if (corpus_misaligned(who, g) || misaligned(who, "d_file", d_file, ULCX_ALIGN_WORD) ||
@@ -2027,6 +2042,7 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &
         misaligned(who, "d_bits", d_bits, ULCX_ALIGN_WORD)) return ULCX_ERR_ARG;
     if (spec && (misaligned(who, "d_coef", spec->coef, ULCX_ALIGN_PCM) || misaligned(who, "d_wc", spec->wc, ULCX_ALIGN_WORD))) return ULCX_ERR_ARG;
     if (spec && (long long)n * nBlocks * ((e->C + 1) / 2) > 0x7FFFFFFFLL) return refuse(who, "bad argument (n x nBlocks x channel pairs exceeds a grid)");
+    if (dist && distortion_bad(who, e, *dist, spec->flags, false)) return ULCX_ERR_ARG;
     // (a plane of a sample crop starts at any sample: the kernels use wider stores only where the address allows them)
     if (samp ? (misaligned(who, "d_start", samp->start, ULCX_ALIGN_OFFS) || misaligned(who, "d_len", samp->len, ULCX_ALIGN_WORD) ||
                 misaligned(who, "d_pcm", d_pcm, (int)sizeof(float)) || misaligned(who, "d_pcm16", d_pcm16, (int)sizeof(int16_t)))
@@ -2047,6 +2063,10 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &
         c.rFirst = crop.sampFirst; crop.cropCount = crop.sampCount;
     }
     if (spec) { crop.specCoef = spec->coef; crop.specWc = spec->wc; crop.specLR = (spec->flags & ULCX_SPECTRA_LR) ? 1 : 0; }
+    if (dist) {
+        crop.distOut = dist->dist; crop.distSeg = dist->nSeg; crop.distRef = dist->ref; crop.distNRef = dist->nRef; crop.distRefBlocks = dist->nRefBlocks;
+        crop.distRefRow = dist->refRow; crop.distRefFirst = dist->refFirst;
+    }
     int set = 0;
     rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &crop);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
@@ -2071,12 +2091,13 @@ static int spectra_wc_down(const int32_t *d_wc, size_t NB, int32_t *h_wc) {
     CKR(hipMemcpy(h_wc, d_wc, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
-// the host forms, either layout: ulcx_decode_crops[_ragged]_host (h_pcm) and ulcx_decode_crops_spectra[_ragged]_host (hspec: h_pcm
-// is its coefficients)
+// the host forms, either layout: ulcx_decode_crops[_ragged]_host (h_pcm), ulcx_decode_crops_spectra[_ragged]_host (hspec: h_pcm
+// is its coefficients) and ulcx_decode_crops_distortion[_ragged]_host (hspec and hdist, all HOST pointers: h_pcm is NULL)
 static int crops_host_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count,
-                          int nBlocks, float *h_pcm, int32_t *h_bits, const CropsSpectra *hspec = nullptr) {
+                          int nBlocks, float *h_pcm, int32_t *h_bits, const CropsSpectra *hspec = nullptr, const CropsDistortion *hdist = nullptr) {
     if (hspec && spectra_flags_bad(who, hspec->flags)) return ULCX_ERR_ARG;
-    if (crops_checks(who, e, g, !h_file || !h_first || (hspec && !hspec->wc) || !h_pcm || !h_bits, n, nBlocks)) return ULCX_ERR_ARG;
+    if (crops_checks(who, e, g, !h_file || !h_first || (hspec && !hspec->wc) || !(hdist ? (const void *)hdist->dist : (const void *)h_pcm) || !h_bits, n, nBlocks)) return ULCX_ERR_ARG;
+    if (hdist && distortion_bad(who, e, *hdist, hspec->flags, true)) return ULCX_ERR_ARG;
     // what the device forms cannot refuse: a ragged corpus's tables, then the rows
     if (g.ragged && ragged_tables_bad(who, g)) return ULCX_ERR_ARG;
     for (int i = 0; i < n; i++) {
@@ -2091,14 +2112,33 @@ static int crops_host_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g,
     int rc = corpus_up(t, g, &d);
     if (rc) return rc;
     CKR(t.get(&dfile, sizeof(int32_t) * n)); CKR(t.get(&df, sizeof(int32_t) * n));
-    CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS)); CKR(t.get(&dbits, sizeof(int32_t) * NB));
+    if (!hdist) CKR(t.get(&dpcm, sizeof(float) * NB * (size_t)e->C * e->BS));
+    CKR(t.get(&dbits, sizeof(int32_t) * NB));
     CKR(hipMemcpy(dfile, h_file, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     CKR(hipMemcpy(df, h_first, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     if (h_count) { CKR(t.get(&dwant, sizeof(int32_t) * n)); CKR(hipMemcpy(dwant, h_count, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
     CropsSpectra ds = {};
     if (hspec) { ds.coef = dpcm; ds.flags = hspec->flags; CKR(t.get(&ds.wc, sizeof(int32_t) * NB)); }
-    rc = decode_crops_any(who, e, d, n, dfile, df, dwant, nBlocks, hspec ? nullptr : dpcm, nullptr, dbits, nullptr, nullptr, hspec ? &ds : nullptr);
-    if (!rc) rc = dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
+    CropsDistortion dd = {};
+    const size_t nDist = NB * (size_t)e->C * (hdist ? hdist->nSeg : 0) * 3;
+    if (hdist) {                                                  // the reference and its two tables up, the sums' buffer
+        dd = *hdist; dd.ref = nullptr; dd.refRow = dd.refFirst = nullptr;
+        CKR(t.get(&dd.dist, sizeof(double) * nDist));
+        if (hdist->ref) {
+            const size_t nRefF = (size_t)hdist->nRef * e->C * hdist->nRefBlocks * e->BS;
+            float *dref = nullptr; int32_t *drow = nullptr, *dfirst = nullptr;
+            CKR(t.get(&dref, sizeof(float) * nRefF)); CKR(hipMemcpy(dref, hdist->ref, sizeof(float) * nRefF, hipMemcpyHostToDevice));
+            if (hdist->refRow) { CKR(t.get(&drow, sizeof(int32_t) * n)); CKR(hipMemcpy(drow, hdist->refRow, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
+            if (hdist->refFirst) { CKR(t.get(&dfirst, sizeof(int32_t) * n)); CKR(hipMemcpy(dfirst, hdist->refFirst, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
+            dd.ref = dref; dd.refRow = drow; dd.refFirst = dfirst;
+        }
+    }
+    rc = decode_crops_any(who, e, d, n, dfile, df, dwant, nBlocks, hspec ? nullptr : dpcm, nullptr, dbits, nullptr, nullptr, hspec ? &ds : nullptr, hdist ? &dd : nullptr);
+    if (!rc && hdist) {
+        CKR(hipDeviceSynchronize());
+        CKR(hipMemcpy(hdist->dist, dd.dist, sizeof(double) * nDist, hipMemcpyDeviceToHost));
+        CKR(hipMemcpy(h_bits, dbits, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
+    } else if (!rc) rc = dec_results_down(e, dpcm, dbits, NB, h_pcm, h_bits);
     return (rc || !hspec) ? rc : spectra_wc_down(ds.wc, NB, hspec->wc);
 }
 extern "C" int ulcx_decode_crops_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
@@ -2210,6 +2250,47 @@ extern "C" int ulcx_decode_crops_spectra_ragged_host(ulcx_decoder *e, int nFiles
     const CropsSpectra sp = { h_coef, h_wc, flags };
     return crops_host_any("ulcx_decode_crops_spectra_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
                           n, h_file, h_first, h_count, nBlocks, h_coef, h_bits, &sp);
+}
+// ---- distortion (include/ulc_amd.h section 3): the spectra calls' bodies, ending in the sums against reference planes instead of the coefficients.
+extern "C" int ulcx_decode_crops_distortion_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                                const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                                int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
+                                                const float *d_ref, int nRef, int nRefBlocks, const int32_t *d_refRow, const int32_t *d_refFirst, int nSeg, int flags,
+                                                double *d_dist, int32_t *d_wc, int32_t *d_bits, void *hipStream) {
+    const CropsSpectra sp = { nullptr, d_wc, flags };
+    const CropsDistortion di = { d_ref, nRef, nRefBlocks, d_refRow, d_refFirst, nSeg, d_dist };
+    return decode_crops_any("ulcx_decode_crops_distortion_dev", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                            n, d_file, d_first, d_count, nBlocks, nullptr, nullptr, d_bits, hipStream, nullptr, &sp, &di);
+}
+extern "C" int ulcx_decode_crops_distortion_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                       const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                       int n, const int32_t *d_file, const int32_t *d_first, const int32_t *d_count, int nBlocks,
+                                                       const float *d_ref, int nRef, int nRefBlocks, const int32_t *d_refRow, const int32_t *d_refFirst, int nSeg, int flags,
+                                                       double *d_dist, int32_t *d_wc, int32_t *d_bits, void *hipStream) {
+    const CropsSpectra sp = { nullptr, d_wc, flags };
+    const CropsDistortion di = { d_ref, nRef, nRefBlocks, d_refRow, d_refFirst, nSeg, d_dist };
+    return decode_crops_any("ulcx_decode_crops_distortion_ragged_dev", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                            n, d_file, d_first, d_count, nBlocks, nullptr, nullptr, d_bits, hipStream, nullptr, &sp, &di);
+}
+extern "C" int ulcx_decode_crops_distortion_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                                 const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                                 int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                                                 const float *h_ref, int nRef, int nRefBlocks, const int32_t *h_refRow, const int32_t *h_refFirst, int nSeg, int flags,
+                                                 double *h_dist, int32_t *h_wc, int32_t *h_bits) {
+    const CropsSpectra sp = { nullptr, h_wc, flags };
+    const CropsDistortion di = { h_ref, nRef, nRefBlocks, h_refRow, h_refFirst, nSeg, h_dist };
+    return crops_host_any("ulcx_decode_crops_distortion_host", e, ulcx_corpus_strided(nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks),
+                          n, h_file, h_first, h_count, nBlocks, nullptr, h_bits, &sp, &di);
+}
+extern "C" int ulcx_decode_crops_distortion_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                                        const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                                        int n, const int32_t *h_file, const int32_t *h_first, const int32_t *h_count, int nBlocks,
+                                                        const float *h_ref, int nRef, int nRefBlocks, const int32_t *h_refRow, const int32_t *h_refFirst, int nSeg, int flags,
+                                                        double *h_dist, int32_t *h_wc, int32_t *h_bits) {
+    const CropsSpectra sp = { nullptr, h_wc, flags };
+    const CropsDistortion di = { h_ref, nRef, nRefBlocks, h_refRow, h_refFirst, nSeg, h_dist };
+    return crops_host_any("ulcx_decode_crops_distortion_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
+                          n, h_file, h_first, h_count, nBlocks, nullptr, h_bits, &sp, &di);
 }
 // ---- sample crops (include/ulc_amd.h section 3): the crop families' bodies with rows given in samples and the output channels-first.
 extern "C" int ulcx_crop_blocks(int BlockSize, int nSamples) {

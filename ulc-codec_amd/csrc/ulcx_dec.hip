@@ -19,6 +19,8 @@
 //   k_dgen    every other geometry (mono, multichannel, BlockSize > 4096): same pieces, one array.
 //   k_dspec   spectra calls (ulcx_decode_crops_spectra_*): in place of the synthesis - the dequantised coefficients themselves,
 //             one workgroup per (row, block, channel pair), stored channels-first; the one call whose coefficients do reach HBM.
+//   k_ddist   distortion calls (ulcx_decode_crops_distortion_*): k_dspec's grid and expansion, and in place of its stores binary64
+//             sums of the coefficients against caller-held reference planes, per segment of the block, in one fixed order.
 // Compiled with -ffp-contract=off (see ulcx_enc.hip).
 #include "ulcx_internal.h"
 #include "ulcx_dec_dev.h"
@@ -1818,20 +1820,32 @@ __device__ __forceinline__ f32x4 spec_ld4(const float *A, int i) {
     f32x4 v = { a.x, a.y, b.x, b.y };
     return v;
 }
-template <bool LR>
-__global__ __launch_bounds__(WG) void k_dspec(UlcxDecCtx c, UlcxSpecArg sp) {
-    static_assert(DPS == 4, "k_dspec: a unit's offset (a multiple of 32) and four consecutive floats stay clear of the padding gaps");
-    extern __shared__ float lds[];
-    const int BS = c.BS, C = c.C, N = c.K - 1;
+// A workgroup of the expansion kernels (k_dspec, k_ddist) and its block: spec_where() is the grid - (row, output block, channel
+// pair), pair fastest - and spec_block() the part those kernels share behind it: the block's liveness and its d_bits / d_wc
+// entries, the generator jump, and the expansion of a channel's units into a padded array.  A dead block ends in onDead(cell), a
+// live one in onLive(cell, dequant): cell is (row, first channel of the pair, output block) as an index of [c.B][C][c.K - 1], where
+// the kernel's output lies, and dequant(ch, A) channel ch of the block into the array A, run by one wave.
+struct SpecWg { int s, kOut, ch0, wv, lane; bool pair, two; SpecLds L; unsigned pr; };
+__device__ __forceinline__ SpecWg spec_where(const UlcxDecCtx &c, int nPairs) {
+    static_assert(DPS == 4, "spec_where: a unit's offset (a multiple of 32) and four consecutive floats stay clear of the padding gaps");
+    const int C = c.C, N = c.K - 1;
     const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const SpecLds L = spec_lds(BS);
-    const bool two = L.nArr == 2;
-    const unsigned pr = blockIdx.x % (unsigned)sp.nPairs, rb = blockIdx.x / (unsigned)sp.nPairs;
-    const int kOut = (int)(rb % (unsigned)N), s = (int)(rb / (unsigned)N), k = kOut + 1;
+    SpecWg w;
+    w.wv = __builtin_amdgcn_readfirstlane(tid >> 6); w.lane = tid & 63;
+    w.L = spec_lds(c.BS);
+    w.two = w.L.nArr == 2;
+    const unsigned rb = blockIdx.x / (unsigned)nPairs;
+    w.pr = blockIdx.x % (unsigned)nPairs;
+    w.kOut = (int)(rb % (unsigned)N); w.s = (int)(rb / (unsigned)N);
+    w.ch0 = 2 * (int)w.pr;
+    w.pair = w.ch0 + 1 < C;
+    return w;
+}
+template <typename DEAD, typename LIVE>
+__device__ __forceinline__ void spec_block(const UlcxDecCtx &c, const SpecWg &w, int32_t *wcOut, float *lds, DEAD &&onDead, LIVE &&onLive) {
+    const int BS = c.BS, C = c.C, N = c.K - 1;
+    const int tid = threadIdx.x, lane = w.lane, s = w.s, k = w.kOut + 1;
     const int blk = s * c.K + k;
-    const int ch0 = 2 * (int)pr;
-    const bool pair = ch0 + 1 < C;
     // entering the block: liveness and the draws of the walked rows in front (k_dsyn's RANGE entry; at most maxBlocksPerCall terms)
     const int2 ri = c.rInfo[s];
     int bad = 0; uint32_t dsum = 0;
@@ -1841,14 +1855,11 @@ __global__ __launch_bounds__(WG) void k_dspec(UlcxDecCtx c, UlcxSpecArg sp) {
         if (j < k) dsum += (uint32_t)c.draws[bj];
     }
     const bool dead = __ballot(bad) != 0ull;                     // (each wave for itself, both the same: uniform over the workgroup)
-    const size_t oblk = (size_t)s * N + kOut;
+    const size_t oblk = (size_t)s * N + w.kOut;
     const int wc = dead ? 0 : c.wcScan[blk];
-    if (pr == 0 && tid == 0) { c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; sp.wc[oblk] = wc; }
-    float *pl0 = sp.coef + (((size_t)s * C + ch0) * N + kOut) * BS, *pl1 = pl0 + (size_t)N * BS;     // the pair's planes
-    if (dead) {
-        for (int i = 4 * tid; i < BS; i += 4 * WG) { st4(pl0 + i, 0.0f, 0.0f, 0.0f, 0.0f); if (pair) st4(pl1 + i, 0.0f, 0.0f, 0.0f, 0.0f); }
-        return;
-    }
+    if (w.pr == 0 && tid == 0) { c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; wcOut[oblk] = wc; }
+    const size_t cell = ((size_t)s * C + w.ch0) * N + w.kOut;
+    if (dead) { onDead(cell); return; }
     const uint32_t seed = rng_jump(c.jumpT, (uint32_t)ri.y, (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add(dsum), 63));
     const int *udraw = c.unitDraws + (size_t)blk * C * 4;
     const int4 *urec = c.unitRec + (size_t)blk * C * 4;
@@ -1859,7 +1870,7 @@ __global__ __launch_bounds__(WG) void k_dspec(UlcxDecCtx c, UlcxSpecArg sp) {
     const int nsub = shape.nsub;
     auto unit_draws = [&](int ch, int j) { return ((j + 1 < nsub) ? udraw[ch * 4 + j + 1] : (ch + 1 < C) ? udraw[(ch + 1) * 4] : c.draws[blk]) - udraw[ch * 4 + j]; };
     SynWave sw;
-    sw.pre = (int *)(lds + (size_t)L.nArr * L.arrFloats) + (two ? wv : 0) * L.listInts;
+    sw.pre = (int *)(lds + (size_t)w.L.nArr * w.L.arrFloats) + (w.two ? w.wv : 0) * w.L.listInts;
     sw.seedTab = (uint32_t *)(sw.pre + 64);
     sw.lane = lane;
 #ifdef ULCX_DSYN_STAMPS
@@ -1876,50 +1887,168 @@ __global__ __launch_bounds__(WG) void k_dspec(UlcxDecCtx c, UlcxSpecArg sp) {
             off += S;
         }
     };
-    if (two) {
-        float *A = lds + (size_t)wv * L.arrFloats;
-        const bool mine = wv == 0 || pair;
-        if (mine) dequant(ch0 + wv, A);
-        float *pl = wv ? pl1 : pl0;
-        if (LR && pair) {
-            __syncthreads();
-            const float *Am = lds, *As = lds + L.arrFloats;
-            for (int i = 4 * lane; i < BS; i += 256) {
-                const f32x4 m = spec_ld4(Am, i), sd = spec_ld4(As, i);                   // ulcDecoder.c:281-289, on the coefficients
-                if (wv == 0) st4(pl + i, m.x + sd.x, m.y + sd.y, m.z + sd.z, m.w + sd.w);
-                else         st4(pl + i, m.x - sd.x, m.y - sd.y, m.z - sd.z, m.w - sd.w);
+    onLive(cell, dequant);
+}
+template <bool LR>
+__global__ __launch_bounds__(WG) void k_dspec(UlcxDecCtx c, UlcxSpecArg sp) {
+    extern __shared__ float lds[];
+    const int BS = c.BS, N = c.K - 1;
+    const int tid = threadIdx.x;
+    const SpecWg w = spec_where(c, sp.nPairs);
+    const int wv = w.wv, lane = w.lane, ch0 = w.ch0;
+    const bool pair = w.pair;
+    const SpecLds L = w.L;
+    spec_block(c, w, sp.wc, lds, [&](size_t cell) {
+        float *pl0 = sp.coef + cell * BS, *pl1 = pl0 + (size_t)N * BS;                     // the pair's planes
+        for (int i = 4 * tid; i < BS; i += 4 * WG) { st4(pl0 + i, 0.0f, 0.0f, 0.0f, 0.0f); if (pair) st4(pl1 + i, 0.0f, 0.0f, 0.0f, 0.0f); }
+    }, [&](size_t cell, auto &dequant) {
+        float *pl0 = sp.coef + cell * BS, *pl1 = pl0 + (size_t)N * BS;
+        if (w.two) {
+            float *A = lds + (size_t)wv * L.arrFloats;
+            const bool mine = wv == 0 || pair;
+            if (mine) dequant(ch0 + wv, A);
+            float *pl = wv ? pl1 : pl0;
+            if (LR && pair) {
+                __syncthreads();
+                const float *Am = lds, *As = lds + L.arrFloats;
+                for (int i = 4 * lane; i < BS; i += 256) {
+                    const f32x4 m = spec_ld4(Am, i), sd = spec_ld4(As, i);                   // ulcDecoder.c:281-289, on the coefficients
+                    if (wv == 0) st4(pl + i, m.x + sd.x, m.y + sd.y, m.z + sd.z, m.w + sd.w);
+                    else         st4(pl + i, m.x - sd.x, m.y - sd.y, m.z - sd.z, m.w - sd.w);
+                }
+            } else if (mine) {
+                for (int i = 4 * lane; i < BS; i += 256) { const f32x4 v = spec_ld4(A, i); st4(pl + i, v.x, v.y, v.z, v.w); }
             }
-        } else if (mine) {
-            for (int i = 4 * lane; i < BS; i += 256) { const f32x4 v = spec_ld4(A, i); st4(pl + i, v.x, v.y, v.z, v.w); }
+        } else {
+            float *A = lds;
+            if (wv == 0) dequant(ch0, A);
+            __syncthreads();
+            for (int i = 4 * tid; i < BS; i += 4 * WG) {
+                const f32x4 v = spec_ld4(A, i);
+                if (LR && pair) *(f32x4 *)(pl0 + i) = v;                                      // (read again below: not non-temporal)
+                else st4(pl0 + i, v.x, v.y, v.z, v.w);
+            }
+            if (!pair) return;
+            if (LR) __threadfence();
+            __syncthreads();                                                                  // the array is free again; LR: plane 0 is visible
+            if (wv == 0) dequant(ch0 + 1, A);
+            __syncthreads();
+            for (int i = 4 * tid; i < BS; i += 4 * WG) {
+                const f32x4 sd = spec_ld4(A, i);
+                if (LR) {
+                    const f32x4 m = *(const f32x4 *)(pl0 + i);
+                    st4(pl0 + i, m.x + sd.x, m.y + sd.y, m.z + sd.z, m.w + sd.w);
+                    st4(pl1 + i, m.x - sd.x, m.y - sd.y, m.z - sd.z, m.w - sd.w);
+                } else st4(pl1 + i, sd.x, sd.y, sd.z, sd.w);
+            }
         }
-    } else {
-        float *A = lds;
-        if (wv == 0) dequant(ch0, A);
-        __syncthreads();
-        for (int i = 4 * tid; i < BS; i += 4 * WG) {
-            const f32x4 v = spec_ld4(A, i);
-            if (LR && pair) *(f32x4 *)(pl0 + i) = v;                                      // (read again below: not non-temporal)
-            else st4(pl0 + i, v.x, v.y, v.z, v.w);
-        }
-        if (!pair) return;
-        if (LR) __threadfence();
-        __syncthreads();                                                                  // the array is free again; LR: plane 0 is visible
-        if (wv == 0) dequant(ch0 + 1, A);
-        __syncthreads();
-        for (int i = 4 * tid; i < BS; i += 4 * WG) {
-            const f32x4 sd = spec_ld4(A, i);
-            if (LR) {
-                const f32x4 m = *(const f32x4 *)(pl0 + i);
-                st4(pl0 + i, m.x + sd.x, m.y + sd.y, m.z + sd.z, m.w + sd.w);
-                st4(pl1 + i, m.x - sd.x, m.y - sd.y, m.z - sd.z, m.w - sd.w);
-            } else st4(pl1 + i, sd.x, sd.y, sd.z, sd.w);
-        }
+    });
+}
+
+// ---------------------------------------------------------------------------
+// Distortion (ulcx_decode_crops_distortion_*): k_dspec's sibling that loads where k_dspec stores.  Behind the same entry and the
+// same expansion into the padded arrays, each channel's BS coefficients y and the caller's reference plane r (16 bytes per lane,
+// non-temporal; absent: +0.0f, nothing read) give per segment of W = BS / nSeg coefficients the sums S = r^2, Y = y^2,
+// E = (r - y)^2, every term formed in binary64 and added by THE PAIRWISE TREE OVER ADJACENT ELEMENTS, so the result is one
+// defined bit pattern (include/ulc_amd.h).  One wave per channel:
+//   lane l of run q (256 coefficients) holds elements 256 q + 4 l .. + 3: (t0 + t1) + (t2 + t3), the tree's levels 1 and 2;
+//   xor butterflies over 1, 2, 4, .. lanes are its levels up to a run (IEEE addition is commutative: both partners of a step
+//   hold the node's bits).  W <= 256: the butterfly stops at W / 4 lanes and the first lane of each group stores.
+//   W > 256: lane q & 63 keeps run q's total (runs 64 .. 127 of BlockSize 32768 in a second set), and a second butterfly over
+//   the kept totals is the tree from a run up to the segment; 128 runs per segment: the two sets' totals added.
+// two = 0 (BlockSize 32768, mid/side only: LR is refused by the API): wave 0 takes the pair's channels one after the other
+// through the one array.  Dead blocks: +0.0 in every sum.  Every entry of the block's [channel][nSeg][3] is stored exactly once.
+// ---------------------------------------------------------------------------
+struct UlcxDistArg { const float *ref; int nRef, nRefBlocks; const int32_t *refRow, *refFirst; int nSeg; double *dist; int32_t *wc; int nPairs; };
+struct Dist3 { double S, Y, E; };
+__device__ __forceinline__ Dist3 dist_terms(const f32x4 r, const f32x4 y) {
+    const double r0 = r.x, r1 = r.y, r2 = r.z, r3 = r.w, y0 = y.x, y1 = y.y, y2 = y.z, y3 = y.w;
+    const double d0 = r0 - y0, d1 = r1 - y1, d2 = r2 - y2, d3 = r3 - y3;
+    Dist3 t;
+    t.S = (r0 * r0 + r1 * r1) + (r2 * r2 + r3 * r3);
+    t.Y = (y0 * y0 + y1 * y1) + (y2 * y2 + y3 * y3);
+    t.E = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    return t;
+}
+__device__ __forceinline__ void dist_xor(Dist3 &t, int m) { t.S += __shfl_xor(t.S, m); t.Y += __shfl_xor(t.Y, m); t.E += __shfl_xor(t.E, m); }
+__device__ __forceinline__ void dist_store(double *p, const Dist3 &t) { p[0] = t.S; p[1] = t.Y; p[2] = t.E; }
+// one wave, one channel: y4(i) the channel's coefficients [i, i + 4), rp its reference plane or NULL, out its [nSeg][3]
+template <typename Y4>
+__device__ __forceinline__ void dist_channel(int BS, int nSeg, int lane, const float *rp, double *out, Y4 &&y4) {
+    const int W = BS / nSeg;
+    const int group = W / 4 < 64 ? W / 4 : 64;                   // lanes of a run that share a segment
+    const f32x4 zero = { 0.0f, 0.0f, 0.0f, 0.0f };
+    Dist3 k0 = { 0.0, 0.0, 0.0 }, k1 = { 0.0, 0.0, 0.0 };
+    f32x4 rn = rp ? __builtin_nontemporal_load((const f32x4 *)(rp + 4 * lane)) : zero;
+    for (int i = 4 * lane, q = 0; i < BS; i += 256, q++) {
+        const f32x4 r = rn;
+        if (rp && i + 256 < BS) rn = __builtin_nontemporal_load((const f32x4 *)(rp + i + 256));
+        Dist3 t = dist_terms(r, y4(i));
+        for (int m = 1; m < group; m <<= 1) dist_xor(t, m);
+        if (W <= 256) { if (!(lane & (group - 1))) dist_store(out + 3 * (size_t)(i / W), t); }
+        else if (lane == (q & 63)) { if (q < 64) k0 = t; else k1 = t; }
     }
+    if (W <= 256) return;
+    const int runs = W / 256, R = BS / 256;                      // runs per segment (2 .. 128), runs of the block
+    const int span = runs < 64 ? runs : 64;
+    for (int m = 1; m < span; m <<= 1) { dist_xor(k0, m); if (R > 64) dist_xor(k1, m); }
+    if (runs == 128) {
+        if (lane == 0) { const Dist3 t = { k0.S + k1.S, k0.Y + k1.Y, k0.E + k1.E }; dist_store(out, t); }
+    } else if (lane < (R < 64 ? R : 64) && !(lane & (span - 1))) {
+        dist_store(out + 3 * (size_t)(lane / runs), k0);
+        if (R > 64) dist_store(out + 3 * (size_t)((64 + lane) / runs), k1);
+    }
+}
+template <bool LR>
+__global__ __launch_bounds__(WG) void k_ddist(UlcxDecCtx c, UlcxDistArg da) {
+    extern __shared__ float lds[];
+    const int BS = c.BS, N = c.K - 1, nSeg = da.nSeg;
+    const int tid = threadIdx.x;
+    const SpecWg w = spec_where(c, da.nPairs);
+    const int wv = w.wv, lane = w.lane, ch0 = w.ch0;
+    const bool pair = w.pair;
+    const SpecLds L = w.L;
+    const size_t och = (size_t)N * nSeg * 3, rch = (size_t)da.nRefBlocks * BS;             // from a channel to the next one: sums, reference
+    spec_block(c, w, da.wc, lds, [&](size_t cell) {
+        double *o0 = da.dist + cell * nSeg * 3;                                            // the pair's sums: these and the ones och behind
+        for (int i = tid; i < 3 * nSeg; i += WG) { o0[i] = 0.0; if (pair) o0[och + i] = 0.0; }
+    }, [&](size_t cell, auto &dequant) {
+        double *o0 = da.dist + cell * nSeg * 3;
+        // the block's reference planes: absent without d_ref, for a row or a block outside the reference (the index in 64 bits)
+        const float *rp = nullptr;
+        if (da.ref) {
+            const int row = da.refRow ? da.refRow[w.s] : w.s;
+            const long long rb = (long long)(da.refFirst ? da.refFirst[w.s] : 0) + w.kOut;
+            if (row >= 0 && row < da.nRef && rb >= 0 && rb < da.nRefBlocks) rp = da.ref + (((size_t)row * c.C + ch0) * da.nRefBlocks + (size_t)rb) * BS;
+        }
+        if (w.two) {
+            float *A = lds + (size_t)wv * L.arrFloats;
+            const bool mine = wv == 0 || pair;
+            if (mine) dequant(ch0 + wv, A);
+            const float *rw = rp ? rp + wv * rch : nullptr;
+            if (LR && pair) {
+                __syncthreads();
+                const float *Am = lds, *As = lds + L.arrFloats;
+                dist_channel(BS, nSeg, lane, rw, o0 + wv * och, [&](int i) {
+                    const f32x4 m = spec_ld4(Am, i), sd = spec_ld4(As, i);                   // what k_dspec<true> stores
+                    const f32x4 l = { m.x + sd.x, m.y + sd.y, m.z + sd.z, m.w + sd.w }, r = { m.x - sd.x, m.y - sd.y, m.z - sd.z, m.w - sd.w };
+                    return wv == 0 ? l : r;
+                });
+            } else if (mine) dist_channel(BS, nSeg, lane, rw, o0 + wv * och, [&](int i) { return spec_ld4(A, i); });
+        } else if (wv == 0) {
+            float *A = lds;
+            for (int h = 0; h < (pair ? 2 : 1); h++) {
+                dequant(ch0 + h, A);
+                dist_channel(BS, nSeg, lane, rp ? rp + h * rch : nullptr, o0 + h * och, [&](int i) { return spec_ld4(A, i); });
+            }
+        }
+    });
 }
 size_t ulcx_spec_lds_bytes(int BS) {
     const SpecLds l = spec_lds(BS);
     return sizeof(float) * (size_t)l.nArr * ((size_t)l.arrFloats + l.listInts);
 }
+int ulcx_spec_arrays(int BS) { return spec_lds(BS).nArr; }
 
 size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds) {
     DsynLds l = dsyn_lds(BS, fast, twInLds);
@@ -1983,8 +2112,9 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     const bool split = c.fastOK && aux.synGrid > 0;
     const bool samp = aux.sampStart != nullptr;                       // a sample-crop call: rows from (start, len) first, then the crop walk on them
     const bool spec = aux.specCoef != nullptr;                        // a spectra call: the crop walk, then k_dspec in place of the synthesis
+    const bool dist = aux.distOut != nullptr;                         // a distortion call: the crop walk, then k_ddist in place of the synthesis
     const int plane = aux.synCoef ? (aux.synLR ? 2 : 1) : 0;          // a synth call: k_synth_rows in place of every walk, then the plane source synthesis
-    const void *syn = spec ? nullptr : c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp, plane) : syn_fn<float>(c, split, c.range != 0, samp, plane);
+    const void *syn = (spec || dist) ? nullptr : c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp, plane) : syn_fn<float>(c, split, c.range != 0, samp, plane);
     if (syn) CK(allow_lds(syn, lds));
     if (plane) hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)(((long long)c.B * c.K + 63) / 64)), dim3(64), 0, st, c.B, c.K, aux.synPlanes, aux.synWc,
                                   c.wcScan, c.draws, c.bits, c.rInfo, aux.sampSkip, aux.sampLenC, aux.nSamples);
@@ -1999,15 +2129,17 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));
-    if (spec) {
-        const void *fn = aux.specLR ? (const void *)k_dspec<true> : (const void *)k_dspec<false>;
+    if (spec || dist) {
+        const void *fn = dist ? (aux.specLR ? (const void *)k_ddist<true> : (const void *)k_ddist<false>)
+                              : (aux.specLR ? (const void *)k_dspec<true> : (const void *)k_dspec<false>);
         const size_t slds = ulcx_spec_lds_bytes(c.BS);
         const int nPairs = (c.C + 1) / 2;
         const long long g = (long long)c.B * (c.K - 1) * nPairs;
-        if (g > 0x7FFFFFFFLL) { ulcx_set_error("spectra call: %lld workgroups", g); return ULCX_ERR_ARG; }
+        if (g > 0x7FFFFFFFLL) { ulcx_set_error("%s call: %lld workgroups", dist ? "distortion" : "spectra", g); return ULCX_ERR_ARG; }
         CK(allow_lds(fn, slds));
         UlcxSpecArg sp = { aux.specCoef, aux.specWc, nPairs };
-        void *args[] = { &c, &sp };
+        UlcxDistArg da = { aux.distRef, aux.distNRef, aux.distRefBlocks, aux.distRefRow, aux.distRefFirst, aux.distSeg, aux.distOut, aux.specWc, nPairs };
+        void *args[] = { &c, dist ? (void *)&da : (void *)&sp };
         CK(hipLaunchKernel(fn, dim3((unsigned)g), dim3(WG), args, slds, st));
     } else if (!(ULCX_DBG(c) & 8)) {
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;

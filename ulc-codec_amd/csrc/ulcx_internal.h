@@ -259,6 +259,12 @@ struct UlcxDecAux {
     float *specCoef = nullptr;           // [c.B][C][c.K - 1][BS] dequantised coefficients, channels-first
     int32_t *specWc = nullptr;           // [c.B][c.K - 1] window codes (0: the block is not live)
     int specLR = 0;                      // channel pairs as m + s, m - s
+    // distortion (ulcx_decode_crops_distortion_*): distOut != NULL - k_ddist in place of k_dspec, on the same grid: the sums of the
+    // coefficients against the caller's reference planes instead of the coefficients; specCoef is NULL, specWc and specLR as above
+    double *distOut = nullptr;           // [c.B][C][c.K - 1][distSeg][3] {S, Y, E}
+    const float *distRef = nullptr;      // [distNRef][C][distRefBlocks][BS] reference planes, or NULL: none
+    int distNRef = 0, distRefBlocks = 0, distSeg = 0;
+    const int32_t *distRefRow = nullptr, *distRefFirst = nullptr;       // [c.B] optional, untrusted: the reference row / first reference block of each row
     // synthesis from spectra (ulcx_synth_spectra_*): synCoef != NULL - no walk at all; k_synth_rows turns the caller's window codes
     // into the per-block rows a range synthesis reads (and sampSkip / sampLenC; nSamples = the output blocks x BlockSize), and the
     // synthesis is the sample-store instantiation with the plane source.  nFiles is 0, c.in is not looked at.
@@ -287,7 +293,8 @@ struct UlcxSpliceArgs {
 };
 int ulcx_splice_launch(const UlcxDecCtx &c, const UlcxSpliceArgs &a, hipStream_t st);
 size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds);
-size_t ulcx_spec_lds_bytes(int BS);               // k_dspec's dynamic LDS: two unit arrays where a CU holds them, else one
+size_t ulcx_spec_lds_bytes(int BS);               // k_dspec's / k_ddist's dynamic LDS: two unit arrays where a CU holds them, else one
+int ulcx_spec_arrays(int BS);                     // how many that is (1: ULCX_SPECTRA_LR cannot be formed on chip by k_ddist)
 int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);

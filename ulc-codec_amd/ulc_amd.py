@@ -54,6 +54,8 @@ EXPORTS = [
     "ulcx_encode_clips_ladder_dev", "ulcx_encode_clips_ladder_dev_pcm16", "ulcx_encode_clips_ladder_host",
     "ulcx_synth_spectra_dev", "ulcx_synth_spectra_dev_pcm16", "ulcx_synth_spectra_host",
     "ulcx_corpus_splice_dev", "ulcx_corpus_splice_ragged_dev", "ulcx_corpus_splice_host", "ulcx_corpus_splice_ragged_host",
+    "ulcx_decode_crops_distortion_dev", "ulcx_decode_crops_distortion_host",
+    "ulcx_decode_crops_distortion_ragged_dev", "ulcx_decode_crops_distortion_ragged_host",
 ]
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -238,6 +240,14 @@ def lib():
                                                                C.c_void_p, C.c_void_p]
             l.ulcx_decode_crops_spectra_ragged_host.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_longlong, _i64p, C.c_void_p, C.c_longlong, _i64p, _i32p,
                                                                 C.c_int, _i32p, _i32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p]
+        if hasattr(l, "ulcx_decode_crops_distortion_dev"): # distortion: binary64 sums of crop rows' coefficients against reference planes
+            # behind the rows: d_ref, nRef, nRefBlocks, d_refRow, d_refFirst, nSeg, flags, d_dist, d_wc, d_bits
+            dist_dev = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            dist_host = [_f32p, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.POINTER(C.c_double), _i32p, _i32p]
+            l.ulcx_decode_crops_distortion_dev.argtypes = l.ulcx_decode_crops_spectra_dev.argtypes[:13] + dist_dev + [C.c_void_p]
+            l.ulcx_decode_crops_distortion_host.argtypes = l.ulcx_decode_crops_spectra_host.argtypes[:13] + dist_host
+            l.ulcx_decode_crops_distortion_ragged_dev.argtypes = l.ulcx_decode_crops_spectra_ragged_dev.argtypes[:14] + dist_dev + [C.c_void_p]
+            l.ulcx_decode_crops_distortion_ragged_host.argtypes = l.ulcx_decode_crops_spectra_ragged_host.argtypes[:14] + dist_host
         if hasattr(l, "ulcx_synth_spectra_dev"):           # synthesis from spectra: PCM from caller-held planes
             l.ulcx_synth_spectra_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             l.ulcx_synth_spectra_dev_pcm16.argtypes = l.ulcx_synth_spectra_dev.argtypes
@@ -1206,6 +1216,84 @@ class BatchDecoder(_StreamSlots):
         _check(lib().ulcx_decode_crops_spectra_ragged_dev(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs,
                                                           d_index_blocks, n, d_file, d_first, d_count or None, n_blocks, int(flags), d_coef, d_wc, d_bits,
                                                           stream or None), "ulcx_decode_crops_spectra_ragged_dev")
+
+    def _distortion_host_args(self, n, n_blocks, ref, ref_row, ref_first, n_seg, flags):
+        """The host forms' arguments behind nBlocks, and the arrays they fill -> (args, dist, wc, bits)."""
+        n_ref = n_ref_blocks = 0
+        if ref is not None:
+            ref = np.ascontiguousarray(ref, dtype=np.float32)
+            assert ref.ndim == 4 and ref.shape[1] == self.C and ref.shape[3] == self.BS
+            n_ref, n_ref_blocks = ref.shape[0], ref.shape[2]
+        row = None if ref_row is None else np.ascontiguousarray(ref_row, dtype=np.int32)
+        rfirst = None if ref_first is None else np.ascontiguousarray(ref_first, dtype=np.int32)
+        assert (row is None or row.shape == (n,)) and (rfirst is None or rfirst.shape == (n,))
+        dist = np.zeros((n, self.C, n_blocks, max(int(n_seg), 1), 3), np.float64)
+        wc = np.zeros((n, n_blocks), np.int32)
+        bits = np.zeros((n, n_blocks), np.int32)
+        args = (_p(ref, _f32p), n_ref, n_ref_blocks, _p(row, _i32p), _p(rfirst, _i32p), int(n_seg), int(flags),
+                _p(dist, C.POINTER(C.c_double)), _p(wc, _i32p), _p(bits, _i32p))
+        return args, dist, wc, bits
+
+    def decode_crops_distortion(self, payload, payload_bytes, index, index_blocks, files, first, n_blocks, ref=None, ref_row=None, ref_first=None,
+                                count=None, n_seg=1, flags=0):
+        """decode_crops_spectra() summed against reference planes instead of returned (ulcx_decode_crops_distortion_host): per (row,
+        channel, block, segment of BS / n_seg coefficients) the binary64 sums {S, Y, E} of the reference's, the coded spectrum's and the
+        error's energy, added in one fixed order.  ref: float32 [n_ref][C][n_ref_blocks][BS] or None (S = 0, E = Y); ref_row[i] /
+        ref_first[i]: the reference row of crop row i (None: i) and the reference block beside its output block 0 (None: 0).
+        -> (dist float64 [n][C][n_blocks][n_seg][3], wc [n][n_blocks], bits [n][n_blocks])."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8)
+        nbytes = np.ascontiguousarray(payload_bytes, dtype=np.int32)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        want = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+        F, stride = payload.shape
+        n = files.shape[0]
+        assert nbytes.shape == (F,) and index.shape[0] == F and blocks.shape == (F,) and first.shape == (n,)
+        assert want is None or want.shape == (n,)
+        args, dist, wc, bits = self._distortion_host_args(n, n_blocks, ref, ref_row, ref_first, n_seg, flags)
+        _check(lib().ulcx_decode_crops_distortion_host(self.h, F, _p(payload, _u8p), stride, _p(nbytes, _i32p), index.ctypes.data, index.shape[1],
+                                                       _p(blocks, _i32p), n, _p(files, _i32p), _p(first, _i32p), _p(want, _i32p), n_blocks, *args),
+               "ulcx_decode_crops_distortion_host")
+        return dist, wc, bits
+
+    def decode_crops_distortion_dev(self, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_first, d_count,
+                                    n_blocks, d_ref, n_ref, n_ref_blocks, d_ref_row, d_ref_first, n_seg, flags, d_dist, d_wc, d_bits, stream=0):
+        """Device form (d_count, d_ref, d_ref_row, d_ref_first 0 / None: not given); d_ref float32 [n_ref][C][n_ref_blocks][BS], d_dist
+        float64 [n][C][n_blocks][n_seg][3], d_wc / d_bits [n][n_blocks]."""
+        _check(lib().ulcx_decode_crops_distortion_dev(self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file,
+                                                      d_first, d_count or None, n_blocks, d_ref or None, n_ref, n_ref_blocks, d_ref_row or None,
+                                                      d_ref_first or None, int(n_seg), int(flags), d_dist, d_wc, d_bits, stream or None),
+               "ulcx_decode_crops_distortion_dev")
+
+    def decode_crops_distortion_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, first, n_blocks, ref=None, ref_row=None,
+                                       ref_first=None, count=None, n_seg=1, flags=0):
+        """decode_crops_distortion() of a ragged corpus, held as for decode_crops_ragged()."""
+        payload = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        poffs = np.ascontiguousarray(payload_offs, dtype=np.int64)
+        index = np.ascontiguousarray(index, dtype=INDEX_DTYPE).reshape(-1)
+        ioffs = np.ascontiguousarray(index_offs, dtype=np.int64)
+        blocks = np.ascontiguousarray(index_blocks, dtype=np.int32)
+        files = np.ascontiguousarray(files, dtype=np.int32)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        want = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+        F, n = blocks.shape[0], files.shape[0]
+        assert poffs.shape == (F + 1,) and ioffs.shape == (F + 1,) and first.shape == (n,) and (want is None or want.shape == (n,))
+        args, dist, wc, bits = self._distortion_host_args(n, n_blocks, ref, ref_row, ref_first, n_seg, flags)
+        _check(lib().ulcx_decode_crops_distortion_ragged_host(self.h, F, _p(payload, _u8p), payload.size, _p(poffs, _i64p), index.ctypes.data, index.size,
+                                                              _p(ioffs, _i64p), _p(blocks, _i32p), n, _p(files, _i32p), _p(first, _i32p), _p(want, _i32p),
+                                                              n_blocks, *args), "ulcx_decode_crops_distortion_ragged_host")
+        return dist, wc, bits
+
+    def decode_crops_distortion_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
+                                           n, d_file, d_first, d_count, n_blocks, d_ref, n_ref, n_ref_blocks, d_ref_row, d_ref_first, n_seg, flags,
+                                           d_dist, d_wc, d_bits, stream=0):
+        """Device form of a ragged corpus (d_count, d_ref, d_ref_row, d_ref_first 0 / None: not given)."""
+        _check(lib().ulcx_decode_crops_distortion_ragged_dev(self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs,
+                                                             d_index_blocks, n, d_file, d_first, d_count or None, n_blocks, d_ref or None, n_ref, n_ref_blocks,
+                                                             d_ref_row or None, d_ref_first or None, int(n_seg), int(flags), d_dist, d_wc, d_bits,
+                                                             stream or None), "ulcx_decode_crops_distortion_ragged_dev")
 
     def decode_crops_samples(self, payload, payload_bytes, index, index_blocks, files, start, n_samples, length=None):
         """Sample crops of a corpus held as for decode_crops(): row i is n_samples samples from sample start[i] (int64) of the
