@@ -70,7 +70,7 @@ def clip_spectra(enc, wave, lengths=None, n_blocks=None, lr=False):
     depth = ulc_amd.clip_blocks(enc.BS, T) if n_blocks is None else int(n_blocks)
     coef, wc, cplx = _spectra_planes(n, ch, depth, enc.BS, dev)
     with torch.cuda.device(dev):
-        enc.analyse_clips_dev(n, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, depth, coef.data_ptr(), wc.data_ptr(), cplx.data_ptr(),
+        enc.analyse_clips_dev(n, wave.data_ptr(), _ptr(want), T, depth, coef.data_ptr(), wc.data_ptr(), cplx.data_ptr(),
                               flags=ulc_amd.SPECTRA_LR if lr else 0, stream=torch.cuda.current_stream(dev).cuda_stream, pcm16=pcm16)
     return coef, wc, cplx
 
@@ -107,6 +107,23 @@ def synth_spectra(dec, coef, wc, *, lr=False, warm=False, pcm16=False):
         dec.synth_spectra_dev(n, depth, flags, coef.data_ptr(), wc.data_ptr(), pcm.data_ptr(), live.data_ptr(),
                               stream=torch.cuda.current_stream(dev).cuda_stream, pcm16=pcm16)
     return pcm, live
+
+
+def _ptr(t):
+    """A tensor's device address for the library; 0 for None: not given."""
+    return t.data_ptr() if t is not None else 0
+
+
+def _empty_strided(n_files, stride, index_stride, dev):
+    """Unwritten tensors of a strided corpus -> (payload, stride, payload_bytes, index, index_stride, index_blocks), the order the
+    library's calls and _adopt() take them in."""
+    import torch
+    return (torch.empty((n_files, stride), dtype=torch.uint8, device=dev), stride, torch.empty(n_files, dtype=torch.int32, device=dev),
+            torch.empty((n_files, index_stride, 2), dtype=torch.int32, device=dev), index_stride, torch.empty(n_files, dtype=torch.int32, device=dev))
+
+
+def _corpus_ptrs(strided):
+    return tuple(_ptr(v) if hasattr(v, "data_ptr") else v for v in strided)
 
 
 def _spectra_planes(n, ch, depth, block_size, dev):
@@ -147,6 +164,36 @@ class CropCorpus:
         what always suffices, slot bytes x blocks of T samples; a row that does not fit keeps its leading blocks).
         layout="ragged" runs ulcx_corpus_ragged_dev behind it; sizing the ragged buffers takes ONE 16-byte read of the totals."""
         import torch
+        c, n, T, dev, pcm16, wave, want = cls._clips_in(enc, dec, wave, lengths, layout)
+        table = None
+        mode, p0, p1 = ulc_amd.MODE_VBR, 50.0, 0.0
+        if isinstance(rate, tuple):
+            mode, p0, p1 = int(rate[0]), float(rate[1]), float(rate[2]) if len(rate) > 2 else 0.0
+        else:
+            table = torch.as_tensor(rate, dtype=torch.float32, device=dev).contiguous()
+            assert tuple(table.shape) == (n, 2)
+        nb, stream, out = cls._clips_out(enc, n, T, payload_stride, dev)
+        planes = None
+        if _tap is not None:
+            depth = nb if _tap[0] is None else int(_tap[0])
+            planes = _spectra_planes(n, enc.C, depth, enc.BS, dev)
+        with torch.cuda.device(dev):
+            args = (dec, n, wave.data_ptr(), _ptr(want), T, *_corpus_ptrs(out))
+            kw = dict(mode=mode, p0=p0, p1=p1, d_rates=_ptr(table), stream=stream, pcm16=pcm16)
+            if planes is None:
+                enc.encode_clips_dev(*args, **kw)
+            else:
+                enc.encode_clips_spectra_dev(*args, depth, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
+                                             flags=ulc_amd.SPECTRA_LR if _tap[1] else 0, **kw)
+            c._adopt(dev, stream, n, *out)
+        c.frozen = True
+        return c if planes is None else (c, *planes)
+
+    @classmethod
+    def _clips_in(cls, enc, dec, wave, lengths, layout):
+        """What the clip calls share in front of their rates: the geometry check, the corpus object, wave and lengths as the call
+        reads them -> (corpus, n, T, device, pcm16, wave, lengths or None)."""
+        import torch
         n, ch, T = wave.shape
         if (ch, enc.BS) != (dec.C, dec.BS) or ch != enc.C:
             raise UlcError(f"corpus: clips of {ch} channels, an encoder of {enc.BS} x {enc.C}, a decoder of {dec.BS} x {dec.C}")
@@ -155,37 +202,15 @@ class CropCorpus:
         pcm16 = wave.dtype == torch.int16
         wave = wave.contiguous() if pcm16 else wave.to(torch.float32).contiguous()
         want = None if lengths is None else torch.as_tensor(lengths, dtype=torch.int32, device=dev).contiguous()
-        table = None
-        mode, p0, p1 = ulc_amd.MODE_VBR, 50.0, 0.0
-        if isinstance(rate, tuple):
-            mode, p0, p1 = int(rate[0]), float(rate[1]), float(rate[2]) if len(rate) > 2 else 0.0
-        else:
-            table = torch.as_tensor(rate, dtype=torch.float32, device=dev).contiguous()
-            assert tuple(table.shape) == (n, 2)
+        return c, n, T, dev, pcm16, wave, want
+
+    @staticmethod
+    def _clips_out(enc, n_files, T, payload_stride, dev):
+        """And behind them: what the call writes -> (blocks of T samples, torch's current stream, _empty_strided() of n_files files
+        at the default strides, which hold every file in full, unless payload_stride is given)."""
+        import torch
         nb = ulc_amd.clip_blocks(enc.BS, T)
-        stride = int(payload_stride or enc.slot * nb)
-        index_stride = nb + 1
-        payload = torch.empty((n, stride), dtype=torch.uint8, device=dev)
-        nbytes = torch.empty(n, dtype=torch.int32, device=dev)
-        index = torch.empty((n, index_stride, 2), dtype=torch.int32, device=dev)
-        blocks = torch.empty(n, dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        planes = None
-        if _tap is not None:
-            depth = nb if _tap[0] is None else int(_tap[0])
-            planes = _spectra_planes(n, ch, depth, enc.BS, dev)
-        with torch.cuda.device(dev):
-            args = (dec, n, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, payload.data_ptr(), stride, nbytes.data_ptr(),
-                    index.data_ptr(), index_stride, blocks.data_ptr())
-            kw = dict(mode=mode, p0=p0, p1=p1, d_rates=table.data_ptr() if table is not None else 0, stream=stream, pcm16=pcm16)
-            if planes is None:
-                enc.encode_clips_dev(*args, **kw)
-            else:
-                enc.encode_clips_spectra_dev(*args, depth, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
-                                             flags=ulc_amd.SPECTRA_LR if _tap[1] else 0, **kw)
-            c._adopt(dev, stream, n, payload, stride, nbytes, index, index_stride, blocks)
-        c.frozen = True
-        return c if planes is None else (c, *planes)
+        return nb, torch.cuda.current_stream(dev).cuda_stream, _empty_strided(n_files, int(payload_stride or enc.slot * nb), nb + 1, dev)
 
     def _adopt(self, dev, stream, n, payload, stride, nbytes, index, index_stride, blocks):
         """The tensors a clips call wrote (n files, strided) become the corpus's; a ragged corpus lays them out with
@@ -201,7 +226,7 @@ class CropCorpus:
         oblocks = torch.empty(n, dtype=torch.int32, device=dev)
         need = torch.empty(2, dtype=torch.int64, device=dev)
         none = torch.empty(16, dtype=torch.uint8, device=dev)
-        args = (n, payload.data_ptr(), stride, nbytes.data_ptr(), index.data_ptr(), index_stride, blocks.data_ptr())
+        args = (n, *_corpus_ptrs((payload, stride, nbytes, index, index_stride, blocks)))
         ulc_amd.corpus_ragged_dev(*args, none.data_ptr(), 0, poffs.data_ptr(), none.data_ptr(), 0, ioffs.data_ptr(), oblocks.data_ptr(),
                                   need.data_ptr(), stream=stream, device=dev.index or 0)
         nbytes_all, nent_all = (int(v) for v in need.cpu())
@@ -223,17 +248,10 @@ class CropCorpus:
         lengths, layout and payload_stride (bytes per FILE) as from_clips takes them."""
         import numbers
         import torch
-        n, ch, T = wave.shape
-        if (ch, enc.BS) != (dec.C, dec.BS) or ch != enc.C:
-            raise UlcError(f"corpus: clips of {ch} channels, an encoder of {enc.BS} x {enc.C}, a decoder of {dec.BS} x {dec.C}")
         rates = list(rates)
         R = len(rates)
-        c = cls(ch, enc.BS, layout)
-        dev = wave.device
-        pcm16 = wave.dtype == torch.int16
-        wave = wave.contiguous() if pcm16 else wave.to(torch.float32).contiguous()
-        want = None if lengths is None else torch.as_tensor(lengths, dtype=torch.int32, device=dev).contiguous()
-        tables = []                                             # (alive until the call is enqueued; torch frees them in stream order)
+        c, n, T, dev, pcm16, wave, want = cls._clips_in(enc, dec, wave, lengths, layout)
+        tables = []                                        # (alive until the call is enqueued; torch frees them in stream order)
 
         def table_ptr(r, t):
             t = torch.as_tensor(t, dtype=torch.float32, device=dev).contiguous()
@@ -257,20 +275,11 @@ class CropCorpus:
             else:
                 rungs.append(table_ptr(r, g))
         auto = any(isinstance(g, tuple) and g[0] in ("auto", "auto_table") for g in rungs)
-        nb = ulc_amd.clip_blocks(enc.BS, T)
-        stride = int(payload_stride or enc.slot * nb)
-        index_stride = nb + 1
-        F = max(R, 1) * n
-        payload = torch.empty((F, stride), dtype=torch.uint8, device=dev)
-        nbytes = torch.empty(F, dtype=torch.int32, device=dev)
-        index = torch.empty((F, index_stride, 2), dtype=torch.int32, device=dev)
-        blocks = torch.empty(F, dtype=torch.int32, device=dev)
+        _, stream, out = cls._clips_out(enc, max(R, 1) * n, T, payload_stride, dev)
         avg = torch.empty(n, dtype=torch.float32, device=dev) if auto else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            enc.encode_clips_ladder_dev(dec, n, rungs, wave.data_ptr(), want.data_ptr() if want is not None else 0, T, payload.data_ptr(), stride, nbytes.data_ptr(),
-                                        index.data_ptr(), index_stride, blocks.data_ptr(), d_avg=avg.data_ptr() if auto else 0, stream=stream, pcm16=pcm16)
-            c._adopt(dev, stream, F, payload, stride, nbytes, index, index_stride, blocks)
+            enc.encode_clips_ladder_dev(dec, n, rungs, wave.data_ptr(), _ptr(want), T, *_corpus_ptrs(out), d_avg=_ptr(avg), stream=stream, pcm16=pcm16)
+            c._adopt(dev, stream, max(R, 1) * n, *out)
         c.n_rungs, c.n_clips, c.avg = R, n, avg
         c.frozen = True
         return c
@@ -442,28 +451,41 @@ class CropCorpus:
         torch's current stream.  `dec`: a BatchDecoder of this geometry with n_streams >= n and max_blocks > n_blocks; no stream
         state of it is read or changed."""
         import torch
+        sfx, corpus = self._ready(dec)._view()
+        n, files, first, want = self._rows(files, first, count)
+        pcm = torch.empty((n, n_blocks * self.BS, self.C), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
+        bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        getattr(dec, f"decode_crops{sfx}_dev")(*corpus, n, files.data_ptr(), first.data_ptr(), _ptr(want), n_blocks, pcm.data_ptr(), bits.data_ptr(),
+                                               stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
+        return pcm, bits
+
+    def _ready(self, dec):
+        """Refuses a corpus that is not frozen and a decoder of another geometry -> self."""
         if not self.frozen:
             raise UlcError("corpus: not frozen")
         if (dec.C, dec.BS) != (self.C, self.BS):
             raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
-        as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=self.device).contiguous()
-        files, first = as_i32(files), as_i32(first)
-        want = None if count is None else as_i32(count)
-        n = files.numel()
-        assert first.numel() == n and (want is None or want.numel() == n)
-        pcm = torch.empty((n, n_blocks * self.BS, self.C), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
-        bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
+        return self
+
+    def _view(self):
+        """The frozen corpus as a device form takes it -> (the suffix of the form's name: decode_crops<suffix>_dev, the arguments
+        n_files .. d_index_blocks of that form)."""
         if self.ragged:
-            dec.decode_crops_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
-                                        self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
-                                        n, files.data_ptr(), first.data_ptr(), want.data_ptr() if want is not None else 0, n_blocks,
-                                        pcm.data_ptr(), bits.data_ptr(), stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
-            return pcm, bits
-        dec.decode_crops_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
-                             self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), first.data_ptr(),
-                             want.data_ptr() if want is not None else 0, n_blocks, pcm.data_ptr(), bits.data_ptr(),
-                             stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
-        return pcm, bits
+            return "_ragged", (self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(), self.d_index.data_ptr(),
+                               self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr())
+        return "", (self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(), self.index_stride,
+                    self.d_index_blocks.data_ptr())
+
+    def _rows(self, files, pos, want, *more, pos_dtype=None):
+        """The rows of a crop call as contiguous tensors on the corpus's device -> (n, files, pos, want, *more): files int32 [n],
+        pos of pos_dtype (default int32), want and `more` int32 [n] or None.  The caller holds them until its call is enqueued."""
+        import torch
+        as_t = lambda v, t=torch.int32: torch.as_tensor(v, dtype=t, device=self.device).contiguous()
+        files, pos = as_t(files), as_t(pos, pos_dtype or torch.int32)
+        opt = [None if v is None else as_t(v) for v in (want, *more)]
+        n = files.numel()
+        assert pos.numel() == n and all(v is None or v.numel() == n for v in opt)
+        return (n, files, pos, *opt)
 
     def splice(self, dec, segments):
         """A new corpus whose files are block ranges of this one's (ulcx_corpus_splice_dev): rung switches, trims, joins.
@@ -475,10 +497,7 @@ class CropCorpus:
         output block at which each segment begins in its file.  Enqueued on torch's current stream.  `dec`: a BatchDecoder of this
         geometry; geometry and tables are all the call reads of it."""
         import torch
-        if not self.frozen:
-            raise UlcError("corpus: not frozen")
-        if (dec.C, dec.BS) != (self.C, self.BS):
-            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
+        sfx, corpus = self._ready(dec)._view()
         dev = self.device
         as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=dev).contiguous()
         if isinstance(segments, tuple):
@@ -509,23 +528,15 @@ class CropCorpus:
         n_blocks, n_bytes = (int(v) for v in most.cpu())
         stride = (n_bytes + PAYLOAD_PAD + 15) & ~15
         index_stride = n_blocks + 1 if n_blocks > 0 else 2
-        payload = torch.empty((n_out, stride), dtype=torch.uint8, device=dev)
-        nbytes = torch.empty(n_out, dtype=torch.int32, device=dev)
-        index = torch.empty((n_out, index_stride, 2), dtype=torch.int32, device=dev)
-        blocks = torch.empty(n_out, dtype=torch.int32, device=dev)
+        out = _empty_strided(n_out, stride, index_stride, dev)
         seg_start = torch.empty(n_seg, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        out = (n_out, offs.data_ptr(), seg.data_ptr(), n_seg, payload.data_ptr(), stride, nbytes.data_ptr(), 0, index.data_ptr(), index_stride,
-               blocks.data_ptr(), seg_start.data_ptr())
+        payload, stride, nbytes, index, index_stride, blocks = _corpus_ptrs(out)
         c = CropCorpus(self.C, self.BS, "ragged" if self.ragged else "strided")
         with torch.cuda.device(dev):
-            if self.ragged:
-                dec.corpus_splice_ragged_dev(F, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(), self.d_index.data_ptr(),
-                                             self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(), *out, stream=stream)
-            else:
-                dec.corpus_splice_dev(F, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(), self.index_stride,
-                                      self.d_index_blocks.data_ptr(), *out, stream=stream)
-            c._adopt(dev, stream, n_out, payload, stride, nbytes, index, index_stride, blocks)
+            getattr(dec, f"corpus_splice{sfx}_dev")(*corpus, n_out, offs.data_ptr(), seg.data_ptr(), n_seg, payload, stride, nbytes, 0, index, index_stride,
+                                                    blocks, seg_start.data_ptr(), stream=stream)
+            c._adopt(dev, stream, n_out, *out)
         c.frozen = True
         return c, seg_start
 
@@ -560,27 +571,12 @@ class CropCorpus:
         torch's current stream.  `dec`: a BatchDecoder of this geometry with n_streams >= n and max_blocks > crop_blocks =
         ulc_amd.crop_blocks(BlockSize, n_samples); no stream state of it is read or changed."""
         import torch
-        if not self.frozen:
-            raise UlcError("corpus: not frozen")
-        if (dec.C, dec.BS) != (self.C, self.BS):
-            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
-        as_t = lambda v, t: torch.as_tensor(v, dtype=t, device=self.device).contiguous()
-        files, start = as_t(files, torch.int32), as_t(start, torch.int64)
-        want = None if length is None else as_t(length, torch.int32)
-        n = files.numel()
-        assert start.numel() == n and (want is None or want.numel() == n)
+        sfx, corpus = self._ready(dec)._view()
+        n, files, start, want = self._rows(files, start, length, pos_dtype=torch.int64)
         pcm = torch.empty((n, self.C, n_samples), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
         bits = torch.empty((n, ulc_amd.crop_blocks(self.BS, n_samples)), dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.ragged:
-            dec.decode_crops_samples_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
-                                                self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
-                                                n, files.data_ptr(), start.data_ptr(), want.data_ptr() if want is not None else 0, n_samples,
-                                                pcm.data_ptr(), bits.data_ptr(), stream=stream, pcm16=pcm16)
-            return pcm, bits
-        dec.decode_crops_samples_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
-                                     self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), start.data_ptr(),
-                                     want.data_ptr() if want is not None else 0, n_samples, pcm.data_ptr(), bits.data_ptr(), stream=stream, pcm16=pcm16)
+        getattr(dec, f"decode_crops_samples{sfx}_dev")(*corpus, n, files.data_ptr(), start.data_ptr(), _ptr(want), n_samples, pcm.data_ptr(), bits.data_ptr(),
+                                                       stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
         return pcm, bits
 
     def spectra(self, dec, files, first, n_blocks, count=None, lr=False):
@@ -591,30 +587,14 @@ class CropCorpus:
         -> (coef [n][nChan][n_blocks][BlockSize] float32, wc int32 [n][n_blocks], bits int32 [n][n_blocks]) on the device, enqueued
         on torch's current stream.  `dec`: as for crops(); no stream state of it is read or changed."""
         import torch
-        if not self.frozen:
-            raise UlcError("corpus: not frozen")
-        if (dec.C, dec.BS) != (self.C, self.BS):
-            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
-        as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=self.device).contiguous()
-        files, first = as_i32(files), as_i32(first)
-        want = None if count is None else as_i32(count)
-        n = files.numel()
-        assert first.numel() == n and (want is None or want.numel() == n)
+        sfx, corpus = self._ready(dec)._view()
+        n, files, first, want = self._rows(files, first, count)
         coef = torch.empty((n, self.C, n_blocks, self.BS), dtype=torch.float32, device=self.device)
         wc = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
         bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
-        flags = ulc_amd.SPECTRA_LR if lr else 0
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.ragged:
-            dec.decode_crops_spectra_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
-                                                self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
-                                                n, files.data_ptr(), first.data_ptr(), want.data_ptr() if want is not None else 0, n_blocks, flags,
-                                                coef.data_ptr(), wc.data_ptr(), bits.data_ptr(), stream=stream)
-            return coef, wc, bits
-        dec.decode_crops_spectra_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
-                                     self.index_stride, self.d_index_blocks.data_ptr(), n, files.data_ptr(), first.data_ptr(),
-                                     want.data_ptr() if want is not None else 0, n_blocks, flags, coef.data_ptr(), wc.data_ptr(), bits.data_ptr(),
-                                     stream=stream)
+        getattr(dec, f"decode_crops_spectra{sfx}_dev")(*corpus, n, files.data_ptr(), first.data_ptr(), _ptr(want), n_blocks, ulc_amd.SPECTRA_LR if lr else 0,
+                                                       coef.data_ptr(), wc.data_ptr(), bits.data_ptr(),
+                                                       stream=torch.cuda.current_stream(self.device).cuda_stream)
         return coef, wc, bits
 
     def distortion(self, dec, files, first, n_blocks, ref=None, ref_row=None, ref_first=None, count=None, n_seg=1, lr=False):
@@ -627,16 +607,8 @@ class CropCorpus:
         -> (dist float64 [n][nChan][n_blocks][n_seg][3], wc int32 [n][n_blocks], bits int32 [n][n_blocks]) on the device, enqueued on
         torch's current stream; a contiguous `ref` is not copied.  `dec`: as for crops(); no stream state of it is read or changed."""
         import torch
-        if not self.frozen:
-            raise UlcError("corpus: not frozen")
-        if (dec.C, dec.BS) != (self.C, self.BS):
-            raise UlcError(f"corpus: a decoder of {dec.BS} x {dec.C} for a corpus of {self.BS} x {self.C}")
-        as_i32 = lambda v: torch.as_tensor(v, dtype=torch.int32, device=self.device).contiguous()
-        opt = lambda v: None if v is None else as_i32(v)
-        files, first = as_i32(files), as_i32(first)
-        want, row, rfirst = opt(count), opt(ref_row), opt(ref_first)
-        n = files.numel()
-        assert first.numel() == n and all(v is None or v.numel() == n for v in (want, row, rfirst))
+        sfx, corpus = self._ready(dec)._view()
+        n, files, first, want, row, rfirst = self._rows(files, first, count, ref_row, ref_first)
         n_ref = n_ref_blocks = 0
         if ref is not None:
             ref = torch.as_tensor(ref, dtype=torch.float32, device=self.device).contiguous()
@@ -646,17 +618,9 @@ class CropCorpus:
         dist = torch.empty((n, self.C, n_blocks, n_seg, 3), dtype=torch.float64, device=self.device)
         wc = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
         bits = torch.empty((n, n_blocks), dtype=torch.int32, device=self.device)
-        ptr = lambda v: v.data_ptr() if v is not None else 0
-        tail = (n, files.data_ptr(), first.data_ptr(), ptr(want), n_blocks, ptr(ref), n_ref, n_ref_blocks, ptr(row), ptr(rfirst), int(n_seg),
-                ulc_amd.SPECTRA_LR if lr else 0, dist.data_ptr(), wc.data_ptr(), bits.data_ptr())
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if self.ragged:
-            dec.decode_crops_distortion_ragged_dev(self.n_files, self.d_payload.data_ptr(), self.d_payload.numel(), self.d_payload_offs.data_ptr(),
-                                                   self.d_index.data_ptr(), self.d_index.shape[0], self.d_index_offs.data_ptr(), self.d_index_blocks.data_ptr(),
-                                                   *tail, stream=stream)
-        else:
-            dec.decode_crops_distortion_dev(self.n_files, self.d_payload.data_ptr(), self.stride, self.d_payload_bytes.data_ptr(), self.d_index.data_ptr(),
-                                            self.index_stride, self.d_index_blocks.data_ptr(), *tail, stream=stream)
+        getattr(dec, f"decode_crops_distortion{sfx}_dev")(*corpus, n, files.data_ptr(), first.data_ptr(), _ptr(want), n_blocks, _ptr(ref), n_ref, n_ref_blocks,
+                                                          _ptr(row), _ptr(rfirst), int(n_seg), ulc_amd.SPECTRA_LR if lr else 0, dist.data_ptr(), wc.data_ptr(),
+                                                          bits.data_ptr(), stream=torch.cuda.current_stream(self.device).cuda_stream)
         return dist, wc, bits
 
 
