@@ -9,6 +9,8 @@ import numpy as np
 import clips_testlib as ct
 import clip_spectra_testlib as cst
 import guarded_buffers as gb
+from ulc_testlib import to_pcm16
+from gpu_testlib import amd as _amd, dev as _dev
 
 # A rung of the tests: ("scalar", (RateKbps, AvgComplexity)) in the tool's convention, ("table",) = clips_testlib.TABLE,
 # ("auto", kbps) = AUTO on a scalar rung, ("auto_table",) = AUTO on TABLE.
@@ -106,20 +108,6 @@ def ladder_cut(bs, ch):
 N, B = 7, 8                                                 # rows of a call and streams of the object, unless a test says otherwise
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _to_pcm16(x):
-    return np.clip(np.rint(x.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)
-
-
 class LadderCall:
     """One ulcx_encode_clips_ladder_dev(_pcm16) call on a guarded arena -> the outputs as numpy, [R * n]...  rungs: of
     clips_ladder_testlib; n rows on an object of `streams` streams; case / rows as tests/test_gpu_clips.py's Call takes them."""
@@ -151,7 +139,7 @@ class LadderCall:
             specs += [word("d_maxBlock", F, "out"), word("d_avg", n, "out")]
         a = self.a = gb.build(_dev(), specs)
         w = ct.wave(bs, ch, T)[rows]
-        a.load("d_pcm", _to_pcm16(w) if pcm16 else w)
+        a.load("d_pcm", to_pcm16(w) if pcm16 else w)
         if not null_len:
             a.load("d_len", np.array(case.lengths, np.int32)[rows])
         if "d_rate" in a.regions:

@@ -8,11 +8,11 @@ import functools
 import numpy as np
 from ulc_testlib import synth_pcm, oracle_encode_debug, oracle_decode_stream
 from seek_testlib import oracle_walk, SEED0
+from corpus_testlib import INDEX_DTYPE
 from rates_testlib import mode_of
 
 RATE = 44100
 GEOMS = [(256, 2), (512, 1), (256, 3)]                      # the stereo vector path, mono, the generic channel loop
-INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
 SCALAR = (-50.0, 0.0)                                       # VBR 50 in the tool's convention
 TABLE = [(-50.0, 0.0), (64.0, 0.0), (96.0, 1.5), (-30.0, 0.0), (48.0, 0.0), (80.0, 2.0), (-70.0, 0.0)]     # VBR, CBR and ABR rows mixed
 # The seven (clip, length) pairs of a test: nSamples of the call and the rows' lengths.  Row i of a call of more rows is pair i % 7.

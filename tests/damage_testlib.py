@@ -12,11 +12,10 @@ CPU only; nothing here runs the library under test."""
 import ctypes as C
 import functools
 import numpy as np
-from ulc_testlib import oracle, ptr, f32p, i32p, u8p
-from seek_testlib import geometries, oracle_stream, oracle_seeds
+from ulc_testlib import oracle, ptr, f32p, i32p, u8p, to_pcm16, same_bytes
+from seek_testlib import geometries
+from corpus_testlib import File, Corpus, geom_files, oracle_file
 
-INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
-PAD = 64                                                   # bytes behind the last payload (corpus.PAYLOAD_PAD)
 MAX_SEED = 400
 EXTRA = {(1024, 2): (50.0, 3)}                             # stereo below BlockSize 2048: no geometry of seek_testlib's has it
 GEOMS = sorted(set(geometries().keys()) | set(EXTRA))      # the six of seek_testlib and 1024 x 2
@@ -28,15 +27,6 @@ def _lib():
     lib = oracle()
     lib.orc_decode_stream_seeded.argtypes = [C.c_int, C.c_int, u8p, C.c_int, C.c_int, f32p, i32p, C.POINTER(C.c_uint32)]
     return lib
-
-
-def to_pcm16(x):
-    return np.clip(np.rint(x.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)       # WavIO_Helper.c:56-63
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def blocks_of(bs, n_samples):
@@ -191,19 +181,13 @@ def draws_block(payload, offs, k, rng_states, ch, bs, cache=None):
     return (damage_block(payload, offs, k, sd), sd) if sd is not None else (None, None)
 
 
-class Stream:
-    """One clean file and its oracle index: payload uint8 [nbytes], offs int64 [K+1], seeds uint32 [K+1], wc [K]."""
+class Stream(File):
+    """A clean corpus_testlib.File - payload, offs, seeds, wc: its oracle index - with the model and the damages bound to that
+    index.  It shares the File's state, so what either computes of the oracle is computed once."""
 
-    def __init__(self, name, bs, ch, blocks, bits):
-        self.name, self.bs, self.ch, self.K = name, bs, ch, len(bits)
-        nb = (np.asarray(bits).astype(np.int64) + 7) // 8
-        self.payload = np.concatenate([blocks[k, :nb[k]] for k in range(self.K)]).astype(np.uint8)
-        self.offs = np.concatenate([[0], np.cumsum(nb)]).astype(np.int64)
-        self.seeds = oracle_seeds(blocks, ch, bs)
-        self.blocks, self.bits = blocks, np.asarray(bits, np.int32)
-        b0 = blocks[:, 0].astype(np.int32)                  # WindowCtrl from a block's first byte (ulcDecoder.c:211-216)
-        self.wc = np.where((b0 & 8) != 0, (b0 & 0xF) | (b0 & 0xF0), (b0 & 0xF) | 0x10)
-        self._cls = {}
+    def __init__(self, f):
+        self.__dict__ = f.__dict__
+        self.__dict__.setdefault("_cls", {})
 
     def model(self, payload, first, n):
         return local_model(payload, self.offs, self.seeds, self.ch, self.bs, first, n)
@@ -222,11 +206,8 @@ def stream_of(geom):
     """The geometry's clean stream: the first of seek_testlib.geometries(), or the local 1024 x 2 one."""
     bs, ch = geom
     if geom in EXTRA:
-        q, sid = EXTRA[geom]
-        blocks, bits, _ = oracle_stream(bs, ch, q, sid)
-        return Stream(f"oracle {bs}x{ch} q{q:g}", bs, ch, blocks, bits)
-    name, blocks, bits, _ = geometries()[geom][0]
-    return Stream(name, bs, ch, blocks, bits)
+        return Stream(oracle_file(bs, ch, *EXTRA[geom]))
+    return Stream(geom_files(geom)[0])
 
 
 def switched_position(st):
@@ -239,8 +220,8 @@ def switched_position(st):
 
 class DamagedCorpus:
     """Files of one geometry that share the clean stream's index: copies of its payload, each with one damaged block.
-    files[f] = (kind, position or None, seed or None); every payload has the clean one's byte count.  Both layouts: host
-    [F][stride] / nbytes / index [F][istride] / count, and ragged / poffs / ioffs with index.reshape(-1)."""
+    files[f] = (kind, position or None, seed or None); every payload has the clean one's byte count.  layout: both layouts
+    (corpus_testlib.Corpus of F times the clean file, with these payloads), whose arrays read as this object's own."""
 
     def __init__(self, st, specs, clean=True):
         """specs: [(kind, position)]; a resize that no seed gives is left out.  clean: file 0 is the undamaged payload."""
@@ -257,22 +238,13 @@ class DamagedCorpus:
                 assert pay.shape == st.payload.shape and (kind == "intact") == np.array_equal(pay, st.payload)
                 self.files.append((kind, j, sd)); self.payloads.append(pay)
         self.F = len(self.files)
-        self.nbytes = np.full(self.F, st.payload.size, np.int32)
-        self.count = np.full(self.F, st.K, np.int32)
-        self.istride = st.K + 1
-        self.stride = (st.payload.size + PAD + 15) & ~15
-        self.host = np.zeros((self.F, self.stride), np.uint8)
-        self.index = np.zeros((self.F, self.istride), INDEX_DTYPE)
-        for f, pay in enumerate(self.payloads):
-            self.host[f, :pay.size] = pay
-            self.index["ByteOffs"][f] = st.offs
-            self.index["RngState"][f] = st.seeds
-        # the same corpus with the files back to back
-        self.poffs = (np.arange(self.F + 1, dtype=np.int64) * st.payload.size)
-        self.ioffs = (np.arange(self.F + 1, dtype=np.int64) * self.istride)
-        self.ragged = np.zeros(int(self.poffs[-1]) + PAD, np.uint8)
-        self.ragged[:self.poffs[-1]] = np.concatenate(self.payloads)
+        self.layout = Corpus([st] * self.F, payloads=self.payloads)
         self._rows = {}
+
+    def __getattr__(self, name):
+        if name == "layout":
+            raise AttributeError(name)
+        return getattr(self.layout, name)                       # host / nbytes / index / count / rpay / poffs / ridx / ioffs / to_device()
 
     def of_kind(self, kind, j=None):
         return [f for f, (kd, pos, _) in enumerate(self.files) if kd == kind and (j is None or pos == j)]

@@ -7,7 +7,8 @@ W = 4), and the cases the GPU tests name.  CPU only; nothing here runs the libra
 import functools
 import numpy as np
 import spectra_testlib as S
-from seek_testlib import oracle_stream
+from ulc_testlib import same_bits64
+from corpus_testlib import Corpus, oracle_file
 
 N_BLOCKS = S.N_BLOCKS
 INT32_MAX = 2 ** 31 - 1
@@ -42,11 +43,6 @@ def halve(dist):
         return dist[..., 0::2, :] + dist[..., 1::2, :]
 
 
-def same_bits64(a, b):
-    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
 def first_diff(a, b):
     """Where two float64 arrays differ in bits (the first few indices), for messages."""
     a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
@@ -77,11 +73,9 @@ def is_denormal(v):
 
 @functools.lru_cache(maxsize=None)
 def small_corpus():
-    """A BlockSize 256 stereo corpus of one oracle-encoded transient file (spectra_testlib.Corpus); signal 11: two window-switched
+    """A BlockSize 256 stereo corpus of one oracle-encoded transient file (corpus_testlib.Corpus); signal 11: two window-switched
     blocks, of two patterns, which row_table() asks of a file."""
-    bs, ch = SMALL
-    blocks, bits, _ = oracle_stream(bs, ch, 50.0, 11)
-    return S.Corpus([S.FileSpec(f"oracle {bs}x{ch} q50", bs, ch, blocks, bits)])
+    return Corpus([oracle_file(*SMALL, 50.0, 11)])
 
 
 def corpus_of(geom):
@@ -117,7 +111,7 @@ def expected_rows(cor, files, first, N, n_seg, ref=None, ref_row=None, ref_first
     """The whole expectation of a call on an undamaged corpus -> (dist [n][ch][N][n_seg][3], wc [n][N], bits [n][N]): the oracle's
     coefficients of the rows, the referee's sums of them against the reference, and +0.0 in all three sums of a block that is not
     live (its reference is not read)."""
-    coef, wc, bits = cor.expected(files, first, N, count, lr=lr)
+    coef, wc, bits = cor.expected_spec(files, first, N, count, lr=lr)
     dist, _ = expected(coef, ref, ref_row, ref_first, n_seg)
     dist[np.broadcast_to((wc == 0)[:, None, :], dist.shape[:3])] = 0.0
     return dist, wc, bits

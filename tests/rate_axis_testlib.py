@@ -60,13 +60,13 @@ def case_id(c):
 # ---------------------------------------------------------------------------
 # the five distinct streams of a batch
 # ---------------------------------------------------------------------------
-def _pcm16(x):
+def _grid16(x):
     return (np.clip(np.rint(x * 32768.0), -32768, 32767) * (1.0 / 32768.0)).astype(np.float32)
 
 
 def white_noise(n, ch, seed):
     """Every Bark band of every block has energy."""
-    return _pcm16(np.random.default_rng([0xA71, seed]).normal(0.0, 0.1, (n, ch)))
+    return _grid16(np.random.default_rng([0xA71, seed]).normal(0.0, 0.1, (n, ch)))
 
 
 def last_channel_silent(n, ch, rate, seed):
@@ -88,7 +88,7 @@ def impulse_per_block(n, ch, bs, seed):
         p = k * bs + (3 * bs) // 4
         ln = min(bs // 8, 48)
         x[p:p + ln] += rng.normal(0.0, 0.6, (ln, ch)) * np.exp(-np.arange(ln) / 40.0)[:, None]
-    return _pcm16(x)
+    return _grid16(x)
 
 
 def distinct_streams(bs, ch, rate, nblk, seed):

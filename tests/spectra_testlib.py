@@ -6,26 +6,14 @@ the properties of the test streams the GPU tests rely on, counted with the decod
 import ctypes as C
 import functools
 import numpy as np
-from ulc_testlib import oracle, synth_pcm, oracle_encode_debug, oracle_decode_stream_coefs
-from seek_testlib import RATE, geometries, oracle_stream, oracle_seeds, pack
+from ulc_testlib import oracle, synth_pcm, oracle_encode_debug, same_bits, wc_of
+from seek_testlib import RATE, oracle_stream
+from corpus_testlib import File, Corpus, geom_files, to_lr
 from spec_decoder import _WINDOWS, decode_block_coefficients
 
-INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
 SPECTRA_LR = 1
 N_BLOCKS = 5                                               # blocks per row of the row tests
 DECIMATED = {(8, 8, 4, 2), (4, 8, 8, 2), (2, 8, 8, 4), (2, 4, 8, 8)}
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def wc_of(blocks):
-    """WindowCtrl of every block from its first byte (ulcDecoder.c:211-216)."""
-    b = blocks[:, 0].astype(np.int32)
-    wc = b & 0xF
-    return np.where((wc & 8) != 0, wc | (b & 0xF0), wc | 0x10).astype(np.int32)
 
 
 def subblocks_of(bs, wc):
@@ -41,89 +29,10 @@ def subblocks_of(bs, wc):
             return tuple(out)
 
 
-def to_lr(coef):
-    """coef [..., C, N, bs] -> the pairs (0,1), (2,3), ... as m + s, m - s in float32; a trailing single channel unchanged."""
-    out = np.array(coef, np.float32, copy=True)
-    ch = out.shape[-3]
-    for c in range(0, ch - 1, 2):
-        m, s = coef[..., c, :, :].astype(np.float32), coef[..., c + 1, :, :].astype(np.float32)
-        out[..., c, :, :] = m + s
-        out[..., c + 1, :, :] = m - s
-    return out
-
-
-class FileSpec:
-    """One file: its slot-form blocks and, from the oracle's sequential decode of the whole file, every block's coefficients
-    [K][C][bs], sizes and window codes."""
-
-    def __init__(self, name, bs, ch, blocks, bits):
-        self.name, self.bs, self.ch, self.K = name, bs, ch, len(bits)
-        rc, _, obits, coefs = oracle_decode_stream_coefs(blocks, ch, bs)
-        # (an encoder's size is its block rounded up to a byte; the decoder's, which the calls report, is exact)
-        assert rc == 0 and np.array_equal((obits + 7) // 8, (np.asarray(bits, np.int64) + 7) // 8), name
-        self.blocks, self.bits = blocks, obits.astype(np.int32)
-        self.coef = coefs.reshape(self.K, ch, bs)
-        self.wc = wc_of(blocks)
-
-    @functools.cached_property
-    def seeds(self):
-        return oracle_seeds(self.blocks, self.ch, self.bs)
-
-    def expected(self, first, N, count=None, lr=False):
-        """-> (coef [C][N][bs], wc [N], bits [N]) of the row that starts at block `first`."""
-        coef, wc, bits = np.zeros((self.ch, N, self.bs), np.float32), np.zeros(N, np.int32), np.zeros(N, np.int32)
-        m = N if count is None else max(0, min(N, int(count)))
-        if 0 <= first <= self.K:
-            m = max(0, min(m, self.K - first))
-            coef[:, :m] = self.coef[first:first + m].transpose(1, 0, 2)
-            wc[:m], bits[:m] = self.wc[first:first + m], self.bits[first:first + m]
-        return (to_lr(coef) if lr else coef), wc, bits
-
-
-class Corpus:
-    """Files of one geometry in the strided layout, with the oracle's index of each."""
-
-    def __init__(self, files):
-        self.files, self.F = list(files), len(files)
-        self.bs, self.ch = files[0].bs, files[0].ch
-        self.host, self.nbytes = pack([(f.blocks, f.bits) for f in files])
-        self.stride = self.host.shape[1]
-        self.K = [f.K for f in files]
-        self.istride = max(self.K) + 1
-        self.index = np.zeros((self.F, self.istride), INDEX_DTYPE)
-        self.index["ByteOffs"] = -1
-        for i, f in enumerate(files):
-            self.index["ByteOffs"][i, :f.K + 1] = np.concatenate([[0], np.cumsum((f.bits.astype(np.int64) + 7) // 8)])
-            self.index["RngState"][i, :f.K + 1] = f.seeds
-        self.count = np.array(self.K, np.int32)
-
-    def ragged(self):
-        """The same corpus with the files back to back -> dict(payload, poffs, index, ioffs, blocks)."""
-        sizes = self.nbytes.astype(np.int64)
-        poffs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        ioffs = np.concatenate([[0], np.cumsum(np.array(self.K, np.int64) + 1)]).astype(np.int64)
-        payload = np.zeros(int(poffs[-1]) + 64, np.uint8)
-        index = np.zeros(int(ioffs[-1]), INDEX_DTYPE)
-        for i in range(self.F):
-            payload[poffs[i]:poffs[i + 1]] = self.host[i, :sizes[i]]
-            index[ioffs[i]:ioffs[i + 1]] = self.index[i, :self.K[i] + 1]
-        return dict(payload=payload, poffs=poffs, index=index, ioffs=ioffs, blocks=self.count.copy())
-
-    def expected(self, files, first, N, count=None, lr=False):
-        """-> (coef [n][C][N][bs], wc [n][N], bits [n][N]); a file number outside the corpus gives a row of zeros."""
-        n = len(files)
-        coef, wc, bits = np.zeros((n, self.ch, N, self.bs), np.float32), np.zeros((n, N), np.int32), np.zeros((n, N), np.int32)
-        for i in range(n):
-            if 0 <= files[i] < self.F:
-                coef[i], wc[i], bits[i] = self.files[files[i]].expected(int(first[i]), N, None if count is None else count[i], lr)
-        return coef, wc, bits
-
-
 @functools.lru_cache(maxsize=None)
 def geom_corpus(geom):
     """The oracle-encoded and hand-assembled streams of a geometry of seek_testlib.geometries(), together in one corpus."""
-    bs, ch = geom
-    return Corpus([FileSpec(name, bs, ch, blocks, bits) for name, blocks, bits, _ in geometries()[geom]])
+    return Corpus(geom_files(geom))
 
 
 def row_table(cor, n_blocks=N_BLOCKS):
@@ -196,7 +105,7 @@ def census(name, blocks, bits, ch, bs):
 
 @functools.lru_cache(maxsize=None)
 def big_stream(ch, transient, n_blocks=3, q=30.0, sid=3):
-    """A BlockSize 32768 file of n_blocks blocks -> FileSpec.  transient=False: tones and noise only - its blocks stay un-decimated."""
+    """A BlockSize 32768 file of n_blocks blocks -> File.  transient=False: tones and noise only - its blocks stay un-decimated."""
     bs = 32768
     if transient:
         blocks, bits, _ = oracle_stream(bs, ch, q, sid, n_blocks=n_blocks)
@@ -204,7 +113,7 @@ def big_stream(ch, transient, n_blocks=3, q=30.0, sid=3):
         pcm = synth_pcm(sid, n_blocks * bs, ch, RATE, transient=False, seed=11)
         r = oracle_encode_debug(pcm, bs, RATE, 0, q, slot=2 * ch * bs + 16)
         blocks, bits = r["out"], r["bits"]
-    return FileSpec(f"oracle 32768x{ch} q{q:g} {'transient' if transient else 'steady'}", bs, ch, blocks, bits)
+    return File(f"oracle 32768x{ch} q{q:g} {'transient' if transient else 'steady'}", bs, ch, blocks, bits)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -6,10 +6,9 @@ the concatenated block rows.  Nothing here comes from the library.  CPU only."""
 import functools
 import numpy as np
 from seek_testlib import SEED0, geometries, oracle_pcm, oracle_stream, oracle_walk
+from corpus_testlib import INDEX_DTYPE, File, Corpus, geom_files
 
-INDEX_DTYPE = np.dtype([("ByteOffs", np.int32), ("RngState", np.uint32)])
 SEGMENT_DTYPE = np.dtype([("File", np.int32), ("First", np.int32), ("Count", np.int32)])
-PAD = 64
 GEOMS = sorted(geometries())
 STEREO = (2048, 2)
 ROTATE = 7                                                 # a geometry with one stream: file 1 is its blocks from block 7 on, then blocks 0 .. 6
@@ -17,85 +16,56 @@ FOREIGN_STATE = 0xDEADBEEF                                 # every RngState of a
 SWITCH_Q = (50.0, 20.0)                                    # the two rungs of the rung-switch tests: VBR 50 and VBR 20 of one clip
 
 
-class File:
-    """One source file: block rows [K][slot] and their bits; payload, byte offsets [K + 1]."""
-
-    def __init__(self, name, blocks, bits):
-        self.name, self.blocks, self.bits, self.K = name, np.ascontiguousarray(blocks), np.asarray(bits, np.int32), len(bits)
-        self.nb = (self.bits.astype(np.int64) + 7) // 8
-        self.offs = np.concatenate([[0], np.cumsum(self.nb)]).astype(np.int64)
-        self.payload = np.concatenate([self.blocks[k, :self.nb[k]] for k in range(self.K)]).astype(np.uint8)
+def source_of(files, payloads=None, offs=None):
+    """A source corpus in both layouts (corpus_testlib.Corpus).  payloads: what the buffers hold (a damaged copy of a file's
+    payload under the clean file's index, for the damage tests); offs: the index the buffers hold (an untrusted one, for some
+    tests); the index is the oracle's offsets with FOREIGN_STATE for every state, in rows with three entries to spare."""
+    return Corpus(files, payloads=payloads, offs=offs, states=FOREIGN_STATE, index_slack=3)
 
 
-class Source:
-    """A source corpus in both layouts.  files: [File]; payloads: what the buffers hold (a damaged copy of a file's payload
-    under the clean file's index, for the damage tests); the index is the oracle's offsets with FOREIGN_STATE for every state."""
+def extent(src, f, k):
+    """Bytes of block k of file f as the buffers hold them, under the index they hold."""
+    return src.payloads[f][max(int(src.offs[f][k]), 0):max(int(src.offs[f][k + 1]), 0)]
 
-    def __init__(self, bs, ch, files, payloads=None, offs=None, index_slack=3):
-        self.bs, self.ch, self.files, self.F = bs, ch, files, len(files)
-        self.payloads = [f.payload for f in files] if payloads is None else payloads
-        self.offs = [f.offs for f in files] if offs is None else offs      # the index the buffers hold (an untrusted one, for some tests)
-        self.stride = (max(len(p) for p in self.payloads) + PAD + 15) & ~15
-        self.istride = max(f.K for f in files) + 1 + index_slack
-        self.host = np.zeros((self.F, self.stride), np.uint8)
-        self.nbytes = np.array([len(p) for p in self.payloads], np.int32)
-        self.index = np.zeros((self.F, self.istride), INDEX_DTYPE)
-        self.index["ByteOffs"] = -1
-        self.count = np.array([f.K for f in files], np.int32)
-        for i, (f, p) in enumerate(zip(files, self.payloads)):
-            self.host[i, :len(p)] = p
-            self.index["ByteOffs"][i, :f.K + 1] = self.offs[i]
-        self.index["RngState"] = FOREIGN_STATE
-        # ragged: payloads back to back (PAD behind the last), rows of K + 1 entries
-        self.poffs = np.concatenate([[0], np.cumsum([len(p) for p in self.payloads])]).astype(np.int64)
-        self.ioffs = np.concatenate([[0], np.cumsum([f.K + 1 for f in files])]).astype(np.int64)
-        self.rpay = np.concatenate(list(self.payloads) + [np.zeros(PAD, np.uint8)])
-        self.ridx = np.concatenate([self.index[i, :f.K + 1] for i, f in enumerate(files)])
-        self._ok = {}
 
-    def extent(self, f, k):
-        """Bytes of block k of file f as the buffers hold them, under the index they hold."""
-        return self.payloads[f][max(int(self.offs[f][k]), 0):max(int(self.offs[f][k + 1]), 0)]
+def takes(src, f, k):
+    """The two entries that bound block k of file f satisfy 0 <= ByteOffs[k] < ByteOffs[k + 1] <= the file's bytes, and the
+    oracle's parse of that extent is valid and consumes exactly the extent."""
+    ok = src.__dict__.setdefault("_takes", {})
+    if (f, k) not in ok:
+        o0, o1 = int(src.offs[f][k]), int(src.offs[f][k + 1])
+        ok[(f, k)] = 0 <= o0 < o1 <= len(src.payloads[f])
+        if ok[(f, k)]:
+            e = extent(src, f, k)
+            bits = oracle_walk(e, len(e), src.ch, src.bs, 1)[0]
+            ok[(f, k)] = len(bits) == 1 and (int(bits[0]) + 7) // 8 == len(e)
+    return ok[(f, k)]
 
-    def takes(self, f, k):
-        """The two entries that bound block k of file f satisfy 0 <= ByteOffs[k] < ByteOffs[k + 1] <= the file's bytes, and the
-        oracle's parse of that extent is valid and consumes exactly the extent."""
-        if (f, k) not in self._ok:
-            o0, o1 = int(self.offs[f][k]), int(self.offs[f][k + 1])
-            ok = 0 <= o0 < o1 <= len(self.payloads[f])
-            if ok:
-                e = self.extent(f, k)
-                bits = oracle_walk(e, len(e), self.ch, self.bs, 1)[0]
-                ok = len(bits) == 1 and (int(bits[0]) + 7) // 8 == len(e)
-            self._ok[(f, k)] = ok
-        return self._ok[(f, k)]
 
-    def row(self, f, k):
-        """The block as a row of the oracle's slot size (zeros behind its bytes)."""
-        r = np.zeros(self.files[f].blocks.shape[1], np.uint8)
-        e = self.extent(f, k)
-        r[:len(e)] = e
-        return r
+def row(src, f, k):
+    """The block as a row of the oracle's slot size (zeros behind its bytes)."""
+    r = np.zeros(src.files[f].blocks.shape[1], np.uint8)
+    e = extent(src, f, k)
+    r[:len(e)] = e
+    return r
 
 
 @functools.lru_cache(maxsize=None)
 def source(geom):
-    bs, ch = geom
-    streams = geometries()[geom]
-    files = [File(name, blocks, bits) for name, blocks, bits, _ in streams]
+    files = list(geom_files(geom))
     if len(files) == 1:
         f = files[0]
         order = [(k + ROTATE) % f.K for k in range(f.K)]
-        files.append(File(f.name + f", from block {ROTATE} on", f.blocks[order], f.bits[order]))
-    return Source(bs, ch, files[:2])
+        files.append(File(f.name + f", from block {ROTATE} on", f.bs, f.ch, f.blocks[order], f.bits[order]))
+    return source_of(files[:2])
 
 
 @functools.lru_cache(maxsize=None)
 def switch_source():
-    """One clip (the stereo 2048 stream of seek_testlib) under the two rungs -> (Source of two files, wc of each)."""
+    """One clip (the stereo 2048 stream of seek_testlib) under the two rungs -> (source of two files, wc of each)."""
     bs, ch = STEREO
     enc = [oracle_stream(bs, ch, q, 3) for q in SWITCH_Q]
-    return Source(bs, ch, [File(f"rung VBR {q:g}", e[0], e[1]) for q, e in zip(SWITCH_Q, enc)]), [np.asarray(e[2]) for e in enc]
+    return source_of([File(f"rung VBR {q:g}", bs, ch, e[0], e[1]) for q, e in zip(SWITCH_Q, enc)]), [np.asarray(e[2]) for e in enc]
 
 
 def alternate(K, every, n_rungs=2):
@@ -132,9 +102,9 @@ def taken(src, segs, out_stride, out_istride, gone=()):
     for f, first, count in segs:
         for r in range(max(int(count), 0)):
             k = first + r
-            if not (0 <= f < src.F) or f in gone or first < 0 or k >= src.files[f].K or not src.takes(f, k):
+            if not (0 <= f < src.F) or f in gone or first < 0 or k >= src.files[f].K or not takes(src, f, k):
                 return got
-            n = len(src.extent(f, k))
+            n = len(extent(src, f, k))
             if len(got) + 1 > out_istride - 1 or nbytes + n > out_stride:
                 return got
             got.append((f, k)); nbytes += n
@@ -147,7 +117,7 @@ class Expected:
 
     def __init__(self, src, blocks, out_istride):
         self.blocks = blocks
-        ext = [src.extent(f, k) for f, k in blocks]
+        ext = [extent(src, f, k) for f, k in blocks]
         self.payload = np.concatenate(ext).astype(np.uint8) if ext else np.zeros(0, np.uint8)
         self.nbytes, self.n = len(self.payload), len(blocks)
         self.max_block = max((len(e) for e in ext), default=0)
@@ -166,7 +136,7 @@ class Expected:
         """[n][bs][ch]: the oracle's sequential decode of the taken blocks as a file of their own."""
         if not self.blocks:
             return np.zeros((0, self._src.bs, self._src.ch), np.float32)
-        rows = np.stack([self._src.row(f, k) for f, k in self.blocks])
+        rows = np.stack([row(self._src, f, k) for f, k in self.blocks])
         pcm, bits = oracle_pcm(rows, self._src.ch, self._src.bs)
         assert np.array_equal(bits, self.bits)
         return pcm

@@ -6,9 +6,10 @@ here runs the library under test."""
 import functools
 import numpy as np
 import mdct_referee as R
-from ulc_testlib import oracle_decode_stream_coefs, spec_stream
-from seek_testlib import geometries
-from spectra_testlib import wc_of, same_bits, subblocks_of, big_stream
+from ulc_testlib import spec_stream, same_bits, to_pcm16
+from seek_testlib import oracle_pcm
+from corpus_testlib import File, geom_files
+from spectra_testlib import subblocks_of, big_stream
 from test_transform_referee import ALL_CODES, TOL, all_codes_sequence
 
 SPECTRA_LR, SYNTH_WARM = 1, 2
@@ -18,43 +19,39 @@ BAD_CODES = (0, 0x05, 0x25, 0x100, -1, 0x7FFFFFFF)
 POISON_F, POISON_I16, POISON_I32 = np.float32(7.25), np.int16(0x5A5A), np.int32(0x5A5A5A5A)
 
 
-def to_pcm16(x):
-    return np.clip(np.rint(x.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)       # WavIO_Helper.c:56-63
+@functools.lru_cache(maxsize=None)
+def planes(f):
+    """A corpus_testlib.File's coefficients as the call takes them: [C][K][bs]."""
+    assert (f.obits > 0).all(), f.name
+    return np.ascontiguousarray(f.coef.transpose(1, 0, 2))
 
 
-class StreamRef:
-    """One stream from the oracle's sequential decode of the whole file: coef [C][K][bs], wc [K] (the decoder's WindowCtrl of every
-    block), pcm [C][K * bs]."""
+@functools.lru_cache(maxsize=None)
+def pcm_planes(f):
+    """A File's sequential decode as the call writes it: [C][K * bs]."""
+    return np.ascontiguousarray(f.pcm.reshape(f.K * f.bs, f.ch).T)
 
-    def __init__(self, name, bs, ch, blocks):
-        rc, pcm, bits, coefs = oracle_decode_stream_coefs(blocks, ch, bs)
-        assert rc == 0 and (bits > 0).all(), name
-        self.name, self.bs, self.ch, self.K = name, bs, ch, blocks.shape[0]
-        self.coef = np.ascontiguousarray(coefs.reshape(self.K, ch, bs).transpose(1, 0, 2))
-        self.wc = wc_of(blocks)
-        self.pcm = np.ascontiguousarray(pcm.T)
 
-    def row(self, first, n_out, warm):
-        """-> (coef [C][nPl][bs], wc [nPl], pcm [C][n_out * bs], live [n_out]) of the row whose output starts at block `first`:
-        planes first - warm .. first + n_out - 1, zeros with code 0 past the stream's end; the PCM of the sequential decode."""
-        assert first - warm >= 0
-        n_pl = n_out + warm
-        coef, wc = np.zeros((self.ch, n_pl, self.bs), np.float32), np.zeros(n_pl, np.int32)
-        pcm, live = np.zeros((self.ch, n_out * self.bs), np.float32), np.zeros(n_out, np.int32)
-        p0 = first - warm
-        m = max(0, min(n_pl, self.K - p0))
-        coef[:, :m], wc[:m] = self.coef[:, p0:p0 + m], self.wc[p0:p0 + m]
-        mo = max(0, min(n_out, self.K - first))
-        pcm[:, :mo * self.bs] = self.pcm[:, first * self.bs:(first + mo) * self.bs]
-        live[:mo] = 1
-        return coef, wc, pcm, live
+def row(f, first, n_out, warm):
+    """-> (coef [C][nPl][bs], wc [nPl], pcm [C][n_out * bs], live [n_out]) of the row of File f whose output starts at block `first`:
+    planes first - warm .. first + n_out - 1, zeros with code 0 past the stream's end; the PCM of the sequential decode."""
+    assert first - warm >= 0
+    n_pl = n_out + warm
+    coef, wc = np.zeros((f.ch, n_pl, f.bs), np.float32), np.zeros(n_pl, np.int32)
+    pcm, live = np.zeros((f.ch, n_out * f.bs), np.float32), np.zeros(n_out, np.int32)
+    p0 = first - warm
+    m = max(0, min(n_pl, f.K - p0))
+    coef[:, :m], wc[:m] = planes(f)[:, p0:p0 + m], f.wc[p0:p0 + m]
+    mo = max(0, min(n_out, f.K - first))
+    pcm[:, :mo * f.bs] = pcm_planes(f)[:, first * f.bs:(first + mo) * f.bs]
+    live[:mo] = 1
+    return coef, wc, pcm, live
 
 
 @functools.lru_cache(maxsize=None)
 def geom_streams(geom):
     """The oracle-encoded and hand-assembled streams of a geometry of seek_testlib.geometries()."""
-    bs, ch = geom
-    return [StreamRef(name, bs, ch, blocks) for name, blocks, _, _ in geometries()[geom]]
+    return geom_files(geom)
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,8 +60,8 @@ def code_stream(bs, ch, seed=7):
     order, behind one plain block."""
     headers = all_codes_sequence(seed, lead=[0])
     blocks, coefs, _ = spec_stream(headers, ch, bs, seed)
-    ref = StreamRef(f"every header code {bs}x{ch}", bs, ch, blocks)
-    assert np.array_equal(ref.coef, coefs.reshape(ref.K, ch, bs).transpose(1, 0, 2))
+    ref = File(f"every header code {bs}x{ch}", bs, ch, blocks, oracle_pcm(blocks, ch, bs)[1])
+    assert np.array_equal(ref.coef, coefs.reshape(ref.K, ch, bs))
     assert {int(w) if w & 8 else int(w) & 7 for w in ref.wc} == set(ALL_CODES)
     return ref
 
@@ -72,8 +69,7 @@ def code_stream(bs, ch, seed=7):
 @functools.lru_cache(maxsize=None)
 def big_ref():
     """Three blocks at 32768 x 1 (spectra_testlib.big_stream, with transients)."""
-    f = big_stream(1, True)
-    return StreamRef(f.name, f.bs, f.ch, f.blocks)
+    return big_stream(1, True)
 
 
 def switched(ref):
@@ -98,7 +94,7 @@ def warm_rows(refs, n_out=N_OUT, total=70, seed=5):
 
 def stack(refs, rows, n_out, warm):
     """-> (coef [n][C][nPl][bs], wc [n][nPl], pcm [n][C][n_out * bs], live [n][n_out]) of (stream, first) rows."""
-    parts = [refs[s].row(first, n_out, warm) for s, first in rows]
+    parts = [row(refs[s], first, n_out, warm) for s, first in rows]
     return tuple(np.stack([p[i] for p in parts]) for i in range(4))
 
 
@@ -110,7 +106,7 @@ def head_rows(refs, n_out=N_OUT, total=70):
     while len(coef) < total:
         ref = refs[i % len(refs)]
         t = n_out - (i // len(refs)) % n_out
-        c, w, p, l = ref.row(0, n_out, 0)
+        c, w, p, l = row(ref, 0, n_out, 0)
         c, w, p, l = c.copy(), w.copy(), p.copy(), l.copy()
         w[t:] = 0; p[:, t * ref.bs:] = 0; l[t:] = 0        # (the planes behind stay: a dead block's coefficients are not looked at)
         coef.append(c); wc.append(w); pcm.append(p); live.append(l)

@@ -4,13 +4,12 @@ the uninterrupted stream), what the call leaves of a "last call", and the tool's
 import os
 import re
 import subprocess
-import sys
-import wave
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from ulc_testlib import write_wav16
+from gpu_testlib import amd as _ulc
 from ulc_testlib import synth_pcm, oracle_encode_debug
 from rates_testlib import OracleStream
 
@@ -19,11 +18,6 @@ pytestmark = pytest.mark.gpu
 # (BlockSize, channels, Hz, K)
 GEOMETRIES = [(2048, 2, 44100, 12), (2048, 1, 44100, 12), (4096, 2, 48000, 10), (256, 2, 44100, 24), (1024, 3, 44100, 10),
               (512, 6, 48000, 10), (16384, 2, 44100, 4)]
-
-
-def _ulc():
-    import ulc_amd
-    return ulc_amd
 
 
 def _batch_pcm(bs, ch, rate, K, seed=41, B=6):
@@ -239,12 +233,6 @@ def test_device_pointers_on_a_side_stream_one_output_at_a_time():
 TOOL = os.path.join(ROOT, "ulc-codec_amd", "ulcx-tool")
 
 
-def _write_wav16(path, pcm16, rate):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(pcm16.shape[1]); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(pcm16.astype("<i2").tobytes())
-
-
 @pytest.mark.parametrize("devices", [1, 2])
 def test_cli_analyse_prints_the_average_complexity_of_each_file(tmp_path, devices):
     rate, ch, bs = 44100, 2, 2048
@@ -256,7 +244,7 @@ def test_cli_analyse_prints_the_average_complexity_of_each_file(tmp_path, device
             pcm16 = np.zeros((n, ch), np.int16)
         else:
             pcm16 = np.clip(np.rint(synth_pcm(80 + i, n, ch, rate, transient=(kind == "transient"), seed=17) * 32767.0), -32768, 32767).astype(np.int16)
-        _write_wav16(work / f"f{i}.wav", pcm16, rate)
+        write_wav16(work / f"f{i}.wav", pcm16, rate)
         ins.append((work / f"f{i}.wav", pcm16))
     env = dict(os.environ)
     env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")

@@ -9,15 +9,12 @@ and the refusal of misaligned pointers.
 No case passes a pointer, size or index the header forbids; every store these tests look for lands inside the arena."""
 import ctypes as C
 import functools
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd, dev as _dev, word
 import guarded_buffers as gb
-from ulc_testlib import synth_pcm, oracle_decode_stream, synth_block_stream
+from ulc_testlib import synth_pcm, oracle_decode_stream, synth_block_stream, to_pcm16
 from rates_testlib import OracleStream
 from seek_testlib import oracle_stream, pack, oracle_seeds, oracle_pcm, expected_range
 
@@ -37,16 +34,6 @@ GEOMS = [(2048, 2, 5, 3, 5),                                # wave writer with d
 CALLS = 2                                                   # consecutive calls per object: the second one starts from carried state
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
 def _sync():
     import torch
     torch.cuda.synchronize()
@@ -58,10 +45,6 @@ def _sync():
 @functools.lru_cache(maxsize=None)
 def _pcm(bs, ch, B, nblk):
     return np.stack([synth_pcm(s, nblk * bs, ch, RATE, transient=True, seed=bs + ch) for s in range(B)])     # [B][n][C]
-
-
-def _pcm16(x):
-    return np.rint(x * 32768.0).astype(np.int16)           # exact: synth_pcm is on the PCM16 grid
 
 
 @functools.lru_cache(maxsize=None)
@@ -141,7 +124,7 @@ def _enc_call(amd, enc, geom, call, entry, what, wc=True, cplx=True, tag=""):
     R = len(rungs)
     a = _enc_arena(_dev(), geom, enc.slot, K, pcm16, R=R, tables=len(tabs), wc=wc, cplx=cplx, out=not analyse)
     x = _pcm(bs, ch, B, CALLS * K)[:, call * K * bs:(call + 1) * K * bs]
-    a.load("d_pcm", _pcm16(x) if pcm16 else x)
+    a.load("d_pcm", to_pcm16(x) if pcm16 else x)          # exact: synth_pcm is on the PCM16 grid
     for t, g in enumerate(tabs):
         a.load(f"d_rate{t}", g)
     p = a.ptr
@@ -241,10 +224,6 @@ def test_analyse_entries_on_poisoned_guarded_buffers(geom):
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. decoder entries, slot form
 # ---------------------------------------------------------------------------------------------------------------------
-def _to_pcm16(x):
-    return np.rint(np.clip(x * np.float32(32768.0), -32768.0, 32767.0)).astype(np.int16)      # WavIO_Helper.c:56-63
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle_blocks(bs, ch, B, nblk):
     """Oracle-encoded VBR 50 blocks [B][nblk][wide slot] and their sizes in bytes."""
@@ -325,7 +304,7 @@ def _dec_slot_run(blocks, ch, bs, K, maxK, tag, cut=None, ref_blocks=None):
             gbits = a.fetch("d_bits", np.int32).reshape(B, K)
             got = a.fetch("d_pcm", np.int16 if pcm16 else np.float32).reshape(B, K, bs, ch)
             w = want[:, c * K:(c + 1) * K]
-            w = _to_pcm16(w) if pcm16 else w
+            w = to_pcm16(w) if pcm16 else w
             assert np.array_equal(gbits, wbits[:, c * K:(c + 1) * K]), f"{t}: bits consumed differ: {_first_diff(gbits, wbits[:, c * K:(c + 1) * K])}"
             assert _same_bits(got, w), f"{t}: decoded samples differ (dead streams {dead} must be silent from there on): {_first_diff(got, w)}"
             if cut is not None:
@@ -390,10 +369,6 @@ def test_decode_even_cut_on_poisoned_guarded_buffers():
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. packed streams: pack, packed decode, index, range
 # ---------------------------------------------------------------------------------------------------------------------
-def _word_spec(name, n, role, maxn=None, rps=1):
-    return dict(name=name, nbytes=4 * n, align=A_WORD, role=role, guard=4 * (maxn or n), row=4, rows_per_stream=rps)
-
-
 def test_pack_streams_on_poisoned_guarded_buffers():
     """ulcx_pack_streams_dev: d_payload[s, :payloadBytes[s]] is the host concatenation, d_payloadBytes and d_maxBlock are
     written in full; with d_maxBlock NULL the rest is the same.  The rest of a payload row is not defined (the header)."""
@@ -407,11 +382,11 @@ def test_pack_streams_on_poisoned_guarded_buffers():
     stride = max(len(p) for p in pays) + 37                 # (an odd stride: rows start anywhere)
     for with_max in (True, False):
         specs = [dict(name="d_slots", nbytes=B * K * slot, align=A_BYTE, role="in", guard=B * maxK * slot, row=slot, rows_per_stream=K),
-                 _word_spec("d_bits", B * K, "in", B * maxK, K),
+                 word("d_bits", B * K, "in", B * maxK, K),
                  dict(name="d_payload", nbytes=B * stride, align=A_BYTE, role="out", guard=B * maxK * slot, row=stride),
-                 _word_spec("d_payloadBytes", B, "out")]
+                 word("d_payloadBytes", B, "out")]
         if with_max:
-            specs.append(_word_spec("d_maxBlock", B, "out"))
+            specs.append(word("d_maxBlock", B, "out"))
         a = gb.build(_dev(), specs)
         a.load("d_slots", blocks); a.load("d_bits", bits)
         rc = amd.lib().ulcx_pack_streams_dev(0, B, K, slot, a.ptr("d_slots"), a.ptr("d_bits"), a.ptr("d_payload"), stride, a.ptr("d_payloadBytes"),
@@ -467,9 +442,9 @@ def test_packed_decode_and_index_on_poisoned_guarded_buffers():
     dec = amd.BatchDecoder(B, ch, bs, maxK)
     for c in range(2):
         a = gb.build(_dev(), [dict(name="d_payload", nbytes=B * stride, align=A_BYTE, role="in", guard=B * stride, row=stride),
-                              _word_spec("d_payloadBytes", B, "in"),
+                              word("d_payloadBytes", B, "in"),
                               dict(name="d_pcm", nbytes=B * K * row, align=A_PCM, role="out", guard=B * maxK * row, row=row, rows_per_stream=K),
-                              _word_spec("d_bits", B * K, "out", B * maxK, K)])
+                              word("d_bits", B * K, "out", B * maxK, K)])
         a.load("d_payload", host); a.load("d_payloadBytes", nbytes)
         dec.decode_packed_dev(a.ptr("d_payload"), stride, a.ptr("d_payloadBytes"), K, a.ptr("d_pcm"), a.ptr("d_bits"))
         _sync()
@@ -485,9 +460,9 @@ def test_packed_decode_and_index_on_poisoned_guarded_buffers():
     # index: maxBlocks = L + 3
     maxB = L + 3
     a = gb.build(_dev(), [dict(name="d_payload", nbytes=B * stride, align=A_BYTE, role="in", guard=B * stride, row=stride),
-                          _word_spec("d_payloadBytes", B, "in"),
+                          word("d_payloadBytes", B, "in"),
                           dict(name="d_index", nbytes=8 * B * (maxB + 1), align=A_WORD, role="out", guard=8 * B * (maxB + 1), row=8, rows_per_stream=maxB + 1),
-                          _word_spec("d_nBlocks", B, "out")])
+                          word("d_nBlocks", B, "out")])
     a.load("d_payload", host); a.load("d_payloadBytes", nbytes)
     dec.index_packed_dev(a.ptr("d_payload"), stride, a.ptr("d_payloadBytes"), maxB, a.ptr("d_index"), a.ptr("d_nBlocks"))
     _sync()
@@ -507,11 +482,11 @@ def _range_call(amd, dec, host, nbytes, index, count, first, N, maxK, bs, ch, pc
     row = bs * ch * esz
     istride = index.shape[1]
     a = gb.build(_dev(), [dict(name="d_payload", nbytes=B * stride, align=A_BYTE, role="in", guard=B * stride, row=stride),
-                          _word_spec("d_payloadBytes", B, "in"),
+                          word("d_payloadBytes", B, "in"),
                           dict(name="d_index", nbytes=8 * B * istride, align=A_WORD, role="in", guard=8 * B * istride, row=8, rows_per_stream=istride),
-                          _word_spec("d_indexBlocks", B, "in"), _word_spec("d_first", B, "in"),
+                          word("d_indexBlocks", B, "in"), word("d_first", B, "in"),
                           dict(name="d_pcm", nbytes=B * N * row, align=A_PCM16 if pcm16 else A_PCM, role="out", guard=B * maxK * row, row=row, rows_per_stream=N),
-                          _word_spec("d_bits", B * N, "out", B * maxK, N)])
+                          word("d_bits", B * N, "out", B * maxK, N)])
     a.load("d_payload", host); a.load("d_payloadBytes", nbytes); a.load("d_index", index); a.load("d_indexBlocks", count); a.load("d_first", first)
     dec.decode_range_dev(a.ptr("d_payload"), stride, a.ptr("d_payloadBytes"), a.ptr("d_index"), istride, a.ptr("d_indexBlocks"), a.ptr("d_first"), N,
                          a.ptr("d_pcm"), a.ptr("d_bits"), pcm16=pcm16)
@@ -537,7 +512,7 @@ def test_range_entries_on_poisoned_guarded_buffers(pcm16):
     for s in range(B):
         p, b = refs[pick[s]]
         want, wb = expected_range(p, b, int(first[s]), N) if first[s] <= L else (np.zeros((N, bs, ch), np.float32), np.zeros(N, np.int32))
-        want = _to_pcm16(want) if pcm16 else want
+        want = to_pcm16(want) if pcm16 else want
         assert np.array_equal(gbits[s], wb), f"stream {s} from block {first[s]}: bits {gbits[s]} != {wb}"
         assert _same_bits(got[s], want), f"stream {s} from block {first[s]}: samples differ"
 
@@ -575,7 +550,7 @@ def test_range_tail_cut_on_poisoned_guarded_buffers():
             sel = np.flatnonzero((pick == j) & (first == f))
             if sel.size:
                 w, b = expected_range(refs[j][0], refs[j][1], f, N)
-                want[sel], wbits[sel] = _to_pcm16(w), b
+                want[sel], wbits[sel] = to_pcm16(w), b
     assert np.array_equal(gbits, wbits), f"bits differ: {_first_diff(gbits, wbits)}"
     assert _same_bits(got, want), f"samples differ: {_first_diff(got, want)}"
 
@@ -605,7 +580,7 @@ def test_host_forms_copy_back_exactly_their_extents():
         sp = [dict(name="h_pcm", nbytes=B * K * row, align=4, role="in", guard=B * maxK * row, row=row, rows_per_stream=K)]
         sp += [dict(name=f"h_rate{t}", nbytes=8 * B, align=4, role="in", row=8) for t in range(tables)]
         sp += [dict(name="h_out", nbytes=R * B * K * slot, align=1, role="out", guard=B * maxK * slot, row=slot, rows_per_stream=K),
-               _word_spec("h_bits", R * B * K, "out", B * maxK, K), _word_spec("h_wc", B * K, "out", B * maxK, K), _word_spec("h_cplx", B * K, "out", B * maxK, K)]
+               word("h_bits", R * B * K, "out", B * maxK, K), word("h_wc", B * K, "out", B * maxK, K), word("h_cplx", B * K, "out", B * maxK, K)]
         return sp
 
     def enc_check(a, R, whats, tag):
@@ -635,7 +610,7 @@ def test_host_forms_copy_back_exactly_their_extents():
                                      _hp(a.ptr("h_wc"), i32p), _hp(a.ptr("h_cplx"), f32p)) == 0
     enc_check(a, 3, [VBR50, tab, CBR64], "ulcx_encode_host_ladder")
     enc.reset()
-    a = gb.build(None, [enc_specs(1)[0], _word_spec("h_wc", B * K, "out", B * maxK, K), _word_spec("h_cplx", B * K, "out", B * maxK, K)])
+    a = gb.build(None, [enc_specs(1)[0], word("h_wc", B * K, "out", B * maxK, K), word("h_cplx", B * K, "out", B * maxK, K)])
     a.load("h_pcm", x)
     assert L.ulcx_analyse_host(enc.h, _hp(a.ptr("h_pcm"), f32p), K, _hp(a.ptr("h_wc"), i32p), _hp(a.ptr("h_cplx"), f32p)) == 0
     a.check()
@@ -652,7 +627,7 @@ def test_host_forms_copy_back_exactly_their_extents():
     dec = amd.BatchDecoder(B, ch, bs, maxK)
     pcm_spec = dict(name="h_pcm", nbytes=B * K * row, align=4, role="out", guard=B * maxK * row, row=row, rows_per_stream=K)
     a = gb.build(None, [dict(name="h_in", nbytes=B * K * wslot, align=1, role="in", guard=B * maxK * wslot, row=wslot, rows_per_stream=K), pcm_spec,
-                        _word_spec("h_bits", B * K, "out", B * maxK, K)])
+                        word("h_bits", B * K, "out", B * maxK, K)])
     a.load("h_in", blocks)
     assert L.ulcx_decode_host(dec.h, _hp(a.ptr("h_in"), u8p), wslot, K, _hp(a.ptr("h_pcm"), f32p), _hp(a.ptr("h_bits"), i32p)) == 0
     a.check()
@@ -665,9 +640,9 @@ def test_host_forms_copy_back_exactly_their_extents():
     pick = np.arange(B) % 4
     host, nbytes = np.ascontiguousarray(host4[pick]), nb4[pick].copy()
     stride = host.shape[1]
-    pay_specs = [dict(name="h_payload", nbytes=B * stride, align=1, role="in", guard=B * stride, row=stride), _word_spec("h_payloadBytes", B, "in")]
+    pay_specs = [dict(name="h_payload", nbytes=B * stride, align=1, role="in", guard=B * stride, row=stride), word("h_payloadBytes", B, "in")]
     dec = amd.BatchDecoder(B, ch, bs, maxK)
-    a = gb.build(None, pay_specs + [pcm_spec, _word_spec("h_bits", B * K, "out", B * maxK, K)])
+    a = gb.build(None, pay_specs + [pcm_spec, word("h_bits", B * K, "out", B * maxK, K)])
     a.load("h_payload", host); a.load("h_payloadBytes", nbytes)
     assert L.ulcx_decode_packed_host(dec.h, _hp(a.ptr("h_payload"), u8p), stride, _hp(a.ptr("h_payloadBytes"), i32p), K, _hp(a.ptr("h_pcm"), f32p),
                                      _hp(a.ptr("h_bits"), i32p)) == 0
@@ -678,7 +653,7 @@ def test_host_forms_copy_back_exactly_their_extents():
         assert np.array_equal(gbits[s], b) and _same_bits(got[s], w), f"ulcx_decode_packed_host stream {s}"
     maxB = Ls + 2
     a = gb.build(None, pay_specs + [dict(name="h_index", nbytes=8 * B * (maxB + 1), align=4, role="out", guard=8 * B * (maxB + 1), row=8, rows_per_stream=maxB + 1),
-                                    _word_spec("h_nBlocks", B, "out")])
+                                    word("h_nBlocks", B, "out")])
     a.load("h_payload", host); a.load("h_payloadBytes", nbytes)
     assert L.ulcx_index_packed_host(dec.h, _hp(a.ptr("h_payload"), u8p), stride, _hp(a.ptr("h_payloadBytes"), i32p), maxB, C.c_void_p(a.ptr("h_index")),
                                     _hp(a.ptr("h_nBlocks"), i32p)) == 0
@@ -687,7 +662,7 @@ def test_host_forms_copy_back_exactly_their_extents():
     assert np.array_equal(a.fetch("h_nBlocks", np.int32), wcnt) and np.array_equal(a.fetch("h_index", amd.INDEX_DTYPE).reshape(B, maxB + 1), widx), "ulcx_index_packed_host"
     first = np.array([0, 2, 5, 3, 1], np.int32)
     a = gb.build(None, pay_specs + [dict(name="h_index", nbytes=8 * B * (maxB + 1), align=4, role="in", row=8, rows_per_stream=maxB + 1),
-                                    _word_spec("h_indexBlocks", B, "in"), _word_spec("h_first", B, "in"), pcm_spec, _word_spec("h_bits", B * K, "out", B * maxK, K)])
+                                    word("h_indexBlocks", B, "in"), word("h_first", B, "in"), pcm_spec, word("h_bits", B * K, "out", B * maxK, K)])
     a.load("h_payload", host); a.load("h_payloadBytes", nbytes); a.load("h_index", widx); a.load("h_indexBlocks", wcnt); a.load("h_first", first)
     assert L.ulcx_decode_range_host(dec.h, _hp(a.ptr("h_payload"), u8p), stride, _hp(a.ptr("h_payloadBytes"), i32p), C.c_void_p(a.ptr("h_index")), maxB + 1,
                                     _hp(a.ptr("h_indexBlocks"), i32p), _hp(a.ptr("h_first"), i32p), K, _hp(a.ptr("h_pcm"), f32p), _hp(a.ptr("h_bits"), i32p)) == 0

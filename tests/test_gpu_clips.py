@@ -6,33 +6,17 @@ Shapes: (BlockSize, nChan) = (256, 2), (512, 1), (256, 3); maxBlocksPerCall = 2,
 middle of one; nSamples = 5 * BS + 3; seven rows of 0, 1, BS - 1, BS, BS + 1, 3 * BS + 7 and nSamples samples.  All outputs sit
 on poisoned buffers between guards (tests/guarded_buffers.py).  tests/test_gpu_clips_paths.py runs the same call (Call, _check_rows)
 at the shapes where the launch sequence pipelines its chunks, and at scale."""
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from ulc_testlib import to_pcm16
+from gpu_testlib import amd as _amd, dev as _dev
 import guarded_buffers as gb
 import clips_testlib as ct
 from ulc_testlib import synth_pcm, oracle_encode_debug
 
 pytestmark = pytest.mark.gpu
 N, B, MAXK = 7, 8, 2
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _to_pcm16(x):
-    return np.clip(np.rint(x.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)
 
 
 class Call:
@@ -62,7 +46,7 @@ class Call:
                   word("d_indexBlocks", n, "out")]
         a = self.a = gb.build(_dev(), specs)
         w = ct.wave(bs, ch, T)[rows]
-        a.load("d_pcm", _to_pcm16(w) if pcm16 else w)
+        a.load("d_pcm", to_pcm16(w) if pcm16 else w)
         if not null_len:
             a.load("d_len", np.array(case.lengths, np.int32)[rows])
         if table:

@@ -4,96 +4,34 @@ oracle's sequential decode of the named file (tests/seek_testlib.py), never agai
 the calls are given come from the oracle too (its block sizes and generator states)."""
 import ctypes as C
 import functools
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
-from seek_testlib import (ORACLE_BLOCKS, geometries, oracle_stream, synth_stream, pack, oracle_seeds, oracle_pcm, expected_range,
-                          switched_starts, oracle_walk)
+from ulc_testlib import same_bits, wc_of
+from gpu_testlib import amd as _amd
+from seek_testlib import ORACLE_BLOCKS, geometries, switched_starts, oracle_walk
+from corpus_testlib import Corpus, geom_files, oracle_file, synth_file
 
 pytestmark = pytest.mark.gpu
 GEOMS = sorted(geometries().keys())
 POISON_F, POISON_I = 7.0, 7
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32).ravel(), np.ascontiguousarray(b, np.float32).ravel()
-    return a.size == b.size and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def _wc_of(blocks):
-    """WindowCtrl of every block from its first byte (ulcDecoder.c:211-216): what switched_starts() needs of a stream the
-    oracle did not encode."""
-    b = blocks[:, 0].astype(np.int32)
-    wc = b & 0xF
-    return np.where((wc & 8) != 0, wc | (b & 0xF0), wc | 0x10)
-
-
-@functools.lru_cache(maxsize=None)
-def _seeds(bs, ch, key):
-    return oracle_seeds(_STREAMS[key][0], ch, bs)
-
-
-_STREAMS = {}
-
-
-class Corpus:
-    """Files [(blocks, bits)] of one geometry: packed payloads, the oracle's index of each, the oracle's decode of each."""
-
-    def __init__(self, bs, ch, files, keys):
-        import ulc_amd
-        self.bs, self.ch, self.F = bs, ch, len(files)
-        self.host, self.nbytes = pack(files)
-        self.K = [len(bits) for _, bits in files]
-        self.istride = max(self.K) + 1
-        self.index = ulc_amd.new_index(self.F, self.istride)
-        for f, ((blocks, bits), key) in enumerate(zip(files, keys)):
-            _STREAMS[key] = (blocks, bits)
-            self.index["ByteOffs"][f, :self.K[f] + 1] = np.concatenate([[0], np.cumsum((bits.astype(np.int64) + 7) // 8)])
-            self.index["RngState"][f, :self.K[f] + 1] = _seeds(bs, ch, key)
-        self.count = np.array(self.K, np.int32)
-        self.refs = [oracle_pcm(blocks, ch, bs) for blocks, _ in files]
-        self.dev = None
-
-    def to_device(self):
-        import torch
-        if self.dev is None:
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-            self.dev = dict(pay=t(self.host), nb=t(self.nbytes), idx=t(self.index.view(np.int32).reshape(self.F, -1)), cnt=t(self.count))
-        return self.dev
-
-    def expected(self, f, first, N, count=None):
-        want, wb = expected_range(self.refs[f][0], self.refs[f][1], int(first), N)
-        if count is not None:
-            m = max(0, min(N, int(count)))
-            want[m:] = 0; wb[m:] = 0
-        return want, wb
-
-
 @functools.lru_cache(maxsize=None)
 def _geom_corpus(geom):
-    bs, ch = geom
-    st = geometries()[geom]
-    for name, blocks, bits, wc in st:
+    for (name, _, _, wc), f in zip(geometries()[geom], geom_files(geom)):
         if wc is not None:
-            assert np.array_equal(_wc_of(blocks), np.asarray(wc)), f"{name}: window codes read from the blocks differ from the oracle's"
-    return Corpus(bs, ch, [(blocks, bits) for _, blocks, bits, _ in st], [(geom, name) for name, _, _, _ in st])
+            assert np.array_equal(f.wc, np.asarray(wc)), f"{name}: window codes read from the blocks differ from the oracle's"
+    return Corpus(geom_files(geom))
+
+
+FOUR = ((50.0, 3), (50.0, 4), (35.0, 5), (65.0, 6))         # (VBR quality, synth_pcm stream id) of four distinct 2048 x 2 streams
 
 
 @functools.lru_cache(maxsize=None)
 def _five_files():
     """Five distinct 2048 x 2 streams: oracle-encoded ids 3 .. 6 and the hand-assembled one."""
-    bs, ch = 2048, 2
-    files = [oracle_stream(bs, ch, q, sid)[:2] for q, sid in ((50.0, 3), (50.0, 4), (35.0, 5), (65.0, 6))] + [synth_stream(bs, ch)]
-    return Corpus(bs, ch, files, [("five", i) for i in range(5)])
+    return Corpus([oracle_file(2048, 2, q, sid) for q, sid in FOUR] + [synth_file(2048, 2)])
 
 
 def _device_crops(dec, cor, files, first, N, count=None, pcm16=False, dev=None, keep=False):
@@ -115,12 +53,12 @@ def _device_crops(dec, cor, files, first, N, count=None, pcm16=False, dev=None, 
 
 def _check_rows(cor, files, first, N, pcm, bits, what, count=None, rows=None):
     for i in (range(len(files)) if rows is None else rows):
-        want, wb = cor.expected(files[i], first[i], N, None if count is None else count[i])
+        want, wb = cor.files[files[i]].expected_pcm(first[i], N, None if count is None else count[i])
         brow, prow = (bits[i].cpu().numpy(), pcm[i].cpu().numpy()) if hasattr(bits, "cpu") else (bits[i], pcm[i])
         assert np.array_equal(brow, wb), f"{what}: row {i} (file {files[i]} from block {first[i]}): bits {bits[i]} vs the oracle's {wb}"
         got = np.asarray(prow).reshape(N, cor.bs, cor.ch)
         for k in range(N):
-            assert _same_bits(got[k], want[k]), f"{what}: row {i}: block {first[i] + k} of file {files[i]} differs from the oracle's sequential decode"
+            assert same_bits(got[k], want[k], shape=False), f"{what}: row {i}: block {first[i] + k} of file {files[i]} differs from the oracle's sequential decode"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -141,7 +79,7 @@ def test_crops_equal_the_oracles_slices(geom):
     bs, ch = geom
     cor = _geom_corpus(geom)
     st = geometries()[geom]
-    sw = [switched_starts(_wc_of(blocks)) for _, blocks, _, _ in st]
+    sw = [switched_starts(wc_of(blocks)) for _, blocks, _, _ in st]
     for (name, _, _, wc), s in zip(st, sw):
         assert len(s) >= 3, f"{name}: {len(s)} starts behind a window-switched block"
     if geom == (2048, 2):
@@ -197,9 +135,9 @@ def test_counts_shorten_rows():
     assert (bits[0] == 0).all() and (pcm[0] == 0).all() and bits[1, 0] > 0 and (bits[1, 1:] == 0).all() and (pcm[1, 1:] == 0).all()
     full, fbits = _device_crops(dec, cor, files, first, N)
     for i in (2, 3):                                       # a count of nBlocks or more: the row without one
-        assert np.array_equal(bits[i], fbits[i]) and _same_bits(pcm[i], full[i]), i
+        assert np.array_equal(bits[i], fbits[i]) and same_bits(pcm[i], full[i], shape=False), i
     hp, hb = dec.decode_crops(cor.host, cor.nbytes, cor.index, cor.count, files, first, N, count=count)
-    assert np.array_equal(hb, bits) and _same_bits(hp, pcm), "host form with counts"
+    assert np.array_equal(hb, bits) and same_bits(hp, pcm, shape=False), "host form with counts"
     dec.close()
 
 
@@ -230,8 +168,8 @@ def test_crop_calls_leave_every_streams_state_untouched():
     def packed(at, n, what):
         pcm, bits = dec.decode_packed(host, nbytes, n)
         for s in range(B):
-            want, wb = cor.expected(pick[s], at, n)
-            assert np.array_equal(bits[s], wb) and _same_bits(pcm[s], want), f"{what}: stream {s}, blocks {at}.."
+            want, wb = cor.files[pick[s]].expected_pcm(at, n)
+            assert np.array_equal(bits[s], wb) and same_bits(pcm[s], want, shape=False), f"{what}: stream {s}, blocks {at}.."
 
     packed(0, 6, "first half")
     before = dec.save_streams(slots)
@@ -248,8 +186,8 @@ def test_crop_calls_leave_every_streams_state_untouched():
     assert before.tobytes() == dec.save_streams(slots).tobytes()
     pcm, bits = dec.decode_packed(host, nbytes, 3)
     for s in range(B):
-        want, wb = cor.expected(pick[s], first[s] + 4, 3)
-        assert np.array_equal(bits[s], wb) and _same_bits(pcm[s], want), f"packed call behind range and crops: stream {s}"
+        want, wb = cor.files[pick[s]].expected_pcm(first[s] + 4, 3)
+        assert np.array_equal(bits[s], wb) and same_bits(pcm[s], want, shape=False), f"packed call behind range and crops: stream {s}"
     # around subset calls: slots 1, 4 and 6 decode slot-form blocks from the start, with crop calls between the two halves
     st = geometries()[(2048, 2)]
     sub = [1, 4, 6]
@@ -261,9 +199,9 @@ def test_crop_calls_leave_every_streams_state_untouched():
     assert before.tobytes() == dec.save_streams(slots).tobytes()
     pcm2, bits2 = dec.decode_subset(sub, blocks[:, 4:8])
     for i, s in enumerate(sub):
-        want, wb = cor.expected(pick[s], 0, 8)
+        want, wb = cor.files[pick[s]].expected_pcm(0, 8)
         got = np.concatenate([pcm[i].reshape(4, bs, ch), pcm2[i].reshape(4, bs, ch)])
-        assert np.array_equal(np.concatenate([bits[i], bits2[i]]), wb) and _same_bits(got, want), f"subset calls around crops: slot {s}"
+        assert np.array_equal(np.concatenate([bits[i], bits2[i]]), wb) and same_bits(got, want, shape=False), f"subset calls around crops: slot {s}"
     dec.close()
 
 
@@ -311,8 +249,7 @@ def test_bad_rows_are_silent_and_leave_their_neighbours_alone():
     files = [0, -1, 1, 3, 0, 1, 2, 2, 0, 1 << 30]
     first = [4, 4, 9, 0, -1, int(count[1]) + 1, 9, 20, 30, 0]
     bad = {1, 3, 4, 5, 6, 9}                                # (row 6 spans the moved entry; row 7, of the same file, does not)
-    big = Corpus.__new__(Corpus)
-    big.__dict__.update(cor.__dict__); big.F = 3; big.refs = cor.refs + cor.refs[:1]
+    big = Corpus(cor.files + cor.files[:1])
     dec = amd.BatchDecoder(16, cor.ch, cor.bs, N + 1)
     pcm, bits = _device_crops(dec, big, files, first, N, dev=dev)
     for i in sorted(bad):
@@ -345,7 +282,7 @@ def test_bad_rows_are_silent_and_leave_their_neighbours_alone():
 # ---------------------------------------------------------------------------------------------------------------------
 def test_few_long_crops_take_the_even_cut():
     amd = _amd()
-    two = Corpus(2048, 2, [oracle_stream(2048, 2, 50.0, sid)[:2] for sid in (3, 4)], [("two", 3), ("two", 4)])
+    two = Corpus([oracle_file(2048, 2, 50.0, sid) for sid in (3, 4)])
     assert two.K == [40, 40]
     n, N = 8, 32
     dec = amd.BatchDecoder(n, two.ch, two.bs, N + 1)
@@ -372,7 +309,7 @@ def test_many_crops_take_the_cut_of_the_last_round():
     full = C.c_int32(0)
     tail = amd.lib().ulcx_dec_range_tail_plan(n, N, resident, C.byref(full))
     assert tail > 0 and full.value == resident, (n, resident, tail)
-    cor = Corpus(bs, ch, [oracle_stream(bs, ch, q, sid)[:2] for q, sid in ((50.0, 3), (50.0, 4), (35.0, 5), (65.0, 6))], [("five", i) for i in range(4)])
+    cor = Corpus([oracle_file(bs, ch, q, sid) for q, sid in FOUR])
     rng = np.random.default_rng(21)
     files = rng.integers(0, 4, n).astype(np.int32)
     first = rng.integers(0, ORACLE_BLOCKS - N + 1, n).astype(np.int32)

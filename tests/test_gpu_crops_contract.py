@@ -2,56 +2,27 @@
 call carved from one poisoned arena between guards (tests/guarded_buffers.py), each pointer misaligned in turn, and follow-up
 work on the call's stream without a synchronisation.  The reference is the oracle's sequential decode (tests/seek_testlib.py)."""
 import functools
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from ulc_testlib import to_pcm16, same_bytes
+from gpu_testlib import amd as _amd, dev as _dev, word
 import guarded_buffers as gb
-from seek_testlib import oracle_stream, pack, oracle_seeds, oracle_pcm, expected_range
+from seek_testlib import expected_range
+from corpus_testlib import Corpus, oracle_file
 
 pytestmark = pytest.mark.gpu
 A_PCM, A_PCM16, A_WORD, A_BYTE = 16, 8, 4, 1               # the header's ALIGNMENT table
 BS, CH, L, F, B, N, MAXK = 2048, 2, 6, 4, 8, 3, 5          # four files of 6 blocks; a decoder of 8 streams, 5 blocks per call; calls of 3
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a).ravel(), np.ascontiguousarray(b).ravel()
-    return a.dtype == b.dtype and a.size == b.size and a.tobytes() == b.tobytes()
-
-
-def _to_pcm16(x):
-    return np.clip(np.rint(x.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)       # WavIO_Helper.c:56-63
-
-
 @functools.lru_cache(maxsize=None)
 def _corpus():
     """Four oracle streams packed with no byte behind the longest (the payload buffer ends with the last file's stride), their
     index from the oracle's block sizes and generator states, and the oracle's decode of each."""
-    import ulc_amd
-    base = [oracle_stream(BS, CH, q, sid, 11, L) for q, sid in ((50.0, 3), (50.0, 4), (35.0, 5), (65.0, 6))]
-    host, nb = pack([(blk, bits) for blk, bits, _ in base], pad=0)
-    index = ulc_amd.new_index(F, L + 1)
-    for f, (blk, bits, _) in enumerate(base):
-        index["ByteOffs"][f] = np.concatenate([[0], np.cumsum((bits.astype(np.int64) + 7) // 8)])
-        index["RngState"][f] = oracle_seeds(blk, CH, BS)
-    return np.ascontiguousarray(host), nb, index, np.full(F, L, np.int32), [oracle_pcm(blk, CH, BS) for blk, _, _ in base]
-
-
-def _word(name, n, role, maxn=None, rps=1):
-    return dict(name=name, nbytes=4 * n, align=A_WORD, role=role, guard=4 * (maxn or n), row=4, rows_per_stream=rps)
+    cor = Corpus([oracle_file(BS, CH, q, sid, 11, L) for q, sid in ((50.0, 3), (50.0, 4), (35.0, 5), (65.0, 6))])
+    tight = (int(cor.nbytes.max()) + 15) & ~15
+    return np.ascontiguousarray(cor.host[:, :tight]), cor.nbytes, cor.index, cor.count, [(f.pcm, f.obits) for f in cor.files]
 
 
 def _arena(n, pcm16, with_count=True):
@@ -59,13 +30,13 @@ def _arena(n, pcm16, with_count=True):
     stride = host.shape[1]
     row = BS * CH * (2 if pcm16 else 4)
     specs = [dict(name="d_payload", nbytes=F * stride, align=A_BYTE, role="in", guard=F * stride, row=stride),
-             _word("d_payloadBytes", F, "in"),
+             word("d_payloadBytes", F, "in"),
              dict(name="d_index", nbytes=8 * F * (L + 1), align=A_WORD, role="in", guard=8 * F * (L + 1), row=8, rows_per_stream=L + 1),
-             _word("d_indexBlocks", F, "in"), _word("d_file", n, "in", B), _word("d_first", n, "in", B)]
+             word("d_indexBlocks", F, "in"), word("d_file", n, "in", B), word("d_first", n, "in", B)]
     if with_count:
-        specs.append(_word("d_count", n, "in", B))
+        specs.append(word("d_count", n, "in", B))
     specs += [dict(name="d_pcm", nbytes=n * N * row, align=A_PCM16 if pcm16 else A_PCM, role="out", guard=B * MAXK * row, row=row, rows_per_stream=N),
-              _word("d_bits", n * N, "out", B * MAXK, N)]
+              word("d_bits", n * N, "out", B * MAXK, N)]
     a = gb.build(_dev(), specs)
     a.load("d_payload", host); a.load("d_payloadBytes", nb); a.load("d_index", index); a.load("d_indexBlocks", count)
     return a, stride
@@ -87,7 +58,7 @@ def _expected(files, first, count, pcm16):
         if count is not None:
             m = max(0, min(N, int(count[i])))
             want[m:] = 0; wb[m:] = 0
-        out.append(_to_pcm16(want) if pcm16 else want); ob.append(wb)
+        out.append(to_pcm16(want) if pcm16 else want); ob.append(wb)
     return np.stack(out), np.stack(ob)
 
 
@@ -97,7 +68,7 @@ def _check(a, n, files, first, count, pcm16, what):
     want, wb = _expected(files, first, count, pcm16)
     for i in range(n):
         assert np.array_equal(gbits[i], wb[i]), f"{what}: row {i} (file {files[i]} from block {first[i]}): bits {gbits[i]} != {wb[i]}"
-        assert _same_bits(got[i], want[i]), f"{what}: row {i} (file {files[i]} from block {first[i]}): samples differ"
+        assert same_bytes(got[i], want[i], shape=False), f"{what}: row {i} (file {files[i]} from block {first[i]}): samples differ"
 
 
 ROWS = ([3, 0, 3, 1, 2, F], [0, 2, 5, 3, L + 1, 0], [3, 3, 3, 1, 3, 3])      # row 2 runs past its end; rows 4 and 5: a bad start, a bad file
@@ -158,7 +129,7 @@ def test_misaligned_crop_pointers_are_refused_and_nothing_is_touched(pcm16):
     pcm, bits = dec.decode_packed(host[pick], nb[pick], 2)  # the packed decode goes on
     for s in range(B):
         want, wb = expected_range(refs[pick[s]][0], refs[pick[s]][1], 2, 2)
-        assert np.array_equal(bits[s], wb) and _same_bits(pcm[s].reshape(2, BS, CH), want), f"stream {s} behind the crop call"
+        assert np.array_equal(bits[s], wb) and same_bytes(pcm[s].reshape(2, BS, CH), want, shape=False), f"stream {s} behind the crop call"
     dec.close()
 
 
@@ -199,4 +170,4 @@ def test_work_behind_a_crop_call_on_its_stream_is_ordered():
         gbits = saved[c]["d_bits"].cpu().numpy().view(np.int32).reshape(n, N)
         want, wb = _expected(files, first, count, False)
         assert np.array_equal(gbits, wb), f"call {c}: bits {gbits.tolist()} != {wb.tolist()}"
-        assert _same_bits(got, want), f"call {c}: samples differ"
+        assert same_bytes(got, want, shape=False), f"call {c}: samples differ"

@@ -4,15 +4,14 @@ _dev_pcm16 / _host and ulcx_index_packed_ragged_dev: every buffer of a call carv
 synchronisation.  The reference is the oracle's sequential decode and its walk (tests/ragged_testlib.py)."""
 import ctypes as C
 import functools
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd, dev as _dev, word
 import guarded_buffers as gb
-from ragged_testlib import INDEX_DTYPE, Ragged, file_refs, to_pcm16, same_bytes
+from ulc_testlib import to_pcm16, same_bytes
+from corpus_testlib import INDEX_DTYPE, Corpus
+from ragged_testlib import file_refs
 
 pytestmark = pytest.mark.gpu
 A_PCM, A_PCM16, A_OFFS, A_WORD, A_BYTE = 16, 8, 8, 4, 1    # the header's ALIGNMENT table
@@ -20,31 +19,17 @@ BS, CH, B, N, MAXK = 2048, 2, 8, 3, 5                      # a decoder of 8 stre
 SENT = (0x5A5A5A5A, 0xA5A5A5A5)
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
 @functools.lru_cache(maxsize=None)
 def _corpus():
     """The files of 2, 7, 12 and 40 blocks with NO byte behind the last payload: the buffer ends with the longest file's last block."""
     r = file_refs((BS, CH))
-    cor = Ragged([r[1], r[2], r[3], r[4]])
-    cor.payload = np.ascontiguousarray(cor.payload[:cor.poffs[-1]])
+    cor = Corpus([r[1], r[2], r[3], r[4]])
+    cor.rpay = np.ascontiguousarray(cor.rpay[:cor.poffs[-1]])
     return cor
 
 
 F = 4
 K = (2, 7, 12, 40)
-
-
-def _word(name, n, role, maxn=None, rps=1):
-    return dict(name=name, nbytes=4 * n, align=A_WORD, role=role, guard=4 * (maxn or n), row=4, rows_per_stream=rps)
 
 
 def _offs(name):
@@ -54,17 +39,17 @@ def _offs(name):
 def _arena(n, pcm16, with_count=True, device="gpu"):
     cor = _corpus()
     row = BS * CH * (2 if pcm16 else 4)
-    specs = [dict(name="d_payload", nbytes=cor.payload.size, align=A_BYTE, role="in", guard=cor.payload.size, row=cor.payload.size),
+    specs = [dict(name="d_payload", nbytes=cor.rpay.size, align=A_BYTE, role="in", guard=cor.rpay.size, row=cor.rpay.size),
              _offs("d_payloadOffs"),
-             dict(name="d_index", nbytes=8 * cor.index.size, align=A_WORD, role="in", guard=8 * cor.index.size, row=8),
-             _offs("d_indexOffs"), _word("d_indexBlocks", F, "in"), _word("d_file", n, "in", B), _word("d_first", n, "in", B)]
+             dict(name="d_index", nbytes=8 * cor.ridx.size, align=A_WORD, role="in", guard=8 * cor.ridx.size, row=8),
+             _offs("d_indexOffs"), word("d_indexBlocks", F, "in"), word("d_file", n, "in", B), word("d_first", n, "in", B)]
     if with_count:
-        specs.append(_word("d_count", n, "in", B))
+        specs.append(word("d_count", n, "in", B))
     specs += [dict(name="d_pcm", nbytes=n * N * row, align=A_PCM16 if pcm16 else A_PCM, role="out", guard=B * MAXK * row, row=row, rows_per_stream=N),
-              _word("d_bits", n * N, "out", B * MAXK, N)]
+              word("d_bits", n * N, "out", B * MAXK, N)]
     a = gb.build(_dev() if device == "gpu" else None, specs)
-    a.load("d_payload", cor.payload); a.load("d_payloadOffs", cor.poffs); a.load("d_index", cor.index); a.load("d_indexOffs", cor.ioffs)
-    a.load("d_indexBlocks", cor.blocks)
+    a.load("d_payload", cor.rpay); a.load("d_payloadOffs", cor.poffs); a.load("d_index", cor.ridx); a.load("d_indexOffs", cor.ioffs)
+    a.load("d_indexBlocks", cor.count)
     return a
 
 
@@ -72,18 +57,18 @@ def _call(dec, a, n, pcm16, stream=0, off=None):
     """off: {name: bytes} added to a pointer (the misalignment cases)"""
     cor = _corpus()
     p = lambda name: (a.ptr(name) + (off or {}).get(name, 0)) if name in a.regions else 0
-    dec.decode_crops_ragged_dev(F, p("d_payload"), cor.payload.size, p("d_payloadOffs"), p("d_index"), cor.index.size, p("d_indexOffs"), p("d_indexBlocks"),
+    dec.decode_crops_ragged_dev(F, p("d_payload"), cor.rpay.size, p("d_payloadOffs"), p("d_index"), cor.ridx.size, p("d_indexOffs"), p("d_indexBlocks"),
                                 n, p("d_file"), p("d_first"), p("d_count"), N, p("d_pcm"), p("d_bits"), stream=stream, pcm16=pcm16)
 
 
 def _check(a, n, files, first, count, pcm16, what):
     got = a.fetch("d_pcm", np.int16 if pcm16 else np.float32).reshape(n, N, BS, CH)
     gbits = a.fetch("d_bits", np.int32).reshape(n, N)
-    want, wb = _corpus().expected(files, first, N, count)
+    want, wb = _corpus().expected_pcm(files, first, N, count)
     want = to_pcm16(want) if pcm16 else want
     for i in range(n):
         assert np.array_equal(gbits[i], wb[i]), f"{what}: row {i} (file {files[i]} from block {first[i]}): bits {gbits[i]} != {wb[i]}"
-        assert same_bytes(got[i], want[i]), f"{what}: row {i} (file {files[i]} from block {first[i]}): samples differ"
+        assert same_bytes(got[i], want[i], shape=False), f"{what}: row {i} (file {files[i]} from block {first[i]}): samples differ"
 
 
 # row 1 ends with the buffer's last byte; row 2 runs past its file's end; rows 4 and 5: a bad start, a bad file
@@ -120,8 +105,8 @@ def test_ragged_host_form_on_poisoned_guarded_host_buffers():
     a.load("d_file", np.array(files, np.int32)); a.load("d_first", np.array(first, np.int32)); a.load("d_count", np.array(count, np.int32))
     dec = amd.BatchDecoder(B, CH, BS, MAXK)
     p = lambda name, t: C.cast(a.ptr(name), C.POINTER(t))
-    rc = amd.lib().ulcx_decode_crops_ragged_host(dec.h, F, p("d_payload", C.c_uint8), cor.payload.size, p("d_payloadOffs", C.c_int64), a.ptr("d_index"),
-                                                 cor.index.size, p("d_indexOffs", C.c_int64), p("d_indexBlocks", C.c_int32), n, p("d_file", C.c_int32),
+    rc = amd.lib().ulcx_decode_crops_ragged_host(dec.h, F, p("d_payload", C.c_uint8), cor.rpay.size, p("d_payloadOffs", C.c_int64), a.ptr("d_index"),
+                                                 cor.ridx.size, p("d_indexOffs", C.c_int64), p("d_indexBlocks", C.c_int32), n, p("d_file", C.c_int32),
                                                  p("d_first", C.c_int32), p("d_count", C.c_int32), N, p("d_pcm", C.c_float), p("d_bits", C.c_int32))
     dec.close()
     assert rc == 0, amd.lib().ulcx_last_error().decode()
@@ -136,29 +121,29 @@ def test_ragged_index_on_poisoned_guarded_buffers():
     amd = _amd()
     cor = _corpus()
     ioffs = cor.ioffs + 3
-    index = np.zeros(cor.index.size + 6, INDEX_DTYPE)
+    index = np.zeros(cor.ridx.size + 6, INDEX_DTYPE)
     index["ByteOffs"], index["RngState"] = SENT
-    specs = [dict(name="d_payload", nbytes=cor.payload.size, align=A_BYTE, role="in", guard=cor.payload.size, row=cor.payload.size),
+    specs = [dict(name="d_payload", nbytes=cor.rpay.size, align=A_BYTE, role="in", guard=cor.rpay.size, row=cor.rpay.size),
              _offs("d_payloadOffs"),
              dict(name="d_index", nbytes=8 * index.size, align=A_WORD, role="inout", guard=8 * index.size, row=8),
-             _offs("d_indexOffs"), _word("d_nBlocks", F, "out")]
+             _offs("d_indexOffs"), word("d_nBlocks", F, "out")]
     a = gb.build(_dev(), specs)
-    a.load("d_payload", cor.payload); a.load("d_payloadOffs", cor.poffs); a.load("d_index", index); a.load("d_indexOffs", ioffs)
+    a.load("d_payload", cor.rpay); a.load("d_payloadOffs", cor.poffs); a.load("d_index", index); a.load("d_indexOffs", ioffs)
     dec = amd.BatchDecoder(1, CH, BS, 2)
-    dec.index_packed_ragged_dev(F, a.ptr("d_payload"), cor.payload.size, a.ptr("d_payloadOffs"), a.ptr("d_index"), index.size, a.ptr("d_indexOffs"),
+    dec.index_packed_ragged_dev(F, a.ptr("d_payload"), cor.rpay.size, a.ptr("d_payloadOffs"), a.ptr("d_index"), index.size, a.ptr("d_indexOffs"),
                                 a.ptr("d_nBlocks"))
     torch.cuda.synchronize()
     a.check()
     want = index.copy()
-    want[3:-3] = cor.index
-    assert np.array_equal(a.fetch("d_nBlocks", np.int32), cor.blocks)
+    want[3:-3] = cor.ridx
+    assert np.array_equal(a.fetch("d_nBlocks", np.int32), cor.count)
     assert np.array_equal(a.fetch("d_index").view(INDEX_DTYPE), want)
     # each pointer misaligned in turn: refused, nothing written
     a.repoison("d_nBlocks"); a.load("d_index", index)
     for name, by in (("d_payloadOffs", 4), ("d_indexOffs", 4), ("d_index", 2), ("d_nBlocks", 2)):
         p = lambda k: a.ptr(k) + (by if k == name else 0)
         with pytest.raises(amd.UlcError, match=r"\(-1\).*" + name + r".*not aligned"):
-            dec.index_packed_ragged_dev(F, p("d_payload"), cor.payload.size, p("d_payloadOffs"), p("d_index"), index.size, p("d_indexOffs"), p("d_nBlocks"))
+            dec.index_packed_ragged_dev(F, p("d_payload"), cor.rpay.size, p("d_payloadOffs"), p("d_index"), index.size, p("d_indexOffs"), p("d_nBlocks"))
     torch.cuda.synchronize()
     dec.close()
     a.check()
@@ -176,7 +161,7 @@ def test_misaligned_ragged_crop_pointers_are_refused_and_nothing_is_touched(pcm1
     files, first, count = ROWS
     n = len(files)
     cor = _corpus()
-    host, nb, _, _ = cor.strided()
+    host, nb = cor.host, cor.nbytes
     a = _arena(n, pcm16)
     a.load("d_file", np.array(files, np.int32)); a.load("d_first", np.array(first, np.int32)); a.load("d_count", np.array(count, np.int32))
     dec = amd.BatchDecoder(B, CH, BS, MAXK)
@@ -199,9 +184,9 @@ def test_misaligned_ragged_crop_pointers_are_refused_and_nothing_is_touched(pcm1
     _check(a, n, files, first, count, pcm16, "valid call behind the refused ones")
     assert before.tobytes() == dec.save_streams(list(range(B))).tobytes(), "the crop call changed a stream's state"
     pcm, bits = dec.decode_packed(host[pick], nb[pick], 2)  # the packed decode goes on
-    want, wb = cor.expected(list(pick), [2] * B, 2)
+    want, wb = cor.expected_pcm(list(pick), [2] * B, 2)
     for s in range(B):
-        assert np.array_equal(bits[s], wb[s]) and same_bytes(pcm[s].reshape(2, BS, CH), want[s]), f"stream {s} behind the crop call"
+        assert np.array_equal(bits[s], wb[s]) and same_bytes(pcm[s].reshape(2, BS, CH), want[s], shape=False), f"stream {s} behind the crop call"
     dec.close()
 
 
@@ -240,6 +225,6 @@ def test_work_behind_a_ragged_crop_call_on_its_stream_is_ordered():
     for c, (files, first, count) in enumerate(calls):
         got = saved[c]["d_pcm"].cpu().numpy().view(np.float32).reshape(n, N, BS, CH)
         gbits = saved[c]["d_bits"].cpu().numpy().view(np.int32).reshape(n, N)
-        want, wb = _corpus().expected(files, first, N, count)
+        want, wb = _corpus().expected_pcm(files, first, N, count)
         assert np.array_equal(gbits, wb), f"call {c}: bits {gbits.tolist()} != {wb.tolist()}"
-        assert same_bytes(got, want), f"call {c}: samples differ"
+        assert same_bytes(got, want, shape=False), f"call {c}: samples differ"

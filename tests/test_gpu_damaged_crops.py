@@ -5,37 +5,18 @@ cut to its index extent - and never against this library's own decode.  Outputs 
 tests/test_damage_model.py checks the model and the damaged copies themselves on the CPU."""
 import ctypes as C
 import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd, to_dev as _t
 import damage_testlib as D
-from damage_testlib import same_bytes, blocks_of
+from ulc_testlib import same_bytes
+from damage_testlib import blocks_of
 
 pytestmark = pytest.mark.gpu
 POISON_F, POISON_I = 7.0, 7
 N = 4                                                       # blocks per row of the small calls
 FMT = pytest.mark.parametrize("pcm16", [False, True], ids=["float", "pcm16"])
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).to("cuda:0")
-
-
-def _dev(cor):
-    """The corpus on the device, in both layouts (once per corpus)."""
-    if getattr(cor, "dev", None) is None:
-        cor.dev = dict(pay=_t(cor.host), nb=_t(cor.nbytes), idx=_t(cor.index.view(np.int32).reshape(cor.F, -1)), cnt=_t(cor.count),
-                       rag=_t(cor.ragged), poffs=_t(cor.poffs), ioffs=_t(cor.ioffs))
-    return cor.dev
 
 
 def _outputs(shape, nbits, pcm16):
@@ -48,13 +29,13 @@ def _outputs(shape, nbits, pcm16):
 def _crops(dec, cor, files, first, n_blocks, pcm16=False, ragged=False, keep=False, count=None):
     """ulcx_decode_crops(_ragged)_dev(_pcm16) on poisoned outputs -> (pcm [n][n_blocks][bs][ch], bits [n][n_blocks])."""
     import torch
-    d, n = _dev(cor), len(files)
+    d, n = cor.to_device(), len(files)
     d_file, d_first = _t(files, np.int32), _t(first, np.int32)
     d_count = _t(count, np.int32) if count is not None else None
     cp = d_count.data_ptr() if d_count is not None else 0
     pcm, bits = _outputs((n, n_blocks, cor.bs, cor.ch), (n, n_blocks), pcm16)
     if ragged:
-        dec.decode_crops_ragged_dev(cor.F, d["rag"].data_ptr(), d["rag"].numel(), d["poffs"].data_ptr(), d["idx"].data_ptr(), cor.F * cor.istride,
+        dec.decode_crops_ragged_dev(cor.F, d["rpay"].data_ptr(), d["rpay"].numel(), d["poffs"].data_ptr(), d["idx"].data_ptr(), cor.F * cor.istride,
                                     d["ioffs"].data_ptr(), d["cnt"].data_ptr(), n, d_file.data_ptr(), d_first.data_ptr(), cp, n_blocks,
                                     pcm.data_ptr(), bits.data_ptr(), pcm16=pcm16)
     else:
@@ -67,7 +48,7 @@ def _crops(dec, cor, files, first, n_blocks, pcm16=False, ragged=False, keep=Fal
 def _range(dec, cor, first, n_blocks, pcm16=False):
     """ulcx_decode_range_dev(_pcm16): the corpus's files are the decoder's streams -> (pcm [F][n_blocks][bs][ch], bits [F][n_blocks])."""
     import torch
-    d = _dev(cor)
+    d = cor.to_device()
     d_first = _t(first, np.int32)
     pcm, bits = _outputs((cor.F, n_blocks, cor.bs, cor.ch), (cor.F, n_blocks), pcm16)
     dec.decode_range_dev(d["pay"].data_ptr(), cor.stride, d["nb"].data_ptr(), d["idx"].data_ptr(), cor.istride, d["cnt"].data_ptr(),
@@ -79,13 +60,13 @@ def _range(dec, cor, first, n_blocks, pcm16=False):
 def _samples(dec, cor, files, start, n_samples, length=None, pcm16=False, ragged=False):
     """ulcx_decode_crops_samples(_ragged)_dev(_pcm16) on poisoned outputs -> (pcm [n][ch][n_samples], bits [n][nB])."""
     import torch
-    d, n = _dev(cor), len(files)
+    d, n = cor.to_device(), len(files)
     d_file, d_start = _t(files, np.int32), _t(start, np.int64)
     d_len = _t(length, np.int32) if length is not None else None
     pcm, bits = _outputs((n, cor.ch, n_samples), (n, blocks_of(cor.bs, n_samples)), pcm16)
     lp = d_len.data_ptr() if d_len is not None else 0
     if ragged:
-        dec.decode_crops_samples_ragged_dev(cor.F, d["rag"].data_ptr(), d["rag"].numel(), d["poffs"].data_ptr(), d["idx"].data_ptr(), cor.F * cor.istride,
+        dec.decode_crops_samples_ragged_dev(cor.F, d["rpay"].data_ptr(), d["rpay"].numel(), d["poffs"].data_ptr(), d["idx"].data_ptr(), cor.F * cor.istride,
                                             d["ioffs"].data_ptr(), d["cnt"].data_ptr(), n, d_file.data_ptr(), d_start.data_ptr(), lp, n_samples,
                                             pcm.data_ptr(), bits.data_ptr(), pcm16=pcm16)
     else:

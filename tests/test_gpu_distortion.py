@@ -3,13 +3,10 @@ rows against caller-held reference planes.  Every comparison of sums is bit for 
 (tests/distortion_testlib.py: numpy float64, separate * and -, the pairwise tree) on the oracle's coded coefficients
 (tests/spectra_testlib.py); d_wc and d_bits against the oracle's.  The device calls run on poisoned buffers carved between guards
 (tests/guarded_buffers.py), the reference planes among them.  What the inputs hold is asserted in tests/test_distortion_capi.py."""
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd, dev as _dev, word
 import guarded_buffers as gb
 import spectra_testlib as S
 import distortion_testlib as T
@@ -22,24 +19,6 @@ LR = S.SPECTRA_LR
 N_REF, N_RB = 3, N + 2                                     # reference rows and blocks per row of the row tests
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _word(name, n, role, rps=1):
-    return dict(name=name, nbytes=4 * n, align=4, role=role, guard=4 * n, row=4, rows_per_stream=rps)
-
-
-def strided(cor):
-    return dict(host=cor.host, nbytes=cor.nbytes, index=cor.index, count=cor.count)
-
-
 def dist_dev(dec, lay, ch, bs, files, first, nb, n_seg, ref=None, ref_row=None, ref_first=None, count=None, flags=0, n_ref=None, n_rb=None):
     """One ulcx_decode_crops_distortion(_ragged)_dev call with every buffer - the reference planes and the two reference tables
     included - carved from a poisoned arena between guards -> (dist [n][ch][nb][n_seg][3], wc [n][nb], bits [n][nb]) after the
@@ -48,24 +27,24 @@ def dist_dev(dec, lay, ch, bs, files, first, nb, n_seg, ref=None, ref_row=None, 
     import torch
     n = len(files)
     ragged = "poffs" in lay
-    specs = [_word("d_indexBlocks", len(lay["blocks" if ragged else "count"]), "in"), _word("d_file", n, "in"), _word("d_first", n, "in")]
+    specs = [word("d_indexBlocks", len(lay["blocks" if ragged else "count"]), "in"), word("d_file", n, "in"), word("d_first", n, "in")]
     if ragged:
         specs += [dict(name="d_payload", nbytes=lay["payload"].size, align=1, role="in"),
                   dict(name="d_payloadOffs", nbytes=8 * lay["poffs"].size, align=8, role="in"),
                   dict(name="d_index", nbytes=8 * lay["index"].size, align=4, role="in"),
                   dict(name="d_indexOffs", nbytes=8 * lay["ioffs"].size, align=8, role="in")]
     else:
-        specs += [dict(name="d_payload", nbytes=lay["host"].size, align=1, role="in", row=lay["host"].shape[1]), _word("d_payloadBytes", lay["nbytes"].size, "in"),
+        specs += [dict(name="d_payload", nbytes=lay["host"].size, align=1, role="in", row=lay["host"].shape[1]), word("d_payloadBytes", lay["nbytes"].size, "in"),
                   dict(name="d_index", nbytes=8 * lay["index"].size, align=4, role="in")]
     for name, v in (("d_count", count), ("d_refRow", ref_row), ("d_refFirst", ref_first)):
         if v is not None:
-            specs.append(_word(name, n, "in"))
+            specs.append(word(name, n, "in"))
     if ref is not None:
         specs.append(dict(name="d_ref", nbytes=ref.nbytes, align=16, role="in", guard=4 * ref.shape[1] * ref.shape[2] * bs, row=4 * bs,
                           rows_per_stream=ref.shape[1] * ref.shape[2]))
     cell = 8 * 3 * n_seg
     specs += [dict(name="d_dist", nbytes=n * ch * nb * cell, align=8, role="out", guard=ch * nb * cell, row=cell, rows_per_stream=ch * nb),
-              _word("d_wc", n * nb, "out", nb), _word("d_bits", n * nb, "out", nb)]
+              word("d_wc", n * nb, "out", rps=nb), word("d_bits", n * nb, "out", rps=nb)]
     a = gb.build(_dev(), specs)
     a.load("d_file", np.array(files, np.int32)); a.load("d_first", np.array(first, np.int32))
     for name, v in (("d_count", count), ("d_refRow", ref_row), ("d_refFirst", ref_first)):
@@ -142,7 +121,7 @@ def test_rows_equal_the_referee_on_the_oracles_coefficients(geom, with_count):
     ref_row, ref_first = [i % N_REF for i in range(n)], [i % 3 for i in range(n)]
     dec = _amd().BatchDecoder(n, ch, bs, N + 1)
     for n_seg in (1, 8, 64):
-        got = dist_dev(dec, strided(cor), ch, bs, files, first, N, n_seg, ref, ref_row, ref_first, count)
+        got = dist_dev(dec, cor.strided(), ch, bs, files, first, N, n_seg, ref, ref_row, ref_first, count)
         want = T.expected_rows(cor, files, first, N, n_seg, ref, ref_row, ref_first, count)
         check(got, want, files, first, f"{bs} x {ch}, nSeg {n_seg}")
     assert dec.last_cut()[:2] == (0, 0)
@@ -159,10 +138,10 @@ def test_seventy_rows_share_files_and_reference_rows():
     ref = T.ref_planes(N_REF, 2, N_RB, 2048, seed=9)
     ref_row = [(i * 7) % N_REF for i in range(n)]
     dec = _amd().BatchDecoder(n, 2, 2048, N + 1)
-    got = dist_dev(dec, strided(cor), 2, 2048, files, first, N, 16, ref, ref_row)
+    got = dist_dev(dec, cor.strided(), 2, 2048, files, first, N, 16, ref, ref_row)
     check(got, T.expected_rows(cor, files, first, N, 16, ref, ref_row), files, first, "seventy rows")
     # d_refRow NULL: row i takes reference row i - rows 3 .. 69 have none
-    got = dist_dev(dec, strided(cor), 2, 2048, files, first, N, 16, ref)
+    got = dist_dev(dec, cor.strided(), 2, 2048, files, first, N, 16, ref)
     want = T.expected_rows(cor, files, first, N, 16, ref)
     check(got, want, files, first, "seventy rows, d_refRow NULL")
     assert not want[0][3:, ..., 0].any() and want[0][:3, ..., 0].any()
@@ -179,7 +158,7 @@ def test_against_its_own_spectra_the_error_is_zero(flags):
     n = len(files)
     dec = _amd().BatchDecoder(n, 3, 2048, N + 1)
     coef, wc, bits = spectra_planes(dec, cor, files, first, N, flags=flags)
-    got = dist_dev(dec, strided(cor), 3, 2048, files, first, N, 8, np.ascontiguousarray(coef), flags=flags)
+    got = dist_dev(dec, cor.strided(), 3, 2048, files, first, N, 8, np.ascontiguousarray(coef), flags=flags)
     dec.close()
     assert np.array_equal(got[1], wc) and np.array_equal(got[2], bits)
     assert not got[0][..., 2].view(np.uint64).any(), "E is not +0.0 everywhere"
@@ -193,7 +172,7 @@ def test_without_a_reference_the_call_gives_the_coded_energies(flags):
     n = len(files)
     dec = _amd().BatchDecoder(n, 2, 4096, N + 1)
     coef, wc, bits = spectra_planes(dec, cor, files, first, N, flags=flags)
-    got = dist_dev(dec, strided(cor), 2, 4096, files, first, N, 32, None, flags=flags, n_ref=-5, n_rb=-7)     # (the counts: ignored without d_ref)
+    got = dist_dev(dec, cor.strided(), 2, 4096, files, first, N, 32, None, flags=flags, n_ref=-5, n_rb=-7)     # (the counts: ignored without d_ref)
     dec.close()
     want = T.sums(np.zeros_like(coef), coef, 32)
     assert np.array_equal(got[1], wc) and np.array_equal(got[2], bits)
@@ -214,7 +193,7 @@ def test_reference_rows_and_blocks_outside_the_reference_count_as_zeros():
     ref = T.ref_planes(N_REF, 2, N_RB, 2048, seed=3)
     ref_row, ref_first = T.absent_tables(n, N_REF, N_RB)
     dec = _amd().BatchDecoder(n, 2, 2048, N + 1)
-    got = dist_dev(dec, strided(cor), 2, 2048, files, first, N, 8, ref, ref_row, ref_first)
+    got = dist_dev(dec, cor.strided(), 2, 2048, files, first, N, 8, ref, ref_row, ref_first)
     want = T.expected_rows(cor, files, first, N, 8, ref, ref_row, ref_first)
     check(got, want, files, first, "absent references")
     out = T.outside(ref_row, ref_first, N_REF, N_RB)
@@ -223,7 +202,7 @@ def test_reference_rows_and_blocks_outside_the_reference_count_as_zeros():
     assert not S_.transpose(0, 2, 1, 3)[out].any() and S_.transpose(0, 2, 1, 3)[~out & live].all(axis=(-1, -2)).all()
     assert T.same_bits64(got[0][..., 2].transpose(0, 2, 1, 3)[out], got[0][..., 1].transpose(0, 2, 1, 3)[out])
     # the blocks without a reference are, in all three sums, those of the call without d_ref
-    base = dist_dev(dec, strided(cor), 2, 2048, files, first, N, 8, None)
+    base = dist_dev(dec, cor.strided(), 2, 2048, files, first, N, 8, None)
     assert T.same_bits64(got[0].transpose(0, 2, 1, 3, 4)[out], base[0].transpose(0, 2, 1, 3, 4)[out])
     dec.close()
     assert (out & live).sum() > 20 and (~out & live).sum() > 20
@@ -242,10 +221,10 @@ def test_lr_sums_the_unmixed_pairs_and_leaves_a_single_channel(geom):
     ref_row = [i % N_REF for i in range(n)]
     dec = _amd().BatchDecoder(n, ch, bs, N + 1)
     n_seg = 64 if bs == 256 else 4
-    got = dist_dev(dec, strided(cor), ch, bs, files, first, N, n_seg, ref, ref_row, flags=LR)
+    got = dist_dev(dec, cor.strided(), ch, bs, files, first, N, n_seg, ref, ref_row, flags=LR)
     want = T.expected_rows(cor, files, first, N, n_seg, ref, ref_row, lr=True)
     check(got, want, files, first, f"{bs} x {ch}, LR")
-    ms = dist_dev(dec, strided(cor), ch, bs, files, first, N, n_seg, ref, ref_row)
+    ms = dist_dev(dec, cor.strided(), ch, bs, files, first, N, n_seg, ref, ref_row)
     dec.close()
     for c in range(0, ch - 1, 2):
         assert not T.same_bits64(got[0][:, c], ms[0][:, c]) and not T.same_bits64(got[0][:, c + 1], ms[0][:, c + 1])
@@ -263,10 +242,10 @@ def test_blocksize_32768_takes_the_one_array_path_and_refuses_lr(ch):
     ref_row = [i % 2 for i in range(len(rows))]
     dec = amd.BatchDecoder(len(rows), ch, 32768, 3)
     for n_seg in (1, 2, 64):
-        got = dist_dev(dec, strided(cor), ch, 32768, files, first, 2, n_seg, ref, ref_row)
+        got = dist_dev(dec, cor.strided(), ch, 32768, files, first, 2, n_seg, ref, ref_row)
         check(got, T.expected_rows(cor, files, first, 2, n_seg, ref, ref_row), files, first, f"32768 x {ch}, nSeg {n_seg}")
     with pytest.raises(amd.UlcError, match=r"\(-1\).*ULCX_SPECTRA_LR at BlockSize 32768"):
-        dist_dev(dec, strided(cor), ch, 32768, files, first, 2, 1, ref, ref_row, flags=LR)
+        dist_dev(dec, cor.strided(), ch, 32768, files, first, 2, 1, ref, ref_row, flags=LR)
     dec.close()
 
 
@@ -274,12 +253,12 @@ def test_blocksize_16384_is_the_largest_with_lr():
     amd = _amd()
     from seek_testlib import oracle_stream
     blocks, bits, _ = oracle_stream(16384, 2, 30.0, 3, n_blocks=3)
-    cor = S.Corpus([S.FileSpec("oracle 16384x2 q30", 16384, 2, blocks, bits)])
+    cor = S.Corpus([S.File("oracle 16384x2 q30", 16384, 2, blocks, bits)])
     files, first = [0, 0], [0, 1]
     ref = T.ref_planes(1, 2, 3, 16384, seed=4)
     dec = amd.BatchDecoder(2, 2, 16384, 3)
     for n_seg in (1, 64):
-        got = dist_dev(dec, strided(cor), 2, 16384, files, first, 2, n_seg, ref, [0, 0], [0, 1], flags=LR)
+        got = dist_dev(dec, cor.strided(), 2, 16384, files, first, 2, n_seg, ref, [0, 0], [0, 1], flags=LR)
         check(got, T.expected_rows(cor, files, first, 2, n_seg, ref, [0, 0], [0, 1], lr=True), files, first, f"16384 x 2 LR, nSeg {n_seg}")
     dec.close()
 
@@ -292,7 +271,7 @@ def test_units_of_more_than_2048_noise_coefficients():
     ref_row = [i % N_REF for i in range(len(rows))]
     dec = _amd().BatchDecoder(len(rows), 2, 4096, N + 1)
     for flags in (0, LR):
-        got = dist_dev(dec, strided(cor), 2, 4096, files, first, N, 16, ref, ref_row, flags=flags)
+        got = dist_dev(dec, cor.strided(), 2, 4096, files, first, N, 16, ref, ref_row, flags=flags)
         check(got, T.expected_rows(cor, files, first, N, 16, ref, ref_row, lr=bool(flags)), files, first, f"4096 x 2, flags {flags}")
     dec.close()
 
@@ -345,12 +324,12 @@ def test_the_device_sums_nest_from_64_segments_down_to_the_block(geom):
     ref = T.ref_planes(N_REF, ch, N_RB, bs, seed=12)
     ref_row = [i % N_REF for i in range(len(files))]
     dec = _amd().BatchDecoder(len(files), ch, bs, N + 1)
-    d = dist_dev(dec, strided(cor), ch, bs, files, first, N, 64, ref, ref_row)[0]
+    d = dist_dev(dec, cor.strided(), ch, bs, files, first, N, 64, ref, ref_row)[0]
     n_seg = 64
     while n_seg > 1:
         n_seg //= 2
         d = T.halve(d)
-        got = dist_dev(dec, strided(cor), ch, bs, files, first, N, n_seg, ref, ref_row)[0]
+        got = dist_dev(dec, cor.strided(), ch, bs, files, first, N, n_seg, ref, ref_row)[0]
         assert T.same_bits64(d, got), f"nSeg {n_seg}: {T.first_diff(d, got)}"
     dec.close()
 
@@ -373,7 +352,7 @@ def test_ragged_entries_equal_the_strided_ones(flags):
     check(got, T.expected_rows(cor, seen, first, N, 16, ref, ref_row, ref_first, count, lr=bool(flags)), files, first, "ragged")
     ok = [i for i, f in enumerate(files) if f != 2]
     pick = lambda v: [v[i] for i in ok]
-    st = dist_dev(dec, strided(cor), 2, 2048, pick(files), pick(first), N, 16, ref, pick(ref_row), pick(ref_first), pick(count), flags)
+    st = dist_dev(dec, cor.strided(), 2, 2048, pick(files), pick(first), N, 16, ref, pick(ref_row), pick(ref_first), pick(count), flags)
     dec.close()
     for j, i in enumerate(ok):
         assert T.same_bits64(st[0][j], got[0][i]) and np.array_equal(st[1][j], got[1][i]) and np.array_equal(st[2][j], got[2][i]), i
@@ -392,7 +371,7 @@ def test_host_forms_equal_the_device_forms_and_refuse_what_the_spectra_host_form
     dec = amd.BatchDecoder(n, 3, 2048, N + 1)
     rg = cor.ragged()
     for flags in (0, LR):
-        dev = dist_dev(dec, strided(cor), 3, 2048, files, first, N, 8, ref, ref_row, ref_first, count, flags)
+        dev = dist_dev(dec, cor.strided(), 3, 2048, files, first, N, 8, ref, ref_row, ref_first, count, flags)
         check(dev, T.expected_rows(cor, files, first, N, 8, ref, ref_row, ref_first, count, lr=bool(flags)), files, first, "device form")
         host = dec.decode_crops_distortion(cor.host, cor.nbytes, cor.index, cor.count, files, first, N, ref, ref_row, ref_first, count=count, n_seg=8, flags=flags)
         check(host, dev, files, first, "host form")
@@ -400,7 +379,7 @@ def test_host_forms_equal_the_device_forms_and_refuse_what_the_spectra_host_form
                                                 count=count, n_seg=8, flags=flags)
         check(hr, dev, files, first, "ragged host form")
     none = dec.decode_crops_distortion(cor.host, cor.nbytes, cor.index, cor.count, files, first, N, n_seg=8)
-    check(none, dist_dev(dec, strided(cor), 3, 2048, files, first, N, 8), files, first, "host form without a reference")
+    check(none, dist_dev(dec, cor.strided(), 3, 2048, files, first, N, 8), files, first, "host form without a reference")
     K = cor.K[0]
     for hf, h1, hc, why in (([0, 1], [0, 0], None, "names file 1"), ([0, -1], [0, 0], None, "names file -1"), ([0, 0], [0, K + 1], None, "starts at block"),
                             ([0, 0], [0, -1], None, "starts at block"), ([0, 0], [0, 0], [1, -1], "wants -1 blocks")):
@@ -500,11 +479,11 @@ def test_a_streaming_decode_continues_across_distortion_calls_and_a_sample_crop_
     stream_call(0)
     before = dec.save_streams(list(range(B)))
     for flags in (0, LR):
-        got = dist_dev(dec, strided(cor), ch, bs, files, first, N, 8, ref, ref_row, flags=flags)
+        got = dist_dev(dec, cor.strided(), ch, bs, files, first, N, 8, ref, ref_row, flags=flags)
         check(got, T.expected_rows(cor, files, first, N, 8, ref, ref_row, lr=bool(flags)), files, first, "between two streaming calls")
     assert before.tobytes() == dec.save_streams(list(range(B))).tobytes(), "a distortion call changed a stream's state"
     stream_call(1)
-    dist_dev(dec, strided(cor), ch, bs, files, first, N, 8, ref, ref_row)
+    dist_dev(dec, cor.strided(), ch, bs, files, first, N, 8, ref, ref_row)
     start, ns = [3 * bs + 100, 0, 20 * bs - 7], 2 * bs + 13
     pcm, _ = dec.decode_crops_samples(cor.host, cor.nbytes, cor.index, cor.count, [0, 1, 0], start, ns)
     for i, (f, st) in enumerate(zip([0, 1, 0], start)):
@@ -527,8 +506,8 @@ def test_nan_and_inf_in_the_reference_stay_inside_their_segment():
     for r, c, k, j, v in spots:
         bad[r, c, k, j] = v
     dec = _amd().BatchDecoder(2, 2, 2048, N + 1)
-    clean = dist_dev(dec, strided(cor), 2, 2048, files, first, N, n_seg, ref)
-    got = dist_dev(dec, strided(cor), 2, 2048, files, first, N, n_seg, bad)
+    clean = dist_dev(dec, cor.strided(), 2, 2048, files, first, N, n_seg, ref)
+    got = dist_dev(dec, cor.strided(), 2, 2048, files, first, N, n_seg, bad)
     dec.close()
     assert np.array_equal(got[1], clean[1]) and (clean[1] != 0).all()
     hit = np.zeros(got[0].shape[:4], bool)
@@ -569,7 +548,7 @@ def test_crop_corpus_distortion_is_the_c_call(layout):
         torch.cuda.synchronize()
         got = (dist.cpu().numpy(), wc.cpu().numpy(), bits.cpu().numpy())
         check(got, T.expected_rows(cor, files, first, N, 16, host_ref, ref_row, ref_first, count, lr=lr), files, first, f"CropCorpus.distortion, {layout}")
-        check(got, dist_dev(dec, strided(cor), cor.ch, cor.bs, files, first, N, 16, host_ref, ref_row, ref_first, count, LR if lr else 0), files, first, "the C call")
+        check(got, dist_dev(dec, cor.strided(), cor.ch, cor.bs, files, first, N, 16, host_ref, ref_row, ref_first, count, LR if lr else 0), files, first, "the C call")
     plain, _, _ = cc.distortion(dec, files, first, N)
     torch.cuda.synchronize()
     assert tuple(plain.shape) == (n, cor.ch, N, 1, 3) and not plain[..., 0].any() and torch.equal(plain[..., 1], plain[..., 2])
@@ -607,7 +586,7 @@ def test_a_ladders_distortion_plans_a_switch():
         coded = np.zeros((n, ch, nb, bs), np.float32)
         for c, i in enumerate(clips):
             cref = ct.ClipRef(bs, ch, ct.wave(bs, ch)[i][:, :lengths[c]], (-q, 0.0))
-            f = S.FileSpec(f"clip {i} q{q:g}", bs, ch, cref.blocks, cref.bits)
+            f = S.File(f"clip {i} q{q:g}", bs, ch, cref.blocks, cref.bits)
             coded[c, :, :f.K] = f.coef.transpose(1, 0, 2)
             assert np.array_equal(wc[c, :f.K].cpu().numpy(), f.wc) and not wc[c, f.K:].any() and np.array_equal(cwc[c, :f.K].cpu().numpy(), f.wc)
         want, _ = T.expected(coded, ref_np, None, None, 8)

@@ -7,25 +7,19 @@ import os
 import struct
 import subprocess
 import sys
-import wave
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
 from ulc_testlib import synth_pcm, oracle_encode_debug, oracle_decode_stream
+from ulc_testlib import write_wav16, run_tool
 
 pytestmark = pytest.mark.gpu
 ENC = os.path.join(ROOT, "oracle", "_ref", "ulcencodetool_amd")
 DEC = os.path.join(ROOT, "oracle", "_ref", "ulcdecodetool_amd")
 needs_tools = pytest.mark.skipif(not (os.path.exists(ENC) and os.path.exists(DEC)),
                                  reason="oracle/_ref tools not built (needs /root/reference at build time)")
-
-
-def _write_wav16(path, pcm16, rate):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(pcm16.shape[1]); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(pcm16.astype("<i2").tobytes())
 
 
 def _expected_ulc(pcm16, rate, bs, mode, p0):
@@ -42,14 +36,6 @@ def _expected_ulc(pcm16, rate, bs, mode, p0):
     return hdr + payload, ref, nblk
 
 
-def _run(cmd):
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run(cmd, capture_output=True, env=env, timeout=600)
-    assert p.returncode == 0, f"{cmd[0]} failed ({p.returncode}): {p.stdout.decode()[-400:]} {p.stderr.decode()[-400:]}"
-    return p
-
-
 @needs_tools
 @pytest.mark.parametrize("ch,rate,seconds,arg,mode,p0,bs", [
     (1, 44100, 10.0, "-50", 0, 50.0, 2048),        # BASELINE configs[0]: 10 s mono 44.1 kHz PCM16, BlockSize 2048, VBR -50
@@ -62,9 +48,9 @@ def test_reference_tools_over_libulc_amd_write_the_oracles_bytes(ch, rate, secon
     pcm = synth_pcm(3, n, ch, rate, transient=True, seed=11)
     pcm16 = np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16)
     wav_in, ulc, wav_f32, wav_16 = tmp_path / "in.wav", tmp_path / "out.ulc", tmp_path / "dec_f32.wav", tmp_path / "dec_16.wav"
-    _write_wav16(wav_in, pcm16, rate)
+    write_wav16(wav_in, pcm16, rate)
     args = [ENC, str(wav_in), str(ulc), arg] + ([f"-blocksize:{bs}"] if bs != 2048 else [])
-    _run(args)
+    run_tool(args)
     want, ref, nblk = _expected_ulc(pcm16, rate, bs, mode, p0)
     got = open(ulc, "rb").read()
     assert got[:24] == want[:24], f"container header differs: {got[:24].hex()} vs {want[:24].hex()}"
@@ -73,11 +59,11 @@ def test_reference_tools_over_libulc_amd_write_the_oracles_bytes(ch, rate, secon
     # decode with the reference's decode tool (float32 and the default PCM16)
     rc, ref_pcm, _ = oracle_decode_stream(ref["out"], ch, bs)
     assert rc == 0
-    _run([DEC, str(ulc), str(wav_f32), "-format:FLOAT32"])
+    run_tool([DEC, str(ulc), str(wav_f32), "-format:FLOAT32"])
     raw = open(wav_f32, "rb").read()
     data = np.frombuffer(raw[-nblk * bs * ch * 4:], dtype="<f4").reshape(nblk * bs, ch)
     assert np.array_equal(data.view(np.uint32), ref_pcm.view(np.uint32)), "decoded float samples differ from the oracle's"
-    _run([DEC, str(ulc), str(wav_16)])
+    run_tool([DEC, str(ulc), str(wav_16)])
     raw = open(wav_16, "rb").read()
     d16 = np.frombuffer(raw[-nblk * bs * ch * 2:], dtype="<i2").reshape(nblk * bs, ch)
     want16 = np.rint(np.clip(ref_pcm * np.float32(32768.0), -32768.0, 32767.0)).astype(np.int16)   # WavIO_Helper.c:57-63
@@ -99,21 +85,21 @@ def test_batched_front_end_matches_the_reference_tools_file_for_file(arg, fmt, t
     for i, sec in enumerate(lens):
         pcm = synth_pcm(20 + i, int(sec * rate), ch, rate, transient=(i & 1) == 0, seed=5)
         p = tmp_path / f"in{i}.wav"
-        _write_wav16(p, np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16), rate)
+        write_wav16(p, np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16), rate)
         ins.append(p)
     refdir, gotdir = tmp_path / "ref", tmp_path / "got"
     refdir.mkdir(); gotdir.mkdir()
-    _run([TOOL, "encode", str(gotdir), arg] + [str(p) for p in ins])
+    run_tool([TOOL, "encode", str(gotdir), arg] + [str(p) for p in ins])
     for p in ins:
-        _run([ENC, str(p), str(refdir / (p.stem + ".ulc")), arg])
+        run_tool([ENC, str(p), str(refdir / (p.stem + ".ulc")), arg])
         assert open(gotdir / (p.stem + ".ulc"), "rb").read() == open(refdir / (p.stem + ".ulc"), "rb").read(), \
             f"{p.name}: batched encode differs from ulcencodetool"
     ulcs = [gotdir / (p.stem + ".ulc") for p in ins]
     wavdir = tmp_path / "wav"; wavdir.mkdir()
-    _run([TOOL, "decode", str(wavdir), f"-format:{fmt}"] + [str(u) for u in ulcs])
+    run_tool([TOOL, "decode", str(wavdir), f"-format:{fmt}"] + [str(u) for u in ulcs])
     for u in ulcs:
         ref_wav = refdir / (u.stem + ".wav")
-        _run([DEC, str(u), str(ref_wav), f"-format:{fmt}"])
+        run_tool([DEC, str(u), str(ref_wav), f"-format:{fmt}"])
         got = open(wavdir / (u.stem + ".wav"), "rb").read()
         ref = open(ref_wav, "rb").read()
         nbytes = struct.unpack("<I", open(u, "rb").read()[8:12])[0] * 2048 * ch * (4 if fmt == "FLOAT32" else 2)
@@ -131,19 +117,19 @@ def test_batched_front_end_devices_option_does_not_change_the_files(ndev, tmp_pa
     for i, sec in enumerate([0.9, 0.4, 1.3, 0.25, 0.7, 1.1, 0.5]):
         pcm = synth_pcm(60 + i, int(sec * rate), ch, rate, transient=(i % 3) != 1, seed=13)
         p = tmp_path / f"d{i}.wav"
-        _write_wav16(p, np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16), rate)
+        write_wav16(p, np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16), rate)
         ins.append(p)
     one, many = tmp_path / "one", tmp_path / "many"
     one.mkdir(); many.mkdir()
-    _run([TOOL, "encode", str(one), "-45"] + [str(p) for p in ins])
-    _run([TOOL, "encode", str(many), "-45", f"-devices:{ndev}"] + [str(p) for p in ins])
+    run_tool([TOOL, "encode", str(one), "-45"] + [str(p) for p in ins])
+    run_tool([TOOL, "encode", str(many), "-45", f"-devices:{ndev}"] + [str(p) for p in ins])
     for p in ins:
         assert open(many / (p.stem + ".ulc"), "rb").read() == open(one / (p.stem + ".ulc"), "rb").read(), f"{p.name}: -devices:{ndev} changed the encoded file"
     w1, wn = tmp_path / "w1", tmp_path / "wn"
     w1.mkdir(); wn.mkdir()
     ulcs = [str(one / (p.stem + ".ulc")) for p in ins]
-    _run([TOOL, "decode", str(w1)] + ulcs)
-    _run([TOOL, "decode", str(wn), f"-devices:{ndev}"] + ulcs)
+    run_tool([TOOL, "decode", str(w1)] + ulcs)
+    run_tool([TOOL, "decode", str(wn), f"-devices:{ndev}"] + ulcs)
     for p in ins:
         assert open(wn / (p.stem + ".wav"), "rb").read() == open(w1 / (p.stem + ".wav"), "rb").read(), f"{p.name}: -devices:{ndev} changed the decoded file"
 
@@ -160,21 +146,21 @@ def test_abr_workflow_analyse_then_encode_matches_the_reference_tools(tmp_path):
     for i, sec in enumerate([1.1, 0.6, 1.7]):
         pcm = synth_pcm(40 + i, int(sec * rate), ch, rate, transient=(i != 1), seed=9)
         p = tmp_path / f"abr{i}.wav"
-        _write_wav16(p, np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16), rate)
+        write_wav16(p, np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16), rate)
         ins.append(p)
     d1 = tmp_path / "pass1"; d1.mkdir()
-    out = _run([TOOL, "encode", str(d1), "-50"] + [str(p) for p in ins]).stdout.decode()
+    out = run_tool([TOOL, "encode", str(d1), "-50"] + [str(p) for p in ins]).stdout.decode()
     got = {m.group(1): m.group(2) for m in re.finditer(r"^(\S+?): .*avg complexity ([0-9.]+)$", out, re.M)}
     refdir, gotdir = tmp_path / "ref", tmp_path / "got"
     refdir.mkdir(); gotdir.mkdir()
     for p in ins:
-        ref_out = _run([ENC, str(p), str(refdir / "a.ulc"), "-50"]).stdout.decode()
+        ref_out = run_tool([ENC, str(p), str(refdir / "a.ulc"), "-50"]).stdout.decode()
         ref_c = re.search(r"Avg complexity = ([0-9.]+)", ref_out).group(1)
         assert got[p.name] == ref_c, f"{p.name}: average complexity {got[p.name]} != reference tool's {ref_c}"
         arg = f"64,{ref_c}"
-        _run([ENC, str(p), str(refdir / (p.stem + ".ulc")), arg])
+        run_tool([ENC, str(p), str(refdir / (p.stem + ".ulc")), arg])
         sub = gotdir / p.stem; sub.mkdir()
-        _run([TOOL, "encode", str(sub), arg, str(p)])
+        run_tool([TOOL, "encode", str(sub), arg, str(p)])
         assert open(sub / (p.stem + ".ulc"), "rb").read() == open(refdir / (p.stem + ".ulc"), "rb").read(), \
             f"{p.name}: ABR file differs from ulcencodetool's"
 

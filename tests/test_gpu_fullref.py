@@ -4,7 +4,6 @@ oracle/_ref/ulc_ref_driver, one stream per driver process, and the reference's o
 tools over the full reference build, file for file.  Only oracle/_ref/ build outputs are read.  The transforms on the
 reference side are the project's spec v2 (refereed in float64 elsewhere); everything else is the real code."""
 import os
-import subprocess
 import sys
 import numpy as np
 import pytest
@@ -12,7 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
 from fullref_cases import ENC_CASES, DEC_ONLY, enc_case, have_driver, driver_encode, driver_decode, REF_DIR  # noqa: E402
-from ulc_testlib import synth_pcm  # noqa: E402
+from ulc_testlib import synth_pcm, run_tool  # noqa: E402
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not have_driver(), reason="oracle/_ref/ulc_ref_driver not built (reference tree absent at build time)")]
 COMPARED = {"streams": 0, "blocks": 0, "decoder streams": 0, "decoder blocks": 0}
@@ -171,13 +170,6 @@ def test_benched_inputs_sampled_against_the_real_reference(name):
         COMPARED["streams"] += 1; COMPARED["blocks"] += K; COMPARED["decoder streams"] += 1; COMPARED["decoder blocks"] += K
 
 
-def _run(cmd):
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run(cmd, capture_output=True, env=env, timeout=600)
-    assert p.returncode == 0, f"{cmd[0]} failed ({p.returncode}): {p.stdout.decode()[-400:]} {p.stderr.decode()[-400:]}"
-
-
 @pytest.mark.skipif(not os.path.exists(os.path.join(REF_DIR, "ulcencodetool_amd")), reason="_amd tools not built")
 @pytest.mark.parametrize("ch,rate,seconds,arg", [
     (2, 44100, 1.5, "-50"),          # VBR
@@ -195,9 +187,9 @@ def test_reference_tools_over_libulc_amd_write_the_real_references_files(ch, rat
     files = {}
     for side in ("amd", "ref"):
         ulc, f32, s16 = tmp_path / f"{side}.ulc", tmp_path / f"{side}_f32.wav", tmp_path / f"{side}_16.wav"
-        _run([os.path.join(REF_DIR, f"ulcencodetool_{side}"), str(wav), str(ulc), arg])
-        _run([os.path.join(REF_DIR, f"ulcdecodetool_{side}"), str(ulc), str(f32), "-format:FLOAT32"])
-        _run([os.path.join(REF_DIR, f"ulcdecodetool_{side}"), str(ulc), str(s16)])
+        run_tool([os.path.join(REF_DIR, f"ulcencodetool_{side}"), str(wav), str(ulc), arg])
+        run_tool([os.path.join(REF_DIR, f"ulcdecodetool_{side}"), str(ulc), str(f32), "-format:FLOAT32"])
+        run_tool([os.path.join(REF_DIR, f"ulcdecodetool_{side}"), str(ulc), str(s16)])
         files[side] = [open(p, "rb").read() for p in (ulc, f32, s16)]
     for i, what in enumerate((".ulc", "float32 WAV", "PCM16 WAV")):
         assert len(files["amd"][i]) > 100

@@ -2,13 +2,10 @@
 nothing, staging that grows or is replaced keeps working, a replaced payload drops its index.  One small geometry - three
 stereo streams, BlockSize 256, four blocks a call at most - since the geometry only has to be valid."""
 import ctypes as C
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd
 from ulc_testlib import synth_pcm
 from seek_testlib import pack
 
@@ -17,11 +14,6 @@ pytestmark = pytest.mark.gpu
 B, CH, BS, RATE, MAXK = 3, 2, 256, 44100, 4
 T = 5                                                      # blocks of signal per stream: calls of 2 and 3
 NAN = float("nan")
-
-
-def amd():
-    import ulc_amd
-    return ulc_amd
 
 
 def p(a, t):

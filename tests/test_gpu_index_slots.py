@@ -9,11 +9,10 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gpu_testlib import amd as _amd, dev as _dev, to_dev as _t
 import guarded_buffers as gb
-from ulc_testlib import oracle, ptr, f32p, i32p, u8p, synth_pcm
+from ulc_testlib import oracle, ptr, f32p, i32p, u8p, synth_pcm, same_bits
 from seek_testlib import RATE, SEED0, geometries, pack, oracle_walk, oracle_pcm, damaged, expected_range
 
 pytestmark = pytest.mark.gpu
@@ -21,29 +20,9 @@ GEOMS = sorted(geometries().keys())
 A_WORD, A_BYTE = 4, 1                                       # the alignments of include/ulc_amd.h, "Caller buffers"
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _t(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
-
-
 def _bytes8(bits):
     """d_bits as the encoder writes them: whole bytes."""
     return ((np.asarray(bits, np.int64) + 7) // 8 * 8).astype(np.int32)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32).ravel(), np.ascontiguousarray(b, np.float32).ravel()
-    return a.size == b.size and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def _walk(blocks, bits, ch, bs):
@@ -433,7 +412,7 @@ def test_range_decode_with_the_grown_index_is_the_oracles_slice():
         ref, rbits = oracle_pcm(e["blocks"][r], e["ch"], e["bs"])
         want, wb = expected_range(ref, rbits, e["first"], e["N"])
         assert np.array_equal(e["obits"][r], wb), (r, e["obits"][r], wb)
-        assert _same_bits(e["pcm"][r], want), f"row {r}: blocks {e['first']} .. differ from the oracle's sequential decode"
+        assert same_bits(e["pcm"][r], want, shape=False), f"row {r}: blocks {e['first']} .. differ from the oracle's sequential decode"
 
 
 def test_resident_decoder_takes_a_stored_index():
@@ -455,15 +434,15 @@ def test_resident_decoder_takes_a_stored_index():
         with pytest.raises(amd.UlcError, match="stream"):
             dec.set_resident_index(idx, cnt)
     p2, b2 = dec.decode_resident_range(first, N)
-    assert np.array_equal(b1, b2) and _same_bits(p1, p2), "a refused index changed the decoder"
+    assert np.array_equal(b1, b2) and same_bits(p1, p2, shape=False), "a refused index changed the decoder"
     dec.upload_payload(e["payload"], e["pbytes"])           # a new upload drops the index
     with pytest.raises(amd.UlcError):
         dec.decode_resident_range(first, N)
     assert np.array_equal(dec.index_resident(e["L"]), e["count"])
     p3, b3 = dec.decode_resident_range(first, N)
     dec.close()
-    assert np.array_equal(b1, b3) and _same_bits(p1, p3), "stored index and ulcx_decoder_index_resident decode differently"
+    assert np.array_equal(b1, b3) and same_bits(p1, p3, shape=False), "stored index and ulcx_decoder_index_resident decode differently"
     for r in range(R):
         ref, rbits = oracle_pcm(e["blocks"][r], e["ch"], e["bs"])
         want, wb = expected_range(ref, rbits, int(first[r]), N)
-        assert np.array_equal(b1[r], wb) and _same_bits(p1[r], want), f"row {r} from block {first[r]}"
+        assert np.array_equal(b1[r], wb) and same_bits(p1[r], want, shape=False), f"row {r} from block {first[r]}"

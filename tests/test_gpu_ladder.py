@@ -5,14 +5,12 @@ plain / per-stream-rates calls give on separate encoders; the streams' state adv
 import functools
 import os
 import re
-import subprocess
-import sys
-import wave
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from ulc_testlib import write_wav16, run_tool
+from gpu_testlib import amd as _ulc
 from ulc_testlib import synth_pcm, oracle_encode_debug
 from rates_testlib import oracle_streams
 
@@ -22,11 +20,6 @@ VBR, CBR, ABR = 0, 1, 2
 # six entries of MIXED (tests/test_gpu_stream_rates.py): CBR 32, ABR (64, 0.02), VBR 37.5, ABR (64, 0.35), VBR 100, ABR (128, 0.98)
 TABLE6 = [(32.0, 0.0), (64.0, 0.02), (-37.5, 0.0), (64.0, 0.35), (-100.0, 0.0), (128.0, 0.98)]
 FIVE = [(VBR, 50.0, 0.0), (CBR, 64.0, 0.0), TABLE6, (VBR, 100.0, 0.0), (ABR, 96.0, 0.3)]
-
-
-def _ulc():
-    import ulc_amd
-    return ulc_amd
 
 
 def _batch_pcm(B, n, ch, rate, seed):
@@ -254,20 +247,6 @@ needs_tools = pytest.mark.skipif(not (os.path.exists(ENC) and os.path.exists(TOO
                                  reason="ulcx-tool or the oracle/_ref tools not built (needs the reference tree at build time)")
 
 
-def _write_wav16(path, pcm16, rate):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(pcm16.shape[1]); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(pcm16.astype("<i2").tobytes())
-
-
-def _run(cmd):
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run(cmd, capture_output=True, env=env, timeout=600)
-    assert p.returncode == 0, f"{cmd[0]} failed ({p.returncode}): {p.stdout.decode()[-400:]} {p.stderr.decode()[-400:]}"
-    return p
-
-
 def _inputs(tmp_path, names, specs, rate, ch):
     ins = []
     for i, (name, (sec, kind)) in enumerate(zip(names, specs)):
@@ -275,7 +254,7 @@ def _inputs(tmp_path, names, specs, rate, ch):
         pcm = synth_pcm(90 + i, n, ch, rate, transient=(kind == "transient"), seed=19)
         pcm16 = np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16)
         p = tmp_path / f"{name}.wav"
-        _write_wav16(p, pcm16, rate)
+        write_wav16(p, pcm16, rate)
         ins.append((p, pcm16))
     return ins
 
@@ -290,13 +269,13 @@ def test_cli_ladder_writes_the_reference_tools_file_for_every_rung(tmp_path):
     got, many, ref = tmp_path / "got", tmp_path / "many", tmp_path / "ref"
     for d in (got, many, ref):
         d.mkdir()
-    _run([TOOL, "encode", str(got)] + args)
-    _run([TOOL, "encode", str(many), args[0], "-devices:2"] + args[1:])
+    run_tool([TOOL, "encode", str(got)] + args)
+    run_tool([TOOL, "encode", str(many), args[0], "-devices:2"] + args[1:])
     assert sorted(os.listdir(got)) == sorted(f"{n}.r{i}.ulc" for n in "abc" for i in range(3))
     for p, _ in ins:
         for i, arg in enumerate(want[p.stem]):
             name = f"{p.stem}.r{i}.ulc"
-            _run([ENC, str(p), str(ref / name), arg])
+            run_tool([ENC, str(p), str(ref / name), arg])
             r = open(ref / name, "rb").read()
             assert open(got / name, "rb").read() == r, f"{name} at {arg}: differs from ulcencodetool"
             assert open(many / name, "rb").read() == r, f"{name} at {arg}: -devices:2 changed the file"
@@ -308,7 +287,7 @@ def test_cli_ladder_with_an_auto_rung_uses_each_files_own_average_complexity(tmp
     ins = _inputs(tmp_path, "xy", [(1.1, "transient"), (0.6, "tone")], rate, ch)
     got, ref = tmp_path / "got", tmp_path / "ref"
     got.mkdir(); ref.mkdir()
-    out = _run([TOOL, "encode", str(got), "64,auto/-50"] + [str(p) for p, _ in ins]).stdout.decode()
+    out = run_tool([TOOL, "encode", str(got), "64,auto/-50"] + [str(p) for p, _ in ins]).stdout.decode()
     printed = {m.group(1): m.group(2) for m in re.finditer(r"^(\S+?): .*ABR complexity (\S+?)(?: \(CBR\))?(?:[,;]|$)", out, re.M)}
     for p, pcm16 in ins:
         n = pcm16.shape[0]
@@ -320,5 +299,5 @@ def test_cli_ladder_with_an_auto_rung_uses_each_files_own_average_complexity(tmp
         assert np.float32(float(printed[p.name])) == avg, f"{p.name}: printed complexity {printed[p.name]} != {avg!r}"
         for i, arg in enumerate([f"64,{float(avg):.9g}", "-50"]):
             name = f"{p.stem}.r{i}.ulc"
-            _run([ENC, str(p), str(ref / name), arg])
+            run_tool([ENC, str(p), str(ref / name), arg])
             assert open(got / name, "rb").read() == open(ref / name, "rb").read(), f"{name}: reference tool at {arg}"

@@ -8,15 +8,10 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd
 from ulc_testlib import synth_pcm, oracle_encode_debug, oracle_decode_stream, synth_block_stream
 
 pytestmark = pytest.mark.gpu
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
 
 
 def _streams(B, nblk, bs, ch, rate, transient, seed):

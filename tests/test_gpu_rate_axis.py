@@ -6,21 +6,13 @@ Each case opens one encoder and asserts from ulcx_encoder_debug_plan that the ob
 A batch is 70 streams - 840 noise rows in stereo, 13 full tiles of k_bark_uniform and a tail of 8 - tiled from 5 distinct
 streams in a seeded permutation, two calls of 6 blocks, so state carries and the window-control pipeline has chunks; every
 copy is compared with its distinct stream's oracle encode."""
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd
 import rate_axis_testlib as R
 
 pytestmark = pytest.mark.gpu
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
 
 
 def _open(bs, ch, rate, cls, B, K, fields=None):

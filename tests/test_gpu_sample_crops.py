@@ -4,35 +4,21 @@ bit for bit (uint32 / int16 views) against the oracle's sequential decode of the
 transposed and sliced in numpy - never against this library's own block-aligned crop call.  Streams and indices are the
 oracle's (seek_testlib.geometries, oracle_stream, synth_stream; the corpora are test_gpu_crops.py's, built once per session)."""
 import ctypes as C
-import os
 import struct
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from ulc_testlib import to_pcm16, same_bytes
+from gpu_testlib import amd as _amd, word
 import guarded_buffers as gb
 from seek_testlib import geometries, switched_starts
-from test_gpu_crops import Corpus, _geom_corpus, _five_files, _wc_of
+from ulc_testlib import wc_of
+from corpus_testlib import Corpus
+from test_gpu_crops import _geom_corpus, _five_files
 
 pytestmark = pytest.mark.gpu
 GEOMS = sorted(geometries().keys())
 POISON_F, POISON_I = 7.0, 7
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _to_pcm16(x):
-    return np.clip(np.rint(x.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)       # WavIO_Helper.c:56-63
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def _blocks_of(bs, n_samples):
@@ -48,7 +34,7 @@ def expected_row(cor, f, start, n_samples, length=None, pcm16=False):
     out, bits = np.zeros((ch, n_samples), np.float32), np.zeros(nB, np.int32)
     ln = n_samples if length is None else max(0, min(n_samples, int(length)))
     if 0 <= f < cor.F and start >= 0 and start // bs <= cor.K[f] and ln > 0:
-        pcm, rb = cor.refs[f]
+        pcm, rb = cor.files[f].pcm, cor.files[f].obits
         stream = pcm.reshape(cor.K[f] * bs, ch).T
         end = min(start + ln, cor.K[f] * bs)
         if end > start:
@@ -56,7 +42,7 @@ def expected_row(cor, f, start, n_samples, length=None, pcm16=False):
         for b in range(start // bs, (start + ln - 1) // bs + 1):
             if b < cor.K[f]:
                 bits[b - start // bs] = rb[b]
-    return (_to_pcm16(out) if pcm16 else out), bits
+    return (to_pcm16(out) if pcm16 else out), bits
 
 
 def _device_samples(dec, cor, files, start, n_samples, length=None, pcm16=False, dev=None):
@@ -81,7 +67,7 @@ def _check_rows(cor, files, start, n_samples, pcm, bits, what, length=None, pcm1
         want, wb = expected_row(cor, int(files[i]), int(start[i]), n_samples, None if length is None else length[i], pcm16)
         where = f"{what}: row {i} (file {files[i]} from sample {start[i]}" + (f", length {length[i]})" if length is not None else ")")
         assert np.array_equal(bits[i], wb), f"{where}: bits {bits[i]} vs the oracle's {wb}"
-        if not _same_bits(pcm[i], want):
+        if not same_bytes(pcm[i], want):
             bad = np.argwhere(pcm[i].view(np.uint16 if pcm16 else np.uint32) != want.view(np.uint16 if pcm16 else np.uint32))
             raise AssertionError(f"{where}: {len(bad)} of {want.size} samples differ from the oracle's sequential decode, first at (channel, t) = "
                                  f"{bad[0].tolist()}, last at {bad[-1].tolist()}")
@@ -114,7 +100,7 @@ def test_sample_crops_equal_the_oracles_slices(geom):
     bs, ch = geom
     cor = _geom_corpus(geom)
     st = geometries()[geom]
-    sw = [switched_starts(_wc_of(blocks)) for _, blocks, _, _ in st]
+    sw = [switched_starts(wc_of(blocks)) for _, blocks, _, _ in st]
     assert all(len(s) >= 3 for s in sw)
     sizes = (1, bs - 1, bs, bs + 1, 3 * bs + 5)
     dec = amd.BatchDecoder(32, ch, bs, _blocks_of(bs, max(sizes)) + 1)
@@ -157,7 +143,7 @@ def test_lengths_shorten_rows(geom):
         full, fbits = _device_samples(dec, cor, files, start, n_samples, pcm16=pcm16)            # NULL d_len: every row takes nSamples
         _check_rows(cor, files, start, n_samples, full, fbits, "without lengths", pcm16=pcm16)
         for i in (3, 4):                                    # a length of nSamples or more: the row without one
-            assert np.array_equal(bits[i], fbits[i]) and _same_bits(pcm[i], full[i]), i
+            assert np.array_equal(bits[i], fbits[i]) and same_bytes(pcm[i], full[i]), i
     hp, hb = dec.decode_crops_samples(cor.host, cor.nbytes, cor.index, cor.count, files, start, n_samples, length=length)
     _check_rows(cor, files, start, n_samples, hp, hb, "host form with lengths", length=length)
     dec.close()
@@ -175,7 +161,6 @@ def _arena(cor, n, pcm16, with_len=True):
     F, stride = cor.host.shape
     esz = 2 if pcm16 else 4
     nB = _blocks_of(G_BS, G_NS)
-    word = lambda name, k, role, maxk=None, rps=1: dict(name=name, nbytes=4 * k, align=A_WORD, role=role, guard=4 * (maxk or k), row=4, rows_per_stream=rps)
     specs = [dict(name="d_payload", nbytes=F * stride, align=1, role="in", guard=F * stride, row=stride),
              word("d_payloadBytes", F, "in"),
              dict(name="d_index", nbytes=8 * F * cor.istride, align=A_WORD, role="in", guard=8 * F * cor.istride, row=8, rows_per_stream=cor.istride),
@@ -343,7 +328,7 @@ def test_ragged_and_strided_corpora_give_the_same_sample_crops():
             torch.cuda.synchronize()
             got[layout] = (pcm.cpu().numpy(), bits.cpu().numpy())
             _check_rows(cor, files, start, n_samples, *got[layout], f"CropCorpus({layout}).sample_crops", length=length, pcm16=pcm16)
-        assert _same_bits(got["strided"][0], got["ragged"][0]) and np.array_equal(got["strided"][1], got["ragged"][1])
+        assert same_bytes(got["strided"][0], got["ragged"][0]) and np.array_equal(got["strided"][1], got["ragged"][1])
     hp, hb = dec.decode_crops_samples_ragged(ccs["ragged"].d_payload.cpu().numpy(), ccs["ragged"].d_payload_offs.cpu().numpy(),
                                              ccs["ragged"].d_index.cpu().numpy().view(amd.INDEX_DTYPE).reshape(-1), ccs["ragged"].d_index_offs.cpu().numpy(),
                                              cor.count, files, start, n_samples, length=length)
@@ -370,8 +355,8 @@ def test_sample_crops_between_two_halves_of_a_packed_decode():
     def packed(at, n, what):
         pcm, bits = dec.decode_packed(host, nbytes, n)
         for s in range(B):
-            want, wb = cor.expected(pick[s], at, n)
-            assert np.array_equal(bits[s], wb) and _same_bits(np.asarray(pcm[s], np.float32).reshape(want.shape), want), f"{what}: stream {s}, blocks {at}.."
+            want, wb = cor.files[pick[s]].expected_pcm(at, n)
+            assert np.array_equal(bits[s], wb) and same_bytes(np.asarray(pcm[s], np.float32).reshape(want.shape), want), f"{what}: stream {s}, blocks {at}.."
 
     packed(0, 6, "first half")
     before = dec.save_streams(slots)
@@ -401,8 +386,7 @@ def test_bad_rows_are_silent_and_leave_their_neighbours_alone():
     index["ByteOffs"][2, 12] = int(nbytes[2]) + 1000
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
     dev = dict(pay=t(host), nb=t(nbytes), idx=t(index.view(np.int32).reshape(3, -1)), cnt=t(count))
-    big = Corpus.__new__(Corpus)
-    big.__dict__.update(cor.__dict__); big.F = 3; big.refs = cor.refs + cor.refs[:1]; big.K = cor.K + cor.K[:1]
+    big = Corpus(cor.files + cor.files[:1])
     K1 = cor.K[1]
     files = [0, -1, 1, 3, 0, 1, 2, 2, 0, 1 << 30, 0, 1]
     start = [4 * bs + 5, 4 * bs, 9 * bs + 1, 0, -1, (K1 + 1) * bs, 10 * bs + 9, 20 * bs + 1, 30 * bs, 0, -(1 << 40), (1 << 45) + 7]

@@ -5,31 +5,19 @@ The reference is always the oracle (tests/seek_testlib.py), never this library's
 import ctypes as C
 import os
 import struct
-import subprocess
-import sys
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd
 from seek_testlib import (RATE, SEED0, ORACLE_BLOCKS, geometries, oracle_stream, pack, oracle_seeds, oracle_pcm, expected_range,
                           switched_starts, damaged, oracle_walk)
-from ulc_testlib import oracle_decode_stream
+from ulc_testlib import oracle_decode_stream, run_tool, same_bits
 
 pytestmark = pytest.mark.gpu
 TOOL = os.path.join(ROOT, "ulc-codec_amd", "ulcx-tool")
 MAXK = 4                                                    # maxBlocksPerCall of the small decoders: range calls of 3 blocks
 GEOMS = sorted(geometries().keys())
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32).ravel(), np.ascontiguousarray(b, np.float32).ravel()
-    return a.size == b.size and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def _group(geom):
@@ -155,7 +143,7 @@ def test_index_and_decode_of_damaged_payloads_match_the_oracle(geom):
             rows[k, :woffs[k + 1] - woffs[k]] = host[s, woffs[k]:woffs[k + 1]]
         rc, rpcm, rbits = oracle_decode_stream(rows[:n], ch, bs) if n else (0, np.zeros((0, ch), np.float32), wbits)
         assert rc == 0 and np.array_equal(rbits, wbits), what
-        assert _same_bits(gpcm[s][:n * bs], rpcm), f"{what}: the decoded samples differ from the oracle's"
+        assert same_bits(gpcm[s][:n * bs], rpcm, shape=False), f"{what}: the decoded samples differ from the oracle's"
         assert not gpcm[s][n * bs:].any(), f"{what}: samples behind block {n}, where the walk stops"
 
 
@@ -200,8 +188,8 @@ def test_range_equals_the_slice_of_the_oracles_decode(geom):
             assert np.array_equal(gb[s], wb), f"{name}: bits of blocks {first[s]}.. are {gb[s]}, the oracle's {wb}"
             got = pcm[s].reshape(N, bs, ch)
             for k in range(N):
-                assert _same_bits(got[k], want[k]), f"{name}: block {first[s] + k} (range from {first[s]}) differs from the oracle's sequential decode"
-            assert np.array_equal(gb2[s], wb) and _same_bits(pcm2[s], want), f"{name}: resident form, range from {first[s]}"
+                assert same_bits(got[k], want[k], shape=False), f"{name}: block {first[s] + k} (range from {first[s]}) differs from the oracle's sequential decode"
+            assert np.array_equal(gb2[s], wb) and same_bits(pcm2[s], want, shape=False), f"{name}: resident form, range from {first[s]}"
             checked += 1
     dec.close()
     assert checked >= 7 * B
@@ -228,7 +216,7 @@ def test_a_start_outside_the_index_gives_a_stream_of_zero_bits():
         torch.cuda.synchronize()
         assert (bits[1] == 0).all() and (pcm[1] == 0).all(), bad
         want, wb = expected_range(*oracle_pcm(streams[0][1], ch, bs), 4, N)
-        assert np.array_equal(bits[0].cpu().numpy(), wb) and _same_bits(pcm[0].cpu().numpy(), want), bad
+        assert np.array_equal(bits[0].cpu().numpy(), wb) and same_bits(pcm[0].cpu().numpy(), want, shape=False), bad
     dec.close()
 
 
@@ -250,7 +238,7 @@ def test_state_after_a_range_call_is_the_sequential_decoders(geom):
         for s, (name, _, _, _) in enumerate(streams):
             want, wb = expected_range(refs[s][0], refs[s][1], int(first[s]), n)
             assert np.array_equal(gb[s], wb), f"{what}: {name}: bits {gb[s]} vs the oracle's {wb}"
-            assert _same_bits(pcm[s], want), f"{what}: {name}: blocks {first[s]}.. differ from the oracle's"
+            assert same_bits(pcm[s], want, shape=False), f"{what}: {name}: blocks {first[s]}.. differ from the oracle's"
 
     # a packed call behind a range call continues with the next block (lapping, LastSubBlockSize, generator, read position)
     sw = switched_starts(streams[0][3])
@@ -269,7 +257,7 @@ def test_state_after_a_range_call_is_the_sequential_decoders(geom):
     fresh = amd.BatchDecoder(B, ch, bs, MAXK)
     p2, b2 = fresh.decode_range(host, nbytes, index, count, back, N)
     fresh.close()
-    assert np.array_equal(b1, b2) and _same_bits(p1, p2)
+    assert np.array_equal(b1, b2) and same_bits(p1, p2, shape=False)
     check(*dec.decode_packed(host, nbytes, MAXK), back + N, MAXK, "packed call behind the backward range")
     dec.close()
 
@@ -284,15 +272,15 @@ def test_range_call_mixed_with_slot_calls_on_a_one_stream_decoder_keeps_the_chai
     index, count = dec.index_packed(host, nbytes, ORACLE_BLOCKS)
     N = MAXK - 1
     p, b = dec.decode(blocks[None, 0:3])
-    assert np.array_equal(b[0], rbits[0:3]) and _same_bits(p[0], ref[0:3])
+    assert np.array_equal(b[0], rbits[0:3]) and same_bits(p[0], ref[0:3], shape=False)
     p, b = dec.decode_range(host, nbytes, index, count, np.array([3], np.int32), N)
-    assert np.array_equal(b[0], rbits[3:6]) and _same_bits(p[0], ref[3:6])
+    assert np.array_equal(b[0], rbits[3:6]) and same_bits(p[0], ref[3:6], shape=False)
     p, b = dec.decode(blocks[None, 6:10])                                 # the slot form goes on where the range ended
-    assert np.array_equal(b[0], rbits[6:10]) and _same_bits(p[0], ref[6:10])
+    assert np.array_equal(b[0], rbits[6:10]) and same_bits(p[0], ref[6:10], shape=False)
     p, b = dec.decode_range(host, nbytes, index, count, np.array([20], np.int32), N)      # a jump, then slots again
-    assert np.array_equal(b[0], rbits[20:23]) and _same_bits(p[0], ref[20:23])
+    assert np.array_equal(b[0], rbits[20:23]) and same_bits(p[0], ref[20:23], shape=False)
     p, b = dec.decode(blocks[None, 23:27])
-    assert np.array_equal(b[0], rbits[23:27]) and _same_bits(p[0], ref[23:27])
+    assert np.array_equal(b[0], rbits[23:27]) and same_bits(p[0], ref[23:27], shape=False)
     dec.close()
 
 
@@ -333,12 +321,12 @@ def test_few_long_streams_take_the_even_cut():
     for s in range(B):
         want, wb = expected_range(refs[s % 2][0], refs[s % 2][1], int(first[s]), N)
         assert np.array_equal(bits[s].cpu().numpy(), wb), s
-        assert _same_bits(pcm[s].cpu().numpy(), want), f"stream {s} from block {first[s]}"
+        assert same_bits(pcm[s].cpu().numpy(), want, shape=False), f"stream {s} from block {first[s]}"
     # the state behind the cut launch: a packed call continues
     nxt, nb = dec.decode_packed(host, nbytes, 8)
     for s in range(B):
         want, wb = expected_range(refs[s % 2][0], refs[s % 2][1], int(first[s]) + N, 8)
-        assert np.array_equal(nb[s], wb) and _same_bits(nxt[s], want), f"stream {s}: packed call behind the cut range"
+        assert np.array_equal(nb[s], wb) and same_bits(nxt[s], want, shape=False), f"stream {s}: packed call behind the cut range"
     dec.close()
     assert resident > 0 and grid > 0 and whole == 0, f"expected an even cut, got {grid} workgroups / {whole} whole streams"
 
@@ -369,11 +357,11 @@ def test_many_short_streams_report_the_tail_cut():
     for s in (0, 1, 2, 3, 777, resident - 1, resident % B, (resident + 1) % B, B - 2, B - 1):
         want, wb = expected_range(refs[s % 4][0], refs[s % 4][1], int(first[s]), N)
         assert np.array_equal(bits[s].cpu().numpy(), wb), s
-        assert _same_bits(pcm[s].cpu().numpy(), want), f"stream {s} from block {first[s]}"
+        assert same_bits(pcm[s].cpu().numpy(), want, shape=False), f"stream {s} from block {first[s]}"
     nxt, nb = dec.decode_packed(host, nbytes, 4)             # the state behind the cut launch
     for s in (0, 3, resident - 1, resident % B, B - 2, B - 1):
         want, wb = expected_range(refs[s % 4][0], refs[s % 4][1], int(first[s]) + N, 4)
-        assert np.array_equal(nb[s], wb) and _same_bits(nxt[s], want), f"stream {s}: packed call behind the cut range"
+        assert np.array_equal(nb[s], wb) and same_bits(nxt[s], want, shape=False), f"stream {s}: packed call behind the cut range"
     dec.close()
     assert grid > 0 and whole > 0, f"expected the tail cut, got {grid} workgroups / {whole} whole streams ({resident} resident)"
     assert (grid, whole) == (full.value + tail, full.value), (grid, whole, tail, full.value)
@@ -411,11 +399,11 @@ def test_range_call_takes_the_cut_of_the_last_round():
     for s in (0, 1, resident - 1, resident, resident + 1, resident + (B - resident) // 2, B - 2, B - 1):
         want, wb = expected_range(refs[s % 4][0], refs[s % 4][1], int(first[s]), N)
         assert np.array_equal(bits[s].cpu().numpy(), wb), s
-        assert _same_bits(pcm[s].cpu().numpy(), want), f"stream {s} from block {first[s]}"
+        assert same_bits(pcm[s].cpu().numpy(), want, shape=False), f"stream {s} from block {first[s]}"
     nxt, nb = dec.decode_packed(host, nbytes, 4)             # the state behind the cut launch
     for s in (0, resident, resident + 7, B - 1):
         want, wb = expected_range(refs[s % 4][0], refs[s % 4][1], int(first[s]) + N, 4)
-        assert np.array_equal(nb[s], wb) and _same_bits(nxt[s], want), f"stream {s}: packed call behind the cut range"
+        assert np.array_equal(nb[s], wb) and same_bits(nxt[s], want, shape=False), f"stream {s}: packed call behind the cut range"
     dec.close()
 
 
@@ -444,12 +432,6 @@ def test_pcm16_form_is_the_float_form_converted(geom):
 # ---------------------------------------------------------------------------------------------------------------------
 # 7. the front-end
 # ---------------------------------------------------------------------------------------------------------------------
-def _run_tool(args):
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    return subprocess.run([TOOL] + args, capture_output=True, env=env, timeout=600)
-
-
 def _write_ulc(path, blocks, bits, bs, ch):
     sizes = (bits + 7) // 8
     payload = b"".join(blocks[k, :sizes[k]].tobytes() for k in range(len(bits)))
@@ -472,11 +454,11 @@ def test_tool_blocks_option_writes_the_bytes_of_the_full_decode(fmt, tmp_path):
     for d in (full, part, part2):
         d.mkdir()
     names = [str(p) for p, _ in files]
-    r = _run_tool(["decode", str(full), f"-format:{fmt}"] + names)
+    r = run_tool([TOOL, "decode", str(full), f"-format:{fmt}"] + names, check=False)
     assert r.returncode == 0, r.stderr.decode()
-    r = _run_tool(["decode", str(part), f"-format:{fmt}", f"-blocks:{F},{N}"] + names)
+    r = run_tool([TOOL, "decode", str(part), f"-format:{fmt}", f"-blocks:{F},{N}"] + names, check=False)
     assert r.returncode == 0, r.stderr.decode()
-    r = _run_tool(["decode", str(part2), f"-blocks:{F},{N}", f"-format:{fmt}", "-devices:2"] + names)
+    r = run_tool([TOOL, "decode", str(part2), f"-blocks:{F},{N}", f"-format:{fmt}", "-devices:2"] + names, check=False)
     assert r.returncode == 0, r.stderr.decode()
     bpf = ch * (4 if fmt == "FLOAT32" else 2) * bs             # bytes per block
     for p, nblk in files:
@@ -491,5 +473,5 @@ def test_tool_blocks_option_writes_the_bytes_of_the_full_decode(fmt, tmp_path):
     # a start at or past a file's block count: an error that names the file
     bad = tmp_path / "bad"
     bad.mkdir()
-    r = _run_tool(["decode", str(bad), f"-blocks:11,4"] + names)
+    r = run_tool([TOOL, "decode", str(bad), f"-blocks:11,4"] + names, check=False)
     assert r.returncode != 0 and "f3.ulc" in r.stderr.decode(), r.stderr.decode()

@@ -7,15 +7,12 @@ device is never compared with itself, except where the property IS an identity (
 plain call).  A `life` below is one stream in a slot: it starts at create, at a reset or at a load."""
 import ctypes as C
 import functools
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd
 import guarded_buffers as gb
-from ulc_testlib import synth_pcm, oracle_encode_debug, oracle_decode_stream
+from ulc_testlib import synth_pcm, oracle_encode_debug, oracle_decode_stream, to_pcm16
 from rates_testlib import mode_of
 from seek_testlib import pack
 
@@ -28,11 +25,6 @@ TABLE = [(-50.0, 0.0), (64.0, 0.0), (96.0, 0.3), (-70.0, 0.0), (48.0, 0.0)]     
 BIG = (2048, 2, 70, 8)                                     # (BlockSize, channels, slots, maxBlocksPerCall): the fused window control, k_select_wave
 SMALL = (512, 1, 9, 8)                                     # generic selection, non-fused window control
 A_PCM, A_PCM16, A_RATE, A_WORD, A_STATE = 16, 8, 8, 4, 16  # include/ulc_amd.h, "Caller buffers" and "Stream slots"
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
 
 
 def _torch():
@@ -85,10 +77,6 @@ def _oracle_dec(bs, ch, key):
     rc, pcm, bits = oracle_decode_stream(blocks, ch, bs)
     assert rc == 0
     return pcm.reshape(len(blocks), bs, ch), bits
-
-
-def _to_pcm16(x):
-    return np.rint(np.clip(x * np.float32(32768.0), -32768.0, 32767.0)).astype(np.int16)      # WavIO_Helper.c:56-63
 
 
 def _schedule(B, seed):
@@ -248,7 +236,7 @@ class DecDriver(_Slots):
         for j, b in enumerate(blocks):
             k, t = first + j, f"{tag}: blocks {key}, block {first + j} of its life"
             assert b["bits"] == rbits[k], f"{t}: bits {b['bits']} != {int(rbits[k])}"
-            want = _to_pcm16(ref[k]) if b["pcm16"] else ref[k]
+            want = to_pcm16(ref[k]) if b["pcm16"] else ref[k]
             assert b["pcm"].tobytes() == want.tobytes(), f"{t}: {np.count_nonzero(b['pcm'] != want)} samples differ (noise included)"
 
     def check(self, tag):

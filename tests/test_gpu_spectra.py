@@ -4,13 +4,10 @@ sequentially over the whole file and sliced, channels-first; LR formed from that
 block's first byte; zeros where a block is not live.  d_bits is additionally compared with what ulcx_decode_crops_dev returns for
 the same rows.  The device calls run on poisoned buffers carved between guards (tests/guarded_buffers.py); what the inputs hold -
 noise units of several passes, every decimation pattern, the units that fill the LDS - is asserted in tests/test_spectra_capi.py."""
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd, dev as _dev, word
 import guarded_buffers as gb
 import spectra_testlib as S
 from seek_testlib import geometries, oracle_pcm
@@ -22,20 +19,6 @@ N = S.N_BLOCKS
 LR = S.SPECTRA_LR
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _word(name, n, role, rps=1):
-    return dict(name=name, nbytes=4 * n, align=4, role=role, guard=4 * n, row=4, rows_per_stream=rps)
-
-
 def spectra_dev(dec, lay, ch, bs, files, first, nb, count=None, flags=0):
     """One ulcx_decode_crops_spectra(_ragged)_dev call with every buffer carved from a poisoned arena between guards -> (coef
     [n][ch][nb][bs], wc [n][nb], bits [n][nb]) after the guards and the inputs have been checked.  lay: dict(host, nbytes, index,
@@ -44,19 +27,19 @@ def spectra_dev(dec, lay, ch, bs, files, first, nb, count=None, flags=0):
     n = len(files)
     ragged = "poffs" in lay
     plane = 4 * nb * bs
-    specs = [_word("d_indexBlocks", len(lay["blocks" if ragged else "count"]), "in"), _word("d_file", n, "in"), _word("d_first", n, "in")]
+    specs = [word("d_indexBlocks", len(lay["blocks" if ragged else "count"]), "in"), word("d_file", n, "in"), word("d_first", n, "in")]
     if ragged:
         specs += [dict(name="d_payload", nbytes=lay["payload"].size, align=1, role="in"),
                   dict(name="d_payloadOffs", nbytes=8 * lay["poffs"].size, align=8, role="in"),
                   dict(name="d_index", nbytes=8 * lay["index"].size, align=4, role="in"),
                   dict(name="d_indexOffs", nbytes=8 * lay["ioffs"].size, align=8, role="in")]
     else:
-        specs += [dict(name="d_payload", nbytes=lay["host"].size, align=1, role="in", row=lay["host"].shape[1]), _word("d_payloadBytes", lay["nbytes"].size, "in"),
+        specs += [dict(name="d_payload", nbytes=lay["host"].size, align=1, role="in", row=lay["host"].shape[1]), word("d_payloadBytes", lay["nbytes"].size, "in"),
                   dict(name="d_index", nbytes=8 * lay["index"].size, align=4, role="in")]
     if count is not None:
-        specs.append(_word("d_count", n, "in"))
+        specs.append(word("d_count", n, "in"))
     specs += [dict(name="d_coef", nbytes=n * ch * plane, align=16, role="out", guard=ch * plane, row=4 * bs, rows_per_stream=ch * nb),
-              _word("d_wc", n * nb, "out", nb), _word("d_bits", n * nb, "out", nb)]
+              word("d_wc", n * nb, "out", rps=nb), word("d_bits", n * nb, "out", rps=nb)]
     a = gb.build(_dev(), specs)
     a.load("d_file", np.array(files, np.int32)); a.load("d_first", np.array(first, np.int32))
     if count is not None:
@@ -76,10 +59,6 @@ def spectra_dev(dec, lay, ch, bs, files, first, nb, count=None, flags=0):
     torch.cuda.synchronize()
     a.check()
     return (a.fetch("d_coef", np.float32).reshape(n, ch, nb, bs), a.fetch("d_wc", np.int32).reshape(n, nb), a.fetch("d_bits", np.int32).reshape(n, nb))
-
-
-def strided(cor):
-    return dict(host=cor.host, nbytes=cor.nbytes, index=cor.index, count=cor.count)
 
 
 def crop_bits(dec, lay, ch, bs, files, first, nb, count=None):
@@ -125,11 +104,11 @@ def test_rows_equal_the_oracles_coefficients(geom, with_count):
     files, first = [f for f, _ in rows], [k for _, k in rows]
     count = [(0, 1, N, N + 3)[i % 4] for i in range(len(rows))] if with_count else None
     dec = amd.BatchDecoder(len(rows), ch, bs, N + 1)
-    got = spectra_dev(dec, strided(cor), ch, bs, files, first, N, count)
+    got = spectra_dev(dec, cor.strided(), ch, bs, files, first, N, count)
     assert dec.last_cut()[:2] == (0, 0)                     # the plain plan: nothing of the synthesis's cuts applies
-    want = cor.expected(files, first, N, count)
+    want = cor.expected_spec(files, first, N, count)
     check(got, want, files, first, f"{bs} x {ch}")
-    assert np.array_equal(got[2], crop_bits(dec, strided(cor), ch, bs, files, first, N, count)), "d_bits differs from the crop call's"
+    assert np.array_equal(got[2], crop_bits(dec, cor.strided(), ch, bs, files, first, N, count)), "d_bits differs from the crop call's"
     dec.close()
     live = want[2] > 0
     assert live.sum() >= (60 if with_count else 150) and (~live).sum() >= 20 and (want[0] != 0).any()
@@ -146,8 +125,8 @@ def test_units_of_more_than_2048_noise_coefficients():
     files, first = [f for f, _ in rows], [k for _, k in rows]
     dec = amd.BatchDecoder(len(rows), 2, 4096, N + 1)
     for flags in (0, LR):
-        got = spectra_dev(dec, strided(cor), 2, 4096, files, first, N, flags=flags)
-        check(got, cor.expected(files, first, N, lr=bool(flags)), files, first, f"4096 x 2, flags {flags}")
+        got = spectra_dev(dec, cor.strided(), 2, 4096, files, first, N, flags=flags)
+        check(got, cor.expected_spec(files, first, N, lr=bool(flags)), files, first, f"4096 x 2, flags {flags}")
     dec.close()
 
 
@@ -164,15 +143,15 @@ def test_blocksize_32768_takes_the_one_array_path(ch):
     rows = [(f, k) for f in range(cor.F) for k in (0, 1)]
     files, first = [f for f, _ in rows], [k for _, k in rows]
     dec = amd.BatchDecoder(len(rows), ch, 32768, 3)
-    plain = spectra_dev(dec, strided(cor), ch, 32768, files, first, 2)
-    check(plain, cor.expected(files, first, 2), files, first, f"32768 x {ch}")
-    lr = spectra_dev(dec, strided(cor), ch, 32768, files, first, 2, flags=LR)
-    check(lr, cor.expected(files, first, 2, lr=True), files, first, f"32768 x {ch}, LR")
+    plain = spectra_dev(dec, cor.strided(), ch, 32768, files, first, 2)
+    check(plain, cor.expected_spec(files, first, 2), files, first, f"32768 x {ch}")
+    lr = spectra_dev(dec, cor.strided(), ch, 32768, files, first, 2, flags=LR)
+    check(lr, cor.expected_spec(files, first, 2, lr=True), files, first, f"32768 x {ch}, LR")
     if ch == 1:
         assert S.same_bits(lr[0], plain[0])
     else:
         assert not S.same_bits(lr[0][:, 0], plain[0][:, 0]) and not S.same_bits(lr[0][:, 1], plain[0][:, 1])
-    assert np.array_equal(plain[2], crop_bits(dec, strided(cor), ch, 32768, files, first, 2))
+    assert np.array_equal(plain[2], crop_bits(dec, cor.strided(), ch, 32768, files, first, 2))
     dec.close()
 
 
@@ -187,9 +166,9 @@ def test_lr_unmixes_the_pairs_and_leaves_a_single_channel(geom):
     rows = S.row_table(cor)
     files, first = [f for f, _ in rows], [k for _, k in rows]
     dec = amd.BatchDecoder(len(rows), ch, bs, N + 1)
-    got = spectra_dev(dec, strided(cor), ch, bs, files, first, N, flags=LR)
-    ms = cor.expected(files, first, N)
-    want = cor.expected(files, first, N, lr=True)
+    got = spectra_dev(dec, cor.strided(), ch, bs, files, first, N, flags=LR)
+    ms = cor.expected_spec(files, first, N)
+    want = cor.expected_spec(files, first, N, lr=True)
     check(got, want, files, first, f"{bs} x {ch}, LR")
     dec.close()
     for c in range(0, ch - 1, 2):                           # the pairs (0,1), (2,3), ...: really un-mixed, in float32
@@ -217,12 +196,12 @@ def test_ragged_entries_equal_the_strided_ones(flags):
     dec = amd.BatchDecoder(len(rows), 2, 2048, N + 1)
     got = spectra_dev(dec, rg, 2, 2048, files, first, N, count, flags)
     seen = [-1 if f == 2 else f for f in files]             # (a file number outside the corpus: the expected row is zeros)
-    want = cor.expected(seen, first, N, count, lr=bool(flags))
+    want = cor.expected_spec(seen, first, N, count, lr=bool(flags))
     check(got, want, files, first, "ragged")
     bad = [i for i, f in enumerate(files) if f == 2]
     assert len(bad) == 2 and not got[0][bad].any() and not got[1][bad].any() and not got[2][bad].any()
     ok = [i for i, f in enumerate(files) if f != 2]
-    st = spectra_dev(dec, strided(cor), 2, 2048, [files[i] for i in ok], [first[i] for i in ok], N, [count[i] for i in ok], flags)
+    st = spectra_dev(dec, cor.strided(), 2, 2048, [files[i] for i in ok], [first[i] for i in ok], N, [count[i] for i in ok], flags)
     for j, i in enumerate(ok):
         assert S.same_bits(st[0][j], got[0][i]) and np.array_equal(st[1][j], got[1][i]) and np.array_equal(st[2][j], got[2][i]), i
     dec.close()
@@ -240,8 +219,8 @@ def test_host_forms_equal_the_device_forms_and_refuse_what_the_crop_host_forms_r
     dec = amd.BatchDecoder(len(rows), 3, 2048, N + 1)
     rg = cor.ragged()
     for flags in (0, LR):
-        want = cor.expected(files, first, N, count, lr=bool(flags))
-        dev = spectra_dev(dec, strided(cor), 3, 2048, files, first, N, count, flags)
+        want = cor.expected_spec(files, first, N, count, lr=bool(flags))
+        dev = spectra_dev(dec, cor.strided(), 3, 2048, files, first, N, count, flags)
         check(dev, want, files, first, "device form")
         host = dec.decode_crops_spectra(cor.host, cor.nbytes, cor.index, cor.count, files, first, N, count=count, flags=flags)
         check(host, want, files, first, "host form")
@@ -292,7 +271,7 @@ def test_misaligned_outputs_and_too_many_rows_are_refused_before_any_device_work
     assert (coef == 7.0).all() and (wc == 7).all() and (bits == 7).all(), "a refused call wrote"
     call()
     torch.cuda.synchronize()
-    want = cor.expected([0, 1], [3, 0], N)
+    want = cor.expected_spec([0, 1], [3, 0], N)
     got = (coef[:2 * 2 * N * 2048].cpu().numpy().reshape(2, 2, N, 2048), wc[:2 * N].cpu().numpy().reshape(2, N), bits[:2 * N].cpu().numpy().reshape(2, N))
     check(got, want, [0, 1], [3, 0], "valid call behind the refused ones")
     assert (coef[2 * 2 * N * 2048:] == 7.0).all() and (wc[2 * N:] == 7).all() and (bits[2 * N:] == 7).all()
@@ -331,12 +310,12 @@ def test_a_streaming_decode_continues_across_spectra_calls_and_a_sample_crop_beh
     stream_call(0)
     before = dec.save_streams(list(range(B)))
     for flags in (0, LR):
-        got = spectra_dev(dec, strided(cor), ch, bs, files, first, N, flags=flags)
-        check(got, cor.expected(files, first, N, lr=bool(flags)), files, first, "between two streaming calls")
+        got = spectra_dev(dec, cor.strided(), ch, bs, files, first, N, flags=flags)
+        check(got, cor.expected_spec(files, first, N, lr=bool(flags)), files, first, "between two streaming calls")
     assert before.tobytes() == dec.save_streams(list(range(B))).tobytes(), "a spectra call changed a stream's state"
     stream_call(1)
     # a sample-crop call behind a spectra call: the oracle's samples, channels-first
-    spectra_dev(dec, strided(cor), ch, bs, files, first, N)
+    spectra_dev(dec, cor.strided(), ch, bs, files, first, N)
     start, ns = [3 * bs + 100, 0, 20 * bs - 7], 2 * bs + 13
     pcm, _ = dec.decode_crops_samples(cor.host, cor.nbytes, cor.index, cor.count, [0, 1, 0], start, ns)
     for i, (f, st) in enumerate(zip([0, 1, 0], start)):
@@ -407,7 +386,7 @@ def test_crop_corpus_spectra_is_the_c_call(layout):
         assert tuple(wc.shape) == tuple(bits.shape) == (len(rows), N) and wc.dtype == bits.dtype == torch.int32
         torch.cuda.synchronize()
         got = (coef.cpu().numpy(), wc.cpu().numpy(), bits.cpu().numpy())
-        check(got, cor.expected(files, first, N, count, lr=lr), files, first, f"CropCorpus.spectra, {layout}")
-        c_call = spectra_dev(dec, strided(cor), cor.ch, cor.bs, files, first, N, count, LR if lr else 0)
+        check(got, cor.expected_spec(files, first, N, count, lr=lr), files, first, f"CropCorpus.spectra, {layout}")
+        c_call = spectra_dev(dec, cor.strided(), cor.ch, cor.bs, files, first, N, count, LR if lr else 0)
         assert S.same_bits(got[0], c_call[0]) and np.array_equal(got[1], c_call[1]) and np.array_equal(got[2], c_call[2])
     dec.close()

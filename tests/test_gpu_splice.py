@@ -4,13 +4,10 @@ oracle's walk of that concatenation, the PCM the oracle's decode of the concaten
 into poisoned buffers between guards (tests/guarded_buffers.py): nothing outside them is written, and no payload byte behind
 d_outPayloadBytes[o]."""
 import functools
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd, to_dev as _t
 import guarded_buffers as gb
 import splice_testlib as S
 from damage_testlib import kill_block, resize_block
@@ -21,21 +18,14 @@ LAYOUTS = ("strided", "ragged")
 POISON_F, POISON_I = 7.0, 7
 
 
-def _amd():
-    import ulc_amd
-    return ulc_amd
-
-
-def _t(a, dtype=None):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).to("cuda:0")
-
-
 def _src_dev(src, poffs=None, ioffs=None):
     """The source's buffers on the device, both layouts (plain tensors: inputs)."""
-    return dict(pay=_t(src.host), nb=_t(src.nbytes), idx=_t(src.index.view(np.int32)), cnt=_t(src.count),
-                rpay=_t(src.rpay), poffs=_t(src.poffs if poffs is None else poffs), ridx=_t(src.ridx.view(np.int32)),
-                ioffs=_t(src.ioffs if ioffs is None else ioffs))
+    d = dict(src.to_device())
+    if poffs is not None:
+        d["poffs"] = _t(poffs)
+    if ioffs is not None:
+        d["ioffs"] = _t(ioffs)
+    return d
 
 
 @functools.lru_cache(maxsize=None)
@@ -208,7 +198,7 @@ def test_capacity_cuts_one_file_and_leaves_the_others(geom, layout):
     files = [others[0], cut_file, others[1], others[2]]
     full = S.expected(src, files, 1 << 20, 64)[0]
     assert full[1].n == 9
-    at = lambda n: int(sum(len(src.extent(f, k)) for f, k in full[1].blocks[:n]))
+    at = lambda n: int(sum(len(S.extent(src, f, k)) for f, k in full[1].blocks[:n]))
     big = max(e.nbytes for e in full) + 5
     dec = _amd().BatchDecoder(2, src.ch, src.bs, 4)
     base = _splice(dec, src, d, layout, files, big, 12)
@@ -295,7 +285,7 @@ def test_untrusted_segment_offsets(layout):
 def _with_offs(src, f, k, value):
     offs = [o.copy() for o in src.offs]
     offs[f][k] = value
-    return S.Source(src.bs, src.ch, src.files, offs=offs)
+    return S.source_of(src.files, offs=offs)
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
@@ -340,13 +330,13 @@ def test_blocks_damaged_behind_the_stored_index(geom, layout):
         for cand in range(12, 18):
             pay, _ = fn(f0.payload, f0.offs, cand, seeds, clean.ch, clean.bs)
             if pay is not None:
-                s = S.Source(clean.bs, clean.ch, clean.files, payloads=[pay, clean.files[1].payload])
-                if not s.takes(0, cand):
+                s = S.source_of(clean.files, payloads=[pay, clean.files[1].payload])
+                if not S.takes(s, 0, cand):
                     src, j = s, cand
                     break
         if src is None:
             continue
-        assert src.takes(0, j - 1) and src.takes(0, j + 1), kind
+        assert S.takes(src, 0, j - 1) and S.takes(src, 0, j + 1), kind
         d = _src_dev(src)
         for place, seg in (("first", (0, j, 3)), ("middle", (0, j - 2, 5)), ("last", (0, j - 3, 4))):
             files = _around([(1, 4, 2), seg, (1, 0, 2)])
@@ -618,8 +608,8 @@ def test_corpus_splice_trim_and_switch(layout):
         pays = [pay[f, :nbytes[f]] for f in range(2 * n_clips)]
     for f, p in enumerate(pays):
         assert p.tobytes() == refs[f].payload.tobytes(), f"file {f} of the ladder corpus is not the oracle's encode"
-    files = [S.File(f"file {f}", r.blocks, r.bits) for f, r in enumerate(refs)]
-    src = S.Source(bs, ch, files)
+    files = [S.File(f"file {f}", bs, ch, r.blocks, r.bits) for f, r in enumerate(refs)]
+    src = S.source_of(files)
 
     def compare(got, segs, what):
         exp, starts = S.expected(src, segs, 1 << 22, nb * 3 + 2)

@@ -5,14 +5,12 @@ in a uniform batch; the command line must write what the reference's tool writes
 import os
 import re
 import struct
-import subprocess
-import sys
-import wave
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from ulc_testlib import write_wav16, run_tool
+from gpu_testlib import amd as _ulc
 from ulc_testlib import synth_pcm, oracle_encode_debug
 from rates_testlib import oracle_streams, mode_of
 
@@ -22,11 +20,6 @@ pytestmark = pytest.mark.gpu
 # ABR at (64, 0.02), (64, 0.35), (128, 0.98)
 MIXED = [(-1.0, 0.0), (32.0, 0.0), (64.0, 0.02), (-37.5, 0.0), (64.0, 0.0), (-50.0, 0.0), (64.0, 0.35), (-100.0, 0.0),
          (229.0, 0.0), (-117.0, 0.0), (128.0, 0.98), (-50.0, 0.3)]
-
-
-def _ulc():
-    import ulc_amd
-    return ulc_amd
 
 
 def _batch_pcm(B, n, ch, rate, seed):
@@ -223,20 +216,6 @@ needs_tools = pytest.mark.skipif(not (os.path.exists(ENC) and os.path.exists(TOO
                                  reason="ulcx-tool or the oracle/_ref tools not built (needs /root/reference at build time)")
 
 
-def _write_wav16(path, pcm16, rate):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(pcm16.shape[1]); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(pcm16.astype("<i2").tobytes())
-
-
-def _run(cmd):
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    p = subprocess.run(cmd, capture_output=True, env=env, timeout=600)
-    assert p.returncode == 0, f"{cmd[0]} failed ({p.returncode}): {p.stdout.decode()[-400:]} {p.stderr.decode()[-400:]}"
-    return p
-
-
 def _inputs(tmp_path, specs, rate, ch):
     ins = []
     for i, (sec, kind) in enumerate(specs):
@@ -247,7 +226,7 @@ def _inputs(tmp_path, specs, rate, ch):
             pcm = synth_pcm(80 + i, n, ch, rate, transient=(kind == "transient"), seed=17)
             pcm16 = np.clip(np.rint(pcm * 32767.0), -32768, 32767).astype(np.int16)
         p = tmp_path / f"f{i}.wav"
-        _write_wav16(p, pcm16, rate)
+        write_wav16(p, pcm16, rate)
         ins.append((p, pcm16))
     return ins
 
@@ -260,11 +239,11 @@ def test_cli_rate_groups_match_the_reference_tool_file_by_file(tmp_path):
     want = ["-50", "48", "48", "96,0.41", "-80"]
     got, ref = tmp_path / "got", tmp_path / "ref"
     got.mkdir(); ref.mkdir()
-    _run([TOOL, "encode", str(got)] + args)
+    run_tool([TOOL, "encode", str(got)] + args)
     many = tmp_path / "many"; many.mkdir()
-    _run([TOOL, "encode", str(many), args[0], "-devices:2"] + args[1:])
+    run_tool([TOOL, "encode", str(many), args[0], "-devices:2"] + args[1:])
     for (p, _), arg in zip(ins, want):
-        _run([ENC, str(p), str(ref / (p.stem + ".ulc")), arg])
+        run_tool([ENC, str(p), str(ref / (p.stem + ".ulc")), arg])
         r = open(ref / (p.stem + ".ulc"), "rb").read()
         assert open(got / (p.stem + ".ulc"), "rb").read() == r, f"{p.name} at {arg}: differs from ulcencodetool"
         assert open(many / (p.stem + ".ulc"), "rb").read() == r, f"{p.name} at {arg}: -devices:2 changed the file"
@@ -276,7 +255,7 @@ def test_cli_two_pass_abr_uses_each_files_own_average_complexity(tmp_path):
     rate, ch, bs = 44100, 2, 2048
     ins = _inputs(tmp_path, [(1.1, "transient"), (0.6, "tone"), (1.7, "transient"), (0.5, "silent")], rate, ch)
     got = tmp_path / "got"; got.mkdir()
-    out = _run([TOOL, "encode", str(got), "64,auto"] + [str(p) for p, _ in ins]).stdout.decode()
+    out = run_tool([TOOL, "encode", str(got), "64,auto"] + [str(p) for p, _ in ins]).stdout.decode()
     printed = {m.group(1): m.group(2) for m in re.finditer(r"^(\S+?): .*ABR complexity (\S+?)(?: \(CBR\))?, avg complexity", out, re.M)}
     for p, pcm16 in ins:
         n = pcm16.shape[0]
@@ -296,5 +275,5 @@ def test_cli_two_pass_abr_uses_each_files_own_average_complexity(tmp_path):
         assert open(got / (p.stem + ".ulc"), "rb").read() == want, f"{p.name}: two-pass ABR file differs from the oracle's"
         # and the reference tool, fed the same complexity, writes the same file
         refdir = tmp_path / "ref"; refdir.mkdir(exist_ok=True)
-        _run([ENC, str(p), str(refdir / (p.stem + ".ulc")), f"64,{float(avg):.9g}"])
+        run_tool([ENC, str(p), str(refdir / (p.stem + ".ulc")), f"64,{float(avg):.9g}"])
         assert open(refdir / (p.stem + ".ulc"), "rb").read() == want, f"{p.name}: reference tool at 64,{float(avg):.9g}"

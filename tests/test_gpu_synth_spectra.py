@@ -3,13 +3,10 @@ the decoder's inverse transform.  Expectations never come from this library's ow
 the two sides of ONE oracle run (tests/synth_spectra_testlib.py, orc_decode_stream_coefs) and are compared bit for bit (uint32 /
 int16 views); arbitrary planes are compared with the float64 referee (tests/mdct_referee.py) at the project's TOL.  What the inputs
 hold is asserted without a GPU in tests/test_synth_spectra_capi.py.  Outputs are poisoned before every call."""
-import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd
 import guarded_buffers as gb
 import mdct_referee as R
 import synth_spectra_testlib as Y
@@ -20,11 +17,6 @@ GEOMS = sorted(geometries().keys())
 LR, WARM = Y.SPECTRA_LR, Y.SYNTH_WARM
 N = Y.N_OUT
 ERR_ARG = -1
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
 
 
 def synth(dec, coef, wc, flags, pcm16=False):
@@ -304,7 +296,7 @@ def test_no_stream_state_moves(geom):
     check_rows(synth(dec, coef, wc, WARM), (pcm, live), bs, "between two decode calls")
     b, _ = dec.decode(two[:, 5:])
     whole = np.concatenate([a, b], axis=1)                  # [2][K bs][C]
-    assert same(whole[0].T, ref.pcm[:, :K * bs]), "stream 0 differs from the unsplit decode"
+    assert same(whole[0].T, Y.pcm_planes(ref)[:, :K * bs]), "stream 0 differs from the unsplit decode"
     cor = _geom_corpus(geom)
     files, start, ns = [0, 0], [3 * bs + 17, 0], 2 * bs + 5
     check_rows(synth(dec, coef, wc, WARM), (pcm, live), bs, "in front of a sample crop")

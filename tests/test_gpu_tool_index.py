@@ -2,33 +2,19 @@
 (include/ulc_amd.h section 3) whose entries are ulcx_index_packed_host's of the file's payload, and `decode -blocks:` writes
 the same bytes with the sidecar, without it, and with one it has to refuse."""
 import os
-import subprocess
 import sys
-import wave
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ulc_testlib import synth_pcm
+from ulc_testlib import synth_pcm, run_tool, write_wav16
 
 pytestmark = pytest.mark.gpu
 TOOL = os.path.join(ROOT, "ulc-codec_amd", "ulcx-tool")
 RATE, BS, CH = 44100, 2048, 2
 FRAMES = (9 * BS + 100, 5 * BS)                             # two short files of different length: 12 and 7 blocks
-
-
-def _run_tool(args):
-    env = dict(os.environ)
-    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
-    return subprocess.run([TOOL] + args, capture_output=True, env=env, timeout=600)
-
-
-def _write_wav16(path, pcm, rate):
-    with wave.open(str(path), "wb") as w:
-        w.setnchannels(pcm.shape[1]); w.setsampwidth(2); w.setframerate(rate)
-        w.writeframes(np.rint(pcm * 32768.0).astype("<i2").tobytes())
 
 
 @pytest.fixture(scope="module")
@@ -38,13 +24,13 @@ def encoded(tmp_path_factory):
     wavs = []
     for i, n in enumerate(FRAMES):
         p = d / f"{'ab'[i]}.wav"
-        _write_wav16(p, synth_pcm(30 + i, n, CH, RATE, transient=True, seed=4), RATE)
+        write_wav16(p, np.rint(synth_pcm(30 + i, n, CH, RATE, transient=True, seed=4) * 32768.0), RATE)
         wavs.append(str(p))
     lad, one = d / "ladder", d / "one"
     lad.mkdir(); one.mkdir()
-    r = _run_tool(["encode", str(lad), "-50/64", "-index"] + wavs)
+    r = run_tool([TOOL, "encode", str(lad), "-50/64", "-index"] + wavs, check=False)
     assert r.returncode == 0, r.stderr.decode()
-    r = _run_tool(["encode", str(one), "-50", "-index"] + wavs)
+    r = run_tool([TOOL, "encode", str(one), "-50", "-index"] + wavs, check=False)
     assert r.returncode == 0, r.stderr.decode()
     return lad, one
 
@@ -98,7 +84,7 @@ def test_decode_blocks_writes_the_same_bytes_with_without_and_with_a_refused_sid
                 open(src / f"{n}.ulx", "wb").write(bytes(x))
         dst = tmp_path / f"out_{tag}"
         dst.mkdir()
-        r = _run_tool(["decode", str(dst), "-format:FLOAT32", "-blocks:3,4", str(src / "a.ulc"), str(src / "b.ulc")])
+        r = run_tool([TOOL, "decode", str(dst), "-format:FLOAT32", "-blocks:3,4", str(src / "a.ulc"), str(src / "b.ulc")], check=False)
         assert r.returncode == 0, r.stderr.decode()
         outs[tag] = {n: open(dst / f"{n}.wav", "rb").read() for n in "ab"}
         assert (NOTICE in r.stderr) == (tag != "with"), (tag, r.stderr.decode())
@@ -108,7 +94,7 @@ def test_decode_blocks_writes_the_same_bytes_with_without_and_with_a_refused_sid
             assert b"a.ulc" in r.stderr and b"ulcx_index_check" in r.stderr, r.stderr.decode()
     full = tmp_path / "full"
     full.mkdir()
-    r = _run_tool(["decode", str(full), "-format:FLOAT32", str(one / "a.ulc"), str(one / "b.ulc")])
+    r = run_tool([TOOL, "decode", str(full), "-format:FLOAT32", str(one / "a.ulc"), str(one / "b.ulc")], check=False)
     assert r.returncode == 0, r.stderr.decode()
     bpf = CH * 4 * BS
     for n in "ab":

@@ -16,17 +16,12 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd
 import mdct_referee as R
 from ulc_testlib import spec_stream
 from test_transform_referee import TOL, ALL_CODES, transient_pcm, decoder_case
 
 pytestmark = pytest.mark.gpu
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
 
 
 def _check_tap(pcm, wc, coef, N, C, what):

@@ -13,20 +13,13 @@ Where the prediction departs from the plain reading "a block over a small capaci
     bit 2 is withheld only beyond that (test_stereo_exact_path_at_scale_stands_back_from_direct_packing).
   * a block that keeps nothing never reaches the exact path, whatever ulcx_encoder_debug_force_exact says."""
 import os
-import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "ulc-codec_amd"))
+from gpu_testlib import amd as _amd
 import writer_tiers_testlib as W
 
 pytestmark = pytest.mark.gpu
-
-
-def _amd():
-    import ulc_amd
-    return ulc_amd
 
 
 def _encoder(case, K, env=None):

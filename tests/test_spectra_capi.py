@@ -246,16 +246,16 @@ def test_expected_values_are_the_oracles_coefficients_channels_first():
     and exact values of the coded coefficients."""
     cor = S.geom_corpus((2048, 2))
     f = cor.files[0]
-    coef, wc, bits = f.expected(37, 5)
+    coef, wc, bits = f.expected_spec(37, 5)
     assert coef.shape == (2, 5, 2048) and (bits[:3] > 0).all() and (bits[3:] == 0).all() and (wc[3:] == 0).all() and not coef[:, 3:].any()
     for k in (1, 9, 24, 38):
         spec, noise, _ = S.decode_block_coefficients(f.blocks[k, :(int(f.bits[k]) + 7) // 8], 2, 2048)
         assert np.array_equal(np.abs(f.coef[k]), np.abs(spec)) and np.array_equal(f.coef[k][noise == 0], spec[noise == 0]), k
-    lr = f.expected(5, 5, lr=True)[0]
+    lr = f.expected_spec(5, 5, lr=True)[0]
     m, s = f.coef[5:10, 0], f.coef[5:10, 1]
     assert S.same_bits(lr[0], m + s) and S.same_bits(lr[1], m - s) and not S.same_bits(lr[0], m)
     c3 = S.geom_corpus((2048, 3)).files[0]
-    lr3 = c3.expected(5, 5, lr=True)[0]
+    lr3 = c3.expected_spec(5, 5, lr=True)[0]
     assert S.same_bits(lr3[2], c3.coef[5:10, 2])            # a trailing single channel is untouched
-    short = f.expected(5, 5, count=2)
+    short = f.expected_spec(5, 5, count=2)
     assert (short[2][:2] > 0).all() and (short[2][2:] == 0).all() and not short[0][:, 2:].any()

@@ -167,7 +167,7 @@ def test_the_sources_and_the_rule():
     for geom in S.GEOMS:
         src = S.source(geom)
         assert src.F == 2 and {f.K for f in src.files} <= {40, 24}
-        assert all(src.takes(f, k) for f in range(2) for k in (0, src.files[f].K - 1))
+        assert all(S.takes(src, f, k) for f in range(2) for k in (0, src.files[f].K - 1))
         names = [n for n, _ in S.shapes(src)]
         assert len(set(names)) == len(names) == 12
         segs = dict(S.shapes(src))

@@ -106,10 +106,10 @@ def test_pcm_of_a_block_depends_on_two_planes(geom):
         sw = Y.switched(ref)
         for k in (sw[0], sw[len(sw) // 2], sw[-1]):
             m = min(Y.N_OUT, ref.K - k)
-            planes = ref.coef[:, k - 1:k + m].transpose(1, 0, 2).reshape(m + 1, ch * bs)
+            planes = Y.planes(ref)[:, k - 1:k + m].transpose(1, 0, 2).reshape(m + 1, ch * bs)
             headers = [Y.referee_header(w) for w in ref.wc[k - 1:k + m + 1]]
             y = R.synthesise(planes, headers, bs, ch)[:(m + 1) * bs]
-            e = R.unit_errors(R.pcm_units(ref.pcm[:, (k - 1) * bs:(k + m) * bs].T, bs), R.pcm_units(y, bs))
+            e = R.unit_errors(R.pcm_units(Y.pcm_planes(ref)[:, (k - 1) * bs:(k + m) * bs].T, bs), R.pcm_units(y, bs))
             worst = max(worst, e[1:].max())
             off += bool(e[0].max() > 100 * Y.TOL)
     assert worst <= Y.TOL, worst

@@ -322,3 +322,53 @@ def spec_stream(headers, n_chan, block_size, seed, silent_blocks=()):
     for b, r in enumerate(rows):
         out[b, :r.size] = r
     return out, coefs, subs_all
+
+
+# ---------------------------------------------------------------------------
+# small helpers every family shares
+# ---------------------------------------------------------------------------
+def to_pcm16(x):
+    return np.clip(np.rint(x.astype(np.float32) * np.float32(32768.0)), -32768, 32767).astype(np.int16)       # WavIO_Helper.c:56-63
+
+
+def same_bits(a, b, shape=True):
+    """float32 arrays equal bit for bit (uint32 views); shape=False: of equal size, whatever their shapes."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    if not shape:
+        a, b = a.ravel(), b.ravel()
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def same_bits64(a, b):
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def same_bytes(a, b, shape=True):
+    """Arrays of one dtype with the same bytes; shape=False: of equal size, whatever their shapes."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and (a.shape == b.shape if shape else a.size == b.size) and a.tobytes() == b.tobytes()
+
+
+def wc_of(blocks):
+    """WindowCtrl of every block [K][slot] from its first byte (ulcDecoder.c:211-216)."""
+    b = blocks[:, 0].astype(np.int32)
+    wc = b & 0xF
+    return np.where((wc & 8) != 0, wc | (b & 0xF0), wc | 0x10).astype(np.int32)
+
+
+def write_wav16(path, pcm16, rate):
+    """pcm16 int16 [n][C] -> a 16-bit WAV file."""
+    import wave
+    with wave.open(str(path), "wb") as w:
+        w.setnchannels(pcm16.shape[1]); w.setsampwidth(2); w.setframerate(rate)
+        w.writeframes(pcm16.astype("<i2").tobytes())
+
+
+def run_tool(cmd, check=True):
+    """One of the built command-line programs with the library on its path -> the finished process; check: it must exit with 0."""
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = os.path.join(ROOT, "ulc-codec_amd") + ":/opt/rocm/lib:" + env.get("LD_LIBRARY_PATH", "")
+    p = subprocess.run(cmd, capture_output=True, env=env, timeout=600)
+    assert not check or p.returncode == 0, f"{cmd[0]} failed ({p.returncode}): {p.stdout.decode()[-400:]} {p.stderr.decode()[-400:]}"
+    return p
