@@ -146,6 +146,14 @@ def _make_cases():
         for i, ch in enumerate((1, 2, 3, 6)):
             mode, p0, p1 = ((VBR, 50.0, 0.0), (CBR, 96.0, 0.0), (ABR, 128.0, 0.4), (VBR, 70.0, 0.0))[i]
             cases[f"shape_{bs}x{ch}"] = lambda bs=bs, ch=ch, mode=mode, p0=p0, p1=p1: _shape(bs, ch) + (mode, p0, p1)
+    # the geometry axis (tests/geometry_axis_testlib.py): the oracle's footing at the channel counts its cases add - gap sums at their
+    # limit (16) and just behind it (17), 32, the header's last count (255) - and mono 4096 in a rate search; 9 blocks of 256 are more
+    # samples than synth_pcm's delay of 7 per channel needs
+    for ch in (16, 17, 32, 255):
+        for mode, p0 in ((VBR, 50.0), (CBR, 48.0 * ((ch + 1) // 2))):
+            cases[f"chan_256x{ch}_m{mode}_{p0:g}"] = lambda ch=ch, mode=mode, p0=p0: (
+                synth_pcm(2000 + ch, 9 * 256, ch, 44100, transient=True, seed=256 * 7 + ch), 256, 44100, mode, p0, 0.0)
+    cases["chan_4096x1_m1_64"] = lambda: (synth_pcm(2001, 6 * 4096, 1, 44100, transient=True, seed=4096 * 7 + 1), 4096, 44100, CBR, 64.0, 0.0)
     return cases
 
 

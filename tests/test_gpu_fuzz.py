@@ -27,3 +27,13 @@ def test_randomised_rate_search_sweep():
     import fuzz_parity
     n, nblk = fuzz_parity.run(budget=40.0, seed=3, rate_search=True)
     assert n >= 8 and nblk >= 100, f"the sweep covered too little in its time budget: {n} configurations, {nblk} blocks"
+
+
+def test_randomised_many_channel_sweep():
+    """The sweep over the geometries tests/geometry_axis_testlib.py adds by hand: BlockSize 256 / 512 / 1024 with 4, 7, 8, 16, 17 and
+    32 channels - wave selections whose lanes hold keys of many channels, the gap sums up to their channel limit and the first
+    counts without them.  The floor is half of what the first run on an MI355X reached in its 20 s: 389 configurations,
+    15568 blocks."""
+    import fuzz_parity
+    n, nblk = fuzz_parity.run(budget=20.0, seed=11, sizes=[256, 512, 1024], chans=[4, 7, 8, 16, 17, 32])
+    assert n >= 194 and nblk >= 7784, f"the sweep covered too little in its time budget: {n} configurations, {nblk} blocks"
