@@ -24,7 +24,8 @@
 // ---------------------------------------------------------------------------
 // launcher
 // ---------------------------------------------------------------------------
-// 4 padded arrays of BS/2 complex + BS/4 twiddles + counter (+ BS/2 floats of line energies for C > 2)
+// 4 padded arrays of BS/2 complex + BS/4 twiddles + 32 bytes (once the non-zero counter's: xf_block's offsets keep the slot)
+// (+ BS/2 floats of line energies for C > 2)
 static size_t ulcx_enc_xf_lds_bytes(int BS, int C) {
     if (BS > 8192) return (size_t)BS * 4;                       // k_xf_big: one unpadded array of BS/2 complex
     int ps = ulcx_xf_pad_shift(BS, C);

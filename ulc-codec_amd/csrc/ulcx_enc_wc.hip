@@ -110,17 +110,28 @@ __global__ __launch_bounds__(64) void k_wc_forward(UlcxEncCtx c, int k0, int k1)
     if (live) c.wcs[s].tf[f] = env;                                   // state for the next call
 }
 
-// (stereo only: the producers split the envelope computation into its three 8-byte loads, issued tiles ahead,
-//  and the arithmetic)
-__device__ __forceinline__ float2 wc_energy_stereo(float2 a, float2 b, float2 d) {        // as wc_energy_at, C == 2
-    float m0 = (a.x + a.y) * 0.5f, m1 = (b.x + b.y) * 0.5f, m2 = (d.x + d.y) * 0.5f;
-    float s0 = (a.x - a.y) * 0.5f, s1 = (b.x - b.y) * 0.5f, s2 = (d.x - d.y) * 0.5f;
+// (stereo only: the producers split the envelope computation into its loads, issued tiles ahead, and the arithmetic)
+__device__ __forceinline__ float2 wc_energy_ms(float m0, float m1, float m2, float s0, float s1, float s2) {   // as wc_energy_at, C == 2, from mid / side
     float ehp = 0.0f, ebp = 0.0f;
     float hp = -m0 + 2 * m1 - m2, bp = -m0 + m2;
     ehp += hp * hp; ebp += bp * bp;
     hp = -s0 + 2 * s1 - s2; bp = -s0 + s2;
     ehp += hp * hp; ebp += bp * bp;
     return make_float2(sqrtf(ehp), sqrtf(ebp));
+}
+// A producer lane holds ONE time step: its own sample pair, M/S-converted once.  The two neighbours' mid / side come from
+// lanes t-1 and t+1 by a whole-wave shift (DPP, no LDS); a lane with no neighbour in the wave (0, 63) keeps `edge`, the
+// M/S of the one sample outside the tile, which only those two lanes load.  A moved M/S is the same float.
+__device__ __forceinline__ float wc_from_prev_lane(float own, float edge) {       // lane t: own of lane t-1; lane 0: edge
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(own), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float wc_from_next_lane(float own, float edge) {       // lane t: own of lane t+1; lane 63: edge
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(own), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float2 wc_energy_lanes(float2 b, float2 e) {           // b: this lane's sample pair, e: lanes 0 / 63 - the pair outside the tile
+    const float m1 = (b.x + b.y) * 0.5f, s1 = (b.x - b.y) * 0.5f;
+    const float me = (e.x + e.y) * 0.5f, se = (e.x - e.y) * 0.5f;
+    return wc_energy_ms(wc_from_prev_lane(m1, me), m1, wc_from_next_lane(m1, me), wc_from_prev_lane(s1, se), s1, wc_from_next_lane(s1, se));
 }
 
 template <int NW, typename IN>
@@ -140,12 +151,16 @@ __global__ __launch_bounds__(NW * 64) void k_wc_ef(UlcxEncCtx c, int k0, int k1)
             if (lane == 0) __atomic_store_n(&flags[p], 0x7ffffff0, __ATOMIC_RELEASE);
             return;
         }
-        // THREE tiles of loads in flight per producer wave (a tile period is shorter than the latency of a load when the
+        // EF_AHEAD tiles of loads in flight per producer wave (a tile period is shorter than the latency of a load when the
         // transform runs beside this kernel): register sets A0/A1/A2 rotate by unrolling the tile loop three times
 #ifndef EF_AHEAD
 #define EF_AHEAD 3
 #endif
-        float2 A[EF_AHEAD][NS][3];
+        float2 A[EF_AHEAD][NS][2];                        // [0] this lane's sample pair, [1] lanes 0 and 63: the pair left / right of the tile
+#pragma unroll
+        for (int a = 0; a < EF_AHEAD; a++)
+#pragma unroll
+            for (int i = 0; i < NS; i++) A[a][i][1] = make_float2(0.0f, 0.0f);      // (the other lanes never load it and never use it)
         // this lane's sample of step 0 of the call, per stream of the wave (the 64-bit stream offset once, not per tile:
         // three quarter-rate multiplies a tile)
         const IN *sbase[NS];
@@ -155,7 +170,9 @@ __global__ __launch_bounds__(NW * 64) void k_wc_ef(UlcxEncCtx c, int k0, int k1)
             const int sc = ((p + NP * i < EF_SPW) && (s < c.B)) ? s : 0;
             sbase[i] = pcm_base<IN>(c) + (size_t)sc * c.K * c.BS * 2 + 2 * lane;
         }
-        auto issue = [&](float2 (&A)[NS][3], int j) {     // the three samples of this lane's time step of tile j, every stream of this wave
+        const bool edgeLane = (lane == 0) || (lane == 63);
+        const int edgeStep = (lane == 0) ? -1 : 1;        // the sample outside the tile, relative to this lane's
+        auto issue = [&](float2 (&A)[NS][2], int j) {     // the sample of this lane's time step of tile j, every stream of this wave
             const int t0 = (k0 * c.BS + j * 64) - c.BS / 2;                                                     // lane 0's centre sample (wave-uniform)
             const int t = t0 + lane;
 #pragma unroll
@@ -165,17 +182,21 @@ __global__ __launch_bounds__(NW * 64) void k_wc_ef(UlcxEncCtx c, int k0, int k1)
                 const int sc = on ? s : 0;                // (a stream that exists: the values are not used)
                 if (t0 >= 1) {
                     // the tile and its two neighbours lie in this call's input (all but the first BS/2 + 1 steps of a call): one
-                    // wave-uniform base, three loads at constant offsets (round 3: the general form below - a history / input
+                    // wave-uniform base, loads at constant offsets (round 3: the general form below - a history / input
                     // select and a 64-bit stream offset per load - was 54 of the 113 vector instructions a step costs here)
                     const IN *q = sbase[i] + 2 * (ptrdiff_t)t0;
-                    A[i][0] = ld2(q - 2); A[i][1] = ld2(q); A[i][2] = ld2(q + 2);
-                } else { A[i][0] = smp_ld2<IN>(c, sc, t - 1); A[i][1] = smp_ld2<IN>(c, sc, t); A[i][2] = smp_ld2<IN>(c, sc, t + 1); }
+                    A[i][0] = ld2(q);
+                    if (edgeLane) A[i][1] = ld2(q + 2 * edgeStep);
+                } else {
+                    A[i][0] = smp_ld2<IN>(c, sc, t);
+                    if (edgeLane) A[i][1] = smp_ld2<IN>(c, sc, t + edgeStep);
+                }
             }
         };
-        auto step = [&](float2 (&A)[NS][3], int j) {
+        auto step = [&](float2 (&A)[NS][2], int j) {
             float2 v[NS];
 #pragma unroll
-            for (int i = 0; i < NS; i++) v[i] = wc_energy_stereo(A[i][0], A[i][1], A[i][2]);
+            for (int i = 0; i < NS; i++) v[i] = wc_energy_lanes(A[i][0], A[i][1]);
             if (j + EF_AHEAD < nT) issue(A, j + EF_AHEAD);
             while (j >= __atomic_load_n(&flags[NP], __ATOMIC_ACQUIRE) + EF_RT) __builtin_amdgcn_s_sleep(4);     // ring full
             float *tile = ring + (j % EF_RT) * EF_TILE_FLOATS;

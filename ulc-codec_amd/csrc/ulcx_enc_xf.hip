@@ -32,9 +32,9 @@ __device__ __forceinline__ float win_apply(float x, int i, int S, int aL, int ov
 // selects fold away, and the four transforms run the compile-time passes (fft_wave_dif_ct).
 // (BSC: 2048, the headline geometry; 4096 since round 4 - the window-switching configuration's un-decimated blocks)
 // AN (the analysis call, k_xfa): the MDCT alone - the two zc arrays side by side, no MDST arrays, fold products, transforms or
-// post-twiddle, no line energies, no non-zero count; what is left is the very arithmetic of the encode instantiation.
+// post-twiddle, no line energies; what is left is the very arithmetic of the encode instantiation.
 template <typename IN, int BSC, bool AN = false>
-__device__ __forceinline__ int xf_fast(const UlcxEncCtx &c, float *lds, int s, int k, int blk, int tid) {
+__device__ __forceinline__ void xf_fast(const UlcxEncCtx &c, float *lds, int s, int k, int blk, int tid) {
     constexpr int BS = BSC, S = BSC, M = BSC / 2, PS = 4, Mp = FFT_PADDEDS(M, PS);
     constexpr int LGM = BSC == 4096 ? 11 : 10;
     static_assert(BSC == 2048 || BSC == 4096, "sizes with a compile-time transform");
@@ -95,7 +95,6 @@ __device__ __forceinline__ int xf_fast(const UlcxEncCtx &c, float *lds, int s, i
     __syncthreads();
     float *coefO = c.coef + (size_t)blk * (2 * BS);
     constexpr float norm = 2.0f / S;
-    int nnz = 0;
     if constexpr (AN) {
         // the MDCT half of the epilogue below: same indices, same products, the same 16-byte stores of the coefficients
 #pragma unroll
@@ -129,7 +128,7 @@ __device__ __forceinline__ int xf_fast(const UlcxEncCtx &c, float *lds, int s, i
                 stnt((float4 *)(coefO + q * BS + 2 * j2), make_float4(re[q][1][0], re[q][1][1], re[q][1][2], re[q][1][3]));
             }
         }
-        return 0;
+        return;
     }
     // A thread takes TWO neighbouring post-twiddle indices (kk = 2 tid, 2 tid + 1: M/2 = 2 WG of them), so that what it
     // writes is contiguous: coefficients 4 tid .. 4 tid + 3 and BS - 4 - 4 tid .. BS - 1 - 4 tid of each channel as 16-byte
@@ -161,8 +160,6 @@ __device__ __forceinline__ int xf_fast(const UlcxEncCtx &c, float *lds, int s, i
                     const float re1 = mdct[2*p+1] * norm, im1 = mdst[2*p+1] * norm;
                     const float re0s = re0 * re0, im0s = im0 * im0, re1s = re1 * re1, im1s = im1 * im1;
                     const float a0 = re0s + im0s, a1 = re1s + im1s;
-                    nnz += (fabsf(re0) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
-                    nnz += (fabsf(re1) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
                     // k1 side: pairs kA, kB ascending; k2 side: pairs k2(kB) = k2(kA) - 1 then k2(kA): ascending too
                     const int slot = p ? (1 - u) : u;
                     re[q][p][2 * slot] = re0; re[q][p][2 * slot + 1] = re1;
@@ -182,7 +179,6 @@ __device__ __forceinline__ int xf_fast(const UlcxEncCtx &c, float *lds, int s, i
         *(float2 *)(c.amp2 + tile_idx(BS / 2, blk, j1)) = make_float2(am[0][0], am[0][1]);
         *(float2 *)(c.amp2 + tile_idx(BS / 2, blk, j2)) = make_float2(am[1][0], am[1][1]);
     }
-    return nnz;
 }
 
 // which blocks take the steady-state path: stereo BlockSize 2048 (the caller's business), un-decimated, full overlap on
@@ -215,11 +211,9 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
     float2 *z    = (float2 *)lds;                     // 4 arrays of up to BS/2 complex: {MDCT, MDST} x {ch, ch+1}
     constexpr int NA = AN ? 2 : 4;                    // (analysis: the two MDCT arrays, side by side)
     float2 *twl  = (float2 *)(lds + NA * FFT_PADDEDS(BS, ps));    // BS/4 complex: this subblock's FFT twiddles (no global-memory latency inside the FFT passes)
-    int    &s_nnz = *(int *)(lds + NA * FFT_PADDEDS(BS, ps) + BS / 2);  // (inside the dynamic region: no static LDS in front of it)
     const bool ampLds = !AN && (C > 2);                      // line energies accumulate across channel pairs: only then in LDS
     const bool twInLds = !(ampLds && (size_t)16 * (BS + (BS >> ps)) + (size_t)BS * 4 + 32 > ULCX_LDS_LIMIT);   // (BlockSize 8192 with C > 2: no room, twiddles from global memory)
     float  *amp2 = twInLds ? lds + 4 * FFT_PADDEDS(BS, ps) + BS / 2 + 4 : lds + 4 * FFT_PADDEDS(BS, ps);   // BS/2 (takes the twiddles' place when they are not resident)
-    if (!AN && tid == 0) s_nnz = 0;
     if (ampLds) for (int i = tid; i < BS / 2; i += WG) amp2[i] = 0.0f;
 
     const int *wrow = c.wcArr + (size_t)s * (c.maxK + 2) + k;
@@ -236,7 +230,6 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
     }
     size_t cb = (size_t)C * BS;
     float *coefO = c.coef + (size_t)blk * cb;
-    int nnz = 0;
     __syncthreads();
 
     // the steady state of the headline geometry (and of BlockSize 4096) takes the all-constants path (xf_fast)
@@ -247,7 +240,7 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
     const bool fastBlk = ST && (BS == 2048 || BS == 4096) && (k >= 2 || std::is_same<IN, float>::value) && (ulcx_pattern(wc) >> 4) == 0
                          && ovFirst == BS && nextOv >= BS;
 #endif
-    if (fastBlk) nnz = (BS == 2048) ? xf_fast<IN, 2048, AN>(c, lds, s, k, blk, tid) : xf_fast<IN, 4096, AN>(c, lds, s, k, blk, tid);
+    if (fastBlk) { if (BS == 2048) xf_fast<IN, 2048, AN>(c, lds, s, k, blk, tid); else xf_fast<IN, 4096, AN>(c, lds, s, k, blk, tid); }
     else
     for (int ch0 = 0; ch0 < C; ch0 += 2) {             // one M/S pair (or a trailing single channel) at a time
         const int nch = ST ? 2 : ((ch0 + 1 < C) ? 2 : 1);
@@ -409,8 +402,6 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
                         float a0 = re0s + im0s, a1 = re1s + im1s;
                         // (the importance key FastLog(Re^2) is a function of the stored coefficient: the kernels that consume
                         //  keys form it from there, key0_of(), instead of this one writing 4 more bytes per coefficient)
-                        nnz += (fabsf(re0) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
-                        nnz += (fabsf(re1) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
                         int j = p ? k2 : k1;
                         size_t gi = (size_t)ch * BS + off + 2 * j;
                         stnt((float2 *)(coefO + gi), make_float2(re0, re1));
@@ -426,13 +417,8 @@ __device__ __forceinline__ void xf_block(const UlcxEncCtx &c, float *lds, int s,
             off += S; ovL = ov;
         } while (pat);
     }
-    if (AN) return;
-    // wave-reduce the non-zero count
-    for (int o = 32; o > 0; o >>= 1) nnz += __shfl_down(nnz, o);
-    if ((tid & 63) == 0) atomicAdd(&s_nnz, nnz);
+    // (the count of non-zero coefficients is taken where they are next read: k_cplx)
     if (ampLds) for (int i = tid; i < BS / 2; i += WG) c.amp2[tile_idx(BS / 2, blk, i)] = amp2[i];
-    __syncthreads();
-    if (tid == 0) c.nnz[blk] = s_nnz;
 }
 
 // Blocks [k0, k1) of every stream, one workgroup each (the chunks of the window-control pipeline: every geometry but the
@@ -467,12 +453,12 @@ __global__ __launch_bounds__(WG, XFA_LB) void k_xfa(UlcxEncCtx c, int k0, int k1
 
 // ---------------------------------------------------------------------------
 // The same transform for BlockSize > 8192 (ulcEncoder.c:32-34 accepts up to 32768): the four arrays of a channel pair do
-// not fit in LDS together, so ONE array at a time - per channel the MDCT (coefficients, non-zero count), then the MDST
+// not fit in LDS together, so ONE array at a time - per channel the MDCT (coefficients), then the MDST
 // (line energies; Re^2 re-formed from the stored coefficient) - folded sample by sample through ms_sample()/win_apply(),
 // transformed by the whole workgroup (fftn_dif: the same butterflies, a barrier per pass).  Every arithmetic step is the
 // one k_xf takes, in the same order; not tuned (such block sizes are not a throughput case).
 // ---------------------------------------------------------------------------
-// (AN: the analysis call - the MDCT pass of every channel, no MDST pass, no count, no list)
+// (AN: the analysis call - the MDCT pass of every channel, no MDST pass, no list)
 template <typename IN, bool AN>
 __device__ __forceinline__ void xf_big_block(const UlcxEncCtx &c, int k0, int k1) {
     extern __shared__ float lds[];
@@ -485,8 +471,6 @@ __device__ __forceinline__ void xf_big_block(const UlcxEncCtx &c, int k0, int k1
     const int blk = s * c.K + k;
     const int tid = threadIdx.x;
     float2 *z = (float2 *)lds;                         // one array of up to BS/2 complex, unpadded
-    __shared__ int s_nnz;
-    if (tid == 0) s_nnz = 0;
     const int *wrow = c.wcArr + (size_t)s * (c.maxK + 2) + k;
     const int wcPrev = wrow[0], wc = wrow[1], wcNext = wrow[2];
     if (!AN && c.barkRing && threadIdx.x == 0 && (ulcx_pattern(wc) & ~8u) != 0) c.decList[atomicAdd(c.decCount, 1)] = blk;
@@ -501,7 +485,6 @@ __device__ __forceinline__ void xf_big_block(const UlcxEncCtx &c, int k0, int k1
     }
     const size_t cb = (size_t)C * BS;
     float *coefO = c.coef + (size_t)blk * cb;
-    int nnz = 0;
     __syncthreads();
     for (int ch = 0; ch < C; ch++) {
         unsigned pat = ulcx_pattern(wc);
@@ -557,8 +540,6 @@ __device__ __forceinline__ void xf_big_block(const UlcxEncCtx &c, int k0, int k1
                         if (kind == 0) {
                             const float m0 = p ? y2.x : y1.x, m1 = p ? y1.y : y2.y;
                             const float re0 = m0 * norm, re1 = m1 * norm;
-                            nnz += (fabsf(re0) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
-                            nnz += (fabsf(re1) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
                             *(float2 *)(coefO + gi) = make_float2(re0, re1);
                         } else {
                             const float m0 = p ? y2.x : y1.x, m1 = p ? y1.y : y2.y;
@@ -579,11 +560,6 @@ __device__ __forceinline__ void xf_big_block(const UlcxEncCtx &c, int k0, int k1
             off += S; ovL = ov;
         } while (pat);
     }
-    if (AN) return;
-    for (int o = 32; o > 0; o >>= 1) nnz += __shfl_down(nnz, o);
-    if ((tid & 63) == 0) atomicAdd(&s_nnz, nnz);
-    __syncthreads();
-    if (tid == 0) c.nnz[blk] = s_nnz;
 }
 
 #ifndef ULCX_XF_ANALYSIS_UNIT
@@ -609,8 +585,10 @@ __global__ __launch_bounds__(64) void k_cplx(UlcxEncCtx c, int k0, int k1) {
     int n = c.C * c.BS;
     const float4 *p = (const float4 *)(c.coef + (size_t)blk * n);
     float cx = 0.0f, cw = 0.0f;
-    int tiny = 0;
-    // n is a multiple of 256: 4 x 16-byte loads in flight per step.  The count of collapsible coefficients only feeds
+    int tiny = 0, nz = 0;
+    // n is a multiple of 256: 4 x 16-byte loads in flight per step.  The count of non-zero coefficients (MaxCoef of the rate
+    // control) is taken here, where every coefficient passes through a register anyway - the transform does not count (the
+    // same compares: this kernel waits for its loads and has the issue slots).  The count of collapsible coefficients only feeds
     // the CBR/ABR probe shortcut below: VBR calls take the loop without it (half the instructions of this
     // issue-bound kernel; the branch is uniform for the whole launch).
     auto sums = [&](auto tinyT) {
@@ -626,6 +604,10 @@ __global__ __launch_bounds__(64) void k_cplx(UlcxEncCtx c, int k0, int k1) {
                 cx += v.y * v.y; cw += fabsf(v.y);
                 cx += v.z * v.z; cw += fabsf(v.z);
                 cx += v.w * v.w; cw += fabsf(v.w);
+                nz += (fabsf(v.x) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
+                nz += (fabsf(v.y) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
+                nz += (fabsf(v.z) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
+                nz += (fabsf(v.w) < 0.5f * ULCX_COEF_EPS) ? 0 : 1;
                 if (TINY) {
                     // non-zero coefficients so small that the coarsest quantizer (2^31) could collapse them (Encode.c:114)
                     tiny += (fabsf(v.x) >= 0.5f * ULCX_COEF_EPS && fabsf(v.x) < 0x1.0p-29f) ? 1 : 0;
@@ -655,7 +637,8 @@ __global__ __launch_bounds__(64) void k_cplx(UlcxEncCtx c, int k0, int k1) {
         if (cx > 1.0f) cx = 1.0f;
     }
     c.cplx[blk] = cx;
-    int maxCoef = c.nnz[blk];
+    const int maxCoef = nz;
+    c.nnz[blk] = nz;                                  // (k_rung_arm re-arms a ladder's further rungs from it)
     if (mode == ULCX_MODE_VBR) {
         int nT = maxCoef;
         if (vbrTarget > 0.0f) {
