@@ -322,6 +322,13 @@ int  ulcx_encoder_debug_writer_plan(ulcx_encoder *enc, int32_t plan[11]);
 int  ulcx_debug_band_plan(int BlockSize, int RateHz, int16_t *edges, int32_t *most, int32_t *ring);
 int  ulcx_debug_band_events(int BlockSize, int RateHz, uint32_t *events);
 int  ulcx_encoder_debug_plan(ulcx_encoder *enc, int32_t plan[7]);
+/* Test hook, read-only: the window axis.  How a call of nBlocks on this object would be cut by the launch of its front half:
+ * out = {transform chunks nCh, window-control steps nW, the nCh + 1 transform cuts, the nW + 1 step boundaries}, the rest of
+ * the ULCX_FRONT_PLAN_WORDS words -1.  The plain launch (short calls, objects without side streams) reports one chunk and one
+ * step, both {0, nBlocks}.  Host arithmetic by the function the launch calls; no device work.  Refuses (ULCX_ERR_ARG) an
+ * nBlocks outside 1 .. maxBlocksPerCall. */
+#define ULCX_FRONT_PLAN_WORDS 44
+int  ulcx_encoder_debug_front_plan(ulcx_encoder *enc, int nBlocks, int32_t *out);
 /* Test hook: how the last decode call's synthesis was launched - workgroups (0: one per stream), how many of them took one
  * whole stream each (ulcx_dec_tail_plan; 0 for an even cut, ulcx_dec_split_plan), and the workgroups of the synthesis kernel
  * the device holds at once (0: this geometry runs the general kernel, never cut). */

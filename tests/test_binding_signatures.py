@@ -50,7 +50,7 @@ PROTOS = prototypes()
 
 
 def test_the_header_and_the_table_name_the_same_functions():
-    assert len(PROTOS) == 148
+    assert len(PROTOS) == 149
     assert set(PROTOS) == set(ulc_amd.EXPORTS)
     assert len(ulc_amd.EXPORTS) == len(set(ulc_amd.EXPORTS))
     assert set(ulc_amd.SIGNATURES) == set(ulc_amd.EXPORTS)

@@ -47,6 +47,16 @@ def _impulse_pcm(B, n, bs, K, rate, seed):
     return pcm
 
 
+# (BlockSize, B, K): (switched blocks over all streams, their WindowCtrl codes) of _impulse_pcm under the oracle
+IMPULSE_CODES = {
+    (256, 3, 2): (3, [0x49]), (256, 3, 3): (3, [0x49]), (256, 3, 5): (3, [0x49]),
+    (256, 9, 2): (12, [0x49]), (256, 9, 3): (12, [0x49]), (256, 9, 5): (15, [0x49, 0x59, 0x69]),
+    (2048, 3, 2): (6, [0x8B, 0xC9, 0xCA, 0xCB]), (2048, 3, 3): (8, [0x89, 0x8B, 0xC9, 0xCA, 0xCB]), (2048, 3, 5): (8, [0x89, 0x8B, 0xC9, 0xCB]),
+    (2048, 9, 2): (18, [0x8B, 0xC9, 0xCA, 0xCB, 0xD9, 0xDB]), (2048, 9, 3): (21, [0x89, 0x8B, 0xC9, 0xCA, 0xCB, 0xDA, 0xDB]),
+    (2048, 9, 5): (22, [0x89, 0x8B, 0xC9, 0xCB, 0xD9]),
+}
+
+
 @pytest.mark.parametrize("K", [2, 3, 5])
 @pytest.mark.parametrize("B", [3, 9])
 @pytest.mark.parametrize("bs", [256, 2048])
@@ -57,7 +67,8 @@ def test_envelope_lane_exchange_matches_the_oracle(bs, B, K):
     rate = 44100
     pcm = _impulse_pcm(B, 2 * K * bs, bs, K, rate, seed=77 + K)
     refs = _encode_calls(pcm, bs, rate, K, 2, taps=False, what=f"wc_ef bs={bs} B={B} K={K}")
-    assert any((r["wc"] != 0x10).any() for r in refs), "the impulses should switch windows somewhere"
+    switched = [int(c) for r in refs for c in r["wc"] if c != 0x10]
+    assert (len(switched), sorted(set(switched))) == IMPULSE_CODES[bs, B, K], "the windows the impulses switch (the oracle's, which the calls above were held against)"
 
 
 # ---------------------------------------------------------------------------

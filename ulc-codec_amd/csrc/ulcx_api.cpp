@@ -1265,6 +1265,22 @@ extern "C" int ulcx_encoder_debug_plan(ulcx_encoder *e, int32_t plan[7]) {
     plan[6] = (cb / 64 == 128 && c.C == 2 && c.selPair) ? 1 : 0;
     return ULCX_OK;
 }
+// Test hook: where launch_front (ulcx_enc.hip) would cut a call of nBlocks - enc_aux's chunk count through ulcx_front_plan, the
+// function the launch itself calls.
+static_assert(ULCX_FRONT_PLAN_WORDS == 2 + (ULCX_XF_MAXCH + 1) + (ULCX_WC_MAXCH + 1), "include/ulc_amd.h: the words the hook may write");
+extern "C" int ulcx_encoder_debug_front_plan(ulcx_encoder *e, int nBlocks, int32_t *out) {
+    const char *who = "ulcx_encoder_debug_front_plan";
+    if (!e || !out) return refuse(who, "no encoder, or no array");
+    if (nBlocks < 1 || nBlocks > e->maxK) return refuse(who, "nBlocks out of range");
+    const UlcxEncAux aux = enc_aux(e, nBlocks);
+    const UlcxFrontPlan fp = ulcx_front_plan(nBlocks, aux.wcPipe, aux.wcSteps);
+    int n = 0;
+    out[n++] = fp.nCh; out[n++] = fp.nW;
+    for (int j = 0; j <= fp.nCh; j++) out[n++] = fp.cut[j];
+    for (int w = 0; w <= fp.nW; w++) out[n++] = fp.wcs[w];
+    while (n < ULCX_FRONT_PLAN_WORDS) out[n++] = -1;
+    return ULCX_OK;
+}
 extern "C" const char *ulcx_encoder_stage_name(int i) { return (i >= 0 && i < ULCX_ENC_STAGES_REPORTED) ? ulcx_enc_stage_names[i] : ""; }
 extern "C" int ulcx_encoder_stage_ms(ulcx_encoder *e, float *ms, int maxStages) {
     if (!e || !e->evRecorded) return 0;

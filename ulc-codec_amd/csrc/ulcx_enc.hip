@@ -155,23 +155,10 @@ static int launch_front(const UlcxEncCtx &c, hipStream_t st, StageMarks &mk, con
     // side: envelope + forward recurrence of step w (the sample-rate chain, back to back over the steps);
     // side2: backward_w behind forward_w;  side3: integrate_w, decide_w behind backward_w;
     // main: transform chunk j behind the step that decides its last block.  The first chunk is a single block so the transform starts early.
-    // The window-control kernels advance in uniform steps of a few blocks (ULCX_WC_STEPS; 0 = in the same chunks as
-    // the transform: first chunk one block, then thirds).  Measured with the chunked transform: 4 steps 8.65-8.70 ms
-    // per step of 65536 blocks, 8 steps 8.73-8.81, 16 steps 8.9-9.0 (every launch of a chain kernel costs its fixed
-    // latency, and a step that has to be dispatched beside a transform chunk waits for its workgroup slots).
-    int nW = aux.wcSteps;
-    if (nW < 0) nW = (c.K >= 8) ? 4 : 0;                               // default: 4 uniform steps (of >= 2 blocks)
-    if (nW > ULCX_WC_MAXCH) nW = ULCX_WC_MAXCH;
-    if (nW > c.K) nW = c.K;
-    const bool sameCuts = nW < 1;
-    if (sameCuts) nW = nCh;
-    int cut[ULCX_XF_MAXCH + 1];
-    // (transform chunks cut where the window-control steps end - eight blocks behind the first step instead of one - :
-    //  the transform's interval +0.37 ms, the exposed window control -0.37 ms, the phase the same 4.0 ms)
-    cut[0] = 0; cut[1] = 1;
-    for (int j = 2; j <= nCh; j++) cut[j] = 1 + (c.K - 1) * (j - 1) / (nCh - 1);
-    int wcs[ULCX_WC_MAXCH + 1];
-    for (int w = 0; w <= nW; w++) wcs[w] = sameCuts ? cut[w] : (int)((long long)c.K * w / nW);
+    // The steps and the cuts: ulcx_front_plan (ulcx_internal.h), which ulcx_encoder_debug_front_plan reports too.
+    const UlcxFrontPlan fp = ulcx_front_plan(c.K, nCh, aux.wcSteps);
+    const int nW = fp.nW;
+    const int *cut = fp.cut, *wcs = fp.wcs;
     CK(hipEventRecord(sy.wcStart, st));
     CK(hipStreamWaitEvent(side, sy.wcStart, 0));
     int jx = 0;                                        // next transform chunk to enqueue

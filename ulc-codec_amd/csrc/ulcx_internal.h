@@ -207,6 +207,32 @@ struct UlcxEncAux {                      // what a call's launch needs beside it
     int wcSteps, wcFuse, nsSlots;        // fine window-control steps per call (ULCX_WC_STEPS); stereo: k_wc_ef; resident workgroups of k_nsums (its persistent grid)
     int &nXf;                            // out: transform launches of a pipelined call (0: one launch, no xfTiming pairs)
 };
+// Where a call of K blocks is cut: nCh transform chunks [cut[j], cut[j + 1]) beside nW window-control steps [wcs[w], wcs[w + 1]).
+// nCh <= 1: the plain launch, one range of each (nW = 1).  Host arithmetic only; launch_front (ulcx_enc.hip) launches by it and
+// ulcx_encoder_debug_front_plan (ulcx_api.cpp) reports it.
+struct UlcxFrontPlan { int nCh, nW; int cut[ULCX_XF_MAXCH + 1]; int wcs[ULCX_WC_MAXCH + 1]; };
+static inline UlcxFrontPlan ulcx_front_plan(int K, int wcPipe, int wcSteps) {
+    UlcxFrontPlan p;
+    p.nCh = wcPipe;
+    if (p.nCh <= 1) { p.nCh = 1; p.nW = 1; p.cut[0] = p.wcs[0] = 0; p.cut[1] = p.wcs[1] = K; return p; }
+    // The window-control kernels advance in uniform steps of a few blocks (ULCX_WC_STEPS; 0 = in the same chunks as
+    // the transform: first chunk one block, then thirds).  Measured with the chunked transform: 4 steps 8.65-8.70 ms
+    // per step of 65536 blocks, 8 steps 8.73-8.81, 16 steps 8.9-9.0 (every launch of a chain kernel costs its fixed
+    // latency, and a step that has to be dispatched beside a transform chunk waits for its workgroup slots).
+    int nW = wcSteps;
+    if (nW < 0) nW = (K >= 8) ? 4 : 0;                                 // default: 4 uniform steps (of >= 2 blocks)
+    if (nW > ULCX_WC_MAXCH) nW = ULCX_WC_MAXCH;
+    if (nW > K) nW = K;
+    const bool sameCuts = nW < 1;
+    if (sameCuts) nW = p.nCh;
+    // (transform chunks cut where the window-control steps end - eight blocks behind the first step instead of one - :
+    //  the transform's interval +0.37 ms, the exposed window control -0.37 ms, the phase the same 4.0 ms)
+    p.cut[0] = 0; p.cut[1] = 1;
+    for (int j = 2; j <= p.nCh; j++) p.cut[j] = 1 + (K - 1) * (j - 1) / (p.nCh - 1);
+    for (int w = 0; w <= nW; w++) p.wcs[w] = sameCuts ? p.cut[w] : (int)((long long)K * w / nW);
+    p.nW = nW;
+    return p;
+}
 int ulcx_enc_launch(const UlcxEncCtx &c, hipStream_t st, hipEvent_t *ev /* ULCX_ENC_STAGES+1 or NULL */, const UlcxEncAux &aux);
 // ulcx_encode_*_ladder: one context per rung (rung 0's carries wcOut / cplxOut); k_rung_arm arms rungs >= 1 (ulcx_enc_ladder.hip)
 int ulcx_enc_launch_ladder(const UlcxEncCtx *rungs, int nRungs, hipStream_t st, hipEvent_t *ev, const UlcxEncAux &aux);

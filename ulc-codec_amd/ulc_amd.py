@@ -16,6 +16,7 @@ _u8p = C.POINTER(C.c_uint8)
 _i64p = C.POINTER(C.c_int64)
 
 N_BARK, MAX_SUB, BARK_EVENTS = 25, 4, 52
+FRONT_PLAN_WORDS = 44            # include/ulc_amd.h: ULCX_FRONT_PLAN_WORDS
 PLAN_FIELDS = ("bark_ring", "most_open", "use_gap_sums", "heap_in_lds", "ns_slots", "wc_pipe", "sel_pair")
 
 MAX_RUNGS = 8                                              # ULCX_MAX_RUNGS
@@ -107,7 +108,7 @@ _sig("ulcx_encoder_stream_state_bytes ulcx_decoder_stream_state_bytes", [_vp], C
 _sig("ulcx_encoder_set_timing ulcx_decoder_set_timing ulcx_encoder_debug_force_exact", [_vp, _int])
 _sig("ulcx_encoder_stage_ms ulcx_decoder_stage_ms", [_vp, _f32p, _int])
 _sig("ulcx_encoder_debug_fetch", [_vp, _int, _f32p, _f32p, _f32p, _u8p, _i32p])
-_sig("ulcx_encoder_debug_writer_flags", [_vp, _int, _i32p])
+_sig("ulcx_encoder_debug_writer_flags ulcx_encoder_debug_front_plan", [_vp, _int, _i32p])
 _sig("ulcx_encoder_debug_writer_plan ulcx_encoder_debug_plan", [_vp, _i32p])
 _sig("ulcx_decoder_last_cut", [_vp, _i32p, _i32p, _i32p])
 # host arithmetic (no handle)
@@ -721,6 +722,14 @@ class BatchEncoder(_StreamSlots):
         p = np.zeros(len(PLAN_FIELDS), np.int32)
         _call("ulcx_encoder_debug_plan", self.h, _p(p, _i32p))
         return {k: int(v) for k, v in zip(PLAN_FIELDS, p)}
+
+    def front_plan(self, n_blocks):
+        """How the front half of a call of n_blocks would be cut on this object: (transform cuts, window-control step
+        boundaries), each a tuple that runs from 0 to n_blocks.  Test hook."""
+        p = np.zeros(FRONT_PLAN_WORDS, np.int32)
+        _call("ulcx_encoder_debug_front_plan", self.h, int(n_blocks), _p(p, _i32p))
+        n_ch, n_w = int(p[0]), int(p[1])
+        return tuple(int(v) for v in p[2:3 + n_ch]), tuple(int(v) for v in p[3 + n_ch:4 + n_ch + n_w])
 
     def force_exact(self, every):
         _call("ulcx_encoder_debug_force_exact", self.h, int(every))
