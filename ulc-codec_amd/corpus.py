@@ -562,18 +562,30 @@ class CropCorpus:
             segments.append(row)
         return self.splice(dec, segments)[0]
 
-    def sample_crops(self, dec, files, start, n_samples, length=None, pcm16=False):
+    def sample_crops(self, dec, files, start, n_samples, length=None, pcm16=False, lowrate=0):
         """Row i: n_samples samples from sample start[i] of the decoded stream of file files[i] (its leading length[i] when
         `length` is given; zeros behind, and behind the file's end), written channels-first by the synthesis itself
         (ulcx_decode_crops_samples_dev): no gather, no transpose.  start: int64; files / length: int32; tensors on the corpus's
         device, or anything torch.as_tensor takes.  Positions are of the decoded stream: the codec's delay is not compensated.
         -> (pcm [n][nChan][n_samples] float32, or int16 with pcm16; bits int32 [n][crop_blocks]) on the device, enqueued on
         torch's current stream.  `dec`: a BatchDecoder of this geometry with n_streams >= n and max_blocks > crop_blocks =
-        ulc_amd.crop_blocks(BlockSize, n_samples); no stream state of it is read or changed."""
+        ulc_amd.crop_blocks(BlockSize, n_samples); no stream state of it is read or changed.
+        lowrate = 1, 2, 3: the crop at 1/2, 1/4, 1/8 of the file's rate straight from the synthesis (ulcx_decode_crops_lowrate_dev):
+        start, length and n_samples count samples of the reduced stream - blocks of BlockSize >> lowrate, reduced sample m at
+        full-rate time D m + (D - 1) / 2 with D = 1 << lowrate - and crop_blocks is that of the reduced BlockSize.  0: the
+        full-rate call, untouched."""
         import torch
         sfx, corpus = self._ready(dec)._view()
         n, files, start, want = self._rows(files, start, length, pos_dtype=torch.int64)
         pcm = torch.empty((n, self.C, n_samples), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
+        if lowrate:
+            bs = ulc_amd.lowrate_block(self.BS, lowrate)
+            if not bs:
+                raise ValueError(f"lowrate {lowrate}: 0 .. 3 with BlockSize {self.BS} >> lowrate >= 256")
+            bits = torch.empty((n, ulc_amd.crop_blocks(bs, n_samples)), dtype=torch.int32, device=self.device)
+            getattr(dec, f"decode_crops_lowrate{sfx}_dev")(*corpus, n, files.data_ptr(), start.data_ptr(), _ptr(want), n_samples, int(lowrate), pcm.data_ptr(),
+                                                           bits.data_ptr(), stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
+            return pcm, bits
         bits = torch.empty((n, ulc_amd.crop_blocks(self.BS, n_samples)), dtype=torch.int32, device=self.device)
         getattr(dec, f"decode_crops_samples{sfx}_dev")(*corpus, n, files.data_ptr(), start.data_ptr(), _ptr(want), n_samples, pcm.data_ptr(), bits.data_ptr(),
                                                        stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)

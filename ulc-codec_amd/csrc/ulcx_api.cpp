@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "ulcx_internal.h"
+#include "../../include/ulc_amd_lowrate.h"
 #include "ulcx_enc_dev.h"                 // (WaveCaps, WAVE_S*, wavecaps_lds: ulcx_encoder_debug_writer_plan)
 #include "ulcx_rng_tables.h"
 
@@ -94,6 +95,14 @@ struct ulcx_encoder {
     // clip spectra (ulcx_analyse_clips_* / ulcx_encode_clips_spectra_*): the chunk's [B][maxK] window codes and complexities (allocated on the first such call)
     int32_t *clipWc = nullptr; float *clipCplx = nullptr;
 };
+// What a low-rate call (ulcx_decode_crops_lowrate_*) keeps per ratio, built by the first call at that ratio (dec_low): the tables of
+// BlockSize >> lgD, the synthesis kernel that geometry picks, its residency and the lapping scratch a cut of it works in.
+struct UlcxDecLow {
+    bool ready = false;
+    void *tables = nullptr; UlcxTables T = {};
+    int fastOK = 0, twInLds = 0, synSlots = 0, scratchRows = 0;
+    float *lapScratch = nullptr;
+};
 struct ulcx_decoder {
     int device = 0, B = 0, C = 0, BS = 0, maxK = 0;
     UlcxDecCtx ctx = {};
@@ -122,6 +131,7 @@ struct ulcx_decoder {
     // synthesis leaves its result, as lap2 .. dead2 are for the object's own arrays) and the device copy of a host form's list
     float *subLap[2] = {}; int *subLastSub[2] = {}; uint32_t *subSeed[2] = {}; int *subDead[2] = {}; int *subPackOff = nullptr;
     int32_t *subSlots = nullptr;
+    UlcxDecLow low[4];                                            // [lgD] (entry 0 is never used: lgD 0 is the sample-crop call)
     int32_t *sampRows = nullptr;                                  // [4][B] a sample-crop call's rows as k_crop_sample_rows leaves them: first, count, skip, len (allocated with the shadow state)
 };
 
@@ -1314,6 +1324,7 @@ static void cleanup(ulcx_decoder *e) {
     if (!e) return;
     for (void *p : e->allocs) hipFree(p);
     if (e->tables) hipFree(e->tables);
+    for (auto &l : e->low) if (l.tables) hipFree(l.tables);
     if (e->evOk) for (auto &v : e->ev) hipEventDestroy(v);
     block1_drop(e->b1);
     if (e->b1.stream) hipStreamDestroy(e->b1.stream);
@@ -1405,25 +1416,32 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subse
     a.synGrid = 0; a.synFull = 0;
     c.lapO = c.lap; c.lastSubO = c.lastSub; c.seedO = c.seed; c.deadO = c.dead;
     const int Kc = c.range ? c.K - 1 : c.K;                       // blocks of the call per stream (a range call's K counts the row of the block in front)
-    if (e->splitOK && e->synSlots > 0 && !a.specCoef && !a.distOut) {      // (a spectra or distortion call has no synthesis to cut: the plain plan)
+    // (a low-rate call: the cut is planned for the kernel of the reduced geometry - its residency, its scratch rows)
+    const bool low = a.lowLgD > 0;
+    const int synSlots = low ? e->low[a.lowLgD].synSlots : e->synSlots, scratchRows = low ? e->low[a.lowLgD].scratchRows : e->scratchRows;
+    if ((low || e->splitOK) && synSlots > 0 && !a.specCoef && !a.distOut) {      // (a spectra or distortion call has no synthesis to cut: the plain plan)
         // A range call of more streams than the device holds at once: whole rounds, and the last one cut
         // (ulcx_dec_range_tail_plan) - an even cut of everything ends every workgroup inside a stream, and in a range call every
         // entry into a stream costs the block in front of the range (ULCX_RANGE_CUT=even: the even cut first, as for other calls)
-        if (c.range && c.B > e->synSlots && e->tailCut && !e->rangeEvenFirst) {
+        if (c.range && c.B > synSlots && e->tailCut && !e->rangeEvenFirst) {
             int full = 0;
-            const int tail = ulcx_dec_range_tail_plan(c.B, Kc, e->synSlots, &full);
-            if (tail > 0 && tail <= e->scratchRows) { a.synGrid = full + tail; a.synFull = full; }
+            const int tail = ulcx_dec_range_tail_plan(c.B, Kc, synSlots, &full);
+            if (tail > 0 && tail <= scratchRows) { a.synGrid = full + tail; a.synFull = full; }
         }
-        if (!a.synGrid) a.synGrid = ulcx_dec_split_plan(c.B, Kc, e->synSlots);
+        if (!a.synGrid) a.synGrid = ulcx_dec_split_plan(c.B, Kc, synSlots);
         if (!a.synGrid) {
             int full = 0;
-            const int tail = c.range ? ulcx_dec_range_tail_plan(c.B, Kc, e->synSlots, &full) : ulcx_dec_tail_plan(c.B, Kc, e->synSlots, &full);
-            if (tail > 0 && tail <= e->scratchRows && e->tailCut) { a.synGrid = full + tail; a.synFull = full; }
+            const int tail = c.range ? ulcx_dec_range_tail_plan(c.B, Kc, synSlots, &full) : ulcx_dec_tail_plan(c.B, Kc, synSlots, &full);
+            if (tail > 0 && tail <= scratchRows && e->tailCut) { a.synGrid = full + tail; a.synFull = full; }
         }
         if (a.synGrid) {
-            if (getenv("ULCX_DEBUG_PRINT")) fprintf(stderr, "[ulcx] synthesis: %lld (stream, block) pairs over %d workgroups (%d of them one stream each; %d resident)\n", (long long)c.B * Kc, a.synGrid, a.synFull, e->synSlots);
-            if (subsetSet) { c.lapO = e->subLap[1]; c.lastSubO = e->subLastSub[1]; c.seedO = e->subSeed[1]; c.deadO = e->subDead[1]; }
-            else { c.lapO = e->lap2; c.lastSubO = e->lastSub2; c.seedO = e->seed2; c.deadO = e->dead2; }
+            if (getenv("ULCX_DEBUG_PRINT")) fprintf(stderr, "[ulcx] synthesis: %lld (stream, block) pairs over %d workgroups (%d of them one stream each; %d resident)\n", (long long)c.B * Kc, a.synGrid, a.synFull, synSlots);
+            // (a range synthesis reads no state in front of the launch: a low-rate call leaves its rows' state in the set it names,
+            //  so a file geometry without a second set - a non-fast one that feeds the stereo kernel - can be cut too)
+            if (!low) {
+                if (subsetSet) { c.lapO = e->subLap[1]; c.lastSubO = e->subLastSub[1]; c.seedO = e->subSeed[1]; c.deadO = e->subDead[1]; }
+                else { c.lapO = e->lap2; c.lastSubO = e->lastSub2; c.seedO = e->seed2; c.deadO = e->dead2; }
+            }
         }
     }
     e->lastGrid = a.synGrid; e->lastFull = a.synFull;
@@ -2005,6 +2023,42 @@ static int corpus_up(DevTmp &t, const UlcxCorpus &h, UlcxCorpus *d) {
     return ULCX_OK;
 }
 
+// ---- low-rate crops (include/ulc_amd_lowrate.h): what the synthesis of BlockSize >> lgD needs beside the object's own arrays, built
+// by the first call at that ratio and kept - nothing is allocated by a later one
+extern "C" int ulcx_lowrate_block(int BlockSize, int lgD) {
+    if (lgD < 0 || lgD > 3 || !validate(1, BlockSize)) return 0;
+    return validate(1, BlockSize >> lgD) ? BlockSize >> lgD : 0;
+}
+static int dec_low(ulcx_decoder *e, int lgD) {
+    UlcxDecLow &l = e->low[lgD];
+    if (l.ready) return ULCX_OK;
+    const int BSr = e->BS >> lgD;
+    int rc;
+    if (!l.tables && (rc = ulcx_tables_build(&l.T, &l.tables, BSr, 44100, false))) return rc;
+    // the kernel pick of the REDUCED geometry (ulcx_decoder_create's rule): stereo up to BlockSize 4096 takes k_dsyn
+    l.fastOK = (e->C == 2 && BSr <= 4096) ? 1 : 0;
+    if (const char *ev = getenv("ULCX_DEC_FAST")) l.fastOK = l.fastOK && (ev[0] != '0');
+    l.twInLds = (l.fastOK && BSr <= 2048 && ULCX_DSYN_TWL) ? 1 : 0;
+    if (l.fastOK) {
+        bool want = true;
+        if (const char *ev = getenv("ULCX_DSYN_SPLIT")) want = ev[0] != '0';
+        UlcxDecCtx cs = e->ctx;
+        cs.BS = BSr; cs.lgBS = ilog2i(BSr); cs.T = l.T; cs.fastOK = l.fastOK; cs.twInLds = l.twInLds;
+        l.synSlots = want ? ulcx_dec_syn_slots(cs, e->BS) : 0;
+        if (l.synSlots > 0 && !l.lapScratch) {
+            l.scratchRows = 4 * l.synSlots;
+            if ((rc = dalloc(e->allocs, &l.lapScratch, (size_t)l.scratchRows * e->C * (BSr / 2), true))) return rc;
+        }
+    }
+    l.ready = true;
+    return ULCX_OK;
+}
+// lgD of a low-rate entry: refused outside 0 .. 3, or where the object's BlockSize >> lgD is no BlockSize
+static int lowrate_bad(const char *who, const ulcx_decoder *e, int lgD) {
+    if (lgD < 0 || lgD > 3) { refuse(who, "bad argument (lgD %d: 0 .. 3)", lgD); return 1; }
+    if (e && !ulcx_lowrate_block(e->BS, lgD)) { refuse(who, "bad argument (lgD %d: BlockSize %d >> %d is below 256)", lgD, e->BS, lgD); return 1; }
+    return 0;
+}
 // ---- crops (include/ulc_amd.h section 3): rows of a call that each name a file of a corpus.  The range synthesis enters every
 // row from nothing, so the call needs no stream's state; what the synthesis leaves behind a row goes to the subset calls'
 // shadow state (dec_shadow) and is never scattered back.
@@ -2022,7 +2076,8 @@ static int crops_checks(const char *who, const ulcx_decoder *e, const UlcxCorpus
     return 0;
 }
 // the rows of a sample-crop call (ulcx_decode_crops_samples_*): d_first / d_count are not given, nBlocks is ulcx_crop_blocks(nSamples)
-struct CropsSamples { const int64_t *start; const int32_t *len; int nSamples; };
+// (lgD > 0: a low-rate call, ulcx_decode_crops_lowrate_* - the rows count samples of the stream reduced by 1 << lgD)
+struct CropsSamples { const int64_t *start; const int32_t *len; int nSamples; int lgD; };
 // the outputs of a spectra call (ulcx_decode_crops_spectra_*) beside d_bits: coefficients instead of samples, and the window codes
 struct CropsSpectra { float *coef; int32_t *wc; int flags; };
 static int spectra_flags_bad(const char *who, int flags) {
@@ -2065,6 +2120,7 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &
              : (misaligned(who, "d_pcm", d_pcm, ULCX_ALIGN_PCM) || misaligned(who, "d_pcm16", d_pcm16, ULCX_ALIGN_PCM16))) return ULCX_ERR_ARG;
     CKR(hipSetDevice(e->device));
     int rc = dec_shadow(e);
+    if (!rc && samp && samp->lgD > 0) rc = dec_low(e, samp->lgD);
     if (rc) return rc;
     UlcxDecCtx c = e->ctx;
     c.B = n; c.K = nBlocks + 1; c.slot = 0; c.in = g.pay; c.inBytes = g.payTotal; c.pcm = d_pcm; c.pcm16 = d_pcm16;
@@ -2077,6 +2133,10 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &
         crop.sampStart = samp->start; crop.sampLen = samp->len; crop.nSamples = samp->nSamples;
         crop.sampFirst = e->sampRows; crop.sampCount = e->sampRows + e->B; crop.sampSkip = e->sampRows + 2 * (size_t)e->B; crop.sampLenC = e->sampRows + 3 * (size_t)e->B;
         c.rFirst = crop.sampFirst; crop.cropCount = crop.sampCount;
+        if (samp->lgD > 0) {
+            const UlcxDecLow &l = e->low[samp->lgD];
+            crop.lowLgD = samp->lgD; crop.lowT = l.T; crop.lowFast = l.fastOK; crop.lowTwInLds = l.twInLds; crop.lowLapScratch = l.lapScratch;
+        }
     }
     if (spec) { crop.specCoef = spec->coef; crop.specWc = spec->wc; crop.specLR = (spec->flags & ULCX_SPECTRA_LR) ? 1 : 0; }
     if (dist) {
@@ -2317,18 +2377,20 @@ extern "C" int ulcx_crop_blocks(int BlockSize, int nSamples) {
 // nSamples of a sample-crop entry -> the blocks per row the crop body is called with (checked there against maxBlocksPerCall - 1);
 // 0: refused here.  Without an object the count is 1: the body then refuses the call for the object's absence, or for what it
 // checks before that.
-static int samples_blocks(const char *who, const ulcx_decoder *e, int nSamples) {
+// (lgD: a low-rate entry - the blocks are those of BlockSize >> lgD)
+static int samples_blocks(const char *who, const ulcx_decoder *e, int nSamples, int lgD = 0) {
     if (nSamples < 1) { refuse(who, "bad argument (nSamples %d)", nSamples); return 0; }
     if (!e) return 1;
-    const int nB = ulcx_crop_blocks(e->BS, nSamples);
+    const int nB = ulcx_crop_blocks(e->BS >> lgD, nSamples);
     if (nB > e->maxK - 1) { refuse(who, "bad argument (nSamples %d touches up to %d blocks; a row has maxBlocksPerCall - 1 = %d)", nSamples, nB, e->maxK - 1); return 0; }
     return nB;
 }
 static int crops_samples_dev_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len,
-                                 int nSamples, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
-    const int nB = samples_blocks(who, e, nSamples);
+                                 int nSamples, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, int lgD = 0) {
+    if (lowrate_bad(who, e, lgD)) return ULCX_ERR_ARG;
+    const int nB = samples_blocks(who, e, nSamples, lgD);
     if (!nB) return ULCX_ERR_ARG;
-    const CropsSamples sm = { d_start, d_len, nSamples };
+    const CropsSamples sm = { d_start, d_len, nSamples, lgD };
     return decode_crops_any(who, e, g, n, d_file, nullptr, nullptr, nB, d_pcm, d_pcm16, d_bits, hipStream, &sm);
 }
 extern "C" int ulcx_decode_crops_samples_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
@@ -2383,22 +2445,23 @@ static int sample_results_down(const ulcx_decoder *e, const SampleStage &g, int 
 }
 // the host forms, either layout
 static int crops_samples_host_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len,
-                                  int nSamples, float *h_pcm, int32_t *h_bits) {
-    const int nB = samples_blocks(who, e, nSamples);
+                                  int nSamples, float *h_pcm, int32_t *h_bits, int lgD = 0) {
+    if (lowrate_bad(who, e, lgD)) return ULCX_ERR_ARG;
+    const int nB = samples_blocks(who, e, nSamples, lgD);
     if (!nB) return ULCX_ERR_ARG;
     if (crops_checks(who, e, g, !h_file || !h_start || !h_pcm || !h_bits, n, nB)) return ULCX_ERR_ARG;
     if (g.ragged && ragged_tables_bad(who, g)) return ULCX_ERR_ARG;
     for (int i = 0; i < n; i++) {
         long long nI;
         if (host_row_file(who, g, i, h_file[i], &nI)) return ULCX_ERR_ARG;
-        if (sample_row_bad(who, i, e->BS, nI < 0 ? 0 : nI, h_start[i], h_len)) return ULCX_ERR_ARG;
+        if (sample_row_bad(who, i, e->BS >> lgD, nI < 0 ? 0 : nI, h_start[i], h_len)) return ULCX_ERR_ARG;
     }
     CKR(hipSetDevice(e->device));
     DevTmp t; UlcxCorpus d; SampleStage sg;
     int rc = corpus_up(t, g, &d);
     if (!rc) rc = sample_rows_up(t, e, n, nB, nSamples, h_file, h_start, h_len, &sg);
     if (rc) return rc;
-    const CropsSamples sm = { sg.start, sg.len, nSamples };
+    const CropsSamples sm = { sg.start, sg.len, nSamples, lgD };
     rc = decode_crops_any(who, e, d, n, sg.file, nullptr, nullptr, nB, sg.pcm, nullptr, sg.bits, nullptr, &sm);
     return rc ? rc : sample_results_down(e, sg, n, nB, nSamples, h_pcm, h_bits);
 }
@@ -2415,6 +2478,49 @@ extern "C" int ulcx_decode_crops_samples_ragged_host(ulcx_decoder *e, int nFiles
                                                      float *h_pcm, int32_t *h_bits) {
     return crops_samples_host_any("ulcx_decode_crops_samples_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
                                   n, h_file, h_start, h_len, nSamples, h_pcm, h_bits);
+}
+// ---- low-rate sample crops (include/ulc_amd_lowrate.h): the sample-crop bodies with one further argument
+extern "C" int ulcx_decode_crops_lowrate_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                             const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                             int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD,
+                                             float *d_pcm, int32_t *d_bits, void *hipStream) {
+    return crops_samples_dev_any("ulcx_decode_crops_lowrate_dev", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, d_pcm, nullptr, d_bits, hipStream, lgD);
+}
+extern "C" int ulcx_decode_crops_lowrate_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                                   const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                                   int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD,
+                                                   int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    return crops_samples_dev_any("ulcx_decode_crops_lowrate_dev_pcm16", e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, nullptr, d_pcm16, d_bits, hipStream, lgD);
+}
+extern "C" int ulcx_decode_crops_lowrate_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                              const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                              int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples, int lgD,
+                                              float *h_pcm, int32_t *h_bits) {
+    return crops_samples_host_any("ulcx_decode_crops_lowrate_host", e, ulcx_corpus_strided(nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks),
+                                  n, h_file, h_start, h_len, nSamples, h_pcm, h_bits, lgD);
+}
+extern "C" int ulcx_decode_crops_lowrate_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                    const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                    int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD,
+                                                    float *d_pcm, int32_t *d_bits, void *hipStream) {
+    return crops_samples_dev_any("ulcx_decode_crops_lowrate_ragged_dev", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, d_pcm, nullptr, d_bits, hipStream, lgD);
+}
+extern "C" int ulcx_decode_crops_lowrate_ragged_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                          const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                          int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD,
+                                                          int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    return crops_samples_dev_any("ulcx_decode_crops_lowrate_ragged_dev_pcm16", e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, nullptr, d_pcm16, d_bits, hipStream, lgD);
+}
+extern "C" int ulcx_decode_crops_lowrate_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                                     const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                                     int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples, int lgD,
+                                                     float *h_pcm, int32_t *h_bits) {
+    return crops_samples_host_any("ulcx_decode_crops_lowrate_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
+                                  n, h_file, h_start, h_len, nSamples, h_pcm, h_bits, lgD);
 }
 // ---- synthesis from spectra (include/ulc_amd.h section 3): the decoder's inverse transform on caller-held planes.  The range
 // synthesis of a crop call without any walk in front: the call runs on the shadow state as the crop calls do (dec_shadow; nothing

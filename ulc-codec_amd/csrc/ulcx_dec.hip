@@ -786,8 +786,11 @@ __device__ __forceinline__ uint32_t par_word(const uint32_t *__restrict__ parT, 
     const uint32_t *J = parT + lane;
     return J[(st & 255u) << 6] ^ J[(256u + ((st >> 8) & 255u)) << 6] ^ J[(512u + ((st >> 16) & 255u)) << 6] ^ J[(768u + (st >> 24)) << 6];
 }
+// LOW (the low-rate source mode, UlcxLowArg): only the pieces below coefficient `keep` are written - keep is a multiple of 32, so a
+// piece lies on one side of it -, while P still covers every draw of the unit: a kept coefficient's draw index counts them all.
+template <bool LOW = false>
 __device__ __forceinline__ void synth_noise(const UlcxDecCtx &c, const SynWave &sw, const uint2 *__restrict__ list, int nE, const uint2 ent0, uint32_t x0, uint32_t unitSeed, int unitDraws,
-                                            float tailRR, const float *tailMag) {
+                                            float tailRR, const float *tailMag, int keep = 0) {
     const int lane = sw.lane;
     uint32_t *P = sw.seedTab;                                 // the unit's whole stream: max(64, BS/32) words + a zero word
     // (ent0: round 0 of the run list, x0: the lane's word of the first pass - both fetched by the caller with the unit's first records)
@@ -811,7 +814,11 @@ __device__ __forceinline__ void synth_noise(const UlcxDecCtx &c, const SynWave &
             const uint2 ent = (e0 == 0) ? ent0 : (have ? list[e] : make_uint2(0u, 0u));
             const int pos = ent.x & 0xFFFF, isTail = (int)(ent.x >> 31);
             const int np = (int)((ent.x >> 16) & 0x7FFF) + isTail;
-            const int nseg = have ? ((pos + np - 1) >> 5) - (pos >> 5) + 1 : 0;
+            int nseg = have ? ((pos + np - 1) >> 5) - (pos >> 5) + 1 : 0;
+            if constexpr (LOW) {                                    // the run's pieces below `keep` (a run at or behind it: none)
+                const int lastC = (pos + np - 1) >> 5, keepC = (keep >> 5) - 1;
+                nseg = (have && pos < keep) ? (lastC < keepC ? lastC : keepC) - (pos >> 5) + 1 : 0;
+            }
             const uint32_t incl = wave_scan_add((uint32_t)nseg);
             const int total = __builtin_amdgcn_readlane((int)incl, 63);
             sw.pre[lane] = have ? (int)(incl - nseg) : 0x7FFFFFFF;
@@ -864,6 +871,8 @@ __device__ __forceinline__ void synth_noise(const UlcxDecCtx &c, const SynWave &
 // Dequantise one (channel, subblock) unit into A[0 .. S) (zeroed by the caller) from what the scan left: one lane per
 // plain-run record (up to seven coefficients each, ulcDecoder.c:69-73), then the noise runs (synth_noise).
 // ur = {first plain-run record, their count, first noise record, their count} of the unit.
+// LOW: S is the leading part of the unit that is kept (its reduced size); the records and the draws are the full unit's.
+template <bool LOW = false>
 __device__ __forceinline__ void synth_unit(const UlcxDecCtx &c, const SynWave &sw, int S, const uint2 *__restrict__ prec, const uint2 *__restrict__ nrec,
                                            int4 ur, uint32_t unitSeed, int unitDraws, float tailRR, const float *tailMag, int zeroFloat2 = 0) {
     const int lane = sw.lane;
@@ -903,7 +912,8 @@ __device__ __forceinline__ void synth_unit(const UlcxDecCtx &c, const SynWave &s
     }
     SSTAMP(sw, 8);
     if (ur.w > 0) {
-        synth_noise(c, sw, nrec + ur.z, ur.w, ent0, x0, unitSeed, unitDraws, tailRR, tailMag);
+        if constexpr (LOW) synth_noise<true>(c, sw, nrec + ur.z, ur.w, ent0, x0, unitSeed, unitDraws, tailRR, tailMag, S);
+        else synth_noise(c, sw, nrec + ur.z, ur.w, ent0, x0, unitSeed, unitDraws, tailRR, tailMag);
     }
     SSTAMP(sw, 10);
     WAVE_SYNC();
@@ -1085,8 +1095,8 @@ __global__ __launch_bounds__(64) void k_crop_sample_rows(int n, int BS, int nSam
 // Row k of a stream's K per-block rows is plane k - (K - nPl): nPl = K when plane 0 is the block in front (ULCX_SYNTH_WARM), else K - 1.
 template <bool LR> struct UlcxPlaneArg { const float *coef; int nPl; };
 struct UlcxPlaneNone {};
-template <typename... SA> struct SynSrc { static constexpr bool plane = false, lr = false; };
-template <bool LR_> struct SynSrc<UlcxSampArg, UlcxPlaneArg<LR_>> { static constexpr bool plane = true, lr = LR_; };
+template <typename... SA> struct SynSrc { static constexpr bool plane = false, lr = false, low = false; };
+template <bool LR_> struct SynSrc<UlcxSampArg, UlcxPlaneArg<LR_>> { static constexpr bool plane = true, lr = LR_, low = false; };
 template <bool LR> __device__ __forceinline__ const UlcxSampArg &samp_arg(const UlcxSampArg &a, const UlcxPlaneArg<LR> &) { return a; }
 __device__ __forceinline__ UlcxPlaneNone plane_arg() { return UlcxPlaneNone{}; }
 __device__ __forceinline__ UlcxPlaneNone plane_arg(const UlcxSampArg &) { return UlcxPlaneNone{}; }
@@ -1095,6 +1105,23 @@ __device__ __forceinline__ const float *plane_of(const UlcxPlaneNone &, int, int
 template <bool LR> __device__ __forceinline__ const float *plane_of(const UlcxPlaneArg<LR> &p, int row, int C, int ch, int K, int k, int BS) {
     return p.coef + (((size_t)row * C + ch) * p.nPl + (k - (K - p.nPl))) * (size_t)BS;
 }
+// Low-rate source mode (ulcx_decode_crops_lowrate_*): a third further argument in the plane source's place (k_dsyn<..., UlcxSampArg,
+// UlcxLowArg>; RANGE launches only).  The walk has run at the file's BlockSize BSw; the context this synthesis gets is that of
+// BlockSize BS = BSw >> lgD - geometry, tables, lapping rows - while the per-block rows, the records and their strides are still
+// the walk's.  A unit of S coefficients is dequantised up to its leading S >> lgD (synth_unit<true>: the records and the draws
+// are the full unit's) and everything behind that is the one shared text at BS: the reference decoder of BlockSize BS whose
+// TransformBuffer holds the low bins.  The per-wave lists (the sign-parity stream covers the FULL unit's draws) are sized by BSw.
+struct UlcxLowArg { int BSw; };
+struct UlcxLowNone {};
+template <> struct SynSrc<UlcxSampArg, UlcxLowArg> { static constexpr bool plane = false, lr = false, low = true; };
+__device__ __forceinline__ const UlcxSampArg &samp_arg(const UlcxSampArg &a, const UlcxLowArg &) { return a; }
+__device__ __forceinline__ UlcxPlaneNone plane_arg(const UlcxSampArg &, const UlcxLowArg &) { return UlcxPlaneNone{}; }
+template <typename... SA> __device__ __forceinline__ UlcxLowNone low_arg(const SA &...) { return UlcxLowNone{}; }
+__device__ __forceinline__ const UlcxLowArg &low_arg(const UlcxSampArg &, const UlcxLowArg &l) { return l; }
+// words of a wave's sign-parity stream: by the BlockSize of the walk
+#define DSYN_PWORDS(BS) (((BS) / 32 > 64 ? (BS) / 32 : 64) + 2)
+__device__ __forceinline__ int low_pwords(const UlcxLowNone &, int BS) { return DSYN_PWORDS(BS); }
+__device__ __forceinline__ int low_pwords(const UlcxLowArg &l, int) { return DSYN_PWORDS(l.BSw); }
 // S coefficients at src (16-byte aligned, read once) into the padded array A; thread t0 of `step`.  DPS 4: four floats at a
 // multiple of four never straddle a padding gap (spec_ld4).  The padding itself is never read by the transform.
 __device__ __forceinline__ void plane_unit(float *A, const float *__restrict__ src, int S, int t0, int step) {
@@ -1126,16 +1153,16 @@ __global__ __launch_bounds__(64) void k_synth_rows(int n, int K, int nPl, const 
 
 // LDS carve, in floats.  Stereo kernel (k_dsyn):  z [2 padded arrays of BS/2 complex] | twl [BS/4 complex] |
 //   per wave: noise runs, prefix counts, seed table | 128 block / unit seeds.  General kernel (k_dgen): z [1 array] | per-wave lists.
-#define DSYN_PWORDS(BS) (((BS) / 32 > 64 ? (BS) / 32 : 64) + 2)
 #define DSYN_CHUNK 32            // blocks of a stream whose RNG states and headers the stereo kernel stages at once (<= 64)
 struct DsynLds { int zFloats, twFloats, listFloats; };
 // twInLds: the stereo kernel's FFT twiddles resident in LDS (BlockSize <= 2048; above it they are read from the tables in
 // global memory, L1/L2-hot: a fourth workgroup per CU).  The lapping state is in global memory for every geometry.
-__host__ __device__ static inline DsynLds dsyn_lds(int BS, int fast, int twInLds) {
+// listBS: the BlockSize the per-wave lists are sized by (the low-rate source mode: the walk's; 0: BS)
+__host__ __device__ static inline DsynLds dsyn_lds(int BS, int fast, int twInLds, int listBS = 0) {
     DsynLds l;
     l.zFloats = (fast ? 2 : 1) * 2 * FFT_PADDEDS(BS / 2, DPS);
     l.twFloats = (fast && BS <= 2048 && twInLds) ? BS / 2 : 0;
-    l.listFloats = 2 * (64 + DSYN_PWORDS(BS)) + 128;             // per wave: prefix counts, sign-parity stream; per workgroup: 128 block / channel RNG states
+    l.listFloats = 2 * (64 + DSYN_PWORDS(listBS ? listBS : BS)) + 128;             // per wave: prefix counts, sign-parity stream; per workgroup: 128 block / channel RNG states
     if (fast) l.listFloats += 2 * (DSYN_CHUNK + 4) * 8;          // stereo kernel: the headers of a chunk of blocks + of a decimated block's four units, per channel
     return l;
 }
@@ -1161,8 +1188,10 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
     const auto &samp = samp_arg(sa...);
     constexpr bool PLANE = SynSrc<SA...>::plane, LR = SynSrc<SA...>::lr;      // the plane source mode (UlcxPlaneArg): no records, no generator
     const auto &pla = plane_arg(sa...);
+    constexpr bool LOW = SynSrc<SA...>::low;                         // the low-rate source mode (UlcxLowArg): the records clipped to the reduced units
     extern __shared__ float lds[];
     const int BS = BSC ? BSC : c.BS, H2 = BS / 2;
+    const int PW = low_pwords(low_arg(sa...), BS);
     constexpr int C = 2;
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -1177,9 +1206,9 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
     float  *scr = ownStream ? c.lapO + (size_t)(c.s0 + blockIdx.x) * C * H2 : c.lapScratch + (size_t)((int)blockIdx.x - c.synFull) * C * H2;
     float2 *twl  = (float2 *)(lds + L.zFloats);        // FFT twiddles: the full-size table, or the three of a decimated block's sizes
     SynWave sw;
-    sw.pre  = (int *)(lds + L.zFloats + L.twFloats) + wv * (64 + DSYN_PWORDS(BS));
+    sw.pre  = (int *)(lds + L.zFloats + L.twFloats) + wv * (64 + PW);
     sw.seedTab = (uint32_t *)(sw.pre + 64);
-    uint32_t *bseed = (uint32_t *)(lds + L.zFloats + L.twFloats + 2 * (64 + DSYN_PWORDS(BS)));   // [0,64): RNG state at each block's start, [64,128): at its second channel
+    uint32_t *bseed = (uint32_t *)(lds + L.zFloats + L.twFloats + 2 * (64 + PW));   // [0,64): RNG state at each block's start, [64,128): at its second channel
     // [wave][block of the chunk][8]: {window code, the first unit's four record fields, its draws (un-decimated block), its tail decay, -}
     int *hdr = (int *)(bseed + 128) + wv * ((DSYN_CHUNK + 4) * 8);
     sw.lane = lane;
@@ -1385,7 +1414,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
                 const int4 ur = whole ? make_int4(hb[1], hb[2], hb[3], hb[4]) : make_int4(uj[1], uj[2], uj[3], uj[4]);
                 const int ud = whole ? hb[5] : uj[5];
                 const float urr = __int_as_float(whole ? hb[6] : uj[6]);
-                if (!(ULCX_DBG(c) & 1)) synth_unit(c, sw, S, prec, nrec, ur, unitSeed, ud, urr, tmag + (size_t)(wv * 4 + j) * c.tailStride, Mp);
+                if (!(ULCX_DBG(c) & 1)) synth_unit<LOW>(c, sw, S, prec, nrec, ur, unitSeed, ud, urr, tmag + (size_t)(wv * 4 + j) * c.tailStride, Mp);
                 else for (int i = lane; i < Mp; i += 64) zj[i] = make_float2(0.0f, 0.0f);
                 }
                 STAMP(2);
@@ -1626,6 +1655,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
     const auto &samp = samp_arg(sa...);
     constexpr bool PLANE = SynSrc<SA...>::plane, LR = SynSrc<SA...>::lr;      // the plane source mode, as k_dsyn's
     const auto &pla = plane_arg(sa...);
+    constexpr bool LOW = SynSrc<SA...>::low;                         // the low-rate source mode, as k_dsyn's
     extern __shared__ float lds[];
     const int BS = c.BS, C = c.C, H2 = BS / 2;
     const int s = c.s0 + blockIdx.x, tid = threadIdx.x;
@@ -1633,7 +1663,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
     const DsynLds L = dsyn_lds(BS, 0, 0);
     float2 *z = (float2 *)lds;
     SynWave sw;
-    sw.pre  = (int *)(lds + L.zFloats) + wv * (64 + DSYN_PWORDS(BS));
+    sw.pre  = (int *)(lds + L.zFloats) + wv * (64 + low_pwords(low_arg(sa...), BS));
     sw.seedTab = (uint32_t *)(sw.pre + 64);
     sw.lane = lane;
 #ifdef ULCX_DSYN_STAMPS
@@ -1702,7 +1732,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
                     if (wv == 0) {
                         sw.A = (float *)z;
                         const uint32_t unitSeed = rng_jump(c.jumpT, seed, (uint32_t)udraw[ch * 4 + j]);
-                        synth_unit(c, sw, S, prec, nrec, urec[ch * 4 + j], unitSeed, unit_draws(ch, j), utail[ch * 4 + j].y, tmag + (size_t)(ch * 4 + j) * c.tailStride);
+                        synth_unit<LOW>(c, sw, S, prec, nrec, urec[ch * 4 + j], unitSeed, unit_draws(ch, j), utail[ch * 4 + j].y, tmag + (size_t)(ch * 4 + j) * c.tailStride);
                     }
                     }
                     __syncthreads();
@@ -2050,8 +2080,8 @@ size_t ulcx_spec_lds_bytes(int BS) {
 }
 int ulcx_spec_arrays(int BS) { return spec_lds(BS).nArr; }
 
-size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds) {
-    DsynLds l = dsyn_lds(BS, fast, twInLds);
+size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS) {
+    DsynLds l = dsyn_lds(BS, fast, twInLds, listBS);
     return sizeof(float) * ((size_t)l.zFloats + l.twFloats + l.listFloats);
 }
 
@@ -2072,9 +2102,11 @@ static const void *syn_pick(const UlcxDecCtx &cc) {
 // split: the grid is a cut of the (stream, block) pairs; range: a range call, which runs the cut form for every grid;
 // samp: a sample-crop call, a range call in the sample store mode; plane: a synth call, that mode with the plane source
 // (1: the planes hold the coded mid/side, 2: left/right)
+// low: a low-rate call, that mode with the low-rate source (cc: the context of the REDUCED geometry)
 template <typename OUT>
-static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range, bool samp = false, int plane = 0) {
-    return plane == 2 ? syn_pick<OUT, true, true, UlcxSampArg, UlcxPlaneArg<true>>(cc)
+static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range, bool samp = false, int plane = 0, bool low = false) {
+    return low ? syn_pick<OUT, true, true, UlcxSampArg, UlcxLowArg>(cc)
+         : plane == 2 ? syn_pick<OUT, true, true, UlcxSampArg, UlcxPlaneArg<true>>(cc)
          : plane ? syn_pick<OUT, true, true, UlcxSampArg, UlcxPlaneArg<false>>(cc)
          : samp ? syn_pick<OUT, true, true, UlcxSampArg>(cc)
          : range ? syn_pick<OUT, true, true>(cc) : split ? syn_pick<OUT, true, false>(cc) : syn_pick<OUT, false, false>(cc);
@@ -2085,11 +2117,13 @@ static hipError_t allow_lds(const void *fn, size_t lds) {
 }
 
 // resident workgroups of the stereo synthesis kernel this context runs: what an even cut of the batch is sized for
-int ulcx_dec_syn_slots(const UlcxDecCtx &c) {
+// (walkBS > 0: of the low-rate source instantiations - c the context of the reduced geometry, walkBS the walk's BlockSize)
+int ulcx_dec_syn_slots(const UlcxDecCtx &c, int walkBS) {
     if (!c.fastOK) return 0;
     // what a cut would launch: the float and the PCM16 instantiation are both asked, the smaller residency sizes the cut
-    const void *fns[2] = { syn_fn<float>(c, true, false), syn_fn<int16_t>(c, true, false) };
-    const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds);
+    const bool low = walkBS > 0;
+    const void *fns[2] = { syn_fn<float>(c, true, low, low, 0, low), syn_fn<int16_t>(c, true, low, low, 0, low) };
+    const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds, walkBS);
     int dev = 0, cus = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
     for (const void *fn : fns) {
@@ -2108,18 +2142,26 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
     if (ev) CK(hipEventRecord(ev[stage++], st));
     UlcxDecCtx c = cIn;
     c.s0 = 0; c.s1 = c.B; c.k0 = c.range ? 1 : 0; c.k1 = c.K;
-    const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds);
-    const bool split = c.fastOK && aux.synGrid > 0;
+    // a low-rate call: the walk runs on c, the file's geometry; the rows and the synthesis on cs, the context of BlockSize >> lgD -
+    // its tables, its kernel pick and its lapping scratch - which still addresses the walk's per-block rows and records
+    const bool low = aux.lowLgD > 0;
+    UlcxDecCtx cs = c;
+    if (low) {
+        cs.BS = c.BS >> aux.lowLgD; cs.lgBS = c.lgBS - aux.lowLgD; cs.T = aux.lowT; cs.fastOK = aux.lowFast; cs.twInLds = aux.lowTwInLds;
+        cs.lapScratch = aux.lowLapScratch;
+    }
+    const size_t lds = ulcx_dec_lds_bytes(cs.BS, cs.fastOK, cs.twInLds, low ? c.BS : 0);
+    const bool split = cs.fastOK && aux.synGrid > 0;
     const bool samp = aux.sampStart != nullptr;                       // a sample-crop call: rows from (start, len) first, then the crop walk on them
     const bool spec = aux.specCoef != nullptr;                        // a spectra call: the crop walk, then k_dspec in place of the synthesis
     const bool dist = aux.distOut != nullptr;                         // a distortion call: the crop walk, then k_ddist in place of the synthesis
     const int plane = aux.synCoef ? (aux.synLR ? 2 : 1) : 0;          // a synth call: k_synth_rows in place of every walk, then the plane source synthesis
-    const void *syn = (spec || dist) ? nullptr : c.pcm16 ? syn_fn<int16_t>(c, split, c.range != 0, samp, plane) : syn_fn<float>(c, split, c.range != 0, samp, plane);
+    const void *syn = (spec || dist) ? nullptr : c.pcm16 ? syn_fn<int16_t>(cs, split, c.range != 0, samp, plane, low) : syn_fn<float>(cs, split, c.range != 0, samp, plane, low);
     if (syn) CK(allow_lds(syn, lds));
     if (plane) hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)(((long long)c.B * c.K + 63) / 64)), dim3(64), 0, st, c.B, c.K, aux.synPlanes, aux.synWc,
                                   c.wcScan, c.draws, c.bits, c.rInfo, aux.sampSkip, aux.sampLenC, aux.nSamples);
     else {
-    if (samp) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, c.BS, aux.nSamples, aux.sampStart, aux.sampLen,
+    if (samp) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, cs.BS, aux.nSamples, aux.sampStart, aux.sampLen,
                                  aux.sampFirst, aux.sampCount, aux.sampSkip, aux.sampLenC);
     // the indexed walk: over a crop call's corpus, or for a range call over the decoder's own streams as a strided corpus (file = stream)
     if (aux.corpus.nFiles > 0) hipLaunchKernelGGL(k_dscan_rows, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.corpus, aux.cropFile, aux.cropCount);
@@ -2143,10 +2185,11 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
         CK(hipLaunchKernel(fn, dim3((unsigned)g), dim3(WG), args, slds, st));
     } else if (!(ULCX_DBG(c) & 8)) {
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
-        c.synFull = split ? aux.synFull : (c.range && c.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
+        cs.synFull = split ? aux.synFull : (c.range && cs.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
         UlcxSampArg sa = { aux.sampSkip, aux.sampLenC, aux.nSamples };
         UlcxPlaneArg<false> pa = { aux.synCoef, aux.synPlanes };     // (one layout for both LR settings)
-        void *args[] = { &c, &sa, &pa };                             // (the second one: the sample-store instantiations only; the third: the plane source's)
+        UlcxLowArg la = { c.BS };
+        void *args[] = { &cs, &sa, low ? (void *)&la : (void *)&pa };   // (the second one: the sample-store instantiations only; the third: the plane source's or the low-rate source's)
         CK(hipLaunchKernel(syn, dim3(g), dim3(WG), args, lds, st));
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));

@@ -298,6 +298,14 @@ struct UlcxDecAux {
     const int32_t *synWc = nullptr;      // [c.B][synPlanes] their window codes (untrusted)
     int synPlanes = 0;                   // planes per row: c.K with the plane in front (ULCX_SYNTH_WARM), else c.K - 1
     int synLR = 0;                       // the planes hold left/right: no un-mix
+    // low-rate sample crops (ulcx_decode_crops_lowrate_*): lowLgD > 0 (with sampStart) - the walk at the object's BlockSize, then
+    // the rows and the synthesis at BlockSize >> lowLgD with the low-rate source: what of that geometry's context differs from the
+    // object's (the rest of it - the per-block rows, the records, their strides - stays the walk's); synGrid / synFull are
+    // planned for THAT kernel
+    int lowLgD = 0;
+    UlcxTables lowT = {};
+    int lowFast = 0, lowTwInLds = 0;
+    float *lowLapScratch = nullptr;      // [cut workgroups][C][(BS >> lowLgD) / 2]
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
@@ -318,10 +326,10 @@ struct UlcxSpliceArgs {
     ulcx_index_entry *outIndex; int outIndexStride; int32_t *outIndexBlocks;
 };
 int ulcx_splice_launch(const UlcxDecCtx &c, const UlcxSpliceArgs &a, hipStream_t st);
-size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds);
+size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS = 0);   // listBS: the BlockSize the per-wave lists are sized by (0: BS)
 size_t ulcx_spec_lds_bytes(int BS);               // k_dspec's / k_ddist's dynamic LDS: two unit arrays where a CU holds them, else one
 int ulcx_spec_arrays(int BS);                     // how many that is (1: ULCX_SPECTRA_LR cannot be formed on chip by k_ddist)
-int ulcx_dec_syn_slots(const UlcxDecCtx &c);      // resident workgroups of the stereo synthesis kernel on the current device
+int ulcx_dec_syn_slots(const UlcxDecCtx &c, int walkBS = 0);   // resident workgroups of the stereo synthesis kernel on the current device (walkBS > 0: of its low-rate source form)
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
 // clips (ulcx_clips.hip): the kernels around the launch sequence of ulcx_encode_clips_* - the shadow state of n rows to the state

@@ -55,9 +55,9 @@ _f64p, _u32p, _rungp = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(R
 _DEVICE_PTR = {_f32p: _vp, _i32p: _vp, _u8p: _vp, _i64p: _vp, _f64p: _vp}
 
 
-def _sig(names, argtypes, restype=C.c_int):
+def _sig(names, argtypes, restype=C.c_int, table=None):
     for name in names.split():
-        SIGNATURES[name] = (argtypes, restype)
+        (SIGNATURES if table is None else table)[name] = (argtypes, restype)
 
 
 def _dev(host):
@@ -65,12 +65,12 @@ def _dev(host):
     return [_DEVICE_PTR.get(t, t) for t in host] + [_vp]
 
 
-def _family(names, host, pcm16=False):
+def _family(names, host, pcm16=False, table=None, twins=None):
     """A call family from its host form: names.format("host" / "dev" / "dev_pcm16"); an int16 twin shares its sibling's entry."""
-    _sig(names.format("host"), host)
-    _sig(names.format("dev") + (" " + names.format("dev_pcm16") if pcm16 else ""), _dev(host))
+    _sig(names.format("host"), host, table=table)
+    _sig(names.format("dev") + (" " + names.format("dev_pcm16") if pcm16 else ""), _dev(host), table=table)
     if pcm16:
-        PCM16_TWIN[names.format("dev")] = names.format("dev_pcm16")
+        (PCM16_TWIN if twins is None else twins)[names.format("dev")] = names.format("dev_pcm16")
 
 
 # shared runs of arguments (the first of every list below is the object's handle unless the comment says otherwise)
@@ -173,6 +173,15 @@ _family("ulcx_analyse_clips_{}", [_vp, _int, _f32p, _i32p, _int] + _TAP, pcm16=T
 
 EXPORTS = list(SIGNATURES)
 
+# ---- The second table: the entries of the headers beside ulc_amd.h (include/ulc_amd_lowrate.h), built and applied as the first.
+EXT_SIGNATURES = {}
+EXT_PCM16_TWIN = {}
+_sig("ulcx_lowrate_block", [_int, _int], table=EXT_SIGNATURES)
+for _sfx, _view in (("", _STRIDED), ("_ragged", _RAGGED)):    # the sample-crop rows with lgD behind nSamples
+    _family(f"ulcx_decode_crops_lowrate{_sfx}_{{}}", [_vp, _int] + _view + _rows(_i64p) + [_int] + _PCM, pcm16=True,
+            table=EXT_SIGNATURES, twins=EXT_PCM16_TWIN)
+EXT_EXPORTS = list(EXT_SIGNATURES)
+
 
 def new_index(n_rows, index_stride):
     """An open index as ulcx_index_begin_dev leaves it: entry 0 = (0, 1234567), every other entry (-1, 0)."""
@@ -217,7 +226,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built: run `make -C ulc-codec_amd` (or __graft_entry__.build())")
         l = C.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in SIGNATURES.items():
+        for name, (argtypes, restype) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             fn = getattr(l, name, None)                    # (an older build named by ULC_AMD_LIB for an A/B run may lack some)
             if fn is not None:
                 fn.argtypes, fn.restype = argtypes, restype
@@ -248,7 +257,7 @@ def _dev_call(name, pcm16, stream, *args):
     """A device form: `name` or, with pcm16, its int16 twin; the stream goes last (0: the null stream).  (Not through _call():
     bench.py's timed loop comes through here, and a second frame per call is all the cost there is to save.)"""
     if pcm16:
-        name = PCM16_TWIN[name]
+        name = PCM16_TWIN[name] if name in PCM16_TWIN else EXT_PCM16_TWIN[name]
     _check((_bound.get(name) or _bind(name))(*args, stream or None), name)
 
 
@@ -302,6 +311,12 @@ def crop_blocks(block_size, n_samples):
     """Blocks a crop of n_samples samples touches at the worst start (ulcx_crop_blocks): a sample-crop call's d_bits row, and
     what max_blocks - 1 of its decoder must reach."""
     return int(lib().ulcx_crop_blocks(int(block_size), int(n_samples)))
+
+
+def lowrate_block(block_size, lowrate):
+    """BlockSize of the reduced stream of a low-rate crop (ulcx_lowrate_block): block_size >> lowrate for lowrate 0 .. 3 when that is
+    a legal BlockSize, else 0."""
+    return int(lib().ulcx_lowrate_block(int(block_size), int(lowrate)))
 
 
 def window_subblocks(block_size, wc):
@@ -905,11 +920,15 @@ class BatchDecoder(_StreamSlots):
         self._corpus_call("decode_crops", ragged, corpus, *rows, n_blocks, _p(pcm, _f32p), _p(bits, _i32p))
         return pcm, bits
 
-    def _crops_samples(self, ragged, corpus, files, start, n_samples, length):
+    def _crops_samples(self, ragged, corpus, files, start, n_samples, length, lowrate=None):
         n, rows = _row_view(files, start, np.int64, length)
         pcm = np.zeros((n, self.C, max(1, n_samples)), np.float32)
-        bits = np.zeros((n, max(1, crop_blocks(self.BS, n_samples))), np.int32)
-        self._corpus_call("decode_crops_samples", ragged, corpus, *rows, n_samples, _p(pcm, _f32p), _p(bits, _i32p))
+        bs = self.BS if lowrate is None else (lowrate_block(self.BS, lowrate) or self.BS)     # (a bad ratio: the call refuses it)
+        bits = np.zeros((n, max(1, crop_blocks(bs, n_samples))), np.int32)
+        if lowrate is None:
+            self._corpus_call("decode_crops_samples", ragged, corpus, *rows, n_samples, _p(pcm, _f32p), _p(bits, _i32p))
+        else:
+            self._corpus_call("decode_crops_lowrate", ragged, corpus, *rows, n_samples, int(lowrate), _p(pcm, _f32p), _p(bits, _i32p))
         return pcm, bits
 
     def _crops_spectra(self, ragged, corpus, files, first, n_blocks, count, flags):
@@ -1118,6 +1137,30 @@ class BatchDecoder(_StreamSlots):
         """Device form (d_len 0 / None: every row takes all n_samples); d_pcm is [n][C][n_samples], int16 with pcm16."""
         _dev_call("ulcx_decode_crops_samples_ragged_dev", pcm16, stream, self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total,
                   d_index_offs, d_index_blocks, n, d_file, d_start, d_len or None, n_samples, d_pcm, d_bits)
+
+    # low-rate sample crops (include/ulc_amd_lowrate.h): the sample-crop calls on the stream reduced by 1 << lowrate - block size
+    # BS >> lowrate, start and n_samples in reduced samples, reduced sample m at full-rate time D m + (D - 1) / 2
+
+    def decode_crops_lowrate(self, payload, payload_bytes, index, index_blocks, files, start, n_samples, lowrate, length=None):
+        """decode_crops_samples() at 1 / (1 << lowrate) of the file's rate, lowrate 0 .. 3 (0: that call, bit for bit)
+        -> (pcm [n][C][n_samples], bits [n][crop_blocks(BS >> lowrate, n_samples)], the full blocks' sizes)."""
+        return self._crops_samples(False, (payload, payload_bytes, index, None, index_blocks), files, start, n_samples, length, lowrate)
+
+    def decode_crops_lowrate_dev(self, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_start, d_len,
+                                 n_samples, lowrate, d_pcm, d_bits, stream=0, pcm16=False):
+        """Device form (d_len 0 / None: every row takes all n_samples); d_pcm is [n][C][n_samples], int16 with pcm16."""
+        _dev_call("ulcx_decode_crops_lowrate_dev", pcm16, stream, self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride,
+                  d_index_blocks, n, d_file, d_start, d_len or None, n_samples, int(lowrate), d_pcm, d_bits)
+
+    def decode_crops_lowrate_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, start, n_samples, lowrate, length=None):
+        """decode_crops_lowrate() of a ragged corpus, held as for decode_crops_ragged()."""
+        return self._crops_samples(True, (payload, payload_offs, index, index_offs, index_blocks), files, start, n_samples, length, lowrate)
+
+    def decode_crops_lowrate_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
+                                        n, d_file, d_start, d_len, n_samples, lowrate, d_pcm, d_bits, stream=0, pcm16=False):
+        """Device form (d_len 0 / None: every row takes all n_samples); d_pcm is [n][C][n_samples], int16 with pcm16."""
+        _dev_call("ulcx_decode_crops_lowrate_ragged_dev", pcm16, stream, self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total,
+                  d_index_offs, d_index_blocks, n, d_file, d_start, d_len or None, n_samples, int(lowrate), d_pcm, d_bits)
 
     def index_packed_ragged(self, payload, payload_offs, index_offs, index=None):
         """The index of files back to back: row f (entries index_offs[f] .. index_offs[f+1]) as index_packed_rows() fills a row of
