@@ -12,18 +12,14 @@ import pytest
 
 from gpu_testlib import amd as _amd
 import guarded_buffers as gb
-from ulc_testlib import synth_pcm, oracle_encode_debug, oracle_decode_stream, to_pcm16
+from ulc_testlib import to_pcm16
 from rates_testlib import mode_of
 from seek_testlib import pack
 
 pytestmark = pytest.mark.gpu
 
-RATE = 44100
-N_BLOCKS = 48                                              # PCM / oracle blocks per test stream (no schedule below feeds more)
-VBR50, CBR64 = (-50.0, 0.0), (64.0, 0.0)                   # settings in the tool's convention (rates_testlib.mode_of)
-TABLE = [(-50.0, 0.0), (64.0, 0.0), (96.0, 0.3), (-70.0, 0.0), (48.0, 0.0)]      # per-stream table: VBR / CBR / ABR by stream id
-BIG = (2048, 2, 70, 8)                                     # (BlockSize, channels, slots, maxBlocksPerCall): the fused window control, k_select_wave
-SMALL = (512, 1, 9, 8)                                     # generic selection, non-fused window control
+from call_axis_testlib import RATE, N_BLOCKS, VBR50, CBR64, TABLE, BIG, SMALL, _pcm, _oracle_enc, _oracle_blocks, _oracle_dec, _setting_fn, _Slots
+
 A_PCM, A_PCM16, A_RATE, A_WORD, A_STATE = 16, 8, 8, 4, 16  # include/ulc_amd.h, "Caller buffers" and "Stream slots"
 
 
@@ -48,37 +44,8 @@ def _sync():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# inputs and oracle references, computed once
+# inputs, oracle references and the lives model (_pcm, _oracle_*, _Slots): tests/call_axis_testlib.py, which extends them
 # ---------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _pcm(bs, ch, sid):
-    """[N_BLOCKS][bs][ch]; every third stream is transient-rich, so that decimated windows occur"""
-    return synth_pcm(sid, N_BLOCKS * bs, ch, RATE, transient=(sid % 3 == 0), seed=bs + ch).reshape(N_BLOCKS, bs, ch)
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_enc(bs, ch, sid, origin, n, setting):
-    """The oracle's encode of blocks origin .. origin + n - 1 of stream sid's PCM from a fresh state, under one setting."""
-    mode, p0, p1 = mode_of(setting)
-    return oracle_encode_debug(_pcm(bs, ch, sid)[origin:origin + n].reshape(n * bs, ch), bs, RATE, mode, p0, p1, slot=2 * ch * bs + 16)
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_blocks(bs, ch, sid):
-    """Oracle-encoded VBR 50 blocks of stream sid: (blocks [N_BLOCKS][slot], bits)"""
-    r = _oracle_enc(bs, ch, sid, 0, N_BLOCKS, VBR50)
-    return r["out"], r["bits"]
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_dec(bs, ch, key):
-    """The oracle's decode from a fresh state of the blocks `key` names: ((sid, first block, count), ...) concatenated."""
-    blocks = np.concatenate([_oracle_blocks(bs, ch, sid)[0][a:a + n] for sid, a, n in key])
-    rc, pcm, bits = oracle_decode_stream(blocks, ch, bs)
-    assert rc == 0
-    return pcm.reshape(len(blocks), bs, ch), bits
-
-
 def _schedule(B, seed):
     """About ten calls: K over {1, 3, 8} (the window-control / transform pipeline's 1 / 3 / 4 launch shapes), n over {1, 5, 65,
     70} clipped to the object's slots (65 crosses the 64-stream group of the window-control kernels and the ragged end of the
@@ -89,49 +56,9 @@ def _schedule(B, seed):
     return [(rng.permutation(B)[:min(int(n), B)].astype(np.int32), int(K)) for K, n in zip(Ks, ns)]
 
 
-def _setting_fn(what):
-    return (lambda sid: TABLE[sid % len(TABLE)]) if what == "table" else (lambda sid: what)
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # drivers: feed slots from their streams' PCM / blocks, keep what came back per life, compare with the oracle
 # ---------------------------------------------------------------------------------------------------------------------
-class _Slots:
-    def __init__(self, geom, sid=None):
-        self.bs, self.ch, self.B, self.maxK = geom
-        self.sid = list(range(self.B)) if sid is None else list(sid)          # the test stream that feeds each slot
-        self.pos = [0] * self.B                                               # next block of it
-        self.lives = [[dict(sid=self.sid[s], origin=0, first=0, blocks=[])] for s in range(self.B)]
-
-    def new_life(self, slot, sid=None, origin=None, first=0):
-        """slot starts another stream (a reset: the same PCM from where it stands) or takes one over (a load: first blocks done elsewhere)"""
-        if sid is not None:
-            self.sid[slot] = sid
-        if origin is not None:
-            self.pos[slot] = origin + first
-        self.lives[slot].append(dict(sid=self.sid[slot], origin=self.pos[slot] - first, first=first, blocks=[]))
-
-    def rows(self, slots, K, bad):
-        """(sid, first block) per row; a list entry outside [0, B) is fed stream bad[row] from its block 0"""
-        r = []
-        for i, s in enumerate(slots):
-            ok = 0 <= s < self.B
-            r.append((self.sid[s], self.pos[s]) if ok else (bad[i], 0))
-            assert r[-1][1] + K <= N_BLOCKS
-        return r
-
-    def keep(self, slots, K, per_row):
-        """per_row[i][k] -> the slot's current life; rows of entries outside [0, B) are returned"""
-        extra = {}
-        for i, s in enumerate(slots):
-            if 0 <= s < self.B:
-                self.lives[s][-1]["blocks"] += per_row[i]
-                self.pos[s] += K
-            else:
-                extra[i] = per_row[i]
-        return extra
-
-
 class EncDriver(_Slots):
     def __init__(self, geom, what=VBR50, sid=None):
         super().__init__(geom, sid)
