@@ -140,6 +140,29 @@ def test_lr_skips_the_unmix(geom):
     assert not same(got[:, 0], pcm[:, 0])                   # (it did skip something)
 
 
+def test_lr_on_stereo_below_2048():
+    """Stereo below BlockSize 2048 takes the two-wave synthesis with the BlockSize read at run time, which no geometry above has
+    under LR: rows of 4 blocks over every header code of a 256 x 2 stream (every decimated tail), with the plane in front and
+    from block 0, float and PCM16 - the coded planes give the oracle's PCM, and under LR its re-mix in numpy, bit for bit."""
+    bs, ch, n_out = 256, 2, 4
+    ref = Y.code_stream(bs, ch)
+    dec = _amd().BatchDecoder(len(Y.windows(ref.K, n_out)), ch, bs, n_out + 1)
+    for rows, warm in (([(0, f) for f in Y.windows(ref.K, n_out)], 1), ([(0, 0)], 0)):
+        coef, wc, pcm, live = Y.stack([ref], rows, n_out, warm)
+        assert any(int(w) != 0x10 for w in wc[:, warm:].ravel() if w)
+        check_both_forms(dec, coef, wc, pcm, live, WARM * warm, bs, f"{bs}x{ch} warm {warm}")
+        for pcm16 in (False, True):
+            got, glive = synth(dec, coef, wc, WARM * warm | LR, pcm16=pcm16)
+            if pcm16:                                       # (the conversion clamps: PCM16 under LR is the conversion of the float planes)
+                check_rows((got, glive), (Y.to_pcm16(lr_f), live), bs, f"{bs}x{ch} warm {warm} LR, pcm16")
+                continue
+            lr_f = got
+            mixed = np.stack([got[:, 0] + got[:, 1], got[:, 0] - got[:, 1]], axis=1)
+            check_rows((mixed, glive), (pcm, live), bs, f"{bs}x{ch} warm {warm} LR, re-mixed in numpy")
+            assert not same(got[:, 0], pcm[:, 0])
+    dec.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. arbitrary planes against the float64 referee
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1407,23 +1407,23 @@ extern "C" int ulcx_decoder_last_cut(ulcx_decoder *e, int *workgroups, int *whol
 // subsetSet != NULL: a subset call - c.B is the number of listed slots (what the cut is planned from) and c.lap .. c.dead are
 // set 0 of the compact shadow state; a cut leaves its result in set 1 of THAT state, the object's own sets are not swapped,
 // and *subsetSet receives the set that holds the result.
-// crop != NULL: a crop call (with subsetSet: it runs on the shadow state as a subset call does) - the walk's corpus arguments;
-// no stream's generator word moves, so the single-block path's host copy stays good.
-static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subsetSet = nullptr, const UlcxDecAux *crop = nullptr) {
-    if (!e->inBlock1 && !crop) e->b1SeedStale = true;             // (a batched / packed call on a one-stream decoder: see b1Seed)
+// call: what kind of call it is and that kind's arguments (NULL: a plain call).  A call on rows of its own - every kind behind ULCX_DEC_RANGE, with
+// subsetSet: it runs on the shadow state as a subset call does - moves no stream's generator word, so the single-block path's host copy stays good.
+static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subsetSet = nullptr, const UlcxDecAux *call = nullptr) {
     UlcxDecAux a;
-    if (crop) a = *crop;
+    if (call) a = *call;
     a.synGrid = 0; a.synFull = 0;
+    const bool range = a.kind != ULCX_DEC_PLAIN, low = a.kind == ULCX_DEC_LOWRATE;
+    if (!e->inBlock1 && a.kind <= ULCX_DEC_RANGE) e->b1SeedStale = true;   // (a batched / packed call on a one-stream decoder: see b1Seed)
     c.lapO = c.lap; c.lastSubO = c.lastSub; c.seedO = c.seed; c.deadO = c.dead;
-    const int Kc = c.range ? c.K - 1 : c.K;                       // blocks of the call per stream (a range call's K counts the row of the block in front)
+    const int Kc = range ? c.K - 1 : c.K;                         // blocks of the call per stream (a range call's K counts the row of the block in front)
     // (a low-rate call: the cut is planned for the kernel of the reduced geometry - its residency, its scratch rows)
-    const bool low = a.lowLgD > 0;
-    const int synSlots = low ? e->low[a.lowLgD].synSlots : e->synSlots, scratchRows = low ? e->low[a.lowLgD].scratchRows : e->scratchRows;
-    if ((low || e->splitOK) && synSlots > 0 && !a.specCoef && !a.distOut) {      // (a spectra or distortion call has no synthesis to cut: the plain plan)
+    const int synSlots = low ? e->low[a.low.lgD].synSlots : e->synSlots, scratchRows = low ? e->low[a.low.lgD].scratchRows : e->scratchRows;
+    if ((low || e->splitOK) && synSlots > 0 && ulcx_dec_has_synthesis(a.kind)) {  // (a spectra or distortion call has no synthesis to cut: the plain plan)
         // A range call of more streams than the device holds at once: whole rounds, and the last one cut
         // (ulcx_dec_range_tail_plan) - an even cut of everything ends every workgroup inside a stream, and in a range call every
         // entry into a stream costs the block in front of the range (ULCX_RANGE_CUT=even: the even cut first, as for other calls)
-        if (c.range && c.B > synSlots && e->tailCut && !e->rangeEvenFirst) {
+        if (range && c.B > synSlots && e->tailCut && !e->rangeEvenFirst) {
             int full = 0;
             const int tail = ulcx_dec_range_tail_plan(c.B, Kc, synSlots, &full);
             if (tail > 0 && tail <= scratchRows) { a.synGrid = full + tail; a.synFull = full; }
@@ -1431,7 +1431,7 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subse
         if (!a.synGrid) a.synGrid = ulcx_dec_split_plan(c.B, Kc, synSlots);
         if (!a.synGrid) {
             int full = 0;
-            const int tail = c.range ? ulcx_dec_range_tail_plan(c.B, Kc, synSlots, &full) : ulcx_dec_tail_plan(c.B, Kc, synSlots, &full);
+            const int tail = range ? ulcx_dec_range_tail_plan(c.B, Kc, synSlots, &full) : ulcx_dec_tail_plan(c.B, Kc, synSlots, &full);
             if (tail > 0 && tail <= scratchRows && e->tailCut) { a.synGrid = full + tail; a.synFull = full; }
         }
         if (a.synGrid) {
@@ -1453,6 +1453,14 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subse
     return rc;
 }
 
+// The synthesis kernel of a geometry (the object's, or a low-rate ratio's reduced one).  fastOK: stereo streams up to BlockSize 4096 take k_dsyn
+// - both channels' FFT arrays in LDS, one wave per channel, the lapping state in global memory (ULCX_DEC_FAST=0: never) -, everything else the
+// general kernel (k_dgen: one array).  twInLds: k_dsyn up to BlockSize 2048 keeps the FFT twiddles in LDS, above it they come from the tables.
+static void dec_syn_geometry(int nChan, int BlockSize, int *fastOK, int *twInLds) {
+    *fastOK = (nChan == 2 && BlockSize <= 4096) ? 1 : 0;
+    if (const char *ev = getenv("ULCX_DEC_FAST")) *fastOK = *fastOK && (ev[0] != '0');
+    *twInLds = (*fastOK && BlockSize <= 2048 && ULCX_DSYN_TWL) ? 1 : 0;
+}
 extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams, int nChan, int BlockSize, int maxBlocksPerCall) {
     const char *who = "ulcx_decoder_create";
     if (!out) return refuse(who, "no place for the object");
@@ -1467,12 +1475,7 @@ extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams,
 #ifdef ULCX_ABLATE
     if (const char *ev = getenv("ULCX_DBG_SKIP")) c.dbgSkip = atoi(ev);
 #endif
-    // stereo streams up to BlockSize 4096 keep their lapping state, both channels' FFT arrays and the twiddles in LDS, one wave
-    // per channel (k_dsyn); everything else takes the general kernel (k_dgen: one array, state in HBM)
-    c.fastOK = (nChan == 2 && BlockSize <= 4096) ? 1 : 0;
-    if (const char *ev = getenv("ULCX_DEC_FAST")) c.fastOK = c.fastOK && (ev[0] != '0');
-    // stereo synthesis kernel: lapping state in global memory; BlockSize <= 2048: FFT twiddles in LDS (mode 2), above: from the tables
-    c.twInLds = (c.fastOK && BlockSize <= 2048 && ULCX_DSYN_TWL) ? 1 : 0;
+    dec_syn_geometry(nChan, BlockSize, &c.fastOK, &c.twInLds);
     rc = ulcx_tables_build(&c.T, &e->tables, BlockSize, 44100, false);
     if (rc) { cleanup(e); return rc; }
     size_t B = nStreams, NB = B * maxBlocksPerCall;
@@ -1486,7 +1489,7 @@ extern "C" int ulcx_decoder_create(ulcx_decoder **out, int device, int nStreams,
         if (const char *ev = getenv("ULCX_DSYN_SPLIT")) want = ev[0] != '0';
         if (const char *ev = getenv("ULCX_DSYN_TAIL")) e->tailCut = ev[0] != '0';          // (A/B: the last round uncut)
         if (const char *ev = getenv("ULCX_RANGE_CUT")) e->rangeEvenFirst = !strcmp(ev, "even");   // (A/B: range calls planned as other calls are)
-        e->synSlots = want ? ulcx_dec_syn_slots(c) : 0;
+        e->synSlots = want ? ulcx_dec_syn_slots(c, ULCX_SYN_CUT) : 0;
         if (e->synSlots > 0) {
             DA(e->lap2, B * nChan * (BlockSize / 2), true);
             DA(e->lastSub2, B, true);
@@ -1891,7 +1894,8 @@ static int decode_range_any(const char *who, ulcx_decoder *e, const uint8_t *d_p
     c.packed = 1; c.payStride = payloadStride; c.payBytes = d_payloadBytes;
     c.inBytes = (long long)e->B * payloadStride;
     c.range = 1; c.rIndex = d_index; c.rIndexStride = indexStride; c.rIndexBlocks = d_indexBlocks; c.rFirst = d_first;
-    int rc = dec_launch(e, c, (hipStream_t)hipStream);
+    UlcxDecAux call = {}; call.kind = ULCX_DEC_RANGE;
+    int rc = dec_launch(e, c, (hipStream_t)hipStream, nullptr, &call);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
     return rc;
 }
@@ -2035,16 +2039,13 @@ static int dec_low(ulcx_decoder *e, int lgD) {
     const int BSr = e->BS >> lgD;
     int rc;
     if (!l.tables && (rc = ulcx_tables_build(&l.T, &l.tables, BSr, 44100, false))) return rc;
-    // the kernel pick of the REDUCED geometry (ulcx_decoder_create's rule): stereo up to BlockSize 4096 takes k_dsyn
-    l.fastOK = (e->C == 2 && BSr <= 4096) ? 1 : 0;
-    if (const char *ev = getenv("ULCX_DEC_FAST")) l.fastOK = l.fastOK && (ev[0] != '0');
-    l.twInLds = (l.fastOK && BSr <= 2048 && ULCX_DSYN_TWL) ? 1 : 0;
+    dec_syn_geometry(e->C, BSr, &l.fastOK, &l.twInLds);      // the kernel pick of the REDUCED geometry
     if (l.fastOK) {
         bool want = true;
         if (const char *ev = getenv("ULCX_DSYN_SPLIT")) want = ev[0] != '0';
         UlcxDecCtx cs = e->ctx;
         cs.BS = BSr; cs.lgBS = ilog2i(BSr); cs.T = l.T; cs.fastOK = l.fastOK; cs.twInLds = l.twInLds;
-        l.synSlots = want ? ulcx_dec_syn_slots(cs, e->BS) : 0;
+        l.synSlots = want ? ulcx_dec_syn_slots(cs, ULCX_SYN_LOW, e->BS) : 0;
         if (l.synSlots > 0 && !l.lapScratch) {
             l.scratchRows = 4 * l.synSlots;
             if ((rc = dalloc(e->allocs, &l.lapScratch, (size_t)l.scratchRows * e->C * (BSr / 2), true))) return rc;
@@ -2128,21 +2129,18 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &
     c.packed = 1; c.range = 1; c.rFirst = d_first;
     c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
     UlcxDecAux crop = {};
+    crop.kind = dist ? ULCX_DEC_DISTORTION : spec ? ULCX_DEC_SPECTRA : !samp ? ULCX_DEC_CROPS : samp->lgD > 0 ? ULCX_DEC_LOWRATE : ULCX_DEC_SAMPLES;
     crop.corpus = g; crop.cropFile = d_file; crop.cropCount = d_count;
     if (samp) {
-        crop.sampStart = samp->start; crop.sampLen = samp->len; crop.nSamples = samp->nSamples;
-        crop.sampFirst = e->sampRows; crop.sampCount = e->sampRows + e->B; crop.sampSkip = e->sampRows + 2 * (size_t)e->B; crop.sampLenC = e->sampRows + 3 * (size_t)e->B;
-        c.rFirst = crop.sampFirst; crop.cropCount = crop.sampCount;
+        crop.samp = { samp->start, samp->len, samp->nSamples, e->sampRows, e->sampRows + e->B, e->sampRows + 2 * (size_t)e->B, e->sampRows + 3 * (size_t)e->B };
+        c.rFirst = crop.samp.first; crop.cropCount = crop.samp.count;
         if (samp->lgD > 0) {
             const UlcxDecLow &l = e->low[samp->lgD];
-            crop.lowLgD = samp->lgD; crop.lowT = l.T; crop.lowFast = l.fastOK; crop.lowTwInLds = l.twInLds; crop.lowLapScratch = l.lapScratch;
+            crop.low = { samp->lgD, l.T, l.fastOK, l.twInLds, l.lapScratch };
         }
     }
-    if (spec) { crop.specCoef = spec->coef; crop.specWc = spec->wc; crop.specLR = (spec->flags & ULCX_SPECTRA_LR) ? 1 : 0; }
-    if (dist) {
-        crop.distOut = dist->dist; crop.distSeg = dist->nSeg; crop.distRef = dist->ref; crop.distNRef = dist->nRef; crop.distRefBlocks = dist->nRefBlocks;
-        crop.distRefRow = dist->refRow; crop.distRefFirst = dist->refFirst;
-    }
+    if (spec) crop.spec = { spec->coef, spec->wc, (spec->flags & ULCX_SPECTRA_LR) ? 1 : 0 };
+    if (dist) crop.dist = { dist->dist, dist->ref, dist->nRef, dist->nRefBlocks, dist->nSeg, dist->refRow, dist->refFirst };
     int set = 0;
     rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &crop);
     e->evRecorded = (rc == ULCX_OK) && e->timing;
@@ -2557,10 +2555,9 @@ static int synth_spectra_any(const char *who, ulcx_decoder *e, int n, int nBlock
     c.packed = 1; c.payStride = 0; c.payBytes = nullptr;
     c.range = 1; c.rIndex = nullptr; c.rIndexStride = 0; c.rIndexBlocks = nullptr; c.rFirst = nullptr;
     c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
-    UlcxDecAux syn = {};
-    syn.synCoef = d_coef; syn.synWc = d_wc; syn.synPlanes = nBlocks; syn.synLR = (flags & ULCX_SPECTRA_LR) ? 1 : 0;
-    syn.nSamples = nOut * e->BS;
-    syn.sampSkip = e->sampRows + 2 * (size_t)e->B; syn.sampLenC = e->sampRows + 3 * (size_t)e->B;
+    UlcxDecAux syn = {}; syn.kind = ULCX_DEC_SYNTH;
+    syn.syn = { d_coef, d_wc, nBlocks, (flags & ULCX_SPECTRA_LR) ? 1 : 0 };
+    syn.samp.nSamples = nOut * e->BS; syn.samp.skip = e->sampRows + 2 * (size_t)e->B; syn.samp.lenC = e->sampRows + 3 * (size_t)e->B;
     int set = 0;
     rc = dec_launch(e, c, (hipStream_t)hipStream, &set, &syn);
     e->evRecorded = (rc == ULCX_OK) && e->timing;

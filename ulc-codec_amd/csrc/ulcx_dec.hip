@@ -786,7 +786,7 @@ __device__ __forceinline__ uint32_t par_word(const uint32_t *__restrict__ parT, 
     const uint32_t *J = parT + lane;
     return J[(st & 255u) << 6] ^ J[(256u + ((st >> 8) & 255u)) << 6] ^ J[(512u + ((st >> 16) & 255u)) << 6] ^ J[(768u + (st >> 24)) << 6];
 }
-// LOW (the low-rate source mode, UlcxLowArg): only the pieces below coefficient `keep` are written - keep is a multiple of 32, so a
+// LOW (the low-rate source mode, SynLow): only the pieces below coefficient `keep` are written - keep is a multiple of 32, so a
 // piece lies on one side of it -, while P still covers every draw of the unit: a kept coefficient's draw index counts them all.
 template <bool LOW = false>
 __device__ __forceinline__ void synth_noise(const UlcxDecCtx &c, const SynWave &sw, const uint2 *__restrict__ list, int nE, const uint2 ent0, uint32_t x0, uint32_t unitSeed, int unitDraws,
@@ -1024,12 +1024,9 @@ template <> __device__ __forceinline__ int16_t *out_base<int16_t>(const UlcxDecC
 // block on, and the output is channels-first, [row][channel][nSamples].  The synthesis is the range synthesis, block for block;
 // only where a sample goes changes: sample m of output block kOut of a row belongs at t = kOut * BlockSize + m - skip of each
 // channel's plane, it is stored when t lies in [0, nSamples), and as 0 when t >= len (the row's length).  Both kernels take the
-// mode as a further argument (k_dsyn<..., UlcxSampArg>): no other instantiation sees any of it.
+// mode's fields in their one further argument (SynSamples, below): no other instantiation sees any of it.
 // One (row, block)'s clip is three bounds on m and is the same for every thread: scalars.
 struct UlcxSampArg { const int32_t *skip, *len; int nSamples; };      // [rows] each, written by k_crop_sample_rows
-struct UlcxSampNone {};
-__device__ __forceinline__ UlcxSampNone samp_arg() { return UlcxSampNone{}; }
-__device__ __forceinline__ const UlcxSampArg &samp_arg(const UlcxSampArg &a) { return a; }
 template <typename OUT>
 struct SampBlk {
     OUT *org;                    // where sample m = 0 of channel 0 would go (in front of the plane when the row starts inside the block: an address only)
@@ -1085,43 +1082,46 @@ __global__ __launch_bounds__(64) void k_crop_sample_rows(int n, int BS, int nSam
 }
 
 // ---------------------------------------------------------------------------
-// Plane source mode (ulcx_synth_spectra_*): the synthesis of caller-held coefficients.  A second further argument beside the
-// sample store mode's (k_dsyn<..., UlcxSampArg, UlcxPlaneArg<LR>>; RANGE launches only): where the other instantiations
-// dequantise a unit from the walk's records (synth_unit), these load its S floats from the row's plane - coef
+// Plane source mode (ulcx_synth_spectra_*): the synthesis of caller-held coefficients.  SynPlanes<LR>, a range launch in the sample
+// store mode: where the other instantiations dequantise a unit from the walk's records (synth_unit), these load its S floats from the row's plane - coef
 // [row][channel][nPl][BS], a block's subblocks in coded order, what the spectra calls write - into the same padded array, and
 // everything behind that is the one shared text.  No walk has run: k_synth_rows wrote the rows the synthesis reads (window
 // codes, liveness), and nothing of the walk's records, draws or generator states is looked at.
 // LR: the planes hold left/right already - the time-domain un-mix (ulcDecoder.c:281-289) is skipped, each channel stored as it stands.
 // Row k of a stream's K per-block rows is plane k - (K - nPl): nPl = K when plane 0 is the block in front (ULCX_SYNTH_WARM), else K - 1.
-template <bool LR> struct UlcxPlaneArg { const float *coef; int nPl; };
-struct UlcxPlaneNone {};
-template <typename... SA> struct SynSrc { static constexpr bool plane = false, lr = false, low = false; };
-template <bool LR_> struct SynSrc<UlcxSampArg, UlcxPlaneArg<LR_>> { static constexpr bool plane = true, lr = LR_, low = false; };
-template <bool LR> __device__ __forceinline__ const UlcxSampArg &samp_arg(const UlcxSampArg &a, const UlcxPlaneArg<LR> &) { return a; }
-__device__ __forceinline__ UlcxPlaneNone plane_arg() { return UlcxPlaneNone{}; }
-__device__ __forceinline__ UlcxPlaneNone plane_arg(const UlcxSampArg &) { return UlcxPlaneNone{}; }
-template <bool LR> __device__ __forceinline__ const UlcxPlaneArg<LR> &plane_arg(const UlcxSampArg &, const UlcxPlaneArg<LR> &p) { return p; }
-__device__ __forceinline__ const float *plane_of(const UlcxPlaneNone &, int, int, int, int, int, int) { return nullptr; }
-template <bool LR> __device__ __forceinline__ const float *plane_of(const UlcxPlaneArg<LR> &p, int row, int C, int ch, int K, int k, int BS) {
-    return p.coef + (((size_t)row * C + ch) * p.nPl + (k - (K - p.nPl))) * (size_t)BS;
-}
-// Low-rate source mode (ulcx_decode_crops_lowrate_*): a third further argument in the plane source's place (k_dsyn<..., UlcxSampArg,
-// UlcxLowArg>; RANGE launches only).  The walk has run at the file's BlockSize BSw; the context this synthesis gets is that of
-// BlockSize BS = BSw >> lgD - geometry, tables, lapping rows - while the per-block rows, the records and their strides are still
-// the walk's.  A unit of S coefficients is dequantised up to its leading S >> lgD (synth_unit<true>: the records and the draws
-// are the full unit's) and everything behind that is the one shared text at BS: the reference decoder of BlockSize BS whose
-// TransformBuffer holds the low bins.  The per-wave lists (the sign-parity stream covers the FULL unit's draws) are sized by BSw.
-struct UlcxLowArg { int BSw; };
-struct UlcxLowNone {};
-template <> struct SynSrc<UlcxSampArg, UlcxLowArg> { static constexpr bool plane = false, lr = false, low = true; };
-__device__ __forceinline__ const UlcxSampArg &samp_arg(const UlcxSampArg &a, const UlcxLowArg &) { return a; }
-__device__ __forceinline__ UlcxPlaneNone plane_arg(const UlcxSampArg &, const UlcxLowArg &) { return UlcxPlaneNone{}; }
-template <typename... SA> __device__ __forceinline__ UlcxLowNone low_arg(const SA &...) { return UlcxLowNone{}; }
-__device__ __forceinline__ const UlcxLowArg &low_arg(const UlcxSampArg &, const UlcxLowArg &l) { return l; }
+// Low-rate source mode (ulcx_decode_crops_lowrate_*): SynLow, a range launch in the sample store mode.  The walk has run at the
+// file's BlockSize BSw; the context this synthesis gets is that of BlockSize BS = BSw >> lgD - geometry, tables, lapping rows -
+// while the per-block rows, the records and their strides are still the walk's.  A unit of S coefficients is dequantised up to
+// its leading S >> lgD (synth_unit<true>: the records and the draws are the full unit's) and everything behind that is the one
+// shared text at BS: the reference decoder of BlockSize BS whose TransformBuffer holds the low bins.  The per-wave lists (the
+// sign-parity stream covers the FULL unit's draws) are sized by BSw.
 // words of a wave's sign-parity stream: by the BlockSize of the walk
 #define DSYN_PWORDS(BS) (((BS) / 32 > 64 ? (BS) / 32 : 64) + 2)
-__device__ __forceinline__ int low_pwords(const UlcxLowNone &, int BS) { return DSYN_PWORDS(BS); }
-__device__ __forceinline__ int low_pwords(const UlcxLowArg &l, int) { return DSYN_PWORDS(l.BSw); }
+// Synthesis modes: what kind of call a launch of k_dsyn / k_dgen serves, one type per kind (host side: UlcxSynKind).  The mode is the
+// kernel's template parameter MODE and its one further argument: constants that say what the kernel text compiles in, and the
+// fields only that kind of call has.
+//   split  the grid is an even cut of the (stream, block) pairs (k_dsyn; k_dgen ignores it)
+//   range  streams are entered from nothing, through the block in front (a range call, and everything built on one)
+//   samp   the sample store mode: s, the rows' clips
+//   plane  the plane source mode (no records, no generator): unit(), where a unit's coefficients lie;  lr: the planes hold left/right
+//   low    the low-rate source mode (the records clipped to the reduced units): pwords(), the sign-parity words of the walk's BlockSize
+#define SYN_MODE(SPLIT, RANGE, SAMP, PLANE, LR_, LOW) static constexpr bool split = SPLIT, range = RANGE, samp = SAMP, plane = PLANE, lr = LR_, low = LOW
+struct SynWhole   { SYN_MODE(false, false, false, false, false, false); };       // one workgroup per stream, from and to the stream's state
+struct SynCut     { SYN_MODE(true,  false, false, false, false, false); };       // the same call over a cut
+struct SynRange   { SYN_MODE(true,  true,  false, false, false, false); };       // range and crop calls
+struct SynSamples { SYN_MODE(true,  true,  true,  false, false, false); UlcxSampArg s; };
+template <bool LR_> struct SynPlanes {
+    SYN_MODE(true, true, true, true, LR_, false); UlcxSampArg s; const float *coef; int nPl;
+    __device__ __forceinline__ const float *unit(int row, int C, int ch, int K, int k, int BS) const { return coef + (((size_t)row * C + ch) * nPl + (k - (K - nPl))) * (size_t)BS; }
+};
+struct SynLow { SYN_MODE(true, true, true, false, false, true); UlcxSampArg s; int BSw; __device__ __forceinline__ int pwords() const { return DSYN_PWORDS(BSw); } };
+#undef SYN_MODE
+template <typename MODE> __device__ __forceinline__ int syn_pwords(const MODE &m, int BS) { if constexpr (MODE::low) return m.pwords(); else return DSYN_PWORDS(BS); }
+// a range call enters streams as a cut does; sample crops are range launches; both sources store samples
+template <typename M> constexpr bool syn_mode_ok = (!M::range || M::split) && (!M::samp || M::range) && (!M::plane || M::samp) && (!M::lr || M::plane) && (!M::low || (M::samp && !M::plane));
+static_assert(syn_mode_ok<SynWhole> && syn_mode_ok<SynCut> && syn_mode_ok<SynRange> && syn_mode_ok<SynSamples> && syn_mode_ok<SynPlanes<false>> && syn_mode_ok<SynPlanes<true>> && syn_mode_ok<SynLow>);
+// the fields behind the sample clips lie where a further kernel argument of their own would: the kernels' argument loads do not move
+static_assert(sizeof(SynSamples) == sizeof(UlcxSampArg) && offsetof(SynPlanes<true>, coef) == sizeof(UlcxSampArg) && offsetof(SynLow, BSw) == sizeof(UlcxSampArg));
 // S coefficients at src (16-byte aligned, read once) into the padded array A; thread t0 of `step`.  DPS 4: four floats at a
 // multiple of four never straddle a padding gap (spec_ld4).  The padding itself is never read by the transform.
 __device__ __forceinline__ void plane_unit(float *A, const float *__restrict__ src, int S, int t0, int step) {
@@ -1171,27 +1171,20 @@ __host__ __device__ static inline DsynLds dsyn_lds(int BS, int fast, int twInLds
 // Stereo streams (BlockSize <= 4096): one workgroup = one stream, one wave per channel up to the end of the FFTs.
 // ---------------------------------------------------------------------------
 // The lapping state lives in global memory (L2-hot: every element is re-read by the thread that wrote it one block earlier);
-// TWL: FFT twiddles in LDS (BlockSize <= 2048); SPLIT: the grid is an even cut of the (stream, block) pairs (else one
-// workgroup per stream: the index arithmetic and the choice of the lapping rows below fold away)
+// TWL: FFT twiddles in LDS (BlockSize <= 2048)
 // BSC: BlockSize as a compile-time constant (2048: the headline geometry - the loops of an un-decimated block unroll, the
 // table and lapping-state loads of a thread's trips can be issued together; 0: read from the context)
-// RANGE: a range call (ulcx_decode_range_*; always with SPLIT).  A stream is entered from nothing instead of from its
-// persistent state: zero lapping state, the generator state the block index holds, and - unless the range starts at
-// block 0 - the block in front of it (row k0 - 1 of the stream) run without output, as a cut enters a stream.
-// SA = UlcxSampArg (one further argument; RANGE launches only): the sample-crop store mode - every store of output samples
-// goes through the (row, block)'s SampBlk instead of to the block's interleaved row.  SA empty: none of that exists.
-template <typename OUT, int DEC_MAXT, bool TWL, bool SPLIT = false, int BSC = 0, bool RANGE = false, typename... SA>
-__global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
-    static_assert(!RANGE || SPLIT, "k_dsyn: a range call enters streams as a cut does");
-    constexpr bool SAMP = sizeof...(SA) != 0;
-    static_assert(!SAMP || RANGE, "k_dsyn: sample crops are range launches");
-    const auto &samp = samp_arg(sa...);
-    constexpr bool PLANE = SynSrc<SA...>::plane, LR = SynSrc<SA...>::lr;      // the plane source mode (UlcxPlaneArg): no records, no generator
-    const auto &pla = plane_arg(sa...);
-    constexpr bool LOW = SynSrc<SA...>::low;                         // the low-rate source mode (UlcxLowArg): the records clipped to the reduced units
+// MODE: the synthesis mode (above).  SynWhole: the index arithmetic and the choice of the lapping rows below fold away.  The range
+// modes (SynRange and on; a cut for every grid): a stream is entered from nothing instead of from its persistent state - zero
+// lapping state, the generator state the block index holds, and - unless the range starts at block 0 - the block in front of it
+// (row k0 - 1 of the stream) run without output, as a cut enters a stream.  The sample store modes (SynSamples and on): every store
+// of output samples goes through the (row, block)'s SampBlk instead of to the block's interleaved row.
+template <typename OUT, int DEC_MAXT, bool TWL, int BSC, typename MODE>
+__global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, MODE mode) {
+    constexpr bool SPLIT = MODE::split, RANGE = MODE::range, SAMP = MODE::samp, PLANE = MODE::plane, LR = MODE::lr, LOW = MODE::low;
     extern __shared__ float lds[];
     const int BS = BSC ? BSC : c.BS, H2 = BS / 2;
-    const int PW = low_pwords(low_arg(sa...), BS);
+    const int PW = syn_pwords(mode, BS);
     constexpr int C = 2;
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -1282,7 +1275,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
             dead = RANGE ? bad : (c.dead[s] | bad);                  // (a corrupt block in front: the stream is dead, no other state matters)
             lastSub = RANGE ? 0 : c.lastSub[s];
             if constexpr (!PLANE) seed = RANGE ? (uint32_t)c.rInfo[s].y : c.seed[s];
-            if constexpr (SAMP) { rowSkip = samp.skip[s]; rowLen = samp.len[s]; }
+            if constexpr (SAMP) { rowSkip = mode.s.skip[s]; rowLen = mode.s.len[s]; }
             if constexpr (RANGE) { if (k == c.k0 && kf == c.k0) for (int i = tid; i < 2 * H2; i += WG) scr[i] = 0.0f; }   // a range from block 0: nothing pending (ordered by the barrier in front of the chunk's tables)
             if (k > kf) {
                 if constexpr (!PLANE) {
@@ -1341,7 +1334,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
         OUT *outp = out_base<OUT>(c) + oblk * C * BS;
         SampBlk<OUT> sb; OUT *sp0 = nullptr, *sp1 = nullptr; bool sal0 = false, sal1 = false;   // SAMP: where this block's samples go instead - the two planes, and whether their pairs are aligned
         if constexpr (SAMP) {
-            sb = samp_blk<OUT>(out_base<OUT>(c), C, BS, samp.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
+            sb = samp_blk<OUT>(out_base<OUT>(c), C, BS, mode.s.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
             sp0 = sb.plane(0); sp1 = sb.plane(1); sal0 = sb.pairs(sp0); sal1 = sb.pairs(sp1);
         }
         if constexpr (RANGE) { if (!warm && tid == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; }
@@ -1383,7 +1376,7 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
         // handed out by lane reads; a unit used to start with its own loads and its own jump, one after the other.
         int *uh = hdr + DSYN_CHUNK * 8;                              // [4 units][8] of this wave, behind its chunk table
         const float *plane = nullptr;                                // PLANE: this wave's channel of the block, where the records' place is
-        if constexpr (PLANE) plane = plane_of(pla, s, C, wv, c.K, k, BS);
+        if constexpr (PLANE) plane = mode.unit(s, C, wv, c.K, k, BS);
         if (!PLANE && !whole) {
             if (lane < nsub) {
                 const int dj = udraw[wv * 4 + lane];
@@ -1648,14 +1641,10 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, SA... sa) {
 // the lapping state and the staging of the time samples in global memory.  Correct for every geometry the
 // reference accepts (ulcDecoder.c:33-35: up to 255 channels, BlockSize up to 32768), not tuned.
 // ---------------------------------------------------------------------------
-template <typename OUT, bool RANGE = false, typename... SA>
-__global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
-    constexpr bool SAMP = sizeof...(SA) != 0;                        // the sample-crop store mode, as k_dsyn's
-    static_assert(!SAMP || RANGE, "k_dgen: sample crops are range launches");
-    const auto &samp = samp_arg(sa...);
-    constexpr bool PLANE = SynSrc<SA...>::plane, LR = SynSrc<SA...>::lr;      // the plane source mode, as k_dsyn's
-    const auto &pla = plane_arg(sa...);
-    constexpr bool LOW = SynSrc<SA...>::low;                         // the low-rate source mode, as k_dsyn's
+// MODE: the synthesis mode, as k_dsyn's; one workgroup per stream whatever its `split` says.
+template <typename OUT, typename MODE>
+__global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, MODE mode) {
+    constexpr bool RANGE = MODE::range, SAMP = MODE::samp, PLANE = MODE::plane, LR = MODE::lr, LOW = MODE::low;
     extern __shared__ float lds[];
     const int BS = c.BS, C = c.C, H2 = BS / 2;
     const int s = c.s0 + blockIdx.x, tid = threadIdx.x;
@@ -1663,7 +1652,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
     const DsynLds L = dsyn_lds(BS, 0, 0);
     float2 *z = (float2 *)lds;
     SynWave sw;
-    sw.pre  = (int *)(lds + L.zFloats) + wv * (64 + low_pwords(low_arg(sa...), BS));
+    sw.pre  = (int *)(lds + L.zFloats) + wv * (64 + syn_pwords(mode, BS));
     sw.seedTab = (uint32_t *)(sw.pre + 64);
     sw.lane = lane;
 #ifdef ULCX_DSYN_STAMPS
@@ -1675,7 +1664,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
     uint32_t seed = c.seed[s];
     float *scr = c.scratch + (size_t)s * 4 * BS;                     // staging: dst[2][BS] | dec[BS] | tmpq[BS/2]
     int kBeg = 0, rowSkip = 0, rowLen = 0;
-    if constexpr (SAMP) { rowSkip = samp.skip[s]; rowLen = samp.len[s]; }
+    if constexpr (SAMP) { rowSkip = mode.s.skip[s]; rowLen = mode.s.len[s]; }
     if constexpr (RANGE) {
         // a range call (k_dsyn): the stream is entered from nothing - zero lapping state, the index's generator state -, and
         // row 0, the block in front of the range, runs without output when there is one
@@ -1692,7 +1681,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
         const size_t oblk = RANGE ? (size_t)s * (c.K - 1) + (warm ? 0 : k - 1) : (size_t)blk;
         OUT *outp = out_base<OUT>(c) + oblk * C * BS;
         SampBlk<OUT> sb;
-        if constexpr (SAMP) sb = samp_blk<OUT>(out_base<OUT>(c), C, BS, samp.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
+        if constexpr (SAMP) sb = samp_blk<OUT>(out_base<OUT>(c), C, BS, mode.s.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
         if constexpr (RANGE) { if (!warm && tid == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; }
         if (dead) {
             if constexpr (SAMP) { if (!warm) sb.zero(C, tid); }
@@ -1725,7 +1714,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, SA... sa) {
                     if (pat & 8) ov >>= (wc & 7);
                     if (ov > last) ov = last;
                     last = S;
-                    if constexpr (PLANE) plane_unit((float *)z, plane_of(pla, s, C, ch, c.K, k, BS) + dpos, S, tid, WG);   // the unit from the caller's plane
+                    if constexpr (PLANE) plane_unit((float *)z, mode.unit(s, C, ch, c.K, k, BS) + dpos, S, tid, WG);   // the unit from the caller's plane
                     else {
                     for (int i = tid; i < Mp; i += WG) z[i] = make_float2(0.0f, 0.0f);
                     __syncthreads();
@@ -2087,42 +2076,44 @@ size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS) {
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { ulcx_set_error("%s: %s", #x, hipGetErrorString(e_)); return ULCX_ERR_HIP; } } while (0)
 
-// The synthesis instantiation of a context, THE one place that maps a geometry to its kernel: what is launched, what has
-// its dynamic-LDS limit raised and what is asked for its occupancy are this pointer.
-// (SA: UlcxSampArg for the sample-crop store mode - the kernel then takes that further argument -, else empty)
-template <typename OUT, bool SPLIT, bool RANGE, typename... SA>
-static const void *syn_pick(const UlcxDecCtx &cc) {
+// The synthesis instantiation of a context in a mode, THE one place that maps a geometry to its kernel: what is launched, what has its
+// dynamic-LDS limit raised and what is asked for its occupancy are this pointer, typed by the mode it takes.  (fastOK means stereo up to BlockSize
+// 4096: with DSYN_C4096 the run-time BlockSize kernel of 32 trips does not exist.  A cut of a plain call is k_dsyn's alone: no k_dgen<SynCut> either.)
+template <typename OUT, typename MODE> using SynFn = void (*)(UlcxDecCtx, MODE);
+template <typename OUT, typename MODE> static SynFn<OUT, MODE> syn_pick(const UlcxDecCtx &cc) {
     constexpr bool TW = DSYN_TWL != 0;
-    if (!cc.fastOK) return (const void *)k_dgen<OUT, RANGE, SA...>;
-    if (cc.BS == 2048 && DSYN_C2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 2048, RANGE, SA...>;
-    if (cc.BS <= 2048) return (const void *)k_dsyn<OUT, 16, TW, SPLIT, 0, RANGE, SA...>;
-    if (cc.BS == 4096 && DSYN_C4096) return (const void *)k_dsyn<OUT, 32, false, SPLIT, 4096, RANGE, SA...>;
-    return (const void *)k_dsyn<OUT, 32, false, SPLIT, 0, RANGE, SA...>;
+    if (!cc.fastOK) { if constexpr (MODE::split && !MODE::range) return nullptr; else return k_dgen<OUT, MODE>; }
+    if (cc.BS == 2048 && DSYN_C2048) return k_dsyn<OUT, 16, TW, 2048, MODE>;
+    if (cc.BS <= 2048) return k_dsyn<OUT, 16, TW, 0, MODE>;
+    if constexpr (DSYN_C4096) return k_dsyn<OUT, 32, false, 4096, MODE>;
+    else return k_dsyn<OUT, 32, false, 0, MODE>;
 }
-// split: the grid is a cut of the (stream, block) pairs; range: a range call, which runs the cut form for every grid;
-// samp: a sample-crop call, a range call in the sample store mode; plane: a synth call, that mode with the plane source
-// (1: the planes hold the coded mid/side, 2: left/right)
-// low: a low-rate call, that mode with the low-rate source (cc: the context of the REDUCED geometry)
-template <typename OUT>
-static const void *syn_fn(const UlcxDecCtx &cc, bool split, bool range, bool samp = false, int plane = 0, bool low = false) {
-    return low ? syn_pick<OUT, true, true, UlcxSampArg, UlcxLowArg>(cc)
-         : plane == 2 ? syn_pick<OUT, true, true, UlcxSampArg, UlcxPlaneArg<true>>(cc)
-         : plane ? syn_pick<OUT, true, true, UlcxSampArg, UlcxPlaneArg<false>>(cc)
-         : samp ? syn_pick<OUT, true, true, UlcxSampArg>(cc)
-         : range ? syn_pick<OUT, true, true>(cc) : split ? syn_pick<OUT, true, false>(cc) : syn_pick<OUT, false, false>(cc);
+// a synthesis kind as its mode type: f(MODE{})
+template <typename F> static auto syn_with_mode(UlcxSynKind kind, F &&f) {
+    switch (kind) {
+    case ULCX_SYN_CUT:       return f(SynCut{});
+    case ULCX_SYN_RANGE:     return f(SynRange{});
+    case ULCX_SYN_SAMPLES:   return f(SynSamples{});
+    case ULCX_SYN_PLANES:    return f(SynPlanes<false>{});
+    case ULCX_SYN_PLANES_LR: return f(SynPlanes<true>{});
+    case ULCX_SYN_LOW:       return f(SynLow{});
+    default:                 return f(SynWhole{});
+    }
 }
 // A launch with more than 48 KiB of dynamic LDS: raise the kernel's limit to this launch's size (ulcx_enc.hip: allow_lds).
 static hipError_t allow_lds(const void *fn, size_t lds) {
     return lds > 48 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
 }
 
-// resident workgroups of the stereo synthesis kernel this context runs: what an even cut of the batch is sized for
-// (walkBS > 0: of the low-rate source instantiations - c the context of the reduced geometry, walkBS the walk's BlockSize)
-int ulcx_dec_syn_slots(const UlcxDecCtx &c, int walkBS) {
+template <typename OUT> static const void *syn_fn(const UlcxDecCtx &cc, UlcxSynKind kind) {       // (ULCX_SYN_LOW: cc the context of the REDUCED geometry)
+    return syn_with_mode(kind, [&](auto m) { return (const void *)syn_pick<OUT, decltype(m)>(cc); });
+}
+// resident workgroups of the stereo synthesis kernel this context runs in a mode: what an even cut of the batch is sized for
+// (ULCX_SYN_LOW: c the context of the reduced geometry, walkBS the walk's BlockSize)
+int ulcx_dec_syn_slots(const UlcxDecCtx &c, UlcxSynKind kind, int walkBS) {
     if (!c.fastOK) return 0;
     // what a cut would launch: the float and the PCM16 instantiation are both asked, the smaller residency sizes the cut
-    const bool low = walkBS > 0;
-    const void *fns[2] = { syn_fn<float>(c, true, low, low, 0, low), syn_fn<int16_t>(c, true, low, low, 0, low) };
+    const void *fns[2] = { syn_fn<float>(c, kind), syn_fn<int16_t>(c, kind) };
     const size_t lds = ulcx_dec_lds_bytes(c.BS, c.fastOK, c.twInLds, walkBS);
     int dev = 0, cus = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
@@ -2134,63 +2125,74 @@ int ulcx_dec_syn_slots(const UlcxDecCtx &c, int walkBS) {
     return cus * per;
 }
 
+// A mode's fields from the call's aux data (walkBS: the BlockSize the walk ran at) and the launch of the instantiation that mode
+// picks for the context: the argument is built as the type the kernel takes.
+template <typename OUT, typename MODE>
+static int syn_launch(const UlcxDecCtx &cs, const UlcxDecAux &aux, int walkBS, unsigned grid, size_t lds, hipStream_t st) {
+    MODE m = {};
+    if constexpr (MODE::samp) m.s = UlcxSampArg{ aux.samp.skip, aux.samp.lenC, aux.samp.nSamples };
+    if constexpr (MODE::plane) { m.coef = aux.syn.coef; m.nPl = aux.syn.planes; }
+    if constexpr (MODE::low) m.BSw = walkBS;
+    const SynFn<OUT, MODE> fn = syn_pick<OUT, MODE>(cs);
+    if (!fn) { ulcx_set_error("synthesis: no kernel of this mode for %d channels of BlockSize %d", cs.C, cs.BS); return ULCX_ERR_ARG; }
+    CK(allow_lds((const void *)fn, lds));
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(WG), lds, st, cs, m);
+    return ULCX_OK;
+}
 // Two kernels on the caller's stream: the syntax walk, then the synthesis.  (Measured and dropped, profiles/NOTES_r01-r04.md:
 // the walk of a chunk of streams / of the second half of the blocks beside the synthesis of the previous one - the
-// synthesis slows down by more than the walk it hides.)
+// synthesis slows down by more than the walk it hides.)  What the two are follows from aux.kind alone.
 int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux) {
     int stage = 0;
     if (ev) CK(hipEventRecord(ev[stage++], st));
+    const UlcxDecKind kind = aux.kind; const bool range = kind != ULCX_DEC_PLAIN, low = kind == ULCX_DEC_LOWRATE;
     UlcxDecCtx c = cIn;
-    c.s0 = 0; c.s1 = c.B; c.k0 = c.range ? 1 : 0; c.k1 = c.K;
+    c.s0 = 0; c.s1 = c.B; c.k0 = range ? 1 : 0; c.k1 = c.K;
     // a low-rate call: the walk runs on c, the file's geometry; the rows and the synthesis on cs, the context of BlockSize >> lgD -
     // its tables, its kernel pick and its lapping scratch - which still addresses the walk's per-block rows and records
-    const bool low = aux.lowLgD > 0;
     UlcxDecCtx cs = c;
     if (low) {
-        cs.BS = c.BS >> aux.lowLgD; cs.lgBS = c.lgBS - aux.lowLgD; cs.T = aux.lowT; cs.fastOK = aux.lowFast; cs.twInLds = aux.lowTwInLds;
-        cs.lapScratch = aux.lowLapScratch;
+        cs.BS = c.BS >> aux.low.lgD; cs.lgBS = c.lgBS - aux.low.lgD; cs.T = aux.low.T; cs.fastOK = aux.low.fast; cs.twInLds = aux.low.twInLds;
+        cs.lapScratch = aux.low.lapScratch;
     }
-    const size_t lds = ulcx_dec_lds_bytes(cs.BS, cs.fastOK, cs.twInLds, low ? c.BS : 0);
-    const bool split = cs.fastOK && aux.synGrid > 0;
-    const bool samp = aux.sampStart != nullptr;                       // a sample-crop call: rows from (start, len) first, then the crop walk on them
-    const bool spec = aux.specCoef != nullptr;                        // a spectra call: the crop walk, then k_dspec in place of the synthesis
-    const bool dist = aux.distOut != nullptr;                         // a distortion call: the crop walk, then k_ddist in place of the synthesis
-    const int plane = aux.synCoef ? (aux.synLR ? 2 : 1) : 0;          // a synth call: k_synth_rows in place of every walk, then the plane source synthesis
-    const void *syn = (spec || dist) ? nullptr : c.pcm16 ? syn_fn<int16_t>(cs, split, c.range != 0, samp, plane, low) : syn_fn<float>(cs, split, c.range != 0, samp, plane, low);
-    if (syn) CK(allow_lds(syn, lds));
-    if (plane) hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)(((long long)c.B * c.K + 63) / 64)), dim3(64), 0, st, c.B, c.K, aux.synPlanes, aux.synWc,
-                                  c.wcScan, c.draws, c.bits, c.rInfo, aux.sampSkip, aux.sampLenC, aux.nSamples);
+    // the rows (sample crops: from (start, len); a synth call: from the window codes, in place of every walk), then the walk: indexed over a
+    // crop call's corpus or, for a range call, over the decoder's own streams as a strided corpus (file = stream)
+    if (kind == ULCX_DEC_SYNTH) hipLaunchKernelGGL(k_synth_rows, dim3((unsigned)(((long long)c.B * c.K + 63) / 64)), dim3(64), 0, st, c.B, c.K, aux.syn.planes, aux.syn.wc,
+                                                   c.wcScan, c.draws, c.bits, c.rInfo, aux.samp.skip, aux.samp.lenC, aux.samp.nSamples);
     else {
-    if (samp) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, cs.BS, aux.nSamples, aux.sampStart, aux.sampLen,
-                                 aux.sampFirst, aux.sampCount, aux.sampSkip, aux.sampLenC);
-    // the indexed walk: over a crop call's corpus, or for a range call over the decoder's own streams as a strided corpus (file = stream)
-    if (aux.corpus.nFiles > 0) hipLaunchKernelGGL(k_dscan_rows, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.corpus, aux.cropFile, aux.cropCount);
-    else if (c.range) hipLaunchKernelGGL(k_dscan_rows, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c,
+    if (kind == ULCX_DEC_SAMPLES || low) hipLaunchKernelGGL(k_crop_sample_rows, dim3((c.B + 63) / 64), dim3(64), 0, st, c.B, cs.BS, aux.samp.nSamples, aux.samp.start,
+                                                            aux.samp.len, aux.samp.first, aux.samp.count, aux.samp.skip, aux.samp.lenC);
+    if (ulcx_dec_has_corpus(kind)) hipLaunchKernelGGL(k_dscan_rows, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c, aux.corpus, aux.cropFile, aux.cropCount);
+    else if (kind == ULCX_DEC_RANGE) hipLaunchKernelGGL(k_dscan_rows, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c,
                                          ulcx_corpus_strided(c.B, c.in, c.payStride, c.payBytes, c.rIndex, c.rIndexStride, c.rIndexBlocks), nullptr, nullptr);
     else if (c.packed) hipLaunchKernelGGL(k_dscan_packed, dim3((c.B + 63) / 64), dim3(64), 0, st, c);
     else hipLaunchKernelGGL(k_dscan, dim3((c.B * c.K + 63) / 64), dim3(64), 0, st, c);
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));
-    if (spec || dist) {
-        const void *fn = dist ? (aux.specLR ? (const void *)k_ddist<true> : (const void *)k_ddist<false>)
-                              : (aux.specLR ? (const void *)k_dspec<true> : (const void *)k_dspec<false>);
+    if (!ulcx_dec_has_synthesis(kind)) {
+        const bool dist = kind == ULCX_DEC_DISTORTION;
+        const void *fn = dist ? (aux.spec.lr ? (const void *)k_ddist<true> : (const void *)k_ddist<false>)
+                              : (aux.spec.lr ? (const void *)k_dspec<true> : (const void *)k_dspec<false>);
         const size_t slds = ulcx_spec_lds_bytes(c.BS);
         const int nPairs = (c.C + 1) / 2;
         const long long g = (long long)c.B * (c.K - 1) * nPairs;
         if (g > 0x7FFFFFFFLL) { ulcx_set_error("%s call: %lld workgroups", dist ? "distortion" : "spectra", g); return ULCX_ERR_ARG; }
         CK(allow_lds(fn, slds));
-        UlcxSpecArg sp = { aux.specCoef, aux.specWc, nPairs };
-        UlcxDistArg da = { aux.distRef, aux.distNRef, aux.distRefBlocks, aux.distRefRow, aux.distRefFirst, aux.distSeg, aux.distOut, aux.specWc, nPairs };
+        UlcxSpecArg sp = { aux.spec.coef, aux.spec.wc, nPairs };
+        UlcxDistArg da = { aux.dist.ref, aux.dist.nRef, aux.dist.refBlocks, aux.dist.refRow, aux.dist.refFirst, aux.dist.seg, aux.dist.out, aux.spec.wc, nPairs };
         void *args[] = { &c, dist ? (void *)&da : (void *)&sp };
         CK(hipLaunchKernel(fn, dim3((unsigned)g), dim3(WG), args, slds, st));
     } else if (!(ULCX_DBG(c) & 8)) {
+        const bool split = cs.fastOK && aux.synGrid > 0;
+        const UlcxSynKind syn = low ? ULCX_SYN_LOW : kind == ULCX_DEC_SYNTH ? (aux.syn.lr ? ULCX_SYN_PLANES_LR : ULCX_SYN_PLANES)
+                              : kind == ULCX_DEC_SAMPLES ? ULCX_SYN_SAMPLES : range ? ULCX_SYN_RANGE : split ? ULCX_SYN_CUT : ULCX_SYN_WHOLE;
+        const size_t lds = ulcx_dec_lds_bytes(cs.BS, cs.fastOK, cs.twInLds, low ? c.BS : 0);
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
-        cs.synFull = split ? aux.synFull : (c.range && cs.fastOK) ? c.B : 0;      // (a range call without a cut: every workgroup one whole stream)
-        UlcxSampArg sa = { aux.sampSkip, aux.sampLenC, aux.nSamples };
-        UlcxPlaneArg<false> pa = { aux.synCoef, aux.synPlanes };     // (one layout for both LR settings)
-        UlcxLowArg la = { c.BS };
-        void *args[] = { &cs, &sa, low ? (void *)&la : (void *)&pa };   // (the second one: the sample-store instantiations only; the third: the plane source's or the low-rate source's)
-        CK(hipLaunchKernel(syn, dim3(g), dim3(WG), args, lds, st));
+        cs.synFull = split ? aux.synFull : (range && cs.fastOK) ? c.B : 0;        // (a range call without a cut: every workgroup one whole stream)
+        const int rc = syn_with_mode(syn, [&](auto m) {
+            return c.pcm16 ? syn_launch<int16_t, decltype(m)>(cs, aux, c.BS, g, lds, st) : syn_launch<float, decltype(m)>(cs, aux, c.BS, g, lds, st);
+        });
+        if (rc) return rc;
     }
     if (ev) CK(hipEventRecord(ev[stage++], st));
     CK(hipGetLastError());

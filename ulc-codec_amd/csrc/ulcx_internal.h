@@ -264,48 +264,47 @@ static inline UlcxCorpus ulcx_corpus_ragged(int nFiles, const uint8_t *pay, long
 // row.  (The kernels' file view and the host forms' row checks both call this.)
 __host__ __device__ static inline long long ulcx_row_blocks(long long nI, long long entries) { return nI < 0 ? 0 : nI > entries - 1 ? entries - 1 : nI; }
 
+// What kind of call a decode launch serves: set where the API layer knows it, read by dec_launch (ulcx_api.cpp) and ulcx_dec_launch.
+// Everything from RANGE on is a range launch (c.range = 1): rows entered from nothing through a block index.
+enum UlcxDecKind {
+    ULCX_DEC_PLAIN,                      // slots or packed payloads, from and to the streams' state: no aux field is looked at
+    ULCX_DEC_RANGE,                      // ulcx_decode_range_*: the decoder's own streams as a strided corpus (file = stream), c.rIndex* / c.rFirst
+    ULCX_DEC_CROPS,                      // ulcx_decode_crops_*: c.B rows that each name a file of `corpus`, found by the indexed walk (k_dscan_rows)
+    ULCX_DEC_SAMPLES,                    // ulcx_decode_crops_samples_*: crops whose rows come from `samp`; the synthesis stores by sample (SynSamples)
+    ULCX_DEC_LOWRATE,                    // ulcx_decode_crops_lowrate_*: that, with the rows and the synthesis at the geometry of `low` (SynLow)
+    ULCX_DEC_SPECTRA,                    // ulcx_decode_crops_spectra_*: the crop walk, then k_dspec in place of the synthesis (`spec`; c.pcm / c.pcm16 both NULL)
+    ULCX_DEC_DISTORTION,                 // ulcx_decode_crops_distortion_*: the crop walk, then k_ddist on the same grid (`dist`, with spec.wc / spec.lr)
+    ULCX_DEC_SYNTH                       // ulcx_synth_spectra_*: no walk at all; k_synth_rows, then the synthesis from the planes of `syn` (SynPlanes); c.in is not looked at
+};
+static inline bool ulcx_dec_has_corpus(UlcxDecKind k) { return k >= ULCX_DEC_CROPS && k <= ULCX_DEC_DISTORTION; }
+static inline bool ulcx_dec_has_synthesis(UlcxDecKind k) { return k != ULCX_DEC_SPECTRA && k != ULCX_DEC_DISTORTION; }
+// What a call's launch needs beside its UlcxDecCtx: the kind, the plan of the synthesis grid, and per kind the fields named above
 struct UlcxDecAux {
-    int synGrid;                         // > 0: workgroups of the synthesis over a cut of the (stream, block) pairs; 0: one per stream
-    int synFull;                         // of those, the leading ones that take one whole stream each (0: an even cut of everything)
-    // crop calls (ulcx_decode_crops_*): corpus.nFiles > 0 - c.B rows that each name a file of the corpus, found by the indexed
-    // walk (k_dscan_rows) as a range call's streams are; c.rFirst and these two describe the rows.  c.payStride, c.payBytes and
-    // c.rIndex* are not looked at.
+    UlcxDecKind kind = ULCX_DEC_PLAIN;
+    int synGrid = 0;                     // > 0: workgroups of the synthesis over a cut of the (stream, block) pairs; 0: one per stream
+    int synFull = 0;                     // of those, the leading ones that take one whole stream each (0: an even cut of everything)
+    // kinds with a corpus (CROPS .. DISTORTION): c.rFirst and these describe the rows; c.payStride, c.payBytes and c.rIndex* are not looked at
     UlcxCorpus corpus = {};
     const int32_t *cropFile = nullptr;   // [c.B] file of each row
     const int32_t *cropCount = nullptr;  // [c.B] leading blocks wanted of each row, or NULL: all of them
-    // sample crops (ulcx_decode_crops_samples_*): sampStart != NULL - k_crop_sample_rows first turns the caller's (start, len) rows
-    // into the decoder-owned arrays below ([nStreams] each); c.rFirst is sampFirst and cropCount is sampCount, so the crop walk
-    // runs on them as on a caller's, and the synthesis is the sample-store instantiation, which takes sampSkip / sampLenC / nSamples
-    const int64_t *sampStart = nullptr;  // [c.B] first sample of each row in its file's decoded stream
-    const int32_t *sampLen = nullptr;    // [c.B] samples wanted of each row, or NULL: nSamples
-    int nSamples = 0;                    // samples per plane of the output
-    int32_t *sampFirst = nullptr, *sampCount = nullptr, *sampSkip = nullptr, *sampLenC = nullptr;
-    // spectra (ulcx_decode_crops_spectra_*): specCoef != NULL - behind the crop walk k_dspec runs in place of the synthesis, one
-    // workgroup per (row, block, channel pair); synGrid / synFull are not looked at, c.pcm / c.pcm16 are both NULL
-    float *specCoef = nullptr;           // [c.B][C][c.K - 1][BS] dequantised coefficients, channels-first
-    int32_t *specWc = nullptr;           // [c.B][c.K - 1] window codes (0: the block is not live)
-    int specLR = 0;                      // channel pairs as m + s, m - s
-    // distortion (ulcx_decode_crops_distortion_*): distOut != NULL - k_ddist in place of k_dspec, on the same grid: the sums of the
-    // coefficients against the caller's reference planes instead of the coefficients; specCoef is NULL, specWc and specLR as above
-    double *distOut = nullptr;           // [c.B][C][c.K - 1][distSeg][3] {S, Y, E}
-    const float *distRef = nullptr;      // [distNRef][C][distRefBlocks][BS] reference planes, or NULL: none
-    int distNRef = 0, distRefBlocks = 0, distSeg = 0;
-    const int32_t *distRefRow = nullptr, *distRefFirst = nullptr;       // [c.B] optional, untrusted: the reference row / first reference block of each row
-    // synthesis from spectra (ulcx_synth_spectra_*): synCoef != NULL - no walk at all; k_synth_rows turns the caller's window codes
-    // into the per-block rows a range synthesis reads (and sampSkip / sampLenC; nSamples = the output blocks x BlockSize), and the
-    // synthesis is the sample-store instantiation with the plane source.  nFiles is 0, c.in is not looked at.
-    const float *synCoef = nullptr;      // [c.B][C][synPlanes][BS] the caller's planes
-    const int32_t *synWc = nullptr;      // [c.B][synPlanes] their window codes (untrusted)
-    int synPlanes = 0;                   // planes per row: c.K with the plane in front (ULCX_SYNTH_WARM), else c.K - 1
-    int synLR = 0;                       // the planes hold left/right: no un-mix
-    // low-rate sample crops (ulcx_decode_crops_lowrate_*): lowLgD > 0 (with sampStart) - the walk at the object's BlockSize, then
-    // the rows and the synthesis at BlockSize >> lowLgD with the low-rate source: what of that geometry's context differs from the
-    // object's (the rest of it - the per-block rows, the records, their strides - stays the walk's); synGrid / synFull are
-    // planned for THAT kernel
-    int lowLgD = 0;
-    UlcxTables lowT = {};
-    int lowFast = 0, lowTwInLds = 0;
-    float *lowLapScratch = nullptr;      // [cut workgroups][C][(BS >> lowLgD) / 2]
+    // k_crop_sample_rows first turns the caller's (start, len) rows into the decoder-owned arrays ([nStreams] each): c.rFirst is `first`
+    // and cropCount is `count`, so the crop walk runs on them as on a caller's, and the synthesis clips its stores by skip / lenC /
+    // nSamples.  (SYNTH: k_synth_rows writes skip / lenC; nSamples = the output blocks x BlockSize.)
+    // start, len: [c.B] first sample of each row in its file's decoded stream; samples wanted of it, or NULL: nSamples, the samples per plane of the output
+    struct Samp { const int64_t *start; const int32_t *len; int nSamples; int32_t *first, *count, *skip, *lenC; } samp = {};
+    struct Spec { float *coef; int32_t *wc; int lr; } spec = {};   // [c.B][C][c.K - 1][BS] dequantised coefficients, channels-first; [c.B][c.K - 1] window codes (0: not live); pairs as m + s, m - s
+    struct Dist {                        // the sums of the coefficients against the caller's reference planes instead of the coefficients
+        double *out;                     // [c.B][C][c.K - 1][seg][3] {S, Y, E}
+        const float *ref;                // [nRef][C][refBlocks][BS] reference planes, or NULL: none
+        int nRef, refBlocks, seg; const int32_t *refRow, *refFirst;     // [c.B] optional, untrusted: the reference row / first reference block of each row
+    } dist = {};
+    struct Syn {                         // k_synth_rows turns the window codes into the per-block rows a range synthesis reads
+        const float *coef; const int32_t *wc;           // [c.B][C][planes][BS] the caller's planes; [c.B][planes] their window codes (untrusted)
+        int planes, lr;                  // planes per row: c.K with the plane in front (ULCX_SYNTH_WARM), else c.K - 1; lr: they hold left/right, no un-mix
+    } syn = {};
+    // what of the context of BlockSize >> lgD differs from the object's (the rest of it - the per-block rows, the records, their
+    // strides - stays the walk's); synGrid / synFull are planned for THAT kernel
+    struct Low { int lgD; UlcxTables T; int fast, twInLds; float *lapScratch; } low = {};      // lapScratch [cut workgroups][C][(BS >> lgD) / 2]
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
@@ -329,7 +328,8 @@ int ulcx_splice_launch(const UlcxDecCtx &c, const UlcxSpliceArgs &a, hipStream_t
 size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS = 0);   // listBS: the BlockSize the per-wave lists are sized by (0: BS)
 size_t ulcx_spec_lds_bytes(int BS);               // k_dspec's / k_ddist's dynamic LDS: two unit arrays where a CU holds them, else one
 int ulcx_spec_arrays(int BS);                     // how many that is (1: ULCX_SPECTRA_LR cannot be formed on chip by k_ddist)
-int ulcx_dec_syn_slots(const UlcxDecCtx &c, int walkBS = 0);   // resident workgroups of the stereo synthesis kernel on the current device (walkBS > 0: of its low-rate source form)
+enum UlcxSynKind { ULCX_SYN_WHOLE, ULCX_SYN_CUT, ULCX_SYN_RANGE, ULCX_SYN_SAMPLES, ULCX_SYN_PLANES, ULCX_SYN_PLANES_LR, ULCX_SYN_LOW };   // the synthesis modes (ulcx_dec.hip: SynWhole .. SynLow)
+int ulcx_dec_syn_slots(const UlcxDecCtx &c, UlcxSynKind kind, int walkBS = 0);   // resident workgroups of that mode's stereo synthesis kernel on the current device (ULCX_SYN_LOW: walkBS, the walk's BlockSize)
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);
 // clips (ulcx_clips.hip): the kernels around the launch sequence of ulcx_encode_clips_* - the shadow state of n rows to the state
