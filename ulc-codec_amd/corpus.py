@@ -562,7 +562,7 @@ class CropCorpus:
             segments.append(row)
         return self.splice(dec, segments)[0]
 
-    def sample_crops(self, dec, files, start, n_samples, length=None, pcm16=False, lowrate=0):
+    def sample_crops(self, dec, files, start, n_samples, length=None, pcm16=False, lowrate=0, part=None):
         """Row i: n_samples samples from sample start[i] of the decoded stream of file files[i] (its leading length[i] when
         `length` is given; zeros behind, and behind the file's end), written channels-first by the synthesis itself
         (ulcx_decode_crops_samples_dev): no gather, no transpose.  start: int64; files / length: int32; tensors on the corpus's
@@ -573,10 +573,29 @@ class CropCorpus:
         lowrate = 1, 2, 3: the crop at 1/2, 1/4, 1/8 of the file's rate straight from the synthesis (ulcx_decode_crops_lowrate_dev):
         start, length and n_samples count samples of the reduced stream - blocks of BlockSize >> lowrate, reduced sample m at
         full-rate time D m + (D - 1) / 2 with D = 1 << lowrate - and crop_blocks is that of the reduced BlockSize.  0: the
-        full-rate call, untouched."""
+        full-rate call, untouched.
+        part = "mid" / "side": one coded channel of every pair, as it stands in front of the decoder's un-mix
+        (ulcx_decode_crops_part_dev; at any lowrate, 0 included) -> pcm [n][part_channels][n_samples]: plane j is coded channel 2 j
+        (mid; an unpaired last channel is the last plane) or 2 j + 1 (side).  The mid of a stereo file is its mono downmix
+        (L + R) / 2 as the file codes it - equal to the folded stereo decode up to the un-mix's two float32 roundings, not bit for
+        bit.  None: the paths above, untouched."""
         import torch
         sfx, corpus = self._ready(dec)._view()
         n, files, start, want = self._rows(files, start, length, pos_dtype=torch.int64)
+        if part is not None:
+            if part not in ("mid", "side"):
+                raise ValueError(f"part {part!r}: 'mid', 'side' or None")
+            which = ulc_amd.PART_MID if part == "mid" else ulc_amd.PART_SIDE
+            planes, bs = ulc_amd.part_channels(self.C, which), ulc_amd.lowrate_block(self.BS, lowrate)
+            if not planes:
+                raise ValueError(f"part {part!r}: {self.C} channel(s) have no side")
+            if not bs:
+                raise ValueError(f"lowrate {lowrate}: 0 .. 3 with BlockSize {self.BS} >> lowrate >= 256")
+            pcm = torch.empty((n, planes, n_samples), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
+            bits = torch.empty((n, ulc_amd.crop_blocks(bs, n_samples)), dtype=torch.int32, device=self.device)
+            getattr(dec, f"decode_crops_part{sfx}_dev")(*corpus, n, files.data_ptr(), start.data_ptr(), _ptr(want), n_samples, int(lowrate), which, pcm.data_ptr(),
+                                                        bits.data_ptr(), stream=torch.cuda.current_stream(self.device).cuda_stream, pcm16=pcm16)
+            return pcm, bits
         pcm = torch.empty((n, self.C, n_samples), dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
         if lowrate:
             bs = ulc_amd.lowrate_block(self.BS, lowrate)

@@ -13,6 +13,7 @@
 #include <vector>
 #include "ulcx_internal.h"
 #include "../../include/ulc_amd_lowrate.h"
+#include "../../include/ulc_amd_part.h"
 #include "ulcx_enc_dev.h"                 // (WaveCaps, WAVE_S*, wavecaps_lds: ulcx_encoder_debug_writer_plan)
 #include "ulcx_rng_tables.h"
 
@@ -1419,7 +1420,8 @@ static int dec_launch(ulcx_decoder *e, UlcxDecCtx &c, hipStream_t st, int *subse
     const int Kc = range ? c.K - 1 : c.K;                         // blocks of the call per stream (a range call's K counts the row of the block in front)
     // (a low-rate call: the cut is planned for the kernel of the reduced geometry - its residency, its scratch rows)
     const int synSlots = low ? e->low[a.low.lgD].synSlots : e->synSlots, scratchRows = low ? e->low[a.low.lgD].scratchRows : e->scratchRows;
-    if ((low || e->splitOK) && synSlots > 0 && ulcx_dec_has_synthesis(a.kind)) {  // (a spectra or distortion call has no synthesis to cut: the plain plan)
+    // (a spectra or distortion call has no synthesis to cut, and a part call's - k_dpart or k_dgen - runs one workgroup per row: the plain plan)
+    if ((low || e->splitOK) && synSlots > 0 && ulcx_dec_has_synthesis(a.kind) && a.kind != ULCX_DEC_PART) {
         // A range call of more streams than the device holds at once: whole rounds, and the last one cut
         // (ulcx_dec_range_tail_plan) - an even cut of everything ends every workgroup inside a stream, and in a range call every
         // entry into a stream costs the block in front of the range (ULCX_RANGE_CUT=even: the even cut first, as for other calls)
@@ -2078,7 +2080,8 @@ static int crops_checks(const char *who, const ulcx_decoder *e, const UlcxCorpus
 }
 // the rows of a sample-crop call (ulcx_decode_crops_samples_*): d_first / d_count are not given, nBlocks is ulcx_crop_blocks(nSamples)
 // (lgD > 0: a low-rate call, ulcx_decode_crops_lowrate_* - the rows count samples of the stream reduced by 1 << lgD)
-struct CropsSamples { const int64_t *start; const int32_t *len; int nSamples; int lgD; };
+// (part >= 0: a part call, ulcx_decode_crops_part_* - the output has ulcx_part_channels planes per row; else -1)
+struct CropsSamples { const int64_t *start; const int32_t *len; int nSamples; int lgD; int part; };
 // the outputs of a spectra call (ulcx_decode_crops_spectra_*) beside d_bits: coefficients instead of samples, and the window codes
 struct CropsSpectra { float *coef; int32_t *wc; int flags; };
 static int spectra_flags_bad(const char *who, int flags) {
@@ -2129,7 +2132,7 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &
     c.packed = 1; c.range = 1; c.rFirst = d_first;
     c.lap = e->subLap[0]; c.lastSub = e->subLastSub[0]; c.seed = e->subSeed[0]; c.dead = e->subDead[0]; c.packOff = e->subPackOff;
     UlcxDecAux crop = {};
-    crop.kind = dist ? ULCX_DEC_DISTORTION : spec ? ULCX_DEC_SPECTRA : !samp ? ULCX_DEC_CROPS : samp->lgD > 0 ? ULCX_DEC_LOWRATE : ULCX_DEC_SAMPLES;
+    crop.kind = dist ? ULCX_DEC_DISTORTION : spec ? ULCX_DEC_SPECTRA : !samp ? ULCX_DEC_CROPS : samp->part >= 0 ? ULCX_DEC_PART : samp->lgD > 0 ? ULCX_DEC_LOWRATE : ULCX_DEC_SAMPLES;
     crop.corpus = g; crop.cropFile = d_file; crop.cropCount = d_count;
     if (samp) {
         crop.samp = { samp->start, samp->len, samp->nSamples, e->sampRows, e->sampRows + e->B, e->sampRows + 2 * (size_t)e->B, e->sampRows + 3 * (size_t)e->B };
@@ -2137,6 +2140,12 @@ static int decode_crops_any(const char *who, ulcx_decoder *e, const UlcxCorpus &
         if (samp->lgD > 0) {
             const UlcxDecLow &l = e->low[samp->lgD];
             crop.low = { samp->lgD, l.T, l.fastOK, l.twInLds, l.lapScratch };
+        }
+        if (samp->part >= 0) {
+            // at full rate the object's own tables and pick serve; no cut: the lapping state is the rows' own shadow rows
+            if (samp->lgD == 0) crop.low = { 0, e->ctx.T, e->ctx.fastOK, e->ctx.twInLds, nullptr };
+            crop.low.lapScratch = nullptr;
+            crop.part = { samp->part, ulcx_part_channels(e->C, samp->part) };
         }
     }
     if (spec) crop.spec = { spec->coef, spec->wc, (spec->flags & ULCX_SPECTRA_LR) ? 1 : 0 };
@@ -2384,11 +2393,11 @@ static int samples_blocks(const char *who, const ulcx_decoder *e, int nSamples, 
     return nB;
 }
 static int crops_samples_dev_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len,
-                                 int nSamples, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, int lgD = 0) {
+                                 int nSamples, float *d_pcm, int16_t *d_pcm16, int32_t *d_bits, void *hipStream, int lgD = 0, int part = -1) {
     if (lowrate_bad(who, e, lgD)) return ULCX_ERR_ARG;
     const int nB = samples_blocks(who, e, nSamples, lgD);
     if (!nB) return ULCX_ERR_ARG;
-    const CropsSamples sm = { d_start, d_len, nSamples, lgD };
+    const CropsSamples sm = { d_start, d_len, nSamples, lgD, part };
     return decode_crops_any(who, e, g, n, d_file, nullptr, nullptr, nB, d_pcm, d_pcm16, d_bits, hipStream, &sm);
 }
 extern "C" int ulcx_decode_crops_samples_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
@@ -2427,23 +2436,24 @@ static int sample_row_bad(const char *who, int i, int BS, long long nI, long lon
 }
 // the rows of a host form up, its output buffers, and after the call the results down: [n][nChan][nSamples] samples, [n][nB] sizes
 struct SampleStage { int32_t *file = nullptr, *len = nullptr, *bits = nullptr; int64_t *start = nullptr; float *pcm = nullptr; };
-static int sample_rows_up(DevTmp &t, const ulcx_decoder *e, int n, int nB, int nSamples, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, SampleStage *g) {
+// (planes: the planes of an output row - nChan, or a part call's ulcx_part_channels)
+static int sample_rows_up(DevTmp &t, int planes, int n, int nB, int nSamples, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, SampleStage *g) {
     CKR(t.get(&g->file, sizeof(int32_t) * n)); CKR(t.get(&g->start, sizeof(int64_t) * n));
-    CKR(t.get(&g->pcm, sizeof(float) * (size_t)n * e->C * (size_t)nSamples)); CKR(t.get(&g->bits, sizeof(int32_t) * (size_t)n * nB));
+    CKR(t.get(&g->pcm, sizeof(float) * (size_t)n * planes * (size_t)nSamples)); CKR(t.get(&g->bits, sizeof(int32_t) * (size_t)n * nB));
     CKR(hipMemcpy(g->file, h_file, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     CKR(hipMemcpy(g->start, h_start, sizeof(int64_t) * n, hipMemcpyHostToDevice));
     if (h_len) { CKR(t.get(&g->len, sizeof(int32_t) * n)); CKR(hipMemcpy(g->len, h_len, sizeof(int32_t) * n, hipMemcpyHostToDevice)); }
     return ULCX_OK;
 }
-static int sample_results_down(const ulcx_decoder *e, const SampleStage &g, int n, int nB, int nSamples, float *h_pcm, int32_t *h_bits) {
+static int sample_results_down(int planes, const SampleStage &g, int n, int nB, int nSamples, float *h_pcm, int32_t *h_bits) {
     CKR(hipDeviceSynchronize());
-    CKR(hipMemcpy(h_pcm, g.pcm, sizeof(float) * (size_t)n * e->C * (size_t)nSamples, hipMemcpyDeviceToHost));
+    CKR(hipMemcpy(h_pcm, g.pcm, sizeof(float) * (size_t)n * planes * (size_t)nSamples, hipMemcpyDeviceToHost));
     CKR(hipMemcpy(h_bits, g.bits, sizeof(int32_t) * (size_t)n * nB, hipMemcpyDeviceToHost));
     return ULCX_OK;
 }
 // the host forms, either layout
 static int crops_samples_host_any(const char *who, ulcx_decoder *e, const UlcxCorpus &g, int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len,
-                                  int nSamples, float *h_pcm, int32_t *h_bits, int lgD = 0) {
+                                  int nSamples, float *h_pcm, int32_t *h_bits, int lgD = 0, int part = -1) {
     if (lowrate_bad(who, e, lgD)) return ULCX_ERR_ARG;
     const int nB = samples_blocks(who, e, nSamples, lgD);
     if (!nB) return ULCX_ERR_ARG;
@@ -2456,12 +2466,13 @@ static int crops_samples_host_any(const char *who, ulcx_decoder *e, const UlcxCo
     }
     CKR(hipSetDevice(e->device));
     DevTmp t; UlcxCorpus d; SampleStage sg;
+    const int planes = part >= 0 ? ulcx_part_channels(e->C, part) : e->C;
     int rc = corpus_up(t, g, &d);
-    if (!rc) rc = sample_rows_up(t, e, n, nB, nSamples, h_file, h_start, h_len, &sg);
+    if (!rc) rc = sample_rows_up(t, planes, n, nB, nSamples, h_file, h_start, h_len, &sg);
     if (rc) return rc;
-    const CropsSamples sm = { sg.start, sg.len, nSamples, lgD };
+    const CropsSamples sm = { sg.start, sg.len, nSamples, lgD, part };
     rc = decode_crops_any(who, e, d, n, sg.file, nullptr, nullptr, nB, sg.pcm, nullptr, sg.bits, nullptr, &sm);
-    return rc ? rc : sample_results_down(e, sg, n, nB, nSamples, h_pcm, h_bits);
+    return rc ? rc : sample_results_down(planes, sg, n, nB, nSamples, h_pcm, h_bits);
 }
 extern "C" int ulcx_decode_crops_samples_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
                                               const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
@@ -2519,6 +2530,72 @@ extern "C" int ulcx_decode_crops_lowrate_ragged_host(ulcx_decoder *e, int nFiles
                                                      float *h_pcm, int32_t *h_bits) {
     return crops_samples_host_any("ulcx_decode_crops_lowrate_ragged_host", e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
                                   n, h_file, h_start, h_len, nSamples, h_pcm, h_bits, lgD);
+}
+// ---- mid and side crops (include/ulc_amd_part.h): the low-rate bodies with one further argument - the coded channels part, part + 2, ...
+// of every row, each as it stands in front of the un-mix, into (nChan + 1 - part) / 2 planes
+extern "C" int ulcx_part_channels(int nChan, int part) {
+    if (nChan < 1 || nChan > 255 || part < ULCX_PART_MID || part > ULCX_PART_SIDE) return 0;
+    return (nChan + 1 - part) / 2;
+}
+// part of a part entry: refused outside 0 .. 1, or where the object's channels have no such part (the side of a mono corpus)
+static int part_bad(const char *who, const ulcx_decoder *e, int part) {
+    if (part < ULCX_PART_MID || part > ULCX_PART_SIDE) { refuse(who, "bad argument (part %d: ULCX_PART_MID or ULCX_PART_SIDE)", part); return 1; }
+    if (e && !ulcx_part_channels(e->C, part)) { refuse(who, "bad argument (part %d: %d channel(s) have no side)", part, e->C); return 1; }
+    return 0;
+}
+extern "C" int ulcx_decode_crops_part_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                          const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                          int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD, int part,
+                                          float *d_pcm, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_part_dev";
+    if (part_bad(who, e, part)) return ULCX_ERR_ARG;
+    return crops_samples_dev_any(who, e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, d_pcm, nullptr, d_bits, hipStream, lgD, part);
+}
+extern "C" int ulcx_decode_crops_part_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadStride, const int32_t *d_payloadBytes,
+                                                const ulcx_index_entry *d_index, int indexStride, const int32_t *d_indexBlocks,
+                                                int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD, int part,
+                                                int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_part_dev_pcm16";
+    if (part_bad(who, e, part)) return ULCX_ERR_ARG;
+    return crops_samples_dev_any(who, e, ulcx_corpus_strided(nFiles, d_payload, payloadStride, d_payloadBytes, d_index, indexStride, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, nullptr, d_pcm16, d_bits, hipStream, lgD, part);
+}
+extern "C" int ulcx_decode_crops_part_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadStride, const int32_t *h_payloadBytes,
+                                           const ulcx_index_entry *h_index, int indexStride, const int32_t *h_indexBlocks,
+                                           int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples, int lgD, int part,
+                                           float *h_pcm, int32_t *h_bits) {
+    const char *who = "ulcx_decode_crops_part_host";
+    if (part_bad(who, e, part)) return ULCX_ERR_ARG;
+    return crops_samples_host_any(who, e, ulcx_corpus_strided(nFiles, h_payload, payloadStride, h_payloadBytes, h_index, indexStride, h_indexBlocks),
+                                  n, h_file, h_start, h_len, nSamples, h_pcm, h_bits, lgD, part);
+}
+extern "C" int ulcx_decode_crops_part_ragged_dev(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                 const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                 int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD, int part,
+                                                 float *d_pcm, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_part_ragged_dev";
+    if (part_bad(who, e, part)) return ULCX_ERR_ARG;
+    return crops_samples_dev_any(who, e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, d_pcm, nullptr, d_bits, hipStream, lgD, part);
+}
+extern "C" int ulcx_decode_crops_part_ragged_dev_pcm16(ulcx_decoder *e, int nFiles, const uint8_t *d_payload, long long payloadTotal, const int64_t *d_payloadOffs,
+                                                       const ulcx_index_entry *d_index, long long indexTotal, const int64_t *d_indexOffs, const int32_t *d_indexBlocks,
+                                                       int n, const int32_t *d_file, const int64_t *d_start, const int32_t *d_len, int nSamples, int lgD, int part,
+                                                       int16_t *d_pcm16, int32_t *d_bits, void *hipStream) {
+    const char *who = "ulcx_decode_crops_part_ragged_dev_pcm16";
+    if (part_bad(who, e, part)) return ULCX_ERR_ARG;
+    return crops_samples_dev_any(who, e, ulcx_corpus_ragged(nFiles, d_payload, payloadTotal, d_payloadOffs, d_index, indexTotal, d_indexOffs, d_indexBlocks),
+                                 n, d_file, d_start, d_len, nSamples, nullptr, d_pcm16, d_bits, hipStream, lgD, part);
+}
+extern "C" int ulcx_decode_crops_part_ragged_host(ulcx_decoder *e, int nFiles, const uint8_t *h_payload, long long payloadTotal, const int64_t *h_payloadOffs,
+                                                  const ulcx_index_entry *h_index, long long indexTotal, const int64_t *h_indexOffs, const int32_t *h_indexBlocks,
+                                                  int n, const int32_t *h_file, const int64_t *h_start, const int32_t *h_len, int nSamples, int lgD, int part,
+                                                  float *h_pcm, int32_t *h_bits) {
+    const char *who = "ulcx_decode_crops_part_ragged_host";
+    if (part_bad(who, e, part)) return ULCX_ERR_ARG;
+    return crops_samples_host_any(who, e, ulcx_corpus_ragged(nFiles, h_payload, payloadTotal, h_payloadOffs, h_index, indexTotal, h_indexOffs, h_indexBlocks),
+                                  n, h_file, h_start, h_len, nSamples, h_pcm, h_bits, lgD, part);
 }
 // ---- synthesis from spectra (include/ulc_amd.h section 3): the decoder's inverse transform on caller-held planes.  The range
 // synthesis of a crop call without any walk in front: the call runs on the shadow state as the crop calls do (dec_shadow; nothing

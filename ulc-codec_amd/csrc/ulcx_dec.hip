@@ -1105,7 +1105,9 @@ __global__ __launch_bounds__(64) void k_crop_sample_rows(int n, int BS, int nSam
 //   samp   the sample store mode: s, the rows' clips
 //   plane  the plane source mode (no records, no generator): unit(), where a unit's coefficients lie;  lr: the planes hold left/right
 //   low    the low-rate source mode (the records clipped to the reduced units): pwords(), the sign-parity words of the walk's BlockSize
-#define SYN_MODE(SPLIT, RANGE, SAMP, PLANE, LR_, LOW) static constexpr bool split = SPLIT, range = RANGE, samp = SAMP, plane = PLANE, lr = LR_, low = LOW
+//   part   one coded channel per pair (ulcx_decode_crops_part_*, SynPart): the low-rate source mode over the coded channels part, part + 2, ...
+//          alone, each stored as it stands - no un-mix - into plane ch >> 1 of nOut (k_dgen, or k_dpart for stereo: syn_pick; never k_dsyn)
+#define SYN_MODE(SPLIT, RANGE, SAMP, PLANE, LR_, LOW) static constexpr bool split = SPLIT, range = RANGE, samp = SAMP, plane = PLANE, lr = LR_, low = LOW, part = false
 struct SynWhole   { SYN_MODE(false, false, false, false, false, false); };       // one workgroup per stream, from and to the stream's state
 struct SynCut     { SYN_MODE(true,  false, false, false, false, false); };       // the same call over a cut
 struct SynRange   { SYN_MODE(true,  true,  false, false, false, false); };       // range and crop calls
@@ -1116,10 +1118,12 @@ template <bool LR_> struct SynPlanes {
 };
 struct SynLow { SYN_MODE(true, true, true, false, false, true); UlcxSampArg s; int BSw; __device__ __forceinline__ int pwords() const { return DSYN_PWORDS(BSw); } };
 #undef SYN_MODE
+struct SynPart : SynLow { static constexpr bool part = true; int which, nOut; };   // which: ULCX_PART_MID / ULCX_PART_SIDE; nOut: the planes of a row
 template <typename MODE> __device__ __forceinline__ int syn_pwords(const MODE &m, int BS) { if constexpr (MODE::low) return m.pwords(); else return DSYN_PWORDS(BS); }
 // a range call enters streams as a cut does; sample crops are range launches; both sources store samples
 template <typename M> constexpr bool syn_mode_ok = (!M::range || M::split) && (!M::samp || M::range) && (!M::plane || M::samp) && (!M::lr || M::plane) && (!M::low || (M::samp && !M::plane));
 static_assert(syn_mode_ok<SynWhole> && syn_mode_ok<SynCut> && syn_mode_ok<SynRange> && syn_mode_ok<SynSamples> && syn_mode_ok<SynPlanes<false>> && syn_mode_ok<SynPlanes<true>> && syn_mode_ok<SynLow>);
+static_assert(syn_mode_ok<SynPart> && SynPart::low && SynPart::part && !SynLow::part);
 // the fields behind the sample clips lie where a further kernel argument of their own would: the kernels' argument loads do not move
 static_assert(sizeof(SynSamples) == sizeof(UlcxSampArg) && offsetof(SynPlanes<true>, coef) == sizeof(UlcxSampArg) && offsetof(SynLow, BSw) == sizeof(UlcxSampArg));
 // S coefficients at src (16-byte aligned, read once) into the padded array A; thread t0 of `step`.  DPS 4: four floats at a
@@ -1158,10 +1162,12 @@ struct DsynLds { int zFloats, twFloats, listFloats; };
 // twInLds: the stereo kernel's FFT twiddles resident in LDS (BlockSize <= 2048; above it they are read from the tables in
 // global memory, L1/L2-hot: a fourth workgroup per CU).  The lapping state is in global memory for every geometry.
 // listBS: the BlockSize the per-wave lists are sized by (the low-rate source mode: the walk's; 0: BS)
-__host__ __device__ static inline DsynLds dsyn_lds(int BS, int fast, int twInLds, int listBS = 0) {
+// oneWave: the one-wave kernel of a stereo part call (k_dpart): z [1 array] | twl as the stereo kernel's | one wave's lists
+__host__ __device__ static inline DsynLds dsyn_lds(int BS, int fast, int twInLds, int listBS = 0, int oneWave = 0) {
     DsynLds l;
-    l.zFloats = (fast ? 2 : 1) * 2 * FFT_PADDEDS(BS / 2, DPS);
+    l.zFloats = (fast && !oneWave ? 2 : 1) * 2 * FFT_PADDEDS(BS / 2, DPS);
     l.twFloats = (fast && BS <= 2048 && twInLds) ? BS / 2 : 0;
+    if (fast && oneWave) { l.listFloats = 64 + DSYN_PWORDS(listBS ? listBS : BS); return l; }
     l.listFloats = 2 * (64 + DSYN_PWORDS(listBS ? listBS : BS)) + 128;             // per wave: prefix counts, sign-parity stream; per workgroup: 128 block / channel RNG states
     if (fast) l.listFloats += 2 * (DSYN_CHUNK + 4) * 8;          // stereo kernel: the headers of a chunk of blocks + of a decimated block's four units, per channel
     return l;
@@ -1644,9 +1650,12 @@ __global__ __launch_bounds__(WG, 3) void k_dsyn(UlcxDecCtx c, MODE mode) {
 // MODE: the synthesis mode, as k_dsyn's; one workgroup per stream whatever its `split` says.
 template <typename OUT, typename MODE>
 __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, MODE mode) {
-    constexpr bool RANGE = MODE::range, SAMP = MODE::samp, PLANE = MODE::plane, LR = MODE::lr, LOW = MODE::low;
+    constexpr bool RANGE = MODE::range, SAMP = MODE::samp, PLANE = MODE::plane, LR = MODE::lr, LOW = MODE::low, PART = MODE::part;
     extern __shared__ float lds[];
     const int BS = c.BS, C = c.C, H2 = BS / 2;
+    // PART: the coded channels ch0, ch0 + 2, ... alone, channel ch into plane ch >> 1 of CO; the records, draws and the lapping rows stay indexed by ch
+    int ch0 = 0, chStep = 1, CO = C;
+    if constexpr (PART) { ch0 = mode.which; chStep = 2; CO = mode.nOut; }
     const int s = c.s0 + blockIdx.x, tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const DsynLds L = dsyn_lds(BS, 0, 0);
@@ -1681,10 +1690,10 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, MODE mode) {
         const size_t oblk = RANGE ? (size_t)s * (c.K - 1) + (warm ? 0 : k - 1) : (size_t)blk;
         OUT *outp = out_base<OUT>(c) + oblk * C * BS;
         SampBlk<OUT> sb;
-        if constexpr (SAMP) sb = samp_blk<OUT>(out_base<OUT>(c), C, BS, mode.s.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
+        if constexpr (SAMP) sb = samp_blk<OUT>(out_base<OUT>(c), PART ? CO : C, BS, mode.s.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
         if constexpr (RANGE) { if (!warm && tid == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk]; }
         if (dead) {
-            if constexpr (SAMP) { if (!warm) sb.zero(C, tid); }
+            if constexpr (SAMP) { if (!warm) sb.zero(PART ? CO : C, tid); }
             else
             if (!warm) for (int i = tid; i < C * BS; i += WG) st1(outp + i, 0.0f);
             if (tid == 0) c.bits[blk] = 0;
@@ -1702,7 +1711,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, MODE mode) {
         {
             float *dec = scr + 2 * BS, *tmpq = scr + 3 * BS;
             int newLast = lastSub;
-            for (int ch = 0; ch < C; ch++) {
+            for (int ch = PART ? ch0 : 0; ch < C; ch += PART ? chStep : 1) {
                 int last = lastSub;                                  // ulcDecoder.c:219
                 float *dst = scr + (size_t)(ch & 1) * BS;
                 float *Lp = glap + (size_t)ch * H2;
@@ -1783,11 +1792,11 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, MODE mode) {
                 } while (pat >>= 4);
                 newLast = last;
                 // inverse M/S + interleave once both members of a pair (or a trailing single) are staged
-                const bool pairDone = LR || (ch & 1) || (ch == C - 1);   // (LR: every channel goes out as it stands)
+                const bool pairDone = LR || PART || (ch & 1) || (ch == C - 1);   // (LR, PART: every channel goes out as it stands)
                 if (pairDone) {
                     __syncthreads();
                     if (warm) {
-                    } else if (!LR && (ch & 1)) {
+                    } else if (!LR && !PART && (ch & 1)) {
                         const float *dm = scr, *ds = scr + BS;
                         for (int n = tid; n < BS; n += WG) {
                             const float m = dm[n], sd = ds[n];                            // ulcDecoder.c:281-289
@@ -1797,7 +1806,7 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, MODE mode) {
                             else { st1(outp + (size_t)n * C + ch - 1, l); st1(outp + (size_t)n * C + ch, r); }
                         }
                     } else {
-                        for (int n = tid; n < BS; n += WG) { if constexpr (SAMP) sb.one(sb.plane(ch), n, dst[n]); else st1(outp + (size_t)n * C + ch, dst[n]); }
+                        for (int n = tid; n < BS; n += WG) { if constexpr (SAMP) sb.one(sb.plane(PART ? ch >> 1 : ch), n, dst[n]); else st1(outp + (size_t)n * C + ch, dst[n]); }
                     }
                     __syncthreads();
                 }
@@ -1807,6 +1816,175 @@ __global__ __launch_bounds__(WG) void k_dgen(UlcxDecCtx c, MODE mode) {
         if constexpr (!PLANE) seed = rng_jump(c.jumpT, seed, (uint32_t)c.draws[blk]);      // the one RNG chain of the stream (ulcDecoder.c:75-81)
     }
     if (tid == 0) { c.lastSub[s] = lastSub; c.seed[s] = seed; c.dead[s] = dead; }
+}
+
+// ---------------------------------------------------------------------------
+// Mid / side crops of stereo rows (ulcx_decode_crops_part_*; reduced BlockSize <= 4096): one workgroup = ONE wave = one row, one
+// coded channel.  Where k_dsyn spends two waves, two FFT arrays and the barriers between them on a block, a row here costs one wave
+// and one padded array; nothing waits for another wave.  The pieces are k_dsyn's per-wave ones - synth_unit<LOW> on the walk's
+// records (SynLow's clip; lgD 0: the whole unit), the in-place pre-twiddle, fft_wave_dif / fft_wave_dif_ct, dec_time_wave for a
+// decimated block - and the un-decimated epilogue for one channel by one wave: post-twiddle fused with the windowed overlap
+// (lap_pair: orc_imdct's products in orc_imdct's order), the pending half rewritten in place, the stores through SampBlk, no un-mix.
+// No cut: the grid is the rows, a row is entered as a range is - zero lapping state, the index's generator state, the block in front
+// run without output - and its workgroup walks its blocks in order.  The state at the side channel's units is the block's state
+// jumped over unitDraws[4 + j]: every draw of the mid channel lies in front of it.  The lapping state is the row's own half-row
+// of the shadow state, in global memory (L2-hot: re-read by the wave that wrote it one block earlier).
+// DEC_MAXT, TWL, BSC: as k_dsyn's, for the reduced geometry.
+// DPART_WAVES: waves per SIMD the registers are capped for.  3 (168 registers; 0 .. 84 bytes of scratch): what the LDS of a launch
+// allows at BlockSize 2048 - 13.3 KB per one-wave workgroup, 12 per CU.  4 (128 registers) spills 120 .. 212 bytes; without a cap the
+// kernel takes 198 .. 257 registers, two waves per SIMD or one (profiles/part_kregs.txt).
+// ---------------------------------------------------------------------------
+#ifndef DPART_WAVES
+#define DPART_WAVES 3
+#endif
+#define DPART_WG 64              // threads of a workgroup: the kernel's launch bound and, in syn_launch, its launch
+template <typename OUT, int DEC_MAXT, bool TWL, int BSC>
+__global__ __launch_bounds__(DPART_WG, DPART_WAVES) void k_dpart(UlcxDecCtx c, SynPart mode) {
+    extern __shared__ float lds[];
+    const int BS = BSC ? BSC : c.BS, H2 = BS / 2;
+    constexpr int C = 2;
+    const int s = blockIdx.x, ch = mode.which;
+    const int lane = threadIdx.x;
+    const DsynLds L = dsyn_lds(BS, 1, TWL, mode.BSw, 1);
+    float2 *z = (float2 *)lds;
+    float2 *twl = (float2 *)(lds + L.zFloats);
+    SynWave sw;
+    sw.pre = (int *)(lds + L.zFloats + L.twFloats);
+    sw.seedTab = (uint32_t *)(sw.pre + 64);
+    sw.lane = lane;
+#ifdef ULCX_DSYN_STAMPS
+    sw.stp = nullptr;
+#endif
+    if (TWL) for (int i = lane; i < BS / 4; i += 64) twl[i] = c.T.tw[0][i];
+    bool twFull = true;
+    const int M0 = BS >> 1;
+    float *Lp = c.lap + ((size_t)s * C + ch) * H2;               // the pending half of this row's channel: time -1 - i at Lp[i]
+    const int2 ri = c.rInfo[s];
+    uint32_t seed = (uint32_t)ri.y;
+    int lastSub = 0, dead = 0;
+    const int rowSkip = mode.s.skip[s], rowLen = mode.s.len[s];
+    for (int i = lane; i < H2; i += 64) Lp[i] = 0.0f;
+    __syncthreads();
+    for (int k = 1 - ri.x; k < c.K; k++) {
+        const int blk = s * c.K + k;
+        const int wc = c.wcScan[blk];
+        if (wc == 0) dead = 1;                                       // a corrupt block ends the row (ulcDecodeTool.c:154-157)
+        const bool warm = k == 0;
+        const size_t oblk = (size_t)s * (c.K - 1) + (warm ? 0 : k - 1);
+        const SampBlk<OUT> sb = samp_blk<OUT>(out_base<OUT>(c), mode.nOut, BS, mode.s.nSamples, s, warm ? 0 : k - 1, rowSkip, rowLen);
+        OUT *sp = sb.plane(0);
+        const bool sal = sb.pairs(sp);
+        if (!warm && lane == 0) c.bitsOut[oblk] = dead ? 0 : c.bits[blk];
+        if (dead) {
+            if (!warm) for (int m = sb.mLo + lane; m < sb.mHi; m += 64) st1(sb.at(sp, m), 0.0f);
+            if (lane == 0) c.bits[blk] = 0;
+            continue;
+        }
+        const int *udraw = c.unitDraws + (size_t)blk * C * 4 + ch * 4;
+        const int4 *urec = c.unitRec + (size_t)blk * C * 4 + ch * 4;
+        const float4 *utail = c.unitTail + (size_t)blk * C * 4 + ch * 4;
+        const uint2 *prec = c.prec + (size_t)blk * c.precStride, *nrec = c.nrec + (size_t)blk * c.nrecStride;
+        const float *tmag = c.tailMag + ((size_t)blk * C * 4 + ch * 4) * c.tailStride;
+        const int blkDraws = c.draws[blk];
+        const int chEnd = (ch + 1 < C) ? c.unitDraws[(size_t)blk * C * 4 + (ch + 1) * 4] : blkDraws;      // draws of the block up to the end of this channel
+        const BlockShape shape = block_shape(BS, wc);
+        const unsigned pat0 = shape.pat;
+        const bool whole = shape.whole;
+        const int nsub = shape.nsub;
+        if (TWL && whole != twFull) {
+            // twiddle tables for this block's transform sizes: the full-size one, or those of N/2, N/4, N/8 back to back (k_dsyn)
+            if (whole) for (int i = lane; i < BS / 4; i += 64) twl[i] = c.T.tw[0][i];
+            else for (int i = lane; i < 7 * BS / 32; i += 64) {
+                const int dd = i < BS / 8 ? 1 : i < 3 * BS / 16 ? 2 : 3;
+                twl[i] = c.T.tw[dd][i - (dd == 1 ? 0 : dd == 2 ? BS / 8 : 3 * BS / 16)];
+            }
+            twFull = whole;
+            WAVE_SYNC();
+        }
+        // ---- coefficients -> spectra, subblock by subblock
+        {
+            unsigned pat = pat0; int off = 0;
+            for (int j = 0; j < nsub; j++, pat >>= 4) {
+                const int d = pat & 7, S = BS >> d, M = S >> 1, Mp = FFT_PADDEDS(M, DPS);
+                float2 *zj = z + FFT_PADS(off >> 1, DPS);
+                sw.A = (float *)zj;
+                const int dj = udraw[j], dn = (j + 1 < nsub) ? udraw[j + 1] : chEnd;
+                const uint32_t unitSeed = rng_jump(c.jumpT, seed, (uint32_t)dj);
+                synth_unit<true>(c, sw, S, prec, nrec, urec[j], unitSeed, dn - dj, utail[j].y, tmag + (size_t)j * c.tailStride, Mp);
+                // DCT-IV pre-twiddle in place: n and M-1-n together read and write the same two complex slots
+                const float2 *pre = c.T.pre[d];
+#pragma unroll
+                for (int n = lane; n < M / 2; n += 64) {
+                    const int n2 = M - 1 - n;
+                    const int pn = FFT_PADS(n, DPS), pn2 = FFT_PADS(n2, DPS);
+                    const float2 a = zj[pn], b = zj[pn2];            // (X[2n], X[2n+1]), (X[S-2-2n], X[S-1-2n])
+                    zj[pn]  = cmulc(make_float2(a.x, b.y), pre[n]);
+                    zj[pn2] = cmulc(make_float2(b.x, a.y), pre[n2]);
+                }
+                if constexpr (!TWL) { if (M == 1024) fft_wave_dif_ct<1024, DPS>(zj, c.T.tw[d], lane); else fft_wave_dif(zj, M, c.T.tw[d], lane, DPS); }
+                else if (M == 1024) fft_wave_dif_ct<1024, DPS>(zj, twl, lane);
+                else fft_wave_dif(zj, M, twl + (d <= 1 ? 0 : d == 2 ? BS / 8 : 3 * BS / 16), lane, DPS);
+                off += S;
+            }
+        }
+        if (whole) {
+            // ---- un-decimated block: post-twiddle fused with the windowed overlap (oracle/orc_fourier.c orc_imdct), one channel, no un-mix.
+            //      Every pending element is read and rewritten by the same lane.
+            int ov = BS;                                             // ulcDecoder.c:234-239
+            if (pat0 & 8) ov >>= (wc & 7);
+            if (ov > lastSub) ov = lastSub;
+            const int S = BS, M = M0;
+            const float2 *pre = c.T.pre[0];
+            const int a = (S - ov) >> 1;
+            const float *fall = c.T.winFall + ov, *rise = c.T.winRise + ov;
+            const int bits = 31 - __clz(M);
+#pragma unroll 4
+            for (int kk = lane; kk < M / 2; kk += 64) {
+                const int k1 = kk, k2 = M - 1 - kk;
+                const int r1 = FFT_PADS((int)(__brev((unsigned)k1) >> (32 - bits)), DPS);
+                const int r2 = FFT_PADS((int)(__brev((unsigned)k2) >> (32 - bits)), DPS);
+                const float2 y1 = cmulc_post(z[r1], pre[k1]), y2 = cmulc_post(z[r2], pre[k2]);      // (Re y, -Im y)
+                if (!warm) {
+                    const float2 Ap = *(const float2 *)(Lp + 2 * k1);
+                    const float Av[2] = { Ap.x, Ap.y }, Bv[2] = { y1.y, y2.x };
+                    const int   pv[2] = { M - 1 - 2 * k1, M - 2 - 2 * k1 };
+                    LapPair r[2];
+#pragma unroll
+                    for (int q = 0; q < 2; q++) {
+                        const int p = pv[q];
+                        const bool pass = p < a;
+                        float cw = 0.0f, sn = 0.0f;
+                        if (!pass) { cw = fall[p - a]; sn = rise[p - a]; }
+                        r[q] = lap_pair(Av[q], Bv[q], cw, sn, pass);                                // outputs at positions p and S-1-p
+                    }
+                    // positions pv[1] = pv[0]-1 and S-1-pv[0], S-pv[0] are neighbours
+                    sb.two(sp, sal, pv[1], r[1].lo, r[0].lo);
+                    sb.two(sp, sal, S - 1 - pv[0], r[0].hi, r[1].hi);
+                }
+                *(float2 *)(Lp + 2 * k1) = make_float2(y1.x, y2.y);
+            }
+            lastSub = BS;
+        } else {
+            // ---- decimated block: the time domain on one timeline (dec_time_wave), the pending list in place; other lanes read what this
+            //      lane's last block left in global memory: ordered by the barriers
+            __syncthreads();
+            const int newLast = dec_time_wave<DEC_MAXT>(c, z, Lp, wc, pat0, nsub, lastSub, lane);
+            __syncthreads();
+            // output = times [-BS/2, BS/2): the old pending list (time -1-i at Lp[i]), then the array
+            const float *t0 = (const float *)z;
+            if (!warm) {
+                for (int n = 2 * lane; n < H2; n += 128) sb.two(sp, sal, n, Lp[H2 - 1 - n], Lp[H2 - 2 - n]);
+                for (int n = 2 * lane; n < H2; n += 128) { const float2 m = *(const float2 *)(t0 + padf(n)); sb.two(sp, sal, H2 + n, m.x, m.y); }
+            }
+            __syncthreads();
+            // new pending list: times [BS/2, BS) of the array
+            for (int i = lane; i < H2; i += 64) Lp[H2 - 1 - i] = t0[padf(H2 + i)];
+            lastSub = newLast;
+        }
+        __syncthreads();                                             // (one wave: the order of this block's LDS and global accesses against the next block's)
+        seed = rng_jump(c.jumpT, seed, (uint32_t)blkDraws);          // the one RNG chain of the stream (ulcDecoder.c:75-81)
+    }
+    if (lane == 0) { c.lastSub[s] = lastSub; c.seed[s] = seed; c.dead[s] = dead; }
 }
 
 // ---------------------------------------------------------------------------
@@ -2069,8 +2247,8 @@ size_t ulcx_spec_lds_bytes(int BS) {
 }
 int ulcx_spec_arrays(int BS) { return spec_lds(BS).nArr; }
 
-size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS) {
-    DsynLds l = dsyn_lds(BS, fast, twInLds, listBS);
+size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS, int oneWave) {
+    DsynLds l = dsyn_lds(BS, fast, twInLds, listBS, oneWave);
     return sizeof(float) * ((size_t)l.zFloats + l.twFloats + l.listFloats);
 }
 
@@ -2082,11 +2260,18 @@ size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS) {
 template <typename OUT, typename MODE> using SynFn = void (*)(UlcxDecCtx, MODE);
 template <typename OUT, typename MODE> static SynFn<OUT, MODE> syn_pick(const UlcxDecCtx &cc) {
     constexpr bool TW = DSYN_TWL != 0;
+    if constexpr (MODE::part) {                                     // stereo up to BlockSize 4096: one wave per row (k_dpart)
+        if (!cc.fastOK) return k_dgen<OUT, MODE>;
+        if (cc.BS == 2048) return k_dpart<OUT, 16, TW, 2048>;
+        if (cc.BS < 2048) return k_dpart<OUT, 16, TW, 0>;
+        return k_dpart<OUT, 32, false, 4096>;
+    } else {
     if (!cc.fastOK) { if constexpr (MODE::split && !MODE::range) return nullptr; else return k_dgen<OUT, MODE>; }
     if (cc.BS == 2048 && DSYN_C2048) return k_dsyn<OUT, 16, TW, 2048, MODE>;
     if (cc.BS <= 2048) return k_dsyn<OUT, 16, TW, 0, MODE>;
     if constexpr (DSYN_C4096) return k_dsyn<OUT, 32, false, 4096, MODE>;
     else return k_dsyn<OUT, 32, false, 0, MODE>;
+    }
 }
 // a synthesis kind as its mode type: f(MODE{})
 template <typename F> static auto syn_with_mode(UlcxSynKind kind, F &&f) {
@@ -2097,6 +2282,7 @@ template <typename F> static auto syn_with_mode(UlcxSynKind kind, F &&f) {
     case ULCX_SYN_PLANES:    return f(SynPlanes<false>{});
     case ULCX_SYN_PLANES_LR: return f(SynPlanes<true>{});
     case ULCX_SYN_LOW:       return f(SynLow{});
+    case ULCX_SYN_PART:      return f(SynPart{});
     default:                 return f(SynWhole{});
     }
 }
@@ -2133,10 +2319,13 @@ static int syn_launch(const UlcxDecCtx &cs, const UlcxDecAux &aux, int walkBS, u
     if constexpr (MODE::samp) m.s = UlcxSampArg{ aux.samp.skip, aux.samp.lenC, aux.samp.nSamples };
     if constexpr (MODE::plane) { m.coef = aux.syn.coef; m.nPl = aux.syn.planes; }
     if constexpr (MODE::low) m.BSw = walkBS;
+    if constexpr (MODE::part) { m.which = aux.part.which; m.nOut = aux.part.planes; }
     const SynFn<OUT, MODE> fn = syn_pick<OUT, MODE>(cs);
     if (!fn) { ulcx_set_error("synthesis: no kernel of this mode for %d channels of BlockSize %d", cs.C, cs.BS); return ULCX_ERR_ARG; }
     CK(allow_lds((const void *)fn, lds));
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(WG), lds, st, cs, m);
+    unsigned threads = WG;                                       // by the kernel that was picked: every instantiation of k_dpart is one wave
+    if constexpr (MODE::part) { if (fn != k_dgen<OUT, MODE>) threads = DPART_WG; }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, st, cs, m);
     return ULCX_OK;
 }
 // Two kernels on the caller's stream: the syntax walk, then the synthesis.  (Measured and dropped, profiles/NOTES_r01-r04.md:
@@ -2145,7 +2334,7 @@ static int syn_launch(const UlcxDecCtx &cs, const UlcxDecAux &aux, int walkBS, u
 int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux) {
     int stage = 0;
     if (ev) CK(hipEventRecord(ev[stage++], st));
-    const UlcxDecKind kind = aux.kind; const bool range = kind != ULCX_DEC_PLAIN, low = kind == ULCX_DEC_LOWRATE;
+    const UlcxDecKind kind = aux.kind; const bool range = kind != ULCX_DEC_PLAIN, part = kind == ULCX_DEC_PART, low = kind == ULCX_DEC_LOWRATE || part;
     UlcxDecCtx c = cIn;
     c.s0 = 0; c.s1 = c.B; c.k0 = range ? 1 : 0; c.k1 = c.K;
     // a low-rate call: the walk runs on c, the file's geometry; the rows and the synthesis on cs, the context of BlockSize >> lgD -
@@ -2183,10 +2372,10 @@ int ulcx_dec_launch(const UlcxDecCtx &cIn, hipStream_t st, hipEvent_t *ev, const
         void *args[] = { &c, dist ? (void *)&da : (void *)&sp };
         CK(hipLaunchKernel(fn, dim3((unsigned)g), dim3(WG), args, slds, st));
     } else if (!(ULCX_DBG(c) & 8)) {
-        const bool split = cs.fastOK && aux.synGrid > 0;
-        const UlcxSynKind syn = low ? ULCX_SYN_LOW : kind == ULCX_DEC_SYNTH ? (aux.syn.lr ? ULCX_SYN_PLANES_LR : ULCX_SYN_PLANES)
+        const bool split = cs.fastOK && aux.synGrid > 0 && !part;
+        const UlcxSynKind syn = part ? ULCX_SYN_PART : low ? ULCX_SYN_LOW : kind == ULCX_DEC_SYNTH ? (aux.syn.lr ? ULCX_SYN_PLANES_LR : ULCX_SYN_PLANES)
                               : kind == ULCX_DEC_SAMPLES ? ULCX_SYN_SAMPLES : range ? ULCX_SYN_RANGE : split ? ULCX_SYN_CUT : ULCX_SYN_WHOLE;
-        const size_t lds = ulcx_dec_lds_bytes(cs.BS, cs.fastOK, cs.twInLds, low ? c.BS : 0);
+        const size_t lds = ulcx_dec_lds_bytes(cs.BS, cs.fastOK, cs.twInLds, low ? c.BS : 0, part ? 1 : 0);
         const unsigned g = split ? (unsigned)aux.synGrid : (unsigned)c.B;
         cs.synFull = split ? aux.synFull : (range && cs.fastOK) ? c.B : 0;        // (a range call without a cut: every workgroup one whole stream)
         const int rc = syn_with_mode(syn, [&](auto m) {

@@ -272,6 +272,7 @@ enum UlcxDecKind {
     ULCX_DEC_CROPS,                      // ulcx_decode_crops_*: c.B rows that each name a file of `corpus`, found by the indexed walk (k_dscan_rows)
     ULCX_DEC_SAMPLES,                    // ulcx_decode_crops_samples_*: crops whose rows come from `samp`; the synthesis stores by sample (SynSamples)
     ULCX_DEC_LOWRATE,                    // ulcx_decode_crops_lowrate_*: that, with the rows and the synthesis at the geometry of `low` (SynLow)
+    ULCX_DEC_PART,                       // ulcx_decode_crops_part_*: that (lgD 0 included), over every other coded channel and without the un-mix (`part`, SynPart)
     ULCX_DEC_SPECTRA,                    // ulcx_decode_crops_spectra_*: the crop walk, then k_dspec in place of the synthesis (`spec`; c.pcm / c.pcm16 both NULL)
     ULCX_DEC_DISTORTION,                 // ulcx_decode_crops_distortion_*: the crop walk, then k_ddist on the same grid (`dist`, with spec.wc / spec.lr)
     ULCX_DEC_SYNTH                       // ulcx_synth_spectra_*: no walk at all; k_synth_rows, then the synthesis from the planes of `syn` (SynPlanes); c.in is not looked at
@@ -305,6 +306,7 @@ struct UlcxDecAux {
     // what of the context of BlockSize >> lgD differs from the object's (the rest of it - the per-block rows, the records, their
     // strides - stays the walk's); synGrid / synFull are planned for THAT kernel
     struct Low { int lgD; UlcxTables T; int fast, twInLds; float *lapScratch; } low = {};      // lapScratch [cut workgroups][C][(BS >> lgD) / 2]
+    struct Part { int which, planes; } part = {};   // PART (beside `low`: the geometry, and whether it takes the one-wave kernel): ULCX_PART_MID / _SIDE; planes of an output row, ulcx_part_channels
 };
 int ulcx_dec_launch(const UlcxDecCtx &c, hipStream_t st, hipEvent_t *ev, const UlcxDecAux &aux);
 // block index of packed payloads (c.in / payStride / payBytes / inBytes set as for a packed call; no stream state is touched)
@@ -325,10 +327,10 @@ struct UlcxSpliceArgs {
     ulcx_index_entry *outIndex; int outIndexStride; int32_t *outIndexBlocks;
 };
 int ulcx_splice_launch(const UlcxDecCtx &c, const UlcxSpliceArgs &a, hipStream_t st);
-size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS = 0);   // listBS: the BlockSize the per-wave lists are sized by (0: BS)
+size_t ulcx_dec_lds_bytes(int BS, int fast, int twInLds, int listBS = 0, int oneWave = 0);   // listBS: the BlockSize the per-wave lists are sized by (0: BS); oneWave: k_dpart's carve
 size_t ulcx_spec_lds_bytes(int BS);               // k_dspec's / k_ddist's dynamic LDS: two unit arrays where a CU holds them, else one
 int ulcx_spec_arrays(int BS);                     // how many that is (1: ULCX_SPECTRA_LR cannot be formed on chip by k_ddist)
-enum UlcxSynKind { ULCX_SYN_WHOLE, ULCX_SYN_CUT, ULCX_SYN_RANGE, ULCX_SYN_SAMPLES, ULCX_SYN_PLANES, ULCX_SYN_PLANES_LR, ULCX_SYN_LOW };   // the synthesis modes (ulcx_dec.hip: SynWhole .. SynLow)
+enum UlcxSynKind { ULCX_SYN_WHOLE, ULCX_SYN_CUT, ULCX_SYN_RANGE, ULCX_SYN_SAMPLES, ULCX_SYN_PLANES, ULCX_SYN_PLANES_LR, ULCX_SYN_LOW, ULCX_SYN_PART };   // the synthesis modes (ulcx_dec.hip: SynWhole .. SynPart)
 int ulcx_dec_syn_slots(const UlcxDecCtx &c, UlcxSynKind kind, int walkBS = 0);   // resident workgroups of that mode's stereo synthesis kernel on the current device (ULCX_SYN_LOW: walkBS, the walk's BlockSize)
 int ulcx_pack_launch(int nStreams, int nBlocks, int slotBytes, const uint8_t *d_slots, const int32_t *d_bits, uint8_t *d_payload,
                      long long stride, int32_t *d_payloadBytes, int32_t *d_maxBlock, hipStream_t st);

@@ -182,6 +182,16 @@ for _sfx, _view in (("", _STRIDED), ("_ragged", _RAGGED)):    # the sample-crop 
             table=EXT_SIGNATURES, twins=EXT_PCM16_TWIN)
 EXT_EXPORTS = list(EXT_SIGNATURES)
 
+# ---- The third table: mid and side crops (include/ulc_amd_part.h), built and applied as the second.
+PART_SIGNATURES = {}
+PART_PCM16_TWIN = {}
+PART_MID, PART_SIDE = 0, 1
+_sig("ulcx_part_channels", [_int, _int], table=PART_SIGNATURES)
+for _sfx, _view in (("", _STRIDED), ("_ragged", _RAGGED)):    # the low-rate rows with part behind lgD
+    _family(f"ulcx_decode_crops_part{_sfx}_{{}}", [_vp, _int] + _view + _rows(_i64p) + [_int, _int] + _PCM, pcm16=True,
+            table=PART_SIGNATURES, twins=PART_PCM16_TWIN)
+PART_EXPORTS = list(PART_SIGNATURES)
+
 
 def new_index(n_rows, index_stride):
     """An open index as ulcx_index_begin_dev leaves it: entry 0 = (0, 1234567), every other entry (-1, 0)."""
@@ -226,7 +236,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} not built: run `make -C ulc-codec_amd` (or __graft_entry__.build())")
         l = C.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for name, (argtypes, restype) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(PART_SIGNATURES.items()):
             fn = getattr(l, name, None)                    # (an older build named by ULC_AMD_LIB for an A/B run may lack some)
             if fn is not None:
                 fn.argtypes, fn.restype = argtypes, restype
@@ -257,7 +267,7 @@ def _dev_call(name, pcm16, stream, *args):
     """A device form: `name` or, with pcm16, its int16 twin; the stream goes last (0: the null stream).  (Not through _call():
     bench.py's timed loop comes through here, and a second frame per call is all the cost there is to save.)"""
     if pcm16:
-        name = PCM16_TWIN[name] if name in PCM16_TWIN else EXT_PCM16_TWIN[name]
+        name = next(t[name] for t in (PCM16_TWIN, EXT_PCM16_TWIN, PART_PCM16_TWIN) if name in t)
     _check((_bound.get(name) or _bind(name))(*args, stream or None), name)
 
 
@@ -317,6 +327,11 @@ def lowrate_block(block_size, lowrate):
     """BlockSize of the reduced stream of a low-rate crop (ulcx_lowrate_block): block_size >> lowrate for lowrate 0 .. 3 when that is
     a legal BlockSize, else 0."""
     return int(lib().ulcx_lowrate_block(int(block_size), int(lowrate)))
+
+
+def part_channels(n_chan, part):
+    """Planes per row of a mid / side crop (ulcx_part_channels): (n_chan + 1 - part) // 2 for part PART_MID / PART_SIDE, else 0."""
+    return int(lib().ulcx_part_channels(int(n_chan), int(part)))
 
 
 def window_subblocks(block_size, wc):
@@ -920,12 +935,15 @@ class BatchDecoder(_StreamSlots):
         self._corpus_call("decode_crops", ragged, corpus, *rows, n_blocks, _p(pcm, _f32p), _p(bits, _i32p))
         return pcm, bits
 
-    def _crops_samples(self, ragged, corpus, files, start, n_samples, length, lowrate=None):
+    def _crops_samples(self, ragged, corpus, files, start, n_samples, length, lowrate=None, part=None):
         n, rows = _row_view(files, start, np.int64, length)
-        pcm = np.zeros((n, self.C, max(1, n_samples)), np.float32)
+        planes = self.C if part is None else max(1, part_channels(self.C, part))              # (a bad part: the call refuses it)
+        pcm = np.zeros((n, planes, max(1, n_samples)), np.float32)
         bs = self.BS if lowrate is None else (lowrate_block(self.BS, lowrate) or self.BS)     # (a bad ratio: the call refuses it)
         bits = np.zeros((n, max(1, crop_blocks(bs, n_samples))), np.int32)
-        if lowrate is None:
+        if part is not None:
+            self._corpus_call("decode_crops_part", ragged, corpus, *rows, n_samples, int(lowrate or 0), int(part), _p(pcm, _f32p), _p(bits, _i32p))
+        elif lowrate is None:
             self._corpus_call("decode_crops_samples", ragged, corpus, *rows, n_samples, _p(pcm, _f32p), _p(bits, _i32p))
         else:
             self._corpus_call("decode_crops_lowrate", ragged, corpus, *rows, n_samples, int(lowrate), _p(pcm, _f32p), _p(bits, _i32p))
@@ -1155,6 +1173,29 @@ class BatchDecoder(_StreamSlots):
     def decode_crops_lowrate_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, start, n_samples, lowrate, length=None):
         """decode_crops_lowrate() of a ragged corpus, held as for decode_crops_ragged()."""
         return self._crops_samples(True, (payload, payload_offs, index, index_offs, index_blocks), files, start, n_samples, length, lowrate)
+
+    # mid and side crops (include/ulc_amd_part.h): the low-rate calls over one coded channel of every pair - plane j of the output is
+    # coded channel 2 j + part as it stands in front of the un-mix, part_channels(C, part) planes per row
+    def decode_crops_part(self, payload, payload_bytes, index, index_blocks, files, start, n_samples, part, lowrate=0, length=None):
+        """decode_crops_lowrate() of the mid (part = PART_MID) or side (PART_SIDE) channels alone
+        -> (pcm [n][part_channels(C, part)][n_samples], bits as decode_crops_lowrate())."""
+        return self._crops_samples(False, (payload, payload_bytes, index, None, index_blocks), files, start, n_samples, length, lowrate, part)
+
+    def decode_crops_part_dev(self, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride, d_index_blocks, n, d_file, d_start, d_len,
+                              n_samples, lowrate, part, d_pcm, d_bits, stream=0, pcm16=False):
+        """ulcx_decode_crops_part_dev / _dev_pcm16 on raw device pointers (d_len: 0 for none)."""
+        _dev_call("ulcx_decode_crops_part_dev", pcm16, stream, self.h, n_files, d_payload, stride, d_payload_bytes, d_index, index_stride,
+                  d_index_blocks, n, d_file, d_start, d_len or None, n_samples, int(lowrate), int(part), d_pcm, d_bits)
+
+    def decode_crops_part_ragged(self, payload, payload_offs, index, index_offs, index_blocks, files, start, n_samples, part, lowrate=0, length=None):
+        """decode_crops_part() of a ragged corpus, held as for decode_crops_ragged()."""
+        return self._crops_samples(True, (payload, payload_offs, index, index_offs, index_blocks), files, start, n_samples, length, lowrate, part)
+
+    def decode_crops_part_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
+                                     n, d_file, d_start, d_len, n_samples, lowrate, part, d_pcm, d_bits, stream=0, pcm16=False):
+        """ulcx_decode_crops_part_ragged_dev / _dev_pcm16 on raw device pointers (d_len: 0 for none)."""
+        _dev_call("ulcx_decode_crops_part_ragged_dev", pcm16, stream, self.h, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total,
+                  d_index_offs, d_index_blocks, n, d_file, d_start, d_len or None, n_samples, int(lowrate), int(part), d_pcm, d_bits)
 
     def decode_crops_lowrate_ragged_dev(self, n_files, d_payload, payload_total, d_payload_offs, d_index, index_total, d_index_offs, d_index_blocks,
                                         n, d_file, d_start, d_len, n_samples, lowrate, d_pcm, d_bits, stream=0, pcm16=False):
